@@ -11,7 +11,7 @@ VAR_REPS=2 timeout 600 python3 scripts/gpu_variants.py $E/libnanorev_hip_base.so
 for v in stamp0 stampmap; do
   POWER_STAGES=3,4 timeout 300 python3 scripts/gpu_power_stage.py $E/libnanorev_hip_$v.so > $O/power_$v.json 2> $O/power_$v.err
 done
-ARGS="python3 bench.py --steps 8 --warmup 3 --prime 20 --no-cpu-baseline --no-extras --no-prof"
+ARGS="python3 bench.py --full --steps 8 --warmup 3 --prime 20 --no-cpu-baseline --no-extras --no-prof"
 for v in base map1; do
   export NRV_LIB=$PWD/$E/libnanorev_hip_$v.so
   i=0

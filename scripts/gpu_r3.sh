@@ -12,7 +12,7 @@ if [ "$WHAT" = all ] || [ "$WHAT" = bench ]; then
   for i in 1 2; do
     timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/bench_driver_$i.log 2>&1
   done
-  timeout 900 python3 bench.py > $O/bench.log 2>&1; echo "bench rc=$?" >> $O/bench.log
+  timeout 900 python3 bench.py --full > $O/bench.log 2>&1; echo "bench rc=$?" >> $O/bench.log
 fi
 grep -E "passed|failed|error" $O/pytest_gpu.log | tail -3; grep -E "^FAILED|^ERROR" $O/pytest_gpu.log | head -20
 tail -2 $O/smoke.log

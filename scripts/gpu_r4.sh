@@ -23,7 +23,7 @@ for WHAT in "$@"; do
       for i in 1 2; do
         timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/bench_driver_$i.log 2>&1
       done
-      timeout 900 python3 bench.py > $O/bench.log 2>&1; echo "bench rc=$?" >> $O/bench.log
+      timeout 900 python3 bench.py --full > $O/bench.log 2>&1; echo "bench rc=$?" >> $O/bench.log
       for f in $O/bench_driver_*.log; do tail -1 $f | cut -c1-300; done
       tail -2 $O/bench.log | cut -c1-3000 ;;
   esac

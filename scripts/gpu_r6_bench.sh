@@ -6,7 +6,7 @@ TAG=${1:-r06d}; O=gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
 T0=$(date +%s); (free -g; df -h /dev/shm /tmp; nproc; cat /sys/fs/cgroup/cpu.max 2>/dev/null; cat /sys/fs/cgroup/memory.max 2>/dev/null) > $O/box.txt 2>&1
 timeout 1200 python3 -m pytest tests/test_gpu_hostpipe.py tests/test_gpu_range.py "tests/test_gpu_multirank.py::test_two_ranks_sharing_the_device_deliver_the_one_rank_total" -q -x -s > $O/pytest_host.log 2>&1; echo "pytest rc=$?" >> $O/pytest_host.log
-timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench rc=$?"
+timeout 1500 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench rc=$?"
 echo "bench seconds: $(( $(date +%s) - T0 ))"
 if [ "${2:-}" = micro ]; then
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -o /tmp/clock_vs_fill tools/microbench/clock_vs_fill.hip 2>/dev/null && \

@@ -5,7 +5,7 @@
 TAG=${1:-r06g}; O=gpurun_out/$TAG; mkdir -p $O
 for rep in 1 2; do
   for B in 4096 8192 16384; do
-    timeout 600 python3 bench.py --batch $B --steps 40 --warmup 5 --prime 200 --no-extras --no-cpu-baseline --prof-all --blocks 1 2>/dev/null | tail -1 > $O/bench_b${B}_$rep.json
+    timeout 600 python3 bench.py --full --batch $B --steps 40 --warmup 5 --prime 200 --no-extras --no-cpu-baseline --prof-all --blocks 1 2>/dev/null | tail -1 > $O/bench_b${B}_$rep.json
     python3 - $O/bench_b${B}_$rep.json $B <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read()); B = int(sys.argv[2]); k = j["kernel_us"]

@@ -13,7 +13,7 @@ for i in 1 2 3; do
   timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/bench_driver_$i.log 2>&1
 done
 timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --prime 64 --no-extras --no-cpu-baseline > $O/bench_driver_prime64.log 2>&1
-timeout 900 python3 bench.py > $O/bench.log 2>&1; echo "bench rc=$?" >> $O/bench.log
+timeout 900 python3 bench.py --full > $O/bench.log 2>&1; echo "bench rc=$?" >> $O/bench.log
 timeout 300 python3 scripts/gpu_hostapi.py > $O/hostapi.log 2>&1
 NRV_HOST_REGISTER=0 timeout 300 python3 scripts/gpu_hostapi.py > $O/hostapi_noreg.log 2>&1
 tail -3 $O/pytest_gpu.log; tail -2 $O/smoke.log; cat $O/f16_probe.log; tail -5 $O/precision.log | cut -c1-400

@@ -140,3 +140,24 @@ def test_round6_line_helpers():
     # a runtime that reports no identity at all must never make N devices look like one
     z0, z1 = {"pci": "0000:00:00", "uuid": "", "device": 0}, {"pci": "0000:00:00", "uuid": "", "device": 1}
     assert bench.device_key(z0) != bench.device_key(z1)
+
+
+def test_dump_outputs_are_float32_and_a_fixed_sample_beyond_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per output array; past the byte budget every rank keeps the same seeded rows."""
+    import torch
+    n = 1000
+    arrays = {"model1_probs": torch.rand(n, 6), "model2_probs": torch.rand(n, 5),
+              "model1_calls": torch.randint(0, 6, (n,), dtype=torch.int8), "model2_calls": torch.randint(0, 5, (n,), dtype=torch.int8)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays, 1, 0)
+    for k, v in arrays.items():
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, v.numpy().astype(np.float32))
+    assert not (tmp_path / "all" / "sample_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 100 * 2 * (13 * 4 + 8))              # room for 100 rows on each of two ranks
+    for r in (0, 1):
+        bench.dump_outputs(str(tmp_path / "cut"), arrays, 2, r)
+    rows = np.load(tmp_path / "cut" / "sample_rows_rank0.npy")
+    assert len(rows) == 100 and np.array_equal(rows, np.load(tmp_path / "cut" / "sample_rows_rank1.npy"))
+    a = np.load(tmp_path / "cut" / "model1_probs_rank1.npy")
+    assert np.array_equal(a, arrays["model1_probs"].numpy()[rows.astype(np.int64)])
+    assert sum(f.stat().st_size for f in (tmp_path / "cut").iterdir()) < 2 * 100 * (13 * 4 + 8) + 8 * 1024

@@ -9,6 +9,7 @@ import shutil
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import GOLD
@@ -23,7 +24,7 @@ FAST5 = os.path.join(GOLD, "fast5")
 @pytest.mark.parametrize("n", [2, 4, 8])
 def test_bench_n_ranks_share_one_device(n):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--share-device",
-                        "--steps", "6", "--warmup", "2", "--prime", "30", "--no-extras", "--no-cpu-baseline"],
+                        "--steps", "6", "--warmup", "2", "--prime", "30", "--full", "--no-extras", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -51,7 +52,7 @@ def test_two_ranks_sharing_the_device_deliver_the_one_rank_total():
     rank's own ms_per_step sits next to its device identity, and the line carries its five timed blocks."""
     def run(n):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "20", "--warmup", "5", "--prime", "200",
-               "--no-extras", "--no-cpu-baseline"] + (["--share-device"] if n > 1 else [])
+               "--full", "--no-extras", "--no-cpu-baseline"] + (["--share-device"] if n > 1 else [])
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-2000:]
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -68,6 +69,31 @@ def test_two_ranks_sharing_the_device_deliver_the_one_rank_total():
         assert max(x["ms_per_step"] for x in devs) <= j["ms_per_step"] * 1.0001
     print(f"SHARE: 1 rank {one['value']:.3e}, 2 ranks on one device {two['value']:.3e} bases/s (x{ratio:.2f}); "
           f"blocks {one['ms_per_step_blocks']}")
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """A plain run: exactly --steps timed steps, the contract keys and nothing of --full; what the timed path computed in its
+    last step, dumped, agrees with the fp64 oracle (the check a --full run makes before it times anything)."""
+    from nanoreviser_amd import workload as W
+    from nanoreviser_amd.weights import load_species
+    from oracle import nrv_oracle as O
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["steps"] == 7 and j["warmup"] == 2 and j["ms_per_step"] > 0 and j["higher_is_better"] is True
+    assert abs(j["value"] - 4096 * 7 / (j["ms_per_step"] * 7e-3)) < 1e-6 * j["value"]
+    assert j["unit"] == "bases/s" and j["dtype"] and len(j["ms_per_step_blocks"]) == 1
+    assert "roofline" not in j and "cpu_baseline" not in j and "host_inclusive" not in j
+    out = {k: np.load(tmp_path / f"{k}.npy") for k in ("model1_probs", "model2_probs", "model1_calls", "model2_calls")}
+    assert all(a.dtype == np.float32 and len(a) == 4096 for a in out.values())
+    m1, m2 = (m.with_window(13) for m in load_species("ecoli"))
+    sig, rd = W.synth_windows(4096, 13, seed=20260)
+    q1, q2, b1, b2 = O.predict_pair(m1.tensors, m2.tensors, sig[:64], rd[:64], np.float64)
+    assert np.abs(out["model1_probs"][:64] - q1).max() <= 1e-4 and np.abs(out["model2_probs"][:64] - q2).max() <= 1e-4
+    assert np.array_equal(out["model1_calls"][:64], b1) and np.array_equal(out["model2_calls"][:64], b2)
 
 
 def test_bench_refuses_more_ranks_than_devices_without_share_device():
@@ -122,7 +148,7 @@ def test_bench_two_ranks_carry_a_fast5_fed_cli_leg():
     """VERDICT r04 #1a: an N > 1 line must also measure the metric as BASELINE.json words it - fast5 in, revised reads
     out, N GPU workers (NanoReviser.py:203-219) - not only the device-resident weak-scaling loop."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-device", "--steps", "6",
-                        "--warmup", "2", "--prime", "30", "--no-cpu-baseline", "--cli-reps", "60"],
+                        "--warmup", "2", "--prime", "30", "--full", "--no-cpu-baseline", "--cli-reps", "60"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
