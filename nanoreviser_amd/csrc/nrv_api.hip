@@ -486,12 +486,21 @@ struct nrv_handle {
   // workspace (per model)
   int cap_rows = 0;                // padded rows the workspace holds
   float *S[2] = {0, 0}, *X1[2] = {0, 0}, *X2[2] = {0, 0}, *X3[2] = {0, 0}, *MO[2] = {0, 0};
+  size_t act_n[5] = {0, 0, 0, 0, 0};   // floats of each buffer of the activation set above (S, X1, X2, X3, MO; for_groups swaps it)
+  // NRV_POISON=<32-bit hex> (read by nrv_create, per handle): a DEBUG switch.  Every workspace, staging and output buffer the
+  // engine allocates holds this pattern instead of zeros / whatever the allocator left; the activation set of a launch group is
+  // filled again before the group, staging and output buffers before each upload or stage.  A kernel then sees only what an
+  // earlier kernel of its own group (or the upload) wrote, or the pattern.  Untouched: the weights and the range-guard counters.
+  bool poison_on = false;
+  unsigned poison = 0;
+  size_t sig_bytes = 0, feat_bytes = 0;   // capacity of each d_sig / d_feat staging buffer
   // Lanes: a launch group of <= 2048 windows leaves most of the 256 CUs idle (512 windows = 32 workgroups per
   // Bi-LSTM launch), so the device-pointer entry points run consecutive groups on up to kMaxLanes streams,
   // each with its own activation buffers; results do not depend on the grouping.  NRV_LANES=0 turns it off.
   static constexpr int kMaxLanes = 8;
   struct Lane {
     float *S[2] = {0, 0}, *X1[2] = {0, 0}, *X2[2] = {0, 0}, *X3[2] = {0, 0}, *MO[2] = {0, 0};
+    size_t act_n[5] = {0, 0, 0, 0, 0};
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
   } lanes[kMaxLanes];
@@ -574,6 +583,19 @@ namespace {
       return NRV_E_HIP;                                                                  \
     }                                                                                    \
   } while (0)
+
+// NRV_POISON: the handle's pattern into the 32-bit words of [p, p + bytes), on stream s (nothing when the switch is off)
+static int poison_fill(nrv_handle* h, void* p, size_t bytes, hipStream_t s) {
+  if (!h->poison_on || !p || bytes < 4) return NRV_OK;
+  HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)p, (int)h->poison, bytes / 4, s));
+  return NRV_OK;
+}
+// a freshly allocated activation buffer: zeros, or the pattern (synchronous, like the hipMemset it replaces)
+static int alloc_fill(nrv_handle* h, void* p, size_t bytes) {
+  if (h->poison_on) HIPCHK(h, hipMemsetD32((hipDeviceptr_t)p, (int)h->poison, bytes / 4));
+  else HIPCHK(h, hipMemset(p, 0, bytes));
+  return NRV_OK;
+}
 
 // unit halves (16 units each) per wave of the f16x2 kernels of lstm2..4: lstm_h2w_kernel (192 -> 128) and lstm_h2s_kernel (256 -> 64)
 // both give a wave one unit group of 16
@@ -864,6 +886,7 @@ static int ensure_workspace(nrv_handle* h) {
   const int rows = ((stage_windows(h, true) + kRowPad - 1) / kRowPad) * kRowPad;   // staging: the larger (read-mode) stage
   if (rows <= h->cap_rows) return NRV_OK;
   free_workspace(h);
+  int rc;
   // activations: ONE launch group (a stage's groups run one after the other on these, or on the lanes' own sets)
   const size_t tiles = (size_t)(((group_windows(h) + kRowPad - 1) / kRowPad) * kRowPad) / 32;
   // event-major S needs (rows + T + 32) events; window-major S needs rows*T "events"
@@ -875,20 +898,25 @@ static int ensure_workspace(nrv_handle* h) {
     HIPCHK(h, hipMalloc(&h->X2[m], n2 * 4));
     HIPCHK(h, hipMalloc(&h->X3[m], n3 * 4));
     HIPCHK(h, hipMalloc(&h->MO[m], tiles * T * 256 * 4));
-    HIPCHK(h, hipMemset(h->MO[m], 0, tiles * T * 256 * 4));
-    HIPCHK(h, hipMemset(h->S[m], 0, nS * 4));
-    HIPCHK(h, hipMemset(h->X1[m], 0, n1 * 4));
-    HIPCHK(h, hipMemset(h->X2[m], 0, n2 * 4));
-    HIPCHK(h, hipMemset(h->X3[m], 0, n3 * 4));
+    const size_t nm = tiles * T * 256;
+    if ((rc = alloc_fill(h, h->MO[m], nm * 4)) || (rc = alloc_fill(h, h->S[m], nS * 4)) || (rc = alloc_fill(h, h->X1[m], n1 * 4)) ||
+        (rc = alloc_fill(h, h->X2[m], n2 * 4)) || (rc = alloc_fill(h, h->X3[m], n3 * 4)))
+      return rc;
+    if (m == 0) { h->act_n[0] = nS; h->act_n[1] = n1; h->act_n[2] = n2; h->act_n[3] = n3; h->act_n[4] = nm; }
   }
+  h->sig_bytes = (size_t)rows * T * kSig * 4 + 4096;
+  h->feat_bytes = (size_t)rows * T * kFeat * 4 + 4096;
   for (int st = 0; st < nrv_handle::kIn; ++st) {
-    HIPCHK(h, hipMalloc(&h->d_sig[st], (size_t)rows * T * kSig * 4 + 4096));
-    HIPCHK(h, hipMalloc(&h->d_feat[st], (size_t)rows * T * kFeat * 4 + 4096));
+    HIPCHK(h, hipMalloc(&h->d_sig[st], h->sig_bytes));
+    HIPCHK(h, hipMalloc(&h->d_feat[st], h->feat_bytes));
+    if ((rc = poison_fill(h, h->d_sig[st], h->sig_bytes, nullptr)) || (rc = poison_fill(h, h->d_feat[st], h->feat_bytes, nullptr)))
+      return rc;
   }
   for (int st = 0; st < 2; ++st) {
     const size_t ob = (size_t)rows * kOutBytes;              // rows is a multiple of kRowPad: the counter behind it is aligned
     HIPCHK(h, hipMalloc((void**)&h->d_out[st], ob + 64));
     HIPCHK(h, hipMemset(h->d_out[st], 0, ob + 64));
+    if ((rc = poison_fill(h, h->d_out[st] + 64, ob, nullptr))) return rc;     // not the counter
     HIPCHK(h, hipHostMalloc((void**)&h->pin_out[st], ob + 64, hipHostMallocDefault));
     memset(h->pin_out[st], 0, ob + 64);
     // [range-guard counter, 64 B][p1 r x 6 f32 | p2 r x 5 f32 | a1 r | a2 r], r = the STAGE's rows padded to kRowPad: the
@@ -902,6 +930,8 @@ static int ensure_workspace(nrv_handle* h) {
     h->pin_sat[st] = (unsigned*)h->pin_out[st];
     h->sat_seen[st] = 0;
   }
+  // the pattern fills above went to the null stream; the copy streams, which fill staging next, are not ordered behind it
+  if (h->poison_on) HIPCHK(h, hipDeviceSynchronize());
   h->cap_rows = rows;
   return NRV_OK;
 }
@@ -939,7 +969,9 @@ static int ensure_lanes(nrv_handle* h) {
       const size_t sz[5] = {nS, n1, n2, n3, nm};
       for (int i = 0; i < 5; ++i) {
         HIPCHK(h, hipMalloc(bufs[i], sz[i] * 4));
-        HIPCHK(h, hipMemset(*bufs[i], 0, sz[i] * 4));
+        const int rc = alloc_fill(h, *bufs[i], sz[i] * 4);
+        if (rc) return rc;
+        L.act_n[i] = sz[i];
       }
     }
   }
@@ -1055,6 +1087,15 @@ static int run_group(nrv_handle* h, const float* d_sig, const float* d_feat, int
                      float* d_p1, float* d_p2, int8_t* d_a1, int8_t* d_a2, unsigned* sat) {
   const int T = h->T;
   const int tiles = (n + 31) / 32;
+  if (h->poison_on) {                // NRV_POISON: this group's activation set holds nothing but the pattern
+    for (int m = 0; m < 2; ++m) {
+      float* const bufs[5] = {h->S[m], h->X1[m], h->X2[m], h->X3[m], h->MO[m]};
+      for (int i = 0; i < 5; ++i) {
+        const int rc0 = poison_fill(h, bufs[i], h->act_n[i] * 4, h->stream);
+        if (rc0) return rc0;
+      }
+    }
+  }
   hipEvent_t* ev = nullptr;
   // prof 3: only every 8th group is bracketed (an event record costs ~6 us of idle pipe)
   if (h->prof && (h->prof != 3 || (h->prof_tick++ & 7) == 0)) {
@@ -1326,6 +1367,7 @@ int nrv_create(const nrv_weights* m1, const nrv_weights* m2, int T, int device, 
   if (const char* e2 = getenv("NRV_HOST_REGISTER")) h->host_register = atoi(e2) != 0;
   if (const char* e3 = getenv("NRV_LANES")) h->lanes_on = atoi(e3) != 0;
   if (const char* e4 = getenv("NRV_COALESCE")) h->coalesce = atoi(e4) != 0;
+  if (const char* e5 = getenv("NRV_POISON"); e5 && *e5) { h->poison_on = true; h->poison = (unsigned)strtoul(e5, nullptr, 16); }
   ok = ok && hipMalloc((void**)&h->d_sat, 4 * sizeof(unsigned)) == hipSuccess &&
        hipMemset(h->d_sat, 0, 4 * sizeof(unsigned)) == hipSuccess;
   if (!ok) { g_create_error = "nrv_create: could not create the copy stream / events / counters"; nrv_destroy(h); return NRV_E_HIP; }
@@ -1427,8 +1469,11 @@ static int for_groups(nrv_handle* h, int64_t n, F&& body) {
   hipStream_t main = h->stream;
   float* keep[5][2];
   for (int m = 0; m < 2; ++m) { keep[0][m] = h->S[m]; keep[1][m] = h->X1[m]; keep[2][m] = h->X2[m]; keep[3][m] = h->X3[m]; keep[4][m] = h->MO[m]; }
+  size_t keep_n[5];
+  memcpy(keep_n, h->act_n, sizeof keep_n);
   auto restore = [&]() {
     for (int m = 0; m < 2; ++m) { h->S[m] = keep[0][m]; h->X1[m] = keep[1][m]; h->X2[m] = keep[2][m]; h->X3[m] = keep[3][m]; h->MO[m] = keep[4][m]; }
+    memcpy(h->act_n, keep_n, sizeof keep_n);
     h->stream = main;
   };
   if (nl) {
@@ -1442,6 +1487,7 @@ static int for_groups(nrv_handle* h, int64_t n, F&& body) {
     if (nl) {
       const nrv_handle::Lane& L = h->lanes[g % nl];
       for (int m = 0; m < 2; ++m) { h->S[m] = L.S[m]; h->X1[m] = L.X1[m]; h->X2[m] = L.X2[m]; h->X3[m] = L.X3[m]; h->MO[m] = L.MO[m]; }
+      memcpy(h->act_n, L.act_n, sizeof L.act_n);
       h->stream = L.stream;
     }
     rc = body(s, nb);
@@ -1523,6 +1569,9 @@ static int upload_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, const in
   if (!h->ev_raw) HIPCHK(h, hipEventCreateWithFlags(&h->ev_raw, hipEventDisableTiming));
   // the previous call's kernels may still read these buffers only if the caller did not sync; the
   // host entry points always end synchronised, so plain stream order on the copy stream is enough
+  if ((rc = poison_fill(h, h->d_raw, h->cap_raw, h->copy_stream)) || (rc = poison_fill(h, h->d_starts, h->cap_starts, h->copy_stream)) ||
+      (rc = poison_fill(h, h->d_reads, h->cap_reads, h->copy_stream)))
+    return rc;
   if (n_raw) HIPCHK(h, hipMemcpyAsync(h->d_raw, raw, (size_t)n_raw * 2, hipMemcpyHostToDevice, h->copy_stream));
   if (N) HIPCHK(h, hipMemcpyAsync(h->d_starts, starts, (size_t)N * 4, hipMemcpyHostToDevice, h->copy_stream));
   if (n_reads) HIPCHK(h, hipMemcpyAsync(h->d_reads, reads, (size_t)n_reads * sizeof(SegRead), hipMemcpyHostToDevice, h->copy_stream));
@@ -1643,6 +1692,8 @@ static int predict_host(nrv_handle* h, const float* sig, const float* feat, int6
   auto run_stage = [&](int nb, int si, int st) -> int {
     const size_t r = block_rows(nb);
     char* const d = h->d_out[st] + 64;
+    const int rc0 = poison_fill(h, d, (size_t)h->cap_rows * kOutBytes, h->stream);   // NRV_POISON: the outputs, not the counter
+    if (rc0) return rc0;
     return for_groups(h, nb, [&](int64_t w, int nw) {
       return run_group(h, h->d_sig[si] + (read_mode ? w * kSig : w * T * kSig),
                        h->d_feat[si] + (read_mode ? w * kFeat : w * T * kFeat), nw, read_mode,
@@ -1681,6 +1732,10 @@ static int predict_host(nrv_handle* h, const float* sig, const float* feat, int6
   auto upload = [&](int64_t s, int si, int want) -> int {
     const int nb = (int)((n - s < want) ? (n - s) : want);
     const size_t ev = read_mode ? (size_t)(nb + T - 1) : (size_t)nb * T;
+    // NRV_POISON: the whole input set, ahead of the copies (raw reads: d_sig is cut by segment_kernel after ev_in)
+    int rc0;
+    if ((rc0 = poison_fill(h, h->d_sig[si], h->sig_bytes, h->copy_stream)) || (rc0 = poison_fill(h, h->d_feat[si], h->feat_bytes, h->copy_stream)))
+      return rc0;
     if (!raw_reads) {
       const float* hs = sig + (read_mode ? s * kSig : s * T * kSig);
       const void* src = hs;
@@ -1787,6 +1842,8 @@ static int raw_enqueue(nrv_handle* h, nrv_handle::RawSlot& sl) {
   const float* d_feat = (const float*)(sl.d_in + sl.off_feat);
   for (int64_t s = 0; s < sl.n; s += stage) {
     const int nb = (int)((sl.n - s < stage) ? (sl.n - s) : stage);
+    const int rc0 = poison_fill(h, h->d_sig[0], h->sig_bytes, h->stream);
+    if (rc0) return rc0;
     launch_segment(h, sl.n_reads, s, nb + T - 1, h->d_sig[0], (const int16_t*)sl.d_in, (const int32_t*)(sl.d_in + sl.off_starts),
                    (const SegRead*)(sl.d_in + sl.off_reads));
     const int rc = for_groups(h, nb, [&](int64_t w, int nw) {
@@ -1849,6 +1906,11 @@ int nrv_reads_raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const 
   }
   if ((rc = ensure_workspace(h))) return rc;
   // inputs -> page-locked staging (a host copy of 92 B per base that overlaps the previous call's kernels) -> ONE upload
+  if (h->poison_on) {          // NRV_POISON: the slot's buffers (the alignment gaps between the input parts included), not the counter
+    for (size_t i = 0; i + 4 <= in_bytes; i += 4) memcpy(sl.pin_in + i, &h->poison, 4);
+    if ((rc = poison_fill(h, sl.d_in, sl.cap_in, h->copy_stream)) || (rc = poison_fill(h, sl.d_out + 64, sl.cap_out - 64, h->stream)))
+      return rc;
+  }
   memcpy(sl.pin_in, raw, (size_t)n_raw * 2);
   memcpy(sl.pin_in + sl.off_starts, starts, (size_t)N * 4);
   memcpy(sl.pin_in + sl.off_reads, reads, (size_t)n_reads * sizeof(SegRead));
@@ -1881,6 +1943,7 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
     // f16x2 range guard: some stage of this call left the f16 range.  Its inputs are still in the slot: the whole call
     // again on the f32 kernels, which have no range limit (behind whatever the other slot has enqueued meanwhile).
     const int h2 = h->h2, split = h->split;
+    if ((rc = poison_fill(h, sl.d_out + 64, sl.cap_out - 64, h->stream))) return rc;
     h->h2 = 0; h->split = 0;
     const int rc2 = raw_enqueue(h, sl);
     h->h2 = h2; h->split = split;
@@ -1925,6 +1988,7 @@ int nrv_segment_reads(nrv_handle* h, const int16_t* raw, int64_t n_raw, const in
   const int64_t chunk = (int64_t)h->cap_rows * h->T;        // events the staging buffer holds
   for (int64_t e0 = 0; e0 < N; e0 += chunk) {
     const int ne = (int)((N - e0 < chunk) ? (N - e0) : chunk);
+    if ((rc = poison_fill(h, h->d_sig[0], h->sig_bytes, h->stream))) return rc;
     launch_segment(h, n_reads, e0, ne, h->d_sig[0]);
     HIPCHK(h, hipMemcpyAsync(sig_ev + e0 * kSig, h->d_sig[0], (size_t)ne * kSig * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));

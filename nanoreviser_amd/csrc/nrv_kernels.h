@@ -39,7 +39,9 @@
 //   NRV_DEV_FAST (-> NRV_ACT1)            DEVELOPMENT ONLY: f16x2 mode with hard_sigmoid only, half the compile time (tools/lstm_exp.sh)
 //   NRV_L3_WS_NBG                         the 192->128 layer's weight ring (4; 8 spills: r04w) - bench.KERNEL_SIGNATURE follows it
 // Run-time environment variables of the engine: NRV_COALESCE / NRV_LANES (round 3's stream lanes instead of coalesced 4096-window
-// groups: tests/test_gpu_parity.py grouping tests), NRV_READ_STAGE, NRV_WINDOW_STAGE_MAX, NRV_HOST_REGISTER, NRV_HOST_TRACE.
+// groups: tests/test_gpu_parity.py grouping tests), NRV_READ_STAGE, NRV_WINDOW_STAGE_MAX, NRV_HOST_REGISTER, NRV_HOST_TRACE,
+// NRV_POISON=<32-bit hex> (DEBUG ONLY, per handle: workspace, staging and outputs hold that pattern instead of what an earlier
+// group or call left - tests/test_gpu_poison.py; unset, nothing changes).
 #pragma once
 #include "nrv_common.h"        // vector types, buffer loads, activations, ActView
 #include "nrv_cnn.h"           // cnn_kernel
