@@ -106,6 +106,36 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket);
 int nrv_segment_reads(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts, int64_t N,
                       const nrv_read_desc* reads, int n_reads, float* sig_ev);
 
+/* Raw reads whose STATISTICS are computed on the device as well (opt-in; nothing above changes): the read's shift / scale
+ * (median and median absolute deviation of its samples, preprocessing.py:100-101) and, per base, the mean and standard
+ * deviation of its samples (preprocessing.py:134-137) that feature columns 1 and 2 are made of
+ * (mean / shift, std / scale; nanorevtrainutils.py:162-169).  The arguments of nrv_reads_raw_begin, plus per read
+ *   last_dur [n_reads]   samples of the read's LAST base (3 or 5 in the reference, preprocessing.py:112-116); base e covers
+ *                        [starts[e], starts[e+1]), the last one [starts[e], starts[e] + last_dur), clipped to raw_len;
+ *   on_device [n_reads]  non-zero: reads[r].shift / .scale and columns 1 - 2 of the read's feat_ev rows are IGNORED and produced
+ *                        on the device ahead of the call's first segmentation stage (the read needs 1 .. 2^32 - 1 samples);
+ *                        zero: the read is used as given, exactly as by nrv_reads_raw_begin.
+ * The numbers are the host stage's bit for bit (integer histograms; f64 sums in NumPy's pairwise order, no contraction; one
+ * correctly rounded division each), so p1 / p2 / a1 / a2 are those of nrv_predict_reads_raw fed by the host stage, in every
+ * precision mode.  One thread works through one base: callers keep reads with a base of more than 16 384 samples on the
+ * host (libnanorev_host.so's loader does) - a cap on work, the results are right for any length.
+ * nrv_reads_raw_end collects the call; tickets, the two-calls-in-flight rule and the range-guard re-run are those of
+ * nrv_reads_raw_begin.  nrv_predict_reads_raw_stats IS _stats_begin + _end. */
+int nrv_reads_raw_stats_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                              const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                              const int32_t* last_dur, const uint8_t* on_device,
+                              float* p1, float* p2, int8_t* a1, int8_t* a2, int* ticket);
+int nrv_predict_reads_raw_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                const int32_t* last_dur, const uint8_t* on_device,
+                                float* p1, float* p2, int8_t* a1, int8_t* a2);
+/* The statistics alone, to HOST memory, by the kernels nrv_reads_raw_stats_begin runs (every read as if on_device; the shift /
+ * scale of `reads` are ignored): shift, scale [n_reads]; mean, std [N] f64 (NaN for a base without samples);
+ * feat12 [N][2] f32 = feature columns 1 and 2.  The twin of nrv_segment_reads, used by the parity tests. */
+int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts, int64_t N,
+                   const nrv_read_desc* reads, int n_reads, const int32_t* last_dur, double* shift, double* scale,
+                   double* mean, double* std, float* feat12);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

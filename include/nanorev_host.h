@@ -78,6 +78,22 @@ int nrvh_load_bundle(const char* const* paths, int n, const char* group, const c
                      nrvh_bundle* out);
 void nrvh_free_bundle(nrvh_bundle* b);
 
+/* The same two loaders for callers that leave the read statistics to the DEVICE (nrv_reads_raw_stats_begin, include/nanorev.h).
+ * flags & NRVH_DEVICE_STATS: the median / MAD pass, the per-base mean / std pass and feature columns 1 - 2 are SKIPPED:
+ * shift = scale = 0 and the two columns are 0 in what comes back, *device_stats (device_stats[i]) = 1.  A read with a base of
+ * more than NRVH_DEVICE_STATS_MAX_BASE samples is declined: it comes back complete, as from nrvh_load_fast5, with the flag 0
+ * (one GPU thread walks one base; a stalled pore must not hand it a million samples).  Everything else - status codes, raw,
+ * starts, bases, columns 0, 3, 4, 5, the Fastq record - is what the plain loaders give.  flags = 0: the plain loaders.
+ *   last_dur       samples of the read's last base (3 or 5), which the device needs for that base's statistics;
+ *   bundle form    last_dur [n], device_stats [n] are the CALLER's arrays, one entry per file (0 where status != NRVH_OK).
+ * Any of the three out-pointers may be NULL. */
+#define NRVH_DEVICE_STATS 1
+#define NRVH_DEVICE_STATS_MAX_BASE 16384
+int nrvh_load_fast5_ex(const char* path, const char* group, const char* subgroup, int want_fastq, int flags, nrvh_read* out,
+                       int32_t* last_dur, int32_t* device_stats, char* err, int err_len);
+int nrvh_load_bundle_ex(const char* const* paths, int n, const char* group, const char* subgroup, int want_fastq, int flags,
+                        nrvh_bundle* out, int32_t* last_dur, uint8_t* device_stats);
+
 /* The calls of one read -> the revised read -> its output file: the merge of nanorevutils/output_handeler.py:83, 104-122
  * (decode as SURVEY.md 8a a16: model1 class = label, model2 class k = label k + 1; window i revises base
  * i + (T - 1) / 2), the record of output_handeler.py:26-62 byte for byte, written to a temporary and renamed to dst.
@@ -94,7 +110,7 @@ int nrvh_finish_bundle(const char* bases, const int64_t* ev_len, int n_reads, co
                        int64_t n_win_total, int T, const uint8_t* qc, const char* const* names, const char* const* dsts,
                        int fastq, int64_t* n_written, int32_t* status);
 
-/* ABI version of this header (2). */
+/* ABI version of this header (3: nrvh_load_fast5_ex / nrvh_load_bundle_ex). */
 int nrvh_abi_version(void);
 
 #ifdef __cplusplus

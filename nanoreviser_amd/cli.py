@@ -88,7 +88,16 @@ def get_args(argv: Optional[Sequence[str]] = None):
                    help="with more than one GPU: a fast5 file above this many MB (~10 MB per 100 k events) AND above a GPU "
                         "worker's fair share of the input has its window range split over the workers, T-1 events of halo "
                         "per slice (0 = never)")
+    p.add_argument("--device_stats", action="store_true", default=False,
+                   help="compute the read statistics (median / MAD of a read, per-base mean / std, feature columns 1 - 2) on the "
+                        "GPU instead of in the host stage: a third less host work per read, the same output byte for byte "
+                        "(also NRV_DEVICE_STATS=1).  Off by default.  Applies to the pipelined native-bundle path; these stay "
+                        "host-fed: the Python fallback reader (libnanorev_host.so not built, or a file it declines), "
+                        "NRV_CLI_PIPELINE=0, several engines per device (NRV_CLI_ENGINES), reads whose window range is split "
+                        "over GPU workers (a slice needs the whole read's median), and any read with a base of more than "
+                        "16384 samples")
     a = p.parse_args(argv)
+    a.device_stats = bool(a.device_stats) or device_stats_env()
     if a.virsion:
         print(f"The virsion of NanoReviser : {VERSION} ")
         raise SystemExit(0)
@@ -96,6 +105,11 @@ def get_args(argv: Optional[Sequence[str]] = None):
         p.print_help()
         raise SystemExit(0)
     return a
+
+
+def device_stats_env() -> bool:
+    """NRV_DEVICE_STATS=1 (anything but empty / 0): the environment form of --device_stats."""
+    return os.environ.get("NRV_DEVICE_STATS", "0").strip() not in ("", "0")
 
 
 def model_paths(args):
@@ -256,14 +270,30 @@ class _LightRead:
         self.bases, self.n_ev = bases, n_ev
 
 
-def _load_bundle(jobs):
+def _load_bundle(jobs, device_stats: bool = False):
     """Worker-process side of the host stage for SEVERAL files: every read through `_load_one`, and the raw reads
     among them concatenated here into the arrays of ONE device call (samples, event starts, event features, one row
     of (raw_len, ev_len, shift, scale) per read), so that the main process neither unpickles thousands of small
     arrays nor concatenates them: a bundle is four big arrays.  Returns (entries, bundle): entries are
     `_load_one`'s tuples, with the tensors of bundled reads replaced by a `_LightRead`; bundle is None when no read
-    qualified."""
+    qualified.  device_stats (--device_stats): the native loader leaves the read statistics to the device; the bundle then
+    carries `last_dur` and `device_stats` per read, and shift / scale / feature columns 1 - 2 of the flagged reads are zeros."""
     t0 = time.perf_counter()
+    if device_stats:
+        nb = hostlib.load_bundle([j[0] for j in jobs], jobs[0][2], jobs[0][3], want_fastq=(jobs[0][4] if len(jobs[0]) > 4 else True),
+                                 device_stats=True) if jobs and all(j[2:] == jobs[0][2:] for j in jobs) else None
+        if nb is None or int((nb["status"] == hostlib.OK).sum()) == 0 or not bool((nb["status"] == hostlib.OK).all()):
+            return _load_bundle(jobs)                 # no library, or a file for the Python reader among them: host-fed as ever
+        good = list(range(len(jobs)))
+        dt = (time.perf_counter() - t0) / len(jobs)
+        entries, eo = [], 0
+        for i, j in enumerate(jobs):
+            el = int(nb["meta"][i, 1])
+            entries.append((j[1], _LightRead(nb["bases"][eo:eo + el], el), nb["fastq"][i], None, dt))
+            eo += el
+        return entries, {"idx": good, "raw": nb["raw"], "starts": nb["starts"], "feat": nb["feat"],
+                         "meta": np.ascontiguousarray(nb["meta"]), "bases": nb["bases"],
+                         "last_dur": np.ascontiguousarray(nb["last_dur"]), "device_stats": np.ascontiguousarray(nb["device_stats"])}
     nb = hostlib.load_bundle([j[0] for j in jobs], jobs[0][2], jobs[0][3], want_fastq=(jobs[0][4] if len(jobs[0]) > 4 else True)) \
         if jobs and all(j[2:] == jobs[0][2:] for j in jobs) else None
     if nb is not None and int((nb["status"] == hostlib.OK).sum()) > 0:
@@ -323,8 +353,28 @@ def _bundle_of(loaded):
     return [tuple(e) for e in entries], bundle
 
 
+def _bundle_host_stats(bundle):
+    """A --device_stats bundle with the statistics of its flagged reads computed HERE (hoststage is the definition): what the
+    plain loader would have delivered.  For the paths that feed a read from the host after all - an engine without the new
+    calls, the per-read retries after a failed batched call."""
+    if bundle is None or "device_stats" not in bundle:
+        return bundle
+    feat, meta = np.array(bundle["feat"], np.float32), np.array(bundle["meta"], np.float64)
+    ro = eo = 0
+    for r, (rl, el) in enumerate(meta[:, :2].astype(np.int64)):
+        if bundle["device_stats"][r]:
+            meta[r, 2], meta[r, 3], feat[eo:eo + el, 1], feat[eo:eo + el, 2] = hs.stats_columns(
+                bundle["raw"][ro:ro + rl], bundle["starts"][eo:eo + el], int(bundle["last_dur"][r]))
+        ro += rl
+        eo += el
+    out = {k: v for k, v in bundle.items() if k not in ("device_stats", "last_dur")}
+    out["feat"], out["meta"] = feat, meta
+    return out
+
+
 def _bundle_reads(bundle):
     """The reads of a bundle as RawReadTensors VIEWS (per-read retries after a failed batched call)."""
+    bundle = _bundle_host_stats(bundle)
     out, ro, eo = [], 0, 0
     for rl, el, sh, sc in bundle["meta"]:
         rl, el = int(rl), int(el)
@@ -548,7 +598,8 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
         from collections import deque
         pend = deque()
         for k in range(0, len(jobs), per_task):
-            pend.append(pool.submit(_load_bundle, jobs[k:k + per_task]))
+            pend.append(pool.submit(_load_bundle, jobs[k:k + per_task], True) if device_stats
+                        else pool.submit(_load_bundle, jobs[k:k + per_task]))
             if k == 0:
                 mark("first task submitted (workers started)")
             if len(pend) >= 3 * nworkers:
@@ -648,6 +699,12 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
     # engine thread enqueues bundle k+1 (nrv_reads_raw_begin: inputs copied, every stage enqueued) BEFORE it collects bundle k
     # (nrv_reads_raw_end), so the device never waits for a call's fill, drain or the Python between two calls.
     pipelined = n_eng == 1 and os.environ.get("NRV_CLI_PIPELINE", "1") != "0"
+    # --device_stats / NRV_DEVICE_STATS=1: the native loader skips the read statistics and the pipelined call computes them
+    # (nrv_reads_raw_stats_begin).  Only on this path - one engine, pipelined, native bundles from the thread pool; every
+    # other path is fed by the host as before.
+    device_stats = bool(getattr(args, "device_stats", False)) and pipelined and native_threads and pool is not None
+    if device_stats:
+        stats["read_stats"] = "device"
     pending = {}                                      # id(engine) -> the call in flight on it: (ticket, batch, bundle, trace index, t0)
 
     def _done():
@@ -793,8 +850,12 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
             rv = box["rv"]
             packed = None
             try:
+                if bundle is not None and "device_stats" in bundle and not (hasattr(rv, "run_packed_raw") and hasattr(rv, "with_device_stats")):
+                    bundle = _bundle_host_stats(bundle)   # an engine without the new calls: the host computes them after all
                 if bundle is not None and hasattr(rv, "run_packed_raw"):
                     packed = type(rv).pack_bundle(bundle["raw"], bundle["starts"], bundle["feat"], bundle["meta"], rv.T)
+                    if "device_stats" in bundle:
+                        packed = type(rv).with_device_stats(packed, bundle["last_dur"], bundle["device_stats"])
                 elif bundle is None and len(batch) > 1:
                     packed = prepare_many(type(rv), [rt for _, rt, _ in batch], rv.T)
             except Exception:

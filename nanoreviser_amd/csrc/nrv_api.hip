@@ -542,6 +542,8 @@ struct nrv_handle {
     char* d_in = nullptr; char* pin_in = nullptr; size_t cap_in = 0;     // [raw i16 | starts i32 | reads | feat f32], 256-B aligned parts
     char* d_out = nullptr; char* pin_out = nullptr; size_t cap_out = 0;   // [counter 64 B | p1 | p2 | a1 | a2]
     size_t off_starts = 0, off_reads = 0, off_feat = 0, rows = 0;
+    size_t off_aux = 0;                                                   // nrv_reads_raw_stats_begin: [.. | StatAux per read] behind feat
+    unsigned* d_stat = nullptr; size_t cap_stat = 0;                      // ... and its scratch (min / max, histograms: nrv_stats.h)
     int64_t N = 0, n = 0;
     int n_reads = 0;
     float *p1 = nullptr, *p2 = nullptr;
@@ -1403,6 +1405,7 @@ void nrv_destroy(nrv_handle* h) {
   (void)hipFree(h->d_raw); (void)hipFree(h->d_starts); (void)hipFree(h->d_reads);
   for (auto& sl : h->raw_slot) {
     (void)hipFree(sl.d_in); (void)hipFree(sl.d_out); (void)hipHostFree(sl.pin_in); (void)hipHostFree(sl.pin_out);
+    (void)hipFree(sl.d_stat);
     if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
     if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
     if (sl.ev_out) (void)hipEventDestroy(sl.ev_out);
@@ -1856,13 +1859,51 @@ static int raw_enqueue(nrv_handle* h, nrv_handle::RawSlot& sl) {
   return NRV_OK;
 }
 
-int nrv_reads_raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
-                        const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
-                        float* p1, float* p2, int8_t* a1, int8_t* a2, int* ticket) {
+// Read statistics on the device (nrv_stats.h) for the reads whose aux says so: shift / scale into d_reads, feature columns
+// 1 and 2 into d_feat (or mean / std / both).  The scratch is zeroed HERE, on the compute stream; max_len = the longest such read.
+static int stats_enqueue(nrv_handle* h, const int16_t* d_raw, const int32_t* d_starts, SegRead* d_reads, const StatAux* d_aux,
+                         unsigned* d_scratch, int n_reads, int64_t N, int64_t max_len, float* d_feat, double* d_mean, double* d_std) {
+  if (n_reads <= 0 || max_len <= 0) return NRV_OK;
+  HIPCHK(h, hipMemsetAsync(d_scratch, 0, (size_t)n_reads * kStatWords * 4, h->stream));
+  const StatArgs a{(const short*)d_raw, d_reads, d_aux, d_scratch, n_reads};
+  const dim3 grid((unsigned)((max_len + kStatChunk - 1) / kStatChunk), (unsigned)n_reads);
+  hipLaunchKernelGGL(stats_minmax_kernel, grid, dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(stats_hist_kernel<0>, grid, dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(stats_scan_kernel<0>, dim3((unsigned)n_reads), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(stats_hist_kernel<1>, grid, dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(stats_scan_kernel<1>, dim3((unsigned)n_reads), dim3(256), 0, h->stream, a);
+  if (N > 0) {
+    const EvStatArgs e{(const short*)d_raw, (const int*)d_starts, d_reads, d_aux, n_reads, (long long)N, d_feat, d_mean, d_std};
+    hipLaunchKernelGGL(event_stats_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, e);
+  }
+  HIPCHK(h, hipGetLastError());
+  return NRV_OK;
+}
+// the reads of a call that take their statistics from the device: each needs 1 .. 2^32 - 1 samples (32-bit counters; the host's
+// median_mad_i16 declines the same).  Returns the longest of them (0: none) or -1.
+static int64_t stats_check(nrv_handle* h, const nrv_read_desc* reads, int n_reads, const int32_t* last_dur, const uint8_t* on_device) {
+  if (n_reads > 0 && (!last_dur || !on_device)) { h->err = "nrv read statistics: null last_dur / flags"; return -1; }
+  int64_t max_len = 0;
+  for (int r = 0; r < n_reads; ++r) {
+    if (!on_device[r]) continue;
+    if (reads[r].raw_len < 1 || reads[r].raw_len >= ((int64_t)1 << 32)) { h->err = "nrv read statistics: a read without samples (or with 2^32 or more)"; return -1; }
+    max_len = reads[r].raw_len > max_len ? reads[r].raw_len : max_len;
+  }
+  return max_len;
+}
+
+// nrv_reads_raw_begin (last_dur == nullptr: today's call, to the byte) and nrv_reads_raw_stats_begin
+static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                     const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                     const int32_t* last_dur, const uint8_t* on_device,
+                     float* p1, float* p2, int8_t* a1, int8_t* a2, int* ticket) {
   int rc = check_handle(h);
   if (rc) return rc;
   if (!ticket) { h->err = "nrv_reads_raw_begin: null ticket"; return NRV_E_INVALID; }
   if ((rc = raw_check(h, raw, n_raw, starts, feat_ev, N, reads, n_reads))) return rc;
+  const bool with_stats = last_dur != nullptr || on_device != nullptr;
+  const int64_t stat_len = with_stats ? stats_check(h, reads, n_reads, last_dur, on_device) : 0;
+  if (stat_len < 0) return NRV_E_INVALID;
   int k = -1;
   for (int i = 0; i < 2; ++i) if (!h->raw_slot[i].busy) { k = i; break; }
   if (k < 0) { h->err = "nrv_reads_raw_begin: two calls are in flight already (collect one with nrv_reads_raw_end)"; return NRV_E_INVALID; }
@@ -1877,7 +1918,8 @@ int nrv_reads_raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const 
   sl.off_starts = up((size_t)n_raw * 2);
   sl.off_reads = sl.off_starts + up((size_t)N * 4);
   sl.off_feat = sl.off_reads + up((size_t)n_reads * sizeof(SegRead));
-  const size_t in_bytes = sl.off_feat + up((size_t)N * kFeat * 4);
+  sl.off_aux = sl.off_feat + up((size_t)N * kFeat * 4);
+  const size_t in_bytes = sl.off_aux + (with_stats ? up((size_t)n_reads * sizeof(StatAux)) : 0);
   sl.rows = ((size_t)sl.n + kRowPad - 1) / kRowPad * kRowPad;
   const size_t out_bytes = 64 + sl.rows * kOutBytes;
   if (!sl.ev_in) {
@@ -1904,7 +1946,15 @@ int nrv_reads_raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const 
     sl.cap_out = c;
     sl.sat_seen = 0;
   }
+  const size_t stat_bytes = stat_len > 0 ? (size_t)n_reads * kStatWords * 4 : 0;
+  if (stat_bytes > sl.cap_stat) {
+    (void)hipFree(sl.d_stat);
+    sl.d_stat = nullptr; sl.cap_stat = 0;
+    HIPCHK(h, hipMalloc((void**)&sl.d_stat, stat_bytes));
+    sl.cap_stat = stat_bytes;
+  }
   if ((rc = ensure_workspace(h))) return rc;
+  if (stat_bytes && (rc = poison_fill(h, sl.d_stat, sl.cap_stat, h->stream))) return rc;   // NRV_POISON: stats_enqueue zeroes what it uses
   // inputs -> page-locked staging (a host copy of 92 B per base that overlaps the previous call's kernels) -> ONE upload
   if (h->poison_on) {          // NRV_POISON: the slot's buffers (the alignment gaps between the input parts included), not the counter
     for (size_t i = 0; i + 4 <= in_bytes; i += 4) memcpy(sl.pin_in + i, &h->poison, 4);
@@ -1915,10 +1965,20 @@ int nrv_reads_raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const 
   memcpy(sl.pin_in + sl.off_starts, starts, (size_t)N * 4);
   memcpy(sl.pin_in + sl.off_reads, reads, (size_t)n_reads * sizeof(SegRead));
   memcpy(sl.pin_in + sl.off_feat, feat_ev, (size_t)N * kFeat * 4);
+  if (with_stats) {
+    StatAux* ax = (StatAux*)(sl.pin_in + sl.off_aux);
+    for (int r = 0; r < n_reads; ++r) ax[r] = StatAux{last_dur[r], on_device[r] ? 1 : 0};
+  }
   HIPCHK(h, hipMemcpyAsync(sl.d_in, sl.pin_in, in_bytes, hipMemcpyHostToDevice, h->copy_stream));
   HIPCHK(h, hipEventRecord(sl.ev_in, h->copy_stream));
   HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
-  if ((rc = raw_enqueue(h, sl))) {
+  // statistics first: every segmentation stage below (and the f32 re-run of _end, which reuses the slot's inputs) reads the
+  // descriptors and feature columns they leave in d_in
+  if (stat_len > 0)
+    rc = stats_enqueue(h, (const int16_t*)sl.d_in, (const int32_t*)(sl.d_in + sl.off_starts), (SegRead*)(sl.d_in + sl.off_reads),
+                       (const StatAux*)(sl.d_in + sl.off_aux), sl.d_stat, n_reads, N, stat_len, (float*)(sl.d_in + sl.off_feat),
+                       nullptr, nullptr);
+  if (rc || (rc = raw_enqueue(h, sl))) {
     (void)hipStreamSynchronize(h->stream);                      // part of the call may be enqueued: nothing of it may outlive the slot
     return rc;
   }
@@ -1929,6 +1989,32 @@ int nrv_reads_raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const 
   HIPCHK(h, hipGetLastError());
   sl.busy = true;
   return NRV_OK;
+}
+
+int nrv_reads_raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                        const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                        float* p1, float* p2, int8_t* a1, int8_t* a2, int* ticket) {
+  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, nullptr, nullptr, p1, p2, a1, a2, ticket);
+}
+
+int nrv_reads_raw_stats_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                              const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                              const int32_t* last_dur, const uint8_t* on_device,
+                              float* p1, float* p2, int8_t* a1, int8_t* a2, int* ticket) {
+  if (h && n_reads > 0 && (!last_dur || !on_device)) { h->err = "nrv_reads_raw_stats_begin: null last_dur / flags"; return NRV_E_INVALID; }
+  static const int32_t no_dur = 0;
+  static const uint8_t no_flag = 0;
+  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur ? last_dur : &no_dur, on_device ? on_device : &no_flag,
+                   p1, p2, a1, a2, ticket);
+}
+
+int nrv_predict_reads_raw_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                const int32_t* last_dur, const uint8_t* on_device,
+                                float* p1, float* p2, int8_t* a1, int8_t* a2) {
+  int t = -1;
+  const int rc = nrv_reads_raw_stats_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, p1, p2, a1, a2, &t);
+  return rc ? rc : nrv_reads_raw_end(h, t);
 }
 
 int nrv_reads_raw_end(nrv_handle* h, int ticket) {
@@ -1993,6 +2079,52 @@ int nrv_segment_reads(nrv_handle* h, const int16_t* raw, int64_t n_raw, const in
     HIPCHK(h, hipMemcpyAsync(sig_ev + e0 * kSig, h->d_sig[0], (size_t)ne * kSig * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
+  return NRV_OK;
+}
+
+int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts, int64_t N,
+                   const nrv_read_desc* reads, int n_reads, const int32_t* last_dur, double* shift, double* scale,
+                   double* mean, double* std, float* feat12) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((n_reads > 0 && (!last_dur || !shift || !scale)) || (N > 0 && (!mean || !std || !feat12))) { h->err = "nrv_read_stats: null argument"; return NRV_E_INVALID; }
+  if ((rc = upload_raw(h, raw, n_raw, starts, N, reads, n_reads))) return rc;
+  if (n_reads == 0) return NRV_OK;
+  const std::vector<uint8_t> on((size_t)n_reads, 1);
+  const int64_t max_len = stats_check(h, reads, n_reads, last_dur, on.data());
+  if (max_len < 0) return NRV_E_INVALID;
+  // one block of its own for everything the kernels write besides the descriptors: [aux | scratch | mean | std | feat]
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_scr = up((size_t)n_reads * sizeof(StatAux)), o_mean = o_scr + up((size_t)n_reads * kStatWords * 4);
+  const size_t o_std = o_mean + up((size_t)N * 8), o_feat = o_std + up((size_t)N * 8), bytes = o_feat + up((size_t)N * kFeat * 4);
+  std::vector<StatAux> ax((size_t)n_reads);
+  for (int r = 0; r < n_reads; ++r) ax[r] = StatAux{last_dur[r], 1};
+  std::vector<float> feat((size_t)N * kFeat);
+  std::vector<SegRead> back((size_t)n_reads);
+  char* d = nullptr;
+  HIPCHK(h, hipMalloc((void**)&d, bytes));
+  auto run = [&]() -> int {
+    int rc2 = poison_fill(h, d, bytes, h->stream);
+    if (rc2) return rc2;
+    HIPCHK(h, hipMemcpyAsync(d, ax.data(), (size_t)n_reads * sizeof(StatAux), hipMemcpyHostToDevice, h->stream));
+    if ((rc2 = stats_enqueue(h, h->d_raw, h->d_starts, h->d_reads, (const StatAux*)d, (unsigned*)(d + o_scr), n_reads, N, max_len,
+                             (float*)(d + o_feat), (double*)(d + o_mean), (double*)(d + o_std))))
+      return rc2;
+    HIPCHK(h, hipMemcpyAsync(back.data(), h->d_reads, (size_t)n_reads * sizeof(SegRead), hipMemcpyDeviceToHost, h->stream));
+    if (N) {
+      HIPCHK(h, hipMemcpyAsync(mean, d + o_mean, (size_t)N * 8, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipMemcpyAsync(std, d + o_std, (size_t)N * 8, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipMemcpyAsync(feat.data(), d + o_feat, (size_t)N * kFeat * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return NRV_OK;
+  };
+  rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  (void)hipFree(d);
+  if (rc) return rc;
+  for (int r = 0; r < n_reads; ++r) { shift[r] = back[r].shift; scale[r] = back[r].scale; }
+  for (int64_t e = 0; e < N; ++e) { feat12[2 * e] = feat[e * kFeat + 1]; feat12[2 * e + 1] = feat[e * kFeat + 2]; }
   return NRV_OK;
 }
 

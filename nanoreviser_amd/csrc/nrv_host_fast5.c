@@ -509,9 +509,11 @@ static int fail(char* err, int err_len, int code, const char* msg) {
 }
 
 /* the image of one file (fsz bytes, not modified, not kept) -> *out; the sanitizer driver (tools/hostfuzz) enters here */
-static int load_fast5_image(const uint8_t* file, long fsz, const char* group, const char* subgroup, int want_fastq,
-                            nrvh_read* out, char* err, int err_len) {
+static int load_fast5_image_ex(const uint8_t* file, long fsz, const char* group, const char* subgroup, int want_fastq,
+                               int flags, nrvh_read* out, int32_t* last_dur, int32_t* device_stats, char* err, int err_len) {
   memset(out, 0, sizeof *out);
+  if (last_dur) *last_dur = 0;
+  if (device_stats) *device_stats = 0;
   Buf B = {file, (size_t)fsz, 0, 0};
   Buf* b = &B;
   int rc = NRVH_UNSUPPORTED;
@@ -620,17 +622,26 @@ static int load_fast5_image(const uint8_t* file, long fsz, const char* group, co
       out->starts[i] = (int32_t)(st64[i] - a0);
     }
     if (!mono) { rc = NRVH_UNSUPPORTED; why = "event starts not ascending"; break; }
-    /* ---- shift / scale, per-base mean / std (preprocessing.py:100-101, 134-137) */
-    if (median_mad_i16(out->raw, out->n_raw, &out->shift, &out->scale)) { rc = NRVH_UNSUPPORTED; why = "empty signal behind the first event"; break; }
-    if (nrvh_event_stats(out->raw, out->n_raw, out->starts, n, (int32_t)len64[n - 1], mean, sd)) { rc = NRVH_UNSUPPORTED; why = "event statistics"; break; }
+    /* ---- shift / scale, per-base mean / std (preprocessing.py:100-101, 134-137).  NRVH_DEVICE_STATS: left to the device
+     * (nrv_reads_raw_stats_begin) - unless a base is longer than NRVH_DEVICE_STATS_MAX_BASE samples: there one GPU thread
+     * walks one base, and a stalled pore must not put a loop of a million samples into it; such a read is computed here */
+    if (out->n_raw <= 0 || out->n_raw >= ((int64_t)1 << 32)) { rc = NRVH_UNSUPPORTED; why = "empty signal behind the first event"; break; }
+    int on_device = (flags & NRVH_DEVICE_STATS) != 0;
+    for (int64_t i = 0; i < n && on_device; ++i) on_device = len64[i] <= (double)NRVH_DEVICE_STATS_MAX_BASE;
+    if (!on_device) {
+      if (median_mad_i16(out->raw, out->n_raw, &out->shift, &out->scale)) { rc = NRVH_UNSUPPORTED; why = "empty signal behind the first event"; break; }
+      if (nrvh_event_stats(out->raw, out->n_raw, out->starts, n, (int32_t)len64[n - 1], mean, sd)) { rc = NRVH_UNSUPPORTED; why = "event statistics"; break; }
+    }
+    if (last_dur) *last_dur = (int32_t)len64[n - 1];
+    if (device_stats) *device_stats = on_device;
     /* ---- the six features, f64 arithmetic, stored as f32 (hoststage.feature_rows + astype(float32)) */
     for (int64_t i = 0; i < n; ++i) {
       double col = 0.0;
       switch (out->bases[i]) { case 'A': col = 250; break; case 'G': col = 180; break; case 'T': col = 100; break; case 'C': col = 30; break; default: break; }
       float* f = out->feat + i * 6;
       f[0] = (float)(col / 300.0);
-      f[1] = (float)(mean[i] / out->shift);
-      f[2] = (float)(sd[i] / out->scale);
+      f[1] = on_device ? 0.0f : (float)(mean[i] / out->shift);
+      f[2] = on_device ? 0.0f : (float)(sd[i] / out->scale);
       f[3] = (float)(len64[i] / 10.0);
       f[4] = (float)(double)abm[i];
       f[5] = (float)(double)abs_[i];
@@ -658,12 +669,24 @@ static int load_fast5_image(const uint8_t* file, long fsz, const char* group, co
   if (sig_owned) free((void*)sig_bytes);
   if (fq_owned) free((void*)fq_bytes);
   free(st64); free(len64); free(abm); free(abs_); free(mean); free(sd);
-  if (rc != NRVH_OK) { nrvh_free_read(out); return fail(err, err_len, rc, why); }
+  if (rc != NRVH_OK) {
+    if (last_dur) *last_dur = 0;
+    if (device_stats) *device_stats = 0;
+    nrvh_free_read(out);
+    return fail(err, err_len, rc, why);
+  }
   return NRVH_OK;
 }
 
 int nrvh_load_fast5(const char* path, const char* group, const char* subgroup, int want_fastq, nrvh_read* out,
                     char* err, int err_len) {
+  return nrvh_load_fast5_ex(path, group, subgroup, want_fastq, 0, out, 0, 0, err, err_len);
+}
+
+int nrvh_load_fast5_ex(const char* path, const char* group, const char* subgroup, int want_fastq, int flags, nrvh_read* out,
+                       int32_t* last_dur, int32_t* device_stats, char* err, int err_len) {
+  if (last_dur) *last_dur = 0;
+  if (device_stats) *device_stats = 0;
   if (!path || !group || !subgroup || !out) return fail(err, err_len, NRVH_E_ARG, "bad arguments");
   memset(out, 0, sizeof *out);
   /* The file is MAPPED, not copied (r06 profile: the fread copy was 9 % of the host stage): the parser touches the metadata and
@@ -701,7 +724,7 @@ int nrvh_load_fast5(const char* path, const char* group, const char* subgroup, i
     if (!file || got != (size_t)fsz) { close(fd); free(file); return fail(err, err_len, NRVH_E_IO, "cannot read the file"); }
   }
   close(fd);
-  const int rc = load_fast5_image(file, fsz, group, subgroup, want_fastq, out, err, err_len);
+  const int rc = load_fast5_image_ex(file, fsz, group, subgroup, want_fastq, flags, out, last_dur, device_stats, err, err_len);
   if (mapped) munmap(file, (size_t)fsz); else free(file);
   return rc;
 }
@@ -716,6 +739,11 @@ void nrvh_free_bundle(nrvh_bundle* b) {
 
 int nrvh_load_bundle(const char* const* paths, int n, const char* group, const char* subgroup, int want_fastq,
                      nrvh_bundle* out) {
+  return nrvh_load_bundle_ex(paths, n, group, subgroup, want_fastq, 0, out, 0, 0);
+}
+
+int nrvh_load_bundle_ex(const char* const* paths, int n, const char* group, const char* subgroup, int want_fastq, int flags,
+                        nrvh_bundle* out, int32_t* last_dur, uint8_t* device_stats) {
   if (!paths || n < 0 || !group || !subgroup || !out) return NRVH_E_ARG;
   memset(out, 0, sizeof *out);
   nrvh_read* rd = (nrvh_read*)calloc((size_t)(n > 0 ? n : 1), sizeof(nrvh_read));
@@ -728,7 +756,11 @@ int nrvh_load_bundle(const char* const* paths, int n, const char* group, const c
   if (rd && out->meta && out->status && out->fastq_off && out->errors) {
     int64_t tr = 0, te = 0, tf = 0;
     for (int i = 0; i < n; ++i) {
-      out->status[i] = nrvh_load_fast5(paths[i], group, subgroup, want_fastq, &rd[i], out->errors + (size_t)i * NRVH_ERR_LEN, NRVH_ERR_LEN);
+      int32_t ld = 0, dev = 0;
+      out->status[i] = nrvh_load_fast5_ex(paths[i], group, subgroup, want_fastq, flags, &rd[i], &ld, &dev,
+                                          out->errors + (size_t)i * NRVH_ERR_LEN, NRVH_ERR_LEN);
+      if (last_dur) last_dur[i] = ld;
+      if (device_stats) device_stats[i] = (uint8_t)(dev != 0);
       if (out->status[i] == NRVH_OK) { tr += rd[i].n_raw; te += rd[i].n_ev; tf += rd[i].fastq_len; ++out->n_ok; }
     }
     out->n_raw = tr; out->n_ev = te;

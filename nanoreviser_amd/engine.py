@@ -33,6 +33,7 @@ SYMBOLS = [
     "nrv_prof_enable", "nrv_prof_read", "nrv_kernel_name", "nrv_last_error", "nrv_backend",
     "nrv_window", "nrv_set_precision", "nrv_get_precision", "nrv_predict_reads_raw", "nrv_reads_raw_begin", "nrv_reads_raw_end", "nrv_segment_reads",
     "nrv_device_count", "nrv_saturated", "nrv_prof_overhead",
+    "nrv_reads_raw_stats_begin", "nrv_predict_reads_raw_stats", "nrv_read_stats",
 ]
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "f16x2": 2}
@@ -137,6 +138,14 @@ def load_library(path: Optional[str] = None):
     lib.nrv_reads_raw_end.argtypes = [vp, C.c_int]
     lib.nrv_reads_raw_end.restype = C.c_int
     lib.nrv_segment_reads.argtypes = [vp, i16p, C.c_int64, i32p, C.c_int64, rdp, C.c_int, fp]
+    u8p, dp = C.POINTER(C.c_uint8), C.POINTER(C.c_double)
+    lib.nrv_predict_reads_raw_stats.argtypes = [vp, i16p, C.c_int64, i32p, fp, C.c_int64, rdp, C.c_int, i32p, u8p, fp, fp, i8p, i8p]
+    lib.nrv_predict_reads_raw_stats.restype = C.c_int
+    lib.nrv_reads_raw_stats_begin.argtypes = [vp, i16p, C.c_int64, i32p, fp, C.c_int64, rdp, C.c_int, i32p, u8p, fp, fp, i8p, i8p,
+                                              C.POINTER(C.c_int)]
+    lib.nrv_reads_raw_stats_begin.restype = C.c_int
+    lib.nrv_read_stats.argtypes = [vp, i16p, C.c_int64, i32p, C.c_int64, rdp, C.c_int, i32p, dp, dp, dp, dp, fp]
+    lib.nrv_read_stats.restype = C.c_int
     lib.nrv_prof_overhead.argtypes = [vp, C.POINTER(C.c_double)]
     lib.nrv_saturated.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.nrv_set_precision.argtypes = [vp, C.c_int]
@@ -312,10 +321,30 @@ class Reviser:
         out = (np.empty((n, 6), np.float32), np.empty((n, 5), np.float32), np.empty(n, np.int8), np.empty(n, np.int8))
         return raw, st, feat, descs, nr, eo, out
 
+    @staticmethod
+    def with_device_stats(packed, last_dur, on_device):
+        """The packed form of a call whose read statistics are computed on the device (include/nanorev.h
+        nrv_reads_raw_stats_begin): what `pack_reads_raw` / `pack_bundle` returned, plus per read the samples of its last
+        base and a flag - non-zero: the read's shift / scale and feature columns 1 - 2 are produced on the device and the
+        values in `packed` ignored; zero: the read is used as given.  `run_packed_raw` / `begin_packed_raw` take either form."""
+        nr = packed[4]
+        ld = np.ascontiguousarray(last_dur, dtype=np.int32).reshape(-1)
+        on = np.ascontiguousarray(on_device, dtype=np.uint8).reshape(-1)
+        if ld.size != nr or on.size != nr:
+            raise ValueError("last_dur / on_device must have one entry per read")
+        return tuple(packed[:7]) + (ld, on)
+
     def run_packed_raw(self, packed):
-        """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared."""
-        raw, st, feat, descs, nr, N, (p1, p2, a1, a2) = packed
+        """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared (or `with_device_stats` extended)."""
         fp, i8p = C.POINTER(C.c_float), C.POINTER(C.c_int8)
+        if len(packed) == 9:
+            raw, st, feat, descs, nr, N, (p1, p2, a1, a2), ld, on = packed
+            self._check(self._lib.nrv_predict_reads_raw_stats(
+                self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)),
+                feat.ctypes.data_as(fp), N, descs, nr, ld.ctypes.data_as(C.POINTER(C.c_int32)), on.ctypes.data_as(C.POINTER(C.c_uint8)),
+                p1.ctypes.data_as(fp), p2.ctypes.data_as(fp), a1.ctypes.data_as(i8p), a2.ctypes.data_as(i8p)))
+            return p1, p2, a1, a2
+        raw, st, feat, descs, nr, N, (p1, p2, a1, a2) = packed
         self._check(self._lib.nrv_predict_reads_raw(
             self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)),
             feat.ctypes.data_as(fp), N, descs, nr,
@@ -325,9 +354,16 @@ class Reviser:
     def begin_packed_raw(self, packed):
         """First half of `run_packed_raw` (nrv_reads_raw_begin): the inputs are copied and the whole call is enqueued; returns a
         ticket for `end_packed_raw`.  At most two calls in flight; the OUTPUT arrays of `packed` must stay alive until the end."""
-        raw, st, feat, descs, nr, N, (p1, p2, a1, a2) = packed
         fp, i8p = C.POINTER(C.c_float), C.POINTER(C.c_int8)
         t = C.c_int(-1)
+        if len(packed) == 9:                          # `with_device_stats`: nrv_reads_raw_stats_begin
+            raw, st, feat, descs, nr, N, (p1, p2, a1, a2), ld, on = packed
+            self._check(self._lib.nrv_reads_raw_stats_begin(
+                self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)),
+                feat.ctypes.data_as(fp), N, descs, nr, ld.ctypes.data_as(C.POINTER(C.c_int32)), on.ctypes.data_as(C.POINTER(C.c_uint8)),
+                p1.ctypes.data_as(fp), p2.ctypes.data_as(fp), a1.ctypes.data_as(i8p), a2.ctypes.data_as(i8p), C.byref(t)))
+            return t.value, (p1, p2, a1, a2)
+        raw, st, feat, descs, nr, N, (p1, p2, a1, a2) = packed
         self._check(self._lib.nrv_reads_raw_begin(
             self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)),
             feat.ctypes.data_as(fp), N, descs, nr,
@@ -354,6 +390,26 @@ class Reviser:
             self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)),
             st.size, descs, nr, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def read_stats(self, raws, starts, last_durs):
+        """The device-side read statistics alone (nrv_read_stats): per read the int16 samples from its first event on, its
+        int32 event starts and the samples of its last base.  Returns (shift[R], scale[R], mean[sum N], std[sum N] float64,
+        feat12 (sum N, 2) float32 = feature columns 1 and 2), bit for bit what the host stage computes."""
+        nr = len(raws)
+        raw, st, descs, _ = self._pack_raw(raws, starts, [0.0] * nr, [0.0] * nr)
+        ld = np.ascontiguousarray(last_durs, dtype=np.int32).reshape(-1)
+        if ld.size != nr:
+            raise ValueError("last_durs must have one entry per read")
+        N = st.size
+        shift, scale = np.empty(nr, np.float64), np.empty(nr, np.float64)
+        mean, std = np.empty(N, np.float64), np.empty(N, np.float64)
+        f12 = np.empty((N, 2), np.float32)
+        dp = C.POINTER(C.c_double)
+        self._check(self._lib.nrv_read_stats(
+            self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)), N, descs, nr,
+            ld.ctypes.data_as(C.POINTER(C.c_int32)), shift.ctypes.data_as(dp), scale.ctypes.data_as(dp),
+            mean.ctypes.data_as(dp), std.ctypes.data_as(dp), f12.ctypes.data_as(C.POINTER(C.c_float))))
+        return shift, scale, mean, std, f12
 
     @staticmethod
     def _fingerprint(a):

@@ -14,7 +14,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libnanorev_host.so")
 SYMBOLS = ["nrvh_abi_version", "nrvh_event_stats", "nrvh_load_fast5", "nrvh_free_read", "nrvh_load_bundle",
-           "nrvh_free_bundle", "nrvh_finish_read", "nrvh_finish_bundle"]
+           "nrvh_free_bundle", "nrvh_finish_read", "nrvh_finish_bundle", "nrvh_load_fast5_ex", "nrvh_load_bundle_ex"]
 _lib = None
 _tried = False
 
@@ -33,6 +33,8 @@ class _NativeBundle(C.Structure):             # include/nanorev_host.h: nrvh_bun
 
 
 OK, UNSUPPORTED, E_READ, E_IO, E_ARG = 0, 1, 2, 3, 4
+DEVICE_STATS = 1                 # include/nanorev_host.h NRVH_DEVICE_STATS
+DEVICE_STATS_MAX_BASE = 16384    # ... NRVH_DEVICE_STATS_MAX_BASE
 ERR_LEN = 96
 
 
@@ -47,7 +49,7 @@ def load() -> Optional[C.CDLL]:
     try:
         lib = C.CDLL(LIB_PATH)
         lib.nrvh_abi_version.restype = C.c_int
-        if lib.nrvh_abi_version() != 2:
+        if lib.nrvh_abi_version() != 3:               # a stale build is not half used: the NumPy path runs
             return None
         lib.nrvh_load_fast5.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(_NativeRead), C.c_char_p, C.c_int]
         lib.nrvh_load_fast5.restype = C.c_int
@@ -55,6 +57,12 @@ def load() -> Optional[C.CDLL]:
         lib.nrvh_free_read.restype = None
         lib.nrvh_load_bundle.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(_NativeBundle)]
         lib.nrvh_load_bundle.restype = C.c_int
+        lib.nrvh_load_fast5_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(_NativeRead),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p, C.c_int]
+        lib.nrvh_load_fast5_ex.restype = C.c_int
+        lib.nrvh_load_bundle_ex.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                            C.POINTER(_NativeBundle), C.c_void_p, C.c_void_p]
+        lib.nrvh_load_bundle_ex.restype = C.c_int
         lib.nrvh_free_bundle.argtypes = [C.POINTER(_NativeBundle)]
         lib.nrvh_free_bundle.restype = None
         lib.nrvh_finish_read.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
@@ -99,17 +107,24 @@ def event_stats(raw_signal, starts, last_dur):
     return mean, std
 
 
-def load_fast5(path: str, group: str, subgroup: str, want_fastq: bool = True):
+def load_fast5(path: str, group: str, subgroup: str, want_fastq: bool = True, device_stats: bool = False):
     """One fast5 file through the native host stage (csrc/nrv_host_fast5.c; the GIL is released for the whole call).
     Returns (code, payload): code OK -> payload = dict(raw int16[L], starts int32[N], feat float32[N,6], bases S1[N],
     shift, scale, fastq str | None); any other code -> payload = the reader's reason, and the caller runs the Python
-    host stage (h5lite + hoststage), which is the definition of every number here.  (None, ...) without the library."""
+    host stage (h5lite + hoststage), which is the definition of every number here.  (None, ...) without the library.
+    device_stats: the loader mode for nrv_reads_raw_stats_begin (nrvh_load_fast5_ex) - the payload also has `last_dur` and
+    `device_stats`; where the latter is True, shift / scale and feature columns 1 - 2 are zeros for the device to fill in."""
     lib = load()
     if lib is None:
         return None, "libnanorev_host.so not built"
     r = _NativeRead()
     err = C.create_string_buffer(160)
-    rc = lib.nrvh_load_fast5(os.fsencode(path), group.encode(), subgroup.encode(), 1 if want_fastq else 0, C.byref(r), err, 160)
+    ld, dev = C.c_int32(0), C.c_int32(0)
+    if device_stats:
+        rc = lib.nrvh_load_fast5_ex(os.fsencode(path), group.encode(), subgroup.encode(), 1 if want_fastq else 0, DEVICE_STATS,
+                                    C.byref(r), C.byref(ld), C.byref(dev), err, 160)
+    else:
+        rc = lib.nrvh_load_fast5(os.fsencode(path), group.encode(), subgroup.encode(), 1 if want_fastq else 0, C.byref(r), err, 160)
     if rc != OK:
         return rc, err.value.decode("utf8", "replace")
     try:
@@ -118,6 +133,8 @@ def load_fast5(path: str, group: str, subgroup: str, want_fastq: bool = True):
                "feat": _arr(r.feat, n * 6, np.float32).reshape(n, 6), "bases": _arr(r.bases, n, "S1"),
                "shift": float(r.shift), "scale": float(r.scale),
                "fastq": C.string_at(r.fastq, int(r.fastq_len)).decode("utf8", "replace") if r.fastq else None}
+        if device_stats:
+            out["last_dur"], out["device_stats"] = int(ld.value), bool(dev.value)
     finally:
         lib.nrvh_free_read(C.byref(r))
     return OK, out
@@ -128,10 +145,12 @@ def _arr(ptr, count, dtype):
     return np.frombuffer(C.string_at(ptr, count * np.dtype(dtype).itemsize), dtype=dtype) if count else np.zeros(0, dtype)
 
 
-def load_bundle(paths, group: str, subgroup: str, want_fastq: bool = True):
+def load_bundle(paths, group: str, subgroup: str, want_fastq: bool = True, device_stats: bool = False):
     """Several fast5 files in ONE native call (GIL released throughout): dict(status int32[n], errors [str], raw, starts,
     feat (E,6), bases S1[E], meta float64[n,4] = (raw_len, ev_len, shift, scale) per file, fastq [str | None]) over the
-    reads whose status is OK, concatenated in file order; None without the library."""
+    reads whose status is OK, concatenated in file order; None without the library.
+    device_stats: nrvh_load_bundle_ex in its NRVH_DEVICE_STATS mode; the dict also has last_dur int32[n] and
+    device_stats uint8[n] per file (1: shift / scale / feature columns 1 - 2 of that read are left to the device)."""
     lib = load()
     if lib is None:
         return None
@@ -139,7 +158,12 @@ def load_bundle(paths, group: str, subgroup: str, want_fastq: bool = True):
     arr = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
     mem = _BundleMem(lib)
     b = mem.b
-    rc = lib.nrvh_load_bundle(arr, n, group.encode(), subgroup.encode(), 1 if want_fastq else 0, C.byref(b))
+    if device_stats:
+        last_dur, dev = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
+        rc = lib.nrvh_load_bundle_ex(arr, n, group.encode(), subgroup.encode(), 1 if want_fastq else 0, DEVICE_STATS, C.byref(b),
+                                     last_dur.ctypes.data, dev.ctypes.data)
+    else:
+        rc = lib.nrvh_load_bundle(arr, n, group.encode(), subgroup.encode(), 1 if want_fastq else 0, C.byref(b))
     if rc != OK:
         return None
     mem.live = True
@@ -157,7 +181,8 @@ def load_bundle(paths, group: str, subgroup: str, want_fastq: bool = True):
                     j += 1
                 fastq[i] = ftxt[int(foff[i]):int(foff[j])].decode("utf8", "replace")
     # the big arrays are NOT copied: they are views of the C buffers, which live until the last view is gone
-    return {"status": status,
+    extra = {"last_dur": last_dur[:n], "device_stats": dev[:n]} if device_stats else {}
+    return {**extra, "status": status,
             "errors": [errs[i * ERR_LEN:(i + 1) * ERR_LEN].split(b"\0")[0].decode("utf8", "replace") if errs else "" for i in range(n)],
             "raw": mem.view(b.raw, int(b.n_raw), np.int16), "starts": mem.view(b.starts, E, np.int32),
             "feat": mem.view(b.feat, E * 6, np.float32).reshape(E, 6), "bases": mem.view(b.bases, E, "S1"),

@@ -5,7 +5,8 @@
  *   gcc -fsanitize=address,undefined -fno-sanitize-recover=all      (modes "fuzz", "api")
  *   gcc -fsanitize=thread                                           (mode "threads")
  * and run by tests/test_hostlib_sanitize.py; it INCLUDES the two sources, so the file image enters load_fast5_image
- * directly and the statics (read_dset, walk_chunks ...) locate what is worth mutating.  Any sanitizer report aborts; every
+ * directly (load_fast5_image_ex, in the plain and in the NRVH_DEVICE_STATS loader mode) and the statics (read_dset,
+ * walk_chunks ...) locate what is worth mutating.  Any sanitizer report aborts; every
  * outcome of a mutated file must be a return code.
  *
  *   host_fuzz fuzz N SEED TMPDIR file.fast5 ...     N mutations per file and class mix below
@@ -17,6 +18,12 @@
 
 #include <errno.h>
 #include <sys/stat.h>
+
+/* the plain loader mode; the mutated images below go through either mode */
+static int load_fast5_image(const uint8_t* file, long fsz, const char* group, const char* subgroup, int want_fastq,
+                            nrvh_read* out, char* err, int err_len) {
+  return load_fast5_image_ex(file, fsz, group, subgroup, want_fastq, 0, out, 0, 0, err, err_len);
+}
 
 static const char* G = "Basecall_1D_000";
 static const char* SG = "BaseCalled_template";
@@ -295,14 +302,31 @@ static int mode_fuzz(int nmut, uint64_t seed, const char* tmpdir, int nfiles, ch
         if (spit(tmpf, img, n)) { fprintf(stderr, "cannot write %s\n", tmpf); return 2; }
         const char* paths[3] = {files[fi], tmpf, "/nonexistent/x.fast5"};
         nrvh_bundle b;
-        if (nrvh_load_bundle(paths, 3, G, SG, (int)below(2), &b) != NRVH_OK) { fprintf(stderr, "bundle failed\n"); abort(); }
+        int32_t ld[3] = {-1, -1, -1};
+        uint8_t dev[3] = {9, 9, 9};
+        const int ex = (int)below(2);                                  /* half of them in the device-statistics mode */
+        if ((ex ? nrvh_load_bundle_ex(paths, 3, G, SG, (int)below(2), NRVH_DEVICE_STATS, &b, ld, dev)
+                : nrvh_load_bundle(paths, 3, G, SG, (int)below(2), &b)) != NRVH_OK) { fprintf(stderr, "bundle failed\n"); abort(); }
         if (b.status[0] != NRVH_OK || b.status[2] != NRVH_E_IO) { fprintf(stderr, "bundle statuses %d %d\n", b.status[0], b.status[2]); abort(); }
         rc = b.status[1];
+        if (ex && (dev[0] > 1 || dev[1] > 1 || dev[2] != 0 || ld[2] != 0 || (ld[0] != 3 && ld[0] != 5) || (rc != NRVH_OK && (dev[1] || ld[1])) ||
+                   (rc == NRVH_OK && ld[1] != 3 && ld[1] != 5))) { fprintf(stderr, "bundle last_dur / device_stats\n"); abort(); }
         if (rc == NRVH_OK && b.n_ev != n_ev0 + (int64_t)b.meta[4 + 1]) { fprintf(stderr, "bundle totals\n"); abort(); }
         nrvh_free_bundle(&b);
       } else {
-        rc = load_fast5_image(img, n, G, SG, (int)below(2), &r, err, sizeof err);
+        const int flags = below(2) ? NRVH_DEVICE_STATS : 0;
+        int32_t ld = -1, dev = -1;
+        rc = load_fast5_image_ex(img, n, G, SG, (int)below(2), flags, &r, &ld, &dev, err, sizeof err);
+        if (rc != NRVH_OK && (ld != 0 || dev != 0)) { fprintf(stderr, "last_dur / device_stats of a refused read\n"); abort(); }
         if (rc == NRVH_OK) {
+          if ((ld != 3 && ld != 5) || (dev != 0 && dev != 1) || (dev && !flags)) { fprintf(stderr, "last_dur %d device_stats %d\n", ld, dev); abort(); }
+          if (dev) {                                                   /* left to the device: zeros, and no base above the cap */
+            if (r.shift != 0.0 || r.scale != 0.0) { fprintf(stderr, "device_stats with a shift\n"); abort(); }
+            for (int64_t i = 0; i < r.n_ev; ++i) {
+              if (r.feat[6 * i + 1] != 0.0f || r.feat[6 * i + 2] != 0.0f) { fprintf(stderr, "device_stats with statistics columns\n"); abort(); }
+              if (i + 1 < r.n_ev && (int64_t)r.starts[i + 1] - r.starts[i] > NRVH_DEVICE_STATS_MAX_BASE) { fprintf(stderr, "device_stats with a long base\n"); abort(); }
+            }
+          }
           if (r.n_ev < 2 || r.n_raw < 0 || !r.raw || !r.starts || !r.feat || !r.bases) { fprintf(stderr, "OK with a broken record\n"); abort(); }
           for (int64_t i = 0; i < r.n_ev; ++i) if (r.starts[i] < 0) { fprintf(stderr, "negative start in an accepted read\n"); abort(); }
           if (it % 64 < 8) finish_some(&r, tmpdir);
@@ -335,6 +359,27 @@ static int mode_api(const char* tmpdir, int nfiles, char** files) {
   if (nrvh_load_fast5(files[0], "no_such_group", SG, 0, &r, err, 1) != NRVH_UNSUPPORTED) abort();
   if (nrvh_load_fast5(tmpdir, G, SG, 0, &r, err, sizeof err) == NRVH_OK) abort();           /* a directory */
   nrvh_free_read(0); nrvh_free_bundle(0);
+  /* the device-statistics loader mode: the same argument rules, out-pointers optional, the flag set for an ordinary read */
+  {
+    int32_t ld = -1, dev = -1;
+    uint8_t devs[64];
+    int32_t lds[64];
+    if (nrvh_load_fast5_ex(0, G, SG, 0, NRVH_DEVICE_STATS, &r, &ld, &dev, err, sizeof err) != NRVH_E_ARG || ld != 0 || dev != 0) abort();
+    if (nrvh_load_fast5_ex("/nonexistent/x", G, SG, 0, NRVH_DEVICE_STATS, &r, 0, 0, 0, 0) != NRVH_E_IO) abort();
+    if (nrvh_load_fast5_ex(files[0], G, SG, 1, NRVH_DEVICE_STATS, &r, 0, 0, err, sizeof err) != NRVH_OK) abort();
+    nrvh_free_read(&r);
+    if (nrvh_load_fast5_ex(files[0], G, SG, 1, NRVH_DEVICE_STATS, &r, &ld, &dev, err, sizeof err) != NRVH_OK || dev != 1 || (ld != 3 && ld != 5)) abort();
+    if (r.shift != 0.0 || r.scale != 0.0 || r.feat[1] != 0.0f || r.feat[2] != 0.0f) abort();
+    nrvh_free_read(&r);
+    if (nrvh_load_fast5_ex(files[0], G, SG, 1, 0, &r, &ld, &dev, err, sizeof err) != NRVH_OK || dev != 0 || r.scale <= 0.0) abort();
+    nrvh_free_read(&r);
+    if (nrvh_load_bundle_ex(0, 1, G, SG, 0, NRVH_DEVICE_STATS, &b, lds, devs) != NRVH_E_ARG) abort();
+    if (nrvh_load_bundle_ex((const char* const*)files, nfiles > 64 ? 64 : nfiles, G, SG, 1, NRVH_DEVICE_STATS, &b, 0, 0) != NRVH_OK) abort();
+    nrvh_free_bundle(&b);
+    if (nrvh_load_bundle_ex((const char* const*)files, nfiles > 64 ? 64 : nfiles, G, SG, 0, NRVH_DEVICE_STATS, &b, lds, devs) != NRVH_OK) abort();
+    for (int i = 0; i < (nfiles > 64 ? 64 : nfiles); ++i) if (devs[i] != 1 || b.meta[4 * i + 2] != 0.0 || b.meta[4 * i + 3] != 0.0) abort();
+    nrvh_free_bundle(&b);
+  }
   if (nrvh_load_bundle(0, 1, G, SG, 0, &b) != NRVH_E_ARG) abort();
   if (nrvh_load_bundle((const char* const*)files, 0, G, SG, 1, &b) != NRVH_OK || b.n_ok != 0 || b.n_ev != 0) abort();
   nrvh_free_bundle(&b);
@@ -405,7 +450,8 @@ static void* thread_main(void* p) {
   snprintf(shared, sizeof shared, "%s/shared_out.fasta", j->tmpdir);
   for (int it = 0; it < j->iters; ++it) {
     nrvh_bundle b;
-    if (nrvh_load_bundle((const char* const*)j->files, j->nfiles, G, SG, it & 1, &b) != NRVH_OK || b.n_ok != j->nfiles) { j->failed = 1; return 0; }
+    if ((it & 2 ? nrvh_load_bundle_ex((const char* const*)j->files, j->nfiles, G, SG, it & 1, NRVH_DEVICE_STATS, &b, 0, 0)
+                : nrvh_load_bundle((const char* const*)j->files, j->nfiles, G, SG, it & 1, &b)) != NRVH_OK || b.n_ok != j->nfiles) { j->failed = 1; return 0; }
     j->n_ev = b.n_ev;
     const int64_t el = (int64_t)b.meta[1], nwin = el - 11;
     int8_t* a = (int8_t*)calloc((size_t)el, 1);
