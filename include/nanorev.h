@@ -136,6 +136,42 @@ int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32
                    const nrv_read_desc* reads, int n_reads, const int32_t* last_dur, double* shift, double* scale,
                    double* mean, double* std, float* feat12);
 
+/* Raw reads in, REVISED reads out (opt-in; nothing above changes): the merge of the two models' calls (output_handeler.py:83,
+ * 104-122 as SURVEY.md 8a a16 decodes it), the per-base quality and the packing of the reads run on the device behind the
+ * call's last launch group, and only the merged block crosses PCIe on the way back - p1 / p2 / a1 / a2 are not downloaded.
+ * The arguments of nrv_reads_raw_stats_begin (last_dur and on_device may BOTH be NULL: statistics from the host, as for
+ * nrv_reads_raw_begin), and instead of the four output arrays
+ *   bases [N]       the reads' original basecalls (ASCII), concatenated like the per-event arrays;
+ *   q_thr [39]      or NULL.  Entry k - 2 is the smallest f32 confidence min(p1[a1], p2[a2]) of a window that earns Phred k,
+ *                   k = 2 .. 40 (ascending): its quality character is 33 + 1 + #{k : q_thr[k] <= confidence}, compared in f32.
+ *                   nrvh_phred_thresholds (include/nanorev_host.h) gives the table of the command line's formula.  NULL (FASTA):
+ *                   no quality is produced and `qual` is not touched;
+ *   seq, qual       uint8, capacity N + max(N - T, 0) each (qual may be NULL): the revised reads back to back.  Event j of a read
+ *                   with ev_len bases emits its own base with quality '#' for j < (T - 1) / 2 or j >= (T - 1) / 2 +
+ *                   max(ev_len - T, 0); otherwise 0, 1 or 2 characters decided by its window's two argmax classes (both models agree
+ *                   on a base: it; model1 'D' and model2 a base: the original base, then model2's; both '-': nothing; else the
+ *                   original base), each with the window's quality.  Window i of a read is window ev_off + i of the call;
+ *   off [n_reads + 1]  int64: read r is seq[off[r] .. off[r + 1]), off[n_reads] the total.
+ * The bytes are those of the host merge (hoststage.emit_calls is the definition) on the outputs of nrv_predict_reads_raw, in
+ * every precision mode.  N <= T: no window - seq is `bases`, qual all '#', nothing is enqueued.  N < 2^31.
+ * nrv_reads_raw_end collects the call (seq / qual / off must stay valid until then); tickets, the two-calls-in-flight rule and the
+ * range-guard re-run (which runs the merge again behind the f32 kernels) are those of nrv_reads_raw_begin.
+ * nrv_revise_reads_raw IS _begin + _end. */
+int nrv_revise_reads_raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                               const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                               const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                               uint8_t* seq, uint8_t* qual, int64_t* off, int* ticket);
+int nrv_revise_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                         const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                         const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                         uint8_t* seq, uint8_t* qual, int64_t* off);
+/* The merge alone, by the kernels nrv_revise_reads_raw_begin runs, on calls the HOST supplies: bases [sum ev_len], ev_len [n_reads],
+ * a1 / a2 [n_win] (any int8: labels are clipped to 0 .. 5 as the host merge does), p1 [n_win][6] / p2 [n_win][5] (needed only with
+ * q_thr; the gather index is clamped to the row), n_win = max(sum ev_len - T, 0).  The twin of nrv_segment_reads / nrv_read_stats,
+ * used by the parity tests. */
+int nrv_merge_calls(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                    const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

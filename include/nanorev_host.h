@@ -110,6 +110,21 @@ int nrvh_finish_bundle(const char* bases, const int64_t* ev_len, int n_reads, co
                        int64_t n_win_total, int T, const uint8_t* qc, const char* const* names, const char* const* dsts,
                        int fastq, int64_t* n_written, int32_t* status);
 
+/* Revised reads that are ALREADY merged - what nrv_revise_reads_raw (include/nanorev.h) returns - to their output files: for
+ * every read r of a call the record of output_handeler.py:26-62 byte for byte (the FASTQ writer's missing newline in front of
+ * '+' included) from seq[off[r] .. off[r + 1]) and, for fastq != 0, qual over the same range ('#' per base when qual is NULL),
+ * written to a temporary and renamed to dsts[r] exactly as nrvh_finish_bundle does.  names[r]: the record's name (file name,
+ * blanks replaced by "|||").  n_seq: the bytes seq / qual hold; off [n_reads + 1].  status[r] / n_written[r] per read as for
+ * nrvh_finish_bundle: a read whose offsets are not ascending or leave [0, n_seq] is NRVH_E_ARG, an unwritable destination
+ * NRVH_E_IO; a failing read does not stop the others. */
+int nrvh_write_records(const uint8_t* seq, const uint8_t* qual, int64_t n_seq, const int64_t* off, int n_reads,
+                       const char* const* names, const char* const* dsts, int fastq, int64_t* n_written, int32_t* status);
+
+/* thr[k - 2], k = 2 .. 40: the smallest f32 confidence c for which clip(round(-10 log10(max(1 - c, 1e-4))), 1, 40) - computed in
+ * f64, rounded half to even: the command line's per-base quality - is at least k.  The q_thr table of nrv_revise_reads_raw for
+ * callers without NumPy (cli.phred_thresholds finds the same 39 values from the NumPy formula itself). */
+int nrvh_phred_thresholds(float thr[39]);
+
 /* ABI version of this header (3: nrvh_load_fast5_ex / nrvh_load_bundle_ex). */
 int nrvh_abi_version(void);
 

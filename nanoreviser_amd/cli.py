@@ -96,8 +96,17 @@ def get_args(argv: Optional[Sequence[str]] = None):
                         "NRV_CLI_PIPELINE=0, several engines per device (NRV_CLI_ENGINES), reads whose window range is split "
                         "over GPU workers (a slice needs the whole read's median), and any read with a base of more than "
                         "16384 samples")
+    p.add_argument("--device_merge", action="store_true", default=False,
+                   help="merge the two models' calls, compute the per-base quality and pack the revised reads on the GPU instead "
+                        "of in the host stage: 2 - 4 bytes per base come back instead of 46 and a device call's reads are "
+                        "written by one native task, the same output byte for byte (also NRV_DEVICE_MERGE=1).  Off by default.  "
+                        "Applies where --device_stats applies (the pipelined native-bundle path) and composes with it; the "
+                        "Python fallback reader, NRV_CLI_PIPELINE=0, several engines per device, reads whose window range is "
+                        "split over GPU workers, a library without the new entry points and the per-read retry after a failed "
+                        "call keep the host merge")
     a = p.parse_args(argv)
     a.device_stats = bool(a.device_stats) or device_stats_env()
+    a.device_merge = bool(a.device_merge) or device_merge_env()
     if a.virsion:
         print(f"The virsion of NanoReviser : {VERSION} ")
         raise SystemExit(0)
@@ -110,6 +119,11 @@ def get_args(argv: Optional[Sequence[str]] = None):
 def device_stats_env() -> bool:
     """NRV_DEVICE_STATS=1 (anything but empty / 0): the environment form of --device_stats."""
     return os.environ.get("NRV_DEVICE_STATS", "0").strip() not in ("", "0")
+
+
+def device_merge_env() -> bool:
+    """NRV_DEVICE_MERGE=1 (anything but empty / 0): the environment form of --device_merge."""
+    return os.environ.get("NRV_DEVICE_MERGE", "0").strip() not in ("", "0")
 
 
 def model_paths(args):
@@ -160,6 +174,38 @@ def phred_chars(p1: np.ndarray, p2: np.ndarray, a1=None, a2=None) -> np.ndarray:
         conf = np.minimum(p1.max(-1), p2.max(-1)).astype(np.float64)
     q = np.clip(np.round(-10.0 * np.log10(np.maximum(1.0 - conf, 1e-4))), 1, 40).astype(np.int64)
     return (q + 33).astype(np.uint8)
+
+
+_PHRED_THR = None
+
+
+def phred_thresholds() -> np.ndarray:
+    """float32[39]: entry k - 2 is the smallest f32 confidence for which `phred_chars` yields Phred >= k, k = 2 .. 40.
+    `phred_chars` is a monotone step function of the f32 confidence on [0, 1] (checked on the CPU: 5 M random values and
+    +-2000 ulps around every step), so 33 + 1 + searchsorted(thr, conf, 'right') reproduces its characters exactly - which is
+    how the device merge (csrc/nrv_merge.h) gives the host's quality bytes without a log10.  Found by bisection over the f32 bit
+    patterns (ascending with the value on [0, 1]) of `phred_chars` ITSELF, once per process."""
+    global _PHRED_THR
+    if _PHRED_THR is None:
+        def q(bits):
+            c = bits.astype(np.uint32).view(np.float32).reshape(-1, 1)
+            return phred_chars(c, c).astype(np.int64) - 33
+        k = np.arange(2, 41, dtype=np.int64)
+        lo, hi = np.zeros(39, np.int64), np.full(39, 0x3F800000, np.int64)        # q(0.0) = 1 < k <= 40 = q(1.0)
+        assert (q(lo) < k).all() and (q(hi) >= k).all()
+        while (hi - lo > 1).any():
+            mid = lo + (hi - lo) // 2
+            up = q(mid) >= k
+            hi, lo = np.where(up, mid, hi), np.where(up, lo, mid)
+        thr = hi.astype(np.uint32).view(np.float32).copy()
+        thr.flags.writeable = False
+        _PHRED_THR = thr
+    return _PHRED_THR
+
+
+def phred_lookup(conf) -> np.ndarray:
+    """`phred_chars` through the table: uint8 characters for f32 confidences (what the device computes per window)."""
+    return (33 + 1 + np.searchsorted(phred_thresholds(), np.asarray(conf, np.float32), "right")).astype(np.uint8)
 
 
 def _finish_read(T: int, rt, p1, p2, a1, a2, want_qual: bool = True):
@@ -445,6 +491,27 @@ def _finish_bundle_native(spec, T, fns, bases, ev_len, a1, a2, qc):
         return [(0, repr(e))] * len(fns)
 
 
+def _write_records_native(spec, fns, seq, qual, off):
+    """All reads of one --device_merge call through nrvh_write_records (one C call, GIL released): [(bases written, error)]."""
+    try:
+        os.makedirs(spec.output_dir, exist_ok=True)
+        r = hostlib.write_records(seq, qual, off, [fn.split("/")[-1].replace(" ", "|||") for fn in fns],
+                                  [out_name(spec.output_dir, fn, spec.output_format) for fn in fns], spec.output_format == "fastq")
+        if r is None:
+            raise RuntimeError("libnanorev_host.so went away")
+        nw, st = r
+        return [(int(n), None if c == hostlib.OK else f"native finisher: error {int(c)}") for n, c in zip(nw, st)]
+    except Exception as e:
+        return [(0, repr(e))] * len(fns)
+
+
+def _host_merge_form(packed):
+    """A `with_device_merge` tuple back in the form whose call returns (p1, p2, a1, a2): for the paths that keep the host merge."""
+    if packed is None or len(packed) != 12:
+        return packed
+    return tuple(packed[:7]) if packed[7] is None else tuple(packed[:9])
+
+
 def usable_cores() -> int:
     """Cores this process can really use: its affinity mask, cut down to the cgroup's CPU quota (a container that shows
     256 CPUs and grants 16 runs sixteen parser workers, not the 32 that --thread's default of 100 would otherwise give:
@@ -687,6 +754,16 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
             for fn, rt, fq in batch:
                 fallback(fn, rt, fq, e)
 
+    def finish_merged(batch, outs):
+        """Finisher thread, --device_merge: the call came back as revised reads; their records and files are one pool task."""
+        try:
+            seq, qual, off = outs
+            fut = pool.submit(_write_records_native, spec, [fn for fn, _, _ in batch], seq, qual if want_qual else None, off)
+            finishing.append((fut, [fn for fn, _, _ in batch], [rt for _, rt, _ in batch], [fq for _, _, fq in batch]))
+        except Exception as e:
+            for fn, rt, fq in batch:
+                fallback(fn, rt, fq, e)
+
     def run_batch(batch, packed=None, bundle=None):
         """Engine thread: one device call for the batch; merging and writing go to the finisher."""
         reviser = free.get()                          # an engine that is not inside a call (all have the same T, weights)
@@ -705,6 +782,12 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
     device_stats = bool(getattr(args, "device_stats", False)) and pipelined and native_threads and pool is not None
     if device_stats:
         stats["read_stats"] = "device"
+    # --device_merge / NRV_DEVICE_MERGE=1: the same path's call merges, scores and packs its reads on the device
+    # (nrv_revise_reads_raw_begin) and its finisher is one nrvh_write_records task.  Needs both libraries' new symbols.
+    device_merge = (bool(getattr(args, "device_merge", False)) and pipelined and native_threads and pool is not None
+                    and hostlib.has_write_records())
+    if device_merge:
+        stats["merge"] = "device"
     pending = {}                                      # id(engine) -> the call in flight on it: (ticket, batch, bundle, trace index, t0)
 
     def _done():
@@ -738,6 +821,8 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
             stats["engine_s"] += time.perf_counter() - t0
         if ti is not None:
             trace[ti] = ("call", t_begin - t_start, time.perf_counter() - t_begin)
+        if isinstance(tk, tuple) and len(tk) == 3:    # a --device_merge call: (seq, qual, off)
+            return fin.submit(finish_merged, batch, outs)
         return fin.submit(finish_bundle, batch, bundle, outs)
 
     def flush_pipeline():
@@ -771,6 +856,7 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                 return collect(reviser, prev) if prev is not None else _done()
         if prev is not None:                          # between a call's two halves nothing else may run on its handle
             collect(reviser, prev)
+        packed = _host_merge_form(packed)             # every path below merges on the host
 
         def reads():                                  # the reads as tensors: only the per-read paths need them
             return _bundle_reads(bundle) if bundle is not None else [rt for _, rt, _ in batch]
@@ -856,6 +942,9 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                     packed = type(rv).pack_bundle(bundle["raw"], bundle["starts"], bundle["feat"], bundle["meta"], rv.T)
                     if "device_stats" in bundle:
                         packed = type(rv).with_device_stats(packed, bundle["last_dur"], bundle["device_stats"])
+                    if (device_merge and hasattr(rv, "with_device_merge") and "bases" in bundle
+                            and len(bundle["bases"]) == int(bundle["meta"][:, 1].sum())):
+                        packed = type(rv).with_device_merge(packed, bundle["bases"], want_qual)
                 elif bundle is None and len(batch) > 1:
                     packed = prepare_many(type(rv), [rt for _, rt, _ in batch], rv.T)
             except Exception:

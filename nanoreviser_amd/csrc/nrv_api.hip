@@ -544,6 +544,16 @@ struct nrv_handle {
     size_t off_starts = 0, off_reads = 0, off_feat = 0, rows = 0;
     size_t off_aux = 0;                                                   // nrv_reads_raw_stats_begin: [.. | StatAux per read] behind feat
     unsigned* d_stat = nullptr; size_t cap_stat = 0;                      // ... and its scratch (min / max, histograms: nrv_stats.h)
+    // nrv_revise_reads_raw_begin (nrv_merge.h): the call's bases [.. | bases u8] at the end of d_in, and a merged-output block of
+    // the slot's own, [off i64 x (n_reads + 1) | seq | qual] - the ONLY part such a call downloads (with the 64-byte counter of
+    // d_out) - followed on the device by the kernels' scratch [rec u32 x N | tile u64]
+    size_t off_bases = 0;
+    char* d_mrg = nullptr; char* pin_mrg = nullptr; size_t cap_mrg = 0;
+    size_t m_seq = 0, m_qual = 0, m_rec = 0, m_tile = 0, m_dl = 0;        // offsets into d_mrg; m_dl = bytes that come back
+    bool merge = false, want_q = false;
+    float thr[kPhredSteps] = {0};
+    uint8_t *seq = nullptr, *qual = nullptr;
+    int64_t* off = nullptr;
     int64_t N = 0, n = 0;
     int n_reads = 0;
     float *p1 = nullptr, *p2 = nullptr;
@@ -1406,6 +1416,7 @@ void nrv_destroy(nrv_handle* h) {
   for (auto& sl : h->raw_slot) {
     (void)hipFree(sl.d_in); (void)hipFree(sl.d_out); (void)hipHostFree(sl.pin_in); (void)hipHostFree(sl.pin_out);
     (void)hipFree(sl.d_stat);
+    (void)hipFree(sl.d_mrg); (void)hipHostFree(sl.pin_mrg);
     if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
     if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
     if (sl.ev_out) (void)hipEventDestroy(sl.ev_out);
@@ -1892,15 +1903,71 @@ static int64_t stats_check(nrv_handle* h, const nrv_read_desc* reads, int n_read
   return max_len;
 }
 
-// nrv_reads_raw_begin (last_dur == nullptr: today's call, to the byte) and nrv_reads_raw_stats_begin
+// The merge kernels (nrv_merge.h) behind whatever produced a.a1 / a2 / p1 / p2 on the compute stream: N >= 1 events
+static int merge_enqueue(nrv_handle* h, const MergeArgs& a) {
+  const unsigned tiles = (unsigned)((a.N + kMergeTile - 1) / kMergeTile);
+  hipLaunchKernelGGL(merge_emit_kernel, dim3(tiles), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(merge_tile_scan_kernel, dim3(1), dim3(256), 0, h->stream, a, (int)tiles);
+  hipLaunchKernelGGL(merge_scatter_kernel, dim3(tiles), dim3(256), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return NRV_OK;
+}
+// layout of a merged block for N events, n windows, n_reads reads: [off | seq | qual] (what comes back) + [rec | tile] (scratch)
+struct MergeLayout { size_t seq, qual, rec, tile, dl, bytes; };
+static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads) {
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  MergeLayout m;
+  const size_t cap = (size_t)(N + n);
+  m.seq = up(((size_t)n_reads + 1) * 8);
+  m.qual = m.seq + up(cap);
+  m.dl = m.qual + up(cap);
+  m.rec = m.dl;
+  m.tile = m.rec + up((size_t)N * 4);
+  m.bytes = m.tile + up((size_t)((N + kMergeTile - 1) / kMergeTile) * 8);
+  return m;
+}
+// No window at all (N <= T): the reads come back as they are, on the host
+static void merge_nothing(const uint8_t* bases, const nrv_read_desc* reads, int n_reads, int64_t N, uint8_t* seq, uint8_t* qual, int64_t* off) {
+  if (N > 0) memcpy(seq, bases, (size_t)N);
+  if (qual && N > 0) memset(qual, '#', (size_t)N);
+  for (int r = 0; r < n_reads; ++r) off[r] = reads[r].ev_off;
+  off[n_reads] = N;
+}
+struct MergeReq {             // what nrv_revise_reads_raw_begin adds to a raw-read call
+  const uint8_t* bases;
+  const float* q_thr;
+  uint8_t *seq, *qual;
+  int64_t* off;
+};
+static MergeArgs slot_merge_args(const nrv_handle* h, const nrv_handle::RawSlot& sl) {
+  char* const d = sl.d_out + 64;
+  MergeArgs a;
+  a.reads = (const SegRead*)(sl.d_in + sl.off_reads);
+  a.n_reads = sl.n_reads; a.T = h->T; a.N = sl.N;
+  a.bases = (const unsigned char*)(sl.d_in + sl.off_bases);
+  a.a1 = (const signed char*)(d + sl.rows * 44); a.a2 = (const signed char*)(d + sl.rows * 45);
+  a.p1 = sl.want_q ? (const float*)d : nullptr; a.p2 = sl.want_q ? (const float*)(d + sl.rows * 24) : nullptr;
+  a.rec = (unsigned*)(sl.d_mrg + sl.m_rec); a.tile = (unsigned long long*)(sl.d_mrg + sl.m_tile);
+  a.off = (long long*)sl.d_mrg; a.seq = (unsigned char*)(sl.d_mrg + sl.m_seq);
+  a.qual = sl.want_q ? (unsigned char*)(sl.d_mrg + sl.m_qual) : nullptr;
+  memcpy(a.thr, sl.thr, sizeof a.thr);
+  return a;
+}
+
+// nrv_reads_raw_begin (last_dur == nullptr: today's call, to the byte), nrv_reads_raw_stats_begin and (mr != nullptr)
+// nrv_revise_reads_raw_begin
 static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
                      const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
                      const int32_t* last_dur, const uint8_t* on_device,
-                     float* p1, float* p2, int8_t* a1, int8_t* a2, int* ticket) {
+                     float* p1, float* p2, int8_t* a1, int8_t* a2, int* ticket, const MergeReq* mr = nullptr) {
   int rc = check_handle(h);
   if (rc) return rc;
   if (!ticket) { h->err = "nrv_reads_raw_begin: null ticket"; return NRV_E_INVALID; }
   if ((rc = raw_check(h, raw, n_raw, starts, feat_ev, N, reads, n_reads))) return rc;
+  if (mr && (!mr->off || (N > 0 && (!mr->bases || !mr->seq)) || N >= ((int64_t)1 << 31))) {
+    h->err = "nrv_revise_reads_raw_begin: null bases / seq / off (or 2^31 events and more)";
+    return NRV_E_INVALID;
+  }
   const bool with_stats = last_dur != nullptr || on_device != nullptr;
   const int64_t stat_len = with_stats ? stats_check(h, reads, n_reads, last_dur, on_device) : 0;
   if (stat_len < 0) return NRV_E_INVALID;
@@ -1912,14 +1979,20 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
   sl.N = N; sl.n = N - T > 0 ? N - T : 0; sl.n_reads = n_reads;
   sl.p1 = p1; sl.p2 = p2; sl.a1 = a1; sl.a2 = a2;
   *ticket = k;
-  if (sl.n == 0) { sl.busy = true; return NRV_OK; }           // nothing to compute: _end returns at once
+  sl.merge = mr != nullptr;
+  if (sl.n == 0) {                                              // nothing to compute: _end returns at once
+    if (mr) merge_nothing(mr->bases, reads, n_reads, N, mr->seq, mr->q_thr ? mr->qual : nullptr, mr->off);
+    sl.busy = true;
+    return NRV_OK;
+  }
   static_assert(sizeof(SegRead) == sizeof(nrv_read_desc), "descriptor layouts must match");
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   sl.off_starts = up((size_t)n_raw * 2);
   sl.off_reads = sl.off_starts + up((size_t)N * 4);
   sl.off_feat = sl.off_reads + up((size_t)n_reads * sizeof(SegRead));
   sl.off_aux = sl.off_feat + up((size_t)N * kFeat * 4);
-  const size_t in_bytes = sl.off_aux + (with_stats ? up((size_t)n_reads * sizeof(StatAux)) : 0);
+  sl.off_bases = sl.off_aux + (with_stats ? up((size_t)n_reads * sizeof(StatAux)) : 0);
+  const size_t in_bytes = sl.off_bases + (mr ? up((size_t)N) : 0);
   sl.rows = ((size_t)sl.n + kRowPad - 1) / kRowPad * kRowPad;
   const size_t out_bytes = 64 + sl.rows * kOutBytes;
   if (!sl.ev_in) {
@@ -1946,6 +2019,21 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
     sl.cap_out = c;
     sl.sat_seen = 0;
   }
+  if (mr) {
+    const MergeLayout m = merge_layout(N, sl.n, n_reads);
+    sl.m_seq = m.seq; sl.m_qual = m.qual; sl.m_rec = m.rec; sl.m_tile = m.tile; sl.m_dl = m.dl;
+    sl.want_q = mr->q_thr != nullptr && mr->qual != nullptr;
+    if (sl.want_q) memcpy(sl.thr, mr->q_thr, sizeof sl.thr);
+    sl.seq = mr->seq; sl.qual = mr->qual; sl.off = mr->off;
+    if (m.bytes > sl.cap_mrg) {
+      (void)hipFree(sl.d_mrg); (void)hipHostFree(sl.pin_mrg);
+      sl.d_mrg = sl.pin_mrg = nullptr; sl.cap_mrg = 0;
+      const size_t c = m.bytes + m.bytes / 2 + 4096;
+      HIPCHK(h, hipMalloc((void**)&sl.d_mrg, c));
+      HIPCHK(h, hipHostMalloc((void**)&sl.pin_mrg, c, hipHostMallocDefault));
+      sl.cap_mrg = c;
+    }
+  }
   const size_t stat_bytes = stat_len > 0 ? (size_t)n_reads * kStatWords * 4 : 0;
   if (stat_bytes > sl.cap_stat) {
     (void)hipFree(sl.d_stat);
@@ -1960,8 +2048,13 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
     for (size_t i = 0; i + 4 <= in_bytes; i += 4) memcpy(sl.pin_in + i, &h->poison, 4);
     if ((rc = poison_fill(h, sl.d_in, sl.cap_in, h->copy_stream)) || (rc = poison_fill(h, sl.d_out + 64, sl.cap_out - 64, h->stream)))
       return rc;
+    if (mr) {
+      for (size_t i = 0; i + 4 <= sl.m_dl; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
+      if ((rc = poison_fill(h, sl.d_mrg, sl.cap_mrg, h->stream))) return rc;
+    }
   }
   memcpy(sl.pin_in, raw, (size_t)n_raw * 2);
+  if (mr) memcpy(sl.pin_in + sl.off_bases, mr->bases, (size_t)N);
   memcpy(sl.pin_in + sl.off_starts, starts, (size_t)N * 4);
   memcpy(sl.pin_in + sl.off_reads, reads, (size_t)n_reads * sizeof(SegRead));
   memcpy(sl.pin_in + sl.off_feat, feat_ev, (size_t)N * kFeat * 4);
@@ -1978,13 +2071,19 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
     rc = stats_enqueue(h, (const int16_t*)sl.d_in, (const int32_t*)(sl.d_in + sl.off_starts), (SegRead*)(sl.d_in + sl.off_reads),
                        (const StatAux*)(sl.d_in + sl.off_aux), sl.d_stat, n_reads, N, stat_len, (float*)(sl.d_in + sl.off_feat),
                        nullptr, nullptr);
-  if (rc || (rc = raw_enqueue(h, sl))) {
+  // the merge reads the slot's output block: behind the call's last launch group, ahead of ev_done
+  if (rc || (rc = raw_enqueue(h, sl)) || (mr && (rc = merge_enqueue(h, slot_merge_args(h, sl))))) {
     (void)hipStreamSynchronize(h->stream);                      // part of the call may be enqueued: nothing of it may outlive the slot
     return rc;
   }
   HIPCHK(h, hipEventRecord(sl.ev_done, h->stream));
   HIPCHK(h, hipStreamWaitEvent(h->d2h_stream, sl.ev_done, 0));
-  HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, out_bytes, hipMemcpyDeviceToHost, h->d2h_stream));
+  if (mr) {                                                     // the counter and the merged block; p1 / p2 / a1 / a2 stay on the device
+    HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64, hipMemcpyDeviceToHost, h->d2h_stream));
+    HIPCHK(h, hipMemcpyAsync(sl.pin_mrg, sl.d_mrg, sl.m_dl, hipMemcpyDeviceToHost, h->d2h_stream));
+  } else {
+    HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, out_bytes, hipMemcpyDeviceToHost, h->d2h_stream));
+  }
   HIPCHK(h, hipEventRecord(sl.ev_out, h->d2h_stream));
   HIPCHK(h, hipGetLastError());
   sl.busy = true;
@@ -2017,6 +2116,25 @@ int nrv_predict_reads_raw_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw
   return rc ? rc : nrv_reads_raw_end(h, t);
 }
 
+int nrv_revise_reads_raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                               const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                               const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                               uint8_t* seq, uint8_t* qual, int64_t* off, int* ticket) {
+  if (h && ((last_dur == nullptr) != (on_device == nullptr))) { h->err = "nrv_revise_reads_raw_begin: last_dur and on_device go together"; return NRV_E_INVALID; }
+  const MergeReq mr{bases, q_thr, seq, qual, off};
+  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, nullptr, nullptr, nullptr, nullptr, ticket, &mr);
+}
+
+int nrv_revise_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                         const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                         const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                         uint8_t* seq, uint8_t* qual, int64_t* off) {
+  int t = -1;
+  const int rc = nrv_revise_reads_raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                            seq, qual, off, &t);
+  return rc ? rc : nrv_reads_raw_end(h, t);
+}
+
 int nrv_reads_raw_end(nrv_handle* h, int ticket) {
   int rc = check_handle(h);
   if (rc) return rc;
@@ -2034,10 +2152,25 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
     const int rc2 = raw_enqueue(h, sl);
     h->h2 = h2; h->split = split;
     if (rc2) return rc2;
-    HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64 + sl.rows * kOutBytes, hipMemcpyDeviceToHost, h->stream));
+    if (sl.merge) {                                             // the merge again, in stream order behind the re-run it reads
+      if ((rc = poison_fill(h, sl.d_mrg, sl.cap_mrg, h->stream)) || (rc = merge_enqueue(h, slot_merge_args(h, sl)))) return rc;
+      HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipMemcpyAsync(sl.pin_mrg, sl.d_mrg, sl.m_dl, hipMemcpyDeviceToHost, h->stream));
+    } else {
+      HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64 + sl.rows * kOutBytes, hipMemcpyDeviceToHost, h->stream));
+    }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     sl.sat_seen = *(unsigned*)sl.pin_out;
     h->sat_reruns += 1;
+  }
+  if (sl.merge) {
+    const int64_t* off = (const int64_t*)sl.pin_mrg;
+    const int64_t total = off[sl.n_reads];
+    if (total < 0 || total > sl.N + sl.n) { h->err = "nrv_reads_raw_end: merged block out of range"; return NRV_E_HIP; }
+    memcpy(sl.off, off, ((size_t)sl.n_reads + 1) * 8);
+    memcpy(sl.seq, sl.pin_mrg + sl.m_seq, (size_t)total);
+    if (sl.want_q) memcpy(sl.qual, sl.pin_mrg + sl.m_qual, (size_t)total);
+    return NRV_OK;
   }
   const char* o = sl.pin_out + 64;
   const size_t n = (size_t)sl.n;
@@ -2125,6 +2258,73 @@ int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32
   if (rc) return rc;
   for (int r = 0; r < n_reads; ++r) { shift[r] = back[r].shift; scale[r] = back[r].scale; }
   for (int64_t e = 0; e < N; ++e) { feat12[2 * e] = feat[e * kFeat + 1]; feat12[2 * e + 1] = feat[e * kFeat + 2]; }
+  return NRV_OK;
+}
+
+int nrv_merge_calls(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                    const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (n_reads < 0 || n_win < 0 || !off || (n_reads > 0 && !ev_len)) { h->err = "nrv_merge_calls: bad arguments"; return NRV_E_INVALID; }
+  std::vector<nrv_read_desc> rd((size_t)n_reads);
+  int64_t N = 0;
+  for (int r = 0; r < n_reads; ++r) {
+    if (ev_len[r] < 0 || N + ev_len[r] >= ((int64_t)1 << 31)) { h->err = "nrv_merge_calls: a negative read length (or 2^31 events and more)"; return NRV_E_INVALID; }
+    rd[r] = nrv_read_desc{0, 0, N, ev_len[r], 0., 0.};
+    N += ev_len[r];
+  }
+  const int T = h->T;
+  const int64_t n = N - T > 0 ? N - T : 0;
+  const bool want_q = q_thr != nullptr && qual != nullptr;
+  if (n_win != n || (N > 0 && (!bases || !seq)) || (n > 0 && (!a1 || !a2 || (want_q && (!p1 || !p2))))) {
+    h->err = "nrv_merge_calls: n_win is not sum(ev_len) - T, or a null array";
+    return NRV_E_INVALID;
+  }
+  if (n == 0) { merge_nothing(bases, rd.data(), n_reads, N, seq, want_q ? qual : nullptr, off); return NRV_OK; }
+  // one block of its own: [reads | bases | a1 | a2 | p1 | p2 | merged block]
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const MergeLayout m = merge_layout(N, n, n_reads);
+  const size_t o_b = up((size_t)n_reads * sizeof(SegRead)), o_a1 = o_b + up((size_t)N), o_a2 = o_a1 + up((size_t)n);
+  const size_t o_p1 = o_a2 + up((size_t)n), o_p2 = o_p1 + (want_q ? up((size_t)n * 24) : 0), o_m = o_p2 + (want_q ? up((size_t)n * 20) : 0);
+  const size_t bytes = o_m + m.bytes;
+  char* d = nullptr;
+  HIPCHK(h, hipMalloc((void**)&d, bytes));
+  std::vector<char> back(m.dl);
+  auto run = [&]() -> int {
+    int rc2 = poison_fill(h, d, bytes, h->stream);
+    if (rc2) return rc2;
+    HIPCHK(h, hipMemcpyAsync(d, rd.data(), (size_t)n_reads * sizeof(SegRead), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d + o_b, bases, (size_t)N, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d + o_a1, a1, (size_t)n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d + o_a2, a2, (size_t)n, hipMemcpyHostToDevice, h->stream));
+    if (want_q) {
+      HIPCHK(h, hipMemcpyAsync(d + o_p1, p1, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(d + o_p2, p2, (size_t)n * 20, hipMemcpyHostToDevice, h->stream));
+    }
+    MergeArgs a;
+    a.reads = (const SegRead*)d; a.n_reads = n_reads; a.T = T; a.N = N;
+    a.bases = (const unsigned char*)(d + o_b);
+    a.a1 = (const signed char*)(d + o_a1); a.a2 = (const signed char*)(d + o_a2);
+    a.p1 = want_q ? (const float*)(d + o_p1) : nullptr; a.p2 = want_q ? (const float*)(d + o_p2) : nullptr;
+    a.rec = (unsigned*)(d + o_m + m.rec); a.tile = (unsigned long long*)(d + o_m + m.tile);
+    a.off = (long long*)(d + o_m); a.seq = (unsigned char*)(d + o_m + m.seq);
+    a.qual = want_q ? (unsigned char*)(d + o_m + m.qual) : nullptr;
+    memset(a.thr, 0, sizeof a.thr);
+    if (want_q) memcpy(a.thr, q_thr, sizeof a.thr);
+    if ((rc2 = merge_enqueue(h, a))) return rc2;
+    HIPCHK(h, hipMemcpyAsync(back.data(), d + o_m, m.dl, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return NRV_OK;
+  };
+  rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  (void)hipFree(d);
+  if (rc) return rc;
+  const int64_t total = ((const int64_t*)back.data())[n_reads];
+  if (total < 0 || total > N + n) { h->err = "nrv_merge_calls: merged block out of range"; return NRV_E_HIP; }
+  memcpy(off, back.data(), ((size_t)n_reads + 1) * 8);
+  memcpy(seq, back.data() + m.seq, (size_t)total);
+  if (want_q) memcpy(qual, back.data() + m.qual, (size_t)total);
   return NRV_OK;
 }
 

@@ -800,6 +800,8 @@ int nrvh_load_bundle_ex(const char* const* paths, int n, const char* group, cons
  * hoststage.merge_calls / expand_calls / revise_read (the decode of output_handeler.py:83, 104-122 with SURVEY 8a a16's
  * fix) + fasta_record / fastq_record (output_handeler.py:26-62, byte for byte, including the missing newline before '+')
  * + cli.write_read's temporary-then-rename.  qc: one Phred character per window (FASTQ) or NULL (FASTA). */
+static unsigned long tmp_serial;         /* one counter for every finisher of the process */
+
 int nrvh_finish_read(const char* bases, int64_t n_ev, const int8_t* a1, const int8_t* a2, int64_t n_win, int T,
                      const uint8_t* qc, const char* name, const char* dst, int fastq, int64_t* n_written) {
   if (!bases || n_ev < 0 || n_win < 0 || (n_win > 0 && (!a1 || !a2)) || !name || !dst || T < 1) return NRVH_E_ARG;
@@ -837,7 +839,6 @@ int nrvh_finish_read(const char* bases, int64_t n_ev, const int8_t* a1, const in
   free(qual);
   /* the finishers are threads of one process and two reads can map to one dst (the stem ends at the first '.'): the
    * temporary is unique per CALL, so the writes never interleave and the last rename wins whole */
-  static unsigned long tmp_serial;
   char tmp[4200];
   if (snprintf(tmp, sizeof tmp, "%s.tmp%ld_%lu", dst, (long)getpid(), __atomic_add_fetch(&tmp_serial, 1, __ATOMIC_RELAXED)) >= (int)sizeof tmp) { free(text); return NRVH_E_ARG; }
   FILE* fp = fopen(tmp, "wb");
@@ -866,6 +867,75 @@ int nrvh_finish_bundle(const char* bases, const int64_t* ev_len, int n_reads, co
                                  fastq, &nw);
     if (n_written) n_written[r] = nw;
     e0 += el;
+  }
+  return NRVH_OK;
+}
+
+/* ---- revised reads that are ALREADY merged (nrv_revise_reads_raw, include/nanorev.h) -> their output files ---------------------
+ * The record and the temporary-then-rename of nrvh_finish_read, from a ready sequence: read r is seq[off[r] .. off[r + 1]) with
+ * qual alongside.  n_seq is what seq / qual hold: an offset pair that is not ascending or leaves [0, n_seq] refuses that read
+ * alone.  FASTQ without qual: '#' per base, as cli.write_read does. */
+static int write_record(const char* name, const uint8_t* seq, const uint8_t* qual, int64_t n, const char* dst, int fastq) {
+  const size_t nl = strlen(name);
+  const size_t cap = nl + 2 + (size_t)n + (fastq ? 2 + (size_t)n : 0) + 1;
+  char* text = (char*)malloc(cap);
+  if (!text) return NRVH_E_IO;
+  size_t p = 0;
+  text[p++] = fastq ? '@' : '>';
+  memcpy(text + p, name, nl); p += nl;
+  text[p++] = '\n';
+  if (n > 0) memcpy(text + p, seq, (size_t)n);
+  p += (size_t)n;
+  if (fastq) {
+    text[p++] = '+'; text[p++] = '\n';                    /* (no newline in front of '+': output_handeler.py:48-62) */
+    if (n > 0) { if (qual) memcpy(text + p, qual, (size_t)n); else memset(text + p, '#', (size_t)n); }
+    p += (size_t)n;
+  }
+  char tmp[4200];
+  if (snprintf(tmp, sizeof tmp, "%s.tmp%ld_%lu", dst, (long)getpid(), __atomic_add_fetch(&tmp_serial, 1, __ATOMIC_RELAXED)) >= (int)sizeof tmp) { free(text); return NRVH_E_ARG; }
+  FILE* fp = fopen(tmp, "wb");
+  if (!fp) { free(text); return NRVH_E_IO; }
+  const int ok = fwrite(text, 1, p, fp) == p;
+  const int ok2 = fclose(fp) == 0;
+  free(text);
+  if (!ok || !ok2 || rename(tmp, dst) != 0) { remove(tmp); return NRVH_E_IO; }
+  return NRVH_OK;
+}
+
+int nrvh_write_records(const uint8_t* seq, const uint8_t* qual, int64_t n_seq, const int64_t* off, int n_reads,
+                       const char* const* names, const char* const* dsts, int fastq, int64_t* n_written, int32_t* status) {
+  if (n_reads < 0 || n_seq < 0 || !status || (n_reads > 0 && (!off || !names || !dsts)) || (n_seq > 0 && !seq)) return NRVH_E_ARG;
+  for (int r = 0; r < n_reads; ++r) {
+    const int64_t a = off[r], b = off[r + 1];
+    if (n_written) n_written[r] = 0;
+    if (a < 0 || b < a || b > n_seq || !names[r] || !dsts[r]) { status[r] = NRVH_E_ARG; continue; }
+    status[r] = write_record(names[r], seq ? seq + a : 0, qual ? qual + a : 0, b - a, dsts[r], fastq);
+    if (status[r] == NRVH_OK && n_written) n_written[r] = b - a;
+  }
+  return NRVH_OK;
+}
+
+/* ---- the Phred steps of cli.phred_chars as a function of the f32 confidence ------------------------------------------------------
+ * q(c) = clip(round_half_even(-10 log10(max(1 - c, 1e-4))), 1, 40) with c widened to f64: a monotone step function on [0, 1].
+ * thr[k - 2] = the smallest f32 c with q(c) >= k, k = 2 .. 40, by bisection over the bit patterns (ascending with the value
+ * for non-negative floats). */
+static int phred_of(float c) {
+  double d = 1.0 - (double)c;
+  if (!(d >= 1e-4)) d = 1e-4;
+  const double v = rint(-10.0 * log10(d));                /* round half to even in the default rounding mode, like np.round */
+  return v < 1.0 ? 1 : (v > 40.0 ? 40 : (int)v);
+}
+int nrvh_phred_thresholds(float thr[39]) {
+  if (!thr) return NRVH_E_ARG;
+  for (int k = 2; k <= 40; ++k) {
+    uint32_t lo = 0, hi = 0x3F800000u;                    /* q(0.0) = 1 < k <= 40 = q(1.0) */
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      float c;
+      memcpy(&c, &mid, 4);
+      if (phred_of(c) >= k) hi = mid; else lo = mid;
+    }
+    memcpy(&thr[k - 2], &hi, 4);
   }
   return NRVH_OK;
 }

@@ -34,6 +34,7 @@ SYMBOLS = [
     "nrv_window", "nrv_set_precision", "nrv_get_precision", "nrv_predict_reads_raw", "nrv_reads_raw_begin", "nrv_reads_raw_end", "nrv_segment_reads",
     "nrv_device_count", "nrv_saturated", "nrv_prof_overhead",
     "nrv_reads_raw_stats_begin", "nrv_predict_reads_raw_stats", "nrv_read_stats",
+    "nrv_revise_reads_raw_begin", "nrv_revise_reads_raw", "nrv_merge_calls",
 ]
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "f16x2": 2}
@@ -146,6 +147,13 @@ def load_library(path: Optional[str] = None):
     lib.nrv_reads_raw_stats_begin.restype = C.c_int
     lib.nrv_read_stats.argtypes = [vp, i16p, C.c_int64, i32p, C.c_int64, rdp, C.c_int, i32p, dp, dp, dp, dp, fp]
     lib.nrv_read_stats.restype = C.c_int
+    i64p = C.POINTER(C.c_int64)
+    lib.nrv_revise_reads_raw.argtypes = [vp, i16p, C.c_int64, i32p, fp, C.c_int64, rdp, C.c_int, i32p, u8p, u8p, fp, u8p, u8p, i64p]
+    lib.nrv_revise_reads_raw.restype = C.c_int
+    lib.nrv_revise_reads_raw_begin.argtypes = lib.nrv_revise_reads_raw.argtypes + [C.POINTER(C.c_int)]
+    lib.nrv_revise_reads_raw_begin.restype = C.c_int
+    lib.nrv_merge_calls.argtypes = [vp, u8p, i64p, C.c_int, i8p, i8p, fp, fp, C.c_int64, fp, u8p, u8p, i64p]
+    lib.nrv_merge_calls.restype = C.c_int
     lib.nrv_prof_overhead.argtypes = [vp, C.POINTER(C.c_double)]
     lib.nrv_saturated.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.nrv_set_precision.argtypes = [vp, C.c_int]
@@ -334,9 +342,55 @@ class Reviser:
             raise ValueError("last_dur / on_device must have one entry per read")
         return tuple(packed[:7]) + (ld, on)
 
+    @staticmethod
+    def with_device_merge(packed, bases, fastq, q_thr=None):
+        """The packed form of a call whose merge runs on the device as well (include/nanorev.h nrv_revise_reads_raw_begin):
+        what `pack_reads_raw` / `pack_bundle` returned, with or without `with_device_stats`, plus the reads' original bases
+        (S1 or uint8 [N], concatenated like the per-event arrays) and, for fastq, the 39 Phred thresholds (default:
+        cli.phred_thresholds()).  `run_packed_raw` / `begin_packed_raw` + `end_packed_raw` then return (seq uint8[total],
+        qual uint8[total] | None, off int64[n_reads + 1]) - read r is seq[off[r]:off[r + 1]] - instead of (p1, p2, a1, a2):
+        the bytes of hoststage.emit_calls on the call's outputs."""
+        from .hostlib import bases_u8
+        nr, N = packed[4], packed[5]
+        b = bases_u8(bases)
+        if b.size != N:
+            raise ValueError("bases must have one entry per event")
+        thr = None
+        if fastq:
+            if q_thr is None:
+                from .cli import phred_thresholds
+                q_thr = phred_thresholds()
+            thr = np.ascontiguousarray(q_thr, dtype=np.float32).reshape(-1)
+            if thr.size != 39:
+                raise ValueError("q_thr must have 39 entries")
+        n = packed[6][2].shape[0]
+        cap = max(N + n, 1)
+        out = (np.empty(cap, np.uint8), np.empty(cap, np.uint8) if fastq else None, np.zeros(nr + 1, np.int64))
+        ld, on = (packed[7], packed[8]) if len(packed) == 9 else (None, None)
+        return tuple(packed[:7]) + (ld, on, b, thr, out)
+
+    def _revise_args(self, packed):
+        raw, st, feat, descs, nr, N, _, ld, on, b, thr, (seq, qual, off) = packed
+        fp, u8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+        return [self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)),
+                feat.ctypes.data_as(fp), N, descs, nr,
+                ld.ctypes.data_as(C.POINTER(C.c_int32)) if ld is not None else None, on.ctypes.data_as(u8p) if on is not None else None,
+                b.ctypes.data_as(u8p), thr.ctypes.data_as(fp) if thr is not None else None, seq.ctypes.data_as(u8p),
+                qual.ctypes.data_as(u8p) if qual is not None else None, off.ctypes.data_as(C.POINTER(C.c_int64))]
+
+    @staticmethod
+    def _trim_merged(out):
+        seq, qual, off = out
+        total = int(off[-1])
+        return seq[:total], (qual[:total] if qual is not None else None), off
+
     def run_packed_raw(self, packed):
-        """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared (or `with_device_stats` extended)."""
+        """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared (or `with_device_stats` /
+        `with_device_merge` extended)."""
         fp, i8p = C.POINTER(C.c_float), C.POINTER(C.c_int8)
+        if len(packed) == 12:                         # `with_device_merge`: nrv_revise_reads_raw
+            self._check(self._lib.nrv_revise_reads_raw(*self._revise_args(packed)))
+            return self._trim_merged(packed[11])
         if len(packed) == 9:
             raw, st, feat, descs, nr, N, (p1, p2, a1, a2), ld, on = packed
             self._check(self._lib.nrv_predict_reads_raw_stats(
@@ -356,6 +410,9 @@ class Reviser:
         ticket for `end_packed_raw`.  At most two calls in flight; the OUTPUT arrays of `packed` must stay alive until the end."""
         fp, i8p = C.POINTER(C.c_float), C.POINTER(C.c_int8)
         t = C.c_int(-1)
+        if len(packed) == 12:                         # `with_device_merge`: nrv_revise_reads_raw_begin
+            self._check(self._lib.nrv_revise_reads_raw_begin(*self._revise_args(packed), C.byref(t)))
+            return t.value, packed[11], "merged"
         if len(packed) == 9:                          # `with_device_stats`: nrv_reads_raw_stats_begin
             raw, st, feat, descs, nr, N, (p1, p2, a1, a2), ld, on = packed
             self._check(self._lib.nrv_reads_raw_stats_begin(
@@ -371,10 +428,11 @@ class Reviser:
         return t.value, (p1, p2, a1, a2)
 
     def end_packed_raw(self, ticket):
-        """Second half: waits for the call `ticket` names and returns its (p1, p2, a1, a2)."""
-        t, out = ticket
+        """Second half: waits for the call `ticket` names and returns its (p1, p2, a1, a2) - or, for a `with_device_merge`
+        call, its (seq, qual, off)."""
+        t, out = ticket[:2]
         self._check(self._lib.nrv_reads_raw_end(self._h, t))
-        return out
+        return self._trim_merged(out) if len(ticket) == 3 else out
 
     def predict_reads_raw(self, raws, starts, feats, shifts, scales):
         """Reads given as raw int16 samples (from their first event on), int32 event starts, (N,6)
@@ -410,6 +468,33 @@ class Reviser:
             ld.ctypes.data_as(C.POINTER(C.c_int32)), shift.ctypes.data_as(dp), scale.ctypes.data_as(dp),
             mean.ctypes.data_as(dp), std.ctypes.data_as(dp), f12.ctypes.data_as(C.POINTER(C.c_float))))
         return shift, scale, mean, std, f12
+
+    def merge_calls_device(self, bases, ev_len, a1, a2, p1=None, p2=None, q_thr=None):
+        """The device-side merge alone (nrv_merge_calls) on calls the host supplies: bases S1 / uint8 [sum ev_len], ev_len per
+        read, a1 / a2 int8 [max(sum ev_len - T, 0)], and for a quality p1 (n, 6), p2 (n, 5) float32 with the 39 thresholds
+        q_thr.  Returns (seq, qual | None, off) - the bytes of hoststage.emit_calls."""
+        from .hostlib import bases_u8
+        b = bases_u8(bases)
+        el = np.ascontiguousarray(ev_len, dtype=np.int64).reshape(-1)
+        x1, x2 = np.ascontiguousarray(a1, dtype=np.int8).reshape(-1), np.ascontiguousarray(a2, dtype=np.int8).reshape(-1)
+        N, n = b.size, x1.size
+        if int(el.sum()) != N or x2.size != n:
+            raise ValueError("bases / ev_len / a1 / a2 do not match")
+        fp, u8p, i8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int8)
+        thr = q1 = q2 = None
+        if q_thr is not None:
+            thr = np.ascontiguousarray(q_thr, dtype=np.float32).reshape(-1)
+            q1, q2 = _as_f32(np.asarray(p1).reshape(-1, 6), (6,)), _as_f32(np.asarray(p2).reshape(-1, 5), (5,))
+            if thr.size != 39 or q1.shape[0] != n or q2.shape[0] != n:
+                raise ValueError("q_thr / p1 / p2 do not match")
+        cap = max(N + n, 1)
+        seq, qual, off = np.empty(cap, np.uint8), (np.empty(cap, np.uint8) if thr is not None else None), np.zeros(el.size + 1, np.int64)
+        self._check(self._lib.nrv_merge_calls(
+            self._h, b.ctypes.data_as(u8p), el.ctypes.data_as(C.POINTER(C.c_int64)), el.size, x1.ctypes.data_as(i8p), x2.ctypes.data_as(i8p),
+            q1.ctypes.data_as(fp) if q1 is not None else None, q2.ctypes.data_as(fp) if q2 is not None else None, n,
+            thr.ctypes.data_as(fp) if thr is not None else None, seq.ctypes.data_as(u8p),
+            qual.ctypes.data_as(u8p) if qual is not None else None, off.ctypes.data_as(C.POINTER(C.c_int64))))
+        return self._trim_merged((seq, qual, off))
 
     @staticmethod
     def _fingerprint(a):

@@ -14,7 +14,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libnanorev_host.so")
 SYMBOLS = ["nrvh_abi_version", "nrvh_event_stats", "nrvh_load_fast5", "nrvh_free_read", "nrvh_load_bundle",
-           "nrvh_free_bundle", "nrvh_finish_read", "nrvh_finish_bundle", "nrvh_load_fast5_ex", "nrvh_load_bundle_ex"]
+           "nrvh_free_bundle", "nrvh_finish_read", "nrvh_finish_bundle", "nrvh_load_fast5_ex", "nrvh_load_bundle_ex",
+           "nrvh_write_records", "nrvh_phred_thresholds"]
 _lib = None
 _tried = False
 
@@ -74,6 +75,13 @@ def load() -> Optional[C.CDLL]:
         lib.nrvh_event_stats.argtypes = [C.POINTER(C.c_int16), C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int32,
                                          C.POINTER(C.c_double), C.POINTER(C.c_double)]
         lib.nrvh_event_stats.restype = C.c_int
+        # the device-merge helpers are found by PRESENCE (the ABI version stays 3): a build without them keeps the host merge
+        if hasattr(lib, "nrvh_write_records") and hasattr(lib, "nrvh_phred_thresholds"):
+            lib.nrvh_write_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(C.c_char_p),
+                                               C.POINTER(C.c_char_p), C.c_int, C.c_void_p, C.c_void_p]
+            lib.nrvh_write_records.restype = C.c_int
+            lib.nrvh_phred_thresholds.argtypes = [C.c_void_p]
+            lib.nrvh_phred_thresholds.restype = C.c_int
         _lib = lib
     except OSError:
         _lib = None
@@ -256,3 +264,49 @@ def finish_bundle(bases, ev_len, a1, a2, T: int, qc, names, dsts, fastq: bool):
     if rc != OK:
         raise ValueError("finish_bundle: bad arguments")
     return nw, st
+
+
+def has_write_records() -> bool:
+    """True when the library is there AND has the device-merge helpers (nrvh_write_records, nrvh_phred_thresholds)."""
+    lib = load()
+    return lib is not None and hasattr(lib, "nrvh_write_records") and hasattr(lib, "nrvh_phred_thresholds")
+
+
+def bases_u8(bases) -> np.ndarray:
+    """The basecalls of a read or a bundle (S1[N], or already uint8) as contiguous uint8[N] ASCII codes, without a copy
+    where the array allows it: what the device merge uploads."""
+    b = np.asarray(bases)
+    if b.dtype != np.uint8:
+        b = np.ascontiguousarray(b, dtype="S1").view(np.uint8)
+    return np.ascontiguousarray(b).reshape(-1)
+
+
+def phred_thresholds():
+    """nrvh_phred_thresholds: float32[39], or None without the library / the symbol."""
+    if not has_write_records():
+        return None
+    thr = np.zeros(39, np.float32)
+    if load().nrvh_phred_thresholds(thr.ctypes.data) != OK:
+        return None
+    return thr
+
+
+def write_records(seq, qual, off, names, dsts, fastq: bool):
+    """The revised reads of one device-merge call (seq uint8[], qual uint8[] | None, off int64[R + 1]: Reviser.end_packed_raw)
+    -> their output files, in ONE native call.  Returns (n_written int64[R], status int32[R]); None without the library."""
+    if not has_write_records():
+        return None
+    sq = np.ascontiguousarray(seq, dtype=np.uint8)
+    ql = np.ascontiguousarray(qual, dtype=np.uint8) if qual is not None else None
+    of = np.ascontiguousarray(off, dtype=np.int64)
+    R = len(of) - 1
+    if R < 0 or len(names) != R or len(dsts) != R or (ql is not None and len(ql) < len(sq)):
+        raise ValueError("write_records: arrays do not match the read table")
+    nm = (C.c_char_p * max(R, 1))(*[n.encode("utf8") for n in names])
+    ds = (C.c_char_p * max(R, 1))(*[os.fsencode(d) for d in dsts])
+    nw, st = np.zeros(max(R, 1), np.int64), np.zeros(max(R, 1), np.int32)
+    rc = load().nrvh_write_records(sq.ctypes.data, ql.ctypes.data if ql is not None else None, len(sq), of.ctypes.data, R,
+                                   nm, ds, 1 if fastq else 0, nw.ctypes.data, st.ctypes.data)
+    if rc != OK:
+        raise ValueError("write_records: bad arguments")
+    return nw[:R], st[:R]

@@ -10,7 +10,7 @@
  * outcome of a mutated file must be a return code.
  *
  *   host_fuzz fuzz N SEED TMPDIR file.fast5 ...     N mutations per file and class mix below
- *   host_fuzz api TMPDIR file.fast5 ...             bundle + finisher entry points, argument edge cases
+ *   host_fuzz api TMPDIR file.fast5 ...             bundle + finisher + record-writer entry points, argument edge cases
  *   host_fuzz threads NTHREADS ITERS TMPDIR file.fast5 ...
  */
 #include "../../nanoreviser_amd/csrc/nrv_host.c"
@@ -423,6 +423,63 @@ static int mode_api(const char* tmpdir, int nfiles, char** files) {
     free(ev_len); free(nw); free(st); free(names); free(dsts); free(dbuf); free(a1); free(a2); free(qc);
   }
   nrvh_free_bundle(&b);
+  /* nrvh_write_records / nrvh_phred_thresholds: what a device-merge call hands over */
+  {
+    float thr[39];
+    if (nrvh_phred_thresholds(0) != NRVH_E_ARG || nrvh_phred_thresholds(thr) != NRVH_OK) abort();
+    for (int k = 1; k < 39; ++k) if (!(thr[k] > thr[k - 1])) abort();
+    if (!(thr[0] > 0.29f && thr[0] < 0.30f && thr[38] > 0.9998f && thr[38] < 1.0f)) abort();
+    uint8_t seq[64], qual[64];
+    for (int i = 0; i < 64; ++i) { seq[i] = (uint8_t)"ACGT"[i & 3]; qual[i] = (uint8_t)(34 + i % 40); }
+    char d0[600], d1[600], d2[600], d3[600];
+    snprintf(d0, sizeof d0, "%s/w0_out.fastq", tmpdir); snprintf(d1, sizeof d1, "%s/w1_out.fastq", tmpdir);
+    snprintf(d2, sizeof d2, "%s/w2_out.fastq", tmpdir); snprintf(d3, sizeof d3, "%s/w3_out.fastq", tmpdir);
+    const char* names[4] = {"a|||b", "", "n2", "n3"};
+    const char* dsts[4] = {d0, d1, d2, d3};
+    int64_t nw[4];
+    int32_t st[4];
+    /* zero reads (with and without arrays) */
+    if (nrvh_write_records(seq, qual, 64, 0, 0, 0, 0, 1, 0, st) != NRVH_OK) abort();
+    if (nrvh_write_records(0, 0, 0, 0, 0, names, dsts, 0, nw, st) != NRVH_OK) abort();
+    if (nrvh_write_records(seq, qual, 64, 0, 1, names, dsts, 0, nw, st) != NRVH_E_ARG) abort();
+    if (nrvh_write_records(seq, qual, 64, (const int64_t[]){0, 1}, 1, names, dsts, 0, nw, 0) != NRVH_E_ARG) abort();
+    if (nrvh_write_records(seq, qual, -1, (const int64_t[]){0, 1}, 1, names, dsts, 0, nw, st) != NRVH_E_ARG) abort();
+    /* an empty read between two others, exactly to the end of the buffer; FASTQ and FASTA; NULL n_written */
+    const int64_t off_ok[5] = {0, 20, 20, 63, 64};
+    if (nrvh_write_records(seq, qual, 64, off_ok, 4, names, dsts, 1, nw, st) != NRVH_OK) abort();
+    for (int r = 0; r < 4; ++r) if (st[r] != NRVH_OK || nw[r] != off_ok[r + 1] - off_ok[r]) abort();
+    {
+      long n = 0;
+      uint8_t* t = slurp(d1, &n);                                       /* the empty read: "@\n+\n" */
+      if (!t || n != 4 || memcmp(t, "@\n+\n", 4)) abort();
+      free(t);
+      t = slurp(d0, &n);
+      if (!t || n != 1 + 5 + 1 + 20 + 2 + 20 || memcmp(t + 7, seq, 20) || memcmp(t + 29, qual, 20)) abort();
+      free(t);
+    }
+    if (nrvh_write_records(seq, 0, 64, off_ok, 4, names, dsts, 0, 0, st) != NRVH_OK || st[3] != NRVH_OK) abort();
+    /* NULL qual with fastq != 0: '#' per base */
+    if (nrvh_write_records(seq, 0, 64, off_ok, 4, names, dsts, 1, nw, st) != NRVH_OK || st[0] != NRVH_OK) abort();
+    {
+      long n = 0;
+      uint8_t* t = slurp(d0, &n);
+      if (!t || n != 1 + 5 + 1 + 20 + 2 + 20) abort();
+      for (int i = 0; i < 20; ++i) if (t[29 + i] != '#') abort();
+      free(t);
+    }
+    /* off not monotone / negative / past the buffer: those reads alone are refused, nothing is read outside seq */
+    const int64_t off_bad[5] = {0, 30, 10, 64, 65};
+    if (nrvh_write_records(seq, qual, 64, off_bad, 4, names, dsts, 1, nw, st) != NRVH_OK) abort();
+    if (st[0] != NRVH_OK || st[1] != NRVH_E_ARG || st[2] != NRVH_OK || st[3] != NRVH_E_ARG || nw[1] != 0 || nw[3] != 0) abort();
+    const int64_t off_wild[5] = {-1, 3, INT64_MAX, INT64_MIN, 4};
+    if (nrvh_write_records(seq, qual, 64, off_wild, 4, names, dsts, 0, nw, st) != NRVH_OK) abort();
+    for (int r = 0; r < 4; ++r) if (st[r] != NRVH_E_ARG) abort();
+    /* an unwritable destination for one read of three, a NULL name for another */
+    const char* dsts2[3] = {d0, "/nonexistent/dir/x", d2};
+    const char* names2[3] = {"x", "y", 0};
+    if (nrvh_write_records(seq, qual, 64, off_ok, 3, names2, dsts2, 1, nw, st) != NRVH_OK) abort();
+    if (st[0] != NRVH_OK || st[1] != NRVH_E_IO || st[2] != NRVH_E_ARG) abort();
+  }
   /* nrvh_event_stats: empty, clipped and out-of-range events */
   {
     int16_t raw[40];
@@ -458,6 +515,13 @@ static void* thread_main(void* p) {
     for (int64_t i = 0; i < nwin; ++i) a[i] = (int8_t)(2 + (i + j->id) % 4);
     int64_t nw;
     if (nrvh_finish_read(b.bases, el, a, a, nwin, 11, 0, "t", it % 3 ? own : shared, 0, &nw) != NRVH_OK) j->failed = 1;
+    {                                                                   /* the same bases through the record writer */
+      const int64_t off[2] = {0, el};
+      const char* nm[1] = {"t"};
+      const char* ds[1] = {it % 3 ? shared : own};
+      int32_t st1 = -1;
+      if (nrvh_write_records((const uint8_t*)b.bases, 0, el, off, 1, nm, ds, 0, &nw, &st1) != NRVH_OK || st1 != NRVH_OK || nw != el) j->failed = 1;
+    }
     free(a);
     nrvh_free_bundle(&b);
   }
