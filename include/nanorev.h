@@ -172,6 +172,47 @@ int nrv_revise_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, const
 int nrv_merge_calls(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
                     const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off);
 
+/* The same revised reads WITH a per-read revision report (opt-in; nothing above changes): what the merge did to each read,
+ * counted on the device behind the merge - the only place where a call made this way still has p1 / p2 / a1 / a2.  The
+ * arguments of nrv_revise_reads_raw_begin up to `off`, then
+ *   tie_eps   a window is a near-tie when, for model 1 or model 2, NOT (top1 - top2 >= tie_eps), top1 / top2 the largest and the
+ *             second largest value of its softmax row (a duplicated maximum gives 0; f32 arithmetic; a NaN row is a near-tie).
+ *             4e-4 is what two precision modes that each meet the parity bar can differ by;
+ *   report    uint64 [n_reads][NRV_REPORT_COLS], filled by nrv_reads_raw_end.  With o = (T - 1) / 2 and n_r = max(ev_len - T, 0),
+ *             window i of a read revises its event o + i.  Columns, per read:
+ *               0 bases_in = ev_len   1 windows = n_r   2 bases_out = off[r + 1] - off[r]   3 edge = ev_len - n_r (events kept as they are)
+ *               4 confirmed    both models agree on a base, and it is the original one
+ *               5 substituted  both models agree on a base, another one
+ *               6 inserted     model1 'D', model2 a base: the original base plus model2's
+ *               7 deleted      both '-': nothing emitted
+ *               8 undecided    none of the three: the original base kept            (4 .. 8 add up to column 1)
+ *               9 .. 14  histogram of model1's class clipped to 0 .. 5;  15 .. 19  of model2's class clipped to 0 .. 4
+ *               20 agree2    windows whose model2 base (label a2 + 1 clipped to 0 .. 5) is the original base
+ *               21 near_tie  see tie_eps
+ *               22 q_sum     sum of (quality character - 33) over the read's output characters; 0 without q_thr / qual
+ *               23 reserved, 0
+ * hoststage.revision_report is the definition; the counts are integers, so the block is that function's on the outputs of
+ * nrv_predict_reads_raw bit for bit, in every precision mode and whatever order the workgroups ran in.  seq / qual / off are
+ * those of nrv_revise_reads_raw_begin.  N <= T: the report is filled on the host (edge = bases_in = bases_out = ev_len;
+ * with a quality q_sum = 2 * ev_len, every character being '#', as the definition has it; everything else 0).
+ * Tickets, the two-calls-in-flight rule, the failure paths and the range-guard re-run (which zeroes the block and counts again)
+ * are those of nrv_revise_reads_raw_begin; `report` must stay valid until nrv_reads_raw_end.
+ * nrv_revise_reads_raw_report IS _report_begin + _end. */
+#define NRV_REPORT_COLS 24
+int nrv_revise_reads_raw_report_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                      const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                      const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                      uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report, int* ticket);
+int nrv_revise_reads_raw_report(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report);
+/* nrv_merge_calls with the report, by the kernel nrv_revise_reads_raw_report_begin runs: p1 / p2 may be given without q_thr
+ * (near_tie is then filled and q_sum 0); without p1 / p2 near_tie is 0.  The twin used by the parity tests. */
+int nrv_merge_calls_report(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                           const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                           float tie_eps, uint64_t* report);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

@@ -104,9 +104,21 @@ def get_args(argv: Optional[Sequence[str]] = None):
                         "Python fallback reader, NRV_CLI_PIPELINE=0, several engines per device, reads whose window range is "
                         "split over GPU workers, a library without the new entry points and the per-read retry after a failed "
                         "call keep the host merge")
+    p.add_argument("--report", dest="report", default=None, metavar="FILE",
+                   help="write a per-read revision report to FILE (also NRV_REPORT=FILE): a TSV with one header line, one line "
+                        "per input read sorted by file name - name, status (revised / unrevised), bases in / out, edge bases, "
+                        "windows confirmed / substituted / inserted / deleted / undecided, the class histograms of both models, "
+                        "how often model 2 agrees with the basecaller, calls on a softmax near-tie, the sum of the qualities - "
+                        "and a last line #total with the sums over the revised reads.  With --device_merge the numbers are "
+                        "counted on the GPU behind the merge, everywhere else by the host stage from the calls it holds: the "
+                        "same file byte for byte.  Off by default; without it nothing changes")
+    p.add_argument("--report_tie_eps", dest="report_tie_eps", type=float, default=hs.REPORT_TIE_EPS,
+                   help="a call is a near-tie when top1 - top2 of either model's softmax row is below this (default 4e-4: what two "
+                        "precision modes that both meet the parity bar can differ by)")
     a = p.parse_args(argv)
     a.device_stats = bool(a.device_stats) or device_stats_env()
     a.device_merge = bool(a.device_merge) or device_merge_env()
+    a.report = a.report or (os.environ.get("NRV_REPORT", "").strip() or None)
     if a.virsion:
         print(f"The virsion of NanoReviser : {VERSION} ")
         raise SystemExit(0)
@@ -505,9 +517,118 @@ def _write_records_native(spec, fns, seq, qual, off):
         return [(0, repr(e))] * len(fns)
 
 
+REPORT_HEADER = "name\tstatus\t" + "\t".join(hs.REPORT_NAMES)
+
+
+def report_rows(T, bases, ev_len, p1, p2, a1, a2, want_qual, tie_eps):
+    """--report on the host: `hoststage.revision_report` on calls the host holds, with the quality characters the writers use
+    (FASTQ: `phred_chars`; FASTA: none).  uint64[len(ev_len)][24]."""
+    qc = None
+    if want_qual:
+        qc = phred_chars(p1, p2, a1, a2) if len(a1) else np.zeros(0, np.uint8)
+    return hs.revision_report(hostlib.bases_u8(bases), ev_len, a1, a2, p1, p2, qc, T, tie_eps)
+
+
+def unrevised_row(n_written: int) -> np.ndarray:
+    """The report row of a read written unrevised: bases_in = bases_out = edge = what was written, zeros elsewhere."""
+    row = np.zeros(hs.REPORT_COLS, np.uint64)
+    row[0] = row[2] = row[3] = max(int(n_written), 0)
+    return row
+
+
+def written_length(path: str) -> int:
+    """Bases of the one record in an output file (its second line); 0 when there is none."""
+    try:
+        with open(path, "rb") as fp:
+            fp.readline()
+            return len(fp.readline().rstrip(b"\r\n"))
+    except OSError:
+        return 0
+
+
+class ReportPart:
+    """One process' share of the --report file: a line per read, appended and flushed as the read's output becomes final (so a
+    worker that dies leaves the lines of what it finished).  `merge_report` puts the parts together."""
+
+    def __init__(self, path: Optional[str]):
+        import threading
+        self.path, self._lock, self._fp = path, threading.Lock(), None
+
+    def __bool__(self):
+        return self.path is not None
+
+    def add(self, fn: str, revised: bool, row):
+        if self.path is None:
+            return
+        line = fn + "\t" + ("revised" if revised else "unrevised") + "\t" + "\t".join(str(int(v)) for v in np.asarray(row)[:23]) + "\n"
+        with self._lock:
+            if self._fp is None:
+                self._fp = open(self.path, "a")
+            self._fp.write(line)
+            self._fp.flush()
+
+    def close(self):
+        with self._lock:
+            if self._fp is not None:
+                self._fp.close()
+                self._fp = None
+
+
+def report_part_path(report: str, rank) -> str:
+    return f"{report}.part{rank}"
+
+
+def clear_report_parts(report: str):
+    import glob
+    for f in glob.glob(glob.escape(report) + ".part*"):
+        try:
+            os.remove(f)
+        except OSError:
+            pass
+
+
+def merge_report(report: str, names: Sequence[str], log: Callable[[str], None] = print):
+    """Parent side of --report: the parts in the order they were written (a later line for the same read wins: the parent's
+    own part comes last), one line per read of `names` sorted by file name, `#total` = the sums over the revised reads; the
+    file appears by rename and the parts are removed."""
+    import glob
+    rows = {}
+    parts = sorted(glob.glob(glob.escape(report) + ".part*"), key=lambda f: (f.endswith(".partparent"), f))
+    for f in parts:
+        with open(f) as fp:
+            for ln in fp:
+                c = ln.rstrip("\n").split("\t")
+                if ln.endswith("\n") and len(c) == 2 + 23:           # a line cut short by a dying worker is not a line
+                    rows[c[0]] = c
+    total = [0] * 23
+    out = [REPORT_HEADER]
+    for fn in sorted(names):
+        c = rows.get(fn)
+        if c is None:                                               # no process accounted for it: nothing was written
+            log(f"[！！！Warning] --report: no record for {fn}")
+            c = [fn, "unrevised"] + ["0"] * 23
+        out.append("\t".join(c))
+        if c[1] == "revised":
+            total = [t + int(v) for t, v in zip(total, c[2:])]
+    out.append("#total\trevised\t" + "\t".join(str(t) for t in total))
+    d = os.path.dirname(report)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    tmp = f"{report}.tmp{os.getpid()}"
+    with open(tmp, "w") as fp:
+        fp.write("\n".join(out) + "\n")
+    os.replace(tmp, report)
+    for f in parts:
+        try:
+            os.remove(f)
+        except OSError:
+            pass
+
+
 def _host_merge_form(packed):
-    """A `with_device_merge` tuple back in the form whose call returns (p1, p2, a1, a2): for the paths that keep the host merge."""
-    if packed is None or len(packed) != 12:
+    """A `with_device_merge` / `with_device_report` tuple back in the form whose call returns (p1, p2, a1, a2): for the paths
+    that keep the host merge."""
+    if packed is None or len(packed) not in (12, 14):
         return packed
     return tuple(packed[:7]) if packed[7] is None else tuple(packed[:9])
 
@@ -567,7 +688,7 @@ def parser_pool_size(threads: int, cores: int, gpu_workers: int, n_files: int, n
 
 def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None],
                   on_file: Optional[Callable[[str, bool], None]] = None, gpu_workers: int = 1,
-                  core_share: Optional[int] = None) -> dict:
+                  core_share: Optional[int] = None, report_part: Optional[str] = None) -> dict:
     """Revise `files` (names inside args.fast5_base_dir) with one engine.  The host stage (HDF5
     parsing, event collapse, signal segmentation) runs in worker PROCESSES (--thread of them, capped
     at the core count) that stay a bounded number of reads ahead of the device.
@@ -576,8 +697,12 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
     gpu_workers: how many such calls run on this host at the same time (one per GPU, `run_workers`): the cores are
     SHARED, so each call's parser pool gets usable_cores() // gpu_workers of them - eight workers on a 16-core cgroup
     start 8 x 2 parser processes, not 8 x 16.  core_share: this call's cores, when the caller has already
-    divided them (a GPU worker pinned to its NUMA slice: `_worker`)."""
+    divided them (a GPU worker pinned to its NUMA slice: `_worker`).  report_part (--report): the file this call appends
+    one line per read to, ahead of on_file (`ReportPart`)."""
     stats = {"reads": 0, "bases": 0, "failed": [], "host_s": 0.0, "engine_s": 0.0}
+    report = ReportPart(report_part)
+    rep_rows = {}                                     # fn -> the row of a read whose output is not final yet
+    tie_eps = float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS))
     # NRV_CLI_TRACE=1: where the wall time of this call goes (first device call, engine idle gaps, tail), to the log
     trace, t_start = ([] if os.environ.get("NRV_CLI_TRACE") else None), time.perf_counter()
     if trace is not None:
@@ -681,15 +806,21 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
     def fallback(fn, rt, fq, e):                      # NanoReviser.py:146-152 / :173-179
         stats["failed"].append(fn)
         log(f"[！！！Error] revising {fn.split('.')[0]}: {e}; writing the original basecalls")
+        nw = 0
         try:
             if args.output_format == "fastq" and fq is not None:
                 b, q = hs.trim_fastq(fq)
                 write_read(args, fn, b, q)
+                nw = len(b)
             else:
                 orig = "".join(x.decode() for x in np.asarray(rt.bases).tolist())
                 write_read(args, fn, orig, None)
+                nw = len(orig)
         except Exception as e2:
             log(f"[！！！Error] stroring : {fn.split('.')[0]}_out.{args.output_format}...... {e2}")
+        if report:
+            rep_rows.pop(fn, None)
+            report.add(fn, False, unrevised_row(nw))
         note(fn, False)
 
     want_qual = args.output_format == "fastq"
@@ -699,6 +830,11 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
 
     def finished(fn, nb):
         stats["bases"] += nb
+        if report:
+            row = rep_rows.pop(fn, None)
+            if row is None:                           # cannot happen: every path that finishes a read stashes its row first
+                log(f"[！！！Warning] --report: no counts for {fn}")
+            report.add(fn, row is not None, row if row is not None else unrevised_row(nb))
         if not args.test_mode:
             log(f"[p:::] {fn.split('.')[0]}_out.{args.output_format} was saved......")
         else:
@@ -714,6 +850,8 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                 fallback(fn, rt, fq, c)
                 continue
             try:
+                if report:
+                    rep_rows[fn] = report_rows(reviser.T, rt.bases, [len(np.asarray(rt.bases))], *c, want_qual, tie_eps)[0]
                 if pool is not None:
                     p1, p2, a1, a2 = c
                     qc = phred_chars(p1, p2, a1, a2) if want_qual and len(a1) else None
@@ -746,6 +884,9 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
         reviser = box["rv"]
         try:
             p1, p2, a1, a2 = outs
+            if report:
+                rows = report_rows(reviser.T, bundle["bases"], bundle["meta"][:, 1].astype(np.int64), p1, p2, a1, a2, want_qual, tie_eps)
+                rep_rows.update((fn, rows[i]) for i, (fn, _, _) in enumerate(batch))
             qc = phred_chars(p1, p2, a1, a2) if want_qual and len(a1) else None
             fut = pool.submit(_finish_bundle_native, spec, reviser.T, [fn for fn, _, _ in batch], bundle["bases"],
                               bundle["meta"][:, 1].astype(np.int64), a1, a2, qc)
@@ -757,7 +898,9 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
     def finish_merged(batch, outs):
         """Finisher thread, --device_merge: the call came back as revised reads; their records and files are one pool task."""
         try:
-            seq, qual, off = outs
+            seq, qual, off = outs[:3]
+            if report:                                # a `with_device_report` call: the rows were counted behind the merge
+                rep_rows.update((fn, outs[3][i]) for i, (fn, _, _) in enumerate(batch))
             fut = pool.submit(_write_records_native, spec, [fn for fn, _, _ in batch], seq, qual if want_qual else None, off)
             finishing.append((fut, [fn for fn, _, _ in batch], [rt for _, rt, _ in batch], [fq for _, _, fq in batch]))
         except Exception as e:
@@ -945,6 +1088,9 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                     if (device_merge and hasattr(rv, "with_device_merge") and "bases" in bundle
                             and len(bundle["bases"]) == int(bundle["meta"][:, 1].sum())):
                         packed = type(rv).with_device_merge(packed, bundle["bases"], want_qual)
+                        # --report: counted on the device as well, or - an engine without that call - the whole bundle on the host
+                        packed = type(rv).with_device_report(packed, tie_eps) if report and hasattr(rv, "with_device_report") \
+                            else (_host_merge_form(packed) if report else packed)
                 elif bundle is None and len(batch) > 1:
                     packed = prepare_many(type(rv), [rt for _, rt, _ in batch], rv.T)
             except Exception:
@@ -964,6 +1110,7 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                 if rt is None:
                     log(f"！！！[Error] fast5 file: {fn.split('.')[0]} {err}")
                     stats["failed"].append(fn)
+                    report.add(fn, False, unrevised_row(0))
                     note(fn, False)
                     continue
                 if err is not None:
@@ -992,6 +1139,7 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
         collect_finished(True)
         if pool is not None:                          # all work is in: an orderly end of the workers (their queues' semaphores
             pool.shutdown(wait=True)                  # are released here, not left to the resource tracker)
+    report.close()
     calls = sorted((c for c in trace if c[0] == "call"), key=lambda c: c[1]) if trace else []
     if trace and not calls:                           # every file failed before a device call: only the marks
         log("[trace] " + "; ".join(f"{w} {t:.3f} s" for k, t, w in trace if k == "mark") + "; no device call")
@@ -1210,6 +1358,8 @@ def revise_part(args, reviser, fn: str, k: int, parts: int):
         a1 = a2 = np.zeros(0, np.int8)
     qc = phred_chars(p1, p2, a1, a2) if args.output_format == "fastq" and len(a1) else None
     out = {"T": T, "n_ev": N, "lo": lo, "a1": np.array(a1, np.int8), "a2": np.array(a2, np.int8), "qc": qc}
+    if getattr(args, "report", None):                 # the parent reports the read once its slices are merged: near-ties need the rows
+        out["p1"], out["p2"] = np.array(p1, np.float32), np.array(p2, np.float32)
     if k == 0:
         out["bases"], out["fq"] = np.asarray(rt.bases), fq
     return out, None
@@ -1247,7 +1397,8 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
                 payload, err = None, repr(e)
             q.put(("part", rank, fn, k, payload, err))
         st = process_files(args, files, rv if rv is not None else make, print,
-                           on_file=lambda fn, ok: q.put(("file", rank, fn, bool(ok))), gpu_workers=world, core_share=share)
+                           on_file=lambda fn, ok: q.put(("file", rank, fn, bool(ok))), gpu_workers=world, core_share=share,
+                           report_part=report_part_path(args.report, rank) if getattr(args, "report", None) else None)
         st["cpus"] = len(cpus) if cpus else 0
         for e in made:
             e.close()
@@ -1256,7 +1407,7 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
         q.put(("done", rank, None, repr(e)))
 
 
-def write_originals(args, files: Sequence[str], log: Callable[[str], None]) -> List[str]:
+def write_originals(args, files: Sequence[str], log: Callable[[str], None], report: Optional[ReportPart] = None) -> List[str]:
     """The failure contract for reads whose WORKER is gone (NanoReviser.py:146-152 / :173-179): every
     file in `files` - the ones the dead worker never reported as final - gets its original basecalls
     written by this process (atomically, replacing whatever an earlier run left under that name).
@@ -1264,19 +1415,24 @@ def write_originals(args, files: Sequence[str], log: Callable[[str], None]) -> L
     done = []
     for fn in files:
         done.append(fn)
+        nw = 0
         try:
             rd, fq = parse_read(os.path.join(args.fast5_base_dir, fn), args.basecall_group, args.basecall_subgroup)
             if args.output_format == "fastq" and fq is not None:
                 b, q = hs.trim_fastq(fq)
                 write_read(args, fn, b, q)
             else:
-                write_read(args, fn, "".join(x.decode() for x in np.asarray(rd.bases).tolist()), None)
+                b = "".join(x.decode() for x in np.asarray(rd.bases).tolist())
+                write_read(args, fn, b, None)
+            nw = len(b)
         except Exception as e:
             log(f"！！！[Error] fast5 file: {fn.split('.')[0]} {e!r}")
+        if report is not None:
+            report.add(fn, False, unrevised_row(nw))
     return done
 
 
-def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[str], None]):
+def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[str], None], report: Optional[ReportPart] = None):
     """Parent side of the split reads: the slices' calls in slice order are the read's calls (window i of slice k is
     window lo_k + i of the read), merged and written exactly as an unsplit read's.  A read with a slice missing (its
     worker died) or failed gets its original basecalls (NanoReviser.py:146-152).  Returns (bases written, failed names)."""
@@ -1300,10 +1456,18 @@ def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[st
             if e2 is None:
                 nb += w
                 log(f"[p:::] {fn.split('.')[0]}_out.{args.output_format} was saved...... ({n} slices)")
+                if report is not None and report:
+                    have_p = all("p1" in p for p in pl)
+                    row = hs.revision_report(
+                        hostlib.bases_u8(pl[0]["bases"]), [N], a1, a2,
+                        np.concatenate([p["p1"] for p in pl]) if have_p else None, np.concatenate([p["p2"] for p in pl]) if have_p else None,
+                        (qc if qc is not None else np.zeros(0, np.uint8)) if args.output_format == "fastq" else None, T,
+                        float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS)))[0]
+                    report.add(fn, True, row)
                 continue
             err = e2
         log(f"[！！！Error] revising {fn.split('.')[0]}: {err}; writing the original basecalls")
-        write_originals(args, [fn], log)
+        write_originals(args, [fn], log, report)
         failed.append(fn)
     return nb, failed
 
@@ -1376,6 +1540,13 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
     names = sorted(f for f in os.listdir(args.fast5_base_dir) if f.endswith(".fast5"))
     os.makedirs(args.output_dir, exist_ok=True)
     t0 = time.time()
+    all_names = list(names)
+    if args.report:                       # --report: every process appends to a part of its own, `merge_report` ends the run
+        clear_report_parts(args.report)
+        d = os.path.dirname(args.report)
+        if d:
+            os.makedirs(d, exist_ok=True)
+    parent_report = ReportPart(report_part_path(args.report, "parent") if args.report else None)
     kept_failed, n_resumed = [], 0
     if args.resume:
         # A finished read is a non-empty <stem>_out.<fmt>: outputs only ever appear by rename of a complete temporary.
@@ -1400,12 +1571,14 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
         else:
             skip -= set(earlier_failed)
         n_resumed, names = len(skip), [f for f in names if f not in skip]
+        for f in sorted(skip):            # not revised by THIS run: reported as what lies on disk
+            parent_report.add(f, False, unrevised_row(written_length(out_name(args.output_dir, f, args.output_format))))
         print(f"[s:::] --resume: {n_resumed} reads already have their output, {len(names)} to do"
               + (f" ({len(earlier_failed)} of them written unrevised by the earlier run"
                  + (", left as they are)" if args.resume_keep_failed else ", revised again)") if earlier_failed else ""))
     if reviser_factory is not None:       # in-process (tests / embedding): one engine, no sharding
         rv = reviser_factory(args, 0)
-        stats = [process_files(args, names, rv, print)]
+        stats = [process_files(args, names, rv, print, report_part=report_part_path(args.report, 0) if args.report else None)]
     else:
         # the command line needs no torch: without it a process starts ~1.5 s sooner.  (engine.py imports
         # torch first only so that a LATER torch import in the same process finds one HIP runtime.)
@@ -1433,7 +1606,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
             def make():                               # runs in the engine thread, beside the parser pool's start-up
                 made.append((worker_factory or _default_factory)(args, 0))
                 return made[-1]                       # called once per engine (process_files: NRV_CLI_ENGINES)
-            stats = [process_files(args, names, make, print)]
+            stats = [process_files(args, names, make, print, report_part=report_part_path(args.report, 0) if args.report else None)]
             for rv in made:
                 rv.close()
         else:
@@ -1444,7 +1617,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
             res = run_workers(args, shards, worker_factory, part_shards=part_shards, parts_out=parts_got)
             stats = [s for _, s, _, _ in res if s is not None]
             if split_fns:
-                nb_split, failed_split = finish_split_reads(args, split_fns, parts_got, print)
+                nb_split, failed_split = finish_split_reads(args, split_fns, parts_got, print, parent_report)
                 stats.append({"reads": len(split_fns), "bases": nb_split, "failed": failed_split, "host_s": 0.0, "engine_s": 0.0})
                 if failed_split:
                     rc = 3
@@ -1454,10 +1627,13 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
                           f"unfinished reads", file=sys.stderr)
                     # what the worker reported final stays (its failed reads keep their failed_reads entry);
                     # everything else - started or not, whatever lies on disk - is written unrevised
-                    lost = write_originals(args, [f for f in shards[r] if f not in final], print)
+                    lost = write_originals(args, [f for f in shards[r] if f not in final], print, parent_report)
                     lost += [f for f, ok in final.items() if not ok]
                     stats.append({"reads": len(shards[r]), "bases": 0, "failed": lost, "host_s": 0.0, "engine_s": 0.0})
                     rc = 3
+    parent_report.close()
+    if args.report:
+        merge_report(args.report, all_names)
     failed = kept_failed + [f for s in stats for f in s["failed"]]
     with open(os.path.join(args.output_dir, args.failed_reads_filename), "w") as fp:
         fp.write("".join(f + "\n" for f in failed))

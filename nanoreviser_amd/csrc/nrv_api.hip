@@ -552,6 +552,12 @@ struct nrv_handle {
     size_t m_seq = 0, m_qual = 0, m_rec = 0, m_tile = 0, m_dl = 0;        // offsets into d_mrg; m_dl = bytes that come back
     bool merge = false, want_q = false;
     float thr[kPhredSteps] = {0};
+    // nrv_revise_reads_raw_report_begin (nrv_report.h): the report block u64 x n_reads x 24 behind qual, inside the part that
+    // comes back (m_dl grows by it; without a report the layout is the merge's own)
+    size_t m_rep = 0;
+    bool report = false;
+    float tie_eps = 0.f;
+    uint64_t* rep_out = nullptr;
     uint8_t *seq = nullptr, *qual = nullptr;
     int64_t* off = nullptr;
     int64_t N = 0, n = 0;
@@ -1912,15 +1918,36 @@ static int merge_enqueue(nrv_handle* h, const MergeArgs& a) {
   HIPCHK(h, hipGetLastError());
   return NRV_OK;
 }
-// layout of a merged block for N events, n windows, n_reads reads: [off | seq | qual] (what comes back) + [rec | tile] (scratch)
-struct MergeLayout { size_t seq, qual, rec, tile, dl, bytes; };
-static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads) {
+// The report kernel (nrv_report.h) behind merge_enqueue on the same stream: it reads the records the merge left in a.rec.  The
+// block is zeroed here, in stream order ahead of the launch - every call of this function starts its counts from nothing.
+static int report_enqueue(nrv_handle* h, const ReportArgs& a) {
+  if (a.n_reads <= 0 || a.N <= 0) return NRV_OK;
+  HIPCHK(h, hipMemsetAsync(a.report, 0, (size_t)a.n_reads * kReportCols * 8, h->stream));
+  const unsigned tiles = (unsigned)((a.N + kMergeTile - 1) / kMergeTile);
+  hipLaunchKernelGGL(report_kernel, dim3(tiles), dim3(256), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return NRV_OK;
+}
+static ReportArgs report_args(const MergeArgs& m, const float* p1, const float* p2, bool want_q, float tie_eps, void* report) {
+  ReportArgs a;
+  a.reads = m.reads; a.n_reads = m.n_reads; a.T = m.T; a.N = m.N;
+  a.bases = m.bases; a.a1 = m.a1; a.a2 = m.a2;
+  a.p1 = p1 && p2 ? p1 : nullptr; a.p2 = p1 && p2 ? p2 : nullptr;
+  a.rec = m.rec; a.want_q = want_q ? 1 : 0; a.tie_eps = tie_eps;
+  a.report = (unsigned long long*)report;
+  return a;
+}
+// layout of a merged block for N events, n windows, n_reads reads: [off | seq | qual | report] (what comes back; the report only
+// where one was asked for) + [rec | tile] (scratch)
+struct MergeLayout { size_t seq, qual, rep, rec, tile, dl, bytes; };
+static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, bool report = false) {
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   MergeLayout m;
   const size_t cap = (size_t)(N + n);
   m.seq = up(((size_t)n_reads + 1) * 8);
   m.qual = m.seq + up(cap);
-  m.dl = m.qual + up(cap);
+  m.rep = m.qual + up(cap);
+  m.dl = m.rep + (report ? up((size_t)n_reads * kReportCols * 8) : 0);
   m.rec = m.dl;
   m.tile = m.rec + up((size_t)N * 4);
   m.bytes = m.tile + up((size_t)((N + kMergeTile - 1) / kMergeTile) * 8);
@@ -1933,11 +1960,24 @@ static void merge_nothing(const uint8_t* bases, const nrv_read_desc* reads, int 
   for (int r = 0; r < n_reads; ++r) off[r] = reads[r].ev_off;
   off[n_reads] = N;
 }
+// ... and its report (hoststage.revision_report on a call without a window): edge = bases_in = bases_out = ev_len; with a
+// quality every character is '#', which is 2 above the Phred offset
+static void report_nothing(const nrv_read_desc* reads, int n_reads, bool want_q, uint64_t* report) {
+  static_assert(NRV_REPORT_COLS == kReportCols, "nanorev.h and nrv_report.h disagree on the report's columns");
+  memset(report, 0, (size_t)n_reads * kReportCols * 8);
+  for (int r = 0; r < n_reads; ++r) {
+    uint64_t* row = report + (size_t)r * kReportCols;
+    row[kRcBasesIn] = row[kRcBasesOut] = row[kRcEdge] = (uint64_t)reads[r].ev_len;
+    if (want_q) row[kRcQSum] = 2 * (uint64_t)reads[r].ev_len;
+  }
+}
 struct MergeReq {             // what nrv_revise_reads_raw_begin adds to a raw-read call
   const uint8_t* bases;
   const float* q_thr;
   uint8_t *seq, *qual;
   int64_t* off;
+  uint64_t* report = nullptr; // nrv_revise_reads_raw_report_begin: [n_reads][24], and the near-tie margin
+  float tie_eps = 0.f;
 };
 static MergeArgs slot_merge_args(const nrv_handle* h, const nrv_handle::RawSlot& sl) {
   char* const d = sl.d_out + 64;
@@ -1952,6 +1992,11 @@ static MergeArgs slot_merge_args(const nrv_handle* h, const nrv_handle::RawSlot&
   a.qual = sl.want_q ? (unsigned char*)(sl.d_mrg + sl.m_qual) : nullptr;
   memcpy(a.thr, sl.thr, sizeof a.thr);
   return a;
+}
+static ReportArgs slot_report_args(const nrv_handle* h, const nrv_handle::RawSlot& sl) {
+  char* const d = sl.d_out + 64;                               // p1 / p2 are in the output block whether a quality is wanted or not
+  return report_args(slot_merge_args(h, sl), (const float*)d, (const float*)(d + sl.rows * 24), sl.want_q, sl.tie_eps,
+                     sl.d_mrg + sl.m_rep);
 }
 
 // nrv_reads_raw_begin (last_dur == nullptr: today's call, to the byte), nrv_reads_raw_stats_begin and (mr != nullptr)
@@ -1980,8 +2025,10 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
   sl.p1 = p1; sl.p2 = p2; sl.a1 = a1; sl.a2 = a2;
   *ticket = k;
   sl.merge = mr != nullptr;
+  sl.report = mr != nullptr && mr->report != nullptr;
   if (sl.n == 0) {                                              // nothing to compute: _end returns at once
     if (mr) merge_nothing(mr->bases, reads, n_reads, N, mr->seq, mr->q_thr ? mr->qual : nullptr, mr->off);
+    if (sl.report) report_nothing(reads, n_reads, mr->q_thr != nullptr && mr->qual != nullptr, mr->report);
     sl.busy = true;
     return NRV_OK;
   }
@@ -2020,8 +2067,9 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
     sl.sat_seen = 0;
   }
   if (mr) {
-    const MergeLayout m = merge_layout(N, sl.n, n_reads);
+    const MergeLayout m = merge_layout(N, sl.n, n_reads, sl.report);
     sl.m_seq = m.seq; sl.m_qual = m.qual; sl.m_rec = m.rec; sl.m_tile = m.tile; sl.m_dl = m.dl;
+    sl.m_rep = m.rep; sl.rep_out = mr->report; sl.tie_eps = mr->tie_eps;
     sl.want_q = mr->q_thr != nullptr && mr->qual != nullptr;
     if (sl.want_q) memcpy(sl.thr, mr->q_thr, sizeof sl.thr);
     sl.seq = mr->seq; sl.qual = mr->qual; sl.off = mr->off;
@@ -2072,7 +2120,8 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
                        (const StatAux*)(sl.d_in + sl.off_aux), sl.d_stat, n_reads, N, stat_len, (float*)(sl.d_in + sl.off_feat),
                        nullptr, nullptr);
   // the merge reads the slot's output block: behind the call's last launch group, ahead of ev_done
-  if (rc || (rc = raw_enqueue(h, sl)) || (mr && (rc = merge_enqueue(h, slot_merge_args(h, sl))))) {
+  if (rc || (rc = raw_enqueue(h, sl)) || (mr && (rc = merge_enqueue(h, slot_merge_args(h, sl)))) ||
+      (sl.report && (rc = report_enqueue(h, slot_report_args(h, sl))))) {
     (void)hipStreamSynchronize(h->stream);                      // part of the call may be enqueued: nothing of it may outlive the slot
     return rc;
   }
@@ -2135,6 +2184,27 @@ int nrv_revise_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, const
   return rc ? rc : nrv_reads_raw_end(h, t);
 }
 
+int nrv_revise_reads_raw_report_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                      const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                      const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                      uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report, int* ticket) {
+  if (h && ((last_dur == nullptr) != (on_device == nullptr))) { h->err = "nrv_revise_reads_raw_report_begin: last_dur and on_device go together"; return NRV_E_INVALID; }
+  if (h && !report) { h->err = "nrv_revise_reads_raw_report_begin: null report"; return NRV_E_INVALID; }
+  MergeReq mr{bases, q_thr, seq, qual, off};
+  mr.report = report; mr.tie_eps = tie_eps;
+  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, nullptr, nullptr, nullptr, nullptr, ticket, &mr);
+}
+
+int nrv_revise_reads_raw_report(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report) {
+  int t = -1;
+  const int rc = nrv_revise_reads_raw_report_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                                   seq, qual, off, tie_eps, report, &t);
+  return rc ? rc : nrv_reads_raw_end(h, t);
+}
+
 int nrv_reads_raw_end(nrv_handle* h, int ticket) {
   int rc = check_handle(h);
   if (rc) return rc;
@@ -2154,6 +2224,8 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
     if (rc2) return rc2;
     if (sl.merge) {                                             // the merge again, in stream order behind the re-run it reads
       if ((rc = poison_fill(h, sl.d_mrg, sl.cap_mrg, h->stream)) || (rc = merge_enqueue(h, slot_merge_args(h, sl)))) return rc;
+      // ... and the report: report_enqueue zeroes the block again, so the first pass's counts are not counted twice
+      if (sl.report && (rc = report_enqueue(h, slot_report_args(h, sl)))) return rc;
       HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64, hipMemcpyDeviceToHost, h->stream));
       HIPCHK(h, hipMemcpyAsync(sl.pin_mrg, sl.d_mrg, sl.m_dl, hipMemcpyDeviceToHost, h->stream));
     } else {
@@ -2170,6 +2242,7 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
     memcpy(sl.off, off, ((size_t)sl.n_reads + 1) * 8);
     memcpy(sl.seq, sl.pin_mrg + sl.m_seq, (size_t)total);
     if (sl.want_q) memcpy(sl.qual, sl.pin_mrg + sl.m_qual, (size_t)total);
+    if (sl.report) memcpy(sl.rep_out, sl.pin_mrg + sl.m_rep, (size_t)sl.n_reads * kReportCols * 8);
     return NRV_OK;
   }
   const char* o = sl.pin_out + 64;
@@ -2261,8 +2334,10 @@ int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32
   return NRV_OK;
 }
 
-int nrv_merge_calls(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
-                    const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off) {
+// nrv_merge_calls (report == nullptr: that call, to the byte) and nrv_merge_calls_report
+static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                            const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                            float tie_eps, uint64_t* report) {
   int rc = check_handle(h);
   if (rc) return rc;
   if (n_reads < 0 || n_win < 0 || !off || (n_reads > 0 && !ev_len)) { h->err = "nrv_merge_calls: bad arguments"; return NRV_E_INVALID; }
@@ -2280,12 +2355,17 @@ int nrv_merge_calls(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, 
     h->err = "nrv_merge_calls: n_win is not sum(ev_len) - T, or a null array";
     return NRV_E_INVALID;
   }
-  if (n == 0) { merge_nothing(bases, rd.data(), n_reads, N, seq, want_q ? qual : nullptr, off); return NRV_OK; }
+  if (n == 0) {
+    merge_nothing(bases, rd.data(), n_reads, N, seq, want_q ? qual : nullptr, off);
+    if (report) report_nothing(rd.data(), n_reads, want_q, report);
+    return NRV_OK;
+  }
   // one block of its own: [reads | bases | a1 | a2 | p1 | p2 | merged block]
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const MergeLayout m = merge_layout(N, n, n_reads);
+  const MergeLayout m = merge_layout(N, n, n_reads, report != nullptr);
+  const bool have_p = want_q || (report && p1 && p2);          // the report's near-tie column reads the rows without a quality too
   const size_t o_b = up((size_t)n_reads * sizeof(SegRead)), o_a1 = o_b + up((size_t)N), o_a2 = o_a1 + up((size_t)n);
-  const size_t o_p1 = o_a2 + up((size_t)n), o_p2 = o_p1 + (want_q ? up((size_t)n * 24) : 0), o_m = o_p2 + (want_q ? up((size_t)n * 20) : 0);
+  const size_t o_p1 = o_a2 + up((size_t)n), o_p2 = o_p1 + (have_p ? up((size_t)n * 24) : 0), o_m = o_p2 + (have_p ? up((size_t)n * 20) : 0);
   const size_t bytes = o_m + m.bytes;
   char* d = nullptr;
   HIPCHK(h, hipMalloc((void**)&d, bytes));
@@ -2297,7 +2377,7 @@ int nrv_merge_calls(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, 
     HIPCHK(h, hipMemcpyAsync(d + o_b, bases, (size_t)N, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d + o_a1, a1, (size_t)n, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d + o_a2, a2, (size_t)n, hipMemcpyHostToDevice, h->stream));
-    if (want_q) {
+    if (have_p) {
       HIPCHK(h, hipMemcpyAsync(d + o_p1, p1, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
       HIPCHK(h, hipMemcpyAsync(d + o_p2, p2, (size_t)n * 20, hipMemcpyHostToDevice, h->stream));
     }
@@ -2312,6 +2392,9 @@ int nrv_merge_calls(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, 
     memset(a.thr, 0, sizeof a.thr);
     if (want_q) memcpy(a.thr, q_thr, sizeof a.thr);
     if ((rc2 = merge_enqueue(h, a))) return rc2;
+    if (report && (rc2 = report_enqueue(h, report_args(a, have_p ? (const float*)(d + o_p1) : nullptr, have_p ? (const float*)(d + o_p2) : nullptr,
+                                                      want_q, tie_eps, d + o_m + m.rep))))
+      return rc2;
     HIPCHK(h, hipMemcpyAsync(back.data(), d + o_m, m.dl, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return NRV_OK;
@@ -2325,7 +2408,21 @@ int nrv_merge_calls(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, 
   memcpy(off, back.data(), ((size_t)n_reads + 1) * 8);
   memcpy(seq, back.data() + m.seq, (size_t)total);
   if (want_q) memcpy(qual, back.data() + m.qual, (size_t)total);
+  if (report) memcpy(report, back.data() + m.rep, (size_t)n_reads * kReportCols * 8);
   return NRV_OK;
+}
+
+int nrv_merge_calls(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                    const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off) {
+  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, seq, qual, off, 0.f, nullptr);
+}
+
+int nrv_merge_calls_report(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                           const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                           float tie_eps, uint64_t* report) {
+  if (h && n_reads > 0 && !report) { h->err = "nrv_merge_calls_report: null report"; return NRV_E_INVALID; }
+  static uint64_t none[NRV_REPORT_COLS];
+  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, seq, qual, off, tie_eps, report ? report : none);
 }
 
 int nrv_saturated(nrv_handle* h, int64_t* pending, int64_t* reruns) {

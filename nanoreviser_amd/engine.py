@@ -35,7 +35,9 @@ SYMBOLS = [
     "nrv_device_count", "nrv_saturated", "nrv_prof_overhead",
     "nrv_reads_raw_stats_begin", "nrv_predict_reads_raw_stats", "nrv_read_stats",
     "nrv_revise_reads_raw_begin", "nrv_revise_reads_raw", "nrv_merge_calls",
+    "nrv_revise_reads_raw_report_begin", "nrv_revise_reads_raw_report", "nrv_merge_calls_report",
 ]
+REPORT_COLS = 24                    # NRV_REPORT_COLS
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "f16x2": 2}
 
@@ -154,6 +156,14 @@ def load_library(path: Optional[str] = None):
     lib.nrv_revise_reads_raw_begin.restype = C.c_int
     lib.nrv_merge_calls.argtypes = [vp, u8p, i64p, C.c_int, i8p, i8p, fp, fp, C.c_int64, fp, u8p, u8p, i64p]
     lib.nrv_merge_calls.restype = C.c_int
+    if hasattr(lib, "nrv_merge_calls_report"):          # by presence: NRV_LIB may name an older build of the same ABI
+        u64p = C.POINTER(C.c_uint64)
+        lib.nrv_revise_reads_raw_report.argtypes = lib.nrv_revise_reads_raw.argtypes + [C.c_float, u64p]
+        lib.nrv_revise_reads_raw_report.restype = C.c_int
+        lib.nrv_revise_reads_raw_report_begin.argtypes = lib.nrv_revise_reads_raw_report.argtypes + [C.POINTER(C.c_int)]
+        lib.nrv_revise_reads_raw_report_begin.restype = C.c_int
+        lib.nrv_merge_calls_report.argtypes = lib.nrv_merge_calls.argtypes + [C.c_float, u64p]
+        lib.nrv_merge_calls_report.restype = C.c_int
     lib.nrv_prof_overhead.argtypes = [vp, C.POINTER(C.c_double)]
     lib.nrv_saturated.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.nrv_set_precision.argtypes = [vp, C.c_int]
@@ -369,6 +379,23 @@ class Reviser:
         ld, on = (packed[7], packed[8]) if len(packed) == 9 else (None, None)
         return tuple(packed[:7]) + (ld, on, b, thr, out)
 
+    @staticmethod
+    def with_device_report(packed, tie_eps=None):
+        """A `with_device_merge` tuple whose call also returns the per-read revision report (include/nanorev.h
+        nrv_revise_reads_raw_report_begin; hoststage.revision_report is the definition): `run_packed_raw` /
+        `begin_packed_raw` + `end_packed_raw` then return (seq, qual | None, off, report uint64[n_reads][24])."""
+        if len(packed) != 12:
+            raise ValueError("with_device_report extends a with_device_merge tuple")
+        if tie_eps is None:
+            from .hoststage import REPORT_TIE_EPS
+            tie_eps = REPORT_TIE_EPS
+        return tuple(packed) + (float(tie_eps), np.zeros((packed[4], REPORT_COLS), np.uint64))
+
+    def _report_args(self, packed):
+        if not hasattr(self._lib, "nrv_revise_reads_raw_report_begin"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_revise_reads_raw_report_begin")
+        return self._revise_args(packed[:12]) + [C.c_float(packed[12]), packed[13].ctypes.data_as(C.POINTER(C.c_uint64))]
+
     def _revise_args(self, packed):
         raw, st, feat, descs, nr, N, _, ld, on, b, thr, (seq, qual, off) = packed
         fp, u8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
@@ -380,14 +407,17 @@ class Reviser:
 
     @staticmethod
     def _trim_merged(out):
-        seq, qual, off = out
+        seq, qual, off = out[:3]
         total = int(off[-1])
-        return seq[:total], (qual[:total] if qual is not None else None), off
+        return (seq[:total], (qual[:total] if qual is not None else None), off) + tuple(out[3:])
 
     def run_packed_raw(self, packed):
         """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared (or `with_device_stats` /
         `with_device_merge` extended)."""
         fp, i8p = C.POINTER(C.c_float), C.POINTER(C.c_int8)
+        if len(packed) == 14:                         # `with_device_report`: nrv_revise_reads_raw_report
+            self._check(self._lib.nrv_revise_reads_raw_report(*self._report_args(packed)))
+            return self._trim_merged(packed[11]) + (packed[13],)
         if len(packed) == 12:                         # `with_device_merge`: nrv_revise_reads_raw
             self._check(self._lib.nrv_revise_reads_raw(*self._revise_args(packed)))
             return self._trim_merged(packed[11])
@@ -410,6 +440,9 @@ class Reviser:
         ticket for `end_packed_raw`.  At most two calls in flight; the OUTPUT arrays of `packed` must stay alive until the end."""
         fp, i8p = C.POINTER(C.c_float), C.POINTER(C.c_int8)
         t = C.c_int(-1)
+        if len(packed) == 14:                         # `with_device_report`: nrv_revise_reads_raw_report_begin
+            self._check(self._lib.nrv_revise_reads_raw_report_begin(*self._report_args(packed), C.byref(t)))
+            return t.value, packed[11] + (packed[13],), "merged"
         if len(packed) == 12:                         # `with_device_merge`: nrv_revise_reads_raw_begin
             self._check(self._lib.nrv_revise_reads_raw_begin(*self._revise_args(packed), C.byref(t)))
             return t.value, packed[11], "merged"
@@ -429,7 +462,7 @@ class Reviser:
 
     def end_packed_raw(self, ticket):
         """Second half: waits for the call `ticket` names and returns its (p1, p2, a1, a2) - or, for a `with_device_merge`
-        call, its (seq, qual, off)."""
+        call, its (seq, qual, off), with the report behind them for a `with_device_report` call."""
         t, out = ticket[:2]
         self._check(self._lib.nrv_reads_raw_end(self._h, t))
         return self._trim_merged(out) if len(ticket) == 3 else out
@@ -495,6 +528,41 @@ class Reviser:
             thr.ctypes.data_as(fp) if thr is not None else None, seq.ctypes.data_as(u8p),
             qual.ctypes.data_as(u8p) if qual is not None else None, off.ctypes.data_as(C.POINTER(C.c_int64))))
         return self._trim_merged((seq, qual, off))
+
+    def merge_calls_report_device(self, bases, ev_len, a1, a2, p1=None, p2=None, q_thr=None, tie_eps=None):
+        """`merge_calls_device` with the per-read revision report (nrv_merge_calls_report): p1 / p2 may be given without q_thr
+        (near_tie filled, q_sum 0).  Returns (seq, qual | None, off, report uint64[n_reads][24]) - the report is
+        hoststage.revision_report's, bit for bit."""
+        from .hostlib import bases_u8
+        from .hoststage import REPORT_TIE_EPS
+        if not hasattr(self._lib, "nrv_merge_calls_report"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_merge_calls_report")
+        b = bases_u8(bases)
+        el = np.ascontiguousarray(ev_len, dtype=np.int64).reshape(-1)
+        x1, x2 = np.ascontiguousarray(a1, dtype=np.int8).reshape(-1), np.ascontiguousarray(a2, dtype=np.int8).reshape(-1)
+        N, n = b.size, x1.size
+        if int(el.sum()) != N or x2.size != n:
+            raise ValueError("bases / ev_len / a1 / a2 do not match")
+        fp, u8p, i8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int8)
+        thr = q1 = q2 = None
+        if p1 is not None and p2 is not None:
+            q1, q2 = _as_f32(np.asarray(p1).reshape(-1, 6), (6,)), _as_f32(np.asarray(p2).reshape(-1, 5), (5,))
+            if q1.shape[0] != n or q2.shape[0] != n:
+                raise ValueError("p1 / p2 do not match")
+        if q_thr is not None:
+            thr = np.ascontiguousarray(q_thr, dtype=np.float32).reshape(-1)
+            if thr.size != 39 or q1 is None:
+                raise ValueError("q_thr needs 39 entries and p1 / p2")
+        cap = max(N + n, 1)
+        seq, qual, off = np.empty(cap, np.uint8), (np.empty(cap, np.uint8) if thr is not None else None), np.zeros(el.size + 1, np.int64)
+        report = np.zeros((el.size, REPORT_COLS), np.uint64)
+        self._check(self._lib.nrv_merge_calls_report(
+            self._h, b.ctypes.data_as(u8p), el.ctypes.data_as(C.POINTER(C.c_int64)), el.size, x1.ctypes.data_as(i8p), x2.ctypes.data_as(i8p),
+            q1.ctypes.data_as(fp) if q1 is not None else None, q2.ctypes.data_as(fp) if q2 is not None else None, n,
+            thr.ctypes.data_as(fp) if thr is not None else None, seq.ctypes.data_as(u8p),
+            qual.ctypes.data_as(u8p) if qual is not None else None, off.ctypes.data_as(C.POINTER(C.c_int64)),
+            C.c_float(REPORT_TIE_EPS if tie_eps is None else tie_eps), report.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return self._trim_merged((seq, qual, off)) + (report,)
 
     @staticmethod
     def _fingerprint(a):
