@@ -15,6 +15,7 @@ import pytest
 
 from nanoreviser_amd import hoststage as hs
 from parity_policy import check_vs_fp64, f32_floor
+from weight_cases import conv1_sample_bound as _conv1_sample_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -25,15 +26,6 @@ def _fixture_windows(reads, key="ch10_read5252", lo=1000, n=320, T=11):
     _, _, rt = reads(key)
     sw, fw = hs.sliding_windows(rt.sig_ev, rt.feat_ev, T)
     return np.ascontiguousarray(sw[lo:lo + n]), np.ascontiguousarray(fw[lo:lo + n])
-
-
-def _conv1_sample_bound(m):
-    """The engine's static bound (nrv_api.hip upload_model, cnn_r_kernel's ep[24]): below it no conv1 + BatchNorm
-    output can leave the f16 range of the f16x2 signal branch (|c1| x 2^6 <= 65504)."""
-    w, b, g, be, mu, var = [np.asarray(x, np.float64) for x in m.tensors[:6]]
-    inv = g / np.sqrt(var + 1e-3)
-    sh = be - mu * inv
-    return float((((1000.0 - np.abs(sh)) / np.abs(inv) - np.abs(b)) / np.abs(w[:, 0, :]).sum(0)).min())
 
 
 @pytest.mark.parametrize("sp", ["ecoli", "human"])
