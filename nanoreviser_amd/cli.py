@@ -35,9 +35,12 @@ from __future__ import annotations
 import argparse
 import math
 import os
+import queue
 import sys
+import threading
 import time
-from concurrent.futures import ProcessPoolExecutor
+from collections import deque
+from concurrent.futures import Future, ProcessPoolExecutor, ThreadPoolExecutor
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -220,24 +223,27 @@ def phred_lookup(conf) -> np.ndarray:
     return (33 + 1 + np.searchsorted(phred_thresholds(), np.asarray(conf, np.float32), "right")).astype(np.uint8)
 
 
-def _finish_read(T: int, rt, p1, p2, a1, a2, want_qual: bool = True):
-    """Calls of one read -> (revised sequence, per-base quality string or None)."""
-    codes = np.frombuffer(np.asarray(rt.bases, dtype="S1").tobytes(), dtype=np.uint8)
+def _merge_read(T: int, bases, a1, a2, qc):
+    """Original bases of one read + its calls -> (revised sequence, per-base quality string or None); qc: per-window Phred
+    characters (FASTQ) or None (FASTA)."""
+    codes = np.frombuffer(np.asarray(bases, dtype="S1").tobytes(), dtype=np.uint8)
     off, n = (T - 1) // 2, len(a1)
     if n == 0:
         return codes.tobytes().decode("ascii"), "#" * len(codes)
     first, second, count = hs.merge_calls(codes[off:off + n], a1, a2)
-    if not want_qual:                                # FASTA output: no quality string to build
-        z = np.zeros(n, np.uint8)
-        seq_mid, _ = hs.expand_calls(first, second, count, z, z)
-        seq = codes[:off].tobytes() + seq_mid.tobytes() + codes[off + n:].tobytes()
-        return seq.decode("ascii"), None
-    qc = phred_chars(p1, p2, a1, a2)
-    seq_mid, q_mid = hs.expand_calls(first, second, count, qc, qc)
+    z = qc if qc is not None else np.zeros(n, np.uint8)
+    seq_mid, q_mid = hs.expand_calls(first, second, count, z, z)
+    seq = (codes[:off].tobytes() + seq_mid.tobytes() + codes[off + n:].tobytes()).decode("ascii")
+    if qc is None:
+        return seq, None
     edge = np.full(1, ord("#"), np.uint8)
-    seq = codes[:off].tobytes() + seq_mid.tobytes() + codes[off + n:].tobytes()
     qual = np.repeat(edge, off).tobytes() + q_mid.tobytes() + np.repeat(edge, len(codes) - off - n).tobytes()
-    return seq.decode("ascii"), qual.decode("ascii")
+    return seq, qual.decode("ascii")
+
+
+def _finish_read(T: int, rt, p1, p2, a1, a2, want_qual: bool = True):
+    """Calls of one read -> (revised sequence, per-base quality string or None)."""
+    return _merge_read(T, rt.bases, a1, a2, phred_chars(p1, p2, a1, a2) if want_qual and len(a1) else None)
 
 
 def predict_one(reviser, rt):
@@ -276,14 +282,29 @@ def predict_many(reviser, rts, packed=None):
         sig = np.concatenate([rt.sig_ev for rt in rts])
         feat = np.concatenate([rt.feat_ev for rt in rts])
         p1, p2, a1, a2 = reviser.predict_read(sig, feat)
-    out, e0 = [], 0
+    return _slice_calls((p1, p2, a1, a2), [len(rt.feat_ev) for rt in rts], T)
+
+
+def _slice_calls(outs, ev_lens, T):
+    """The outputs of one call over concatenated reads -> one (p1, p2, a1, a2) per read."""
+    p1, p2, a1, a2 = outs
+    calls, e0 = [], 0
+    for N in ev_lens:
+        sl = slice(e0, e0 + max(int(N) - T, 0))    # window i of the read == window e0+i of the call
+        calls.append((p1[sl], p2[sl], a1[sl], a2[sl]))
+        e0 += int(N)
+    return calls
+
+
+def _predict_each(reviser, rts):
+    """Read by read, after a call over all of them failed: each read's calls, or its exception."""
+    calls = []
     for rt in rts:
-        N = len(rt.feat_ev)
-        n = max(N - T, 0)
-        sl = slice(e0, e0 + n)                     # window i of the read == window e0+i of the batch
-        out.append((p1[sl], p2[sl], a1[sl], a2[sl]))
-        e0 += N
-    return out
+        try:
+            calls.append(predict_one(reviser, rt))
+        except Exception as e:
+            calls.append(e)
+    return calls
 
 
 def revise_one(reviser, rt, want_qual: bool = True):
@@ -337,24 +358,14 @@ def _load_bundle(jobs, device_stats: bool = False):
     qualified.  device_stats (--device_stats): the native loader leaves the read statistics to the device; the bundle then
     carries `last_dur` and `device_stats` per read, and shift / scale / feature columns 1 - 2 of the flagged reads are zeros."""
     t0 = time.perf_counter()
-    if device_stats:
-        nb = hostlib.load_bundle([j[0] for j in jobs], jobs[0][2], jobs[0][3], want_fastq=(jobs[0][4] if len(jobs[0]) > 4 else True),
-                                 device_stats=True) if jobs and all(j[2:] == jobs[0][2:] for j in jobs) else None
-        if nb is None or int((nb["status"] == hostlib.OK).sum()) == 0 or not bool((nb["status"] == hostlib.OK).all()):
-            return _load_bundle(jobs)                 # no library, or a file for the Python reader among them: host-fed as ever
-        good = list(range(len(jobs)))
-        dt = (time.perf_counter() - t0) / len(jobs)
-        entries, eo = [], 0
-        for i, j in enumerate(jobs):
-            el = int(nb["meta"][i, 1])
-            entries.append((j[1], _LightRead(nb["bases"][eo:eo + el], el), nb["fastq"][i], None, dt))
-            eo += el
-        return entries, {"idx": good, "raw": nb["raw"], "starts": nb["starts"], "feat": nb["feat"],
-                         "meta": np.ascontiguousarray(nb["meta"]), "bases": nb["bases"],
-                         "last_dur": np.ascontiguousarray(nb["last_dur"]), "device_stats": np.ascontiguousarray(nb["device_stats"])}
-    nb = hostlib.load_bundle([j[0] for j in jobs], jobs[0][2], jobs[0][3], want_fastq=(jobs[0][4] if len(jobs[0]) > 4 else True)) \
+    # (device_stats is passed only when set: a stand-in for hostlib.load_bundle without that keyword keeps working)
+    nb = hostlib.load_bundle([j[0] for j in jobs], jobs[0][2], jobs[0][3], want_fastq=(jobs[0][4] if len(jobs[0]) > 4 else True),
+                             **({"device_stats": True} if device_stats else {})) \
         if jobs and all(j[2:] == jobs[0][2:] for j in jobs) else None
-    if nb is not None and int((nb["status"] == hostlib.OK).sum()) > 0:
+    n_ok = int((nb["status"] == hostlib.OK).sum()) if nb is not None else 0
+    if device_stats and not 0 < n_ok == len(jobs):
+        return _load_bundle(jobs)                     # no library, or a file for the Python reader among them: host-fed as ever
+    if n_ok > 0:
         # ONE native call for the whole task: the reads it took are already concatenated; the others (a layout the native
         # reader does not know, a broken file) go through the Python host stage one by one
         dt = (time.perf_counter() - t0) / len(jobs)
@@ -385,6 +396,8 @@ def _load_bundle(jobs, device_stats: bool = False):
             return _bundle_of(out)
         bundle = {"idx": good, "raw": nb["raw"], "starts": nb["starts"], "feat": nb["feat"],
                   "meta": np.ascontiguousarray(nb["meta"][good]), "bases": nb["bases"]}
+        if device_stats:                              # (every read is in the bundle)
+            bundle["last_dur"], bundle["device_stats"] = np.ascontiguousarray(nb["last_dur"]), np.ascontiguousarray(nb["device_stats"])
         return entries, bundle
     return _bundle_of([_load_one(j) for j in jobs])
 
@@ -455,20 +468,7 @@ def _finish_in_worker(spec, T, fn, bases, a1, a2, qc):
     (the 0.5 ms of NumPy, string building and file IO per read that the main process' finisher thread used to spend
     under the GIL).  qc: per-window Phred characters (FASTQ) or None (FASTA).  Returns (bases written, error)."""
     try:
-        codes = np.frombuffer(np.asarray(bases, dtype="S1").tobytes(), dtype=np.uint8)
-        off, n = (T - 1) // 2, len(a1)
-        if n == 0:
-            seq, qual = codes.tobytes().decode("ascii"), "#" * len(codes)
-        else:
-            first, second, count = hs.merge_calls(codes[off:off + n], a1, a2)
-            z = qc if qc is not None else np.zeros(n, np.uint8)
-            seq_mid, q_mid = hs.expand_calls(first, second, count, z, z)
-            seq = (codes[:off].tobytes() + seq_mid.tobytes() + codes[off + n:].tobytes()).decode("ascii")
-            qual = None
-            if qc is not None:
-                edge = np.full(1, ord("#"), np.uint8)
-                qual = (np.repeat(edge, off).tobytes() + q_mid.tobytes()
-                        + np.repeat(edge, len(codes) - off - n).tobytes()).decode("ascii")
+        seq, qual = _merge_read(T, bases, a1, a2, qc)
         write_read(spec, fn, seq, qual)
         return len(seq), None
     except Exception as e:
@@ -489,32 +489,27 @@ def _finish_native(spec, T, fn, bases, a1, a2, qc):
         return 0, repr(e)
 
 
-def _finish_bundle_native(spec, T, fns, bases, ev_len, a1, a2, qc):
-    """All reads of one device call through nrvh_finish_bundle (one C call, GIL released): [(bases written, error)]."""
+def _native_task(spec, fns, call):
+    """One native finisher call for the reads `fns` (GIL released): call(names, destinations, fastq) -> [(bases written, error)]."""
     try:
         os.makedirs(spec.output_dir, exist_ok=True)
-        r = hostlib.finish_bundle(bases, ev_len, a1, a2, T, qc, [fn.split("/")[-1].replace(" ", "|||") for fn in fns],
-                                  [out_name(spec.output_dir, fn, spec.output_format) for fn in fns], spec.output_format == "fastq")
+        r = call([fn.split("/")[-1].replace(" ", "|||") for fn in fns],
+                 [out_name(spec.output_dir, fn, spec.output_format) for fn in fns], spec.output_format == "fastq")
         if r is None:
             raise RuntimeError("libnanorev_host.so went away")
-        nw, st = r
-        return [(int(n), None if c == hostlib.OK else f"native finisher: error {int(c)}") for n, c in zip(nw, st)]
+        return [(int(n), None if c == hostlib.OK else f"native finisher: error {int(c)}") for n, c in zip(*r)]
     except Exception as e:
         return [(0, repr(e))] * len(fns)
+
+
+def _finish_bundle_native(spec, T, fns, bases, ev_len, a1, a2, qc):
+    """All reads of one device call through nrvh_finish_bundle: [(bases written, error)]."""
+    return _native_task(spec, fns, lambda names, dsts, fq: hostlib.finish_bundle(bases, ev_len, a1, a2, T, qc, names, dsts, fq))
 
 
 def _write_records_native(spec, fns, seq, qual, off):
-    """All reads of one --device_merge call through nrvh_write_records (one C call, GIL released): [(bases written, error)]."""
-    try:
-        os.makedirs(spec.output_dir, exist_ok=True)
-        r = hostlib.write_records(seq, qual, off, [fn.split("/")[-1].replace(" ", "|||") for fn in fns],
-                                  [out_name(spec.output_dir, fn, spec.output_format) for fn in fns], spec.output_format == "fastq")
-        if r is None:
-            raise RuntimeError("libnanorev_host.so went away")
-        nw, st = r
-        return [(int(n), None if c == hostlib.OK else f"native finisher: error {int(c)}") for n, c in zip(nw, st)]
-    except Exception as e:
-        return [(0, repr(e))] * len(fns)
+    """All reads of one --device_merge call through nrvh_write_records: [(bases written, error)]."""
+    return _native_task(spec, fns, lambda names, dsts, fq: hostlib.write_records(seq, qual, off, names, dsts, fq))
 
 
 REPORT_HEADER = "name\tstatus\t" + "\t".join(hs.REPORT_NAMES)
@@ -551,7 +546,6 @@ class ReportPart:
     worker that dies leaves the lines of what it finished).  `merge_report` puts the parts together."""
 
     def __init__(self, path: Optional[str]):
-        import threading
         self.path, self._lock, self._fp = path, threading.Lock(), None
 
     def __bool__(self):
@@ -633,6 +627,54 @@ def _host_merge_form(packed):
     return tuple(packed[:7]) if packed[7] is None else tuple(packed[:9])
 
 
+def _is_merged_ticket(tk) -> bool:
+    """The ticket of a call that comes back as revised reads (seq, qual, off[, report]): engine.Reviser.begin_packed_raw."""
+    return isinstance(tk, tuple) and len(tk) == 3
+
+
+def _bundle_has_bases(bundle) -> bool:
+    """This bundle carries one original base per event: what the bundle finishers and the device merge work from."""
+    return "bases" in bundle and len(bundle["bases"]) == int(bundle["meta"][:, 1].sum())
+
+
+def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, report):
+    """The one decision about a batch: (packed form `_FileRun.submit` builds, route `_FileRun.run_batch` takes).  Pure: it looks at what
+    the engine object offers, at the bundle (None: reads that arrived one by one) and at the run's switches - pipelined (one
+    engine, NRV_CLI_PIPELINE != 0), native_pool (libnanorev_host.so driven from the thread pool), device_merge (--device_merge
+    and what it needs: pipelined, native_pool, nrvh_write_records), report (--report).  "bases": `_bundle_has_bases`.  A form is
+    the length of the packed tuple (engine.Reviser), None, or "host-merge": the merge form built and taken back.
+
+      bundle  engine offers / bundle / switches                              form            route
+      none    one read                                                       None            per-read
+      none    several reads, no pack_reads_raw                               None            predict_many
+      none    several reads, pack_reads_raw                                  7 [1]           predict_many
+      yes     no run_packed_raw                                              None            predict_many (one read: per-read)
+      yes     run_packed_raw; bundle without / with "device_stats"           7 / 9           by the last three rows
+      yes     + device_merge, with_device_merge, bases; report off           12              by the last three rows
+      yes     + report on, with_device_report                                14              by the last three rows
+      yes     + report on, no with_device_report                             host-merge [2]  by the last three rows
+      yes     any form; pipelined, native_pool, begin_packed_raw, bases                      pipelined [3]
+      yes     any form; native_pool, bases, not (pipelined, begin_packed_raw)                packed+finish_bundle
+      yes     any form; no native_pool, or no bases                                          packed sliced
+
+    [1] None when `prepare_many` declines (not all raw reads) or building a form raises; the route is then predict_many.
+    [2] the whole bundle on the host: merge, quality and report rows from the calls.
+    [3] begin_packed_raw raising -> packed+finish_bundle.  Every route but this one takes a 12 / 14 form back through
+        `_host_merge_form`; any call raising -> per-read retries on reads that `_bundle_reads` completes on the host."""
+    unpacked = "per-read" if n_reads == 1 else "predict_many"
+    if bundle is None:
+        return (7 if n_reads > 1 and hasattr(rv, "pack_reads_raw") else None), unpacked
+    if not hasattr(rv, "run_packed_raw"):
+        return None, unpacked
+    bases = _bundle_has_bases(bundle)
+    form = 9 if "device_stats" in bundle else 7
+    if device_merge and hasattr(rv, "with_device_merge") and bases:
+        form = 12 if not report else (14 if hasattr(rv, "with_device_report") else "host-merge")
+    if not (native_pool and bases):
+        return form, "packed sliced"
+    return form, ("pipelined" if pipelined and hasattr(rv, "begin_packed_raw") else "packed+finish_bundle")
+
+
 def usable_cores() -> int:
     """Cores this process can really use: its affinity mask, cut down to the cgroup's CPU quota (a container that shows
     256 CPUs and grants 16 runs sixteen parser workers, not the 32 that --thread's default of 100 would otherwise give:
@@ -686,125 +728,199 @@ def parser_pool_size(threads: int, cores: int, gpu_workers: int, n_files: int, n
     return max(1, min(int(threads), share, native_pool_max() if native else 32, max(1, n_files)))
 
 
-def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None],
-                  on_file: Optional[Callable[[str, bool], None]] = None, gpu_workers: int = 1,
-                  core_share: Optional[int] = None, report_part: Optional[str] = None) -> dict:
-    """Revise `files` (names inside args.fast5_base_dir) with one engine.  The host stage (HDF5
-    parsing, event collapse, signal segmentation) runs in worker PROCESSES (--thread of them, capped
-    at the core count) that stay a bounded number of reads ahead of the device.
-    on_file(fn, revised): called once per file when its output is final (revised, or the original
-    basecalls after a failure; revised=False also for files that could not be parsed at all).
-    gpu_workers: how many such calls run on this host at the same time (one per GPU, `run_workers`): the cores are
-    SHARED, so each call's parser pool gets usable_cores() // gpu_workers of them - eight workers on a 16-core cgroup
-    start 8 x 2 parser processes, not 8 x 16.  core_share: this call's cores, when the caller has already
-    divided them (a GPU worker pinned to its NUMA slice: `_worker`).  report_part (--report): the file this call appends
-    one line per read to, ahead of on_file (`ReportPart`)."""
-    stats = {"reads": 0, "bases": 0, "failed": [], "host_s": 0.0, "engine_s": 0.0}
-    report = ReportPart(report_part)
-    rep_rows = {}                                     # fn -> the row of a read whose output is not final yet
-    tie_eps = float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS))
-    # NRV_CLI_TRACE=1: where the wall time of this call goes (first device call, engine idle gaps, tail), to the log
-    trace, t_start = ([] if os.environ.get("NRV_CLI_TRACE") else None), time.perf_counter()
-    if trace is not None:
-        try:                                          # age of this process: interpreter start, imports, main() so far
-            with open("/proc/self/stat") as f:
-                ticks = int(f.read().rsplit(")", 1)[1].split()[19])
-            with open("/proc/uptime") as f:
-                trace.append(("mark", 0.0, f"process age {float(f.read().split()[0]) - ticks / os.sysconf('SC_CLK_TCK'):.2f} s at"))
-        except Exception:
-            pass
+class _Trace:
+    """NRV_CLI_TRACE=1: where the wall time of a `process_files` call goes, to the log.  Without it no method does anything."""
 
-    def mark(what):
-        if trace is not None:
-            trace.append(("mark", time.perf_counter() - t_start, what))
-    note = on_file or (lambda fn, ok: None)
-    # `reviser` may be a zero-argument factory: the engine is then created by the engine thread as its first task,
-    # i.e. WHILE the parser pool starts and the first reads are parsed (nrv_create: HIP context + weight packing,
-    # 0.15-0.3 s that used to precede everything else)
-    lazy = callable(reviser) and not hasattr(reviser, "predict_read")
-    box = {"rv": None if lazy else reviser}
-    # NRV_CLI_ENGINES=n: n engines on the same device, each driven by its own thread, so that the pipeline fill / drain
-    # of one engine's device call overlaps the other's kernels.  Measured (r03, 4000 reads, 16 launch groups per call):
-    # 1 engine 11.0, 2 engines 10.1-10.4, 3 engines 10.0 M bases/s end to end - the device is already the limit and the
-    # two engines' persistent kernels get in each other's way - so the default stays ONE; the knob is kept, tested.
-    import queue
-    import threading
-    n_eng = max(1, int(os.environ.get("NRV_CLI_ENGINES", "1"))) if lazy else 1
-    free = queue.Queue()                              # engines not inside a call
-    engines = []
-    if not lazy:
-        free.put(reviser)
-        engines.append(reviser)
-    stats_lock = threading.Lock()
-    native_threads = hostlib.load() is not None and os.environ.get("NRV_HOST_THREADS", "1") != "0"
-    nworkers = parser_pool_size(int(args.thread), usable_cores(), gpu_workers, len(files), native=native_threads) \
-        if core_share is None else parser_pool_size(int(args.thread), int(core_share), 1, len(files), native=native_threads)
-    stats["parser_workers"] = nworkers
-    jobs = [(os.path.join(args.fast5_base_dir, fn), fn, args.basecall_group, args.basecall_subgroup,
-             args.output_format == "fastq") for fn in files]
+    def __init__(self):
+        self.on, self.t_start, self.items = bool(os.environ.get("NRV_CLI_TRACE")), time.perf_counter(), []
+        if self.on:
+            try:                                      # age of this process: interpreter start, imports, main() so far
+                with open("/proc/self/stat") as f:
+                    ticks = int(f.read().rsplit(")", 1)[1].split()[19])
+                with open("/proc/uptime") as f:
+                    self.items.append(("mark", 0.0, f"process age {float(f.read().split()[0]) - ticks / os.sysconf('SC_CLK_TCK'):.2f} s at"))
+            except Exception:
+                pass
 
-    # Files per worker task: one task = one device call (>= kBatchEvents events at ~6.5 k events per read); the
-    # worker hands back the reads of a task already concatenated (`_load_bundle`).
-    # 16 launch groups per device call (r03, 4000 reads: 8 -> 7.6, 16 -> 10.2, 32 -> 10.3 M bases/s end to end: a call's
-    # pipeline fill / drain is paid once per call), but never so many reads per task that the workers run dry
-    kBatchEvents = int(os.environ.get("NRV_CLI_GROUPS", "16")) * max(int(getattr(args, "batch", 4096)), 1024)
-    per_task = max(1, min(32, kBatchEvents // 6500, -(-len(jobs) // (2 * nworkers))))
+    def mark(self, what):
+        if self.on:
+            self.items.append(("mark", time.perf_counter() - self.t_start, what))
 
-    pool = None
-    # With the native host stage (libnanorev_host.so) a task is ONE C call per bundle of files and one per finished read,
-    # both with the GIL released: the pool is THREADS of this process - nothing is spawned, nothing is pickled, a bundle's
-    # arrays are handed over by reference.  Without the library (or NRV_HOST_THREADS=0) the same tasks run in worker
-    # PROCESSES on the Python host stage, as in round 3.
-    stats["host_stage"] = "native, threads" if native_threads else ("python, processes" if hostlib.load() is None else "native, processes")
-    old_switch = None
-    if nworkers > 1 and len(files) >= 4 and native_threads:
-        from concurrent.futures import ThreadPoolExecutor as _TPE
-        pool = _TPE(nworkers)
-        # A pool thread coming back from its C call needs the GIL for ~0.1 ms of bookkeeping; with CPython's default
-        # switch interval (5 ms) it waited that long behind whichever thread held it, and four parser threads delivered
-        # what one does (r04: 3.2 M bases/s with 1, 4 or 8 threads; 10 / 13 M with 4 / 8 at 0.2 ms).  Restored on return.
-        # A process-global setting: only touched when the embedding caller has left it at CPython's default (a caller
-        # that tuned it keeps its value), NRV_SWITCH_INTERVAL=0 leaves it alone altogether, and it is restored on return.
+    def call_begin(self, t0):
+        if self.on:
+            self.items.append(("call", t0 - self.t_start, 0.0))
+            return len(self.items) - 1
+
+    def call_end(self, ti, t0):
+        if ti is not None:
+            self.items[ti] = ("call", t0 - self.t_start, time.perf_counter() - t0)
+
+    def log_summary(self, log, n_engines):
+        calls = sorted((c for c in self.items if c[0] == "call"), key=lambda c: c[1])
+        if self.items and not calls:                  # every file failed before a device call: only the marks
+            log("[trace] " + "; ".join(f"{w} {t:.3f} s" for k, t, w in self.items if k == "mark") + "; no device call")
+        if not calls:
+            return
+        t_end = time.perf_counter() - self.t_start
+        busy, idle, end = sum(c[2] for c in calls), 0.0, calls[0][1]
+        for _, t, d in calls:                         # time with NO engine inside a call, between the first and the last call
+            idle += max(0.0, t - end)
+            end = max(end, t + d)
+        log("[trace] " + "; ".join(f"{w} {t:.3f} s" for k, t, w in self.items if k == "mark"))
+        log(f"[trace] process_files {t_end:.3f} s: first device call at {calls[0][1]:.3f} s, {len(calls)} calls on "
+            f"{n_engines} engine(s), {busy:.3f} s summed, no call running for {idle:.3f} s, "
+            f"tail after the last call {t_end - end:.3f} s; first call {calls[0][2]:.3f} s, "
+            f"median call {sorted(c[2] for c in calls)[len(calls) // 2]:.4f} s")
+
+
+class _FileRun:
+    """One `process_files` call: its state and its three kinds of thread.  MAIN reads `results()`, packs device calls as
+    `_route_batch` says (`submit`) and collects the pooled finishers; the ENGINE thread(s) make the calls (`run_batch`, `collect`);
+    the one FINISHER thread merges, reports and writes, or hands that to the parser pool (`finish_batch`, `finish_call`)."""
+    def __init__(self, stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part):
+        self.args, self.log, self.note = args, log, on_file or (lambda fn, ok: None)
+        self.stats = {"reads": 0, "bases": 0, "failed": [], "host_s": 0.0, "engine_s": 0.0}
+        self.stats_lock = threading.Lock()
+        self.report = ReportPart(report_part)
+        self.rep_rows = {}                            # fn -> the row of a read whose output is not final yet
+        self.tie_eps = float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS))
+        self.trace = _Trace()
+        self.want_qual, self.spec = args.output_format == "fastq", _OutSpec(args)
+        # `reviser` may be a zero-argument factory: the engine is then created by the engine thread as its first task, WHILE
+        # the parser pool starts and the first reads are parsed (nrv_create: HIP context + weight packing, 0.15-0.3 s)
+        self.lazy = callable(reviser) and not hasattr(reviser, "predict_read")
+        self.factory, self.rv = reviser, (None if self.lazy else reviser)
+        # NRV_CLI_ENGINES=n: n engines on the same device, one thread each, so that one call's fill / drain overlaps the other's
+        # kernels.  Slower than one (HISTORY.md r03j: 10.1-10.4 against 11.0 M bases/s): the default stays ONE, the knob is tested.
+        self.n_eng = max(1, int(os.environ.get("NRV_CLI_ENGINES", "1"))) if self.lazy else 1
+        self.free, self.engines = queue.Queue(), []   # engines not inside a call; all engines
+        if not self.lazy:
+            self.free.put(reviser)
+            self.engines.append(reviser)
+        self.created = None                           # the future of the first engine's creation (lazy)
+        self.native_threads = hostlib.load() is not None and os.environ.get("NRV_HOST_THREADS", "1") != "0"
+        self.nworkers = parser_pool_size(int(args.thread), usable_cores(), gpu_workers, len(files), native=self.native_threads) \
+            if core_share is None else parser_pool_size(int(args.thread), int(core_share), 1, len(files), native=self.native_threads)
+        self.stats["parser_workers"] = self.nworkers
+        self.jobs = [(os.path.join(args.fast5_base_dir, fn), fn, args.basecall_group, args.basecall_subgroup,
+                      args.output_format == "fastq") for fn in files]
+        # One worker task = one device call of >= batch_events events (~6.5 k per read), handed back concatenated (`_load_bundle`):
+        # 16 launch groups (HISTORY.md r03: 8 -> 7.6, 16 -> 10.2, 32 -> 10.3 M bases/s), but never so many reads that the workers run dry
+        self.batch_events = int(os.environ.get("NRV_CLI_GROUPS", "16")) * max(int(getattr(args, "batch", 4096)), 1024)
+        self.per_task = max(1, min(32, self.batch_events // 6500, -(-len(self.jobs) // (2 * self.nworkers))))
+        self.finishing = []                           # (future, fn, rt, fq) of merges handed to the pool
+        self.pending = {}                             # id(engine) -> the call in flight on it: (ticket, batch, bundle, trace index, t0)
+        self.inflight = deque()                       # futures of the engine thread's tasks, oldest first
+        self.done = Future()                          # what an engine task returns when it handed nothing to the finisher
+        self.done.set_result(None)
+        self._start(stack, len(files))
+
+    def _start(self, stack, n_files):
+        """The parser pool - THREADS inside libnanorev_host.so (one C call per bundle and per finished read, GIL released), else
+        PROCESSES on the Python host stage -, the switches that depend on it, and the engine and finisher threads.  `stack`
+        undoes each step from the moment it is taken: the switch interval is restored and the pool never outlives the call."""
+        args, self.pool = self.args, None
+        self.stats["host_stage"] = "native, threads" if self.native_threads else \
+            ("python, processes" if hostlib.load() is None else "native, processes")
+        if self.nworkers > 1 and n_files >= 4 and self.native_threads:
+            # A pool thread back from its C call waits a switch interval for the GIL (r04: at 5 ms four threads deliver what one
+            # does).  Only touched when at CPython's default, never with NRV_SWITCH_INTERVAL=0 (INTEGRATION.md).
+            try:
+                want = float(os.environ.get("NRV_SWITCH_INTERVAL", kSwitchInterval))
+            except ValueError:
+                want = kSwitchInterval
+            if want > 0 and abs(sys.getswitchinterval() - 0.005) < 1e-9:
+                stack.callback(sys.setswitchinterval, sys.getswitchinterval())
+                sys.setswitchinterval(want)
+            self.pool = ThreadPoolExecutor(self.nworkers)
+        elif self.nworkers > 1 and n_files >= 4:
+            import multiprocessing as mp
+            for v in ("OPENBLAS_NUM_THREADS", "OMP_NUM_THREADS", "MKL_NUM_THREADS"):   # the workers never call BLAS (HISTORY.md r03)
+                os.environ.setdefault(v, "1")
+            self.pool = ProcessPoolExecutor(self.nworkers, mp_context=mp.get_context("spawn"))
+        if self.pool is not None:
+            stack.callback(self.pool.shutdown, wait=False, cancel_futures=True)
+        # PIPELINED two deep (r06): the engine thread enqueues bundle k+1 (nrv_reads_raw_begin) BEFORE it collects bundle k
+        self.pipelined = self.n_eng == 1 and os.environ.get("NRV_CLI_PIPELINE", "1") != "0"
+        self.native_pool = self.native_threads and self.pool is not None
+        # --device_stats / --device_merge: statistics, merge and records move into the pipelined call, and only there
+        self.device_stats = bool(getattr(args, "device_stats", False)) and self.pipelined and self.native_pool
+        self.device_merge = (bool(getattr(args, "device_merge", False)) and self.pipelined and self.native_pool
+                             and hostlib.has_write_records())
+        if self.device_stats:
+            self.stats["read_stats"] = "device"
+        if self.device_merge:
+            self.stats["merge"] = "device"
+        self.eng = stack.enter_context(ThreadPoolExecutor(self.n_eng))
+        self.fin = stack.enter_context(ThreadPoolExecutor(1))
+        if self.lazy:
+            self.created = self.eng.submit(self.create, True)
+        for _ in range(self.n_eng - 1):
+            self.eng.submit(self.create, False)
+
+    def create(self, first):
+        if not first and self.created.exception() is not None:       # one at a time, the first one first - or none
+            return
         try:
-            want = float(os.environ.get("NRV_SWITCH_INTERVAL", kSwitchInterval))
-        except ValueError:
-            want = kSwitchInterval
-        if want > 0 and abs(sys.getswitchinterval() - 0.005) < 1e-9:
-            old_switch = sys.getswitchinterval()
-            sys.setswitchinterval(want)
-    elif nworkers > 1 and len(files) >= 4:
-        import multiprocessing as mp
-        # The workers never call BLAS; without a cap every one of them starts, at `import numpy`, an OpenBLAS pool sized
-        # for the machine (256 CPUs on the GPU boxes, 16 in the cgroup): the first parsed reads came back after 0.73 s
-        # instead of 0.15 s (r03, scripts/gpu_cli_trace.sh).  Inherited through the environment of the spawned children.
-        for v in ("OPENBLAS_NUM_THREADS", "OMP_NUM_THREADS", "MKL_NUM_THREADS"):
-            os.environ.setdefault(v, "1")
-        pool = ProcessPoolExecutor(nworkers, mp_context=mp.get_context("spawn"))
+            rv = self.factory()
+        except BaseException as e:
+            if first:
+                raise                                 # no engine at all: loud (submit() re-raises it)
+            self.log(f"[s:::] a second engine on this device could not be created ({e!r}): continuing with one")
+            return
+        if first:
+            self.rv = rv
+        self.engines.append(rv)
+        self.free.put(rv)
+        self.trace.mark("engine created")
 
-    def results():
+    def end(self):
+        """Main thread, behind the last `submit`: everything in flight comes in, the pool ends in order."""
+        if self.pipelined:
+            self.inflight.append(self.eng.submit(self.flush_pipeline))
+        self.drain(0)
+        if self.created is not None:
+            self.created.result()
+        self.collect_finished(True)
+        if self.pool is not None:                     # all work is in: an orderly end of the workers (their queues' semaphores
+            self.pool.shutdown(wait=True)             # are released here, not left to the resource tracker)
+
+    def summary(self):
+        """After the threads have ended: the report part closed, the trace and the range guard logged; the statistics."""
+        self.report.close()
+        self.trace.log_summary(self.log, len(self.engines))
+        guarded = [rv for rv in self.engines if callable(getattr(rv, "saturated", None))]
+        if guarded:                                   # f16x2 range guard: stages re-run on the f32 kernels
+            self.stats["range_reruns"] = sum(int(rv.saturated()[1]) for rv in guarded)
+            if self.stats["range_reruns"]:
+                self.log(f"[s:::] {self.stats['range_reruns']} device stage(s) held out-of-range signal (spikes / tiny MAD) "
+                         "and were computed on the f32 kernels")
+        return self.stats
+
+    def results(self):
         """Yields (entries, bundle): `_load_one` tuples, and for pooled tasks their pre-concatenated raw reads."""
-        if pool is None:
-            for j in jobs:
+        if self.pool is None:
+            for j in self.jobs:
                 yield [_load_one(j)], None
             return
-        from collections import deque
-        pend = deque()
-        for k in range(0, len(jobs), per_task):
-            pend.append(pool.submit(_load_bundle, jobs[k:k + per_task], True) if device_stats
-                        else pool.submit(_load_bundle, jobs[k:k + per_task]))
+        pend, nw, per_task = deque(), self.nworkers, self.per_task
+        for k in range(0, len(self.jobs), per_task):
+            pend.append(self.pool.submit(_load_bundle, self.jobs[k:k + per_task], True) if self.device_stats
+                        else self.pool.submit(_load_bundle, self.jobs[k:k + per_task]))
             if k == 0:
-                mark("first task submitted (workers started)")
-            if len(pend) >= 3 * nworkers:
-                if len(pend) == 3 * nworkers and k == (3 * nworkers - 1) * per_task:
-                    mark("3 x workers tasks submitted")
+                self.trace.mark("first task submitted (workers started)")
+            if len(pend) >= 3 * nw:
+                if len(pend) == 3 * nw and k == (3 * nw - 1) * per_task:
+                    self.trace.mark("3 x workers tasks submitted")
                 yield pend.popleft().result()
-                if k == (3 * nworkers - 1) * per_task:
-                    mark("first bundle back")
+                if k == (3 * nw - 1) * per_task:
+                    self.trace.mark("first bundle back")
         while pend:
             yield pend.popleft().result()
 
-    def fallback(fn, rt, fq, e):                      # NanoReviser.py:146-152 / :173-179
-        stats["failed"].append(fn)
+    def fallback(self, fn, rt, fq, e):                # NanoReviser.py:146-152 / :173-179
+        args, log = self.args, self.log
+        self.stats["failed"].append(fn)
         log(f"[！！！Error] revising {fn.split('.')[0]}: {e}; writing the original basecalls")
         nw = 0
         try:
@@ -818,54 +934,58 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                 nw = len(orig)
         except Exception as e2:
             log(f"[！！！Error] stroring : {fn.split('.')[0]}_out.{args.output_format}...... {e2}")
-        if report:
-            rep_rows.pop(fn, None)
-            report.add(fn, False, unrevised_row(nw))
-        note(fn, False)
+        if self.report:
+            self.rep_rows.pop(fn, None)
+            self.report.add(fn, False, unrevised_row(nw))
+        self.note(fn, False)
 
-    want_qual = args.output_format == "fastq"
-
-    spec = _OutSpec(args)
-    finishing = []                                    # (future, fn, rt, fq) of merges handed to the pool
-
-    def finished(fn, nb):
-        stats["bases"] += nb
-        if report:
-            row = rep_rows.pop(fn, None)
+    def finished(self, fn, nb):
+        self.stats["bases"] += nb
+        if self.report:
+            row = self.rep_rows.pop(fn, None)
             if row is None:                           # cannot happen: every path that finishes a read stashes its row first
-                log(f"[！！！Warning] --report: no counts for {fn}")
-            report.add(fn, row is not None, row if row is not None else unrevised_row(nb))
-        if not args.test_mode:
-            log(f"[p:::] {fn.split('.')[0]}_out.{args.output_format} was saved......")
+                self.log(f"[！！！Warning] --report: no counts for {fn}")
+            self.report.add(fn, row is not None, row if row is not None else unrevised_row(nb))
+        if not self.args.test_mode:
+            self.log(f"[p:::] {fn.split('.')[0]}_out.{self.args.output_format} was saved......")
         else:
-            log("INFO Congratulations, NanoReviser is installed properly")
-        note(fn, True)
+            self.log("INFO Congratulations, NanoReviser is installed properly")
+        self.note(fn, True)
 
-    def finish_batch(batch, calls):
-        """Finisher thread.  With a worker pool the merge + file write of each read is a pool task (the calls and
-        the original bases are ~20 KB per read); without one it happens here."""
-        reviser = box["rv"]
-        for (fn, rt, fq), c in zip(batch, calls):
-            if isinstance(c, Exception):
-                fallback(fn, rt, fq, c)
-                continue
-            try:
-                if report:
-                    rep_rows[fn] = report_rows(reviser.T, rt.bases, [len(np.asarray(rt.bases))], *c, want_qual, tie_eps)[0]
-                if pool is not None:
-                    p1, p2, a1, a2 = c
-                    qc = phred_chars(p1, p2, a1, a2) if want_qual and len(a1) else None
-                    finishing.append((pool.submit(_finish_native if native_threads else _finish_in_worker, spec, reviser.T, fn,
-                                                  np.asarray(rt.bases), np.asarray(a1), np.asarray(a2), qc), fn, rt, fq))
-                    continue
-                seq, qual = _finish_read(reviser.T, rt, *c, want_qual=want_qual)
-                write_read(args, fn, seq, qual)
-                finished(fn, len(seq))
-            except Exception as e:
-                fallback(fn, rt, fq, e)
+    def submit(self, batch, bundle=None):
+        """One batch to the engine thread, in the packed form and on the route `_route_batch` gives.  The NumPy half of the device
+        call (descriptors, output arrays, concatenation) happens HERE, while the engine thread is inside the previous call."""
+        if self.created is not None:
+            self.created.result()                     # raises what the factory raised: loud, no fallback engine
+        rv, cls, packed = self.rv, type(self.rv), None
+        try:
+            if bundle is not None and "device_stats" in bundle and not (hasattr(rv, "run_packed_raw") and hasattr(rv, "with_device_stats")):
+                bundle = _bundle_host_stats(bundle)   # an engine without the new calls: the host computes them after all
+            form, route = _route_batch(rv, bundle, len(batch), self.pipelined, self.native_pool, self.device_merge, bool(self.report))
+            if form is not None and bundle is None:
+                packed = prepare_many(cls, [rt for _, rt, _ in batch], rv.T)
+            elif form is not None:
+                packed = cls.pack_bundle(bundle["raw"], bundle["starts"], bundle["feat"], bundle["meta"], rv.T)
+                if "device_stats" in bundle:
+                    packed = cls.with_device_stats(packed, bundle["last_dur"], bundle["device_stats"])
+                if form != len(packed):               # a merge form: alone, taken back, or - --report - counted on the device too
+                    packed = cls.with_device_merge(packed, bundle["bases"], self.want_qual)
+                    if form != len(packed):
+                        packed = _host_merge_form(packed) if form == "host-merge" else cls.with_device_report(packed, self.tie_eps)
+        except Exception:
+            packed = None
+        if packed is None:
+            route = "predict_many"                    # (one read: `predict_one`)
+        self.inflight.append(self.eng.submit(self.run_batch, batch, packed, bundle, route))
+        self.drain(self.n_eng + 1)
 
-    def collect_finished(block):
+    def drain(self, limit):
+        while len(self.inflight) > limit:
+            self.inflight.popleft().result().result()
+
+    def collect_finished(self, block):
         """Results of the pooled merges (main thread).  An entry is one read, or (fn is a list) all reads of a device call."""
+        finishing = self.finishing
         while finishing and (block or finishing[0][0].done()):
             fut, fn, rt, fq = finishing.pop(0)
             many = isinstance(fn, list)
@@ -875,291 +995,171 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                 res = [(0, repr(e))] * len(fn) if many else (0, repr(e))
             for (nb, err), f1, r1, q1 in (zip(res, fn, rt, fq) if many else [(res, fn, rt, fq)]):
                 if err is None:
-                    finished(f1, nb)
+                    self.finished(f1, nb)
                 else:
-                    fallback(f1, r1, q1, err)
+                    self.fallback(f1, r1, q1, err)
 
-    def finish_bundle(batch, bundle, outs):
-        """Finisher thread, native host stage: merge + record + file of ALL reads of a device call as one pool task."""
-        reviser = box["rv"]
+    def finish_batch(self, batch, calls):
+        """Read by read: with a worker pool the merge + file write is a pool task (~20 KB per read), without one it happens here."""
+        T = self.rv.T
+        for (fn, rt, fq), c in zip(batch, calls):
+            if isinstance(c, Exception):
+                self.fallback(fn, rt, fq, c)
+                continue
+            try:
+                if self.report:
+                    self.rep_rows[fn] = report_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual, self.tie_eps)[0]
+                if self.pool is not None:
+                    p1, p2, a1, a2 = c
+                    qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
+                    task = self.pool.submit(_finish_native if self.native_threads else _finish_in_worker, self.spec, T, fn,
+                                            np.asarray(rt.bases), np.asarray(a1), np.asarray(a2), qc)
+                    self.finishing.append((task, fn, rt, fq))
+                    continue
+                seq, qual = _finish_read(T, rt, *c, want_qual=self.want_qual)
+                write_read(self.args, fn, seq, qual)
+                self.finished(fn, len(seq))
+            except Exception as e:
+                self.fallback(fn, rt, fq, e)
+
+    def finish_call(self, batch, bundle, outs, merged):
+        """ALL reads of a device call as one pool task: merge + record + file (nrvh_finish_bundle), or - merged, a --device_merge
+        call that came back as revised reads - record + file alone (nrvh_write_records)."""
         try:
-            p1, p2, a1, a2 = outs
-            if report:
-                rows = report_rows(reviser.T, bundle["bases"], bundle["meta"][:, 1].astype(np.int64), p1, p2, a1, a2, want_qual, tie_eps)
-                rep_rows.update((fn, rows[i]) for i, (fn, _, _) in enumerate(batch))
-            qc = phred_chars(p1, p2, a1, a2) if want_qual and len(a1) else None
-            fut = pool.submit(_finish_bundle_native, spec, reviser.T, [fn for fn, _, _ in batch], bundle["bases"],
-                              bundle["meta"][:, 1].astype(np.int64), a1, a2, qc)
-            finishing.append((fut, [fn for fn, _, _ in batch], [rt for _, rt, _ in batch], [fq for _, _, fq in batch]))
+            fns, rts, fqs = map(list, zip(*batch))
+            if merged:
+                if self.report:                       # a `with_device_report` call: the rows were counted behind the merge
+                    self.rep_rows.update(zip(fns, outs[3]))
+                fut = self.pool.submit(_write_records_native, self.spec, fns, outs[0], outs[1] if self.want_qual else None, outs[2])
+            else:
+                p1, p2, a1, a2 = outs
+                T, ev_len = self.rv.T, bundle["meta"][:, 1].astype(np.int64)
+                if self.report:
+                    self.rep_rows.update(zip(fns, report_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2, self.want_qual, self.tie_eps)))
+                qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
+                fut = self.pool.submit(_finish_bundle_native, self.spec, T, fns, bundle["bases"], ev_len, a1, a2, qc)
+            self.finishing.append((fut, fns, rts, fqs))
         except Exception as e:
             for fn, rt, fq in batch:
-                fallback(fn, rt, fq, e)
+                self.fallback(fn, rt, fq, e)
 
-    def finish_merged(batch, outs):
-        """Finisher thread, --device_merge: the call came back as revised reads; their records and files are one pool task."""
-        try:
-            seq, qual, off = outs[:3]
-            if report:                                # a `with_device_report` call: the rows were counted behind the merge
-                rep_rows.update((fn, outs[3][i]) for i, (fn, _, _) in enumerate(batch))
-            fut = pool.submit(_write_records_native, spec, [fn for fn, _, _ in batch], seq, qual if want_qual else None, off)
-            finishing.append((fut, [fn for fn, _, _ in batch], [rt for _, rt, _ in batch], [fq for _, _, fq in batch]))
-        except Exception as e:
-            for fn, rt, fq in batch:
-                fallback(fn, rt, fq, e)
+    def engine_time(self, t0, ti=None, t_call=None):
+        """Books the engine time since t0; with a trace index, the end of that device call (begun at t_call, else t0) as well."""
+        with self.stats_lock:
+            self.stats["engine_s"] += time.perf_counter() - t0
+        self.trace.call_end(ti, t0 if t_call is None else t_call)
 
-    def run_batch(batch, packed=None, bundle=None):
-        """Engine thread: one device call for the batch; merging and writing go to the finisher."""
-        reviser = free.get()                          # an engine that is not inside a call (all have the same T, weights)
-        try:
-            return run_batch_on(reviser, batch, packed, bundle)
-        finally:
-            free.put(reviser)
-
-    # Device calls PIPELINED two deep (r06; one engine, native bundles; NRV_CLI_PIPELINE=0: one call at a time as before): the
-    # engine thread enqueues bundle k+1 (nrv_reads_raw_begin: inputs copied, every stage enqueued) BEFORE it collects bundle k
-    # (nrv_reads_raw_end), so the device never waits for a call's fill, drain or the Python between two calls.
-    pipelined = n_eng == 1 and os.environ.get("NRV_CLI_PIPELINE", "1") != "0"
-    # --device_stats / NRV_DEVICE_STATS=1: the native loader skips the read statistics and the pipelined call computes them
-    # (nrv_reads_raw_stats_begin).  Only on this path - one engine, pipelined, native bundles from the thread pool; every
-    # other path is fed by the host as before.
-    device_stats = bool(getattr(args, "device_stats", False)) and pipelined and native_threads and pool is not None
-    if device_stats:
-        stats["read_stats"] = "device"
-    # --device_merge / NRV_DEVICE_MERGE=1: the same path's call merges, scores and packs its reads on the device
-    # (nrv_revise_reads_raw_begin) and its finisher is one nrvh_write_records task.  Needs both libraries' new symbols.
-    device_merge = (bool(getattr(args, "device_merge", False)) and pipelined and native_threads and pool is not None
-                    and hostlib.has_write_records())
-    if device_merge:
-        stats["merge"] = "device"
-    pending = {}                                      # id(engine) -> the call in flight on it: (ticket, batch, bundle, trace index, t0)
-
-    def _done():
-        from concurrent.futures import Future
-        f = Future()
-        f.set_result(None)
-        return f
-
-    def collect(reviser, item):
-        """Second half of a pipelined call: wait for it, hand its reads to the finisher; a failure is isolated read by read
-        on the synchronous path, exactly as for an unpipelined call."""
+    def collect(self, reviser, item):
+        """Second half of a pipelined call: wait for it, hand its reads to the finisher; a failure is isolated read by read."""
         tk, batch, bundle, ti, t_begin = item
         t0 = time.perf_counter()
         try:
             outs = reviser.end_packed_raw(tk)
         except Exception:
             # the per-read retries are other entry points of the handle: first collect the call that was enqueued behind this one
-            nxt = pending.pop(id(reviser), None)
+            nxt = self.pending.pop(id(reviser), None)
             if nxt is not None:
-                collect(reviser, nxt)
-            calls = []
-            for rt in _bundle_reads(bundle):
-                try:
-                    calls.append(predict_one(reviser, rt))
-                except Exception as e:
-                    calls.append(e)
-            with stats_lock:
-                stats["engine_s"] += time.perf_counter() - t0
-            return fin.submit(finish_batch, batch, calls)         # (the finisher is one thread: behind nxt's hand-over)
-        with stats_lock:
-            stats["engine_s"] += time.perf_counter() - t0
-        if ti is not None:
-            trace[ti] = ("call", t_begin - t_start, time.perf_counter() - t_begin)
-        if isinstance(tk, tuple) and len(tk) == 3:    # a --device_merge call: (seq, qual, off)
-            return fin.submit(finish_merged, batch, outs)
-        return fin.submit(finish_bundle, batch, bundle, outs)
+                self.collect(reviser, nxt)
+            calls = _predict_each(reviser, _bundle_reads(bundle))
+            self.engine_time(t0)
+            return self.fin.submit(self.finish_batch, batch, calls)      # (the finisher is one thread: behind nxt's hand-over)
+        self.engine_time(t0, ti, t_begin)
+        return self.fin.submit(self.finish_call, batch, bundle, outs, _is_merged_ticket(tk))
 
-    def flush_pipeline():
-        """Engine thread, behind the last batch: whatever is still in flight."""
-        last = _done()
-        for rv in list(engines):
-            item = pending.pop(id(rv), None)
+    def flush_pipeline(self):
+        """Behind the last batch: whatever is still in flight."""
+        last = self.done
+        for rv in list(self.engines):
+            item = self.pending.pop(id(rv), None)
             if item is not None:
-                last = collect(rv, item)
+                last = self.collect(rv, item)
         return last
 
-    def run_batch_on(reviser, batch, packed, bundle):
-        t0 = time.perf_counter()
-        ti = None
-        if trace is not None:
-            ti = len(trace)
-            trace.append(("call", t0 - t_start, 0.0))
-        rts = None
-        prev = pending.pop(id(reviser), None)
-        if (pipelined and bundle is not None and packed is not None and native_threads and pool is not None
-                and hasattr(reviser, "begin_packed_raw") and "bases" in bundle
-                and len(bundle["bases"]) == int(bundle["meta"][:, 1].sum())):
-            try:
-                tk = reviser.begin_packed_raw(packed)
-            except Exception:
-                tk = None                             # e.g. a handle that could not grow its buffers: the synchronous path decides
-            if tk is not None:
-                pending[id(reviser)] = (tk, batch, bundle, ti, t0)
-                with stats_lock:
-                    stats["engine_s"] += time.perf_counter() - t0
-                return collect(reviser, prev) if prev is not None else _done()
-        if prev is not None:                          # between a call's two halves nothing else may run on its handle
-            collect(reviser, prev)
-        packed = _host_merge_form(packed)             # every path below merges on the host
-
-        def reads():                                  # the reads as tensors: only the per-read paths need them
-            return _bundle_reads(bundle) if bundle is not None else [rt for _, rt, _ in batch]
+    def run_batch(self, batch, packed, bundle, route):
+        """One device call for the batch on an engine that is not inside a call (all have the same T, weights): the routes of
+        `_route_batch` with their fall-throughs (its note [3]); merging and writing go to the finisher."""
+        reviser = self.free.get()
         try:
-            if bundle is not None and packed is not None:
-                p1, p2, a1, a2 = reviser.run_packed_raw(packed)
-                if native_threads and pool is not None and "bases" in bundle and len(bundle["bases"]) == int(bundle["meta"][:, 1].sum()):
-                    with stats_lock:
-                        stats["engine_s"] += time.perf_counter() - t0
-                    if ti is not None:
-                        trace[ti] = ("call", t0 - t_start, time.perf_counter() - t0)
-                    return fin.submit(finish_bundle, batch, bundle, (p1, p2, a1, a2))
-                calls, e0, T = [], 0, reviser.T
-                for rl, el, _, _ in bundle["meta"]:        # window i of a read == window e0 + i of the bundle
-                    n = max(int(el) - T, 0)
-                    calls.append((p1[e0:e0 + n], p2[e0:e0 + n], a1[e0:e0 + n], a2[e0:e0 + n]))
-                    e0 += int(el)
-            else:
-                rts = reads()
-                calls = predict_many(reviser, rts, packed)
-        except Exception:
-            calls = []
-            for rt in (rts if rts is not None else reads()):   # isolate the failing read(s)
+            t0 = time.perf_counter()
+            ti = self.trace.call_begin(t0)
+            prev = self.pending.pop(id(reviser), None)
+            if route == "pipelined":
                 try:
-                    calls.append(predict_one(reviser, rt))
-                except Exception as e:
-                    calls.append(e)
-        with stats_lock:
-            stats["engine_s"] += time.perf_counter() - t0
-        if ti is not None:
-            trace[ti] = ("call", t0 - t_start, time.perf_counter() - t0)
-        return fin.submit(finish_batch, batch, calls)
+                    tk = reviser.begin_packed_raw(packed)
+                except Exception:
+                    tk = None                             # e.g. a handle that could not grow its buffers: the synchronous path decides
+                if tk is not None:
+                    self.pending[id(reviser)] = (tk, batch, bundle, ti, t0)
+                    self.engine_time(t0)
+                    return self.collect(reviser, prev) if prev is not None else self.done
+                route = "packed+finish_bundle"
+            if prev is not None:                          # between a call's two halves nothing else may run on its handle
+                self.collect(reviser, prev)
+            packed = _host_merge_form(packed)             # every route below merges on the host
+            rts = None
+            try:
+                if route in ("packed+finish_bundle", "packed sliced"):
+                    p1, p2, a1, a2 = reviser.run_packed_raw(packed)
+                    if route == "packed+finish_bundle":
+                        self.engine_time(t0, ti)
+                        return self.fin.submit(self.finish_call, batch, bundle, (p1, p2, a1, a2), False)
+                    calls = _slice_calls((p1, p2, a1, a2), bundle["meta"][:, 1], reviser.T)
+                else:                                     # predict_many / per-read: the reads as tensors
+                    rts = _bundle_reads(bundle) if bundle is not None else [rt for _, rt, _ in batch]
+                    calls = predict_many(reviser, rts, packed)
+            except Exception:                             # isolate the failing read(s)
+                calls = _predict_each(reviser, rts if rts is not None else
+                                      _bundle_reads(bundle) if bundle is not None else [rt for _, rt, _ in batch])
+            self.engine_time(t0, ti)
+            return self.fin.submit(self.finish_batch, batch, calls)
+        finally:
+            self.free.put(reviser)
 
-    # reads are grouped into device calls of >= kBatchEvents events; the engine runs in its own
-    # thread (the C-ABI call releases the GIL) so unpickling the next reads overlaps the device
-    from concurrent.futures import ThreadPoolExecutor
-    from collections import deque
-    inflight = deque()
+
+def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None],
+                  on_file: Optional[Callable[[str, bool], None]] = None, gpu_workers: int = 1,
+                  core_share: Optional[int] = None, report_part: Optional[str] = None) -> dict:
+    """Revise `files` (names inside args.fast5_base_dir) with one engine.  The host stage (HDF5 parsing, event collapse,
+    statistics) runs --thread parser workers that stay a bounded number of reads ahead of the device: THREADS of this process
+    inside libnanorev_host.so (at most kNativePoolMax), or PROCESSES on the Python host stage without it / with NRV_HOST_THREADS=0.
+    on_file(fn, revised): called once per file when its output is final (revised, or the original
+    basecalls after a failure; revised=False also for files that could not be parsed at all).
+    gpu_workers: how many such calls run on this host at the same time (one per GPU, `run_workers`): the cores are
+    SHARED, so each call's parser pool gets usable_cores() // gpu_workers of them - eight workers on a 16-core cgroup
+    start 8 x 2 parser workers, not 8 x 16.  core_share: this call's cores, when the caller has already
+    divided them (a GPU worker pinned to its NUMA slice: `_worker`).  report_part (--report): the file this call appends
+    one line per read to, ahead of on_file (`ReportPart`)."""
     import contextlib
-    with contextlib.ExitStack() as stack:
-        if old_switch is not None:
-            stack.callback(lambda: sys.setswitchinterval(old_switch))
-        if pool is not None:                          # whatever happens below, the parser pool does not outlive us
-            stack.callback(lambda: pool.shutdown(wait=False, cancel_futures=True))
-        eng = stack.enter_context(ThreadPoolExecutor(n_eng))
-        fin = stack.enter_context(ThreadPoolExecutor(1))
-
-        def create(first):
-            try:
-                rv = reviser()
-            except BaseException as e:
-                if first:
-                    raise                             # no engine at all: loud (submit() re-raises it)
-                log(f"[s:::] a second engine on this device could not be created ({e!r}): continuing with one")
-                return
-            if first:
-                box["rv"] = rv
-            engines.append(rv)
-            free.put(rv)
-            mark("engine created")
-
-        def create_next():
-            try:
-                created.result()                      # one at a time, the first one first
-            except BaseException:
-                return
-            create(False)
-        created = eng.submit(create, True) if lazy else None
-        for _ in range(n_eng - 1):
-            eng.submit(create_next)
-
-        def submit(batch, bundle=None):
-            # the NumPy half of the device call (descriptors, output arrays; for unbundled reads also the concatenation)
-            # happens HERE, in the main thread, while the engine thread is inside the previous batch's call
-            if created is not None:
-                created.result()                      # raises what the factory raised: loud, no fallback engine
-            rv = box["rv"]
-            packed = None
-            try:
-                if bundle is not None and "device_stats" in bundle and not (hasattr(rv, "run_packed_raw") and hasattr(rv, "with_device_stats")):
-                    bundle = _bundle_host_stats(bundle)   # an engine without the new calls: the host computes them after all
-                if bundle is not None and hasattr(rv, "run_packed_raw"):
-                    packed = type(rv).pack_bundle(bundle["raw"], bundle["starts"], bundle["feat"], bundle["meta"], rv.T)
-                    if "device_stats" in bundle:
-                        packed = type(rv).with_device_stats(packed, bundle["last_dur"], bundle["device_stats"])
-                    if (device_merge and hasattr(rv, "with_device_merge") and "bases" in bundle
-                            and len(bundle["bases"]) == int(bundle["meta"][:, 1].sum())):
-                        packed = type(rv).with_device_merge(packed, bundle["bases"], want_qual)
-                        # --report: counted on the device as well, or - an engine without that call - the whole bundle on the host
-                        packed = type(rv).with_device_report(packed, tie_eps) if report and hasattr(rv, "with_device_report") \
-                            else (_host_merge_form(packed) if report else packed)
-                elif bundle is None and len(batch) > 1:
-                    packed = prepare_many(type(rv), [rt for _, rt, _ in batch], rv.T)
-            except Exception:
-                packed = None
-            return eng.submit(run_batch, batch, packed, bundle)
-
-        def drain(limit):
-            while len(inflight) > limit:
-                inflight.popleft().result().result()
-
-        batch, nev = [], 0
-        for entries, bundle in results():
+    with contextlib.ExitStack() as stack:             # its exit ends the run's threads and undoes what `_FileRun._start` did
+        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part)
+        batch, nev = [], 0                            # unbundled reads are grouped into device calls of >= batch_events events
+        for entries, bundle in run.results():
             bundled = []
             for k, (fn, rt, fq, err, dt) in enumerate(entries):
-                stats["host_s"] += dt
-                stats["reads"] += 1
-                if rt is None:
+                run.stats["host_s"] += dt
+                run.stats["reads"] += 1
+                if rt is None:                        # could not be parsed at all: nothing to write
                     log(f"！！！[Error] fast5 file: {fn.split('.')[0]} {err}")
-                    stats["failed"].append(fn)
-                    report.add(fn, False, unrevised_row(0))
-                    note(fn, False)
-                    continue
-                if err is not None:
-                    fallback(fn, rt, fq, err)
-                    continue
-                if bundle is not None and k in bundle["idx"]:
+                    run.stats["failed"].append(fn)
+                    run.report.add(fn, False, unrevised_row(0))
+                    run.note(fn, False)
+                elif err is not None:
+                    run.fallback(fn, rt, fq, err)
+                elif bundle is not None and k in bundle["idx"]:
                     bundled.append((fn, rt, fq))
-                    continue
-                batch.append((fn, rt, fq))           # unbundled reads (sequential mode, non-int16 signals)
-                nev += len(rt.feat_ev)
-                if nev >= kBatchEvents:
-                    inflight.append(submit(batch))
-                    batch, nev = [], 0
-                    drain(n_eng + 1)
+                else:
+                    batch.append((fn, rt, fq))       # unbundled reads (sequential mode, non-int16 signals)
+                    nev += len(rt.feat_ev)
+                    if nev >= run.batch_events:
+                        run.submit(batch)
+                        batch, nev = [], 0
             if bundled:
-                inflight.append(submit(bundled, bundle))
-                drain(n_eng + 1)
-            collect_finished(False)
+                run.submit(bundled, bundle)
+            run.collect_finished(False)
         if batch:
-            inflight.append(submit(batch))
-        if pipelined:
-            inflight.append(eng.submit(flush_pipeline))
-        drain(0)
-        if created is not None:
-            created.result()
-        collect_finished(True)
-        if pool is not None:                          # all work is in: an orderly end of the workers (their queues' semaphores
-            pool.shutdown(wait=True)                  # are released here, not left to the resource tracker)
-    report.close()
-    calls = sorted((c for c in trace if c[0] == "call"), key=lambda c: c[1]) if trace else []
-    if trace and not calls:                           # every file failed before a device call: only the marks
-        log("[trace] " + "; ".join(f"{w} {t:.3f} s" for k, t, w in trace if k == "mark") + "; no device call")
-    if calls:
-        t_end = time.perf_counter() - t_start
-        busy, idle, end = sum(c[2] for c in calls), 0.0, calls[0][1]
-        for _, t, d in calls:                         # time with NO engine inside a call, between the first and the last call
-            idle += max(0.0, t - end)
-            end = max(end, t + d)
-        log("[trace] " + "; ".join(f"{w} {t:.3f} s" for k, t, w in trace if k == "mark"))
-        log(f"[trace] process_files {t_end:.3f} s: first device call at {calls[0][1]:.3f} s, {len(calls)} calls on "
-            f"{len(engines)} engine(s), {busy:.3f} s summed, no call running for {idle:.3f} s, "
-            f"tail after the last call {t_end - end:.3f} s; first call {calls[0][2]:.3f} s, "
-            f"median call {sorted(c[2] for c in calls)[len(calls) // 2]:.4f} s")
-    if any(callable(getattr(rv, "saturated", None)) for rv in engines):   # f16x2 range guard: stages re-run on the f32 kernels
-        stats["range_reruns"] = sum(int(rv.saturated()[1]) for rv in engines if callable(getattr(rv, "saturated", None)))
-        if stats["range_reruns"]:
-            log(f"[s:::] {stats['range_reruns']} device stage(s) held out-of-range signal (spikes / tiny MAD) "
-                "and were computed on the f32 kernels")
-    return stats
+            run.submit(batch)
+        run.end()
+    return run.summary()
 
 
 def _default_factory(args, device: int):

@@ -57,6 +57,41 @@ class _ReadDesc(C.Structure):
                 ("shift", C.c_double), ("scale", C.c_double)]
 
 
+_FP, _DP = C.POINTER(C.c_float), C.POINTER(C.c_double)
+_I8P, _U8P, _I16P, _I32P = C.POINTER(C.c_int8), C.POINTER(C.c_uint8), C.POINTER(C.c_int16), C.POINTER(C.c_int32)
+_I64P, _U64P = C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+
+
+def _ptr(a, typ):
+    """The C pointer to a NumPy array's data; None (NULL) for None."""
+    return None if a is None else a.ctypes.data_as(typ)
+
+
+def _marshal(values, types):
+    """Python values -> C arguments of `types`: arrays (or None) to pointers, a float to c_float, the rest as it is."""
+    return [_ptr(v, typ) if issubclass(typ, C._Pointer) else (typ(v) if typ is C.c_float else v) for v, typ in zip(values, types)]
+
+
+# The raw-read family (include/nanorev.h).  Every entry point takes the head, then some of the blocks below in this order; its
+# *_begin form ends with the ticket.  A block is (C types, where a packed tuple holds the values).  `load_library` declares the
+# signatures and `Reviser._raw_call` marshals the calls from the same table, so neither two signatures nor a signature and its
+# call can drift apart.
+_RAW_HEAD_T = [C.c_void_p, _I16P, C.c_int64, _I32P, _FP, C.c_int64, C.POINTER(_ReadDesc), C.c_int]
+_CALLS = ([_FP, _FP, _I8P, _I8P], lambda p: p[6])                                        # p1, p2, a1, a2
+_STATS = ([_I32P, _U8P], lambda p: p[7:9])                                               # last_dur, on_device
+_MERGE = ([_U8P, _FP, _U8P, _U8P, _I64P], lambda p: (p[9], p[10]) + tuple(p[11]))        # bases, q_thr, seq, qual, off
+_REPORT = ([C.c_float, _U64P], lambda p: p[12:14])                                       # tie_eps, report
+# len(packed) -> (synchronous symbol, begin symbol, blocks, whether the call returns merged reads: (seq, qual, off[, report]))
+_RAW_FORMS = {
+    7: ("nrv_predict_reads_raw", "nrv_reads_raw_begin", (_CALLS,), False),
+    9: ("nrv_predict_reads_raw_stats", "nrv_reads_raw_stats_begin", (_STATS, _CALLS), False),
+    12: ("nrv_revise_reads_raw", "nrv_revise_reads_raw_begin", (_STATS, _MERGE), True),
+    14: ("nrv_revise_reads_raw_report", "nrv_revise_reads_raw_report_begin", (_STATS, _MERGE, _REPORT), True),
+}
+_READS_HEAD_T = _RAW_HEAD_T[:4] + [C.c_int64, C.POINTER(_ReadDesc), C.c_int]     # nrv_segment_reads, nrv_read_stats: no features
+_MERGE_CALLS_T = [C.c_void_p, _U8P, _I64P, C.c_int, _I8P, _I8P, _FP, _FP, C.c_int64] + _MERGE[0][1:]   # nrv_merge_calls
+
+
 _lib = None
 
 
@@ -107,7 +142,7 @@ def load_library(path: Optional[str] = None):
                       "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     _one_hip_runtime()
     lib = C.CDLL(p)
-    fp, i8p, vp = C.POINTER(C.c_float), C.POINTER(C.c_int8), C.c_void_p
+    fp, i8p, vp = _FP, _I8P, C.c_void_p
     lib.nrv_create.argtypes = [C.POINTER(_Weights), C.POINTER(_Weights), C.c_int, C.c_int, C.c_int,
                                C.POINTER(vp)]
     lib.nrv_create.restype = C.c_int
@@ -134,36 +169,17 @@ def load_library(path: Optional[str] = None):
     lib.nrv_backend.argtypes = [vp]
     lib.nrv_window.argtypes = [vp]
     lib.nrv_device_count.argtypes = []
-    i16p, i32p, rdp = C.POINTER(C.c_int16), C.POINTER(C.c_int32), C.POINTER(_ReadDesc)
-    lib.nrv_predict_reads_raw.argtypes = [vp, i16p, C.c_int64, i32p, fp, C.c_int64, rdp, C.c_int, fp, fp, i8p, i8p]
-    lib.nrv_reads_raw_begin.argtypes = [vp, i16p, C.c_int64, i32p, fp, C.c_int64, rdp, C.c_int, fp, fp, i8p, i8p, C.POINTER(C.c_int)]
-    lib.nrv_reads_raw_begin.restype = C.c_int
+    have_report = hasattr(lib, "nrv_merge_calls_report")   # by presence: NRV_LIB may name an older build of the same ABI
+    for sync, begin, blocks, _ in _RAW_FORMS.values():  # (every restype is ctypes' default, int: the nrv_* status)
+        if have_report or _REPORT not in blocks:
+            getattr(lib, sync).argtypes = _RAW_HEAD_T + [t for types, _ in blocks for t in types]
+            getattr(lib, begin).argtypes = getattr(lib, sync).argtypes + [C.POINTER(C.c_int)]
+    lib.nrv_merge_calls.argtypes = _MERGE_CALLS_T
+    if have_report:
+        lib.nrv_merge_calls_report.argtypes = _MERGE_CALLS_T + _REPORT[0]
     lib.nrv_reads_raw_end.argtypes = [vp, C.c_int]
-    lib.nrv_reads_raw_end.restype = C.c_int
-    lib.nrv_segment_reads.argtypes = [vp, i16p, C.c_int64, i32p, C.c_int64, rdp, C.c_int, fp]
-    u8p, dp = C.POINTER(C.c_uint8), C.POINTER(C.c_double)
-    lib.nrv_predict_reads_raw_stats.argtypes = [vp, i16p, C.c_int64, i32p, fp, C.c_int64, rdp, C.c_int, i32p, u8p, fp, fp, i8p, i8p]
-    lib.nrv_predict_reads_raw_stats.restype = C.c_int
-    lib.nrv_reads_raw_stats_begin.argtypes = [vp, i16p, C.c_int64, i32p, fp, C.c_int64, rdp, C.c_int, i32p, u8p, fp, fp, i8p, i8p,
-                                              C.POINTER(C.c_int)]
-    lib.nrv_reads_raw_stats_begin.restype = C.c_int
-    lib.nrv_read_stats.argtypes = [vp, i16p, C.c_int64, i32p, C.c_int64, rdp, C.c_int, i32p, dp, dp, dp, dp, fp]
-    lib.nrv_read_stats.restype = C.c_int
-    i64p = C.POINTER(C.c_int64)
-    lib.nrv_revise_reads_raw.argtypes = [vp, i16p, C.c_int64, i32p, fp, C.c_int64, rdp, C.c_int, i32p, u8p, u8p, fp, u8p, u8p, i64p]
-    lib.nrv_revise_reads_raw.restype = C.c_int
-    lib.nrv_revise_reads_raw_begin.argtypes = lib.nrv_revise_reads_raw.argtypes + [C.POINTER(C.c_int)]
-    lib.nrv_revise_reads_raw_begin.restype = C.c_int
-    lib.nrv_merge_calls.argtypes = [vp, u8p, i64p, C.c_int, i8p, i8p, fp, fp, C.c_int64, fp, u8p, u8p, i64p]
-    lib.nrv_merge_calls.restype = C.c_int
-    if hasattr(lib, "nrv_merge_calls_report"):          # by presence: NRV_LIB may name an older build of the same ABI
-        u64p = C.POINTER(C.c_uint64)
-        lib.nrv_revise_reads_raw_report.argtypes = lib.nrv_revise_reads_raw.argtypes + [C.c_float, u64p]
-        lib.nrv_revise_reads_raw_report.restype = C.c_int
-        lib.nrv_revise_reads_raw_report_begin.argtypes = lib.nrv_revise_reads_raw_report.argtypes + [C.POINTER(C.c_int)]
-        lib.nrv_revise_reads_raw_report_begin.restype = C.c_int
-        lib.nrv_merge_calls_report.argtypes = lib.nrv_merge_calls.argtypes + [C.c_float, u64p]
-        lib.nrv_merge_calls_report.restype = C.c_int
+    lib.nrv_segment_reads.argtypes = _READS_HEAD_T + [fp]
+    lib.nrv_read_stats.argtypes = _READS_HEAD_T + [_I32P, _DP, _DP, _DP, _DP, fp]
     lib.nrv_prof_overhead.argtypes = [vp, C.POINTER(C.c_double)]
     lib.nrv_saturated.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.nrv_set_precision.argtypes = [vp, C.c_int]
@@ -183,6 +199,11 @@ def _as_f32(a, shape_tail):
     if a.ndim >= 1 and tuple(a.shape[-len(shape_tail):]) != tuple(shape_tail):
         raise ValueError(f"expected trailing shape {shape_tail}, got {a.shape}")
     return a
+
+
+def _empty_calls(n):
+    """The output arrays of a call over n windows: (p1, p2, a1, a2)."""
+    return np.empty((n, 6), np.float32), np.empty((n, 5), np.float32), np.empty(n, np.int8), np.empty(n, np.int8)
 
 
 class _ModelFacade:
@@ -258,15 +279,9 @@ class Reviser:
         signal_x = np.ascontiguousarray(signal_x, dtype=np.float32).reshape(n, self.T, 50)
         if batch_size:
             self.set_batch(int(batch_size))
-        p1 = np.empty((n, 6), np.float32)
-        p2 = np.empty((n, 5), np.float32)
-        a1 = np.empty(n, np.int8)
-        a2 = np.empty(n, np.int8)
-        fp, i8p = C.POINTER(C.c_float), C.POINTER(C.c_int8)
-        self._check(self._lib.nrv_predict(
-            self._h, signal_x.ctypes.data_as(fp), read_x.ctypes.data_as(fp), n,
-            p1.ctypes.data_as(fp), p2.ctypes.data_as(fp), a1.ctypes.data_as(i8p), a2.ctypes.data_as(i8p)))
-        return p1, p2, a1, a2
+        out = _empty_calls(n)
+        self._check(self._lib.nrv_predict(self._h, _ptr(signal_x, _FP), _ptr(read_x, _FP), n, *_marshal(out, _CALLS[0])))
+        return out
 
     def predict_read(self, sig_ev, feat_ev):
         """Whole read: per-event arrays (N,50), (N,6) -> outputs for the N-T sliding windows."""
@@ -276,15 +291,9 @@ class Reviser:
         if sig_ev.shape[0] != N:
             raise ValueError("sig_ev / feat_ev length mismatch")
         n = max(N - self.T, 0)
-        p1 = np.empty((n, 6), np.float32)
-        p2 = np.empty((n, 5), np.float32)
-        a1 = np.empty(n, np.int8)
-        a2 = np.empty(n, np.int8)
-        fp, i8p = C.POINTER(C.c_float), C.POINTER(C.c_int8)
-        self._check(self._lib.nrv_predict_read(
-            self._h, sig_ev.ctypes.data_as(fp), feat_ev.ctypes.data_as(fp), N,
-            p1.ctypes.data_as(fp), p2.ctypes.data_as(fp), a1.ctypes.data_as(i8p), a2.ctypes.data_as(i8p)))
-        return p1, p2, a1, a2
+        out = _empty_calls(n)
+        self._check(self._lib.nrv_predict_read(self._h, _ptr(sig_ev, _FP), _ptr(feat_ev, _FP), N, *_marshal(out, _CALLS[0])))
+        return out
 
     # ------------------------------------------------------------------ raw reads (device-side segmentation)
     @staticmethod
@@ -391,74 +400,43 @@ class Reviser:
             tie_eps = REPORT_TIE_EPS
         return tuple(packed) + (float(tie_eps), np.zeros((packed[4], REPORT_COLS), np.uint64))
 
-    def _report_args(self, packed):
-        if not hasattr(self._lib, "nrv_revise_reads_raw_report_begin"):
-            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_revise_reads_raw_report_begin")
-        return self._revise_args(packed[:12]) + [C.c_float(packed[12]), packed[13].ctypes.data_as(C.POINTER(C.c_uint64))]
-
-    def _revise_args(self, packed):
-        raw, st, feat, descs, nr, N, _, ld, on, b, thr, (seq, qual, off) = packed
-        fp, u8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
-        return [self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)),
-                feat.ctypes.data_as(fp), N, descs, nr,
-                ld.ctypes.data_as(C.POINTER(C.c_int32)) if ld is not None else None, on.ctypes.data_as(u8p) if on is not None else None,
-                b.ctypes.data_as(u8p), thr.ctypes.data_as(fp) if thr is not None else None, seq.ctypes.data_as(u8p),
-                qual.ctypes.data_as(u8p) if qual is not None else None, off.ctypes.data_as(C.POINTER(C.c_int64))]
-
     @staticmethod
     def _trim_merged(out):
         seq, qual, off = out[:3]
         total = int(off[-1])
         return (seq[:total], (qual[:total] if qual is not None else None), off) + tuple(out[3:])
 
+    def _raw_head(self, packed):
+        """The leading C arguments every raw-read entry point shares: handle, raw, n_raw, starts, feat, N, descs, n_reads."""
+        raw, st, feat, descs, nr, N = packed[:6]
+        return [self._h, _ptr(raw, _I16P), raw.size, _ptr(st, _I32P), _ptr(feat, _FP), N, descs, nr]
+
+    def _raw_call(self, packed, begin: bool):
+        """One call of the raw-read family for a packed tuple of any form (`_RAW_FORMS`): its synchronous entry point, or its
+        *_begin with the ticket behind the same arguments.  Returns (ticket number or None, outputs, merged)."""
+        if len(packed) not in _RAW_FORMS:
+            raise ValueError(f"a packed raw-read call has 7, 9, 12 or 14 elements, not {len(packed)}")
+        sync, beg, blocks, merged = _RAW_FORMS[len(packed)]
+        if not hasattr(self._lib, beg):               # the report pair is found by presence
+            raise NrvError(-1, f"this build of libnanorev_hip.so has no {beg}")
+        args = self._raw_head(packed)
+        for types, pick in blocks:
+            args += _marshal(pick(packed), types)
+        t = C.c_int(-1)
+        self._check(getattr(self._lib, beg)(*args, C.byref(t)) if begin else getattr(self._lib, sync)(*args))
+        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) if merged else packed[6]), merged
+
     def run_packed_raw(self, packed):
         """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared (or `with_device_stats` /
-        `with_device_merge` extended)."""
-        fp, i8p = C.POINTER(C.c_float), C.POINTER(C.c_int8)
-        if len(packed) == 14:                         # `with_device_report`: nrv_revise_reads_raw_report
-            self._check(self._lib.nrv_revise_reads_raw_report(*self._report_args(packed)))
-            return self._trim_merged(packed[11]) + (packed[13],)
-        if len(packed) == 12:                         # `with_device_merge`: nrv_revise_reads_raw
-            self._check(self._lib.nrv_revise_reads_raw(*self._revise_args(packed)))
-            return self._trim_merged(packed[11])
-        if len(packed) == 9:
-            raw, st, feat, descs, nr, N, (p1, p2, a1, a2), ld, on = packed
-            self._check(self._lib.nrv_predict_reads_raw_stats(
-                self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)),
-                feat.ctypes.data_as(fp), N, descs, nr, ld.ctypes.data_as(C.POINTER(C.c_int32)), on.ctypes.data_as(C.POINTER(C.c_uint8)),
-                p1.ctypes.data_as(fp), p2.ctypes.data_as(fp), a1.ctypes.data_as(i8p), a2.ctypes.data_as(i8p)))
-            return p1, p2, a1, a2
-        raw, st, feat, descs, nr, N, (p1, p2, a1, a2) = packed
-        self._check(self._lib.nrv_predict_reads_raw(
-            self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)),
-            feat.ctypes.data_as(fp), N, descs, nr,
-            p1.ctypes.data_as(fp), p2.ctypes.data_as(fp), a1.ctypes.data_as(i8p), a2.ctypes.data_as(i8p)))
-        return p1, p2, a1, a2
+        `with_device_merge` / `with_device_report` extended)."""
+        _, out, merged = self._raw_call(packed, False)
+        return self._trim_merged(out) if merged else out
 
     def begin_packed_raw(self, packed):
         """First half of `run_packed_raw` (nrv_reads_raw_begin): the inputs are copied and the whole call is enqueued; returns a
         ticket for `end_packed_raw`.  At most two calls in flight; the OUTPUT arrays of `packed` must stay alive until the end."""
-        fp, i8p = C.POINTER(C.c_float), C.POINTER(C.c_int8)
-        t = C.c_int(-1)
-        if len(packed) == 14:                         # `with_device_report`: nrv_revise_reads_raw_report_begin
-            self._check(self._lib.nrv_revise_reads_raw_report_begin(*self._report_args(packed), C.byref(t)))
-            return t.value, packed[11] + (packed[13],), "merged"
-        if len(packed) == 12:                         # `with_device_merge`: nrv_revise_reads_raw_begin
-            self._check(self._lib.nrv_revise_reads_raw_begin(*self._revise_args(packed), C.byref(t)))
-            return t.value, packed[11], "merged"
-        if len(packed) == 9:                          # `with_device_stats`: nrv_reads_raw_stats_begin
-            raw, st, feat, descs, nr, N, (p1, p2, a1, a2), ld, on = packed
-            self._check(self._lib.nrv_reads_raw_stats_begin(
-                self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)),
-                feat.ctypes.data_as(fp), N, descs, nr, ld.ctypes.data_as(C.POINTER(C.c_int32)), on.ctypes.data_as(C.POINTER(C.c_uint8)),
-                p1.ctypes.data_as(fp), p2.ctypes.data_as(fp), a1.ctypes.data_as(i8p), a2.ctypes.data_as(i8p), C.byref(t)))
-            return t.value, (p1, p2, a1, a2)
-        raw, st, feat, descs, nr, N, (p1, p2, a1, a2) = packed
-        self._check(self._lib.nrv_reads_raw_begin(
-            self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)),
-            feat.ctypes.data_as(fp), N, descs, nr,
-            p1.ctypes.data_as(fp), p2.ctypes.data_as(fp), a1.ctypes.data_as(i8p), a2.ctypes.data_as(i8p), C.byref(t)))
-        return t.value, (p1, p2, a1, a2)
+        t, out, merged = self._raw_call(packed, True)
+        return (t, out, "merged") if merged else (t, out)
 
     def end_packed_raw(self, ticket):
         """Second half: waits for the call `ticket` names and returns its (p1, p2, a1, a2) - or, for a `with_device_merge`
@@ -477,9 +455,8 @@ class Reviser:
         """The device-side signal segmentation alone: (sum(N), 50) float32."""
         raw, st, descs, nr = self._pack_raw(raws, starts, shifts, scales)
         out = np.empty((st.size, 50), np.float32)
-        self._check(self._lib.nrv_segment_reads(
-            self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)),
-            st.size, descs, nr, out.ctypes.data_as(C.POINTER(C.c_float))))
+        self._check(self._lib.nrv_segment_reads(self._h, _ptr(raw, _I16P), raw.size, _ptr(st, _I32P), st.size, descs, nr,
+                                                _ptr(out, _FP)))
         return out
 
     def read_stats(self, raws, starts, last_durs):
@@ -495,74 +472,58 @@ class Reviser:
         shift, scale = np.empty(nr, np.float64), np.empty(nr, np.float64)
         mean, std = np.empty(N, np.float64), np.empty(N, np.float64)
         f12 = np.empty((N, 2), np.float32)
-        dp = C.POINTER(C.c_double)
-        self._check(self._lib.nrv_read_stats(
-            self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), raw.size, st.ctypes.data_as(C.POINTER(C.c_int32)), N, descs, nr,
-            ld.ctypes.data_as(C.POINTER(C.c_int32)), shift.ctypes.data_as(dp), scale.ctypes.data_as(dp),
-            mean.ctypes.data_as(dp), std.ctypes.data_as(dp), f12.ctypes.data_as(C.POINTER(C.c_float))))
+        self._check(self._lib.nrv_read_stats(self._h, _ptr(raw, _I16P), raw.size, _ptr(st, _I32P), N, descs, nr, _ptr(ld, _I32P),
+                                             *_marshal((shift, scale, mean, std, f12), [_DP, _DP, _DP, _DP, _FP])))
         return shift, scale, mean, std, f12
+
+    @staticmethod
+    def _merge_inputs(bases, ev_len, a1, a2, p1, p2, q_thr, with_p):
+        """The inputs of nrv_merge_calls / nrv_merge_calls_report as contiguous arrays: (b, el, x1, x2, q1, q2, thr), the last
+        three None where not given (q1 / q2: where not wanted)."""
+        from .hostlib import bases_u8
+        b = bases_u8(bases)
+        el = np.ascontiguousarray(ev_len, dtype=np.int64).reshape(-1)
+        x1, x2 = np.ascontiguousarray(a1, dtype=np.int8).reshape(-1), np.ascontiguousarray(a2, dtype=np.int8).reshape(-1)
+        if int(el.sum()) != b.size or x2.size != x1.size:
+            raise ValueError("bases / ev_len / a1 / a2 do not match")
+        thr = None if q_thr is None else np.ascontiguousarray(q_thr, dtype=np.float32).reshape(-1)
+        q1, q2 = (_as_f32(np.asarray(p1).reshape(-1, 6), (6,)), _as_f32(np.asarray(p2).reshape(-1, 5), (5,))) if with_p else (None, None)
+        return b, el, x1, x2, q1, q2, thr
+
+    def _merge_call(self, name, b, el, x1, x2, q1, q2, thr, *more):
+        """`name` (nrv_merge_calls, or nrv_merge_calls_report with its two arguments in `more`) on checked inputs -> (seq, qual, off)."""
+        n = x1.size
+        cap = max(b.size + n, 1)
+        out = (np.empty(cap, np.uint8), (np.empty(cap, np.uint8) if thr is not None else None), np.zeros(el.size + 1, np.int64))
+        self._check(getattr(self._lib, name)(*_marshal((self._h, b, el, el.size, x1, x2, q1, q2, n, thr) + out, _MERGE_CALLS_T), *more))
+        return self._trim_merged(out)
 
     def merge_calls_device(self, bases, ev_len, a1, a2, p1=None, p2=None, q_thr=None):
         """The device-side merge alone (nrv_merge_calls) on calls the host supplies: bases S1 / uint8 [sum ev_len], ev_len per
         read, a1 / a2 int8 [max(sum ev_len - T, 0)], and for a quality p1 (n, 6), p2 (n, 5) float32 with the 39 thresholds
         q_thr.  Returns (seq, qual | None, off) - the bytes of hoststage.emit_calls."""
-        from .hostlib import bases_u8
-        b = bases_u8(bases)
-        el = np.ascontiguousarray(ev_len, dtype=np.int64).reshape(-1)
-        x1, x2 = np.ascontiguousarray(a1, dtype=np.int8).reshape(-1), np.ascontiguousarray(a2, dtype=np.int8).reshape(-1)
-        N, n = b.size, x1.size
-        if int(el.sum()) != N or x2.size != n:
-            raise ValueError("bases / ev_len / a1 / a2 do not match")
-        fp, u8p, i8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int8)
-        thr = q1 = q2 = None
-        if q_thr is not None:
-            thr = np.ascontiguousarray(q_thr, dtype=np.float32).reshape(-1)
-            q1, q2 = _as_f32(np.asarray(p1).reshape(-1, 6), (6,)), _as_f32(np.asarray(p2).reshape(-1, 5), (5,))
-            if thr.size != 39 or q1.shape[0] != n or q2.shape[0] != n:
-                raise ValueError("q_thr / p1 / p2 do not match")
-        cap = max(N + n, 1)
-        seq, qual, off = np.empty(cap, np.uint8), (np.empty(cap, np.uint8) if thr is not None else None), np.zeros(el.size + 1, np.int64)
-        self._check(self._lib.nrv_merge_calls(
-            self._h, b.ctypes.data_as(u8p), el.ctypes.data_as(C.POINTER(C.c_int64)), el.size, x1.ctypes.data_as(i8p), x2.ctypes.data_as(i8p),
-            q1.ctypes.data_as(fp) if q1 is not None else None, q2.ctypes.data_as(fp) if q2 is not None else None, n,
-            thr.ctypes.data_as(fp) if thr is not None else None, seq.ctypes.data_as(u8p),
-            qual.ctypes.data_as(u8p) if qual is not None else None, off.ctypes.data_as(C.POINTER(C.c_int64))))
-        return self._trim_merged((seq, qual, off))
+        ins = self._merge_inputs(bases, ev_len, a1, a2, p1, p2, q_thr, q_thr is not None)     # p1 / p2 count only with q_thr
+        n, (q1, q2, thr) = ins[2].size, ins[4:]
+        if thr is not None and (thr.size != 39 or q1.shape[0] != n or q2.shape[0] != n):
+            raise ValueError("q_thr / p1 / p2 do not match")
+        return self._merge_call("nrv_merge_calls", *ins)
 
     def merge_calls_report_device(self, bases, ev_len, a1, a2, p1=None, p2=None, q_thr=None, tie_eps=None):
         """`merge_calls_device` with the per-read revision report (nrv_merge_calls_report): p1 / p2 may be given without q_thr
         (near_tie filled, q_sum 0).  Returns (seq, qual | None, off, report uint64[n_reads][24]) - the report is
         hoststage.revision_report's, bit for bit."""
-        from .hostlib import bases_u8
         from .hoststage import REPORT_TIE_EPS
         if not hasattr(self._lib, "nrv_merge_calls_report"):
             raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_merge_calls_report")
-        b = bases_u8(bases)
-        el = np.ascontiguousarray(ev_len, dtype=np.int64).reshape(-1)
-        x1, x2 = np.ascontiguousarray(a1, dtype=np.int8).reshape(-1), np.ascontiguousarray(a2, dtype=np.int8).reshape(-1)
-        N, n = b.size, x1.size
-        if int(el.sum()) != N or x2.size != n:
-            raise ValueError("bases / ev_len / a1 / a2 do not match")
-        fp, u8p, i8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int8)
-        thr = q1 = q2 = None
-        if p1 is not None and p2 is not None:
-            q1, q2 = _as_f32(np.asarray(p1).reshape(-1, 6), (6,)), _as_f32(np.asarray(p2).reshape(-1, 5), (5,))
-            if q1.shape[0] != n or q2.shape[0] != n:
-                raise ValueError("p1 / p2 do not match")
-        if q_thr is not None:
-            thr = np.ascontiguousarray(q_thr, dtype=np.float32).reshape(-1)
-            if thr.size != 39 or q1 is None:
-                raise ValueError("q_thr needs 39 entries and p1 / p2")
-        cap = max(N + n, 1)
-        seq, qual, off = np.empty(cap, np.uint8), (np.empty(cap, np.uint8) if thr is not None else None), np.zeros(el.size + 1, np.int64)
-        report = np.zeros((el.size, REPORT_COLS), np.uint64)
-        self._check(self._lib.nrv_merge_calls_report(
-            self._h, b.ctypes.data_as(u8p), el.ctypes.data_as(C.POINTER(C.c_int64)), el.size, x1.ctypes.data_as(i8p), x2.ctypes.data_as(i8p),
-            q1.ctypes.data_as(fp) if q1 is not None else None, q2.ctypes.data_as(fp) if q2 is not None else None, n,
-            thr.ctypes.data_as(fp) if thr is not None else None, seq.ctypes.data_as(u8p),
-            qual.ctypes.data_as(u8p) if qual is not None else None, off.ctypes.data_as(C.POINTER(C.c_int64)),
-            C.c_float(REPORT_TIE_EPS if tie_eps is None else tie_eps), report.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return self._trim_merged((seq, qual, off)) + (report,)
+        ins = self._merge_inputs(bases, ev_len, a1, a2, p1, p2, q_thr, p1 is not None and p2 is not None)
+        n, (q1, q2, thr) = ins[2].size, ins[4:]
+        if q1 is not None and (q1.shape[0] != n or q2.shape[0] != n):
+            raise ValueError("p1 / p2 do not match")
+        if thr is not None and (thr.size != 39 or q1 is None):
+            raise ValueError("q_thr needs 39 entries and p1 / p2")
+        rep = np.zeros((ins[1].size, REPORT_COLS), np.uint64)
+        more = _marshal((REPORT_TIE_EPS if tie_eps is None else tie_eps, rep), _REPORT[0])
+        return self._merge_call("nrv_merge_calls_report", *ins, *more) + (rep,)
 
     @staticmethod
     def _fingerprint(a):
