@@ -213,6 +213,58 @@ int nrv_merge_calls_report(nrv_handle* h, const uint8_t* bases, const int64_t* e
                            const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
                            float tie_eps, uint64_t* report);
 
+/* The same revised reads WITH a per-read edit list (opt-in; nothing above changes): WHICH bases the merge substituted, inserted
+ * or deleted, where, and with what confidence - compacted in event order on the device behind the merge (and the report), the
+ * only place where a call made this way still has p1 / p2 / a1 / a2.  The arguments of nrv_revise_reads_raw_report_begin up to
+ * `report`, which may be NULL here (then no report is counted and tie_eps is ignored), then
+ *   edits     nrv_edit [max(N - T, 0)]: at most one record per window.  Only the used prefix crosses PCIe and is written:
+ *             records at and beyond edit_off[n_reads] are not touched;
+ *   edit_off  int64 [n_reads + 1]: read r owns edits[edit_off[r] .. edit_off[r + 1]), ascending in pos_in; edit_off[n_reads] is
+ *             the total.
+ * With o = (T - 1) / 2, window i of a read revises its event o + i; one record for an event whose window is
+ *   kind 1 substituted  both models agree on a base that is not the original one; alt = the agreed base
+ *   kind 2 inserted     model1 'D', model2 a base; alt = model2's base, which sits at pos_out + 1 (pos_out is the kept original)
+ *   kind 3 deleted      both '-'; alt = '-', pos_out = the position the next emitted character takes
+ * (the rules of the report's columns 5 - 7); confirmed, undecided and edge events have none.  Fields:
+ *   pos_in   the event's index inside its read (0-based position in the ORIGINAL read)
+ *   pos_out  position inside the REVISED read (relative to off[r]) of the first character the event emitted
+ *   ref      the original base (ASCII)
+ *   qual     the window's quality character; 0 without q_thr / qual
+ *   conf     v < u ? v : u with u = p1[w][clip(a1, 0, 5)], v = p2[w][clip(a2, 0, 4)]: the f32 operand the quality is computed
+ *            from, copied, in FASTA calls too (p1 / p2 are in the call's output block either way)
+ * hoststage.revision_edits is the definition; slots and positions are integer scans, so the records are that function's on the
+ * outputs of nrv_predict_reads_raw bit for bit, in every precision mode and whatever order the workgroups ran in.  seq / qual /
+ * off / report are those of nrv_revise_reads_raw_report_begin.  N <= T: edit_off is zeros, filled on the host.
+ * Tickets, the two-calls-in-flight rule, the failure paths and the range-guard re-run (which runs the three launches again
+ * behind the merge: plain stores, nothing accumulates) are those of nrv_revise_reads_raw_begin; `edits` and `edit_off` must
+ * stay valid until nrv_reads_raw_end, which reads the total from the downloaded edit_off and fetches total x 16 bytes in a
+ * second copy.  nrv_revise_reads_raw_edits IS _edits_begin + _end. */
+typedef struct nrv_edit {
+  uint32_t pos_in, pos_out;
+  uint8_t kind, ref, alt, qual;
+  float conf;
+} nrv_edit;
+#ifdef __cplusplus
+static_assert(sizeof(nrv_edit) == 16, "nrv_edit is 16 bytes");
+#else
+_Static_assert(sizeof(nrv_edit) == 16, "nrv_edit is 16 bytes");
+#endif
+int nrv_revise_reads_raw_edits_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                     const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                     const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                     uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                     nrv_edit* edits, int64_t* edit_off, int* ticket);
+int nrv_revise_reads_raw_edits(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                               const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                               const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                               uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                               nrv_edit* edits, int64_t* edit_off);
+/* nrv_merge_calls_report with the edit list, by the kernels nrv_revise_reads_raw_edits_begin runs: `report` may be NULL; p1 / p2
+ * may be given without q_thr (conf is then filled and qual 0); without p1 / p2 conf is 0.  The twin used by the parity tests. */
+int nrv_merge_calls_edits(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                          const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                          float tie_eps, uint64_t* report, nrv_edit* edits, int64_t* edit_off);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

@@ -118,7 +118,16 @@ def get_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("--report_tie_eps", dest="report_tie_eps", type=float, default=hs.REPORT_TIE_EPS,
                    help="a call is a near-tie when top1 - top2 of either model's softmax row is below this (default 4e-4: what two "
                         "precision modes that both meet the parity bar can differ by)")
+    p.add_argument("--edits", dest="edits", default=None, metavar="DIR",
+                   help="write a per-read edit list into DIR (also NRV_EDITS=DIR): for every read that is written a file "
+                        "<stem>_edits.tsv with one header line and one line per base the revision substituted (S), inserted (I) or "
+                        "deleted (D) - position in the original read, position in the revised read, kind, original base, new base "
+                        "('-' for a deletion), the call's quality character ('.' in FASTA runs) and the confidence the quality is "
+                        "computed from.  A read written unrevised gets the header alone.  With --device_merge the list is compacted on "
+                        "the GPU behind the merge, everywhere else it is formed by the host stage from the calls it holds: the same "
+                        "files byte for byte.  Off by default; without it nothing changes and DIR is not created")
     a = p.parse_args(argv)
+    a.edits = a.edits or (os.environ.get("NRV_EDITS", "").strip() or None)
     a.device_stats = bool(a.device_stats) or device_stats_env()
     a.device_merge = bool(a.device_merge) or device_merge_env()
     a.report = a.report or (os.environ.get("NRV_REPORT", "").strip() or None)
@@ -619,10 +628,42 @@ def merge_report(report: str, names: Sequence[str], log: Callable[[str], None] =
             pass
 
 
+EDITS_HEADER = "#pos_in\tpos_out\tkind\tref\talt\tqual\tconf"
+
+
+def edits_name(edits_dir: str, fast5_fn: str) -> str:
+    return os.path.join(edits_dir, fast5_fn.split(".")[0] + "_edits.tsv")
+
+
+def edit_rows(T, bases, ev_len, p1, p2, a1, a2, want_qual):
+    """--edits on the host: `hoststage.revision_edits` on calls the host holds, with the quality characters the writers use
+    (FASTQ: `phred_chars`; FASTA: none).  (edits, edit_off)."""
+    qc = None
+    if want_qual:
+        qc = phred_chars(p1, p2, a1, a2) if len(a1) else np.zeros(0, np.uint8)
+    return hs.revision_edits(hostlib.bases_u8(bases), ev_len, a1, a2, p1, p2, qc, T)
+
+
+def write_edits(edits_dir: str, fast5_fn: str, edits=None, want_qual: bool = False):
+    """One read's <stem>_edits.tsv by temporary + rename: the header, then one line per record (None: a read written unrevised,
+    the header alone)."""
+    os.makedirs(edits_dir, exist_ok=True)
+    lines = [EDITS_HEADER]
+    if edits is not None:
+        for pi, po, k, ref, alt, q, conf in np.asarray(edits).tolist():
+            lines.append(f"{pi}\t{po}\t{hs.EDIT_KINDS[k]}\t{chr(ref)}\t{chr(alt)}\t{chr(q) if want_qual else '.'}\t"
+                         + format(float(np.float32(conf)), ".9g"))
+    dst = edits_name(edits_dir, fast5_fn)
+    tmp = f"{dst}.tmp{os.getpid()}"
+    with open(tmp, "w") as fp:
+        fp.write("\n".join(lines) + "\n")
+    os.replace(tmp, dst)
+
+
 def _host_merge_form(packed):
-    """A `with_device_merge` / `with_device_report` tuple back in the form whose call returns (p1, p2, a1, a2): for the paths
-    that keep the host merge."""
-    if packed is None or len(packed) not in (12, 14):
+    """A `with_device_merge` / `with_device_report` / `with_device_edits` tuple back in the form whose call returns (p1, p2, a1,
+    a2): for the paths that keep the host merge."""
+    if packed is None or len(packed) not in (12, 14, 16):
         return packed
     return tuple(packed[:7]) if packed[7] is None else tuple(packed[:9])
 
@@ -637,11 +678,11 @@ def _bundle_has_bases(bundle) -> bool:
     return "bases" in bundle and len(bundle["bases"]) == int(bundle["meta"][:, 1].sum())
 
 
-def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, report):
+def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, report, edits=False):
     """The one decision about a batch: (packed form `_FileRun.submit` builds, route `_FileRun.run_batch` takes).  Pure: it looks at what
     the engine object offers, at the bundle (None: reads that arrived one by one) and at the run's switches - pipelined (one
     engine, NRV_CLI_PIPELINE != 0), native_pool (libnanorev_host.so driven from the thread pool), device_merge (--device_merge
-    and what it needs: pipelined, native_pool, nrvh_write_records), report (--report).  "bases": `_bundle_has_bases`.  A form is
+    and what it needs: pipelined, native_pool, nrvh_write_records), report (--report), edits (--edits).  "bases": `_bundle_has_bases`.  A form is
     the length of the packed tuple (engine.Reviser), None, or "host-merge": the merge form built and taken back.
 
       bundle  engine offers / bundle / switches                              form            route
@@ -653,6 +694,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
       yes     + device_merge, with_device_merge, bases; report off           12              by the last three rows
       yes     + report on, with_device_report                                14              by the last three rows
       yes     + report on, no with_device_report                             host-merge [2]  by the last three rows
+      yes     + edits on, with_device_edits (+ report on: with_device_report)  16 [4]          by the last three rows
+      yes     + edits on, one of them missing                                host-merge [2]  by the last three rows
       yes     any form; pipelined, native_pool, begin_packed_raw, bases                      pipelined [3]
       yes     any form; native_pool, bases, not (pipelined, begin_packed_raw)                packed+finish_bundle
       yes     any form; no native_pool, or no bases                                          packed sliced
@@ -660,7 +703,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
     [1] None when `prepare_many` declines (not all raw reads) or building a form raises; the route is then predict_many.
     [2] the whole bundle on the host: merge, quality and report rows from the calls.
     [3] begin_packed_raw raising -> packed+finish_bundle.  Every route but this one takes a 12 / 14 form back through
-        `_host_merge_form`; any call raising -> per-read retries on reads that `_bundle_reads` completes on the host."""
+        `_host_merge_form`; any call raising -> per-read retries on reads that `_bundle_reads` completes on the host.
+    [4] the one call carries the report too when --report is set."""
     unpacked = "per-read" if n_reads == 1 else "predict_many"
     if bundle is None:
         return (7 if n_reads > 1 and hasattr(rv, "pack_reads_raw") else None), unpacked
@@ -670,6 +714,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
     form = 9 if "device_stats" in bundle else 7
     if device_merge and hasattr(rv, "with_device_merge") and bases:
         form = 12 if not report else (14 if hasattr(rv, "with_device_report") else "host-merge")
+        if edits:
+            form = 16 if hasattr(rv, "with_device_edits") and form != "host-merge" else "host-merge"
     if not (native_pool and bases):
         return form, "packed sliced"
     return form, ("pipelined" if pipelined and hasattr(rv, "begin_packed_raw") else "packed+finish_bundle")
@@ -784,6 +830,7 @@ class _FileRun:
         self.report = ReportPart(report_part)
         self.rep_rows = {}                            # fn -> the row of a read whose output is not final yet
         self.tie_eps = float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS))
+        self.edits_dir = getattr(args, "edits", None) # --edits: every read's list is written BEFORE its output is
         self.trace = _Trace()
         self.want_qual, self.spec = args.output_format == "fastq", _OutSpec(args)
         # `reviser` may be a zero-argument factory: the engine is then created by the engine thread as its first task, WHILE
@@ -923,6 +970,11 @@ class _FileRun:
         self.stats["failed"].append(fn)
         log(f"[！！！Error] revising {fn.split('.')[0]}: {e}; writing the original basecalls")
         nw = 0
+        if self.edits_dir:                            # unrevised: the header alone, replacing what a revision may have left
+            try:
+                write_edits(self.edits_dir, fn)
+            except Exception as e2:
+                log(f"[！！！Error] stroring : {fn.split('.')[0]}_edits.tsv...... {e2}")
         try:
             if args.output_format == "fastq" and fq is not None:
                 b, q = hs.trim_fastq(fq)
@@ -961,7 +1013,8 @@ class _FileRun:
         try:
             if bundle is not None and "device_stats" in bundle and not (hasattr(rv, "run_packed_raw") and hasattr(rv, "with_device_stats")):
                 bundle = _bundle_host_stats(bundle)   # an engine without the new calls: the host computes them after all
-            form, route = _route_batch(rv, bundle, len(batch), self.pipelined, self.native_pool, self.device_merge, bool(self.report))
+            form, route = _route_batch(rv, bundle, len(batch), self.pipelined, self.native_pool, self.device_merge, bool(self.report),
+                                       edits=bool(self.edits_dir))
             if form is not None and bundle is None:
                 packed = prepare_many(cls, [rt for _, rt, _ in batch], rv.T)
             elif form is not None:
@@ -970,8 +1023,13 @@ class _FileRun:
                     packed = cls.with_device_stats(packed, bundle["last_dur"], bundle["device_stats"])
                 if form != len(packed):               # a merge form: alone, taken back, or - --report - counted on the device too
                     packed = cls.with_device_merge(packed, bundle["bases"], self.want_qual)
-                    if form != len(packed):
-                        packed = _host_merge_form(packed) if form == "host-merge" else cls.with_device_report(packed, self.tie_eps)
+                    if form == "host-merge":
+                        packed = _host_merge_form(packed)
+                    elif form != len(packed):
+                        if self.report:
+                            packed = cls.with_device_report(packed, self.tie_eps)
+                        if form == 16:                # --edits: the list behind the merge (and the report)
+                            packed = cls.with_device_edits(packed)
         except Exception:
             packed = None
         if packed is None:
@@ -1009,6 +1067,8 @@ class _FileRun:
             try:
                 if self.report:
                     self.rep_rows[fn] = report_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual, self.tie_eps)[0]
+                if self.edits_dir:
+                    write_edits(self.edits_dir, fn, edit_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual)[0], self.want_qual)
                 if self.pool is not None:
                     p1, p2, a1, a2 = c
                     qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
@@ -1030,18 +1090,27 @@ class _FileRun:
             if merged:
                 if self.report:                       # a `with_device_report` call: the rows were counted behind the merge
                     self.rep_rows.update(zip(fns, outs[3]))
+                if self.edits_dir:                    # a `with_device_edits` call: the lists were compacted behind the merge
+                    self.write_call_edits(fns, outs[4], outs[5])
                 fut = self.pool.submit(_write_records_native, self.spec, fns, outs[0], outs[1] if self.want_qual else None, outs[2])
             else:
                 p1, p2, a1, a2 = outs
                 T, ev_len = self.rv.T, bundle["meta"][:, 1].astype(np.int64)
                 if self.report:
                     self.rep_rows.update(zip(fns, report_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2, self.want_qual, self.tie_eps)))
+                if self.edits_dir:
+                    self.write_call_edits(fns, *edit_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2, self.want_qual))
                 qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
                 fut = self.pool.submit(_finish_bundle_native, self.spec, T, fns, bundle["bases"], ev_len, a1, a2, qc)
             self.finishing.append((fut, fns, rts, fqs))
         except Exception as e:
             for fn, rt, fq in batch:
                 self.fallback(fn, rt, fq, e)
+
+    def write_call_edits(self, fns, edits, edit_off):
+        """--edits for all reads of a device call: read r owns edits[edit_off[r]:edit_off[r + 1]]."""
+        for r, fn in enumerate(fns):
+            write_edits(self.edits_dir, fn, edits[int(edit_off[r]):int(edit_off[r + 1])], self.want_qual)
 
     def engine_time(self, t0, ti=None, t_call=None):
         """Books the engine time since t0; with a trace index, the end of that device call (begun at t_call, else t0) as well."""
@@ -1358,7 +1427,7 @@ def revise_part(args, reviser, fn: str, k: int, parts: int):
         a1 = a2 = np.zeros(0, np.int8)
     qc = phred_chars(p1, p2, a1, a2) if args.output_format == "fastq" and len(a1) else None
     out = {"T": T, "n_ev": N, "lo": lo, "a1": np.array(a1, np.int8), "a2": np.array(a2, np.int8), "qc": qc}
-    if getattr(args, "report", None):                 # the parent reports the read once its slices are merged: near-ties need the rows
+    if getattr(args, "report", None) or getattr(args, "edits", None):   # the parent reports the read once its slices are merged: near-ties (and the edits' conf) need the rows
         out["p1"], out["p2"] = np.array(p1, np.float32), np.array(p2, np.float32)
     if k == 0:
         out["bases"], out["fq"] = np.asarray(rt.bases), fq
@@ -1418,6 +1487,8 @@ def write_originals(args, files: Sequence[str], log: Callable[[str], None], repo
         nw = 0
         try:
             rd, fq = parse_read(os.path.join(args.fast5_base_dir, fn), args.basecall_group, args.basecall_subgroup)
+            if getattr(args, "edits", None):         # unrevised: the header alone
+                write_edits(args.edits, fn)
             if args.output_format == "fastq" and fq is not None:
                 b, q = hs.trim_fastq(fq)
                 write_read(args, fn, b, q)
@@ -1452,12 +1523,18 @@ def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[st
             a1, a2 = np.concatenate([p["a1"] for p in pl]), np.concatenate([p["a2"] for p in pl])
             qc = np.concatenate([p["qc"] if p["qc"] is not None else np.zeros(0, np.uint8) for p in pl]) \
                 if args.output_format == "fastq" and len(a1) else None
+            have_p = all("p1" in p for p in pl)
+            if getattr(args, "edits", None):
+                write_edits(args.edits, fn, hs.revision_edits(
+                    hostlib.bases_u8(pl[0]["bases"]), [N], a1, a2,
+                    np.concatenate([p["p1"] for p in pl]) if have_p else None, np.concatenate([p["p2"] for p in pl]) if have_p else None,
+                    (qc if qc is not None else np.zeros(0, np.uint8)) if args.output_format == "fastq" else None, T)[0],
+                    args.output_format == "fastq")
             w, e2 = (_finish_native if hostlib.load() is not None else _finish_in_worker)(spec, T, fn, pl[0]["bases"], a1, a2, qc)
             if e2 is None:
                 nb += w
                 log(f"[p:::] {fn.split('.')[0]}_out.{args.output_format} was saved...... ({n} slices)")
                 if report is not None and report:
-                    have_p = all("p1" in p for p in pl)
                     row = hs.revision_report(
                         hostlib.bases_u8(pl[0]["bases"]), [N], a1, a2,
                         np.concatenate([p["p1"] for p in pl]) if have_p else None, np.concatenate([p["p2"] for p in pl]) if have_p else None,

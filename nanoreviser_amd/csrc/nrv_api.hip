@@ -522,6 +522,8 @@ struct nrv_handle {
   unsigned* d_sat_st[2] = {nullptr, nullptr};
   hipStream_t copy_stream = nullptr;      // host -> device
   hipStream_t d2h_stream = nullptr;       // device -> host (its own stream: an upload never queues behind a download)
+  hipStream_t edit_stream = nullptr;      // nrv_revise_reads_raw_edits_begin only, created with the first such call: the second download
+                                          // of nrv_reads_raw_end (d2h_stream may already wait for the OTHER slot's kernels)
   hipEvent_t ev_in[kIn] = {0, 0, 0}, ev_done[2] = {0, 0}, ev_out[2] = {0, 0};
   // page-locked host staging: outputs always land here first (46 B per window); inputs only when the
   // caller's arrays could not be registered in place (bounce copies)
@@ -558,6 +560,13 @@ struct nrv_handle {
     bool report = false;
     float tie_eps = 0.f;
     uint64_t* rep_out = nullptr;
+    // nrv_revise_reads_raw_edits_begin (nrv_edits.h): edit_off i64 x (n_reads + 1) behind the report, the last part that comes
+    // back with the block (m_dl grows by it); the records nrv_edit x n and their scratch etile u64 x tiles behind rec / tile.  The
+    // used prefix of the records is fetched by nrv_reads_raw_end in a copy of its own, on edit_stream
+    size_t m_eoff = 0, m_edits = 0, m_etile = 0;
+    bool edits = false;
+    nrv_edit* edits_out = nullptr;
+    int64_t* eoff_out = nullptr;
     uint8_t *seq = nullptr, *qual = nullptr;
     int64_t* off = nullptr;
     int64_t N = 0, n = 0;
@@ -1413,6 +1422,7 @@ void nrv_destroy(nrv_handle* h) {
   for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
   if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
   if (h->d2h_stream) { (void)hipStreamSynchronize(h->d2h_stream); (void)hipStreamDestroy(h->d2h_stream); }
+  if (h->edit_stream) { (void)hipStreamSynchronize(h->edit_stream); (void)hipStreamDestroy(h->edit_stream); }
   for (int st = 0; st < nrv_handle::kIn; ++st) if (h->ev_in[st]) (void)hipEventDestroy(h->ev_in[st]);
   for (int st = 0; st < 2; ++st) {
     if (h->ev_done[st]) (void)hipEventDestroy(h->ev_done[st]);
@@ -1937,20 +1947,46 @@ static ReportArgs report_args(const MergeArgs& m, const float* p1, const float* 
   a.report = (unsigned long long*)report;
   return a;
 }
-// layout of a merged block for N events, n windows, n_reads reads: [off | seq | qual | report] (what comes back; the report only
-// where one was asked for) + [rec | tile] (scratch)
-struct MergeLayout { size_t seq, qual, rep, rec, tile, dl, bytes; };
-static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, bool report = false) {
+// The edit kernels (nrv_edits.h) behind merge_enqueue (and report_enqueue) on the same stream: they read the records, the tile
+// offsets and the read offsets the merge left.  Plain stores into every word that is read back: a second pass accumulates nothing.
+static int edits_enqueue(nrv_handle* h, const EditsArgs& a) {
+  if (a.n_reads <= 0 || a.N <= 0) return NRV_OK;
+  const unsigned tiles = (unsigned)((a.N + kMergeTile - 1) / kMergeTile);
+  hipLaunchKernelGGL(edits_count_kernel, dim3(tiles), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(edits_tile_scan_kernel, dim3(1), dim3(256), 0, h->stream, a, (int)tiles);
+  hipLaunchKernelGGL(edits_scatter_kernel, dim3(tiles), dim3(256), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return NRV_OK;
+}
+static EditsArgs edits_args(const MergeArgs& m, const float* p1, const float* p2, bool want_q, void* etile, void* edit_off, void* edits) {
+  static_assert(sizeof(EditRec) == sizeof(nrv_edit), "nanorev.h and nrv_edits.h disagree on the edit record");
+  EditsArgs a;
+  a.reads = m.reads; a.n_reads = m.n_reads; a.T = m.T; a.N = m.N;
+  a.cap = m.N - m.T > 0 ? m.N - m.T : 0;
+  a.bases = m.bases; a.a1 = m.a1; a.a2 = m.a2;
+  a.p1 = p1 && p2 ? p1 : nullptr; a.p2 = p1 && p2 ? p2 : nullptr;
+  a.rec = m.rec; a.tile = m.tile; a.off = m.off; a.want_q = want_q ? 1 : 0;
+  a.etile = (unsigned long long*)etile; a.edit_off = (long long*)edit_off; a.edits = (EditRec*)edits;
+  return a;
+}
+// layout of a merged block for N events, n windows, n_reads reads: [off | seq | qual | report | edit_off] (what comes back; the
+// report and edit_off only where asked for) + [rec | tile] (scratch) + [edits | etile] (the edit records, fetched by their used
+// prefix, and their scratch; only where asked for)
+struct MergeLayout { size_t seq, qual, rep, eoff, rec, tile, edits, etile, dl, bytes; };
+static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, bool report = false, bool edits = false) {
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   MergeLayout m;
-  const size_t cap = (size_t)(N + n);
+  const size_t cap = (size_t)(N + n), tiles = (size_t)((N + kMergeTile - 1) / kMergeTile);
   m.seq = up(((size_t)n_reads + 1) * 8);
   m.qual = m.seq + up(cap);
   m.rep = m.qual + up(cap);
-  m.dl = m.rep + (report ? up((size_t)n_reads * kReportCols * 8) : 0);
+  m.eoff = m.rep + (report ? up((size_t)n_reads * kReportCols * 8) : 0);
+  m.dl = m.eoff + (edits ? up(((size_t)n_reads + 1) * 8) : 0);
   m.rec = m.dl;
   m.tile = m.rec + up((size_t)N * 4);
-  m.bytes = m.tile + up((size_t)((N + kMergeTile - 1) / kMergeTile) * 8);
+  m.edits = m.tile + up(tiles * 8);
+  m.etile = m.edits + (edits ? up((size_t)n * sizeof(nrv_edit)) : 0);
+  m.bytes = m.etile + (edits ? up(tiles * 8) : 0);
   return m;
 }
 // No window at all (N <= T): the reads come back as they are, on the host
@@ -1978,6 +2014,8 @@ struct MergeReq {             // what nrv_revise_reads_raw_begin adds to a raw-r
   int64_t* off;
   uint64_t* report = nullptr; // nrv_revise_reads_raw_report_begin: [n_reads][24], and the near-tie margin
   float tie_eps = 0.f;
+  nrv_edit* edits = nullptr;  // nrv_revise_reads_raw_edits_begin: [max(N - T, 0)] and [n_reads + 1]
+  int64_t* edit_off = nullptr;
 };
 static MergeArgs slot_merge_args(const nrv_handle* h, const nrv_handle::RawSlot& sl) {
   char* const d = sl.d_out + 64;
@@ -1998,6 +2036,11 @@ static ReportArgs slot_report_args(const nrv_handle* h, const nrv_handle::RawSlo
   return report_args(slot_merge_args(h, sl), (const float*)d, (const float*)(d + sl.rows * 24), sl.want_q, sl.tie_eps,
                      sl.d_mrg + sl.m_rep);
 }
+static EditsArgs slot_edits_args(const nrv_handle* h, const nrv_handle::RawSlot& sl) {
+  char* const d = sl.d_out + 64;                               // p1 / p2: as for the report
+  return edits_args(slot_merge_args(h, sl), (const float*)d, (const float*)(d + sl.rows * 24), sl.want_q,
+                    sl.d_mrg + sl.m_etile, sl.d_mrg + sl.m_eoff, sl.d_mrg + sl.m_edits);
+}
 
 // nrv_reads_raw_begin (last_dur == nullptr: today's call, to the byte), nrv_reads_raw_stats_begin and (mr != nullptr)
 // nrv_revise_reads_raw_begin
@@ -2013,6 +2056,7 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
     h->err = "nrv_revise_reads_raw_begin: null bases / seq / off (or 2^31 events and more)";
     return NRV_E_INVALID;
   }
+  if (mr && mr->edit_off && N > h->T && !mr->edits) { h->err = "nrv_revise_reads_raw_edits_begin: null edits"; return NRV_E_INVALID; }
   const bool with_stats = last_dur != nullptr || on_device != nullptr;
   const int64_t stat_len = with_stats ? stats_check(h, reads, n_reads, last_dur, on_device) : 0;
   if (stat_len < 0) return NRV_E_INVALID;
@@ -2026,9 +2070,11 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
   *ticket = k;
   sl.merge = mr != nullptr;
   sl.report = mr != nullptr && mr->report != nullptr;
+  sl.edits = mr != nullptr && mr->edit_off != nullptr;
   if (sl.n == 0) {                                              // nothing to compute: _end returns at once
     if (mr) merge_nothing(mr->bases, reads, n_reads, N, mr->seq, mr->q_thr ? mr->qual : nullptr, mr->off);
     if (sl.report) report_nothing(reads, n_reads, mr->q_thr != nullptr && mr->qual != nullptr, mr->report);
+    if (sl.edits) memset(mr->edit_off, 0, ((size_t)n_reads + 1) * 8);   // no window, no record
     sl.busy = true;
     return NRV_OK;
   }
@@ -2067,9 +2113,11 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
     sl.sat_seen = 0;
   }
   if (mr) {
-    const MergeLayout m = merge_layout(N, sl.n, n_reads, sl.report);
+    const MergeLayout m = merge_layout(N, sl.n, n_reads, sl.report, sl.edits);
     sl.m_seq = m.seq; sl.m_qual = m.qual; sl.m_rec = m.rec; sl.m_tile = m.tile; sl.m_dl = m.dl;
     sl.m_rep = m.rep; sl.rep_out = mr->report; sl.tie_eps = mr->tie_eps;
+    sl.m_eoff = m.eoff; sl.m_edits = m.edits; sl.m_etile = m.etile; sl.edits_out = mr->edits; sl.eoff_out = mr->edit_off;
+    if (sl.edits && !h->edit_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->edit_stream, hipStreamNonBlocking));
     sl.want_q = mr->q_thr != nullptr && mr->qual != nullptr;
     if (sl.want_q) memcpy(sl.thr, mr->q_thr, sizeof sl.thr);
     sl.seq = mr->seq; sl.qual = mr->qual; sl.off = mr->off;
@@ -2098,6 +2146,7 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
       return rc;
     if (mr) {
       for (size_t i = 0; i + 4 <= sl.m_dl; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
+      if (sl.edits) for (size_t i = sl.m_edits; i + 4 <= sl.m_etile; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
       if ((rc = poison_fill(h, sl.d_mrg, sl.cap_mrg, h->stream))) return rc;
     }
   }
@@ -2121,7 +2170,8 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
                        nullptr, nullptr);
   // the merge reads the slot's output block: behind the call's last launch group, ahead of ev_done
   if (rc || (rc = raw_enqueue(h, sl)) || (mr && (rc = merge_enqueue(h, slot_merge_args(h, sl)))) ||
-      (sl.report && (rc = report_enqueue(h, slot_report_args(h, sl))))) {
+      (sl.report && (rc = report_enqueue(h, slot_report_args(h, sl)))) ||
+      (sl.edits && (rc = edits_enqueue(h, slot_edits_args(h, sl))))) {
     (void)hipStreamSynchronize(h->stream);                      // part of the call may be enqueued: nothing of it may outlive the slot
     return rc;
   }
@@ -2205,6 +2255,30 @@ int nrv_revise_reads_raw_report(nrv_handle* h, const int16_t* raw, int64_t n_raw
   return rc ? rc : nrv_reads_raw_end(h, t);
 }
 
+int nrv_revise_reads_raw_edits_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                     const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                     const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                     uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                     nrv_edit* edits, int64_t* edit_off, int* ticket) {
+  if (h && ((last_dur == nullptr) != (on_device == nullptr))) { h->err = "nrv_revise_reads_raw_edits_begin: last_dur and on_device go together"; return NRV_E_INVALID; }
+  if (h && !edit_off) { h->err = "nrv_revise_reads_raw_edits_begin: null edit_off"; return NRV_E_INVALID; }
+  MergeReq mr{bases, q_thr, seq, qual, off};
+  mr.report = report; mr.tie_eps = tie_eps;                    // report == NULL: none is counted
+  mr.edits = edits; mr.edit_off = edit_off;
+  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, nullptr, nullptr, nullptr, nullptr, ticket, &mr);
+}
+
+int nrv_revise_reads_raw_edits(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                               const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                               const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                               uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                               nrv_edit* edits, int64_t* edit_off) {
+  int t = -1;
+  const int rc = nrv_revise_reads_raw_edits_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                                  seq, qual, off, tie_eps, report, edits, edit_off, &t);
+  return rc ? rc : nrv_reads_raw_end(h, t);
+}
+
 int nrv_reads_raw_end(nrv_handle* h, int ticket) {
   int rc = check_handle(h);
   if (rc) return rc;
@@ -2226,6 +2300,8 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
       if ((rc = poison_fill(h, sl.d_mrg, sl.cap_mrg, h->stream)) || (rc = merge_enqueue(h, slot_merge_args(h, sl)))) return rc;
       // ... and the report: report_enqueue zeroes the block again, so the first pass's counts are not counted twice
       if (sl.report && (rc = report_enqueue(h, slot_report_args(h, sl)))) return rc;
+      // ... and the edit list: plain stores into what is read back, nothing accumulates
+      if (sl.edits && (rc = edits_enqueue(h, slot_edits_args(h, sl)))) return rc;
       HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64, hipMemcpyDeviceToHost, h->stream));
       HIPCHK(h, hipMemcpyAsync(sl.pin_mrg, sl.d_mrg, sl.m_dl, hipMemcpyDeviceToHost, h->stream));
     } else {
@@ -2243,6 +2319,20 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
     memcpy(sl.seq, sl.pin_mrg + sl.m_seq, (size_t)total);
     if (sl.want_q) memcpy(sl.qual, sl.pin_mrg + sl.m_qual, (size_t)total);
     if (sl.report) memcpy(sl.rep_out, sl.pin_mrg + sl.m_rep, (size_t)sl.n_reads * kReportCols * 8);
+    if (sl.edits) {
+      // the used prefix of the records alone: a copy of its own size on a stream of its own - the records are complete (ev_done
+      // lies behind the edit kernels, or the re-run above was waited for), and neither the compute stream nor d2h_stream, which
+      // may hold the other slot's kernels or wait for them, stands in front of it
+      const int64_t* eoff = (const int64_t*)(sl.pin_mrg + sl.m_eoff);
+      const int64_t n_ed = eoff[sl.n_reads];
+      if (n_ed < 0 || n_ed > sl.n) { h->err = "nrv_reads_raw_end: edit list out of range"; return NRV_E_HIP; }
+      memcpy(sl.eoff_out, eoff, ((size_t)sl.n_reads + 1) * 8);
+      if (n_ed > 0) {
+        HIPCHK(h, hipMemcpyAsync(sl.pin_mrg + sl.m_edits, sl.d_mrg + sl.m_edits, (size_t)n_ed * sizeof(nrv_edit), hipMemcpyDeviceToHost, h->edit_stream));
+        HIPCHK(h, hipStreamSynchronize(h->edit_stream));
+        memcpy(sl.edits_out, sl.pin_mrg + sl.m_edits, (size_t)n_ed * sizeof(nrv_edit));
+      }
+    }
     return NRV_OK;
   }
   const char* o = sl.pin_out + 64;
@@ -2334,10 +2424,10 @@ int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32
   return NRV_OK;
 }
 
-// nrv_merge_calls (report == nullptr: that call, to the byte) and nrv_merge_calls_report
+// nrv_merge_calls (report == nullptr: that call, to the byte), nrv_merge_calls_report and (edit_off != nullptr) nrv_merge_calls_edits
 static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
                             const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
-                            float tie_eps, uint64_t* report) {
+                            float tie_eps, uint64_t* report, nrv_edit* edits = nullptr, int64_t* edit_off = nullptr) {
   int rc = check_handle(h);
   if (rc) return rc;
   if (n_reads < 0 || n_win < 0 || !off || (n_reads > 0 && !ev_len)) { h->err = "nrv_merge_calls: bad arguments"; return NRV_E_INVALID; }
@@ -2358,18 +2448,21 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
   if (n == 0) {
     merge_nothing(bases, rd.data(), n_reads, N, seq, want_q ? qual : nullptr, off);
     if (report) report_nothing(rd.data(), n_reads, want_q, report);
+    if (edit_off) memset(edit_off, 0, ((size_t)n_reads + 1) * 8);
     return NRV_OK;
   }
+  if (edit_off && !edits) { h->err = "nrv_merge_calls_edits: null edits"; return NRV_E_INVALID; }
   // one block of its own: [reads | bases | a1 | a2 | p1 | p2 | merged block]
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const MergeLayout m = merge_layout(N, n, n_reads, report != nullptr);
-  const bool have_p = want_q || (report && p1 && p2);          // the report's near-tie column reads the rows without a quality too
+  const MergeLayout m = merge_layout(N, n, n_reads, report != nullptr, edit_off != nullptr);
+  const bool have_p = want_q || ((report || edit_off) && p1 && p2);   // the report's near-tie column and the edits' conf read the rows without a quality too
   const size_t o_b = up((size_t)n_reads * sizeof(SegRead)), o_a1 = o_b + up((size_t)N), o_a2 = o_a1 + up((size_t)n);
   const size_t o_p1 = o_a2 + up((size_t)n), o_p2 = o_p1 + (have_p ? up((size_t)n * 24) : 0), o_m = o_p2 + (have_p ? up((size_t)n * 20) : 0);
   const size_t bytes = o_m + m.bytes;
   char* d = nullptr;
   HIPCHK(h, hipMalloc((void**)&d, bytes));
   std::vector<char> back(m.dl);
+  int64_t n_ed = 0;
   auto run = [&]() -> int {
     int rc2 = poison_fill(h, d, bytes, h->stream);
     if (rc2) return rc2;
@@ -2395,8 +2488,16 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
     if (report && (rc2 = report_enqueue(h, report_args(a, have_p ? (const float*)(d + o_p1) : nullptr, have_p ? (const float*)(d + o_p2) : nullptr,
                                                       want_q, tie_eps, d + o_m + m.rep))))
       return rc2;
+    if (edit_off && (rc2 = edits_enqueue(h, edits_args(a, have_p ? (const float*)(d + o_p1) : nullptr, have_p ? (const float*)(d + o_p2) : nullptr,
+                                                      want_q, d + o_m + m.etile, d + o_m + m.eoff, d + o_m + m.edits))))
+      return rc2;
     HIPCHK(h, hipMemcpyAsync(back.data(), d + o_m, m.dl, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (edit_off) {                                             // the used prefix of the records, once the total is known
+      n_ed = ((const int64_t*)(back.data() + m.eoff))[n_reads];
+      if (n_ed < 0 || n_ed > n) { h->err = "nrv_merge_calls_edits: edit list out of range"; return NRV_E_HIP; }
+      if (n_ed > 0) HIPCHK(h, hipMemcpy(edits, d + o_m + m.edits, (size_t)n_ed * sizeof(nrv_edit), hipMemcpyDeviceToHost));
+    }
     return NRV_OK;
   };
   rc = run();
@@ -2409,6 +2510,7 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
   memcpy(seq, back.data() + m.seq, (size_t)total);
   if (want_q) memcpy(qual, back.data() + m.qual, (size_t)total);
   if (report) memcpy(report, back.data() + m.rep, (size_t)n_reads * kReportCols * 8);
+  if (edit_off) memcpy(edit_off, back.data() + m.eoff, ((size_t)n_reads + 1) * 8);
   return NRV_OK;
 }
 
@@ -2423,6 +2525,13 @@ int nrv_merge_calls_report(nrv_handle* h, const uint8_t* bases, const int64_t* e
   if (h && n_reads > 0 && !report) { h->err = "nrv_merge_calls_report: null report"; return NRV_E_INVALID; }
   static uint64_t none[NRV_REPORT_COLS];
   return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, seq, qual, off, tie_eps, report ? report : none);
+}
+
+int nrv_merge_calls_edits(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                          const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                          float tie_eps, uint64_t* report, nrv_edit* edits, int64_t* edit_off) {
+  if (h && !edit_off) { h->err = "nrv_merge_calls_edits: null edit_off"; return NRV_E_INVALID; }
+  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, seq, qual, off, tie_eps, report, edits, edit_off);
 }
 
 int nrv_saturated(nrv_handle* h, int64_t* pending, int64_t* reruns) {

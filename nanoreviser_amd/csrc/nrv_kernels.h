@@ -28,7 +28,9 @@
 //     samples, and ahead of it - once per call, only for nrv_reads_raw_stats_begin - the six launches of nrv_stats.h (median /
 //     MAD through integer histograms, per-base mean / std in NumPy's summation order), and behind the call's last group - only
 //     for nrv_revise_reads_raw_begin - the three launches of nrv_merge.h (calls -> packed revised reads) and, only for
-//     nrv_revise_reads_raw_report_begin, report_kernel of nrv_report.h behind them.  Rows (windows) are independent: no inter-workgroup communication anywhere.
+//     nrv_revise_reads_raw_report_begin, report_kernel of nrv_report.h behind them, and, only for nrv_revise_reads_raw_edits_begin,
+//     the three launches of nrv_edits.h (edits_count / edits_tile_scan / edits_scatter_kernel: the per-read edit list, a stream
+//     compaction in event order) behind those.  Rows (windows) are independent: no inter-workgroup communication anywhere.
 //   * One Bi-LSTM layer = one launch; a wave owns a group of hidden units x 4 gates x R row tiles, so
 //     i,f,g,o of one (window, unit) sit in the same lane and the cell update is register-local; c never leaves the
 //     wave, h_t goes through an LDS image (lstm_h2s_kernel: double-buffered, one barrier per step; lstm_h2w_kernel:
@@ -62,3 +64,4 @@
 #include "nrv_stats.h"         // stats_minmax / stats_hist / stats_scan / event_stats_kernel (read statistics on the device, opt-in)
 #include "nrv_merge.h"         // merge_emit / merge_tile_scan / merge_scatter_kernel (calls -> revised reads on the device, opt-in)
 #include "nrv_report.h"        // report_kernel (per-read revision report behind the merge, opt-in)
+#include "nrv_edits.h"         // edits_count / edits_tile_scan / edits_scatter_kernel (per-read edit list behind the merge, opt-in)

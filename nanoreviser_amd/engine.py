@@ -36,6 +36,7 @@ SYMBOLS = [
     "nrv_reads_raw_stats_begin", "nrv_predict_reads_raw_stats", "nrv_read_stats",
     "nrv_revise_reads_raw_begin", "nrv_revise_reads_raw", "nrv_merge_calls",
     "nrv_revise_reads_raw_report_begin", "nrv_revise_reads_raw_report", "nrv_merge_calls_report",
+    "nrv_revise_reads_raw_edits_begin", "nrv_revise_reads_raw_edits", "nrv_merge_calls_edits",
 ]
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 
@@ -81,12 +82,15 @@ _CALLS = ([_FP, _FP, _I8P, _I8P], lambda p: p[6])                               
 _STATS = ([_I32P, _U8P], lambda p: p[7:9])                                               # last_dur, on_device
 _MERGE = ([_U8P, _FP, _U8P, _U8P, _I64P], lambda p: (p[9], p[10]) + tuple(p[11]))        # bases, q_thr, seq, qual, off
 _REPORT = ([C.c_float, _U64P], lambda p: p[12:14])                                       # tie_eps, report
-# len(packed) -> (synchronous symbol, begin symbol, blocks, whether the call returns merged reads: (seq, qual, off[, report]))
+_EDITS = ([C.c_void_p, _I64P], lambda p: (p[14].ctypes.data, p[15]))                     # edits (nrv_edit records), edit_off
+# len(packed) -> (synchronous symbol, begin symbol, blocks, whether the call returns merged reads: (seq, qual, off[, report]
+# [, edits, edit_off]))
 _RAW_FORMS = {
     7: ("nrv_predict_reads_raw", "nrv_reads_raw_begin", (_CALLS,), False),
     9: ("nrv_predict_reads_raw_stats", "nrv_reads_raw_stats_begin", (_STATS, _CALLS), False),
     12: ("nrv_revise_reads_raw", "nrv_revise_reads_raw_begin", (_STATS, _MERGE), True),
     14: ("nrv_revise_reads_raw_report", "nrv_revise_reads_raw_report_begin", (_STATS, _MERGE, _REPORT), True),
+    16: ("nrv_revise_reads_raw_edits", "nrv_revise_reads_raw_edits_begin", (_STATS, _MERGE, _REPORT, _EDITS), True),
 }
 _READS_HEAD_T = _RAW_HEAD_T[:4] + [C.c_int64, C.POINTER(_ReadDesc), C.c_int]     # nrv_segment_reads, nrv_read_stats: no features
 _MERGE_CALLS_T = [C.c_void_p, _U8P, _I64P, C.c_int, _I8P, _I8P, _FP, _FP, C.c_int64] + _MERGE[0][1:]   # nrv_merge_calls
@@ -170,13 +174,16 @@ def load_library(path: Optional[str] = None):
     lib.nrv_window.argtypes = [vp]
     lib.nrv_device_count.argtypes = []
     have_report = hasattr(lib, "nrv_merge_calls_report")   # by presence: NRV_LIB may name an older build of the same ABI
+    have_edits = hasattr(lib, "nrv_merge_calls_edits")
     for sync, begin, blocks, _ in _RAW_FORMS.values():  # (every restype is ctypes' default, int: the nrv_* status)
-        if have_report or _REPORT not in blocks:
+        if (have_edits or _EDITS not in blocks) and (have_report or _REPORT not in blocks):
             getattr(lib, sync).argtypes = _RAW_HEAD_T + [t for types, _ in blocks for t in types]
             getattr(lib, begin).argtypes = getattr(lib, sync).argtypes + [C.POINTER(C.c_int)]
     lib.nrv_merge_calls.argtypes = _MERGE_CALLS_T
     if have_report:
         lib.nrv_merge_calls_report.argtypes = _MERGE_CALLS_T + _REPORT[0]
+    if have_edits:
+        lib.nrv_merge_calls_edits.argtypes = _MERGE_CALLS_T + _REPORT[0] + _EDITS[0]
     lib.nrv_reads_raw_end.argtypes = [vp, C.c_int]
     lib.nrv_segment_reads.argtypes = _READS_HEAD_T + [fp]
     lib.nrv_read_stats.argtypes = _READS_HEAD_T + [_I32P, _DP, _DP, _DP, _DP, fp]
@@ -401,10 +408,28 @@ class Reviser:
         return tuple(packed) + (float(tie_eps), np.zeros((packed[4], REPORT_COLS), np.uint64))
 
     @staticmethod
+    def with_device_edits(packed):
+        """A `with_device_merge` (12 elements) or `with_device_report` (14) tuple whose call also returns the per-read edit list
+        (include/nanorev.h nrv_revise_reads_raw_edits_begin; hoststage.revision_edits is the definition): `run_packed_raw` /
+        `begin_packed_raw` + `end_packed_raw` then return (seq, qual | None, off, report | None, edits[:total], edit_off) -
+        edits a hoststage.EDIT_DTYPE array, read r owning edits[edit_off[r]:edit_off[r + 1]].  Without a report (a 12-tuple) none
+        is counted."""
+        from .hoststage import EDIT_DTYPE
+        if len(packed) not in (12, 14):
+            raise ValueError("with_device_edits extends a with_device_merge or a with_device_report tuple")
+        if len(packed) == 12:
+            packed = tuple(packed) + (0.0, None)
+        n = packed[6][2].shape[0]
+        return tuple(packed) + (np.zeros(max(n, 1), EDIT_DTYPE), np.zeros(packed[4] + 1, np.int64))
+
+    @staticmethod
     def _trim_merged(out):
         seq, qual, off = out[:3]
         total = int(off[-1])
-        return (seq[:total], (qual[:total] if qual is not None else None), off) + tuple(out[3:])
+        more = tuple(out[3:])
+        if len(more) == 3:                            # (report | None, edits, edit_off): the used prefix of the records
+            more = (more[0], more[1][:int(more[2][-1])], more[2])
+        return (seq[:total], (qual[:total] if qual is not None else None), off) + more
 
     def _raw_head(self, packed):
         """The leading C arguments every raw-read entry point shares: handle, raw, n_raw, starts, feat, N, descs, n_reads."""
@@ -415,20 +440,20 @@ class Reviser:
         """One call of the raw-read family for a packed tuple of any form (`_RAW_FORMS`): its synchronous entry point, or its
         *_begin with the ticket behind the same arguments.  Returns (ticket number or None, outputs, merged)."""
         if len(packed) not in _RAW_FORMS:
-            raise ValueError(f"a packed raw-read call has 7, 9, 12 or 14 elements, not {len(packed)}")
+            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14 or 16 elements, not {len(packed)}")
         sync, beg, blocks, merged = _RAW_FORMS[len(packed)]
-        if not hasattr(self._lib, beg):               # the report pair is found by presence
+        if not hasattr(self._lib, beg):               # the report pair and the edits pair are found by presence
             raise NrvError(-1, f"this build of libnanorev_hip.so has no {beg}")
         args = self._raw_head(packed)
         for types, pick in blocks:
             args += _marshal(pick(packed), types)
         t = C.c_int(-1)
         self._check(getattr(self._lib, beg)(*args, C.byref(t)) if begin else getattr(self._lib, sync)(*args))
-        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) if merged else packed[6]), merged
+        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) if merged else packed[6]), merged
 
     def run_packed_raw(self, packed):
         """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared (or `with_device_stats` /
-        `with_device_merge` / `with_device_report` extended)."""
+        `with_device_merge` / `with_device_report` / `with_device_edits` extended)."""
         _, out, merged = self._raw_call(packed, False)
         return self._trim_merged(out) if merged else out
 
@@ -440,7 +465,8 @@ class Reviser:
 
     def end_packed_raw(self, ticket):
         """Second half: waits for the call `ticket` names and returns its (p1, p2, a1, a2) - or, for a `with_device_merge`
-        call, its (seq, qual, off), with the report behind them for a `with_device_report` call."""
+        call, its (seq, qual, off), with the report behind them for a `with_device_report` call and (report | None, edits,
+        edit_off) for a `with_device_edits` call."""
         t, out = ticket[:2]
         self._check(self._lib.nrv_reads_raw_end(self._h, t))
         return self._trim_merged(out) if len(ticket) == 3 else out
@@ -524,6 +550,24 @@ class Reviser:
         rep = np.zeros((ins[1].size, REPORT_COLS), np.uint64)
         more = _marshal((REPORT_TIE_EPS if tie_eps is None else tie_eps, rep), _REPORT[0])
         return self._merge_call("nrv_merge_calls_report", *ins, *more) + (rep,)
+
+    def merge_calls_edits_device(self, bases, ev_len, a1, a2, p1=None, p2=None, q_thr=None, tie_eps=None, report=True):
+        """`merge_calls_report_device` with the per-read edit list (nrv_merge_calls_edits): p1 / p2 may be given without q_thr
+        (conf filled, qual 0).  report=False: no report is counted.  Returns (seq, qual | None, off, report | None,
+        edits[:total], edit_off) - edits and edit_off are hoststage.revision_edits', bit for bit."""
+        from .hoststage import EDIT_DTYPE, REPORT_TIE_EPS
+        if not hasattr(self._lib, "nrv_merge_calls_edits"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_merge_calls_edits")
+        ins = self._merge_inputs(bases, ev_len, a1, a2, p1, p2, q_thr, p1 is not None and p2 is not None)
+        n, (q1, q2, thr) = ins[2].size, ins[4:]
+        if q1 is not None and (q1.shape[0] != n or q2.shape[0] != n):
+            raise ValueError("p1 / p2 do not match")
+        if thr is not None and (thr.size != 39 or q1 is None):
+            raise ValueError("q_thr needs 39 entries and p1 / p2")
+        rep = np.zeros((ins[1].size, REPORT_COLS), np.uint64) if report else None
+        edits, edit_off = np.zeros(max(n, 1), EDIT_DTYPE), np.zeros(ins[1].size + 1, np.int64)
+        more = _marshal((REPORT_TIE_EPS if tie_eps is None else tie_eps, rep, edits.ctypes.data, edit_off), _REPORT[0] + _EDITS[0])
+        return self._merge_call("nrv_merge_calls_edits", *ins, *more) + (rep, edits[:int(edit_off[-1])], edit_off)
 
     @staticmethod
     def _fingerprint(a):
