@@ -265,6 +265,47 @@ int nrv_merge_calls_edits(nrv_handle* h, const uint8_t* bases, const int64_t* ev
                           const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
                           float tie_eps, uint64_t* report, nrv_edit* edits, int64_t* edit_off);
 
+/* The same revised reads laid out as the BYTES OF AN OUTPUT FILE (opt-in; nothing above changes): one well-formed FASTA / FASTQ
+ * record per read, packed on the device behind the merge (and the report / edit launches), so that a caller appends `blob` to a
+ * file with one write and derives an index from rec_off.  The arguments of nrv_revise_reads_raw_edits_begin - `report` may be
+ * NULL as there, `edits` / `edit_off` may both be NULL (no edit list), and `seq` / `qual` may be NULL (the merged reads are then
+ * not handed back and do not cross PCIe; `off` is still filled) - then
+ *   names     uint8 [name_off[n_reads]]: the record names, concatenated (no terminators); uploaded with the call's inputs;
+ *   name_off  int64 [n_reads + 1]: read r's name is names[name_off[r] .. name_off[r + 1]); ascending from 0;
+ *   blob      uint8 [name_off[n_reads] + q (N + max(N - T, 0)) + 3 q n_reads], q = 2 for FASTQ and 1 for FASTA: the capacity.  Only
+ *             the used prefix crosses PCIe and is written: bytes at and beyond rec_off[n_reads] are not touched;
+ *   rec_off   int64 [n_reads + 1]: read r owns blob[rec_off[r] .. rec_off[r + 1]); rec_off[n_reads] is the total.
+ * With L = off[r + 1] - off[r] and nl the length of the name, a record is
+ *   FASTA  '>' name '\n' seq '\n'                       nl + L + 3 bytes
+ *   FASTQ  '@' name '\n' seq '\n' '+' '\n' qual '\n'    nl + 2 L + 6 bytes
+ * without line wrapping; a read without bases has its record too (empty lines).  FASTQ or FASTA is decided by q_thr (non-NULL:
+ * FASTQ), whether `qual` is handed back or not.  hoststage.pack_records is the definition: copies and integer offsets only, so
+ * the bytes are that function's on the (seq, qual, off) of nrv_revise_reads_raw_begin, in every precision mode and whatever
+ * order the workgroups ran in.  seq / qual / off / report / edits / edit_off are those of nrv_revise_reads_raw_edits_begin.
+ * N <= T: nothing is enqueued; the records are formed on the host from `bases`, every quality '#'.  A call whose capacity
+ * reaches 4 GiB is declined (NRV_E_INVALID).
+ * Tickets, the two-calls-in-flight rule, the failure paths and the range-guard re-run (which runs the two launches again behind
+ * the merge: plain stores, nothing accumulates) are those of nrv_revise_reads_raw_begin; `blob` and `rec_off` must stay valid
+ * until nrv_reads_raw_end, which reads the total from the downloaded rec_off, checks it against the capacity and fetches
+ * `total` bytes in a second copy, as it fetches the edit records.  nrv_revise_reads_raw_records IS _records_begin + _end. */
+int nrv_revise_reads_raw_records_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                       const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                       const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                       uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                       nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                       uint8_t* blob, int64_t* rec_off, int* ticket);
+int nrv_revise_reads_raw_records(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                 const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                 const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                 uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                 nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                 uint8_t* blob, int64_t* rec_off);
+/* The record launches alone, on merged reads the HOST supplies (what nrv_merge_calls returned): seq / qual uint8 [off[n_reads]]
+ * (qual NULL: FASTA), off int64 [n_reads + 1] ascending from 0, names / name_off / blob / rec_off as above, the blob's capacity
+ * being name_off[n_reads] + q off[n_reads] + 3 q n_reads.  The twin of nrv_merge_calls used by the parity tests. */
+int nrv_pack_records(nrv_handle* h, const uint8_t* seq, const uint8_t* qual, const int64_t* off, int n_reads,
+                     const uint8_t* names, const int64_t* name_off, uint8_t* blob, int64_t* rec_off);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

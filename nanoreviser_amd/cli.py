@@ -126,7 +126,20 @@ def get_args(argv: Optional[Sequence[str]] = None):
                         "computed from.  A read written unrevised gets the header alone.  With --device_merge the list is compacted on "
                         "the GPU behind the merge, everywhere else it is formed by the host stage from the calls it holds: the same "
                         "files byte for byte.  Off by default; without it nothing changes and DIR is not created")
+    p.add_argument("--combined", dest="combined", default=None, metavar="FILE",
+                   help="write every read's record into ONE file, FILE, instead of one <stem>_out.<format> per read (also "
+                        "NRV_COMBINED=FILE): well-formed FASTA / FASTQ records without line wrapping (in FASTQ a newline in front of "
+                        "'+' and one at the end, which the per-read files leave out), sequence and quality lines exactly those of the "
+                        "per-read files, plus FILE.fai in samtools faidx layout.  With --device_merge the records are laid out on the "
+                        "GPU behind the merge and a device call's reads are appended with one write; everywhere else the host stage "
+                        "forms them from the reads it holds: the same records.  Their order is not specified beyond the reads of one "
+                        "device call staying together.  --report and --edits work unchanged next to it; --resume does not.  Off by "
+                        "default; without it nothing changes and FILE is not created")
     a = p.parse_args(argv)
+    a.combined = a.combined or (os.environ.get("NRV_COMBINED", "").strip() or None)
+    if a.combined and a.resume:
+        print("[！！！Error] --resume cannot be used with --combined: a combined run cannot be resumed", file=sys.stderr)
+        raise SystemExit(2)
     a.edits = a.edits or (os.environ.get("NRV_EDITS", "").strip() or None)
     a.device_stats = bool(a.device_stats) or device_stats_env()
     a.device_merge = bool(a.device_merge) or device_merge_env()
@@ -521,6 +534,210 @@ def _write_records_native(spec, fns, seq, qual, off):
     return _native_task(spec, fns, lambda names, dsts, fq: hostlib.write_records(seq, qual, off, names, dsts, fq))
 
 
+def _fai_line(name: bytes, length: int, start: int, fastq: bool) -> bytes:
+    """The samtools faidx line of the record that starts at byte `start` of its file: name, length, offset of the first base,
+    linebases (= length: no wrapping), linewidth (= length + 1) and, FASTQ, the offset of the first quality."""
+    o = start + len(name) + 2
+    cols = [length, o, length, length + 1] + ([o + length + 3] if fastq else [])
+    return name + b"\t" + "\t".join(str(int(c)) for c in cols).encode() + b"\n"
+
+
+def _fai_record(cols, fastq: bool):
+    """(start, bytes) of the record an index line describes."""
+    name, length, o = cols[0], int(cols[1]), int(cols[2])
+    return o - len(name) - 2, len(name) + (2 * length + 6 if fastq else length + 3)
+
+
+class CombinedPart:
+    """One process' share of --combined FILE: the records go to `path`, one faidx line per record (offsets inside the part) to
+    `path`'s index part - the blob first, then the index lines, both flushed per call, so a record counts as written when its
+    index line is complete.  `merge_combined` puts the parts together."""
+
+    def __init__(self, path: Optional[str], fastq: bool = False):
+        self.path, self.fastq, self._lock, self._fp, self._ix, self._size = path, fastq, threading.Lock(), None, None, 0
+        self.index_path = combined_index_part(path) if path else None
+
+    def __bool__(self):
+        return self.path is not None
+
+    def add_blob(self, fns, blob, rec_off, off):
+        """The records of the reads `fns` as one blob (hoststage.pack_records' layout; off: the reads' offsets into seq)."""
+        names = [hs.record_name(fn) for fn in fns]
+        data = np.ascontiguousarray(blob, dtype=np.uint8)[:int(rec_off[-1])].tobytes()
+        with self._lock:
+            if self._fp is None:
+                d = os.path.dirname(self.path)
+                if d:
+                    os.makedirs(d, exist_ok=True)
+                self._fp, self._ix = open(self.path, "wb"), open(self.index_path, "wb")
+            self._fp.write(data)
+            self._fp.flush()
+            self._ix.write(b"".join(_fai_line(nm, int(off[r + 1]) - int(off[r]), self._size + int(rec_off[r]), self.fastq)
+                                    for r, nm in enumerate(names)))
+            self._ix.flush()
+            self._size += len(data)
+
+    def add(self, fns, seq, qual, off):
+        """Merged reads (hoststage.emit_calls' form) through the definition of the records."""
+        seq = np.asarray(seq, np.uint8).reshape(-1)
+        if self.fastq and qual is None:               # no window at all: every base keeps quality '#'
+            qual = np.full(seq.size, ord("#"), np.uint8)
+        blob, rec_off = hs.pack_records([hs.record_name(fn) for fn in fns], seq, qual if self.fastq else None, off)
+        self.add_blob(fns, blob, rec_off, off)
+
+    def add_read(self, fn: str, seq: str, qual: Optional[str]):
+        s = np.frombuffer(seq.encode("ascii"), np.uint8)
+        q = np.frombuffer(qual.encode("ascii"), np.uint8) if (self.fastq and qual is not None) else None
+        self.add([fn], s, q, np.array([0, s.size], np.int64))
+
+    def close(self):
+        with self._lock:
+            for fp in (self._fp, self._ix):
+                if fp is not None:
+                    fp.close()
+            self._fp = self._ix = None
+
+
+def combined_part_path(combined: str, rank) -> str:
+    return f"{combined}.part{rank}"
+
+
+def combined_index_part(part: str) -> str:
+    """FILE.part<rank> -> FILE.fai.part<rank>."""
+    head, _, rank = part.rpartition(".part")
+    return f"{head}.fai.part{rank}"
+
+
+def clear_combined_parts(combined: str):
+    import glob
+    for f in glob.glob(glob.escape(combined) + ".part*") + glob.glob(glob.escape(combined) + ".fai.part*"):
+        try:
+            os.remove(f)
+        except OSError:
+            pass
+
+
+def merge_combined(combined: str, fastq: bool):
+    """Parent side of --combined: the parts in ascending rank order, the parent's own last, become FILE and FILE.fai with the
+    offsets shifted.  A part's records are those of its complete index lines that lie inside the part (bytes beyond the last of
+    them - a worker died mid-write - are dropped); of a read with several records the LAST one stays (a lost worker's read the
+    parent wrote again).  One part with nothing to drop is renamed, not copied.  Both files appear by rename; the parts are removed."""
+    import glob
+
+    def rank_of(f):
+        r = f.rsplit(".part", 1)[1]
+        return (1, 0) if r == "parent" else (0, int(r) if r.isdigit() else 1 << 30)
+    parts = sorted((f for f in glob.glob(glob.escape(combined) + ".part*")), key=rank_of)
+    ncol = 6 if fastq else 5
+    recs, last = [], {}                               # (part, name, length, start, bytes); name -> index of its last record
+    clean = True
+    for k, f in enumerate(parts):
+        try:
+            size = os.path.getsize(f)
+            with open(combined_index_part(f), "rb") as fp:
+                lines = fp.read().split(b"\n")
+        except OSError:
+            clean = False
+            continue
+        end = 0
+        if lines[-1] != b"":                          # a line cut short is not a line
+            clean = False
+        for ln in lines[:-1]:
+            c = ln.split(b"\t")
+            try:
+                start, nbytes = _fai_record(c, fastq) if len(c) == ncol else (-1, 0)
+            except ValueError:
+                start = -1
+            if start != end or start + nbytes > size:  # records lie back to back: anything else ends the part
+                clean = False
+                break
+            if c[0] in last:
+                clean = False
+            last[c[0]] = len(recs)
+            recs.append((k, c[0], int(c[1]), start, nbytes))
+            end = start + nbytes
+        if end != size:
+            clean = False
+    d = os.path.dirname(combined)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    if clean and len(parts) == 1:
+        os.replace(combined_index_part(parts[0]), combined + ".fai")
+        os.replace(parts[0], combined)
+        return
+    tmp, tmp_ix = f"{combined}.tmp{os.getpid()}", f"{combined}.fai.tmp{os.getpid()}"
+    with open(tmp, "wb") as out, open(tmp_ix, "wb") as ix:
+        pos, src, src_k = 0, None, None
+        for i, (k, name, length, start, nbytes) in enumerate(recs):
+            if last[name] != i:
+                continue
+            if src_k != k:
+                if src is not None:
+                    src.close()
+                src, src_k = open(parts[k], "rb"), k
+            src.seek(start)
+            out.write(src.read(nbytes))
+            ix.write(_fai_line(name, length, pos, fastq))
+            pos += nbytes
+        if src is not None:
+            src.close()
+    os.replace(tmp, combined)
+    os.replace(tmp_ix, combined + ".fai")
+    for f in parts:
+        for g in (f, combined_index_part(f)):
+            try:
+                os.remove(g)
+            except OSError:
+                pass
+
+
+def deliver(spec, sink, fns, payload, native: bool = True):
+    """THE decision about where finished reads go, for every path that has some: into the --combined sink (`CombinedPart`, through
+    hoststage.pack_records - or as they are, when the device laid the records out) or, without one, into one file per read by the
+    writer the path has always used.  payload is what the path holds:
+      ("text", seq, qual)                          one read as strings (`write_read`)
+      ("calls", T, bases, a1, a2, qc)              one read's calls (`_finish_native` / `_finish_in_worker`)
+      ("bundle", T, bases, ev_len, a1, a2, qc)     the calls of all reads of a device call (`_finish_bundle_native`)
+      ("merged", seq, qual, off)                   a --device_merge call's revised reads (`_write_records_native`)
+      ("records", blob, rec_off, off)              a `with_device_records` call's blob (sink only)
+    Returns [(bases written, error)] per read; "text" raises instead, as `write_read` does."""
+    kind, rest = payload[0], payload[1:]
+    if sink is None or not sink:
+        if kind == "text":
+            write_read(spec, fns[0], *rest)
+            return [(len(rest[0]), None)]
+        if kind == "calls":
+            return [(_finish_native if native else _finish_in_worker)(spec, rest[0], fns[0], *rest[1:])]
+        if kind == "bundle":
+            return _finish_bundle_native(spec, rest[0], fns, *rest[1:])
+        if kind == "merged":
+            return _write_records_native(spec, fns, *rest)
+        raise ValueError(f"deliver: {kind} needs a sink")
+    if kind == "text":
+        sink.add_read(fns[0], *rest)
+        return [(len(rest[0]), None)]
+    try:
+        if kind == "calls":
+            seq, qual = _merge_read(rest[0], *rest[1:])
+            sink.add_read(fns[0], seq, qual)
+            return [(len(seq), None)]
+        if kind == "bundle":
+            T, bases, ev_len, a1, a2, qc = rest
+            seq, qual, off = hs.emit_calls(hostlib.bases_u8(bases), ev_len, a1, a2, qc, T)
+            sink.add(fns, seq, qual, off)
+        elif kind == "merged":
+            seq, qual, off = rest
+            sink.add(fns, seq, qual, off)
+        else:
+            blob, rec_off, off = rest
+            if len(rec_off) != len(fns) + 1 or len(off) != len(fns) + 1:
+                raise ValueError("deliver: the records do not match the reads")
+            sink.add_blob(fns, blob, rec_off, off)
+        return [(int(off[r + 1]) - int(off[r]), None) for r in range(len(fns))]
+    except Exception as e:
+        return [(0, repr(e))] * len(fns)
+
+
 REPORT_HEADER = "name\tstatus\t" + "\t".join(hs.REPORT_NAMES)
 
 
@@ -661,9 +878,9 @@ def write_edits(edits_dir: str, fast5_fn: str, edits=None, want_qual: bool = Fal
 
 
 def _host_merge_form(packed):
-    """A `with_device_merge` / `with_device_report` / `with_device_edits` tuple back in the form whose call returns (p1, p2, a1,
-    a2): for the paths that keep the host merge."""
-    if packed is None or len(packed) not in (12, 14, 16):
+    """A `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` tuple back in the form whose call
+    returns (p1, p2, a1, a2): for the paths that keep the host merge."""
+    if packed is None or len(packed) not in (12, 14, 16, 20):
         return packed
     return tuple(packed[:7]) if packed[7] is None else tuple(packed[:9])
 
@@ -678,11 +895,12 @@ def _bundle_has_bases(bundle) -> bool:
     return "bases" in bundle and len(bundle["bases"]) == int(bundle["meta"][:, 1].sum())
 
 
-def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, report, edits=False):
+def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, report, edits=False, combined=False):
     """The one decision about a batch: (packed form `_FileRun.submit` builds, route `_FileRun.run_batch` takes).  Pure: it looks at what
     the engine object offers, at the bundle (None: reads that arrived one by one) and at the run's switches - pipelined (one
     engine, NRV_CLI_PIPELINE != 0), native_pool (libnanorev_host.so driven from the thread pool), device_merge (--device_merge
-    and what it needs: pipelined, native_pool, nrvh_write_records), report (--report), edits (--edits).  "bases": `_bundle_has_bases`.  A form is
+    and what it needs: pipelined, native_pool, nrvh_write_records), report (--report), edits (--edits), combined (--combined).  "bases":
+    `_bundle_has_bases`.  A form is
     the length of the packed tuple (engine.Reviser), None, or "host-merge": the merge form built and taken back.
 
       bundle  engine offers / bundle / switches                              form            route
@@ -696,6 +914,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
       yes     + report on, no with_device_report                             host-merge [2]  by the last three rows
       yes     + edits on, with_device_edits (+ report on: with_device_report)  16 [4]          by the last three rows
       yes     + edits on, one of them missing                                host-merge [2]  by the last three rows
+      yes     + combined on, a form 12 / 14 / 16 above, with_device_records  20 [5]          by the last three rows
+      yes     + combined on, no with_device_records                          12 / 14 / 16 [6]  by the last three rows
       yes     any form; pipelined, native_pool, begin_packed_raw, bases                      pipelined [3]
       yes     any form; native_pool, bases, not (pipelined, begin_packed_raw)                packed+finish_bundle
       yes     any form; no native_pool, or no bases                                          packed sliced
@@ -704,7 +924,10 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
     [2] the whole bundle on the host: merge, quality and report rows from the calls.
     [3] begin_packed_raw raising -> packed+finish_bundle.  Every route but this one takes a 12 / 14 form back through
         `_host_merge_form`; any call raising -> per-read retries on reads that `_bundle_reads` completes on the host.
-    [4] the one call carries the report too when --report is set."""
+    [4] the one call carries the report too when --report is set.
+    [5] the one call carries the report and the edit list too when --report / --edits are set; its blob is appended to the
+        --combined part as it is, and no native writer is called.
+    [6] the merged reads come back and the host forms the records (hoststage.pack_records), as on every host route."""
     unpacked = "per-read" if n_reads == 1 else "predict_many"
     if bundle is None:
         return (7 if n_reads > 1 and hasattr(rv, "pack_reads_raw") else None), unpacked
@@ -716,6 +939,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
         form = 12 if not report else (14 if hasattr(rv, "with_device_report") else "host-merge")
         if edits:
             form = 16 if hasattr(rv, "with_device_edits") and form != "host-merge" else "host-merge"
+        if combined and form != "host-merge" and hasattr(rv, "with_device_records"):
+            form = 20
     if not (native_pool and bases):
         return form, "packed sliced"
     return form, ("pipelined" if pipelined and hasattr(rv, "begin_packed_raw") else "packed+finish_bundle")
@@ -823,7 +1048,7 @@ class _FileRun:
     """One `process_files` call: its state and its three kinds of thread.  MAIN reads `results()`, packs device calls as
     `_route_batch` says (`submit`) and collects the pooled finishers; the ENGINE thread(s) make the calls (`run_batch`, `collect`);
     the one FINISHER thread merges, reports and writes, or hands that to the parser pool (`finish_batch`, `finish_call`)."""
-    def __init__(self, stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part):
+    def __init__(self, stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part=None):
         self.args, self.log, self.note = args, log, on_file or (lambda fn, ok: None)
         self.stats = {"reads": 0, "bases": 0, "failed": [], "host_s": 0.0, "engine_s": 0.0}
         self.stats_lock = threading.Lock()
@@ -831,6 +1056,7 @@ class _FileRun:
         self.rep_rows = {}                            # fn -> the row of a read whose output is not final yet
         self.tie_eps = float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS))
         self.edits_dir = getattr(args, "edits", None) # --edits: every read's list is written BEFORE its output is
+        self.sink = CombinedPart(combined_part, args.output_format == "fastq") if combined_part else None   # --combined (`deliver`)
         self.trace = _Trace()
         self.want_qual, self.spec = args.output_format == "fastq", _OutSpec(args)
         # `reviser` may be a zero-argument factory: the engine is then created by the engine thread as its first task, WHILE
@@ -935,6 +1161,8 @@ class _FileRun:
     def summary(self):
         """After the threads have ended: the report part closed, the trace and the range guard logged; the statistics."""
         self.report.close()
+        if self.sink is not None:
+            self.sink.close()
         self.trace.log_summary(self.log, len(self.engines))
         guarded = [rv for rv in self.engines if callable(getattr(rv, "saturated", None))]
         if guarded:                                   # f16x2 range guard: stages re-run on the f32 kernels
@@ -978,11 +1206,11 @@ class _FileRun:
         try:
             if args.output_format == "fastq" and fq is not None:
                 b, q = hs.trim_fastq(fq)
-                write_read(args, fn, b, q)
+                deliver(args, self.sink, [fn], ("text", b, q))
                 nw = len(b)
             else:
                 orig = "".join(x.decode() for x in np.asarray(rt.bases).tolist())
-                write_read(args, fn, orig, None)
+                deliver(args, self.sink, [fn], ("text", orig, None))
                 nw = len(orig)
         except Exception as e2:
             log(f"[！！！Error] stroring : {fn.split('.')[0]}_out.{args.output_format}...... {e2}")
@@ -1014,7 +1242,7 @@ class _FileRun:
             if bundle is not None and "device_stats" in bundle and not (hasattr(rv, "run_packed_raw") and hasattr(rv, "with_device_stats")):
                 bundle = _bundle_host_stats(bundle)   # an engine without the new calls: the host computes them after all
             form, route = _route_batch(rv, bundle, len(batch), self.pipelined, self.native_pool, self.device_merge, bool(self.report),
-                                       edits=bool(self.edits_dir))
+                                       edits=bool(self.edits_dir), combined=self.sink is not None)
             if form is not None and bundle is None:
                 packed = prepare_many(cls, [rt for _, rt, _ in batch], rv.T)
             elif form is not None:
@@ -1028,8 +1256,10 @@ class _FileRun:
                     elif form != len(packed):
                         if self.report:
                             packed = cls.with_device_report(packed, self.tie_eps)
-                        if form == 16:                # --edits: the list behind the merge (and the report)
+                        if form == 16 or (form == 20 and self.edits_dir):   # --edits: the list behind the merge (and the report)
                             packed = cls.with_device_edits(packed)
+                        if form == 20:                # --combined: the records behind them all; seq / qual stay on the device
+                            packed = cls.with_device_records(packed, [hs.record_name(fn) for fn, _, _ in batch], hand_back=False)
         except Exception:
             packed = None
         if packed is None:
@@ -1049,6 +1279,7 @@ class _FileRun:
             many = isinstance(fn, list)
             try:
                 res = fut.result()
+                res = res if many else res[0]         # (`deliver` answers per read)
             except Exception as e:                    # the pool broke (a parser process died)
                 res = [(0, repr(e))] * len(fn) if many else (0, repr(e))
             for (nb, err), f1, r1, q1 in (zip(res, fn, rt, fq) if many else [(res, fn, rt, fq)]):
@@ -1069,15 +1300,21 @@ class _FileRun:
                     self.rep_rows[fn] = report_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual, self.tie_eps)[0]
                 if self.edits_dir:
                     write_edits(self.edits_dir, fn, edit_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual)[0], self.want_qual)
-                if self.pool is not None:
+                if self.pool is not None or self.sink is not None:
                     p1, p2, a1, a2 = c
                     qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
-                    task = self.pool.submit(_finish_native if self.native_threads else _finish_in_worker, self.spec, T, fn,
-                                            np.asarray(rt.bases), np.asarray(a1), np.asarray(a2), qc)
-                    self.finishing.append((task, fn, rt, fq))
+                    payload = ("calls", T, np.asarray(rt.bases), np.asarray(a1), np.asarray(a2), qc)
+                    if self.sink is None:
+                        task = self.pool.submit(deliver, self.spec, None, [fn], payload, self.native_threads)
+                        self.finishing.append((task, fn, rt, fq))
+                        continue
+                    (nb, err), = deliver(self.spec, self.sink, [fn], payload)      # the sink is this process' own: written here
+                    if err is not None:
+                        raise RuntimeError(err)
+                    self.finished(fn, nb)
                     continue
                 seq, qual = _finish_read(T, rt, *c, want_qual=self.want_qual)
-                write_read(self.args, fn, seq, qual)
+                deliver(self.args, None, [fn], ("text", seq, qual))
                 self.finished(fn, len(seq))
             except Exception as e:
                 self.fallback(fn, rt, fq, e)
@@ -1092,7 +1329,8 @@ class _FileRun:
                     self.rep_rows.update(zip(fns, outs[3]))
                 if self.edits_dir:                    # a `with_device_edits` call: the lists were compacted behind the merge
                     self.write_call_edits(fns, outs[4], outs[5])
-                fut = self.pool.submit(_write_records_native, self.spec, fns, outs[0], outs[1] if self.want_qual else None, outs[2])
+                payload = ("records", outs[6], outs[7], outs[2]) if len(outs) == 8 else \
+                    ("merged", outs[0], outs[1] if self.want_qual else None, outs[2])
             else:
                 p1, p2, a1, a2 = outs
                 T, ev_len = self.rv.T, bundle["meta"][:, 1].astype(np.int64)
@@ -1101,8 +1339,15 @@ class _FileRun:
                 if self.edits_dir:
                     self.write_call_edits(fns, *edit_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2, self.want_qual))
                 qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
-                fut = self.pool.submit(_finish_bundle_native, self.spec, T, fns, bundle["bases"], ev_len, a1, a2, qc)
-            self.finishing.append((fut, fns, rts, fqs))
+                payload = ("bundle", T, bundle["bases"], ev_len, a1, a2, qc)
+            if self.sink is None:
+                self.finishing.append((self.pool.submit(deliver, self.spec, None, fns, payload), fns, rts, fqs))
+                return
+            for (nb, err), fn, rt, fq in zip(deliver(self.spec, self.sink, fns, payload), fns, rts, fqs):   # one append, here
+                if err is None:
+                    self.finished(fn, nb)
+                else:
+                    self.fallback(fn, rt, fq, err)
         except Exception as e:
             for fn, rt, fq in batch:
                 self.fallback(fn, rt, fq, e)
@@ -1187,7 +1432,7 @@ class _FileRun:
 
 def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None],
                   on_file: Optional[Callable[[str, bool], None]] = None, gpu_workers: int = 1,
-                  core_share: Optional[int] = None, report_part: Optional[str] = None) -> dict:
+                  core_share: Optional[int] = None, report_part: Optional[str] = None, combined_part: Optional[str] = None) -> dict:
     """Revise `files` (names inside args.fast5_base_dir) with one engine.  The host stage (HDF5 parsing, event collapse,
     statistics) runs --thread parser workers that stay a bounded number of reads ahead of the device: THREADS of this process
     inside libnanorev_host.so (at most kNativePoolMax), or PROCESSES on the Python host stage without it / with NRV_HOST_THREADS=0.
@@ -1197,10 +1442,11 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
     SHARED, so each call's parser pool gets usable_cores() // gpu_workers of them - eight workers on a 16-core cgroup
     start 8 x 2 parser workers, not 8 x 16.  core_share: this call's cores, when the caller has already
     divided them (a GPU worker pinned to its NUMA slice: `_worker`).  report_part (--report): the file this call appends
-    one line per read to, ahead of on_file (`ReportPart`)."""
+    one line per read to, ahead of on_file (`ReportPart`).  combined_part (--combined): the part this call appends
+    every read's record to INSTEAD of writing one file per read (`CombinedPart`, `deliver`)."""
     import contextlib
     with contextlib.ExitStack() as stack:             # its exit ends the run's threads and undoes what `_FileRun._start` did
-        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part)
+        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part)
         batch, nev = [], 0                            # unbundled reads are grouped into device calls of >= batch_events events
         for entries, bundle in run.results():
             bundled = []
@@ -1367,6 +1613,8 @@ def check_output_rate(args, world: int, n_reads: int, log=print) -> Optional[flo
     must cover the whole run's share with a factor of two to spare (the finishers are a few threads per worker).
     NRV_OUTPUT_PROBE=0 turns the probe off, =1 forces it."""
     mode = os.environ.get("NRV_OUTPUT_PROBE", "")
+    if getattr(args, "combined", None):               # --combined: no per-read creates, nothing to probe
+        return None
     if mode == "0" or (mode != "1" and (world < 2 or n_reads < 4000)):
         return None
     rate = probe_rename_rate(args.output_dir)
@@ -1467,7 +1715,8 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
             q.put(("part", rank, fn, k, payload, err))
         st = process_files(args, files, rv if rv is not None else make, print,
                            on_file=lambda fn, ok: q.put(("file", rank, fn, bool(ok))), gpu_workers=world, core_share=share,
-                           report_part=report_part_path(args.report, rank) if getattr(args, "report", None) else None)
+                           report_part=report_part_path(args.report, rank) if getattr(args, "report", None) else None,
+                           combined_part=combined_part_path(args.combined, rank) if getattr(args, "combined", None) else None)
         st["cpus"] = len(cpus) if cpus else 0
         for e in made:
             e.close()
@@ -1476,7 +1725,8 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
         q.put(("done", rank, None, repr(e)))
 
 
-def write_originals(args, files: Sequence[str], log: Callable[[str], None], report: Optional[ReportPart] = None) -> List[str]:
+def write_originals(args, files: Sequence[str], log: Callable[[str], None], report: Optional[ReportPart] = None,
+                    sink: Optional[CombinedPart] = None) -> List[str]:
     """The failure contract for reads whose WORKER is gone (NanoReviser.py:146-152 / :173-179): every
     file in `files` - the ones the dead worker never reported as final - gets its original basecalls
     written by this process (atomically, replacing whatever an earlier run left under that name).
@@ -1491,10 +1741,10 @@ def write_originals(args, files: Sequence[str], log: Callable[[str], None], repo
                 write_edits(args.edits, fn)
             if args.output_format == "fastq" and fq is not None:
                 b, q = hs.trim_fastq(fq)
-                write_read(args, fn, b, q)
+                deliver(args, sink, [fn], ("text", b, q))
             else:
                 b = "".join(x.decode() for x in np.asarray(rd.bases).tolist())
-                write_read(args, fn, b, None)
+                deliver(args, sink, [fn], ("text", b, None))
             nw = len(b)
         except Exception as e:
             log(f"！！！[Error] fast5 file: {fn.split('.')[0]} {e!r}")
@@ -1503,7 +1753,8 @@ def write_originals(args, files: Sequence[str], log: Callable[[str], None], repo
     return done
 
 
-def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[str], None], report: Optional[ReportPart] = None):
+def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[str], None], report: Optional[ReportPart] = None,
+                       sink: Optional[CombinedPart] = None):
     """Parent side of the split reads: the slices' calls in slice order are the read's calls (window i of slice k is
     window lo_k + i of the read), merged and written exactly as an unsplit read's.  A read with a slice missing (its
     worker died) or failed gets its original basecalls (NanoReviser.py:146-152).  Returns (bases written, failed names)."""
@@ -1530,7 +1781,7 @@ def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[st
                     np.concatenate([p["p1"] for p in pl]) if have_p else None, np.concatenate([p["p2"] for p in pl]) if have_p else None,
                     (qc if qc is not None else np.zeros(0, np.uint8)) if args.output_format == "fastq" else None, T)[0],
                     args.output_format == "fastq")
-            w, e2 = (_finish_native if hostlib.load() is not None else _finish_in_worker)(spec, T, fn, pl[0]["bases"], a1, a2, qc)
+            (w, e2), = deliver(spec, sink, [fn], ("calls", T, pl[0]["bases"], a1, a2, qc), hostlib.load() is not None)
             if e2 is None:
                 nb += w
                 log(f"[p:::] {fn.split('.')[0]}_out.{args.output_format} was saved...... ({n} slices)")
@@ -1544,7 +1795,7 @@ def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[st
                 continue
             err = e2
         log(f"[！！！Error] revising {fn.split('.')[0]}: {err}; writing the original basecalls")
-        write_originals(args, [fn], log, report)
+        write_originals(args, [fn], log, report, sink)
         failed.append(fn)
     return nb, failed
 
@@ -1624,6 +1875,10 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
         if d:
             os.makedirs(d, exist_ok=True)
     parent_report = ReportPart(report_part_path(args.report, "parent") if args.report else None)
+    if args.combined:                     # --combined: a part per process too, `merge_combined` ends the run
+        clear_combined_parts(args.combined)
+    parent_sink = CombinedPart(combined_part_path(args.combined, "parent"), args.output_format == "fastq") if args.combined else None
+    part0 = combined_part_path(args.combined, 0) if args.combined else None
     kept_failed, n_resumed = [], 0
     if args.resume:
         # A finished read is a non-empty <stem>_out.<fmt>: outputs only ever appear by rename of a complete temporary.
@@ -1655,7 +1910,8 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
                  + (", left as they are)" if args.resume_keep_failed else ", revised again)") if earlier_failed else ""))
     if reviser_factory is not None:       # in-process (tests / embedding): one engine, no sharding
         rv = reviser_factory(args, 0)
-        stats = [process_files(args, names, rv, print, report_part=report_part_path(args.report, 0) if args.report else None)]
+        stats = [process_files(args, names, rv, print, report_part=report_part_path(args.report, 0) if args.report else None,
+                               combined_part=part0)]
     else:
         # the command line needs no torch: without it a process starts ~1.5 s sooner.  (engine.py imports
         # torch first only so that a LATER torch import in the same process finds one HIP runtime.)
@@ -1683,7 +1939,8 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
             def make():                               # runs in the engine thread, beside the parser pool's start-up
                 made.append((worker_factory or _default_factory)(args, 0))
                 return made[-1]                       # called once per engine (process_files: NRV_CLI_ENGINES)
-            stats = [process_files(args, names, make, print, report_part=report_part_path(args.report, 0) if args.report else None)]
+            stats = [process_files(args, names, make, print, report_part=report_part_path(args.report, 0) if args.report else None,
+                                   combined_part=part0)]
             for rv in made:
                 rv.close()
         else:
@@ -1694,7 +1951,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
             res = run_workers(args, shards, worker_factory, part_shards=part_shards, parts_out=parts_got)
             stats = [s for _, s, _, _ in res if s is not None]
             if split_fns:
-                nb_split, failed_split = finish_split_reads(args, split_fns, parts_got, print, parent_report)
+                nb_split, failed_split = finish_split_reads(args, split_fns, parts_got, print, parent_report, parent_sink)
                 stats.append({"reads": len(split_fns), "bases": nb_split, "failed": failed_split, "host_s": 0.0, "engine_s": 0.0})
                 if failed_split:
                     rc = 3
@@ -1704,13 +1961,16 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
                           f"unfinished reads", file=sys.stderr)
                     # what the worker reported final stays (its failed reads keep their failed_reads entry);
                     # everything else - started or not, whatever lies on disk - is written unrevised
-                    lost = write_originals(args, [f for f in shards[r] if f not in final], print, parent_report)
+                    lost = write_originals(args, [f for f in shards[r] if f not in final], print, parent_report, parent_sink)
                     lost += [f for f, ok in final.items() if not ok]
                     stats.append({"reads": len(shards[r]), "bases": 0, "failed": lost, "host_s": 0.0, "engine_s": 0.0})
                     rc = 3
     parent_report.close()
     if args.report:
         merge_report(args.report, all_names)
+    if args.combined:
+        parent_sink.close()
+        merge_combined(args.combined, args.output_format == "fastq")
     failed = kept_failed + [f for s in stats for f in s["failed"]]
     with open(os.path.join(args.output_dir, args.failed_reads_filename), "w") as fp:
         fp.write("".join(f + "\n" for f in failed))

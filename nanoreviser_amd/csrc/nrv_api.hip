@@ -522,8 +522,8 @@ struct nrv_handle {
   unsigned* d_sat_st[2] = {nullptr, nullptr};
   hipStream_t copy_stream = nullptr;      // host -> device
   hipStream_t d2h_stream = nullptr;       // device -> host (its own stream: an upload never queues behind a download)
-  hipStream_t edit_stream = nullptr;      // nrv_revise_reads_raw_edits_begin only, created with the first such call: the second download
-                                          // of nrv_reads_raw_end (d2h_stream may already wait for the OTHER slot's kernels)
+  hipStream_t edit_stream = nullptr;      // nrv_revise_reads_raw_edits_begin / _records_begin only, created with the first such call: the
+                                          // second download of nrv_reads_raw_end (d2h_stream may already wait for the OTHER slot's kernels)
   hipEvent_t ev_in[kIn] = {0, 0, 0}, ev_done[2] = {0, 0}, ev_out[2] = {0, 0};
   // page-locked host staging: outputs always land here first (46 B per window); inputs only when the
   // caller's arrays could not be registered in place (bounce copies)
@@ -567,6 +567,14 @@ struct nrv_handle {
     bool edits = false;
     nrv_edit* edits_out = nullptr;
     int64_t* eoff_out = nullptr;
+    // nrv_revise_reads_raw_records_begin (nrv_pack.h): the names [.. | name_off i64 x (n_reads + 1) | names u8] behind bases in
+    // d_in; rec_off i64 x (n_reads + 1) behind edit_off, the last part that comes back with the block (m_dl grows by it); the blob
+    // of blob_cap bytes behind the merge / edits scratch, its used prefix fetched by nrv_reads_raw_end like the edit records.  A
+    // call that hands back neither seq nor qual leaves them on the device: [off] and [report | edit_off | rec_off] come back
+    size_t off_noff = 0, off_names = 0, m_roff = 0, m_blob = 0, m_bytes = 0, blob_cap = 0;
+    bool records = false;
+    uint8_t* blob_out = nullptr;
+    int64_t* roff_out = nullptr;
     uint8_t *seq = nullptr, *qual = nullptr;
     int64_t* off = nullptr;
     int64_t N = 0, n = 0;
@@ -1969,11 +1977,61 @@ static EditsArgs edits_args(const MergeArgs& m, const float* p1, const float* p2
   a.etile = (unsigned long long*)etile; a.edit_off = (long long*)edit_off; a.edits = (EditRec*)edits;
   return a;
 }
-// layout of a merged block for N events, n windows, n_reads reads: [off | seq | qual | report | edit_off] (what comes back; the
-// report and edit_off only where asked for) + [rec | tile] (scratch) + [edits | etile] (the edit records, fetched by their used
-// prefix, and their scratch; only where asked for)
-struct MergeLayout { size_t seq, qual, rep, eoff, rec, tile, edits, etile, dl, bytes; };
-static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, bool report = false, bool edits = false) {
+// The record kernels (nrv_pack.h) behind merge_enqueue (and report_enqueue / edits_enqueue) on the same stream: they read seq /
+// qual / off as the merge left them.  Plain stores, each byte by one thread: a second pass accumulates nothing.
+static int pack_enqueue(nrv_handle* h, const PackArgs& a) {
+  if (a.n_reads <= 0) {
+    HIPCHK(h, hipMemsetAsync(a.rec_off, 0, 8, h->stream));
+    return NRV_OK;
+  }
+  hipLaunchKernelGGL(pack_offsets_kernel, dim3(1), dim3(256), 0, h->stream, a);
+  const unsigned long long words = (a.cap + 3) / 4;
+  if (words > 0) hipLaunchKernelGGL(pack_copy_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return NRV_OK;
+}
+// bytes the records of a call can take: hoststage.pack_records on N + max(N - T, 0) characters at the most
+static size_t blob_capacity(int64_t N, int64_t n, int n_reads, int64_t name_bytes, bool fastq) {
+  const size_t q = fastq ? 2 : 1;
+  return (size_t)name_bytes + q * (size_t)(N + n) + 3 * q * (size_t)n_reads;
+}
+// names / name_off of a records call: offsets from 0, ascending
+static bool names_ok(const uint8_t* names, const int64_t* name_off, int n_reads) {
+  if (!name_off || name_off[0] != 0) return false;
+  for (int r = 0; r < n_reads; ++r) if (name_off[r + 1] < name_off[r]) return false;
+  return names != nullptr || name_off[n_reads] == 0;
+}
+// hoststage.pack_records on the host, for the calls that have no window (N <= T): qual == nullptr with fastq: every quality is '#'
+static void records_host(const uint8_t* seq, const uint8_t* qual, const int64_t* off, int n_reads, const uint8_t* names,
+                         const int64_t* name_off, bool fastq, uint8_t* blob, int64_t* rec_off) {
+  int64_t p = 0;
+  for (int r = 0; r < n_reads; ++r) {
+    const int64_t nl = name_off[r + 1] - name_off[r], L = off[r + 1] - off[r];
+    rec_off[r] = p;
+    blob[p++] = fastq ? '@' : '>';
+    if (nl > 0) memcpy(blob + p, names + name_off[r], (size_t)nl);
+    p += nl;
+    blob[p++] = '\n';
+    if (L > 0) memcpy(blob + p, seq + off[r], (size_t)L);
+    p += L;
+    blob[p++] = '\n';
+    if (fastq) {
+      blob[p++] = '+';
+      blob[p++] = '\n';
+      if (L > 0) { if (qual) memcpy(blob + p, qual + off[r], (size_t)L); else memset(blob + p, '#', (size_t)L); }
+      p += L;
+      blob[p++] = '\n';
+    }
+  }
+  rec_off[n_reads] = p;
+}
+// layout of a merged block for N events, n windows, n_reads reads: [off | seq | qual | report | edit_off | rec_off] (what comes
+// back; the report, edit_off and rec_off only where asked for) + [rec | tile] (scratch) + [edits | etile] (the edit records,
+// fetched by their used prefix, and their scratch; only where asked for) + [blob] (the FASTA / FASTQ records, fetched by their
+// used prefix; only where asked for)
+struct MergeLayout { size_t seq, qual, rep, eoff, roff, rec, tile, edits, etile, blob, dl, bytes; };
+static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, bool report = false, bool edits = false, bool records = false,
+                                size_t blob_cap = 0) {
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   MergeLayout m;
   const size_t cap = (size_t)(N + n), tiles = (size_t)((N + kMergeTile - 1) / kMergeTile);
@@ -1981,17 +2039,19 @@ static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, bool report =
   m.qual = m.seq + up(cap);
   m.rep = m.qual + up(cap);
   m.eoff = m.rep + (report ? up((size_t)n_reads * kReportCols * 8) : 0);
-  m.dl = m.eoff + (edits ? up(((size_t)n_reads + 1) * 8) : 0);
+  m.roff = m.eoff + (edits ? up(((size_t)n_reads + 1) * 8) : 0);
+  m.dl = m.roff + (records ? up(((size_t)n_reads + 1) * 8) : 0);
   m.rec = m.dl;
   m.tile = m.rec + up((size_t)N * 4);
   m.edits = m.tile + up(tiles * 8);
   m.etile = m.edits + (edits ? up((size_t)n * sizeof(nrv_edit)) : 0);
-  m.bytes = m.etile + (edits ? up(tiles * 8) : 0);
+  m.blob = m.etile + (edits ? up(tiles * 8) : 0);
+  m.bytes = m.blob + (records ? up(blob_cap) : 0);
   return m;
 }
 // No window at all (N <= T): the reads come back as they are, on the host
 static void merge_nothing(const uint8_t* bases, const nrv_read_desc* reads, int n_reads, int64_t N, uint8_t* seq, uint8_t* qual, int64_t* off) {
-  if (N > 0) memcpy(seq, bases, (size_t)N);
+  if (seq && N > 0) memcpy(seq, bases, (size_t)N);
   if (qual && N > 0) memset(qual, '#', (size_t)N);
   for (int r = 0; r < n_reads; ++r) off[r] = reads[r].ev_off;
   off[n_reads] = N;
@@ -2016,6 +2076,10 @@ struct MergeReq {             // what nrv_revise_reads_raw_begin adds to a raw-r
   float tie_eps = 0.f;
   nrv_edit* edits = nullptr;  // nrv_revise_reads_raw_edits_begin: [max(N - T, 0)] and [n_reads + 1]
   int64_t* edit_off = nullptr;
+  const uint8_t* names = nullptr;     // nrv_revise_reads_raw_records_begin: the names, and where the records go
+  const int64_t* name_off = nullptr;
+  uint8_t* blob = nullptr;
+  int64_t* rec_off = nullptr;
 };
 static MergeArgs slot_merge_args(const nrv_handle* h, const nrv_handle::RawSlot& sl) {
   char* const d = sl.d_out + 64;
@@ -2041,6 +2105,25 @@ static EditsArgs slot_edits_args(const nrv_handle* h, const nrv_handle::RawSlot&
   return edits_args(slot_merge_args(h, sl), (const float*)d, (const float*)(d + sl.rows * 24), sl.want_q,
                     sl.d_mrg + sl.m_etile, sl.d_mrg + sl.m_eoff, sl.d_mrg + sl.m_edits);
 }
+static PackArgs slot_pack_args(const nrv_handle::RawSlot& sl) {
+  PackArgs a;
+  a.n_reads = sl.n_reads; a.fastq = sl.want_q ? 1 : 0;
+  a.off = (const long long*)sl.d_mrg;
+  a.name_off = (const long long*)(sl.d_in + sl.off_noff); a.names = (const unsigned char*)(sl.d_in + sl.off_names);
+  a.seq = (const unsigned char*)(sl.d_mrg + sl.m_seq); a.qual = (const unsigned char*)(sl.d_mrg + sl.m_qual);
+  a.rec_off = (long long*)(sl.d_mrg + sl.m_roff); a.blob = (unsigned char*)(sl.d_mrg + sl.m_blob);
+  a.cap = sl.blob_cap;
+  return a;
+}
+// what comes back of a merged block, on stream s: all of [0, m_dl) - or, for a records call that hands back neither seq nor qual,
+// the parts in front of and behind them
+static int merged_download(nrv_handle* h, nrv_handle::RawSlot& sl, hipStream_t s) {
+  const bool skip = sl.records && !sl.seq && !sl.qual;
+  const size_t head = skip ? sl.m_seq : sl.m_dl;
+  HIPCHK(h, hipMemcpyAsync(sl.pin_mrg, sl.d_mrg, head, hipMemcpyDeviceToHost, s));
+  if (skip) HIPCHK(h, hipMemcpyAsync(sl.pin_mrg + sl.m_rep, sl.d_mrg + sl.m_rep, sl.m_dl - sl.m_rep, hipMemcpyDeviceToHost, s));
+  return NRV_OK;
+}
 
 // nrv_reads_raw_begin (last_dur == nullptr: today's call, to the byte), nrv_reads_raw_stats_begin and (mr != nullptr)
 // nrv_revise_reads_raw_begin
@@ -2052,11 +2135,20 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
   if (rc) return rc;
   if (!ticket) { h->err = "nrv_reads_raw_begin: null ticket"; return NRV_E_INVALID; }
   if ((rc = raw_check(h, raw, n_raw, starts, feat_ev, N, reads, n_reads))) return rc;
-  if (mr && (!mr->off || (N > 0 && (!mr->bases || !mr->seq)) || N >= ((int64_t)1 << 31))) {
+  if (mr && (!mr->off || (N > 0 && (!mr->bases || (!mr->seq && !mr->rec_off))) || N >= ((int64_t)1 << 31))) {
     h->err = "nrv_revise_reads_raw_begin: null bases / seq / off (or 2^31 events and more)";
     return NRV_E_INVALID;
   }
   if (mr && mr->edit_off && N > h->T && !mr->edits) { h->err = "nrv_revise_reads_raw_edits_begin: null edits"; return NRV_E_INVALID; }
+  const bool records = mr != nullptr && mr->rec_off != nullptr;
+  const bool rec_fastq = records && mr->q_thr != nullptr;       // FASTQ or FASTA: by q_thr, whether qual is handed back or not
+  size_t blob_cap = 0;
+  if (records) {
+    if (!names_ok(mr->names, mr->name_off, n_reads)) { h->err = "nrv_revise_reads_raw_records_begin: null names / name_off, or offsets that do not ascend from 0"; return NRV_E_INVALID; }
+    blob_cap = blob_capacity(N, N - h->T > 0 ? N - h->T : 0, n_reads, mr->name_off[n_reads], rec_fastq);
+    if (blob_cap > 0 && !mr->blob) { h->err = "nrv_revise_reads_raw_records_begin: null blob"; return NRV_E_INVALID; }
+    if (blob_cap >= ((size_t)1 << 32)) { h->err = "nrv_revise_reads_raw_records_begin: records of 4 GiB and more in one call"; return NRV_E_INVALID; }
+  }
   const bool with_stats = last_dur != nullptr || on_device != nullptr;
   const int64_t stat_len = with_stats ? stats_check(h, reads, n_reads, last_dur, on_device) : 0;
   if (stat_len < 0) return NRV_E_INVALID;
@@ -2071,10 +2163,12 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
   sl.merge = mr != nullptr;
   sl.report = mr != nullptr && mr->report != nullptr;
   sl.edits = mr != nullptr && mr->edit_off != nullptr;
+  sl.records = records;
   if (sl.n == 0) {                                              // nothing to compute: _end returns at once
     if (mr) merge_nothing(mr->bases, reads, n_reads, N, mr->seq, mr->q_thr ? mr->qual : nullptr, mr->off);
-    if (sl.report) report_nothing(reads, n_reads, mr->q_thr != nullptr && mr->qual != nullptr, mr->report);
+    if (sl.report) report_nothing(reads, n_reads, mr->q_thr != nullptr && (mr->qual != nullptr || records), mr->report);
     if (sl.edits) memset(mr->edit_off, 0, ((size_t)n_reads + 1) * 8);   // no window, no record
+    if (records) records_host(mr->bases, nullptr, mr->off, n_reads, mr->names, mr->name_off, rec_fastq, mr->blob, mr->rec_off);
     sl.busy = true;
     return NRV_OK;
   }
@@ -2085,7 +2179,9 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
   sl.off_feat = sl.off_reads + up((size_t)n_reads * sizeof(SegRead));
   sl.off_aux = sl.off_feat + up((size_t)N * kFeat * 4);
   sl.off_bases = sl.off_aux + (with_stats ? up((size_t)n_reads * sizeof(StatAux)) : 0);
-  const size_t in_bytes = sl.off_bases + (mr ? up((size_t)N) : 0);
+  sl.off_noff = sl.off_bases + (mr ? up((size_t)N) : 0);
+  sl.off_names = sl.off_noff + (records ? up(((size_t)n_reads + 1) * 8) : 0);
+  const size_t in_bytes = sl.off_names + (records ? up((size_t)mr->name_off[n_reads]) : 0);
   sl.rows = ((size_t)sl.n + kRowPad - 1) / kRowPad * kRowPad;
   const size_t out_bytes = 64 + sl.rows * kOutBytes;
   if (!sl.ev_in) {
@@ -2113,12 +2209,14 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
     sl.sat_seen = 0;
   }
   if (mr) {
-    const MergeLayout m = merge_layout(N, sl.n, n_reads, sl.report, sl.edits);
+    const MergeLayout m = merge_layout(N, sl.n, n_reads, sl.report, sl.edits, records, blob_cap);
+    sl.m_roff = m.roff; sl.m_blob = m.blob; sl.m_bytes = m.bytes; sl.blob_cap = blob_cap;
+    sl.blob_out = mr->blob; sl.roff_out = mr->rec_off;
     sl.m_seq = m.seq; sl.m_qual = m.qual; sl.m_rec = m.rec; sl.m_tile = m.tile; sl.m_dl = m.dl;
     sl.m_rep = m.rep; sl.rep_out = mr->report; sl.tie_eps = mr->tie_eps;
     sl.m_eoff = m.eoff; sl.m_edits = m.edits; sl.m_etile = m.etile; sl.edits_out = mr->edits; sl.eoff_out = mr->edit_off;
-    if (sl.edits && !h->edit_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->edit_stream, hipStreamNonBlocking));
-    sl.want_q = mr->q_thr != nullptr && mr->qual != nullptr;
+    if ((sl.edits || records) && !h->edit_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->edit_stream, hipStreamNonBlocking));
+    sl.want_q = mr->q_thr != nullptr && (mr->qual != nullptr || records);
     if (sl.want_q) memcpy(sl.thr, mr->q_thr, sizeof sl.thr);
     sl.seq = mr->seq; sl.qual = mr->qual; sl.off = mr->off;
     if (m.bytes > sl.cap_mrg) {
@@ -2147,11 +2245,16 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
     if (mr) {
       for (size_t i = 0; i + 4 <= sl.m_dl; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
       if (sl.edits) for (size_t i = sl.m_edits; i + 4 <= sl.m_etile; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
+      if (records) for (size_t i = sl.m_blob; i + 4 <= sl.m_bytes; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
       if ((rc = poison_fill(h, sl.d_mrg, sl.cap_mrg, h->stream))) return rc;
     }
   }
   memcpy(sl.pin_in, raw, (size_t)n_raw * 2);
   if (mr) memcpy(sl.pin_in + sl.off_bases, mr->bases, (size_t)N);
+  if (records) {
+    memcpy(sl.pin_in + sl.off_noff, mr->name_off, ((size_t)n_reads + 1) * 8);
+    if (mr->name_off[n_reads] > 0) memcpy(sl.pin_in + sl.off_names, mr->names, (size_t)mr->name_off[n_reads]);
+  }
   memcpy(sl.pin_in + sl.off_starts, starts, (size_t)N * 4);
   memcpy(sl.pin_in + sl.off_reads, reads, (size_t)n_reads * sizeof(SegRead));
   memcpy(sl.pin_in + sl.off_feat, feat_ev, (size_t)N * kFeat * 4);
@@ -2171,7 +2274,8 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
   // the merge reads the slot's output block: behind the call's last launch group, ahead of ev_done
   if (rc || (rc = raw_enqueue(h, sl)) || (mr && (rc = merge_enqueue(h, slot_merge_args(h, sl)))) ||
       (sl.report && (rc = report_enqueue(h, slot_report_args(h, sl)))) ||
-      (sl.edits && (rc = edits_enqueue(h, slot_edits_args(h, sl))))) {
+      (sl.edits && (rc = edits_enqueue(h, slot_edits_args(h, sl)))) ||
+      (records && (rc = pack_enqueue(h, slot_pack_args(sl))))) {
     (void)hipStreamSynchronize(h->stream);                      // part of the call may be enqueued: nothing of it may outlive the slot
     return rc;
   }
@@ -2179,7 +2283,7 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
   HIPCHK(h, hipStreamWaitEvent(h->d2h_stream, sl.ev_done, 0));
   if (mr) {                                                     // the counter and the merged block; p1 / p2 / a1 / a2 stay on the device
     HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64, hipMemcpyDeviceToHost, h->d2h_stream));
-    HIPCHK(h, hipMemcpyAsync(sl.pin_mrg, sl.d_mrg, sl.m_dl, hipMemcpyDeviceToHost, h->d2h_stream));
+    if ((rc = merged_download(h, sl, h->d2h_stream))) return rc;
   } else {
     HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, out_bytes, hipMemcpyDeviceToHost, h->d2h_stream));
   }
@@ -2279,6 +2383,34 @@ int nrv_revise_reads_raw_edits(nrv_handle* h, const int16_t* raw, int64_t n_raw,
   return rc ? rc : nrv_reads_raw_end(h, t);
 }
 
+int nrv_revise_reads_raw_records_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                       const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                       const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                       uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                       nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                       uint8_t* blob, int64_t* rec_off, int* ticket) {
+  if (h && ((last_dur == nullptr) != (on_device == nullptr))) { h->err = "nrv_revise_reads_raw_records_begin: last_dur and on_device go together"; return NRV_E_INVALID; }
+  if (h && !rec_off) { h->err = "nrv_revise_reads_raw_records_begin: null rec_off"; return NRV_E_INVALID; }
+  if (h && edits && !edit_off) { h->err = "nrv_revise_reads_raw_records_begin: edits without edit_off"; return NRV_E_INVALID; }
+  MergeReq mr{bases, q_thr, seq, qual, off};
+  mr.report = report; mr.tie_eps = tie_eps;                    // report == NULL: none is counted
+  mr.edits = edits; mr.edit_off = edit_off;                    // edit_off == NULL: no edit list
+  mr.names = names; mr.name_off = name_off; mr.blob = blob; mr.rec_off = rec_off;
+  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, nullptr, nullptr, nullptr, nullptr, ticket, &mr);
+}
+
+int nrv_revise_reads_raw_records(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                 const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                 const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                 uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                 nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                 uint8_t* blob, int64_t* rec_off) {
+  int t = -1;
+  const int rc = nrv_revise_reads_raw_records_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                                    seq, qual, off, tie_eps, report, edits, edit_off, names, name_off, blob, rec_off, &t);
+  return rc ? rc : nrv_reads_raw_end(h, t);
+}
+
 int nrv_reads_raw_end(nrv_handle* h, int ticket) {
   int rc = check_handle(h);
   if (rc) return rc;
@@ -2302,8 +2434,10 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
       if (sl.report && (rc = report_enqueue(h, slot_report_args(h, sl)))) return rc;
       // ... and the edit list: plain stores into what is read back, nothing accumulates
       if (sl.edits && (rc = edits_enqueue(h, slot_edits_args(h, sl)))) return rc;
+      // ... and the records, from the seq / qual / off of the second merge; rec_off is read again below
+      if (sl.records && (rc = pack_enqueue(h, slot_pack_args(sl)))) return rc;
       HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipMemcpyAsync(sl.pin_mrg, sl.d_mrg, sl.m_dl, hipMemcpyDeviceToHost, h->stream));
+      if ((rc = merged_download(h, sl, h->stream))) return rc;
     } else {
       HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64 + sl.rows * kOutBytes, hipMemcpyDeviceToHost, h->stream));
     }
@@ -2316,8 +2450,8 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
     const int64_t total = off[sl.n_reads];
     if (total < 0 || total > sl.N + sl.n) { h->err = "nrv_reads_raw_end: merged block out of range"; return NRV_E_HIP; }
     memcpy(sl.off, off, ((size_t)sl.n_reads + 1) * 8);
-    memcpy(sl.seq, sl.pin_mrg + sl.m_seq, (size_t)total);
-    if (sl.want_q) memcpy(sl.qual, sl.pin_mrg + sl.m_qual, (size_t)total);
+    if (sl.seq) memcpy(sl.seq, sl.pin_mrg + sl.m_seq, (size_t)total);
+    if (sl.want_q && sl.qual) memcpy(sl.qual, sl.pin_mrg + sl.m_qual, (size_t)total);
     if (sl.report) memcpy(sl.rep_out, sl.pin_mrg + sl.m_rep, (size_t)sl.n_reads * kReportCols * 8);
     if (sl.edits) {
       // the used prefix of the records alone: a copy of its own size on a stream of its own - the records are complete (ev_done
@@ -2331,6 +2465,18 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
         HIPCHK(h, hipMemcpyAsync(sl.pin_mrg + sl.m_edits, sl.d_mrg + sl.m_edits, (size_t)n_ed * sizeof(nrv_edit), hipMemcpyDeviceToHost, h->edit_stream));
         HIPCHK(h, hipStreamSynchronize(h->edit_stream));
         memcpy(sl.edits_out, sl.pin_mrg + sl.m_edits, (size_t)n_ed * sizeof(nrv_edit));
+      }
+    }
+    if (sl.records) {
+      // the used prefix of the blob, as the edit records above: a copy of its own size on the stream that queues behind nothing
+      const int64_t* roff = (const int64_t*)(sl.pin_mrg + sl.m_roff);
+      const int64_t n_b = roff[sl.n_reads];
+      if (n_b < 0 || (uint64_t)n_b > sl.blob_cap) { h->err = "nrv_reads_raw_end: records out of range"; return NRV_E_HIP; }
+      memcpy(sl.roff_out, roff, ((size_t)sl.n_reads + 1) * 8);
+      if (n_b > 0) {
+        HIPCHK(h, hipMemcpyAsync(sl.pin_mrg + sl.m_blob, sl.d_mrg + sl.m_blob, (size_t)n_b, hipMemcpyDeviceToHost, h->edit_stream));
+        HIPCHK(h, hipStreamSynchronize(h->edit_stream));
+        memcpy(sl.blob_out, sl.pin_mrg + sl.m_blob, (size_t)n_b);
       }
     }
     return NRV_OK;
@@ -2532,6 +2678,53 @@ int nrv_merge_calls_edits(nrv_handle* h, const uint8_t* bases, const int64_t* ev
                           float tie_eps, uint64_t* report, nrv_edit* edits, int64_t* edit_off) {
   if (h && !edit_off) { h->err = "nrv_merge_calls_edits: null edit_off"; return NRV_E_INVALID; }
   return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, seq, qual, off, tie_eps, report, edits, edit_off);
+}
+
+int nrv_pack_records(nrv_handle* h, const uint8_t* seq, const uint8_t* qual, const int64_t* off, int n_reads,
+                     const uint8_t* names, const int64_t* name_off, uint8_t* blob, int64_t* rec_off) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (n_reads < 0 || !off || !rec_off || off[0] != 0) { h->err = "nrv_pack_records: bad arguments"; return NRV_E_INVALID; }
+  for (int r = 0; r < n_reads; ++r) if (off[r + 1] < off[r]) { h->err = "nrv_pack_records: off does not ascend"; return NRV_E_INVALID; }
+  if (!names_ok(names, name_off, n_reads)) { h->err = "nrv_pack_records: null names / name_off, or offsets that do not ascend from 0"; return NRV_E_INVALID; }
+  const int64_t total_in = off[n_reads], name_bytes = name_off[n_reads];
+  const bool fastq = qual != nullptr;
+  const size_t q = fastq ? 2 : 1, cap = (size_t)name_bytes + q * (size_t)total_in + 3 * q * (size_t)n_reads;
+  if ((total_in > 0 && !seq) || (cap > 0 && !blob)) { h->err = "nrv_pack_records: null seq / blob"; return NRV_E_INVALID; }
+  if (cap >= ((size_t)1 << 32)) { h->err = "nrv_pack_records: records of 4 GiB and more in one call"; return NRV_E_INVALID; }
+  if (n_reads == 0) { rec_off[0] = 0; return NRV_OK; }
+  // one block of its own: [off | name_off | names | seq | qual | rec_off | blob]
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t nb = ((size_t)n_reads + 1) * 8;
+  const size_t o_noff = up(nb), o_names = o_noff + up(nb), o_seq = o_names + up((size_t)name_bytes), o_qual = o_seq + up((size_t)total_in);
+  const size_t o_roff = o_qual + (fastq ? up((size_t)total_in) : 0), o_blob = o_roff + up(nb), bytes = o_blob + up(cap);
+  char* d = nullptr;
+  HIPCHK(h, hipMalloc((void**)&d, bytes));
+  auto run = [&]() -> int {
+    int rc2 = poison_fill(h, d, bytes, h->stream);
+    if (rc2) return rc2;
+    HIPCHK(h, hipMemcpyAsync(d, off, nb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d + o_noff, name_off, nb, hipMemcpyHostToDevice, h->stream));
+    if (name_bytes > 0) HIPCHK(h, hipMemcpyAsync(d + o_names, names, (size_t)name_bytes, hipMemcpyHostToDevice, h->stream));
+    if (total_in > 0) HIPCHK(h, hipMemcpyAsync(d + o_seq, seq, (size_t)total_in, hipMemcpyHostToDevice, h->stream));
+    if (fastq && total_in > 0) HIPCHK(h, hipMemcpyAsync(d + o_qual, qual, (size_t)total_in, hipMemcpyHostToDevice, h->stream));
+    PackArgs a;
+    a.n_reads = n_reads; a.fastq = fastq ? 1 : 0;
+    a.off = (const long long*)d; a.name_off = (const long long*)(d + o_noff); a.names = (const unsigned char*)(d + o_names);
+    a.seq = (const unsigned char*)(d + o_seq); a.qual = (const unsigned char*)(d + o_qual);
+    a.rec_off = (long long*)(d + o_roff); a.blob = (unsigned char*)(d + o_blob); a.cap = cap;
+    if ((rc2 = pack_enqueue(h, a))) return rc2;
+    HIPCHK(h, hipMemcpyAsync(rec_off, d + o_roff, nb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const int64_t n_b = rec_off[n_reads];                       // the used prefix of the blob, once the total is known
+    if (n_b < 0 || (uint64_t)n_b > cap) { h->err = "nrv_pack_records: records out of range"; return NRV_E_HIP; }
+    if (n_b > 0) HIPCHK(h, hipMemcpy(blob, d + o_blob, (size_t)n_b, hipMemcpyDeviceToHost));
+    return NRV_OK;
+  };
+  rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  (void)hipFree(d);
+  return rc;
 }
 
 int nrv_saturated(nrv_handle* h, int64_t* pending, int64_t* reruns) {

@@ -37,6 +37,7 @@ SYMBOLS = [
     "nrv_revise_reads_raw_begin", "nrv_revise_reads_raw", "nrv_merge_calls",
     "nrv_revise_reads_raw_report_begin", "nrv_revise_reads_raw_report", "nrv_merge_calls_report",
     "nrv_revise_reads_raw_edits_begin", "nrv_revise_reads_raw_edits", "nrv_merge_calls_edits",
+    "nrv_revise_reads_raw_records_begin", "nrv_revise_reads_raw_records", "nrv_pack_records",
 ]
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 
@@ -82,16 +83,19 @@ _CALLS = ([_FP, _FP, _I8P, _I8P], lambda p: p[6])                               
 _STATS = ([_I32P, _U8P], lambda p: p[7:9])                                               # last_dur, on_device
 _MERGE = ([_U8P, _FP, _U8P, _U8P, _I64P], lambda p: (p[9], p[10]) + tuple(p[11]))        # bases, q_thr, seq, qual, off
 _REPORT = ([C.c_float, _U64P], lambda p: p[12:14])                                       # tie_eps, report
-_EDITS = ([C.c_void_p, _I64P], lambda p: (p[14].ctypes.data, p[15]))                     # edits (nrv_edit records), edit_off
+_EDITS = ([C.c_void_p, _I64P], lambda p: (None if p[14] is None else p[14].ctypes.data, p[15]))   # edits (nrv_edit records), edit_off
+_RECORDS = ([_U8P, _I64P, _U8P, _I64P], lambda p: p[16:20])                              # names, name_off, blob, rec_off
 # len(packed) -> (synchronous symbol, begin symbol, blocks, whether the call returns merged reads: (seq, qual, off[, report]
-# [, edits, edit_off]))
+# [, edits, edit_off][, blob, rec_off]))
 _RAW_FORMS = {
     7: ("nrv_predict_reads_raw", "nrv_reads_raw_begin", (_CALLS,), False),
     9: ("nrv_predict_reads_raw_stats", "nrv_reads_raw_stats_begin", (_STATS, _CALLS), False),
     12: ("nrv_revise_reads_raw", "nrv_revise_reads_raw_begin", (_STATS, _MERGE), True),
     14: ("nrv_revise_reads_raw_report", "nrv_revise_reads_raw_report_begin", (_STATS, _MERGE, _REPORT), True),
     16: ("nrv_revise_reads_raw_edits", "nrv_revise_reads_raw_edits_begin", (_STATS, _MERGE, _REPORT, _EDITS), True),
+    20: ("nrv_revise_reads_raw_records", "nrv_revise_reads_raw_records_begin", (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS), True),
 }
+_PACK_RECORDS_T = [C.c_void_p, _U8P, _U8P, _I64P, C.c_int, _U8P, _I64P, _U8P, _I64P]         # nrv_pack_records
 _READS_HEAD_T = _RAW_HEAD_T[:4] + [C.c_int64, C.POINTER(_ReadDesc), C.c_int]     # nrv_segment_reads, nrv_read_stats: no features
 _MERGE_CALLS_T = [C.c_void_p, _U8P, _I64P, C.c_int, _I8P, _I8P, _FP, _FP, C.c_int64] + _MERGE[0][1:]   # nrv_merge_calls
 
@@ -175,8 +179,9 @@ def load_library(path: Optional[str] = None):
     lib.nrv_device_count.argtypes = []
     have_report = hasattr(lib, "nrv_merge_calls_report")   # by presence: NRV_LIB may name an older build of the same ABI
     have_edits = hasattr(lib, "nrv_merge_calls_edits")
+    have_records = hasattr(lib, "nrv_pack_records")
     for sync, begin, blocks, _ in _RAW_FORMS.values():  # (every restype is ctypes' default, int: the nrv_* status)
-        if (have_edits or _EDITS not in blocks) and (have_report or _REPORT not in blocks):
+        if (have_records or _RECORDS not in blocks) and (have_edits or _EDITS not in blocks) and (have_report or _REPORT not in blocks):
             getattr(lib, sync).argtypes = _RAW_HEAD_T + [t for types, _ in blocks for t in types]
             getattr(lib, begin).argtypes = getattr(lib, sync).argtypes + [C.POINTER(C.c_int)]
     lib.nrv_merge_calls.argtypes = _MERGE_CALLS_T
@@ -184,6 +189,8 @@ def load_library(path: Optional[str] = None):
         lib.nrv_merge_calls_report.argtypes = _MERGE_CALLS_T + _REPORT[0]
     if have_edits:
         lib.nrv_merge_calls_edits.argtypes = _MERGE_CALLS_T + _REPORT[0] + _EDITS[0]
+    if have_records:
+        lib.nrv_pack_records.argtypes = _PACK_RECORDS_T
     lib.nrv_reads_raw_end.argtypes = [vp, C.c_int]
     lib.nrv_segment_reads.argtypes = _READS_HEAD_T + [fp]
     lib.nrv_read_stats.argtypes = _READS_HEAD_T + [_I32P, _DP, _DP, _DP, _DP, fp]
@@ -423,13 +430,48 @@ class Reviser:
         return tuple(packed) + (np.zeros(max(n, 1), EDIT_DTYPE), np.zeros(packed[4] + 1, np.int64))
 
     @staticmethod
+    def _names_block(names):
+        """R byte strings -> (names uint8[], name_off int64[R + 1]): the name arguments of the record calls."""
+        names = [bytes(n) for n in names]
+        lens = np.array([len(n) for n in names], np.int64).reshape(-1)
+        joined = np.frombuffer(b"".join(names), np.uint8)
+        return (joined.copy() if joined.size else np.zeros(1, np.uint8)), np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+
+    @classmethod
+    def with_device_records(cls, packed, names, hand_back=True):
+        """A `with_device_merge` (12 elements), `with_device_report` (14) or `with_device_edits` (16) tuple whose call also lays
+        the reads out as FASTA / FASTQ records (include/nanorev.h nrv_revise_reads_raw_records_begin; hoststage.pack_records is
+        the definition).  names: one byte string per read (hoststage.record_name).  `run_packed_raw` / `begin_packed_raw` +
+        `end_packed_raw` then return (seq, qual | None, off, report | None, edits[:total] | None, edit_off | None,
+        blob[:rec_off[-1]], rec_off) - read r owns blob[rec_off[r]:rec_off[r + 1]].  hand_back=False: seq and qual are left on
+        the device (both None in the result); off is still filled.  FASTQ or FASTA is what `with_device_merge` was given."""
+        if len(packed) not in (12, 14, 16):
+            raise ValueError("with_device_records extends a with_device_merge, a with_device_report or a with_device_edits tuple")
+        packed = tuple(packed)
+        if len(packed) == 12:
+            packed += (0.0, None)
+        if len(packed) == 14:
+            packed += (None, None)
+        nr, N = packed[4], packed[5]
+        if len(names) != nr:
+            raise ValueError("names must have one entry per read")
+        nm, name_off = cls._names_block(names)
+        q = 2 if packed[10] is not None else 1
+        cap = int(name_off[-1]) + q * (N + packed[6][2].shape[0]) + 3 * q * nr
+        if not hand_back:
+            packed = packed[:11] + ((None, None, packed[11][2]),) + packed[12:]
+        return packed + (nm, name_off, np.empty(max(cap, 1), np.uint8), np.zeros(nr + 1, np.int64))
+
+    @staticmethod
     def _trim_merged(out):
         seq, qual, off = out[:3]
         total = int(off[-1])
         more = tuple(out[3:])
-        if len(more) == 3:                            # (report | None, edits, edit_off): the used prefix of the records
-            more = (more[0], more[1][:int(more[2][-1])], more[2])
-        return (seq[:total], (qual[:total] if qual is not None else None), off) + more
+        if len(more) in (3, 5) and more[1] is not None:   # (report | None, edits, edit_off, ...): the used prefix of the records
+            more = (more[0], more[1][:int(more[2][-1])], more[2]) + more[3:]
+        if len(more) == 5:                            # (..., blob, rec_off): the used prefix of the blob
+            more = more[:3] + (more[3][:int(more[4][-1])], more[4])
+        return ((seq[:total] if seq is not None else None), (qual[:total] if qual is not None else None), off) + more
 
     def _raw_head(self, packed):
         """The leading C arguments every raw-read entry point shares: handle, raw, n_raw, starts, feat, N, descs, n_reads."""
@@ -440,20 +482,20 @@ class Reviser:
         """One call of the raw-read family for a packed tuple of any form (`_RAW_FORMS`): its synchronous entry point, or its
         *_begin with the ticket behind the same arguments.  Returns (ticket number or None, outputs, merged)."""
         if len(packed) not in _RAW_FORMS:
-            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14 or 16 elements, not {len(packed)}")
+            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14, 16 or 20 elements, not {len(packed)}")
         sync, beg, blocks, merged = _RAW_FORMS[len(packed)]
-        if not hasattr(self._lib, beg):               # the report pair and the edits pair are found by presence
+        if not hasattr(self._lib, beg):               # the report, edits and records pairs are found by presence
             raise NrvError(-1, f"this build of libnanorev_hip.so has no {beg}")
         args = self._raw_head(packed)
         for types, pick in blocks:
             args += _marshal(pick(packed), types)
         t = C.c_int(-1)
         self._check(getattr(self._lib, beg)(*args, C.byref(t)) if begin else getattr(self._lib, sync)(*args))
-        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) if merged else packed[6]), merged
+        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) + tuple(packed[18:20]) if merged else packed[6]), merged
 
     def run_packed_raw(self, packed):
         """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared (or `with_device_stats` /
-        `with_device_merge` / `with_device_report` / `with_device_edits` extended)."""
+        `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` extended)."""
         _, out, merged = self._raw_call(packed, False)
         return self._trim_merged(out) if merged else out
 
@@ -465,8 +507,9 @@ class Reviser:
 
     def end_packed_raw(self, ticket):
         """Second half: waits for the call `ticket` names and returns its (p1, p2, a1, a2) - or, for a `with_device_merge`
-        call, its (seq, qual, off), with the report behind them for a `with_device_report` call and (report | None, edits,
-        edit_off) for a `with_device_edits` call."""
+        call, its (seq, qual, off), with the report behind them for a `with_device_report` call, (report | None, edits,
+        edit_off) for a `with_device_edits` call and (report | None, edits | None, edit_off | None, blob, rec_off) - the blob
+        trimmed to rec_off[-1] - for a `with_device_records` call."""
         t, out = ticket[:2]
         self._check(self._lib.nrv_reads_raw_end(self._h, t))
         return self._trim_merged(out) if len(ticket) == 3 else out
@@ -568,6 +611,35 @@ class Reviser:
         edits, edit_off = np.zeros(max(n, 1), EDIT_DTYPE), np.zeros(ins[1].size + 1, np.int64)
         more = _marshal((REPORT_TIE_EPS if tie_eps is None else tie_eps, rep, edits.ctypes.data, edit_off), _REPORT[0] + _EDITS[0])
         return self._merge_call("nrv_merge_calls_edits", *ins, *more) + (rep, edits[:int(edit_off[-1])], edit_off)
+
+    def pack_records_device(self, names, seq, qual, off, blob=None):
+        """The device-side record layout alone (nrv_pack_records) on merged reads the host supplies: the arguments and the
+        result (blob, rec_off) of hoststage.pack_records, byte for byte.  blob: a uint8 array of at least the capacity to write
+        into (the result is a view of its used prefix; nothing behind it is written)."""
+        if not hasattr(self._lib, "nrv_pack_records"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_pack_records")
+        off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+        nr = off.size - 1
+        if len(names) != nr:
+            raise ValueError("names must have one entry per read")
+        s = np.ascontiguousarray(seq, dtype=np.uint8).reshape(-1)
+        ql = None if qual is None else np.ascontiguousarray(qual, dtype=np.uint8).reshape(-1)
+        if s.size < int(off[-1]) or (ql is not None and ql.size < int(off[-1])):
+            raise ValueError("seq / qual are shorter than off[-1]")
+        nm, name_off = self._names_block(names)
+        q = 2 if ql is not None else 1
+        cap = max(int(name_off[-1]) + q * int(off[-1]) + 3 * q * nr, 1)
+        if blob is None:
+            blob = np.empty(cap, np.uint8)
+        elif blob.dtype != np.uint8 or blob.ndim != 1 or blob.size < cap or not blob.flags.c_contiguous:
+            raise ValueError(f"blob must be a contiguous uint8 array of at least {cap} bytes")
+        rec_off = np.zeros(nr + 1, np.int64)
+        if s.size == 0:
+            s = np.zeros(1, np.uint8)
+        if ql is not None and ql.size == 0:
+            ql = np.zeros(1, np.uint8)
+        self._check(self._lib.nrv_pack_records(*_marshal((self._h, s, ql, off, nr, nm, name_off, blob, rec_off), _PACK_RECORDS_T)))
+        return blob[:int(rec_off[-1])], rec_off
 
     @staticmethod
     def _fingerprint(a):
