@@ -8,10 +8,12 @@ import numpy as np
 class EchoEngine:
     """Stand-in for engine.Reviser in host-logic tests: 'predicts' exactly the original base at
     every window centre (model1 label, model2 label-1), so revise_read must return the input."""
-    T = 11
+    T = 11                                                             # the shipped window length; `T=` sets another per engine
 
-    def __init__(self, fail_marker=None):
+    def __init__(self, fail_marker=None, T=None):
         self.fail_marker, self.calls = fail_marker, 0
+        if T is not None:
+            self.T = int(T)
 
     def predict_read(self, sig_ev, feat_ev):
         self.calls += 1
@@ -20,10 +22,10 @@ class EchoEngine:
         if self.fail_marker is not None and np.array_equal(feat_ev[0], self.fail_marker):
             raise RuntimeError("injected engine failure")
         assert sig_ev.dtype == np.float32 and sig_ev.shape[1] == 50 and feat_ev.shape[1] == 6
-        n = len(feat_ev) - self.T
+        n = max(len(feat_ev) - self.T, 0)
         col = np.rint(feat_ev[:, 0] * 300).astype(int)                 # 250/180/100/30 -> A/G/T/C
         lab = np.select([col == 250, col == 180, col == 100, col == 30], [5, 4, 3, 2])
-        a1 = lab[5:5 + n].astype(np.int8)
+        a1 = lab[(self.T - 1) // 2:(self.T - 1) // 2 + n].astype(np.int8)
         p1 = np.eye(6, dtype=np.float32)[a1] * 0.9 + 0.1 / 6
         p2 = np.eye(5, dtype=np.float32)[a1 - 1] * 0.9 + 0.1 / 5
         return p1, p2, a1, (a1 - 1).astype(np.int8)
@@ -58,7 +60,7 @@ class PackedEcho(EchoEngine):
         n = max(N - self.T, 0)
         col = np.rint(feat[:, 0] * 300).astype(int)
         lab = np.select([col == 250, col == 180, col == 100, col == 30], [5, 4, 3, 2])
-        a1[:] = lab[5:5 + n]
+        a1[:] = lab[(self.T - 1) // 2:(self.T - 1) // 2 + n]
         a2[:] = a1 - 1
         p1[:] = np.eye(6, dtype=np.float32)[a1] * 0.9 + 0.1 / 6
         p2[:] = np.eye(5, dtype=np.float32)[a2] * 0.9 + 0.1 / 5
@@ -71,8 +73,8 @@ class PipelinedEcho(PackedEcho):
     nothing else may run on the engine between a call's halves.  `fail_in_end`: the call whose first event matches
     fail_marker fails in its SECOND half (the first half only enqueues)."""
 
-    def __init__(self, fail_marker=None, fail_in_end=False):
-        super().__init__(None if fail_in_end else fail_marker)
+    def __init__(self, fail_marker=None, fail_in_end=False, T=None):
+        super().__init__(None if fail_in_end else fail_marker, T)
         self.end_marker = fail_marker if fail_in_end else None
         self.flight, self.max_in_flight, self.begun, self.violations = {}, 0, 0, []
 
@@ -118,7 +120,7 @@ class HashEngine(EchoEngine):
         self.calls += 1
         n = max(len(feat_ev) - self.T, 0)
         h = (np.ascontiguousarray(feat_ev[:, 1:4], np.float32).view(np.uint32).astype(np.uint64) *
-             np.array([2654435761, 40503, 2246822519], np.uint64)).sum(1)[5:5 + n]
+             np.array([2654435761, 40503, 2246822519], np.uint64)).sum(1)[(self.T - 1) // 2:(self.T - 1) // 2 + n]
         a1, a2 = ((h >> np.uint64(7)) % np.uint64(6)).astype(np.int8), ((h >> np.uint64(13)) % np.uint64(5)).astype(np.int8)
         p1 = np.eye(6, dtype=np.float32)[a1] * ((h % np.uint64(89)).astype(np.float32)[:, None] / 100 + 0.1)
         p2 = np.eye(5, dtype=np.float32)[a2] * ((h % np.uint64(83)).astype(np.float32)[:, None] / 100 + 0.1)

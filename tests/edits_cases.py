@@ -73,7 +73,7 @@ def _rows(rng, n):
     return p1, p2
 
 
-def density_case(what, ev_len=(0, 300, 0, 13, 256, 700, 0), seed=7):
+def density_case(what, ev_len=(0, 300, 0, 13, 256, 700, 0), seed=7, T=T):
     """`what`: "deletion" (a1 = 1, a2 = 0 everywhere), "insertion" (a1 = 0, a2 a base) or "none" (both models repeat the basecaller)."""
     rng = np.random.default_rng(seed)
     el = np.array(ev_len, np.int64)
@@ -93,7 +93,7 @@ def density_case(what, ev_len=(0, 300, 0, 13, 256, 700, 0), seed=7):
             "N": N, "n": n}
 
 
-def carry_case(deletions, seed=9):
+def carry_case(deletions, seed=9, T=T):
     """257 * 256 + 3 events in four reads; the second spans 256 * 256 + 100 events (more than 256 tiles)."""
     rng = np.random.default_rng(seed)
     el = np.array([90, 256 * 256 + 100, 0, 69], np.int64)

@@ -75,23 +75,24 @@ def parse_records(blob, fastq):
     return out
 
 
-def merged_of(c, fastq):
-    """The merged reads of a calls case (report_case / carry_case): (seq, qual | None, off), by the host definition of the merge."""
+def merged_of(c, fastq, T=T):
+    """The merged reads of a calls case (report_case / carry_case at window length T): (seq, qual | None, off), by the host
+    definition of the merge."""
     from nanoreviser_amd import hoststage as hs
     return hs.emit_calls(c["bases"], c["ev_len"], c["a1"], c["a2"], c["qc"] if fastq else None, T)
 
 
-def report_records_case(fastq):
-    """`report_case()` merged: a read boundary on a tile edge, empty reads first, in the middle and last."""
-    c = report_case()
-    seq, qual, off = merged_of(c, fastq)
+def report_records_case(fastq, T=T):
+    """`report_case(T)` merged: a read boundary on a tile edge, empty reads first, in the middle and last."""
+    c = report_case(T=T)
+    seq, qual, off = merged_of(c, fastq, T)
     return {"names": names_for(len(c["ev_len"])), "seq": seq, "qual": qual, "off": off, "calls": c}
 
 
-def carry_records_case(fastq):
-    """`carry_case()` merged: 257 * 256 + 3 events in four reads, one record spanning many workgroups of the copy."""
-    c = carry_case(False)
-    seq, qual, off = merged_of(c, fastq)
+def carry_records_case(fastq, T=T):
+    """`carry_case(T)` merged: 257 * 256 + 3 events in four reads, one record spanning many workgroups of the copy."""
+    c = carry_case(False, T=T)
+    seq, qual, off = merged_of(c, fastq, T)
     return {"names": names_for(len(c["ev_len"]), seed=6), "seq": seq, "qual": qual, "off": off, "calls": c}
 
 

@@ -1,22 +1,31 @@
 """Inputs and the reference loop shared by tests/test_revision_report_host.py and tests/test_gpu_device_report.py (no test here).
 
-`report_case()` is ONE call of ~2.8 k events, T = 11.  The order of the read lengths is chosen for the device kernel's tiles of
-256 events: the first non-empty read ends on a tile edge (256), tile 1 holds the reads of 10, 11, 12, 1 and 13 events and the
-head of the next, every later boundary falls mid-tile, the read of 3 * 256 + 5 events covers whole tiles, and reads without
-events stand first, in the middle and last.  The lengths are the mix {0, 1, 10, 11, 12, 13, 255, 256, 257, 600} plus that read.
+`report_case(T=11)` is ONE call of ~2.8 k events.  The order of the read lengths (`ev_len_for(T)`) is chosen for the device
+kernel's tiles of 256 events: the first non-empty read ends on a tile edge (256), tile 1 holds the reads of T - 1, T, T + 1, 1 and
+T + 2 events and the head of the next, every later boundary falls mid-tile, the read of 3 * 256 + 5 events covers whole tiles,
+and reads without events stand first, in the middle and last.  At the shipped T = 11 the lengths are the mix {0, 1, 10, 11, 12,
+13, 255, 256, 257, 600} plus that read (`EV_LEN`); tests/test_window_lengths_host.py pins those arrays by their sha256.
 `loop_report` is the per-read, per-window restatement of the rule text of include/nanorev.h in plain Python: it shares no code
 with hoststage (no emit_calls, no merge_calls)."""
 import numpy as np
 
 T = 11
 TIE_EPS = 4e-4
-EV_LEN = [0, 256, 0, 10, 11, 12, 1, 13, 255, 257, 600, 3 * 256 + 5, 0, 600, 0]
 LAB = "D-CTGA"
 
 
-def report_case(seed=2604):
+def ev_len_for(T):
+    """The read lengths of `report_case(T)`: reads of T - 1, T (no window), T + 1 (one) and T + 2 events share tile 1."""
+    return [max(x, 0) for x in (0, 256, 0, T - 1, T, T + 1, 1, T + 2, 255, 257, 600, 3 * 256 + 5, 0, 600, 0)]
+
+
+EV_LEN = ev_len_for(T)
+assert EV_LEN == [0, 256, 0, 10, 11, 12, 1, 13, 255, 257, 600, 3 * 256 + 5, 0, 600, 0]
+
+
+def report_case(seed=2604, T=T):
     rng = np.random.default_rng(seed)
-    el = np.array(EV_LEN, np.int64)
+    el = np.array(ev_len_for(T), np.int64)
     N = int(el.sum())
     n = N - T
     bases = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, N)].copy()
@@ -24,7 +33,7 @@ def report_case(seed=2604):
     lab_of = {ord("C"): 2, ord("T"): 3, ord("G"): 4, ord("A"): 5}
     a1 = rng.integers(0, 6, n).astype(np.int8)
     a2 = rng.integers(0, 5, n).astype(np.int8)
-    centre = np.array([lab_of[b] for b in bases[5:5 + n]], np.int8)
+    centre = np.array([lab_of[b] for b in bases[(T - 1) // 2:(T - 1) // 2 + n]], np.int8)
     same = rng.random(n) < 0.5
     a1[same] = centre[same]
     agree = same & (rng.random(n) < 0.7)

@@ -2,7 +2,8 @@
 nrv_revise_reads_raw_records_begin / nrv_revise_reads_raw_records and the command line's --combined.
 
 Everything is compared BYTE FOR BYTE - copies and integer offsets, nothing here has a tolerance.  hoststage.pack_records is the
-definition (tests/test_combined_records_host.py holds it to the rule text).  T = 11, the shipped E. coli weights:
+definition (tests/test_combined_records_host.py holds it to the rule text).  T = 11, the shipped E. coli weights (the records call
+at T = 1, 2, 12, 13, 32: tests/test_gpu_window_lengths.py; nrv_pack_records itself does not depend on T):
   1. nrv_pack_records on the merged reads of tests/report_cases.py, two passes on one handle, FASTQ and FASTA; the caller's blob
      is pre-filled with 0xA5 and untouched at and beyond the total;
   2. edge shapes: no read, only empty reads, names of 1 / 3 / 4 / 5 / 15 / 16 / 17 / 255 bytes and one with `|||` (the kernel

@@ -3,7 +3,7 @@ nrv_revise_reads_raw_edits_begin / nrv_revise_reads_raw_edits and the command li
 
 Everything is compared BIT FOR BIT - slots and positions are integers, conf is a copied f32 - the records as .tobytes().
 hoststage.revision_edits is the definition (tests/test_revision_edits_host.py holds it to the rule text).  T = 11, the shipped
-E. coli weights:
+E. coli weights (the kernels and the edits call at T = 1, 2, 12, 13, 32: tests/test_gpu_window_lengths.py):
   1. nrv_merge_calls_edits on tests/report_cases.py (a read boundary on a tile edge, five reads in one tile, a read over whole
      tiles, empty reads first / in the middle / last), two passes on one handle: FASTQ, rows without q_thr, bare; seq / qual /
      off / report are nrv_merge_calls_report's;

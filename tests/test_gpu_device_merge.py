@@ -1,7 +1,8 @@
 """Merge, Phred and packing of revised reads on the device (MI355X only, -m gpu): csrc/nrv_merge.h through nrv_merge_calls,
 nrv_revise_reads_raw_begin / nrv_revise_reads_raw and the command line's --device_merge.
 
-Everything is compared BYTE FOR BYTE - nothing here has a tolerance.  hoststage.emit_calls with cli.phred_chars is the definition:
+Everything is compared BYTE FOR BYTE - nothing here has a tolerance.  hoststage.emit_calls with cli.phred_chars is the definition.
+T = 11, the shipped weights (the same synthetic calls and the raw-read call at T = 1, 2, 12, 13, 32: tests/test_gpu_window_lengths.py):
   1. nrv_merge_calls on synthetic calls: all 6 x 5 class pairs x the 4 bases and an out-of-alphabet base, each at a read's first
      window, at its last window and either side of a tile boundary of the scan; confidences at every Phred threshold +- 1 ulp, the
      smaller one in p1 and in p2; reads of 0, 1, T, T + 1, T + 2, 4096 + T and 200 000 events; 1, 2 and 37 reads per call; empty

@@ -2,7 +2,8 @@
 nrv_revise_reads_raw_report_begin / nrv_revise_reads_raw_report and the command line's --report.
 
 Everything is compared BIT FOR BIT - the counts are integers, nothing here has a tolerance.  hoststage.revision_report is the
-definition (tests/test_revision_report_host.py holds it to the rule text).  T = 11, the shipped E. coli weights:
+definition (tests/test_revision_report_host.py holds it to the rule text).  T = 11, the shipped E. coli weights (the kernel and
+the report call at T = 1, 2, 12, 13, 32: tests/test_gpu_window_lengths.py):
   3. nrv_merge_calls_report on the inputs of tests/report_cases.py (one call of ~2.8 k events: a read boundary on a tile edge, others
      mid-tile, a tile with five reads, a read over whole tiles, empty reads first / in the middle / last; labels out of range; ties,
      margins one ulp either side of tie_eps, NaNs), with and without q_thr; seq / qual / off are nrv_merge_calls';
