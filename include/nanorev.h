@@ -306,6 +306,45 @@ int nrv_revise_reads_raw_records(nrv_handle* h, const int16_t* raw, int64_t n_ra
 int nrv_pack_records(nrv_handle* h, const uint8_t* seq, const uint8_t* qual, const int64_t* off, int n_reads,
                      const uint8_t* names, const int64_t* name_off, uint8_t* blob, int64_t* rec_off);
 
+/* The per-read QUALITY AND BASE PROFILE of the same revised reads (opt-in; nothing above changes): what a sequencing summary is
+ * computed from - mean and median quality over the error probabilities, Q10 / Q20 / Q30 counts, base composition -, counted on
+ * the device behind the merge (and the report / edit / record launches).  The arguments of nrv_revise_reads_raw_records_begin -
+ * `report`, `edits` / `edit_off` and `seq` / `qual` may be NULL as there, and `names` / `name_off` / `blob` / `rec_off` may ALL be
+ * NULL (no records; `seq` is then required as in nrv_revise_reads_raw_begin) - then
+ *   prof_thr  float [39]: the thresholds the profile's qualities are computed with; the layout of q_thr and independent of it
+ *             (q_thr alone still decides between FASTA and FASTQ);
+ *   profile   uint64 [n_reads][NRV_PROFILE_COLS], one row per read:
+ *     0 .. 41  output characters of the read whose quality q has clip(q - 33, 0, 41) == k;
+ *     42 .. 46 output characters equal to 'A', 'C', 'G', 'T' (exact upper-case ASCII), and everything else;
+ *     47       reserved, 0.
+ *   Columns 0 .. 41 and columns 42 .. 46 each add up to off[r + 1] - off[r].
+ * Both are required.  The profile is ALWAYS that of the FASTQ form of the call, whether a quality is written or not: a window's
+ * quality is 33 + 1 + #{k : prof_thr[k] <= min(p1[clip(a1)], p2[clip(a2)])}, compared in f32, as in nrv_revise_reads_raw_begin;
+ * an edge event has '#' (Phred 2).  hoststage.read_profile (on what hoststage.emit_calls returns for cli.phred_chars of the
+ * call's outputs) is the definition; every counter is an integer, so the bytes do not depend on the order of the workgroups.
+ * N <= T: nothing is enqueued; the block is filled on the host - column 2 is ev_len, the base counts are those of `bases`.
+ * Tickets, the two-calls-in-flight rule, the failure paths and the range-guard re-run (which zeroes the block and counts again
+ * behind the f32 kernels, as the report) are those of nrv_revise_reads_raw_begin; `profile` is filled by nrv_reads_raw_end,
+ * downloaded with the call's block, and must stay valid until then.  nrv_revise_reads_raw_profile IS _profile_begin + _end. */
+#define NRV_PROFILE_COLS 48
+int nrv_revise_reads_raw_profile_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                       const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                       const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                       uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                       nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                       uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile, int* ticket);
+int nrv_revise_reads_raw_profile(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                 const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                 const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                 uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                 nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                 uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile);
+/* nrv_merge_calls with the profile, by the kernel nrv_revise_reads_raw_profile_begin runs: p1 / p2 are required (NRV_E_INVALID
+ * without them), q_thr may be NULL - a FASTA merge whose profile is still filled.  The twin used by the parity tests. */
+int nrv_merge_calls_profile(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                            const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                            const float* prof_thr, uint64_t* profile);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

@@ -135,7 +135,17 @@ def get_args(argv: Optional[Sequence[str]] = None):
                         "forms them from the reads it holds: the same records.  Their order is not specified beyond the reads of one "
                         "device call staying together.  --report and --edits work unchanged next to it; --resume does not.  Off by "
                         "default; without it nothing changes and FILE is not created")
+    p.add_argument("--summary", dest="summary", default=None, metavar="FILE",
+                   help="write a per-read sequencing summary to FILE (also NRV_SUMMARY=FILE): a TSV with one header line, one line "
+                        "per input read sorted by file name - name, status (revised / unrevised), bases, mean and median quality "
+                        "(the mean is that of the error probabilities, as Guppy and NanoStat define it), bases of Q10 / Q20 / Q30 and "
+                        "more, GC content, the counts of A / C / G / T / other - then a line #total over the revised reads and a "
+                        "line #reads with the revised and unrevised reads and the N50 of the revised ones.  The qualities are those "
+                        "of the FASTQ form of the run, in FASTA runs too; a read written unrevised has its base counts and no "
+                        "quality.  With --device_merge the counts are made on the GPU behind the merge, everywhere else by the host "
+                        "stage from the calls it holds: the same file byte for byte.  Off by default; without it nothing changes")
     a = p.parse_args(argv)
+    a.summary = a.summary or (os.environ.get("NRV_SUMMARY", "").strip() or None)
     a.combined = a.combined or (os.environ.get("NRV_COMBINED", "").strip() or None)
     if a.combined and a.resume:
         print("[！！！Error] --resume cannot be used with --combined: a combined run cannot be resumed", file=sys.stderr)
@@ -757,22 +767,90 @@ def unrevised_row(n_written: int) -> np.ndarray:
     return row
 
 
-def written_length(path: str) -> int:
-    """Bases of the one record in an output file (its second line); 0 when there is none."""
+def _second_line(path: str) -> bytes:
     try:
         with open(path, "rb") as fp:
             fp.readline()
-            return len(fp.readline().rstrip(b"\r\n"))
+            return fp.readline().rstrip(b"\r\n")
     except OSError:
-        return 0
+        return b""
+
+
+def written_sequence(path: str, fastq: bool) -> bytes:
+    """The sequence of the one record in a per-read output file; empty when there is none.  It is the file's second line; in a
+    FASTQ file that line ends with the '+' `hoststage.fastq_record` puts there without a newline in front, which is not a base."""
+    line = _second_line(path)
+    return line[:-1] if fastq and line.endswith(b"+") else line
+
+
+def written_length(path: str) -> int:
+    """Length of the second line of an output file (--report's bases of a --resume skip); 0 when there is none."""
+    return len(_second_line(path))
+
+
+SUMMARY_HEADER = "name\tstatus\tbases\tmean_q\tmedian_q\tq10\tq20\tq30\tgc\tA\tC\tG\tT\tother"
+SUMMARY_COLS = 47                          # the columns of a profile row a part line carries: 48 less the reserved one
+
+
+def profile_rows(T, bases, ev_len, p1, p2, a1, a2):
+    """--summary on the host: `hoststage.read_profile` on calls the host holds.  The profile is that of the FASTQ form of the
+    calls whether the run writes a quality or not: `phred_chars`, then `emit_calls`, then `read_profile`.  uint64[len(ev_len)][48]."""
+    qc = phred_chars(p1, p2, a1, a2) if len(a1) else np.zeros(0, np.uint8)
+    return hs.read_profile(*hs.emit_calls(hostlib.bases_u8(bases), ev_len, a1, a2, qc, T))
+
+
+def unrevised_profile(seq) -> np.ndarray:
+    """The profile row of a read written unrevised: the base counts of the sequence that was written (str or bytes), no histogram."""
+    row = np.zeros(hs.PROFILE_COLS, np.uint64)
+    text = seq.encode("ascii", "replace") if isinstance(seq, str) else bytes(seq)
+    for i, c in enumerate(b"ACGT"):
+        row[42 + i] = text.count(bytes([c]))
+    row[46] = len(text) - int(row[42:46].sum())
+    return row
+
+
+def summary_fields(row) -> List[str]:
+    """The fields of a summary line behind name and status, from ONE integer profile row (or a sum of rows): bases, mean_q,
+    median_q, q10, q20, q30, gc, A, C, G, T, other.  Every route formats through this function, so equal rows give equal bytes."""
+    v = [int(x) for x in np.asarray(row).reshape(-1)[:SUMMARY_COLS]]
+    h, acgt = v[:42], v[42:47]
+    bases, L = sum(acgt), sum(h)
+    mean_q = format(-10 * math.log10(math.fsum(h[k] * 10.0 ** (-k / 10.0) for k in range(42)) / L), ".4f") if L else "0.0000"
+    median_q, cum = 0, 0
+    if L:
+        for k in range(42):
+            cum += h[k]
+            if 2 * cum >= L:
+                median_q = k
+                break
+    gc = format((acgt[1] + acgt[2]) / bases, ".4f") if bases else "0.0000"
+    return [str(bases), mean_q, str(median_q)] + [str(sum(h[n:])) for n in (10, 20, 30)] + [gc] + [str(x) for x in acgt]
+
+
+def n50(lengths) -> int:
+    """The largest L such that the reads of at least L bases hold at least half of all bases; 0 when there are none."""
+    ls = sorted((int(x) for x in lengths), reverse=True)
+    total, cum = sum(ls), 0
+    for x in ls:
+        cum += x
+        if 2 * cum >= total:
+            return x
+    return 0
+
+
+def _summary_closing(lines):
+    """The last line of the --summary file from its (status, integer row) pairs: revised reads, unrevised reads, N50 of the revised."""
+    rev = [sum(v[42:47]) for st, v in lines if st == "revised"]
+    return [f"#reads\t{len(rev)}\t{len(lines) - len(rev)}\t{n50(rev)}"]
 
 
 class ReportPart:
-    """One process' share of the --report file: a line per read, appended and flushed as the read's output becomes final (so a
-    worker that dies leaves the lines of what it finished).  `merge_report` puts the parts together."""
+    """One process' share of the --report file (or, with cols = SUMMARY_COLS, of the --summary file): a line per read, appended
+    and flushed as the read's output becomes final (so a worker that dies leaves the lines of what it finished).  `merge_report`
+    puts the parts together."""
 
-    def __init__(self, path: Optional[str]):
-        self.path, self._lock, self._fp = path, threading.Lock(), None
+    def __init__(self, path: Optional[str], cols: int = 23):
+        self.path, self.cols, self._lock, self._fp = path, cols, threading.Lock(), None
 
     def __bool__(self):
         return self.path is not None
@@ -780,7 +858,7 @@ class ReportPart:
     def add(self, fn: str, revised: bool, row):
         if self.path is None:
             return
-        line = fn + "\t" + ("revised" if revised else "unrevised") + "\t" + "\t".join(str(int(v)) for v in np.asarray(row)[:23]) + "\n"
+        line = fn + "\t" + ("revised" if revised else "unrevised") + "\t" + "\t".join(str(int(v)) for v in np.asarray(row)[:self.cols]) + "\n"
         with self._lock:
             if self._fp is None:
                 self._fp = open(self.path, "a")
@@ -807,30 +885,41 @@ def clear_report_parts(report: str):
             pass
 
 
-def merge_report(report: str, names: Sequence[str], log: Callable[[str], None] = print):
-    """Parent side of --report: the parts in the order they were written (a later line for the same read wins: the parent's
-    own part comes last), one line per read of `names` sorted by file name, `#total` = the sums over the revised reads; the
-    file appears by rename and the parts are removed."""
+# what `merge_report` writes from the parts' integer columns: (columns per line, header, the switch's name, the integers -> the
+# fields of a line (None: the integers themselves), [(status, integers)] -> the lines behind #total (None: none))
+REPORT_TABLE = (23, REPORT_HEADER, "--report", None, None)
+SUMMARY_TABLE = (SUMMARY_COLS, SUMMARY_HEADER, "--summary", summary_fields, _summary_closing)
+
+
+def merge_report(report: str, names: Sequence[str], log: Callable[[str], None] = print, table=REPORT_TABLE):
+    """Parent side of --report (and, with SUMMARY_TABLE, of --summary): the parts in the order they were written (a later line
+    for the same read wins: the parent's own part comes last), one line per read of `names` sorted by file name, `#total` = the
+    sums over the revised reads; the file appears by rename and the parts are removed."""
     import glob
+    cols, header, switch, fields, closing = table
     rows = {}
     parts = sorted(glob.glob(glob.escape(report) + ".part*"), key=lambda f: (f.endswith(".partparent"), f))
     for f in parts:
         with open(f) as fp:
             for ln in fp:
                 c = ln.rstrip("\n").split("\t")
-                if ln.endswith("\n") and len(c) == 2 + 23:           # a line cut short by a dying worker is not a line
+                if ln.endswith("\n") and len(c) == 2 + cols:         # a line cut short by a dying worker is not a line
                     rows[c[0]] = c
-    total = [0] * 23
-    out = [REPORT_HEADER]
+    total, seen = [0] * cols, []
+    out = [header]
     for fn in sorted(names):
         c = rows.get(fn)
         if c is None:                                               # no process accounted for it: nothing was written
-            log(f"[！！！Warning] --report: no record for {fn}")
-            c = [fn, "unrevised"] + ["0"] * 23
-        out.append("\t".join(c))
+            log(f"[！！！Warning] {switch}: no record for {fn}")
+            c = [fn, "unrevised"] + ["0"] * cols
+        out.append("\t".join(c if fields is None else c[:2] + fields([int(v) for v in c[2:]])))
         if c[1] == "revised":
             total = [t + int(v) for t, v in zip(total, c[2:])]
-    out.append("#total\trevised\t" + "\t".join(str(t) for t in total))
+        if closing is not None:
+            seen.append((c[1], [int(v) for v in c[2:]]))
+    out.append("#total\trevised\t" + "\t".join(str(t) for t in total) if fields is None else "\t".join(["#total", "revised"] + fields(total)))
+    if closing is not None:
+        out += closing(seen)
     d = os.path.dirname(report)
     if d:
         os.makedirs(d, exist_ok=True)
@@ -878,9 +967,9 @@ def write_edits(edits_dir: str, fast5_fn: str, edits=None, want_qual: bool = Fal
 
 
 def _host_merge_form(packed):
-    """A `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` tuple back in the form whose call
+    """A `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` tuple back in the form whose call
     returns (p1, p2, a1, a2): for the paths that keep the host merge."""
-    if packed is None or len(packed) not in (12, 14, 16, 20):
+    if packed is None or len(packed) not in (12, 14, 16, 20, 22):
         return packed
     return tuple(packed[:7]) if packed[7] is None else tuple(packed[:9])
 
@@ -895,11 +984,12 @@ def _bundle_has_bases(bundle) -> bool:
     return "bases" in bundle and len(bundle["bases"]) == int(bundle["meta"][:, 1].sum())
 
 
-def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, report, edits=False, combined=False):
+def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, report, edits=False, combined=False, summary=False):
     """The one decision about a batch: (packed form `_FileRun.submit` builds, route `_FileRun.run_batch` takes).  Pure: it looks at what
     the engine object offers, at the bundle (None: reads that arrived one by one) and at the run's switches - pipelined (one
     engine, NRV_CLI_PIPELINE != 0), native_pool (libnanorev_host.so driven from the thread pool), device_merge (--device_merge
-    and what it needs: pipelined, native_pool, nrvh_write_records), report (--report), edits (--edits), combined (--combined).  "bases":
+    and what it needs: pipelined, native_pool, nrvh_write_records), report (--report), edits (--edits), combined (--combined),
+    summary (--summary).  "bases":
     `_bundle_has_bases`.  A form is
     the length of the packed tuple (engine.Reviser), None, or "host-merge": the merge form built and taken back.
 
@@ -916,6 +1006,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
       yes     + edits on, one of them missing                                host-merge [2]  by the last three rows
       yes     + combined on, a form 12 / 14 / 16 above, with_device_records  20 [5]          by the last three rows
       yes     + combined on, no with_device_records                          12 / 14 / 16 [6]  by the last three rows
+      yes     + summary on, a form 12 / 14 / 16 / 20 above, with_device_profile  22 [7]        by the last three rows
+      yes     + summary on, such a form, no with_device_profile              host-merge [2]  by the last three rows
       yes     any form; pipelined, native_pool, begin_packed_raw, bases                      pipelined [3]
       yes     any form; native_pool, bases, not (pipelined, begin_packed_raw)                packed+finish_bundle
       yes     any form; no native_pool, or no bases                                          packed sliced
@@ -927,7 +1019,9 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
     [4] the one call carries the report too when --report is set.
     [5] the one call carries the report and the edit list too when --report / --edits are set; its blob is appended to the
         --combined part as it is, and no native writer is called.
-    [6] the merged reads come back and the host forms the records (hoststage.pack_records), as on every host route."""
+    [6] the merged reads come back and the host forms the records (hoststage.pack_records), as on every host route.
+    [7] the one call carries whatever the form above carried (report, edit list, records) and the per-read profile last; every
+        other route forms the summary rows on the host from the calls (`profile_rows`)."""
     unpacked = "per-read" if n_reads == 1 else "predict_many"
     if bundle is None:
         return (7 if n_reads > 1 and hasattr(rv, "pack_reads_raw") else None), unpacked
@@ -941,6 +1035,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
             form = 16 if hasattr(rv, "with_device_edits") and form != "host-merge" else "host-merge"
         if combined and form != "host-merge" and hasattr(rv, "with_device_records"):
             form = 20
+        if summary and form != "host-merge":
+            form = 22 if hasattr(rv, "with_device_profile") else "host-merge"
     if not (native_pool and bases):
         return form, "packed sliced"
     return form, ("pipelined" if pipelined and hasattr(rv, "begin_packed_raw") else "packed+finish_bundle")
@@ -1048,12 +1144,15 @@ class _FileRun:
     """One `process_files` call: its state and its three kinds of thread.  MAIN reads `results()`, packs device calls as
     `_route_batch` says (`submit`) and collects the pooled finishers; the ENGINE thread(s) make the calls (`run_batch`, `collect`);
     the one FINISHER thread merges, reports and writes, or hands that to the parser pool (`finish_batch`, `finish_call`)."""
-    def __init__(self, stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part=None):
+    def __init__(self, stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part=None,
+                 summary_part=None):
         self.args, self.log, self.note = args, log, on_file or (lambda fn, ok: None)
         self.stats = {"reads": 0, "bases": 0, "failed": [], "host_s": 0.0, "engine_s": 0.0}
         self.stats_lock = threading.Lock()
         self.report = ReportPart(report_part)
         self.rep_rows = {}                            # fn -> the row of a read whose output is not final yet
+        self.sumpart = ReportPart(summary_part, SUMMARY_COLS)        # --summary: stashed and emitted wherever a report row is
+        self.sum_rows = {}
         self.tie_eps = float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS))
         self.edits_dir = getattr(args, "edits", None) # --edits: every read's list is written BEFORE its output is
         self.sink = CombinedPart(combined_part, args.output_format == "fastq") if combined_part else None   # --combined (`deliver`)
@@ -1161,6 +1260,7 @@ class _FileRun:
     def summary(self):
         """After the threads have ended: the report part closed, the trace and the range guard logged; the statistics."""
         self.report.close()
+        self.sumpart.close()
         if self.sink is not None:
             self.sink.close()
         self.trace.log_summary(self.log, len(self.engines))
@@ -1197,7 +1297,7 @@ class _FileRun:
         args, log = self.args, self.log
         self.stats["failed"].append(fn)
         log(f"[！！！Error] revising {fn.split('.')[0]}: {e}; writing the original basecalls")
-        nw = 0
+        nw, text = 0, ""
         if self.edits_dir:                            # unrevised: the header alone, replacing what a revision may have left
             try:
                 write_edits(self.edits_dir, fn)
@@ -1207,16 +1307,19 @@ class _FileRun:
             if args.output_format == "fastq" and fq is not None:
                 b, q = hs.trim_fastq(fq)
                 deliver(args, self.sink, [fn], ("text", b, q))
-                nw = len(b)
+                nw, text = len(b), b
             else:
                 orig = "".join(x.decode() for x in np.asarray(rt.bases).tolist())
                 deliver(args, self.sink, [fn], ("text", orig, None))
-                nw = len(orig)
+                nw, text = len(orig), orig
         except Exception as e2:
             log(f"[！！！Error] stroring : {fn.split('.')[0]}_out.{args.output_format}...... {e2}")
         if self.report:
             self.rep_rows.pop(fn, None)
             self.report.add(fn, False, unrevised_row(nw))
+        if self.sumpart:
+            self.sum_rows.pop(fn, None)
+            self.sumpart.add(fn, False, unrevised_profile(text))
         self.note(fn, False)
 
     def finished(self, fn, nb):
@@ -1226,6 +1329,11 @@ class _FileRun:
             if row is None:                           # cannot happen: every path that finishes a read stashes its row first
                 self.log(f"[！！！Warning] --report: no counts for {fn}")
             self.report.add(fn, row is not None, row if row is not None else unrevised_row(nb))
+        if self.sumpart:
+            row = self.sum_rows.pop(fn, None)
+            if row is None:                           # cannot happen, as above
+                self.log(f"[！！！Warning] --summary: no counts for {fn}")
+            self.sumpart.add(fn, row is not None, row if row is not None else np.zeros(hs.PROFILE_COLS, np.uint64))
         if not self.args.test_mode:
             self.log(f"[p:::] {fn.split('.')[0]}_out.{self.args.output_format} was saved......")
         else:
@@ -1242,7 +1350,7 @@ class _FileRun:
             if bundle is not None and "device_stats" in bundle and not (hasattr(rv, "run_packed_raw") and hasattr(rv, "with_device_stats")):
                 bundle = _bundle_host_stats(bundle)   # an engine without the new calls: the host computes them after all
             form, route = _route_batch(rv, bundle, len(batch), self.pipelined, self.native_pool, self.device_merge, bool(self.report),
-                                       edits=bool(self.edits_dir), combined=self.sink is not None)
+                                       edits=bool(self.edits_dir), combined=self.sink is not None, summary=bool(self.sumpart))
             if form is not None and bundle is None:
                 packed = prepare_many(cls, [rt for _, rt, _ in batch], rv.T)
             elif form is not None:
@@ -1256,10 +1364,13 @@ class _FileRun:
                     elif form != len(packed):
                         if self.report:
                             packed = cls.with_device_report(packed, self.tie_eps)
-                        if form == 16 or (form == 20 and self.edits_dir):   # --edits: the list behind the merge (and the report)
+                        if form == 16 or (form in (20, 22) and self.edits_dir):   # --edits: the list behind the merge (and the report)
                             packed = cls.with_device_edits(packed)
-                        if form == 20:                # --combined: the records behind them all; seq / qual stay on the device
+                        if form == 20 or (form == 22 and self.sink is not None and hasattr(rv, "with_device_records")):
+                            # --combined: the records behind them all; seq / qual stay on the device
                             packed = cls.with_device_records(packed, [hs.record_name(fn) for fn, _, _ in batch], hand_back=False)
+                        if form == 22:                # --summary: the profile last, behind whatever the call carries
+                            packed = cls.with_device_profile(packed)
         except Exception:
             packed = None
         if packed is None:
@@ -1298,6 +1409,8 @@ class _FileRun:
             try:
                 if self.report:
                     self.rep_rows[fn] = report_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual, self.tie_eps)[0]
+                if self.sumpart:
+                    self.sum_rows[fn] = profile_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c)[0]
                 if self.edits_dir:
                     write_edits(self.edits_dir, fn, edit_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual)[0], self.want_qual)
                 if self.pool is not None or self.sink is not None:
@@ -1325,17 +1438,23 @@ class _FileRun:
         try:
             fns, rts, fqs = map(list, zip(*batch))
             if merged:
+                if len(outs) == 9:                    # a `with_device_profile` call: the rows were counted behind the merge, last output
+                    if self.sumpart:
+                        self.sum_rows.update(zip(fns, outs[8]))
+                    outs = outs[:8]
                 if self.report:                       # a `with_device_report` call: the rows were counted behind the merge
                     self.rep_rows.update(zip(fns, outs[3]))
                 if self.edits_dir:                    # a `with_device_edits` call: the lists were compacted behind the merge
                     self.write_call_edits(fns, outs[4], outs[5])
-                payload = ("records", outs[6], outs[7], outs[2]) if len(outs) == 8 else \
+                payload = ("records", outs[6], outs[7], outs[2]) if len(outs) == 8 and outs[6] is not None else \
                     ("merged", outs[0], outs[1] if self.want_qual else None, outs[2])
             else:
                 p1, p2, a1, a2 = outs
                 T, ev_len = self.rv.T, bundle["meta"][:, 1].astype(np.int64)
                 if self.report:
                     self.rep_rows.update(zip(fns, report_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2, self.want_qual, self.tie_eps)))
+                if self.sumpart:
+                    self.sum_rows.update(zip(fns, profile_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2)))
                 if self.edits_dir:
                     self.write_call_edits(fns, *edit_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2, self.want_qual))
                 qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
@@ -1432,7 +1551,8 @@ class _FileRun:
 
 def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None],
                   on_file: Optional[Callable[[str, bool], None]] = None, gpu_workers: int = 1,
-                  core_share: Optional[int] = None, report_part: Optional[str] = None, combined_part: Optional[str] = None) -> dict:
+                  core_share: Optional[int] = None, report_part: Optional[str] = None, combined_part: Optional[str] = None,
+                  summary_part: Optional[str] = None) -> dict:
     """Revise `files` (names inside args.fast5_base_dir) with one engine.  The host stage (HDF5 parsing, event collapse,
     statistics) runs --thread parser workers that stay a bounded number of reads ahead of the device: THREADS of this process
     inside libnanorev_host.so (at most kNativePoolMax), or PROCESSES on the Python host stage without it / with NRV_HOST_THREADS=0.
@@ -1443,10 +1563,11 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
     start 8 x 2 parser workers, not 8 x 16.  core_share: this call's cores, when the caller has already
     divided them (a GPU worker pinned to its NUMA slice: `_worker`).  report_part (--report): the file this call appends
     one line per read to, ahead of on_file (`ReportPart`).  combined_part (--combined): the part this call appends
-    every read's record to INSTEAD of writing one file per read (`CombinedPart`, `deliver`)."""
+    every read's record to INSTEAD of writing one file per read (`CombinedPart`, `deliver`).  summary_part (--summary): as
+    report_part, for the summary's lines."""
     import contextlib
     with contextlib.ExitStack() as stack:             # its exit ends the run's threads and undoes what `_FileRun._start` did
-        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part)
+        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part, summary_part)
         batch, nev = [], 0                            # unbundled reads are grouped into device calls of >= batch_events events
         for entries, bundle in run.results():
             bundled = []
@@ -1457,6 +1578,7 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                     log(f"！！！[Error] fast5 file: {fn.split('.')[0]} {err}")
                     run.stats["failed"].append(fn)
                     run.report.add(fn, False, unrevised_row(0))
+                    run.sumpart.add(fn, False, unrevised_profile(b""))
                     run.note(fn, False)
                 elif err is not None:
                     run.fallback(fn, rt, fq, err)
@@ -1675,7 +1797,7 @@ def revise_part(args, reviser, fn: str, k: int, parts: int):
         a1 = a2 = np.zeros(0, np.int8)
     qc = phred_chars(p1, p2, a1, a2) if args.output_format == "fastq" and len(a1) else None
     out = {"T": T, "n_ev": N, "lo": lo, "a1": np.array(a1, np.int8), "a2": np.array(a2, np.int8), "qc": qc}
-    if getattr(args, "report", None) or getattr(args, "edits", None):   # the parent reports the read once its slices are merged: near-ties (and the edits' conf) need the rows
+    if getattr(args, "report", None) or getattr(args, "edits", None) or getattr(args, "summary", None):   # the parent reports the read once its slices are merged: near-ties (and the edits' conf) need the rows
         out["p1"], out["p2"] = np.array(p1, np.float32), np.array(p2, np.float32)
     if k == 0:
         out["bases"], out["fq"] = np.asarray(rt.bases), fq
@@ -1716,7 +1838,8 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
         st = process_files(args, files, rv if rv is not None else make, print,
                            on_file=lambda fn, ok: q.put(("file", rank, fn, bool(ok))), gpu_workers=world, core_share=share,
                            report_part=report_part_path(args.report, rank) if getattr(args, "report", None) else None,
-                           combined_part=combined_part_path(args.combined, rank) if getattr(args, "combined", None) else None)
+                           combined_part=combined_part_path(args.combined, rank) if getattr(args, "combined", None) else None,
+                           summary_part=report_part_path(args.summary, rank) if getattr(args, "summary", None) else None)
         st["cpus"] = len(cpus) if cpus else 0
         for e in made:
             e.close()
@@ -1726,7 +1849,7 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
 
 
 def write_originals(args, files: Sequence[str], log: Callable[[str], None], report: Optional[ReportPart] = None,
-                    sink: Optional[CombinedPart] = None) -> List[str]:
+                    sink: Optional[CombinedPart] = None, summary: Optional[ReportPart] = None) -> List[str]:
     """The failure contract for reads whose WORKER is gone (NanoReviser.py:146-152 / :173-179): every
     file in `files` - the ones the dead worker never reported as final - gets its original basecalls
     written by this process (atomically, replacing whatever an earlier run left under that name).
@@ -1734,7 +1857,7 @@ def write_originals(args, files: Sequence[str], log: Callable[[str], None], repo
     done = []
     for fn in files:
         done.append(fn)
-        nw = 0
+        nw, text = 0, ""
         try:
             rd, fq = parse_read(os.path.join(args.fast5_base_dir, fn), args.basecall_group, args.basecall_subgroup)
             if getattr(args, "edits", None):         # unrevised: the header alone
@@ -1745,16 +1868,18 @@ def write_originals(args, files: Sequence[str], log: Callable[[str], None], repo
             else:
                 b = "".join(x.decode() for x in np.asarray(rd.bases).tolist())
                 deliver(args, sink, [fn], ("text", b, None))
-            nw = len(b)
+            nw, text = len(b), b
         except Exception as e:
             log(f"！！！[Error] fast5 file: {fn.split('.')[0]} {e!r}")
         if report is not None:
             report.add(fn, False, unrevised_row(nw))
+        if summary is not None:
+            summary.add(fn, False, unrevised_profile(text))
     return done
 
 
 def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[str], None], report: Optional[ReportPart] = None,
-                       sink: Optional[CombinedPart] = None):
+                       sink: Optional[CombinedPart] = None, summary: Optional[ReportPart] = None):
     """Parent side of the split reads: the slices' calls in slice order are the read's calls (window i of slice k is
     window lo_k + i of the read), merged and written exactly as an unsplit read's.  A read with a slice missing (its
     worker died) or failed gets its original basecalls (NanoReviser.py:146-152).  Returns (bases written, failed names)."""
@@ -1792,10 +1917,13 @@ def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[st
                         (qc if qc is not None else np.zeros(0, np.uint8)) if args.output_format == "fastq" else None, T,
                         float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS)))[0]
                     report.add(fn, True, row)
+                if summary is not None and summary and have_p:
+                    summary.add(fn, True, profile_rows(T, pl[0]["bases"], [N], np.concatenate([p["p1"] for p in pl]),
+                                                       np.concatenate([p["p2"] for p in pl]), a1, a2)[0])
                 continue
             err = e2
         log(f"[！！！Error] revising {fn.split('.')[0]}: {err}; writing the original basecalls")
-        write_originals(args, [fn], log, report, sink)
+        write_originals(args, [fn], log, report, sink, summary)
         failed.append(fn)
     return nb, failed
 
@@ -1875,6 +2003,13 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
         if d:
             os.makedirs(d, exist_ok=True)
     parent_report = ReportPart(report_part_path(args.report, "parent") if args.report else None)
+    if args.summary:                      # --summary: parts and a parent-side merge as for --report
+        clear_report_parts(args.summary)
+        d = os.path.dirname(args.summary)
+        if d:
+            os.makedirs(d, exist_ok=True)
+    parent_summary = ReportPart(report_part_path(args.summary, "parent") if args.summary else None, SUMMARY_COLS)
+    sum_part0 = report_part_path(args.summary, 0) if args.summary else None
     if args.combined:                     # --combined: a part per process too, `merge_combined` ends the run
         clear_combined_parts(args.combined)
     parent_sink = CombinedPart(combined_part_path(args.combined, "parent"), args.output_format == "fastq") if args.combined else None
@@ -1905,13 +2040,16 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
         n_resumed, names = len(skip), [f for f in names if f not in skip]
         for f in sorted(skip):            # not revised by THIS run: reported as what lies on disk
             parent_report.add(f, False, unrevised_row(written_length(out_name(args.output_dir, f, args.output_format))))
+            if args.summary:
+                parent_summary.add(f, False, unrevised_profile(written_sequence(out_name(args.output_dir, f, args.output_format),
+                                                                                  args.output_format == "fastq")))
         print(f"[s:::] --resume: {n_resumed} reads already have their output, {len(names)} to do"
               + (f" ({len(earlier_failed)} of them written unrevised by the earlier run"
                  + (", left as they are)" if args.resume_keep_failed else ", revised again)") if earlier_failed else ""))
     if reviser_factory is not None:       # in-process (tests / embedding): one engine, no sharding
         rv = reviser_factory(args, 0)
         stats = [process_files(args, names, rv, print, report_part=report_part_path(args.report, 0) if args.report else None,
-                               combined_part=part0)]
+                               combined_part=part0, summary_part=sum_part0)]
     else:
         # the command line needs no torch: without it a process starts ~1.5 s sooner.  (engine.py imports
         # torch first only so that a LATER torch import in the same process finds one HIP runtime.)
@@ -1940,7 +2078,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
                 made.append((worker_factory or _default_factory)(args, 0))
                 return made[-1]                       # called once per engine (process_files: NRV_CLI_ENGINES)
             stats = [process_files(args, names, make, print, report_part=report_part_path(args.report, 0) if args.report else None,
-                                   combined_part=part0)]
+                                   combined_part=part0, summary_part=sum_part0)]
             for rv in made:
                 rv.close()
         else:
@@ -1951,7 +2089,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
             res = run_workers(args, shards, worker_factory, part_shards=part_shards, parts_out=parts_got)
             stats = [s for _, s, _, _ in res if s is not None]
             if split_fns:
-                nb_split, failed_split = finish_split_reads(args, split_fns, parts_got, print, parent_report, parent_sink)
+                nb_split, failed_split = finish_split_reads(args, split_fns, parts_got, print, parent_report, parent_sink, parent_summary)
                 stats.append({"reads": len(split_fns), "bases": nb_split, "failed": failed_split, "host_s": 0.0, "engine_s": 0.0})
                 if failed_split:
                     rc = 3
@@ -1961,13 +2099,16 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
                           f"unfinished reads", file=sys.stderr)
                     # what the worker reported final stays (its failed reads keep their failed_reads entry);
                     # everything else - started or not, whatever lies on disk - is written unrevised
-                    lost = write_originals(args, [f for f in shards[r] if f not in final], print, parent_report, parent_sink)
+                    lost = write_originals(args, [f for f in shards[r] if f not in final], print, parent_report, parent_sink, parent_summary)
                     lost += [f for f, ok in final.items() if not ok]
                     stats.append({"reads": len(shards[r]), "bases": 0, "failed": lost, "host_s": 0.0, "engine_s": 0.0})
                     rc = 3
     parent_report.close()
     if args.report:
         merge_report(args.report, all_names)
+    parent_summary.close()
+    if args.summary:
+        merge_report(args.summary, all_names, table=SUMMARY_TABLE)
     if args.combined:
         parent_sink.close()
         merge_combined(args.combined, args.output_format == "fastq")

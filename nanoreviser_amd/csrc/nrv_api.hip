@@ -575,6 +575,12 @@ struct nrv_handle {
     bool records = false;
     uint8_t* blob_out = nullptr;
     int64_t* roff_out = nullptr;
+    // nrv_revise_reads_raw_profile_begin (nrv_profile.h): the profile block u64 x n_reads x 48 behind rec_off, the last part that
+    // comes back with the block (m_dl grows by it), and the call's own 39 thresholds
+    size_t m_prof = 0;
+    bool profile = false;
+    float prof_thr[kPhredSteps] = {0};
+    uint64_t* prof_out = nullptr;
     uint8_t *seq = nullptr, *qual = nullptr;
     int64_t* off = nullptr;
     int64_t N = 0, n = 0;
@@ -1990,6 +1996,25 @@ static int pack_enqueue(nrv_handle* h, const PackArgs& a) {
   HIPCHK(h, hipGetLastError());
   return NRV_OK;
 }
+// The profile kernel (nrv_profile.h) behind merge_enqueue (and the report / edit / record launches) on the same stream: it reads
+// the records the merge left in rec.  The block is zeroed here, in stream order ahead of the launch, as the report's is.
+static int profile_enqueue(nrv_handle* h, const ProfileArgs& a) {
+  if (a.n_reads <= 0 || a.N <= 0) return NRV_OK;
+  HIPCHK(h, hipMemsetAsync(a.profile, 0, (size_t)a.n_reads * kProfileCols * 8, h->stream));
+  const unsigned tiles = (unsigned)((a.N + kMergeTile - 1) / kMergeTile);
+  hipLaunchKernelGGL(profile_kernel, dim3(tiles), dim3(256), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return NRV_OK;
+}
+static ProfileArgs profile_args(const MergeArgs& m, const float* p1, const float* p2, const float* thr, void* profile) {
+  ProfileArgs a;
+  a.reads = m.reads; a.n_reads = m.n_reads; a.T = m.T; a.N = m.N;
+  a.a1 = m.a1; a.a2 = m.a2; a.p1 = p1; a.p2 = p2;
+  a.rec = m.rec;
+  a.profile = (unsigned long long*)profile;
+  memcpy(a.thr, thr, sizeof a.thr);
+  return a;
+}
 // bytes the records of a call can take: hoststage.pack_records on N + max(N - T, 0) characters at the most
 static size_t blob_capacity(int64_t N, int64_t n, int n_reads, int64_t name_bytes, bool fastq) {
   const size_t q = fastq ? 2 : 1;
@@ -2025,13 +2050,13 @@ static void records_host(const uint8_t* seq, const uint8_t* qual, const int64_t*
   }
   rec_off[n_reads] = p;
 }
-// layout of a merged block for N events, n windows, n_reads reads: [off | seq | qual | report | edit_off | rec_off] (what comes
-// back; the report, edit_off and rec_off only where asked for) + [rec | tile] (scratch) + [edits | etile] (the edit records,
+// layout of a merged block for N events, n windows, n_reads reads: [off | seq | qual | report | edit_off | rec_off | profile] (what comes
+// back; the report, edit_off, rec_off and profile only where asked for) + [rec | tile] (scratch) + [edits | etile] (the edit records,
 // fetched by their used prefix, and their scratch; only where asked for) + [blob] (the FASTA / FASTQ records, fetched by their
 // used prefix; only where asked for)
-struct MergeLayout { size_t seq, qual, rep, eoff, roff, rec, tile, edits, etile, blob, dl, bytes; };
+struct MergeLayout { size_t seq, qual, rep, eoff, roff, prof, rec, tile, edits, etile, blob, dl, bytes; };
 static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, bool report = false, bool edits = false, bool records = false,
-                                size_t blob_cap = 0) {
+                                size_t blob_cap = 0, bool profile = false) {
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   MergeLayout m;
   const size_t cap = (size_t)(N + n), tiles = (size_t)((N + kMergeTile - 1) / kMergeTile);
@@ -2040,7 +2065,8 @@ static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, bool report =
   m.rep = m.qual + up(cap);
   m.eoff = m.rep + (report ? up((size_t)n_reads * kReportCols * 8) : 0);
   m.roff = m.eoff + (edits ? up(((size_t)n_reads + 1) * 8) : 0);
-  m.dl = m.roff + (records ? up(((size_t)n_reads + 1) * 8) : 0);
+  m.prof = m.roff + (records ? up(((size_t)n_reads + 1) * 8) : 0);
+  m.dl = m.prof + (profile ? up((size_t)n_reads * kProfileCols * 8) : 0);
   m.rec = m.dl;
   m.tile = m.rec + up((size_t)N * 4);
   m.edits = m.tile + up(tiles * 8);
@@ -2067,6 +2093,19 @@ static void report_nothing(const nrv_read_desc* reads, int n_reads, bool want_q,
     if (want_q) row[kRcQSum] = 2 * (uint64_t)reads[r].ev_len;
   }
 }
+// ... and its profile (hoststage.read_profile on a call without a window): every character is an original base with '#', Phred 2
+static void profile_nothing(const uint8_t* bases, const nrv_read_desc* reads, int n_reads, uint64_t* profile) {
+  static_assert(NRV_PROFILE_COLS == kProfileCols, "nanorev.h and nrv_profile.h disagree on the profile's columns");
+  memset(profile, 0, (size_t)n_reads * kProfileCols * 8);
+  for (int r = 0; r < n_reads; ++r) {
+    uint64_t* row = profile + (size_t)r * kProfileCols;
+    row[2] = (uint64_t)reads[r].ev_len;
+    for (int64_t e = reads[r].ev_off; e < reads[r].ev_off + reads[r].ev_len; ++e) {
+      const uint8_t c = bases[e];
+      row[kPfBase + (c == 'A' ? 0 : (c == 'C' ? 1 : (c == 'G' ? 2 : (c == 'T' ? 3 : 4))))] += 1;
+    }
+  }
+}
 struct MergeReq {             // what nrv_revise_reads_raw_begin adds to a raw-read call
   const uint8_t* bases;
   const float* q_thr;
@@ -2080,6 +2119,8 @@ struct MergeReq {             // what nrv_revise_reads_raw_begin adds to a raw-r
   const int64_t* name_off = nullptr;
   uint8_t* blob = nullptr;
   int64_t* rec_off = nullptr;
+  const float* prof_thr = nullptr;    // nrv_revise_reads_raw_profile_begin: its own 39 thresholds and [n_reads][48]
+  uint64_t* profile = nullptr;
 };
 static MergeArgs slot_merge_args(const nrv_handle* h, const nrv_handle::RawSlot& sl) {
   char* const d = sl.d_out + 64;
@@ -2105,6 +2146,10 @@ static EditsArgs slot_edits_args(const nrv_handle* h, const nrv_handle::RawSlot&
   return edits_args(slot_merge_args(h, sl), (const float*)d, (const float*)(d + sl.rows * 24), sl.want_q,
                     sl.d_mrg + sl.m_etile, sl.d_mrg + sl.m_eoff, sl.d_mrg + sl.m_edits);
 }
+static ProfileArgs slot_profile_args(const nrv_handle* h, const nrv_handle::RawSlot& sl) {
+  char* const d = sl.d_out + 64;                               // p1 / p2: as for the report
+  return profile_args(slot_merge_args(h, sl), (const float*)d, (const float*)(d + sl.rows * 24), sl.prof_thr, sl.d_mrg + sl.m_prof);
+}
 static PackArgs slot_pack_args(const nrv_handle::RawSlot& sl) {
   PackArgs a;
   a.n_reads = sl.n_reads; a.fastq = sl.want_q ? 1 : 0;
@@ -2116,7 +2161,7 @@ static PackArgs slot_pack_args(const nrv_handle::RawSlot& sl) {
   return a;
 }
 // what comes back of a merged block, on stream s: all of [0, m_dl) - or, for a records call that hands back neither seq nor qual,
-// the parts in front of and behind them
+// the parts in front of and behind them (the profile lies behind rec_off, inside m_dl)
 static int merged_download(nrv_handle* h, nrv_handle::RawSlot& sl, hipStream_t s) {
   const bool skip = sl.records && !sl.seq && !sl.qual;
   const size_t head = skip ? sl.m_seq : sl.m_dl;
@@ -2164,11 +2209,13 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
   sl.report = mr != nullptr && mr->report != nullptr;
   sl.edits = mr != nullptr && mr->edit_off != nullptr;
   sl.records = records;
+  sl.profile = mr != nullptr && mr->profile != nullptr;
   if (sl.n == 0) {                                              // nothing to compute: _end returns at once
     if (mr) merge_nothing(mr->bases, reads, n_reads, N, mr->seq, mr->q_thr ? mr->qual : nullptr, mr->off);
     if (sl.report) report_nothing(reads, n_reads, mr->q_thr != nullptr && (mr->qual != nullptr || records), mr->report);
     if (sl.edits) memset(mr->edit_off, 0, ((size_t)n_reads + 1) * 8);   // no window, no record
     if (records) records_host(mr->bases, nullptr, mr->off, n_reads, mr->names, mr->name_off, rec_fastq, mr->blob, mr->rec_off);
+    if (sl.profile) profile_nothing(mr->bases, reads, n_reads, mr->profile);
     sl.busy = true;
     return NRV_OK;
   }
@@ -2209,7 +2256,9 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
     sl.sat_seen = 0;
   }
   if (mr) {
-    const MergeLayout m = merge_layout(N, sl.n, n_reads, sl.report, sl.edits, records, blob_cap);
+    const MergeLayout m = merge_layout(N, sl.n, n_reads, sl.report, sl.edits, records, blob_cap, sl.profile);
+    sl.m_prof = m.prof; sl.prof_out = mr->profile;
+    if (sl.profile) memcpy(sl.prof_thr, mr->prof_thr, sizeof sl.prof_thr);
     sl.m_roff = m.roff; sl.m_blob = m.blob; sl.m_bytes = m.bytes; sl.blob_cap = blob_cap;
     sl.blob_out = mr->blob; sl.roff_out = mr->rec_off;
     sl.m_seq = m.seq; sl.m_qual = m.qual; sl.m_rec = m.rec; sl.m_tile = m.tile; sl.m_dl = m.dl;
@@ -2275,7 +2324,8 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
   if (rc || (rc = raw_enqueue(h, sl)) || (mr && (rc = merge_enqueue(h, slot_merge_args(h, sl)))) ||
       (sl.report && (rc = report_enqueue(h, slot_report_args(h, sl)))) ||
       (sl.edits && (rc = edits_enqueue(h, slot_edits_args(h, sl)))) ||
-      (records && (rc = pack_enqueue(h, slot_pack_args(sl))))) {
+      (records && (rc = pack_enqueue(h, slot_pack_args(sl)))) ||
+      (sl.profile && (rc = profile_enqueue(h, slot_profile_args(h, sl))))) {
     (void)hipStreamSynchronize(h->stream);                      // part of the call may be enqueued: nothing of it may outlive the slot
     return rc;
   }
@@ -2411,6 +2461,37 @@ int nrv_revise_reads_raw_records(nrv_handle* h, const int16_t* raw, int64_t n_ra
   return rc ? rc : nrv_reads_raw_end(h, t);
 }
 
+int nrv_revise_reads_raw_profile_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                       const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                       const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                       uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                       nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                       uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile, int* ticket) {
+  if (h && ((last_dur == nullptr) != (on_device == nullptr))) { h->err = "nrv_revise_reads_raw_profile_begin: last_dur and on_device go together"; return NRV_E_INVALID; }
+  if (h && (!prof_thr || !profile)) { h->err = "nrv_revise_reads_raw_profile_begin: null prof_thr / profile"; return NRV_E_INVALID; }
+  if (h && edits && !edit_off) { h->err = "nrv_revise_reads_raw_profile_begin: edits without edit_off"; return NRV_E_INVALID; }
+  if (h && !rec_off && (names || name_off || blob)) { h->err = "nrv_revise_reads_raw_profile_begin: names / name_off / blob without rec_off"; return NRV_E_INVALID; }
+  MergeReq mr{bases, q_thr, seq, qual, off};
+  mr.report = report; mr.tie_eps = tie_eps;                    // report == NULL: none is counted
+  mr.edits = edits; mr.edit_off = edit_off;                    // edit_off == NULL: no edit list
+  mr.names = names; mr.name_off = name_off; mr.blob = blob; mr.rec_off = rec_off;   // rec_off == NULL: no records
+  mr.prof_thr = prof_thr; mr.profile = profile;
+  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, nullptr, nullptr, nullptr, nullptr, ticket, &mr);
+}
+
+int nrv_revise_reads_raw_profile(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                 const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                 const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                 uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                 nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                 uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile) {
+  int t = -1;
+  const int rc = nrv_revise_reads_raw_profile_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                                    seq, qual, off, tie_eps, report, edits, edit_off, names, name_off, blob, rec_off,
+                                                    prof_thr, profile, &t);
+  return rc ? rc : nrv_reads_raw_end(h, t);
+}
+
 int nrv_reads_raw_end(nrv_handle* h, int ticket) {
   int rc = check_handle(h);
   if (rc) return rc;
@@ -2436,6 +2517,8 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
       if (sl.edits && (rc = edits_enqueue(h, slot_edits_args(h, sl)))) return rc;
       // ... and the records, from the seq / qual / off of the second merge; rec_off is read again below
       if (sl.records && (rc = pack_enqueue(h, slot_pack_args(sl)))) return rc;
+      // ... and the profile: profile_enqueue zeroes the block again, as the report's
+      if (sl.profile && (rc = profile_enqueue(h, slot_profile_args(h, sl)))) return rc;
       HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64, hipMemcpyDeviceToHost, h->stream));
       if ((rc = merged_download(h, sl, h->stream))) return rc;
     } else {
@@ -2453,6 +2536,7 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
     if (sl.seq) memcpy(sl.seq, sl.pin_mrg + sl.m_seq, (size_t)total);
     if (sl.want_q && sl.qual) memcpy(sl.qual, sl.pin_mrg + sl.m_qual, (size_t)total);
     if (sl.report) memcpy(sl.rep_out, sl.pin_mrg + sl.m_rep, (size_t)sl.n_reads * kReportCols * 8);
+    if (sl.profile) memcpy(sl.prof_out, sl.pin_mrg + sl.m_prof, (size_t)sl.n_reads * kProfileCols * 8);
     if (sl.edits) {
       // the used prefix of the records alone: a copy of its own size on a stream of its own - the records are complete (ev_done
       // lies behind the edit kernels, or the re-run above was waited for), and neither the compute stream nor d2h_stream, which
@@ -2570,10 +2654,12 @@ int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32
   return NRV_OK;
 }
 
-// nrv_merge_calls (report == nullptr: that call, to the byte), nrv_merge_calls_report and (edit_off != nullptr) nrv_merge_calls_edits
+// nrv_merge_calls (report == nullptr: that call, to the byte), nrv_merge_calls_report, (edit_off != nullptr) nrv_merge_calls_edits
+// and (profile != nullptr) nrv_merge_calls_profile
 static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
                             const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
-                            float tie_eps, uint64_t* report, nrv_edit* edits = nullptr, int64_t* edit_off = nullptr) {
+                            float tie_eps, uint64_t* report, nrv_edit* edits = nullptr, int64_t* edit_off = nullptr,
+                            const float* prof_thr = nullptr, uint64_t* profile = nullptr) {
   int rc = check_handle(h);
   if (rc) return rc;
   if (n_reads < 0 || n_win < 0 || !off || (n_reads > 0 && !ev_len)) { h->err = "nrv_merge_calls: bad arguments"; return NRV_E_INVALID; }
@@ -2595,13 +2681,14 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
     merge_nothing(bases, rd.data(), n_reads, N, seq, want_q ? qual : nullptr, off);
     if (report) report_nothing(rd.data(), n_reads, want_q, report);
     if (edit_off) memset(edit_off, 0, ((size_t)n_reads + 1) * 8);
+    if (profile) profile_nothing(bases, rd.data(), n_reads, profile);
     return NRV_OK;
   }
   if (edit_off && !edits) { h->err = "nrv_merge_calls_edits: null edits"; return NRV_E_INVALID; }
   // one block of its own: [reads | bases | a1 | a2 | p1 | p2 | merged block]
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const MergeLayout m = merge_layout(N, n, n_reads, report != nullptr, edit_off != nullptr);
-  const bool have_p = want_q || ((report || edit_off) && p1 && p2);   // the report's near-tie column and the edits' conf read the rows without a quality too
+  const MergeLayout m = merge_layout(N, n, n_reads, report != nullptr, edit_off != nullptr, false, 0, profile != nullptr);
+  const bool have_p = want_q || ((report || edit_off || profile) && p1 && p2);   // the report's near-tie column and the edits' conf read the rows without a quality too
   const size_t o_b = up((size_t)n_reads * sizeof(SegRead)), o_a1 = o_b + up((size_t)N), o_a2 = o_a1 + up((size_t)n);
   const size_t o_p1 = o_a2 + up((size_t)n), o_p2 = o_p1 + (have_p ? up((size_t)n * 24) : 0), o_m = o_p2 + (have_p ? up((size_t)n * 20) : 0);
   const size_t bytes = o_m + m.bytes;
@@ -2637,6 +2724,8 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
     if (edit_off && (rc2 = edits_enqueue(h, edits_args(a, have_p ? (const float*)(d + o_p1) : nullptr, have_p ? (const float*)(d + o_p2) : nullptr,
                                                       want_q, d + o_m + m.etile, d + o_m + m.eoff, d + o_m + m.edits))))
       return rc2;
+    if (profile && (rc2 = profile_enqueue(h, profile_args(a, (const float*)(d + o_p1), (const float*)(d + o_p2), prof_thr, d + o_m + m.prof))))
+      return rc2;
     HIPCHK(h, hipMemcpyAsync(back.data(), d + o_m, m.dl, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (edit_off) {                                             // the used prefix of the records, once the total is known
@@ -2657,6 +2746,7 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
   if (want_q) memcpy(qual, back.data() + m.qual, (size_t)total);
   if (report) memcpy(report, back.data() + m.rep, (size_t)n_reads * kReportCols * 8);
   if (edit_off) memcpy(edit_off, back.data() + m.eoff, ((size_t)n_reads + 1) * 8);
+  if (profile) memcpy(profile, back.data() + m.prof, (size_t)n_reads * kProfileCols * 8);
   return NRV_OK;
 }
 
@@ -2678,6 +2768,15 @@ int nrv_merge_calls_edits(nrv_handle* h, const uint8_t* bases, const int64_t* ev
                           float tie_eps, uint64_t* report, nrv_edit* edits, int64_t* edit_off) {
   if (h && !edit_off) { h->err = "nrv_merge_calls_edits: null edit_off"; return NRV_E_INVALID; }
   return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, seq, qual, off, tie_eps, report, edits, edit_off);
+}
+
+int nrv_merge_calls_profile(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                            const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                            const float* prof_thr, uint64_t* profile) {
+  if (h && (!prof_thr || !profile)) { h->err = "nrv_merge_calls_profile: null prof_thr / profile"; return NRV_E_INVALID; }
+  if (h && (!p1 || !p2)) { h->err = "nrv_merge_calls_profile: null p1 / p2"; return NRV_E_INVALID; }
+  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, seq, qual, off, 0.f, nullptr, nullptr, nullptr,
+                          prof_thr, profile);
 }
 
 int nrv_pack_records(nrv_handle* h, const uint8_t* seq, const uint8_t* qual, const int64_t* off, int n_reads,

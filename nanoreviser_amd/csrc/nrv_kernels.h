@@ -31,7 +31,9 @@
 //     nrv_revise_reads_raw_report_begin, report_kernel of nrv_report.h behind them, and, only for nrv_revise_reads_raw_edits_begin,
 //     the three launches of nrv_edits.h (edits_count / edits_tile_scan / edits_scatter_kernel: the per-read edit list, a stream
 //     compaction in event order) behind those, and, only for nrv_revise_reads_raw_records_begin, the two launches of nrv_pack.h
-//     (pack_offsets / pack_copy_kernel: the reads' FASTA / FASTQ records as the bytes of the output file) last of all.  Rows (windows) are independent: no inter-workgroup communication anywhere.
+//     (pack_offsets / pack_copy_kernel: the reads' FASTA / FASTQ records as the bytes of the output file) behind those, and, only for
+//     nrv_revise_reads_raw_profile_begin, profile_kernel of nrv_profile.h (per-read Phred histogram and base counts) last of all.
+//     Rows (windows) are independent: no inter-workgroup communication anywhere.
 //   * One Bi-LSTM layer = one launch; a wave owns a group of hidden units x 4 gates x R row tiles, so
 //     i,f,g,o of one (window, unit) sit in the same lane and the cell update is register-local; c never leaves the
 //     wave, h_t goes through an LDS image (lstm_h2s_kernel: double-buffered, one barrier per step; lstm_h2w_kernel:
@@ -67,3 +69,4 @@
 #include "nrv_report.h"        // report_kernel (per-read revision report behind the merge, opt-in)
 #include "nrv_edits.h"         // edits_count / edits_tile_scan / edits_scatter_kernel (per-read edit list behind the merge, opt-in)
 #include "nrv_pack.h"          // pack_offsets / pack_copy_kernel (FASTA / FASTQ records of the merged reads, opt-in)
+#include "nrv_profile.h"       // profile_kernel (per-read quality histogram and base counts behind the merge, opt-in)

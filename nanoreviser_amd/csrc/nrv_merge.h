@@ -61,6 +61,14 @@ __device__ __forceinline__ unsigned merge_block_scan(unsigned v, unsigned* total
   return before + x - v;
 }
 
+// #{k : thr[k] <= conf}, compared in f32: a window's Phred value is 1 + this (merge_emit, and profile_kernel of nrv_profile.h)
+__device__ __forceinline__ unsigned merge_phred_steps(const float (&thr)[kPhredSteps], const float conf) {
+  unsigned k = 0;
+#pragma unroll
+  for (int i = 0; i < kPhredSteps; ++i) k += thr[i] <= conf ? 1u : 0u;
+  return k;
+}
+
 __global__ void __launch_bounds__(256) merge_emit_kernel(const MergeArgs a) {
   const long long E = (long long)blockIdx.x * kMergeTile + threadIdx.x;
   unsigned count = 0, rec = 0;
@@ -91,10 +99,7 @@ __global__ void __launch_bounds__(256) merge_emit_kernel(const MergeArgs a) {
         const int g1 = c1 < 0 ? 0 : (c1 > 5 ? 5 : c1), g2 = c2 < 0 ? 0 : (c2 > 4 ? 4 : c2);
         const float u = a.p1[w * 6 + g1], v = a.p2[w * 5 + g2];
         const float conf = v < u ? v : u;
-        unsigned k = 0;
-#pragma unroll
-        for (int i = 0; i < kPhredSteps; ++i) k += a.thr[i] <= conf ? 1u : 0u;
-        q = 33 + 1 + k;
+        q = 33 + 1 + merge_phred_steps(a.thr, conf);
       }
     }
     rec = count | (j == 0 ? 4u : 0u) | first << 8 | second << 16 | q << 24;

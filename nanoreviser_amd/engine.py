@@ -38,8 +38,10 @@ SYMBOLS = [
     "nrv_revise_reads_raw_report_begin", "nrv_revise_reads_raw_report", "nrv_merge_calls_report",
     "nrv_revise_reads_raw_edits_begin", "nrv_revise_reads_raw_edits", "nrv_merge_calls_edits",
     "nrv_revise_reads_raw_records_begin", "nrv_revise_reads_raw_records", "nrv_pack_records",
+    "nrv_revise_reads_raw_profile_begin", "nrv_revise_reads_raw_profile", "nrv_merge_calls_profile",
 ]
 REPORT_COLS = 24                    # NRV_REPORT_COLS
+PROFILE_COLS = 48                   # NRV_PROFILE_COLS
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "f16x2": 2}
 
@@ -85,8 +87,9 @@ _MERGE = ([_U8P, _FP, _U8P, _U8P, _I64P], lambda p: (p[9], p[10]) + tuple(p[11])
 _REPORT = ([C.c_float, _U64P], lambda p: p[12:14])                                       # tie_eps, report
 _EDITS = ([C.c_void_p, _I64P], lambda p: (None if p[14] is None else p[14].ctypes.data, p[15]))   # edits (nrv_edit records), edit_off
 _RECORDS = ([_U8P, _I64P, _U8P, _I64P], lambda p: p[16:20])                              # names, name_off, blob, rec_off
+_PROFILE = ([_FP, _U64P], lambda p: p[20:22])                                            # prof_thr, profile
 # len(packed) -> (synchronous symbol, begin symbol, blocks, whether the call returns merged reads: (seq, qual, off[, report]
-# [, edits, edit_off][, blob, rec_off]))
+# [, edits, edit_off][, blob, rec_off][, profile]))
 _RAW_FORMS = {
     7: ("nrv_predict_reads_raw", "nrv_reads_raw_begin", (_CALLS,), False),
     9: ("nrv_predict_reads_raw_stats", "nrv_reads_raw_stats_begin", (_STATS, _CALLS), False),
@@ -94,6 +97,7 @@ _RAW_FORMS = {
     14: ("nrv_revise_reads_raw_report", "nrv_revise_reads_raw_report_begin", (_STATS, _MERGE, _REPORT), True),
     16: ("nrv_revise_reads_raw_edits", "nrv_revise_reads_raw_edits_begin", (_STATS, _MERGE, _REPORT, _EDITS), True),
     20: ("nrv_revise_reads_raw_records", "nrv_revise_reads_raw_records_begin", (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS), True),
+    22: ("nrv_revise_reads_raw_profile", "nrv_revise_reads_raw_profile_begin", (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS, _PROFILE), True),
 }
 _PACK_RECORDS_T = [C.c_void_p, _U8P, _U8P, _I64P, C.c_int, _U8P, _I64P, _U8P, _I64P]         # nrv_pack_records
 _READS_HEAD_T = _RAW_HEAD_T[:4] + [C.c_int64, C.POINTER(_ReadDesc), C.c_int]     # nrv_segment_reads, nrv_read_stats: no features
@@ -180,8 +184,10 @@ def load_library(path: Optional[str] = None):
     have_report = hasattr(lib, "nrv_merge_calls_report")   # by presence: NRV_LIB may name an older build of the same ABI
     have_edits = hasattr(lib, "nrv_merge_calls_edits")
     have_records = hasattr(lib, "nrv_pack_records")
+    have_profile = hasattr(lib, "nrv_merge_calls_profile")
     for sync, begin, blocks, _ in _RAW_FORMS.values():  # (every restype is ctypes' default, int: the nrv_* status)
-        if (have_records or _RECORDS not in blocks) and (have_edits or _EDITS not in blocks) and (have_report or _REPORT not in blocks):
+        if (have_profile or _PROFILE not in blocks) and (have_records or _RECORDS not in blocks) \
+                and (have_edits or _EDITS not in blocks) and (have_report or _REPORT not in blocks):
             getattr(lib, sync).argtypes = _RAW_HEAD_T + [t for types, _ in blocks for t in types]
             getattr(lib, begin).argtypes = getattr(lib, sync).argtypes + [C.POINTER(C.c_int)]
     lib.nrv_merge_calls.argtypes = _MERGE_CALLS_T
@@ -191,6 +197,8 @@ def load_library(path: Optional[str] = None):
         lib.nrv_merge_calls_edits.argtypes = _MERGE_CALLS_T + _REPORT[0] + _EDITS[0]
     if have_records:
         lib.nrv_pack_records.argtypes = _PACK_RECORDS_T
+    if have_profile:
+        lib.nrv_merge_calls_profile.argtypes = _MERGE_CALLS_T + _PROFILE[0]
     lib.nrv_reads_raw_end.argtypes = [vp, C.c_int]
     lib.nrv_segment_reads.argtypes = _READS_HEAD_T + [fp]
     lib.nrv_read_stats.argtypes = _READS_HEAD_T + [_I32P, _DP, _DP, _DP, _DP, fp]
@@ -463,15 +471,44 @@ class Reviser:
         return packed + (nm, name_off, np.empty(max(cap, 1), np.uint8), np.zeros(nr + 1, np.int64))
 
     @staticmethod
+    def with_device_profile(packed, q_thr=None):
+        """A `with_device_merge` (12 elements), `with_device_report` (14), `with_device_edits` (16) or `with_device_records` (20)
+        tuple whose call also returns the per-read quality and base profile (include/nanorev.h
+        nrv_revise_reads_raw_profile_begin; hoststage.read_profile is the definition).  q_thr: the 39 thresholds the profile's
+        qualities are computed with (default: cli.phred_thresholds()) - its own, whether the call writes a quality or not.
+        `run_packed_raw` / `begin_packed_raw` + `end_packed_raw` then return (seq, qual | None, off, report | None,
+        edits[:total] | None, edit_off | None, blob[:rec_off[-1]] | None, rec_off | None, profile uint64[n_reads][48]): what
+        the tuple's own call returns, None for the blocks it does not carry, and the profile last."""
+        if len(packed) not in (12, 14, 16, 20):
+            raise ValueError("with_device_profile extends a with_device_merge, a with_device_report, a with_device_edits or a "
+                             "with_device_records tuple")
+        packed = tuple(packed)
+        if len(packed) == 12:
+            packed += (0.0, None)
+        if len(packed) == 14:
+            packed += (None, None)
+        if len(packed) == 16:
+            packed += (None, None, None, None)
+        if q_thr is None:
+            from .cli import phred_thresholds
+            q_thr = phred_thresholds()
+        thr = np.ascontiguousarray(q_thr, dtype=np.float32).reshape(-1)
+        if thr.size != 39:
+            raise ValueError("q_thr must have 39 entries")
+        return packed + (thr, np.zeros((packed[4], PROFILE_COLS), np.uint64))
+
+    @staticmethod
     def _trim_merged(out):
         seq, qual, off = out[:3]
         total = int(off[-1])
-        more = tuple(out[3:])
+        more, tail = tuple(out[3:]), ()
+        if len(more) == 6:                            # (..., profile): a `with_device_profile` call; blocks it does not carry are None
+            more, tail = more[:5], more[5:]
         if len(more) in (3, 5) and more[1] is not None:   # (report | None, edits, edit_off, ...): the used prefix of the records
             more = (more[0], more[1][:int(more[2][-1])], more[2]) + more[3:]
-        if len(more) == 5:                            # (..., blob, rec_off): the used prefix of the blob
+        if len(more) == 5 and more[3] is not None:    # (..., blob, rec_off): the used prefix of the blob
             more = more[:3] + (more[3][:int(more[4][-1])], more[4])
-        return ((seq[:total] if seq is not None else None), (qual[:total] if qual is not None else None), off) + more
+        return ((seq[:total] if seq is not None else None), (qual[:total] if qual is not None else None), off) + more + tail
 
     def _raw_head(self, packed):
         """The leading C arguments every raw-read entry point shares: handle, raw, n_raw, starts, feat, N, descs, n_reads."""
@@ -482,20 +519,20 @@ class Reviser:
         """One call of the raw-read family for a packed tuple of any form (`_RAW_FORMS`): its synchronous entry point, or its
         *_begin with the ticket behind the same arguments.  Returns (ticket number or None, outputs, merged)."""
         if len(packed) not in _RAW_FORMS:
-            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14, 16 or 20 elements, not {len(packed)}")
+            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14, 16, 20 or 22 elements, not {len(packed)}")
         sync, beg, blocks, merged = _RAW_FORMS[len(packed)]
-        if not hasattr(self._lib, beg):               # the report, edits and records pairs are found by presence
+        if not hasattr(self._lib, beg):               # the report, edits, records and profile pairs are found by presence
             raise NrvError(-1, f"this build of libnanorev_hip.so has no {beg}")
         args = self._raw_head(packed)
         for types, pick in blocks:
             args += _marshal(pick(packed), types)
         t = C.c_int(-1)
         self._check(getattr(self._lib, beg)(*args, C.byref(t)) if begin else getattr(self._lib, sync)(*args))
-        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) + tuple(packed[18:20]) if merged else packed[6]), merged
+        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) + tuple(packed[18:20]) + tuple(packed[21:22]) if merged else packed[6]), merged
 
     def run_packed_raw(self, packed):
         """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared (or `with_device_stats` /
-        `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` extended)."""
+        `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` extended)."""
         _, out, merged = self._raw_call(packed, False)
         return self._trim_merged(out) if merged else out
 
@@ -509,7 +546,8 @@ class Reviser:
         """Second half: waits for the call `ticket` names and returns its (p1, p2, a1, a2) - or, for a `with_device_merge`
         call, its (seq, qual, off), with the report behind them for a `with_device_report` call, (report | None, edits,
         edit_off) for a `with_device_edits` call and (report | None, edits | None, edit_off | None, blob, rec_off) - the blob
-        trimmed to rec_off[-1] - for a `with_device_records` call."""
+        trimmed to rec_off[-1] - for a `with_device_records` call; a `with_device_profile` call returns the latter with the
+        profile behind it."""
         t, out = ticket[:2]
         self._check(self._lib.nrv_reads_raw_end(self._h, t))
         return self._trim_merged(out) if len(ticket) == 3 else out
@@ -611,6 +649,25 @@ class Reviser:
         edits, edit_off = np.zeros(max(n, 1), EDIT_DTYPE), np.zeros(ins[1].size + 1, np.int64)
         more = _marshal((REPORT_TIE_EPS if tie_eps is None else tie_eps, rep, edits.ctypes.data, edit_off), _REPORT[0] + _EDITS[0])
         return self._merge_call("nrv_merge_calls_edits", *ins, *more) + (rep, edits[:int(edit_off[-1])], edit_off)
+
+    def merge_calls_profile_device(self, bases, ev_len, a1, a2, p1, p2, q_thr=None, prof_thr=None):
+        """`merge_calls_device` with the per-read quality and base profile (nrv_merge_calls_profile): p1 / p2 are required, q_thr
+        may be None (a FASTA merge whose profile is still filled), prof_thr defaults to cli.phred_thresholds().  Returns
+        (seq, qual | None, off, profile uint64[n_reads][48]) - the profile is hoststage.read_profile's, bit for bit."""
+        if not hasattr(self._lib, "nrv_merge_calls_profile"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_merge_calls_profile")
+        if p1 is None or p2 is None:
+            raise ValueError("the profile needs p1 / p2")
+        if prof_thr is None:
+            from .cli import phred_thresholds
+            prof_thr = phred_thresholds()
+        pthr = np.ascontiguousarray(prof_thr, dtype=np.float32).reshape(-1)
+        ins = self._merge_inputs(bases, ev_len, a1, a2, p1, p2, q_thr, True)
+        n, (q1, q2, thr) = ins[2].size, ins[4:]
+        if q1.shape[0] != n or q2.shape[0] != n or pthr.size != 39 or (thr is not None and thr.size != 39):
+            raise ValueError("p1 / p2 / q_thr / prof_thr do not match")
+        prof = np.zeros((ins[1].size, PROFILE_COLS), np.uint64)
+        return self._merge_call("nrv_merge_calls_profile", *ins, *_marshal((pthr, prof), _PROFILE[0])) + (prof,)
 
     def pack_records_device(self, names, seq, qual, off, blob=None):
         """The device-side record layout alone (nrv_pack_records) on merged reads the host supplies: the arguments and the
