@@ -476,6 +476,59 @@ struct DevModel {
   int C;
 };
 
+// ---- a merged raw-read call (nrv_revise_reads_raw*_begin; nrv_merge_calls* is its test twin) -------------------------------
+// The merged block of a call of N events, n windows, n_reads reads - offsets into one device allocation:
+//   [off i64 x (n_reads + 1) | seq | qual | report u64 x n_reads x 24 | edit_off i64 x (n_reads + 1) | rec_off i64 x (n_reads + 1) |
+//    profile u64 x n_reads x 48]      what comes back in one copy of `dl` bytes, mirrored in page-locked memory (nrv_merge.h,
+//                                     nrv_report.h, nrv_edits.h, nrv_pack.h, nrv_profile.h); the report, edit_off, rec_off and
+//                                     the profile only where asked for - without them the layout is the merge's own.  A records
+//                                     call that hands back neither seq nor qual leaves those two on the device
+//   [rec u32 x N | tile u64]          the merge kernels' scratch
+//   [edits nrv_edit x n | etile u64]  the edit records, fetched by their used prefix in a copy of their own, and their scratch;
+//                                     only where asked for
+//   [blob]                            the FASTA / FASTQ records of blob_cap bytes, fetched by their used prefix like the edit
+//                                     records; only where asked for
+// Every part is 256-byte aligned.
+struct MergeLayout { size_t seq, qual, rep, eoff, roff, prof, rec, tile, edits, etile, blob, dl, bytes; };
+
+// What a merged call reads besides the raw reads.  Consumed inside _begin: the caller's pointers are dead once it returns, so
+// nothing that outlives _begin keeps one (the slot keeps the VALUES of both threshold sets for the re-run of nrv_reads_raw_end)
+struct MergeIn {
+  const uint8_t* bases = nullptr;
+  const float* q_thr = nullptr;         // null: FASTA
+  const uint8_t* names = nullptr;       // nrv_revise_reads_raw_records_begin
+  const int64_t* name_off = nullptr;
+  const float* prof_thr = nullptr;      // nrv_revise_reads_raw_profile_begin: its own 39 thresholds
+};
+// What a merged call hands back and where: the caller keeps these arrays alive until _end.  A null pointer: not asked for.
+// The entry points fill it (and MergeIn, and RawIn) as a positional aggregate: the ORDER of the members is relied on
+struct MergeOut {
+  uint8_t *seq = nullptr, *qual = nullptr;
+  int64_t* off = nullptr;               // every merged call has it: null = not a merged call
+  uint64_t* report = nullptr;           // [n_reads][24], and the near-tie margin
+  float tie_eps = 0.f;
+  nrv_edit* edits = nullptr;            // [max(N - T, 0)] and [n_reads + 1]; edit_off decides
+  int64_t* edit_off = nullptr;
+  uint8_t* blob = nullptr;              // the records and [n_reads + 1]; rec_off decides
+  int64_t* rec_off = nullptr;
+  uint64_t* profile = nullptr;          // [n_reads][48]
+};
+// Where a merged call's inputs lie on the device, and its merged block
+struct MergeView {
+  const SegRead* reads;
+  int n_reads;
+  int64_t N;
+  const unsigned char* bases;
+  const signed char *a1, *a2;
+  const float *p1, *p2;                  // both null: the call has no rows (nrv_merge_calls* without them)
+  const long long* name_off;             // records only
+  const unsigned char* names;
+  char* blk;                             // MergeLayout offsets count from here
+};
+// The quality rule: characters get a Phred quality when there are thresholds and somebody reads it - the caller's qual or the
+// FASTQ records (nrv_merge_calls* has no records: q_thr && qual there)
+static bool wants_quality(const float* q_thr, const MergeOut& o) { return q_thr && (o.qual || o.rec_off); }
+
 }  // namespace
 
 struct nrv_handle {
@@ -546,43 +599,16 @@ struct nrv_handle {
     size_t off_starts = 0, off_reads = 0, off_feat = 0, rows = 0;
     size_t off_aux = 0;                                                   // nrv_reads_raw_stats_begin: [.. | StatAux per read] behind feat
     unsigned* d_stat = nullptr; size_t cap_stat = 0;                      // ... and its scratch (min / max, histograms: nrv_stats.h)
-    // nrv_revise_reads_raw_begin (nrv_merge.h): the call's bases [.. | bases u8] at the end of d_in, and a merged-output block of
-    // the slot's own, [off i64 x (n_reads + 1) | seq | qual] - the ONLY part such a call downloads (with the 64-byte counter of
-    // d_out) - followed on the device by the kernels' scratch [rec u32 x N | tile u64]
-    size_t off_bases = 0;
+    // a merged call: its bases and, for records, its names [.. | bases u8 | name_off i64 x (n_reads + 1) | names u8] at the end of
+    // d_in; the merged block (MergeLayout) with its page-locked mirror - the ONLY part such a call downloads, with the 64-byte
+    // counter of d_out; where the results go; and the values the re-run of nrv_reads_raw_end needs once the inputs are gone
+    size_t off_bases = 0, off_noff = 0, off_names = 0;
     char* d_mrg = nullptr; char* pin_mrg = nullptr; size_t cap_mrg = 0;
-    size_t m_seq = 0, m_qual = 0, m_rec = 0, m_tile = 0, m_dl = 0;        // offsets into d_mrg; m_dl = bytes that come back
-    bool merge = false, want_q = false;
-    float thr[kPhredSteps] = {0};
-    // nrv_revise_reads_raw_report_begin (nrv_report.h): the report block u64 x n_reads x 24 behind qual, inside the part that
-    // comes back (m_dl grows by it; without a report the layout is the merge's own)
-    size_t m_rep = 0;
-    bool report = false;
-    float tie_eps = 0.f;
-    uint64_t* rep_out = nullptr;
-    // nrv_revise_reads_raw_edits_begin (nrv_edits.h): edit_off i64 x (n_reads + 1) behind the report, the last part that comes
-    // back with the block (m_dl grows by it); the records nrv_edit x n and their scratch etile u64 x tiles behind rec / tile.  The
-    // used prefix of the records is fetched by nrv_reads_raw_end in a copy of its own, on edit_stream
-    size_t m_eoff = 0, m_edits = 0, m_etile = 0;
-    bool edits = false;
-    nrv_edit* edits_out = nullptr;
-    int64_t* eoff_out = nullptr;
-    // nrv_revise_reads_raw_records_begin (nrv_pack.h): the names [.. | name_off i64 x (n_reads + 1) | names u8] behind bases in
-    // d_in; rec_off i64 x (n_reads + 1) behind edit_off, the last part that comes back with the block (m_dl grows by it); the blob
-    // of blob_cap bytes behind the merge / edits scratch, its used prefix fetched by nrv_reads_raw_end like the edit records.  A
-    // call that hands back neither seq nor qual leaves them on the device: [off] and [report | edit_off | rec_off] come back
-    size_t off_noff = 0, off_names = 0, m_roff = 0, m_blob = 0, m_bytes = 0, blob_cap = 0;
-    bool records = false;
-    uint8_t* blob_out = nullptr;
-    int64_t* roff_out = nullptr;
-    // nrv_revise_reads_raw_profile_begin (nrv_profile.h): the profile block u64 x n_reads x 48 behind rec_off, the last part that
-    // comes back with the block (m_dl grows by it), and the call's own 39 thresholds
-    size_t m_prof = 0;
-    bool profile = false;
-    float prof_thr[kPhredSteps] = {0};
-    uint64_t* prof_out = nullptr;
-    uint8_t *seq = nullptr, *qual = nullptr;
-    int64_t* off = nullptr;
+    MergeLayout m = {};
+    MergeOut out;
+    bool want_q = false;
+    float thr[kPhredSteps] = {0}, prof_thr[kPhredSteps] = {0};
+    size_t blob_cap = 0;
     int64_t N = 0, n = 0;
     int n_reads = 0;
     float *p1 = nullptr, *p2 = nullptr;
@@ -1547,6 +1573,45 @@ static int for_groups(nrv_handle* h, int64_t n, F&& body) {
   return rc;
 }
 
+// a synchronous entry point of the raw-read family: its _begin, then nrv_reads_raw_end
+template <class Begin>
+static int begin_then_end(nrv_handle* h, Begin begin) {
+  int t = -1;
+  const int rc = begin(&t);
+  return rc ? rc : nrv_reads_raw_end(h, t);
+}
+// What a merged call hands back, from `head`, the host's copy of the first m.dl bytes of the block v.blk: the three totals are
+// checked against what the block can hold, the blocks copied out, and the used prefix of the edit records and of the blob fetched
+// with fetch(dst, offset into the block, bytes) -> status, the caller's way of reading the device block.  who names the entry point
+// in the error texts, who_edits in the edit list's (nrv_merge_calls_edits has a text of its own)
+template <class Fetch>
+static int merged_collect(nrv_handle* h, const char* who, const char* who_edits, const char* head, const MergeView& v,
+                          const MergeLayout& m, const MergeOut& o, bool want_q, size_t blob_cap, Fetch fetch) {
+  const int64_t n = v.N - h->T > 0 ? v.N - h->T : 0;
+  const size_t nb = ((size_t)v.n_reads + 1) * 8;
+  const int64_t total = ((const int64_t*)head)[v.n_reads];
+  if (total < 0 || total > v.N + n) { h->err = std::string(who) + ": merged block out of range"; return NRV_E_HIP; }
+  memcpy(o.off, head, nb);
+  if (o.seq) memcpy(o.seq, head + m.seq, (size_t)total);
+  if (want_q && o.qual) memcpy(o.qual, head + m.qual, (size_t)total);
+  if (o.report) memcpy(o.report, head + m.rep, (size_t)v.n_reads * kReportCols * 8);
+  if (o.profile) memcpy(o.profile, head + m.prof, (size_t)v.n_reads * kProfileCols * 8);
+  int rc = NRV_OK;
+  if (o.edit_off) {
+    const int64_t n_ed = ((const int64_t*)(head + m.eoff))[v.n_reads];
+    if (n_ed < 0 || n_ed > n) { h->err = std::string(who_edits) + ": edit list out of range"; return NRV_E_HIP; }
+    memcpy(o.edit_off, head + m.eoff, nb);
+    if (n_ed > 0 && (rc = fetch(o.edits, m.edits, (size_t)n_ed * sizeof(nrv_edit)))) return rc;
+  }
+  if (o.rec_off) {
+    const int64_t n_b = ((const int64_t*)(head + m.roff))[v.n_reads];
+    if (n_b < 0 || (uint64_t)n_b > blob_cap) { h->err = std::string(who) + ": records out of range"; return NRV_E_HIP; }
+    memcpy(o.rec_off, head + m.roff, nb);
+    if (n_b > 0 && (rc = fetch(o.blob, m.blob, (size_t)n_b))) return rc;
+  }
+  return NRV_OK;
+}
+
 extern "C" {
 
 int nrv_predict_device(nrv_handle* h, const float* d_signal, const float* d_read, int64_t n,
@@ -2050,29 +2115,24 @@ static void records_host(const uint8_t* seq, const uint8_t* qual, const int64_t*
   }
   rec_off[n_reads] = p;
 }
-// layout of a merged block for N events, n windows, n_reads reads: [off | seq | qual | report | edit_off | rec_off | profile] (what comes
-// back; the report, edit_off, rec_off and profile only where asked for) + [rec | tile] (scratch) + [edits | etile] (the edit records,
-// fetched by their used prefix, and their scratch; only where asked for) + [blob] (the FASTA / FASTQ records, fetched by their
-// used prefix; only where asked for)
-struct MergeLayout { size_t seq, qual, rep, eoff, roff, prof, rec, tile, edits, etile, blob, dl, bytes; };
-static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, bool report = false, bool edits = false, bool records = false,
-                                size_t blob_cap = 0, bool profile = false) {
+// the merged block (MergeLayout) of a call that hands back what `o` asks for
+static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, const MergeOut& o, size_t blob_cap) {
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   MergeLayout m;
   const size_t cap = (size_t)(N + n), tiles = (size_t)((N + kMergeTile - 1) / kMergeTile);
   m.seq = up(((size_t)n_reads + 1) * 8);
   m.qual = m.seq + up(cap);
   m.rep = m.qual + up(cap);
-  m.eoff = m.rep + (report ? up((size_t)n_reads * kReportCols * 8) : 0);
-  m.roff = m.eoff + (edits ? up(((size_t)n_reads + 1) * 8) : 0);
-  m.prof = m.roff + (records ? up(((size_t)n_reads + 1) * 8) : 0);
-  m.dl = m.prof + (profile ? up((size_t)n_reads * kProfileCols * 8) : 0);
+  m.eoff = m.rep + (o.report ? up((size_t)n_reads * kReportCols * 8) : 0);
+  m.roff = m.eoff + (o.edit_off ? up(((size_t)n_reads + 1) * 8) : 0);
+  m.prof = m.roff + (o.rec_off ? up(((size_t)n_reads + 1) * 8) : 0);
+  m.dl = m.prof + (o.profile ? up((size_t)n_reads * kProfileCols * 8) : 0);
   m.rec = m.dl;
   m.tile = m.rec + up((size_t)N * 4);
   m.edits = m.tile + up(tiles * 8);
-  m.etile = m.edits + (edits ? up((size_t)n * sizeof(nrv_edit)) : 0);
-  m.blob = m.etile + (edits ? up(tiles * 8) : 0);
-  m.bytes = m.blob + (records ? up(blob_cap) : 0);
+  m.etile = m.edits + (o.edit_off ? up((size_t)n * sizeof(nrv_edit)) : 0);
+  m.blob = m.etile + (o.edit_off ? up(tiles * 8) : 0);
+  m.bytes = m.blob + (o.rec_off ? up(blob_cap) : 0);
   return m;
 }
 // No window at all (N <= T): the reads come back as they are, on the host
@@ -2106,92 +2166,97 @@ static void profile_nothing(const uint8_t* bases, const nrv_read_desc* reads, in
     }
   }
 }
-struct MergeReq {             // what nrv_revise_reads_raw_begin adds to a raw-read call
-  const uint8_t* bases;
-  const float* q_thr;
-  uint8_t *seq, *qual;
-  int64_t* off;
-  uint64_t* report = nullptr; // nrv_revise_reads_raw_report_begin: [n_reads][24], and the near-tie margin
-  float tie_eps = 0.f;
-  nrv_edit* edits = nullptr;  // nrv_revise_reads_raw_edits_begin: [max(N - T, 0)] and [n_reads + 1]
-  int64_t* edit_off = nullptr;
-  const uint8_t* names = nullptr;     // nrv_revise_reads_raw_records_begin: the names, and where the records go
-  const int64_t* name_off = nullptr;
-  uint8_t* blob = nullptr;
-  int64_t* rec_off = nullptr;
-  const float* prof_thr = nullptr;    // nrv_revise_reads_raw_profile_begin: its own 39 thresholds and [n_reads][48]
-  uint64_t* profile = nullptr;
-};
-static MergeArgs slot_merge_args(const nrv_handle* h, const nrv_handle::RawSlot& sl) {
-  char* const d = sl.d_out + 64;
+// ... and everything a merged call asks for, for both callers that can meet N <= T
+static void merged_nothing(const MergeIn& in, const MergeOut& o, const nrv_read_desc* reads, int n_reads, int64_t N) {
+  merge_nothing(in.bases, reads, n_reads, N, o.seq, in.q_thr ? o.qual : nullptr, o.off);
+  if (o.report) report_nothing(reads, n_reads, wants_quality(in.q_thr, o), o.report);
+  if (o.edit_off) memset(o.edit_off, 0, ((size_t)n_reads + 1) * 8);   // no window, no record
+  if (o.rec_off) records_host(in.bases, nullptr, o.off, n_reads, in.names, in.name_off, in.q_thr != nullptr, o.blob, o.rec_off);
+  if (o.profile) profile_nothing(in.bases, reads, n_reads, o.profile);
+}
+
+// The kernels of a merged call behind whatever produced v.a1 / a2 / p1 / p2 on the compute stream: the merge, then what `o` asks
+// for - report, edit list, records, profile - each reading what the merge left.  q_thr: the thresholds of the quality (null:
+// none is written); the merge reads the rows only for a quality, the report and the edits whenever there are rows, the profile
+// always.  A second pass over the same block (the re-run of nrv_reads_raw_end) counts nothing twice: report_enqueue and
+// profile_enqueue zero their blocks in stream order, the edit and record kernels store plainly into every word that is read back
+static int merged_enqueue(nrv_handle* h, const MergeView& v, const MergeLayout& m, const MergeOut& o, const float* q_thr,
+                          const float* prof_thr, size_t blob_cap) {
+  const bool want_q = q_thr != nullptr;
   MergeArgs a;
-  a.reads = (const SegRead*)(sl.d_in + sl.off_reads);
-  a.n_reads = sl.n_reads; a.T = h->T; a.N = sl.N;
-  a.bases = (const unsigned char*)(sl.d_in + sl.off_bases);
-  a.a1 = (const signed char*)(d + sl.rows * 44); a.a2 = (const signed char*)(d + sl.rows * 45);
-  a.p1 = sl.want_q ? (const float*)d : nullptr; a.p2 = sl.want_q ? (const float*)(d + sl.rows * 24) : nullptr;
-  a.rec = (unsigned*)(sl.d_mrg + sl.m_rec); a.tile = (unsigned long long*)(sl.d_mrg + sl.m_tile);
-  a.off = (long long*)sl.d_mrg; a.seq = (unsigned char*)(sl.d_mrg + sl.m_seq);
-  a.qual = sl.want_q ? (unsigned char*)(sl.d_mrg + sl.m_qual) : nullptr;
-  memcpy(a.thr, sl.thr, sizeof a.thr);
-  return a;
+  a.reads = v.reads; a.n_reads = v.n_reads; a.T = h->T; a.N = v.N;
+  a.bases = v.bases; a.a1 = v.a1; a.a2 = v.a2;
+  a.p1 = want_q ? v.p1 : nullptr; a.p2 = want_q ? v.p2 : nullptr;
+  a.rec = (unsigned*)(v.blk + m.rec); a.tile = (unsigned long long*)(v.blk + m.tile);
+  a.off = (long long*)v.blk; a.seq = (unsigned char*)(v.blk + m.seq);
+  a.qual = want_q ? (unsigned char*)(v.blk + m.qual) : nullptr;
+  memset(a.thr, 0, sizeof a.thr);
+  if (want_q) memcpy(a.thr, q_thr, sizeof a.thr);
+  int rc = merge_enqueue(h, a);
+  if (!rc && o.report) rc = report_enqueue(h, report_args(a, v.p1, v.p2, want_q, o.tie_eps, v.blk + m.rep));
+  if (!rc && o.edit_off) rc = edits_enqueue(h, edits_args(a, v.p1, v.p2, want_q, v.blk + m.etile, v.blk + m.eoff, v.blk + m.edits));
+  if (!rc && o.rec_off) {
+    PackArgs k;
+    k.n_reads = v.n_reads; k.fastq = want_q ? 1 : 0;
+    k.off = a.off; k.name_off = v.name_off; k.names = v.names;
+    k.seq = a.seq; k.qual = (const unsigned char*)(v.blk + m.qual);
+    k.rec_off = (long long*)(v.blk + m.roff); k.blob = (unsigned char*)(v.blk + m.blob);
+    k.cap = blob_cap;
+    rc = pack_enqueue(h, k);
+  }
+  if (!rc && o.profile) rc = profile_enqueue(h, profile_args(a, v.p1, v.p2, prof_thr, v.blk + m.prof));
+  return rc;
 }
-static ReportArgs slot_report_args(const nrv_handle* h, const nrv_handle::RawSlot& sl) {
-  char* const d = sl.d_out + 64;                               // p1 / p2 are in the output block whether a quality is wanted or not
-  return report_args(slot_merge_args(h, sl), (const float*)d, (const float*)(d + sl.rows * 24), sl.want_q, sl.tie_eps,
-                     sl.d_mrg + sl.m_rep);
+// the merged part of a slot's call
+static MergeView slot_view(const nrv_handle::RawSlot& sl) {
+  const char* const d = sl.d_out + 64;   // p1 / p2 are in the output block whether a quality is wanted or not
+  return MergeView{(const SegRead*)(sl.d_in + sl.off_reads), sl.n_reads, sl.N, (const unsigned char*)(sl.d_in + sl.off_bases),
+                   (const signed char*)(d + sl.rows * 44), (const signed char*)(d + sl.rows * 45), (const float*)d,
+                   (const float*)(d + sl.rows * 24), (const long long*)(sl.d_in + sl.off_noff),
+                   (const unsigned char*)(sl.d_in + sl.off_names), sl.d_mrg};
 }
-static EditsArgs slot_edits_args(const nrv_handle* h, const nrv_handle::RawSlot& sl) {
-  char* const d = sl.d_out + 64;                               // p1 / p2: as for the report
-  return edits_args(slot_merge_args(h, sl), (const float*)d, (const float*)(d + sl.rows * 24), sl.want_q,
-                    sl.d_mrg + sl.m_etile, sl.d_mrg + sl.m_eoff, sl.d_mrg + sl.m_edits);
-}
-static ProfileArgs slot_profile_args(const nrv_handle* h, const nrv_handle::RawSlot& sl) {
-  char* const d = sl.d_out + 64;                               // p1 / p2: as for the report
-  return profile_args(slot_merge_args(h, sl), (const float*)d, (const float*)(d + sl.rows * 24), sl.prof_thr, sl.d_mrg + sl.m_prof);
-}
-static PackArgs slot_pack_args(const nrv_handle::RawSlot& sl) {
-  PackArgs a;
-  a.n_reads = sl.n_reads; a.fastq = sl.want_q ? 1 : 0;
-  a.off = (const long long*)sl.d_mrg;
-  a.name_off = (const long long*)(sl.d_in + sl.off_noff); a.names = (const unsigned char*)(sl.d_in + sl.off_names);
-  a.seq = (const unsigned char*)(sl.d_mrg + sl.m_seq); a.qual = (const unsigned char*)(sl.d_mrg + sl.m_qual);
-  a.rec_off = (long long*)(sl.d_mrg + sl.m_roff); a.blob = (unsigned char*)(sl.d_mrg + sl.m_blob);
-  a.cap = sl.blob_cap;
-  return a;
-}
-// what comes back of a merged block, on stream s: all of [0, m_dl) - or, for a records call that hands back neither seq nor qual,
-// the parts in front of and behind them (the profile lies behind rec_off, inside m_dl)
-static int merged_download(nrv_handle* h, nrv_handle::RawSlot& sl, hipStream_t s) {
-  const bool skip = sl.records && !sl.seq && !sl.qual;
-  const size_t head = skip ? sl.m_seq : sl.m_dl;
-  HIPCHK(h, hipMemcpyAsync(sl.pin_mrg, sl.d_mrg, head, hipMemcpyDeviceToHost, s));
-  if (skip) HIPCHK(h, hipMemcpyAsync(sl.pin_mrg + sl.m_rep, sl.d_mrg + sl.m_rep, sl.m_dl - sl.m_rep, hipMemcpyDeviceToHost, s));
+// What comes back of a slot's call, on stream s.  A plain call: its output block.  A merged call: the counter and the merged block,
+// all of [0, m.dl) - or, for a records call that hands back neither seq nor qual, the parts in front of and behind them; p1 / p2 /
+// a1 / a2 stay on the device
+static int slot_download(nrv_handle* h, nrv_handle::RawSlot& sl, hipStream_t s) {
+  if (!sl.out.off) {
+    HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64 + sl.rows * kOutBytes, hipMemcpyDeviceToHost, s));
+    return NRV_OK;
+  }
+  HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64, hipMemcpyDeviceToHost, s));
+  const MergeLayout& m = sl.m;
+  const bool skip = sl.out.rec_off && !sl.out.seq && !sl.out.qual;
+  HIPCHK(h, hipMemcpyAsync(sl.pin_mrg, sl.d_mrg, skip ? m.seq : m.dl, hipMemcpyDeviceToHost, s));
+  if (skip) HIPCHK(h, hipMemcpyAsync(sl.pin_mrg + m.rep, sl.d_mrg + m.rep, m.dl - m.rep, hipMemcpyDeviceToHost, s));
   return NRV_OK;
 }
 
-// nrv_reads_raw_begin (last_dur == nullptr: today's call, to the byte), nrv_reads_raw_stats_begin and (mr != nullptr)
-// nrv_revise_reads_raw_begin
-static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
-                     const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
-                     const int32_t* last_dur, const uint8_t* on_device,
-                     float* p1, float* p2, int8_t* a1, int8_t* a2, int* ticket, const MergeReq* mr = nullptr) {
+// the arguments every raw-read entry point shares, and the two of the device statistics (filled positionally: keep the order)
+struct RawIn {
+  const int16_t* raw; int64_t n_raw; const int32_t* starts; const float* feat_ev; int64_t N; const nrv_read_desc* reads; int n_reads;
+  const int32_t* last_dur = nullptr; const uint8_t* on_device = nullptr;
+};
+// nrv_reads_raw_begin (last_dur == nullptr: today's call, to the byte), nrv_reads_raw_stats_begin and (mr != nullptr: the inputs,
+// with mo, what to hand back) nrv_revise_reads_raw_begin and the forms behind it
+static int raw_begin(nrv_handle* h, const RawIn& in, float* p1, float* p2, int8_t* a1, int8_t* a2, int* ticket,
+                     const MergeIn* mr = nullptr, const MergeOut* mo = nullptr) {
   int rc = check_handle(h);
   if (rc) return rc;
+  const auto [raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device] = in;
   if (!ticket) { h->err = "nrv_reads_raw_begin: null ticket"; return NRV_E_INVALID; }
   if ((rc = raw_check(h, raw, n_raw, starts, feat_ev, N, reads, n_reads))) return rc;
-  if (mr && (!mr->off || (N > 0 && (!mr->bases || (!mr->seq && !mr->rec_off))) || N >= ((int64_t)1 << 31))) {
+  if (mr && (!mo->off || (N > 0 && (!mr->bases || (!mo->seq && !mo->rec_off))) || N >= ((int64_t)1 << 31))) {
     h->err = "nrv_revise_reads_raw_begin: null bases / seq / off (or 2^31 events and more)";
     return NRV_E_INVALID;
   }
-  if (mr && mr->edit_off && N > h->T && !mr->edits) { h->err = "nrv_revise_reads_raw_edits_begin: null edits"; return NRV_E_INVALID; }
-  const bool records = mr != nullptr && mr->rec_off != nullptr;
-  const bool rec_fastq = records && mr->q_thr != nullptr;       // FASTQ or FASTA: by q_thr, whether qual is handed back or not
+  if (mr && mo->edit_off && N > h->T && !mo->edits) { h->err = "nrv_revise_reads_raw_edits_begin: null edits"; return NRV_E_INVALID; }
+  const bool records = mr != nullptr && mo->rec_off != nullptr;
   size_t blob_cap = 0;
   if (records) {
     if (!names_ok(mr->names, mr->name_off, n_reads)) { h->err = "nrv_revise_reads_raw_records_begin: null names / name_off, or offsets that do not ascend from 0"; return NRV_E_INVALID; }
-    blob_cap = blob_capacity(N, N - h->T > 0 ? N - h->T : 0, n_reads, mr->name_off[n_reads], rec_fastq);
-    if (blob_cap > 0 && !mr->blob) { h->err = "nrv_revise_reads_raw_records_begin: null blob"; return NRV_E_INVALID; }
+    // FASTQ or FASTA: by q_thr, whether qual is handed back or not
+    blob_cap = blob_capacity(N, N - h->T > 0 ? N - h->T : 0, n_reads, mr->name_off[n_reads], mr->q_thr != nullptr);
+    if (blob_cap > 0 && !mo->blob) { h->err = "nrv_revise_reads_raw_records_begin: null blob"; return NRV_E_INVALID; }
     if (blob_cap >= ((size_t)1 << 32)) { h->err = "nrv_revise_reads_raw_records_begin: records of 4 GiB and more in one call"; return NRV_E_INVALID; }
   }
   const bool with_stats = last_dur != nullptr || on_device != nullptr;
@@ -2205,17 +2270,9 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
   sl.N = N; sl.n = N - T > 0 ? N - T : 0; sl.n_reads = n_reads;
   sl.p1 = p1; sl.p2 = p2; sl.a1 = a1; sl.a2 = a2;
   *ticket = k;
-  sl.merge = mr != nullptr;
-  sl.report = mr != nullptr && mr->report != nullptr;
-  sl.edits = mr != nullptr && mr->edit_off != nullptr;
-  sl.records = records;
-  sl.profile = mr != nullptr && mr->profile != nullptr;
+  sl.out = mr ? *mo : MergeOut{};
   if (sl.n == 0) {                                              // nothing to compute: _end returns at once
-    if (mr) merge_nothing(mr->bases, reads, n_reads, N, mr->seq, mr->q_thr ? mr->qual : nullptr, mr->off);
-    if (sl.report) report_nothing(reads, n_reads, mr->q_thr != nullptr && (mr->qual != nullptr || records), mr->report);
-    if (sl.edits) memset(mr->edit_off, 0, ((size_t)n_reads + 1) * 8);   // no window, no record
-    if (records) records_host(mr->bases, nullptr, mr->off, n_reads, mr->names, mr->name_off, rec_fastq, mr->blob, mr->rec_off);
-    if (sl.profile) profile_nothing(mr->bases, reads, n_reads, mr->profile);
+    if (mr) merged_nothing(*mr, sl.out, reads, n_reads, N);
     sl.busy = true;
     return NRV_OK;
   }
@@ -2256,18 +2313,12 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
     sl.sat_seen = 0;
   }
   if (mr) {
-    const MergeLayout m = merge_layout(N, sl.n, n_reads, sl.report, sl.edits, records, blob_cap, sl.profile);
-    sl.m_prof = m.prof; sl.prof_out = mr->profile;
-    if (sl.profile) memcpy(sl.prof_thr, mr->prof_thr, sizeof sl.prof_thr);
-    sl.m_roff = m.roff; sl.m_blob = m.blob; sl.m_bytes = m.bytes; sl.blob_cap = blob_cap;
-    sl.blob_out = mr->blob; sl.roff_out = mr->rec_off;
-    sl.m_seq = m.seq; sl.m_qual = m.qual; sl.m_rec = m.rec; sl.m_tile = m.tile; sl.m_dl = m.dl;
-    sl.m_rep = m.rep; sl.rep_out = mr->report; sl.tie_eps = mr->tie_eps;
-    sl.m_eoff = m.eoff; sl.m_edits = m.edits; sl.m_etile = m.etile; sl.edits_out = mr->edits; sl.eoff_out = mr->edit_off;
-    if ((sl.edits || records) && !h->edit_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->edit_stream, hipStreamNonBlocking));
-    sl.want_q = mr->q_thr != nullptr && (mr->qual != nullptr || records);
-    if (sl.want_q) memcpy(sl.thr, mr->q_thr, sizeof sl.thr);
-    sl.seq = mr->seq; sl.qual = mr->qual; sl.off = mr->off;
+    const MergeLayout& m = sl.m = merge_layout(N, sl.n, n_reads, sl.out, blob_cap);
+    sl.blob_cap = blob_cap;
+    sl.want_q = wants_quality(mr->q_thr, sl.out);
+    if (sl.want_q) memcpy(sl.thr, mr->q_thr, sizeof sl.thr);    // the VALUES: the caller's inputs are gone when _end re-runs the call
+    if (sl.out.profile) memcpy(sl.prof_thr, mr->prof_thr, sizeof sl.prof_thr);
+    if ((sl.out.edit_off || records) && !h->edit_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->edit_stream, hipStreamNonBlocking));
     if (m.bytes > sl.cap_mrg) {
       (void)hipFree(sl.d_mrg); (void)hipHostFree(sl.pin_mrg);
       sl.d_mrg = sl.pin_mrg = nullptr; sl.cap_mrg = 0;
@@ -2292,9 +2343,9 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
     if ((rc = poison_fill(h, sl.d_in, sl.cap_in, h->copy_stream)) || (rc = poison_fill(h, sl.d_out + 64, sl.cap_out - 64, h->stream)))
       return rc;
     if (mr) {
-      for (size_t i = 0; i + 4 <= sl.m_dl; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
-      if (sl.edits) for (size_t i = sl.m_edits; i + 4 <= sl.m_etile; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
-      if (records) for (size_t i = sl.m_blob; i + 4 <= sl.m_bytes; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
+      for (size_t i = 0; i + 4 <= sl.m.dl; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
+      if (sl.out.edit_off) for (size_t i = sl.m.edits; i + 4 <= sl.m.etile; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
+      if (records) for (size_t i = sl.m.blob; i + 4 <= sl.m.bytes; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
       if ((rc = poison_fill(h, sl.d_mrg, sl.cap_mrg, h->stream))) return rc;
     }
   }
@@ -2321,32 +2372,37 @@ static int raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int
                        (const StatAux*)(sl.d_in + sl.off_aux), sl.d_stat, n_reads, N, stat_len, (float*)(sl.d_in + sl.off_feat),
                        nullptr, nullptr);
   // the merge reads the slot's output block: behind the call's last launch group, ahead of ev_done
-  if (rc || (rc = raw_enqueue(h, sl)) || (mr && (rc = merge_enqueue(h, slot_merge_args(h, sl)))) ||
-      (sl.report && (rc = report_enqueue(h, slot_report_args(h, sl)))) ||
-      (sl.edits && (rc = edits_enqueue(h, slot_edits_args(h, sl)))) ||
-      (records && (rc = pack_enqueue(h, slot_pack_args(sl)))) ||
-      (sl.profile && (rc = profile_enqueue(h, slot_profile_args(h, sl))))) {
+  if (rc || (rc = raw_enqueue(h, sl)) ||
+      (mr && (rc = merged_enqueue(h, slot_view(sl), sl.m, sl.out, sl.want_q ? sl.thr : nullptr, sl.prof_thr, sl.blob_cap)))) {
     (void)hipStreamSynchronize(h->stream);                      // part of the call may be enqueued: nothing of it may outlive the slot
     return rc;
   }
   HIPCHK(h, hipEventRecord(sl.ev_done, h->stream));
   HIPCHK(h, hipStreamWaitEvent(h->d2h_stream, sl.ev_done, 0));
-  if (mr) {                                                     // the counter and the merged block; p1 / p2 / a1 / a2 stay on the device
-    HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64, hipMemcpyDeviceToHost, h->d2h_stream));
-    if ((rc = merged_download(h, sl, h->d2h_stream))) return rc;
-  } else {
-    HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, out_bytes, hipMemcpyDeviceToHost, h->d2h_stream));
-  }
+  if ((rc = slot_download(h, sl, h->d2h_stream))) return rc;
   HIPCHK(h, hipEventRecord(sl.ev_out, h->d2h_stream));
   HIPCHK(h, hipGetLastError());
   sl.busy = true;
   return NRV_OK;
 }
 
+// Every nrv_revise_reads_raw*_begin: the argument checks they share, under the entry point's name `who`, then raw_begin.
+// missing: what the entry point itself requires and did not get ("null report", ...), or null
+static int revise_begin(nrv_handle* h, const char* who, const char* missing, const RawIn& in, const MergeIn& mr, const MergeOut& mo,
+                        int* ticket) {
+  const char* bad = nullptr;
+  if ((in.last_dur == nullptr) != (in.on_device == nullptr)) bad = "last_dur and on_device go together";
+  else if (missing) bad = missing;
+  else if (mo.edits && !mo.edit_off) bad = "edits without edit_off";
+  else if (!mo.rec_off && (mr.names || mr.name_off || mo.blob)) bad = "names / name_off / blob without rec_off";
+  if (h && bad) { h->err = std::string(who) + ": " + bad; return NRV_E_INVALID; }
+  return raw_begin(h, in, nullptr, nullptr, nullptr, nullptr, ticket, &mr, &mo);
+}
+
 int nrv_reads_raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
                         const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
                         float* p1, float* p2, int8_t* a1, int8_t* a2, int* ticket) {
-  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, nullptr, nullptr, p1, p2, a1, a2, ticket);
+  return raw_begin(h, RawIn{raw, n_raw, starts, feat_ev, N, reads, n_reads}, p1, p2, a1, a2, ticket);
 }
 
 int nrv_reads_raw_stats_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
@@ -2356,7 +2412,7 @@ int nrv_reads_raw_stats_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, 
   if (h && n_reads > 0 && (!last_dur || !on_device)) { h->err = "nrv_reads_raw_stats_begin: null last_dur / flags"; return NRV_E_INVALID; }
   static const int32_t no_dur = 0;
   static const uint8_t no_flag = 0;
-  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur ? last_dur : &no_dur, on_device ? on_device : &no_flag,
+  return raw_begin(h, RawIn{raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur ? last_dur : &no_dur, on_device ? on_device : &no_flag},
                    p1, p2, a1, a2, ticket);
 }
 
@@ -2364,62 +2420,56 @@ int nrv_predict_reads_raw_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw
                                 const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
                                 const int32_t* last_dur, const uint8_t* on_device,
                                 float* p1, float* p2, int8_t* a1, int8_t* a2) {
-  int t = -1;
-  const int rc = nrv_reads_raw_stats_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, p1, p2, a1, a2, &t);
-  return rc ? rc : nrv_reads_raw_end(h, t);
+  return begin_then_end(h, [&](int* t) {
+    return nrv_reads_raw_stats_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, p1, p2, a1, a2, t);
+  });
 }
 
 int nrv_revise_reads_raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
                                const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
                                const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
                                uint8_t* seq, uint8_t* qual, int64_t* off, int* ticket) {
-  if (h && ((last_dur == nullptr) != (on_device == nullptr))) { h->err = "nrv_revise_reads_raw_begin: last_dur and on_device go together"; return NRV_E_INVALID; }
-  const MergeReq mr{bases, q_thr, seq, qual, off};
-  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, nullptr, nullptr, nullptr, nullptr, ticket, &mr);
+  return revise_begin(h, "nrv_revise_reads_raw_begin", nullptr, RawIn{raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device},
+                      MergeIn{bases, q_thr}, MergeOut{seq, qual, off}, ticket);
 }
 
 int nrv_revise_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
                          const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
                          const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
                          uint8_t* seq, uint8_t* qual, int64_t* off) {
-  int t = -1;
-  const int rc = nrv_revise_reads_raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
-                                            seq, qual, off, &t);
-  return rc ? rc : nrv_reads_raw_end(h, t);
+  return begin_then_end(h, [&](int* t) {
+    return nrv_revise_reads_raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr, seq, qual, off, t);
+  });
 }
 
 int nrv_revise_reads_raw_report_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
                                       const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
                                       const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
                                       uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report, int* ticket) {
-  if (h && ((last_dur == nullptr) != (on_device == nullptr))) { h->err = "nrv_revise_reads_raw_report_begin: last_dur and on_device go together"; return NRV_E_INVALID; }
-  if (h && !report) { h->err = "nrv_revise_reads_raw_report_begin: null report"; return NRV_E_INVALID; }
-  MergeReq mr{bases, q_thr, seq, qual, off};
-  mr.report = report; mr.tie_eps = tie_eps;
-  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, nullptr, nullptr, nullptr, nullptr, ticket, &mr);
+  return revise_begin(h, "nrv_revise_reads_raw_report_begin", report ? nullptr : "null report",
+                      RawIn{raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device}, MergeIn{bases, q_thr},
+                      MergeOut{seq, qual, off, report, tie_eps}, ticket);
 }
 
 int nrv_revise_reads_raw_report(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
                                 const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
                                 const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
                                 uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report) {
-  int t = -1;
-  const int rc = nrv_revise_reads_raw_report_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
-                                                   seq, qual, off, tie_eps, report, &t);
-  return rc ? rc : nrv_reads_raw_end(h, t);
+  return begin_then_end(h, [&](int* t) {
+    return nrv_revise_reads_raw_report_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                             seq, qual, off, tie_eps, report, t);
+  });
 }
 
+// report == NULL: none is counted (here and in the forms below)
 int nrv_revise_reads_raw_edits_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
                                      const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
                                      const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
                                      uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
                                      nrv_edit* edits, int64_t* edit_off, int* ticket) {
-  if (h && ((last_dur == nullptr) != (on_device == nullptr))) { h->err = "nrv_revise_reads_raw_edits_begin: last_dur and on_device go together"; return NRV_E_INVALID; }
-  if (h && !edit_off) { h->err = "nrv_revise_reads_raw_edits_begin: null edit_off"; return NRV_E_INVALID; }
-  MergeReq mr{bases, q_thr, seq, qual, off};
-  mr.report = report; mr.tie_eps = tie_eps;                    // report == NULL: none is counted
-  mr.edits = edits; mr.edit_off = edit_off;
-  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, nullptr, nullptr, nullptr, nullptr, ticket, &mr);
+  return revise_begin(h, "nrv_revise_reads_raw_edits_begin", edit_off ? nullptr : "null edit_off",
+                      RawIn{raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device}, MergeIn{bases, q_thr},
+                      MergeOut{seq, qual, off, report, tie_eps, edits, edit_off}, ticket);
 }
 
 int nrv_revise_reads_raw_edits(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
@@ -2427,26 +2477,22 @@ int nrv_revise_reads_raw_edits(nrv_handle* h, const int16_t* raw, int64_t n_raw,
                                const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
                                uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
                                nrv_edit* edits, int64_t* edit_off) {
-  int t = -1;
-  const int rc = nrv_revise_reads_raw_edits_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
-                                                  seq, qual, off, tie_eps, report, edits, edit_off, &t);
-  return rc ? rc : nrv_reads_raw_end(h, t);
+  return begin_then_end(h, [&](int* t) {
+    return nrv_revise_reads_raw_edits_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                            seq, qual, off, tie_eps, report, edits, edit_off, t);
+  });
 }
 
+// edit_off == NULL: no edit list (here and in the form below)
 int nrv_revise_reads_raw_records_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
                                        const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
                                        const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
                                        uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
                                        nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
                                        uint8_t* blob, int64_t* rec_off, int* ticket) {
-  if (h && ((last_dur == nullptr) != (on_device == nullptr))) { h->err = "nrv_revise_reads_raw_records_begin: last_dur and on_device go together"; return NRV_E_INVALID; }
-  if (h && !rec_off) { h->err = "nrv_revise_reads_raw_records_begin: null rec_off"; return NRV_E_INVALID; }
-  if (h && edits && !edit_off) { h->err = "nrv_revise_reads_raw_records_begin: edits without edit_off"; return NRV_E_INVALID; }
-  MergeReq mr{bases, q_thr, seq, qual, off};
-  mr.report = report; mr.tie_eps = tie_eps;                    // report == NULL: none is counted
-  mr.edits = edits; mr.edit_off = edit_off;                    // edit_off == NULL: no edit list
-  mr.names = names; mr.name_off = name_off; mr.blob = blob; mr.rec_off = rec_off;
-  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, nullptr, nullptr, nullptr, nullptr, ticket, &mr);
+  return revise_begin(h, "nrv_revise_reads_raw_records_begin", rec_off ? nullptr : "null rec_off",
+                      RawIn{raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device}, MergeIn{bases, q_thr, names, name_off},
+                      MergeOut{seq, qual, off, report, tie_eps, edits, edit_off, blob, rec_off}, ticket);
 }
 
 int nrv_revise_reads_raw_records(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
@@ -2455,28 +2501,23 @@ int nrv_revise_reads_raw_records(nrv_handle* h, const int16_t* raw, int64_t n_ra
                                  uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
                                  nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
                                  uint8_t* blob, int64_t* rec_off) {
-  int t = -1;
-  const int rc = nrv_revise_reads_raw_records_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
-                                                    seq, qual, off, tie_eps, report, edits, edit_off, names, name_off, blob, rec_off, &t);
-  return rc ? rc : nrv_reads_raw_end(h, t);
+  return begin_then_end(h, [&](int* t) {
+    return nrv_revise_reads_raw_records_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                              seq, qual, off, tie_eps, report, edits, edit_off, names, name_off, blob, rec_off, t);
+  });
 }
 
+// rec_off == NULL: no records
 int nrv_revise_reads_raw_profile_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
                                        const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
                                        const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
                                        uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
                                        nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
                                        uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile, int* ticket) {
-  if (h && ((last_dur == nullptr) != (on_device == nullptr))) { h->err = "nrv_revise_reads_raw_profile_begin: last_dur and on_device go together"; return NRV_E_INVALID; }
-  if (h && (!prof_thr || !profile)) { h->err = "nrv_revise_reads_raw_profile_begin: null prof_thr / profile"; return NRV_E_INVALID; }
-  if (h && edits && !edit_off) { h->err = "nrv_revise_reads_raw_profile_begin: edits without edit_off"; return NRV_E_INVALID; }
-  if (h && !rec_off && (names || name_off || blob)) { h->err = "nrv_revise_reads_raw_profile_begin: names / name_off / blob without rec_off"; return NRV_E_INVALID; }
-  MergeReq mr{bases, q_thr, seq, qual, off};
-  mr.report = report; mr.tie_eps = tie_eps;                    // report == NULL: none is counted
-  mr.edits = edits; mr.edit_off = edit_off;                    // edit_off == NULL: no edit list
-  mr.names = names; mr.name_off = name_off; mr.blob = blob; mr.rec_off = rec_off;   // rec_off == NULL: no records
-  mr.prof_thr = prof_thr; mr.profile = profile;
-  return raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, nullptr, nullptr, nullptr, nullptr, ticket, &mr);
+  return revise_begin(h, "nrv_revise_reads_raw_profile_begin", prof_thr && profile ? nullptr : "null prof_thr / profile",
+                      RawIn{raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device},
+                      MergeIn{bases, q_thr, names, name_off, prof_thr},
+                      MergeOut{seq, qual, off, report, tie_eps, edits, edit_off, blob, rec_off, profile}, ticket);
 }
 
 int nrv_revise_reads_raw_profile(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
@@ -2485,11 +2526,11 @@ int nrv_revise_reads_raw_profile(nrv_handle* h, const int16_t* raw, int64_t n_ra
                                  uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
                                  nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
                                  uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile) {
-  int t = -1;
-  const int rc = nrv_revise_reads_raw_profile_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
-                                                    seq, qual, off, tie_eps, report, edits, edit_off, names, name_off, blob, rec_off,
-                                                    prof_thr, profile, &t);
-  return rc ? rc : nrv_reads_raw_end(h, t);
+  return begin_then_end(h, [&](int* t) {
+    return nrv_revise_reads_raw_profile_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                              seq, qual, off, tie_eps, report, edits, edit_off, names, name_off, blob, rec_off,
+                                              prof_thr, profile, t);
+  });
 }
 
 int nrv_reads_raw_end(nrv_handle* h, int ticket) {
@@ -2509,61 +2550,26 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
     const int rc2 = raw_enqueue(h, sl);
     h->h2 = h2; h->split = split;
     if (rc2) return rc2;
-    if (sl.merge) {                                             // the merge again, in stream order behind the re-run it reads
-      if ((rc = poison_fill(h, sl.d_mrg, sl.cap_mrg, h->stream)) || (rc = merge_enqueue(h, slot_merge_args(h, sl)))) return rc;
-      // ... and the report: report_enqueue zeroes the block again, so the first pass's counts are not counted twice
-      if (sl.report && (rc = report_enqueue(h, slot_report_args(h, sl)))) return rc;
-      // ... and the edit list: plain stores into what is read back, nothing accumulates
-      if (sl.edits && (rc = edits_enqueue(h, slot_edits_args(h, sl)))) return rc;
-      // ... and the records, from the seq / qual / off of the second merge; rec_off is read again below
-      if (sl.records && (rc = pack_enqueue(h, slot_pack_args(sl)))) return rc;
-      // ... and the profile: profile_enqueue zeroes the block again, as the report's
-      if (sl.profile && (rc = profile_enqueue(h, slot_profile_args(h, sl)))) return rc;
-      HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64, hipMemcpyDeviceToHost, h->stream));
-      if ((rc = merged_download(h, sl, h->stream))) return rc;
-    } else {
-      HIPCHK(h, hipMemcpyAsync(sl.pin_out, sl.d_out, 64 + sl.rows * kOutBytes, hipMemcpyDeviceToHost, h->stream));
-    }
+    // a merged call: its kernels again, in stream order behind the re-run they read, on a block that holds nothing of the first pass
+    if (sl.out.off && ((rc = poison_fill(h, sl.d_mrg, sl.cap_mrg, h->stream)) ||
+                       (rc = merged_enqueue(h, slot_view(sl), sl.m, sl.out, sl.want_q ? sl.thr : nullptr, sl.prof_thr, sl.blob_cap))))
+      return rc;
+    if ((rc = slot_download(h, sl, h->stream))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     sl.sat_seen = *(unsigned*)sl.pin_out;
     h->sat_reruns += 1;
   }
-  if (sl.merge) {
-    const int64_t* off = (const int64_t*)sl.pin_mrg;
-    const int64_t total = off[sl.n_reads];
-    if (total < 0 || total > sl.N + sl.n) { h->err = "nrv_reads_raw_end: merged block out of range"; return NRV_E_HIP; }
-    memcpy(sl.off, off, ((size_t)sl.n_reads + 1) * 8);
-    if (sl.seq) memcpy(sl.seq, sl.pin_mrg + sl.m_seq, (size_t)total);
-    if (sl.want_q && sl.qual) memcpy(sl.qual, sl.pin_mrg + sl.m_qual, (size_t)total);
-    if (sl.report) memcpy(sl.rep_out, sl.pin_mrg + sl.m_rep, (size_t)sl.n_reads * kReportCols * 8);
-    if (sl.profile) memcpy(sl.prof_out, sl.pin_mrg + sl.m_prof, (size_t)sl.n_reads * kProfileCols * 8);
-    if (sl.edits) {
-      // the used prefix of the records alone: a copy of its own size on a stream of its own - the records are complete (ev_done
-      // lies behind the edit kernels, or the re-run above was waited for), and neither the compute stream nor d2h_stream, which
-      // may hold the other slot's kernels or wait for them, stands in front of it
-      const int64_t* eoff = (const int64_t*)(sl.pin_mrg + sl.m_eoff);
-      const int64_t n_ed = eoff[sl.n_reads];
-      if (n_ed < 0 || n_ed > sl.n) { h->err = "nrv_reads_raw_end: edit list out of range"; return NRV_E_HIP; }
-      memcpy(sl.eoff_out, eoff, ((size_t)sl.n_reads + 1) * 8);
-      if (n_ed > 0) {
-        HIPCHK(h, hipMemcpyAsync(sl.pin_mrg + sl.m_edits, sl.d_mrg + sl.m_edits, (size_t)n_ed * sizeof(nrv_edit), hipMemcpyDeviceToHost, h->edit_stream));
-        HIPCHK(h, hipStreamSynchronize(h->edit_stream));
-        memcpy(sl.edits_out, sl.pin_mrg + sl.m_edits, (size_t)n_ed * sizeof(nrv_edit));
-      }
-    }
-    if (sl.records) {
-      // the used prefix of the blob, as the edit records above: a copy of its own size on the stream that queues behind nothing
-      const int64_t* roff = (const int64_t*)(sl.pin_mrg + sl.m_roff);
-      const int64_t n_b = roff[sl.n_reads];
-      if (n_b < 0 || (uint64_t)n_b > sl.blob_cap) { h->err = "nrv_reads_raw_end: records out of range"; return NRV_E_HIP; }
-      memcpy(sl.roff_out, roff, ((size_t)sl.n_reads + 1) * 8);
-      if (n_b > 0) {
-        HIPCHK(h, hipMemcpyAsync(sl.pin_mrg + sl.m_blob, sl.d_mrg + sl.m_blob, (size_t)n_b, hipMemcpyDeviceToHost, h->edit_stream));
-        HIPCHK(h, hipStreamSynchronize(h->edit_stream));
-        memcpy(sl.blob_out, sl.pin_mrg + sl.m_blob, (size_t)n_b);
-      }
-    }
-    return NRV_OK;
+  if (sl.out.off) {
+    // the used prefix alone: a copy of its own size on a stream of its own - the records are complete (ev_done lies behind the
+    // edit kernels, or the re-run above was waited for), and neither the compute stream nor d2h_stream, which may hold the other
+    // slot's kernels or wait for them, stands in front of it
+    auto fetch = [&](void* dst, size_t at, size_t bytes) -> int {
+      HIPCHK(h, hipMemcpyAsync(sl.pin_mrg + at, sl.d_mrg + at, bytes, hipMemcpyDeviceToHost, h->edit_stream));
+      HIPCHK(h, hipStreamSynchronize(h->edit_stream));
+      memcpy(dst, sl.pin_mrg + at, bytes);
+      return NRV_OK;
+    };
+    return merged_collect(h, "nrv_reads_raw_end", "nrv_reads_raw_end", sl.pin_mrg, slot_view(sl), sl.m, sl.out, sl.want_q, sl.blob_cap, fetch);
   }
   const char* o = sl.pin_out + 64;
   const size_t n = (size_t)sl.n;
@@ -2583,9 +2589,7 @@ int nrv_predict_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, cons
   // the whole call at once (nrv_reads_raw_begin + _end).  Same kernels on the same windows: the same bits.
   static const bool staged = getenv("NRV_RAW_STAGED") && atoi(getenv("NRV_RAW_STAGED")) != 0;
   if (!staged && !h->raw_slot[0].busy && !h->raw_slot[1].busy) {
-    int t = -1;
-    if ((rc = nrv_reads_raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, p1, p2, a1, a2, &t))) return rc;
-    return nrv_reads_raw_end(h, t);
+    return begin_then_end(h, [&](int* t) { return nrv_reads_raw_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, p1, p2, a1, a2, t); });
   }
   if ((rc = upload_raw(h, raw, n_raw, starts, N, reads, n_reads))) return rc;
   return predict_host(h, nullptr, feat_ev, N, true, p1, p2, a1, a2, n_reads);
@@ -2654,15 +2658,14 @@ int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32
   return NRV_OK;
 }
 
-// nrv_merge_calls (report == nullptr: that call, to the byte), nrv_merge_calls_report, (edit_off != nullptr) nrv_merge_calls_edits
-// and (profile != nullptr) nrv_merge_calls_profile
+// nrv_merge_calls (o.report == nullptr: that call, to the byte), nrv_merge_calls_report, (o.edit_off != nullptr)
+// nrv_merge_calls_edits and (o.profile != nullptr) nrv_merge_calls_profile
 static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
-                            const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
-                            float tie_eps, uint64_t* report, nrv_edit* edits = nullptr, int64_t* edit_off = nullptr,
-                            const float* prof_thr = nullptr, uint64_t* profile = nullptr) {
+                            const float* p1, const float* p2, int64_t n_win, const float* q_thr, const MergeOut& o,
+                            const float* prof_thr = nullptr) {
   int rc = check_handle(h);
   if (rc) return rc;
-  if (n_reads < 0 || n_win < 0 || !off || (n_reads > 0 && !ev_len)) { h->err = "nrv_merge_calls: bad arguments"; return NRV_E_INVALID; }
+  if (n_reads < 0 || n_win < 0 || !o.off || (n_reads > 0 && !ev_len)) { h->err = "nrv_merge_calls: bad arguments"; return NRV_E_INVALID; }
   std::vector<nrv_read_desc> rd((size_t)n_reads);
   int64_t N = 0;
   for (int r = 0; r < n_reads; ++r) {
@@ -2670,32 +2673,29 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
     rd[r] = nrv_read_desc{0, 0, N, ev_len[r], 0., 0.};
     N += ev_len[r];
   }
-  const int T = h->T;
-  const int64_t n = N - T > 0 ? N - T : 0;
-  const bool want_q = q_thr != nullptr && qual != nullptr;
-  if (n_win != n || (N > 0 && (!bases || !seq)) || (n > 0 && (!a1 || !a2 || (want_q && (!p1 || !p2))))) {
+  const int64_t n = N - h->T > 0 ? N - h->T : 0;
+  const bool want_q = wants_quality(q_thr, o);
+  if (n_win != n || (N > 0 && (!bases || !o.seq)) || (n > 0 && (!a1 || !a2 || (want_q && (!p1 || !p2))))) {
     h->err = "nrv_merge_calls: n_win is not sum(ev_len) - T, or a null array";
     return NRV_E_INVALID;
   }
   if (n == 0) {
-    merge_nothing(bases, rd.data(), n_reads, N, seq, want_q ? qual : nullptr, off);
-    if (report) report_nothing(rd.data(), n_reads, want_q, report);
-    if (edit_off) memset(edit_off, 0, ((size_t)n_reads + 1) * 8);
-    if (profile) profile_nothing(bases, rd.data(), n_reads, profile);
+    merged_nothing(MergeIn{bases, q_thr}, o, rd.data(), n_reads, N);
     return NRV_OK;
   }
-  if (edit_off && !edits) { h->err = "nrv_merge_calls_edits: null edits"; return NRV_E_INVALID; }
+  if (o.edit_off && !o.edits) { h->err = "nrv_merge_calls_edits: null edits"; return NRV_E_INVALID; }
   // one block of its own: [reads | bases | a1 | a2 | p1 | p2 | merged block]
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const MergeLayout m = merge_layout(N, n, n_reads, report != nullptr, edit_off != nullptr, false, 0, profile != nullptr);
-  const bool have_p = want_q || ((report || edit_off || profile) && p1 && p2);   // the report's near-tie column and the edits' conf read the rows without a quality too
+  const MergeLayout m = merge_layout(N, n, n_reads, o, 0);
+  // the rows go up for a quality - and without one where they are given and the report's near-tie column, the edits' conf or the
+  // profile reads them
+  const bool have_p = want_q || ((o.report || o.edit_off || o.profile) && p1 && p2);
   const size_t o_b = up((size_t)n_reads * sizeof(SegRead)), o_a1 = o_b + up((size_t)N), o_a2 = o_a1 + up((size_t)n);
   const size_t o_p1 = o_a2 + up((size_t)n), o_p2 = o_p1 + (have_p ? up((size_t)n * 24) : 0), o_m = o_p2 + (have_p ? up((size_t)n * 20) : 0);
   const size_t bytes = o_m + m.bytes;
   char* d = nullptr;
   HIPCHK(h, hipMalloc((void**)&d, bytes));
   std::vector<char> back(m.dl);
-  int64_t n_ed = 0;
   auto run = [&]() -> int {
     int rc2 = poison_fill(h, d, bytes, h->stream);
     if (rc2) return rc2;
@@ -2707,52 +2707,28 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
       HIPCHK(h, hipMemcpyAsync(d + o_p1, p1, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
       HIPCHK(h, hipMemcpyAsync(d + o_p2, p2, (size_t)n * 20, hipMemcpyHostToDevice, h->stream));
     }
-    MergeArgs a;
-    a.reads = (const SegRead*)d; a.n_reads = n_reads; a.T = T; a.N = N;
-    a.bases = (const unsigned char*)(d + o_b);
-    a.a1 = (const signed char*)(d + o_a1); a.a2 = (const signed char*)(d + o_a2);
-    a.p1 = want_q ? (const float*)(d + o_p1) : nullptr; a.p2 = want_q ? (const float*)(d + o_p2) : nullptr;
-    a.rec = (unsigned*)(d + o_m + m.rec); a.tile = (unsigned long long*)(d + o_m + m.tile);
-    a.off = (long long*)(d + o_m); a.seq = (unsigned char*)(d + o_m + m.seq);
-    a.qual = want_q ? (unsigned char*)(d + o_m + m.qual) : nullptr;
-    memset(a.thr, 0, sizeof a.thr);
-    if (want_q) memcpy(a.thr, q_thr, sizeof a.thr);
-    if ((rc2 = merge_enqueue(h, a))) return rc2;
-    if (report && (rc2 = report_enqueue(h, report_args(a, have_p ? (const float*)(d + o_p1) : nullptr, have_p ? (const float*)(d + o_p2) : nullptr,
-                                                      want_q, tie_eps, d + o_m + m.rep))))
-      return rc2;
-    if (edit_off && (rc2 = edits_enqueue(h, edits_args(a, have_p ? (const float*)(d + o_p1) : nullptr, have_p ? (const float*)(d + o_p2) : nullptr,
-                                                      want_q, d + o_m + m.etile, d + o_m + m.eoff, d + o_m + m.edits))))
-      return rc2;
-    if (profile && (rc2 = profile_enqueue(h, profile_args(a, (const float*)(d + o_p1), (const float*)(d + o_p2), prof_thr, d + o_m + m.prof))))
-      return rc2;
+    const MergeView v{(const SegRead*)d, n_reads, N, (const unsigned char*)(d + o_b), (const signed char*)(d + o_a1),
+                      (const signed char*)(d + o_a2), have_p ? (const float*)(d + o_p1) : nullptr,
+                      have_p ? (const float*)(d + o_p2) : nullptr, nullptr, nullptr, d + o_m};
+    if ((rc2 = merged_enqueue(h, v, m, o, want_q ? q_thr : nullptr, prof_thr, 0))) return rc2;
     HIPCHK(h, hipMemcpyAsync(back.data(), d + o_m, m.dl, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (edit_off) {                                             // the used prefix of the records, once the total is known
-      n_ed = ((const int64_t*)(back.data() + m.eoff))[n_reads];
-      if (n_ed < 0 || n_ed > n) { h->err = "nrv_merge_calls_edits: edit list out of range"; return NRV_E_HIP; }
-      if (n_ed > 0) HIPCHK(h, hipMemcpy(edits, d + o_m + m.edits, (size_t)n_ed * sizeof(nrv_edit), hipMemcpyDeviceToHost));
-    }
-    return NRV_OK;
+    // a test twin, not timed: the used prefix of the edit records in a plain copy, straight into the caller's array
+    auto fetch = [&](void* dst, size_t at, size_t bytes) -> int {
+      HIPCHK(h, hipMemcpy(dst, d + o_m + at, bytes, hipMemcpyDeviceToHost));
+      return NRV_OK;
+    };
+    return merged_collect(h, "nrv_merge_calls", "nrv_merge_calls_edits", back.data(), v, m, o, want_q, 0, fetch);
   };
   rc = run();
   if (rc) (void)hipStreamSynchronize(h->stream);
   (void)hipFree(d);
-  if (rc) return rc;
-  const int64_t total = ((const int64_t*)back.data())[n_reads];
-  if (total < 0 || total > N + n) { h->err = "nrv_merge_calls: merged block out of range"; return NRV_E_HIP; }
-  memcpy(off, back.data(), ((size_t)n_reads + 1) * 8);
-  memcpy(seq, back.data() + m.seq, (size_t)total);
-  if (want_q) memcpy(qual, back.data() + m.qual, (size_t)total);
-  if (report) memcpy(report, back.data() + m.rep, (size_t)n_reads * kReportCols * 8);
-  if (edit_off) memcpy(edit_off, back.data() + m.eoff, ((size_t)n_reads + 1) * 8);
-  if (profile) memcpy(profile, back.data() + m.prof, (size_t)n_reads * kProfileCols * 8);
-  return NRV_OK;
+  return rc;
 }
 
 int nrv_merge_calls(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
                     const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off) {
-  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, seq, qual, off, 0.f, nullptr);
+  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, MergeOut{seq, qual, off});
 }
 
 int nrv_merge_calls_report(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
@@ -2760,14 +2736,14 @@ int nrv_merge_calls_report(nrv_handle* h, const uint8_t* bases, const int64_t* e
                            float tie_eps, uint64_t* report) {
   if (h && n_reads > 0 && !report) { h->err = "nrv_merge_calls_report: null report"; return NRV_E_INVALID; }
   static uint64_t none[NRV_REPORT_COLS];
-  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, seq, qual, off, tie_eps, report ? report : none);
+  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, MergeOut{seq, qual, off, report ? report : none, tie_eps});
 }
 
 int nrv_merge_calls_edits(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
                           const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
                           float tie_eps, uint64_t* report, nrv_edit* edits, int64_t* edit_off) {
   if (h && !edit_off) { h->err = "nrv_merge_calls_edits: null edit_off"; return NRV_E_INVALID; }
-  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, seq, qual, off, tie_eps, report, edits, edit_off);
+  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, MergeOut{seq, qual, off, report, tie_eps, edits, edit_off});
 }
 
 int nrv_merge_calls_profile(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
@@ -2775,8 +2751,9 @@ int nrv_merge_calls_profile(nrv_handle* h, const uint8_t* bases, const int64_t* 
                             const float* prof_thr, uint64_t* profile) {
   if (h && (!prof_thr || !profile)) { h->err = "nrv_merge_calls_profile: null prof_thr / profile"; return NRV_E_INVALID; }
   if (h && (!p1 || !p2)) { h->err = "nrv_merge_calls_profile: null p1 / p2"; return NRV_E_INVALID; }
-  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, seq, qual, off, 0.f, nullptr, nullptr, nullptr,
-                          prof_thr, profile);
+  MergeOut o{seq, qual, off};
+  o.profile = profile;
+  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, o, prof_thr);
 }
 
 int nrv_pack_records(nrv_handle* h, const uint8_t* seq, const uint8_t* qual, const int64_t* off, int n_reads,
@@ -2788,7 +2765,7 @@ int nrv_pack_records(nrv_handle* h, const uint8_t* seq, const uint8_t* qual, con
   if (!names_ok(names, name_off, n_reads)) { h->err = "nrv_pack_records: null names / name_off, or offsets that do not ascend from 0"; return NRV_E_INVALID; }
   const int64_t total_in = off[n_reads], name_bytes = name_off[n_reads];
   const bool fastq = qual != nullptr;
-  const size_t q = fastq ? 2 : 1, cap = (size_t)name_bytes + q * (size_t)total_in + 3 * q * (size_t)n_reads;
+  const size_t cap = blob_capacity(total_in, 0, n_reads, name_bytes, fastq);
   if ((total_in > 0 && !seq) || (cap > 0 && !blob)) { h->err = "nrv_pack_records: null seq / blob"; return NRV_E_INVALID; }
   if (cap >= ((size_t)1 << 32)) { h->err = "nrv_pack_records: records of 4 GiB and more in one call"; return NRV_E_INVALID; }
   if (n_reads == 0) { rec_off[0] = 0; return NRV_OK; }
