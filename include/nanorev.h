@@ -345,6 +345,59 @@ int nrv_merge_calls_profile(nrv_handle* h, const uint8_t* bases, const int64_t* 
                             const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
                             const float* prof_thr, uint64_t* profile);
 
+/* SLIDING-WINDOW QUALITY TRIM AND LENGTH FILTER of the same revised reads (opt-in; nothing above changes): per read the part
+ * worth keeping, found on the device behind the merge (and the report / edit launches) and AHEAD of the record launches, which
+ * lay out the trimmed reads only.  The arguments of nrv_revise_reads_raw_profile_begin - `report`, `edits` / `edit_off`,
+ * `seq` / `qual`, the records' four and `prof_thr` / `profile` (both or neither) may be NULL as there - then
+ *   trim_thr  float [39]: the thresholds the trim's qualities are computed with; the layout of q_thr and independent of it;
+ *   Q, W      the window rule: 1 <= Q <= 40, 1 <= W <= 64 (NRV_E_INVALID outside);
+ *   min_len   >= 0: a read whose kept part is shorter has no record;
+ *   trim      int64 [n_reads][2] = (lo, hi) per read.
+ * The rule, integers only: read r has L = off[r + 1] - off[r] output characters with q[i] = Phred of character i - that of the
+ * FASTQ form of the call, whether a quality is written or not: 1 + #{k : trim_thr[k] <= min(p1[clip(a1)], p2[clip(a2)])} for a
+ * window, 2 for an edge event.  Position i is good when i + W <= L (a window never reaches into the next read) and
+ * q[i] + ... + q[i + W - 1] >= Q * W; lo is the smallest good i, hi the largest good i plus W; no good position (L < W is one
+ * case): lo = hi = 0.  hoststage.trim_bounds is the definition; minima and maxima of integers, so the bytes do not depend on the
+ * order of the workgroups.
+ * `seq` / `qual` / `off`, the report, the edit list and the profile describe the UNTRIMMED reads, as without the trim.  The
+ * records are the exception: a read with hi - lo >= min_len has the record of seq[lo:hi] (and qual[lo:hi]), every other read is
+ * DROPPED and has no record, rec_off[r + 1] == rec_off[r] (hoststage.pack_records with trim / min_len).  The blob's capacity is
+ * that of the untrimmed call.
+ * N <= T: nothing is enqueued; `trim` is filled on the host from the rule with every quality 2.  Tickets, the two-calls-in-flight
+ * rule, the failure paths and the range-guard re-run (which starts the bounds from nothing behind the f32 kernels) are those of
+ * nrv_revise_reads_raw_begin; `trim` is filled by nrv_reads_raw_end, downloaded with the call's block, and must stay valid until
+ * then.  nrv_revise_reads_raw_trim IS _trim_begin + _end. */
+int nrv_revise_reads_raw_trim_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                    const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                    const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                    uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                    nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                    uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                    const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim, int* ticket);
+int nrv_revise_reads_raw_trim(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                              const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                              const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                              uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                              nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                              uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                              const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim);
+/* nrv_merge_calls with the trim, by the kernels nrv_revise_reads_raw_trim_begin runs: p1 / p2 are required, q_thr may be NULL.
+ * names / name_off / blob / rec_off: all NULL, or the trimmed records as above (FASTQ by q_thr), the blob's capacity being
+ * name_off[n_reads] + q (N + n_win) + 3 q n_reads.  The twin used by the parity tests. */
+int nrv_merge_calls_trim(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                         const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                         const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                         const uint8_t* names, const int64_t* name_off, uint8_t* blob, int64_t* rec_off);
+/* The window and finish launches alone, on quality CHARACTERS the host supplies: qual uint8 [off[n_reads]] with
+ * q[i] = max(qual[i] - 33, 0), off int64 [n_reads + 1] ascending from 0, trim int64 [n_reads][2].  The unit door of the window
+ * kernel for arbitrary qualities. */
+int nrv_trim_reads(nrv_handle* h, const uint8_t* qual, const int64_t* off, int n_reads, int Q, int W, int64_t* trim);
+/* nrv_pack_records with a trim: trim int64 [n_reads][2] with 0 <= lo <= hi <= off[r + 1] - off[r] (NRV_E_INVALID otherwise) and
+ * min_len >= 0, or trim NULL: nrv_pack_records' bytes. */
+int nrv_pack_records_trim(nrv_handle* h, const uint8_t* seq, const uint8_t* qual, const int64_t* off, int n_reads,
+                          const uint8_t* names, const int64_t* name_off, const int64_t* trim, int64_t min_len,
+                          uint8_t* blob, int64_t* rec_off);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

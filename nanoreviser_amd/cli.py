@@ -144,7 +144,42 @@ def get_args(argv: Optional[Sequence[str]] = None):
                         "of the FASTQ form of the run, in FASTA runs too; a read written unrevised has its base counts and no "
                         "quality.  With --device_merge the counts are made on the GPU behind the merge, everywhere else by the host "
                         "stage from the calls it holds: the same file byte for byte.  Off by default; without it nothing changes")
+    p.add_argument("--trim_q", dest="trim_q", type=int, default=None, metavar="Q",
+                   help="cut every revised read down to the part a sliding quality window keeps (also NRV_TRIM_Q=Q): the read is "
+                        "written from the first to the last window of --trim_window bases whose mean quality is at least Q "
+                        "(1 .. 40; integers: the window's Phred values add up to Q x W or more), and a read whose kept part is "
+                        "shorter than --min_len is DROPPED - no output file, no record in --combined, not a failed read.  The "
+                        "qualities are those of the FASTQ form of the run, in FASTA runs too; the first and last bases of a read "
+                        "have no window and Phred 2, so any Q above 2 cuts them off.  A read written unrevised is written whole.  "
+                        "--report, --edits and --summary keep describing the UNTRIMMED revision (positions, counts): their bytes "
+                        "are what they are without the trim.  With --device_merge the bounds are found on the GPU behind the merge "
+                        "and the records of --combined are cut there, everywhere else the host stage applies them: the same files "
+                        "byte for byte.  --resume does not work with it.  Off by default; without it nothing changes")
+    p.add_argument("--trim_window", dest="trim_window", type=int, default=10, metavar="W",
+                   help="with --trim_q: bases per window, 1 .. 64 (default 10)")
+    p.add_argument("--min_len", dest="min_len", type=int, default=1, metavar="L",
+                   help="with --trim_q: a read with fewer than L bases left is dropped (default 1; 0 keeps empty reads)")
+    p.add_argument("--trim_log", dest="trim_log", default=None, metavar="FILE",
+                   help="with --trim_q: write what the trim did to FILE, a TSV with one header line, one line per input read sorted "
+                        "by file name - name, status (revised / unrevised), bases of the untrimmed read, lo, hi, kept (1 / 0) - "
+                        "and a last line #total with the sums over the revised reads.  The same file on every route")
     a = p.parse_args(argv)
+    if a.trim_q is None and os.environ.get("NRV_TRIM_Q", "").strip():
+        try:
+            a.trim_q = int(os.environ["NRV_TRIM_Q"].strip())
+        except ValueError:
+            print("[！！！Error] NRV_TRIM_Q must be an integer", file=sys.stderr)
+            raise SystemExit(2)
+    if a.trim_q is not None:
+        if not (1 <= a.trim_q <= 40 and 1 <= a.trim_window <= 64 and a.min_len >= 0):
+            print("[！！！Error] --trim_q must be in 1 .. 40, --trim_window in 1 .. 64 and --min_len 0 or more", file=sys.stderr)
+            raise SystemExit(2)
+        if a.resume:
+            print("[！！！Error] --resume cannot be used with --trim_q: a dropped read has no output to resume from", file=sys.stderr)
+            raise SystemExit(2)
+    elif a.trim_log:
+        print("[！！！Error] --trim_log needs --trim_q", file=sys.stderr)
+        raise SystemExit(2)
     a.summary = a.summary or (os.environ.get("NRV_SUMMARY", "").strip() or None)
     a.combined = a.combined or (os.environ.get("NRV_COMBINED", "").strip() or None)
     if a.combined and a.resume:
@@ -701,7 +736,65 @@ def merge_combined(combined: str, fastq: bool):
                 pass
 
 
-def deliver(spec, sink, fns, payload, native: bool = True):
+def _deliver_trimmed(spec, sink, fns, payload, native, bounds, min_len):
+    """`deliver` for reads that are cut to `bounds` (int64[len(fns)][2], `hoststage.trim_bounds`) first: every payload becomes
+    the kept reads' own characters (a records blob is cut already and only loses the dropped reads' index lines) and goes
+    through `deliver`.  A dropped read (hi - lo < min_len) is written nowhere and answers (0, None)."""
+    kind, rest = payload[0], payload[1:]
+    t = np.asarray(bounds, np.int64).reshape(-1, 2)
+    keep = hs.trim_kept(t, min_len)
+    if len(t) != len(fns):
+        raise ValueError("deliver: the trim does not match the reads")
+    if kind == "text":
+        seq, qual = rest
+        lo, hi = int(t[0, 0]), int(t[0, 1])
+        return deliver(spec, sink, fns, ("text", seq[lo:hi], qual[lo:hi] if qual is not None else None), native) if keep[0] else [(0, None)]
+    try:
+        if kind == "calls":
+            seq, qual = _merge_read(rest[0], *rest[1:])
+            lo, hi = int(t[0, 0]), int(t[0, 1])
+            return deliver(spec, sink, fns, ("text", seq[lo:hi], qual[lo:hi] if qual is not None else None), native) if keep[0] else [(0, None)]
+        lens = (t[:, 1] - t[:, 0])[keep]
+        fns_k = [fn for fn, k in zip(fns, keep) if k]
+        off_k = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        if kind == "records":
+            blob, rec_off, off = rest
+            if len(rec_off) != len(fns) + 1:
+                raise ValueError("deliver: the records do not match the reads")
+            if sink is None or not sink:
+                raise ValueError("deliver: records needs a sink")
+            rec_off = np.asarray(rec_off, np.int64)
+            sink.add_blob(fns_k, blob, np.concatenate([rec_off[:-1][keep], rec_off[-1:]]), off_k)      # a dropped read has no bytes
+            res_k = [(int(n), None) for n in lens]
+        else:
+            if kind == "bundle":
+                T, bases, ev_len, a1, a2, qc = rest
+                seq, qual, off = hs.emit_calls(hostlib.bases_u8(bases), ev_len, a1, a2, qc, T)
+            elif kind == "merged":
+                seq, qual, off = rest
+            else:
+                raise ValueError(f"deliver: unknown payload {kind}")
+            off = np.asarray(off, np.int64)
+            at = np.repeat((off[:-1] + t[:, 0])[keep] - off_k[:-1], lens) + np.arange(int(off_k[-1]), dtype=np.int64)
+            seq_k = np.asarray(seq, np.uint8).reshape(-1)[at]
+            qual_k = None if qual is None else np.asarray(qual, np.uint8).reshape(-1)[at]
+            if not fns_k:
+                res_k = []
+            elif (sink is None or not sink) and not (native and hostlib.has_write_records()):
+                res_k = []
+                for r, fn in enumerate(fns_k):
+                    a, b = int(off_k[r]), int(off_k[r + 1])
+                    res_k += deliver(spec, None, [fn], ("text", seq_k[a:b].tobytes().decode("ascii"),
+                                                        None if qual_k is None else qual_k[a:b].tobytes().decode("ascii")), native)
+            else:
+                res_k = deliver(spec, sink, fns_k, ("merged", seq_k, qual_k, off_k), native)
+        it = iter(res_k)
+        return [next(it) if k else (0, None) for k in keep]
+    except Exception as e:
+        return [(0, repr(e))] * len(fns)
+
+
+def deliver(spec, sink, fns, payload, native: bool = True, trim=None):
     """THE decision about where finished reads go, for every path that has some: into the --combined sink (`CombinedPart`, through
     hoststage.pack_records - or as they are, when the device laid the records out) or, without one, into one file per read by the
     writer the path has always used.  payload is what the path holds:
@@ -710,7 +803,12 @@ def deliver(spec, sink, fns, payload, native: bool = True):
       ("bundle", T, bases, ev_len, a1, a2, qc)     the calls of all reads of a device call (`_finish_bundle_native`)
       ("merged", seq, qual, off)                   a --device_merge call's revised reads (`_write_records_native`)
       ("records", blob, rec_off, off)              a `with_device_records` call's blob (sink only)
+    trim (--trim_q): (bounds int64[len(fns)][2], min_len), or None.  THE place where the bounds are applied, for every path: a
+    kept read is written as its characters [lo, hi), a dropped one not at all (0 bases, no error); the blob of a
+    `with_device_trim` call is cut already.  A read written unrevised comes without a trim and is written whole.
     Returns [(bases written, error)] per read; "text" raises instead, as `write_read` does."""
+    if trim is not None:
+        return _deliver_trimmed(spec, sink, fns, payload, native, *trim)
     kind, rest = payload[0], payload[1:]
     if sink is None or not sink:
         if kind == "text":
@@ -799,6 +897,40 @@ def profile_rows(T, bases, ev_len, p1, p2, a1, a2):
     return hs.read_profile(*hs.emit_calls(hostlib.bases_u8(bases), ev_len, a1, a2, qc, T))
 
 
+def trim_rule(args):
+    """(Q, W, min_len) of --trim_q / --trim_window / --min_len, or None without --trim_q."""
+    q = getattr(args, "trim_q", None)
+    return None if q is None else (int(q), int(getattr(args, "trim_window", 10)), int(getattr(args, "min_len", 1)))
+
+
+def _trim_rows_len(T, bases, ev_len, p1, p2, a1, a2, Q, W):
+    """`trim_rows` and the lengths of the untrimmed revised reads: (int64[R][2], int64[R])."""
+    qc = phred_chars(p1, p2, a1, a2) if len(a1) else np.zeros(0, np.uint8)
+    _, qual, off = hs.emit_calls(hostlib.bases_u8(bases), ev_len, a1, a2, qc, T)
+    return hs.trim_bounds(qual, off, Q, W), np.diff(off)
+
+
+def trim_rows(T, bases, ev_len, p1, p2, a1, a2, Q, W):
+    """--trim_q on the host: `hoststage.trim_bounds` on calls the host holds.  The qualities are those of the FASTQ form of the
+    calls whether the run writes a quality or not: `phred_chars`, then `emit_calls`, then `trim_bounds`.  int64[len(ev_len)][2]."""
+    return _trim_rows_len(T, bases, ev_len, p1, p2, a1, a2, Q, W)[0]
+
+
+TRIM_HEADER = "name\tstatus\tbases\tlo\thi\tkept"
+
+
+def trim_log_row(n_bases, bounds, min_len) -> List[int]:
+    """The integers of a --trim_log line: bases of the untrimmed read, lo, hi, kept."""
+    lo, hi = int(bounds[0]), int(bounds[1])
+    return [int(n_bases), lo, hi, int(hi - lo >= int(min_len))]
+
+
+def unrevised_trim(n_written: int) -> List[int]:
+    """The --trim_log integers of a read written unrevised: whole, and kept."""
+    n = max(int(n_written), 0)
+    return [n, 0, n, 1]
+
+
 def unrevised_profile(seq) -> np.ndarray:
     """The profile row of a read written unrevised: the base counts of the sequence that was written (str or bytes), no histogram."""
     row = np.zeros(hs.PROFILE_COLS, np.uint64)
@@ -845,7 +977,8 @@ def _summary_closing(lines):
 
 
 class ReportPart:
-    """One process' share of the --report file (or, with cols = SUMMARY_COLS, of the --summary file): a line per read, appended
+    """One process' share of the --report file (or, with cols = SUMMARY_COLS, of the --summary file; with cols = 4, of the
+    --trim_log file): a line per read, appended
     and flushed as the read's output becomes final (so a worker that dies leaves the lines of what it finished).  `merge_report`
     puts the parts together."""
 
@@ -889,10 +1022,11 @@ def clear_report_parts(report: str):
 # fields of a line (None: the integers themselves), [(status, integers)] -> the lines behind #total (None: none))
 REPORT_TABLE = (23, REPORT_HEADER, "--report", None, None)
 SUMMARY_TABLE = (SUMMARY_COLS, SUMMARY_HEADER, "--summary", summary_fields, _summary_closing)
+TRIM_TABLE = (4, TRIM_HEADER, "--trim_log", None, None)
 
 
 def merge_report(report: str, names: Sequence[str], log: Callable[[str], None] = print, table=REPORT_TABLE):
-    """Parent side of --report (and, with SUMMARY_TABLE, of --summary): the parts in the order they were written (a later line
+    """Parent side of --report (and, with SUMMARY_TABLE, of --summary; with TRIM_TABLE, of --trim_log): the parts in the order they were written (a later line
     for the same read wins: the parent's own part comes last), one line per read of `names` sorted by file name, `#total` = the
     sums over the revised reads; the file appears by rename and the parts are removed."""
     import glob
@@ -969,7 +1103,7 @@ def write_edits(edits_dir: str, fast5_fn: str, edits=None, want_qual: bool = Fal
 def _host_merge_form(packed):
     """A `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` tuple back in the form whose call
     returns (p1, p2, a1, a2): for the paths that keep the host merge."""
-    if packed is None or len(packed) not in (12, 14, 16, 20, 22):
+    if packed is None or len(packed) not in (12, 14, 16, 20, 22, 27):
         return packed
     return tuple(packed[:7]) if packed[7] is None else tuple(packed[:9])
 
@@ -984,12 +1118,13 @@ def _bundle_has_bases(bundle) -> bool:
     return "bases" in bundle and len(bundle["bases"]) == int(bundle["meta"][:, 1].sum())
 
 
-def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, report, edits=False, combined=False, summary=False):
+def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, report, edits=False, combined=False, summary=False,
+                 trim=False):
     """The one decision about a batch: (packed form `_FileRun.submit` builds, route `_FileRun.run_batch` takes).  Pure: it looks at what
     the engine object offers, at the bundle (None: reads that arrived one by one) and at the run's switches - pipelined (one
     engine, NRV_CLI_PIPELINE != 0), native_pool (libnanorev_host.so driven from the thread pool), device_merge (--device_merge
     and what it needs: pipelined, native_pool, nrvh_write_records), report (--report), edits (--edits), combined (--combined),
-    summary (--summary).  "bases":
+    summary (--summary), trim (--trim_q).  "bases":
     `_bundle_has_bases`.  A form is
     the length of the packed tuple (engine.Reviser), None, or "host-merge": the merge form built and taken back.
 
@@ -1008,6 +1143,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
       yes     + combined on, no with_device_records                          12 / 14 / 16 [6]  by the last three rows
       yes     + summary on, a form 12 / 14 / 16 / 20 above, with_device_profile  22 [7]        by the last three rows
       yes     + summary on, such a form, no with_device_profile              host-merge [2]  by the last three rows
+      yes     + trim on, a form 12 / 14 / 16 / 20 / 22 above, with_device_trim  27 [8]         by the last three rows
+      yes     + trim on, such a form, no with_device_trim                    host-merge [2]  by the last three rows
       yes     any form; pipelined, native_pool, begin_packed_raw, bases                      pipelined [3]
       yes     any form; native_pool, bases, not (pipelined, begin_packed_raw)                packed+finish_bundle
       yes     any form; no native_pool, or no bases                                          packed sliced
@@ -1021,7 +1158,10 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
         --combined part as it is, and no native writer is called.
     [6] the merged reads come back and the host forms the records (hoststage.pack_records), as on every host route.
     [7] the one call carries whatever the form above carried (report, edit list, records) and the per-read profile last; every
-        other route forms the summary rows on the host from the calls (`profile_rows`)."""
+        other route forms the summary rows on the host from the calls (`profile_rows`).
+    [8] the one call carries whatever the form above carried and the per-read trim bounds last; its records, where it has some,
+        are those of the trimmed reads.  Every other route finds the bounds on the host from the calls (`trim_rows`); `deliver`
+        applies them on every route."""
     unpacked = "per-read" if n_reads == 1 else "predict_many"
     if bundle is None:
         return (7 if n_reads > 1 and hasattr(rv, "pack_reads_raw") else None), unpacked
@@ -1037,6 +1177,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
             form = 20
         if summary and form != "host-merge":
             form = 22 if hasattr(rv, "with_device_profile") else "host-merge"
+        if trim and form != "host-merge":
+            form = 27 if hasattr(rv, "with_device_trim") else "host-merge"
     if not (native_pool and bases):
         return form, "packed sliced"
     return form, ("pipelined" if pipelined and hasattr(rv, "begin_packed_raw") else "packed+finish_bundle")
@@ -1145,7 +1287,7 @@ class _FileRun:
     `_route_batch` says (`submit`) and collects the pooled finishers; the ENGINE thread(s) make the calls (`run_batch`, `collect`);
     the one FINISHER thread merges, reports and writes, or hands that to the parser pool (`finish_batch`, `finish_call`)."""
     def __init__(self, stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part=None,
-                 summary_part=None):
+                 summary_part=None, trim_part=None):
         self.args, self.log, self.note = args, log, on_file or (lambda fn, ok: None)
         self.stats = {"reads": 0, "bases": 0, "failed": [], "host_s": 0.0, "engine_s": 0.0}
         self.stats_lock = threading.Lock()
@@ -1153,6 +1295,9 @@ class _FileRun:
         self.rep_rows = {}                            # fn -> the row of a read whose output is not final yet
         self.sumpart = ReportPart(summary_part, SUMMARY_COLS)        # --summary: stashed and emitted wherever a report row is
         self.sum_rows = {}
+        self.trim = trim_rule(args)                   # --trim_q: (Q, W, min_len); the bounds are stashed like a report row and
+        self.trim_rows = {}                           # applied by `deliver`; fn -> (bases of the untrimmed read, (lo, hi))
+        self.trimpart = ReportPart(trim_part if self.trim else None, 4)
         self.tie_eps = float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS))
         self.edits_dir = getattr(args, "edits", None) # --edits: every read's list is written BEFORE its output is
         self.sink = CombinedPart(combined_part, args.output_format == "fastq") if combined_part else None   # --combined (`deliver`)
@@ -1261,6 +1406,7 @@ class _FileRun:
         """After the threads have ended: the report part closed, the trace and the range guard logged; the statistics."""
         self.report.close()
         self.sumpart.close()
+        self.trimpart.close()
         if self.sink is not None:
             self.sink.close()
         self.trace.log_summary(self.log, len(self.engines))
@@ -1320,6 +1466,8 @@ class _FileRun:
         if self.sumpart:
             self.sum_rows.pop(fn, None)
             self.sumpart.add(fn, False, unrevised_profile(text))
+        self.trim_rows.pop(fn, None)
+        self.trimpart.add(fn, False, unrevised_trim(nw))
         self.note(fn, False)
 
     def finished(self, fn, nb):
@@ -1334,6 +1482,14 @@ class _FileRun:
             if row is None:                           # cannot happen, as above
                 self.log(f"[！！！Warning] --summary: no counts for {fn}")
             self.sumpart.add(fn, row is not None, row if row is not None else np.zeros(hs.PROFILE_COLS, np.uint64))
+        if self.trim:
+            row = self.trim_rows.pop(fn, None)
+            log_row = trim_log_row(row[0], row[1], self.trim[2]) if row is not None else unrevised_trim(nb)
+            self.trimpart.add(fn, row is not None, log_row)
+            if not log_row[3]:
+                self.log(f"[p:::] {fn.split('.')[0]} was dropped by --trim_q ({log_row[2] - log_row[1]} of {log_row[0]} bases left)......")
+                self.note(fn, True)
+                return
         if not self.args.test_mode:
             self.log(f"[p:::] {fn.split('.')[0]}_out.{self.args.output_format} was saved......")
         else:
@@ -1350,7 +1506,8 @@ class _FileRun:
             if bundle is not None and "device_stats" in bundle and not (hasattr(rv, "run_packed_raw") and hasattr(rv, "with_device_stats")):
                 bundle = _bundle_host_stats(bundle)   # an engine without the new calls: the host computes them after all
             form, route = _route_batch(rv, bundle, len(batch), self.pipelined, self.native_pool, self.device_merge, bool(self.report),
-                                       edits=bool(self.edits_dir), combined=self.sink is not None, summary=bool(self.sumpart))
+                                       edits=bool(self.edits_dir), combined=self.sink is not None, summary=bool(self.sumpart),
+                                       trim=self.trim is not None)
             if form is not None and bundle is None:
                 packed = prepare_many(cls, [rt for _, rt, _ in batch], rv.T)
             elif form is not None:
@@ -1364,13 +1521,15 @@ class _FileRun:
                     elif form != len(packed):
                         if self.report:
                             packed = cls.with_device_report(packed, self.tie_eps)
-                        if form == 16 or (form in (20, 22) and self.edits_dir):   # --edits: the list behind the merge (and the report)
+                        if form == 16 or (form in (20, 22, 27) and self.edits_dir):   # --edits: the list behind the merge (and the report)
                             packed = cls.with_device_edits(packed)
-                        if form == 20 or (form == 22 and self.sink is not None and hasattr(rv, "with_device_records")):
+                        if form == 20 or (form in (22, 27) and self.sink is not None and hasattr(rv, "with_device_records")):
                             # --combined: the records behind them all; seq / qual stay on the device
                             packed = cls.with_device_records(packed, [hs.record_name(fn) for fn, _, _ in batch], hand_back=False)
-                        if form == 22:                # --summary: the profile last, behind whatever the call carries
+                        if form == 22 or (form == 27 and self.sumpart):   # --summary: the profile, behind whatever the call carries
                             packed = cls.with_device_profile(packed)
+                        if form == 27:                # --trim_q: the bounds last; the records above are then those of the trimmed reads
+                            packed = cls.with_device_trim(packed, *self.trim)
         except Exception:
             packed = None
         if packed is None:
@@ -1411,6 +1570,10 @@ class _FileRun:
                     self.rep_rows[fn] = report_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual, self.tie_eps)[0]
                 if self.sumpart:
                     self.sum_rows[fn] = profile_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c)[0]
+                trim = None
+                if self.trim:
+                    tb, tl = _trim_rows_len(T, rt.bases, [len(np.asarray(rt.bases))], *c, *self.trim[:2])
+                    self.trim_rows[fn], trim = (int(tl[0]), tb[0]), (tb, self.trim[2])
                 if self.edits_dir:
                     write_edits(self.edits_dir, fn, edit_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual)[0], self.want_qual)
                 if self.pool is not None or self.sink is not None:
@@ -1418,17 +1581,17 @@ class _FileRun:
                     qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
                     payload = ("calls", T, np.asarray(rt.bases), np.asarray(a1), np.asarray(a2), qc)
                     if self.sink is None:
-                        task = self.pool.submit(deliver, self.spec, None, [fn], payload, self.native_threads)
+                        task = self.pool.submit(deliver, self.spec, None, [fn], payload, self.native_threads, trim)
                         self.finishing.append((task, fn, rt, fq))
                         continue
-                    (nb, err), = deliver(self.spec, self.sink, [fn], payload)      # the sink is this process' own: written here
+                    (nb, err), = deliver(self.spec, self.sink, [fn], payload, trim=trim)      # the sink is this process' own: written here
                     if err is not None:
                         raise RuntimeError(err)
                     self.finished(fn, nb)
                     continue
                 seq, qual = _finish_read(T, rt, *c, want_qual=self.want_qual)
-                deliver(self.args, None, [fn], ("text", seq, qual))
-                self.finished(fn, len(seq))
+                (nb, _), = deliver(self.args, None, [fn], ("text", seq, qual), trim=trim)
+                self.finished(fn, nb)
             except Exception as e:
                 self.fallback(fn, rt, fq, e)
 
@@ -1437,7 +1600,13 @@ class _FileRun:
         call that came back as revised reads - record + file alone (nrvh_write_records)."""
         try:
             fns, rts, fqs = map(list, zip(*batch))
+            trim = None
             if merged:
+                if len(outs) == 10:                   # a `with_device_trim` call: the bounds were found behind the merge, last output
+                    if self.trim:
+                        self.trim_rows.update(zip(fns, zip(np.diff(outs[2]).tolist(), outs[9])))
+                        trim = (outs[9], self.trim[2])
+                    outs = outs[:9]
                 if len(outs) == 9:                    # a `with_device_profile` call: the rows were counted behind the merge, last output
                     if self.sumpart:
                         self.sum_rows.update(zip(fns, outs[8]))
@@ -1455,14 +1624,18 @@ class _FileRun:
                     self.rep_rows.update(zip(fns, report_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2, self.want_qual, self.tie_eps)))
                 if self.sumpart:
                     self.sum_rows.update(zip(fns, profile_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2)))
+                if self.trim:
+                    tb, tl = _trim_rows_len(T, bundle["bases"], ev_len, p1, p2, a1, a2, *self.trim[:2])
+                    self.trim_rows.update(zip(fns, zip(tl.tolist(), tb)))
+                    trim = (tb, self.trim[2])
                 if self.edits_dir:
                     self.write_call_edits(fns, *edit_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2, self.want_qual))
                 qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
                 payload = ("bundle", T, bundle["bases"], ev_len, a1, a2, qc)
             if self.sink is None:
-                self.finishing.append((self.pool.submit(deliver, self.spec, None, fns, payload), fns, rts, fqs))
+                self.finishing.append((self.pool.submit(deliver, self.spec, None, fns, payload, True, trim), fns, rts, fqs))
                 return
-            for (nb, err), fn, rt, fq in zip(deliver(self.spec, self.sink, fns, payload), fns, rts, fqs):   # one append, here
+            for (nb, err), fn, rt, fq in zip(deliver(self.spec, self.sink, fns, payload, trim=trim), fns, rts, fqs):   # one append, here
                 if err is None:
                     self.finished(fn, nb)
                 else:
@@ -1552,7 +1725,7 @@ class _FileRun:
 def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None],
                   on_file: Optional[Callable[[str, bool], None]] = None, gpu_workers: int = 1,
                   core_share: Optional[int] = None, report_part: Optional[str] = None, combined_part: Optional[str] = None,
-                  summary_part: Optional[str] = None) -> dict:
+                  summary_part: Optional[str] = None, trim_part: Optional[str] = None) -> dict:
     """Revise `files` (names inside args.fast5_base_dir) with one engine.  The host stage (HDF5 parsing, event collapse,
     statistics) runs --thread parser workers that stay a bounded number of reads ahead of the device: THREADS of this process
     inside libnanorev_host.so (at most kNativePoolMax), or PROCESSES on the Python host stage without it / with NRV_HOST_THREADS=0.
@@ -1564,10 +1737,10 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
     divided them (a GPU worker pinned to its NUMA slice: `_worker`).  report_part (--report): the file this call appends
     one line per read to, ahead of on_file (`ReportPart`).  combined_part (--combined): the part this call appends
     every read's record to INSTEAD of writing one file per read (`CombinedPart`, `deliver`).  summary_part (--summary): as
-    report_part, for the summary's lines."""
+    report_part, for the summary's lines.  trim_part (--trim_log): as report_part, for the trim log's lines."""
     import contextlib
     with contextlib.ExitStack() as stack:             # its exit ends the run's threads and undoes what `_FileRun._start` did
-        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part, summary_part)
+        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part, summary_part, trim_part)
         batch, nev = [], 0                            # unbundled reads are grouped into device calls of >= batch_events events
         for entries, bundle in run.results():
             bundled = []
@@ -1579,6 +1752,7 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                     run.stats["failed"].append(fn)
                     run.report.add(fn, False, unrevised_row(0))
                     run.sumpart.add(fn, False, unrevised_profile(b""))
+                    run.trimpart.add(fn, False, unrevised_trim(0))
                     run.note(fn, False)
                 elif err is not None:
                     run.fallback(fn, rt, fq, err)
@@ -1797,7 +1971,8 @@ def revise_part(args, reviser, fn: str, k: int, parts: int):
         a1 = a2 = np.zeros(0, np.int8)
     qc = phred_chars(p1, p2, a1, a2) if args.output_format == "fastq" and len(a1) else None
     out = {"T": T, "n_ev": N, "lo": lo, "a1": np.array(a1, np.int8), "a2": np.array(a2, np.int8), "qc": qc}
-    if getattr(args, "report", None) or getattr(args, "edits", None) or getattr(args, "summary", None):   # the parent reports the read once its slices are merged: near-ties (and the edits' conf) need the rows
+    if getattr(args, "report", None) or getattr(args, "edits", None) or getattr(args, "summary", None) \
+            or getattr(args, "trim_q", None) is not None:   # the parent reports the read once its slices are merged: near-ties (and the edits' conf) need the rows
         out["p1"], out["p2"] = np.array(p1, np.float32), np.array(p2, np.float32)
     if k == 0:
         out["bases"], out["fq"] = np.asarray(rt.bases), fq
@@ -1839,7 +2014,8 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
                            on_file=lambda fn, ok: q.put(("file", rank, fn, bool(ok))), gpu_workers=world, core_share=share,
                            report_part=report_part_path(args.report, rank) if getattr(args, "report", None) else None,
                            combined_part=combined_part_path(args.combined, rank) if getattr(args, "combined", None) else None,
-                           summary_part=report_part_path(args.summary, rank) if getattr(args, "summary", None) else None)
+                           summary_part=report_part_path(args.summary, rank) if getattr(args, "summary", None) else None,
+                           trim_part=report_part_path(args.trim_log, rank) if getattr(args, "trim_log", None) else None)
         st["cpus"] = len(cpus) if cpus else 0
         for e in made:
             e.close()
@@ -1849,7 +2025,8 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
 
 
 def write_originals(args, files: Sequence[str], log: Callable[[str], None], report: Optional[ReportPart] = None,
-                    sink: Optional[CombinedPart] = None, summary: Optional[ReportPart] = None) -> List[str]:
+                    sink: Optional[CombinedPart] = None, summary: Optional[ReportPart] = None,
+                    trimlog: Optional[ReportPart] = None) -> List[str]:
     """The failure contract for reads whose WORKER is gone (NanoReviser.py:146-152 / :173-179): every
     file in `files` - the ones the dead worker never reported as final - gets its original basecalls
     written by this process (atomically, replacing whatever an earlier run left under that name).
@@ -1875,11 +2052,14 @@ def write_originals(args, files: Sequence[str], log: Callable[[str], None], repo
             report.add(fn, False, unrevised_row(nw))
         if summary is not None:
             summary.add(fn, False, unrevised_profile(text))
+        if trimlog is not None:
+            trimlog.add(fn, False, unrevised_trim(nw))
     return done
 
 
 def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[str], None], report: Optional[ReportPart] = None,
-                       sink: Optional[CombinedPart] = None, summary: Optional[ReportPart] = None):
+                       sink: Optional[CombinedPart] = None, summary: Optional[ReportPart] = None,
+                       trimlog: Optional[ReportPart] = None):
     """Parent side of the split reads: the slices' calls in slice order are the read's calls (window i of slice k is
     window lo_k + i of the read), merged and written exactly as an unsplit read's.  A read with a slice missing (its
     worker died) or failed gets its original basecalls (NanoReviser.py:146-152).  Returns (bases written, failed names)."""
@@ -1906,10 +2086,21 @@ def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[st
                     np.concatenate([p["p1"] for p in pl]) if have_p else None, np.concatenate([p["p2"] for p in pl]) if have_p else None,
                     (qc if qc is not None else np.zeros(0, np.uint8)) if args.output_format == "fastq" else None, T)[0],
                     args.output_format == "fastq")
-            (w, e2), = deliver(spec, sink, [fn], ("calls", T, pl[0]["bases"], a1, a2, qc), hostlib.load() is not None)
+            trim, rule = None, trim_rule(args)
+            if rule is not None and not have_p:
+                ok, err = False, "the slices carry no rows to trim by"
+            elif rule is not None:
+                tb, tl = _trim_rows_len(T, pl[0]["bases"], [N], np.concatenate([p["p1"] for p in pl]),
+                                        np.concatenate([p["p2"] for p in pl]), a1, a2, *rule[:2])
+                trim = (tb, rule[2])
+        if ok:
+            (w, e2), = deliver(spec, sink, [fn], ("calls", T, pl[0]["bases"], a1, a2, qc), hostlib.load() is not None, trim)
             if e2 is None:
                 nb += w
-                log(f"[p:::] {fn.split('.')[0]}_out.{args.output_format} was saved...... ({n} slices)")
+                if trim is not None and trimlog is not None:
+                    trimlog.add(fn, True, trim_log_row(tl[0], tb[0], rule[2]))
+                log(f"[p:::] {fn.split('.')[0]}_out.{args.output_format} was saved...... ({n} slices)" if trim is None or hs.trim_kept(tb, rule[2])[0]
+                    else f"[p:::] {fn.split('.')[0]} was dropped by --trim_q...... ({n} slices)")
                 if report is not None and report:
                     row = hs.revision_report(
                         hostlib.bases_u8(pl[0]["bases"]), [N], a1, a2,
@@ -1923,7 +2114,7 @@ def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[st
                 continue
             err = e2
         log(f"[！！！Error] revising {fn.split('.')[0]}: {err}; writing the original basecalls")
-        write_originals(args, [fn], log, report, sink, summary)
+        write_originals(args, [fn], log, report, sink, summary, trimlog)
         failed.append(fn)
     return nb, failed
 
@@ -2010,6 +2201,14 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
             os.makedirs(d, exist_ok=True)
     parent_summary = ReportPart(report_part_path(args.summary, "parent") if args.summary else None, SUMMARY_COLS)
     sum_part0 = report_part_path(args.summary, 0) if args.summary else None
+    trim_log = getattr(args, "trim_log", None)
+    if trim_log:                          # --trim_log: parts and a parent-side merge as for --report
+        clear_report_parts(trim_log)
+        d = os.path.dirname(trim_log)
+        if d:
+            os.makedirs(d, exist_ok=True)
+    parent_trim = ReportPart(report_part_path(trim_log, "parent") if trim_log else None, 4)
+    trim_part0 = report_part_path(trim_log, 0) if trim_log else None
     if args.combined:                     # --combined: a part per process too, `merge_combined` ends the run
         clear_combined_parts(args.combined)
     parent_sink = CombinedPart(combined_part_path(args.combined, "parent"), args.output_format == "fastq") if args.combined else None
@@ -2049,7 +2248,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
     if reviser_factory is not None:       # in-process (tests / embedding): one engine, no sharding
         rv = reviser_factory(args, 0)
         stats = [process_files(args, names, rv, print, report_part=report_part_path(args.report, 0) if args.report else None,
-                               combined_part=part0, summary_part=sum_part0)]
+                               combined_part=part0, summary_part=sum_part0, trim_part=trim_part0)]
     else:
         # the command line needs no torch: without it a process starts ~1.5 s sooner.  (engine.py imports
         # torch first only so that a LATER torch import in the same process finds one HIP runtime.)
@@ -2078,7 +2277,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
                 made.append((worker_factory or _default_factory)(args, 0))
                 return made[-1]                       # called once per engine (process_files: NRV_CLI_ENGINES)
             stats = [process_files(args, names, make, print, report_part=report_part_path(args.report, 0) if args.report else None,
-                                   combined_part=part0, summary_part=sum_part0)]
+                                   combined_part=part0, summary_part=sum_part0, trim_part=trim_part0)]
             for rv in made:
                 rv.close()
         else:
@@ -2089,7 +2288,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
             res = run_workers(args, shards, worker_factory, part_shards=part_shards, parts_out=parts_got)
             stats = [s for _, s, _, _ in res if s is not None]
             if split_fns:
-                nb_split, failed_split = finish_split_reads(args, split_fns, parts_got, print, parent_report, parent_sink, parent_summary)
+                nb_split, failed_split = finish_split_reads(args, split_fns, parts_got, print, parent_report, parent_sink, parent_summary, parent_trim)
                 stats.append({"reads": len(split_fns), "bases": nb_split, "failed": failed_split, "host_s": 0.0, "engine_s": 0.0})
                 if failed_split:
                     rc = 3
@@ -2099,7 +2298,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
                           f"unfinished reads", file=sys.stderr)
                     # what the worker reported final stays (its failed reads keep their failed_reads entry);
                     # everything else - started or not, whatever lies on disk - is written unrevised
-                    lost = write_originals(args, [f for f in shards[r] if f not in final], print, parent_report, parent_sink, parent_summary)
+                    lost = write_originals(args, [f for f in shards[r] if f not in final], print, parent_report, parent_sink, parent_summary, parent_trim)
                     lost += [f for f, ok in final.items() if not ok]
                     stats.append({"reads": len(shards[r]), "bases": 0, "failed": lost, "host_s": 0.0, "engine_s": 0.0})
                     rc = 3
@@ -2109,6 +2308,9 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
     parent_summary.close()
     if args.summary:
         merge_report(args.summary, all_names, table=SUMMARY_TABLE)
+    parent_trim.close()
+    if trim_log:
+        merge_report(trim_log, all_names, table=TRIM_TABLE)
     if args.combined:
         parent_sink.close()
         merge_combined(args.combined, args.output_format == "fastq")

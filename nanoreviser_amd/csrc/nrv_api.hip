@@ -479,17 +479,21 @@ struct DevModel {
 // ---- a merged raw-read call (nrv_revise_reads_raw*_begin; nrv_merge_calls* is its test twin) -------------------------------
 // The merged block of a call of N events, n windows, n_reads reads - offsets into one device allocation:
 //   [off i64 x (n_reads + 1) | seq | qual | report u64 x n_reads x 24 | edit_off i64 x (n_reads + 1) | rec_off i64 x (n_reads + 1) |
-//    profile u64 x n_reads x 48]      what comes back in one copy of `dl` bytes, mirrored in page-locked memory (nrv_merge.h,
-//                                     nrv_report.h, nrv_edits.h, nrv_pack.h, nrv_profile.h); the report, edit_off, rec_off and
-//                                     the profile only where asked for - without them the layout is the merge's own.  A records
-//                                     call that hands back neither seq nor qual leaves those two on the device
+//    profile u64 x n_reads x 48 | trim i64 x n_reads x 2]
+//                                     what comes back in one copy of `dl` bytes, mirrored in page-locked memory (nrv_merge.h,
+//                                     nrv_report.h, nrv_edits.h, nrv_pack.h, nrv_profile.h, nrv_trim.h); the report, edit_off,
+//                                     rec_off, the profile and the trim only where asked for - without them the layout is the
+//                                     merge's own.  A records call that hands back neither seq nor qual leaves those two on
+//                                     the device
 //   [rec u32 x N | tile u64]          the merge kernels' scratch
 //   [edits nrv_edit x n | etile u64]  the edit records, fetched by their used prefix in a copy of their own, and their scratch;
 //                                     only where asked for
 //   [blob]                            the FASTA / FASTQ records of blob_cap bytes, fetched by their used prefix like the edit
 //                                     records; only where asked for
+//   [tq u8 x (N + n) | acc u64 x n_reads x 2]   the trim kernels' scratch: Phred per output character, the bounds' accumulators;
+//                                     only where asked for
 // Every part is 256-byte aligned.
-struct MergeLayout { size_t seq, qual, rep, eoff, roff, prof, rec, tile, edits, etile, blob, dl, bytes; };
+struct MergeLayout { size_t seq, qual, rep, eoff, roff, prof, trim, rec, tile, edits, etile, blob, tq, acc, dl, bytes; };
 
 // What a merged call reads besides the raw reads.  Consumed inside _begin: the caller's pointers are dead once it returns, so
 // nothing that outlives _begin keeps one (the slot keeps the VALUES of both threshold sets for the re-run of nrv_reads_raw_end)
@@ -499,7 +503,12 @@ struct MergeIn {
   const uint8_t* names = nullptr;       // nrv_revise_reads_raw_records_begin
   const int64_t* name_off = nullptr;
   const float* prof_thr = nullptr;      // nrv_revise_reads_raw_profile_begin: its own 39 thresholds
+  const float* trim_thr = nullptr;      // nrv_revise_reads_raw_trim_begin: its own 39 thresholds, and the rule
+  int Q = 0, W = 0;
+  int64_t min_len = 0;
 };
+// The trim's rule as the kernels take it: the VALUES a slot keeps for the re-run are of this form too (thr points into the slot)
+struct TrimRule { const float* thr = nullptr; int Q = 0, W = 0; int64_t min_len = 0; };
 // What a merged call hands back and where: the caller keeps these arrays alive until _end.  A null pointer: not asked for.
 // The entry points fill it (and MergeIn, and RawIn) as a positional aggregate: the ORDER of the members is relied on
 struct MergeOut {
@@ -512,6 +521,7 @@ struct MergeOut {
   uint8_t* blob = nullptr;              // the records and [n_reads + 1]; rec_off decides
   int64_t* rec_off = nullptr;
   uint64_t* profile = nullptr;          // [n_reads][48]
+  int64_t* trim = nullptr;              // [n_reads][2]
 };
 // Where a merged call's inputs lie on the device, and its merged block
 struct MergeView {
@@ -607,7 +617,9 @@ struct nrv_handle {
     MergeLayout m = {};
     MergeOut out;
     bool want_q = false;
-    float thr[kPhredSteps] = {0}, prof_thr[kPhredSteps] = {0};
+    float thr[kPhredSteps] = {0}, prof_thr[kPhredSteps] = {0}, trim_thr[kPhredSteps] = {0};
+    int trim_Q = 0, trim_W = 0;
+    int64_t trim_min_len = 0;
     size_t blob_cap = 0;
     int64_t N = 0, n = 0;
     int n_reads = 0;
@@ -1596,6 +1608,7 @@ static int merged_collect(nrv_handle* h, const char* who, const char* who_edits,
   if (want_q && o.qual) memcpy(o.qual, head + m.qual, (size_t)total);
   if (o.report) memcpy(o.report, head + m.rep, (size_t)v.n_reads * kReportCols * 8);
   if (o.profile) memcpy(o.profile, head + m.prof, (size_t)v.n_reads * kProfileCols * 8);
+  if (o.trim) memcpy(o.trim, head + m.trim, (size_t)v.n_reads * 16);
   int rc = NRV_OK;
   if (o.edit_off) {
     const int64_t n_ed = ((const int64_t*)(head + m.eoff))[v.n_reads];
@@ -2080,6 +2093,37 @@ static ProfileArgs profile_args(const MergeArgs& m, const float* p1, const float
   memcpy(a.thr, thr, sizeof a.thr);
   return a;
 }
+// The window and finish kernels (nrv_trim.h) on the qualities a.q: the accumulators start from 0xFF bytes HERE, in stream order
+// ahead of the launch (and behind any NRV_POISON fill) - every call of this function starts its bounds from nothing.
+static int trim_bounds_enqueue(nrv_handle* h, const TrimArgs& a) {
+  if (a.n_reads <= 0) return NRV_OK;
+  HIPCHK(h, hipMemsetAsync(a.acc, 0xFF, (size_t)a.n_reads * 16, h->stream));
+  const unsigned tiles = (unsigned)((a.cap + 255) / 256);
+  if (tiles > 0) hipLaunchKernelGGL(trim_window_kernel, dim3(tiles), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(trim_finish_kernel, dim3((unsigned)((a.n_reads + 255) / 256)), dim3(256), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return NRV_OK;
+}
+// The trim kernels behind merge_enqueue (and the report / edit launches), AHEAD of pack_enqueue, which reads `trim`: they read the
+// records, the tile offsets and the read offsets the merge left, and the rows
+static int trim_enqueue(nrv_handle* h, const MergeArgs& m, const float* p1, const float* p2, const TrimRule& t, void* tq, void* acc,
+                        void* trim) {
+  if (m.n_reads <= 0 || m.N <= 0) return NRV_OK;
+  TrimQualArgs q;
+  q.reads = m.reads; q.n_reads = m.n_reads; q.T = m.T; q.N = m.N;
+  q.a1 = m.a1; q.a2 = m.a2; q.p1 = p1; q.p2 = p2;
+  q.rec = m.rec; q.tile = m.tile; q.tq = (unsigned char*)tq;
+  q.cap = m.N + (m.N - m.T > 0 ? m.N - m.T : 0);
+  memcpy(q.thr, t.thr, sizeof q.thr);
+  const unsigned tiles = (unsigned)((m.N + kMergeTile - 1) / kMergeTile);
+  hipLaunchKernelGGL(trim_qual_kernel, dim3(tiles), dim3(256), 0, h->stream, q);
+  TrimArgs a;
+  a.n_reads = m.n_reads; a.Q = t.Q; a.W = t.W; a.bias = 0;
+  a.off = m.off; a.q = (const unsigned char*)tq; a.cap = q.cap;
+  a.acc = (unsigned long long*)acc; a.trim = (long long*)trim;
+  return trim_bounds_enqueue(h, a);
+}
+static bool trim_rule_ok(int Q, int W, int64_t min_len) { return Q >= 1 && Q <= 40 && W >= 1 && W <= kTrimMaxW && min_len >= 0; }
 // bytes the records of a call can take: hoststage.pack_records on N + max(N - T, 0) characters at the most
 static size_t blob_capacity(int64_t N, int64_t n, int n_reads, int64_t name_bytes, bool fastq) {
   const size_t q = fastq ? 2 : 1;
@@ -2092,23 +2136,27 @@ static bool names_ok(const uint8_t* names, const int64_t* name_off, int n_reads)
   return names != nullptr || name_off[n_reads] == 0;
 }
 // hoststage.pack_records on the host, for the calls that have no window (N <= T): qual == nullptr with fastq: every quality is '#'
+// trim / min_len: as nrv_pack_records_trim (null: the whole reads)
 static void records_host(const uint8_t* seq, const uint8_t* qual, const int64_t* off, int n_reads, const uint8_t* names,
-                         const int64_t* name_off, bool fastq, uint8_t* blob, int64_t* rec_off) {
+                         const int64_t* name_off, bool fastq, uint8_t* blob, int64_t* rec_off, const int64_t* trim = nullptr,
+                         int64_t min_len = 0) {
   int64_t p = 0;
   for (int r = 0; r < n_reads; ++r) {
-    const int64_t nl = name_off[r + 1] - name_off[r], L = off[r + 1] - off[r];
+    const int64_t nl = name_off[r + 1] - name_off[r];
+    const int64_t s0 = off[r] + (trim ? trim[2 * r] : 0), L = trim ? trim[2 * r + 1] - trim[2 * r] : off[r + 1] - off[r];
     rec_off[r] = p;
+    if (trim && L < min_len) continue;
     blob[p++] = fastq ? '@' : '>';
     if (nl > 0) memcpy(blob + p, names + name_off[r], (size_t)nl);
     p += nl;
     blob[p++] = '\n';
-    if (L > 0) memcpy(blob + p, seq + off[r], (size_t)L);
+    if (L > 0) memcpy(blob + p, seq + s0, (size_t)L);
     p += L;
     blob[p++] = '\n';
     if (fastq) {
       blob[p++] = '+';
       blob[p++] = '\n';
-      if (L > 0) { if (qual) memcpy(blob + p, qual + off[r], (size_t)L); else memset(blob + p, '#', (size_t)L); }
+      if (L > 0) { if (qual) memcpy(blob + p, qual + s0, (size_t)L); else memset(blob + p, '#', (size_t)L); }
       p += L;
       blob[p++] = '\n';
     }
@@ -2126,13 +2174,16 @@ static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, const MergeOu
   m.eoff = m.rep + (o.report ? up((size_t)n_reads * kReportCols * 8) : 0);
   m.roff = m.eoff + (o.edit_off ? up(((size_t)n_reads + 1) * 8) : 0);
   m.prof = m.roff + (o.rec_off ? up(((size_t)n_reads + 1) * 8) : 0);
-  m.dl = m.prof + (o.profile ? up((size_t)n_reads * kProfileCols * 8) : 0);
+  m.trim = m.prof + (o.profile ? up((size_t)n_reads * kProfileCols * 8) : 0);
+  m.dl = m.trim + (o.trim ? up((size_t)n_reads * 16) : 0);
   m.rec = m.dl;
   m.tile = m.rec + up((size_t)N * 4);
   m.edits = m.tile + up(tiles * 8);
   m.etile = m.edits + (o.edit_off ? up((size_t)n * sizeof(nrv_edit)) : 0);
   m.blob = m.etile + (o.edit_off ? up(tiles * 8) : 0);
-  m.bytes = m.blob + (o.rec_off ? up(blob_cap) : 0);
+  m.tq = m.blob + (o.rec_off ? up(blob_cap) : 0);
+  m.acc = m.tq + (o.trim ? up(cap) : 0);
+  m.bytes = m.acc + (o.trim ? up((size_t)n_reads * 16) : 0);
   return m;
 }
 // No window at all (N <= T): the reads come back as they are, on the host
@@ -2166,22 +2217,34 @@ static void profile_nothing(const uint8_t* bases, const nrv_read_desc* reads, in
     }
   }
 }
+// ... and its trim (hoststage.trim_bounds on a call without a window): every character has Phred 2, so every position with a
+// whole window in the read is good or none is
+static void trim_nothing(const nrv_read_desc* reads, int n_reads, int Q, int W, int64_t* trim) {
+  for (int r = 0; r < n_reads; ++r) {
+    const bool any = reads[r].ev_len >= W && 2 * W >= Q * W;
+    trim[2 * r] = 0;
+    trim[2 * r + 1] = any ? reads[r].ev_len : 0;
+  }
+}
 // ... and everything a merged call asks for, for both callers that can meet N <= T
 static void merged_nothing(const MergeIn& in, const MergeOut& o, const nrv_read_desc* reads, int n_reads, int64_t N) {
   merge_nothing(in.bases, reads, n_reads, N, o.seq, in.q_thr ? o.qual : nullptr, o.off);
   if (o.report) report_nothing(reads, n_reads, wants_quality(in.q_thr, o), o.report);
   if (o.edit_off) memset(o.edit_off, 0, ((size_t)n_reads + 1) * 8);   // no window, no record
-  if (o.rec_off) records_host(in.bases, nullptr, o.off, n_reads, in.names, in.name_off, in.q_thr != nullptr, o.blob, o.rec_off);
+  if (o.trim) trim_nothing(reads, n_reads, in.Q, in.W, o.trim);
+  if (o.rec_off) records_host(in.bases, nullptr, o.off, n_reads, in.names, in.name_off, in.q_thr != nullptr, o.blob, o.rec_off,
+                              o.trim, in.min_len);
   if (o.profile) profile_nothing(in.bases, reads, n_reads, o.profile);
 }
 
 // The kernels of a merged call behind whatever produced v.a1 / a2 / p1 / p2 on the compute stream: the merge, then what `o` asks
 // for - report, edit list, records, profile - each reading what the merge left.  q_thr: the thresholds of the quality (null:
 // none is written); the merge reads the rows only for a quality, the report and the edits whenever there are rows, the profile
-// always.  A second pass over the same block (the re-run of nrv_reads_raw_end) counts nothing twice: report_enqueue and
-// profile_enqueue zero their blocks in stream order, the edit and record kernels store plainly into every word that is read back
+// always, and so does the trim (t: its rule), whose bounds the records are then cut to.  A second pass over the same block (the
+// re-run of nrv_reads_raw_end) counts nothing twice: report_enqueue and profile_enqueue zero their blocks and trim_bounds_enqueue
+// resets its accumulators in stream order, the edit and record kernels store plainly into every word that is read back
 static int merged_enqueue(nrv_handle* h, const MergeView& v, const MergeLayout& m, const MergeOut& o, const float* q_thr,
-                          const float* prof_thr, size_t blob_cap) {
+                          const float* prof_thr, size_t blob_cap, const TrimRule& t = TrimRule{}) {
   const bool want_q = q_thr != nullptr;
   MergeArgs a;
   a.reads = v.reads; a.n_reads = v.n_reads; a.T = h->T; a.N = v.N;
@@ -2195,6 +2258,7 @@ static int merged_enqueue(nrv_handle* h, const MergeView& v, const MergeLayout& 
   int rc = merge_enqueue(h, a);
   if (!rc && o.report) rc = report_enqueue(h, report_args(a, v.p1, v.p2, want_q, o.tie_eps, v.blk + m.rep));
   if (!rc && o.edit_off) rc = edits_enqueue(h, edits_args(a, v.p1, v.p2, want_q, v.blk + m.etile, v.blk + m.eoff, v.blk + m.edits));
+  if (!rc && o.trim) rc = trim_enqueue(h, a, v.p1, v.p2, t, v.blk + m.tq, v.blk + m.acc, v.blk + m.trim);
   if (!rc && o.rec_off) {
     PackArgs k;
     k.n_reads = v.n_reads; k.fastq = want_q ? 1 : 0;
@@ -2202,11 +2266,14 @@ static int merged_enqueue(nrv_handle* h, const MergeView& v, const MergeLayout& 
     k.seq = a.seq; k.qual = (const unsigned char*)(v.blk + m.qual);
     k.rec_off = (long long*)(v.blk + m.roff); k.blob = (unsigned char*)(v.blk + m.blob);
     k.cap = blob_cap;
+    k.trim = o.trim ? (const long long*)(v.blk + m.trim) : nullptr; k.min_len = t.min_len;
     rc = pack_enqueue(h, k);
   }
   if (!rc && o.profile) rc = profile_enqueue(h, profile_args(a, v.p1, v.p2, prof_thr, v.blk + m.prof));
   return rc;
 }
+// the trim rule a slot keeps
+static TrimRule slot_trim(const nrv_handle::RawSlot& sl) { return TrimRule{sl.trim_thr, sl.trim_Q, sl.trim_W, sl.trim_min_len}; }
 // the merged part of a slot's call
 static MergeView slot_view(const nrv_handle::RawSlot& sl) {
   const char* const d = sl.d_out + 64;   // p1 / p2 are in the output block whether a quality is wanted or not
@@ -2318,6 +2385,10 @@ static int raw_begin(nrv_handle* h, const RawIn& in, float* p1, float* p2, int8_
     sl.want_q = wants_quality(mr->q_thr, sl.out);
     if (sl.want_q) memcpy(sl.thr, mr->q_thr, sizeof sl.thr);    // the VALUES: the caller's inputs are gone when _end re-runs the call
     if (sl.out.profile) memcpy(sl.prof_thr, mr->prof_thr, sizeof sl.prof_thr);
+    if (sl.out.trim) {
+      memcpy(sl.trim_thr, mr->trim_thr, sizeof sl.trim_thr);
+      sl.trim_Q = mr->Q; sl.trim_W = mr->W; sl.trim_min_len = mr->min_len;
+    }
     if ((sl.out.edit_off || records) && !h->edit_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->edit_stream, hipStreamNonBlocking));
     if (m.bytes > sl.cap_mrg) {
       (void)hipFree(sl.d_mrg); (void)hipHostFree(sl.pin_mrg);
@@ -2345,7 +2416,7 @@ static int raw_begin(nrv_handle* h, const RawIn& in, float* p1, float* p2, int8_
     if (mr) {
       for (size_t i = 0; i + 4 <= sl.m.dl; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
       if (sl.out.edit_off) for (size_t i = sl.m.edits; i + 4 <= sl.m.etile; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
-      if (records) for (size_t i = sl.m.blob; i + 4 <= sl.m.bytes; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
+      if (records) for (size_t i = sl.m.blob; i + 4 <= sl.m.tq; i += 4) memcpy(sl.pin_mrg + i, &h->poison, 4);
       if ((rc = poison_fill(h, sl.d_mrg, sl.cap_mrg, h->stream))) return rc;
     }
   }
@@ -2373,7 +2444,7 @@ static int raw_begin(nrv_handle* h, const RawIn& in, float* p1, float* p2, int8_
                        nullptr, nullptr);
   // the merge reads the slot's output block: behind the call's last launch group, ahead of ev_done
   if (rc || (rc = raw_enqueue(h, sl)) ||
-      (mr && (rc = merged_enqueue(h, slot_view(sl), sl.m, sl.out, sl.want_q ? sl.thr : nullptr, sl.prof_thr, sl.blob_cap)))) {
+      (mr && (rc = merged_enqueue(h, slot_view(sl), sl.m, sl.out, sl.want_q ? sl.thr : nullptr, sl.prof_thr, sl.blob_cap, slot_trim(sl))))) {
     (void)hipStreamSynchronize(h->stream);                      // part of the call may be enqueued: nothing of it may outlive the slot
     return rc;
   }
@@ -2395,6 +2466,8 @@ static int revise_begin(nrv_handle* h, const char* who, const char* missing, con
   else if (missing) bad = missing;
   else if (mo.edits && !mo.edit_off) bad = "edits without edit_off";
   else if (!mo.rec_off && (mr.names || mr.name_off || mo.blob)) bad = "names / name_off / blob without rec_off";
+  else if ((mr.prof_thr == nullptr) != (mo.profile == nullptr)) bad = "prof_thr and profile go together";
+  else if (mo.trim && !trim_rule_ok(mr.Q, mr.W, mr.min_len)) bad = "Q must be in 1 .. 40, W in 1 .. 64 and min_len >= 0";
   if (h && bad) { h->err = std::string(who) + ": " + bad; return NRV_E_INVALID; }
   return raw_begin(h, in, nullptr, nullptr, nullptr, nullptr, ticket, &mr, &mo);
 }
@@ -2533,6 +2606,34 @@ int nrv_revise_reads_raw_profile(nrv_handle* h, const int16_t* raw, int64_t n_ra
   });
 }
 
+// prof_thr / profile == NULL: no profile
+int nrv_revise_reads_raw_trim_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                    const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                    const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                    uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                    nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                    uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                    const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim, int* ticket) {
+  return revise_begin(h, "nrv_revise_reads_raw_trim_begin", trim_thr && trim ? nullptr : "null trim_thr / trim",
+                      RawIn{raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device},
+                      MergeIn{bases, q_thr, names, name_off, prof_thr, trim_thr, Q, W, min_len},
+                      MergeOut{seq, qual, off, report, tie_eps, edits, edit_off, blob, rec_off, profile, trim}, ticket);
+}
+
+int nrv_revise_reads_raw_trim(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                              const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                              const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                              uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                              nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                              uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                              const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim) {
+  return begin_then_end(h, [&](int* t) {
+    return nrv_revise_reads_raw_trim_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                           seq, qual, off, tie_eps, report, edits, edit_off, names, name_off, blob, rec_off,
+                                           prof_thr, profile, trim_thr, Q, W, min_len, trim, t);
+  });
+}
+
 int nrv_reads_raw_end(nrv_handle* h, int ticket) {
   int rc = check_handle(h);
   if (rc) return rc;
@@ -2552,7 +2653,7 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
     if (rc2) return rc2;
     // a merged call: its kernels again, in stream order behind the re-run they read, on a block that holds nothing of the first pass
     if (sl.out.off && ((rc = poison_fill(h, sl.d_mrg, sl.cap_mrg, h->stream)) ||
-                       (rc = merged_enqueue(h, slot_view(sl), sl.m, sl.out, sl.want_q ? sl.thr : nullptr, sl.prof_thr, sl.blob_cap))))
+                       (rc = merged_enqueue(h, slot_view(sl), sl.m, sl.out, sl.want_q ? sl.thr : nullptr, sl.prof_thr, sl.blob_cap, slot_trim(sl)))))
       return rc;
     if ((rc = slot_download(h, sl, h->stream))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2659,10 +2760,11 @@ int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32
 }
 
 // nrv_merge_calls (o.report == nullptr: that call, to the byte), nrv_merge_calls_report, (o.edit_off != nullptr)
-// nrv_merge_calls_edits and (o.profile != nullptr) nrv_merge_calls_profile
+// nrv_merge_calls_edits, (o.profile != nullptr) nrv_merge_calls_profile and (o.trim != nullptr; `more`: its rule, and the names of
+// its records) nrv_merge_calls_trim
 static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
                             const float* p1, const float* p2, int64_t n_win, const float* q_thr, const MergeOut& o,
-                            const float* prof_thr = nullptr) {
+                            const float* prof_thr = nullptr, const MergeIn& more = MergeIn{}) {
   int rc = check_handle(h);
   if (rc) return rc;
   if (n_reads < 0 || n_win < 0 || !o.off || (n_reads > 0 && !ev_len)) { h->err = "nrv_merge_calls: bad arguments"; return NRV_E_INVALID; }
@@ -2679,19 +2781,28 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
     h->err = "nrv_merge_calls: n_win is not sum(ev_len) - T, or a null array";
     return NRV_E_INVALID;
   }
+  size_t blob_cap = 0;
+  if (o.rec_off) {
+    if (!names_ok(more.names, more.name_off, n_reads)) { h->err = "nrv_merge_calls_trim: null names / name_off, or offsets that do not ascend from 0"; return NRV_E_INVALID; }
+    blob_cap = blob_capacity(N, n, n_reads, more.name_off[n_reads], q_thr != nullptr);
+    if ((blob_cap > 0 && !o.blob) || blob_cap >= ((size_t)1 << 32)) { h->err = "nrv_merge_calls_trim: null blob (or records of 4 GiB and more)"; return NRV_E_INVALID; }
+  }
   if (n == 0) {
-    merged_nothing(MergeIn{bases, q_thr}, o, rd.data(), n_reads, N);
+    MergeIn in = more;
+    in.bases = bases; in.q_thr = q_thr;
+    merged_nothing(in, o, rd.data(), n_reads, N);
     return NRV_OK;
   }
   if (o.edit_off && !o.edits) { h->err = "nrv_merge_calls_edits: null edits"; return NRV_E_INVALID; }
-  // one block of its own: [reads | bases | a1 | a2 | p1 | p2 | merged block]
+  // one block of its own: [reads | bases | a1 | a2 | p1 | p2 | name_off | names | merged block]
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const MergeLayout m = merge_layout(N, n, n_reads, o, 0);
-  // the rows go up for a quality - and without one where they are given and the report's near-tie column, the edits' conf or the
-  // profile reads them
-  const bool have_p = want_q || ((o.report || o.edit_off || o.profile) && p1 && p2);
+  const MergeLayout m = merge_layout(N, n, n_reads, o, blob_cap);
+  // the rows go up for a quality - and without one where they are given and the report's near-tie column, the edits' conf, the
+  // profile or the trim reads them
+  const bool have_p = want_q || ((o.report || o.edit_off || o.profile || o.trim) && p1 && p2);
   const size_t o_b = up((size_t)n_reads * sizeof(SegRead)), o_a1 = o_b + up((size_t)N), o_a2 = o_a1 + up((size_t)n);
-  const size_t o_p1 = o_a2 + up((size_t)n), o_p2 = o_p1 + (have_p ? up((size_t)n * 24) : 0), o_m = o_p2 + (have_p ? up((size_t)n * 20) : 0);
+  const size_t o_p1 = o_a2 + up((size_t)n), o_p2 = o_p1 + (have_p ? up((size_t)n * 24) : 0), o_no = o_p2 + (have_p ? up((size_t)n * 20) : 0);
+  const size_t o_nm = o_no + (o.rec_off ? up(((size_t)n_reads + 1) * 8) : 0), o_m = o_nm + (o.rec_off ? up((size_t)more.name_off[n_reads]) : 0);
   const size_t bytes = o_m + m.bytes;
   char* d = nullptr;
   HIPCHK(h, hipMalloc((void**)&d, bytes));
@@ -2707,10 +2818,15 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
       HIPCHK(h, hipMemcpyAsync(d + o_p1, p1, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
       HIPCHK(h, hipMemcpyAsync(d + o_p2, p2, (size_t)n * 20, hipMemcpyHostToDevice, h->stream));
     }
+    if (o.rec_off) {
+      HIPCHK(h, hipMemcpyAsync(d + o_no, more.name_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
+      if (more.name_off[n_reads] > 0) HIPCHK(h, hipMemcpyAsync(d + o_nm, more.names, (size_t)more.name_off[n_reads], hipMemcpyHostToDevice, h->stream));
+    }
     const MergeView v{(const SegRead*)d, n_reads, N, (const unsigned char*)(d + o_b), (const signed char*)(d + o_a1),
                       (const signed char*)(d + o_a2), have_p ? (const float*)(d + o_p1) : nullptr,
-                      have_p ? (const float*)(d + o_p2) : nullptr, nullptr, nullptr, d + o_m};
-    if ((rc2 = merged_enqueue(h, v, m, o, want_q ? q_thr : nullptr, prof_thr, 0))) return rc2;
+                      have_p ? (const float*)(d + o_p2) : nullptr, (const long long*)(d + o_no), (const unsigned char*)(d + o_nm), d + o_m};
+    if ((rc2 = merged_enqueue(h, v, m, o, want_q ? q_thr : nullptr, prof_thr, blob_cap, TrimRule{more.trim_thr, more.Q, more.W, more.min_len})))
+      return rc2;
     HIPCHK(h, hipMemcpyAsync(back.data(), d + o_m, m.dl, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     // a test twin, not timed: the used prefix of the edit records in a plain copy, straight into the caller's array
@@ -2718,7 +2834,7 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
       HIPCHK(h, hipMemcpy(dst, d + o_m + at, bytes, hipMemcpyDeviceToHost));
       return NRV_OK;
     };
-    return merged_collect(h, "nrv_merge_calls", "nrv_merge_calls_edits", back.data(), v, m, o, want_q, 0, fetch);
+    return merged_collect(h, "nrv_merge_calls", "nrv_merge_calls_edits", back.data(), v, m, o, want_q, blob_cap, fetch);
   };
   rc = run();
   if (rc) (void)hipStreamSynchronize(h->stream);
@@ -2756,12 +2872,79 @@ int nrv_merge_calls_profile(nrv_handle* h, const uint8_t* bases, const int64_t* 
   return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, o, prof_thr);
 }
 
+int nrv_merge_calls_trim(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                         const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                         const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                         const uint8_t* names, const int64_t* name_off, uint8_t* blob, int64_t* rec_off) {
+  if (h && (!trim_thr || (n_reads > 0 && !trim))) { h->err = "nrv_merge_calls_trim: null trim_thr / trim"; return NRV_E_INVALID; }
+  if (h && (!p1 || !p2) && n_win > 0) { h->err = "nrv_merge_calls_trim: null p1 / p2"; return NRV_E_INVALID; }
+  if (h && !trim_rule_ok(Q, W, min_len)) { h->err = "nrv_merge_calls_trim: Q must be in 1 .. 40, W in 1 .. 64 and min_len >= 0"; return NRV_E_INVALID; }
+  if (h && !rec_off && (names || name_off || blob)) { h->err = "nrv_merge_calls_trim: names / name_off / blob without rec_off"; return NRV_E_INVALID; }
+  static int64_t none[2];
+  MergeOut o{seq, qual, off};
+  o.blob = blob; o.rec_off = rec_off;
+  o.trim = trim ? trim : none;
+  MergeIn more;
+  more.names = names; more.name_off = name_off;
+  more.trim_thr = trim_thr; more.Q = Q; more.W = W; more.min_len = min_len;
+  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, o, nullptr, more);
+}
+
+int nrv_trim_reads(nrv_handle* h, const uint8_t* qual, const int64_t* off, int n_reads, int Q, int W, int64_t* trim) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (n_reads < 0 || !off || off[0] != 0 || (n_reads > 0 && !trim)) { h->err = "nrv_trim_reads: bad arguments"; return NRV_E_INVALID; }
+  if (!trim_rule_ok(Q, W, 0)) { h->err = "nrv_trim_reads: Q must be in 1 .. 40 and W in 1 .. 64"; return NRV_E_INVALID; }
+  for (int r = 0; r < n_reads; ++r) if (off[r + 1] < off[r]) { h->err = "nrv_trim_reads: off does not ascend"; return NRV_E_INVALID; }
+  if (n_reads == 0) return NRV_OK;
+  const int64_t total = off[n_reads];
+  if (total > 0 && !qual) { h->err = "nrv_trim_reads: null qual"; return NRV_E_INVALID; }
+  // one block of its own: [off | qual | acc | trim]
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t nb = ((size_t)n_reads + 1) * 8, tb = (size_t)n_reads * 16;
+  const size_t o_q = up(nb), o_acc = o_q + up((size_t)total), o_trim = o_acc + up(tb), bytes = o_trim + up(tb);
+  char* d = nullptr;
+  HIPCHK(h, hipMalloc((void**)&d, bytes));
+  auto run = [&]() -> int {
+    int rc2 = poison_fill(h, d, bytes, h->stream);
+    if (rc2) return rc2;
+    HIPCHK(h, hipMemcpyAsync(d, off, nb, hipMemcpyHostToDevice, h->stream));
+    if (total > 0) HIPCHK(h, hipMemcpyAsync(d + o_q, qual, (size_t)total, hipMemcpyHostToDevice, h->stream));
+    TrimArgs a;
+    a.n_reads = n_reads; a.Q = Q; a.W = W; a.bias = 33;
+    a.off = (const long long*)d; a.q = (const unsigned char*)(d + o_q); a.cap = total;
+    a.acc = (unsigned long long*)(d + o_acc); a.trim = (long long*)(d + o_trim);
+    if ((rc2 = trim_bounds_enqueue(h, a))) return rc2;
+    HIPCHK(h, hipMemcpyAsync(trim, d + o_trim, tb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return NRV_OK;
+  };
+  rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  (void)hipFree(d);
+  return rc;
+}
+
 int nrv_pack_records(nrv_handle* h, const uint8_t* seq, const uint8_t* qual, const int64_t* off, int n_reads,
                      const uint8_t* names, const int64_t* name_off, uint8_t* blob, int64_t* rec_off) {
+  return nrv_pack_records_trim(h, seq, qual, off, n_reads, names, name_off, nullptr, 0, blob, rec_off);
+}
+
+int nrv_pack_records_trim(nrv_handle* h, const uint8_t* seq, const uint8_t* qual, const int64_t* off, int n_reads,
+                          const uint8_t* names, const int64_t* name_off, const int64_t* trim, int64_t min_len,
+                          uint8_t* blob, int64_t* rec_off) {
   int rc = check_handle(h);
   if (rc) return rc;
   if (n_reads < 0 || !off || !rec_off || off[0] != 0) { h->err = "nrv_pack_records: bad arguments"; return NRV_E_INVALID; }
   for (int r = 0; r < n_reads; ++r) if (off[r + 1] < off[r]) { h->err = "nrv_pack_records: off does not ascend"; return NRV_E_INVALID; }
+  if (trim) {
+    if (min_len < 0) { h->err = "nrv_pack_records_trim: negative min_len"; return NRV_E_INVALID; }
+    for (int r = 0; r < n_reads; ++r)
+      if (trim[2 * r] < 0 || trim[2 * r + 1] < trim[2 * r] || trim[2 * r + 1] > off[r + 1] - off[r]) {
+        h->err = "nrv_pack_records_trim: a trim outside its read";
+        return NRV_E_INVALID;
+      }
+  }
   if (!names_ok(names, name_off, n_reads)) { h->err = "nrv_pack_records: null names / name_off, or offsets that do not ascend from 0"; return NRV_E_INVALID; }
   const int64_t total_in = off[n_reads], name_bytes = name_off[n_reads];
   const bool fastq = qual != nullptr;
@@ -2773,7 +2956,8 @@ int nrv_pack_records(nrv_handle* h, const uint8_t* seq, const uint8_t* qual, con
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t nb = ((size_t)n_reads + 1) * 8;
   const size_t o_noff = up(nb), o_names = o_noff + up(nb), o_seq = o_names + up((size_t)name_bytes), o_qual = o_seq + up((size_t)total_in);
-  const size_t o_roff = o_qual + (fastq ? up((size_t)total_in) : 0), o_blob = o_roff + up(nb), bytes = o_blob + up(cap);
+  const size_t o_roff = o_qual + (fastq ? up((size_t)total_in) : 0), o_blob = o_roff + up(nb), o_trim = o_blob + up(cap);
+  const size_t bytes = o_trim + (trim ? up((size_t)n_reads * 16) : 0);
   char* d = nullptr;
   HIPCHK(h, hipMalloc((void**)&d, bytes));
   auto run = [&]() -> int {
@@ -2789,6 +2973,11 @@ int nrv_pack_records(nrv_handle* h, const uint8_t* seq, const uint8_t* qual, con
     a.off = (const long long*)d; a.name_off = (const long long*)(d + o_noff); a.names = (const unsigned char*)(d + o_names);
     a.seq = (const unsigned char*)(d + o_seq); a.qual = (const unsigned char*)(d + o_qual);
     a.rec_off = (long long*)(d + o_roff); a.blob = (unsigned char*)(d + o_blob); a.cap = cap;
+    a.trim = nullptr; a.min_len = min_len;
+    if (trim) {
+      HIPCHK(h, hipMemcpyAsync(d + o_trim, trim, (size_t)n_reads * 16, hipMemcpyHostToDevice, h->stream));
+      a.trim = (const long long*)(d + o_trim);
+    }
     if ((rc2 = pack_enqueue(h, a))) return rc2;
     HIPCHK(h, hipMemcpyAsync(rec_off, d + o_roff, nb, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));

@@ -70,3 +70,4 @@
 #include "nrv_edits.h"         // edits_count / edits_tile_scan / edits_scatter_kernel (per-read edit list behind the merge, opt-in)
 #include "nrv_pack.h"          // pack_offsets / pack_copy_kernel (FASTA / FASTQ records of the merged reads, opt-in)
 #include "nrv_profile.h"       // profile_kernel (per-read quality histogram and base counts behind the merge, opt-in)
+#include "nrv_trim.h"          // trim_qual / trim_window / trim_finish_kernel (sliding-window quality trim behind the merge, opt-in)

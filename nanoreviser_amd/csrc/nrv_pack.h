@@ -16,12 +16,17 @@ namespace nrv {
 //   merge_tile_scan walks its tiles) -> pack_copy (the work follows the BYTES of the blob, not the reads: one thread per aligned
 //   4-byte word, the read of its first byte found by binary search over rec_off, as merge_emit finds the read of an event).
 // Store width: 32 bits.  A thread forms the four bytes of its word one by one (a word may span the end of one record and the
-// head of the next two: a record has at least 3 bytes) and writes them with ONE 4-byte store; the blob's base is 256-byte
-// aligned.  The last word of the blob, when the total is no multiple of 4, is written byte by byte, so nothing at or beyond
+// heads of the following ones: a record that exists has at least 3 bytes) and writes them with ONE 4-byte store; the blob's
+// base is 256-byte aligned.  The last word of the blob, when the total is no multiple of 4, is written byte by byte, so nothing at or beyond
 // rec_off[n_reads] is touched.  Integers and copies only, no atomics, every byte written by exactly one thread and a function
 // of its position alone: the bytes do not depend on the order of the workgroups, and a second pass accumulates nothing.
 // The grid is sized from the host's bound `cap` on the blob; threads beyond rec_off[n_reads] (or beyond cap, whatever the
 // offsets say) do nothing.  A pass of 256 record lengths is summed in 32 bits: the host declines a blob of 4 GiB and more.
+// With `trim` (nrv_trim.h; hoststage.pack_records with trim / min_len) read r's record holds seq[lo:hi] (and qual[lo:hi]) of the
+// read when hi - lo >= min_len, and a read below that is DROPPED: it has no record at all, rec_off[r + 1] == rec_off[r].
+// rec_off is then ascending, not strictly so: pack_copy's search takes the LAST read with rec_off <= B, which is the one whose
+// record holds byte B (rec_off[r + 1] > B), whether the empty records lie at the head, in runs in the middle or at the tail -
+// and its walk to the next byte's record steps over every empty record in between.  trim == NULL: the whole reads, all of them.
 // ---------------------------------------------------------------------------------------
 struct PackArgs {
   int n_reads, fastq;
@@ -32,7 +37,19 @@ struct PackArgs {
   long long* rec_off;                    // [n_reads + 1] out
   unsigned char* blob;                   // [cap] out, 4-byte aligned
   unsigned long long cap;                // bytes the blob holds
+  const long long* trim;                 // [n_reads][2] (lo, hi) inside each read, or null: the whole reads
+  long long min_len;                     // with trim: a read with hi - lo below this has no record
 };
+
+// the part of read r that goes into its record: *s0 its first character in seq / qual, *L their number; false: no record
+__device__ __forceinline__ bool pack_part(const PackArgs& a, const int r, long long* s0, long long* L) {
+  *s0 = a.off[r]; *L = a.off[r + 1] - a.off[r];
+  if (!a.trim) return true;
+  const long long lo = a.trim[2 * r], hi = a.trim[2 * r + 1];
+  if (lo < 0 || hi < lo || hi > *L) { *L = 0; return false; }       // (never from trim_finish: nothing outside the read is read)
+  *s0 += lo; *L = hi - lo;
+  return hi - lo >= a.min_len;
+}
 
 // One workgroup: per-read record lengths -> exclusive offsets, 256 at a time with a running carry; the total goes to rec_off[n_reads].
 __global__ void __launch_bounds__(256) pack_offsets_kernel(const PackArgs a) {
@@ -41,7 +58,8 @@ __global__ void __launch_bounds__(256) pack_offsets_kernel(const PackArgs a) {
   for (int b = 0; b < a.n_reads; b += 256) {
     const int r = b + threadIdx.x;
     unsigned v = 0;
-    if (r < a.n_reads) v = (unsigned)(a.name_off[r + 1] - a.name_off[r]) + q * (unsigned)(a.off[r + 1] - a.off[r]) + 3u * q;
+    long long s0, L;
+    if (r < a.n_reads && pack_part(a, r, &s0, &L)) v = (unsigned)(a.name_off[r + 1] - a.name_off[r]) + q * (unsigned)L + 3u * q;
     unsigned total;
     const unsigned before = merge_block_scan(v, &total);
     if (r < a.n_reads) a.rec_off[r] = (long long)(carry + before);
@@ -52,7 +70,9 @@ __global__ void __launch_bounds__(256) pack_offsets_kernel(const PackArgs a) {
 
 // byte k of read r's record
 __device__ __forceinline__ unsigned pack_byte(const PackArgs& a, const int r, long long k) {
-  const long long n0 = a.name_off[r], nl = a.name_off[r + 1] - n0, s0 = a.off[r], L = a.off[r + 1] - s0;
+  const long long n0 = a.name_off[r], nl = a.name_off[r + 1] - n0;
+  long long s0, L;
+  (void)pack_part(a, r, &s0, &L);
   if (k == 0) return a.fastq ? '@' : '>';
   k -= 1;
   if (k < nl) return a.names[n0 + k];
@@ -74,7 +94,7 @@ __global__ void __launch_bounds__(256) pack_copy_kernel(const PackArgs a) {
   unsigned long long total = (unsigned long long)a.rec_off[a.n_reads];
   if (total > a.cap) total = a.cap;
   if (B >= total) return;
-  int r = 0, hi_r = a.n_reads - 1;                        // last read with rec_off <= B (records are never empty: strictly ascending)
+  int r = 0, hi_r = a.n_reads - 1;                        // LAST read with rec_off <= B: rec_off[r + 1] > B, so its record holds B
   while (r < hi_r) {
     const int mid = (r + hi_r + 1) >> 1;
     if ((unsigned long long)a.rec_off[mid] <= B) r = mid; else hi_r = mid - 1;

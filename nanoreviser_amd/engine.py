@@ -39,6 +39,7 @@ SYMBOLS = [
     "nrv_revise_reads_raw_edits_begin", "nrv_revise_reads_raw_edits", "nrv_merge_calls_edits",
     "nrv_revise_reads_raw_records_begin", "nrv_revise_reads_raw_records", "nrv_pack_records",
     "nrv_revise_reads_raw_profile_begin", "nrv_revise_reads_raw_profile", "nrv_merge_calls_profile",
+    "nrv_revise_reads_raw_trim_begin", "nrv_revise_reads_raw_trim", "nrv_merge_calls_trim", "nrv_trim_reads", "nrv_pack_records_trim",
 ]
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 PROFILE_COLS = 48                   # NRV_PROFILE_COLS
@@ -88,8 +89,9 @@ _REPORT = ([C.c_float, _U64P], lambda p: p[12:14])                              
 _EDITS = ([C.c_void_p, _I64P], lambda p: (None if p[14] is None else p[14].ctypes.data, p[15]))   # edits (nrv_edit records), edit_off
 _RECORDS = ([_U8P, _I64P, _U8P, _I64P], lambda p: p[16:20])                              # names, name_off, blob, rec_off
 _PROFILE = ([_FP, _U64P], lambda p: p[20:22])                                            # prof_thr, profile
+_TRIM = ([_FP, C.c_int, C.c_int, C.c_int64, _I64P], lambda p: p[22:27])                   # trim_thr, Q, W, min_len, trim
 # len(packed) -> (synchronous symbol, begin symbol, blocks, whether the call returns merged reads: (seq, qual, off[, report]
-# [, edits, edit_off][, blob, rec_off][, profile]))
+# [, edits, edit_off][, blob, rec_off][, profile][, trim]))
 _RAW_FORMS = {
     7: ("nrv_predict_reads_raw", "nrv_reads_raw_begin", (_CALLS,), False),
     9: ("nrv_predict_reads_raw_stats", "nrv_reads_raw_stats_begin", (_STATS, _CALLS), False),
@@ -98,10 +100,13 @@ _RAW_FORMS = {
     16: ("nrv_revise_reads_raw_edits", "nrv_revise_reads_raw_edits_begin", (_STATS, _MERGE, _REPORT, _EDITS), True),
     20: ("nrv_revise_reads_raw_records", "nrv_revise_reads_raw_records_begin", (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS), True),
     22: ("nrv_revise_reads_raw_profile", "nrv_revise_reads_raw_profile_begin", (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS, _PROFILE), True),
+    27: ("nrv_revise_reads_raw_trim", "nrv_revise_reads_raw_trim_begin", (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS, _PROFILE, _TRIM), True),
 }
 _PACK_RECORDS_T = [C.c_void_p, _U8P, _U8P, _I64P, C.c_int, _U8P, _I64P, _U8P, _I64P]         # nrv_pack_records
 _READS_HEAD_T = _RAW_HEAD_T[:4] + [C.c_int64, C.POINTER(_ReadDesc), C.c_int]     # nrv_segment_reads, nrv_read_stats: no features
 _MERGE_CALLS_T = [C.c_void_p, _U8P, _I64P, C.c_int, _I8P, _I8P, _FP, _FP, C.c_int64] + _MERGE[0][1:]   # nrv_merge_calls
+_TRIM_READS_T = [C.c_void_p, _U8P, _I64P, C.c_int, C.c_int, C.c_int, _I64P]                  # nrv_trim_reads
+_PACK_RECORDS_TRIM_T = _PACK_RECORDS_T[:7] + [_I64P, C.c_int64] + _PACK_RECORDS_T[7:]        # nrv_pack_records_trim
 
 
 _lib = None
@@ -185,8 +190,9 @@ def load_library(path: Optional[str] = None):
     have_edits = hasattr(lib, "nrv_merge_calls_edits")
     have_records = hasattr(lib, "nrv_pack_records")
     have_profile = hasattr(lib, "nrv_merge_calls_profile")
+    have_trim = hasattr(lib, "nrv_merge_calls_trim")
     for sync, begin, blocks, _ in _RAW_FORMS.values():  # (every restype is ctypes' default, int: the nrv_* status)
-        if (have_profile or _PROFILE not in blocks) and (have_records or _RECORDS not in blocks) \
+        if (have_trim or _TRIM not in blocks) and (have_profile or _PROFILE not in blocks) and (have_records or _RECORDS not in blocks) \
                 and (have_edits or _EDITS not in blocks) and (have_report or _REPORT not in blocks):
             getattr(lib, sync).argtypes = _RAW_HEAD_T + [t for types, _ in blocks for t in types]
             getattr(lib, begin).argtypes = getattr(lib, sync).argtypes + [C.POINTER(C.c_int)]
@@ -199,6 +205,10 @@ def load_library(path: Optional[str] = None):
         lib.nrv_pack_records.argtypes = _PACK_RECORDS_T
     if have_profile:
         lib.nrv_merge_calls_profile.argtypes = _MERGE_CALLS_T + _PROFILE[0]
+    if have_trim:
+        lib.nrv_merge_calls_trim.argtypes = _MERGE_CALLS_T + _TRIM[0] + _RECORDS[0]
+        lib.nrv_trim_reads.argtypes = _TRIM_READS_T
+        lib.nrv_pack_records_trim.argtypes = _PACK_RECORDS_TRIM_T
     lib.nrv_reads_raw_end.argtypes = [vp, C.c_int]
     lib.nrv_segment_reads.argtypes = _READS_HEAD_T + [fp]
     lib.nrv_read_stats.argtypes = _READS_HEAD_T + [_I32P, _DP, _DP, _DP, _DP, fp]
@@ -498,11 +508,50 @@ class Reviser:
         return packed + (thr, np.zeros((packed[4], PROFILE_COLS), np.uint64))
 
     @staticmethod
+    def _trim_rule(Q, W, min_len, q_thr):
+        """The arguments of the trim, checked: (thr float32[39], Q, W, min_len)."""
+        Q, W, min_len = int(Q), int(W), int(min_len)
+        if not (1 <= Q <= 40 and 1 <= W <= 64 and min_len >= 0):
+            raise ValueError("the trim needs Q in 1 .. 40, W in 1 .. 64 and min_len >= 0")
+        if q_thr is None:
+            from .cli import phred_thresholds
+            q_thr = phred_thresholds()
+        thr = np.ascontiguousarray(q_thr, dtype=np.float32).reshape(-1)
+        if thr.size != 39:
+            raise ValueError("q_thr must have 39 entries")
+        return thr, Q, W, min_len
+
+    @classmethod
+    def with_device_trim(cls, packed, Q, W=10, min_len=1, q_thr=None):
+        """A `with_device_merge` (12 elements), `with_device_report` (14), `with_device_edits` (16), `with_device_records` (20) or
+        `with_device_profile` (22) tuple whose call also finds, per read, the part a sliding quality window keeps (include/nanorev.h
+        nrv_revise_reads_raw_trim_begin; hoststage.trim_bounds is the definition): Q in 1 .. 40, W in 1 .. 64; q_thr: the 39
+        thresholds the trim's qualities are computed with (default: cli.phred_thresholds()) - its own, whether the call writes a
+        quality or not.  `run_packed_raw` / `begin_packed_raw` + `end_packed_raw` then return what a `with_device_profile` call
+        returns - None for the blocks the tuple does not carry, the profile included - and trim int64[n_reads][2] last.  seq,
+        qual, off, report, edits and profile describe the untrimmed reads; the blob of a `with_device_records` tuple is the
+        exception: hoststage.pack_records with this trim and min_len (a read whose kept part is shorter has no record)."""
+        if len(packed) not in (12, 14, 16, 20, 22):
+            raise ValueError("with_device_trim extends a with_device_merge, a with_device_report, a with_device_edits, a "
+                             "with_device_records or a with_device_profile tuple")
+        packed = tuple(packed)
+        if len(packed) == 12:
+            packed += (0.0, None)
+        if len(packed) == 14:
+            packed += (None, None)
+        if len(packed) == 16:
+            packed += (None, None, None, None)
+        if len(packed) == 20:
+            packed += (None, None)
+        thr, Q, W, min_len = cls._trim_rule(Q, W, min_len, q_thr)
+        return packed + (thr, Q, W, min_len, np.zeros((packed[4], 2), np.int64))
+
+    @staticmethod
     def _trim_merged(out):
         seq, qual, off = out[:3]
         total = int(off[-1])
         more, tail = tuple(out[3:]), ()
-        if len(more) == 6:                            # (..., profile): a `with_device_profile` call; blocks it does not carry are None
+        if len(more) in (6, 7):                       # (..., profile[, trim]): a `with_device_profile` / `with_device_trim` call; blocks it does not carry are None
             more, tail = more[:5], more[5:]
         if len(more) in (3, 5) and more[1] is not None:   # (report | None, edits, edit_off, ...): the used prefix of the records
             more = (more[0], more[1][:int(more[2][-1])], more[2]) + more[3:]
@@ -519,20 +568,21 @@ class Reviser:
         """One call of the raw-read family for a packed tuple of any form (`_RAW_FORMS`): its synchronous entry point, or its
         *_begin with the ticket behind the same arguments.  Returns (ticket number or None, outputs, merged)."""
         if len(packed) not in _RAW_FORMS:
-            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14, 16, 20 or 22 elements, not {len(packed)}")
+            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14, 16, 20, 22 or 27 elements, not {len(packed)}")
         sync, beg, blocks, merged = _RAW_FORMS[len(packed)]
-        if not hasattr(self._lib, beg):               # the report, edits, records and profile pairs are found by presence
+        if not hasattr(self._lib, beg):               # the report, edits, records, profile and trim pairs are found by presence
             raise NrvError(-1, f"this build of libnanorev_hip.so has no {beg}")
         args = self._raw_head(packed)
         for types, pick in blocks:
             args += _marshal(pick(packed), types)
         t = C.c_int(-1)
         self._check(getattr(self._lib, beg)(*args, C.byref(t)) if begin else getattr(self._lib, sync)(*args))
-        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) + tuple(packed[18:20]) + tuple(packed[21:22]) if merged else packed[6]), merged
+        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) + tuple(packed[18:20]) + tuple(packed[21:22]) + tuple(packed[26:27]) if merged else packed[6]), merged
 
     def run_packed_raw(self, packed):
         """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared (or `with_device_stats` /
-        `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` extended)."""
+        `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` /
+        `with_device_trim` extended)."""
         _, out, merged = self._raw_call(packed, False)
         return self._trim_merged(out) if merged else out
 
@@ -547,7 +597,7 @@ class Reviser:
         call, its (seq, qual, off), with the report behind them for a `with_device_report` call, (report | None, edits,
         edit_off) for a `with_device_edits` call and (report | None, edits | None, edit_off | None, blob, rec_off) - the blob
         trimmed to rec_off[-1] - for a `with_device_records` call; a `with_device_profile` call returns the latter with the
-        profile behind it."""
+        profile behind it, a `with_device_trim` call with (profile | None, trim) behind it."""
         t, out = ticket[:2]
         self._check(self._lib.nrv_reads_raw_end(self._h, t))
         return self._trim_merged(out) if len(ticket) == 3 else out
@@ -669,7 +719,61 @@ class Reviser:
         prof = np.zeros((ins[1].size, PROFILE_COLS), np.uint64)
         return self._merge_call("nrv_merge_calls_profile", *ins, *_marshal((pthr, prof), _PROFILE[0])) + (prof,)
 
-    def pack_records_device(self, names, seq, qual, off, blob=None):
+    def merge_calls_trim(self, bases, ev_len, a1, a2, p1, p2, Q, W=10, q_thr=None, trim_thr=None, names=None, min_len=1):
+        """`merge_calls_device` with the sliding-window trim (nrv_merge_calls_trim): p1 / p2 are required, q_thr may be None (a
+        FASTA merge whose trim is still computed), trim_thr defaults to cli.phred_thresholds().  Returns (seq, qual | None, off,
+        trim int64[n_reads][2]) - the trim is cli.trim_rows', bit for bit - and with names (one byte string per read) the
+        trimmed records (blob, rec_off) of hoststage.pack_records behind them."""
+        if not hasattr(self._lib, "nrv_merge_calls_trim"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_merge_calls_trim")
+        if p1 is None or p2 is None:
+            raise ValueError("the trim needs p1 / p2")
+        tthr, Q, W, min_len = self._trim_rule(Q, W, min_len, trim_thr)
+        ins = self._merge_inputs(bases, ev_len, a1, a2, p1, p2, q_thr, True)
+        n, (q1, q2, thr) = ins[2].size, ins[4:]
+        if q1.shape[0] != n or q2.shape[0] != n or (thr is not None and thr.size != 39):
+            raise ValueError("p1 / p2 / q_thr do not match")
+        nr = ins[1].size
+        trim = np.zeros((nr, 2), np.int64)
+        rec = (None, None, None, None)
+        if names is not None:
+            if len(names) != nr:
+                raise ValueError("names must have one entry per read")
+            nm, name_off = self._names_block(names)
+            q = 2 if thr is not None else 1
+            rec = (nm, name_off, np.empty(max(int(name_off[-1]) + q * (ins[0].size + n) + 3 * q * nr, 1), np.uint8), np.zeros(nr + 1, np.int64))
+        out = self._merge_call("nrv_merge_calls_trim", *ins, *_marshal((tthr, Q, W, min_len, trim) + rec, _TRIM[0] + _RECORDS[0])) + (trim,)
+        return out if names is None else out + (rec[2][:int(rec[3][-1])], rec[3])
+
+    def trim_reads(self, qual, off, Q, W=10):
+        """The window and finish kernels alone (nrv_trim_reads) on quality characters the host supplies: the arguments and the
+        result int64[n_reads][2] of hoststage.trim_bounds, bit for bit."""
+        if not hasattr(self._lib, "nrv_trim_reads"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_trim_reads")
+        _, Q, W, _ = self._trim_rule(Q, W, 0, np.zeros(39, np.float32))
+        off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+        nr = off.size - 1
+        ql = np.ascontiguousarray(qual, dtype=np.uint8).reshape(-1)
+        if ql.size < int(off[-1]):
+            raise ValueError("qual is shorter than off[-1]")
+        if ql.size == 0:
+            ql = np.zeros(1, np.uint8)
+        trim = np.zeros((nr, 2), np.int64)
+        self._check(self._lib.nrv_trim_reads(*_marshal((self._h, ql, off, nr, Q, W, trim), _TRIM_READS_T)))
+        return trim
+
+    def pack_records_trim(self, names, seq, qual, off, trim, min_len=1, blob=None):
+        """`pack_records_device` with a trim (nrv_pack_records_trim): the arguments and the result of hoststage.pack_records with
+        trim / min_len, byte for byte; trim None: `pack_records_device`'s bytes."""
+        if not hasattr(self._lib, "nrv_pack_records_trim"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_pack_records_trim")
+        if trim is not None:
+            trim = np.ascontiguousarray(trim, dtype=np.int64).reshape(-1, 2)
+            if trim.shape[0] != np.asarray(off).size - 1:
+                raise ValueError("trim must have one row per read")
+        return self.pack_records_device(names, seq, qual, off, blob, _trim=(trim, int(min_len)))
+
+    def pack_records_device(self, names, seq, qual, off, blob=None, _trim=None):
         """The device-side record layout alone (nrv_pack_records) on merged reads the host supplies: the arguments and the
         result (blob, rec_off) of hoststage.pack_records, byte for byte.  blob: a uint8 array of at least the capacity to write
         into (the result is a view of its used prefix; nothing behind it is written)."""
@@ -695,6 +799,10 @@ class Reviser:
             s = np.zeros(1, np.uint8)
         if ql is not None and ql.size == 0:
             ql = np.zeros(1, np.uint8)
+        if _trim is not None:                         # `pack_records_trim`
+            self._check(self._lib.nrv_pack_records_trim(*_marshal((self._h, s, ql, off, nr, nm, name_off) + _trim + (blob, rec_off),
+                                                                  _PACK_RECORDS_TRIM_T)))
+            return blob[:int(rec_off[-1])], rec_off
         self._check(self._lib.nrv_pack_records(*_marshal((self._h, s, ql, off, nr, nm, name_off, blob, rec_off), _PACK_RECORDS_T)))
         return blob[:int(rec_off[-1])], rec_off
 
