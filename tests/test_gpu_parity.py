@@ -25,6 +25,7 @@ from nanoreviser_amd import hoststage as hs
 pytestmark = pytest.mark.gpu
 
 from parity_policy import BAR, check_vs_fp64, f32_floor
+from weight_cases import extreme_windows, f32_floor_act
 
 MODES = ["f16x2", "bf16x3", "f32"]
 
@@ -248,37 +249,77 @@ def test_batch_grouping_is_invisible(reads, species_models):
     rv.close()
 
 
-def test_sigmoid_variant_matches_oracle(reads, species_models):
+_REFERENCES = {}
+
+
+def _live_reference(key, m1, m2, sig, rd, act):
+    """(fp64 oracle of both models, their f32 floors) on these windows: computed once for the three modes, left unchanged."""
+    from oracle import nrv_oracle as O
+    if key not in _REFERENCES:
+        with np.errstate(over="ignore"):
+            q1, q2, _, _ = O.predict_pair(m1.tensors, m2.tensors, sig, rd, np.float64, recurrent_act=act)
+            nf = f32_floor(m1, m2, sig, rd, q1, q2) if act == "hard_sigmoid" else f32_floor_act(m1, m2, sig, rd, q1, q2, act)
+        for a in (q1, q2) + tuple(nf):
+            a.setflags(write=False)
+        _REFERENCES[key] = (q1, q2) + tuple(nf)
+    return _REFERENCES[key]
+
+
+@pytest.mark.parametrize("sp", ["ecoli", "human"])
+def test_sigmoid_variant_matches_oracle(reads, species_models, sp, precision):
     """recurrent_act=1 (Keras >= 2.3 default, enviroment/NanoReviser_macOS.yaml) is a different
-    function; the engine implements it too and it must match the oracle's sigmoid variant."""
+    function; the engine implements it too and it must match the oracle's sigmoid variant: the module's
+    policy against the fp64 arbiter and the f32 floors of the sigmoid function on these windows (the
+    reference alone: tests/test_weight_cases_host.py)."""
     from nanoreviser_amd.engine import Reviser
     from oracle import nrv_oracle as O
-    m1, m2 = species_models["ecoli"]
+    m1, m2 = species_models[sp]
     _, sw, fw = _windows(reads, "ch117_read6465")
     sw, fw = np.ascontiguousarray(sw[:200]), np.ascontiguousarray(fw[:200])
     rv = Reviser(m1, m2, recurrent_activation="sigmoid")
+    assert rv.precision == precision
     p1, p2, a1, a2 = rv.predict_pair(sw, fw)
-    q1, q2, b1, b2 = O.predict_pair(m1.tensors, m2.tensors, sw, fw, np.float64, recurrent_act="sigmoid")
-    assert np.abs(p1 - q1).max() <= 1e-4 and np.abs(p2 - q2).max() <= 1e-4
-    assert np.array_equal(a1, b1) and np.array_equal(a2, b2)
+    assert rv.saturated() == (0, 0)
+    rv.close()
+    q1, q2, nf1, nf2 = _live_reference(("sigmoid", sp), m1, m2, sw, fw, "sigmoid")
+    b1, b2 = q1.argmax(-1), q2.argmax(-1)
+    r1 = check_vs_fp64(p1, a1, q1, nf1, f"sigmoid {sp} m1", max_ill=0.01, bar=BAR)
+    r2 = check_vs_fp64(p2, a2, q2, nf2, f"sigmoid {sp} m2", max_ill=0.01, bar=BAR)
+    print(f"SIGMOID {sp} {precision}: m1 {r1} m2 {r2}")
+    if sp == "ecoli":
+        assert np.abs(p1 - q1).max() <= 1e-4 and np.abs(p2 - q2).max() <= 1e-4
+        assert np.array_equal(a1, b1) and np.array_equal(a2, b2)
     h1 = O.forward(m1.tensors, sw, fw, np.float64)
     assert np.abs(p1 - h1).max() > 1e-3          # and it is NOT the hard_sigmoid function
-    rv.close()
 
 
-def test_extreme_inputs_stay_finite(engines):
-    """Saturating gates, zero signal, huge features: no NaN/Inf, valid distributions."""
+@pytest.mark.parametrize("act", ["hard_sigmoid", "sigmoid"])
+@pytest.mark.parametrize("sp", ["ecoli", "human"])
+def test_extreme_inputs_stay_finite(engines, species_models, sp, act, precision):
+    """Saturating gates, zero signal, huge features: no NaN/Inf, valid distributions - and the oracle's answer.
+    On the CPU these windows are as well-conditioned as real ones (tests/test_weight_cases_host.py: at most
+    one of the 256 above the f32 floor of BAR / 2, every sample below the conv1 bound), so they are held
+    to the fp64 arbiter under the module's policy, and no stage may be handed to the f32 kernels."""
+    from nanoreviser_amd.engine import Reviser
     from oracle import nrv_oracle as O
-    rv = engines["ecoli"]
-    sig, rd = O.synth_windows(96, 11, seed=3)
-    sig[:32] = 0.0
-    rd[32:64] *= 50.0
-    sig[64:] = np.where(np.arange(50) % 2 == 0, 4.8, -8.4)
+    m1, m2 = species_models[sp]
+    sig, rd = extreme_windows()
+    rv = engines[sp] if act == "hard_sigmoid" else Reviser(m1, m2, recurrent_activation=act)
+    assert rv.precision == precision
+    _, reruns0 = rv.saturated()
     p1, p2, a1, a2 = rv.predict_pair(sig, rd)
+    sat, reruns = rv.saturated()
+    if act != "hard_sigmoid":
+        rv.close()
     for p in (p1, p2):
         assert np.isfinite(p).all() and (p >= 0).all()
         assert np.abs(p.sum(-1) - 1).max() < 1e-5
     assert np.array_equal(a1, p1.argmax(-1)) and np.array_equal(a2, p2.argmax(-1))
+    assert (sat, reruns - reruns0) == (0, 0)
+    q1, q2, nf1, nf2 = _live_reference(("extreme", sp, act), m1, m2, sig, rd, act)
+    r1 = check_vs_fp64(p1, a1, q1, nf1, f"extreme {sp} {act} m1", max_ill=0.01, bar=BAR)
+    r2 = check_vs_fp64(p2, a2, q2, nf2, f"extreme {sp} {act} m2", max_ill=0.01, bar=BAR)
+    print(f"EXTREME {sp} {act} {precision}: m1 {r1} m2 {r2}")
 
 
 @pytest.mark.parametrize("sp", ["ecoli", "human"])

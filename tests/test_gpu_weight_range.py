@@ -13,13 +13,24 @@ test_weight_cases_host.py pins that: the oracle's answer does not change by one 
     oracle and the f32 floors of the SHIPPED weights; it may hand a stage to the f32 kernels only where its fixed scales
     cannot hold the values (then the result is the f32 mode's, bit for bit), and must not where they can;
   * degenerate weights (zero tensors, BatchNorm scales of 0, a layer 2^-20 of its size) against their own live oracle.
+
+The reparametrisations cannot change WHICH block of a layer sets its accumulator exponent (plan_exponent's minimum): every
+exponent they move is matched by the weights it scales.  Two more families do, both against their own live oracle, in every
+mode, with no stage handed to the f32 kernels (tests/test_weight_cases_host.py pins on the CPU that each case reaches the
+branch it names, that the reference alone has no ill-conditioned window on it and that every value fits the fixed scales):
+
+  * weight_cases.plan_case: input rows starved until the recurrent block (13 + room(U)) binds by three binades - it binds in
+    no shipped model - or until the BatchNorm block of the 192 -> 128 layer does;
+  * weight_cases.unseen: hybrids of the two species, their midpoint, jittered, pruned, outlier-ridden, recurrent-heavy,
+    BatchNorm-shifted and freshly initialised weights.
 """
 import numpy as np
 import pytest
 
 from nanoreviser_amd import hoststage as hs
 from parity_policy import BAR, check_vs_fp64, f32_floor
-from weight_cases import (DEGENERATE_CASES, REPARAM_CASES, case_windows, conv1_sample_bound, degenerate, reparam)
+from weight_cases import (DEGENERATE_CASES, LAYERS, PLAN_CASES, REPARAM_CASES, SIGMOID_ADMITTED, UNSEEN_ADMITTED, binding,
+                          case_windows, degenerate, f16x2_must_not_rerun, f32_floor_act, plan_case, plan_terms, reparam, unseen)
 
 pytestmark = pytest.mark.gpu
 
@@ -59,24 +70,6 @@ def _policy(got, q, nf, what):
     return {"m1": r1, "m2": r2}
 
 
-def _f16x2_must_not_rerun(k1, k2, sw):
-    """The CPU preconditions under which the fixed scales of the f16x2 signal branch hold every value of these windows:
-    |S| < 1000 (kept x 2^6 as an f16 pair), every sample below the conv1 guard's static bound, and the 400 -> 64 dense
-    weights x 2^10 inside the f16 range."""
-    from oracle import nrv_oracle as O
-    ev = np.asarray(sw, np.float64).reshape(-1, 50)
-    xmax = float(np.abs(ev).max())
-    for k in (k1, k2):
-        w = [np.asarray(t, np.float64) for t in k.tensors]
-        if not float(np.abs(O.signal_branch(w, ev)).max()) < 1000.0:
-            return False
-        if not xmax < conv1_sample_bound(k):
-            return False
-        if not float(np.abs(k.tensors[32]).max()) * 1024.0 < 65504.0:
-            return False
-    return True
-
-
 @pytest.mark.parametrize("sp", SPECIES)
 @pytest.mark.parametrize("c", CS)
 @pytest.mark.parametrize("site", SCALED)
@@ -106,7 +99,7 @@ def test_reparametrised_weights(shipped, species_models, sp, site, c):
     if reruns > 0:
         for g, r in zip(got, ref32):
             assert np.array_equal(g, r)                        # a re-run stage IS the f32 kernels' result
-    if _f16x2_must_not_rerun(k1, k2, sw):
+    if f16x2_must_not_rerun(k1, k2, sw):
         assert reruns == 0, f"{sp} {site} c={c:g}: every value fits the f16x2 scales, yet {reruns} stage(s) ran in f32"
 
 
@@ -150,12 +143,55 @@ def test_degenerate_weights(shipped, species_models, sp, name):
     rv.close()
 
 
-def test_reparametrised_weights_through_the_raw_read_path(reads, species_models):
-    """`all` at 2^6 through nrv_predict_reads_raw (the slot path: its own launch sequence, the same weight plan): the first
-    400 events of a fixture read give nrv_predict_read's bits on the same weights."""
+def _live_oracle_every_mode(k1, k2, sw, fw, what, act="hard_sigmoid"):
+    """test_degenerate_weights' shape: the case's own fp64 oracle and f32 floors, every mode, finite, the policy, no re-run."""
     from nanoreviser_amd.engine import Reviser
-    m1, m2 = species_models["human"]
-    k1, k2 = reparam(m1, "all", 64.0), reparam(m2, "all", 64.0)
+    from oracle import nrv_oracle as O
+    with np.errstate(over="ignore"):
+        q1, q2, _, _ = O.predict_pair(k1.tensors, k2.tensors, sw, fw, np.float64, recurrent_act=act)
+        nf = f32_floor(k1, k2, sw, fw, q1, q2) if act == "hard_sigmoid" else f32_floor_act(k1, k2, sw, fw, q1, q2, act)
+    bind = "/".join(",".join(binding(plan_terms(k)[l])[0][:3] for l in LAYERS) for k in (k1, k2))
+    rv = Reviser(k1, k2, recurrent_activation=act)
+    try:
+        for mode in MODES:
+            rv.set_precision(mode)
+            got = rv.predict_pair(sw, fw)
+            assert np.isfinite(got[0]).all() and np.isfinite(got[1]).all(), f"{what} {mode}"
+            res = _policy(got, (q1, q2), nf, f"{mode} {what}")
+            _, reruns = rv.saturated()
+            print(f"WEIGHTS {what} {act} {mode}: binds {bind} reruns {reruns} {res}")
+            assert reruns == 0, f"{what} {mode}"
+    finally:
+        rv.close()
+
+
+def _acts(sp, name):
+    return ["hard_sigmoid"] + (["sigmoid"] if sp in SIGMOID_ADMITTED.get(name, ()) else [])
+
+
+@pytest.mark.parametrize("sp", SPECIES)
+@pytest.mark.parametrize("name", list(PLAN_CASES))
+def test_plan_cases(shipped, species_models, sp, name):
+    """The recurrent block, or the BatchNorm block of the 192 -> 128 layer, sets the accumulator exponent."""
+    m1, m2 = species_models[sp]
+    k1, k2 = plan_case(m1, name), plan_case(m2, name)
+    assert f16x2_must_not_rerun(k1, k2, shipped["sw"])
+    for act in _acts(sp, name):
+        _live_oracle_every_mode(k1, k2, shipped["sw"], shipped["fw"], f"{sp} {name}", act)
+
+
+@pytest.mark.parametrize("sp,name", [(sp, name) for sp in SPECIES for name in UNSEEN_ADMITTED[sp]])
+def test_unseen_weights(shipped, species_models, sp, name):
+    other = "human" if sp == "ecoli" else "ecoli"
+    (m1, m2), (o1, o2) = species_models[sp], species_models[other]
+    k1, k2 = unseen(m1, o1, name), unseen(m2, o2, name)
+    assert f16x2_must_not_rerun(k1, k2, shipped["sw"])
+    for act in _acts(sp, name):
+        _live_oracle_every_mode(k1, k2, shipped["sw"], shipped["fw"], f"{sp} {name}", act)
+
+
+def _raw_path_gives_predict_reads_bits(reads, k1, k2):
+    from nanoreviser_amd.engine import Reviser
     _, rd, _ = reads("ch141_read5436")
     rr = hs.read_tensors_raw(rd)
     N = 400
@@ -172,3 +208,17 @@ def test_reparametrised_weights_through_the_raw_read_path(reads, species_models)
     assert got[0].shape == (N - 11, 6) and reruns_both == 2 * reruns_raw
     for g, w in zip(got, want):
         assert np.array_equal(g, w)
+    return reruns_raw
+
+
+def test_recurrent_block_binding_through_the_raw_read_path(reads, species_models):
+    """`all_rec_bind` through nrv_predict_reads_raw: nrv_predict_read's bits on the same weights, nothing re-run."""
+    m1, m2 = species_models["human"]
+    assert _raw_path_gives_predict_reads_bits(reads, plan_case(m1, "all_rec_bind"), plan_case(m2, "all_rec_bind")) == 0
+
+
+def test_reparametrised_weights_through_the_raw_read_path(reads, species_models):
+    """`all` at 2^6 through nrv_predict_reads_raw (the slot path: its own launch sequence, the same weight plan): the first
+    400 events of a fixture read give nrv_predict_read's bits on the same weights."""
+    m1, m2 = species_models["human"]
+    _raw_path_gives_predict_reads_bits(reads, reparam(m1, "all", 64.0), reparam(m2, "all", 64.0))
