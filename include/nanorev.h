@@ -398,6 +398,57 @@ int nrv_pack_records_trim(nrv_handle* h, const uint8_t* seq, const uint8_t* qual
                           const uint8_t* names, const int64_t* name_off, const int64_t* trim, int64_t min_len,
                           uint8_t* blob, int64_t* rec_off);
 
+/* EDIT DISTANCE TO A TRUTH SET of the same reads (opt-in; nothing above changes): per read how far the original and the revised
+ * read are from the true sequence the caller holds, found on the device by ONE launch behind everything else of the call.
+ * The rule, integers only: d(t, s) is the global unit-cost edit distance of a truth t (m bytes) and a read s (n bytes):
+ *   D[0][j] = j and D[i][0] = i;  D[i][j] = min(D[i-1][j] + 1, D[i][j-1] + 1, D[i-1][j-1] + c);
+ *   c = 0 exactly when t[i-1] == s[j-1] and that byte is one of A C G T - any other byte (N, lower case, anything else) matches
+ *   nothing, itself included;  d = D[m][n].  n = 0 gives d = m.  m = 0 means "this read has no truth": its row is all zeros
+ *   and no distance is formed.
+ * hoststage.edit_distance is the definition.  The arguments of nrv_revise_reads_raw_trim_begin - every block of it may be NULL
+ * as there, and here the trim too: with trim == NULL the rule Q / W / min_len / trim_thr is not checked and no trim enqueued -
+ * then, all three required,
+ *   truth      uint8: the true sequences, one behind the other;
+ *   truth_off  int64 [n_reads + 1] ascending from 0: read r has truth[truth_off[r] .. truth_off[r + 1]); no single truth of
+ *              2^31 - 64 characters or more (NRV_E_INVALID);
+ *   accuracy   uint64 [n_reads][NRV_ACCURACY_COLS]:
+ *     0  truth_len
+ *     1  dist_in  = d(truth, the original bases of the read)
+ *     2  dist_out = d(truth, seq[off[r] .. off[r + 1])): the UNTRIMMED revision, as the report, the edits and the profile
+ *     3  reserved, 0
+ * One wave per (read, original | revised) pair; every word is a function of its pair alone, stored plainly: the bytes do not
+ * depend on the order of the workgroups and the range-guard re-run accumulates nothing.  The truth travels with the call's one
+ * input transfer; the caller's truth arrays are dead once _begin returns.  N <= T: nothing is enqueued, the block is filled
+ * on the host with dist_out = dist_in.  Tickets, the two-calls-in-flight rule and the failure paths are those of
+ * nrv_revise_reads_raw_begin; `accuracy` is filled by nrv_reads_raw_end.  nrv_revise_reads_raw_accuracy IS _accuracy_begin + _end. */
+#define NRV_ACCURACY_COLS 4
+int nrv_revise_reads_raw_accuracy_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                        const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                        const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                        uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                        nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                        uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                        const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                                        const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, int* ticket);
+int nrv_revise_reads_raw_accuracy(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                  const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                  const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                  uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                  nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                  uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                  const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                                  const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy);
+/* nrv_merge_calls with the accuracy block, by the kernel nrv_revise_reads_raw_accuracy_begin runs, on calls the host supplies.
+ * The twin used by the parity tests. */
+int nrv_merge_calls_accuracy(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                             const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                             const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy);
+/* The same kernel on pairs the host supplies: pair k is the truth a[a_off[k] .. a_off[k + 1]) against the read
+ * b[b_off[k] .. b_off[k + 1]); a_off / b_off int64 [n_pairs + 1] ascending from 0, no sequence of 2^31 - 64 characters or more
+ * (NRV_E_INVALID); dist int64 [n_pairs], -1 for an empty truth.  The unit door of the kernel. */
+int nrv_edit_distance(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
+                      int64_t* dist);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

@@ -163,7 +163,36 @@ def get_args(argv: Optional[Sequence[str]] = None):
                    help="with --trim_q: write what the trim did to FILE, a TSV with one header line, one line per input read sorted "
                         "by file name - name, status (revised / unrevised), bases of the untrimmed read, lo, hi, kept (1 / 0) - "
                         "and a last line #total with the sums over the revised reads.  The same file on every route")
+    p.add_argument("--truth", dest="truth", default=None, metavar="FASTA",
+                   help="the true sequence of the reads, for --accuracy (also NRV_TRUTH=FASTA): a FASTA file whose records may be "
+                        "wrapped and are upper-cased on load; the first word of a header is the read's name, matched against the "
+                        "fast5 file name with or without .fast5.  A name that occurs twice is an error.  A read without a record "
+                        "has no truth")
+    p.add_argument("--accuracy", dest="accuracy", default=None, metavar="FILE",
+                   help="with --truth: write to FILE (also NRV_ACCURACY=FILE) how far every read is from its truth before and "
+                        "after the revision, a TSV with one header line, one line per input read sorted by file name - name, "
+                        "status (revised / unrevised), truth_len, len_in, dist_in, len_out, dist_out, id_in, id_out - then a line "
+                        "#total with the sums over the reads with a truth and the pooled identities and a line #reads with the "
+                        "reads with a truth, without one and too long.  dist is the global unit-cost edit distance (only equal "
+                        "A / C / G / T match), id = 1 - dist / max(len, truth_len); the revised read is the untrimmed one.  "
+                        "With --device_merge the distances are found on the GPU behind the merge, everywhere else by the host "
+                        "stage at about 0.1 s per read: the same file byte for byte.  --resume does not work with it.  Off by "
+                        "default; without it nothing changes")
+    p.add_argument("--accuracy_max_len", dest="accuracy_max_len", type=int, default=65536, metavar="L",
+                   help="with --accuracy: a read whose truth or original length exceeds L is treated as having no truth and "
+                        "counted as too_long (default 65536)")
     a = p.parse_args(argv)
+    a.truth = a.truth or (os.environ.get("NRV_TRUTH", "").strip() or None)
+    a.accuracy = a.accuracy or (os.environ.get("NRV_ACCURACY", "").strip() or None)
+    if (a.truth is None) != (a.accuracy is None):
+        print("[！！！Error] --truth and --accuracy go together", file=sys.stderr)
+        raise SystemExit(2)
+    if a.accuracy and a.resume:
+        print("[！！！Error] --resume cannot be used with --accuracy: a skipped read's written form is not at hand", file=sys.stderr)
+        raise SystemExit(2)
+    if a.accuracy and a.accuracy_max_len < 0:
+        print("[！！！Error] --accuracy_max_len must be 0 or more", file=sys.stderr)
+        raise SystemExit(2)
     if a.trim_q is None and os.environ.get("NRV_TRIM_Q", "").strip():
         try:
             a.trim_q = int(os.environ["NRV_TRIM_Q"].strip())
@@ -931,6 +960,64 @@ def unrevised_trim(n_written: int) -> List[int]:
     return [n, 0, n, 1]
 
 
+ACCURACY_HEADER = "name\tstatus\ttruth_len\tlen_in\tdist_in\tlen_out\tdist_out\tid_in\tid_out"
+ACCURACY_PART_COLS = 6                     # a part line's integers: truth_len, len_in, dist_in, len_out, dist_out, flag
+ACC_WITH_TRUTH, ACC_NO_TRUTH, ACC_TOO_LONG = 0, 1, 2            # the flag
+
+
+def _truth_key(name: str) -> str:
+    return name[:-len(".fast5")] if name.endswith(".fast5") else name
+
+
+def load_truth(path: str) -> dict:
+    """--truth: {name: sequence bytes} of a FASTA file.  Records may be wrapped; sequences are upper-cased; the name is the first
+    word of the header, kept without a trailing .fast5.  A name that occurs twice - with or without .fast5 - raises ValueError."""
+    truths, name, parts = {}, None, []
+    with open(path, "rb") as fp:
+        for ln in fp:
+            ln = ln.strip()
+            if ln.startswith(b">"):
+                if name is not None:
+                    truths[name] = b"".join(parts).upper()
+                words = ln[1:].split()
+                name, parts = _truth_key(words[0].decode() if words else ""), []
+                if name in truths:
+                    raise ValueError(f"--truth: the name {name} occurs twice in {path}")
+            elif ln and name is not None:
+                parts.append(ln)
+    if name is not None:
+        truths[name] = b"".join(parts).upper()
+    return truths
+
+
+def truth_of(truths: dict, fast5_fn: str):
+    """The truth of a fast5 file, whether its record names it with or without .fast5; None when there is none."""
+    return truths.get(_truth_key(fast5_fn))
+
+
+def accuracy_rows(T, bases, ev_len, a1, a2, truth, truth_off):
+    """--accuracy on the host: `hoststage.read_accuracy` on calls the host holds - `emit_calls` for the untrimmed revised reads,
+    then the definition.  (uint64[len(ev_len)][4], the lengths of the revised reads)."""
+    b = hostlib.bases_u8(bases)
+    seq, _, off = hs.emit_calls(b, ev_len, a1, a2, None, T)
+    return hs.read_accuracy(b, ev_len, seq, off, truth, truth_off), np.diff(off)
+
+
+def identity_field(dist: int, denom: int) -> str:
+    """1 - dist / denom with six decimals, denom = max(len, truth_len) of a read or the sum of those over reads: THE identity
+    of the --accuracy file, formed from the integers on every route."""
+    x = 1.0 - int(dist) / int(denom) if int(denom) > 0 else 1.0
+    return f"{x:.6f}"
+
+
+def accuracy_fields(v) -> List[str]:
+    """The fields of an --accuracy line behind name and status from a part line's integers."""
+    m, len_in, d_in, len_out, d_out, flag = (int(x) for x in v[:ACCURACY_PART_COLS])
+    if flag != ACC_WITH_TRUTH:
+        return ["0"] + ["."] * 6
+    return [str(m), str(len_in), str(d_in), str(len_out), str(d_out), identity_field(d_in, max(len_in, m)), identity_field(d_out, max(len_out, m))]
+
+
 def unrevised_profile(seq) -> np.ndarray:
     """The profile row of a read written unrevised: the base counts of the sequence that was written (str or bytes), no histogram."""
     row = np.zeros(hs.PROFILE_COLS, np.uint64)
@@ -1025,12 +1112,10 @@ SUMMARY_TABLE = (SUMMARY_COLS, SUMMARY_HEADER, "--summary", summary_fields, _sum
 TRIM_TABLE = (4, TRIM_HEADER, "--trim_log", None, None)
 
 
-def merge_report(report: str, names: Sequence[str], log: Callable[[str], None] = print, table=REPORT_TABLE):
-    """Parent side of --report (and, with SUMMARY_TABLE, of --summary; with TRIM_TABLE, of --trim_log): the parts in the order they were written (a later line
-    for the same read wins: the parent's own part comes last), one line per read of `names` sorted by file name, `#total` = the
-    sums over the revised reads; the file appears by rename and the parts are removed."""
+def _part_rows(report: str, cols: int):
+    """({name: fields of its last whole line}, the part files) of a report's parts, in the order they were written: the parent's
+    own part comes last."""
     import glob
-    cols, header, switch, fields, closing = table
     rows = {}
     parts = sorted(glob.glob(glob.escape(report) + ".part*"), key=lambda f: (f.endswith(".partparent"), f))
     for f in parts:
@@ -1039,6 +1124,31 @@ def merge_report(report: str, names: Sequence[str], log: Callable[[str], None] =
                 c = ln.rstrip("\n").split("\t")
                 if ln.endswith("\n") and len(c) == 2 + cols:         # a line cut short by a dying worker is not a line
                     rows[c[0]] = c
+    return rows, parts
+
+
+def _replace_report(report: str, lines, parts):
+    """The merged file appears by rename; the parts are removed."""
+    d = os.path.dirname(report)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    tmp = f"{report}.tmp{os.getpid()}"
+    with open(tmp, "w") as fp:
+        fp.write("\n".join(lines) + "\n")
+    os.replace(tmp, report)
+    for f in parts:
+        try:
+            os.remove(f)
+        except OSError:
+            pass
+
+
+def merge_report(report: str, names: Sequence[str], log: Callable[[str], None] = print, table=REPORT_TABLE):
+    """Parent side of --report (and, with SUMMARY_TABLE, of --summary; with TRIM_TABLE, of --trim_log): the parts in the order they were written (a later line
+    for the same read wins: the parent's own part comes last), one line per read of `names` sorted by file name, `#total` = the
+    sums over the revised reads; the file appears by rename and the parts are removed."""
+    cols, header, switch, fields, closing = table
+    rows, parts = _part_rows(report, cols)
     total, seen = [0] * cols, []
     out = [header]
     for fn in sorted(names):
@@ -1054,18 +1164,74 @@ def merge_report(report: str, names: Sequence[str], log: Callable[[str], None] =
     out.append("#total\trevised\t" + "\t".join(str(t) for t in total) if fields is None else "\t".join(["#total", "revised"] + fields(total)))
     if closing is not None:
         out += closing(seen)
-    d = os.path.dirname(report)
-    if d:
-        os.makedirs(d, exist_ok=True)
-    tmp = f"{report}.tmp{os.getpid()}"
-    with open(tmp, "w") as fp:
-        fp.write("\n".join(out) + "\n")
-    os.replace(tmp, report)
-    for f in parts:
-        try:
-            os.remove(f)
-        except OSError:
-            pass
+    _replace_report(report, out, parts)
+
+
+class AccuracyPart(ReportPart):
+    """One process' share of the --accuracy file, and what forms its lines: the truth set, --accuracy_max_len, the rows of the
+    host routes (`host_rows`) and of a read written unrevised (`add_unrevised`)."""
+
+    def __init__(self, path: Optional[str], truths: Optional[dict], max_len: int = 65536, log: Callable[[str], None] = print):
+        super().__init__(path, ACCURACY_PART_COLS)
+        self.truths, self.max_len, self.log, self.warned = truths or {}, int(max_len), log, False
+
+    def block(self, fns, lens_in):
+        """The truth set of a device call: (truth uint8[], truth_off int64[R + 1], flags).  A read without a record, or whose
+        truth or original length exceeds --accuracy_max_len, has an empty truth."""
+        parts, flags = [], []
+        for fn, n in zip(fns, lens_in):
+            t = truth_of(self.truths, fn)
+            flag = ACC_NO_TRUTH if t is None or len(t) == 0 else (ACC_TOO_LONG if max(len(t), int(n)) > self.max_len else ACC_WITH_TRUTH)
+            parts.append(t if flag == ACC_WITH_TRUTH else b"")
+            flags.append(flag)
+        toff = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.int64)
+        return np.frombuffer(b"".join(parts), np.uint8), toff, flags
+
+    @staticmethod
+    def rows(acc, lens_in, lens_out, flags):
+        """A part line's integers per read from an accuracy block (hoststage.read_accuracy's or the device's)."""
+        return [[int(a[0]), int(n), int(a[1]), int(k), int(a[2]), f] if f == ACC_WITH_TRUTH else [0, int(n), 0, int(k), 0, f]
+                for a, n, k, f in zip(np.asarray(acc).tolist(), lens_in, lens_out, flags)]
+
+    def host_rows(self, T, fns, bases, ev_len, a1, a2):
+        if not self.warned:
+            self.warned = True
+            self.log("[！！！Warning] --accuracy: the edit distances are computed by the host stage, about 0.1 s per read "
+                     "(--device_merge computes them on the GPU)")
+        truth, toff, flags = self.block(fns, ev_len)
+        acc, lens_out = accuracy_rows(T, bases, ev_len, a1, a2, truth, toff)
+        return self.rows(acc, ev_len, lens_out, flags)
+
+    def add_unrevised(self, fn: str, text):
+        """A read written unrevised (text: what was written, str or bytes): len_out = len_in, dist_out = dist_in."""
+        if self.path is None:
+            return
+        text = text.encode("ascii", "replace") if isinstance(text, str) else bytes(text)
+        truth, toff, (flag,) = self.block([fn], [len(text)])
+        d = hs.edit_distance(truth, text) if flag == ACC_WITH_TRUTH else 0
+        self.add(fn, False, [int(toff[1]), len(text), d, len(text), d, flag])
+
+
+def merge_accuracy(path: str, names: Sequence[str], log: Callable[[str], None] = print):
+    """Parent side of --accuracy: the parts as `merge_report` reads them, one line per read of `names` sorted by file name, then
+    #total - the sums over the reads WITH a truth, revised or not, and the pooled identities 1 - sum(dist) / sum(max(len,
+    truth_len)) - and #reads with_truth / no_truth / too_long; the file appears by rename and the parts are removed."""
+    rows, parts = _part_rows(path, ACCURACY_PART_COLS)
+    out, total, den, counts = [ACCURACY_HEADER], [0] * 5, [0, 0], [0, 0, 0]
+    for fn in sorted(names):
+        c = rows.get(fn)
+        if c is None:
+            log(f"[！！！Warning] --accuracy: no record for {fn}")
+            c = [fn, "unrevised", "0", "0", "0", "0", "0", str(ACC_NO_TRUTH)]
+        v = [int(x) for x in c[2:]]
+        out.append("\t".join(c[:2] + accuracy_fields(v)))
+        counts[v[5]] += 1
+        if v[5] == ACC_WITH_TRUTH:
+            total = [t + x for t, x in zip(total, v[:5])]
+            den = [den[0] + max(v[1], v[0]), den[1] + max(v[3], v[0])]
+    out.append("\t".join(["#total", "with_truth"] + [str(t) for t in total] + [identity_field(total[2], den[0]), identity_field(total[4], den[1])]))
+    out.append("#reads\t" + "\t".join(str(x) for x in counts))
+    _replace_report(path, out, parts)
 
 
 EDITS_HEADER = "#pos_in\tpos_out\tkind\tref\talt\tqual\tconf"
@@ -1101,9 +1267,10 @@ def write_edits(edits_dir: str, fast5_fn: str, edits=None, want_qual: bool = Fal
 
 
 def _host_merge_form(packed):
-    """A `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` tuple back in the form whose call
-    returns (p1, p2, a1, a2): for the paths that keep the host merge."""
-    if packed is None or len(packed) not in (12, 14, 16, 20, 22, 27):
+    """A `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` /
+    `with_device_trim` / `with_device_accuracy` tuple back in the form whose call returns (p1, p2, a1, a2): for the paths that
+    keep the host merge."""
+    if packed is None or len(packed) not in (12, 14, 16, 20, 22, 27, 30):
         return packed
     return tuple(packed[:7]) if packed[7] is None else tuple(packed[:9])
 
@@ -1119,12 +1286,12 @@ def _bundle_has_bases(bundle) -> bool:
 
 
 def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, report, edits=False, combined=False, summary=False,
-                 trim=False):
+                 trim=False, accuracy=False):
     """The one decision about a batch: (packed form `_FileRun.submit` builds, route `_FileRun.run_batch` takes).  Pure: it looks at what
     the engine object offers, at the bundle (None: reads that arrived one by one) and at the run's switches - pipelined (one
     engine, NRV_CLI_PIPELINE != 0), native_pool (libnanorev_host.so driven from the thread pool), device_merge (--device_merge
     and what it needs: pipelined, native_pool, nrvh_write_records), report (--report), edits (--edits), combined (--combined),
-    summary (--summary), trim (--trim_q).  "bases":
+    summary (--summary), trim (--trim_q), accuracy (--truth / --accuracy).  "bases":
     `_bundle_has_bases`.  A form is
     the length of the packed tuple (engine.Reviser), None, or "host-merge": the merge form built and taken back.
 
@@ -1145,6 +1312,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
       yes     + summary on, such a form, no with_device_profile              host-merge [2]  by the last three rows
       yes     + trim on, a form 12 / 14 / 16 / 20 / 22 above, with_device_trim  27 [8]         by the last three rows
       yes     + trim on, such a form, no with_device_trim                    host-merge [2]  by the last three rows
+      yes     + accuracy on, a form 12 ... 27 above, with_device_accuracy    30 [9]          by the last three rows
+      yes     + accuracy on, such a form, no with_device_accuracy            host-merge [2]  by the last three rows
       yes     any form; pipelined, native_pool, begin_packed_raw, bases                      pipelined [3]
       yes     any form; native_pool, bases, not (pipelined, begin_packed_raw)                packed+finish_bundle
       yes     any form; no native_pool, or no bases                                          packed sliced
@@ -1161,7 +1330,10 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
         other route forms the summary rows on the host from the calls (`profile_rows`).
     [8] the one call carries whatever the form above carried and the per-read trim bounds last; its records, where it has some,
         are those of the trimmed reads.  Every other route finds the bounds on the host from the calls (`trim_rows`); `deliver`
-        applies them on every route."""
+        applies them on every route.
+    [9] the one call carries whatever the form above carried and the accuracy block last: per read the edit distance of the
+        original and of the (untrimmed) revised read to its truth.  Every other route computes the rows on the host from the
+        reads it holds (`accuracy_rows`)."""
     unpacked = "per-read" if n_reads == 1 else "predict_many"
     if bundle is None:
         return (7 if n_reads > 1 and hasattr(rv, "pack_reads_raw") else None), unpacked
@@ -1179,6 +1351,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
             form = 22 if hasattr(rv, "with_device_profile") else "host-merge"
         if trim and form != "host-merge":
             form = 27 if hasattr(rv, "with_device_trim") else "host-merge"
+        if accuracy and form != "host-merge":
+            form = 30 if hasattr(rv, "with_device_accuracy") else "host-merge"
     if not (native_pool and bases):
         return form, "packed sliced"
     return form, ("pipelined" if pipelined and hasattr(rv, "begin_packed_raw") else "packed+finish_bundle")
@@ -1287,7 +1461,7 @@ class _FileRun:
     `_route_batch` says (`submit`) and collects the pooled finishers; the ENGINE thread(s) make the calls (`run_batch`, `collect`);
     the one FINISHER thread merges, reports and writes, or hands that to the parser pool (`finish_batch`, `finish_call`)."""
     def __init__(self, stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part=None,
-                 summary_part=None, trim_part=None):
+                 summary_part=None, trim_part=None, accuracy_part=None):
         self.args, self.log, self.note = args, log, on_file or (lambda fn, ok: None)
         self.stats = {"reads": 0, "bases": 0, "failed": [], "host_s": 0.0, "engine_s": 0.0}
         self.stats_lock = threading.Lock()
@@ -1298,6 +1472,11 @@ class _FileRun:
         self.trim = trim_rule(args)                   # --trim_q: (Q, W, min_len); the bounds are stashed like a report row and
         self.trim_rows = {}                           # applied by `deliver`; fn -> (bases of the untrimmed read, (lo, hi))
         self.trimpart = ReportPart(trim_part if self.trim else None, 4)
+        # --truth / --accuracy: the rows are stashed like a report row; every process loads the truth set itself
+        self.accpart = AccuracyPart(accuracy_part, load_truth(args.truth) if accuracy_part else None,
+                                    getattr(args, "accuracy_max_len", 65536), log)
+        self.acc_rows = {}
+        self.acc_flags = {}                           # id(batch) -> the flags of a form 30 call's truth block, until its call is back
         self.tie_eps = float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS))
         self.edits_dir = getattr(args, "edits", None) # --edits: every read's list is written BEFORE its output is
         self.sink = CombinedPart(combined_part, args.output_format == "fastq") if combined_part else None   # --combined (`deliver`)
@@ -1407,6 +1586,7 @@ class _FileRun:
         self.report.close()
         self.sumpart.close()
         self.trimpart.close()
+        self.accpart.close()
         if self.sink is not None:
             self.sink.close()
         self.trace.log_summary(self.log, len(self.engines))
@@ -1468,6 +1648,8 @@ class _FileRun:
             self.sumpart.add(fn, False, unrevised_profile(text))
         self.trim_rows.pop(fn, None)
         self.trimpart.add(fn, False, unrevised_trim(nw))
+        self.acc_rows.pop(fn, None)
+        self.accpart.add_unrevised(fn, text)
         self.note(fn, False)
 
     def finished(self, fn, nb):
@@ -1482,6 +1664,11 @@ class _FileRun:
             if row is None:                           # cannot happen, as above
                 self.log(f"[！！！Warning] --summary: no counts for {fn}")
             self.sumpart.add(fn, row is not None, row if row is not None else np.zeros(hs.PROFILE_COLS, np.uint64))
+        if self.accpart:
+            row = self.acc_rows.pop(fn, None)
+            if row is None:                           # cannot happen, as above
+                self.log(f"[！！！Warning] --accuracy: no distances for {fn}")
+            self.accpart.add(fn, row is not None, row if row is not None else [0, nb, 0, nb, 0, ACC_NO_TRUTH])
         if self.trim:
             row = self.trim_rows.pop(fn, None)
             log_row = trim_log_row(row[0], row[1], self.trim[2]) if row is not None else unrevised_trim(nb)
@@ -1507,7 +1694,7 @@ class _FileRun:
                 bundle = _bundle_host_stats(bundle)   # an engine without the new calls: the host computes them after all
             form, route = _route_batch(rv, bundle, len(batch), self.pipelined, self.native_pool, self.device_merge, bool(self.report),
                                        edits=bool(self.edits_dir), combined=self.sink is not None, summary=bool(self.sumpart),
-                                       trim=self.trim is not None)
+                                       trim=self.trim is not None, accuracy=bool(self.accpart))
             if form is not None and bundle is None:
                 packed = prepare_many(cls, [rt for _, rt, _ in batch], rv.T)
             elif form is not None:
@@ -1521,15 +1708,20 @@ class _FileRun:
                     elif form != len(packed):
                         if self.report:
                             packed = cls.with_device_report(packed, self.tie_eps)
-                        if form == 16 or (form in (20, 22, 27) and self.edits_dir):   # --edits: the list behind the merge (and the report)
+                        if form == 16 or (form in (20, 22, 27, 30) and self.edits_dir):   # --edits: the list behind the merge (and the report)
                             packed = cls.with_device_edits(packed)
-                        if form == 20 or (form in (22, 27) and self.sink is not None and hasattr(rv, "with_device_records")):
+                        if form == 20 or (form in (22, 27, 30) and self.sink is not None and hasattr(rv, "with_device_records")):
                             # --combined: the records behind them all; seq / qual stay on the device
                             packed = cls.with_device_records(packed, [hs.record_name(fn) for fn, _, _ in batch], hand_back=False)
-                        if form == 22 or (form == 27 and self.sumpart):   # --summary: the profile, behind whatever the call carries
+                        if form == 22 or (form in (27, 30) and self.sumpart):   # --summary: the profile, behind whatever the call carries
                             packed = cls.with_device_profile(packed)
-                        if form == 27:                # --trim_q: the bounds last; the records above are then those of the trimmed reads
+                        if form == 27 or (form == 30 and self.trim):   # --trim_q: the bounds last; the records above are then those of the trimmed reads
                             packed = cls.with_device_trim(packed, *self.trim)
+                        if form == 30:                # --accuracy: the distances to the truth, behind everything else
+                            fns = [fn for fn, _, _ in batch]
+                            truth, toff, flags = self.accpart.block(fns, bundle["meta"][:, 1].tolist())
+                            packed = cls.with_device_accuracy(packed, truth, toff)
+                            self.acc_flags[id(batch)] = flags
         except Exception:
             packed = None
         if packed is None:
@@ -1561,6 +1753,7 @@ class _FileRun:
     def finish_batch(self, batch, calls):
         """Read by read: with a worker pool the merge + file write is a pool task (~20 KB per read), without one it happens here."""
         T = self.rv.T
+        self.acc_flags.pop(id(batch), None)
         for (fn, rt, fq), c in zip(batch, calls):
             if isinstance(c, Exception):
                 self.fallback(fn, rt, fq, c)
@@ -1574,6 +1767,8 @@ class _FileRun:
                 if self.trim:
                     tb, tl = _trim_rows_len(T, rt.bases, [len(np.asarray(rt.bases))], *c, *self.trim[:2])
                     self.trim_rows[fn], trim = (int(tl[0]), tb[0]), (tb, self.trim[2])
+                if self.accpart:
+                    self.acc_rows[fn] = self.accpart.host_rows(T, [fn], rt.bases, [len(np.asarray(rt.bases))], c[2], c[3])[0]
                 if self.edits_dir:
                     write_edits(self.edits_dir, fn, edit_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual)[0], self.want_qual)
                 if self.pool is not None or self.sink is not None:
@@ -1601,7 +1796,13 @@ class _FileRun:
         try:
             fns, rts, fqs = map(list, zip(*batch))
             trim = None
+            flags = self.acc_flags.pop(id(batch), None)
             if merged:
+                if len(outs) == 11:                   # a `with_device_accuracy` call: the distances were found behind everything else, last output
+                    if self.accpart and flags is not None:
+                        ev_len = bundle["meta"][:, 1].astype(np.int64)
+                        self.acc_rows.update(zip(fns, self.accpart.rows(outs[10], ev_len.tolist(), np.diff(outs[2]).tolist(), flags)))
+                    outs = outs[:10]
                 if len(outs) == 10:                   # a `with_device_trim` call: the bounds were found behind the merge, last output
                     if self.trim:
                         self.trim_rows.update(zip(fns, zip(np.diff(outs[2]).tolist(), outs[9])))
@@ -1628,6 +1829,8 @@ class _FileRun:
                     tb, tl = _trim_rows_len(T, bundle["bases"], ev_len, p1, p2, a1, a2, *self.trim[:2])
                     self.trim_rows.update(zip(fns, zip(tl.tolist(), tb)))
                     trim = (tb, self.trim[2])
+                if self.accpart:
+                    self.acc_rows.update(zip(fns, self.accpart.host_rows(T, fns, bundle["bases"], ev_len.tolist(), a1, a2)))
                 if self.edits_dir:
                     self.write_call_edits(fns, *edit_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2, self.want_qual))
                 qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
@@ -1725,7 +1928,7 @@ class _FileRun:
 def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None],
                   on_file: Optional[Callable[[str, bool], None]] = None, gpu_workers: int = 1,
                   core_share: Optional[int] = None, report_part: Optional[str] = None, combined_part: Optional[str] = None,
-                  summary_part: Optional[str] = None, trim_part: Optional[str] = None) -> dict:
+                  summary_part: Optional[str] = None, trim_part: Optional[str] = None, accuracy_part: Optional[str] = None) -> dict:
     """Revise `files` (names inside args.fast5_base_dir) with one engine.  The host stage (HDF5 parsing, event collapse,
     statistics) runs --thread parser workers that stay a bounded number of reads ahead of the device: THREADS of this process
     inside libnanorev_host.so (at most kNativePoolMax), or PROCESSES on the Python host stage without it / with NRV_HOST_THREADS=0.
@@ -1737,10 +1940,11 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
     divided them (a GPU worker pinned to its NUMA slice: `_worker`).  report_part (--report): the file this call appends
     one line per read to, ahead of on_file (`ReportPart`).  combined_part (--combined): the part this call appends
     every read's record to INSTEAD of writing one file per read (`CombinedPart`, `deliver`).  summary_part (--summary): as
-    report_part, for the summary's lines.  trim_part (--trim_log): as report_part, for the trim log's lines."""
+    report_part, for the summary's lines.  trim_part (--trim_log): as report_part, for the trim log's lines.  accuracy_part
+    (--accuracy): as report_part, for the accuracy file's lines."""
     import contextlib
     with contextlib.ExitStack() as stack:             # its exit ends the run's threads and undoes what `_FileRun._start` did
-        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part, summary_part, trim_part)
+        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part, summary_part, trim_part, accuracy_part)
         batch, nev = [], 0                            # unbundled reads are grouped into device calls of >= batch_events events
         for entries, bundle in run.results():
             bundled = []
@@ -1753,6 +1957,7 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                     run.report.add(fn, False, unrevised_row(0))
                     run.sumpart.add(fn, False, unrevised_profile(b""))
                     run.trimpart.add(fn, False, unrevised_trim(0))
+                    run.accpart.add_unrevised(fn, b"")
                     run.note(fn, False)
                 elif err is not None:
                     run.fallback(fn, rt, fq, err)
@@ -2015,7 +2220,8 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
                            report_part=report_part_path(args.report, rank) if getattr(args, "report", None) else None,
                            combined_part=combined_part_path(args.combined, rank) if getattr(args, "combined", None) else None,
                            summary_part=report_part_path(args.summary, rank) if getattr(args, "summary", None) else None,
-                           trim_part=report_part_path(args.trim_log, rank) if getattr(args, "trim_log", None) else None)
+                           trim_part=report_part_path(args.trim_log, rank) if getattr(args, "trim_log", None) else None,
+                           accuracy_part=report_part_path(args.accuracy, rank) if getattr(args, "accuracy", None) else None)
         st["cpus"] = len(cpus) if cpus else 0
         for e in made:
             e.close()
@@ -2026,7 +2232,7 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
 
 def write_originals(args, files: Sequence[str], log: Callable[[str], None], report: Optional[ReportPart] = None,
                     sink: Optional[CombinedPart] = None, summary: Optional[ReportPart] = None,
-                    trimlog: Optional[ReportPart] = None) -> List[str]:
+                    trimlog: Optional[ReportPart] = None, accuracy: Optional["AccuracyPart"] = None) -> List[str]:
     """The failure contract for reads whose WORKER is gone (NanoReviser.py:146-152 / :173-179): every
     file in `files` - the ones the dead worker never reported as final - gets its original basecalls
     written by this process (atomically, replacing whatever an earlier run left under that name).
@@ -2054,12 +2260,14 @@ def write_originals(args, files: Sequence[str], log: Callable[[str], None], repo
             summary.add(fn, False, unrevised_profile(text))
         if trimlog is not None:
             trimlog.add(fn, False, unrevised_trim(nw))
+        if accuracy is not None:
+            accuracy.add_unrevised(fn, text)
     return done
 
 
 def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[str], None], report: Optional[ReportPart] = None,
                        sink: Optional[CombinedPart] = None, summary: Optional[ReportPart] = None,
-                       trimlog: Optional[ReportPart] = None):
+                       trimlog: Optional[ReportPart] = None, accuracy: Optional["AccuracyPart"] = None):
     """Parent side of the split reads: the slices' calls in slice order are the read's calls (window i of slice k is
     window lo_k + i of the read), merged and written exactly as an unsplit read's.  A read with a slice missing (its
     worker died) or failed gets its original basecalls (NanoReviser.py:146-152).  Returns (bases written, failed names)."""
@@ -2108,13 +2316,15 @@ def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[st
                         (qc if qc is not None else np.zeros(0, np.uint8)) if args.output_format == "fastq" else None, T,
                         float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS)))[0]
                     report.add(fn, True, row)
+                if accuracy is not None and accuracy:  # the slices are merged: the read's distances, here in the parent
+                    accuracy.add(fn, True, accuracy.host_rows(T, [fn], pl[0]["bases"], [N], a1, a2)[0])
                 if summary is not None and summary and have_p:
                     summary.add(fn, True, profile_rows(T, pl[0]["bases"], [N], np.concatenate([p["p1"] for p in pl]),
                                                        np.concatenate([p["p2"] for p in pl]), a1, a2)[0])
                 continue
             err = e2
         log(f"[！！！Error] revising {fn.split('.')[0]}: {err}; writing the original basecalls")
-        write_originals(args, [fn], log, report, sink, summary, trimlog)
+        write_originals(args, [fn], log, report, sink, summary, trimlog, accuracy)
         failed.append(fn)
     return nb, failed
 
@@ -2209,6 +2419,19 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
             os.makedirs(d, exist_ok=True)
     parent_trim = ReportPart(report_part_path(trim_log, "parent") if trim_log else None, 4)
     trim_part0 = report_part_path(trim_log, 0) if trim_log else None
+    parent_acc, acc_part0 = None, None
+    if args.accuracy:                     # --accuracy: parts and a parent-side merge as for --report; the truth set is checked here
+        try:
+            truths = load_truth(args.truth)
+        except (OSError, ValueError) as e:
+            print(f"[！！！Error] {e}", file=sys.stderr)
+            return 2
+        clear_report_parts(args.accuracy)
+        d = os.path.dirname(args.accuracy)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        parent_acc = AccuracyPart(report_part_path(args.accuracy, "parent"), truths, args.accuracy_max_len)
+        acc_part0 = report_part_path(args.accuracy, 0)
     if args.combined:                     # --combined: a part per process too, `merge_combined` ends the run
         clear_combined_parts(args.combined)
     parent_sink = CombinedPart(combined_part_path(args.combined, "parent"), args.output_format == "fastq") if args.combined else None
@@ -2248,7 +2471,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
     if reviser_factory is not None:       # in-process (tests / embedding): one engine, no sharding
         rv = reviser_factory(args, 0)
         stats = [process_files(args, names, rv, print, report_part=report_part_path(args.report, 0) if args.report else None,
-                               combined_part=part0, summary_part=sum_part0, trim_part=trim_part0)]
+                               combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0)]
     else:
         # the command line needs no torch: without it a process starts ~1.5 s sooner.  (engine.py imports
         # torch first only so that a LATER torch import in the same process finds one HIP runtime.)
@@ -2277,7 +2500,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
                 made.append((worker_factory or _default_factory)(args, 0))
                 return made[-1]                       # called once per engine (process_files: NRV_CLI_ENGINES)
             stats = [process_files(args, names, make, print, report_part=report_part_path(args.report, 0) if args.report else None,
-                                   combined_part=part0, summary_part=sum_part0, trim_part=trim_part0)]
+                                   combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0)]
             for rv in made:
                 rv.close()
         else:
@@ -2288,7 +2511,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
             res = run_workers(args, shards, worker_factory, part_shards=part_shards, parts_out=parts_got)
             stats = [s for _, s, _, _ in res if s is not None]
             if split_fns:
-                nb_split, failed_split = finish_split_reads(args, split_fns, parts_got, print, parent_report, parent_sink, parent_summary, parent_trim)
+                nb_split, failed_split = finish_split_reads(args, split_fns, parts_got, print, parent_report, parent_sink, parent_summary, parent_trim, parent_acc)
                 stats.append({"reads": len(split_fns), "bases": nb_split, "failed": failed_split, "host_s": 0.0, "engine_s": 0.0})
                 if failed_split:
                     rc = 3
@@ -2298,7 +2521,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
                           f"unfinished reads", file=sys.stderr)
                     # what the worker reported final stays (its failed reads keep their failed_reads entry);
                     # everything else - started or not, whatever lies on disk - is written unrevised
-                    lost = write_originals(args, [f for f in shards[r] if f not in final], print, parent_report, parent_sink, parent_summary, parent_trim)
+                    lost = write_originals(args, [f for f in shards[r] if f not in final], print, parent_report, parent_sink, parent_summary, parent_trim, parent_acc)
                     lost += [f for f, ok in final.items() if not ok]
                     stats.append({"reads": len(shards[r]), "bases": 0, "failed": lost, "host_s": 0.0, "engine_s": 0.0})
                     rc = 3
@@ -2311,6 +2534,9 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
     parent_trim.close()
     if trim_log:
         merge_report(trim_log, all_names, table=TRIM_TABLE)
+    if parent_acc is not None:
+        parent_acc.close()
+        merge_accuracy(args.accuracy, all_names)
     if args.combined:
         parent_sink.close()
         merge_combined(args.combined, args.output_format == "fastq")

@@ -479,11 +479,11 @@ struct DevModel {
 // ---- a merged raw-read call (nrv_revise_reads_raw*_begin; nrv_merge_calls* is its test twin) -------------------------------
 // The merged block of a call of N events, n windows, n_reads reads - offsets into one device allocation:
 //   [off i64 x (n_reads + 1) | seq | qual | report u64 x n_reads x 24 | edit_off i64 x (n_reads + 1) | rec_off i64 x (n_reads + 1) |
-//    profile u64 x n_reads x 48 | trim i64 x n_reads x 2]
+//    profile u64 x n_reads x 48 | trim i64 x n_reads x 2 | accu u64 x n_reads x 4]
 //                                     what comes back in one copy of `dl` bytes, mirrored in page-locked memory (nrv_merge.h,
-//                                     nrv_report.h, nrv_edits.h, nrv_pack.h, nrv_profile.h, nrv_trim.h); the report, edit_off,
-//                                     rec_off, the profile and the trim only where asked for - without them the layout is the
-//                                     merge's own.  A records call that hands back neither seq nor qual leaves those two on
+//                                     nrv_report.h, nrv_edits.h, nrv_pack.h, nrv_profile.h, nrv_trim.h, nrv_align.h); the report,
+//                                     edit_off, rec_off, the profile, the trim and the accuracy only where asked for - without
+//                                     them the layout is the merge's own.  A records call that hands back neither seq nor qual leaves those two on
 //                                     the device
 //   [rec u32 x N | tile u64]          the merge kernels' scratch
 //   [edits nrv_edit x n | etile u64]  the edit records, fetched by their used prefix in a copy of their own, and their scratch;
@@ -492,8 +492,10 @@ struct DevModel {
 //                                     records; only where asked for
 //   [tq u8 x (N + n) | acc u64 x n_reads x 2]   the trim kernels' scratch: Phred per output character, the bounds' accumulators;
 //                                     only where asked for
+//   [hc u8 x N | hc u8 x (N + n)]     the alignment's stripe carries, one byte per character of the original and of the revised
+//                                     reads; only where asked for
 // Every part is 256-byte aligned.
-struct MergeLayout { size_t seq, qual, rep, eoff, roff, prof, trim, rec, tile, edits, etile, blob, tq, acc, dl, bytes; };
+struct MergeLayout { size_t seq, qual, rep, eoff, roff, prof, trim, rec, tile, edits, etile, blob, tq, acc, dl, bytes, accu, hc; };
 
 // What a merged call reads besides the raw reads.  Consumed inside _begin: the caller's pointers are dead once it returns, so
 // nothing that outlives _begin keeps one (the slot keeps the VALUES of both threshold sets for the re-run of nrv_reads_raw_end)
@@ -506,6 +508,8 @@ struct MergeIn {
   const float* trim_thr = nullptr;      // nrv_revise_reads_raw_trim_begin: its own 39 thresholds, and the rule
   int Q = 0, W = 0;
   int64_t min_len = 0;
+  const uint8_t* truth = nullptr;       // nrv_revise_reads_raw_accuracy_begin: the true sequences and [n_reads + 1]
+  const int64_t* truth_off = nullptr;
 };
 // The trim's rule as the kernels take it: the VALUES a slot keeps for the re-run are of this form too (thr points into the slot)
 struct TrimRule { const float* thr = nullptr; int Q = 0, W = 0; int64_t min_len = 0; };
@@ -522,6 +526,7 @@ struct MergeOut {
   int64_t* rec_off = nullptr;
   uint64_t* profile = nullptr;          // [n_reads][48]
   int64_t* trim = nullptr;              // [n_reads][2]
+  uint64_t* accuracy = nullptr;         // [n_reads][4]
 };
 // Where a merged call's inputs lie on the device, and its merged block
 struct MergeView {
@@ -534,6 +539,8 @@ struct MergeView {
   const long long* name_off;             // records only
   const unsigned char* names;
   char* blk;                             // MergeLayout offsets count from here
+  const unsigned char* truth = nullptr;  // accuracy only
+  const long long* truth_off = nullptr;
 };
 // The quality rule: characters get a Phred quality when there are thresholds and somebody reads it - the caller's qual or the
 // FASTQ records (nrv_merge_calls* has no records: q_thr && qual there)
@@ -610,9 +617,10 @@ struct nrv_handle {
     size_t off_aux = 0;                                                   // nrv_reads_raw_stats_begin: [.. | StatAux per read] behind feat
     unsigned* d_stat = nullptr; size_t cap_stat = 0;                      // ... and its scratch (min / max, histograms: nrv_stats.h)
     // a merged call: its bases and, for records, its names [.. | bases u8 | name_off i64 x (n_reads + 1) | names u8] at the end of
-    // d_in; the merged block (MergeLayout) with its page-locked mirror - the ONLY part such a call downloads, with the 64-byte
+    // d_in (and behind them, for the accuracy, the truth); the merged block (MergeLayout) with its page-locked mirror - the ONLY part such a call downloads, with the 64-byte
     // counter of d_out; where the results go; and the values the re-run of nrv_reads_raw_end needs once the inputs are gone
     size_t off_bases = 0, off_noff = 0, off_names = 0;
+    size_t off_toff = 0, off_truth = 0;                                   // accuracy: [.. | truth_off i64 x (n_reads + 1) | truth u8] behind names
     char* d_mrg = nullptr; char* pin_mrg = nullptr; size_t cap_mrg = 0;
     MergeLayout m = {};
     MergeOut out;
@@ -1609,6 +1617,7 @@ static int merged_collect(nrv_handle* h, const char* who, const char* who_edits,
   if (o.report) memcpy(o.report, head + m.rep, (size_t)v.n_reads * kReportCols * 8);
   if (o.profile) memcpy(o.profile, head + m.prof, (size_t)v.n_reads * kProfileCols * 8);
   if (o.trim) memcpy(o.trim, head + m.trim, (size_t)v.n_reads * 16);
+  if (o.accuracy) memcpy(o.accuracy, head + m.accu, (size_t)v.n_reads * kAccuracyCols * 8);
   int rc = NRV_OK;
   if (o.edit_off) {
     const int64_t n_ed = ((const int64_t*)(head + m.eoff))[v.n_reads];
@@ -2123,6 +2132,20 @@ static int trim_enqueue(nrv_handle* h, const MergeArgs& m, const float* p1, cons
   a.acc = (unsigned long long*)acc; a.trim = (long long*)trim;
   return trim_bounds_enqueue(h, a);
 }
+// align_kernel (nrv_align.h): one wave per (read, kind) pair; every word of its result is stored plainly
+static int align_enqueue(nrv_handle* h, const AlignArgs& a) {
+  if (a.n_reads <= 0) return NRV_OK;
+  hipLaunchKernelGGL(align_kernel, dim3((unsigned)a.n_reads * (unsigned)a.kinds), dim3(64), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return NRV_OK;
+}
+// a truth set: offsets that ascend from 0, bytes where there are any, and no sequence of 2^31 - 64 characters or more
+static bool truth_ok(const uint8_t* truth, const int64_t* truth_off, int n_reads) {
+  if (!truth_off || truth_off[0] != 0) return false;
+  for (int r = 0; r < n_reads; ++r)
+    if (truth_off[r + 1] < truth_off[r] || truth_off[r + 1] - truth_off[r] >= ((int64_t)1 << 31) - 64) return false;
+  return truth != nullptr || truth_off[n_reads] == 0;
+}
 static bool trim_rule_ok(int Q, int W, int64_t min_len) { return Q >= 1 && Q <= 40 && W >= 1 && W <= kTrimMaxW && min_len >= 0; }
 // bytes the records of a call can take: hoststage.pack_records on N + max(N - T, 0) characters at the most
 static size_t blob_capacity(int64_t N, int64_t n, int n_reads, int64_t name_bytes, bool fastq) {
@@ -2175,7 +2198,8 @@ static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, const MergeOu
   m.roff = m.eoff + (o.edit_off ? up(((size_t)n_reads + 1) * 8) : 0);
   m.prof = m.roff + (o.rec_off ? up(((size_t)n_reads + 1) * 8) : 0);
   m.trim = m.prof + (o.profile ? up((size_t)n_reads * kProfileCols * 8) : 0);
-  m.dl = m.trim + (o.trim ? up((size_t)n_reads * 16) : 0);
+  m.accu = m.trim + (o.trim ? up((size_t)n_reads * 16) : 0);
+  m.dl = m.accu + (o.accuracy ? up((size_t)n_reads * kAccuracyCols * 8) : 0);
   m.rec = m.dl;
   m.tile = m.rec + up((size_t)N * 4);
   m.edits = m.tile + up(tiles * 8);
@@ -2183,7 +2207,8 @@ static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, const MergeOu
   m.blob = m.etile + (o.edit_off ? up(tiles * 8) : 0);
   m.tq = m.blob + (o.rec_off ? up(blob_cap) : 0);
   m.acc = m.tq + (o.trim ? up(cap) : 0);
-  m.bytes = m.acc + (o.trim ? up((size_t)n_reads * 16) : 0);
+  m.hc = m.acc + (o.trim ? up((size_t)n_reads * 16) : 0);
+  m.bytes = m.hc + (o.accuracy ? up((size_t)N) + up(cap) : 0);
   return m;
 }
 // No window at all (N <= T): the reads come back as they are, on the host
@@ -2226,6 +2251,36 @@ static void trim_nothing(const nrv_read_desc* reads, int n_reads, int Q, int W, 
     trim[2 * r + 1] = any ? reads[r].ev_len : 0;
   }
 }
+// hoststage.edit_distance by two rows of the table, on the host: the calls without a window and nothing else
+static int64_t edit_distance_host(const uint8_t* t, int64_t m, const uint8_t* s, int64_t n) {
+  std::vector<int64_t> row((size_t)n + 1);
+  for (int64_t j = 0; j <= n; ++j) row[(size_t)j] = j;
+  for (int64_t i = 1; i <= m; ++i) {
+    int64_t diag = row[0];
+    row[0] = i;
+    const uint8_t c = t[i - 1];
+    const bool base = c == 'A' || c == 'C' || c == 'G' || c == 'T';
+    for (int64_t j = 1; j <= n; ++j) {
+      const int64_t up_ = row[(size_t)j] + 1, left = row[(size_t)j - 1] + 1, dg = diag + ((base && c == s[j - 1]) ? 0 : 1);
+      diag = row[(size_t)j];
+      row[(size_t)j] = std::min(std::min(up_, left), dg);
+    }
+  }
+  return row[(size_t)n];
+}
+// ... and its accuracy (hoststage.read_accuracy on a call without a window): the reads come back as they are, dist_out = dist_in
+static void accuracy_nothing(const uint8_t* bases, const nrv_read_desc* reads, int n_reads, const uint8_t* truth, const int64_t* truth_off,
+                             uint64_t* accuracy) {
+  static_assert(NRV_ACCURACY_COLS == kAccuracyCols, "nanorev.h and nrv_align.h disagree on the accuracy's columns");
+  memset(accuracy, 0, (size_t)n_reads * kAccuracyCols * 8);
+  for (int r = 0; r < n_reads; ++r) {
+    const int64_t m = truth_off[r + 1] - truth_off[r];
+    if (m <= 0) continue;
+    uint64_t* row = accuracy + (size_t)r * kAccuracyCols;
+    row[0] = (uint64_t)m;
+    row[1] = row[2] = (uint64_t)edit_distance_host(truth + truth_off[r], m, bases + reads[r].ev_off, reads[r].ev_len);
+  }
+}
 // ... and everything a merged call asks for, for both callers that can meet N <= T
 static void merged_nothing(const MergeIn& in, const MergeOut& o, const nrv_read_desc* reads, int n_reads, int64_t N) {
   merge_nothing(in.bases, reads, n_reads, N, o.seq, in.q_thr ? o.qual : nullptr, o.off);
@@ -2235,6 +2290,7 @@ static void merged_nothing(const MergeIn& in, const MergeOut& o, const nrv_read_
   if (o.rec_off) records_host(in.bases, nullptr, o.off, n_reads, in.names, in.name_off, in.q_thr != nullptr, o.blob, o.rec_off,
                               o.trim, in.min_len);
   if (o.profile) profile_nothing(in.bases, reads, n_reads, o.profile);
+  if (o.accuracy) accuracy_nothing(in.bases, reads, n_reads, in.truth, in.truth_off, o.accuracy);
 }
 
 // The kernels of a merged call behind whatever produced v.a1 / a2 / p1 / p2 on the compute stream: the merge, then what `o` asks
@@ -2270,6 +2326,17 @@ static int merged_enqueue(nrv_handle* h, const MergeView& v, const MergeLayout& 
     rc = pack_enqueue(h, k);
   }
   if (!rc && o.profile) rc = profile_enqueue(h, profile_args(a, v.p1, v.p2, prof_thr, v.blk + m.prof));
+  if (!rc && o.accuracy) {                                 // LAST: it reads bases, the descriptors, off / seq and the truth
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    AlignArgs k;
+    k.n_reads = v.n_reads; k.kinds = 2;
+    k.truth = v.truth; k.truth_off = v.truth_off;
+    k.reads = v.reads; k.bases = v.bases; k.off = a.off; k.seq = a.seq;
+    k.cap0 = v.N; k.cap1 = v.N + (v.N - h->T > 0 ? v.N - h->T : 0);
+    k.hc0 = (unsigned char*)(v.blk + m.hc); k.hc1 = k.hc0 + up((size_t)v.N);
+    k.accu = (unsigned long long*)(v.blk + m.accu); k.dist = nullptr;
+    rc = align_enqueue(h, k);
+  }
   return rc;
 }
 // the trim rule a slot keeps
@@ -2280,7 +2347,8 @@ static MergeView slot_view(const nrv_handle::RawSlot& sl) {
   return MergeView{(const SegRead*)(sl.d_in + sl.off_reads), sl.n_reads, sl.N, (const unsigned char*)(sl.d_in + sl.off_bases),
                    (const signed char*)(d + sl.rows * 44), (const signed char*)(d + sl.rows * 45), (const float*)d,
                    (const float*)(d + sl.rows * 24), (const long long*)(sl.d_in + sl.off_noff),
-                   (const unsigned char*)(sl.d_in + sl.off_names), sl.d_mrg};
+                   (const unsigned char*)(sl.d_in + sl.off_names), sl.d_mrg,
+                   (const unsigned char*)(sl.d_in + sl.off_truth), (const long long*)(sl.d_in + sl.off_toff)};
 }
 // What comes back of a slot's call, on stream s.  A plain call: its output block.  A merged call: the counter and the merged block,
 // all of [0, m.dl) - or, for a records call that hands back neither seq nor qual, the parts in front of and behind them; p1 / p2 /
@@ -2326,6 +2394,7 @@ static int raw_begin(nrv_handle* h, const RawIn& in, float* p1, float* p2, int8_
     if (blob_cap > 0 && !mo->blob) { h->err = "nrv_revise_reads_raw_records_begin: null blob"; return NRV_E_INVALID; }
     if (blob_cap >= ((size_t)1 << 32)) { h->err = "nrv_revise_reads_raw_records_begin: records of 4 GiB and more in one call"; return NRV_E_INVALID; }
   }
+  const bool accuracy = mr != nullptr && mo->accuracy != nullptr;   // (revise_begin has checked the truth)
   const bool with_stats = last_dur != nullptr || on_device != nullptr;
   const int64_t stat_len = with_stats ? stats_check(h, reads, n_reads, last_dur, on_device) : 0;
   if (stat_len < 0) return NRV_E_INVALID;
@@ -2352,7 +2421,9 @@ static int raw_begin(nrv_handle* h, const RawIn& in, float* p1, float* p2, int8_
   sl.off_bases = sl.off_aux + (with_stats ? up((size_t)n_reads * sizeof(StatAux)) : 0);
   sl.off_noff = sl.off_bases + (mr ? up((size_t)N) : 0);
   sl.off_names = sl.off_noff + (records ? up(((size_t)n_reads + 1) * 8) : 0);
-  const size_t in_bytes = sl.off_names + (records ? up((size_t)mr->name_off[n_reads]) : 0);
+  sl.off_toff = sl.off_names + (records ? up((size_t)mr->name_off[n_reads]) : 0);
+  sl.off_truth = sl.off_toff + (accuracy ? up(((size_t)n_reads + 1) * 8) : 0);
+  const size_t in_bytes = sl.off_truth + (accuracy ? up((size_t)mr->truth_off[n_reads]) : 0);
   sl.rows = ((size_t)sl.n + kRowPad - 1) / kRowPad * kRowPad;
   const size_t out_bytes = 64 + sl.rows * kOutBytes;
   if (!sl.ev_in) {
@@ -2426,6 +2497,10 @@ static int raw_begin(nrv_handle* h, const RawIn& in, float* p1, float* p2, int8_
     memcpy(sl.pin_in + sl.off_noff, mr->name_off, ((size_t)n_reads + 1) * 8);
     if (mr->name_off[n_reads] > 0) memcpy(sl.pin_in + sl.off_names, mr->names, (size_t)mr->name_off[n_reads]);
   }
+  if (accuracy) {
+    memcpy(sl.pin_in + sl.off_toff, mr->truth_off, ((size_t)n_reads + 1) * 8);
+    if (mr->truth_off[n_reads] > 0) memcpy(sl.pin_in + sl.off_truth, mr->truth, (size_t)mr->truth_off[n_reads]);
+  }
   memcpy(sl.pin_in + sl.off_starts, starts, (size_t)N * 4);
   memcpy(sl.pin_in + sl.off_reads, reads, (size_t)n_reads * sizeof(SegRead));
   memcpy(sl.pin_in + sl.off_feat, feat_ev, (size_t)N * kFeat * 4);
@@ -2468,6 +2543,9 @@ static int revise_begin(nrv_handle* h, const char* who, const char* missing, con
   else if (!mo.rec_off && (mr.names || mr.name_off || mo.blob)) bad = "names / name_off / blob without rec_off";
   else if ((mr.prof_thr == nullptr) != (mo.profile == nullptr)) bad = "prof_thr and profile go together";
   else if (mo.trim && !trim_rule_ok(mr.Q, mr.W, mr.min_len)) bad = "Q must be in 1 .. 40, W in 1 .. 64 and min_len >= 0";
+  else if (mo.accuracy && (in.n_reads < 0 || !truth_ok(mr.truth, mr.truth_off, in.n_reads)))
+    bad = "null truth / truth_off, offsets that do not ascend from 0, or a truth of 2^31 - 64 characters and more";
+  else if (mo.accuracy && in.N >= ((int64_t)1 << 30)) bad = "2^30 events and more in a call with a truth";
   if (h && bad) { h->err = std::string(who) + ": " + bad; return NRV_E_INVALID; }
   return raw_begin(h, in, nullptr, nullptr, nullptr, nullptr, ticket, &mr, &mo);
 }
@@ -2634,6 +2712,39 @@ int nrv_revise_reads_raw_trim(nrv_handle* h, const int16_t* raw, int64_t n_raw, 
   });
 }
 
+// every earlier block may be NULL, the trim included: trim == NULL, no rule is checked and no trim enqueued
+int nrv_revise_reads_raw_accuracy_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                        const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                        const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                        uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                        nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                        uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                        const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                                        const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, int* ticket) {
+  const char* missing = nullptr;
+  if (!accuracy || !truth_off) missing = "null truth_off / accuracy";
+  else if (trim && !trim_thr) missing = "trim without trim_thr";
+  return revise_begin(h, "nrv_revise_reads_raw_accuracy_begin", missing,
+                      RawIn{raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device},
+                      MergeIn{bases, q_thr, names, name_off, prof_thr, trim_thr, Q, W, min_len, truth, truth_off},
+                      MergeOut{seq, qual, off, report, tie_eps, edits, edit_off, blob, rec_off, profile, trim, accuracy}, ticket);
+}
+
+int nrv_revise_reads_raw_accuracy(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                  const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                  const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                  uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                  nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                  uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                  const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                                  const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy) {
+  return begin_then_end(h, [&](int* t) {
+    return nrv_revise_reads_raw_accuracy_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                               seq, qual, off, tie_eps, report, edits, edit_off, names, name_off, blob, rec_off,
+                                               prof_thr, profile, trim_thr, Q, W, min_len, trim, truth, truth_off, accuracy, t);
+  });
+}
+
 int nrv_reads_raw_end(nrv_handle* h, int ticket) {
   int rc = check_handle(h);
   if (rc) return rc;
@@ -2761,7 +2872,7 @@ int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32
 
 // nrv_merge_calls (o.report == nullptr: that call, to the byte), nrv_merge_calls_report, (o.edit_off != nullptr)
 // nrv_merge_calls_edits, (o.profile != nullptr) nrv_merge_calls_profile and (o.trim != nullptr; `more`: its rule, and the names of
-// its records) nrv_merge_calls_trim
+// its records) nrv_merge_calls_trim and (o.accuracy != nullptr; `more`: the truth) nrv_merge_calls_accuracy
 static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
                             const float* p1, const float* p2, int64_t n_win, const float* q_thr, const MergeOut& o,
                             const float* prof_thr = nullptr, const MergeIn& more = MergeIn{}) {
@@ -2787,6 +2898,11 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
     blob_cap = blob_capacity(N, n, n_reads, more.name_off[n_reads], q_thr != nullptr);
     if ((blob_cap > 0 && !o.blob) || blob_cap >= ((size_t)1 << 32)) { h->err = "nrv_merge_calls_trim: null blob (or records of 4 GiB and more)"; return NRV_E_INVALID; }
   }
+  if (o.accuracy && !truth_ok(more.truth, more.truth_off, n_reads)) {
+    h->err = "nrv_merge_calls_accuracy: null truth / truth_off, offsets that do not ascend from 0, or a truth of 2^31 - 64 characters and more";
+    return NRV_E_INVALID;
+  }
+  if (o.accuracy && N >= ((int64_t)1 << 30)) { h->err = "nrv_merge_calls_accuracy: 2^30 events and more"; return NRV_E_INVALID; }
   if (n == 0) {
     MergeIn in = more;
     in.bases = bases; in.q_thr = q_thr;
@@ -2794,7 +2910,7 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
     return NRV_OK;
   }
   if (o.edit_off && !o.edits) { h->err = "nrv_merge_calls_edits: null edits"; return NRV_E_INVALID; }
-  // one block of its own: [reads | bases | a1 | a2 | p1 | p2 | name_off | names | merged block]
+  // one block of its own: [reads | bases | a1 | a2 | p1 | p2 | name_off | names | truth_off | truth | merged block]
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const MergeLayout m = merge_layout(N, n, n_reads, o, blob_cap);
   // the rows go up for a quality - and without one where they are given and the report's near-tie column, the edits' conf, the
@@ -2802,7 +2918,8 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
   const bool have_p = want_q || ((o.report || o.edit_off || o.profile || o.trim) && p1 && p2);
   const size_t o_b = up((size_t)n_reads * sizeof(SegRead)), o_a1 = o_b + up((size_t)N), o_a2 = o_a1 + up((size_t)n);
   const size_t o_p1 = o_a2 + up((size_t)n), o_p2 = o_p1 + (have_p ? up((size_t)n * 24) : 0), o_no = o_p2 + (have_p ? up((size_t)n * 20) : 0);
-  const size_t o_nm = o_no + (o.rec_off ? up(((size_t)n_reads + 1) * 8) : 0), o_m = o_nm + (o.rec_off ? up((size_t)more.name_off[n_reads]) : 0);
+  const size_t o_nm = o_no + (o.rec_off ? up(((size_t)n_reads + 1) * 8) : 0), o_to = o_nm + (o.rec_off ? up((size_t)more.name_off[n_reads]) : 0);
+  const size_t o_tr = o_to + (o.accuracy ? up(((size_t)n_reads + 1) * 8) : 0), o_m = o_tr + (o.accuracy ? up((size_t)more.truth_off[n_reads]) : 0);
   const size_t bytes = o_m + m.bytes;
   char* d = nullptr;
   HIPCHK(h, hipMalloc((void**)&d, bytes));
@@ -2822,9 +2939,14 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
       HIPCHK(h, hipMemcpyAsync(d + o_no, more.name_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
       if (more.name_off[n_reads] > 0) HIPCHK(h, hipMemcpyAsync(d + o_nm, more.names, (size_t)more.name_off[n_reads], hipMemcpyHostToDevice, h->stream));
     }
+    if (o.accuracy) {
+      HIPCHK(h, hipMemcpyAsync(d + o_to, more.truth_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
+      if (more.truth_off[n_reads] > 0) HIPCHK(h, hipMemcpyAsync(d + o_tr, more.truth, (size_t)more.truth_off[n_reads], hipMemcpyHostToDevice, h->stream));
+    }
     const MergeView v{(const SegRead*)d, n_reads, N, (const unsigned char*)(d + o_b), (const signed char*)(d + o_a1),
                       (const signed char*)(d + o_a2), have_p ? (const float*)(d + o_p1) : nullptr,
-                      have_p ? (const float*)(d + o_p2) : nullptr, (const long long*)(d + o_no), (const unsigned char*)(d + o_nm), d + o_m};
+                      have_p ? (const float*)(d + o_p2) : nullptr, (const long long*)(d + o_no), (const unsigned char*)(d + o_nm), d + o_m,
+                      (const unsigned char*)(d + o_tr), (const long long*)(d + o_to)};
     if ((rc2 = merged_enqueue(h, v, m, o, want_q ? q_thr : nullptr, prof_thr, blob_cap, TrimRule{more.trim_thr, more.Q, more.W, more.min_len})))
       return rc2;
     HIPCHK(h, hipMemcpyAsync(back.data(), d + o_m, m.dl, hipMemcpyDeviceToHost, h->stream));
@@ -2888,6 +3010,61 @@ int nrv_merge_calls_trim(nrv_handle* h, const uint8_t* bases, const int64_t* ev_
   more.names = names; more.name_off = name_off;
   more.trim_thr = trim_thr; more.Q = Q; more.W = W; more.min_len = min_len;
   return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, o, nullptr, more);
+}
+
+int nrv_merge_calls_accuracy(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                             const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                             const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy) {
+  if (h && (!truth_off || (n_reads > 0 && !accuracy))) { h->err = "nrv_merge_calls_accuracy: null truth_off / accuracy"; return NRV_E_INVALID; }
+  static uint64_t none[NRV_ACCURACY_COLS];
+  MergeOut o{seq, qual, off};
+  o.accuracy = accuracy ? accuracy : none;
+  MergeIn more;
+  more.truth = truth; more.truth_off = truth_off;
+  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, o, nullptr, more);
+}
+
+int nrv_edit_distance(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
+                      int64_t* dist) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (n_pairs < 0 || (n_pairs > 0 && !dist)) { h->err = "nrv_edit_distance: bad arguments"; return NRV_E_INVALID; }
+  if (!truth_ok(a, a_off, n_pairs) || !truth_ok(b, b_off, n_pairs)) {
+    h->err = "nrv_edit_distance: null sequences / offsets, offsets that do not ascend from 0, or a sequence of 2^31 - 64 characters and more";
+    return NRV_E_INVALID;
+  }
+  if (n_pairs == 0) return NRV_OK;
+  const int64_t ta = a_off[n_pairs], tb = b_off[n_pairs];
+  // one block of its own: [a_off | b_off | a | b | hc | dist]
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t nb = ((size_t)n_pairs + 1) * 8;
+  const size_t o_bo = up(nb), o_a = o_bo + up(nb), o_b = o_a + up((size_t)ta), o_hc = o_b + up((size_t)tb), o_d = o_hc + up((size_t)tb);
+  const size_t bytes = o_d + up((size_t)n_pairs * 8);
+  char* d = nullptr;
+  HIPCHK(h, hipMalloc((void**)&d, bytes));
+  auto run = [&]() -> int {
+    int rc2 = poison_fill(h, d, bytes, h->stream);
+    if (rc2) return rc2;
+    HIPCHK(h, hipMemcpyAsync(d, a_off, nb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d + o_bo, b_off, nb, hipMemcpyHostToDevice, h->stream));
+    if (ta > 0) HIPCHK(h, hipMemcpyAsync(d + o_a, a, (size_t)ta, hipMemcpyHostToDevice, h->stream));
+    if (tb > 0) HIPCHK(h, hipMemcpyAsync(d + o_b, b, (size_t)tb, hipMemcpyHostToDevice, h->stream));
+    AlignArgs k;
+    k.n_reads = n_pairs; k.kinds = 1;
+    k.truth = (const unsigned char*)(d + o_a); k.truth_off = (const long long*)d;
+    k.reads = nullptr; k.bases = nullptr; k.cap0 = 0; k.hc0 = nullptr;
+    k.off = (const long long*)(d + o_bo); k.seq = (const unsigned char*)(d + o_b); k.cap1 = tb;
+    k.hc1 = (unsigned char*)(d + o_hc);
+    k.accu = nullptr; k.dist = (long long*)(d + o_d);
+    if ((rc2 = align_enqueue(h, k))) return rc2;
+    HIPCHK(h, hipMemcpyAsync(dist, d + o_d, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return NRV_OK;
+  };
+  rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  (void)hipFree(d);
+  return rc;
 }
 
 int nrv_trim_reads(nrv_handle* h, const uint8_t* qual, const int64_t* off, int n_reads, int Q, int W, int64_t* trim) {

@@ -71,3 +71,4 @@
 #include "nrv_pack.h"          // pack_offsets / pack_copy_kernel (FASTA / FASTQ records of the merged reads, opt-in)
 #include "nrv_profile.h"       // profile_kernel (per-read quality histogram and base counts behind the merge, opt-in)
 #include "nrv_trim.h"          // trim_qual / trim_window / trim_finish_kernel (sliding-window quality trim behind the merge, opt-in)
+#include "nrv_align.h"         // align_kernel (edit distance of the original and the revised reads to a truth set, one wave per pair, opt-in)

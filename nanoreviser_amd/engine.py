@@ -40,9 +40,11 @@ SYMBOLS = [
     "nrv_revise_reads_raw_records_begin", "nrv_revise_reads_raw_records", "nrv_pack_records",
     "nrv_revise_reads_raw_profile_begin", "nrv_revise_reads_raw_profile", "nrv_merge_calls_profile",
     "nrv_revise_reads_raw_trim_begin", "nrv_revise_reads_raw_trim", "nrv_merge_calls_trim", "nrv_trim_reads", "nrv_pack_records_trim",
+    "nrv_revise_reads_raw_accuracy_begin", "nrv_revise_reads_raw_accuracy", "nrv_merge_calls_accuracy", "nrv_edit_distance",
 ]
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 PROFILE_COLS = 48                   # NRV_PROFILE_COLS
+ACCURACY_COLS = 4                   # NRV_ACCURACY_COLS
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "f16x2": 2}
 
@@ -90,8 +92,9 @@ _EDITS = ([C.c_void_p, _I64P], lambda p: (None if p[14] is None else p[14].ctype
 _RECORDS = ([_U8P, _I64P, _U8P, _I64P], lambda p: p[16:20])                              # names, name_off, blob, rec_off
 _PROFILE = ([_FP, _U64P], lambda p: p[20:22])                                            # prof_thr, profile
 _TRIM = ([_FP, C.c_int, C.c_int, C.c_int64, _I64P], lambda p: p[22:27])                   # trim_thr, Q, W, min_len, trim
+_TRUTH = ([_U8P, _I64P, _U64P], lambda p: p[27:30])                                      # truth, truth_off, accuracy
 # len(packed) -> (synchronous symbol, begin symbol, blocks, whether the call returns merged reads: (seq, qual, off[, report]
-# [, edits, edit_off][, blob, rec_off][, profile][, trim]))
+# [, edits, edit_off][, blob, rec_off][, profile][, trim][, accuracy]))
 _RAW_FORMS = {
     7: ("nrv_predict_reads_raw", "nrv_reads_raw_begin", (_CALLS,), False),
     9: ("nrv_predict_reads_raw_stats", "nrv_reads_raw_stats_begin", (_STATS, _CALLS), False),
@@ -102,11 +105,17 @@ _RAW_FORMS = {
     22: ("nrv_revise_reads_raw_profile", "nrv_revise_reads_raw_profile_begin", (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS, _PROFILE), True),
     27: ("nrv_revise_reads_raw_trim", "nrv_revise_reads_raw_trim_begin", (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS, _PROFILE, _TRIM), True),
 }
+# ... and the forms that carry a truth set, in a table of their own (`_raw_call` consults it after the first)
+_RAW_FORMS_TRUTH = {
+    30: ("nrv_revise_reads_raw_accuracy", "nrv_revise_reads_raw_accuracy_begin",
+         (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS, _PROFILE, _TRIM, _TRUTH), True),
+}
 _PACK_RECORDS_T = [C.c_void_p, _U8P, _U8P, _I64P, C.c_int, _U8P, _I64P, _U8P, _I64P]         # nrv_pack_records
 _READS_HEAD_T = _RAW_HEAD_T[:4] + [C.c_int64, C.POINTER(_ReadDesc), C.c_int]     # nrv_segment_reads, nrv_read_stats: no features
 _MERGE_CALLS_T = [C.c_void_p, _U8P, _I64P, C.c_int, _I8P, _I8P, _FP, _FP, C.c_int64] + _MERGE[0][1:]   # nrv_merge_calls
 _TRIM_READS_T = [C.c_void_p, _U8P, _I64P, C.c_int, C.c_int, C.c_int, _I64P]                  # nrv_trim_reads
 _PACK_RECORDS_TRIM_T = _PACK_RECORDS_T[:7] + [_I64P, C.c_int64] + _PACK_RECORDS_T[7:]        # nrv_pack_records_trim
+_EDIT_DISTANCE_T = [C.c_void_p, _U8P, _I64P, _U8P, _I64P, C.c_int, _I64P]                    # nrv_edit_distance
 
 
 _lib = None
@@ -191,8 +200,9 @@ def load_library(path: Optional[str] = None):
     have_records = hasattr(lib, "nrv_pack_records")
     have_profile = hasattr(lib, "nrv_merge_calls_profile")
     have_trim = hasattr(lib, "nrv_merge_calls_trim")
-    for sync, begin, blocks, _ in _RAW_FORMS.values():  # (every restype is ctypes' default, int: the nrv_* status)
-        if (have_trim or _TRIM not in blocks) and (have_profile or _PROFILE not in blocks) and (have_records or _RECORDS not in blocks) \
+    have_truth = hasattr(lib, "nrv_merge_calls_accuracy")
+    for sync, begin, blocks, _ in list(_RAW_FORMS.values()) + list(_RAW_FORMS_TRUTH.values()):  # (every restype is ctypes' default, int: the nrv_* status)
+        if (have_truth or _TRUTH not in blocks) and (have_trim or _TRIM not in blocks) and (have_profile or _PROFILE not in blocks) and (have_records or _RECORDS not in blocks) \
                 and (have_edits or _EDITS not in blocks) and (have_report or _REPORT not in blocks):
             getattr(lib, sync).argtypes = _RAW_HEAD_T + [t for types, _ in blocks for t in types]
             getattr(lib, begin).argtypes = getattr(lib, sync).argtypes + [C.POINTER(C.c_int)]
@@ -209,6 +219,9 @@ def load_library(path: Optional[str] = None):
         lib.nrv_merge_calls_trim.argtypes = _MERGE_CALLS_T + _TRIM[0] + _RECORDS[0]
         lib.nrv_trim_reads.argtypes = _TRIM_READS_T
         lib.nrv_pack_records_trim.argtypes = _PACK_RECORDS_TRIM_T
+    if have_truth:
+        lib.nrv_merge_calls_accuracy.argtypes = _MERGE_CALLS_T + _TRUTH[0]
+        lib.nrv_edit_distance.argtypes = _EDIT_DISTANCE_T
     lib.nrv_reads_raw_end.argtypes = [vp, C.c_int]
     lib.nrv_segment_reads.argtypes = _READS_HEAD_T + [fp]
     lib.nrv_read_stats.argtypes = _READS_HEAD_T + [_I32P, _DP, _DP, _DP, _DP, fp]
@@ -547,11 +560,52 @@ class Reviser:
         return packed + (thr, Q, W, min_len, np.zeros((packed[4], 2), np.int64))
 
     @staticmethod
+    def _truth_block(truth, truth_off, n_reads):
+        """A truth set, checked: (truth uint8 - one byte where there is none, so that its pointer is not NULL -, truth_off
+        int64[n_reads + 1])."""
+        toff = np.ascontiguousarray(truth_off, dtype=np.int64).reshape(-1)
+        if toff.size != n_reads + 1 or toff[0] != 0 or np.any(np.diff(toff) < 0):
+            raise ValueError("truth_off must have n_reads + 1 entries that ascend from 0")
+        if isinstance(truth, (bytes, bytearray)):
+            truth = np.frombuffer(bytes(truth), np.uint8)
+        t = np.ascontiguousarray(truth, dtype=np.uint8).reshape(-1)
+        if t.size < int(toff[-1]):
+            raise ValueError("truth is shorter than truth_off[-1]")
+        return (t if t.size else np.zeros(1, np.uint8)), toff
+
+    @classmethod
+    def with_device_accuracy(cls, packed, truth, truth_off):
+        """A `with_device_merge` (12 elements), `with_device_report` (14), `with_device_edits` (16), `with_device_records` (20),
+        `with_device_profile` (22) or `with_device_trim` (27) tuple whose call also finds, per read, the edit distance of the
+        original and of the revised read to the true sequence truth[truth_off[r]:truth_off[r + 1]] (include/nanorev.h
+        nrv_revise_reads_raw_accuracy_begin; hoststage.read_accuracy is the definition; an empty truth: the read has none).
+        The result has 30 elements: blocks the tuple does not carry are padded with their "not asked for" values, a NULL trim
+        included, and elements 27 - 29 are truth uint8, truth_off int64[n_reads + 1] and accuracy uint64[n_reads][4].
+        `run_packed_raw` / `begin_packed_raw` + `end_packed_raw` then return what a `with_device_trim` call returns - None
+        for the blocks not carried - and the accuracy block LAST."""
+        if len(packed) not in (12, 14, 16, 20, 22, 27):
+            raise ValueError("with_device_accuracy extends a with_device_merge, a with_device_report, a with_device_edits, a "
+                             "with_device_records, a with_device_profile or a with_device_trim tuple")
+        packed = tuple(packed)
+        if len(packed) == 12:
+            packed += (0.0, None)
+        if len(packed) == 14:
+            packed += (None, None)
+        if len(packed) == 16:
+            packed += (None, None, None, None)
+        if len(packed) == 20:
+            packed += (None, None)
+        if len(packed) == 22:
+            packed += (None, 0, 0, 0, None)
+        t, toff = cls._truth_block(truth, truth_off, packed[4])
+        return packed + (t, toff, np.zeros((packed[4], ACCURACY_COLS), np.uint64))
+
+    @staticmethod
     def _trim_merged(out):
         seq, qual, off = out[:3]
         total = int(off[-1])
         more, tail = tuple(out[3:]), ()
-        if len(more) in (6, 7):                       # (..., profile[, trim]): a `with_device_profile` / `with_device_trim` call; blocks it does not carry are None
+        if len(more) in (6, 7, 8):                    # (..., profile[, trim[, accuracy]]): a `with_device_profile` / `with_device_trim` / `with_device_accuracy` call; blocks it does not carry are None
             more, tail = more[:5], more[5:]
         if len(more) in (3, 5) and more[1] is not None:   # (report | None, edits, edit_off, ...): the used prefix of the records
             more = (more[0], more[1][:int(more[2][-1])], more[2]) + more[3:]
@@ -567,22 +621,23 @@ class Reviser:
     def _raw_call(self, packed, begin: bool):
         """One call of the raw-read family for a packed tuple of any form (`_RAW_FORMS`): its synchronous entry point, or its
         *_begin with the ticket behind the same arguments.  Returns (ticket number or None, outputs, merged)."""
-        if len(packed) not in _RAW_FORMS:
-            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14, 16, 20, 22 or 27 elements, not {len(packed)}")
-        sync, beg, blocks, merged = _RAW_FORMS[len(packed)]
-        if not hasattr(self._lib, beg):               # the report, edits, records, profile and trim pairs are found by presence
+        form = _RAW_FORMS.get(len(packed)) or _RAW_FORMS_TRUTH.get(len(packed))
+        if form is None:
+            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14, 16, 20, 22, 27 or 30 elements, not {len(packed)}")
+        sync, beg, blocks, merged = form
+        if not hasattr(self._lib, beg):               # the report, edits, records, profile, trim and accuracy pairs are found by presence
             raise NrvError(-1, f"this build of libnanorev_hip.so has no {beg}")
         args = self._raw_head(packed)
         for types, pick in blocks:
             args += _marshal(pick(packed), types)
         t = C.c_int(-1)
         self._check(getattr(self._lib, beg)(*args, C.byref(t)) if begin else getattr(self._lib, sync)(*args))
-        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) + tuple(packed[18:20]) + tuple(packed[21:22]) + tuple(packed[26:27]) if merged else packed[6]), merged
+        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) + tuple(packed[18:20]) + tuple(packed[21:22]) + tuple(packed[26:27]) + tuple(packed[29:30]) if merged else packed[6]), merged
 
     def run_packed_raw(self, packed):
         """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared (or `with_device_stats` /
         `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` /
-        `with_device_trim` extended)."""
+        `with_device_trim` / `with_device_accuracy` extended)."""
         _, out, merged = self._raw_call(packed, False)
         return self._trim_merged(out) if merged else out
 
@@ -597,7 +652,8 @@ class Reviser:
         call, its (seq, qual, off), with the report behind them for a `with_device_report` call, (report | None, edits,
         edit_off) for a `with_device_edits` call and (report | None, edits | None, edit_off | None, blob, rec_off) - the blob
         trimmed to rec_off[-1] - for a `with_device_records` call; a `with_device_profile` call returns the latter with the
-        profile behind it, a `with_device_trim` call with (profile | None, trim) behind it."""
+        profile behind it, a `with_device_trim` call with (profile | None, trim) behind it, a `with_device_accuracy` call with
+        (profile | None, trim | None, accuracy) behind it."""
         t, out = ticket[:2]
         self._check(self._lib.nrv_reads_raw_end(self._h, t))
         return self._trim_merged(out) if len(ticket) == 3 else out
@@ -718,6 +774,43 @@ class Reviser:
             raise ValueError("p1 / p2 / q_thr / prof_thr do not match")
         prof = np.zeros((ins[1].size, PROFILE_COLS), np.uint64)
         return self._merge_call("nrv_merge_calls_profile", *ins, *_marshal((pthr, prof), _PROFILE[0])) + (prof,)
+
+    def merge_calls_accuracy_device(self, bases, ev_len, a1, a2, truth, truth_off, p1=None, p2=None, q_thr=None):
+        """`merge_calls_device` with the accuracy block (nrv_merge_calls_accuracy): truth uint8 and truth_off int64[n_reads + 1]
+        as `with_device_accuracy` takes them.  Returns (seq, qual | None, off, accuracy uint64[n_reads][4]) - the block is
+        hoststage.read_accuracy's, bit for bit."""
+        if not hasattr(self._lib, "nrv_merge_calls_accuracy"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_merge_calls_accuracy")
+        ins = self._merge_inputs(bases, ev_len, a1, a2, p1, p2, q_thr, q_thr is not None)
+        n, (q1, q2, thr) = ins[2].size, ins[4:]
+        if thr is not None and (thr.size != 39 or q1.shape[0] != n or q2.shape[0] != n):
+            raise ValueError("q_thr / p1 / p2 do not match")
+        nr = ins[1].size
+        t, toff = self._truth_block(truth, truth_off, nr)
+        acc = np.zeros((nr, ACCURACY_COLS), np.uint64)
+        return self._merge_call("nrv_merge_calls_accuracy", *ins, *_marshal((t, toff, acc), _TRUTH[0])) + (acc,)
+
+    def edit_distance_device(self, truths, reads):
+        """align_kernel alone (nrv_edit_distance): truths and reads are equally long lists of byte strings (or uint8 arrays);
+        returns int64[n_pairs], hoststage.edit_distance(truths[k], reads[k]) - and -1 where truths[k] is empty."""
+        if not hasattr(self._lib, "nrv_edit_distance"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_edit_distance")
+        if len(truths) != len(reads):
+            raise ValueError("one read per truth")
+        a, a_off = self._names_block(truths)
+        b, b_off = self._names_block(reads)
+        return self.edit_distance_offsets(a, a_off, b, b_off)
+
+    def edit_distance_offsets(self, a, a_off, b, b_off):
+        """`edit_distance_device` on the arrays as nrv_edit_distance takes them; the offsets are passed on unchecked."""
+        a_off = np.ascontiguousarray(a_off, dtype=np.int64).reshape(-1)
+        b_off = np.ascontiguousarray(b_off, dtype=np.int64).reshape(-1)
+        a, b = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1), np.ascontiguousarray(b, dtype=np.uint8).reshape(-1)
+        n = a_off.size - 1
+        dist = np.zeros(max(n, 1), np.int64)
+        self._check(self._lib.nrv_edit_distance(*_marshal((self._h, a if a.size else np.zeros(1, np.uint8), a_off,
+                                                           b if b.size else np.zeros(1, np.uint8), b_off, n, dist), _EDIT_DISTANCE_T)))
+        return dist[:n]
 
     def merge_calls_trim(self, bases, ev_len, a1, a2, p1, p2, Q, W=10, q_thr=None, trim_thr=None, names=None, min_len=1):
         """`merge_calls_device` with the sliding-window trim (nrv_merge_calls_trim): p1 / p2 are required, q_thr may be None (a
