@@ -449,6 +449,56 @@ int nrv_merge_calls_accuracy(nrv_handle* h, const uint8_t* bases, const int64_t*
 int nrv_edit_distance(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
                       int64_t* dist);
 
+/* ERROR CLASSES AGAINST THE TRUTH SET (opt-in; nothing above changes): per read how many substitutions, insertions and
+ * deletions separate the original and the revised read from the true sequence, found on the device by ONE launch behind
+ * the accuracy's.  The rule, integers only, no traceback and no tie-break rule: for a truth t (m bytes) and a read s (n bytes),
+ * bytes matching as above (equal, and one of A C G T; any other byte matches nothing, itself included), take among all global
+ * alignments with the minimum number of edits d those with the largest number of matched columns, M.  (d, M) is unique and
+ * follows from a forward recurrence over pairs compared lexicographically on (d, -M):
+ *   W[0][j] = (j, 0) and W[i][0] = (i, 0);
+ *   W[i][j] = min(W[i-1][j] + (1, 0), W[i][j-1] + (1, 0), W[i-1][j-1] + ((0, -1) on a match, (1, 0) otherwise));
+ *   (d, -M) = W[m][n].  d is the d of the accuracy block.  n = 0 gives (m, 0).  m = 0 means "this read has no truth": its row
+ *   is all zeros.
+ * From the four integers: substitutions S = m + n - 2M - d, insertions (read characters absent from the truth) I = d - (m - M),
+ * deletions (truth characters absent from the read) D = d - (n - M); M + S + I = n, M + S + D = m, S + I + D = d.
+ * hoststage.edit_classes is the definition.  The arguments of nrv_revise_reads_raw_accuracy_begin - every block of it may be
+ * NULL as there, and here `accuracy` too - then, required,
+ *   errclass   uint64 [n_reads][NRV_ERRCLASS_COLS]:
+ *     0  truth_len
+ *     1  dist_in    2  match_in   = (d, M) of the truth and the original bases of the read
+ *     3  dist_out   4  match_out  = (d, M) of the truth and seq[off[r] .. off[r + 1]): the UNTRIMMED revision
+ *     5  reserved, 0
+ * One wave per (read, original | revised) pair; every word is a function of its pair alone, stored plainly: the bytes do not
+ * depend on the order of the workgroups and the range-guard re-run accumulates nothing.  N <= T: nothing is enqueued, the block
+ * is filled on the host with out = in.  Tickets, the two-calls-in-flight rule and the failure paths are those of
+ * nrv_revise_reads_raw_begin; `errclass` is filled by nrv_reads_raw_end.  nrv_revise_reads_raw_errclass IS _errclass_begin + _end. */
+#define NRV_ERRCLASS_COLS 6
+int nrv_revise_reads_raw_errclass_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                        const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                        const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                        uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                        nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                        uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                        const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                                        const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, uint64_t* errclass, int* ticket);
+int nrv_revise_reads_raw_errclass(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                  const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                  const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                  uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                  nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                  uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                  const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                                  const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, uint64_t* errclass);
+/* nrv_merge_calls with the error-class block, by the kernel nrv_revise_reads_raw_errclass_begin runs, on calls the host
+ * supplies.  The twin used by the parity tests. */
+int nrv_merge_calls_errclass(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                             const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                             const uint8_t* truth, const int64_t* truth_off, uint64_t* errclass);
+/* The same kernel on pairs the host supplies, as nrv_edit_distance takes them and refuses them; dist and match int64 [n_pairs],
+ * -1 / -1 for an empty truth.  The unit door of the kernel. */
+int nrv_edit_classes(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
+                     int64_t* dist, int64_t* match);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

@@ -181,7 +181,18 @@ def get_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("--accuracy_max_len", dest="accuracy_max_len", type=int, default=65536, metavar="L",
                    help="with --accuracy: a read whose truth or original length exceeds L is treated as having no truth and "
                         "counted as too_long (default 65536)")
+    p.add_argument("--error_classes", dest="error_classes", default=None, metavar="FILE",
+                   help="with --truth and --accuracy: write to FILE (also NRV_ERROR_CLASSES=FILE) which errors separate every read "
+                        "from its truth before and after the revision, a TSV with one header line, one line per input read sorted "
+                        "by file name - name, status, truth_len, then for the original and for the revised (untrimmed) read its "
+                        "length and the matched, substituted, inserted (absent from the truth) and deleted (absent from the read) "
+                        "characters of the alignments with the fewest edits that match the most characters - then a line #total "
+                        "with the sums over the reads with a truth and the pooled substitution / insertion / deletion rates per "
+                        "truth base before and after, and a line #reads as in --accuracy.  It shares --accuracy_max_len.  With "
+                        "--device_merge the counts are found on the GPU behind the merge, everywhere else by the host stage at "
+                        "about 0.3 s per read: the same file byte for byte.  Off by default; without it nothing changes")
     a = p.parse_args(argv)
+    a.error_classes = a.error_classes or (os.environ.get("NRV_ERROR_CLASSES", "").strip() or None)
     a.truth = a.truth or (os.environ.get("NRV_TRUTH", "").strip() or None)
     a.accuracy = a.accuracy or (os.environ.get("NRV_ACCURACY", "").strip() or None)
     if (a.truth is None) != (a.accuracy is None):
@@ -189,6 +200,9 @@ def get_args(argv: Optional[Sequence[str]] = None):
         raise SystemExit(2)
     if a.accuracy and a.resume:
         print("[！！！Error] --resume cannot be used with --accuracy: a skipped read's written form is not at hand", file=sys.stderr)
+        raise SystemExit(2)
+    if a.error_classes and not (a.truth and a.accuracy):
+        print("[！！！Error] --error_classes goes with --truth and --accuracy", file=sys.stderr)
         raise SystemExit(2)
     if a.accuracy and a.accuracy_max_len < 0:
         print("[！！！Error] --accuracy_max_len must be 0 or more", file=sys.stderr)
@@ -1018,6 +1032,34 @@ def accuracy_fields(v) -> List[str]:
     return [str(m), str(len_in), str(d_in), str(len_out), str(d_out), identity_field(d_in, max(len_in, m)), identity_field(d_out, max(len_out, m))]
 
 
+ERRCLASS_HEADER = "name\tstatus\ttruth_len\tlen_in\tmatch_in\tsub_in\tins_in\tdel_in\tlen_out\tmatch_out\tsub_out\tins_out\tdel_out"
+ERRCLASS_PART_COLS = 8                     # a part line's integers: truth_len, len_in, dist_in, match_in, len_out, dist_out, match_out, flag
+
+
+def error_class_rows(T, bases, ev_len, a1, a2, truth, truth_off):
+    """--error_classes on the host: `hoststage.read_error_classes` on calls the host holds, as `accuracy_rows`.
+    (uint64[len(ev_len)][6], the lengths of the revised reads)."""
+    b = hostlib.bases_u8(bases)
+    seq, _, off = hs.emit_calls(b, ev_len, a1, a2, None, T)
+    return hs.read_error_classes(b, ev_len, seq, off, truth, truth_off), np.diff(off)
+
+
+def error_class_fields(v, rates: bool = False) -> List[str]:
+    """The fields of an --error_classes line behind name and status from a part line's integers - or, rates=True, of #total from
+    their sums: THE place where the four integers m, n, d, M of a pair become its counts, substitutions S = m + n - 2M - d,
+    insertions I = d - (m - M), deletions D = d - (n - M) (all linear: the counts of the sums are the sums of the counts), and
+    where a rate count / truth_len gets its six decimals, on every route."""
+    m, len_in, d_in, M_in, len_out, d_out, M_out, flag = (int(x) for x in v[:ERRCLASS_PART_COLS])
+    if flag != ACC_WITH_TRUTH:
+        return ["0"] + ["."] * 10
+    out, tail = [str(m)], []
+    for n, d, M in ((len_in, d_in, M_in), (len_out, d_out, M_out)):
+        counts = (m + n - 2 * M - d, d - (m - M), d - (n - M))
+        out += [str(n), str(M)] + [str(c) for c in counts]
+        tail += [f"{(c / m if m > 0 else 0.0):.6f}" for c in counts]
+    return out + (tail if rates else [])
+
+
 def unrevised_profile(seq) -> np.ndarray:
     """The profile row of a read written unrevised: the base counts of the sequence that was written (str or bytes), no histogram."""
     row = np.zeros(hs.PROFILE_COLS, np.uint64)
@@ -1174,6 +1216,7 @@ class AccuracyPart(ReportPart):
     def __init__(self, path: Optional[str], truths: Optional[dict], max_len: int = 65536, log: Callable[[str], None] = print):
         super().__init__(path, ACCURACY_PART_COLS)
         self.truths, self.max_len, self.log, self.warned = truths or {}, int(max_len), log, False
+        self.classes = None                           # the parent's --error_classes part rides along (`write_originals`, `finish_split_reads`)
 
     def block(self, fns, lens_in):
         """The truth set of a device call: (truth uint8[], truth_off int64[R + 1], flags).  A read without a record, or whose
@@ -1234,6 +1277,60 @@ def merge_accuracy(path: str, names: Sequence[str], log: Callable[[str], None] =
     _replace_report(path, out, parts)
 
 
+class ErrclassPart(AccuracyPart):
+    """One process' share of the --error_classes file: an `AccuracyPart` - the same truth set, the same --accuracy_max_len, the
+    same flags - whose lines carry (d, M) of both forms of a read."""
+
+    def __init__(self, path: Optional[str], truths: Optional[dict], max_len: int = 65536, log: Callable[[str], None] = print):
+        ReportPart.__init__(self, path, ERRCLASS_PART_COLS)
+        self.truths, self.max_len, self.log, self.warned, self.classes = truths or {}, int(max_len), log, False, None
+
+    @staticmethod
+    def rows(ec, lens_in, lens_out, flags):
+        """A part line's integers per read from an error-class block (hoststage.read_error_classes' or the device's)."""
+        return [[int(e[0]), int(n), int(e[1]), int(e[2]), int(k), int(e[3]), int(e[4]), f] if f == ACC_WITH_TRUTH else [0, int(n), 0, 0, int(k), 0, 0, f]
+                for e, n, k, f in zip(np.asarray(ec).tolist(), lens_in, lens_out, flags)]
+
+    def host_rows(self, T, fns, bases, ev_len, a1, a2):
+        if not self.warned:
+            self.warned = True
+            self.log("[！！！Warning] --error_classes: the error classes are computed by the host stage, about 0.3 s per read "
+                     "(--device_merge computes them on the GPU)")
+        truth, toff, flags = self.block(fns, ev_len)
+        ec, lens_out = error_class_rows(T, bases, ev_len, a1, a2, truth, toff)
+        return self.rows(ec, ev_len, lens_out, flags)
+
+    def add_unrevised(self, fn: str, text):
+        """A read written unrevised (text: what was written, str or bytes): out = in, the classes of what was written."""
+        if self.path is None:
+            return
+        text = text.encode("ascii", "replace") if isinstance(text, str) else bytes(text)
+        truth, toff, (flag,) = self.block([fn], [len(text)])
+        d, M = hs.edit_classes(truth, text) if flag == ACC_WITH_TRUTH else (0, 0)
+        self.add(fn, False, [int(toff[1]), len(text), d, M, len(text), d, M, flag])
+
+
+def merge_error_classes(path: str, names: Sequence[str], log: Callable[[str], None] = print):
+    """Parent side of --error_classes: the parts as `merge_report` reads them, one line per read of `names` sorted by file name,
+    then #total - the sums over the reads WITH a truth, revised or not, and the pooled rates count / sum(truth_len) - and #reads
+    with_truth / no_truth / too_long; the file appears by rename and the parts are removed."""
+    rows, parts = _part_rows(path, ERRCLASS_PART_COLS)
+    out, total, counts = [ERRCLASS_HEADER], [0] * (ERRCLASS_PART_COLS - 1), [0, 0, 0]
+    for fn in sorted(names):
+        c = rows.get(fn)
+        if c is None:
+            log(f"[！！！Warning] --error_classes: no record for {fn}")
+            c = [fn, "unrevised"] + ["0"] * (ERRCLASS_PART_COLS - 1) + [str(ACC_NO_TRUTH)]
+        v = [int(x) for x in c[2:]]
+        out.append("\t".join(c[:2] + error_class_fields(v)))
+        counts[v[-1]] += 1
+        if v[-1] == ACC_WITH_TRUTH:
+            total = [t + x for t, x in zip(total, v[:-1])]
+    out.append("\t".join(["#total", "with_truth"] + error_class_fields(total + [ACC_WITH_TRUTH], rates=True)))
+    out.append("#reads\t" + "\t".join(str(x) for x in counts))
+    _replace_report(path, out, parts)
+
+
 EDITS_HEADER = "#pos_in\tpos_out\tkind\tref\talt\tqual\tconf"
 
 
@@ -1268,9 +1365,9 @@ def write_edits(edits_dir: str, fast5_fn: str, edits=None, want_qual: bool = Fal
 
 def _host_merge_form(packed):
     """A `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` /
-    `with_device_trim` / `with_device_accuracy` tuple back in the form whose call returns (p1, p2, a1, a2): for the paths that
+    `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` tuple back in the form whose call returns (p1, p2, a1, a2): for the paths that
     keep the host merge."""
-    if packed is None or len(packed) not in (12, 14, 16, 20, 22, 27, 30):
+    if packed is None or len(packed) not in (12, 14, 16, 20, 22, 27, 30, 31):
         return packed
     return tuple(packed[:7]) if packed[7] is None else tuple(packed[:9])
 
@@ -1286,12 +1383,12 @@ def _bundle_has_bases(bundle) -> bool:
 
 
 def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, report, edits=False, combined=False, summary=False,
-                 trim=False, accuracy=False):
+                 trim=False, accuracy=False, error_classes=False):
     """The one decision about a batch: (packed form `_FileRun.submit` builds, route `_FileRun.run_batch` takes).  Pure: it looks at what
     the engine object offers, at the bundle (None: reads that arrived one by one) and at the run's switches - pipelined (one
     engine, NRV_CLI_PIPELINE != 0), native_pool (libnanorev_host.so driven from the thread pool), device_merge (--device_merge
     and what it needs: pipelined, native_pool, nrvh_write_records), report (--report), edits (--edits), combined (--combined),
-    summary (--summary), trim (--trim_q), accuracy (--truth / --accuracy).  "bases":
+    summary (--summary), trim (--trim_q), accuracy (--truth / --accuracy), error_classes (--error_classes).  "bases":
     `_bundle_has_bases`.  A form is
     the length of the packed tuple (engine.Reviser), None, or "host-merge": the merge form built and taken back.
 
@@ -1314,6 +1411,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
       yes     + trim on, such a form, no with_device_trim                    host-merge [2]  by the last three rows
       yes     + accuracy on, a form 12 ... 27 above, with_device_accuracy    30 [9]          by the last three rows
       yes     + accuracy on, such a form, no with_device_accuracy            host-merge [2]  by the last three rows
+      yes     + error_classes on, form 30 above, with_device_error_classes   31 [10]         by the last three rows
+      yes     + error_classes on, form 30 above, no with_device_error_classes  host-merge [2]  by the last three rows
       yes     any form; pipelined, native_pool, begin_packed_raw, bases                      pipelined [3]
       yes     any form; native_pool, bases, not (pipelined, begin_packed_raw)                packed+finish_bundle
       yes     any form; no native_pool, or no bases                                          packed sliced
@@ -1333,7 +1432,11 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
         applies them on every route.
     [9] the one call carries whatever the form above carried and the accuracy block last: per read the edit distance of the
         original and of the (untrimmed) revised read to its truth.  Every other route computes the rows on the host from the
-        reads it holds (`accuracy_rows`)."""
+        reads it holds (`accuracy_rows`).
+    [10] the one call is the form 30 call with the error-class block behind the accuracy block: per read the edits and the matched
+        columns of the original and of the (untrimmed) revised read against its truth.  Every other route computes the rows on
+        the host (`error_class_rows`) - an engine without the call too: a form 30 call need not hand the merged characters back,
+        so the route is the one the accuracy takes without ITS call."""
     unpacked = "per-read" if n_reads == 1 else "predict_many"
     if bundle is None:
         return (7 if n_reads > 1 and hasattr(rv, "pack_reads_raw") else None), unpacked
@@ -1353,6 +1456,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
             form = 27 if hasattr(rv, "with_device_trim") else "host-merge"
         if accuracy and form != "host-merge":
             form = 30 if hasattr(rv, "with_device_accuracy") else "host-merge"
+        if error_classes and form == 30:
+            form = 31 if hasattr(rv, "with_device_error_classes") else "host-merge"
     if not (native_pool and bases):
         return form, "packed sliced"
     return form, ("pipelined" if pipelined and hasattr(rv, "begin_packed_raw") else "packed+finish_bundle")
@@ -1461,7 +1566,7 @@ class _FileRun:
     `_route_batch` says (`submit`) and collects the pooled finishers; the ENGINE thread(s) make the calls (`run_batch`, `collect`);
     the one FINISHER thread merges, reports and writes, or hands that to the parser pool (`finish_batch`, `finish_call`)."""
     def __init__(self, stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part=None,
-                 summary_part=None, trim_part=None, accuracy_part=None):
+                 summary_part=None, trim_part=None, accuracy_part=None, errclass_part=None):
         self.args, self.log, self.note = args, log, on_file or (lambda fn, ok: None)
         self.stats = {"reads": 0, "bases": 0, "failed": [], "host_s": 0.0, "engine_s": 0.0}
         self.stats_lock = threading.Lock()
@@ -1476,6 +1581,9 @@ class _FileRun:
         self.accpart = AccuracyPart(accuracy_part, load_truth(args.truth) if accuracy_part else None,
                                     getattr(args, "accuracy_max_len", 65536), log)
         self.acc_rows = {}
+        # --error_classes: its own part next to the accuracy's, on the truth set that one loaded
+        self.eclpart = ErrclassPart(errclass_part if accuracy_part else None, self.accpart.truths, self.accpart.max_len, log)
+        self.ecl_rows = {}
         self.acc_flags = {}                           # id(batch) -> the flags of a form 30 call's truth block, until its call is back
         self.tie_eps = float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS))
         self.edits_dir = getattr(args, "edits", None) # --edits: every read's list is written BEFORE its output is
@@ -1587,6 +1695,7 @@ class _FileRun:
         self.sumpart.close()
         self.trimpart.close()
         self.accpart.close()
+        self.eclpart.close()
         if self.sink is not None:
             self.sink.close()
         self.trace.log_summary(self.log, len(self.engines))
@@ -1650,6 +1759,8 @@ class _FileRun:
         self.trimpart.add(fn, False, unrevised_trim(nw))
         self.acc_rows.pop(fn, None)
         self.accpart.add_unrevised(fn, text)
+        self.ecl_rows.pop(fn, None)
+        self.eclpart.add_unrevised(fn, text)
         self.note(fn, False)
 
     def finished(self, fn, nb):
@@ -1669,6 +1780,11 @@ class _FileRun:
             if row is None:                           # cannot happen, as above
                 self.log(f"[！！！Warning] --accuracy: no distances for {fn}")
             self.accpart.add(fn, row is not None, row if row is not None else [0, nb, 0, nb, 0, ACC_NO_TRUTH])
+        if self.eclpart:
+            row = self.ecl_rows.pop(fn, None)
+            if row is None:                           # cannot happen, as above
+                self.log(f"[！！！Warning] --error_classes: no counts for {fn}")
+            self.eclpart.add(fn, row is not None, row if row is not None else [0, nb, 0, 0, nb, 0, 0, ACC_NO_TRUTH])
         if self.trim:
             row = self.trim_rows.pop(fn, None)
             log_row = trim_log_row(row[0], row[1], self.trim[2]) if row is not None else unrevised_trim(nb)
@@ -1694,7 +1810,7 @@ class _FileRun:
                 bundle = _bundle_host_stats(bundle)   # an engine without the new calls: the host computes them after all
             form, route = _route_batch(rv, bundle, len(batch), self.pipelined, self.native_pool, self.device_merge, bool(self.report),
                                        edits=bool(self.edits_dir), combined=self.sink is not None, summary=bool(self.sumpart),
-                                       trim=self.trim is not None, accuracy=bool(self.accpart))
+                                       trim=self.trim is not None, accuracy=bool(self.accpart), error_classes=bool(self.eclpart))
             if form is not None and bundle is None:
                 packed = prepare_many(cls, [rt for _, rt, _ in batch], rv.T)
             elif form is not None:
@@ -1706,6 +1822,7 @@ class _FileRun:
                     if form == "host-merge":
                         packed = _host_merge_form(packed)
                     elif form != len(packed):
+                        classes, form = form == 31, (30 if form == 31 else form)   # --error_classes: form 30 with one block more
                         if self.report:
                             packed = cls.with_device_report(packed, self.tie_eps)
                         if form == 16 or (form in (20, 22, 27, 30) and self.edits_dir):   # --edits: the list behind the merge (and the report)
@@ -1722,6 +1839,8 @@ class _FileRun:
                             truth, toff, flags = self.accpart.block(fns, bundle["meta"][:, 1].tolist())
                             packed = cls.with_device_accuracy(packed, truth, toff)
                             self.acc_flags[id(batch)] = flags
+                            if classes:               # --error_classes: behind the accuracy, on the same truth block
+                                packed = cls.with_device_error_classes(packed)
         except Exception:
             packed = None
         if packed is None:
@@ -1769,6 +1888,8 @@ class _FileRun:
                     self.trim_rows[fn], trim = (int(tl[0]), tb[0]), (tb, self.trim[2])
                 if self.accpart:
                     self.acc_rows[fn] = self.accpart.host_rows(T, [fn], rt.bases, [len(np.asarray(rt.bases))], c[2], c[3])[0]
+                if self.eclpart:
+                    self.ecl_rows[fn] = self.eclpart.host_rows(T, [fn], rt.bases, [len(np.asarray(rt.bases))], c[2], c[3])[0]
                 if self.edits_dir:
                     write_edits(self.edits_dir, fn, edit_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual)[0], self.want_qual)
                 if self.pool is not None or self.sink is not None:
@@ -1798,6 +1919,11 @@ class _FileRun:
             trim = None
             flags = self.acc_flags.pop(id(batch), None)
             if merged:
+                if len(outs) == 12:                   # a `with_device_error_classes` call: the counts were found behind the distances, last output
+                    if self.eclpart and flags is not None:
+                        ev_len = bundle["meta"][:, 1].astype(np.int64)
+                        self.ecl_rows.update(zip(fns, self.eclpart.rows(outs[11], ev_len.tolist(), np.diff(outs[2]).tolist(), flags)))
+                    outs = outs[:11]
                 if len(outs) == 11:                   # a `with_device_accuracy` call: the distances were found behind everything else, last output
                     if self.accpart and flags is not None:
                         ev_len = bundle["meta"][:, 1].astype(np.int64)
@@ -1831,6 +1957,8 @@ class _FileRun:
                     trim = (tb, self.trim[2])
                 if self.accpart:
                     self.acc_rows.update(zip(fns, self.accpart.host_rows(T, fns, bundle["bases"], ev_len.tolist(), a1, a2)))
+                if self.eclpart:
+                    self.ecl_rows.update(zip(fns, self.eclpart.host_rows(T, fns, bundle["bases"], ev_len.tolist(), a1, a2)))
                 if self.edits_dir:
                     self.write_call_edits(fns, *edit_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2, self.want_qual))
                 qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
@@ -1928,7 +2056,8 @@ class _FileRun:
 def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None],
                   on_file: Optional[Callable[[str, bool], None]] = None, gpu_workers: int = 1,
                   core_share: Optional[int] = None, report_part: Optional[str] = None, combined_part: Optional[str] = None,
-                  summary_part: Optional[str] = None, trim_part: Optional[str] = None, accuracy_part: Optional[str] = None) -> dict:
+                  summary_part: Optional[str] = None, trim_part: Optional[str] = None, accuracy_part: Optional[str] = None,
+                  errclass_part: Optional[str] = None) -> dict:
     """Revise `files` (names inside args.fast5_base_dir) with one engine.  The host stage (HDF5 parsing, event collapse,
     statistics) runs --thread parser workers that stay a bounded number of reads ahead of the device: THREADS of this process
     inside libnanorev_host.so (at most kNativePoolMax), or PROCESSES on the Python host stage without it / with NRV_HOST_THREADS=0.
@@ -1941,10 +2070,10 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
     one line per read to, ahead of on_file (`ReportPart`).  combined_part (--combined): the part this call appends
     every read's record to INSTEAD of writing one file per read (`CombinedPart`, `deliver`).  summary_part (--summary): as
     report_part, for the summary's lines.  trim_part (--trim_log): as report_part, for the trim log's lines.  accuracy_part
-    (--accuracy): as report_part, for the accuracy file's lines."""
+    (--accuracy): as report_part, for the accuracy file's lines.  errclass_part (--error_classes): as accuracy_part, for that file's."""
     import contextlib
     with contextlib.ExitStack() as stack:             # its exit ends the run's threads and undoes what `_FileRun._start` did
-        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part, summary_part, trim_part, accuracy_part)
+        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part, summary_part, trim_part, accuracy_part, errclass_part)
         batch, nev = [], 0                            # unbundled reads are grouped into device calls of >= batch_events events
         for entries, bundle in run.results():
             bundled = []
@@ -1958,6 +2087,7 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                     run.sumpart.add(fn, False, unrevised_profile(b""))
                     run.trimpart.add(fn, False, unrevised_trim(0))
                     run.accpart.add_unrevised(fn, b"")
+                    run.eclpart.add_unrevised(fn, b"")
                     run.note(fn, False)
                 elif err is not None:
                     run.fallback(fn, rt, fq, err)
@@ -2221,7 +2351,8 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
                            combined_part=combined_part_path(args.combined, rank) if getattr(args, "combined", None) else None,
                            summary_part=report_part_path(args.summary, rank) if getattr(args, "summary", None) else None,
                            trim_part=report_part_path(args.trim_log, rank) if getattr(args, "trim_log", None) else None,
-                           accuracy_part=report_part_path(args.accuracy, rank) if getattr(args, "accuracy", None) else None)
+                           accuracy_part=report_part_path(args.accuracy, rank) if getattr(args, "accuracy", None) else None,
+                           errclass_part=report_part_path(args.error_classes, rank) if getattr(args, "error_classes", None) else None)
         st["cpus"] = len(cpus) if cpus else 0
         for e in made:
             e.close()
@@ -2262,6 +2393,8 @@ def write_originals(args, files: Sequence[str], log: Callable[[str], None], repo
             trimlog.add(fn, False, unrevised_trim(nw))
         if accuracy is not None:
             accuracy.add_unrevised(fn, text)
+            if accuracy.classes is not None:
+                accuracy.classes.add_unrevised(fn, text)
     return done
 
 
@@ -2318,6 +2451,8 @@ def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[st
                     report.add(fn, True, row)
                 if accuracy is not None and accuracy:  # the slices are merged: the read's distances, here in the parent
                     accuracy.add(fn, True, accuracy.host_rows(T, [fn], pl[0]["bases"], [N], a1, a2)[0])
+                    if accuracy.classes is not None:
+                        accuracy.classes.add(fn, True, accuracy.classes.host_rows(T, [fn], pl[0]["bases"], [N], a1, a2)[0])
                 if summary is not None and summary and have_p:
                     summary.add(fn, True, profile_rows(T, pl[0]["bases"], [N], np.concatenate([p["p1"] for p in pl]),
                                                        np.concatenate([p["p2"] for p in pl]), a1, a2)[0])
@@ -2432,6 +2567,14 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
             os.makedirs(d, exist_ok=True)
         parent_acc = AccuracyPart(report_part_path(args.accuracy, "parent"), truths, args.accuracy_max_len)
         acc_part0 = report_part_path(args.accuracy, 0)
+    ecl_part0 = None
+    if args.error_classes:                # --error_classes: the same again, on the truth set just loaded
+        clear_report_parts(args.error_classes)
+        d = os.path.dirname(args.error_classes)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        parent_acc.classes = ErrclassPart(report_part_path(args.error_classes, "parent"), truths, args.accuracy_max_len)
+        ecl_part0 = report_part_path(args.error_classes, 0)
     if args.combined:                     # --combined: a part per process too, `merge_combined` ends the run
         clear_combined_parts(args.combined)
     parent_sink = CombinedPart(combined_part_path(args.combined, "parent"), args.output_format == "fastq") if args.combined else None
@@ -2471,7 +2614,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
     if reviser_factory is not None:       # in-process (tests / embedding): one engine, no sharding
         rv = reviser_factory(args, 0)
         stats = [process_files(args, names, rv, print, report_part=report_part_path(args.report, 0) if args.report else None,
-                               combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0)]
+                               combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0, errclass_part=ecl_part0)]
     else:
         # the command line needs no torch: without it a process starts ~1.5 s sooner.  (engine.py imports
         # torch first only so that a LATER torch import in the same process finds one HIP runtime.)
@@ -2500,7 +2643,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
                 made.append((worker_factory or _default_factory)(args, 0))
                 return made[-1]                       # called once per engine (process_files: NRV_CLI_ENGINES)
             stats = [process_files(args, names, make, print, report_part=report_part_path(args.report, 0) if args.report else None,
-                                   combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0)]
+                                   combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0, errclass_part=ecl_part0)]
             for rv in made:
                 rv.close()
         else:
@@ -2537,6 +2680,9 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
     if parent_acc is not None:
         parent_acc.close()
         merge_accuracy(args.accuracy, all_names)
+        if parent_acc.classes is not None:
+            parent_acc.classes.close()
+            merge_error_classes(args.error_classes, all_names)
     if args.combined:
         parent_sink.close()
         merge_combined(args.combined, args.output_format == "fastq")

@@ -479,10 +479,10 @@ struct DevModel {
 // ---- a merged raw-read call (nrv_revise_reads_raw*_begin; nrv_merge_calls* is its test twin) -------------------------------
 // The merged block of a call of N events, n windows, n_reads reads - offsets into one device allocation:
 //   [off i64 x (n_reads + 1) | seq | qual | report u64 x n_reads x 24 | edit_off i64 x (n_reads + 1) | rec_off i64 x (n_reads + 1) |
-//    profile u64 x n_reads x 48 | trim i64 x n_reads x 2 | accu u64 x n_reads x 4]
+//    profile u64 x n_reads x 48 | trim i64 x n_reads x 2 | accu u64 x n_reads x 4 | ecls u64 x n_reads x 6]
 //                                     what comes back in one copy of `dl` bytes, mirrored in page-locked memory (nrv_merge.h,
-//                                     nrv_report.h, nrv_edits.h, nrv_pack.h, nrv_profile.h, nrv_trim.h, nrv_align.h); the report,
-//                                     edit_off, rec_off, the profile, the trim and the accuracy only where asked for - without
+//                                     nrv_report.h, nrv_edits.h, nrv_pack.h, nrv_profile.h, nrv_trim.h, nrv_align.h, nrv_errclass.h); the report,
+//                                     edit_off, rec_off, the profile, the trim, the accuracy and the error classes only where asked for - without
 //                                     them the layout is the merge's own.  A records call that hands back neither seq nor qual leaves those two on
 //                                     the device
 //   [rec u32 x N | tile u64]          the merge kernels' scratch
@@ -494,8 +494,10 @@ struct DevModel {
 //                                     only where asked for
 //   [hc u8 x N | hc u8 x (N + n)]     the alignment's stripe carries, one byte per character of the original and of the revised
 //                                     reads; only where asked for
+//   [hc8 i64 x N | hc8 i64 x (N + n)] the error classes' stripe carries, one packed cell per character of the original and of the
+//                                     revised reads; only where asked for
 // Every part is 256-byte aligned.
-struct MergeLayout { size_t seq, qual, rep, eoff, roff, prof, trim, rec, tile, edits, etile, blob, tq, acc, dl, bytes, accu, hc; };
+struct MergeLayout { size_t seq, qual, rep, eoff, roff, prof, trim, rec, tile, edits, etile, blob, tq, acc, dl, bytes, accu, hc, ecls, hc8; };
 
 // What a merged call reads besides the raw reads.  Consumed inside _begin: the caller's pointers are dead once it returns, so
 // nothing that outlives _begin keeps one (the slot keeps the VALUES of both threshold sets for the re-run of nrv_reads_raw_end)
@@ -527,6 +529,8 @@ struct MergeOut {
   uint64_t* profile = nullptr;          // [n_reads][48]
   int64_t* trim = nullptr;              // [n_reads][2]
   uint64_t* accuracy = nullptr;         // [n_reads][4]
+  uint64_t* errclass = nullptr;         // [n_reads][6]
+  bool wants_truth() const { return accuracy != nullptr || errclass != nullptr; }
 };
 // Where a merged call's inputs lie on the device, and its merged block
 struct MergeView {
@@ -539,7 +543,7 @@ struct MergeView {
   const long long* name_off;             // records only
   const unsigned char* names;
   char* blk;                             // MergeLayout offsets count from here
-  const unsigned char* truth = nullptr;  // accuracy only
+  const unsigned char* truth = nullptr;  // accuracy and error classes only
   const long long* truth_off = nullptr;
 };
 // The quality rule: characters get a Phred quality when there are thresholds and somebody reads it - the caller's qual or the
@@ -1618,6 +1622,7 @@ static int merged_collect(nrv_handle* h, const char* who, const char* who_edits,
   if (o.profile) memcpy(o.profile, head + m.prof, (size_t)v.n_reads * kProfileCols * 8);
   if (o.trim) memcpy(o.trim, head + m.trim, (size_t)v.n_reads * 16);
   if (o.accuracy) memcpy(o.accuracy, head + m.accu, (size_t)v.n_reads * kAccuracyCols * 8);
+  if (o.errclass) memcpy(o.errclass, head + m.ecls, (size_t)v.n_reads * kErrclassCols * 8);
   int rc = NRV_OK;
   if (o.edit_off) {
     const int64_t n_ed = ((const int64_t*)(head + m.eoff))[v.n_reads];
@@ -2139,6 +2144,13 @@ static int align_enqueue(nrv_handle* h, const AlignArgs& a) {
   HIPCHK(h, hipGetLastError());
   return NRV_OK;
 }
+// errclass_kernel (nrv_errclass.h): one wave per (read, kind) pair; every word of its result is stored plainly
+static int errclass_enqueue(nrv_handle* h, const ErrclassArgs& a) {
+  if (a.n_reads <= 0) return NRV_OK;
+  hipLaunchKernelGGL(errclass_kernel, dim3((unsigned)a.n_reads * (unsigned)a.kinds), dim3(64), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return NRV_OK;
+}
 // a truth set: offsets that ascend from 0, bytes where there are any, and no sequence of 2^31 - 64 characters or more
 static bool truth_ok(const uint8_t* truth, const int64_t* truth_off, int n_reads) {
   if (!truth_off || truth_off[0] != 0) return false;
@@ -2199,7 +2211,8 @@ static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, const MergeOu
   m.prof = m.roff + (o.rec_off ? up(((size_t)n_reads + 1) * 8) : 0);
   m.trim = m.prof + (o.profile ? up((size_t)n_reads * kProfileCols * 8) : 0);
   m.accu = m.trim + (o.trim ? up((size_t)n_reads * 16) : 0);
-  m.dl = m.accu + (o.accuracy ? up((size_t)n_reads * kAccuracyCols * 8) : 0);
+  m.ecls = m.accu + (o.accuracy ? up((size_t)n_reads * kAccuracyCols * 8) : 0);
+  m.dl = m.ecls + (o.errclass ? up((size_t)n_reads * kErrclassCols * 8) : 0);
   m.rec = m.dl;
   m.tile = m.rec + up((size_t)N * 4);
   m.edits = m.tile + up(tiles * 8);
@@ -2208,7 +2221,8 @@ static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, const MergeOu
   m.tq = m.blob + (o.rec_off ? up(blob_cap) : 0);
   m.acc = m.tq + (o.trim ? up(cap) : 0);
   m.hc = m.acc + (o.trim ? up((size_t)n_reads * 16) : 0);
-  m.bytes = m.hc + (o.accuracy ? up((size_t)N) + up(cap) : 0);
+  m.hc8 = m.hc + (o.accuracy ? up((size_t)N) + up(cap) : 0);
+  m.bytes = m.hc8 + (o.errclass ? up((size_t)N * 8) + up(cap * 8) : 0);
   return m;
 }
 // No window at all (N <= T): the reads come back as they are, on the host
@@ -2281,6 +2295,38 @@ static void accuracy_nothing(const uint8_t* bases, const nrv_read_desc* reads, i
     row[1] = row[2] = (uint64_t)edit_distance_host(truth + truth_off[r], m, bases + reads[r].ev_off, reads[r].ev_len);
   }
 }
+// hoststage.edit_classes by two rows of the table of packed cells (d << 32) - M, on the host: the calls without a window, as above
+static void edit_classes_host(const uint8_t* t, int64_t m, const uint8_t* s, int64_t n, uint64_t* d_out, uint64_t* M_out) {
+  std::vector<int64_t> row((size_t)n + 1);
+  for (int64_t j = 0; j <= n; ++j) row[(size_t)j] = j * kEdit;
+  for (int64_t i = 1; i <= m; ++i) {
+    int64_t diag = row[0];
+    row[0] = i * kEdit;
+    const uint8_t c = t[i - 1];
+    const bool base = c == 'A' || c == 'C' || c == 'G' || c == 'T';
+    for (int64_t j = 1; j <= n; ++j) {
+      const int64_t up_ = row[(size_t)j] + kEdit, left = row[(size_t)j - 1] + kEdit, dg = diag + ((base && c == s[j - 1]) ? -1 : kEdit);
+      diag = row[(size_t)j];
+      row[(size_t)j] = std::min(std::min(up_, left), dg);
+    }
+  }
+  const int64_t w = row[(size_t)n], d = (w + kEdit - 1) >> 32;
+  *d_out = (uint64_t)d; *M_out = (uint64_t)(d * kEdit - w);
+}
+// ... and its error classes (hoststage.read_error_classes on a call without a window): out = in
+static void errclass_nothing(const uint8_t* bases, const nrv_read_desc* reads, int n_reads, const uint8_t* truth, const int64_t* truth_off,
+                             uint64_t* errclass) {
+  static_assert(NRV_ERRCLASS_COLS == kErrclassCols, "nanorev.h and nrv_errclass.h disagree on the error classes' columns");
+  memset(errclass, 0, (size_t)n_reads * kErrclassCols * 8);
+  for (int r = 0; r < n_reads; ++r) {
+    const int64_t m = truth_off[r + 1] - truth_off[r];
+    if (m <= 0) continue;
+    uint64_t* row = errclass + (size_t)r * kErrclassCols;
+    row[0] = (uint64_t)m;
+    edit_classes_host(truth + truth_off[r], m, bases + reads[r].ev_off, reads[r].ev_len, row + 1, row + 2);
+    row[3] = row[1]; row[4] = row[2];
+  }
+}
 // ... and everything a merged call asks for, for both callers that can meet N <= T
 static void merged_nothing(const MergeIn& in, const MergeOut& o, const nrv_read_desc* reads, int n_reads, int64_t N) {
   merge_nothing(in.bases, reads, n_reads, N, o.seq, in.q_thr ? o.qual : nullptr, o.off);
@@ -2291,6 +2337,7 @@ static void merged_nothing(const MergeIn& in, const MergeOut& o, const nrv_read_
                               o.trim, in.min_len);
   if (o.profile) profile_nothing(in.bases, reads, n_reads, o.profile);
   if (o.accuracy) accuracy_nothing(in.bases, reads, n_reads, in.truth, in.truth_off, o.accuracy);
+  if (o.errclass) errclass_nothing(in.bases, reads, n_reads, in.truth, in.truth_off, o.errclass);
 }
 
 // The kernels of a merged call behind whatever produced v.a1 / a2 / p1 / p2 on the compute stream: the merge, then what `o` asks
@@ -2326,7 +2373,7 @@ static int merged_enqueue(nrv_handle* h, const MergeView& v, const MergeLayout& 
     rc = pack_enqueue(h, k);
   }
   if (!rc && o.profile) rc = profile_enqueue(h, profile_args(a, v.p1, v.p2, prof_thr, v.blk + m.prof));
-  if (!rc && o.accuracy) {                                 // LAST: it reads bases, the descriptors, off / seq and the truth
+  if (!rc && o.accuracy) {                                 // behind everything that writes off / seq: it reads bases, the descriptors, off / seq and the truth
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     AlignArgs k;
     k.n_reads = v.n_reads; k.kinds = 2;
@@ -2336,6 +2383,17 @@ static int merged_enqueue(nrv_handle* h, const MergeView& v, const MergeLayout& 
     k.hc0 = (unsigned char*)(v.blk + m.hc); k.hc1 = k.hc0 + up((size_t)v.N);
     k.accu = (unsigned long long*)(v.blk + m.accu); k.dist = nullptr;
     rc = align_enqueue(h, k);
+  }
+  if (!rc && o.errclass) {                                 // ... and behind it: the same inputs, carry words of its own
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    ErrclassArgs k;
+    k.n_reads = v.n_reads; k.kinds = 2;
+    k.truth = v.truth; k.truth_off = v.truth_off;
+    k.reads = v.reads; k.bases = v.bases; k.off = a.off; k.seq = a.seq;
+    k.cap0 = v.N; k.cap1 = v.N + (v.N - h->T > 0 ? v.N - h->T : 0);
+    k.hc0 = (long long*)(v.blk + m.hc8); k.hc1 = (long long*)(v.blk + m.hc8 + up((size_t)v.N * 8));
+    k.ecls = (unsigned long long*)(v.blk + m.ecls); k.dist = nullptr; k.match = nullptr;
+    rc = errclass_enqueue(h, k);
   }
   return rc;
 }
@@ -2394,7 +2452,7 @@ static int raw_begin(nrv_handle* h, const RawIn& in, float* p1, float* p2, int8_
     if (blob_cap > 0 && !mo->blob) { h->err = "nrv_revise_reads_raw_records_begin: null blob"; return NRV_E_INVALID; }
     if (blob_cap >= ((size_t)1 << 32)) { h->err = "nrv_revise_reads_raw_records_begin: records of 4 GiB and more in one call"; return NRV_E_INVALID; }
   }
-  const bool accuracy = mr != nullptr && mo->accuracy != nullptr;   // (revise_begin has checked the truth)
+  const bool accuracy = mr != nullptr && mo->wants_truth();   // (revise_begin has checked the truth)
   const bool with_stats = last_dur != nullptr || on_device != nullptr;
   const int64_t stat_len = with_stats ? stats_check(h, reads, n_reads, last_dur, on_device) : 0;
   if (stat_len < 0) return NRV_E_INVALID;
@@ -2543,9 +2601,9 @@ static int revise_begin(nrv_handle* h, const char* who, const char* missing, con
   else if (!mo.rec_off && (mr.names || mr.name_off || mo.blob)) bad = "names / name_off / blob without rec_off";
   else if ((mr.prof_thr == nullptr) != (mo.profile == nullptr)) bad = "prof_thr and profile go together";
   else if (mo.trim && !trim_rule_ok(mr.Q, mr.W, mr.min_len)) bad = "Q must be in 1 .. 40, W in 1 .. 64 and min_len >= 0";
-  else if (mo.accuracy && (in.n_reads < 0 || !truth_ok(mr.truth, mr.truth_off, in.n_reads)))
+  else if (mo.wants_truth() && (in.n_reads < 0 || !truth_ok(mr.truth, mr.truth_off, in.n_reads)))
     bad = "null truth / truth_off, offsets that do not ascend from 0, or a truth of 2^31 - 64 characters and more";
-  else if (mo.accuracy && in.N >= ((int64_t)1 << 30)) bad = "2^30 events and more in a call with a truth";
+  else if (mo.wants_truth() && in.N >= ((int64_t)1 << 30)) bad = "2^30 events and more in a call with a truth";
   if (h && bad) { h->err = std::string(who) + ": " + bad; return NRV_E_INVALID; }
   return raw_begin(h, in, nullptr, nullptr, nullptr, nullptr, ticket, &mr, &mo);
 }
@@ -2745,6 +2803,40 @@ int nrv_revise_reads_raw_accuracy(nrv_handle* h, const int16_t* raw, int64_t n_r
   });
 }
 
+// every earlier block may be NULL, the accuracy included: the truth is then read by the error classes alone
+int nrv_revise_reads_raw_errclass_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                        const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                        const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                        uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                        nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                        uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                        const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                                        const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, uint64_t* errclass, int* ticket) {
+  const char* missing = nullptr;
+  if (!errclass || !truth_off) missing = "null truth_off / errclass";
+  else if (trim && !trim_thr) missing = "trim without trim_thr";
+  MergeOut mo{seq, qual, off, report, tie_eps, edits, edit_off, blob, rec_off, profile, trim, accuracy};
+  mo.errclass = errclass;
+  return revise_begin(h, "nrv_revise_reads_raw_errclass_begin", missing,
+                      RawIn{raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device},
+                      MergeIn{bases, q_thr, names, name_off, prof_thr, trim_thr, Q, W, min_len, truth, truth_off}, mo, ticket);
+}
+
+int nrv_revise_reads_raw_errclass(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                  const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                  const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                  uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                  nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                  uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                  const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                                  const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, uint64_t* errclass) {
+  return begin_then_end(h, [&](int* t) {
+    return nrv_revise_reads_raw_errclass_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                               seq, qual, off, tie_eps, report, edits, edit_off, names, name_off, blob, rec_off,
+                                               prof_thr, profile, trim_thr, Q, W, min_len, trim, truth, truth_off, accuracy, errclass, t);
+  });
+}
+
 int nrv_reads_raw_end(nrv_handle* h, int ticket) {
   int rc = check_handle(h);
   if (rc) return rc;
@@ -2872,7 +2964,8 @@ int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32
 
 // nrv_merge_calls (o.report == nullptr: that call, to the byte), nrv_merge_calls_report, (o.edit_off != nullptr)
 // nrv_merge_calls_edits, (o.profile != nullptr) nrv_merge_calls_profile and (o.trim != nullptr; `more`: its rule, and the names of
-// its records) nrv_merge_calls_trim and (o.accuracy != nullptr; `more`: the truth) nrv_merge_calls_accuracy
+// its records) nrv_merge_calls_trim, (o.accuracy != nullptr; `more`: the truth) nrv_merge_calls_accuracy and (o.errclass != nullptr;
+// `more`: the truth) nrv_merge_calls_errclass
 static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
                             const float* p1, const float* p2, int64_t n_win, const float* q_thr, const MergeOut& o,
                             const float* prof_thr = nullptr, const MergeIn& more = MergeIn{}) {
@@ -2898,11 +2991,12 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
     blob_cap = blob_capacity(N, n, n_reads, more.name_off[n_reads], q_thr != nullptr);
     if ((blob_cap > 0 && !o.blob) || blob_cap >= ((size_t)1 << 32)) { h->err = "nrv_merge_calls_trim: null blob (or records of 4 GiB and more)"; return NRV_E_INVALID; }
   }
-  if (o.accuracy && !truth_ok(more.truth, more.truth_off, n_reads)) {
-    h->err = "nrv_merge_calls_accuracy: null truth / truth_off, offsets that do not ascend from 0, or a truth of 2^31 - 64 characters and more";
+  const std::string who_truth = o.errclass ? "nrv_merge_calls_errclass" : "nrv_merge_calls_accuracy";
+  if (o.wants_truth() && !truth_ok(more.truth, more.truth_off, n_reads)) {
+    h->err = who_truth + ": null truth / truth_off, offsets that do not ascend from 0, or a truth of 2^31 - 64 characters and more";
     return NRV_E_INVALID;
   }
-  if (o.accuracy && N >= ((int64_t)1 << 30)) { h->err = "nrv_merge_calls_accuracy: 2^30 events and more"; return NRV_E_INVALID; }
+  if (o.wants_truth() && N >= ((int64_t)1 << 30)) { h->err = who_truth + ": 2^30 events and more"; return NRV_E_INVALID; }
   if (n == 0) {
     MergeIn in = more;
     in.bases = bases; in.q_thr = q_thr;
@@ -2919,7 +3013,7 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
   const size_t o_b = up((size_t)n_reads * sizeof(SegRead)), o_a1 = o_b + up((size_t)N), o_a2 = o_a1 + up((size_t)n);
   const size_t o_p1 = o_a2 + up((size_t)n), o_p2 = o_p1 + (have_p ? up((size_t)n * 24) : 0), o_no = o_p2 + (have_p ? up((size_t)n * 20) : 0);
   const size_t o_nm = o_no + (o.rec_off ? up(((size_t)n_reads + 1) * 8) : 0), o_to = o_nm + (o.rec_off ? up((size_t)more.name_off[n_reads]) : 0);
-  const size_t o_tr = o_to + (o.accuracy ? up(((size_t)n_reads + 1) * 8) : 0), o_m = o_tr + (o.accuracy ? up((size_t)more.truth_off[n_reads]) : 0);
+  const size_t o_tr = o_to + (o.wants_truth() ? up(((size_t)n_reads + 1) * 8) : 0), o_m = o_tr + (o.wants_truth() ? up((size_t)more.truth_off[n_reads]) : 0);
   const size_t bytes = o_m + m.bytes;
   char* d = nullptr;
   HIPCHK(h, hipMalloc((void**)&d, bytes));
@@ -2939,7 +3033,7 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
       HIPCHK(h, hipMemcpyAsync(d + o_no, more.name_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
       if (more.name_off[n_reads] > 0) HIPCHK(h, hipMemcpyAsync(d + o_nm, more.names, (size_t)more.name_off[n_reads], hipMemcpyHostToDevice, h->stream));
     }
-    if (o.accuracy) {
+    if (o.wants_truth()) {
       HIPCHK(h, hipMemcpyAsync(d + o_to, more.truth_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
       if (more.truth_off[n_reads] > 0) HIPCHK(h, hipMemcpyAsync(d + o_tr, more.truth, (size_t)more.truth_off[n_reads], hipMemcpyHostToDevice, h->stream));
     }
@@ -3024,6 +3118,18 @@ int nrv_merge_calls_accuracy(nrv_handle* h, const uint8_t* bases, const int64_t*
   return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, o, nullptr, more);
 }
 
+int nrv_merge_calls_errclass(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                             const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                             const uint8_t* truth, const int64_t* truth_off, uint64_t* errclass) {
+  if (h && (!truth_off || (n_reads > 0 && !errclass))) { h->err = "nrv_merge_calls_errclass: null truth_off / errclass"; return NRV_E_INVALID; }
+  static uint64_t none[NRV_ERRCLASS_COLS];
+  MergeOut o{seq, qual, off};
+  o.errclass = errclass ? errclass : none;
+  MergeIn more;
+  more.truth = truth; more.truth_off = truth_off;
+  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, o, nullptr, more);
+}
+
 int nrv_edit_distance(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
                       int64_t* dist) {
   int rc = check_handle(h);
@@ -3058,6 +3164,50 @@ int nrv_edit_distance(nrv_handle* h, const uint8_t* a, const int64_t* a_off, con
     k.accu = nullptr; k.dist = (long long*)(d + o_d);
     if ((rc2 = align_enqueue(h, k))) return rc2;
     HIPCHK(h, hipMemcpyAsync(dist, d + o_d, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return NRV_OK;
+  };
+  rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  (void)hipFree(d);
+  return rc;
+}
+
+int nrv_edit_classes(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
+                     int64_t* dist, int64_t* match) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (n_pairs < 0 || (n_pairs > 0 && (!dist || !match))) { h->err = "nrv_edit_classes: bad arguments"; return NRV_E_INVALID; }
+  if (!truth_ok(a, a_off, n_pairs) || !truth_ok(b, b_off, n_pairs)) {
+    h->err = "nrv_edit_classes: null sequences / offsets, offsets that do not ascend from 0, or a sequence of 2^31 - 64 characters and more";
+    return NRV_E_INVALID;
+  }
+  if (n_pairs == 0) return NRV_OK;
+  const int64_t ta = a_off[n_pairs], tb = b_off[n_pairs];
+  // one block of its own: [a_off | b_off | a | b | hc8 | dist | match]
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t nb = ((size_t)n_pairs + 1) * 8, nd = up((size_t)n_pairs * 8);
+  const size_t o_bo = up(nb), o_a = o_bo + up(nb), o_b = o_a + up((size_t)ta), o_hc = o_b + up((size_t)tb), o_d = o_hc + up((size_t)tb * 8);
+  const size_t bytes = o_d + 2 * nd;
+  char* d = nullptr;
+  HIPCHK(h, hipMalloc((void**)&d, bytes));
+  auto run = [&]() -> int {
+    int rc2 = poison_fill(h, d, bytes, h->stream);
+    if (rc2) return rc2;
+    HIPCHK(h, hipMemcpyAsync(d, a_off, nb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d + o_bo, b_off, nb, hipMemcpyHostToDevice, h->stream));
+    if (ta > 0) HIPCHK(h, hipMemcpyAsync(d + o_a, a, (size_t)ta, hipMemcpyHostToDevice, h->stream));
+    if (tb > 0) HIPCHK(h, hipMemcpyAsync(d + o_b, b, (size_t)tb, hipMemcpyHostToDevice, h->stream));
+    ErrclassArgs k;
+    k.n_reads = n_pairs; k.kinds = 1;
+    k.truth = (const unsigned char*)(d + o_a); k.truth_off = (const long long*)d;
+    k.reads = nullptr; k.bases = nullptr; k.cap0 = 0; k.hc0 = nullptr;
+    k.off = (const long long*)(d + o_bo); k.seq = (const unsigned char*)(d + o_b); k.cap1 = tb;
+    k.hc1 = (long long*)(d + o_hc);
+    k.ecls = nullptr; k.dist = (long long*)(d + o_d); k.match = (long long*)(d + o_d + nd);
+    if ((rc2 = errclass_enqueue(h, k))) return rc2;
+    HIPCHK(h, hipMemcpyAsync(dist, d + o_d, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(match, d + o_d + nd, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return NRV_OK;
   };

@@ -72,3 +72,4 @@
 #include "nrv_profile.h"       // profile_kernel (per-read quality histogram and base counts behind the merge, opt-in)
 #include "nrv_trim.h"          // trim_qual / trim_window / trim_finish_kernel (sliding-window quality trim behind the merge, opt-in)
 #include "nrv_align.h"         // align_kernel (edit distance of the original and the revised reads to a truth set, one wave per pair, opt-in)
+#include "nrv_errclass.h"      // errclass_kernel (edits and matched columns of the original and the revised reads against a truth set: a wavefront across the lanes, one wave per pair, opt-in)

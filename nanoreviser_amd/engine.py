@@ -41,10 +41,13 @@ SYMBOLS = [
     "nrv_revise_reads_raw_profile_begin", "nrv_revise_reads_raw_profile", "nrv_merge_calls_profile",
     "nrv_revise_reads_raw_trim_begin", "nrv_revise_reads_raw_trim", "nrv_merge_calls_trim", "nrv_trim_reads", "nrv_pack_records_trim",
     "nrv_revise_reads_raw_accuracy_begin", "nrv_revise_reads_raw_accuracy", "nrv_merge_calls_accuracy", "nrv_edit_distance",
+    "nrv_revise_reads_raw_errclass_begin", "nrv_revise_reads_raw_errclass", "nrv_merge_calls_errclass", "nrv_edit_classes",
 ]
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 PROFILE_COLS = 48                   # NRV_PROFILE_COLS
 ACCURACY_COLS = 4                   # NRV_ACCURACY_COLS
+ERRCLASS_COLS = 6                   # NRV_ERRCLASS_COLS
+ERRCLASS_R = 16                     # kErrclassR of csrc/nrv_errclass.h: truth characters per lane; a stripe is 64 of them
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "f16x2": 2}
 
@@ -93,8 +96,9 @@ _RECORDS = ([_U8P, _I64P, _U8P, _I64P], lambda p: p[16:20])                     
 _PROFILE = ([_FP, _U64P], lambda p: p[20:22])                                            # prof_thr, profile
 _TRIM = ([_FP, C.c_int, C.c_int, C.c_int64, _I64P], lambda p: p[22:27])                   # trim_thr, Q, W, min_len, trim
 _TRUTH = ([_U8P, _I64P, _U64P], lambda p: p[27:30])                                      # truth, truth_off, accuracy
+_ERRCLASS = ([_U64P], lambda p: p[30:31])                                                # errclass
 # len(packed) -> (synchronous symbol, begin symbol, blocks, whether the call returns merged reads: (seq, qual, off[, report]
-# [, edits, edit_off][, blob, rec_off][, profile][, trim][, accuracy]))
+# [, edits, edit_off][, blob, rec_off][, profile][, trim][, accuracy][, errclass]))
 _RAW_FORMS = {
     7: ("nrv_predict_reads_raw", "nrv_reads_raw_begin", (_CALLS,), False),
     9: ("nrv_predict_reads_raw_stats", "nrv_reads_raw_stats_begin", (_STATS, _CALLS), False),
@@ -109,6 +113,8 @@ _RAW_FORMS = {
 _RAW_FORMS_TRUTH = {
     30: ("nrv_revise_reads_raw_accuracy", "nrv_revise_reads_raw_accuracy_begin",
          (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS, _PROFILE, _TRIM, _TRUTH), True),
+    31: ("nrv_revise_reads_raw_errclass", "nrv_revise_reads_raw_errclass_begin",
+         (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS, _PROFILE, _TRIM, _TRUTH, _ERRCLASS), True),
 }
 _PACK_RECORDS_T = [C.c_void_p, _U8P, _U8P, _I64P, C.c_int, _U8P, _I64P, _U8P, _I64P]         # nrv_pack_records
 _READS_HEAD_T = _RAW_HEAD_T[:4] + [C.c_int64, C.POINTER(_ReadDesc), C.c_int]     # nrv_segment_reads, nrv_read_stats: no features
@@ -116,6 +122,7 @@ _MERGE_CALLS_T = [C.c_void_p, _U8P, _I64P, C.c_int, _I8P, _I8P, _FP, _FP, C.c_in
 _TRIM_READS_T = [C.c_void_p, _U8P, _I64P, C.c_int, C.c_int, C.c_int, _I64P]                  # nrv_trim_reads
 _PACK_RECORDS_TRIM_T = _PACK_RECORDS_T[:7] + [_I64P, C.c_int64] + _PACK_RECORDS_T[7:]        # nrv_pack_records_trim
 _EDIT_DISTANCE_T = [C.c_void_p, _U8P, _I64P, _U8P, _I64P, C.c_int, _I64P]                    # nrv_edit_distance
+_EDIT_CLASSES_T = _EDIT_DISTANCE_T + [_I64P]                                                 # nrv_edit_classes
 
 
 _lib = None
@@ -201,8 +208,9 @@ def load_library(path: Optional[str] = None):
     have_profile = hasattr(lib, "nrv_merge_calls_profile")
     have_trim = hasattr(lib, "nrv_merge_calls_trim")
     have_truth = hasattr(lib, "nrv_merge_calls_accuracy")
+    have_errclass = hasattr(lib, "nrv_merge_calls_errclass")
     for sync, begin, blocks, _ in list(_RAW_FORMS.values()) + list(_RAW_FORMS_TRUTH.values()):  # (every restype is ctypes' default, int: the nrv_* status)
-        if (have_truth or _TRUTH not in blocks) and (have_trim or _TRIM not in blocks) and (have_profile or _PROFILE not in blocks) and (have_records or _RECORDS not in blocks) \
+        if (have_errclass or _ERRCLASS not in blocks) and (have_truth or _TRUTH not in blocks) and (have_trim or _TRIM not in blocks) and (have_profile or _PROFILE not in blocks) and (have_records or _RECORDS not in blocks) \
                 and (have_edits or _EDITS not in blocks) and (have_report or _REPORT not in blocks):
             getattr(lib, sync).argtypes = _RAW_HEAD_T + [t for types, _ in blocks for t in types]
             getattr(lib, begin).argtypes = getattr(lib, sync).argtypes + [C.POINTER(C.c_int)]
@@ -222,6 +230,9 @@ def load_library(path: Optional[str] = None):
     if have_truth:
         lib.nrv_merge_calls_accuracy.argtypes = _MERGE_CALLS_T + _TRUTH[0]
         lib.nrv_edit_distance.argtypes = _EDIT_DISTANCE_T
+    if have_errclass:
+        lib.nrv_merge_calls_errclass.argtypes = _MERGE_CALLS_T + _TRUTH[0]
+        lib.nrv_edit_classes.argtypes = _EDIT_CLASSES_T
     lib.nrv_reads_raw_end.argtypes = [vp, C.c_int]
     lib.nrv_segment_reads.argtypes = _READS_HEAD_T + [fp]
     lib.nrv_read_stats.argtypes = _READS_HEAD_T + [_I32P, _DP, _DP, _DP, _DP, fp]
@@ -600,12 +611,23 @@ class Reviser:
         t, toff = cls._truth_block(truth, truth_off, packed[4])
         return packed + (t, toff, np.zeros((packed[4], ACCURACY_COLS), np.uint64))
 
+    @classmethod
+    def with_device_error_classes(cls, packed):
+        """A `with_device_accuracy` tuple (30 elements) whose call also finds, per read, the edits and the matched columns of
+        the best alignments of its truth with the original and with the revised read (include/nanorev.h
+        nrv_revise_reads_raw_errclass_begin; hoststage.read_error_classes is the definition).  The result has 31 elements;
+        element 30 is errclass uint64[n_reads][6].  `run_packed_raw` / `begin_packed_raw` + `end_packed_raw` then return what
+        the `with_device_accuracy` call returns and the error-class block LAST."""
+        if len(packed) != 30:
+            raise ValueError("with_device_error_classes extends a with_device_accuracy tuple")
+        return tuple(packed) + (np.zeros((packed[4], ERRCLASS_COLS), np.uint64),)
+
     @staticmethod
     def _trim_merged(out):
         seq, qual, off = out[:3]
         total = int(off[-1])
         more, tail = tuple(out[3:]), ()
-        if len(more) in (6, 7, 8):                    # (..., profile[, trim[, accuracy]]): a `with_device_profile` / `with_device_trim` / `with_device_accuracy` call; blocks it does not carry are None
+        if len(more) in (6, 7, 8, 9):                 # (..., profile[, trim[, accuracy[, errclass]]]): a `with_device_profile` / `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` call; blocks it does not carry are None
             more, tail = more[:5], more[5:]
         if len(more) in (3, 5) and more[1] is not None:   # (report | None, edits, edit_off, ...): the used prefix of the records
             more = (more[0], more[1][:int(more[2][-1])], more[2]) + more[3:]
@@ -623,21 +645,21 @@ class Reviser:
         *_begin with the ticket behind the same arguments.  Returns (ticket number or None, outputs, merged)."""
         form = _RAW_FORMS.get(len(packed)) or _RAW_FORMS_TRUTH.get(len(packed))
         if form is None:
-            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14, 16, 20, 22, 27 or 30 elements, not {len(packed)}")
+            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14, 16, 20, 22, 27 or 30 elements - or 31, a 30 with the error classes -, not {len(packed)}")
         sync, beg, blocks, merged = form
-        if not hasattr(self._lib, beg):               # the report, edits, records, profile, trim and accuracy pairs are found by presence
+        if not hasattr(self._lib, beg):               # the report, edits, records, profile, trim, accuracy and error-class pairs are found by presence
             raise NrvError(-1, f"this build of libnanorev_hip.so has no {beg}")
         args = self._raw_head(packed)
         for types, pick in blocks:
             args += _marshal(pick(packed), types)
         t = C.c_int(-1)
         self._check(getattr(self._lib, beg)(*args, C.byref(t)) if begin else getattr(self._lib, sync)(*args))
-        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) + tuple(packed[18:20]) + tuple(packed[21:22]) + tuple(packed[26:27]) + tuple(packed[29:30]) if merged else packed[6]), merged
+        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) + tuple(packed[18:20]) + tuple(packed[21:22]) + tuple(packed[26:27]) + tuple(packed[29:31]) if merged else packed[6]), merged
 
     def run_packed_raw(self, packed):
         """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared (or `with_device_stats` /
         `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` /
-        `with_device_trim` / `with_device_accuracy` extended)."""
+        `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` extended)."""
         _, out, merged = self._raw_call(packed, False)
         return self._trim_merged(out) if merged else out
 
@@ -653,7 +675,8 @@ class Reviser:
         edit_off) for a `with_device_edits` call and (report | None, edits | None, edit_off | None, blob, rec_off) - the blob
         trimmed to rec_off[-1] - for a `with_device_records` call; a `with_device_profile` call returns the latter with the
         profile behind it, a `with_device_trim` call with (profile | None, trim) behind it, a `with_device_accuracy` call with
-        (profile | None, trim | None, accuracy) behind it."""
+        (profile | None, trim | None, accuracy) behind it, a `with_device_error_classes` call with the error classes behind
+        that."""
         t, out = ticket[:2]
         self._check(self._lib.nrv_reads_raw_end(self._h, t))
         return self._trim_merged(out) if len(ticket) == 3 else out
@@ -811,6 +834,45 @@ class Reviser:
         self._check(self._lib.nrv_edit_distance(*_marshal((self._h, a if a.size else np.zeros(1, np.uint8), a_off,
                                                            b if b.size else np.zeros(1, np.uint8), b_off, n, dist), _EDIT_DISTANCE_T)))
         return dist[:n]
+
+    def merge_calls_errclass_device(self, bases, ev_len, a1, a2, truth, truth_off, p1=None, p2=None, q_thr=None):
+        """`merge_calls_accuracy_device` with the error-class block in the accuracy's place (nrv_merge_calls_errclass).  Returns
+        (seq, qual | None, off, errclass uint64[n_reads][6]) - the block is hoststage.read_error_classes', bit for bit."""
+        if not hasattr(self._lib, "nrv_merge_calls_errclass"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_merge_calls_errclass")
+        ins = self._merge_inputs(bases, ev_len, a1, a2, p1, p2, q_thr, q_thr is not None)
+        n, (q1, q2, thr) = ins[2].size, ins[4:]
+        if thr is not None and (thr.size != 39 or q1.shape[0] != n or q2.shape[0] != n):
+            raise ValueError("q_thr / p1 / p2 do not match")
+        nr = ins[1].size
+        t, toff = self._truth_block(truth, truth_off, nr)
+        ec = np.zeros((nr, ERRCLASS_COLS), np.uint64)
+        return self._merge_call("nrv_merge_calls_errclass", *ins, *_marshal((t, toff, ec), _TRUTH[0])) + (ec,)
+
+    def edit_classes_device(self, truths, reads):
+        """errclass_kernel alone (nrv_edit_classes): truths and reads are equally long lists of byte strings (or uint8 arrays);
+        returns (dist, match), int64[n_pairs] each, hoststage.edit_classes(truths[k], reads[k]) - and -1 / -1 where truths[k] is
+        empty."""
+        if not hasattr(self._lib, "nrv_edit_classes"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_edit_classes")
+        if len(truths) != len(reads):
+            raise ValueError("one read per truth")
+        a, a_off = self._names_block(truths)
+        b, b_off = self._names_block(reads)
+        return self.edit_classes_offsets(a, a_off, b, b_off)
+
+    def edit_classes_offsets(self, a, a_off, b, b_off):
+        """`edit_classes_device` on the arrays as nrv_edit_classes takes them; the offsets are passed on unchecked."""
+        if not hasattr(self._lib, "nrv_edit_classes"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_edit_classes")
+        a_off = np.ascontiguousarray(a_off, dtype=np.int64).reshape(-1)
+        b_off = np.ascontiguousarray(b_off, dtype=np.int64).reshape(-1)
+        a, b = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1), np.ascontiguousarray(b, dtype=np.uint8).reshape(-1)
+        n = a_off.size - 1
+        dist, match = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        self._check(self._lib.nrv_edit_classes(*_marshal((self._h, a if a.size else np.zeros(1, np.uint8), a_off,
+                                                          b if b.size else np.zeros(1, np.uint8), b_off, n, dist, match), _EDIT_CLASSES_T)))
+        return dist[:n], match[:n]
 
     def merge_calls_trim(self, bases, ev_len, a1, a2, p1, p2, Q, W=10, q_thr=None, trim_thr=None, names=None, min_len=1):
         """`merge_calls_device` with the sliding-window trim (nrv_merge_calls_trim): p1 / p2 are required, q_thr may be None (a
