@@ -499,6 +499,66 @@ int nrv_merge_calls_errclass(nrv_handle* h, const uint8_t* bases, const int64_t*
 int nrv_edit_classes(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
                      int64_t* dist, int64_t* match);
 
+/* TRUTH REGIONS: INFIX ALIGNMENT ON BOTH STRANDS (opt-in; nothing above changes).  The accuracy and the error classes want the
+ * exact true sequence of a read; a user has a reference and a mapper's approximate coordinates, so the truth is a REGION a few
+ * bases long or short at each end, and half of them lie on the other strand.  This block places the original and the revised
+ * read INSIDE its region, free ends on the region, on the forward strand or on both, by ONE launch behind the error classes'.
+ * The rule, integers only, no traceback: for a region t (m bytes) and a read s (n bytes), bytes matching as above, take among
+ * all substrings t[start:end] (0-based, half-open) the one with, in this order, the fewest edits d of a global alignment with
+ * s, the most matched columns M, the largest start, the smallest end.  On the reverse strand t is first replaced by its
+ * reverse complement (A<->T, C<->G; any other byte stays as it is and matches nothing) and start / end count on THAT.
+ * (d, M, start, end) follows from a forward recurrence over triples compared lexicographically on (d, -M, -start):
+ *   W[0][j] = (j, 0, 0) and W[i][0] = (0, 0, -i);
+ *   W[i][j] = min(W[i-1][j] + (1, 0, 0), W[i][j-1] + (1, 0, 0), W[i-1][j-1] + ((0, -1, 0) on a match, (1, 0, 0) otherwise));
+ *   (d, -M, -start, end) = the minimum over i = 0 .. m of (W[i][n], i).  n = 0 gives (0, 0, m, m).  m = 0 means "this read has
+ *   no truth": its row is all zeros.
+ * A cell is one signed 64-bit value d 2^42 - M 2^21 - start, so a region, and a read that has one, holds at most
+ * NRV_INFIX_MAX_LEN characters: longer input is refused under the entry point's name (a REVISED read above it - the call
+ * cannot know it beforehand - counts as empty).  hoststage.infix_classes is the definition.  The arguments of
+ * nrv_revise_reads_raw_errclass_begin - every block of it may be NULL as there, `accuracy` and `errclass` too - then, required,
+ *   strands    1: the forward strand alone; 2: both
+ *   infix      uint64 [n_reads][NRV_INFIX_COLS]:
+ *     0  truth_len     1  strands run (1 or 2)
+ *     2 ..  5  dist, match, start, end of the ORIGINAL bases of the read on the forward strand
+ *     6 ..  9  the same on the reverse strand (zeros with strands = 1)
+ *    10 .. 13  of seq[off[r] .. off[r + 1]), the UNTRIMMED revision, on the forward strand
+ *    14 .. 17  the same on the reverse strand (zeros with strands = 1)
+ * One wave per (read, original | revised, forward | reverse) triple; every word is a function of its triple alone, stored
+ * plainly: the bytes do not depend on the order of the workgroups and the range-guard re-run accumulates nothing.  N <= T:
+ * nothing is enqueued, the block is filled on the host with out = in.  Tickets, the two-calls-in-flight rule and the failure
+ * paths are those of nrv_revise_reads_raw_begin; `infix` is filled by nrv_reads_raw_end.  nrv_revise_reads_raw_infix IS
+ * _infix_begin + _end. */
+#define NRV_INFIX_COLS 18
+#define NRV_INFIX_MAX_LEN 2097151 /* 2^21 - 1 */
+int nrv_revise_reads_raw_infix_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                     const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                     const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                     uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                     nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                     uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                     const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                                     const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, uint64_t* errclass,
+                                     int strands, uint64_t* infix, int* ticket);
+int nrv_revise_reads_raw_infix(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                               const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                               const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                               uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                               nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                               uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                               const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                               const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, uint64_t* errclass,
+                               int strands, uint64_t* infix);
+/* nrv_merge_calls with the infix block, by the kernel nrv_revise_reads_raw_infix_begin runs, on calls the host supplies.  The
+ * twin used by the parity tests. */
+int nrv_merge_calls_infix(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                          const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                          const uint8_t* truth, const int64_t* truth_off, int strands, uint64_t* infix);
+/* The same kernel on pairs the host supplies (a: the regions, b: the reads), on ONE strand - reverse is 0 or 1; dist, match,
+ * start and end int64 [n_pairs], -1 in all four for an empty region.  Offsets that do not ascend from 0, another `reverse` and
+ * a length above NRV_INFIX_MAX_LEN are refused.  The unit door of the kernel. */
+int nrv_infix_classes(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
+                      int reverse, int64_t* dist, int64_t* match, int64_t* start, int64_t* end);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

@@ -191,12 +191,34 @@ def get_args(argv: Optional[Sequence[str]] = None):
                         "truth base before and after, and a line #reads as in --accuracy.  It shares --accuracy_max_len.  With "
                         "--device_merge the counts are found on the GPU behind the merge, everywhere else by the host stage at "
                         "about 0.3 s per read: the same file byte for byte.  Off by default; without it nothing changes")
+    p.add_argument("--infix", dest="infix", default=None, metavar="FILE",
+                   help="with --truth (--accuracy is not needed): treat every truth as a REGION that holds the read somewhere, on "
+                        "either strand, and write to FILE (also NRV_INFIX=FILE) where the original and the revised (untrimmed) "
+                        "read lie in it, a TSV with one header line, one line per input read sorted by file name - name, status, "
+                        "truth_len, strand, then for both forms of the read its length, dist, match, start, end and id - then a "
+                        "line #total with the summed integers and the pooled identities and a line #reads as in --accuracy.  "
+                        "Among all substrings of the region the one with the fewest edits, then the most matched columns, then "
+                        "the largest start, then the smallest end; strand is - when the ORIGINAL read fits the reverse complement "
+                        "strictly better, and both forms are reported on that strand; start / end are 0-based half-open on the "
+                        "region as given; id = match / (match + dist).  --accuracy_max_len applies, capped at 2097151.  With "
+                        "--device_merge the figures are found on the GPU behind the merge, everywhere else by the host stage at "
+                        "about 2 s per read: the same file byte for byte.  --resume does not work with it.  Off by default; "
+                        "without it nothing changes")
+    p.add_argument("--infix_strand", dest="infix_strand", default="both", choices=("both", "forward"),
+                   help="with --infix: try both strands of a region (default) or the forward strand alone")
     a = p.parse_args(argv)
+    a.infix = a.infix or (os.environ.get("NRV_INFIX", "").strip() or None)
     a.error_classes = a.error_classes or (os.environ.get("NRV_ERROR_CLASSES", "").strip() or None)
     a.truth = a.truth or (os.environ.get("NRV_TRUTH", "").strip() or None)
     a.accuracy = a.accuracy or (os.environ.get("NRV_ACCURACY", "").strip() or None)
-    if (a.truth is None) != (a.accuracy is None):
+    if a.infix and not a.truth:
+        print("[！！！Error] --infix goes with --truth", file=sys.stderr)
+        raise SystemExit(2)
+    if (a.truth is None) != (a.accuracy is None) and not (a.infix and a.truth):
         print("[！！！Error] --truth and --accuracy go together", file=sys.stderr)
+        raise SystemExit(2)
+    if a.infix and a.resume:
+        print("[！！！Error] --resume cannot be used with --infix: a skipped read's written form is not at hand", file=sys.stderr)
         raise SystemExit(2)
     if a.accuracy and a.resume:
         print("[！！！Error] --resume cannot be used with --accuracy: a skipped read's written form is not at hand", file=sys.stderr)
@@ -204,9 +226,11 @@ def get_args(argv: Optional[Sequence[str]] = None):
     if a.error_classes and not (a.truth and a.accuracy):
         print("[！！！Error] --error_classes goes with --truth and --accuracy", file=sys.stderr)
         raise SystemExit(2)
-    if a.accuracy and a.accuracy_max_len < 0:
+    if (a.accuracy or a.infix) and a.accuracy_max_len < 0:
         print("[！！！Error] --accuracy_max_len must be 0 or more", file=sys.stderr)
         raise SystemExit(2)
+    if a.infix:                           # a packed cell of the infix recurrence holds lengths up to NRV_INFIX_MAX_LEN
+        a.accuracy_max_len = min(a.accuracy_max_len, hs.INFIX_MAX_LEN)
     if a.trim_q is None and os.environ.get("NRV_TRIM_Q", "").strip():
         try:
             a.trim_q = int(os.environ["NRV_TRIM_Q"].strip())
@@ -1060,6 +1084,50 @@ def error_class_fields(v, rates: bool = False) -> List[str]:
     return out + (tail if rates else [])
 
 
+INFIX_HEADER = ("name\tstatus\ttruth_len\tstrand\tlen_in\tdist_in\tmatch_in\tstart_in\tend_in\tid_in"
+                "\tlen_out\tdist_out\tmatch_out\tstart_out\tend_out\tid_out")
+INFIX_PART_COLS = 21                       # a part line's integers: truth_len, strands, len_in, len_out, the block's columns 2 .. 17, flag
+
+
+def infix_rows(T, bases, ev_len, a1, a2, truth, truth_off, strands=2):
+    """--infix on the host: `hoststage.read_infix` on calls the host holds, as `accuracy_rows`.
+    (uint64[len(ev_len)][18], the lengths of the revised reads)."""
+    b = hostlib.bases_u8(bases)
+    seq, _, off = hs.emit_calls(b, ev_len, a1, a2, None, T)
+    return hs.read_infix(b, ev_len, seq, off, truth, truth_off, strands), np.diff(off)
+
+
+def infix_identity(match: int, dist: int) -> str:
+    """match / (match + dist) with six decimals - matched columns over alignment columns -, `.` when there is no column: THE
+    identity of the --infix file, formed from the integers on every route."""
+    return f"{int(match) / (int(match) + int(dist)):.6f}" if int(match) + int(dist) > 0 else "."
+
+
+def infix_fields(v) -> List[str]:
+    """The fields of an --infix line behind name and status from a part line's integers: THE place where the strand is picked
+    (`hoststage.pick_strand`: - exactly when the ORIGINAL read fits the reverse strand strictly better; both forms are then
+    reported on it) and where start / end of the reverse strand become 0-based half-open positions on the region AS GIVEN
+    (m - end, m - start)."""
+    v = [int(x) for x in v[:INFIX_PART_COLS]]
+    m, strands, len_in, len_out, flag = v[0], v[1], v[2], v[3], v[-1]
+    if flag != ACC_WITH_TRUTH:
+        return ["0"] + ["."] * 13
+    strand = hs.pick_strand([m, strands] + v[4:20])
+    out = [str(m), strand]
+    for n, g in ((len_in, 4), (len_out, 12)):
+        d, M, st, en = v[g + 4:g + 8] if strand == "-" else v[g:g + 4]
+        if strand == "-":
+            st, en = m - en, m - st
+        out += [str(n), str(d), str(M), str(st), str(en), infix_identity(M, d)]
+    return out
+
+
+def infix_sums(v) -> List[int]:
+    """What #total adds up of a read with a truth: truth_len, then len, dist, match of both forms on the strand reported."""
+    f = infix_fields(v)
+    return [int(f[k]) for k in (0, 2, 3, 4, 8, 9, 10)]
+
+
 def unrevised_profile(seq) -> np.ndarray:
     """The profile row of a read written unrevised: the base counts of the sequence that was written (str or bytes), no histogram."""
     row = np.zeros(hs.PROFILE_COLS, np.uint64)
@@ -1217,6 +1285,7 @@ class AccuracyPart(ReportPart):
         super().__init__(path, ACCURACY_PART_COLS)
         self.truths, self.max_len, self.log, self.warned = truths or {}, int(max_len), log, False
         self.classes = None                           # the parent's --error_classes part rides along (`write_originals`, `finish_split_reads`)
+        self.infix = None                             # ... and its --infix part (this part may then have no path: --infix without --accuracy)
 
     def block(self, fns, lens_in):
         """The truth set of a device call: (truth uint8[], truth_off int64[R + 1], flags).  A read without a record, or whose
@@ -1310,6 +1379,66 @@ class ErrclassPart(AccuracyPart):
         self.add(fn, False, [int(toff[1]), len(text), d, M, len(text), d, M, flag])
 
 
+class InfixPart(AccuracyPart):
+    """One process' share of the --infix file: an `AccuracyPart` - the same truth set (every truth a REGION here), the same
+    --accuracy_max_len, the same flags - whose lines carry the infix block's sixteen figures of a read."""
+
+    def __init__(self, path: Optional[str], truths: Optional[dict], max_len: int = 65536, strands: int = 2, log: Callable[[str], None] = print):
+        ReportPart.__init__(self, path, INFIX_PART_COLS)
+        self.truths, self.max_len, self.log, self.warned, self.classes, self.infix = truths or {}, int(max_len), log, False, None, None
+        self.strands = int(strands)
+
+    @staticmethod
+    def rows(blk, lens_in, lens_out, flags):
+        """A part line's integers per read from an infix block (hoststage.read_infix's or the device's)."""
+        return [[int(e[0]), int(e[1]), int(n), int(k)] + [int(x) for x in e[2:18]] + [f] if f == ACC_WITH_TRUTH
+                else [0, 0, int(n), int(k)] + [0] * 16 + [f]
+                for e, n, k, f in zip(np.asarray(blk).tolist(), lens_in, lens_out, flags)]
+
+    def host_rows(self, T, fns, bases, ev_len, a1, a2):
+        if not self.warned:
+            self.warned = True
+            self.log("[！！！Warning] --infix: the reads are placed in their truth regions by the host stage, about 2 s per read "
+                     "(--device_merge places them on the GPU)")
+        truth, toff, flags = self.block(fns, ev_len)
+        blk, lens_out = infix_rows(T, bases, ev_len, a1, a2, truth, toff, self.strands)
+        return self.rows(blk, ev_len, lens_out, flags)
+
+    def add_unrevised(self, fn: str, text):
+        """A read written unrevised (text: what was written, str or bytes): out = in, the figures of what was written."""
+        if self.path is None:
+            return
+        text = text.encode("ascii", "replace") if isinstance(text, str) else bytes(text)
+        truth, toff, (flag,) = self.block([fn], [len(text)])
+        g = [0] * 8
+        if flag == ACC_WITH_TRUTH:
+            g = [int(x) for rev in range(self.strands) for x in hs.infix_classes(truth, text, bool(rev))] + [0] * (4 * (2 - self.strands))
+        self.add(fn, False, [int(toff[1]), self.strands if flag == ACC_WITH_TRUTH else 0, len(text), len(text)] + g + g + [flag])
+
+
+def merge_infix(path: str, names: Sequence[str], log: Callable[[str], None] = print):
+    """Parent side of --infix: the parts as `merge_report` reads them, one line per read of `names` sorted by file name, then
+    #total - over the reads WITH a truth, revised or not, the sums of truth_len and of len, dist and match of both forms (`.` in
+    the columns of strand, start and end, which do not add up) and the pooled identities sum(match) / (sum(match) + sum(dist)) -
+    and #reads with_truth / no_truth / too_long; the file appears by rename and the parts are removed."""
+    rows, parts = _part_rows(path, INFIX_PART_COLS)
+    out, t, counts = [INFIX_HEADER], [0] * 7, [0, 0, 0]
+    for fn in sorted(names):
+        c = rows.get(fn)
+        if c is None:
+            log(f"[！！！Warning] --infix: no record for {fn}")
+            c = [fn, "unrevised"] + ["0"] * (INFIX_PART_COLS - 1) + [str(ACC_NO_TRUTH)]
+        v = [int(x) for x in c[2:]]
+        out.append("\t".join(c[:2] + infix_fields(v)))
+        counts[v[-1]] += 1
+        if v[-1] == ACC_WITH_TRUTH:
+            t = [a + b for a, b in zip(t, infix_sums(v))]
+    out.append("\t".join(["#total", "with_truth", str(t[0]), ".", str(t[1]), str(t[2]), str(t[3]), ".", ".", infix_identity(t[3], t[2]),
+                          str(t[4]), str(t[5]), str(t[6]), ".", ".", infix_identity(t[6], t[5])]))
+    out.append("#reads\t" + "\t".join(str(x) for x in counts))
+    _replace_report(path, out, parts)
+
+
 def merge_error_classes(path: str, names: Sequence[str], log: Callable[[str], None] = print):
     """Parent side of --error_classes: the parts as `merge_report` reads them, one line per read of `names` sorted by file name,
     then #total - the sums over the reads WITH a truth, revised or not, and the pooled rates count / sum(truth_len) - and #reads
@@ -1365,9 +1494,9 @@ def write_edits(edits_dir: str, fast5_fn: str, edits=None, want_qual: bool = Fal
 
 def _host_merge_form(packed):
     """A `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` /
-    `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` tuple back in the form whose call returns (p1, p2, a1, a2): for the paths that
+    `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` / `with_device_infix` tuple back in the form whose call returns (p1, p2, a1, a2): for the paths that
     keep the host merge."""
-    if packed is None or len(packed) not in (12, 14, 16, 20, 22, 27, 30, 31):
+    if packed is None or len(packed) not in (12, 14, 16, 20, 22, 27, 30, 31, 33):
         return packed
     return tuple(packed[:7]) if packed[7] is None else tuple(packed[:9])
 
@@ -1383,12 +1512,12 @@ def _bundle_has_bases(bundle) -> bool:
 
 
 def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, report, edits=False, combined=False, summary=False,
-                 trim=False, accuracy=False, error_classes=False):
+                 trim=False, accuracy=False, error_classes=False, infix=False):
     """The one decision about a batch: (packed form `_FileRun.submit` builds, route `_FileRun.run_batch` takes).  Pure: it looks at what
     the engine object offers, at the bundle (None: reads that arrived one by one) and at the run's switches - pipelined (one
     engine, NRV_CLI_PIPELINE != 0), native_pool (libnanorev_host.so driven from the thread pool), device_merge (--device_merge
     and what it needs: pipelined, native_pool, nrvh_write_records), report (--report), edits (--edits), combined (--combined),
-    summary (--summary), trim (--trim_q), accuracy (--truth / --accuracy), error_classes (--error_classes).  "bases":
+    summary (--summary), trim (--trim_q), accuracy (--truth / --accuracy), error_classes (--error_classes), infix (--infix).  "bases":
     `_bundle_has_bases`.  A form is
     the length of the packed tuple (engine.Reviser), None, or "host-merge": the merge form built and taken back.
 
@@ -1413,6 +1542,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
       yes     + accuracy on, such a form, no with_device_accuracy            host-merge [2]  by the last three rows
       yes     + error_classes on, form 30 above, with_device_error_classes   31 [10]         by the last three rows
       yes     + error_classes on, form 30 above, no with_device_error_classes  host-merge [2]  by the last three rows
+      yes     + infix on, a form 12 ... 31 above, with_device_accuracy + _infix  33 [11]         by the last three rows
+      yes     + infix on, such a form, one of the two missing                host-merge [2]  by the last three rows
       yes     any form; pipelined, native_pool, begin_packed_raw, bases                      pipelined [3]
       yes     any form; native_pool, bases, not (pipelined, begin_packed_raw)                packed+finish_bundle
       yes     any form; no native_pool, or no bases                                          packed sliced
@@ -1436,7 +1567,10 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
     [10] the one call is the form 30 call with the error-class block behind the accuracy block: per read the edits and the matched
         columns of the original and of the (untrimmed) revised read against its truth.  Every other route computes the rows on
         the host (`error_class_rows`) - an engine without the call too: a form 30 call need not hand the merged characters back,
-        so the route is the one the accuracy takes without ITS call."""
+        so the route is the one the accuracy takes without ITS call.
+    [11] the one call is the form 30 / 31 call - without --accuracy a form 30 call whose accuracy block nobody reads - with the
+        infix block last: per read where the original and the (untrimmed) revised read lie in the truth region, per strand.
+        Every other route computes the rows on the host (`infix_rows`)."""
     unpacked = "per-read" if n_reads == 1 else "predict_many"
     if bundle is None:
         return (7 if n_reads > 1 and hasattr(rv, "pack_reads_raw") else None), unpacked
@@ -1458,6 +1592,11 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
             form = 30 if hasattr(rv, "with_device_accuracy") else "host-merge"
         if error_classes and form == 30:
             form = 31 if hasattr(rv, "with_device_error_classes") else "host-merge"
+        if infix and form != "host-merge":
+            if form not in (30, 31):
+                form = 30 if hasattr(rv, "with_device_accuracy") else "host-merge"
+            if form != "host-merge":
+                form = 33 if hasattr(rv, "with_device_infix") else "host-merge"
     if not (native_pool and bases):
         return form, "packed sliced"
     return form, ("pipelined" if pipelined and hasattr(rv, "begin_packed_raw") else "packed+finish_bundle")
@@ -1566,7 +1705,7 @@ class _FileRun:
     `_route_batch` says (`submit`) and collects the pooled finishers; the ENGINE thread(s) make the calls (`run_batch`, `collect`);
     the one FINISHER thread merges, reports and writes, or hands that to the parser pool (`finish_batch`, `finish_call`)."""
     def __init__(self, stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part=None,
-                 summary_part=None, trim_part=None, accuracy_part=None, errclass_part=None):
+                 summary_part=None, trim_part=None, accuracy_part=None, errclass_part=None, infix_part=None):
         self.args, self.log, self.note = args, log, on_file or (lambda fn, ok: None)
         self.stats = {"reads": 0, "bases": 0, "failed": [], "host_s": 0.0, "engine_s": 0.0}
         self.stats_lock = threading.Lock()
@@ -1578,12 +1717,16 @@ class _FileRun:
         self.trim_rows = {}                           # applied by `deliver`; fn -> (bases of the untrimmed read, (lo, hi))
         self.trimpart = ReportPart(trim_part if self.trim else None, 4)
         # --truth / --accuracy: the rows are stashed like a report row; every process loads the truth set itself
-        self.accpart = AccuracyPart(accuracy_part, load_truth(args.truth) if accuracy_part else None,
+        self.accpart = AccuracyPart(accuracy_part, load_truth(args.truth) if accuracy_part or infix_part else None,
                                     getattr(args, "accuracy_max_len", 65536), log)
         self.acc_rows = {}
         # --error_classes: its own part next to the accuracy's, on the truth set that one loaded
         self.eclpart = ErrclassPart(errclass_part if accuracy_part else None, self.accpart.truths, self.accpart.max_len, log)
         self.ecl_rows = {}
+        # --infix: a part of its own on the same truth set, with or without --accuracy
+        self.infpart = InfixPart(infix_part, self.accpart.truths, self.accpart.max_len,
+                                 1 if getattr(args, "infix_strand", "both") == "forward" else 2, log)
+        self.inf_rows = {}
         self.acc_flags = {}                           # id(batch) -> the flags of a form 30 call's truth block, until its call is back
         self.tie_eps = float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS))
         self.edits_dir = getattr(args, "edits", None) # --edits: every read's list is written BEFORE its output is
@@ -1696,6 +1839,7 @@ class _FileRun:
         self.trimpart.close()
         self.accpart.close()
         self.eclpart.close()
+        self.infpart.close()
         if self.sink is not None:
             self.sink.close()
         self.trace.log_summary(self.log, len(self.engines))
@@ -1761,6 +1905,8 @@ class _FileRun:
         self.accpart.add_unrevised(fn, text)
         self.ecl_rows.pop(fn, None)
         self.eclpart.add_unrevised(fn, text)
+        self.inf_rows.pop(fn, None)
+        self.infpart.add_unrevised(fn, text)
         self.note(fn, False)
 
     def finished(self, fn, nb):
@@ -1785,6 +1931,11 @@ class _FileRun:
             if row is None:                           # cannot happen, as above
                 self.log(f"[！！！Warning] --error_classes: no counts for {fn}")
             self.eclpart.add(fn, row is not None, row if row is not None else [0, nb, 0, 0, nb, 0, 0, ACC_NO_TRUTH])
+        if self.infpart:
+            row = self.inf_rows.pop(fn, None)
+            if row is None:                           # cannot happen, as above
+                self.log(f"[！！！Warning] --infix: no figures for {fn}")
+            self.infpart.add(fn, row is not None, row if row is not None else [0, 0, nb, nb] + [0] * 16 + [ACC_NO_TRUTH])
         if self.trim:
             row = self.trim_rows.pop(fn, None)
             log_row = trim_log_row(row[0], row[1], self.trim[2]) if row is not None else unrevised_trim(nb)
@@ -1810,7 +1961,8 @@ class _FileRun:
                 bundle = _bundle_host_stats(bundle)   # an engine without the new calls: the host computes them after all
             form, route = _route_batch(rv, bundle, len(batch), self.pipelined, self.native_pool, self.device_merge, bool(self.report),
                                        edits=bool(self.edits_dir), combined=self.sink is not None, summary=bool(self.sumpart),
-                                       trim=self.trim is not None, accuracy=bool(self.accpart), error_classes=bool(self.eclpart))
+                                       trim=self.trim is not None, accuracy=bool(self.accpart), error_classes=bool(self.eclpart),
+                                       infix=bool(self.infpart))
             if form is not None and bundle is None:
                 packed = prepare_many(cls, [rt for _, rt, _ in batch], rv.T)
             elif form is not None:
@@ -1822,6 +1974,7 @@ class _FileRun:
                     if form == "host-merge":
                         packed = _host_merge_form(packed)
                     elif form != len(packed):
+                        infix, form = form == 33, (31 if form == 33 and self.eclpart else 30 if form == 33 else form)   # --infix: form 30 / 31 with one block more
                         classes, form = form == 31, (30 if form == 31 else form)   # --error_classes: form 30 with one block more
                         if self.report:
                             packed = cls.with_device_report(packed, self.tie_eps)
@@ -1841,6 +1994,8 @@ class _FileRun:
                             self.acc_flags[id(batch)] = flags
                             if classes:               # --error_classes: behind the accuracy, on the same truth block
                                 packed = cls.with_device_error_classes(packed)
+                            if infix:                 # --infix: last, on the same truth block
+                                packed = cls.with_device_infix(packed, self.infpart.strands)
         except Exception:
             packed = None
         if packed is None:
@@ -1890,6 +2045,8 @@ class _FileRun:
                     self.acc_rows[fn] = self.accpart.host_rows(T, [fn], rt.bases, [len(np.asarray(rt.bases))], c[2], c[3])[0]
                 if self.eclpart:
                     self.ecl_rows[fn] = self.eclpart.host_rows(T, [fn], rt.bases, [len(np.asarray(rt.bases))], c[2], c[3])[0]
+                if self.infpart:
+                    self.inf_rows[fn] = self.infpart.host_rows(T, [fn], rt.bases, [len(np.asarray(rt.bases))], c[2], c[3])[0]
                 if self.edits_dir:
                     write_edits(self.edits_dir, fn, edit_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual)[0], self.want_qual)
                 if self.pool is not None or self.sink is not None:
@@ -1919,6 +2076,11 @@ class _FileRun:
             trim = None
             flags = self.acc_flags.pop(id(batch), None)
             if merged:
+                if len(outs) == 13:                   # a `with_device_infix` call: (..., accuracy, error classes | None, infix)
+                    if self.infpart and flags is not None:
+                        ev_len = bundle["meta"][:, 1].astype(np.int64)
+                        self.inf_rows.update(zip(fns, self.infpart.rows(outs[12], ev_len.tolist(), np.diff(outs[2]).tolist(), flags)))
+                    outs = outs[:12] if outs[11] is not None else outs[:11]
                 if len(outs) == 12:                   # a `with_device_error_classes` call: the counts were found behind the distances, last output
                     if self.eclpart and flags is not None:
                         ev_len = bundle["meta"][:, 1].astype(np.int64)
@@ -1959,6 +2121,8 @@ class _FileRun:
                     self.acc_rows.update(zip(fns, self.accpart.host_rows(T, fns, bundle["bases"], ev_len.tolist(), a1, a2)))
                 if self.eclpart:
                     self.ecl_rows.update(zip(fns, self.eclpart.host_rows(T, fns, bundle["bases"], ev_len.tolist(), a1, a2)))
+                if self.infpart:
+                    self.inf_rows.update(zip(fns, self.infpart.host_rows(T, fns, bundle["bases"], ev_len.tolist(), a1, a2)))
                 if self.edits_dir:
                     self.write_call_edits(fns, *edit_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2, self.want_qual))
                 qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
@@ -2057,7 +2221,7 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                   on_file: Optional[Callable[[str, bool], None]] = None, gpu_workers: int = 1,
                   core_share: Optional[int] = None, report_part: Optional[str] = None, combined_part: Optional[str] = None,
                   summary_part: Optional[str] = None, trim_part: Optional[str] = None, accuracy_part: Optional[str] = None,
-                  errclass_part: Optional[str] = None) -> dict:
+                  errclass_part: Optional[str] = None, infix_part: Optional[str] = None) -> dict:
     """Revise `files` (names inside args.fast5_base_dir) with one engine.  The host stage (HDF5 parsing, event collapse,
     statistics) runs --thread parser workers that stay a bounded number of reads ahead of the device: THREADS of this process
     inside libnanorev_host.so (at most kNativePoolMax), or PROCESSES on the Python host stage without it / with NRV_HOST_THREADS=0.
@@ -2070,10 +2234,11 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
     one line per read to, ahead of on_file (`ReportPart`).  combined_part (--combined): the part this call appends
     every read's record to INSTEAD of writing one file per read (`CombinedPart`, `deliver`).  summary_part (--summary): as
     report_part, for the summary's lines.  trim_part (--trim_log): as report_part, for the trim log's lines.  accuracy_part
-    (--accuracy): as report_part, for the accuracy file's lines.  errclass_part (--error_classes): as accuracy_part, for that file's."""
+    (--accuracy): as report_part, for the accuracy file's lines.  errclass_part (--error_classes): as accuracy_part, for that file's.  infix_part
+    (--infix): the same for the infix file's."""
     import contextlib
     with contextlib.ExitStack() as stack:             # its exit ends the run's threads and undoes what `_FileRun._start` did
-        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part, summary_part, trim_part, accuracy_part, errclass_part)
+        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part, summary_part, trim_part, accuracy_part, errclass_part, infix_part)
         batch, nev = [], 0                            # unbundled reads are grouped into device calls of >= batch_events events
         for entries, bundle in run.results():
             bundled = []
@@ -2088,6 +2253,7 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                     run.trimpart.add(fn, False, unrevised_trim(0))
                     run.accpart.add_unrevised(fn, b"")
                     run.eclpart.add_unrevised(fn, b"")
+                    run.infpart.add_unrevised(fn, b"")
                     run.note(fn, False)
                 elif err is not None:
                     run.fallback(fn, rt, fq, err)
@@ -2352,7 +2518,8 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
                            summary_part=report_part_path(args.summary, rank) if getattr(args, "summary", None) else None,
                            trim_part=report_part_path(args.trim_log, rank) if getattr(args, "trim_log", None) else None,
                            accuracy_part=report_part_path(args.accuracy, rank) if getattr(args, "accuracy", None) else None,
-                           errclass_part=report_part_path(args.error_classes, rank) if getattr(args, "error_classes", None) else None)
+                           errclass_part=report_part_path(args.error_classes, rank) if getattr(args, "error_classes", None) else None,
+                           infix_part=report_part_path(args.infix, rank) if getattr(args, "infix", None) else None)
         st["cpus"] = len(cpus) if cpus else 0
         for e in made:
             e.close()
@@ -2395,6 +2562,8 @@ def write_originals(args, files: Sequence[str], log: Callable[[str], None], repo
             accuracy.add_unrevised(fn, text)
             if accuracy.classes is not None:
                 accuracy.classes.add_unrevised(fn, text)
+            if accuracy.infix is not None:
+                accuracy.infix.add_unrevised(fn, text)
     return done
 
 
@@ -2453,6 +2622,8 @@ def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[st
                     accuracy.add(fn, True, accuracy.host_rows(T, [fn], pl[0]["bases"], [N], a1, a2)[0])
                     if accuracy.classes is not None:
                         accuracy.classes.add(fn, True, accuracy.classes.host_rows(T, [fn], pl[0]["bases"], [N], a1, a2)[0])
+                if accuracy is not None and accuracy.infix is not None:
+                    accuracy.infix.add(fn, True, accuracy.infix.host_rows(T, [fn], pl[0]["bases"], [N], a1, a2)[0])
                 if summary is not None and summary and have_p:
                     summary.add(fn, True, profile_rows(T, pl[0]["bases"], [N], np.concatenate([p["p1"] for p in pl]),
                                                        np.concatenate([p["p2"] for p in pl]), a1, a2)[0])
@@ -2555,18 +2726,19 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
     parent_trim = ReportPart(report_part_path(trim_log, "parent") if trim_log else None, 4)
     trim_part0 = report_part_path(trim_log, 0) if trim_log else None
     parent_acc, acc_part0 = None, None
-    if args.accuracy:                     # --accuracy: parts and a parent-side merge as for --report; the truth set is checked here
+    if args.accuracy or args.infix:       # --accuracy (--infix without it: a part without a path): parts and a parent-side merge as for --report; the truth set is checked here
         try:
             truths = load_truth(args.truth)
         except (OSError, ValueError) as e:
             print(f"[！！！Error] {e}", file=sys.stderr)
             return 2
-        clear_report_parts(args.accuracy)
-        d = os.path.dirname(args.accuracy)
-        if d:
-            os.makedirs(d, exist_ok=True)
-        parent_acc = AccuracyPart(report_part_path(args.accuracy, "parent"), truths, args.accuracy_max_len)
-        acc_part0 = report_part_path(args.accuracy, 0)
+        if args.accuracy:
+            clear_report_parts(args.accuracy)
+            d = os.path.dirname(args.accuracy)
+            if d:
+                os.makedirs(d, exist_ok=True)
+            acc_part0 = report_part_path(args.accuracy, 0)
+        parent_acc = AccuracyPart(report_part_path(args.accuracy, "parent") if args.accuracy else None, truths, args.accuracy_max_len)
     ecl_part0 = None
     if args.error_classes:                # --error_classes: the same again, on the truth set just loaded
         clear_report_parts(args.error_classes)
@@ -2575,6 +2747,15 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
             os.makedirs(d, exist_ok=True)
         parent_acc.classes = ErrclassPart(report_part_path(args.error_classes, "parent"), truths, args.accuracy_max_len)
         ecl_part0 = report_part_path(args.error_classes, 0)
+    inf_part0 = None
+    if args.infix:                        # --infix: the same again
+        clear_report_parts(args.infix)
+        d = os.path.dirname(args.infix)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        parent_acc.infix = InfixPart(report_part_path(args.infix, "parent"), truths, args.accuracy_max_len,
+                                     1 if args.infix_strand == "forward" else 2)
+        inf_part0 = report_part_path(args.infix, 0)
     if args.combined:                     # --combined: a part per process too, `merge_combined` ends the run
         clear_combined_parts(args.combined)
     parent_sink = CombinedPart(combined_part_path(args.combined, "parent"), args.output_format == "fastq") if args.combined else None
@@ -2614,7 +2795,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
     if reviser_factory is not None:       # in-process (tests / embedding): one engine, no sharding
         rv = reviser_factory(args, 0)
         stats = [process_files(args, names, rv, print, report_part=report_part_path(args.report, 0) if args.report else None,
-                               combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0, errclass_part=ecl_part0)]
+                               combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0, errclass_part=ecl_part0, infix_part=inf_part0)]
     else:
         # the command line needs no torch: without it a process starts ~1.5 s sooner.  (engine.py imports
         # torch first only so that a LATER torch import in the same process finds one HIP runtime.)
@@ -2643,7 +2824,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
                 made.append((worker_factory or _default_factory)(args, 0))
                 return made[-1]                       # called once per engine (process_files: NRV_CLI_ENGINES)
             stats = [process_files(args, names, make, print, report_part=report_part_path(args.report, 0) if args.report else None,
-                                   combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0, errclass_part=ecl_part0)]
+                                   combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0, errclass_part=ecl_part0, infix_part=inf_part0)]
             for rv in made:
                 rv.close()
         else:
@@ -2679,7 +2860,11 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
         merge_report(trim_log, all_names, table=TRIM_TABLE)
     if parent_acc is not None:
         parent_acc.close()
-        merge_accuracy(args.accuracy, all_names)
+        if args.accuracy:
+            merge_accuracy(args.accuracy, all_names)
+        if parent_acc.infix is not None:
+            parent_acc.infix.close()
+            merge_infix(args.infix, all_names)
         if parent_acc.classes is not None:
             parent_acc.classes.close()
             merge_error_classes(args.error_classes, all_names)

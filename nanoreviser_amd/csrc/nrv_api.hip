@@ -479,10 +479,11 @@ struct DevModel {
 // ---- a merged raw-read call (nrv_revise_reads_raw*_begin; nrv_merge_calls* is its test twin) -------------------------------
 // The merged block of a call of N events, n windows, n_reads reads - offsets into one device allocation:
 //   [off i64 x (n_reads + 1) | seq | qual | report u64 x n_reads x 24 | edit_off i64 x (n_reads + 1) | rec_off i64 x (n_reads + 1) |
-//    profile u64 x n_reads x 48 | trim i64 x n_reads x 2 | accu u64 x n_reads x 4 | ecls u64 x n_reads x 6]
+//    profile u64 x n_reads x 48 | trim i64 x n_reads x 2 | accu u64 x n_reads x 4 | ecls u64 x n_reads x 6 |
+//    infx u64 x n_reads x 18]
 //                                     what comes back in one copy of `dl` bytes, mirrored in page-locked memory (nrv_merge.h,
-//                                     nrv_report.h, nrv_edits.h, nrv_pack.h, nrv_profile.h, nrv_trim.h, nrv_align.h, nrv_errclass.h); the report,
-//                                     edit_off, rec_off, the profile, the trim, the accuracy and the error classes only where asked for - without
+//                                     nrv_report.h, nrv_edits.h, nrv_pack.h, nrv_profile.h, nrv_trim.h, nrv_align.h, nrv_errclass.h, nrv_infix.h); the report,
+//                                     edit_off, rec_off, the profile, the trim, the accuracy, the error classes and the infix block only where asked for - without
 //                                     them the layout is the merge's own.  A records call that hands back neither seq nor qual leaves those two on
 //                                     the device
 //   [rec u32 x N | tile u64]          the merge kernels' scratch
@@ -496,8 +497,9 @@ struct DevModel {
 //                                     reads; only where asked for
 //   [hc8 i64 x N | hc8 i64 x (N + n)] the error classes' stripe carries, one packed cell per character of the original and of the
 //                                     revised reads; only where asked for
+//   [hci i64 x N x 2 | hci i64 x (N + n) x 2]  the infix block's stripe carries, the same per strand; only where asked for
 // Every part is 256-byte aligned.
-struct MergeLayout { size_t seq, qual, rep, eoff, roff, prof, trim, rec, tile, edits, etile, blob, tq, acc, dl, bytes, accu, hc, ecls, hc8; };
+struct MergeLayout { size_t seq, qual, rep, eoff, roff, prof, trim, rec, tile, edits, etile, blob, tq, acc, dl, bytes, accu, hc, ecls, hc8, infx, hci; };
 
 // What a merged call reads besides the raw reads.  Consumed inside _begin: the caller's pointers are dead once it returns, so
 // nothing that outlives _begin keeps one (the slot keeps the VALUES of both threshold sets for the re-run of nrv_reads_raw_end)
@@ -530,7 +532,9 @@ struct MergeOut {
   int64_t* trim = nullptr;              // [n_reads][2]
   uint64_t* accuracy = nullptr;         // [n_reads][4]
   uint64_t* errclass = nullptr;         // [n_reads][6]
-  bool wants_truth() const { return accuracy != nullptr || errclass != nullptr; }
+  uint64_t* infix = nullptr;            // [n_reads][18]
+  int strands = 2;                      // of the infix block: 1 (forward) or 2
+  bool wants_truth() const { return accuracy != nullptr || errclass != nullptr || infix != nullptr; }
 };
 // Where a merged call's inputs lie on the device, and its merged block
 struct MergeView {
@@ -1623,6 +1627,7 @@ static int merged_collect(nrv_handle* h, const char* who, const char* who_edits,
   if (o.trim) memcpy(o.trim, head + m.trim, (size_t)v.n_reads * 16);
   if (o.accuracy) memcpy(o.accuracy, head + m.accu, (size_t)v.n_reads * kAccuracyCols * 8);
   if (o.errclass) memcpy(o.errclass, head + m.ecls, (size_t)v.n_reads * kErrclassCols * 8);
+  if (o.infix) memcpy(o.infix, head + m.infx, (size_t)v.n_reads * kInfixCols * 8);
   int rc = NRV_OK;
   if (o.edit_off) {
     const int64_t n_ed = ((const int64_t*)(head + m.eoff))[v.n_reads];
@@ -2151,6 +2156,23 @@ static int errclass_enqueue(nrv_handle* h, const ErrclassArgs& a) {
   HIPCHK(h, hipGetLastError());
   return NRV_OK;
 }
+// infix_kernel (nrv_infix.h): one wave per (read, kind, strand) triple; every word of its result is stored plainly
+static int infix_enqueue(nrv_handle* h, const InfixArgs& a) {
+  if (a.n_reads <= 0) return NRV_OK;
+  hipLaunchKernelGGL(infix_kernel, dim3((unsigned)a.n_reads * (unsigned)(a.kinds * a.strands)), dim3(64), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return NRV_OK;
+}
+// the lengths of an infix call: no sequence (region, or - lens given - read that has a region) above NRV_INFIX_MAX_LEN
+static bool infix_lengths_ok(const int64_t* truth_off, int n, const int64_t* len_off = nullptr, const nrv_read_desc* reads = nullptr) {
+  for (int r = 0; r < n; ++r) {
+    const int64_t m = truth_off[r + 1] - truth_off[r];
+    if (m > NRV_INFIX_MAX_LEN) return false;
+    if (m > 0 && len_off && len_off[r + 1] - len_off[r] > NRV_INFIX_MAX_LEN) return false;
+    if (m > 0 && reads && reads[r].ev_len > NRV_INFIX_MAX_LEN) return false;
+  }
+  return true;
+}
 // a truth set: offsets that ascend from 0, bytes where there are any, and no sequence of 2^31 - 64 characters or more
 static bool truth_ok(const uint8_t* truth, const int64_t* truth_off, int n_reads) {
   if (!truth_off || truth_off[0] != 0) return false;
@@ -2212,7 +2234,8 @@ static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, const MergeOu
   m.trim = m.prof + (o.profile ? up((size_t)n_reads * kProfileCols * 8) : 0);
   m.accu = m.trim + (o.trim ? up((size_t)n_reads * 16) : 0);
   m.ecls = m.accu + (o.accuracy ? up((size_t)n_reads * kAccuracyCols * 8) : 0);
-  m.dl = m.ecls + (o.errclass ? up((size_t)n_reads * kErrclassCols * 8) : 0);
+  m.infx = m.ecls + (o.errclass ? up((size_t)n_reads * kErrclassCols * 8) : 0);
+  m.dl = m.infx + (o.infix ? up((size_t)n_reads * kInfixCols * 8) : 0);
   m.rec = m.dl;
   m.tile = m.rec + up((size_t)N * 4);
   m.edits = m.tile + up(tiles * 8);
@@ -2222,7 +2245,8 @@ static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, const MergeOu
   m.acc = m.tq + (o.trim ? up(cap) : 0);
   m.hc = m.acc + (o.trim ? up((size_t)n_reads * 16) : 0);
   m.hc8 = m.hc + (o.accuracy ? up((size_t)N) + up(cap) : 0);
-  m.bytes = m.hc8 + (o.errclass ? up((size_t)N * 8) + up(cap * 8) : 0);
+  m.hci = m.hc8 + (o.errclass ? up((size_t)N * 8) + up(cap * 8) : 0);
+  m.bytes = m.hci + (o.infix ? 2 * up((size_t)N * 8) + 2 * up(cap * 8) : 0);
   return m;
 }
 // No window at all (N <= T): the reads come back as they are, on the host
@@ -2327,6 +2351,44 @@ static void errclass_nothing(const uint8_t* bases, const nrv_read_desc* reads, i
     row[3] = row[1]; row[4] = row[2];
   }
 }
+// hoststage.infix_classes by two rows of the table of packed cells d 2^42 - M 2^21 - start, on the host: the calls without a window
+static void infix_classes_host(const uint8_t* t, int64_t m, const uint8_t* s, int64_t n, bool rev, uint64_t* out4) {
+  std::vector<int64_t> row((size_t)n + 1);
+  for (int64_t j = 0; j <= n; ++j) row[(size_t)j] = j * kInfixEdit;
+  int64_t best = row[(size_t)n], best_i = 0;
+  for (int64_t i = 1; i <= m; ++i) {
+    int64_t diag = row[0];
+    row[0] = -i;
+    uint8_t c = t[rev ? m - i : i - 1];
+    if (rev) c = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 0;
+    const bool base = c == 'A' || c == 'C' || c == 'G' || c == 'T';
+    for (int64_t j = 1; j <= n; ++j) {
+      const int64_t up_ = row[(size_t)j] + kInfixEdit, left = row[(size_t)j - 1] + kInfixEdit;
+      const int64_t dg = diag + ((base && c == s[j - 1]) ? -kInfixMatch : kInfixEdit);
+      diag = row[(size_t)j];
+      row[(size_t)j] = std::min(std::min(up_, left), dg);
+    }
+    if (row[(size_t)n] < best) { best = row[(size_t)n]; best_i = i; }
+  }
+  const int64_t d = (best + kInfixEdit - 1) >> 42, rest = d * kInfixEdit - best;
+  out4[0] = (uint64_t)d; out4[1] = (uint64_t)(rest >> 21); out4[2] = (uint64_t)(rest & kInfixMaxLen); out4[3] = (uint64_t)best_i;
+}
+// ... and its infix block (hoststage.read_infix on a call without a window): out = in
+static void infix_nothing(const uint8_t* bases, const nrv_read_desc* reads, int n_reads, const uint8_t* truth, const int64_t* truth_off,
+                          int strands, uint64_t* infix) {
+  static_assert(NRV_INFIX_COLS == kInfixCols && NRV_INFIX_MAX_LEN == kInfixMaxLen, "nanorev.h and nrv_infix.h disagree on the infix block");
+  memset(infix, 0, (size_t)n_reads * kInfixCols * 8);
+  for (int r = 0; r < n_reads; ++r) {
+    const int64_t m = truth_off[r + 1] - truth_off[r];
+    if (m <= 0) continue;
+    uint64_t* row = infix + (size_t)r * kInfixCols;
+    row[0] = (uint64_t)m; row[1] = (uint64_t)strands;
+    for (int rev = 0; rev < strands; ++rev) {
+      infix_classes_host(truth + truth_off[r], m, bases + reads[r].ev_off, reads[r].ev_len, rev != 0, row + 2 + 4 * rev);
+      memcpy(row + 10 + 4 * rev, row + 2 + 4 * rev, 32);
+    }
+  }
+}
 // ... and everything a merged call asks for, for both callers that can meet N <= T
 static void merged_nothing(const MergeIn& in, const MergeOut& o, const nrv_read_desc* reads, int n_reads, int64_t N) {
   merge_nothing(in.bases, reads, n_reads, N, o.seq, in.q_thr ? o.qual : nullptr, o.off);
@@ -2338,6 +2400,7 @@ static void merged_nothing(const MergeIn& in, const MergeOut& o, const nrv_read_
   if (o.profile) profile_nothing(in.bases, reads, n_reads, o.profile);
   if (o.accuracy) accuracy_nothing(in.bases, reads, n_reads, in.truth, in.truth_off, o.accuracy);
   if (o.errclass) errclass_nothing(in.bases, reads, n_reads, in.truth, in.truth_off, o.errclass);
+  if (o.infix) infix_nothing(in.bases, reads, n_reads, in.truth, in.truth_off, o.strands, o.infix);
 }
 
 // The kernels of a merged call behind whatever produced v.a1 / a2 / p1 / p2 on the compute stream: the merge, then what `o` asks
@@ -2394,6 +2457,19 @@ static int merged_enqueue(nrv_handle* h, const MergeView& v, const MergeLayout& 
     k.hc0 = (long long*)(v.blk + m.hc8); k.hc1 = (long long*)(v.blk + m.hc8 + up((size_t)v.N * 8));
     k.ecls = (unsigned long long*)(v.blk + m.ecls); k.dist = nullptr; k.match = nullptr;
     rc = errclass_enqueue(h, k);
+  }
+  if (!rc && o.infix) {                                    // ... and LAST: the same inputs on one strand or on both, carry words per strand
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t s0 = up((size_t)v.N * 8), s1 = (m.bytes - m.hci - 2 * s0) / 2;   // (merge_layout: the block ends with them)
+    InfixArgs k;
+    k.n_reads = v.n_reads; k.kinds = 2; k.strands = o.strands; k.reverse = 0;
+    k.truth = v.truth; k.truth_off = v.truth_off;
+    k.reads = v.reads; k.bases = v.bases; k.off = a.off; k.seq = a.seq;
+    k.cap0 = v.N; k.cap1 = v.N + (v.N - h->T > 0 ? v.N - h->T : 0);
+    k.hc0 = (long long*)(v.blk + m.hci); k.hs0 = (long long)(s0 / 8);
+    k.hc1 = (long long*)(v.blk + m.hci + 2 * s0); k.hs1 = (long long)(s1 / 8);
+    k.infx = (unsigned long long*)(v.blk + m.infx); k.dist = k.match = k.start = k.end = nullptr;
+    rc = infix_enqueue(h, k);
   }
   return rc;
 }
@@ -2604,6 +2680,9 @@ static int revise_begin(nrv_handle* h, const char* who, const char* missing, con
   else if (mo.wants_truth() && (in.n_reads < 0 || !truth_ok(mr.truth, mr.truth_off, in.n_reads)))
     bad = "null truth / truth_off, offsets that do not ascend from 0, or a truth of 2^31 - 64 characters and more";
   else if (mo.wants_truth() && in.N >= ((int64_t)1 << 30)) bad = "2^30 events and more in a call with a truth";
+  else if (mo.infix && mo.strands != 1 && mo.strands != 2) bad = "strands must be 1 or 2";
+  else if (mo.infix && !infix_lengths_ok(mr.truth_off, in.n_reads, nullptr, in.reads))
+    bad = "a truth region, or a read that has one, above NRV_INFIX_MAX_LEN = 2^21 - 1 characters";
   if (h && bad) { h->err = std::string(who) + ": " + bad; return NRV_E_INVALID; }
   return raw_begin(h, in, nullptr, nullptr, nullptr, nullptr, ticket, &mr, &mo);
 }
@@ -2837,6 +2916,43 @@ int nrv_revise_reads_raw_errclass(nrv_handle* h, const int16_t* raw, int64_t n_r
   });
 }
 
+// every earlier block may be NULL, the accuracy and the error classes included: the truth is then read by the infix block alone
+int nrv_revise_reads_raw_infix_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                     const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                     const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                     uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                     nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                     uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                     const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                                     const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, uint64_t* errclass,
+                                     int strands, uint64_t* infix, int* ticket) {
+  const char* missing = nullptr;
+  if (!infix || !truth_off) missing = "null truth_off / infix";
+  else if (trim && !trim_thr) missing = "trim without trim_thr";
+  MergeOut mo{seq, qual, off, report, tie_eps, edits, edit_off, blob, rec_off, profile, trim, accuracy};
+  mo.errclass = errclass; mo.infix = infix; mo.strands = strands;
+  return revise_begin(h, "nrv_revise_reads_raw_infix_begin", missing,
+                      RawIn{raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device},
+                      MergeIn{bases, q_thr, names, name_off, prof_thr, trim_thr, Q, W, min_len, truth, truth_off}, mo, ticket);
+}
+
+int nrv_revise_reads_raw_infix(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                               const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                               const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                               uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                               nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                               uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                               const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                               const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, uint64_t* errclass,
+                               int strands, uint64_t* infix) {
+  return begin_then_end(h, [&](int* t) {
+    return nrv_revise_reads_raw_infix_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                            seq, qual, off, tie_eps, report, edits, edit_off, names, name_off, blob, rec_off,
+                                            prof_thr, profile, trim_thr, Q, W, min_len, trim, truth, truth_off, accuracy, errclass,
+                                            strands, infix, t);
+  });
+}
+
 int nrv_reads_raw_end(nrv_handle* h, int ticket) {
   int rc = check_handle(h);
   if (rc) return rc;
@@ -2965,7 +3081,7 @@ int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32
 // nrv_merge_calls (o.report == nullptr: that call, to the byte), nrv_merge_calls_report, (o.edit_off != nullptr)
 // nrv_merge_calls_edits, (o.profile != nullptr) nrv_merge_calls_profile and (o.trim != nullptr; `more`: its rule, and the names of
 // its records) nrv_merge_calls_trim, (o.accuracy != nullptr; `more`: the truth) nrv_merge_calls_accuracy and (o.errclass != nullptr;
-// `more`: the truth) nrv_merge_calls_errclass
+// `more`: the truth) nrv_merge_calls_errclass and (o.infix != nullptr; `more`: the truth) nrv_merge_calls_infix
 static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
                             const float* p1, const float* p2, int64_t n_win, const float* q_thr, const MergeOut& o,
                             const float* prof_thr = nullptr, const MergeIn& more = MergeIn{}) {
@@ -2991,12 +3107,20 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
     blob_cap = blob_capacity(N, n, n_reads, more.name_off[n_reads], q_thr != nullptr);
     if ((blob_cap > 0 && !o.blob) || blob_cap >= ((size_t)1 << 32)) { h->err = "nrv_merge_calls_trim: null blob (or records of 4 GiB and more)"; return NRV_E_INVALID; }
   }
-  const std::string who_truth = o.errclass ? "nrv_merge_calls_errclass" : "nrv_merge_calls_accuracy";
+  const std::string who_truth = o.infix ? "nrv_merge_calls_infix" : o.errclass ? "nrv_merge_calls_errclass" : "nrv_merge_calls_accuracy";
   if (o.wants_truth() && !truth_ok(more.truth, more.truth_off, n_reads)) {
     h->err = who_truth + ": null truth / truth_off, offsets that do not ascend from 0, or a truth of 2^31 - 64 characters and more";
     return NRV_E_INVALID;
   }
   if (o.wants_truth() && N >= ((int64_t)1 << 30)) { h->err = who_truth + ": 2^30 events and more"; return NRV_E_INVALID; }
+  if (o.infix) {
+    bool ok = o.strands == 1 || o.strands == 2;
+    for (int r = 0; ok && r < n_reads; ++r) {
+      const int64_t tl = more.truth_off[r + 1] - more.truth_off[r];
+      ok = tl <= NRV_INFIX_MAX_LEN && (tl == 0 || ev_len[r] <= NRV_INFIX_MAX_LEN);
+    }
+    if (!ok) { h->err = who_truth + ": strands must be 1 or 2, and no truth region or read that has one above NRV_INFIX_MAX_LEN = 2^21 - 1 characters"; return NRV_E_INVALID; }
+  }
   if (n == 0) {
     MergeIn in = more;
     in.bases = bases; in.q_thr = q_thr;
@@ -3130,6 +3254,18 @@ int nrv_merge_calls_errclass(nrv_handle* h, const uint8_t* bases, const int64_t*
   return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, o, nullptr, more);
 }
 
+int nrv_merge_calls_infix(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                          const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                          const uint8_t* truth, const int64_t* truth_off, int strands, uint64_t* infix) {
+  if (h && (!truth_off || (n_reads > 0 && !infix))) { h->err = "nrv_merge_calls_infix: null truth_off / infix"; return NRV_E_INVALID; }
+  static uint64_t none[NRV_INFIX_COLS];
+  MergeOut o{seq, qual, off};
+  o.infix = infix ? infix : none; o.strands = strands;
+  MergeIn more;
+  more.truth = truth; more.truth_off = truth_off;
+  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, o, nullptr, more);
+}
+
 int nrv_edit_distance(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
                       int64_t* dist) {
   int rc = check_handle(h);
@@ -3208,6 +3344,56 @@ int nrv_edit_classes(nrv_handle* h, const uint8_t* a, const int64_t* a_off, cons
     if ((rc2 = errclass_enqueue(h, k))) return rc2;
     HIPCHK(h, hipMemcpyAsync(dist, d + o_d, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(match, d + o_d + nd, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return NRV_OK;
+  };
+  rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  (void)hipFree(d);
+  return rc;
+}
+
+int nrv_infix_classes(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
+                      int reverse, int64_t* dist, int64_t* match, int64_t* start, int64_t* end) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (n_pairs < 0 || (n_pairs > 0 && (!dist || !match || !start || !end))) { h->err = "nrv_infix_classes: bad arguments"; return NRV_E_INVALID; }
+  if (reverse != 0 && reverse != 1) { h->err = "nrv_infix_classes: reverse must be 0 or 1"; return NRV_E_INVALID; }
+  if (!truth_ok(a, a_off, n_pairs) || !truth_ok(b, b_off, n_pairs)) {
+    h->err = "nrv_infix_classes: null sequences / offsets, or offsets that do not ascend from 0";
+    return NRV_E_INVALID;
+  }
+  if (!infix_lengths_ok(a_off, n_pairs, b_off)) {
+    h->err = "nrv_infix_classes: a truth region, or a read that has one, above NRV_INFIX_MAX_LEN = 2^21 - 1 characters";
+    return NRV_E_INVALID;
+  }
+  if (n_pairs == 0) return NRV_OK;
+  const int64_t ta = a_off[n_pairs], tb = b_off[n_pairs];
+  // one block of its own: [a_off | b_off | a | b | hc | dist | match | start | end]
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t nb = ((size_t)n_pairs + 1) * 8, nd = up((size_t)n_pairs * 8);
+  const size_t o_bo = up(nb), o_a = o_bo + up(nb), o_b = o_a + up((size_t)ta), o_hc = o_b + up((size_t)tb), o_d = o_hc + up((size_t)tb * 8);
+  const size_t bytes = o_d + 4 * nd;
+  char* d = nullptr;
+  HIPCHK(h, hipMalloc((void**)&d, bytes));
+  auto run = [&]() -> int {
+    int rc2 = poison_fill(h, d, bytes, h->stream);
+    if (rc2) return rc2;
+    HIPCHK(h, hipMemcpyAsync(d, a_off, nb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d + o_bo, b_off, nb, hipMemcpyHostToDevice, h->stream));
+    if (ta > 0) HIPCHK(h, hipMemcpyAsync(d + o_a, a, (size_t)ta, hipMemcpyHostToDevice, h->stream));
+    if (tb > 0) HIPCHK(h, hipMemcpyAsync(d + o_b, b, (size_t)tb, hipMemcpyHostToDevice, h->stream));
+    InfixArgs k;
+    k.n_reads = n_pairs; k.kinds = 1; k.strands = 1; k.reverse = reverse;
+    k.truth = (const unsigned char*)(d + o_a); k.truth_off = (const long long*)d;
+    k.reads = nullptr; k.bases = nullptr; k.cap0 = 0; k.hc0 = nullptr; k.hs0 = 0;
+    k.off = (const long long*)(d + o_bo); k.seq = (const unsigned char*)(d + o_b); k.cap1 = tb;
+    k.hc1 = (long long*)(d + o_hc); k.hs1 = 0;          // one strand per call: one set of carry words
+    k.infx = nullptr;
+    k.dist = (long long*)(d + o_d); k.match = (long long*)(d + o_d + nd); k.start = (long long*)(d + o_d + 2 * nd); k.end = (long long*)(d + o_d + 3 * nd);
+    if ((rc2 = infix_enqueue(h, k))) return rc2;
+    int64_t* const outs[4] = {dist, match, start, end};
+    for (int q = 0; q < 4; ++q) HIPCHK(h, hipMemcpyAsync(outs[q], d + o_d + (size_t)q * nd, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return NRV_OK;
   };

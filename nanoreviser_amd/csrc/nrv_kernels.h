@@ -73,3 +73,4 @@
 #include "nrv_trim.h"          // trim_qual / trim_window / trim_finish_kernel (sliding-window quality trim behind the merge, opt-in)
 #include "nrv_align.h"         // align_kernel (edit distance of the original and the revised reads to a truth set, one wave per pair, opt-in)
 #include "nrv_errclass.h"      // errclass_kernel (edits and matched columns of the original and the revised reads against a truth set: a wavefront across the lanes, one wave per pair, opt-in)
+#include "nrv_infix.h"         // infix_kernel (the original and the revised reads placed inside truth regions, free ends on the region, both strands: the wavefront of nrv_errclass.h with a reduced final column, one wave per (read, kind, strand), opt-in)

@@ -42,11 +42,15 @@ SYMBOLS = [
     "nrv_revise_reads_raw_trim_begin", "nrv_revise_reads_raw_trim", "nrv_merge_calls_trim", "nrv_trim_reads", "nrv_pack_records_trim",
     "nrv_revise_reads_raw_accuracy_begin", "nrv_revise_reads_raw_accuracy", "nrv_merge_calls_accuracy", "nrv_edit_distance",
     "nrv_revise_reads_raw_errclass_begin", "nrv_revise_reads_raw_errclass", "nrv_merge_calls_errclass", "nrv_edit_classes",
+    "nrv_revise_reads_raw_infix_begin", "nrv_revise_reads_raw_infix", "nrv_merge_calls_infix", "nrv_infix_classes",
 ]
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 PROFILE_COLS = 48                   # NRV_PROFILE_COLS
 ACCURACY_COLS = 4                   # NRV_ACCURACY_COLS
 ERRCLASS_COLS = 6                   # NRV_ERRCLASS_COLS
+INFIX_COLS = 18                     # NRV_INFIX_COLS
+INFIX_MAX_LEN = (1 << 21) - 1       # NRV_INFIX_MAX_LEN
+INFIX_R = 16                        # kInfixR of csrc/nrv_infix.h: region characters per lane; a stripe is 64 of them
 ERRCLASS_R = 16                     # kErrclassR of csrc/nrv_errclass.h: truth characters per lane; a stripe is 64 of them
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "f16x2": 2}
@@ -97,8 +101,9 @@ _PROFILE = ([_FP, _U64P], lambda p: p[20:22])                                   
 _TRIM = ([_FP, C.c_int, C.c_int, C.c_int64, _I64P], lambda p: p[22:27])                   # trim_thr, Q, W, min_len, trim
 _TRUTH = ([_U8P, _I64P, _U64P], lambda p: p[27:30])                                      # truth, truth_off, accuracy
 _ERRCLASS = ([_U64P], lambda p: p[30:31])                                                # errclass
+_INFIX = ([C.c_int, _U64P], lambda p: p[31:33])                                          # strands, infix
 # len(packed) -> (synchronous symbol, begin symbol, blocks, whether the call returns merged reads: (seq, qual, off[, report]
-# [, edits, edit_off][, blob, rec_off][, profile][, trim][, accuracy][, errclass]))
+# [, edits, edit_off][, blob, rec_off][, profile][, trim][, accuracy][, errclass][, errclass | None, infix]))
 _RAW_FORMS = {
     7: ("nrv_predict_reads_raw", "nrv_reads_raw_begin", (_CALLS,), False),
     9: ("nrv_predict_reads_raw_stats", "nrv_reads_raw_stats_begin", (_STATS, _CALLS), False),
@@ -116,6 +121,11 @@ _RAW_FORMS_TRUTH = {
     31: ("nrv_revise_reads_raw_errclass", "nrv_revise_reads_raw_errclass_begin",
          (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS, _PROFILE, _TRIM, _TRUTH, _ERRCLASS), True),
 }
+# ... and the form that places the reads inside truth REGIONS, in a table of its own (tests/test_errclass_host.py pins the one above)
+_RAW_FORMS_INFIX = {
+    33: ("nrv_revise_reads_raw_infix", "nrv_revise_reads_raw_infix_begin",
+         (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS, _PROFILE, _TRIM, _TRUTH, _ERRCLASS, _INFIX), True),
+}
 _PACK_RECORDS_T = [C.c_void_p, _U8P, _U8P, _I64P, C.c_int, _U8P, _I64P, _U8P, _I64P]         # nrv_pack_records
 _READS_HEAD_T = _RAW_HEAD_T[:4] + [C.c_int64, C.POINTER(_ReadDesc), C.c_int]     # nrv_segment_reads, nrv_read_stats: no features
 _MERGE_CALLS_T = [C.c_void_p, _U8P, _I64P, C.c_int, _I8P, _I8P, _FP, _FP, C.c_int64] + _MERGE[0][1:]   # nrv_merge_calls
@@ -123,6 +133,7 @@ _TRIM_READS_T = [C.c_void_p, _U8P, _I64P, C.c_int, C.c_int, C.c_int, _I64P]     
 _PACK_RECORDS_TRIM_T = _PACK_RECORDS_T[:7] + [_I64P, C.c_int64] + _PACK_RECORDS_T[7:]        # nrv_pack_records_trim
 _EDIT_DISTANCE_T = [C.c_void_p, _U8P, _I64P, _U8P, _I64P, C.c_int, _I64P]                    # nrv_edit_distance
 _EDIT_CLASSES_T = _EDIT_DISTANCE_T + [_I64P]                                                 # nrv_edit_classes
+_INFIX_CLASSES_T = _EDIT_DISTANCE_T[:6] + [C.c_int, _I64P, _I64P, _I64P, _I64P]              # nrv_infix_classes
 
 
 _lib = None
@@ -209,8 +220,9 @@ def load_library(path: Optional[str] = None):
     have_trim = hasattr(lib, "nrv_merge_calls_trim")
     have_truth = hasattr(lib, "nrv_merge_calls_accuracy")
     have_errclass = hasattr(lib, "nrv_merge_calls_errclass")
-    for sync, begin, blocks, _ in list(_RAW_FORMS.values()) + list(_RAW_FORMS_TRUTH.values()):  # (every restype is ctypes' default, int: the nrv_* status)
-        if (have_errclass or _ERRCLASS not in blocks) and (have_truth or _TRUTH not in blocks) and (have_trim or _TRIM not in blocks) and (have_profile or _PROFILE not in blocks) and (have_records or _RECORDS not in blocks) \
+    have_infix = hasattr(lib, "nrv_merge_calls_infix")
+    for sync, begin, blocks, _ in list(_RAW_FORMS.values()) + list(_RAW_FORMS_TRUTH.values()) + list(_RAW_FORMS_INFIX.values()):  # (every restype is ctypes' default, int: the nrv_* status)
+        if (have_infix or _INFIX not in blocks) and (have_errclass or _ERRCLASS not in blocks) and (have_truth or _TRUTH not in blocks) and (have_trim or _TRIM not in blocks) and (have_profile or _PROFILE not in blocks) and (have_records or _RECORDS not in blocks) \
                 and (have_edits or _EDITS not in blocks) and (have_report or _REPORT not in blocks):
             getattr(lib, sync).argtypes = _RAW_HEAD_T + [t for types, _ in blocks for t in types]
             getattr(lib, begin).argtypes = getattr(lib, sync).argtypes + [C.POINTER(C.c_int)]
@@ -233,6 +245,9 @@ def load_library(path: Optional[str] = None):
     if have_errclass:
         lib.nrv_merge_calls_errclass.argtypes = _MERGE_CALLS_T + _TRUTH[0]
         lib.nrv_edit_classes.argtypes = _EDIT_CLASSES_T
+    if have_infix:
+        lib.nrv_merge_calls_infix.argtypes = _MERGE_CALLS_T + _TRUTH[0][:2] + _INFIX[0]
+        lib.nrv_infix_classes.argtypes = _INFIX_CLASSES_T
     lib.nrv_reads_raw_end.argtypes = [vp, C.c_int]
     lib.nrv_segment_reads.argtypes = _READS_HEAD_T + [fp]
     lib.nrv_read_stats.argtypes = _READS_HEAD_T + [_I32P, _DP, _DP, _DP, _DP, fp]
@@ -622,12 +637,27 @@ class Reviser:
             raise ValueError("with_device_error_classes extends a with_device_accuracy tuple")
         return tuple(packed) + (np.zeros((packed[4], ERRCLASS_COLS), np.uint64),)
 
+    @classmethod
+    def with_device_infix(cls, packed, strands=2):
+        """A `with_device_accuracy` (30 elements) or `with_device_error_classes` (31) tuple whose call also places, per read,
+        the original and the revised read inside its truth REGION, free ends on the region, on the forward strand (strands = 1)
+        or on both (include/nanorev.h nrv_revise_reads_raw_infix_begin; hoststage.read_infix is the definition).  The result
+        has 33 elements: element 30 is the error-class block or None, 31 strands, 32 infix uint64[n_reads][18].
+        `run_packed_raw` / `begin_packed_raw` + `end_packed_raw` then return what the `with_device_error_classes` call returns
+        - None for its block where the tuple had none - and the infix block LAST."""
+        if len(packed) not in (30, 31):
+            raise ValueError("with_device_infix extends a with_device_accuracy or a with_device_error_classes tuple")
+        if strands not in (1, 2):
+            raise ValueError("strands is 1 or 2")
+        packed = tuple(packed) + ((None,) if len(packed) == 30 else ())
+        return packed + (int(strands), np.zeros((packed[4], INFIX_COLS), np.uint64))
+
     @staticmethod
     def _trim_merged(out):
         seq, qual, off = out[:3]
         total = int(off[-1])
         more, tail = tuple(out[3:]), ()
-        if len(more) in (6, 7, 8, 9):                 # (..., profile[, trim[, accuracy[, errclass]]]): a `with_device_profile` / `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` call; blocks it does not carry are None
+        if len(more) in (6, 7, 8, 9, 10):             # (..., profile[, trim[, accuracy[, errclass[, infix]]]]): a `with_device_profile` / `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` / `with_device_infix` call; blocks it does not carry are None
             more, tail = more[:5], more[5:]
         if len(more) in (3, 5) and more[1] is not None:   # (report | None, edits, edit_off, ...): the used prefix of the records
             more = (more[0], more[1][:int(more[2][-1])], more[2]) + more[3:]
@@ -643,23 +673,23 @@ class Reviser:
     def _raw_call(self, packed, begin: bool):
         """One call of the raw-read family for a packed tuple of any form (`_RAW_FORMS`): its synchronous entry point, or its
         *_begin with the ticket behind the same arguments.  Returns (ticket number or None, outputs, merged)."""
-        form = _RAW_FORMS.get(len(packed)) or _RAW_FORMS_TRUTH.get(len(packed))
+        form = _RAW_FORMS.get(len(packed)) or _RAW_FORMS_TRUTH.get(len(packed)) or _RAW_FORMS_INFIX.get(len(packed))
         if form is None:
-            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14, 16, 20, 22, 27 or 30 elements - or 31, a 30 with the error classes -, not {len(packed)}")
+            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14, 16, 20, 22, 27 or 30 elements - or 31, a 30 with the error classes, or 33, with the infix block -, not {len(packed)}")
         sync, beg, blocks, merged = form
-        if not hasattr(self._lib, beg):               # the report, edits, records, profile, trim, accuracy and error-class pairs are found by presence
+        if not hasattr(self._lib, beg):               # the report, edits, records, profile, trim, accuracy, error-class and infix pairs are found by presence
             raise NrvError(-1, f"this build of libnanorev_hip.so has no {beg}")
         args = self._raw_head(packed)
         for types, pick in blocks:
             args += _marshal(pick(packed), types)
         t = C.c_int(-1)
         self._check(getattr(self._lib, beg)(*args, C.byref(t)) if begin else getattr(self._lib, sync)(*args))
-        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) + tuple(packed[18:20]) + tuple(packed[21:22]) + tuple(packed[26:27]) + tuple(packed[29:31]) if merged else packed[6]), merged
+        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) + tuple(packed[18:20]) + tuple(packed[21:22]) + tuple(packed[26:27]) + tuple(packed[29:31]) + tuple(packed[32:33]) if merged else packed[6]), merged
 
     def run_packed_raw(self, packed):
         """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared (or `with_device_stats` /
         `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` /
-        `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` extended)."""
+        `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` / `with_device_infix` extended)."""
         _, out, merged = self._raw_call(packed, False)
         return self._trim_merged(out) if merged else out
 
@@ -676,7 +706,7 @@ class Reviser:
         trimmed to rec_off[-1] - for a `with_device_records` call; a `with_device_profile` call returns the latter with the
         profile behind it, a `with_device_trim` call with (profile | None, trim) behind it, a `with_device_accuracy` call with
         (profile | None, trim | None, accuracy) behind it, a `with_device_error_classes` call with the error classes behind
-        that."""
+        that, a `with_device_infix` call with (error classes | None, infix) behind the accuracy."""
         t, out = ticket[:2]
         self._check(self._lib.nrv_reads_raw_end(self._h, t))
         return self._trim_merged(out) if len(ticket) == 3 else out
@@ -873,6 +903,45 @@ class Reviser:
         self._check(self._lib.nrv_edit_classes(*_marshal((self._h, a if a.size else np.zeros(1, np.uint8), a_off,
                                                           b if b.size else np.zeros(1, np.uint8), b_off, n, dist, match), _EDIT_CLASSES_T)))
         return dist[:n], match[:n]
+
+    def merge_calls_infix_device(self, bases, ev_len, a1, a2, truth, truth_off, strands=2, p1=None, p2=None, q_thr=None):
+        """`merge_calls_errclass_device` with the infix block in the error classes' place (nrv_merge_calls_infix).  Returns
+        (seq, qual | None, off, infix uint64[n_reads][18]) - the block is hoststage.read_infix's, bit for bit."""
+        if not hasattr(self._lib, "nrv_merge_calls_infix"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_merge_calls_infix")
+        ins = self._merge_inputs(bases, ev_len, a1, a2, p1, p2, q_thr, q_thr is not None)
+        n, (q1, q2, thr) = ins[2].size, ins[4:]
+        if thr is not None and (thr.size != 39 or q1.shape[0] != n or q2.shape[0] != n):
+            raise ValueError("q_thr / p1 / p2 do not match")
+        nr = ins[1].size
+        t, toff = self._truth_block(truth, truth_off, nr)
+        blk = np.zeros((nr, INFIX_COLS), np.uint64)
+        return self._merge_call("nrv_merge_calls_infix", *ins, *_marshal((t, toff, int(strands), blk), _TRUTH[0][:2] + _INFIX[0])) + (blk,)
+
+    def infix_classes_device(self, truths, reads, reverse=False):
+        """infix_kernel alone (nrv_infix_classes): truths (the regions) and reads are equally long lists of byte strings (or
+        uint8 arrays); returns (dist, match, start, end), int64[n_pairs] each, hoststage.infix_classes(truths[k], reads[k],
+        reverse) - and -1 in all four where truths[k] is empty."""
+        if not hasattr(self._lib, "nrv_infix_classes"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_infix_classes")
+        if len(truths) != len(reads):
+            raise ValueError("one read per truth")
+        a, a_off = self._names_block(truths)
+        b, b_off = self._names_block(reads)
+        return self.infix_classes_offsets(a, a_off, b, b_off, reverse)
+
+    def infix_classes_offsets(self, a, a_off, b, b_off, reverse=False):
+        """`infix_classes_device` on the arrays as nrv_infix_classes takes them; the offsets and `reverse` are passed on unchecked."""
+        if not hasattr(self._lib, "nrv_infix_classes"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_infix_classes")
+        a_off = np.ascontiguousarray(a_off, dtype=np.int64).reshape(-1)
+        b_off = np.ascontiguousarray(b_off, dtype=np.int64).reshape(-1)
+        a, b = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1), np.ascontiguousarray(b, dtype=np.uint8).reshape(-1)
+        n = a_off.size - 1
+        outs = tuple(np.zeros(max(n, 1), np.int64) for _ in range(4))
+        self._check(self._lib.nrv_infix_classes(*_marshal((self._h, a if a.size else np.zeros(1, np.uint8), a_off,
+                                                           b if b.size else np.zeros(1, np.uint8), b_off, n, int(reverse)) + outs, _INFIX_CLASSES_T)))
+        return tuple(x[:n] for x in outs)
 
     def merge_calls_trim(self, bases, ev_len, a1, a2, p1, p2, Q, W=10, q_thr=None, trim_thr=None, names=None, min_len=1):
         """`merge_calls_device` with the sliding-window trim (nrv_merge_calls_trim): p1 / p2 are required, q_thr may be None (a
