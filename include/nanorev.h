@@ -96,7 +96,8 @@ int nrv_predict_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, cons
  *                        valid until then; any may be NULL).  A call that tripped the f16x2 range guard is re-run whole on the
  *                        f32 kernels here (nrv_saturated's *reruns counts it).
  * At most two calls in flight per handle (a third _begin returns NRV_E_INVALID); calls complete in the order they began; between
- * a _begin and its _end only these two entry points may be called on the handle.  nrv_predict_reads_raw IS _begin + _end. */
+ * a _begin and its _end only these two entry points may be called on the handle - and, the one exception, nrv_align_labels,
+ * which works on a stream and a block of its own.  nrv_predict_reads_raw IS _begin + _end. */
 int nrv_reads_raw_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
                         const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
                         float* p1, float* p2, int8_t* a1, int8_t* a2, int* ticket);
@@ -558,6 +559,50 @@ int nrv_merge_calls_infix(nrv_handle* h, const uint8_t* bases, const int64_t* ev
  * a length above NRV_INFIX_MAX_LEN are refused.  The unit door of the kernel. */
 int nrv_infix_classes(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
                       int reverse, int64_t* dist, int64_t* match, int64_t* start, int64_t* end);
+
+/* PER-BASE TRAINING LABELS: THE TRUTH ALIGNMENT WITH ITS TRACEBACK (opt-in; nothing above changes).  The blocks above say how
+ * far a read is from its truth in integers that need no traceback; the labels the two classifiers are trained on are the
+ * per-base answer - which truth character stands opposite each read base, which read bases are inserted or followed by a
+ * deletion - which the reference derives from an external mapper's SAM record (NanoReviser_train.py: parse_sam_record,
+ * clean_read_map_ref, get_base_label).  With the infix block's placement of a read in its region, on either strand, the
+ * alignment and its traceback are formed here.  hoststage.align_labels is the definition.
+ * Per pair: a region t (m bytes), a read s (n bytes), reverse (0 or 1) and bounds 0 <= start <= end <= m;
+ * u = strand(t)[start:end], L = end - start bytes; the strand and the matching of bytes as in the infix block.  The recurrence
+ * is the error classes' on (u, s), cells (d, -M) compared lexicographically: G[0][j] = (j, 0), G[i][0] = (i, 0), and for
+ * i, j >= 1 three candidates in this order: 0 the diagonal G[i-1][j-1] + ((0, -1) on a match, (1, 0) otherwise); 1 "I", the
+ * read character alone, G[i][j-1] + (1, 0); 2 "D", the truth character alone, G[i-1][j] + (1, 0).  G[i][j] is their minimum,
+ * dir[i][j] the FIRST candidate that attains it.  The path starts at (L, n) and, while i > 0 or j > 0, takes I if i == 0, D if
+ * j == 0 and dir[i][j] otherwise; the columns visited, reversed, are the alignment.  Among all alignments with the optimal
+ * (d, M) it is the one whose columns, read from the end backwards, are lexicographically smallest under diagonal < I < D: gaps
+ * land left-aligned.
+ *   labels   uint8 [b_off[n_pairs]], one byte per read base:
+ *     bits 0 .. 2  the code of the column's truth character: 1 ("-") on an I column; on a diagonal column A 5, G 4, T 3, C 2
+ *                  and 0 for any other byte - on the reverse strand of the complemented character
+ *     bit 3 (8)    a diagonal column that is not a match
+ *     bit 4 (16)   the next column or columns are D: the base is followed by deleted truth characters (a leading run of D,
+ *                  in front of the first read base, flags nothing)
+ *   summary  int64 [n_pairs][NRV_LABEL_COLS]:
+ *     0 match   1 sub   2 ins   3 del (D columns, the leading ones included)
+ *     4 clip_start  read bases in front of the first diagonal column, n when there is none
+ *     5 clip_end    read bases behind the last diagonal column, 0 when there is none
+ *     6 lead_del    D columns in front of the first read base
+ * hoststage.label_strings gives the text forms: map (D if bit 4, else I if the code is 1, else X if bit 3, else M), label1 (0
+ * if bit 4, else the code: model1's six classes) and label2 (the code: model2's five).  n = 0: no bytes and
+ * (0, 0, 0, L, 0, 0, L); L = 0: every base is I; an EMPTY region, m = 0, means "no truth": -1 in all seven columns, zero bytes.
+ * a: the regions, b: the reads, as nrv_infix_classes takes them; reverse, start and end per pair.  Refused under the entry
+ * point's name, the handle staying usable: null arguments, offsets that do not ascend from 0, a reverse byte other than 0 or
+ * 1, bounds outside the region, a read - or an end - start - above NRV_LABELS_MAX_LEN.
+ * Two launches per batch of pairs (csrc/nrv_labels.h): the error classes' wavefront, one wave per pair, storing a 2-bit
+ * direction per cell - ceil(L / 1024) (n + 63) 256 bytes of direction words per pair -, then one thread per pair walking back.
+ * Pairs run in consecutive batches whose direction words fit 2 GiB (NRV_LABELS_BUDGET=<bytes>, read by nrv_create; a pair runs
+ * alone if need be, 1.0 GiB at the most).  The block - inputs, carry words, direction words, outputs - is kept in the handle,
+ * grown on demand and freed by nrv_destroy.  Plain stores, no atomics: the bytes do not depend on the batches.  Not timed yet.
+ * The call runs on a non-blocking stream of its own and waits for that stream alone; it reads and writes nothing else of the
+ * handle, so it MAY be called between a nrv_reads_raw_begin (or any other _begin) and its _end. */
+#define NRV_LABEL_COLS 7
+#define NRV_LABELS_MAX_LEN 65536 /* of a read and of end - start */
+int nrv_align_labels(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
+                     const uint8_t* reverse, const int64_t* start, const int64_t* end, uint8_t* labels, int64_t* summary);
 
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be

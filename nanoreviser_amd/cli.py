@@ -206,11 +206,29 @@ def get_args(argv: Optional[Sequence[str]] = None):
                         "without it nothing changes")
     p.add_argument("--infix_strand", dest="infix_strand", default="both", choices=("both", "forward"),
                    help="with --infix: try both strands of a region (default) or the forward strand alone")
+    p.add_argument("--labels", dest="labels", default=None, metavar="DIR",
+                   help="with --truth and --infix: write the per-base training labels of every read into DIR (also "
+                        "NRV_LABELS=DIR).  The ORIGINAL bases of a read whose --infix line is with_truth are aligned against its "
+                        "region on that line's strand at start_in:end_in - revised or written unrevised alike - and "
+                        "DIR/<stem>_labels.txt gets five lines: #name, strand, start, end, len, match, sub, ins, del, clip_start, "
+                        "clip_end, lead_del (tab separated); the bases; per base M / X / I, or D where deleted truth characters "
+                        "follow; label1 (0 D, 1 -, 2 C, 3 T, 4 G, 5 A: the truth character opposite the base, 0 where a deletion "
+                        "follows); label2 (the same without the deletions).  A read without a truth, or whose length or "
+                        "end - start exceeds 65536, gets no file.  DIR/labels.tsv has a header, one line per input read sorted by "
+                        "file name - name, status (with_truth / no_truth / too_long), strand, start, end, len, the seven figures, "
+                        "the counts of label1 = 0 .. 5 and of label2 = 0 .. 5 -, a line #total with the sums (the class balance) "
+                        "and a line #reads.  With --device_merge the labels of a device call's reads are found on the GPU by one "
+                        "call while the next is in flight (not timed yet), everywhere else by the host stage: the same files "
+                        "byte for byte.  Off by default; without it nothing changes")
     a = p.parse_args(argv)
     a.infix = a.infix or (os.environ.get("NRV_INFIX", "").strip() or None)
+    a.labels = a.labels or (os.environ.get("NRV_LABELS", "").strip() or None)
     a.error_classes = a.error_classes or (os.environ.get("NRV_ERROR_CLASSES", "").strip() or None)
     a.truth = a.truth or (os.environ.get("NRV_TRUTH", "").strip() or None)
     a.accuracy = a.accuracy or (os.environ.get("NRV_ACCURACY", "").strip() or None)
+    if a.labels and not (a.truth and a.infix):
+        print("[！！！Error] --labels goes with --truth and --infix", file=sys.stderr)
+        raise SystemExit(2)
     if a.infix and not a.truth:
         print("[！！！Error] --infix goes with --truth", file=sys.stderr)
         raise SystemExit(2)
@@ -1387,6 +1405,12 @@ class InfixPart(AccuracyPart):
         ReportPart.__init__(self, path, INFIX_PART_COLS)
         self.truths, self.max_len, self.log, self.warned, self.classes, self.infix = truths or {}, int(max_len), log, False, None, None
         self.strands = int(strands)
+        self.labels = None                            # --labels: a `LabelsPart` rides along (a read's labels follow from its line)
+
+    def close(self):
+        if self.labels is not None:
+            self.labels.close()
+        super().close()
 
     @staticmethod
     def rows(blk, lens_in, lens_out, flags):
@@ -1413,7 +1437,105 @@ class InfixPart(AccuracyPart):
         g = [0] * 8
         if flag == ACC_WITH_TRUTH:
             g = [int(x) for rev in range(self.strands) for x in hs.infix_classes(truth, text, bool(rev))] + [0] * (4 * (2 - self.strands))
-        self.add(fn, False, [int(toff[1]), self.strands if flag == ACC_WITH_TRUTH else 0, len(text), len(text)] + g + g + [flag])
+        row = [int(toff[1]), self.strands if flag == ACC_WITH_TRUTH else 0, len(text), len(text)] + g + g + [flag]
+        self.add(fn, False, row)
+        if self.labels is not None:                   # --labels: the bases that were written ARE the original bases
+            self.labels.add_read(fn, text, row)
+
+
+LABELS_HEADER = ("name\tstatus\tstrand\tstart\tend\tlen\tmatch\tsub\tins\tdel\tclip_start\tclip_end\tlead_del\t"
+                 + "\t".join(f"label1_{k}" for k in range(6)) + "\t" + "\t".join(f"label2_{k}" for k in range(6)))
+LABELS_PART_COLS = 24                      # a part line's integers: reverse, start, end, len, the seven figures, 6 + 6 counts, flag
+LABELS_STATUS = {ACC_WITH_TRUTH: "with_truth", ACC_NO_TRUTH: "no_truth", ACC_TOO_LONG: "too_long"}
+
+
+def labels_index_path(labels_dir: str) -> str:
+    return os.path.join(labels_dir, "labels.tsv")
+
+
+def labels_file(labels_dir: str, fast5_fn: str) -> str:
+    return os.path.join(labels_dir, fast5_fn.split(".")[0] + "_labels.txt")
+
+
+def labels_plan(v, n: int):
+    """What --labels aligns of a read with n original bases from its --infix part line's integers: (flag, reverse, start, end),
+    start / end on the strand `infix_fields` reports (`hoststage.pick_strand`), those of the ORIGINAL read.  A read that is not
+    with_truth keeps its flag; one whose length or end - start exceeds LABELS_MAX_LEN becomes too_long."""
+    v = [int(x) for x in v[:INFIX_PART_COLS]]
+    if v[-1] != ACC_WITH_TRUTH:
+        return v[-1], 0, 0, 0
+    rev = hs.pick_strand([v[0], v[1]] + v[4:20]) == "-"
+    st, en = (v[10], v[11]) if rev else (v[6], v[7])
+    if int(n) > hs.LABELS_MAX_LEN or en - st > hs.LABELS_MAX_LEN:
+        return ACC_TOO_LONG, 0, 0, 0
+    return ACC_WITH_TRUTH, int(rev), st, en
+
+
+class LabelsPart(ReportPart):
+    """One process' share of --labels: the files DIR/<stem>_labels.txt, written by temporary + rename, and the part of the index
+    DIR/labels.tsv (`merge_labels`).  It rides on an `InfixPart`: a read's labels are formed when its --infix line is."""
+
+    def __init__(self, labels_dir: Optional[str], rank, truths: Optional[dict], log: Callable[[str], None] = print):
+        super().__init__(report_part_path(labels_index_path(labels_dir), rank) if labels_dir else None, LABELS_PART_COLS)
+        self.dir, self.truths, self.log, self.warned = labels_dir, truths or {}, log, False
+
+    def add_read(self, fn: str, bases, inf_row, result=None):
+        """The labels of one read: bases (its ORIGINAL bases, uint8 / bytes / str), inf_row (the integers of its --infix part
+        line), result ((label bytes, the seven figures) found on the device for `labels_plan`'s bounds, or None: the host stage
+        aligns, `hoststage.align_labels`)."""
+        if self.path is None:
+            return
+        b = hs._as_u8(bases.encode("ascii", "replace") if isinstance(bases, str) else bases)
+        flag, rev, st, en = labels_plan(inf_row, b.size)
+        out = labels_file(self.dir, fn)
+        if flag != ACC_WITH_TRUTH:                     # no file: not one an earlier run left either
+            try:
+                os.remove(out)
+            except OSError:
+                pass
+            self.add(fn, False, [0, 0, 0, b.size] + [0] * 19 + [flag])
+            return
+        if result is None:
+            if not self.warned:
+                self.warned = True
+                self.log("[！！！Warning] --labels: the reads are aligned to their truth regions by the host stage "
+                         "(--device_merge aligns them on the GPU)")
+            result = hs.align_labels(truth_of(self.truths, fn), b, bool(rev), st, en)
+        lab, summ = np.asarray(result[0], np.uint8).reshape(-1), [int(x) for x in np.asarray(result[1]).reshape(-1)]
+        m = int(inf_row[0])
+        lo, hi = (m - en, m - st) if rev else (st, en)  # 0-based half-open on the region AS GIVEN, as the --infix line has them
+        mp, l1, l2 = hs.label_strings(lab)
+        head = "\t".join(["#" + fn, "-" if rev else "+", str(lo), str(hi), str(b.size)] + [str(x) for x in summ])
+        tmp = f"{out}.tmp{os.getpid()}"
+        with open(tmp, "w") as fp:
+            fp.write("\n".join([head, b.tobytes().decode("ascii", "replace"), mp, l1, l2]) + "\n")
+        os.replace(tmp, out)
+        self.add(fn, True, [rev, lo, hi, b.size] + summ + [l1.count(str(k)) for k in range(6)] + [l2.count(str(k)) for k in range(6)] + [flag])
+
+
+def merge_labels(labels_dir: str, names: Sequence[str], log: Callable[[str], None] = print):
+    """Parent side of --labels: DIR/labels.tsv from the parts as `merge_infix` reads them - one line per read of `names` sorted by
+    file name, then #total, the sums over the reads with a file of len, the seven figures and the twelve class counts (`.` in the
+    columns of strand, start and end), and #reads with_truth / no_truth / too_long; the file appears by rename and the parts are
+    removed."""
+    path = labels_index_path(labels_dir)
+    rows, parts = _part_rows(path, LABELS_PART_COLS)
+    out, t, counts = [LABELS_HEADER], [0] * 20, [0, 0, 0]
+    for fn in sorted(names):
+        c = rows.get(fn)
+        if c is None:
+            log(f"[！！！Warning] --labels: no record for {fn}")
+            c = [fn, "unrevised"] + ["0"] * (LABELS_PART_COLS - 1) + [str(ACC_NO_TRUTH)]
+        v = [int(x) for x in c[2:]]
+        counts[v[-1]] += 1
+        if v[-1] == ACC_WITH_TRUTH:
+            out.append("\t".join([fn, LABELS_STATUS[v[-1]], "-" if v[0] else "+"] + [str(x) for x in v[1:23]]))
+            t = [a + b for a, b in zip(t, v[3:23])]
+        else:
+            out.append("\t".join([fn, LABELS_STATUS[v[-1]], ".", ".", ".", str(v[3])] + ["."] * 19))
+    out.append("\t".join(["#total", "with_truth", ".", ".", "."] + [str(x) for x in t]))
+    out.append("#reads\t" + "\t".join(str(x) for x in counts))
+    _replace_report(path, out, parts)
 
 
 def merge_infix(path: str, names: Sequence[str], log: Callable[[str], None] = print):
@@ -1727,6 +1849,12 @@ class _FileRun:
         self.infpart = InfixPart(infix_part, self.accpart.truths, self.accpart.max_len,
                                  1 if getattr(args, "infix_strand", "both") == "forward" else 2, log)
         self.inf_rows = {}
+        # --labels: rides on the infix part (the part of its index carries the suffix of the infix part); fn -> (the read's
+        # original bases, its labels from the device | None) is stashed wherever an infix row is
+        if getattr(args, "labels", None) and infix_part:
+            self.infpart.labels = LabelsPart(args.labels, infix_part.rsplit(".part", 1)[-1], self.accpart.truths, log)
+        self.lab_in = {}
+        self.lab_truth = {}                           # id(batch) -> (truth, truth_off) of a form 33 call, until its call is back
         self.acc_flags = {}                           # id(batch) -> the flags of a form 30 call's truth block, until its call is back
         self.tie_eps = float(getattr(args, "report_tie_eps", hs.REPORT_TIE_EPS))
         self.edits_dir = getattr(args, "edits", None) # --edits: every read's list is written BEFORE its output is
@@ -1906,6 +2034,7 @@ class _FileRun:
         self.ecl_rows.pop(fn, None)
         self.eclpart.add_unrevised(fn, text)
         self.inf_rows.pop(fn, None)
+        self.lab_in.pop(fn, None)
         self.infpart.add_unrevised(fn, text)
         self.note(fn, False)
 
@@ -1936,6 +2065,9 @@ class _FileRun:
             if row is None:                           # cannot happen, as above
                 self.log(f"[！！！Warning] --infix: no figures for {fn}")
             self.infpart.add(fn, row is not None, row if row is not None else [0, 0, nb, nb] + [0] * 16 + [ACC_NO_TRUTH])
+            if self.infpart.labels is not None:
+                bases, found = self.lab_in.pop(fn, (b"", None))
+                self.infpart.labels.add_read(fn, bases, row if row is not None else [0, 0, nb, nb] + [0] * 16 + [ACC_NO_TRUTH], found)
         if self.trim:
             row = self.trim_rows.pop(fn, None)
             log_row = trim_log_row(row[0], row[1], self.trim[2]) if row is not None else unrevised_trim(nb)
@@ -1996,6 +2128,8 @@ class _FileRun:
                                 packed = cls.with_device_error_classes(packed)
                             if infix:                 # --infix: last, on the same truth block
                                 packed = cls.with_device_infix(packed, self.infpart.strands)
+                                if self.infpart.labels is not None:
+                                    self.lab_truth[id(batch)] = (truth, toff)
         except Exception:
             packed = None
         if packed is None:
@@ -2028,6 +2162,7 @@ class _FileRun:
         """Read by read: with a worker pool the merge + file write is a pool task (~20 KB per read), without one it happens here."""
         T = self.rv.T
         self.acc_flags.pop(id(batch), None)
+        self.lab_truth.pop(id(batch), None)
         for (fn, rt, fq), c in zip(batch, calls):
             if isinstance(c, Exception):
                 self.fallback(fn, rt, fq, c)
@@ -2047,6 +2182,8 @@ class _FileRun:
                     self.ecl_rows[fn] = self.eclpart.host_rows(T, [fn], rt.bases, [len(np.asarray(rt.bases))], c[2], c[3])[0]
                 if self.infpart:
                     self.inf_rows[fn] = self.infpart.host_rows(T, [fn], rt.bases, [len(np.asarray(rt.bases))], c[2], c[3])[0]
+                    if self.infpart.labels is not None:
+                        self.lab_in[fn] = (hostlib.bases_u8(rt.bases), None)
                 if self.edits_dir:
                     write_edits(self.edits_dir, fn, edit_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual)[0], self.want_qual)
                 if self.pool is not None or self.sink is not None:
@@ -2068,18 +2205,51 @@ class _FileRun:
             except Exception as e:
                 self.fallback(fn, rt, fq, e)
 
-    def finish_call(self, batch, bundle, outs, merged):
+    def stash_labels(self, fns, bases, ev_len, found=None):
+        """--labels: every read's original bases - and, found = (labels, b_off, summary) of `device_labels`, its labels - until
+        `finished` forms its line."""
+        b, off = hostlib.bases_u8(bases), np.concatenate([[0], np.cumsum(np.asarray(ev_len, np.int64))])
+        for r, fn in enumerate(fns):
+            got = None if found is None else (found[0][int(found[1][r]):int(found[1][r + 1])], found[2][r])
+            self.lab_in[fn] = (b[int(off[r]):int(off[r + 1])], got)
+
+    def device_labels(self, reviser, batch, bundle, outs):
+        """--labels on the device route: the labels of ALL reads of a form 33 call by ONE nrv_align_labels call, made on the engine's
+        thread right behind the call's `end_packed_raw` - on a stream of its own, so the next call stays in flight.  The regions
+        are the call's truth block, the bounds and the strand those `labels_plan` reads off the infix block; a read that gets no
+        file goes up empty, with an empty region.  None where the engine cannot (the host stage aligns then)."""
+        kept = self.lab_truth.pop(id(batch), None)
+        flags = self.acc_flags.get(id(batch))
+        if kept is None or flags is None or len(outs) != 13 or not hasattr(reviser, "align_labels_arrays"):
+            return None
+        truth, toff = kept
+        ev_len = bundle["meta"][:, 1].astype(np.int64)
+        rows = self.infpart.rows(outs[12], ev_len.tolist(), np.diff(outs[2]).tolist(), flags)
+        plans = [labels_plan(v, n) for v, n in zip(rows, ev_len.tolist())]
+        bases, off = hostlib.bases_u8(bundle["bases"]), np.concatenate([[0], np.cumsum(ev_len)])
+        parts = [truth[int(toff[r]):int(toff[r + 1])] if p[0] == ACC_WITH_TRUTH else truth[:0] for r, p in enumerate(plans)]
+        texts = [bases[int(off[r]):int(off[r + 1])] if p[0] == ACC_WITH_TRUTH else bases[:0] for r, p in enumerate(plans)]   # (the call refuses a read above its limit)
+        a_off = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.int64)
+        b_off = np.concatenate([[0], np.cumsum([len(x) for x in texts])]).astype(np.int64)
+        lab, summ = reviser.align_labels_arrays(np.concatenate(parts) if parts else truth[:0], a_off, np.concatenate(texts) if texts else bases[:0], b_off,
+                                                [p[1] for p in plans], [p[2] for p in plans], [p[3] for p in plans])
+        return lab, b_off, summ
+
+    def finish_call(self, batch, bundle, outs, merged, labels=None):
         """ALL reads of a device call as one pool task: merge + record + file (nrvh_finish_bundle), or - merged, a --device_merge
-        call that came back as revised reads - record + file alone (nrvh_write_records)."""
+        call that came back as revised reads - record + file alone (nrvh_write_records).  labels: what `device_labels` found."""
         try:
             fns, rts, fqs = map(list, zip(*batch))
             trim = None
             flags = self.acc_flags.pop(id(batch), None)
+            self.lab_truth.pop(id(batch), None)
             if merged:
                 if len(outs) == 13:                   # a `with_device_infix` call: (..., accuracy, error classes | None, infix)
                     if self.infpart and flags is not None:
                         ev_len = bundle["meta"][:, 1].astype(np.int64)
                         self.inf_rows.update(zip(fns, self.infpart.rows(outs[12], ev_len.tolist(), np.diff(outs[2]).tolist(), flags)))
+                        if self.infpart.labels is not None:
+                            self.stash_labels(fns, bundle["bases"], ev_len, labels)
                     outs = outs[:12] if outs[11] is not None else outs[:11]
                 if len(outs) == 12:                   # a `with_device_error_classes` call: the counts were found behind the distances, last output
                     if self.eclpart and flags is not None:
@@ -2123,6 +2293,8 @@ class _FileRun:
                     self.ecl_rows.update(zip(fns, self.eclpart.host_rows(T, fns, bundle["bases"], ev_len.tolist(), a1, a2)))
                 if self.infpart:
                     self.inf_rows.update(zip(fns, self.infpart.host_rows(T, fns, bundle["bases"], ev_len.tolist(), a1, a2)))
+                    if self.infpart.labels is not None:
+                        self.stash_labels(fns, bundle["bases"], ev_len)
                 if self.edits_dir:
                     self.write_call_edits(fns, *edit_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2, self.want_qual))
                 qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
@@ -2164,8 +2336,14 @@ class _FileRun:
             calls = _predict_each(reviser, _bundle_reads(bundle))
             self.engine_time(t0)
             return self.fin.submit(self.finish_batch, batch, calls)      # (the finisher is one thread: behind nxt's hand-over)
+        labels = None
+        if self.infpart.labels is not None and _is_merged_ticket(tk):
+            try:                                       # --labels: ONE call for the reads of this one, while the next is in flight
+                labels = self.device_labels(reviser, batch, bundle, outs)
+            except Exception as e:
+                self.log(f"[！！！Warning] --labels: the device call failed ({e}); the host stage aligns these reads")
         self.engine_time(t0, ti, t_begin)
-        return self.fin.submit(self.finish_call, batch, bundle, outs, _is_merged_ticket(tk))
+        return self.fin.submit(self.finish_call, batch, bundle, outs, _is_merged_ticket(tk), labels)
 
     def flush_pipeline(self):
         """Behind the last batch: whatever is still in flight."""
@@ -2623,7 +2801,10 @@ def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[st
                     if accuracy.classes is not None:
                         accuracy.classes.add(fn, True, accuracy.classes.host_rows(T, [fn], pl[0]["bases"], [N], a1, a2)[0])
                 if accuracy is not None and accuracy.infix is not None:
-                    accuracy.infix.add(fn, True, accuracy.infix.host_rows(T, [fn], pl[0]["bases"], [N], a1, a2)[0])
+                    inf_row = accuracy.infix.host_rows(T, [fn], pl[0]["bases"], [N], a1, a2)[0]
+                    accuracy.infix.add(fn, True, inf_row)
+                    if accuracy.infix.labels is not None:
+                        accuracy.infix.labels.add_read(fn, hostlib.bases_u8(pl[0]["bases"]), inf_row)
                 if summary is not None and summary and have_p:
                     summary.add(fn, True, profile_rows(T, pl[0]["bases"], [N], np.concatenate([p["p1"] for p in pl]),
                                                        np.concatenate([p["p2"] for p in pl]), a1, a2)[0])
@@ -2756,6 +2937,10 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
         parent_acc.infix = InfixPart(report_part_path(args.infix, "parent"), truths, args.accuracy_max_len,
                                      1 if args.infix_strand == "forward" else 2)
         inf_part0 = report_part_path(args.infix, 0)
+        if args.labels:                   # --labels: the files' directory; the parts of its index ride on the infix parts
+            os.makedirs(args.labels, exist_ok=True)
+            clear_report_parts(labels_index_path(args.labels))
+            parent_acc.infix.labels = LabelsPart(args.labels, "parent", truths)
     if args.combined:                     # --combined: a part per process too, `merge_combined` ends the run
         clear_combined_parts(args.combined)
     parent_sink = CombinedPart(combined_part_path(args.combined, "parent"), args.output_format == "fastq") if args.combined else None
@@ -2865,6 +3050,8 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
         if parent_acc.infix is not None:
             parent_acc.infix.close()
             merge_infix(args.infix, all_names)
+            if args.labels:
+                merge_labels(args.labels, all_names)
         if parent_acc.classes is not None:
             parent_acc.classes.close()
             merge_error_classes(args.error_classes, all_names)

@@ -652,6 +652,14 @@ struct nrv_handle {
   unsigned sat_seen[2] = {0, 0};   // the staging sets' counters only grow: a stage fired iff its counter moved since the last look
   bool host_call_open = false;     // a host-pointer call that left through an error path: its stages may have moved the counters
                                    // without anybody looking - the next call reads them back first
+  // nrv_align_labels: ONE block of its own [inputs | hc | outputs | direction words], grown on demand and kept, on a non-blocking
+  // stream of its own - the call touches nothing else of the handle but err, so it may run while a raw call is in flight.  A
+  // block that became too small is RETIRED, not freed (hipFree would wait for the raw call in flight): nrv_destroy frees them.
+  char* d_lab = nullptr;
+  size_t cap_lab = 0;
+  std::vector<char*> lab_retired;
+  hipStream_t lab_stream = nullptr;
+  size_t lab_budget = kLabelsBudget;     // bytes of direction words per batch of pairs (NRV_LABELS_BUDGET, read by nrv_create)
   int64_t sat_reruns = 0;          // pipeline stages the host entry points re-ran on the f32 kernels
   int h2 = 1;                      // 1: f16x2 mode (the default) - lstm2..4 on lstm_h2o / lstm_h2s_kernel, activations between the kernels
                                    // as f16 split planes (cnn dense and head stay on their bf16x3 kernels)
@@ -1462,6 +1470,7 @@ int nrv_create(const nrv_weights* m1, const nrv_weights* m2, int T, int device, 
   if (const char* e2 = getenv("NRV_HOST_REGISTER")) h->host_register = atoi(e2) != 0;
   if (const char* e3 = getenv("NRV_LANES")) h->lanes_on = atoi(e3) != 0;
   if (const char* e4 = getenv("NRV_COALESCE")) h->coalesce = atoi(e4) != 0;
+  if (const char* e6 = getenv("NRV_LABELS_BUDGET"); e6 && *e6) { const long long v = atoll(e6); if (v > 0) h->lab_budget = (size_t)v; }
   if (const char* e5 = getenv("NRV_POISON"); e5 && *e5) { h->poison_on = true; h->poison = (unsigned)strtoul(e5, nullptr, 16); }
   ok = ok && hipMalloc((void**)&h->d_sat, 4 * sizeof(unsigned)) == hipSuccess &&
        hipMemset(h->d_sat, 0, 4 * sizeof(unsigned)) == hipSuccess;
@@ -1491,6 +1500,9 @@ void nrv_destroy(nrv_handle* h) {
   if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
   if (h->d2h_stream) { (void)hipStreamSynchronize(h->d2h_stream); (void)hipStreamDestroy(h->d2h_stream); }
   if (h->edit_stream) { (void)hipStreamSynchronize(h->edit_stream); (void)hipStreamDestroy(h->edit_stream); }
+  if (h->lab_stream) { (void)hipStreamSynchronize(h->lab_stream); (void)hipStreamDestroy(h->lab_stream); }
+  (void)hipFree(h->d_lab);
+  for (char* p : h->lab_retired) (void)hipFree(p);
   for (int st = 0; st < nrv_handle::kIn; ++st) if (h->ev_in[st]) (void)hipEventDestroy(h->ev_in[st]);
   for (int st = 0; st < 2; ++st) {
     if (h->ev_done[st]) (void)hipEventDestroy(h->ev_done[st]);
@@ -3400,6 +3412,101 @@ int nrv_infix_classes(nrv_handle* h, const uint8_t* a, const int64_t* a_off, con
   rc = run();
   if (rc) (void)hipStreamSynchronize(h->stream);
   (void)hipFree(d);
+  return rc;
+}
+
+// labels_kernel + labels_walk_kernel (nrv_labels.h) on the pairs of one batch, the walk behind the forward pass on the labels' stream
+static int labels_enqueue(nrv_handle* h, const LabelsArgs& a) {
+  if (a.n_pairs <= 0) return NRV_OK;
+  hipLaunchKernelGGL(labels_kernel, dim3((unsigned)a.n_pairs), dim3(64), 0, h->lab_stream, a);
+  HIPCHK(h, hipGetLastError());
+  hipLaunchKernelGGL(labels_walk_kernel, dim3(((unsigned)a.n_pairs + 63u) / 64u), dim3(64), 0, h->lab_stream, a);
+  HIPCHK(h, hipGetLastError());
+  return NRV_OK;
+}
+
+int nrv_align_labels(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
+                     const uint8_t* reverse, const int64_t* start, const int64_t* end, uint8_t* labels, int64_t* summary) {
+  static_assert(NRV_LABEL_COLS == kLabelCols && NRV_LABELS_MAX_LEN == kLabelsMaxLen, "nanorev.h and nrv_labels.h disagree on the labels");
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (n_pairs < 0 || (n_pairs > 0 && (!reverse || !start || !end || !summary))) { h->err = "nrv_align_labels: bad arguments"; return NRV_E_INVALID; }
+  if (!truth_ok(a, a_off, n_pairs) || !truth_ok(b, b_off, n_pairs) || (b_off[n_pairs] > 0 && !labels)) {
+    h->err = "nrv_align_labels: null sequences / offsets / labels, or offsets that do not ascend from 0";
+    return NRV_E_INVALID;
+  }
+  for (int r = 0; r < n_pairs; ++r) {
+    if (reverse[r] > 1) { h->err = "nrv_align_labels: reverse must be 0 or 1"; return NRV_E_INVALID; }
+    if (start[r] < 0 || end[r] < start[r] || end[r] > a_off[r + 1] - a_off[r]) {
+      h->err = "nrv_align_labels: bounds outside the region (0 <= start <= end <= its length)";
+      return NRV_E_INVALID;
+    }
+    if (b_off[r + 1] - b_off[r] > kLabelsMaxLen || end[r] - start[r] > kLabelsMaxLen) {
+      h->err = "nrv_align_labels: a read, or an end - start, above NRV_LABELS_MAX_LEN = 65536 characters";
+      return NRV_E_INVALID;
+    }
+  }
+  if (n_pairs == 0) return NRV_OK;
+  const int64_t ta = a_off[n_pairs], tb = b_off[n_pairs];
+  // consecutive batches whose direction words fit the budget (a pair alone if need be); dir_off: a pair's words inside its batch's
+  std::vector<int64_t> dir_off((size_t)n_pairs);
+  std::vector<int> batch_end;
+  size_t words = 0, max_words = 0;
+  for (int r = 0; r < n_pairs; ++r) {
+    const int64_t L = end[r] - start[r], n = b_off[r + 1] - b_off[r];
+    const size_t w = (a_off[r + 1] > a_off[r] && L > 0 && n > 0) ? (size_t)((L + kLabelsStripe - 1) / kLabelsStripe) * (size_t)(n + 63) * 64 : 0;
+    if (words > 0 && (words + w) * 4 > h->lab_budget) { batch_end.push_back(r); words = 0; }
+    dir_off[(size_t)r] = (int64_t)words;
+    words += w;
+    max_words = std::max(max_words, words);
+  }
+  batch_end.push_back(n_pairs);
+  // the handle's block: [a_off | b_off | start | end | dir_off | reverse | a | b | hc | labels | summary | direction words]
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t nb = ((size_t)n_pairs + 1) * 8, np8 = up((size_t)n_pairs * 8);
+  const size_t o_bo = up(nb), o_st = o_bo + up(nb), o_en = o_st + np8, o_do = o_en + np8, o_rv = o_do + np8, o_a = o_rv + up((size_t)n_pairs);
+  const size_t o_b = o_a + up((size_t)ta), o_hc = o_b + up((size_t)tb), o_lab = o_hc + up((size_t)tb * 8), o_sum = o_lab + up((size_t)tb);
+  const size_t o_dir = o_sum + up((size_t)n_pairs * kLabelCols * 8), bytes = o_dir + up(max_words * 4);
+  if (!h->lab_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->lab_stream, hipStreamNonBlocking));
+  if (bytes > h->cap_lab) {                                // grown on demand; the old block is retired (no hipFree on this path)
+    const size_t want = std::max(bytes, h->cap_lab + h->cap_lab / 2);
+    char* p = nullptr;
+    HIPCHK(h, hipMalloc((void**)&p, want));
+    if (h->d_lab) h->lab_retired.push_back(h->d_lab);
+    h->d_lab = p; h->cap_lab = want;
+  }
+  char* const d = h->d_lab;
+  hipStream_t const s = h->lab_stream;
+  auto run = [&]() -> int {
+    int rc2 = poison_fill(h, d, bytes, s);                // NRV_POISON: the part this call uses
+    if (rc2) return rc2;
+    HIPCHK(h, hipMemcpyAsync(d, a_off, nb, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d + o_bo, b_off, nb, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d + o_st, start, (size_t)n_pairs * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d + o_en, end, (size_t)n_pairs * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d + o_do, dir_off.data(), (size_t)n_pairs * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d + o_rv, reverse, (size_t)n_pairs, hipMemcpyHostToDevice, s));
+    if (ta > 0) HIPCHK(h, hipMemcpyAsync(d + o_a, a, (size_t)ta, hipMemcpyHostToDevice, s));
+    if (tb > 0) HIPCHK(h, hipMemcpyAsync(d + o_b, b, (size_t)tb, hipMemcpyHostToDevice, s));
+    LabelsArgs k;
+    k.truth = (const unsigned char*)(d + o_a); k.truth_off = (const long long*)d;
+    k.seq = (const unsigned char*)(d + o_b); k.off = (const long long*)(d + o_bo);
+    k.reverse = (const unsigned char*)(d + o_rv); k.start = (const long long*)(d + o_st); k.end = (const long long*)(d + o_en);
+    k.hc = (long long*)(d + o_hc); k.dirw = (unsigned*)(d + o_dir); k.dir_off = (const long long*)(d + o_do);
+    k.labels = (unsigned char*)(d + o_lab); k.summary = (long long*)(d + o_sum);
+    int p0 = 0;
+    for (int p1 : batch_end) {                            // in stream order: a batch's walk ends before the next forward pass stores
+      k.pair0 = p0; k.n_pairs = p1 - p0;
+      if ((rc2 = labels_enqueue(h, k))) return rc2;
+      p0 = p1;
+    }
+    if (tb > 0) HIPCHK(h, hipMemcpyAsync(labels, d + o_lab, (size_t)tb, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(summary, d + o_sum, (size_t)n_pairs * kLabelCols * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return NRV_OK;
+  };
+  rc = run();
+  if (rc) (void)hipStreamSynchronize(s);
   return rc;
 }
 

@@ -43,6 +43,7 @@ SYMBOLS = [
     "nrv_revise_reads_raw_accuracy_begin", "nrv_revise_reads_raw_accuracy", "nrv_merge_calls_accuracy", "nrv_edit_distance",
     "nrv_revise_reads_raw_errclass_begin", "nrv_revise_reads_raw_errclass", "nrv_merge_calls_errclass", "nrv_edit_classes",
     "nrv_revise_reads_raw_infix_begin", "nrv_revise_reads_raw_infix", "nrv_merge_calls_infix", "nrv_infix_classes",
+    "nrv_align_labels",
 ]
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 PROFILE_COLS = 48                   # NRV_PROFILE_COLS
@@ -51,6 +52,8 @@ ERRCLASS_COLS = 6                   # NRV_ERRCLASS_COLS
 INFIX_COLS = 18                     # NRV_INFIX_COLS
 INFIX_MAX_LEN = (1 << 21) - 1       # NRV_INFIX_MAX_LEN
 INFIX_R = 16                        # kInfixR of csrc/nrv_infix.h: region characters per lane; a stripe is 64 of them
+LABEL_COLS = 7                      # NRV_LABEL_COLS
+LABELS_MAX_LEN = 65536              # NRV_LABELS_MAX_LEN: of a read and of end - start
 ERRCLASS_R = 16                     # kErrclassR of csrc/nrv_errclass.h: truth characters per lane; a stripe is 64 of them
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "f16x2": 2}
@@ -134,6 +137,7 @@ _PACK_RECORDS_TRIM_T = _PACK_RECORDS_T[:7] + [_I64P, C.c_int64] + _PACK_RECORDS_
 _EDIT_DISTANCE_T = [C.c_void_p, _U8P, _I64P, _U8P, _I64P, C.c_int, _I64P]                    # nrv_edit_distance
 _EDIT_CLASSES_T = _EDIT_DISTANCE_T + [_I64P]                                                 # nrv_edit_classes
 _INFIX_CLASSES_T = _EDIT_DISTANCE_T[:6] + [C.c_int, _I64P, _I64P, _I64P, _I64P]              # nrv_infix_classes
+_ALIGN_LABELS_T = _EDIT_DISTANCE_T[:6] + [_U8P, _I64P, _I64P, _U8P, _I64P]                   # nrv_align_labels
 
 
 _lib = None
@@ -248,6 +252,8 @@ def load_library(path: Optional[str] = None):
     if have_infix:
         lib.nrv_merge_calls_infix.argtypes = _MERGE_CALLS_T + _TRUTH[0][:2] + _INFIX[0]
         lib.nrv_infix_classes.argtypes = _INFIX_CLASSES_T
+    if hasattr(lib, "nrv_align_labels"):
+        lib.nrv_align_labels.argtypes = _ALIGN_LABELS_T
     lib.nrv_reads_raw_end.argtypes = [vp, C.c_int]
     lib.nrv_segment_reads.argtypes = _READS_HEAD_T + [fp]
     lib.nrv_read_stats.argtypes = _READS_HEAD_T + [_I32P, _DP, _DP, _DP, _DP, fp]
@@ -942,6 +948,38 @@ class Reviser:
         self._check(self._lib.nrv_infix_classes(*_marshal((self._h, a if a.size else np.zeros(1, np.uint8), a_off,
                                                            b if b.size else np.zeros(1, np.uint8), b_off, n, int(reverse)) + outs, _INFIX_CLASSES_T)))
         return tuple(x[:n] for x in outs)
+
+    def align_labels_device(self, regions, reads, reverse, start, end):
+        """labels_kernel and labels_walk_kernel (nrv_align_labels): regions and reads are equally long lists of byte strings (or
+        uint8 arrays), reverse / start / end one value per pair; returns (a list of uint8 arrays, one label byte per read base,
+        and summary int64[n_pairs][7]) - hoststage.align_labels(regions[k], reads[k], reverse[k], start[k], end[k]) bit for bit.
+        The call runs on a stream of its own: it may be made while a `begin_packed_raw` call is in flight."""
+        if not hasattr(self._lib, "nrv_align_labels"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_align_labels")
+        if not len(regions) == len(reads) == len(reverse) == len(start) == len(end):
+            raise ValueError("one read, one strand and one pair of bounds per region")
+        a, a_off = self._names_block(regions)
+        b, b_off = self._names_block(reads)
+        labels, summary = self.align_labels_arrays(a, a_off, b, b_off, reverse, start, end)
+        return [labels[int(b_off[k]):int(b_off[k + 1])] for k in range(len(reads))], summary
+
+    def align_labels_arrays(self, a, a_off, b, b_off, reverse, start, end):
+        """`align_labels_device` on the arrays as nrv_align_labels takes them: returns (labels uint8[b_off[-1]], summary
+        int64[n_pairs][7]); the offsets, strands and bounds are passed on unchecked."""
+        if not hasattr(self._lib, "nrv_align_labels"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_align_labels")
+        a_off = np.ascontiguousarray(a_off, dtype=np.int64).reshape(-1)
+        b_off = np.ascontiguousarray(b_off, dtype=np.int64).reshape(-1)
+        a, b = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1), np.ascontiguousarray(b, dtype=np.uint8).reshape(-1)
+        n = a_off.size - 1
+        rev, st, en = (np.ascontiguousarray(x, dtype=t).reshape(-1) for x, t in ((reverse, np.uint8), (start, np.int64), (end, np.int64)))
+        if not rev.size == st.size == en.size == n:
+            raise ValueError("one strand and one pair of bounds per pair")
+        labels, summary = np.zeros(max(b.size, 1), np.uint8), np.zeros((max(n, 1), LABEL_COLS), np.int64)
+        pad = lambda x: x if x.size else np.zeros(1, x.dtype)   # noqa: E731
+        self._check(self._lib.nrv_align_labels(*_marshal((self._h, pad(a), a_off, pad(b), b_off, n, pad(rev), pad(st), pad(en), labels, summary),
+                                                         _ALIGN_LABELS_T)))
+        return labels[:min(max(int(b_off[-1]), 0), b.size) if b_off.size else 0], summary[:max(n, 0)]
 
     def merge_calls_trim(self, bases, ev_len, a1, a2, p1, p2, Q, W=10, q_thr=None, trim_thr=None, names=None, min_len=1):
         """`merge_calls_device` with the sliding-window trim (nrv_merge_calls_trim): p1 / p2 are required, q_thr may be None (a
