@@ -21,6 +21,23 @@ def f32_floor(m1, m2, sig, rd, p64_1, p64_2, T=11, numpy_too=True):
     return nf1, nf2
 
 
+LOG_PMIN = 1e-6
+
+
+def log_dev(p, p64, pmin=LOG_PMIN):
+    """Per-window deviation in the log domain: max over the classes with p64 >= pmin of |log p - log p64|.  An error in the
+    logit of a class at p = 1e-4 does not show in |dp| at any bar; it shows here."""
+    p, p64 = np.asarray(p, np.float64), np.asarray(p64, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = np.abs(np.log(p) - np.log(p64))
+    return np.where(p64 >= pmin, d, 0.0).max(-1)
+
+
+def f32_floor_log(p64, evals, pmin=LOG_PMIN):
+    """The log-domain twin of f32_floor: per window, the largest log_dev of the oracle's own f32 evaluations `evals`."""
+    return np.max([log_dev(e, p64, pmin) for e in evals], axis=0)
+
+
 def check_vs_fp64(p, a, p64, nf, what="", max_ill=0.01, bar=BAR):
     """The policy of the module docstring for one model's outputs.  Returns a dict of what was seen."""
     p, a, p64 = np.asarray(p), np.asarray(a), np.asarray(p64)
