@@ -31,9 +31,10 @@ namespace nrv {
 constexpr int kAccuracyCols = 4;
 constexpr int kAlignStripe = 4096;       // truth characters per stripe: 64 lanes x 64 bits
 
-struct AlignArgs {
-  int n_reads;                           // pairs of the unit door; reads of a merged call (two waves each)
-  int kinds;                             // 2: a merged call, accu; 1: the unit door (texts by off / seq alone), dist
+// What align_kernel, errclass_kernel and infix_kernel share: the pairs, the truth and the two places a text can come from
+struct PairArgs {
+  int n_reads;                           // pairs of the unit door; reads of a merged call (kinds waves each; infix: x strands)
+  int kinds;                             // 2: a merged call, one row per read; 1: the unit door (texts by off / seq alone), one array per figure
   const unsigned char* truth;
   const long long* truth_off;            // [n_reads + 1] ascending from 0
   const SegRead* reads;                  // kind 0: bases[ev_off .. ev_off + ev_len)
@@ -41,6 +42,35 @@ struct AlignArgs {
   const long long* off;                  // kind 1 (and the unit door): seq[off[r] .. off[r + 1])
   const unsigned char* seq;
   long long cap0, cap1;                  // characters bases / seq hold: a text that is not inside them counts as empty
+};
+
+// Pair (r, kind) resolved: the truth t (m bytes; m <= 0: no truth, and nothing of the text is read) and the text s (n bytes),
+// which starts `at` characters into bases (kind 0) or seq (kind 1) - the pair's carry starts as far into its own array.  A
+// text that is not inside cap0 / cap1, or longer than max_len, counts as empty and lies at 0
+struct PairText {
+  const unsigned char *t, *s;
+  int m, n;
+  long long at;
+};
+__device__ inline PairText pair_text(const PairArgs& a, int r, int kind, long long max_len = 0x7fffffffffffffffll) {
+  PairText p;
+  const long long t_at = a.truth_off[r];
+  p.t = a.truth + t_at; p.m = (int)(a.truth_off[r + 1] - t_at);
+  p.s = a.seq; p.n = 0; p.at = 0;
+  if (p.m <= 0) return p;
+  if (kind == 0) {
+    const SegRead rd = a.reads[r];
+    const bool ok = rd.ev_off >= 0 && rd.ev_len >= 0 && rd.ev_len <= max_len && rd.ev_off + rd.ev_len <= a.cap0;
+    p.at = ok ? rd.ev_off : 0; p.s = a.bases + p.at; p.n = ok ? (int)rd.ev_len : 0;
+  } else {
+    const long long o0 = a.off[r], o1 = a.off[r + 1];
+    const bool ok = o0 >= 0 && o1 >= o0 && o1 - o0 <= max_len && o1 <= a.cap1;
+    p.at = ok ? o0 : 0; p.s = a.seq + p.at; p.n = ok ? (int)(o1 - o0) : 0;
+  }
+  return p;
+}
+
+struct AlignArgs : PairArgs {
   unsigned char *hc0, *hc1;              // carry bytes, one per text character: hc0[ev_off + j], hc1[off[r] + j]
   unsigned long long* accu;              // [n_reads][kAccuracyCols] (kinds == 2)
   long long* dist;                       // [n_reads] (kinds == 1): -1 for an empty truth
@@ -50,8 +80,8 @@ __global__ void __launch_bounds__(64) align_kernel(const AlignArgs a) {
   const int lane = threadIdx.x;
   const int r = (int)(blockIdx.x / (unsigned)a.kinds), kind = a.kinds == 2 ? (int)(blockIdx.x & 1u) : 1;
   if (r >= a.n_reads) return;
-  const long long t_at = a.truth_off[r];
-  const int m = (int)(a.truth_off[r + 1] - t_at);
+  const PairText p = pair_text(a, r, kind);
+  const int m = p.m, n = p.n;
   if (m <= 0) {                                           // no truth: the row is zeros and no distance is formed
     if (lane == 0) {
       if (a.kinds == 2) {
@@ -63,19 +93,8 @@ __global__ void __launch_bounds__(64) align_kernel(const AlignArgs a) {
     }
     return;
   }
-  const unsigned char* t = a.truth + t_at;
-  const unsigned char* s;
-  unsigned char* hc;
-  int n;
-  if (kind == 0) {
-    const SegRead rd = a.reads[r];
-    const bool ok = rd.ev_off >= 0 && rd.ev_len >= 0 && rd.ev_off + rd.ev_len <= a.cap0;
-    s = a.bases + (ok ? rd.ev_off : 0); hc = a.hc0 + (ok ? rd.ev_off : 0); n = ok ? (int)rd.ev_len : 0;
-  } else {
-    const long long o0 = a.off[r], o1 = a.off[r + 1];
-    const bool ok = o0 >= 0 && o1 >= o0 && o1 <= a.cap1;
-    s = a.seq + (ok ? o0 : 0); hc = a.hc1 + (ok ? o0 : 0); n = ok ? (int)(o1 - o0) : 0;
-  }
+  const unsigned char *t = p.t, *s = p.s;
+  unsigned char* hc = (kind == 0 ? a.hc0 : a.hc1) + p.at;
   int score = 0;                                          // the sum of hout of the truth's last block (its lane only)
   int last_lane = 0;
   for (int base = 0; base < m; base += kAlignStripe) {

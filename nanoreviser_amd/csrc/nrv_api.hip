@@ -2,6 +2,7 @@
 // the C-ABI declared in include/nanorev.h.  gfx950 only; no CPU path.
 #include "../../include/nanorev.h"
 #include "nrv_kernels.h"
+#include "nrv_block.h"
 
 #include <algorithm>
 #include <cmath>
@@ -698,6 +699,23 @@ static int alloc_fill(nrv_handle* h, void* p, size_t bytes) {
   if (h->poison_on) HIPCHK(h, hipMemsetD32((hipDeviceptr_t)p, (int)h->poison, bytes / 4));
   else HIPCHK(h, hipMemset(p, 0, bytes));
   return NRV_OK;
+}
+// host -> device on stream s; a length of 0 copies nothing (src may be null then)
+static int put(nrv_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s) {
+  if (bytes > 0) HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+  return NRV_OK;
+}
+// "One block of its own" (layouts: nrv_block.h): allocated, NRV_POISON over all of it, body(d) - the uploads, the kernels, the
+// downloads and the wait for them, all on stream s - and freed.  What a failed body left in flight is waited for before the block goes
+template <class Body>
+static int with_block(nrv_handle* h, size_t bytes, hipStream_t s, Body&& body) {
+  char* d = nullptr;
+  HIPCHK(h, hipMalloc((void**)&d, bytes));
+  int rc = poison_fill(h, d, bytes, s);
+  if (!rc) rc = body(d);
+  if (rc) (void)hipStreamSynchronize(s);
+  (void)hipFree(d);
+  return rc;
 }
 
 // unit halves (16 units each) per wave of the f16x2 kernels of lstm2..4: lstm_h2w_kernel (192 -> 128) and lstm_h2s_kernel (256 -> 64)
@@ -1656,6 +1674,70 @@ static int merged_collect(nrv_handle* h, const char* who, const char* who_edits,
   return NRV_OK;
 }
 
+// the lengths of an infix call: no sequence (region, or - lens given - read that has a region) above NRV_INFIX_MAX_LEN
+static bool infix_lengths_ok(const int64_t* truth_off, int n, const int64_t* len_off = nullptr, const nrv_read_desc* reads = nullptr) {
+  for (int r = 0; r < n; ++r) {
+    const int64_t m = truth_off[r + 1] - truth_off[r];
+    if (m > NRV_INFIX_MAX_LEN) return false;
+    if (m > 0 && len_off && len_off[r + 1] - len_off[r] > NRV_INFIX_MAX_LEN) return false;
+    if (m > 0 && reads && reads[r].ev_len > NRV_INFIX_MAX_LEN) return false;
+  }
+  return true;
+}
+// a truth set: offsets that ascend from 0, bytes where there are any, and no sequence of 2^31 - 64 characters or more
+static bool truth_ok(const uint8_t* truth, const int64_t* truth_off, int n_reads) {
+  if (!truth_off || truth_off[0] != 0) return false;
+  for (int r = 0; r < n_reads; ++r)
+    if (truth_off[r + 1] < truth_off[r] || truth_off[r + 1] - truth_off[r] >= ((int64_t)1 << 31) - 64) return false;
+  return truth != nullptr || truth_off[n_reads] == 0;
+}
+// What one of the three pair doors (nrv_edit_distance, nrv_edit_classes, nrv_infix_classes) brings to pair_door: its refusals
+// to the letter and in the order they are tried, the bytes of carry per character of b, and its k outputs of int64[n_pairs]
+struct PairDoor {
+  const char* bad_args;                  // n_pairs < 0, or a null output
+  const char* refused;                   // a refusal of the door's own, decided by the caller (null: none)
+  const char* bad_pair;                  // a or b is no truth set (truth_ok)
+  const char* bad_lengths;               // infix_lengths_ok (null: the door has no such limit)
+  size_t carry;
+  int k;
+  int64_t* out[kPairMaxOuts];
+};
+// A pair door: the checks, one block of its own (pair_layout), the pair up, enqueue(the shared arguments, the carry, the k
+// outputs on the device) for the door's own kernel, the k outputs down
+template <class Enqueue>
+static int pair_door(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
+                     const PairDoor& w, Enqueue&& enqueue) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  bool outs = true;
+  for (int q = 0; q < w.k; ++q) outs = outs && w.out[q];
+  if (n_pairs < 0 || (n_pairs > 0 && !outs)) { h->err = w.bad_args; return NRV_E_INVALID; }
+  if (w.refused) { h->err = w.refused; return NRV_E_INVALID; }
+  if (!truth_ok(a, a_off, n_pairs) || !truth_ok(b, b_off, n_pairs)) { h->err = w.bad_pair; return NRV_E_INVALID; }
+  if (w.bad_lengths && !infix_lengths_ok(a_off, n_pairs, b_off)) { h->err = w.bad_lengths; return NRV_E_INVALID; }
+  if (n_pairs == 0) return NRV_OK;
+  const size_t nb = ((size_t)n_pairs + 1) * 8, ta = (size_t)a_off[n_pairs], tb = (size_t)b_off[n_pairs];
+  const PairLayout l = pair_layout((size_t)n_pairs, ta, tb, w.carry, w.k);
+  hipStream_t const s = h->stream;
+  return with_block(h, l.bytes, s, [&](char* d) -> int {
+    int rc2;
+    if ((rc2 = put(h, d + l.a_off, a_off, nb, s)) || (rc2 = put(h, d + l.b_off, b_off, nb, s)) ||
+        (rc2 = put(h, d + l.a, a, ta, s)) || (rc2 = put(h, d + l.b, b, tb, s)))
+      return rc2;
+    PairArgs k;                                           // one kind: a is the truth, b the text
+    k.n_reads = n_pairs; k.kinds = 1;
+    k.truth = (const unsigned char*)(d + l.a); k.truth_off = (const long long*)(d + l.a_off);
+    k.reads = nullptr; k.bases = nullptr; k.cap0 = 0;
+    k.off = (const long long*)(d + l.b_off); k.seq = (const unsigned char*)(d + l.b); k.cap1 = (long long)tb;
+    long long* out[kPairMaxOuts] = {};
+    for (int q = 0; q < w.k; ++q) out[q] = (long long*)(d + l.out[q]);
+    if ((rc2 = enqueue(k, d + l.hc, out))) return rc2;
+    for (int q = 0; q < w.k; ++q) HIPCHK(h, hipMemcpyAsync(w.out[q], d + l.out[q], (size_t)n_pairs * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return NRV_OK;
+  });
+}
+
 extern "C" {
 
 int nrv_predict_device(nrv_handle* h, const float* d_signal, const float* d_read, int64_t n,
@@ -2175,23 +2257,6 @@ static int infix_enqueue(nrv_handle* h, const InfixArgs& a) {
   HIPCHK(h, hipGetLastError());
   return NRV_OK;
 }
-// the lengths of an infix call: no sequence (region, or - lens given - read that has a region) above NRV_INFIX_MAX_LEN
-static bool infix_lengths_ok(const int64_t* truth_off, int n, const int64_t* len_off = nullptr, const nrv_read_desc* reads = nullptr) {
-  for (int r = 0; r < n; ++r) {
-    const int64_t m = truth_off[r + 1] - truth_off[r];
-    if (m > NRV_INFIX_MAX_LEN) return false;
-    if (m > 0 && len_off && len_off[r + 1] - len_off[r] > NRV_INFIX_MAX_LEN) return false;
-    if (m > 0 && reads && reads[r].ev_len > NRV_INFIX_MAX_LEN) return false;
-  }
-  return true;
-}
-// a truth set: offsets that ascend from 0, bytes where there are any, and no sequence of 2^31 - 64 characters or more
-static bool truth_ok(const uint8_t* truth, const int64_t* truth_off, int n_reads) {
-  if (!truth_off || truth_off[0] != 0) return false;
-  for (int r = 0; r < n_reads; ++r)
-    if (truth_off[r + 1] < truth_off[r] || truth_off[r + 1] - truth_off[r] >= ((int64_t)1 << 31) - 64) return false;
-  return truth != nullptr || truth_off[n_reads] == 0;
-}
 static bool trim_rule_ok(int Q, int W, int64_t min_len) { return Q >= 1 && Q <= 40 && W >= 1 && W <= kTrimMaxW && min_len >= 0; }
 // bytes the records of a call can take: hoststage.pack_records on N + max(N - T, 0) characters at the most
 static size_t blob_capacity(int64_t N, int64_t n, int n_reads, int64_t name_bytes, bool fastq) {
@@ -2234,31 +2299,30 @@ static void records_host(const uint8_t* seq, const uint8_t* qual, const int64_t*
 }
 // the merged block (MergeLayout) of a call that hands back what `o` asks for
 static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, const MergeOut& o, size_t blob_cap) {
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   MergeLayout m;
   const size_t cap = (size_t)(N + n), tiles = (size_t)((N + kMergeTile - 1) / kMergeTile);
-  m.seq = up(((size_t)n_reads + 1) * 8);
-  m.qual = m.seq + up(cap);
-  m.rep = m.qual + up(cap);
-  m.eoff = m.rep + (o.report ? up((size_t)n_reads * kReportCols * 8) : 0);
-  m.roff = m.eoff + (o.edit_off ? up(((size_t)n_reads + 1) * 8) : 0);
-  m.prof = m.roff + (o.rec_off ? up(((size_t)n_reads + 1) * 8) : 0);
-  m.trim = m.prof + (o.profile ? up((size_t)n_reads * kProfileCols * 8) : 0);
-  m.accu = m.trim + (o.trim ? up((size_t)n_reads * 16) : 0);
-  m.ecls = m.accu + (o.accuracy ? up((size_t)n_reads * kAccuracyCols * 8) : 0);
-  m.infx = m.ecls + (o.errclass ? up((size_t)n_reads * kErrclassCols * 8) : 0);
-  m.dl = m.infx + (o.infix ? up((size_t)n_reads * kInfixCols * 8) : 0);
+  m.seq = up256(((size_t)n_reads + 1) * 8);
+  m.qual = m.seq + up256(cap);
+  m.rep = m.qual + up256(cap);
+  m.eoff = m.rep + (o.report ? up256((size_t)n_reads * kReportCols * 8) : 0);
+  m.roff = m.eoff + (o.edit_off ? up256(((size_t)n_reads + 1) * 8) : 0);
+  m.prof = m.roff + (o.rec_off ? up256(((size_t)n_reads + 1) * 8) : 0);
+  m.trim = m.prof + (o.profile ? up256((size_t)n_reads * kProfileCols * 8) : 0);
+  m.accu = m.trim + (o.trim ? up256((size_t)n_reads * 16) : 0);
+  m.ecls = m.accu + (o.accuracy ? up256((size_t)n_reads * kAccuracyCols * 8) : 0);
+  m.infx = m.ecls + (o.errclass ? up256((size_t)n_reads * kErrclassCols * 8) : 0);
+  m.dl = m.infx + (o.infix ? up256((size_t)n_reads * kInfixCols * 8) : 0);
   m.rec = m.dl;
-  m.tile = m.rec + up((size_t)N * 4);
-  m.edits = m.tile + up(tiles * 8);
-  m.etile = m.edits + (o.edit_off ? up((size_t)n * sizeof(nrv_edit)) : 0);
-  m.blob = m.etile + (o.edit_off ? up(tiles * 8) : 0);
-  m.tq = m.blob + (o.rec_off ? up(blob_cap) : 0);
-  m.acc = m.tq + (o.trim ? up(cap) : 0);
-  m.hc = m.acc + (o.trim ? up((size_t)n_reads * 16) : 0);
-  m.hc8 = m.hc + (o.accuracy ? up((size_t)N) + up(cap) : 0);
-  m.hci = m.hc8 + (o.errclass ? up((size_t)N * 8) + up(cap * 8) : 0);
-  m.bytes = m.hci + (o.infix ? 2 * up((size_t)N * 8) + 2 * up(cap * 8) : 0);
+  m.tile = m.rec + up256((size_t)N * 4);
+  m.edits = m.tile + up256(tiles * 8);
+  m.etile = m.edits + (o.edit_off ? up256((size_t)n * sizeof(nrv_edit)) : 0);
+  m.blob = m.etile + (o.edit_off ? up256(tiles * 8) : 0);
+  m.tq = m.blob + (o.rec_off ? up256(blob_cap) : 0);
+  m.acc = m.tq + (o.trim ? up256(cap) : 0);
+  m.hc = m.acc + (o.trim ? up256((size_t)n_reads * 16) : 0);
+  m.hc8 = m.hc + (o.accuracy ? carry_layout((size_t)N, cap, 1, 1).bytes : 0);
+  m.hci = m.hc8 + (o.errclass ? carry_layout((size_t)N, cap, 8, 1).bytes : 0);
+  m.bytes = m.hci + (o.infix ? carry_layout((size_t)N, cap, 8, 2).bytes : 0);
   return m;
 }
 // No window at all (N <= T): the reads come back as they are, on the host
@@ -2415,6 +2479,16 @@ static void merged_nothing(const MergeIn& in, const MergeOut& o, const nrv_read_
   if (o.infix) infix_nothing(in.bases, reads, n_reads, in.truth, in.truth_off, o.strands, o.infix);
 }
 
+// What the three truth kernels share (PairArgs, nrv_align.h) in a merged call: both kinds of every read, the revised text as
+// the merge (a) leaves it
+static PairArgs pair_args(const MergeView& v, const MergeArgs& a, int T) {
+  PairArgs k;
+  k.n_reads = v.n_reads; k.kinds = 2;
+  k.truth = v.truth; k.truth_off = v.truth_off;
+  k.reads = v.reads; k.bases = v.bases; k.off = a.off; k.seq = a.seq;
+  k.cap0 = v.N; k.cap1 = v.N + (v.N - T > 0 ? v.N - T : 0);
+  return k;
+}
 // The kernels of a merged call behind whatever produced v.a1 / a2 / p1 / p2 on the compute stream: the merge, then what `o` asks
 // for - report, edit list, records, profile - each reading what the merge left.  q_thr: the thresholds of the quality (null:
 // none is written); the merge reads the rows only for a quality, the report and the edits whenever there are rows, the profile
@@ -2448,38 +2522,29 @@ static int merged_enqueue(nrv_handle* h, const MergeView& v, const MergeLayout& 
     rc = pack_enqueue(h, k);
   }
   if (!rc && o.profile) rc = profile_enqueue(h, profile_args(a, v.p1, v.p2, prof_thr, v.blk + m.prof));
+  const PairArgs pa = pair_args(v, a, h->T);
+  const size_t cap = (size_t)pa.cap1;                      // the carries lie where merge_layout put them
   if (!rc && o.accuracy) {                                 // behind everything that writes off / seq: it reads bases, the descriptors, off / seq and the truth
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     AlignArgs k;
-    k.n_reads = v.n_reads; k.kinds = 2;
-    k.truth = v.truth; k.truth_off = v.truth_off;
-    k.reads = v.reads; k.bases = v.bases; k.off = a.off; k.seq = a.seq;
-    k.cap0 = v.N; k.cap1 = v.N + (v.N - h->T > 0 ? v.N - h->T : 0);
-    k.hc0 = (unsigned char*)(v.blk + m.hc); k.hc1 = k.hc0 + up((size_t)v.N);
+    static_cast<PairArgs&>(k) = pa;
+    k.hc0 = (unsigned char*)(v.blk + m.hc); k.hc1 = k.hc0 + carry_layout((size_t)v.N, cap, 1, 1).hc1;
     k.accu = (unsigned long long*)(v.blk + m.accu); k.dist = nullptr;
     rc = align_enqueue(h, k);
   }
   if (!rc && o.errclass) {                                 // ... and behind it: the same inputs, carry words of its own
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     ErrclassArgs k;
-    k.n_reads = v.n_reads; k.kinds = 2;
-    k.truth = v.truth; k.truth_off = v.truth_off;
-    k.reads = v.reads; k.bases = v.bases; k.off = a.off; k.seq = a.seq;
-    k.cap0 = v.N; k.cap1 = v.N + (v.N - h->T > 0 ? v.N - h->T : 0);
-    k.hc0 = (long long*)(v.blk + m.hc8); k.hc1 = (long long*)(v.blk + m.hc8 + up((size_t)v.N * 8));
+    static_cast<PairArgs&>(k) = pa;
+    k.hc0 = (long long*)(v.blk + m.hc8); k.hc1 = (long long*)(v.blk + m.hc8 + carry_layout((size_t)v.N, cap, 8, 1).hc1);
     k.ecls = (unsigned long long*)(v.blk + m.ecls); k.dist = nullptr; k.match = nullptr;
     rc = errclass_enqueue(h, k);
   }
   if (!rc && o.infix) {                                    // ... and LAST: the same inputs on one strand or on both, carry words per strand
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t s0 = up((size_t)v.N * 8), s1 = (m.bytes - m.hci - 2 * s0) / 2;   // (merge_layout: the block ends with them)
+    const CarryLayout c = carry_layout((size_t)v.N, cap, 8, 2);
     InfixArgs k;
-    k.n_reads = v.n_reads; k.kinds = 2; k.strands = o.strands; k.reverse = 0;
-    k.truth = v.truth; k.truth_off = v.truth_off;
-    k.reads = v.reads; k.bases = v.bases; k.off = a.off; k.seq = a.seq;
-    k.cap0 = v.N; k.cap1 = v.N + (v.N - h->T > 0 ? v.N - h->T : 0);
-    k.hc0 = (long long*)(v.blk + m.hci); k.hs0 = (long long)(s0 / 8);
-    k.hc1 = (long long*)(v.blk + m.hci + 2 * s0); k.hs1 = (long long)(s1 / 8);
+    static_cast<PairArgs&>(k) = pa;
+    k.strands = o.strands; k.reverse = 0;
+    k.hc0 = (long long*)(v.blk + m.hci); k.hs0 = (long long)(c.hs0 / 8);
+    k.hc1 = (long long*)(v.blk + m.hci + c.hc1); k.hs1 = (long long)(c.hs1 / 8);
     k.infx = (unsigned long long*)(v.blk + m.infx); k.dist = k.match = k.start = k.end = nullptr;
     rc = infix_enqueue(h, k);
   }
@@ -2559,17 +2624,16 @@ static int raw_begin(nrv_handle* h, const RawIn& in, float* p1, float* p2, int8_
     return NRV_OK;
   }
   static_assert(sizeof(SegRead) == sizeof(nrv_read_desc), "descriptor layouts must match");
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  sl.off_starts = up((size_t)n_raw * 2);
-  sl.off_reads = sl.off_starts + up((size_t)N * 4);
-  sl.off_feat = sl.off_reads + up((size_t)n_reads * sizeof(SegRead));
-  sl.off_aux = sl.off_feat + up((size_t)N * kFeat * 4);
-  sl.off_bases = sl.off_aux + (with_stats ? up((size_t)n_reads * sizeof(StatAux)) : 0);
-  sl.off_noff = sl.off_bases + (mr ? up((size_t)N) : 0);
-  sl.off_names = sl.off_noff + (records ? up(((size_t)n_reads + 1) * 8) : 0);
-  sl.off_toff = sl.off_names + (records ? up((size_t)mr->name_off[n_reads]) : 0);
-  sl.off_truth = sl.off_toff + (accuracy ? up(((size_t)n_reads + 1) * 8) : 0);
-  const size_t in_bytes = sl.off_truth + (accuracy ? up((size_t)mr->truth_off[n_reads]) : 0);
+  sl.off_starts = up256((size_t)n_raw * 2);
+  sl.off_reads = sl.off_starts + up256((size_t)N * 4);
+  sl.off_feat = sl.off_reads + up256((size_t)n_reads * sizeof(SegRead));
+  sl.off_aux = sl.off_feat + up256((size_t)N * kFeat * 4);
+  sl.off_bases = sl.off_aux + (with_stats ? up256((size_t)n_reads * sizeof(StatAux)) : 0);
+  sl.off_noff = sl.off_bases + (mr ? up256((size_t)N) : 0);
+  sl.off_names = sl.off_noff + (records ? up256(((size_t)n_reads + 1) * 8) : 0);
+  sl.off_toff = sl.off_names + (records ? up256((size_t)mr->name_off[n_reads]) : 0);
+  sl.off_truth = sl.off_toff + (accuracy ? up256(((size_t)n_reads + 1) * 8) : 0);
+  const size_t in_bytes = sl.off_truth + (accuracy ? up256((size_t)mr->truth_off[n_reads]) : 0);
   sl.rows = ((size_t)sl.n + kRowPad - 1) / kRowPad * kRowPad;
   const size_t out_bytes = 64 + sl.rows * kOutBytes;
   if (!sl.ev_in) {
@@ -3056,9 +3120,8 @@ int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32
   const int64_t max_len = stats_check(h, reads, n_reads, last_dur, on.data());
   if (max_len < 0) return NRV_E_INVALID;
   // one block of its own for everything the kernels write besides the descriptors: [aux | scratch | mean | std | feat]
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_scr = up((size_t)n_reads * sizeof(StatAux)), o_mean = o_scr + up((size_t)n_reads * kStatWords * 4);
-  const size_t o_std = o_mean + up((size_t)N * 8), o_feat = o_std + up((size_t)N * 8), bytes = o_feat + up((size_t)N * kFeat * 4);
+  const size_t o_scr = up256((size_t)n_reads * sizeof(StatAux)), o_mean = o_scr + up256((size_t)n_reads * kStatWords * 4);
+  const size_t o_std = o_mean + up256((size_t)N * 8), o_feat = o_std + up256((size_t)N * 8), bytes = o_feat + up256((size_t)N * kFeat * 4);
   std::vector<StatAux> ax((size_t)n_reads);
   for (int r = 0; r < n_reads; ++r) ax[r] = StatAux{last_dur[r], 1};
   std::vector<float> feat((size_t)N * kFeat);
@@ -3141,57 +3204,40 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
   }
   if (o.edit_off && !o.edits) { h->err = "nrv_merge_calls_edits: null edits"; return NRV_E_INVALID; }
   // one block of its own: [reads | bases | a1 | a2 | p1 | p2 | name_off | names | truth_off | truth | merged block]
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const MergeLayout m = merge_layout(N, n, n_reads, o, blob_cap);
   // the rows go up for a quality - and without one where they are given and the report's near-tie column, the edits' conf, the
   // profile or the trim reads them
   const bool have_p = want_q || ((o.report || o.edit_off || o.profile || o.trim) && p1 && p2);
-  const size_t o_b = up((size_t)n_reads * sizeof(SegRead)), o_a1 = o_b + up((size_t)N), o_a2 = o_a1 + up((size_t)n);
-  const size_t o_p1 = o_a2 + up((size_t)n), o_p2 = o_p1 + (have_p ? up((size_t)n * 24) : 0), o_no = o_p2 + (have_p ? up((size_t)n * 20) : 0);
-  const size_t o_nm = o_no + (o.rec_off ? up(((size_t)n_reads + 1) * 8) : 0), o_to = o_nm + (o.rec_off ? up((size_t)more.name_off[n_reads]) : 0);
-  const size_t o_tr = o_to + (o.wants_truth() ? up(((size_t)n_reads + 1) * 8) : 0), o_m = o_tr + (o.wants_truth() ? up((size_t)more.truth_off[n_reads]) : 0);
-  const size_t bytes = o_m + m.bytes;
-  char* d = nullptr;
-  HIPCHK(h, hipMalloc((void**)&d, bytes));
+  const bool records = o.rec_off != nullptr, truth = o.wants_truth();
+  const size_t name_bytes = records ? (size_t)more.name_off[n_reads] : 0, truth_bytes = truth ? (size_t)more.truth_off[n_reads] : 0;
+  const size_t nb = ((size_t)n_reads + 1) * 8;
+  const MergeInLayout l = merge_in_layout((size_t)n_reads, sizeof(SegRead), (size_t)N, (size_t)n, have_p, records, name_bytes, truth,
+                                          truth_bytes, m.bytes);
   std::vector<char> back(m.dl);
-  auto run = [&]() -> int {
-    int rc2 = poison_fill(h, d, bytes, h->stream);
-    if (rc2) return rc2;
-    HIPCHK(h, hipMemcpyAsync(d, rd.data(), (size_t)n_reads * sizeof(SegRead), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d + o_b, bases, (size_t)N, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d + o_a1, a1, (size_t)n, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d + o_a2, a2, (size_t)n, hipMemcpyHostToDevice, h->stream));
-    if (have_p) {
-      HIPCHK(h, hipMemcpyAsync(d + o_p1, p1, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
-      HIPCHK(h, hipMemcpyAsync(d + o_p2, p2, (size_t)n * 20, hipMemcpyHostToDevice, h->stream));
-    }
-    if (o.rec_off) {
-      HIPCHK(h, hipMemcpyAsync(d + o_no, more.name_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
-      if (more.name_off[n_reads] > 0) HIPCHK(h, hipMemcpyAsync(d + o_nm, more.names, (size_t)more.name_off[n_reads], hipMemcpyHostToDevice, h->stream));
-    }
-    if (o.wants_truth()) {
-      HIPCHK(h, hipMemcpyAsync(d + o_to, more.truth_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
-      if (more.truth_off[n_reads] > 0) HIPCHK(h, hipMemcpyAsync(d + o_tr, more.truth, (size_t)more.truth_off[n_reads], hipMemcpyHostToDevice, h->stream));
-    }
-    const MergeView v{(const SegRead*)d, n_reads, N, (const unsigned char*)(d + o_b), (const signed char*)(d + o_a1),
-                      (const signed char*)(d + o_a2), have_p ? (const float*)(d + o_p1) : nullptr,
-                      have_p ? (const float*)(d + o_p2) : nullptr, (const long long*)(d + o_no), (const unsigned char*)(d + o_nm), d + o_m,
-                      (const unsigned char*)(d + o_tr), (const long long*)(d + o_to)};
+  hipStream_t const s = h->stream;
+  return with_block(h, l.bytes, s, [&](char* d) -> int {
+    int rc2;
+    if ((rc2 = put(h, d + l.reads, rd.data(), (size_t)n_reads * sizeof(SegRead), s)) || (rc2 = put(h, d + l.bases, bases, (size_t)N, s)) ||
+        (rc2 = put(h, d + l.a1, a1, (size_t)n, s)) || (rc2 = put(h, d + l.a2, a2, (size_t)n, s)) ||
+        (rc2 = put(h, d + l.p1, p1, have_p ? (size_t)n * 24 : 0, s)) || (rc2 = put(h, d + l.p2, p2, have_p ? (size_t)n * 20 : 0, s)) ||
+        (rc2 = put(h, d + l.name_off, more.name_off, records ? nb : 0, s)) || (rc2 = put(h, d + l.names, more.names, name_bytes, s)) ||
+        (rc2 = put(h, d + l.truth_off, more.truth_off, truth ? nb : 0, s)) || (rc2 = put(h, d + l.truth, more.truth, truth_bytes, s)))
+      return rc2;
+    const MergeView v{(const SegRead*)(d + l.reads), n_reads, N, (const unsigned char*)(d + l.bases), (const signed char*)(d + l.a1),
+                      (const signed char*)(d + l.a2), have_p ? (const float*)(d + l.p1) : nullptr,
+                      have_p ? (const float*)(d + l.p2) : nullptr, (const long long*)(d + l.name_off), (const unsigned char*)(d + l.names),
+                      d + l.merged, (const unsigned char*)(d + l.truth), (const long long*)(d + l.truth_off)};
     if ((rc2 = merged_enqueue(h, v, m, o, want_q ? q_thr : nullptr, prof_thr, blob_cap, TrimRule{more.trim_thr, more.Q, more.W, more.min_len})))
       return rc2;
-    HIPCHK(h, hipMemcpyAsync(back.data(), d + o_m, m.dl, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(back.data(), d + l.merged, m.dl, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
     // a test twin, not timed: the used prefix of the edit records in a plain copy, straight into the caller's array
     auto fetch = [&](void* dst, size_t at, size_t bytes) -> int {
-      HIPCHK(h, hipMemcpy(dst, d + o_m + at, bytes, hipMemcpyDeviceToHost));
+      HIPCHK(h, hipMemcpy(dst, d + l.merged + at, bytes, hipMemcpyDeviceToHost));
       return NRV_OK;
     };
     return merged_collect(h, "nrv_merge_calls", "nrv_merge_calls_edits", back.data(), v, m, o, want_q, blob_cap, fetch);
-  };
-  rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);
-  (void)hipFree(d);
-  return rc;
+  });
 }
 
 int nrv_merge_calls(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
@@ -3280,139 +3326,46 @@ int nrv_merge_calls_infix(nrv_handle* h, const uint8_t* bases, const int64_t* ev
 
 int nrv_edit_distance(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
                       int64_t* dist) {
-  int rc = check_handle(h);
-  if (rc) return rc;
-  if (n_pairs < 0 || (n_pairs > 0 && !dist)) { h->err = "nrv_edit_distance: bad arguments"; return NRV_E_INVALID; }
-  if (!truth_ok(a, a_off, n_pairs) || !truth_ok(b, b_off, n_pairs)) {
-    h->err = "nrv_edit_distance: null sequences / offsets, offsets that do not ascend from 0, or a sequence of 2^31 - 64 characters and more";
-    return NRV_E_INVALID;
-  }
-  if (n_pairs == 0) return NRV_OK;
-  const int64_t ta = a_off[n_pairs], tb = b_off[n_pairs];
-  // one block of its own: [a_off | b_off | a | b | hc | dist]
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t nb = ((size_t)n_pairs + 1) * 8;
-  const size_t o_bo = up(nb), o_a = o_bo + up(nb), o_b = o_a + up((size_t)ta), o_hc = o_b + up((size_t)tb), o_d = o_hc + up((size_t)tb);
-  const size_t bytes = o_d + up((size_t)n_pairs * 8);
-  char* d = nullptr;
-  HIPCHK(h, hipMalloc((void**)&d, bytes));
-  auto run = [&]() -> int {
-    int rc2 = poison_fill(h, d, bytes, h->stream);
-    if (rc2) return rc2;
-    HIPCHK(h, hipMemcpyAsync(d, a_off, nb, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d + o_bo, b_off, nb, hipMemcpyHostToDevice, h->stream));
-    if (ta > 0) HIPCHK(h, hipMemcpyAsync(d + o_a, a, (size_t)ta, hipMemcpyHostToDevice, h->stream));
-    if (tb > 0) HIPCHK(h, hipMemcpyAsync(d + o_b, b, (size_t)tb, hipMemcpyHostToDevice, h->stream));
+  const PairDoor w{"nrv_edit_distance: bad arguments", nullptr,
+                   "nrv_edit_distance: null sequences / offsets, offsets that do not ascend from 0, or a sequence of 2^31 - 64 characters and more",
+                   nullptr, 1, 1, {dist}};
+  return pair_door(h, a, a_off, b, b_off, n_pairs, w, [&](const PairArgs& p, char* hc, long long* const* out) {
     AlignArgs k;
-    k.n_reads = n_pairs; k.kinds = 1;
-    k.truth = (const unsigned char*)(d + o_a); k.truth_off = (const long long*)d;
-    k.reads = nullptr; k.bases = nullptr; k.cap0 = 0; k.hc0 = nullptr;
-    k.off = (const long long*)(d + o_bo); k.seq = (const unsigned char*)(d + o_b); k.cap1 = tb;
-    k.hc1 = (unsigned char*)(d + o_hc);
-    k.accu = nullptr; k.dist = (long long*)(d + o_d);
-    if ((rc2 = align_enqueue(h, k))) return rc2;
-    HIPCHK(h, hipMemcpyAsync(dist, d + o_d, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return NRV_OK;
-  };
-  rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);
-  (void)hipFree(d);
-  return rc;
+    static_cast<PairArgs&>(k) = p;
+    k.hc0 = nullptr; k.hc1 = (unsigned char*)hc;
+    k.accu = nullptr; k.dist = out[0];
+    return align_enqueue(h, k);
+  });
 }
 
 int nrv_edit_classes(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
                      int64_t* dist, int64_t* match) {
-  int rc = check_handle(h);
-  if (rc) return rc;
-  if (n_pairs < 0 || (n_pairs > 0 && (!dist || !match))) { h->err = "nrv_edit_classes: bad arguments"; return NRV_E_INVALID; }
-  if (!truth_ok(a, a_off, n_pairs) || !truth_ok(b, b_off, n_pairs)) {
-    h->err = "nrv_edit_classes: null sequences / offsets, offsets that do not ascend from 0, or a sequence of 2^31 - 64 characters and more";
-    return NRV_E_INVALID;
-  }
-  if (n_pairs == 0) return NRV_OK;
-  const int64_t ta = a_off[n_pairs], tb = b_off[n_pairs];
-  // one block of its own: [a_off | b_off | a | b | hc8 | dist | match]
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t nb = ((size_t)n_pairs + 1) * 8, nd = up((size_t)n_pairs * 8);
-  const size_t o_bo = up(nb), o_a = o_bo + up(nb), o_b = o_a + up((size_t)ta), o_hc = o_b + up((size_t)tb), o_d = o_hc + up((size_t)tb * 8);
-  const size_t bytes = o_d + 2 * nd;
-  char* d = nullptr;
-  HIPCHK(h, hipMalloc((void**)&d, bytes));
-  auto run = [&]() -> int {
-    int rc2 = poison_fill(h, d, bytes, h->stream);
-    if (rc2) return rc2;
-    HIPCHK(h, hipMemcpyAsync(d, a_off, nb, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d + o_bo, b_off, nb, hipMemcpyHostToDevice, h->stream));
-    if (ta > 0) HIPCHK(h, hipMemcpyAsync(d + o_a, a, (size_t)ta, hipMemcpyHostToDevice, h->stream));
-    if (tb > 0) HIPCHK(h, hipMemcpyAsync(d + o_b, b, (size_t)tb, hipMemcpyHostToDevice, h->stream));
+  const PairDoor w{"nrv_edit_classes: bad arguments", nullptr,
+                   "nrv_edit_classes: null sequences / offsets, offsets that do not ascend from 0, or a sequence of 2^31 - 64 characters and more",
+                   nullptr, 8, 2, {dist, match}};
+  return pair_door(h, a, a_off, b, b_off, n_pairs, w, [&](const PairArgs& p, char* hc, long long* const* out) {
     ErrclassArgs k;
-    k.n_reads = n_pairs; k.kinds = 1;
-    k.truth = (const unsigned char*)(d + o_a); k.truth_off = (const long long*)d;
-    k.reads = nullptr; k.bases = nullptr; k.cap0 = 0; k.hc0 = nullptr;
-    k.off = (const long long*)(d + o_bo); k.seq = (const unsigned char*)(d + o_b); k.cap1 = tb;
-    k.hc1 = (long long*)(d + o_hc);
-    k.ecls = nullptr; k.dist = (long long*)(d + o_d); k.match = (long long*)(d + o_d + nd);
-    if ((rc2 = errclass_enqueue(h, k))) return rc2;
-    HIPCHK(h, hipMemcpyAsync(dist, d + o_d, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(match, d + o_d + nd, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return NRV_OK;
-  };
-  rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);
-  (void)hipFree(d);
-  return rc;
+    static_cast<PairArgs&>(k) = p;
+    k.hc0 = nullptr; k.hc1 = (long long*)hc;
+    k.ecls = nullptr; k.dist = out[0]; k.match = out[1];
+    return errclass_enqueue(h, k);
+  });
 }
 
 int nrv_infix_classes(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
                       int reverse, int64_t* dist, int64_t* match, int64_t* start, int64_t* end) {
-  int rc = check_handle(h);
-  if (rc) return rc;
-  if (n_pairs < 0 || (n_pairs > 0 && (!dist || !match || !start || !end))) { h->err = "nrv_infix_classes: bad arguments"; return NRV_E_INVALID; }
-  if (reverse != 0 && reverse != 1) { h->err = "nrv_infix_classes: reverse must be 0 or 1"; return NRV_E_INVALID; }
-  if (!truth_ok(a, a_off, n_pairs) || !truth_ok(b, b_off, n_pairs)) {
-    h->err = "nrv_infix_classes: null sequences / offsets, or offsets that do not ascend from 0";
-    return NRV_E_INVALID;
-  }
-  if (!infix_lengths_ok(a_off, n_pairs, b_off)) {
-    h->err = "nrv_infix_classes: a truth region, or a read that has one, above NRV_INFIX_MAX_LEN = 2^21 - 1 characters";
-    return NRV_E_INVALID;
-  }
-  if (n_pairs == 0) return NRV_OK;
-  const int64_t ta = a_off[n_pairs], tb = b_off[n_pairs];
-  // one block of its own: [a_off | b_off | a | b | hc | dist | match | start | end]
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t nb = ((size_t)n_pairs + 1) * 8, nd = up((size_t)n_pairs * 8);
-  const size_t o_bo = up(nb), o_a = o_bo + up(nb), o_b = o_a + up((size_t)ta), o_hc = o_b + up((size_t)tb), o_d = o_hc + up((size_t)tb * 8);
-  const size_t bytes = o_d + 4 * nd;
-  char* d = nullptr;
-  HIPCHK(h, hipMalloc((void**)&d, bytes));
-  auto run = [&]() -> int {
-    int rc2 = poison_fill(h, d, bytes, h->stream);
-    if (rc2) return rc2;
-    HIPCHK(h, hipMemcpyAsync(d, a_off, nb, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d + o_bo, b_off, nb, hipMemcpyHostToDevice, h->stream));
-    if (ta > 0) HIPCHK(h, hipMemcpyAsync(d + o_a, a, (size_t)ta, hipMemcpyHostToDevice, h->stream));
-    if (tb > 0) HIPCHK(h, hipMemcpyAsync(d + o_b, b, (size_t)tb, hipMemcpyHostToDevice, h->stream));
+  const PairDoor w{"nrv_infix_classes: bad arguments", (reverse != 0 && reverse != 1) ? "nrv_infix_classes: reverse must be 0 or 1" : nullptr,
+                   "nrv_infix_classes: null sequences / offsets, or offsets that do not ascend from 0",
+                   "nrv_infix_classes: a truth region, or a read that has one, above NRV_INFIX_MAX_LEN = 2^21 - 1 characters",
+                   8, 4, {dist, match, start, end}};
+  return pair_door(h, a, a_off, b, b_off, n_pairs, w, [&](const PairArgs& p, char* hc, long long* const* out) {
     InfixArgs k;
-    k.n_reads = n_pairs; k.kinds = 1; k.strands = 1; k.reverse = reverse;
-    k.truth = (const unsigned char*)(d + o_a); k.truth_off = (const long long*)d;
-    k.reads = nullptr; k.bases = nullptr; k.cap0 = 0; k.hc0 = nullptr; k.hs0 = 0;
-    k.off = (const long long*)(d + o_bo); k.seq = (const unsigned char*)(d + o_b); k.cap1 = tb;
-    k.hc1 = (long long*)(d + o_hc); k.hs1 = 0;          // one strand per call: one set of carry words
-    k.infx = nullptr;
-    k.dist = (long long*)(d + o_d); k.match = (long long*)(d + o_d + nd); k.start = (long long*)(d + o_d + 2 * nd); k.end = (long long*)(d + o_d + 3 * nd);
-    if ((rc2 = infix_enqueue(h, k))) return rc2;
-    int64_t* const outs[4] = {dist, match, start, end};
-    for (int q = 0; q < 4; ++q) HIPCHK(h, hipMemcpyAsync(outs[q], d + o_d + (size_t)q * nd, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return NRV_OK;
-  };
-  rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);
-  (void)hipFree(d);
-  return rc;
+    static_cast<PairArgs&>(k) = p;
+    k.strands = 1; k.reverse = reverse;
+    k.hc0 = nullptr; k.hs0 = 0; k.hc1 = (long long*)hc; k.hs1 = 0;          // one strand per call: one set of carry words
+    k.infx = nullptr; k.dist = out[0]; k.match = out[1]; k.start = out[2]; k.end = out[3];
+    return infix_enqueue(h, k);
+  });
 }
 
 // labels_kernel + labels_walk_kernel (nrv_labels.h) on the pairs of one batch, the walk behind the forward pass on the labels' stream
@@ -3462,11 +3415,9 @@ int nrv_align_labels(nrv_handle* h, const uint8_t* a, const int64_t* a_off, cons
   }
   batch_end.push_back(n_pairs);
   // the handle's block: [a_off | b_off | start | end | dir_off | reverse | a | b | hc | labels | summary | direction words]
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t nb = ((size_t)n_pairs + 1) * 8, np8 = up((size_t)n_pairs * 8);
-  const size_t o_bo = up(nb), o_st = o_bo + up(nb), o_en = o_st + np8, o_do = o_en + np8, o_rv = o_do + np8, o_a = o_rv + up((size_t)n_pairs);
-  const size_t o_b = o_a + up((size_t)ta), o_hc = o_b + up((size_t)tb), o_lab = o_hc + up((size_t)tb * 8), o_sum = o_lab + up((size_t)tb);
-  const size_t o_dir = o_sum + up((size_t)n_pairs * kLabelCols * 8), bytes = o_dir + up(max_words * 4);
+  const size_t nb = ((size_t)n_pairs + 1) * 8, np8 = (size_t)n_pairs * 8;
+  const LabelsLayout l = labels_layout((size_t)n_pairs, (size_t)ta, (size_t)tb, kLabelCols, max_words);
+  const size_t bytes = l.bytes;
   if (!h->lab_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->lab_stream, hipStreamNonBlocking));
   if (bytes > h->cap_lab) {                                // grown on demand; the old block is retired (no hipFree on this path)
     const size_t want = std::max(bytes, h->cap_lab + h->cap_lab / 2);
@@ -3479,29 +3430,25 @@ int nrv_align_labels(nrv_handle* h, const uint8_t* a, const int64_t* a_off, cons
   hipStream_t const s = h->lab_stream;
   auto run = [&]() -> int {
     int rc2 = poison_fill(h, d, bytes, s);                // NRV_POISON: the part this call uses
-    if (rc2) return rc2;
-    HIPCHK(h, hipMemcpyAsync(d, a_off, nb, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d + o_bo, b_off, nb, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d + o_st, start, (size_t)n_pairs * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d + o_en, end, (size_t)n_pairs * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d + o_do, dir_off.data(), (size_t)n_pairs * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d + o_rv, reverse, (size_t)n_pairs, hipMemcpyHostToDevice, s));
-    if (ta > 0) HIPCHK(h, hipMemcpyAsync(d + o_a, a, (size_t)ta, hipMemcpyHostToDevice, s));
-    if (tb > 0) HIPCHK(h, hipMemcpyAsync(d + o_b, b, (size_t)tb, hipMemcpyHostToDevice, s));
+    if (rc2 || (rc2 = put(h, d + l.a_off, a_off, nb, s)) || (rc2 = put(h, d + l.b_off, b_off, nb, s)) ||
+        (rc2 = put(h, d + l.start, start, np8, s)) || (rc2 = put(h, d + l.end, end, np8, s)) ||
+        (rc2 = put(h, d + l.dir_off, dir_off.data(), np8, s)) || (rc2 = put(h, d + l.reverse, reverse, (size_t)n_pairs, s)) ||
+        (rc2 = put(h, d + l.a, a, (size_t)ta, s)) || (rc2 = put(h, d + l.b, b, (size_t)tb, s)))
+      return rc2;
     LabelsArgs k;
-    k.truth = (const unsigned char*)(d + o_a); k.truth_off = (const long long*)d;
-    k.seq = (const unsigned char*)(d + o_b); k.off = (const long long*)(d + o_bo);
-    k.reverse = (const unsigned char*)(d + o_rv); k.start = (const long long*)(d + o_st); k.end = (const long long*)(d + o_en);
-    k.hc = (long long*)(d + o_hc); k.dirw = (unsigned*)(d + o_dir); k.dir_off = (const long long*)(d + o_do);
-    k.labels = (unsigned char*)(d + o_lab); k.summary = (long long*)(d + o_sum);
+    k.truth = (const unsigned char*)(d + l.a); k.truth_off = (const long long*)(d + l.a_off);
+    k.seq = (const unsigned char*)(d + l.b); k.off = (const long long*)(d + l.b_off);
+    k.reverse = (const unsigned char*)(d + l.reverse); k.start = (const long long*)(d + l.start); k.end = (const long long*)(d + l.end);
+    k.hc = (long long*)(d + l.hc); k.dirw = (unsigned*)(d + l.dir); k.dir_off = (const long long*)(d + l.dir_off);
+    k.labels = (unsigned char*)(d + l.labels); k.summary = (long long*)(d + l.summary);
     int p0 = 0;
     for (int p1 : batch_end) {                            // in stream order: a batch's walk ends before the next forward pass stores
       k.pair0 = p0; k.n_pairs = p1 - p0;
       if ((rc2 = labels_enqueue(h, k))) return rc2;
       p0 = p1;
     }
-    if (tb > 0) HIPCHK(h, hipMemcpyAsync(labels, d + o_lab, (size_t)tb, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(summary, d + o_sum, (size_t)n_pairs * kLabelCols * 8, hipMemcpyDeviceToHost, s));
+    if (tb > 0) HIPCHK(h, hipMemcpyAsync(labels, d + l.labels, (size_t)tb, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(summary, d + l.summary, (size_t)n_pairs * kLabelCols * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     return NRV_OK;
   };
@@ -3519,30 +3466,20 @@ int nrv_trim_reads(nrv_handle* h, const uint8_t* qual, const int64_t* off, int n
   if (n_reads == 0) return NRV_OK;
   const int64_t total = off[n_reads];
   if (total > 0 && !qual) { h->err = "nrv_trim_reads: null qual"; return NRV_E_INVALID; }
-  // one block of its own: [off | qual | acc | trim]
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t nb = ((size_t)n_reads + 1) * 8, tb = (size_t)n_reads * 16;
-  const size_t o_q = up(nb), o_acc = o_q + up((size_t)total), o_trim = o_acc + up(tb), bytes = o_trim + up(tb);
-  char* d = nullptr;
-  HIPCHK(h, hipMalloc((void**)&d, bytes));
-  auto run = [&]() -> int {
-    int rc2 = poison_fill(h, d, bytes, h->stream);
-    if (rc2) return rc2;
-    HIPCHK(h, hipMemcpyAsync(d, off, nb, hipMemcpyHostToDevice, h->stream));
-    if (total > 0) HIPCHK(h, hipMemcpyAsync(d + o_q, qual, (size_t)total, hipMemcpyHostToDevice, h->stream));
+  const TrimLayout l = trim_layout((size_t)n_reads, (size_t)total);
+  hipStream_t const s = h->stream;
+  return with_block(h, l.bytes, s, [&](char* d) -> int {
+    int rc2;
+    if ((rc2 = put(h, d + l.off, off, ((size_t)n_reads + 1) * 8, s)) || (rc2 = put(h, d + l.qual, qual, (size_t)total, s))) return rc2;
     TrimArgs a;
     a.n_reads = n_reads; a.Q = Q; a.W = W; a.bias = 33;
-    a.off = (const long long*)d; a.q = (const unsigned char*)(d + o_q); a.cap = total;
-    a.acc = (unsigned long long*)(d + o_acc); a.trim = (long long*)(d + o_trim);
+    a.off = (const long long*)(d + l.off); a.q = (const unsigned char*)(d + l.qual); a.cap = total;
+    a.acc = (unsigned long long*)(d + l.acc); a.trim = (long long*)(d + l.trim);
     if ((rc2 = trim_bounds_enqueue(h, a))) return rc2;
-    HIPCHK(h, hipMemcpyAsync(trim, d + o_trim, tb, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(trim, d + l.trim, (size_t)n_reads * 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
     return NRV_OK;
-  };
-  rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);
-  (void)hipFree(d);
-  return rc;
+  });
 }
 
 int nrv_pack_records(nrv_handle* h, const uint8_t* seq, const uint8_t* qual, const int64_t* off, int n_reads,
@@ -3572,44 +3509,29 @@ int nrv_pack_records_trim(nrv_handle* h, const uint8_t* seq, const uint8_t* qual
   if ((total_in > 0 && !seq) || (cap > 0 && !blob)) { h->err = "nrv_pack_records: null seq / blob"; return NRV_E_INVALID; }
   if (cap >= ((size_t)1 << 32)) { h->err = "nrv_pack_records: records of 4 GiB and more in one call"; return NRV_E_INVALID; }
   if (n_reads == 0) { rec_off[0] = 0; return NRV_OK; }
-  // one block of its own: [off | name_off | names | seq | qual | rec_off | blob]
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t nb = ((size_t)n_reads + 1) * 8;
-  const size_t o_noff = up(nb), o_names = o_noff + up(nb), o_seq = o_names + up((size_t)name_bytes), o_qual = o_seq + up((size_t)total_in);
-  const size_t o_roff = o_qual + (fastq ? up((size_t)total_in) : 0), o_blob = o_roff + up(nb), o_trim = o_blob + up(cap);
-  const size_t bytes = o_trim + (trim ? up((size_t)n_reads * 16) : 0);
-  char* d = nullptr;
-  HIPCHK(h, hipMalloc((void**)&d, bytes));
-  auto run = [&]() -> int {
-    int rc2 = poison_fill(h, d, bytes, h->stream);
-    if (rc2) return rc2;
-    HIPCHK(h, hipMemcpyAsync(d, off, nb, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d + o_noff, name_off, nb, hipMemcpyHostToDevice, h->stream));
-    if (name_bytes > 0) HIPCHK(h, hipMemcpyAsync(d + o_names, names, (size_t)name_bytes, hipMemcpyHostToDevice, h->stream));
-    if (total_in > 0) HIPCHK(h, hipMemcpyAsync(d + o_seq, seq, (size_t)total_in, hipMemcpyHostToDevice, h->stream));
-    if (fastq && total_in > 0) HIPCHK(h, hipMemcpyAsync(d + o_qual, qual, (size_t)total_in, hipMemcpyHostToDevice, h->stream));
+  const RecordLayout l = record_layout((size_t)n_reads, (size_t)name_bytes, (size_t)total_in, fastq, cap, trim != nullptr);
+  hipStream_t const s = h->stream;
+  return with_block(h, l.bytes, s, [&](char* d) -> int {
+    int rc2;
+    if ((rc2 = put(h, d + l.off, off, nb, s)) || (rc2 = put(h, d + l.name_off, name_off, nb, s)) ||
+        (rc2 = put(h, d + l.names, names, (size_t)name_bytes, s)) || (rc2 = put(h, d + l.seq, seq, (size_t)total_in, s)) ||
+        (rc2 = put(h, d + l.qual, qual, fastq ? (size_t)total_in : 0, s)) || (rc2 = put(h, d + l.trim, trim, trim ? (size_t)n_reads * 16 : 0, s)))
+      return rc2;
     PackArgs a;
     a.n_reads = n_reads; a.fastq = fastq ? 1 : 0;
-    a.off = (const long long*)d; a.name_off = (const long long*)(d + o_noff); a.names = (const unsigned char*)(d + o_names);
-    a.seq = (const unsigned char*)(d + o_seq); a.qual = (const unsigned char*)(d + o_qual);
-    a.rec_off = (long long*)(d + o_roff); a.blob = (unsigned char*)(d + o_blob); a.cap = cap;
-    a.trim = nullptr; a.min_len = min_len;
-    if (trim) {
-      HIPCHK(h, hipMemcpyAsync(d + o_trim, trim, (size_t)n_reads * 16, hipMemcpyHostToDevice, h->stream));
-      a.trim = (const long long*)(d + o_trim);
-    }
+    a.off = (const long long*)(d + l.off); a.name_off = (const long long*)(d + l.name_off); a.names = (const unsigned char*)(d + l.names);
+    a.seq = (const unsigned char*)(d + l.seq); a.qual = (const unsigned char*)(d + l.qual);
+    a.rec_off = (long long*)(d + l.rec_off); a.blob = (unsigned char*)(d + l.blob); a.cap = cap;
+    a.trim = trim ? (const long long*)(d + l.trim) : nullptr; a.min_len = min_len;
     if ((rc2 = pack_enqueue(h, a))) return rc2;
-    HIPCHK(h, hipMemcpyAsync(rec_off, d + o_roff, nb, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(rec_off, d + l.rec_off, nb, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
     const int64_t n_b = rec_off[n_reads];                       // the used prefix of the blob, once the total is known
     if (n_b < 0 || (uint64_t)n_b > cap) { h->err = "nrv_pack_records: records out of range"; return NRV_E_HIP; }
-    if (n_b > 0) HIPCHK(h, hipMemcpy(blob, d + o_blob, (size_t)n_b, hipMemcpyDeviceToHost));
+    if (n_b > 0) HIPCHK(h, hipMemcpy(blob, d + l.blob, (size_t)n_b, hipMemcpyDeviceToHost));
     return NRV_OK;
-  };
-  rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);
-  (void)hipFree(d);
-  return rc;
+  });
 }
 
 int nrv_saturated(nrv_handle* h, int64_t* pending, int64_t* reruns) {

@@ -37,16 +37,7 @@ constexpr int kErrclassR = 16;                         // truth characters (and 
 constexpr int kErrclassStripe = 64 * kErrclassR;       // truth characters per stripe
 constexpr long long kEdit = 1ll << 32;                 // one edit in a packed cell
 
-struct ErrclassArgs {
-  int n_reads;                           // pairs of the unit door; reads of a merged call (two waves each)
-  int kinds;                             // 2: a merged call, ecls; 1: the unit door (texts by off / seq alone), dist / match
-  const unsigned char* truth;
-  const long long* truth_off;            // [n_reads + 1] ascending from 0
-  const SegRead* reads;                  // kind 0: bases[ev_off .. ev_off + ev_len)
-  const unsigned char* bases;
-  const long long* off;                  // kind 1 (and the unit door): seq[off[r] .. off[r + 1])
-  const unsigned char* seq;
-  long long cap0, cap1;                  // characters bases / seq hold: a text that is not inside them counts as empty
+struct ErrclassArgs : PairArgs {         // (nrv_align.h)
   long long *hc0, *hc1;                  // carry words, one per text character: hc0[ev_off + j], hc1[off[r] + j]
   unsigned long long* ecls;              // [n_reads][kErrclassCols] (kinds == 2)
   long long *dist, *match;               // [n_reads] each (kinds == 1): -1 / -1 for an empty truth
@@ -57,8 +48,8 @@ __global__ void __launch_bounds__(64) errclass_kernel(const ErrclassArgs a) {
   const int lane = threadIdx.x;
   const int r = (int)(blockIdx.x / (unsigned)a.kinds), kind = a.kinds == 2 ? (int)(blockIdx.x & 1u) : 1;
   if (r >= a.n_reads) return;
-  const long long t_at = a.truth_off[r];
-  const int m = (int)(a.truth_off[r + 1] - t_at);
+  const PairText p = pair_text(a, r, kind);
+  const int m = p.m, n = p.n;
   if (m <= 0) {                                           // no truth: the row is zeros and nothing is formed
     if (lane == 0) {
       if (a.kinds == 2) {
@@ -70,19 +61,8 @@ __global__ void __launch_bounds__(64) errclass_kernel(const ErrclassArgs a) {
     }
     return;
   }
-  const unsigned char* t = a.truth + t_at;
-  const unsigned char* s;
-  long long* hc;
-  int n;
-  if (kind == 0) {
-    const SegRead rd = a.reads[r];
-    const bool ok = rd.ev_off >= 0 && rd.ev_len >= 0 && rd.ev_off + rd.ev_len <= a.cap0;
-    s = a.bases + (ok ? rd.ev_off : 0); hc = a.hc0 + (ok ? rd.ev_off : 0); n = ok ? (int)rd.ev_len : 0;
-  } else {
-    const long long o0 = a.off[r], o1 = a.off[r + 1];
-    const bool ok = o0 >= 0 && o1 >= o0 && o1 <= a.cap1;
-    s = a.seq + (ok ? o0 : 0); hc = a.hc1 + (ok ? o0 : 0); n = ok ? (int)(o1 - o0) : 0;
-  }
+  const unsigned char *t = p.t, *s = p.s;
+  long long* hc = (kind == 0 ? a.hc0 : a.hc1) + p.at;
   long long res = 0;                                      // W[m][n], picked by the lane that owns row m
   int res_lane = 0;
   for (long long base = 0; base < m; base += kErrclassStripe) {

@@ -50,18 +50,9 @@ constexpr int kInfixMaxLen = (1 << 21) - 1;            // of a region and of a r
 constexpr long long kInfixEdit = 1ll << 42;            // one edit in a packed cell
 constexpr long long kInfixMatch = 1ll << 21;           // one matched column
 
-struct InfixArgs {
-  int n_reads;                           // pairs of the unit door; reads of a merged call (kinds x strands waves each)
-  int kinds;                             // 2: a merged call, infx; 1: the unit door (texts by off / seq alone), dist .. end
+struct InfixArgs : PairArgs {            // (nrv_align.h)
   int strands;                           // a merged call: 1 or 2 waves per (read, kind); the unit door: 1
   int reverse;                           // the unit door's strand
-  const unsigned char* truth;
-  const long long* truth_off;            // [n_reads + 1] ascending from 0
-  const SegRead* reads;                  // kind 0: bases[ev_off .. ev_off + ev_len)
-  const unsigned char* bases;
-  const long long* off;                  // kind 1 (and the unit door): seq[off[r] .. off[r + 1])
-  const unsigned char* seq;
-  long long cap0, cap1;                  // characters bases / seq hold: a text that is not inside them counts as empty
   long long *hc0, *hc1;                  // carry words, one per text character and strand: hc0[rev * hs0 + ev_off + j], hc1[rev * hs1 + off[r] + j]
   long long hs0, hs1;                    // words between the forward and the reverse strand's carry words
   unsigned long long* infx;              // [n_reads][kInfixCols] (kinds == 2)
@@ -89,8 +80,8 @@ __global__ void __launch_bounds__(64) infix_kernel(const InfixArgs a) {
   if (r >= a.n_reads) return;
   const int kind = a.kinds == 2 ? sub / a.strands : 1;
   const int rev = a.kinds == 2 ? sub % a.strands : (a.reverse != 0);
-  const long long t_at = a.truth_off[r];
-  const int m = (int)(a.truth_off[r + 1] - t_at);
+  const PairText p = pair_text(a, r, kind, kInfixMaxLen);
+  const int m = p.m, n = p.n;
   if (m <= 0) {                                           // no truth: zeros (the unit door: -1) and nothing is formed
     if (lane == 0) {
       const long long v = a.kinds == 2 ? 0 : -1;
@@ -98,19 +89,8 @@ __global__ void __launch_bounds__(64) infix_kernel(const InfixArgs a) {
     }
     return;
   }
-  const unsigned char* t = a.truth + t_at;
-  const unsigned char* s;
-  long long* hc;
-  int n;
-  if (kind == 0) {
-    const SegRead rd = a.reads[r];
-    const bool ok = rd.ev_off >= 0 && rd.ev_len >= 0 && rd.ev_len <= kInfixMaxLen && rd.ev_off + rd.ev_len <= a.cap0;
-    s = a.bases + (ok ? rd.ev_off : 0); hc = a.hc0 + (rev ? a.hs0 : 0) + (ok ? rd.ev_off : 0); n = ok ? (int)rd.ev_len : 0;
-  } else {
-    const long long o0 = a.off[r], o1 = a.off[r + 1];
-    const bool ok = o0 >= 0 && o1 >= o0 && o1 - o0 <= kInfixMaxLen && o1 <= a.cap1;
-    s = a.seq + (ok ? o0 : 0); hc = a.hc1 + (rev ? a.hs1 : 0) + (ok ? o0 : 0); n = ok ? (int)(o1 - o0) : 0;
-  }
+  const unsigned char *t = p.t, *s = p.s;
+  long long* hc = (kind == 0 ? a.hc0 + (rev ? a.hs0 : 0) : a.hc1 + (rev ? a.hs1 : 0)) + p.at;
   if (n == 0) {                                           // nothing to place: the empty substring at the region's end
     if (lane == 0) infix_store(a, r, kind, rev, m, 0, 0, m, m);
     return;
