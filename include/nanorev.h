@@ -604,6 +604,72 @@ int nrv_infix_classes(nrv_handle* h, const uint8_t* a, const int64_t* a_off, con
 int nrv_align_labels(nrv_handle* h, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off, int n_pairs,
                      const uint8_t* reverse, const int64_t* start, const int64_t* end, uint8_t* labels, int64_t* summary);
 
+/* BOTH CLASSIFIERS SCORED AGAINST PER-BASE LABELS (opt-in; nothing above changes): what Keras' model.evaluate gives for this
+ * pair of models - loss and accuracy per model, the confusion matrices, whether the confidence behind the Phred characters is
+ * calibrated - and, per window, what the merge did to true errors and to correct bases.  The softmax rows of a merged call
+ * never leave the device, so the join with the labels happens there, by ONE launch behind the merge (behind the report where
+ * there is one).  hoststage.score_calls is the definition.  The arguments of nrv_revise_reads_raw_infix_begin - every block of
+ * it may be NULL as there, and here the truth, `truth_off` and `infix` too: the score reads no truth - then, all three required,
+ *   labels     uint8 [N], one byte per event of the call in nrv_align_labels' format (bits 0 .. 2 the code, bit 3 a non-match,
+ *              bit 4 followed by deleted truth); the byte 0xFF means "unlabelled";
+ *   score_thr  float [39] ascending: the thresholds of the calibration bins; the layout of q_thr and independent of it;
+ *   score      uint64 [n_reads][NRV_SCORE_COLS], one row per read.
+ * The rule, integers only.  Read r has n_r = max(ev_len - T, 0) windows; its window i is window w = ev_off + i of the call and
+ * revises event j = (T - 1) / 2 + i of the read.  A window is LABELLED when its event's byte is not 0xFF and its code is
+ * 1 .. 5; only labelled windows are counted.  Per labelled window, with a1 / a2 / p1 / p2 the call's own outputs at w:
+ *   y1 = 0 if bit 4 else code (model 1's six classes), y2 = code - 1 (model 2's five); c1 = clip(a1, 0, 5), c2 = clip(a2, 0, 4);
+ *   bin(p) = #{k : score_thr[k] <= p}, compared in f32 (bin b is Phred b + 1; a NaN lands in bin 0);
+ *   decision d, on the UNCLIPPED x = a1, y = a2 + 1 as in the report: x == y and x >= 2: 0 confirmed where the base of label
+ *     clip(x, 0, 5) ("D-CTGA") is the original base, 1 substituted where not; else x == 0 and y >= 2: 2 inserted; else
+ *     x == 1 and y == 1: 3 deleted; else 4 undecided;
+ *   kind k: 3 (D) if bit 4, else 2 (I) if code == 1, else 1 (X) if bit 3, else 0 (M).
+ * Columns:
+ *     0         windows n_r (stored once)          1  labelled windows
+ *     2 ..  37  confusion of model 1: 2 + 6 y1 + c1
+ *    38 ..  62  confusion of model 2: 38 + 5 y2 + c2
+ *    63 .. 102  model 1 calibration: windows per bin(p1[w][c1]);   103 .. 142  those of them with c1 == y1
+ *   143 .. 182  model 2 calibration: windows per bin(p2[w][c2]);   183 .. 222  those of them with c2 == y2
+ *   223, 224    sum of nll16(p1[w][y1]), of nll16(p2[w][y2])
+ *   225 .. 244  decision x kind: 225 + 4 d + k
+ *   245         sub_right: d == 1 and clip(x, 0, 5) == code (the agreed base is the truth's)
+ *   246, 247    reserved, 0
+ * nll16(p) is -log2 p in units of 2^-16 bit, from the f32 bit pattern u by integers alone, e = (u >> 23) & 255, m = u & 0x7FFFFF:
+ * the sign bit set, e == 0 or e == 255 (NaN, Inf, zero, denormals, negatives): 127 << 16; e >= 127 (p >= 1): 0; otherwise
+ * y = 2^23 | m, f = 0, sixteen times { y = (y y) >> 23 in 64 bits; f <<= 1; if y >= 2^24 { f |= 1; y >>= 1 } } and
+ * nll16 = ((127 - e) << 16) - f.  It exceeds -65536 log2 p by less than 2 (in its units).  The loss in nats, Keras' categorical
+ * cross-entropy, is column 223 (224) x ln 2 / 65536 / column 1.
+ * Every counter is an integer, so the bytes do not depend on the order of the workgroups.  The labels travel with the call's
+ * one input transfer; the caller's `labels` and `score_thr` are dead once _begin returns.  N <= T: nothing is enqueued; the
+ * block is filled on the host with zeros.  Tickets, the two-calls-in-flight rule, the failure paths and the range-guard re-run
+ * (which zeroes the block and counts again behind the f32 kernels, as the report) are those of nrv_revise_reads_raw_begin;
+ * `score` is filled by nrv_reads_raw_end, downloaded with the call's block, and must stay valid until then.
+ * nrv_revise_reads_raw_score IS _score_begin + _end.  Not timed yet. */
+#define NRV_SCORE_COLS 248
+int nrv_revise_reads_raw_score_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                     const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                     const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                     uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                     nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                     uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                     const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                                     const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, uint64_t* errclass,
+                                     int strands, uint64_t* infix, const uint8_t* labels, const float* score_thr, uint64_t* score,
+                                     int* ticket);
+int nrv_revise_reads_raw_score(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                               const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                               const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                               uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                               nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                               uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                               const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                               const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, uint64_t* errclass,
+                               int strands, uint64_t* infix, const uint8_t* labels, const float* score_thr, uint64_t* score);
+/* nrv_merge_calls with the score, by the kernel nrv_revise_reads_raw_score_begin runs, on calls the host supplies: p1 / p2 may
+ * be NULL (both: columns 63 .. 224 stay 0).  The twin used by the parity tests. */
+int nrv_merge_calls_score(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                          const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                          const uint8_t* labels, const float* score_thr, uint64_t* score);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

@@ -220,7 +220,27 @@ def get_args(argv: Optional[Sequence[str]] = None):
                         "and a line #reads.  With --device_merge the labels of a device call's reads are found on the GPU by one "
                         "call while the next is in flight (not timed yet), everywhere else by the host stage: the same files "
                         "byte for byte.  Off by default; without it nothing changes")
+    p.add_argument("--score", dest="score", default=None, metavar="FILE",
+                   help="with --labels_from: score both classifiers against the per-base labels an earlier --labels run wrote and "
+                        "write the result to FILE (also NRV_SCORE=FILE): what Keras' model.evaluate gives for this pair of models.  "
+                        "Neither --truth nor --infix is needed.  A window counts when the base it revises has a label (clipped ends "
+                        "and bases opposite no A / C / G / T have none).  One header line, one line per input read sorted by file "
+                        "name - name, status (scored; stale_labels: the labels file holds other bases; no_labels: no file; "
+                        "unrevised), windows, labelled, correct1, correct2, acc1, acc2, loss1, loss2 (categorical cross-entropy in "
+                        "nats, from an integer -log2 in units of 2^-16 bit), the twenty counts decision x kind (confirmed, "
+                        "substituted, inserted, deleted, undecided x M, X, I, D: what the merge did to a base that matches, "
+                        "mismatches, is an insertion, is followed by a deletion) and sub_right (substitutions to the truth's base) - "
+                        "then #total, #confusion1 (6 lines: true class x answer), #confusion2 (5 lines), #calibration1 / "
+                        "#calibration2 - per non-empty confidence bin the Phred the quality rule gives it, n, ok and the empirical "
+                        "Phred -10 log10((n - ok + 0.5) / (n + 1)) - and #reads scored / stale_labels / no_labels / unrevised.  With "
+                        "--device_merge the counts are found on the GPU behind the merge (not timed yet), everywhere else by the "
+                        "host stage: the same file byte for byte.  --resume does not work with it.  Off by default; without it "
+                        "nothing changes")
+    p.add_argument("--labels_from", dest="labels_from", default=None, metavar="DIR",
+                   help="with --score: the directory an earlier run's --labels wrote (also NRV_LABELS_FROM=DIR); never this run's own")
     a = p.parse_args(argv)
+    a.score = a.score or (os.environ.get("NRV_SCORE", "").strip() or None)
+    a.labels_from = a.labels_from or (os.environ.get("NRV_LABELS_FROM", "").strip() or None)
     a.infix = a.infix or (os.environ.get("NRV_INFIX", "").strip() or None)
     a.labels = a.labels or (os.environ.get("NRV_LABELS", "").strip() or None)
     a.error_classes = a.error_classes or (os.environ.get("NRV_ERROR_CLASSES", "").strip() or None)
@@ -228,6 +248,16 @@ def get_args(argv: Optional[Sequence[str]] = None):
     a.accuracy = a.accuracy or (os.environ.get("NRV_ACCURACY", "").strip() or None)
     if a.labels and not (a.truth and a.infix):
         print("[！！！Error] --labels goes with --truth and --infix", file=sys.stderr)
+        raise SystemExit(2)
+    if (a.score is None) != (a.labels_from is None):
+        print("[！！！Error] --score goes with --labels_from", file=sys.stderr)
+        raise SystemExit(2)
+    if a.score and a.labels and os.path.abspath(a.labels_from) == os.path.abspath(a.labels):
+        print("[！！！Error] --labels_from cannot be the directory this run's --labels writes: the labels of a read are formed "
+              "after the call that would score it", file=sys.stderr)
+        raise SystemExit(2)
+    if a.score and a.resume:
+        print("[！！！Error] --resume cannot be used with --score: a skipped read's calls are not at hand", file=sys.stderr)
         raise SystemExit(2)
     if a.infix and not a.truth:
         print("[！！！Error] --infix goes with --truth", file=sys.stderr)
@@ -552,6 +582,15 @@ def _load_bundle(jobs, device_stats: bool = False):
             bundle["last_dur"], bundle["device_stats"] = np.ascontiguousarray(nb["last_dur"]), np.ascontiguousarray(nb["device_stats"])
         return entries, bundle
     return _bundle_of([_load_one(j) for j in jobs])
+
+
+def _load_bundle_labelled(jobs, device_stats: bool, labels_dir: str):
+    """`_load_bundle` for a --score run: the label bytes of the bundle's reads are read HERE, in the parser pool beside the
+    parse, and ride with the bundle: bundle["labels"] = (labels uint8[N], flags) as `ScorePart.block` gives them."""
+    entries, bundle = _load_bundle(jobs, True) if device_stats else _load_bundle(jobs)
+    if bundle is not None and _bundle_has_bases(bundle):
+        bundle["labels"] = ScorePart(None, labels_dir).block([entries[i][0] for i in bundle["idx"]], bundle["bases"], bundle["meta"][:, 1])
+    return entries, bundle
 
 
 def _bundle_of(loaded):
@@ -1538,6 +1577,117 @@ def merge_labels(labels_dir: str, names: Sequence[str], log: Callable[[str], Non
     _replace_report(path, out, parts)
 
 
+SCORE_SCORED, SCORE_STALE, SCORE_NO_LABELS = 0, 1, 2
+SCORE_STATUS = {SCORE_SCORED: "scored", SCORE_STALE: "stale_labels", SCORE_NO_LABELS: "no_labels"}
+SCORE_PART_COLS = hs.SCORE_COLS + 1        # a part line's integers: the read's row of the score block, then its flag
+SCORE_HEADER = ("name\tstatus\twindows\tlabelled\tcorrect1\tcorrect2\tacc1\tacc2\tloss1\tloss2\t"
+                + "\t".join(f"{d}_{k}" for d in hs.SCORE_DECISIONS for k in hs.SCORE_KINDS) + "\tsub_right")
+
+
+def score_fields(v) -> List[str]:
+    """The fields of a --score line behind name and status from a row of the score block: integers, and the four figures that
+    follow from integers alone - acc = correct / labelled and loss = nll16 sum x ln 2 / 65536 / labelled (nats), six decimals,
+    `.` without a labelled window."""
+    v = [int(x) for x in v[:hs.SCORE_COLS]]
+    n = v[hs.SC_LABELLED]
+    ok1, ok2 = sum(v[hs.SC_CONF1 + 7 * k] for k in range(6)), sum(v[hs.SC_CONF2 + 6 * k] for k in range(5))
+    ratio = lambda a: f"{a / n:.6f}" if n else "."
+    loss = lambda s: f"{s * math.log(2.0) / 65536.0 / n:.6f}" if n else "."
+    return [str(v[0]), str(n), str(ok1), str(ok2), ratio(ok1), ratio(ok2), loss(v[hs.SC_NLL1]), loss(v[hs.SC_NLL2])] + \
+        [str(x) for x in v[hs.SC_DEC_KIND:hs.SC_DEC_KIND + 20]] + [str(v[hs.SC_SUB_RIGHT])]
+
+
+def _score_closing(t) -> List[str]:
+    """The lines behind #total from the summed block: the two confusion matrices (a line per TRUE class, a column per answer) and,
+    per model, a line per non-empty confidence bin - the Phred the quality rule gives the bin, n, ok and the empirical Phred
+    -10 log10((n - ok + 0.5) / (n + 1)), two decimals."""
+    out = [f"#confusion1\t{k}\t" + "\t".join(str(x) for x in t[hs.SC_CONF1 + 6 * k:hs.SC_CONF1 + 6 * k + 6]) for k in range(6)]
+    out += [f"#confusion2\t{k}\t" + "\t".join(str(x) for x in t[hs.SC_CONF2 + 5 * k:hs.SC_CONF2 + 5 * k + 5]) for k in range(5)]
+    for tag, at_n, at_ok in (("#calibration1", hs.SC_CAL1_N, hs.SC_CAL1_OK), ("#calibration2", hs.SC_CAL2_N, hs.SC_CAL2_OK)):
+        for b in range(hs.SCORE_BINS):
+            n, ok = t[at_n + b], t[at_ok + b]
+            if n:
+                out.append(f"{tag}\t{b + 1}\t{n}\t{ok}\t{-10.0 * math.log10((n - ok + 0.5) / (n + 1)):.2f}")
+    return out
+
+
+class ScorePart(ReportPart):
+    """One process' share of the --score file, and what forms its lines: the label bytes of a read from --labels_from
+    (`read_labels`, `block`), the rows of the host routes (`host_rows`) and of a read written unrevised (`add_unrevised`)."""
+
+    def __init__(self, path: Optional[str], labels_dir: Optional[str], log: Callable[[str], None] = print):
+        super().__init__(path, SCORE_PART_COLS)
+        self.dir, self.log, self.warned = labels_dir, log, False
+
+    def announce(self, fns, flags):
+        """One warning per process, for the first stale labels file it meets."""
+        for fn, f in zip(fns, flags):
+            if f == SCORE_STALE and not self.warned:
+                self.warned = True
+                self.log(f"[！！！Warning] --score: {labels_file(self.dir, fn)} does not hold this read's bases; it is not scored "
+                         "(stale_labels; further ones are not announced)")
+
+    def read_labels(self, fn: str, bases):
+        """(label bytes uint8[n], flag) of a read with the original bases `bases` (uint8): from <stem>_labels.txt where its
+        bases line is the read's; every byte 0xFF where there is no file (no_labels) or it holds other bases (stale_labels).
+        Silent (it also runs in the parser pool): `announce` speaks."""
+        none = np.full(bases.size, hs.SCORE_UNLABELLED, np.uint8)
+        try:
+            with open(labels_file(self.dir, fn)) as fp:
+                lines = fp.read().split("\n")
+        except OSError:
+            return none, SCORE_NO_LABELS
+        try:
+            if lines[1].encode("ascii", "replace") != bases.tobytes():
+                raise ValueError("other bases")
+            return hs.score_labels_from_text(*lines[:5]), SCORE_SCORED
+        except (ValueError, IndexError, TypeError):
+            return none, SCORE_STALE
+
+    def block(self, fns, bases, ev_len):
+        """The labels of a device call: (labels uint8[N], flags)."""
+        b, off = hostlib.bases_u8(bases), np.concatenate([[0], np.cumsum(np.asarray(ev_len, np.int64))])
+        got = [self.read_labels(fn, b[int(off[r]):int(off[r + 1])]) for r, fn in enumerate(fns)]
+        return (np.concatenate([g[0] for g in got]) if got else np.zeros(0, np.uint8)), [g[1] for g in got]
+
+    @staticmethod
+    def rows(block, flags):
+        """A part line's integers per read from a score block (hoststage.score_calls' or the device's)."""
+        return [row + [f] for row, f in zip(np.asarray(block).tolist(), flags)]
+
+    def host_rows(self, T, fns, bases, ev_len, p1, p2, a1, a2, found=None):
+        """The same on a host route, from the calls; found: (labels, flags) where `block` has run for these reads already."""
+        labels, flags = found if found is not None else self.block(fns, bases, ev_len)
+        self.announce(fns, flags)
+        return self.rows(hs.score_calls(hostlib.bases_u8(bases), ev_len, a1, a2, p1, p2, labels, phred_thresholds(), T), flags)
+
+    def add_unrevised(self, fn: str):
+        self.add(fn, False, [0] * SCORE_PART_COLS)
+
+
+def merge_score(path: str, names: Sequence[str], log: Callable[[str], None] = print):
+    """Parent side of --score: the parts as `merge_report` reads them, one line per read of `names` sorted by file name
+    (`score_fields`), then #total - the sums over the scored reads -, the lines of `_score_closing` on those sums and #reads
+    scored / stale_labels / no_labels / unrevised; the file appears by rename and the parts are removed."""
+    rows, parts = _part_rows(path, SCORE_PART_COLS)
+    out, t, counts = [SCORE_HEADER], [0] * hs.SCORE_COLS, [0, 0, 0, 0]
+    for fn in sorted(names):
+        c = rows.get(fn)
+        if c is None:
+            log(f"[！！！Warning] --score: no record for {fn}")
+            c = [fn, "unrevised"] + ["0"] * SCORE_PART_COLS
+        v = [int(x) for x in c[2:]]
+        status = SCORE_STATUS.get(v[-1], "scored") if c[1] == "revised" else "unrevised"
+        counts[3 if status == "unrevised" else v[-1]] += 1
+        out.append("\t".join([fn, status] + score_fields(v)))
+        if status == "scored":
+            t = [a + b for a, b in zip(t, v)]
+    out.append("\t".join(["#total", "scored"] + score_fields(t)))
+    out += _score_closing(t)
+    out.append("#reads\t" + "\t".join(str(x) for x in counts))
+    _replace_report(path, out, parts)
+
+
 def merge_infix(path: str, names: Sequence[str], log: Callable[[str], None] = print):
     """Parent side of --infix: the parts as `merge_report` reads them, one line per read of `names` sorted by file name, then
     #total - over the reads WITH a truth, revised or not, the sums of truth_len and of len, dist and match of both forms (`.` in
@@ -1616,9 +1766,9 @@ def write_edits(edits_dir: str, fast5_fn: str, edits=None, want_qual: bool = Fal
 
 def _host_merge_form(packed):
     """A `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` /
-    `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` / `with_device_infix` tuple back in the form whose call returns (p1, p2, a1, a2): for the paths that
+    `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` / `with_device_infix` / `with_device_score` tuple back in the form whose call returns (p1, p2, a1, a2): for the paths that
     keep the host merge."""
-    if packed is None or len(packed) not in (12, 14, 16, 20, 22, 27, 30, 31, 33):
+    if packed is None or len(packed) not in (12, 14, 16, 20, 22, 27, 30, 31, 33, 36):
         return packed
     return tuple(packed[:7]) if packed[7] is None else tuple(packed[:9])
 
@@ -1634,12 +1784,13 @@ def _bundle_has_bases(bundle) -> bool:
 
 
 def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, report, edits=False, combined=False, summary=False,
-                 trim=False, accuracy=False, error_classes=False, infix=False):
+                 trim=False, accuracy=False, error_classes=False, infix=False, score=False):
     """The one decision about a batch: (packed form `_FileRun.submit` builds, route `_FileRun.run_batch` takes).  Pure: it looks at what
     the engine object offers, at the bundle (None: reads that arrived one by one) and at the run's switches - pipelined (one
     engine, NRV_CLI_PIPELINE != 0), native_pool (libnanorev_host.so driven from the thread pool), device_merge (--device_merge
     and what it needs: pipelined, native_pool, nrvh_write_records), report (--report), edits (--edits), combined (--combined),
-    summary (--summary), trim (--trim_q), accuracy (--truth / --accuracy), error_classes (--error_classes), infix (--infix).  "bases":
+    summary (--summary), trim (--trim_q), accuracy (--truth / --accuracy), error_classes (--error_classes), infix (--infix), score
+    (--score).  "bases":
     `_bundle_has_bases`.  A form is
     the length of the packed tuple (engine.Reviser), None, or "host-merge": the merge form built and taken back.
 
@@ -1666,6 +1817,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
       yes     + error_classes on, form 30 above, no with_device_error_classes  host-merge [2]  by the last three rows
       yes     + infix on, a form 12 ... 31 above, with_device_accuracy + _infix  33 [11]         by the last three rows
       yes     + infix on, such a form, one of the two missing                host-merge [2]  by the last three rows
+      yes     + score on, a form 12 ... 33 above, with_device_score          36 [12]         by the last three rows
+      yes     + score on, such a form, no with_device_score                  host-merge [2]  by the last three rows
       yes     any form; pipelined, native_pool, begin_packed_raw, bases                      pipelined [3]
       yes     any form; native_pool, bases, not (pipelined, begin_packed_raw)                packed+finish_bundle
       yes     any form; no native_pool, or no bases                                          packed sliced
@@ -1692,7 +1845,9 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
         so the route is the one the accuracy takes without ITS call.
     [11] the one call is the form 30 / 31 call - without --accuracy a form 30 call whose accuracy block nobody reads - with the
         infix block last: per read where the original and the (untrimmed) revised read lie in the truth region, per strand.
-        Every other route computes the rows on the host (`infix_rows`)."""
+        Every other route computes the rows on the host (`infix_rows`).
+    [12] the one call is the call of the form above - `_route_batch(..., score=False)` names it - with the label bytes of its
+        reads going up and the score block last.  Every other route scores on the host from the calls (`ScorePart.host_rows`)."""
     unpacked = "per-read" if n_reads == 1 else "predict_many"
     if bundle is None:
         return (7 if n_reads > 1 and hasattr(rv, "pack_reads_raw") else None), unpacked
@@ -1719,6 +1874,8 @@ def _route_batch(rv, bundle, n_reads, pipelined, native_pool, device_merge, repo
                 form = 30 if hasattr(rv, "with_device_accuracy") else "host-merge"
             if form != "host-merge":
                 form = 33 if hasattr(rv, "with_device_infix") else "host-merge"
+        if score and form != "host-merge":
+            form = 36 if hasattr(rv, "with_device_score") else "host-merge"
     if not (native_pool and bases):
         return form, "packed sliced"
     return form, ("pipelined" if pipelined and hasattr(rv, "begin_packed_raw") else "packed+finish_bundle")
@@ -1827,7 +1984,7 @@ class _FileRun:
     `_route_batch` says (`submit`) and collects the pooled finishers; the ENGINE thread(s) make the calls (`run_batch`, `collect`);
     the one FINISHER thread merges, reports and writes, or hands that to the parser pool (`finish_batch`, `finish_call`)."""
     def __init__(self, stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part=None,
-                 summary_part=None, trim_part=None, accuracy_part=None, errclass_part=None, infix_part=None):
+                 summary_part=None, trim_part=None, accuracy_part=None, errclass_part=None, infix_part=None, score_part=None):
         self.args, self.log, self.note = args, log, on_file or (lambda fn, ok: None)
         self.stats = {"reads": 0, "bases": 0, "failed": [], "host_s": 0.0, "engine_s": 0.0}
         self.stats_lock = threading.Lock()
@@ -1853,6 +2010,9 @@ class _FileRun:
         # original bases, its labels from the device | None) is stashed wherever an infix row is
         if getattr(args, "labels", None) and infix_part:
             self.infpart.labels = LabelsPart(args.labels, infix_part.rsplit(".part", 1)[-1], self.accpart.truths, log)
+        # --score: the rows are stashed like a report row; id(batch) -> (labels, flags) of a form 36 call, until its reads are final
+        self.scorepart = ScorePart(score_part, getattr(args, "labels_from", None), log)
+        self.score_rows, self.score_in = {}, {}
         self.lab_in = {}
         self.lab_truth = {}                           # id(batch) -> (truth, truth_off) of a form 33 call, until its call is back
         self.acc_flags = {}                           # id(batch) -> the flags of a form 30 call's truth block, until its call is back
@@ -1987,7 +2147,8 @@ class _FileRun:
             return
         pend, nw, per_task = deque(), self.nworkers, self.per_task
         for k in range(0, len(self.jobs), per_task):
-            pend.append(self.pool.submit(_load_bundle, self.jobs[k:k + per_task], True) if self.device_stats
+            pend.append(self.pool.submit(_load_bundle_labelled, self.jobs[k:k + per_task], self.device_stats, self.scorepart.dir) if self.scorepart
+                        else self.pool.submit(_load_bundle, self.jobs[k:k + per_task], True) if self.device_stats
                         else self.pool.submit(_load_bundle, self.jobs[k:k + per_task]))
             if k == 0:
                 self.trace.mark("first task submitted (workers started)")
@@ -2036,6 +2197,8 @@ class _FileRun:
         self.inf_rows.pop(fn, None)
         self.lab_in.pop(fn, None)
         self.infpart.add_unrevised(fn, text)
+        self.score_rows.pop(fn, None)
+        self.scorepart.add_unrevised(fn)
         self.note(fn, False)
 
     def finished(self, fn, nb):
@@ -2068,6 +2231,11 @@ class _FileRun:
             if self.infpart.labels is not None:
                 bases, found = self.lab_in.pop(fn, (b"", None))
                 self.infpart.labels.add_read(fn, bases, row if row is not None else [0, 0, nb, nb] + [0] * 16 + [ACC_NO_TRUTH], found)
+        if self.scorepart:
+            row = self.score_rows.pop(fn, None)
+            if row is None:                           # cannot happen, as above
+                self.log(f"[！！！Warning] --score: no counts for {fn}")
+            self.scorepart.add(fn, row is not None, row if row is not None else [0] * SCORE_PART_COLS)
         if self.trim:
             row = self.trim_rows.pop(fn, None)
             log_row = trim_log_row(row[0], row[1], self.trim[2]) if row is not None else unrevised_trim(nb)
@@ -2092,6 +2260,12 @@ class _FileRun:
             if bundle is not None and "device_stats" in bundle and not (hasattr(rv, "run_packed_raw") and hasattr(rv, "with_device_stats")):
                 bundle = _bundle_host_stats(bundle)   # an engine without the new calls: the host computes them after all
             form, route = _route_batch(rv, bundle, len(batch), self.pipelined, self.native_pool, self.device_merge, bool(self.report),
+                                       edits=bool(self.edits_dir), combined=self.sink is not None, summary=bool(self.sumpart),
+                                       trim=self.trim is not None, accuracy=bool(self.accpart), error_classes=bool(self.eclpart),
+                                       infix=bool(self.infpart), score=bool(self.scorepart))
+            score = form == 36                        # --score: the call of the form without it, with one block more
+            if score:
+                form, _ = _route_batch(rv, bundle, len(batch), self.pipelined, self.native_pool, self.device_merge, bool(self.report),
                                        edits=bool(self.edits_dir), combined=self.sink is not None, summary=bool(self.sumpart),
                                        trim=self.trim is not None, accuracy=bool(self.accpart), error_classes=bool(self.eclpart),
                                        infix=bool(self.infpart))
@@ -2130,6 +2304,10 @@ class _FileRun:
                                 packed = cls.with_device_infix(packed, self.infpart.strands)
                                 if self.infpart.labels is not None:
                                     self.lab_truth[id(batch)] = (truth, toff)
+                    if score:                         # --score: the labels of the call's reads go up with it, the block comes back last
+                        found = bundle.get("labels") or self.scorepart.block([fn for fn, _, _ in batch], bundle["bases"], bundle["meta"][:, 1])
+                        packed = cls.with_device_score(packed, found[0], phred_thresholds())
+                        self.score_in[id(batch)] = found
         except Exception:
             packed = None
         if packed is None:
@@ -2163,6 +2341,7 @@ class _FileRun:
         T = self.rv.T
         self.acc_flags.pop(id(batch), None)
         self.lab_truth.pop(id(batch), None)
+        self.score_in.pop(id(batch), None)
         for (fn, rt, fq), c in zip(batch, calls):
             if isinstance(c, Exception):
                 self.fallback(fn, rt, fq, c)
@@ -2184,6 +2363,8 @@ class _FileRun:
                     self.inf_rows[fn] = self.infpart.host_rows(T, [fn], rt.bases, [len(np.asarray(rt.bases))], c[2], c[3])[0]
                     if self.infpart.labels is not None:
                         self.lab_in[fn] = (hostlib.bases_u8(rt.bases), None)
+                if self.scorepart:
+                    self.score_rows[fn] = self.scorepart.host_rows(T, [fn], rt.bases, [len(np.asarray(rt.bases))], *c)[0]
                 if self.edits_dir:
                     write_edits(self.edits_dir, fn, edit_rows(T, rt.bases, [len(np.asarray(rt.bases))], *c, self.want_qual)[0], self.want_qual)
                 if self.pool is not None or self.sink is not None:
@@ -2220,7 +2401,7 @@ class _FileRun:
         file goes up empty, with an empty region.  None where the engine cannot (the host stage aligns then)."""
         kept = self.lab_truth.pop(id(batch), None)
         flags = self.acc_flags.get(id(batch))
-        if kept is None or flags is None or len(outs) != 13 or not hasattr(reviser, "align_labels_arrays"):
+        if kept is None or flags is None or len(outs) not in (13, 14) or not hasattr(reviser, "align_labels_arrays"):
             return None
         truth, toff = kept
         ev_len = bundle["meta"][:, 1].astype(np.int64)
@@ -2243,7 +2424,13 @@ class _FileRun:
             trim = None
             flags = self.acc_flags.pop(id(batch), None)
             self.lab_truth.pop(id(batch), None)
+            found = self.score_in.pop(id(batch), None) or (bundle.get("labels") if bundle is not None else None)
             if merged:
+                if len(outs) == 14:                   # a `with_device_score` call: the block was counted behind the merge, last output;
+                    if self.scorepart and found is not None:   # blocks the call does not carry are None
+                        self.scorepart.announce(fns, found[1])
+                        self.score_rows.update(zip(fns, self.scorepart.rows(outs[13], found[1])))
+                    outs = outs[:13] if outs[12] is not None else outs[:12] if outs[11] is not None else outs[:11]
                 if len(outs) == 13:                   # a `with_device_infix` call: (..., accuracy, error classes | None, infix)
                     if self.infpart and flags is not None:
                         ev_len = bundle["meta"][:, 1].astype(np.int64)
@@ -2295,6 +2482,8 @@ class _FileRun:
                     self.inf_rows.update(zip(fns, self.infpart.host_rows(T, fns, bundle["bases"], ev_len.tolist(), a1, a2)))
                     if self.infpart.labels is not None:
                         self.stash_labels(fns, bundle["bases"], ev_len)
+                if self.scorepart:
+                    self.score_rows.update(zip(fns, self.scorepart.host_rows(T, fns, bundle["bases"], ev_len.tolist(), p1, p2, a1, a2, found)))
                 if self.edits_dir:
                     self.write_call_edits(fns, *edit_rows(T, bundle["bases"], ev_len, p1, p2, a1, a2, self.want_qual))
                 qc = phred_chars(p1, p2, a1, a2) if self.want_qual and len(a1) else None
@@ -2399,7 +2588,7 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                   on_file: Optional[Callable[[str, bool], None]] = None, gpu_workers: int = 1,
                   core_share: Optional[int] = None, report_part: Optional[str] = None, combined_part: Optional[str] = None,
                   summary_part: Optional[str] = None, trim_part: Optional[str] = None, accuracy_part: Optional[str] = None,
-                  errclass_part: Optional[str] = None, infix_part: Optional[str] = None) -> dict:
+                  errclass_part: Optional[str] = None, infix_part: Optional[str] = None, score_part: Optional[str] = None) -> dict:
     """Revise `files` (names inside args.fast5_base_dir) with one engine.  The host stage (HDF5 parsing, event collapse,
     statistics) runs --thread parser workers that stay a bounded number of reads ahead of the device: THREADS of this process
     inside libnanorev_host.so (at most kNativePoolMax), or PROCESSES on the Python host stage without it / with NRV_HOST_THREADS=0.
@@ -2413,10 +2602,10 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
     every read's record to INSTEAD of writing one file per read (`CombinedPart`, `deliver`).  summary_part (--summary): as
     report_part, for the summary's lines.  trim_part (--trim_log): as report_part, for the trim log's lines.  accuracy_part
     (--accuracy): as report_part, for the accuracy file's lines.  errclass_part (--error_classes): as accuracy_part, for that file's.  infix_part
-    (--infix): the same for the infix file's."""
+    (--infix): the same for the infix file's.  score_part (--score): the same for the score file's."""
     import contextlib
     with contextlib.ExitStack() as stack:             # its exit ends the run's threads and undoes what `_FileRun._start` did
-        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part, summary_part, trim_part, accuracy_part, errclass_part, infix_part)
+        run = _FileRun(stack, args, files, reviser, log, on_file, gpu_workers, core_share, report_part, combined_part, summary_part, trim_part, accuracy_part, errclass_part, infix_part, score_part)
         batch, nev = [], 0                            # unbundled reads are grouped into device calls of >= batch_events events
         for entries, bundle in run.results():
             bundled = []
@@ -2432,6 +2621,7 @@ def process_files(args, files: Sequence[str], reviser, log: Callable[[str], None
                     run.accpart.add_unrevised(fn, b"")
                     run.eclpart.add_unrevised(fn, b"")
                     run.infpart.add_unrevised(fn, b"")
+                    run.scorepart.add_unrevised(fn)
                     run.note(fn, False)
                 elif err is not None:
                     run.fallback(fn, rt, fq, err)
@@ -2650,8 +2840,8 @@ def revise_part(args, reviser, fn: str, k: int, parts: int):
         a1 = a2 = np.zeros(0, np.int8)
     qc = phred_chars(p1, p2, a1, a2) if args.output_format == "fastq" and len(a1) else None
     out = {"T": T, "n_ev": N, "lo": lo, "a1": np.array(a1, np.int8), "a2": np.array(a2, np.int8), "qc": qc}
-    if getattr(args, "report", None) or getattr(args, "edits", None) or getattr(args, "summary", None) \
-            or getattr(args, "trim_q", None) is not None:   # the parent reports the read once its slices are merged: near-ties (and the edits' conf) need the rows
+    if getattr(args, "report", None) or getattr(args, "edits", None) or getattr(args, "summary", None) or getattr(args, "score", None) \
+            or getattr(args, "trim_q", None) is not None:   # the parent reports the read once its slices are merged: near-ties (and the edits' conf, the score's loss) need the rows
         out["p1"], out["p2"] = np.array(p1, np.float32), np.array(p2, np.float32)
     if k == 0:
         out["bases"], out["fq"] = np.asarray(rt.bases), fq
@@ -2697,7 +2887,8 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
                            trim_part=report_part_path(args.trim_log, rank) if getattr(args, "trim_log", None) else None,
                            accuracy_part=report_part_path(args.accuracy, rank) if getattr(args, "accuracy", None) else None,
                            errclass_part=report_part_path(args.error_classes, rank) if getattr(args, "error_classes", None) else None,
-                           infix_part=report_part_path(args.infix, rank) if getattr(args, "infix", None) else None)
+                           infix_part=report_part_path(args.infix, rank) if getattr(args, "infix", None) else None,
+                           score_part=report_part_path(args.score, rank) if getattr(args, "score", None) else None)
         st["cpus"] = len(cpus) if cpus else 0
         for e in made:
             e.close()
@@ -2708,7 +2899,8 @@ def _worker(rank: int, world: int, args, files: List[str], q, factory=None, part
 
 def write_originals(args, files: Sequence[str], log: Callable[[str], None], report: Optional[ReportPart] = None,
                     sink: Optional[CombinedPart] = None, summary: Optional[ReportPart] = None,
-                    trimlog: Optional[ReportPart] = None, accuracy: Optional["AccuracyPart"] = None) -> List[str]:
+                    trimlog: Optional[ReportPart] = None, accuracy: Optional["AccuracyPart"] = None,
+                    score: Optional["ScorePart"] = None) -> List[str]:
     """The failure contract for reads whose WORKER is gone (NanoReviser.py:146-152 / :173-179): every
     file in `files` - the ones the dead worker never reported as final - gets its original basecalls
     written by this process (atomically, replacing whatever an earlier run left under that name).
@@ -2742,12 +2934,15 @@ def write_originals(args, files: Sequence[str], log: Callable[[str], None], repo
                 accuracy.classes.add_unrevised(fn, text)
             if accuracy.infix is not None:
                 accuracy.infix.add_unrevised(fn, text)
+        if score is not None:
+            score.add_unrevised(fn)
     return done
 
 
 def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[str], None], report: Optional[ReportPart] = None,
                        sink: Optional[CombinedPart] = None, summary: Optional[ReportPart] = None,
-                       trimlog: Optional[ReportPart] = None, accuracy: Optional["AccuracyPart"] = None):
+                       trimlog: Optional[ReportPart] = None, accuracy: Optional["AccuracyPart"] = None,
+                       score: Optional["ScorePart"] = None):
     """Parent side of the split reads: the slices' calls in slice order are the read's calls (window i of slice k is
     window lo_k + i of the read), merged and written exactly as an unsplit read's.  A read with a slice missing (its
     worker died) or failed gets its original basecalls (NanoReviser.py:146-152).  Returns (bases written, failed names)."""
@@ -2805,13 +3000,17 @@ def finish_split_reads(args, split_fns: dict, parts_got: dict, log: Callable[[st
                     accuracy.infix.add(fn, True, inf_row)
                     if accuracy.infix.labels is not None:
                         accuracy.infix.labels.add_read(fn, hostlib.bases_u8(pl[0]["bases"]), inf_row)
+                if score is not None and score:        # the slices are merged: the read's score, here in the parent
+                    score.add(fn, True, score.host_rows(T, [fn], pl[0]["bases"], [N],
+                                                        np.concatenate([p["p1"] for p in pl]) if have_p else None,
+                                                        np.concatenate([p["p2"] for p in pl]) if have_p else None, a1, a2)[0])
                 if summary is not None and summary and have_p:
                     summary.add(fn, True, profile_rows(T, pl[0]["bases"], [N], np.concatenate([p["p1"] for p in pl]),
                                                        np.concatenate([p["p2"] for p in pl]), a1, a2)[0])
                 continue
             err = e2
         log(f"[！！！Error] revising {fn.split('.')[0]}: {err}; writing the original basecalls")
-        write_originals(args, [fn], log, report, sink, summary, trimlog, accuracy)
+        write_originals(args, [fn], log, report, sink, summary, trimlog, accuracy, score)
         failed.append(fn)
     return nb, failed
 
@@ -2941,6 +3140,13 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
             os.makedirs(args.labels, exist_ok=True)
             clear_report_parts(labels_index_path(args.labels))
             parent_acc.infix.labels = LabelsPart(args.labels, "parent", truths)
+    if args.score:                        # --score: parts and a parent-side merge as for --report
+        clear_report_parts(args.score)
+        d = os.path.dirname(args.score)
+        if d:
+            os.makedirs(d, exist_ok=True)
+    parent_score = ScorePart(report_part_path(args.score, "parent") if args.score else None, args.labels_from)
+    score_part0 = report_part_path(args.score, 0) if args.score else None
     if args.combined:                     # --combined: a part per process too, `merge_combined` ends the run
         clear_combined_parts(args.combined)
     parent_sink = CombinedPart(combined_part_path(args.combined, "parent"), args.output_format == "fastq") if args.combined else None
@@ -2980,7 +3186,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
     if reviser_factory is not None:       # in-process (tests / embedding): one engine, no sharding
         rv = reviser_factory(args, 0)
         stats = [process_files(args, names, rv, print, report_part=report_part_path(args.report, 0) if args.report else None,
-                               combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0, errclass_part=ecl_part0, infix_part=inf_part0)]
+                               combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0, errclass_part=ecl_part0, infix_part=inf_part0, score_part=score_part0)]
     else:
         # the command line needs no torch: without it a process starts ~1.5 s sooner.  (engine.py imports
         # torch first only so that a LATER torch import in the same process finds one HIP runtime.)
@@ -3009,7 +3215,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
                 made.append((worker_factory or _default_factory)(args, 0))
                 return made[-1]                       # called once per engine (process_files: NRV_CLI_ENGINES)
             stats = [process_files(args, names, make, print, report_part=report_part_path(args.report, 0) if args.report else None,
-                                   combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0, errclass_part=ecl_part0, infix_part=inf_part0)]
+                                   combined_part=part0, summary_part=sum_part0, trim_part=trim_part0, accuracy_part=acc_part0, errclass_part=ecl_part0, infix_part=inf_part0, score_part=score_part0)]
             for rv in made:
                 rv.close()
         else:
@@ -3020,7 +3226,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
             res = run_workers(args, shards, worker_factory, part_shards=part_shards, parts_out=parts_got)
             stats = [s for _, s, _, _ in res if s is not None]
             if split_fns:
-                nb_split, failed_split = finish_split_reads(args, split_fns, parts_got, print, parent_report, parent_sink, parent_summary, parent_trim, parent_acc)
+                nb_split, failed_split = finish_split_reads(args, split_fns, parts_got, print, parent_report, parent_sink, parent_summary, parent_trim, parent_acc, parent_score)
                 stats.append({"reads": len(split_fns), "bases": nb_split, "failed": failed_split, "host_s": 0.0, "engine_s": 0.0})
                 if failed_split:
                     rc = 3
@@ -3030,7 +3236,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
                           f"unfinished reads", file=sys.stderr)
                     # what the worker reported final stays (its failed reads keep their failed_reads entry);
                     # everything else - started or not, whatever lies on disk - is written unrevised
-                    lost = write_originals(args, [f for f in shards[r] if f not in final], print, parent_report, parent_sink, parent_summary, parent_trim, parent_acc)
+                    lost = write_originals(args, [f for f in shards[r] if f not in final], print, parent_report, parent_sink, parent_summary, parent_trim, parent_acc, parent_score)
                     lost += [f for f, ok in final.items() if not ok]
                     stats.append({"reads": len(shards[r]), "bases": 0, "failed": lost, "host_s": 0.0, "engine_s": 0.0})
                     rc = 3
@@ -3055,6 +3261,9 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None, standalone:
         if parent_acc.classes is not None:
             parent_acc.classes.close()
             merge_error_classes(args.error_classes, all_names)
+    parent_score.close()
+    if args.score:
+        merge_score(args.score, all_names)
     if args.combined:
         parent_sink.close()
         merge_combined(args.combined, args.output_format == "fastq")

@@ -481,10 +481,10 @@ struct DevModel {
 // The merged block of a call of N events, n windows, n_reads reads - offsets into one device allocation:
 //   [off i64 x (n_reads + 1) | seq | qual | report u64 x n_reads x 24 | edit_off i64 x (n_reads + 1) | rec_off i64 x (n_reads + 1) |
 //    profile u64 x n_reads x 48 | trim i64 x n_reads x 2 | accu u64 x n_reads x 4 | ecls u64 x n_reads x 6 |
-//    infx u64 x n_reads x 18]
+//    infx u64 x n_reads x 18 | scor u64 x n_reads x 248]
 //                                     what comes back in one copy of `dl` bytes, mirrored in page-locked memory (nrv_merge.h,
-//                                     nrv_report.h, nrv_edits.h, nrv_pack.h, nrv_profile.h, nrv_trim.h, nrv_align.h, nrv_errclass.h, nrv_infix.h); the report,
-//                                     edit_off, rec_off, the profile, the trim, the accuracy, the error classes and the infix block only where asked for - without
+//                                     nrv_report.h, nrv_edits.h, nrv_pack.h, nrv_profile.h, nrv_trim.h, nrv_align.h, nrv_errclass.h, nrv_infix.h, nrv_score.h); the report,
+//                                     edit_off, rec_off, the profile, the trim, the accuracy, the error classes, the infix block and the score only where asked for - without
 //                                     them the layout is the merge's own.  A records call that hands back neither seq nor qual leaves those two on
 //                                     the device
 //   [rec u32 x N | tile u64]          the merge kernels' scratch
@@ -500,7 +500,7 @@ struct DevModel {
 //                                     revised reads; only where asked for
 //   [hci i64 x N x 2 | hci i64 x (N + n) x 2]  the infix block's stripe carries, the same per strand; only where asked for
 // Every part is 256-byte aligned.
-struct MergeLayout { size_t seq, qual, rep, eoff, roff, prof, trim, rec, tile, edits, etile, blob, tq, acc, dl, bytes, accu, hc, ecls, hc8, infx, hci; };
+struct MergeLayout { size_t seq, qual, rep, eoff, roff, prof, trim, rec, tile, edits, etile, blob, tq, acc, dl, bytes, accu, hc, ecls, hc8, infx, hci, scor; };
 
 // What a merged call reads besides the raw reads.  Consumed inside _begin: the caller's pointers are dead once it returns, so
 // nothing that outlives _begin keeps one (the slot keeps the VALUES of both threshold sets for the re-run of nrv_reads_raw_end)
@@ -515,6 +515,8 @@ struct MergeIn {
   int64_t min_len = 0;
   const uint8_t* truth = nullptr;       // nrv_revise_reads_raw_accuracy_begin: the true sequences and [n_reads + 1]
   const int64_t* truth_off = nullptr;
+  const uint8_t* labels = nullptr;      // nrv_revise_reads_raw_score_begin: one label byte per event and its own 39 thresholds
+  const float* score_thr = nullptr;
 };
 // The trim's rule as the kernels take it: the VALUES a slot keeps for the re-run are of this form too (thr points into the slot)
 struct TrimRule { const float* thr = nullptr; int Q = 0, W = 0; int64_t min_len = 0; };
@@ -535,6 +537,7 @@ struct MergeOut {
   uint64_t* errclass = nullptr;         // [n_reads][6]
   uint64_t* infix = nullptr;            // [n_reads][18]
   int strands = 2;                      // of the infix block: 1 (forward) or 2
+  uint64_t* score = nullptr;            // [n_reads][248]
   bool wants_truth() const { return accuracy != nullptr || errclass != nullptr || infix != nullptr; }
 };
 // Where a merged call's inputs lie on the device, and its merged block
@@ -550,6 +553,7 @@ struct MergeView {
   char* blk;                             // MergeLayout offsets count from here
   const unsigned char* truth = nullptr;  // accuracy and error classes only
   const long long* truth_off = nullptr;
+  const unsigned char* labels = nullptr; // the score only
 };
 // The quality rule: characters get a Phred quality when there are thresholds and somebody reads it - the caller's qual or the
 // FASTQ records (nrv_merge_calls* has no records: q_thr && qual there)
@@ -630,6 +634,8 @@ struct nrv_handle {
     // counter of d_out; where the results go; and the values the re-run of nrv_reads_raw_end needs once the inputs are gone
     size_t off_bases = 0, off_noff = 0, off_names = 0;
     size_t off_toff = 0, off_truth = 0;                                   // accuracy: [.. | truth_off i64 x (n_reads + 1) | truth u8] behind names
+    size_t off_labels = 0;                                                // score: [.. | labels u8 x N] behind the truth
+    float score_thr[kPhredSteps] = {0};
     char* d_mrg = nullptr; char* pin_mrg = nullptr; size_t cap_mrg = 0;
     MergeLayout m = {};
     MergeOut out;
@@ -1658,6 +1664,7 @@ static int merged_collect(nrv_handle* h, const char* who, const char* who_edits,
   if (o.accuracy) memcpy(o.accuracy, head + m.accu, (size_t)v.n_reads * kAccuracyCols * 8);
   if (o.errclass) memcpy(o.errclass, head + m.ecls, (size_t)v.n_reads * kErrclassCols * 8);
   if (o.infix) memcpy(o.infix, head + m.infx, (size_t)v.n_reads * kInfixCols * 8);
+  if (o.score) memcpy(o.score, head + m.scor, (size_t)v.n_reads * kScoreCols * 8);
   int rc = NRV_OK;
   if (o.edit_off) {
     const int64_t n_ed = ((const int64_t*)(head + m.eoff))[v.n_reads];
@@ -2152,6 +2159,25 @@ static ReportArgs report_args(const MergeArgs& m, const float* p1, const float* 
   a.report = (unsigned long long*)report;
   return a;
 }
+// The score kernel (nrv_score.h) behind merge_enqueue (and report_enqueue) on the same stream: it reads what the merge read and
+// the label bytes, nothing the merge left.  The block is zeroed here, in stream order ahead of the launch, as the report's is.
+static int score_enqueue(nrv_handle* h, const ScoreArgs& a) {
+  if (a.n_reads <= 0 || a.N <= 0) return NRV_OK;
+  HIPCHK(h, hipMemsetAsync(a.score, 0, (size_t)a.n_reads * kScoreCols * 8, h->stream));
+  const unsigned tiles = (unsigned)((a.N + kMergeTile - 1) / kMergeTile);
+  hipLaunchKernelGGL(score_kernel, dim3(tiles), dim3(256), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return NRV_OK;
+}
+static ScoreArgs score_args(const MergeArgs& m, const float* p1, const float* p2, const unsigned char* labels, const float* thr, void* score) {
+  ScoreArgs a;
+  a.reads = m.reads; a.n_reads = m.n_reads; a.T = m.T; a.N = m.N;
+  a.bases = m.bases; a.labels = labels; a.a1 = m.a1; a.a2 = m.a2;
+  a.p1 = p1 && p2 ? p1 : nullptr; a.p2 = p1 && p2 ? p2 : nullptr;
+  a.score = (unsigned long long*)score;
+  memcpy(a.thr, thr, sizeof a.thr);
+  return a;
+}
 // The edit kernels (nrv_edits.h) behind merge_enqueue (and report_enqueue) on the same stream: they read the records, the tile
 // offsets and the read offsets the merge left.  Plain stores into every word that is read back: a second pass accumulates nothing.
 static int edits_enqueue(nrv_handle* h, const EditsArgs& a) {
@@ -2311,7 +2337,8 @@ static MergeLayout merge_layout(int64_t N, int64_t n, int n_reads, const MergeOu
   m.accu = m.trim + (o.trim ? up256((size_t)n_reads * 16) : 0);
   m.ecls = m.accu + (o.accuracy ? up256((size_t)n_reads * kAccuracyCols * 8) : 0);
   m.infx = m.ecls + (o.errclass ? up256((size_t)n_reads * kErrclassCols * 8) : 0);
-  m.dl = m.infx + (o.infix ? up256((size_t)n_reads * kInfixCols * 8) : 0);
+  m.scor = m.infx + (o.infix ? up256((size_t)n_reads * kInfixCols * 8) : 0);
+  m.dl = m.scor + (o.score ? up256((size_t)n_reads * kScoreCols * 8) : 0);
   m.rec = m.dl;
   m.tile = m.rec + up256((size_t)N * 4);
   m.edits = m.tile + up256(tiles * 8);
@@ -2477,6 +2504,8 @@ static void merged_nothing(const MergeIn& in, const MergeOut& o, const nrv_read_
   if (o.accuracy) accuracy_nothing(in.bases, reads, n_reads, in.truth, in.truth_off, o.accuracy);
   if (o.errclass) errclass_nothing(in.bases, reads, n_reads, in.truth, in.truth_off, o.errclass);
   if (o.infix) infix_nothing(in.bases, reads, n_reads, in.truth, in.truth_off, o.strands, o.infix);
+  static_assert(NRV_SCORE_COLS == kScoreCols, "nanorev.h and nrv_score.h disagree on the score's columns");
+  if (o.score) memset(o.score, 0, (size_t)n_reads * kScoreCols * 8);   // hoststage.score_calls on a call without a window: nothing to score
 }
 
 // What the three truth kernels share (PairArgs, nrv_align.h) in a merged call: both kinds of every read, the revised text as
@@ -2494,9 +2523,10 @@ static PairArgs pair_args(const MergeView& v, const MergeArgs& a, int T) {
 // none is written); the merge reads the rows only for a quality, the report and the edits whenever there are rows, the profile
 // always, and so does the trim (t: its rule), whose bounds the records are then cut to.  A second pass over the same block (the
 // re-run of nrv_reads_raw_end) counts nothing twice: report_enqueue and profile_enqueue zero their blocks and trim_bounds_enqueue
-// resets its accumulators in stream order, the edit and record kernels store plainly into every word that is read back
+// resets its accumulators in stream order, the edit and record kernels store plainly into every word that is read back; the
+// score (score_thr: its own thresholds) is zeroed by score_enqueue like the report
 static int merged_enqueue(nrv_handle* h, const MergeView& v, const MergeLayout& m, const MergeOut& o, const float* q_thr,
-                          const float* prof_thr, size_t blob_cap, const TrimRule& t = TrimRule{}) {
+                          const float* prof_thr, size_t blob_cap, const TrimRule& t = TrimRule{}, const float* score_thr = nullptr) {
   const bool want_q = q_thr != nullptr;
   MergeArgs a;
   a.reads = v.reads; a.n_reads = v.n_reads; a.T = h->T; a.N = v.N;
@@ -2509,6 +2539,7 @@ static int merged_enqueue(nrv_handle* h, const MergeView& v, const MergeLayout& 
   if (want_q) memcpy(a.thr, q_thr, sizeof a.thr);
   int rc = merge_enqueue(h, a);
   if (!rc && o.report) rc = report_enqueue(h, report_args(a, v.p1, v.p2, want_q, o.tie_eps, v.blk + m.rep));
+  if (!rc && o.score) rc = score_enqueue(h, score_args(a, v.p1, v.p2, v.labels, score_thr, v.blk + m.scor));
   if (!rc && o.edit_off) rc = edits_enqueue(h, edits_args(a, v.p1, v.p2, want_q, v.blk + m.etile, v.blk + m.eoff, v.blk + m.edits));
   if (!rc && o.trim) rc = trim_enqueue(h, a, v.p1, v.p2, t, v.blk + m.tq, v.blk + m.acc, v.blk + m.trim);
   if (!rc && o.rec_off) {
@@ -2559,7 +2590,8 @@ static MergeView slot_view(const nrv_handle::RawSlot& sl) {
                    (const signed char*)(d + sl.rows * 44), (const signed char*)(d + sl.rows * 45), (const float*)d,
                    (const float*)(d + sl.rows * 24), (const long long*)(sl.d_in + sl.off_noff),
                    (const unsigned char*)(sl.d_in + sl.off_names), sl.d_mrg,
-                   (const unsigned char*)(sl.d_in + sl.off_truth), (const long long*)(sl.d_in + sl.off_toff)};
+                   (const unsigned char*)(sl.d_in + sl.off_truth), (const long long*)(sl.d_in + sl.off_toff),
+                   (const unsigned char*)(sl.d_in + sl.off_labels)};
 }
 // What comes back of a slot's call, on stream s.  A plain call: its output block.  A merged call: the counter and the merged block,
 // all of [0, m.dl) - or, for a records call that hands back neither seq nor qual, the parts in front of and behind them; p1 / p2 /
@@ -2633,7 +2665,9 @@ static int raw_begin(nrv_handle* h, const RawIn& in, float* p1, float* p2, int8_
   sl.off_names = sl.off_noff + (records ? up256(((size_t)n_reads + 1) * 8) : 0);
   sl.off_toff = sl.off_names + (records ? up256((size_t)mr->name_off[n_reads]) : 0);
   sl.off_truth = sl.off_toff + (accuracy ? up256(((size_t)n_reads + 1) * 8) : 0);
-  const size_t in_bytes = sl.off_truth + (accuracy ? up256((size_t)mr->truth_off[n_reads]) : 0);
+  const bool score = mr != nullptr && mo->score != nullptr;   // (the entry point has checked labels / score_thr)
+  sl.off_labels = sl.off_truth + (accuracy ? up256((size_t)mr->truth_off[n_reads]) : 0);
+  const size_t in_bytes = sl.off_labels + (score ? up256((size_t)N) : 0);
   sl.rows = ((size_t)sl.n + kRowPad - 1) / kRowPad * kRowPad;
   const size_t out_bytes = 64 + sl.rows * kOutBytes;
   if (!sl.ev_in) {
@@ -2670,6 +2704,7 @@ static int raw_begin(nrv_handle* h, const RawIn& in, float* p1, float* p2, int8_
       memcpy(sl.trim_thr, mr->trim_thr, sizeof sl.trim_thr);
       sl.trim_Q = mr->Q; sl.trim_W = mr->W; sl.trim_min_len = mr->min_len;
     }
+    if (score) memcpy(sl.score_thr, mr->score_thr, sizeof sl.score_thr);
     if ((sl.out.edit_off || records) && !h->edit_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->edit_stream, hipStreamNonBlocking));
     if (m.bytes > sl.cap_mrg) {
       (void)hipFree(sl.d_mrg); (void)hipHostFree(sl.pin_mrg);
@@ -2711,6 +2746,7 @@ static int raw_begin(nrv_handle* h, const RawIn& in, float* p1, float* p2, int8_
     memcpy(sl.pin_in + sl.off_toff, mr->truth_off, ((size_t)n_reads + 1) * 8);
     if (mr->truth_off[n_reads] > 0) memcpy(sl.pin_in + sl.off_truth, mr->truth, (size_t)mr->truth_off[n_reads]);
   }
+  if (score) memcpy(sl.pin_in + sl.off_labels, mr->labels, (size_t)N);
   memcpy(sl.pin_in + sl.off_starts, starts, (size_t)N * 4);
   memcpy(sl.pin_in + sl.off_reads, reads, (size_t)n_reads * sizeof(SegRead));
   memcpy(sl.pin_in + sl.off_feat, feat_ev, (size_t)N * kFeat * 4);
@@ -2729,7 +2765,7 @@ static int raw_begin(nrv_handle* h, const RawIn& in, float* p1, float* p2, int8_
                        nullptr, nullptr);
   // the merge reads the slot's output block: behind the call's last launch group, ahead of ev_done
   if (rc || (rc = raw_enqueue(h, sl)) ||
-      (mr && (rc = merged_enqueue(h, slot_view(sl), sl.m, sl.out, sl.want_q ? sl.thr : nullptr, sl.prof_thr, sl.blob_cap, slot_trim(sl))))) {
+      (mr && (rc = merged_enqueue(h, slot_view(sl), sl.m, sl.out, sl.want_q ? sl.thr : nullptr, sl.prof_thr, sl.blob_cap, slot_trim(sl), sl.score_thr)))) {
     (void)hipStreamSynchronize(h->stream);                      // part of the call may be enqueued: nothing of it may outlive the slot
     return rc;
   }
@@ -3029,6 +3065,45 @@ int nrv_revise_reads_raw_infix(nrv_handle* h, const int16_t* raw, int64_t n_raw,
   });
 }
 
+// every earlier block may be NULL, the truth and the infix block included: the score reads the labels, not the truth
+int nrv_revise_reads_raw_score_begin(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                                     const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                                     const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                                     uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                                     nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                                     uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                                     const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                                     const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, uint64_t* errclass,
+                                     int strands, uint64_t* infix, const uint8_t* labels, const float* score_thr, uint64_t* score,
+                                     int* ticket) {
+  const char* missing = nullptr;
+  if (!labels || !score_thr || !score) missing = "null labels / score_thr / score";
+  else if (trim && !trim_thr) missing = "trim without trim_thr";
+  MergeOut mo{seq, qual, off, report, tie_eps, edits, edit_off, blob, rec_off, profile, trim, accuracy};
+  mo.errclass = errclass; mo.infix = infix; mo.strands = strands; mo.score = score;
+  MergeIn mi{bases, q_thr, names, name_off, prof_thr, trim_thr, Q, W, min_len, truth, truth_off};
+  mi.labels = labels; mi.score_thr = score_thr;
+  return revise_begin(h, "nrv_revise_reads_raw_score_begin", missing,
+                      RawIn{raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device}, mi, mo, ticket);
+}
+
+int nrv_revise_reads_raw_score(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts,
+                               const float* feat_ev, int64_t N, const nrv_read_desc* reads, int n_reads,
+                               const int32_t* last_dur, const uint8_t* on_device, const uint8_t* bases, const float* q_thr,
+                               uint8_t* seq, uint8_t* qual, int64_t* off, float tie_eps, uint64_t* report,
+                               nrv_edit* edits, int64_t* edit_off, const uint8_t* names, const int64_t* name_off,
+                               uint8_t* blob, int64_t* rec_off, const float* prof_thr, uint64_t* profile,
+                               const float* trim_thr, int Q, int W, int64_t min_len, int64_t* trim,
+                               const uint8_t* truth, const int64_t* truth_off, uint64_t* accuracy, uint64_t* errclass,
+                               int strands, uint64_t* infix, const uint8_t* labels, const float* score_thr, uint64_t* score) {
+  return begin_then_end(h, [&](int* t) {
+    return nrv_revise_reads_raw_score_begin(h, raw, n_raw, starts, feat_ev, N, reads, n_reads, last_dur, on_device, bases, q_thr,
+                                            seq, qual, off, tie_eps, report, edits, edit_off, names, name_off, blob, rec_off,
+                                            prof_thr, profile, trim_thr, Q, W, min_len, trim, truth, truth_off, accuracy, errclass,
+                                            strands, infix, labels, score_thr, score, t);
+  });
+}
+
 int nrv_reads_raw_end(nrv_handle* h, int ticket) {
   int rc = check_handle(h);
   if (rc) return rc;
@@ -3048,7 +3123,7 @@ int nrv_reads_raw_end(nrv_handle* h, int ticket) {
     if (rc2) return rc2;
     // a merged call: its kernels again, in stream order behind the re-run they read, on a block that holds nothing of the first pass
     if (sl.out.off && ((rc = poison_fill(h, sl.d_mrg, sl.cap_mrg, h->stream)) ||
-                       (rc = merged_enqueue(h, slot_view(sl), sl.m, sl.out, sl.want_q ? sl.thr : nullptr, sl.prof_thr, sl.blob_cap, slot_trim(sl)))))
+                       (rc = merged_enqueue(h, slot_view(sl), sl.m, sl.out, sl.want_q ? sl.thr : nullptr, sl.prof_thr, sl.blob_cap, slot_trim(sl), sl.score_thr))))
       return rc;
     if ((rc = slot_download(h, sl, h->stream))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3156,7 +3231,8 @@ int nrv_read_stats(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32
 // nrv_merge_calls (o.report == nullptr: that call, to the byte), nrv_merge_calls_report, (o.edit_off != nullptr)
 // nrv_merge_calls_edits, (o.profile != nullptr) nrv_merge_calls_profile and (o.trim != nullptr; `more`: its rule, and the names of
 // its records) nrv_merge_calls_trim, (o.accuracy != nullptr; `more`: the truth) nrv_merge_calls_accuracy and (o.errclass != nullptr;
-// `more`: the truth) nrv_merge_calls_errclass and (o.infix != nullptr; `more`: the truth) nrv_merge_calls_infix
+// `more`: the truth) nrv_merge_calls_errclass and (o.infix != nullptr; `more`: the truth) nrv_merge_calls_infix and (o.score !=
+// nullptr; `more`: the labels and their thresholds) nrv_merge_calls_score
 static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
                             const float* p1, const float* p2, int64_t n_win, const float* q_thr, const MergeOut& o,
                             const float* prof_thr = nullptr, const MergeIn& more = MergeIn{}) {
@@ -3207,12 +3283,12 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
   const MergeLayout m = merge_layout(N, n, n_reads, o, blob_cap);
   // the rows go up for a quality - and without one where they are given and the report's near-tie column, the edits' conf, the
   // profile or the trim reads them
-  const bool have_p = want_q || ((o.report || o.edit_off || o.profile || o.trim) && p1 && p2);
+  const bool have_p = want_q || ((o.report || o.edit_off || o.profile || o.trim || o.score) && p1 && p2);
   const bool records = o.rec_off != nullptr, truth = o.wants_truth();
   const size_t name_bytes = records ? (size_t)more.name_off[n_reads] : 0, truth_bytes = truth ? (size_t)more.truth_off[n_reads] : 0;
   const size_t nb = ((size_t)n_reads + 1) * 8;
   const MergeInLayout l = merge_in_layout((size_t)n_reads, sizeof(SegRead), (size_t)N, (size_t)n, have_p, records, name_bytes, truth,
-                                          truth_bytes, m.bytes);
+                                          truth_bytes, m.bytes, o.score != nullptr);
   std::vector<char> back(m.dl);
   hipStream_t const s = h->stream;
   return with_block(h, l.bytes, s, [&](char* d) -> int {
@@ -3221,13 +3297,16 @@ static int merge_calls_impl(nrv_handle* h, const uint8_t* bases, const int64_t* 
         (rc2 = put(h, d + l.a1, a1, (size_t)n, s)) || (rc2 = put(h, d + l.a2, a2, (size_t)n, s)) ||
         (rc2 = put(h, d + l.p1, p1, have_p ? (size_t)n * 24 : 0, s)) || (rc2 = put(h, d + l.p2, p2, have_p ? (size_t)n * 20 : 0, s)) ||
         (rc2 = put(h, d + l.name_off, more.name_off, records ? nb : 0, s)) || (rc2 = put(h, d + l.names, more.names, name_bytes, s)) ||
-        (rc2 = put(h, d + l.truth_off, more.truth_off, truth ? nb : 0, s)) || (rc2 = put(h, d + l.truth, more.truth, truth_bytes, s)))
+        (rc2 = put(h, d + l.truth_off, more.truth_off, truth ? nb : 0, s)) || (rc2 = put(h, d + l.truth, more.truth, truth_bytes, s)) ||
+        (rc2 = put(h, d + l.labels, more.labels, o.score ? (size_t)N : 0, s)))
       return rc2;
     const MergeView v{(const SegRead*)(d + l.reads), n_reads, N, (const unsigned char*)(d + l.bases), (const signed char*)(d + l.a1),
                       (const signed char*)(d + l.a2), have_p ? (const float*)(d + l.p1) : nullptr,
                       have_p ? (const float*)(d + l.p2) : nullptr, (const long long*)(d + l.name_off), (const unsigned char*)(d + l.names),
-                      d + l.merged, (const unsigned char*)(d + l.truth), (const long long*)(d + l.truth_off)};
-    if ((rc2 = merged_enqueue(h, v, m, o, want_q ? q_thr : nullptr, prof_thr, blob_cap, TrimRule{more.trim_thr, more.Q, more.W, more.min_len})))
+                      d + l.merged, (const unsigned char*)(d + l.truth), (const long long*)(d + l.truth_off),
+                      (const unsigned char*)(d + l.labels)};
+    if ((rc2 = merged_enqueue(h, v, m, o, want_q ? q_thr : nullptr, prof_thr, blob_cap, TrimRule{more.trim_thr, more.Q, more.W, more.min_len},
+                              more.score_thr)))
       return rc2;
     HIPCHK(h, hipMemcpyAsync(back.data(), d + l.merged, m.dl, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
@@ -3321,6 +3400,18 @@ int nrv_merge_calls_infix(nrv_handle* h, const uint8_t* bases, const int64_t* ev
   o.infix = infix ? infix : none; o.strands = strands;
   MergeIn more;
   more.truth = truth; more.truth_off = truth_off;
+  return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, o, nullptr, more);
+}
+
+int nrv_merge_calls_score(nrv_handle* h, const uint8_t* bases, const int64_t* ev_len, int n_reads, const int8_t* a1, const int8_t* a2,
+                          const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
+                          const uint8_t* labels, const float* score_thr, uint64_t* score) {
+  if (h && (!labels || !score_thr || (n_reads > 0 && !score))) { h->err = "nrv_merge_calls_score: null labels / score_thr / score"; return NRV_E_INVALID; }
+  static uint64_t none[NRV_SCORE_COLS];
+  MergeOut o{seq, qual, off};
+  o.score = score ? score : none;
+  MergeIn more;
+  more.labels = labels; more.score_thr = score_thr;
   return merge_calls_impl(h, bases, ev_len, n_reads, a1, a2, p1, p2, n_win, q_thr, o, nullptr, more);
 }
 

@@ -81,12 +81,13 @@ inline LabelsLayout labels_layout(size_t n_pairs, size_t ta, size_t tb, size_t c
   return l;
 }
 
-// nrv_merge_calls*: [reads | bases | a1 | a2 | p1 | p2 | name_off | names | truth_off | truth | merged block].  desc: the bytes
-// of a read's descriptor; N events, n windows; p1 / p2 (24 and 20 bytes a window) only where the rows go up, the names only for
-// records, the truth only where one is asked for; merged: the bytes of the merged block (MergeLayout)
-struct MergeInLayout { size_t reads, bases, a1, a2, p1, p2, name_off, names, truth_off, truth, merged, bytes; };
+// nrv_merge_calls*: [reads | bases | a1 | a2 | p1 | p2 | name_off | names | truth_off | truth | labels | merged block].  desc: the
+// bytes of a read's descriptor; N events, n windows; p1 / p2 (24 and 20 bytes a window) only where the rows go up, the names only
+// for records, the truth only where one is asked for, the labels (one byte per event) only for the score; merged: the bytes of
+// the merged block (MergeLayout)
+struct MergeInLayout { size_t reads, bases, a1, a2, p1, p2, name_off, names, truth_off, truth, merged, bytes, labels; };
 inline MergeInLayout merge_in_layout(size_t n_reads, size_t desc, size_t N, size_t n, bool have_p, bool records, size_t name_bytes,
-                                     bool truth, size_t truth_bytes, size_t merged) {
+                                     bool truth, size_t truth_bytes, size_t merged, bool labels = false) {
   Block blk;
   MergeInLayout l{};
   l.reads = blk.take(n_reads * desc);
@@ -95,6 +96,7 @@ inline MergeInLayout merge_in_layout(size_t n_reads, size_t desc, size_t N, size
   l.p1 = blk.take(have_p ? n * 24 : 0); l.p2 = blk.take(have_p ? n * 20 : 0);
   l.name_off = blk.take(records ? (n_reads + 1) * 8 : 0); l.names = blk.take(records ? name_bytes : 0);
   l.truth_off = blk.take(truth ? (n_reads + 1) * 8 : 0); l.truth = blk.take(truth ? truth_bytes : 0);
+  l.labels = blk.take(labels ? N : 0);
   l.merged = blk.take(merged);
   l.bytes = blk.bytes;
   return l;

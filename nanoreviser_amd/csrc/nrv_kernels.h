@@ -75,3 +75,4 @@
 #include "nrv_errclass.h"      // errclass_kernel (edits and matched columns of the original and the revised reads against a truth set: a wavefront across the lanes, one wave per pair, opt-in)
 #include "nrv_infix.h"         // infix_kernel (the original and the revised reads placed inside truth regions, free ends on the region, both strands: the wavefront of nrv_errclass.h with a reduced final column, one wave per (read, kind, strand), opt-in)
 #include "nrv_labels.h"        // labels_kernel / labels_walk_kernel (per-base training labels: the truth alignment WITH its traceback - the wavefront of nrv_errclass.h storing a 2-bit direction per cell, then one thread per pair walking back, opt-in)
+#include "nrv_score.h"         // score_kernel (both classifiers scored against per-base labels behind the merge: confusion, calibration, integer loss, opt-in)

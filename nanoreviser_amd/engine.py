@@ -44,6 +44,7 @@ SYMBOLS = [
     "nrv_revise_reads_raw_errclass_begin", "nrv_revise_reads_raw_errclass", "nrv_merge_calls_errclass", "nrv_edit_classes",
     "nrv_revise_reads_raw_infix_begin", "nrv_revise_reads_raw_infix", "nrv_merge_calls_infix", "nrv_infix_classes",
     "nrv_align_labels",
+    "nrv_revise_reads_raw_score_begin", "nrv_revise_reads_raw_score", "nrv_merge_calls_score",
 ]
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 PROFILE_COLS = 48                   # NRV_PROFILE_COLS
@@ -54,6 +55,7 @@ INFIX_MAX_LEN = (1 << 21) - 1       # NRV_INFIX_MAX_LEN
 INFIX_R = 16                        # kInfixR of csrc/nrv_infix.h: region characters per lane; a stripe is 64 of them
 LABEL_COLS = 7                      # NRV_LABEL_COLS
 LABELS_MAX_LEN = 65536              # NRV_LABELS_MAX_LEN: of a read and of end - start
+SCORE_COLS = 248                    # NRV_SCORE_COLS
 ERRCLASS_R = 16                     # kErrclassR of csrc/nrv_errclass.h: truth characters per lane; a stripe is 64 of them
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "f16x2": 2}
@@ -105,8 +107,9 @@ _TRIM = ([_FP, C.c_int, C.c_int, C.c_int64, _I64P], lambda p: p[22:27])         
 _TRUTH = ([_U8P, _I64P, _U64P], lambda p: p[27:30])                                      # truth, truth_off, accuracy
 _ERRCLASS = ([_U64P], lambda p: p[30:31])                                                # errclass
 _INFIX = ([C.c_int, _U64P], lambda p: p[31:33])                                          # strands, infix
+_SCORE = ([_U8P, _FP, _U64P], lambda p: p[33:36])                                        # labels, score_thr, score
 # len(packed) -> (synchronous symbol, begin symbol, blocks, whether the call returns merged reads: (seq, qual, off[, report]
-# [, edits, edit_off][, blob, rec_off][, profile][, trim][, accuracy][, errclass][, errclass | None, infix]))
+# [, edits, edit_off][, blob, rec_off][, profile][, trim][, accuracy][, errclass][, errclass | None, infix][, score]))
 _RAW_FORMS = {
     7: ("nrv_predict_reads_raw", "nrv_reads_raw_begin", (_CALLS,), False),
     9: ("nrv_predict_reads_raw_stats", "nrv_reads_raw_stats_begin", (_STATS, _CALLS), False),
@@ -128,6 +131,11 @@ _RAW_FORMS_TRUTH = {
 _RAW_FORMS_INFIX = {
     33: ("nrv_revise_reads_raw_infix", "nrv_revise_reads_raw_infix_begin",
          (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS, _PROFILE, _TRIM, _TRUTH, _ERRCLASS, _INFIX), True),
+}
+# ... and the form that scores both classifiers against per-base labels (tests/test_infix_host.py pins the one above)
+_RAW_FORMS_SCORE = {
+    36: ("nrv_revise_reads_raw_score", "nrv_revise_reads_raw_score_begin",
+         (_STATS, _MERGE, _REPORT, _EDITS, _RECORDS, _PROFILE, _TRIM, _TRUTH, _ERRCLASS, _INFIX, _SCORE), True),
 }
 _PACK_RECORDS_T = [C.c_void_p, _U8P, _U8P, _I64P, C.c_int, _U8P, _I64P, _U8P, _I64P]         # nrv_pack_records
 _READS_HEAD_T = _RAW_HEAD_T[:4] + [C.c_int64, C.POINTER(_ReadDesc), C.c_int]     # nrv_segment_reads, nrv_read_stats: no features
@@ -225,8 +233,9 @@ def load_library(path: Optional[str] = None):
     have_truth = hasattr(lib, "nrv_merge_calls_accuracy")
     have_errclass = hasattr(lib, "nrv_merge_calls_errclass")
     have_infix = hasattr(lib, "nrv_merge_calls_infix")
-    for sync, begin, blocks, _ in list(_RAW_FORMS.values()) + list(_RAW_FORMS_TRUTH.values()) + list(_RAW_FORMS_INFIX.values()):  # (every restype is ctypes' default, int: the nrv_* status)
-        if (have_infix or _INFIX not in blocks) and (have_errclass or _ERRCLASS not in blocks) and (have_truth or _TRUTH not in blocks) and (have_trim or _TRIM not in blocks) and (have_profile or _PROFILE not in blocks) and (have_records or _RECORDS not in blocks) \
+    have_score = hasattr(lib, "nrv_merge_calls_score")
+    for sync, begin, blocks, _ in list(_RAW_FORMS.values()) + list(_RAW_FORMS_TRUTH.values()) + list(_RAW_FORMS_INFIX.values()) + list(_RAW_FORMS_SCORE.values()):  # (every restype is ctypes' default, int: the nrv_* status)
+        if (have_score or _SCORE not in blocks) and (have_infix or _INFIX not in blocks) and (have_errclass or _ERRCLASS not in blocks) and (have_truth or _TRUTH not in blocks) and (have_trim or _TRIM not in blocks) and (have_profile or _PROFILE not in blocks) and (have_records or _RECORDS not in blocks) \
                 and (have_edits or _EDITS not in blocks) and (have_report or _REPORT not in blocks):
             getattr(lib, sync).argtypes = _RAW_HEAD_T + [t for types, _ in blocks for t in types]
             getattr(lib, begin).argtypes = getattr(lib, sync).argtypes + [C.POINTER(C.c_int)]
@@ -254,6 +263,8 @@ def load_library(path: Optional[str] = None):
         lib.nrv_infix_classes.argtypes = _INFIX_CLASSES_T
     if hasattr(lib, "nrv_align_labels"):
         lib.nrv_align_labels.argtypes = _ALIGN_LABELS_T
+    if have_score:
+        lib.nrv_merge_calls_score.argtypes = _MERGE_CALLS_T + _SCORE[0]
     lib.nrv_reads_raw_end.argtypes = [vp, C.c_int]
     lib.nrv_segment_reads.argtypes = _READS_HEAD_T + [fp]
     lib.nrv_read_stats.argtypes = _READS_HEAD_T + [_I32P, _DP, _DP, _DP, _DP, fp]
@@ -659,11 +670,44 @@ class Reviser:
         return packed + (int(strands), np.zeros((packed[4], INFIX_COLS), np.uint64))
 
     @staticmethod
+    def _score_inputs(labels, score_thr, N):
+        """The label bytes and the thresholds of a score, checked: (labels uint8[max(N, 1)], thr float32[39])."""
+        lab = np.ascontiguousarray(labels, dtype=np.uint8).reshape(-1)
+        if lab.size != N:
+            raise ValueError("labels must have one byte per event")
+        if score_thr is None:
+            from .cli import phred_thresholds
+            score_thr = phred_thresholds()
+        thr = np.ascontiguousarray(score_thr, dtype=np.float32).reshape(-1)
+        if thr.size != 39:
+            raise ValueError("score_thr must have 39 entries")
+        return (lab if lab.size else np.full(1, 0xFF, np.uint8)), thr
+
+    @classmethod
+    def with_device_score(cls, packed, labels, score_thr=None):
+        """Any merged tuple - `with_device_merge` (12 elements) up to `with_device_infix` (33) - whose call also scores both
+        classifiers against per-base labels (include/nanorev.h nrv_revise_reads_raw_score_begin; hoststage.score_calls is the
+        definition).  labels: uint8 [N], one byte per event in `align_labels`' format, 0xFF = unlabelled; score_thr: the 39
+        thresholds of the calibration bins (default: cli.phred_thresholds()).  The result has 36 elements: blocks the tuple does
+        not carry are padded with their "not asked for" values - a NULL truth included: the score reads none - and elements
+        33 - 35 are labels, score_thr and score uint64[n_reads][248].  `run_packed_raw` / `begin_packed_raw` + `end_packed_raw`
+        then return what a `with_device_infix` call returns - None for the blocks not carried - and the score block LAST."""
+        if len(packed) not in (12, 14, 16, 20, 22, 27, 30, 31, 33):
+            raise ValueError("with_device_score extends a merged tuple of 12, 14, 16, 20, 22, 27, 30, 31 or 33 elements")
+        packed = tuple(packed)
+        for size, pad in ((12, (0.0, None)), (14, (None, None)), (16, (None, None, None, None)), (20, (None, None)),
+                          (22, (None, 0, 0, 0, None)), (27, (None, None, None)), (30, (None,)), (31, (2, None))):
+            if len(packed) == size:
+                packed += pad
+        lab, thr = cls._score_inputs(labels, score_thr, packed[5])
+        return packed + (lab, thr, np.zeros((packed[4], SCORE_COLS), np.uint64))
+
+    @staticmethod
     def _trim_merged(out):
         seq, qual, off = out[:3]
         total = int(off[-1])
         more, tail = tuple(out[3:]), ()
-        if len(more) in (6, 7, 8, 9, 10):             # (..., profile[, trim[, accuracy[, errclass[, infix]]]]): a `with_device_profile` / `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` / `with_device_infix` call; blocks it does not carry are None
+        if len(more) in (6, 7, 8, 9, 10, 11):         # (..., profile[, trim[, accuracy[, errclass[, infix[, score]]]]]): a `with_device_profile` / `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` / `with_device_infix` / `with_device_score` call; blocks it does not carry are None
             more, tail = more[:5], more[5:]
         if len(more) in (3, 5) and more[1] is not None:   # (report | None, edits, edit_off, ...): the used prefix of the records
             more = (more[0], more[1][:int(more[2][-1])], more[2]) + more[3:]
@@ -679,9 +723,9 @@ class Reviser:
     def _raw_call(self, packed, begin: bool):
         """One call of the raw-read family for a packed tuple of any form (`_RAW_FORMS`): its synchronous entry point, or its
         *_begin with the ticket behind the same arguments.  Returns (ticket number or None, outputs, merged)."""
-        form = _RAW_FORMS.get(len(packed)) or _RAW_FORMS_TRUTH.get(len(packed)) or _RAW_FORMS_INFIX.get(len(packed))
+        form = _RAW_FORMS.get(len(packed)) or _RAW_FORMS_TRUTH.get(len(packed)) or _RAW_FORMS_INFIX.get(len(packed)) or _RAW_FORMS_SCORE.get(len(packed))
         if form is None:
-            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14, 16, 20, 22, 27 or 30 elements - or 31, a 30 with the error classes, or 33, with the infix block -, not {len(packed)}")
+            raise ValueError(f"a packed raw-read call has 7, 9, 12, 14, 16, 20, 22, 27 or 30 elements - or 31, a 30 with the error classes, or 33, with the infix block, or 36, with the score -, not {len(packed)}")
         sync, beg, blocks, merged = form
         if not hasattr(self._lib, beg):               # the report, edits, records, profile, trim, accuracy, error-class and infix pairs are found by presence
             raise NrvError(-1, f"this build of libnanorev_hip.so has no {beg}")
@@ -690,12 +734,13 @@ class Reviser:
             args += _marshal(pick(packed), types)
         t = C.c_int(-1)
         self._check(getattr(self._lib, beg)(*args, C.byref(t)) if begin else getattr(self._lib, sync)(*args))
-        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) + tuple(packed[18:20]) + tuple(packed[21:22]) + tuple(packed[26:27]) + tuple(packed[29:31]) + tuple(packed[32:33]) if merged else packed[6]), merged
+        return (t.value if begin else None), (packed[11] + tuple(packed[13:14]) + tuple(packed[14:16]) + tuple(packed[18:20]) + tuple(packed[21:22]) + tuple(packed[26:27]) + tuple(packed[29:31]) + tuple(packed[32:33]) + tuple(packed[35:36]) if merged else packed[6]), merged
 
     def run_packed_raw(self, packed):
         """The device call of `predict_reads_raw` on what `pack_reads_raw` prepared (or `with_device_stats` /
         `with_device_merge` / `with_device_report` / `with_device_edits` / `with_device_records` / `with_device_profile` /
-        `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` / `with_device_infix` extended)."""
+        `with_device_trim` / `with_device_accuracy` / `with_device_error_classes` / `with_device_infix` / `with_device_score`
+        extended)."""
         _, out, merged = self._raw_call(packed, False)
         return self._trim_merged(out) if merged else out
 
@@ -712,7 +757,8 @@ class Reviser:
         trimmed to rec_off[-1] - for a `with_device_records` call; a `with_device_profile` call returns the latter with the
         profile behind it, a `with_device_trim` call with (profile | None, trim) behind it, a `with_device_accuracy` call with
         (profile | None, trim | None, accuracy) behind it, a `with_device_error_classes` call with the error classes behind
-        that, a `with_device_infix` call with (error classes | None, infix) behind the accuracy."""
+        that, a `with_device_infix` call with (error classes | None, infix) behind the accuracy, a `with_device_score` call
+        with (accuracy | None, error classes | None, infix | None, score) there."""
         t, out = ticket[:2]
         self._check(self._lib.nrv_reads_raw_end(self._h, t))
         return self._trim_merged(out) if len(ticket) == 3 else out
@@ -923,6 +969,22 @@ class Reviser:
         t, toff = self._truth_block(truth, truth_off, nr)
         blk = np.zeros((nr, INFIX_COLS), np.uint64)
         return self._merge_call("nrv_merge_calls_infix", *ins, *_marshal((t, toff, int(strands), blk), _TRUTH[0][:2] + _INFIX[0])) + (blk,)
+
+    def merge_calls_score_device(self, bases, ev_len, a1, a2, labels, p1=None, p2=None, q_thr=None, score_thr=None):
+        """`merge_calls_device` with the score of both classifiers against per-base labels (nrv_merge_calls_score): labels uint8
+        [sum ev_len], 0xFF = unlabelled; p1 / p2 may be given without q_thr (a FASTA merge whose calibration and loss columns are
+        still filled) or left out (those columns stay 0); score_thr defaults to cli.phred_thresholds().  Returns (seq,
+        qual | None, off, score uint64[n_reads][248]) - the block is hoststage.score_calls', bit for bit."""
+        if not hasattr(self._lib, "nrv_merge_calls_score"):
+            raise NrvError(-1, "this build of libnanorev_hip.so has no nrv_merge_calls_score")
+        have_p = p1 is not None and p2 is not None
+        ins = self._merge_inputs(bases, ev_len, a1, a2, p1, p2, q_thr, have_p)
+        n, (q1, q2, thr) = ins[2].size, ins[4:]
+        if (thr is not None and (thr.size != 39 or not have_p)) or (have_p and (q1.shape[0] != n or q2.shape[0] != n)):
+            raise ValueError("q_thr / p1 / p2 do not match")
+        lab, sthr = self._score_inputs(labels, score_thr, ins[0].size)
+        blk = np.zeros((ins[1].size, SCORE_COLS), np.uint64)
+        return self._merge_call("nrv_merge_calls_score", *ins, *_marshal((lab, sthr, blk), _SCORE[0])) + (blk,)
 
     def infix_classes_device(self, truths, reads, reverse=False):
         """infix_kernel alone (nrv_infix_classes): truths (the regions) and reads are equally long lists of byte strings (or
