@@ -670,6 +670,81 @@ int nrv_merge_calls_score(nrv_handle* h, const uint8_t* bases, const int64_t* ev
                           const float* p1, const float* p2, int64_t n_win, const float* q_thr, uint8_t* seq, uint8_t* qual, int64_t* off,
                           const uint8_t* labels, const float* score_thr, uint64_t* score);
 
+/* FITTING THE PER-WINDOW TAIL ON THE DEVICE (opt-in; nothing above changes): what Keras' model.fit gives for the layers behind
+ * Flatten(main_out) - tensors 56 .. 59: feature.kernel Wf [6T][16], feature.bias bf [16], final_out.kernel Wo [16][C],
+ * final_out.bias bo [C] - with the 56 tensors in front of them frozen (the reference: NanoReviser_train.py).  These four are the
+ * only tensors that depend on T or on the class layout; weights.ModelWeights.with_window fills them with noise at T != the
+ * shipped T.  The frozen backbone runs ONCE per window; its 6T main_out values stay on the device, and an epoch touches those
+ * alone.  nanoreviser_amd/tailfit.py is the definition.  Not fitted here: anything in front of main_out (no backbone
+ * gradients); and a fitted tail is not installed into the live handle - the caller writes a weight file and creates a new one.
+ * THE SET.  Per model, flat f32 [rows][6T] (index t * 6 + k) and y uint8 [rows] in device memory, kept in the handle, grown on
+ * demand, freed by nrv_destroy; at most NRV_FIT_MAX_ROWS rows (environment, read by nrv_create; default 2^24, 8.4 GB at T = 11).
+ * Both models always hold the same rows.  A window is LABELLED as in the score block: labels are nrv_align_labels' bytes, one
+ * per event, 0xFF = unlabelled; read r has max(ev_len - T, 0) windows, its window i revises event (T - 1) / 2 + i, and is
+ * labelled when that event's byte is not 0xFF and its code (bits 0 .. 2) is 1 .. 5; y1 = 0 if bit 4 else code, y2 = code - 1.
+ * Windows that straddle two reads are never added.
+ *   nrv_fit_add_reads_raw  the inputs of nrv_reads_raw_stats_begin (last_dur / on_device may both be NULL: no device
+ *     statistics) and labels uint8 [N]; synchronous.  The call's launch groups run on the NRV_PREC_F32 kernels WHATEVER the
+ *     handle's precision mode (selected as the range guard's re-run selects them; in the f16x2 mode main_out never reaches
+ *     memory), and behind each group's head launch a gather moves the six values per (row, t) of every labelled window to its
+ *     slot: rows are appended in window order, slots from an integer prefix scan over the call's events.  Plain stores, no
+ *     atomics.  *n_added = rows added; N <= T adds nothing.  A call that would pass the row cap is refused whole.
+ *   nrv_fit_set_rows / nrv_fit_get_rows  replace the set by n host rows / read rows [first, first + count): the unit doors.
+ *   nrv_fit_reset  empties the set (memory is kept);  nrv_fit_count  its rows (negative: an error code).
+ * THE FIT, per model (0 or 1) with C = 6 or 5 classes.  Parameters travel as ONE vector of
+ *   NRV_FIT_PARAMS(T, C) = 96T + 16 + 16C + C + 16C floats: [Wf | bf | Wo | bo | Ce], Ce [C][16] the centres.
+ * Forward of a row F: z = F Wf + bf, f = max(z, 0), l = f Wo + bo, p = softmax(l) - in the operation order of the f32 mode's
+ * tail, so p is what nrv_predict* returns in NRV_PREC_F32, bit for bit.  Loss of a batch of b rows (lstmmodel.py:63-74; class
+ * weights multiply the row's cross-entropy, and the batch is divided by b):
+ *   L = (1 / b) sum cw[y_i] (-ln p_i[y_i]) + lambda (1 / b) sum |f_i - Ce[y_i]|^2
+ * Gradients with respect to all five tensors; the ReLU derivative is 1 exactly where z > 0.  Per batch two launches
+ * (csrc/nrv_tailfit.h): one workgroup per 32 rows sums its rows in ascending order into a partial vector; one workgroup then
+ * forms g = (sum of the partials in ascending order) / b and, unless some g is not finite, the Adam step of Keras 2.2.4 in f32,
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) (g g);  theta = theta - (lr_t m) / (sqrt(v) + eps),
+ * every operation rounded on its own, sqrt and / correctly rounded, 1 - beta formed in f32, and
+ *   lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t) computed on the host in f64 and rounded to f32, t counting from 1.
+ * A batch with a non-finite g is SKIPPED: no update, t does not advance, it counts in `nonfinite` and in nothing else.
+ * No atomics anywhere: the same calls give the same bytes.
+ *   nrv_fit_begin   params NULL: the handle's own tensors 56 .. 59 and zero centres.  Resets m, v and t.  opts NULL: defaults
+ *                   (B 512, lr 1e-3, beta 0.9 / 0.999, eps 1e-7, lambda 0.4, cw (3, 5, 1, 1, 1, 1) for model 0 and
+ *                   (5, 1, 1, 1, 1) for model 1).  B in 1 .. NRV_FIT_MAX_BATCH.
+ *   nrv_fit_grad    the reduced gradient g [NRV_FIT_PARAMS] of the batch `rows` [b] (row indices into the set) at the current
+ *                   parameters, and its statistics; nothing is updated.  The unit door of the gradient kernel.
+ *   nrv_fit_epoch   rows in the order of `order` [n], in consecutive batches of B, the last one short and divided by its own
+ *                   size: 2 ceil(n / B) launches enqueued on the handle's stream with no host synchronisation in between.
+ *                   Statistics are those BEFORE each batch's update, summed over the batches that were not skipped.
+ *   nrv_fit_eval    forward only over `order` [n]; p [n][C] (may be NULL) and the statistics.  Updates nothing.
+ *   nrv_fit_params  the current vector and t (either may be NULL).
+ * nrv_fit_stats: rows; correct (argmax, ties to the lowest index, equal to the label); ce_sum = sum of cw[y] (-ln p[y]);
+ * center_sum = sum of |f - Ce[y]|^2 (without lambda); steps (updates made); nonfinite (batches skipped - for nrv_fit_grad: 1 if
+ * its g is not finite).  The sums are f64 sums of f32 terms.
+ * Every nrv_fit_* call is refused with NRV_E_INVALID under its own name between a nrv_*_begin and its nrv_reads_raw_end, and
+ * for null pointers, a model other than 0 / 1, a row index >= nrv_fit_count, b outside 1 .. NRV_FIT_MAX_BATCH, a label above
+ * the class count, and nrv_fit_grad / _epoch / _eval / _params before nrv_fit_begin; the handle stays usable.  Not timed yet. */
+#define NRV_FIT_MAX_BATCH 65536
+#define NRV_FIT_PARAMS(T, C) (96 * (T) + 16 + 16 * (C) + (C) + 16 * (C))
+typedef struct nrv_fit_opts {
+  int32_t B;
+  float lr, beta1, beta2, eps, lambda;
+  float cw[6];
+} nrv_fit_opts;
+typedef struct nrv_fit_stats {
+  int64_t rows, correct, steps, nonfinite;
+  double ce_sum, center_sum;
+} nrv_fit_stats;
+int nrv_fit_reset(nrv_handle* h);
+int64_t nrv_fit_count(nrv_handle* h);
+int nrv_fit_add_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts, const float* feat_ev, int64_t N,
+                          const nrv_read_desc* reads, int n_reads, const int32_t* last_dur, const uint8_t* on_device,
+                          const uint8_t* labels, int64_t* n_added);
+int nrv_fit_set_rows(nrv_handle* h, const float* flat1, const float* flat2, const uint8_t* y1, const uint8_t* y2, int64_t n);
+int nrv_fit_get_rows(nrv_handle* h, int64_t first, int64_t count, float* flat1, float* flat2, uint8_t* y1, uint8_t* y2);
+int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_opts* opts);
+int nrv_fit_grad(nrv_handle* h, int model, const uint32_t* rows, int b, float* grad, nrv_fit_stats* stats);
+int nrv_fit_epoch(nrv_handle* h, int model, const uint32_t* order, int64_t n, nrv_fit_stats* stats);
+int nrv_fit_eval(nrv_handle* h, int model, const uint32_t* order, int64_t n, float* p, nrv_fit_stats* stats);
+int nrv_fit_params(nrv_handle* h, int model, float* params, int64_t* t);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

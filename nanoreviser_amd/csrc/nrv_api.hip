@@ -2,6 +2,7 @@
 // the C-ABI declared in include/nanorev.h.  gfx950 only; no CPU path.
 #include "../../include/nanorev.h"
 #include "nrv_kernels.h"
+#include "nrv_tailfit.h"      // the training set and the two kernels of a fitting step (nrv_fit_*, opt-in)
 #include "nrv_block.h"
 
 #include <algorithm>
@@ -667,6 +668,26 @@ struct nrv_handle {
   std::vector<char*> lab_retired;
   hipStream_t lab_stream = nullptr;
   size_t lab_budget = kLabelsBudget;     // bytes of direction words per batch of pairs (NRV_LABELS_BUDGET, read by nrv_create)
+  // nrv_fit_*: the training set of the per-window tail (per model flat [cap][6T] f32 and y [cap] u8, both models the same
+  // rows; grown on demand, poisoned under NRV_POISON, freed by nrv_destroy), the scratch of a step, and per model the
+  // parameter block [theta | m | v | g] with its state on the device.  Everything runs on the handle's stream.
+  struct Fit {
+    float* flat[2] = {nullptr, nullptr};
+    uint8_t* y[2] = {nullptr, nullptr};
+    int64_t rows = 0, cap = 0, max_rows = (int64_t)1 << 24;   // NRV_FIT_MAX_ROWS, read by nrv_create
+    float* d_partial = nullptr; size_t cap_partial = 0;       // [workgroups][P]
+    TailStat* d_pstat = nullptr; size_t cap_pstat = 0;        // [workgroups]
+    unsigned* d_order = nullptr; size_t cap_order = 0;        // row indices of a call
+    float* d_p = nullptr; size_t cap_p = 0;                   // nrv_fit_eval's rows
+    struct Model {
+      float* d_par = nullptr;                                 // [4][P]
+      TailState* d_state = nullptr;
+      float* d_lr = nullptr; size_t cap_lr = 0;
+      bool begun = false;
+      long long t = 0;
+      nrv_fit_opts o = {};
+    } m[2];
+  } fit;
   int64_t sat_reruns = 0;          // pipeline stages the host entry points re-ran on the f32 kernels
   int h2 = 1;                      // 1: f16x2 mode (the default) - lstm2..4 on lstm_h2o / lstm_h2s_kernel, activations between the kernels
                                    // as f16 split planes (cnn dense and head stay on their bf16x3 kernels)
@@ -1495,6 +1516,7 @@ int nrv_create(const nrv_weights* m1, const nrv_weights* m2, int T, int device, 
   if (const char* e3 = getenv("NRV_LANES")) h->lanes_on = atoi(e3) != 0;
   if (const char* e4 = getenv("NRV_COALESCE")) h->coalesce = atoi(e4) != 0;
   if (const char* e6 = getenv("NRV_LABELS_BUDGET"); e6 && *e6) { const long long v = atoll(e6); if (v > 0) h->lab_budget = (size_t)v; }
+  if (const char* e7 = getenv("NRV_FIT_MAX_ROWS"); e7 && *e7) { const long long v = atoll(e7); if (v > 0) h->fit.max_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e5 = getenv("NRV_POISON"); e5 && *e5) { h->poison_on = true; h->poison = (unsigned)strtoul(e5, nullptr, 16); }
   ok = ok && hipMalloc((void**)&h->d_sat, 4 * sizeof(unsigned)) == hipSuccess &&
        hipMemset(h->d_sat, 0, 4 * sizeof(unsigned)) == hipSuccess;
@@ -1527,6 +1549,11 @@ void nrv_destroy(nrv_handle* h) {
   if (h->lab_stream) { (void)hipStreamSynchronize(h->lab_stream); (void)hipStreamDestroy(h->lab_stream); }
   (void)hipFree(h->d_lab);
   for (char* p : h->lab_retired) (void)hipFree(p);
+  for (int m = 0; m < 2; ++m) {
+    (void)hipFree(h->fit.flat[m]); (void)hipFree(h->fit.y[m]);
+    (void)hipFree(h->fit.m[m].d_par); (void)hipFree(h->fit.m[m].d_state); (void)hipFree(h->fit.m[m].d_lr);
+  }
+  (void)hipFree(h->fit.d_partial); (void)hipFree(h->fit.d_pstat); (void)hipFree(h->fit.d_order); (void)hipFree(h->fit.d_p);
   for (int st = 0; st < nrv_handle::kIn; ++st) if (h->ev_in[st]) (void)hipEventDestroy(h->ev_in[st]);
   for (int st = 0; st < 2; ++st) {
     if (h->ev_done[st]) (void)hipEventDestroy(h->ev_done[st]);
@@ -3623,6 +3650,386 @@ int nrv_pack_records_trim(nrv_handle* h, const uint8_t* seq, const uint8_t* qual
     if (n_b > 0) HIPCHK(h, hipMemcpy(blob, d + l.blob, (size_t)n_b, hipMemcpyDeviceToHost));
     return NRV_OK;
   });
+}
+
+// ---- nrv_fit_*: the per-window tail fitted on the device (csrc/nrv_tailfit.h; nanoreviser_amd/tailfit.py is the definition) ----
+// every nrv_fit_* call: a usable handle and no raw-read call in flight (they share the stream, the activation set and d_sig)
+static int fit_enter(nrv_handle* h, const char* who) {
+  const int rc = check_handle(h);
+  if (rc) return rc;
+  if (h->raw_slot[0].busy || h->raw_slot[1].busy) {
+    h->err = std::string(who) + ": a raw-read call is in flight (collect it with nrv_reads_raw_end first)";
+    return NRV_E_INVALID;
+  }
+  return NRV_OK;
+}
+static int fit_refuse(nrv_handle* h, const char* who, const char* what) {
+  h->err = std::string(who) + ": " + what;
+  return NRV_E_INVALID;
+}
+// a scratch buffer of at least `bytes`, contents not kept
+static int fit_scratch(nrv_handle* h, void** p, size_t* cap, size_t bytes) {
+  if (bytes <= *cap) return NRV_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  (void)hipFree(*p);
+  *p = nullptr; *cap = 0;
+  const size_t c = bytes + bytes / 2 + 4096;
+  HIPCHK(h, hipMalloc(p, c));
+  *cap = c;
+  return poison_fill(h, *p, c, h->stream);
+}
+// room for `need` rows in the set, the rows it holds kept
+static int fit_reserve(nrv_handle* h, int64_t need) {
+  nrv_handle::Fit& F = h->fit;
+  if (need <= F.cap) return NRV_OK;
+  int64_t c = F.cap * 2 > need ? F.cap * 2 : need;
+  if (c < 1024) c = 1024;
+  if (c > F.max_rows) c = F.max_rows;
+  const size_t K = 6 * (size_t)h->T;
+  float* nf[2] = {nullptr, nullptr};
+  uint8_t* ny[2] = {nullptr, nullptr};
+  int rc = NRV_OK;
+  for (int m = 0; m < 2 && !rc; ++m) {
+    if (hipMalloc((void**)&nf[m], (size_t)c * K * 4) != hipSuccess || hipMalloc((void**)&ny[m], ((size_t)c + 3) / 4 * 4) != hipSuccess) {
+      h->err = "nrv_fit: out of device memory for the training set";
+      rc = NRV_E_NOMEM;
+      break;
+    }
+    if ((rc = poison_fill(h, nf[m], (size_t)c * K * 4, h->stream)) || (rc = poison_fill(h, ny[m], ((size_t)c + 3) / 4 * 4, h->stream))) break;
+    if (F.rows > 0) {
+      if (hipMemcpyAsync(nf[m], F.flat[m], (size_t)F.rows * K * 4, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
+          hipMemcpyAsync(ny[m], F.y[m], (size_t)F.rows, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
+        h->err = "nrv_fit: copying the training set failed";
+        rc = NRV_E_HIP;
+      }
+    }
+  }
+  if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) { h->err = "nrv_fit: growing the training set failed"; rc = NRV_E_HIP; }
+  if (rc) {
+    for (int m = 0; m < 2; ++m) { (void)hipFree(nf[m]); (void)hipFree(ny[m]); }
+    return rc;
+  }
+  for (int m = 0; m < 2; ++m) {
+    (void)hipFree(F.flat[m]); (void)hipFree(F.y[m]);
+    F.flat[m] = nf[m]; F.y[m] = ny[m];
+  }
+  F.cap = c;
+  return NRV_OK;
+}
+
+// Every stage of the call onto the compute stream as raw_enqueue does it, on the kernels the handle's mode selects (the caller
+// has selected the f32 ones), and behind each launch group the gather of its labelled windows out of h->MO
+static int fit_enqueue(nrv_handle* h, const char* d_in, size_t off_starts, size_t off_reads, size_t off_feat, const int* d_slot,
+                       int n_reads, int64_t n) {
+  const int T = h->T;
+  const int stage = stage_windows(h, true);
+  const float* d_feat = (const float*)(d_in + off_feat);
+  for (int64_t s = 0; s < n; s += stage) {
+    const int nb = (int)((n - s < stage) ? (n - s) : stage);
+    const int rc0 = poison_fill(h, h->d_sig[0], h->sig_bytes, h->stream);
+    if (rc0) return rc0;
+    launch_segment(h, n_reads, s, nb + T - 1, h->d_sig[0], (const int16_t*)d_in, (const int32_t*)(d_in + off_starts),
+                   (const SegRead*)(d_in + off_reads));
+    const int rc = for_groups(h, nb, [&](int64_t w, int nw) -> int {
+      const int rc1 = run_group(h, h->d_sig[0] + w * kSig, d_feat + (s + w) * kFeat, nw, true, h->d_p[0][0] + w * 6, h->d_p[0][1] + w * 5,
+                                h->d_a[0][0] + w, h->d_a[0][1] + w, h->d_sat + 3);
+      if (rc1) return rc1;
+      TailGatherArgs g;
+      for (int m = 0; m < 2; ++m) { g.mo[m] = h->MO[m]; g.flat[m] = h->fit.flat[m]; }
+      g.slot = d_slot + s + w; g.n = nw; g.T = T; g.cap = h->fit.cap;
+      const long long total = (long long)nw * 6 * T;
+      hipLaunchKernelGGL(tail_gather_kernel, dim3((unsigned)((total + 255) / 256), 2), dim3(256), 0, h->stream, g);
+      HIPCHK(h, hipGetLastError());
+      return (int)NRV_OK;
+    });
+    if (rc) return rc;
+  }
+  return NRV_OK;
+}
+
+int nrv_fit_reset(nrv_handle* h) {
+  const int rc = fit_enter(h, "nrv_fit_reset");
+  if (rc) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.rows = 0;
+  return NRV_OK;
+}
+
+int64_t nrv_fit_count(nrv_handle* h) {
+  const int rc = fit_enter(h, "nrv_fit_count");
+  return rc ? (int64_t)rc : h->fit.rows;
+}
+
+int nrv_fit_add_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, const int32_t* starts, const float* feat_ev, int64_t N,
+                          const nrv_read_desc* reads, int n_reads, const int32_t* last_dur, const uint8_t* on_device,
+                          const uint8_t* labels, int64_t* n_added) {
+  static const char* who = "nrv_fit_add_reads_raw";
+  int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (!n_added || (N > 0 && !labels)) return fit_refuse(h, who, "null labels / n_added");
+  if ((last_dur == nullptr) != (on_device == nullptr)) return fit_refuse(h, who, "last_dur and on_device go together");
+  if ((rc = raw_check(h, raw, n_raw, starts, feat_ev, N, reads, n_reads))) { h->err = std::string(who) + ": " + h->err; return rc; }
+  if (N >= ((int64_t)1 << 31)) return fit_refuse(h, who, "2^31 events and more in one call");
+  const bool with_stats = last_dur != nullptr;
+  const int64_t stat_len = with_stats ? stats_check(h, reads, n_reads, last_dur, on_device) : 0;
+  if (stat_len < 0) { h->err = std::string(who) + ": " + h->err; return NRV_E_INVALID; }
+  const int T = h->T;
+  const int64_t n = N - T > 0 ? N - T : 0;
+  *n_added = 0;
+  if (n == 0) return NRV_OK;
+  // the rows this call adds, by the rule of the device's scan: the set is sized, and the cap checked, before anything runs
+  int64_t add = 0;
+  const int64_t o = (T - 1) / 2;
+  for (int r = 0; r < n_reads; ++r) {
+    const int64_t n_r = reads[r].ev_len - T > 0 ? reads[r].ev_len - T : 0;
+    const uint8_t* lb = labels + reads[r].ev_off + o;
+    for (int64_t i = 0; i < n_r; ++i) add += lb[i] != 0xFF && (lb[i] & 7) >= 1 && (lb[i] & 7) <= 5;
+  }
+  nrv_handle::Fit& F = h->fit;
+  if (F.rows + add > F.max_rows) return fit_refuse(h, who, "the call would pass the row cap of the training set (NRV_FIT_MAX_ROWS)");
+  if (add == 0) return NRV_OK;
+  if ((rc = fit_reserve(h, F.rows + add)) || (rc = ensure_workspace(h))) return rc;
+  const int tiles = (int)((N + kMergeTile - 1) / kMergeTile);
+  const size_t off_starts = up256((size_t)n_raw * 2), off_reads = off_starts + up256((size_t)N * 4);
+  const size_t off_feat = off_reads + up256((size_t)n_reads * sizeof(SegRead)), off_aux = off_feat + up256((size_t)N * kFeat * 4);
+  const size_t off_labels = off_aux + (with_stats ? up256((size_t)n_reads * sizeof(StatAux)) : 0);
+  const size_t off_slot = off_labels + up256((size_t)N), off_tile = off_slot + up256((size_t)n * 4);
+  const size_t off_stat = off_tile + up256(((size_t)tiles + 1) * 8);
+  const size_t bytes = off_stat + (stat_len > 0 ? up256((size_t)n_reads * kStatWords * 4) : 0);
+  std::vector<StatAux> aux;
+  if (with_stats) for (int r = 0; r < n_reads; ++r) aux.push_back(StatAux{last_dur[r], on_device[r] ? 1 : 0});
+  const int h2 = h->h2, split = h->split;
+  rc = with_block(h, bytes, h->stream, [&](char* d) -> int {
+    int rc2;
+    if ((rc2 = put(h, d, raw, (size_t)n_raw * 2, h->stream)) || (rc2 = put(h, d + off_starts, starts, (size_t)N * 4, h->stream)) ||
+        (rc2 = put(h, d + off_reads, reads, (size_t)n_reads * sizeof(SegRead), h->stream)) ||
+        (rc2 = put(h, d + off_feat, feat_ev, (size_t)N * kFeat * 4, h->stream)) ||
+        (rc2 = put(h, d + off_aux, aux.data(), aux.size() * sizeof(StatAux), h->stream)) ||
+        (rc2 = put(h, d + off_labels, labels, (size_t)N, h->stream)))
+      return rc2;
+    HIPCHK(h, hipMemsetAsync(d + off_slot, 0xFF, (size_t)n * 4, h->stream));
+    if (stat_len > 0 &&
+        (rc2 = stats_enqueue(h, (const int16_t*)d, (const int32_t*)(d + off_starts), (SegRead*)(d + off_reads), (const StatAux*)(d + off_aux),
+                             (unsigned*)(d + off_stat), n_reads, N, stat_len, (float*)(d + off_feat), nullptr, nullptr)))
+      return rc2;
+    const FitLabelArgs la{(const SegRead*)(d + off_reads), n_reads, T, (long long)N, (const unsigned char*)(d + off_labels),
+                          (unsigned long long*)(d + off_tile), (int*)(d + off_slot), (long long)F.rows, (long long)F.cap, F.y[0], F.y[1]};
+    hipLaunchKernelGGL(fit_label_count_kernel, dim3((unsigned)tiles), dim3(256), 0, h->stream, la);
+    hipLaunchKernelGGL(fit_tile_scan_kernel, dim3(1), dim3(256), 0, h->stream, la, tiles);
+    hipLaunchKernelGGL(fit_label_scatter_kernel, dim3((unsigned)tiles), dim3(256), 0, h->stream, la);
+    HIPCHK(h, hipGetLastError());
+    h->h2 = 0; h->split = 0;                               // the f32 kernels, as the range guard's re-run selects them
+    rc2 = fit_enqueue(h, d, off_starts, off_reads, off_feat, (const int*)(d + off_slot), n_reads, n);
+    h->h2 = h2; h->split = split;
+    if (rc2) return rc2;
+    unsigned long long total = 0;
+    HIPCHK(h, hipMemcpyAsync(&total, d + off_tile + (size_t)tiles * 8, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if ((int64_t)total != add) { h->err = std::string(who) + ": the device counted other labelled windows than the host"; return NRV_E_HIP; }
+    return NRV_OK;
+  });
+  if (rc) return rc;
+  F.rows += add;
+  *n_added = add;
+  return NRV_OK;
+}
+
+int nrv_fit_set_rows(nrv_handle* h, const float* flat1, const float* flat2, const uint8_t* y1, const uint8_t* y2, int64_t n) {
+  static const char* who = "nrv_fit_set_rows";
+  int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && (!flat1 || !flat2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
+  if (n > h->fit.max_rows) return fit_refuse(h, who, "more rows than the cap of the training set (NRV_FIT_MAX_ROWS)");
+  for (int64_t i = 0; i < n; ++i)
+    if (y1[i] > 5 || y2[i] > 4) return fit_refuse(h, who, "a label outside the model's classes (y1 0 .. 5, y2 0 .. 4)");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.rows = 0;
+  if (n == 0) return NRV_OK;
+  if ((rc = fit_reserve(h, n))) return rc;
+  const size_t K = 6 * (size_t)h->T;
+  if ((rc = put(h, h->fit.flat[0], flat1, (size_t)n * K * 4, h->stream)) || (rc = put(h, h->fit.flat[1], flat2, (size_t)n * K * 4, h->stream)) ||
+      (rc = put(h, h->fit.y[0], y1, (size_t)n, h->stream)) || (rc = put(h, h->fit.y[1], y2, (size_t)n, h->stream)))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.rows = n;
+  return NRV_OK;
+}
+
+int nrv_fit_get_rows(nrv_handle* h, int64_t first, int64_t count, float* flat1, float* flat2, uint8_t* y1, uint8_t* y2) {
+  static const char* who = "nrv_fit_get_rows";
+  const int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (count == 0) return NRV_OK;
+  const size_t K = 6 * (size_t)h->T;
+  float* const fl[2] = {flat1, flat2};
+  uint8_t* const yy[2] = {y1, y2};
+  for (int m = 0; m < 2; ++m) {
+    if (fl[m]) HIPCHK(h, hipMemcpy(fl[m], h->fit.flat[m] + (size_t)first * K, (size_t)count * K * 4, hipMemcpyDeviceToHost));
+    if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
+  }
+  return NRV_OK;
+}
+
+static int fit_params_n(const nrv_handle* h, int model) { const int C = h->dm[model].C; return NRV_FIT_PARAMS(h->T, C); }
+
+int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_opts* opts) {
+  static const char* who = "nrv_fit_begin";
+  const int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (model != 0 && model != 1) return fit_refuse(h, who, "model must be 0 or 1");
+  nrv_fit_opts o;
+  if (opts) o = *opts;
+  else {
+    o.B = 512; o.lr = 1e-3f; o.beta1 = 0.9f; o.beta2 = 0.999f; o.eps = 1e-7f; o.lambda = 0.4f;
+    static const float cw1[6] = {3.f, 5.f, 1.f, 1.f, 1.f, 1.f}, cw2[6] = {5.f, 1.f, 1.f, 1.f, 1.f, 0.f};
+    memcpy(o.cw, model == 0 ? cw1 : cw2, sizeof o.cw);
+  }
+  if (o.B < 1 || o.B > NRV_FIT_MAX_BATCH) return fit_refuse(h, who, "B outside 1 .. NRV_FIT_MAX_BATCH");
+  nrv_handle::Fit::Model& M = h->fit.m[model];
+  const DevModel& d = h->dm[model];
+  const int C = d.C, K = 6 * h->T, P = fit_params_n(h, model);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  M.begun = false;
+  if (!M.d_par) {
+    HIPCHK(h, hipMalloc((void**)&M.d_par, (size_t)4 * P * 4));
+    HIPCHK(h, hipMalloc((void**)&M.d_state, sizeof(TailState)));
+  }
+  HIPCHK(h, hipMemsetAsync(M.d_par, 0, (size_t)4 * P * 4, h->stream));
+  if (params) HIPCHK(h, hipMemcpyAsync(M.d_par, params, (size_t)P * 4, hipMemcpyHostToDevice, h->stream));
+  else {
+    const size_t src[4] = {d.fw, d.fb, d.ow, d.ob}, cnt[4] = {(size_t)16 * K, 16, (size_t)16 * C, (size_t)C};
+    size_t at = 0;
+    for (int i = 0; i < 4; ++i) {
+      HIPCHK(h, hipMemcpyAsync(M.d_par + at, d.all + src[i], cnt[i] * 4, hipMemcpyDeviceToDevice, h->stream));
+      at += cnt[i];
+    }
+  }
+  HIPCHK(h, hipMemsetAsync(M.d_state, 0, sizeof(TailState), h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  M.o = o; M.t = 0; M.begun = true;
+  return NRV_OK;
+}
+
+// the checks nrv_fit_grad / _epoch / _eval share, and the upload of their row indices
+static int fit_rows_in(nrv_handle* h, const char* who, int model, const uint32_t* rows, int64_t n) {
+  if (model != 0 && model != 1) return fit_refuse(h, who, "model must be 0 or 1");
+  if (!h->fit.m[model].begun) return fit_refuse(h, who, "no fit in progress for this model (call nrv_fit_begin first)");
+  if (n < 0 || (n > 0 && !rows)) return fit_refuse(h, who, "null row indices (or a negative count)");
+  for (int64_t i = 0; i < n; ++i)
+    if ((int64_t)rows[i] >= h->fit.rows) return fit_refuse(h, who, "a row index outside the training set (>= nrv_fit_count)");
+  int rc;
+  if ((rc = fit_scratch(h, (void**)&h->fit.d_order, &h->fit.cap_order, (size_t)(n > 0 ? n : 1) * 4))) return rc;
+  return put(h, h->fit.d_order, rows, (size_t)n * 4, h->stream);
+}
+static TailGradArgs fit_grad_args(nrv_handle* h, int model, const unsigned* d_rows, int b, float* d_p) {
+  const nrv_handle::Fit::Model& M = h->fit.m[model];
+  TailGradArgs a;
+  a.flat = h->fit.flat[model]; a.y = h->fit.y[model]; a.rows = d_rows; a.par = M.d_par;
+  a.partial = h->fit.d_partial; a.pstat = h->fit.d_pstat; a.p_out = d_p;
+  a.T = h->T; a.C = h->dm[model].C; a.b = b; a.lambda = M.o.lambda;
+  memcpy(a.cw, M.o.cw, sizeof a.cw);
+  return a;
+}
+static TailAdamArgs fit_adam_args(nrv_handle* h, int model, int n_wg, int b, int mode, long long n_lr) {
+  nrv_handle::Fit::Model& M = h->fit.m[model];
+  const int P = fit_params_n(h, model);
+  return TailAdamArgs{h->fit.d_partial, h->fit.d_pstat, n_wg, b, P, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
+                      M.d_state, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+}
+// the device's state of a model as a call starts (t kept, the sums zero) and what it holds once the call's launches are done
+static int fit_state_put(nrv_handle* h, int model) {
+  TailState s{};
+  s.t = h->fit.m[model].t;
+  HIPCHK(h, hipMemcpyAsync(h->fit.m[model].d_state, &s, sizeof s, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));              // (s is a local)
+  return NRV_OK;
+}
+static int fit_state_get(nrv_handle* h, int model, nrv_fit_stats* stats) {
+  TailState s{};
+  HIPCHK(h, hipMemcpyAsync(&s, h->fit.m[model].d_state, sizeof s, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.m[model].t = s.t;
+  if (stats) *stats = nrv_fit_stats{s.rows, s.correct, s.steps, s.nonfinite, s.ce, s.center};
+  return NRV_OK;
+}
+static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
+  const size_t wg = ((size_t)b_max + 31) / 32;
+  int rc;
+  if (grad && (rc = fit_scratch(h, (void**)&h->fit.d_partial, &h->fit.cap_partial, wg * fit_params_n(h, model) * 4))) return rc;
+  return fit_scratch(h, (void**)&h->fit.d_pstat, &h->fit.cap_pstat, wg * sizeof(TailStat));
+}
+
+int nrv_fit_grad(nrv_handle* h, int model, const uint32_t* rows, int b, float* grad, nrv_fit_stats* stats) {
+  static const char* who = "nrv_fit_grad";
+  int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (b < 1 || b > NRV_FIT_MAX_BATCH) return fit_refuse(h, who, "b outside 1 .. NRV_FIT_MAX_BATCH");
+  if (!grad || !rows) return fit_refuse(h, who, "null rows / grad");
+  if ((rc = fit_rows_in(h, who, model, rows, b)) || (rc = fit_step_scratch(h, model, b, true)) || (rc = fit_state_put(h, model))) return rc;
+  const int wg = (b + 31) / 32, P = fit_params_n(h, model);
+  hipLaunchKernelGGL(tail_grad_kernel<true>, dim3(wg), dim3(256), 0, h->stream, fit_grad_args(h, model, h->fit.d_order, b, nullptr));
+  hipLaunchKernelGGL(tail_adam_kernel, dim3(1), dim3(kFitAdamThreads), 0, h->stream, fit_adam_args(h, model, wg, b, kTailGradOnly, 0));
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(grad, h->fit.m[model].d_par + 3 * (size_t)P, (size_t)P * 4, hipMemcpyDeviceToHost, h->stream));
+  return fit_state_get(h, model, stats);
+}
+
+int nrv_fit_epoch(nrv_handle* h, int model, const uint32_t* order, int64_t n, nrv_fit_stats* stats) {
+  static const char* who = "nrv_fit_epoch";
+  int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if ((rc = fit_rows_in(h, who, model, order, n))) return rc;
+  nrv_handle::Fit::Model& M = h->fit.m[model];
+  const int B = M.o.B;
+  const int64_t nb = (n + B - 1) / B;
+  if ((rc = fit_step_scratch(h, model, B, true)) || (rc = fit_scratch(h, (void**)&M.d_lr, &M.cap_lr, (size_t)(nb > 0 ? nb : 1) * 4))) return rc;
+  std::vector<float> lr((size_t)nb);
+  for (int64_t k = 0; k < nb; ++k) {                       // lr_t for t = M.t + 1 .. M.t + nb, in f64, rounded once
+    const double t = (double)(M.t + k + 1);
+    lr[(size_t)k] = (float)((double)M.o.lr * std::sqrt(1.0 - std::pow((double)M.o.beta2, t)) / (1.0 - std::pow((double)M.o.beta1, t)));
+  }
+  if ((rc = put(h, M.d_lr, lr.data(), (size_t)nb * 4, h->stream)) || (rc = fit_state_put(h, model))) return rc;
+  for (int64_t k = 0; k < nb; ++k) {
+    const int b = (int)(n - k * B < B ? n - k * B : B), wg = (b + 31) / 32;
+    hipLaunchKernelGGL(tail_grad_kernel<true>, dim3(wg), dim3(256), 0, h->stream, fit_grad_args(h, model, h->fit.d_order + k * B, b, nullptr));
+    hipLaunchKernelGGL(tail_adam_kernel, dim3(1), dim3(kFitAdamThreads), 0, h->stream, fit_adam_args(h, model, wg, b, kTailTrain, nb));
+  }
+  HIPCHK(h, hipGetLastError());
+  return fit_state_get(h, model, stats);
+}
+
+int nrv_fit_eval(nrv_handle* h, int model, const uint32_t* order, int64_t n, float* p, nrv_fit_stats* stats) {
+  static const char* who = "nrv_fit_eval";
+  int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if ((rc = fit_rows_in(h, who, model, order, n))) return rc;
+  const int C = h->dm[model].C;
+  if ((rc = fit_step_scratch(h, model, kFitMaxB, false)) ||
+      (p && (rc = fit_scratch(h, (void**)&h->fit.d_p, &h->fit.cap_p, (size_t)(n > 0 ? n : 1) * C * 4))) || (rc = fit_state_put(h, model)))
+    return rc;
+  for (int64_t s = 0; s < n; s += kFitMaxB) {
+    const int b = (int)(n - s < kFitMaxB ? n - s : kFitMaxB), wg = (b + 31) / 32;
+    hipLaunchKernelGGL(tail_grad_kernel<false>, dim3(wg), dim3(256), 0, h->stream,
+                       fit_grad_args(h, model, h->fit.d_order + s, b, p ? h->fit.d_p + (size_t)s * C : nullptr));
+    hipLaunchKernelGGL(tail_adam_kernel, dim3(1), dim3(kFitAdamThreads), 0, h->stream, fit_adam_args(h, model, wg, b, kTailEval, 0));
+  }
+  HIPCHK(h, hipGetLastError());
+  if (p && n > 0) HIPCHK(h, hipMemcpyAsync(p, h->fit.d_p, (size_t)n * C * 4, hipMemcpyDeviceToHost, h->stream));
+  return fit_state_get(h, model, stats);
+}
+
+int nrv_fit_params(nrv_handle* h, int model, float* params, int64_t* t) {
+  static const char* who = "nrv_fit_params";
+  const int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (model != 0 && model != 1) return fit_refuse(h, who, "model must be 0 or 1");
+  if (!h->fit.m[model].begun) return fit_refuse(h, who, "no fit in progress for this model (call nrv_fit_begin first)");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (params) HIPCHK(h, hipMemcpy(params, h->fit.m[model].d_par, (size_t)fit_params_n(h, model) * 4, hipMemcpyDeviceToHost));
+  if (t) *t = h->fit.m[model].t;
+  return NRV_OK;
 }
 
 int nrv_saturated(nrv_handle* h, int64_t* pending, int64_t* reruns) {

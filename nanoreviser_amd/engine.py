@@ -45,7 +45,10 @@ SYMBOLS = [
     "nrv_revise_reads_raw_infix_begin", "nrv_revise_reads_raw_infix", "nrv_merge_calls_infix", "nrv_infix_classes",
     "nrv_align_labels",
     "nrv_revise_reads_raw_score_begin", "nrv_revise_reads_raw_score", "nrv_merge_calls_score",
+    "nrv_fit_reset", "nrv_fit_count", "nrv_fit_add_reads_raw", "nrv_fit_set_rows", "nrv_fit_get_rows", "nrv_fit_begin",
+    "nrv_fit_grad", "nrv_fit_epoch", "nrv_fit_eval", "nrv_fit_params",
 ]
+FIT_MAX_BATCH = 65536               # NRV_FIT_MAX_BATCH
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 PROFILE_COLS = 48                   # NRV_PROFILE_COLS
 ACCURACY_COLS = 4                   # NRV_ACCURACY_COLS
@@ -146,6 +149,31 @@ _EDIT_DISTANCE_T = [C.c_void_p, _U8P, _I64P, _U8P, _I64P, C.c_int, _I64P]       
 _EDIT_CLASSES_T = _EDIT_DISTANCE_T + [_I64P]                                                 # nrv_edit_classes
 _INFIX_CLASSES_T = _EDIT_DISTANCE_T[:6] + [C.c_int, _I64P, _I64P, _I64P, _I64P]              # nrv_infix_classes
 _ALIGN_LABELS_T = _EDIT_DISTANCE_T[:6] + [_U8P, _I64P, _I64P, _U8P, _I64P]                   # nrv_align_labels
+_U32P = C.POINTER(C.c_uint32)
+
+
+class _FitOpts(C.Structure):                                                                 # nrv_fit_opts
+    _fields_ = [("B", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("lam", C.c_float), ("cw", C.c_float * 6)]
+
+
+class _FitStats(C.Structure):                                                                # nrv_fit_stats
+    _fields_ = [("rows", C.c_int64), ("correct", C.c_int64), ("steps", C.c_int64), ("nonfinite", C.c_int64),
+                ("ce_sum", C.c_double), ("center_sum", C.c_double)]
+
+
+_FIT_T = {                                                                                   # the nrv_fit_* family
+    "nrv_fit_reset": [C.c_void_p],
+    "nrv_fit_count": [C.c_void_p],
+    "nrv_fit_add_reads_raw": _RAW_HEAD_T + _STATS[0] + [_U8P, _I64P],
+    "nrv_fit_set_rows": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
+    "nrv_fit_get_rows": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
+    "nrv_fit_begin": [C.c_void_p, C.c_int, _FP, C.POINTER(_FitOpts)],
+    "nrv_fit_grad": [C.c_void_p, C.c_int, _U32P, C.c_int, _FP, C.POINTER(_FitStats)],
+    "nrv_fit_epoch": [C.c_void_p, C.c_int, _U32P, C.c_int64, C.POINTER(_FitStats)],
+    "nrv_fit_eval": [C.c_void_p, C.c_int, _U32P, C.c_int64, _FP, C.POINTER(_FitStats)],
+    "nrv_fit_params": [C.c_void_p, C.c_int, _FP, _I64P],
+}
 
 
 _lib = None
@@ -265,6 +293,10 @@ def load_library(path: Optional[str] = None):
         lib.nrv_align_labels.argtypes = _ALIGN_LABELS_T
     if have_score:
         lib.nrv_merge_calls_score.argtypes = _MERGE_CALLS_T + _SCORE[0]
+    if hasattr(lib, "nrv_fit_begin"):
+        for name, types in _FIT_T.items():
+            getattr(lib, name).argtypes = types
+        lib.nrv_fit_count.restype = C.c_int64
     lib.nrv_reads_raw_end.argtypes = [vp, C.c_int]
     lib.nrv_segment_reads.argtypes = _READS_HEAD_T + [fp]
     lib.nrv_read_stats.argtypes = _READS_HEAD_T + [_I32P, _DP, _DP, _DP, _DP, fp]
@@ -768,6 +800,99 @@ class Reviser:
         event features and the read's shift / scale; the signal windows are cut on the device.
         Returns the outputs of `predict_read` on the concatenated per-event arrays (sum(N) - T rows)."""
         return self.run_packed_raw(self.pack_reads_raw(raws, starts, feats, shifts, scales, self.T))
+
+    # ------------------------------------------------------------------ fitting the per-window tail (nrv_fit_*)
+    # include/nanorev.h states the rule; nanoreviser_amd/tailfit.py is the definition.  `model` is 0 or 1.
+    def _n_class(self, model):
+        return 6 if model == 0 else 5
+
+    def fit_reset(self):
+        self._check(self._lib.nrv_fit_reset(self._h))
+
+    def fit_count(self) -> int:
+        n = int(self._lib.nrv_fit_count(self._h))
+        if n < 0:
+            self._check(n)
+        return n
+
+    def fit_add_packed(self, packed, labels) -> int:
+        """The labelled windows of a packed raw-read call (`pack_reads_raw` / `pack_bundle`, with or without
+        `with_device_stats`) appended to the training set; labels: one nrv_align_labels byte per event, 0xFF = unlabelled.
+        Returns the rows added."""
+        N = packed[5]
+        lb = np.ascontiguousarray(labels, dtype=np.uint8).reshape(-1)
+        if lb.size != N:
+            raise ValueError("labels must have one byte per event")
+        stats = packed[7:9] if len(packed) >= 9 else (None, None)
+        added = C.c_int64(0)
+        self._check(self._lib.nrv_fit_add_reads_raw(*self._raw_head(packed), *_marshal(stats, _STATS[0]), _ptr(lb, _U8P),
+                                                    C.byref(added)))
+        return int(added.value)
+
+    def fit_set_rows(self, flat1, flat2, y1, y2):
+        K = 6 * self.T
+        f1, f2 = _as_f32(flat1, (K,)), _as_f32(flat2, (K,))
+        a, b = (np.ascontiguousarray(v, dtype=np.uint8).reshape(-1) for v in (y1, y2))
+        n = f1.shape[0]
+        if f2.shape[0] != n or a.size != n or b.size != n:
+            raise ValueError("flat1 / flat2 / y1 / y2 must have one entry per row")
+        self._check(self._lib.nrv_fit_set_rows(self._h, _ptr(f1, _FP), _ptr(f2, _FP), _ptr(a, _U8P), _ptr(b, _U8P), n))
+
+    def fit_get_rows(self, first=0, count=None):
+        """-> (flat1, flat2, y1, y2) of rows [first, first + count)."""
+        count = self.fit_count() - first if count is None else count
+        K = 6 * self.T
+        out = (np.empty((count, K), np.float32), np.empty((count, K), np.float32), np.empty(count, np.uint8), np.empty(count, np.uint8))
+        self._check(self._lib.nrv_fit_get_rows(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _U8P),
+                                               _ptr(out[3], _U8P)))
+        return out
+
+    def fit_begin(self, model, params=None, opts=None):
+        """opts: a tailfit.FitOpts (None: the engine's defaults); params: the vector [Wf | bf | Wo | bo | Ce] (None: the
+        handle's own tail and zero centres)."""
+        o = None
+        if opts is not None:
+            o = _FitOpts(int(opts.B), opts.lr, opts.beta1, opts.beta2, opts.eps, opts.lam, (C.c_float * 6)(*opts.cw6()))
+        p = None if params is None else np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
+        if p is not None and p.size != self.fit_n_params(model):
+            raise ValueError(f"expected {self.fit_n_params(model)} parameters, got {p.size}")
+        self._check(self._lib.nrv_fit_begin(self._h, model, _ptr(p, _FP), None if o is None else C.byref(o)))
+
+    def fit_n_params(self, model) -> int:
+        c = self._n_class(model)
+        return 96 * self.T + 16 + 16 * c + c + 16 * c
+
+    @staticmethod
+    def _fit_stats(s):
+        from .tailfit import FitStats
+        return FitStats(rows=s.rows, correct=s.correct, ce_sum=s.ce_sum, center_sum=s.center_sum, steps=s.steps, nonfinite=s.nonfinite)
+
+    def fit_grad(self, model, rows):
+        """-> (g [P], FitStats) of the batch `rows` at the current parameters; nothing is updated."""
+        r = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        g, s = np.empty(self.fit_n_params(model), np.float32), _FitStats()
+        self._check(self._lib.nrv_fit_grad(self._h, model, _ptr(r, _U32P), r.size, _ptr(g, _FP), C.byref(s)))
+        return g, self._fit_stats(s)
+
+    def fit_epoch(self, model, order):
+        r = np.ascontiguousarray(order, dtype=np.uint32).reshape(-1)
+        s = _FitStats()
+        self._check(self._lib.nrv_fit_epoch(self._h, model, _ptr(r, _U32P), r.size, C.byref(s)))
+        return self._fit_stats(s)
+
+    def fit_eval(self, model, order, want_p=True):
+        """-> (p [n][C] | None, FitStats): forward only."""
+        r = np.ascontiguousarray(order, dtype=np.uint32).reshape(-1)
+        p = np.empty((r.size, self._n_class(model)), np.float32) if want_p else None
+        s = _FitStats()
+        self._check(self._lib.nrv_fit_eval(self._h, model, _ptr(r, _U32P), r.size, _ptr(p, _FP), C.byref(s)))
+        return p, self._fit_stats(s)
+
+    def fit_params(self, model):
+        """-> (the parameter vector, t)."""
+        p, t = np.empty(self.fit_n_params(model), np.float32), C.c_int64(0)
+        self._check(self._lib.nrv_fit_params(self._h, model, _ptr(p, _FP), C.byref(t)))
+        return p, int(t.value)
 
     def segment_reads(self, raws, starts, shifts, scales):
         """The device-side signal segmentation alone: (sum(N), 50) float32."""

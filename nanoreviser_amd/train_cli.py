@@ -1,0 +1,222 @@
+"""NanoReviser_train.py - the counterpart of the reference's script of this name: fit the per-window tail of both models on
+the device from the per-base labels an earlier `NanoReviser.py --labels` run wrote.
+
+What is kept: -d, -S, -M / --output_model, -w / --window_size, -e, -b, --validation_split, --model_type, --model1_train_dir /
+--model2_train_dir, and the names of the files under <M>/<S>/.  What is changed: --labels_from DIR replaces -r / -m graphmap
+(the truth alignment is `--truth --infix --labels`' job); only the layers behind Flatten(main_out) are fitted - tensors
+56 .. 59, the ones that depend on the window length and the class layout - with the 56 tensors in front frozen
+(nanoreviser_amd/tailfit.py is the definition, include/nanorev.h nrv_fit_* the engine's side).  The frozen backbone runs once
+per labelled window; an epoch touches 6T floats per window.  Device only: the product has no CPU forward.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import cli, tailfit
+from .weights import load_model, load_species
+
+HISTORY_HEAD = "epoch\tloss\tce\tcenter\tacc\tval_loss\tval_acc\tnonfinite"
+
+
+def get_args(argv: Optional[Sequence[str]] = None):
+    p = argparse.ArgumentParser(prog="NanoReviser_train.py", description=__doc__.split("\n\n")[0])
+    p.add_argument("-d", "--fast5_base_dir", dest="fast5_base_dir", help="path to the fast5 files")
+    p.add_argument("-S", "--species", dest="species", default="ecoli", help="whose weights are the frozen backbone and the starting tail")
+    p.add_argument("-M", "--output_model", dest="output_model", default="./model_trained/", help="output model directory")
+    p.add_argument("-w", "--window_size", dest="window_size", type=int, default=None, help="default: the loaded weights' T")
+    p.add_argument("-e", "--epochs", dest="epochs", type=int, default=50)
+    p.add_argument("-b", "--batch_size", dest="batch_size", type=int, default=512)
+    p.add_argument("--validation_split", type=float, default=0.01,
+                   help="the LAST fraction of the rows in file order, before shuffling, as Keras does")
+    p.add_argument("--model_type", default="both", help="both, model1 or model2")
+    p.add_argument("--model1_train_dir", default=None, help="start model 1 from a tail written by an earlier run (.f32 / .h5)")
+    p.add_argument("--model2_train_dir", default=None)
+    p.add_argument("--labels_from", default=None, metavar="DIR", help="required: the directory of an earlier --labels run")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--lr", type=float, default=1e-3)
+    p.add_argument("--center_weight", type=float, default=tailfit.LAMBDA)
+    p.add_argument("--class_weight1", default=",".join(str(int(x)) for x in tailfit.CW1), help="six weights, model 1's classes")
+    p.add_argument("--class_weight2", default=",".join(str(int(x)) for x in tailfit.CW2), help="five weights, model 2's classes")
+    p.add_argument("--fit_init", default="transfer", help="transfer (the loaded tail) or fresh (seeded Glorot-uniform, zero biases)")
+    p.add_argument("--model_dir", default=None, help="root of model/<species>/ (default: next to the package)")
+    p.add_argument("-g", "--basecall_group", dest="basecall_group", default="Basecall_1D_000")
+    p.add_argument("-s", "--basecall_subgroup", dest="basecall_subgroup", default="BaseCalled_template")
+    p.add_argument("--reads_per_call", type=int, default=64, help="reads per device call of the feature extraction")
+    return p.parse_args(argv)
+
+
+def _weights(text, n, what):
+    try:
+        w = [float(x) for x in text.split(",")]
+    except ValueError:
+        w = []
+    if len(w) != n or any(not np.isfinite(x) or x < 0 for x in w):
+        raise ValueError(f"{what} takes {n} non-negative numbers separated by commas")
+    return tuple(w)
+
+
+def check_args(a):
+    """-> the message of the first refusal, or None."""
+    if not a.fast5_base_dir or not os.path.isdir(a.fast5_base_dir):
+        return "-d: not a directory"
+    if not a.labels_from:
+        return "--labels_from DIR is required: the labels come from an earlier `NanoReviser.py --truth --infix --labels` run"
+    if not os.path.isdir(a.labels_from):
+        return "--labels_from: not a directory"
+    if a.model_type not in ("both", "model1", "model2"):
+        return "--model_type must be both, model1 or model2"
+    if a.fit_init not in ("transfer", "fresh"):
+        return "--fit_init must be transfer or fresh"
+    if a.window_size is not None and not 1 <= a.window_size <= 32:
+        return "-w must be in 1 .. 32"
+    if a.epochs < 1:
+        return "-e must be at least 1"
+    if not 1 <= a.batch_size <= tailfit.MAX_BATCH:
+        return f"-b must be in 1 .. {tailfit.MAX_BATCH}"
+    if not 0.0 <= a.validation_split < 1.0:
+        return "--validation_split must be in [0, 1)"
+    if not (a.lr > 0 and np.isfinite(a.lr)) or not (a.center_weight >= 0 and np.isfinite(a.center_weight)):
+        return "--lr must be positive and --center_weight non-negative"
+    try:
+        a.cw1, a.cw2 = _weights(a.class_weight1, 6, "--class_weight1"), _weights(a.class_weight2, 5, "--class_weight2")
+    except ValueError as e:
+        return str(e)
+    return None
+
+
+def stem(output_model, species, model_no):
+    return os.path.join(output_model, species, f"{species}_win13_50ep_model{model_no}")
+
+
+def _start(a, k, m, T):
+    """The starting parameter vector of model k (0 / 1) and where it came from."""
+    path = (a.model1_train_dir, a.model2_train_dir)[k]
+    if path:
+        prev = load_model(path)
+        if prev.T != T or prev.n_class != m.n_class:
+            raise ValueError(f"{path}: a model of T = {prev.T} and {prev.n_class} classes, expected T = {T} and {m.n_class}")
+        th = tailfit.params_from_model(prev)
+        cen = os.path.splitext(path)[0] + "_centers.f32"
+        if os.path.exists(cen):
+            c = np.fromfile(cen, "<f4")
+            if c.size == 16 * m.n_class:
+                th[-c.size:] = c
+        return th, "continued"
+    if a.fit_init == "fresh" or T != m.T:
+        return tailfit.fresh_params(T, m.n_class, a.seed + k), "fresh"
+    return tailfit.params_from_model(m), "transfer"
+
+
+def _default_factory(a, m1, m2):
+    from .engine import Reviser
+    return Reviser(m1, m2, device=0)
+
+
+def add_reads(a, rv, log=print):
+    """Every read of -d through the host stage and its labelled windows into the engine's training set, in file order.
+    -> (reads used, [(file, why)] skipped)."""
+    names = sorted(f for f in os.listdir(a.fast5_base_dir) if f.endswith(".fast5"))
+    used, skipped = 0, []
+    for s in range(0, len(names), max(a.reads_per_call, 1)):
+        jobs = [(os.path.join(a.fast5_base_dir, fn), fn, a.basecall_group, a.basecall_subgroup, False)
+                for fn in names[s:s + max(a.reads_per_call, 1)]]
+        entries, bundle = cli._load_bundle_labelled(jobs, False, a.labels_from)
+        in_bundle = set(bundle["idx"]) if bundle is not None else set()
+        for i, e in enumerate(entries):
+            if i not in in_bundle:
+                skipped.append((e[0], "unreadable"))
+        if bundle is None:
+            continue
+        if "labels" not in bundle:
+            skipped += [(entries[i][0], "no_bases") for i in bundle["idx"]]
+            continue
+        labels, flags = bundle["labels"]
+        for i, f in zip(bundle["idx"], flags):
+            if f == cli.SCORE_SCORED:
+                used += 1
+            else:
+                skipped.append((entries[i][0], "stale_labels" if f == cli.SCORE_STALE else "no_labels"))
+        # (a skipped read's bytes are all 0xFF: it rides along and adds no row)
+        rv.fit_add_packed(rv.pack_bundle(bundle["raw"], bundle["starts"], bundle["feat"], bundle["meta"], rv.T), labels)
+    for fn, why in skipped:
+        log(f"[！！！Warning] {fn}: {why}; the read is not trained on")
+    return used, skipped
+
+
+def fit_model(a, rv, k, theta0, n_train, n_val, log=print):
+    """-> (theta, history lines)."""
+    C = 6 if k == 0 else 5
+    opts = tailfit.FitOpts(B=a.batch_size, lr=a.lr, lam=a.center_weight, cw=a.cw1 if k == 0 else a.cw2)
+    rv.fit_begin(k, theta0, opts)
+    val = np.arange(n_train, n_train + n_val, dtype=np.uint32)
+    lines = []
+    for ep in range(a.epochs):
+        st = rv.fit_epoch(k, tailfit.epoch_order(n_train, a.seed, ep))
+        loss, ce, cn = st.loss(opts.lam)
+        if n_val:
+            sv = rv.fit_eval(k, val, want_p=False)[1]
+            vl, va = f"{sv.loss(opts.lam)[0]:.6f}", f"{sv.acc():.6f}"
+        else:
+            vl = va = "nan"
+        lines.append(f"{ep + 1}\t{loss:.6f}\t{ce:.6f}\t{cn:.6f}\t{st.acc():.6f}\t{vl}\t{va}\t{st.nonfinite}")
+        log(f"[s:::] model{k + 1} epoch {ep + 1}/{a.epochs}: loss {loss:.4f} acc {st.acc():.4f} val_loss {vl} val_acc {va}")
+    theta, _ = rv.fit_params(k)
+    assert theta.size == tailfit.n_params(rv.T, C)
+    return theta, lines
+
+
+def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
+    a = get_args(argv)
+    bad = check_args(a)
+    if bad:
+        print(f"[！！！Error] {bad}", file=sys.stderr)
+        return 2
+    t0 = time.time()
+    m1, m2 = load_species(a.species, a.model_dir)
+    T = a.window_size or m1.T
+    try:
+        starts = [_start(a, k, m, T) for k, m in enumerate((m1, m2))]
+    except (ValueError, OSError) as e:
+        print(f"[！！！Error] {e}", file=sys.stderr)
+        return 2
+    rv = (reviser_factory or _default_factory)(a, m1.with_window(T), m2.with_window(T))
+    try:
+        rv.fit_reset()
+        used, skipped = add_reads(a, rv)
+        n = rv.fit_count()
+        if n == 0:
+            print("[！！！Error] no labelled window: nothing to train on", file=sys.stderr)
+            return 2
+        n_train, n_val = tailfit.val_split(n, a.validation_split)
+        if n_train == 0:
+            print("[！！！Error] --validation_split leaves no row to train on", file=sys.stderr)
+            return 2
+        print(f"[s:::] {n} labelled windows of {used} reads ({len(skipped)} skipped): {n_train} to train on, {n_val} held out")
+        os.makedirs(os.path.join(a.output_model, a.species), exist_ok=True)
+        which = [k for k in (0, 1) if a.model_type in ("both", f"model{k + 1}")]
+        for k in which:
+            theta, lines = fit_model(a, rv, k, starts[k][0], n_train, n_val)
+            st = stem(a.output_model, a.species, k + 1)
+            m = (m1, m2)[k]
+            tailfit.write_f32(tailfit.fitted_model(m, theta, T), st)
+            tailfit.unpack(theta, T, m.n_class)[4].astype("<f4").tofile(st + "_centers.f32")
+            with open(st + "_history.tsv", "w") as fp:
+                fp.write(HISTORY_HEAD + "\n" + "\n".join(lines) + "\n")
+            with open(st + "_summary.json", "w") as fp:
+                json.dump({"options": {"species": a.species, "window_size": T, "epochs": a.epochs, "batch_size": a.batch_size,
+                                       "validation_split": a.validation_split, "seed": a.seed, "lr": a.lr,
+                                       "center_weight": a.center_weight, "class_weight": list(a.cw1 if k == 0 else a.cw2),
+                                       "init": starts[k][1], "labels_from": os.path.abspath(a.labels_from)},
+                           "rows": n, "train_rows": n_train, "val_rows": n_val, "reads": used,
+                           "skipped_reads": [list(s) for s in skipped], "seconds": round(time.time() - t0, 3)}, fp, indent=1)
+                fp.write("\n")
+    finally:
+        rv.close()
+    return 0
