@@ -230,7 +230,7 @@ NRV_HOST_COLD static void pack_lstm_h2s(const Blob& b, int base, int K0, int s0,
   memcpy(out.data(), w.data(), w.size() * 2);
 }
 
-// lstm2_u_kernel (nrv_lstm2_u.h): the 32->64 layer's weights as A operands of the transposed product.
+// lstm2_r_kernel (nrv_lstm2_u.h): the 32->64 layer's weights as A operands of the transposed product.
 // [dir][kb 3: input, recurrent 0, recurrent 1][tile mt 16][term 2][64 lanes][8 f16]; tile mt = gate g * 4 + unit tile ut;
 // lane l = (m = l & 15, q = l >> 4) holds gate-unit (g, u = 16 ut + m) for the k slots 8 q + j:
 //   input block      feature 8 q + j                                   x 2^(E - s_in)
@@ -463,10 +463,10 @@ struct DevModel {
   // shift with the buffer exponents folded in, the producers' scaled epilogue constants
   size_t l_s2[4], l_h2[4];
   // layers 2, 3 (192->128, 256->64) with the BatchNorm IN FRONT of them folded into their weights and bias:
-  // their BatchNorm'd input segment is then the raw h x 2^13 of the layer before (lstm2_u / lstm_h2s RAW copy-out)
+  // their BatchNorm'd input segment is then the raw h x 2^13 of the layer before (lstm2_r / lstm_h2s RAW copy-out)
   size_t l_w2sf[4] = {0, 0, 0, 0}, l_b2sf[4] = {0, 0, 0, 0};
   float descale_f[4] = {1.f, 1.f, 1.f, 1.f};
-  size_t l2t_w = 0, l2t_b = 0;      // lstm2_u_kernel: transposed fragments / bias image of the 32->64 layer
+  size_t l2t_w = 0, l2t_b = 0;      // lstm2_r_kernel: transposed fragments / bias image of the 32->64 layer
   float descale[4];
   size_t l1s2, l1h2;
   size_t cr_dbias = 0;                   // cnn_r_kernel: dense bias x 2^16
@@ -1340,17 +1340,18 @@ static int run_group(nrv_handle* h, const float* d_sig, const float* d_feat, int
     }
     const ActView none[2] = {ActView{}, ActView{}};
     if (h->h2) {
-      // wave-private transposed kernel; hands over h x 2^13 (BatchNorm(128) is in the 192->128 layer's weights)
-      Lstm2TArgs ta;
+      // transposed kernel, one 32-row chain per workgroup; hands over h x 2^13 (BatchNorm(128) is in the 192->128 layer's
+      // weights).  Whole 64-row blocks, as the layers around it: two chains per block.
+      Lstm2RArgs ta;
       ta.T = T; ta.n_rows = n;
       for (int m = 0; m < 2; ++m) {
         const DevModel& d = h->dm[m];
-        ta.m[m] = Lstm2TModelParams{d.all + d.l2t_w, d.all + d.l2t_b, h->X1[m], h->X2[m], d.descale[1]};
+        ta.m[m] = Lstm2RModelParams{d.all + d.l2t_w, d.all + d.l2t_b, h->X1[m], h->X2[m], d.descale[1]};
       }
-      dim3 grid((n + 63) / 64, 2, 2);
+      dim3 grid(2 * ((n + 63) / 64), 2, 2);
       if (!NRV_RUN_STAGE(2)) {}
-      else if (h->act == 0) hipLaunchKernelGGL(lstm2_u_kernel<0>, grid, dim3(kL2uThreads), 0, h->stream, ta);
-      NRV_ACT1(else hipLaunchKernelGGL(lstm2_u_kernel<1>, grid, dim3(kL2uThreads), 0, h->stream, ta);)
+      else if (h->act == 0) hipLaunchKernelGGL(lstm2_r_kernel<0>, grid, dim3(kL2rThreads), 0, h->stream, ta);
+      NRV_ACT1(else hipLaunchKernelGGL(lstm2_r_kernel<1>, grid, dim3(kL2rThreads), 0, h->stream, ta);)
     }
     else if (h->split & 2) {
       const float* ws[2] = {h->dm[0].all + h->dm[0].l_ws[1], h->dm[1].all + h->dm[1].l_ws[1]};

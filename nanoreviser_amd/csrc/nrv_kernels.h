@@ -19,7 +19,7 @@
 //   * FIVE launches per group of 4096 windows in the default (f16x2) mode:
 //       cnn_r_kernel      signal branch (conv1 on the VALU -> conv2 -> dense 400->64 on the matrix pipe, in registers)
 //                         + the 6->16 Bi-LSTM (lstm1_unit) as four more waves of the same workgroups
-//       lstm2_u_kernel    32->64 Bi-LSTM, transposed products, two waves per 16-row chain (r05)
+//       lstm2_r_kernel    32->64 Bi-LSTM, transposed products, weights in registers, four waves per 32-row chain (r07)
 //       lstm_h2w_kernel   192->128 Bi-LSTM, 16x16x32 f16 tiles, eight waves: two per SIMD running a step in opposite order
 //       lstm_h2s_kernel   256->64 Bi-LSTM <64,0,64,...>, 16x16x32 f16 tiles, one wave per SIMD
 //       head_h2_kernel    per-timestep MLP 128->128->32->6 + flatten, feature dense, softmax, argmax
@@ -37,7 +37,7 @@
 //   * One Bi-LSTM layer = one launch; a wave owns a group of hidden units x 4 gates x R row tiles, so
 //     i,f,g,o of one (window, unit) sit in the same lane and the cell update is register-local; c never leaves the
 //     wave, h_t goes through an LDS image (lstm_h2s_kernel: double-buffered, one barrier per step; lstm_h2w_kernel:
-//     one image, two barriers; lstm2_u_kernel: the two halves of a chain's h_t through LDS, one barrier)
+//     one image, two barriers; lstm2_r_kernel: one image per row tile, the two row tiles half a step apart, one barrier each)
 //     and is written out coalesced, the BatchNorm behind it fused or folded into the next layer's weights.
 //
 // Compile-time switches left in these sources (round 6 removed the experiment variants that lost; HISTORY.md keeps the record).
@@ -59,7 +59,7 @@
 #include "nrv_lstm_f16x2.h"    // the scaled two-term f16 split (NRV_PREC_F16X2): types, split2, LstmH2Args
 #include "nrv_lstm_f16x2s.h"   // lstm_h2s_kernel (256->64 layer of the f16x2 mode, 16x16x32 tiles, one wave per SIMD)
 #include "nrv_lstm_f16x2w.h"   // lstm_h2w_kernel (192->128 layer: eight waves, two groups running a step in opposite order)
-#include "nrv_lstm2_u.h"       // lstm2_u_kernel (32->64 layer: transposed products, two waves per chain, h halves through LDS: r05)
+#include "nrv_lstm2_u.h"       // lstm2_r_kernel (32->64 layer: transposed products, weights in registers, 32-row chains of four waves: r07)
 #include "nrv_cnn_r.h"         // cnn_r_kernel (signal branch of the f16x2 mode: conv1 -> conv2 -> dense in registers)
 #include "nrv_head.h"          // head_mlp_kernel, head_mlp_split_kernel, head_final_kernel
 #include "nrv_head_f16x2.h"    // head_h2_kernel (per-timestep MLP + per-window tail, f16x2 mode)
