@@ -1199,6 +1199,21 @@ static void launch_lstm_h2s(nrv_handle* h, int layer, const ActView (&in0)[2], c
   NRV_ACT1(else hipLaunchKernelGGL((lstm_h2s_kernel<KQ0, KQ1, H, R, WR, UH, 1, NBG, NA, KBL, RAW>), grid, blk, 0, h->stream, sa);)
 }
 
+// lstm4_r_kernel (nrv_lstm4_r.h): the 256->64 layer; lstm_h2s_kernel's arguments, packing and grid at <64, 0, 64, 2, 1, 1, ...>
+static void launch_lstm4_r(nrv_handle* h, int layer, const ActView (&in0)[2], float* const out[2], int T, int n, int tiles) {
+  LstmH2Args sa;
+  sa.T = T; sa.n_rows = n;
+  for (int m = 0; m < 2; ++m) {
+    const DevModel& d = h->dm[m];
+    sa.m[m] = LstmH2ModelParams{d.all + d.l_w2sf[layer], d.all + d.l_b2sf[layer], d.all + d.l_s2[layer], d.all + d.l_h2[layer],
+                                in0[m], ActView{}, out[m], d.descale_f[layer]};
+  }
+  sa.n_blk = (tiles + 1) / 2;                        // 64 rows per workgroup
+  dim3 grid(lstm_grid(sa.n_blk)), blk(kL4rThreads);
+  if (h->act == 0) hipLaunchKernelGGL(lstm4_r_kernel<0>, grid, blk, 0, h->stream, sa);
+  NRV_ACT1(else hipLaunchKernelGGL(lstm4_r_kernel<1>, grid, blk, 0, h->stream, sa);)
+}
+
 #ifndef NRV_L3_WS_NBG
 #define NRV_L3_WS_NBG 4                              // weight ring: 4 entries (8: 36 B of scratch and 2 % slower, r04w)
 #endif
@@ -1390,9 +1405,13 @@ static int run_group(nrv_handle* h, const float* d_sig, const float* d_feat, int
     if (h->h2) {
       const ActView i0[2] = {win_view(h->X3[0], 64), win_view(h->X3[1], 64)};
       float* const o[2] = {h->X2[0], h->X2[1]};           // X4 aliases X2; split planes for head_h2_kernel
-      // no BatchNorm behind this layer (RAW); the one in front of it is folded into its weights;
-      // 3 of its 10 weight k-blocks of 32 stay in LDS (96 KB; -3 %)
+      // no BatchNorm behind this layer (raw copy-out); the one in front of it is folded into its weights;
+      // of its 10 weight k-blocks of 32, 3 stay in LDS (96 KB), 5 in registers, 2 are streamed (lstm4_r_kernel)
+#if defined(NRV_L4_H2S) || NRV_STAMP                      // development builds: the kernel before r08, to time one against the other; the stamps live in it
       if (NRV_RUN_STAGE(4)) launch_lstm_h2s<64, 0, 64, 2, 1, 1, 8, 2, 3, true>(h, 3, i0, none, o, T, n, tiles);
+#else
+      if (NRV_RUN_STAGE(4)) launch_lstm4_r(h, 3, i0, o, T, n, tiles);
+#endif
     } else if (h->split & 8) {
       const float* ws[2] = {h->dm[0].all + h->dm[0].l_ws[3], h->dm[1].all + h->dm[1].l_ws[3]};
       launch_lstm_split<64, 0, 64, 1, 2>(h, a, ws, tiles);

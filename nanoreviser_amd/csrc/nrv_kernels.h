@@ -21,7 +21,8 @@
 //                         + the 6->16 Bi-LSTM (lstm1_unit) as four more waves of the same workgroups
 //       lstm2_r_kernel    32->64 Bi-LSTM, transposed products, weights in registers, four waves per 32-row chain (r07)
 //       lstm_h2w_kernel   192->128 Bi-LSTM, 16x16x32 f16 tiles, eight waves: two per SIMD running a step in opposite order
-//       lstm_h2s_kernel   256->64 Bi-LSTM <64,0,64,...>, 16x16x32 f16 tiles, one wave per SIMD
+//       lstm4_r_kernel    256->64 Bi-LSTM, 16x16x32 f16 tiles, one wave per SIMD: lstm_h2s_kernel<64,0,64,...>'s schedule with the
+//                         recurrent and the last three input weight k-blocks in registers (r08)
 //       head_h2_kernel    per-timestep MLP 128->128->32->6 + flatten, feature dense, softmax, argmax
 //     seven in the bf16x3 / f32 modes (cnn_kernel, lstm1_kernel, lstm_pair_kernel / lstm_split_kernel or
 //     lstm_layer_kernel x3, head_mlp(_split)_kernel, head_final_kernel); plus segment_kernel when reads arrive as raw
@@ -45,6 +46,9 @@
 //   NRV_STAMP (+ NRV_STAMP_REC_ENTRIES)   DIAGNOSTIC ONLY: s_memtime stamps at the phase edges of lstm_h2s_kernel / lstm_h2w_kernel and
 //                                         nrv_exp_only_stage / nrv_exp_stamps (scripts/gpu_stamps*.py, gpu_power_stage.py)
 //   NRV_DEV_FAST (-> NRV_ACT1)            DEVELOPMENT ONLY: f16x2 mode with hard_sigmoid only, half the compile time (tools/lstm_exp.sh)
+//   NRV_L4_H2S                            DEVELOPMENT ONLY: the 256->64 layer on lstm_h2s_kernel as before r08, to time one build against
+//                                         the other (scripts/gpu_variants.py); NRV_L4_KBL / NRV_L4_KBR / NRV_L4_NBG: lstm4_r_kernel's
+//                                         LDS blocks / register blocks / ring (3 / 5 / 4; the variants measured: DESIGN.md 3)
 //   NRV_L3_WS_NBG                         the 192->128 layer's weight ring (4; 8 spills: r04w) - bench.KERNEL_SIGNATURE follows it
 // Run-time environment variables of the engine: NRV_COALESCE / NRV_LANES (round 3's stream lanes instead of coalesced 4096-window
 // groups: tests/test_gpu_parity.py grouping tests), NRV_READ_STAGE, NRV_WINDOW_STAGE_MAX, NRV_HOST_REGISTER, NRV_HOST_TRACE,
@@ -58,6 +62,7 @@
 #include "nrv_lstm_bf16x3.h"   // lstm_split_kernel, lstm_pair_kernel
 #include "nrv_lstm_f16x2.h"    // the scaled two-term f16 split (NRV_PREC_F16X2): types, split2, LstmH2Args
 #include "nrv_lstm_f16x2s.h"   // lstm_h2s_kernel (256->64 layer of the f16x2 mode, 16x16x32 tiles, one wave per SIMD)
+#include "nrv_lstm4_r.h"       // lstm4_r_kernel (256->64 layer: lstm_h2s_kernel's schedule, recurrent and late input weights in registers: r08)
 #include "nrv_lstm_f16x2w.h"   // lstm_h2w_kernel (192->128 layer: eight waves, two groups running a step in opposite order)
 #include "nrv_lstm2_u.h"       // lstm2_r_kernel (32->64 layer: transposed products, weights in registers, 32-row chains of four waves: r07)
 #include "nrv_cnn_r.h"         // cnn_r_kernel (signal branch of the f16x2 mode: conv1 -> conv2 -> dense in registers)

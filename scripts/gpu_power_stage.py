@@ -51,7 +51,7 @@ def sampler():
 
 
 names = {-1: "whole step", 0: "cnn_r_kernel (+ lstm1)", 2: "lstm2_r_kernel", 3: "lstm_h2w_kernel (192->128)",
-         4: "lstm_h2s_kernel (256->64)", 5: "head_h2_kernel"}
+         4: "lstm4_r_kernel (256->64)", 5: "head_h2_kernel"}
 res = {}
 for k in [int(x) for x in os.environ.get("POWER_STAGES", "-1,0,2,3,4,5").split(",")]:
     cl.nrv_exp_only_stage(k)

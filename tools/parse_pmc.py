@@ -19,6 +19,8 @@ def short(name):
     if m:
         return {"0, 0, 16": "lstm1", "8, 0, 64": "lstm2", "32, 16, 128": "lstm3", "64, 0, 64": "lstm4"}.get(
             ", ".join(m.groups()), name)
+    if "lstm4_r_kernel" in name:
+        return "lstm4"
     if "lstm1_kernel" in name:
         return "lstm1"
     if "lstm2_t_kernel" in name or "lstm2_u_kernel" in name or "lstm2_r_kernel" in name:
