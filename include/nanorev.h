@@ -60,7 +60,11 @@ void nrv_destroy(nrv_handle* h);
  * (output_handeler.py:250-251, :302-303) on n independent windows.
  *   signal [n][T][50] f32, read [n][T][6] f32 (feature order nanorevtrainutils.py:169).
  *   p1 [n][6], p2 [n][5] softmax outputs; a1, a2 [n] argmax (ties -> lowest index).
- * Any output pointer may be NULL.  All pointers are HOST memory. */
+ * Any output pointer may be NULL.  All pointers are HOST memory.
+ * Alignment is C's: 4 bytes for the float arrays, 1 for a1 / a2; an array may be a view anywhere inside a larger one.
+ * No byte outside the extents stated above is read into a result or written (nrv_predict_read likewise: the N events
+ * in, N-T rows out).  Arrays of 4 MiB and more are page-locked in place for the call (whole pages around them, their
+ * contents untouched) unless NRV_HOST_REGISTER=0 is in the environment. */
 int nrv_predict(nrv_handle* h, const float* signal, const float* read, int64_t n,
                 float* p1, float* p2, int8_t* a1, int8_t* a2);
 
@@ -750,7 +754,11 @@ int nrv_fit_params(nrv_handle* h, int model, float* params, int64_t* t);
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered
  * after work already queued on the legacy default stream (where e.g. torch produces tensors by
  * default); producers on any other stream must be synchronised by the caller, or the handle
- * pointed at that stream with nrv_set_stream. */
+ * pointed at that stream with nrv_set_stream.
+ * Alignment is C's: 4 bytes for the float arrays, 1 for d_a1 / d_a2; a pointer may lie anywhere inside an allocation.
+ * No byte outside [n][T][50] / [n][T][6] in (read form: [N][50] / [N][6]) and [n][6], [n][5], [n], [n] out (read form:
+ * n = N-T rows) is read into a result or written, whatever the launch grouping.
+ * Each of d_p1, d_p2, d_a1, d_a2 may be NULL: that output is not produced, the others are unchanged by it. */
 int nrv_predict_device(nrv_handle* h, const float* d_signal, const float* d_read, int64_t n,
                        float* d_p1, float* d_p2, int8_t* d_a1, int8_t* d_a2);
 int nrv_predict_read_device(nrv_handle* h, const float* d_sig_ev, const float* d_feat_ev,
