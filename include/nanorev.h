@@ -724,7 +724,9 @@ int nrv_merge_calls_score(nrv_handle* h, const uint8_t* bases, const int64_t* ev
  * its g is not finite).  The sums are f64 sums of f32 terms.
  * Every nrv_fit_* call is refused with NRV_E_INVALID under its own name between a nrv_*_begin and its nrv_reads_raw_end, and
  * for null pointers, a model other than 0 / 1, a row index >= nrv_fit_count, b outside 1 .. NRV_FIT_MAX_BATCH, a label above
- * the class count, and nrv_fit_grad / _epoch / _eval / _params before nrv_fit_begin; the handle stays usable.  Not timed yet. */
+ * the class count, and nrv_fit_grad / _epoch / _eval / _params before nrv_fit_begin; the handle stays usable.
+ * Timed (tools/fit_bench.py, one MI355X, 65 536 rows, B 512, T 11, nine epochs after three untimed): 17.06 M rows/s at tail depth
+ * (17.01 .. 17.09), 1.452 M rows/s at head depth (1.451 .. 1.453; see the block below). */
 #define NRV_FIT_MAX_BATCH 65536
 #define NRV_FIT_PARAMS(T, C) (96 * (T) + 16 + 16 * (C) + (C) + 16 * (C))
 typedef struct nrv_fit_opts {
@@ -748,6 +750,50 @@ int nrv_fit_grad(nrv_handle* h, int model, const uint32_t* rows, int b, float* g
 int nrv_fit_epoch(nrv_handle* h, int model, const uint32_t* order, int64_t n, nrv_fit_stats* stats);
 int nrv_fit_eval(nrv_handle* h, int model, const uint32_t* order, int64_t n, float* p, nrv_fit_stats* stats);
 int nrv_fit_params(nrv_handle* h, int model, float* params, int64_t* t);
+
+/* ---- Fitting the whole head behind the frozen Bi-LSTMs: a second DEPTH of nrv_fit_* (opt-in) ----
+ * At depth NRV_FIT_TAIL (the default) everything above holds as it stands.  At depth NRV_FIT_HEAD the frozen boundary moves
+ * from main_out back to the output of lstm4: fitted are the three per-timestep dense layers - tensors 50 .. 55: dense1 W1
+ * [128][128] b1 [128], dense2 W2 [128][32] b2 [32], main_out Wm [32][6] bm [6], every one behind a ReLU - and the tail's
+ * tensors 56 .. 59 with the centres.  nanoreviser_amd/headfit.py is the definition.  Not fitted: the four Bi-LSTMs and the
+ * signal branch.
+ *   nrv_fit_set_depth  NRV_FIT_TAIL or NRV_FIT_HEAD.  Refused by name unless the set is empty (call nrv_fit_reset first), and
+ *                      between a nrv_*_begin and its nrv_reads_raw_end.  It forgets any nrv_fit_begin (the vector has another
+ *                      length) and frees the other depth's set.     nrv_fit_depth  the current depth.
+ * THE SET at head depth.  Per model x4 f32 [rows][T][128] - the f32 lstm4 output of the window, forward and backward halves
+ * concatenated as the head kernels read them - and the same y arrays, grown on demand, freed by nrv_destroy; the flat main_out
+ * rows are not kept.  A row is 512 T bytes, so the depth has its own cap: at most NRV_FIT_MAX_HEAD_ROWS rows (environment, read
+ * by nrv_create; default 2^21, 11.8 GB at T = 11); a call that would pass it is refused whole, by that name.
+ *   nrv_fit_add_reads_raw  unchanged signature and label rule; still the NRV_PREC_F32 kernels whatever the mode.  Behind each
+ *     launch group a gather moves the T x 128 values of every labelled window, 16 bytes at a time with plain stores, from the
+ *     head's input [tile][t][kq 32][32 rows][4] to the window's slot (slots from the same prefix scan).
+ *   nrv_fit_set_rows_head / nrv_fit_get_rows_head  the unit doors at head depth, x [n][T][128].  The flat doors
+ *     nrv_fit_set_rows / _get_rows are refused at head depth and the _head doors at tail depth, each under its own name; the
+ *     handle stays usable.
+ * THE FIT at head depth.  One vector of NRV_FIT_PARAMS_HEAD(T, C) = 20838 + NRV_FIT_PARAMS(T, C) floats:
+ *   [W1 | b1 | W2 | b2 | Wm | bm | Wf | bf | Wo | bo | Ce]      kernels row-major [in][out]; the last five as the tail has them.
+ * nrv_fit_begin, _grad, _epoch, _eval and _params take and return vectors of the CURRENT depth's length; params NULL at head
+ * depth: the handle's own tensors 50 .. 59 and zero centres.  Forward of a row X [T][128], for every t:
+ *   h1 = relu(X_t W1 + b1), h2 = relu(h1 W2 + b2), mo_t = relu(h2 Wm + bm), F[t * 6 + k] = mo_t[k], then the tail's forward
+ * and loss - in the operation order of the f32 mode's head kernels (the same v_mfma_f32_32x32x2_f32 chains in the same k
+ * order), so at the handle's own tensors nrv_fit_eval's p is what nrv_predict* returns in NRV_PREC_F32, bit for bit.
+ * Backward, with the tail's dz [16]: dF = dz Wf^T, dmo_t = dF[t * 6 ..] where mo_t > 0, dh2 = dmo_t Wm^T where h2 > 0,
+ * dh1 = dh2 W2^T where h1 > 0; the kernel gradients, summed over rows and t, are h2^T dmo, h1^T dh2, X_t^T dh1, the bias
+ * gradients the column sums; the tail's five as above.  The 128- and 32-wide products run on the f32 matrix pipe; the backward
+ * pass recomputes h1 and h2 of a timestep instead of keeping them (csrc/nrv_headfit.h).  Per batch three launches: the
+ * gradient (at most 128 workgroups, each over its 32-row tiles in ascending order, one partial vector each), the reduction
+ * g = (sum of the partials in ascending order) / b with the finite check, and the Adam step above, operation for operation,
+ * which no parameter takes unless ALL of g is finite.  A batch with a non-finite g is skipped and counted as above.  Every
+ * sum's order is a function of (b, T) alone and there are no atomics: the same calls give the same bytes.  nrv_fit_epoch
+ * enqueues 3 ceil(n / B) launches with no host synchronisation in between.
+ * A parameter count of the other depth cannot be passed (the vector's length is implied); the Python layer checks it. */
+#define NRV_FIT_TAIL 0
+#define NRV_FIT_HEAD 1
+#define NRV_FIT_PARAMS_HEAD(T, C) (20838 + NRV_FIT_PARAMS(T, C))
+int nrv_fit_set_depth(nrv_handle* h, int depth);
+int nrv_fit_depth(nrv_handle* h);
+int nrv_fit_set_rows_head(nrv_handle* h, const float* x1, const float* x2, const uint8_t* y1, const uint8_t* y2, int64_t n);
+int nrv_fit_get_rows_head(nrv_handle* h, int64_t first, int64_t count, float* x1, float* x2, uint8_t* y1, uint8_t* y2);
 
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be

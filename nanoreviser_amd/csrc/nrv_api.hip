@@ -3,6 +3,7 @@
 #include "../../include/nanorev.h"
 #include "nrv_kernels.h"
 #include "nrv_tailfit.h"      // the training set and the two kernels of a fitting step (nrv_fit_*, opt-in)
+#include "nrv_headfit.h"      // ... at depth NRV_FIT_HEAD: lstm4 outputs as the set, the gradient through the three dense layers
 #include "nrv_block.h"
 
 #include <algorithm>
@@ -675,6 +676,12 @@ struct nrv_handle {
     float* flat[2] = {nullptr, nullptr};
     uint8_t* y[2] = {nullptr, nullptr};
     int64_t rows = 0, cap = 0, max_rows = (int64_t)1 << 24;   // NRV_FIT_MAX_ROWS, read by nrv_create
+    // depth NRV_FIT_HEAD (nrv_fit_set_depth, on an empty set only): the set is x4 [cap][T][128] and y, flat stays null; the
+    // other depth's arrays and both models' parameter blocks are freed when the depth changes, so `cap` counts one kind of row
+    int depth = 0;
+    float* x4[2] = {nullptr, nullptr};
+    int64_t max_head_rows = (int64_t)1 << 21;                 // NRV_FIT_MAX_HEAD_ROWS, read by nrv_create
+    int* d_flag = nullptr; size_t cap_flag = 0;               // head_reduce_kernel's per-workgroup flags
     float* d_partial = nullptr; size_t cap_partial = 0;       // [workgroups][P]
     TailStat* d_pstat = nullptr; size_t cap_pstat = 0;        // [workgroups]
     unsigned* d_order = nullptr; size_t cap_order = 0;        // row indices of a call
@@ -1537,6 +1544,7 @@ int nrv_create(const nrv_weights* m1, const nrv_weights* m2, int T, int device, 
   if (const char* e4 = getenv("NRV_COALESCE")) h->coalesce = atoi(e4) != 0;
   if (const char* e6 = getenv("NRV_LABELS_BUDGET"); e6 && *e6) { const long long v = atoll(e6); if (v > 0) h->lab_budget = (size_t)v; }
   if (const char* e7 = getenv("NRV_FIT_MAX_ROWS"); e7 && *e7) { const long long v = atoll(e7); if (v > 0) h->fit.max_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
+  if (const char* e8 = getenv("NRV_FIT_MAX_HEAD_ROWS"); e8 && *e8) { const long long v = atoll(e8); if (v > 0) h->fit.max_head_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e5 = getenv("NRV_POISON"); e5 && *e5) { h->poison_on = true; h->poison = (unsigned)strtoul(e5, nullptr, 16); }
   ok = ok && hipMalloc((void**)&h->d_sat, 4 * sizeof(unsigned)) == hipSuccess &&
        hipMemset(h->d_sat, 0, 4 * sizeof(unsigned)) == hipSuccess;
@@ -1570,10 +1578,10 @@ void nrv_destroy(nrv_handle* h) {
   (void)hipFree(h->d_lab);
   for (char* p : h->lab_retired) (void)hipFree(p);
   for (int m = 0; m < 2; ++m) {
-    (void)hipFree(h->fit.flat[m]); (void)hipFree(h->fit.y[m]);
+    (void)hipFree(h->fit.flat[m]); (void)hipFree(h->fit.y[m]); (void)hipFree(h->fit.x4[m]);
     (void)hipFree(h->fit.m[m].d_par); (void)hipFree(h->fit.m[m].d_state); (void)hipFree(h->fit.m[m].d_lr);
   }
-  (void)hipFree(h->fit.d_partial); (void)hipFree(h->fit.d_pstat); (void)hipFree(h->fit.d_order); (void)hipFree(h->fit.d_p);
+  (void)hipFree(h->fit.d_partial); (void)hipFree(h->fit.d_pstat); (void)hipFree(h->fit.d_order); (void)hipFree(h->fit.d_p); (void)hipFree(h->fit.d_flag);
   for (int st = 0; st < nrv_handle::kIn; ++st) if (h->ev_in[st]) (void)hipEventDestroy(h->ev_in[st]);
   for (int st = 0; st < 2; ++st) {
     if (h->ev_done[st]) (void)hipEventDestroy(h->ev_done[st]);
@@ -3698,14 +3706,22 @@ static int fit_scratch(nrv_handle* h, void** p, size_t* cap, size_t bytes) {
   *cap = c;
   return poison_fill(h, *p, c, h->stream);
 }
+// floats of one row of the set at the handle's depth, and the parameters of a model's vector
+static size_t fit_row_floats(const nrv_handle* h) { return h->fit.depth ? (size_t)h->T * 128 : 6 * (size_t)h->T; }
+static int fit_params_n(const nrv_handle* h, int model) {
+  const int C = h->dm[model].C;
+  return h->fit.depth ? NRV_FIT_PARAMS_HEAD(h->T, C) : NRV_FIT_PARAMS(h->T, C);
+}
 // room for `need` rows in the set, the rows it holds kept
 static int fit_reserve(nrv_handle* h, int64_t need) {
   nrv_handle::Fit& F = h->fit;
   if (need <= F.cap) return NRV_OK;
   int64_t c = F.cap * 2 > need ? F.cap * 2 : need;
   if (c < 1024) c = 1024;
-  if (c > F.max_rows) c = F.max_rows;
-  const size_t K = 6 * (size_t)h->T;
+  const int64_t cmax = F.depth ? F.max_head_rows : F.max_rows;
+  if (c > cmax) c = cmax;
+  const size_t K = fit_row_floats(h);
+  float** const set = F.depth ? F.x4 : F.flat;
   float* nf[2] = {nullptr, nullptr};
   uint8_t* ny[2] = {nullptr, nullptr};
   int rc = NRV_OK;
@@ -3717,7 +3733,7 @@ static int fit_reserve(nrv_handle* h, int64_t need) {
     }
     if ((rc = poison_fill(h, nf[m], (size_t)c * K * 4, h->stream)) || (rc = poison_fill(h, ny[m], ((size_t)c + 3) / 4 * 4, h->stream))) break;
     if (F.rows > 0) {
-      if (hipMemcpyAsync(nf[m], F.flat[m], (size_t)F.rows * K * 4, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
+      if (hipMemcpyAsync(nf[m], set[m], (size_t)F.rows * K * 4, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
           hipMemcpyAsync(ny[m], F.y[m], (size_t)F.rows, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
         h->err = "nrv_fit: copying the training set failed";
         rc = NRV_E_HIP;
@@ -3730,8 +3746,8 @@ static int fit_reserve(nrv_handle* h, int64_t need) {
     return rc;
   }
   for (int m = 0; m < 2; ++m) {
-    (void)hipFree(F.flat[m]); (void)hipFree(F.y[m]);
-    F.flat[m] = nf[m]; F.y[m] = ny[m];
+    (void)hipFree(set[m]); (void)hipFree(F.y[m]);
+    set[m] = nf[m]; F.y[m] = ny[m];
   }
   F.cap = c;
   return NRV_OK;
@@ -3754,6 +3770,15 @@ static int fit_enqueue(nrv_handle* h, const char* d_in, size_t off_starts, size_
       const int rc1 = run_group(h, h->d_sig[0] + w * kSig, d_feat + (s + w) * kFeat, nw, true, h->d_p[0][0] + w * 6, h->d_p[0][1] + w * 5,
                                 h->d_a[0][0] + w, h->d_a[0][1] + w, h->d_sat + 3);
       if (rc1) return rc1;
+      if (h->fit.depth) {                                  // the head's f32 input (lstm4's output) of the group, still in X2
+        HeadGatherArgs g;
+        for (int m = 0; m < 2; ++m) { g.in[m] = h->X2[m]; g.x[m] = h->fit.x4[m]; }
+        g.slot = d_slot + s + w; g.n = nw; g.T = T; g.cap = h->fit.cap;
+        const long long total = (long long)nw * T * 32;
+        hipLaunchKernelGGL(head_gather_kernel, dim3((unsigned)((total + 255) / 256), 2), dim3(256), 0, h->stream, g);
+        HIPCHK(h, hipGetLastError());
+        return (int)NRV_OK;
+      }
       TailGatherArgs g;
       for (int m = 0; m < 2; ++m) { g.mo[m] = h->MO[m]; g.flat[m] = h->fit.flat[m]; }
       g.slot = d_slot + s + w; g.n = nw; g.T = T; g.cap = h->fit.cap;
@@ -3806,7 +3831,9 @@ int nrv_fit_add_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, cons
     for (int64_t i = 0; i < n_r; ++i) add += lb[i] != 0xFF && (lb[i] & 7) >= 1 && (lb[i] & 7) <= 5;
   }
   nrv_handle::Fit& F = h->fit;
-  if (F.rows + add > F.max_rows) return fit_refuse(h, who, "the call would pass the row cap of the training set (NRV_FIT_MAX_ROWS)");
+  if (F.depth && F.rows + add > F.max_head_rows)
+    return fit_refuse(h, who, "the call would pass the row cap of the training set at head depth (NRV_FIT_MAX_HEAD_ROWS)");
+  if (!F.depth && F.rows + add > F.max_rows) return fit_refuse(h, who, "the call would pass the row cap of the training set (NRV_FIT_MAX_ROWS)");
   if (add == 0) return NRV_OK;
   if ((rc = fit_reserve(h, F.rows + add)) || (rc = ensure_workspace(h))) return rc;
   const int tiles = (int)((N + kMergeTile - 1) / kMergeTile);
@@ -3858,6 +3885,7 @@ int nrv_fit_set_rows(nrv_handle* h, const float* flat1, const float* flat2, cons
   static const char* who = "nrv_fit_set_rows";
   int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)");
   if (n < 0 || (n > 0 && (!flat1 || !flat2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
   if (n > h->fit.max_rows) return fit_refuse(h, who, "more rows than the cap of the training set (NRV_FIT_MAX_ROWS)");
   for (int64_t i = 0; i < n; ++i)
@@ -3879,6 +3907,7 @@ int nrv_fit_get_rows(nrv_handle* h, int64_t first, int64_t count, float* flat1, 
   static const char* who = "nrv_fit_get_rows";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)");
   if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (count == 0) return NRV_OK;
@@ -3892,7 +3921,99 @@ int nrv_fit_get_rows(nrv_handle* h, int64_t first, int64_t count, float* flat1, 
   return NRV_OK;
 }
 
-static int fit_params_n(const nrv_handle* h, int model) { const int C = h->dm[model].C; return NRV_FIT_PARAMS(h->T, C); }
+int nrv_fit_depth(nrv_handle* h) {
+  const int rc = check_handle(h);
+  return rc ? rc : h->fit.depth;
+}
+
+int nrv_fit_set_depth(nrv_handle* h, int depth) {
+  static const char* who = "nrv_fit_set_depth";
+  const int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (depth != NRV_FIT_TAIL && depth != NRV_FIT_HEAD) return fit_refuse(h, who, "depth must be NRV_FIT_TAIL or NRV_FIT_HEAD");
+  nrv_handle::Fit& F = h->fit;
+  if (F.rows != 0) return fit_refuse(h, who, "the training set is not empty (call nrv_fit_reset first)");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int m = 0; m < 2; ++m) {                            // any nrv_fit_begin is forgotten: its vector has the other length
+    F.m[m].begun = false;
+    F.m[m].t = 0;
+  }
+  if (depth == F.depth) return NRV_OK;
+  for (int m = 0; m < 2; ++m) {
+    (void)hipFree(F.flat[m]); (void)hipFree(F.x4[m]); (void)hipFree(F.y[m]);
+    F.flat[m] = nullptr; F.x4[m] = nullptr; F.y[m] = nullptr;
+    (void)hipFree(F.m[m].d_par); (void)hipFree(F.m[m].d_state);
+    F.m[m].d_par = nullptr; F.m[m].d_state = nullptr;
+  }
+  F.cap = 0;
+  F.depth = depth;
+  return NRV_OK;
+}
+
+int nrv_fit_set_rows_head(nrv_handle* h, const float* x1, const float* x2, const uint8_t* y1, const uint8_t* y2, int64_t n) {
+  static const char* who = "nrv_fit_set_rows_head";
+  int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (!h->fit.depth) return fit_refuse(h, who, "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_HEAD) on an empty set first)");
+  if (n < 0 || (n > 0 && (!x1 || !x2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
+  if (n > h->fit.max_head_rows) return fit_refuse(h, who, "more rows than the cap of the training set at head depth (NRV_FIT_MAX_HEAD_ROWS)");
+  for (int64_t i = 0; i < n; ++i)
+    if (y1[i] > 5 || y2[i] > 4) return fit_refuse(h, who, "a label outside the model's classes (y1 0 .. 5, y2 0 .. 4)");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.rows = 0;
+  if (n == 0) return NRV_OK;
+  if ((rc = fit_reserve(h, n))) return rc;
+  const size_t K = fit_row_floats(h);
+  if ((rc = put(h, h->fit.x4[0], x1, (size_t)n * K * 4, h->stream)) || (rc = put(h, h->fit.x4[1], x2, (size_t)n * K * 4, h->stream)) ||
+      (rc = put(h, h->fit.y[0], y1, (size_t)n, h->stream)) || (rc = put(h, h->fit.y[1], y2, (size_t)n, h->stream)))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.rows = n;
+  return NRV_OK;
+}
+
+int nrv_fit_get_rows_head(nrv_handle* h, int64_t first, int64_t count, float* x1, float* x2, uint8_t* y1, uint8_t* y2) {
+  static const char* who = "nrv_fit_get_rows_head";
+  const int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (!h->fit.depth) return fit_refuse(h, who, "the set is at tail depth (rows are main_out values: nrv_fit_get_rows)");
+  if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (count == 0) return NRV_OK;
+  const size_t K = fit_row_floats(h);
+  float* const xs[2] = {x1, x2};
+  uint8_t* const yy[2] = {y1, y2};
+  for (int m = 0; m < 2; ++m) {
+    if (xs[m]) HIPCHK(h, hipMemcpy(xs[m], h->fit.x4[m] + (size_t)first * K, (size_t)count * K * 4, hipMemcpyDeviceToHost));
+    if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
+  }
+  return NRV_OK;
+}
+
+// tensors 50 .. 55 of the handle's own model, row-major as the parameter vector has them, to the front of d_par: the device
+// holds the three kernels only in pack_dense's fragment order, which is undone here; the biases are there as they are
+static int fit_head_own(nrv_handle* h, int model, float* d_par) {
+  const DevModel& d = h->dm[model];
+  const struct { size_t src; int K, N, at; } ker[3] = {{d.d1p, 128, 128, kHfW1}, {d.d2p, 128, 32, kHfW2}, {d.mop, 32, 6, kHfWm}};
+  std::vector<float> own((size_t)kHfMlp), pk;
+  for (const auto& k : ker) {
+    const int NT = (k.N + 31) / 32, KG = k.K / 8;
+    pk.resize((size_t)NT * KG * 256);
+    HIPCHK(h, hipMemcpy(pk.data(), d.all + k.src, pk.size() * 4, hipMemcpyDeviceToHost));
+    for (int nt = 0; nt < NT; ++nt)
+      for (int kg = 0; kg < KG; ++kg)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int j = 0; j < 4; ++j) {
+            const int kk = 8 * kg + 4 * (lane >> 5) + j, col = nt * 32 + (lane & 31);
+            if (col < k.N) own[(size_t)k.at + (size_t)kk * k.N + col] = pk[((size_t)nt * KG + kg) * 256 + lane * 4 + j];
+          }
+  }
+  HIPCHK(h, hipMemcpy(own.data() + kHfB1, d.all + d.d1b, 128 * 4, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(own.data() + kHfB2, d.all + d.d2b, 32 * 4, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(own.data() + kHfBm, d.all + d.mob, 6 * 4, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(d_par, own.data(), own.size() * 4, hipMemcpyHostToDevice));
+  return NRV_OK;
+}
 
 int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_opts* opts) {
   static const char* who = "nrv_fit_begin";
@@ -3914,13 +4035,19 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
   M.begun = false;
   if (!M.d_par) {
     HIPCHK(h, hipMalloc((void**)&M.d_par, (size_t)4 * P * 4));
-    HIPCHK(h, hipMalloc((void**)&M.d_state, sizeof(TailState)));
+    HIPCHK(h, hipMalloc((void**)&M.d_state, sizeof(HeadState)));      // (the tail's state is its front)
   }
   HIPCHK(h, hipMemsetAsync(M.d_par, 0, (size_t)4 * P * 4, h->stream));
   if (params) HIPCHK(h, hipMemcpyAsync(M.d_par, params, (size_t)P * 4, hipMemcpyHostToDevice, h->stream));
   else {
     const size_t src[4] = {d.fw, d.fb, d.ow, d.ob}, cnt[4] = {(size_t)16 * K, 16, (size_t)16 * C, (size_t)C};
     size_t at = 0;
+    if (h->fit.depth) {
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      const int rc2 = fit_head_own(h, model, M.d_par);
+      if (rc2) return rc2;
+      at = kHfMlp;
+    }
     for (int i = 0; i < 4; ++i) {
       HIPCHK(h, hipMemcpyAsync(M.d_par + at, d.all + src[i], cnt[i] * 4, hipMemcpyDeviceToDevice, h->stream));
       at += cnt[i];
@@ -3974,11 +4101,41 @@ static int fit_state_get(nrv_handle* h, int model, nrv_fit_stats* stats) {
   if (stats) *stats = nrv_fit_stats{s.rows, s.correct, s.steps, s.nonfinite, s.ce, s.center};
   return NRV_OK;
 }
+static int fit_head_wgs(int b) { const int tiles = (b + 31) / 32; return tiles < kHeadFitMaxWg ? tiles : kHeadFitMaxWg; }
 static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
-  const size_t wg = ((size_t)b_max + 31) / 32;
+  size_t wg = ((size_t)b_max + 31) / 32;
   int rc;
+  if (h->fit.depth) {
+    wg = (size_t)fit_head_wgs(b_max);
+    if ((rc = fit_scratch(h, (void**)&h->fit.d_flag, &h->fit.cap_flag, (size_t)((kHeadFitMaxP + 255) / 256) * 4))) return rc;
+  }
   if (grad && (rc = fit_scratch(h, (void**)&h->fit.d_partial, &h->fit.cap_partial, wg * fit_params_n(h, model) * 4))) return rc;
   return fit_scratch(h, (void**)&h->fit.d_pstat, &h->fit.cap_pstat, wg * sizeof(TailStat));
+}
+
+// one batch of b rows onto the stream: the gradient (mode kTailGradOnly / kTailTrain) or the forward alone (kTailEval) and the
+// reduce / update behind it - two launches at tail depth, three at head depth
+static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, int mode, long long n_lr, float* d_p) {
+  if (!h->fit.depth) {
+    const int wg = (b + 31) / 32;
+    if (mode == kTailEval) hipLaunchKernelGGL(tail_grad_kernel<false>, dim3(wg), dim3(256), 0, h->stream, fit_grad_args(h, model, d_rows, b, d_p));
+    else hipLaunchKernelGGL(tail_grad_kernel<true>, dim3(wg), dim3(256), 0, h->stream, fit_grad_args(h, model, d_rows, b, d_p));
+    hipLaunchKernelGGL(tail_adam_kernel, dim3(1), dim3(kFitAdamThreads), 0, h->stream, fit_adam_args(h, model, wg, b, mode, n_lr));
+    return;
+  }
+  nrv_handle::Fit::Model& M = h->fit.m[model];
+  const int wg = fit_head_wgs(b), P = fit_params_n(h, model), blocks = (P + 255) / 256;
+  HeadGradArgs a;
+  a.x = h->fit.x4[model]; a.y = h->fit.y[model]; a.rows = d_rows; a.par = M.d_par;
+  a.partial = h->fit.d_partial; a.pstat = h->fit.d_pstat; a.p_out = d_p;
+  a.T = h->T; a.C = h->dm[model].C; a.b = b; a.lambda = M.o.lambda;
+  memcpy(a.cw, M.o.cw, sizeof a.cw);
+  if (mode == kTailEval) hipLaunchKernelGGL(head_grad_kernel<false>, dim3(wg), dim3(256), 0, h->stream, a);
+  else hipLaunchKernelGGL(head_grad_kernel<true>, dim3(wg), dim3(256), 0, h->stream, a);
+  const HeadAdamArgs u{h->fit.d_partial, h->fit.d_pstat, wg, b, P, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
+                       (HeadState*)M.d_state, h->fit.d_flag, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+  hipLaunchKernelGGL(head_reduce_kernel, dim3(blocks), dim3(256), 0, h->stream, u);
+  hipLaunchKernelGGL(head_adam_kernel, dim3(blocks), dim3(256), 0, h->stream, u);
 }
 
 int nrv_fit_grad(nrv_handle* h, int model, const uint32_t* rows, int b, float* grad, nrv_fit_stats* stats) {
@@ -3988,9 +4145,8 @@ int nrv_fit_grad(nrv_handle* h, int model, const uint32_t* rows, int b, float* g
   if (b < 1 || b > NRV_FIT_MAX_BATCH) return fit_refuse(h, who, "b outside 1 .. NRV_FIT_MAX_BATCH");
   if (!grad || !rows) return fit_refuse(h, who, "null rows / grad");
   if ((rc = fit_rows_in(h, who, model, rows, b)) || (rc = fit_step_scratch(h, model, b, true)) || (rc = fit_state_put(h, model))) return rc;
-  const int wg = (b + 31) / 32, P = fit_params_n(h, model);
-  hipLaunchKernelGGL(tail_grad_kernel<true>, dim3(wg), dim3(256), 0, h->stream, fit_grad_args(h, model, h->fit.d_order, b, nullptr));
-  hipLaunchKernelGGL(tail_adam_kernel, dim3(1), dim3(kFitAdamThreads), 0, h->stream, fit_adam_args(h, model, wg, b, kTailGradOnly, 0));
+  const int P = fit_params_n(h, model);
+  fit_launch(h, model, h->fit.d_order, b, kTailGradOnly, 0, nullptr);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(grad, h->fit.m[model].d_par + 3 * (size_t)P, (size_t)P * 4, hipMemcpyDeviceToHost, h->stream));
   return fit_state_get(h, model, stats);
@@ -4012,9 +4168,8 @@ int nrv_fit_epoch(nrv_handle* h, int model, const uint32_t* order, int64_t n, nr
   }
   if ((rc = put(h, M.d_lr, lr.data(), (size_t)nb * 4, h->stream)) || (rc = fit_state_put(h, model))) return rc;
   for (int64_t k = 0; k < nb; ++k) {
-    const int b = (int)(n - k * B < B ? n - k * B : B), wg = (b + 31) / 32;
-    hipLaunchKernelGGL(tail_grad_kernel<true>, dim3(wg), dim3(256), 0, h->stream, fit_grad_args(h, model, h->fit.d_order + k * B, b, nullptr));
-    hipLaunchKernelGGL(tail_adam_kernel, dim3(1), dim3(kFitAdamThreads), 0, h->stream, fit_adam_args(h, model, wg, b, kTailTrain, nb));
+    const int b = (int)(n - k * B < B ? n - k * B : B);
+    fit_launch(h, model, h->fit.d_order + k * B, b, kTailTrain, nb, nullptr);
   }
   HIPCHK(h, hipGetLastError());
   return fit_state_get(h, model, stats);
@@ -4030,10 +4185,8 @@ int nrv_fit_eval(nrv_handle* h, int model, const uint32_t* order, int64_t n, flo
       (p && (rc = fit_scratch(h, (void**)&h->fit.d_p, &h->fit.cap_p, (size_t)(n > 0 ? n : 1) * C * 4))) || (rc = fit_state_put(h, model)))
     return rc;
   for (int64_t s = 0; s < n; s += kFitMaxB) {
-    const int b = (int)(n - s < kFitMaxB ? n - s : kFitMaxB), wg = (b + 31) / 32;
-    hipLaunchKernelGGL(tail_grad_kernel<false>, dim3(wg), dim3(256), 0, h->stream,
-                       fit_grad_args(h, model, h->fit.d_order + s, b, p ? h->fit.d_p + (size_t)s * C : nullptr));
-    hipLaunchKernelGGL(tail_adam_kernel, dim3(1), dim3(kFitAdamThreads), 0, h->stream, fit_adam_args(h, model, wg, b, kTailEval, 0));
+    const int b = (int)(n - s < kFitMaxB ? n - s : kFitMaxB);
+    fit_launch(h, model, h->fit.d_order + s, b, kTailEval, 0, p ? h->fit.d_p + (size_t)s * C : nullptr);
   }
   HIPCHK(h, hipGetLastError());
   if (p && n > 0) HIPCHK(h, hipMemcpyAsync(p, h->fit.d_p, (size_t)n * C * 4, hipMemcpyDeviceToHost, h->stream));

@@ -47,7 +47,9 @@ SYMBOLS = [
     "nrv_revise_reads_raw_score_begin", "nrv_revise_reads_raw_score", "nrv_merge_calls_score",
     "nrv_fit_reset", "nrv_fit_count", "nrv_fit_add_reads_raw", "nrv_fit_set_rows", "nrv_fit_get_rows", "nrv_fit_begin",
     "nrv_fit_grad", "nrv_fit_epoch", "nrv_fit_eval", "nrv_fit_params",
+    "nrv_fit_set_depth", "nrv_fit_depth", "nrv_fit_set_rows_head", "nrv_fit_get_rows_head",
 ]
+FIT_TAIL, FIT_HEAD = 0, 1           # NRV_FIT_TAIL, NRV_FIT_HEAD
 FIT_MAX_BATCH = 65536               # NRV_FIT_MAX_BATCH
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 PROFILE_COLS = 48                   # NRV_PROFILE_COLS
@@ -173,6 +175,10 @@ _FIT_T = {                                                                      
     "nrv_fit_epoch": [C.c_void_p, C.c_int, _U32P, C.c_int64, C.POINTER(_FitStats)],
     "nrv_fit_eval": [C.c_void_p, C.c_int, _U32P, C.c_int64, _FP, C.POINTER(_FitStats)],
     "nrv_fit_params": [C.c_void_p, C.c_int, _FP, _I64P],
+    "nrv_fit_set_depth": [C.c_void_p, C.c_int],
+    "nrv_fit_depth": [C.c_void_p],
+    "nrv_fit_set_rows_head": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
+    "nrv_fit_get_rows_head": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
 }
 
 
@@ -859,8 +865,38 @@ class Reviser:
         self._check(self._lib.nrv_fit_begin(self._h, model, _ptr(p, _FP), None if o is None else C.byref(o)))
 
     def fit_n_params(self, model) -> int:
+        """The length of a model's parameter vector at the current depth."""
         c = self._n_class(model)
-        return 96 * self.T + 16 + 16 * c + c + 16 * c
+        return (20838 if self.fit_depth() == FIT_HEAD else 0) + 96 * self.T + 16 + 16 * c + c + 16 * c
+
+    # ---- the second depth (nanoreviser_amd/headfit.py is the definition): the set holds lstm4 outputs [T][128] per window
+    def fit_set_depth(self, depth):
+        """FIT_TAIL / FIT_HEAD (or "tail" / "head"), on an empty set only; forgets any fit_begin."""
+        depth = {"tail": FIT_TAIL, "head": FIT_HEAD}.get(depth, depth)
+        self._check(self._lib.nrv_fit_set_depth(self._h, int(depth)))
+
+    def fit_depth(self) -> int:
+        d = int(self._lib.nrv_fit_depth(self._h))
+        if d < 0:
+            self._check(d)
+        return d
+
+    def fit_set_rows_head(self, x1, x2, y1, y2):
+        a1, a2 = _as_f32(x1, (self.T, 128)), _as_f32(x2, (self.T, 128))
+        a, b = (np.ascontiguousarray(v, dtype=np.uint8).reshape(-1) for v in (y1, y2))
+        n = a1.shape[0]
+        if a2.shape[0] != n or a.size != n or b.size != n:
+            raise ValueError("x1 / x2 / y1 / y2 must have one entry per row")
+        self._check(self._lib.nrv_fit_set_rows_head(self._h, _ptr(a1, _FP), _ptr(a2, _FP), _ptr(a, _U8P), _ptr(b, _U8P), n))
+
+    def fit_get_rows_head(self, first=0, count=None):
+        """-> (x1, x2, y1, y2) of rows [first, first + count), x [count][T][128]."""
+        count = self.fit_count() - first if count is None else count
+        sh = (count, self.T, 128)
+        out = (np.empty(sh, np.float32), np.empty(sh, np.float32), np.empty(count, np.uint8), np.empty(count, np.uint8))
+        self._check(self._lib.nrv_fit_get_rows_head(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _U8P),
+                                                    _ptr(out[3], _U8P)))
+        return out
 
     @staticmethod
     def _fit_stats(s):

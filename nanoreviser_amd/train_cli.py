@@ -7,6 +7,10 @@ What is kept: -d, -S, -M / --output_model, -w / --window_size, -e, -b, --validat
 56 .. 59, the ones that depend on the window length and the class layout - with the 56 tensors in front frozen
 (nanoreviser_amd/tailfit.py is the definition, include/nanorev.h nrv_fit_* the engine's side).  The frozen backbone runs once
 per labelled window; an epoch touches 6T floats per window.  Device only: the product has no CPU forward.
+
+--fit_depth head moves the frozen boundary back to the output of lstm4: the three per-timestep dense layers (tensors 50 .. 55)
+are fitted too, a window is its 128 T lstm4 values (nanoreviser_amd/headfit.py is the definition).  The default, tail, is
+everything above, byte for byte.
 """
 from __future__ import annotations
 
@@ -19,7 +23,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import cli, tailfit
+from . import cli, headfit, tailfit
 from .weights import load_model, load_species
 
 HISTORY_HEAD = "epoch\tloss\tce\tcenter\tacc\tval_loss\tval_acc\tnonfinite"
@@ -45,6 +49,9 @@ def get_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("--class_weight1", default=",".join(str(int(x)) for x in tailfit.CW1), help="six weights, model 1's classes")
     p.add_argument("--class_weight2", default=",".join(str(int(x)) for x in tailfit.CW2), help="five weights, model 2's classes")
     p.add_argument("--fit_init", default="transfer", help="transfer (the loaded tail) or fresh (seeded Glorot-uniform, zero biases)")
+    p.add_argument("--fit_depth", default="tail",
+                   help="tail: tensors 56 .. 59 behind Flatten(main_out); head: tensors 50 .. 59 behind lstm4 (then --fit_init "
+                        "fresh keeps the shipped 50 .. 55 and fresh_head draws all five layers)")
     p.add_argument("--model_dir", default=None, help="root of model/<species>/ (default: next to the package)")
     p.add_argument("-g", "--basecall_group", dest="basecall_group", default="Basecall_1D_000")
     p.add_argument("-s", "--basecall_subgroup", dest="basecall_subgroup", default="BaseCalled_template")
@@ -72,8 +79,12 @@ def check_args(a):
         return "--labels_from: not a directory"
     if a.model_type not in ("both", "model1", "model2"):
         return "--model_type must be both, model1 or model2"
-    if a.fit_init not in ("transfer", "fresh"):
-        return "--fit_init must be transfer or fresh"
+    if a.fit_depth not in ("tail", "head"):
+        return f"--fit_depth must be tail or head, not {a.fit_depth!r}"
+    if a.fit_depth == "tail" and a.fit_init == "fresh_head":
+        return "--fit_init fresh_head draws the three dense layers behind lstm4, which --fit_depth tail does not fit"
+    if a.fit_init not in (("transfer", "fresh") if a.fit_depth == "tail" else ("transfer", "fresh", "fresh_head")):
+        return "--fit_init must be transfer or fresh" + (f" or fresh_head, not {a.fit_init!r}" if a.fit_depth == "head" else "")
     if a.window_size is not None and not 1 <= a.window_size <= 32:
         return "-w must be in 1 .. 32"
     if a.epochs < 1:
@@ -95,8 +106,32 @@ def stem(output_model, species, model_no):
     return os.path.join(output_model, species, f"{species}_win13_50ep_model{model_no}")
 
 
+def _start_head(a, k, m, T):
+    """_start at --fit_depth head: tensors 50 .. 59 of the loaded or continued model; a fresh tail keeps the shipped 50 .. 55
+    (they do not depend on T), fresh_head draws all five layers."""
+    path = (a.model1_train_dir, a.model2_train_dir)[k]
+    if path:
+        prev = load_model(path)
+        if prev.T != T or prev.n_class != m.n_class:
+            raise ValueError(f"{path}: a model of T = {prev.T} and {prev.n_class} classes, expected T = {T} and {m.n_class}")
+        th = headfit.params_from_model(prev)
+        cen = os.path.splitext(path)[0] + "_centers.f32"
+        if os.path.exists(cen):
+            c = np.fromfile(cen, "<f4")
+            if c.size == 16 * m.n_class:
+                th[-c.size:] = c
+        return th, "continued"
+    if a.fit_init == "fresh_head":
+        return headfit.fresh_params(T, m.n_class, a.seed + k), "fresh_head"
+    if a.fit_init == "fresh" or T != m.T:
+        return headfit.with_tail(headfit.params_from_model(m.with_window(T)), tailfit.fresh_params(T, m.n_class, a.seed + k)), "fresh"
+    return headfit.params_from_model(m), "transfer"
+
+
 def _start(a, k, m, T):
     """The starting parameter vector of model k (0 / 1) and where it came from."""
+    if a.fit_depth == "head":
+        return _start_head(a, k, m, T)
     path = (a.model1_train_dir, a.model2_train_dir)[k]
     if path:
         prev = load_model(path)
@@ -168,7 +203,7 @@ def fit_model(a, rv, k, theta0, n_train, n_val, log=print):
         lines.append(f"{ep + 1}\t{loss:.6f}\t{ce:.6f}\t{cn:.6f}\t{st.acc():.6f}\t{vl}\t{va}\t{st.nonfinite}")
         log(f"[s:::] model{k + 1} epoch {ep + 1}/{a.epochs}: loss {loss:.4f} acc {st.acc():.4f} val_loss {vl} val_acc {va}")
     theta, _ = rv.fit_params(k)
-    assert theta.size == tailfit.n_params(rv.T, C)
+    assert theta.size == (headfit if a.fit_depth == "head" else tailfit).n_params(rv.T, C)
     return theta, lines
 
 
@@ -189,6 +224,8 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
     rv = (reviser_factory or _default_factory)(a, m1.with_window(T), m2.with_window(T))
     try:
         rv.fit_reset()
+        if a.fit_depth == "head":
+            rv.fit_set_depth("head")
         used, skipped = add_reads(a, rv)
         n = rv.fit_count()
         if n == 0:
@@ -205,15 +242,17 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
             theta, lines = fit_model(a, rv, k, starts[k][0], n_train, n_val)
             st = stem(a.output_model, a.species, k + 1)
             m = (m1, m2)[k]
-            tailfit.write_f32(tailfit.fitted_model(m, theta, T), st)
-            tailfit.unpack(theta, T, m.n_class)[4].astype("<f4").tofile(st + "_centers.f32")
+            head = a.fit_depth == "head"
+            tailfit.write_f32(headfit.fitted_model(m, theta, T) if head else tailfit.fitted_model(m, theta, T), st)
+            (headfit if head else tailfit).unpack(theta, T, m.n_class)[-1].astype("<f4").tofile(st + "_centers.f32")
             with open(st + "_history.tsv", "w") as fp:
                 fp.write(HISTORY_HEAD + "\n" + "\n".join(lines) + "\n")
             with open(st + "_summary.json", "w") as fp:
                 json.dump({"options": {"species": a.species, "window_size": T, "epochs": a.epochs, "batch_size": a.batch_size,
                                        "validation_split": a.validation_split, "seed": a.seed, "lr": a.lr,
                                        "center_weight": a.center_weight, "class_weight": list(a.cw1 if k == 0 else a.cw2),
-                                       "init": starts[k][1], "labels_from": os.path.abspath(a.labels_from)},
+                                       "init": starts[k][1], "labels_from": os.path.abspath(a.labels_from),
+                                       **({"fit_depth": "head"} if head else {})},
                            "rows": n, "train_rows": n_train, "val_rows": n_val, "reads": used,
                            "skipped_reads": [list(s) for s in skipped], "seconds": round(time.time() - t0, 3)}, fp, indent=1)
                 fp.write("\n")

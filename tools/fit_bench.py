@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""Time nrv_fit_epoch at both fit depths (tail: tensors 56 .. 59; head: tensors 50 .. 59) on the device.  A plain script: it
+takes no part in bench.py and sets no bar.
+
+A set of seeded rows goes in through the unit doors (nrv_fit_set_rows / nrv_fit_set_rows_head), so the frozen backbone never
+runs: what is timed is one whole nrv_fit_epoch call - the upload of the row order, every batch's launches enqueued back to back
+and the one synchronise at the end - by a host clock around the call, which returns only after that synchronise.  Per depth:
+untimed epochs first (first launches load code objects and size the scratch buffers), then --repeats timed epochs; the median
+and the spread (min .. max) are printed as rows/s, then one JSON line with everything.
+
+    python tools/fit_bench.py [--rows 65536] [-b 512] [-w 11] [--warmup 3] [--repeats 9] [--model 0]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def flop_per_row(depth, T, C):
+    """Multiply-adds x 2 the algorithm needs per row and batch: forward once, data and weight gradients; at head depth the
+    kernel's recomputation of the two wide forward products is NOT counted (it is the implementation's choice)."""
+    tail = 2 * (96 * T + 16 * C) * 3
+    mlp = 2 * T * (128 * 128 + 128 * 32 + 32 * 6)
+    return tail if depth == "tail" else tail + 3 * mlp - 2 * T * 128 * 128      # (no data gradient into X)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--rows", type=int, default=65536)
+    ap.add_argument("-b", "--batch_size", type=int, default=512)
+    ap.add_argument("-w", "--window_size", type=int, default=11)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=9)
+    ap.add_argument("--model", type=int, default=0, choices=(0, 1))
+    ap.add_argument("--species", default="ecoli")
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args(argv)
+    from nanoreviser_amd import headfit, tailfit
+    from nanoreviser_amd.engine import Reviser
+    from nanoreviser_amd.weights import load_species
+    T, k, n = a.window_size, a.model, a.rows
+    C = 6 - k
+    m1, m2 = load_species(a.species)
+    rv = Reviser(m1.with_window(T), m2.with_window(T), device=0)            # no device: this raises, there is no fallback
+    rng = np.random.default_rng(a.seed)
+    y1, y2 = rng.integers(0, 6, n).astype(np.uint8), rng.integers(0, 5, n).astype(np.uint8)
+    opts = tailfit.default_opts(k, B=a.batch_size)
+    out = {"rows": n, "B": a.batch_size, "T": T, "model": k, "warmup": a.warmup, "repeats": a.repeats, "device": None}
+    try:
+        import torch
+        out["device"] = torch.cuda.get_device_name(0)
+    except Exception:
+        pass
+    try:
+        for depth in ("tail", "head"):
+            rv.fit_reset()
+            rv.fit_set_depth(depth)
+            if depth == "tail":
+                F = np.maximum(rng.normal(0, 1, (n, 6 * T)), 0).astype(np.float32)
+                rv.fit_set_rows(F, F, y1, y2)
+                th = tailfit.fresh_params(T, C, a.seed)
+            else:
+                X = np.clip(rng.normal(0, 0.5, (n, T, 128)), -0.999, 0.999).astype(np.float32)
+                rv.fit_set_rows_head(X, X, y1, y2)
+                th = headfit.fresh_params(T, C, a.seed)
+            rv.fit_begin(k, th, opts)
+            for ep in range(a.warmup):
+                rv.fit_epoch(k, tailfit.epoch_order(n, a.seed, ep))
+            secs = []
+            for ep in range(a.repeats):
+                order = tailfit.epoch_order(n, a.seed, a.warmup + ep)
+                t0 = time.perf_counter()
+                st = rv.fit_epoch(k, order)                # returns after the stream's synchronise
+                secs.append(time.perf_counter() - t0)
+                assert st.rows == n and st.nonfinite == 0, st
+            secs = np.array(secs)
+            rate = n / secs
+            gf = flop_per_row(depth, T, C) * 1e-9
+            out[depth] = {"params": int(th.size), "batches": -(-n // a.batch_size), "epoch_ms_median": float(np.median(secs) * 1e3),
+                          "epoch_ms_min": float(secs.min() * 1e3), "epoch_ms_max": float(secs.max() * 1e3),
+                          "rows_per_s_median": float(np.median(rate)), "rows_per_s_min": float(rate.min()),
+                          "rows_per_s_max": float(rate.max()), "gflop_per_batch": gf * a.batch_size,
+                          "gflop_per_s_median": float(np.median(rate) * gf)}
+            print(f"{depth}: {np.median(rate):,.0f} rows/s (min {rate.min():,.0f}, max {rate.max():,.0f}); epoch of {n} rows in "
+                  f"{np.median(secs) * 1e3:.2f} ms = {np.median(secs) / out[depth]['batches'] * 1e6:.1f} us per batch of {a.batch_size}; "
+                  f"{out[depth]['gflop_per_s_median']:,.0f} GFLOP/s of the algorithm's own operations")
+    finally:
+        rv.close()
+    print(json.dumps(out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
