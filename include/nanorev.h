@@ -757,7 +757,7 @@ int nrv_fit_params(nrv_handle* h, int model, float* params, int64_t* t);
  * [128][128] b1 [128], dense2 W2 [128][32] b2 [32], main_out Wm [32][6] bm [6], every one behind a ReLU - and the tail's
  * tensors 56 .. 59 with the centres.  nanoreviser_amd/headfit.py is the definition.  Not fitted: the four Bi-LSTMs and the
  * signal branch.
- *   nrv_fit_set_depth  NRV_FIT_TAIL or NRV_FIT_HEAD.  Refused by name unless the set is empty (call nrv_fit_reset first), and
+ *   nrv_fit_set_depth  NRV_FIT_TAIL or NRV_FIT_HEAD (or NRV_FIT_LSTM4, below).  Refused by name unless the set is empty (call nrv_fit_reset first), and
  *                      between a nrv_*_begin and its nrv_reads_raw_end.  It forgets any nrv_fit_begin (the vector has another
  *                      length) and frees the other depth's set.     nrv_fit_depth  the current depth.
  * THE SET at head depth.  Per model x4 f32 [rows][T][128] - the f32 lstm4 output of the window, forward and backward halves
@@ -794,6 +794,38 @@ int nrv_fit_set_depth(nrv_handle* h, int depth);
 int nrv_fit_depth(nrv_handle* h);
 int nrv_fit_set_rows_head(nrv_handle* h, const float* x1, const float* x2, const uint8_t* y1, const uint8_t* y2, int64_t n);
 int nrv_fit_get_rows_head(nrv_handle* h, int64_t first, int64_t count, float* x1, float* x2, uint8_t* y1, uint8_t* y2);
+
+/* ---- Fitting the last Bi-LSTM with the head: a third DEPTH of nrv_fit_* (opt-in) ----
+ * At depth NRV_FIT_LSTM4 the frozen boundary moves back to the input of lstm4, the 256 -> 64 Bi-LSTM: fitted are its tensors
+ * 44 .. 49 (164352 weights) and everything the head depth fits.  nanoreviser_amd/lstm4fit.py is the definition.  Not fitted:
+ * lstm1 .. lstm3, the BatchNorms and the signal branch.  The number names the Bi-LSTM the fit starts at; 2 and 3 are refused.
+ *   nrv_fit_set_depth  takes NRV_FIT_LSTM4 under the rules above (an empty set, nothing in flight; it forgets any nrv_fit_begin
+ *                      and frees the other depths' sets).
+ * THE SET at this depth.  Per model xb f32 [rows][T][256] - the BatchNorm (tensors 40 .. 43: xb = x sc + sh) of the f32 lstm3
+ * output of the window, in input time order, as the f32 lstm4 launch reads it - and the same y arrays.  A row is 1024 T bytes;
+ * the depth's own cap is NRV_FIT_MAX_LSTM4_ROWS (environment, read by nrv_create; default 2^20, 11.8 GB per model at T = 11); a
+ * call that would pass it is refused whole, by that name.
+ *   nrv_fit_add_reads_raw  unchanged signature and label rule; the NRV_PREC_F32 kernels whatever the mode.  Behind each launch
+ *     group a gather moves the T x 256 values of every labelled window, 16 bytes at a time with plain stores, from lstm4's
+ *     input [tile][t][kq 64][32 rows][4] to the window's slot (the f32 lstm3 launch has applied sc / sh in its epilogue).
+ *   nrv_fit_set_rows_lstm4 / nrv_fit_get_rows_lstm4  the unit doors, xb [n][T][256].  Each depth's doors are refused at the
+ *     other two depths under their own names; the handle stays usable.
+ * THE FIT.  One vector of NRV_FIT_PARAMS_LSTM4(T, C) = 164352 + NRV_FIT_PARAMS_HEAD(T, C) floats:
+ *   [W4f [256][256] | U4f [64][256] | b4f [256] | W4b | U4b | b4b | the head depth's vector]
+ * row-major [in][out], gate columns in Keras order i, f, c, o, forward direction first.  params NULL: the handle's own tensors
+ * 44 .. 59 as the file has them (no BatchNorm folded in) and zero centres.  Forward per direction over its own step order (the
+ * backward direction walks t = T - 1 .. 0): z = xb_t W + h U + b, i f o = act(z) with the handle's recurrent_act, g = tanh(z),
+ * c = f c + i g, h = o tanh(c); X4_t = [h_fw,t | h_bw,t], then the head depth's forward and loss.  Backward: dX4 = dh1 W1^T,
+ * then back through time in both directions, act' decided on the forward VALUE (hard sigmoid: 0.2 exactly where 0 < a < 1);
+ * gW = sum xb_t^T dz, gU = sum h_{s-1}^T dz, gb = sum dz (csrc/nrv_lstm4fit.h).  A batch runs in chunks of 4096 rows in
+ * ascending order: forward, head (which also forms dX4), backward and the weight gradients are separate launches, then the
+ * reduction and the Adam step of the head depth over the longer vector; the finite check covers the whole vector before any
+ * parameter moves.  No atomics; every sum's order is a function of (b, T) alone: the same calls give the same bytes.
+ * nrv_fit_epoch enqueues all launches with no host synchronisation in between; nrv_fit_eval runs the forward launches alone. */
+#define NRV_FIT_LSTM4 4
+#define NRV_FIT_PARAMS_LSTM4(T, C) (164352 + NRV_FIT_PARAMS_HEAD(T, C))
+int nrv_fit_set_rows_lstm4(nrv_handle* h, const float* xb1, const float* xb2, const uint8_t* y1, const uint8_t* y2, int64_t n);
+int nrv_fit_get_rows_lstm4(nrv_handle* h, int64_t first, int64_t count, float* xb1, float* xb2, uint8_t* y1, uint8_t* y2);
 
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be

@@ -4,6 +4,7 @@
 #include "nrv_kernels.h"
 #include "nrv_tailfit.h"      // the training set and the two kernels of a fitting step (nrv_fit_*, opt-in)
 #include "nrv_headfit.h"      // ... at depth NRV_FIT_HEAD: lstm4 outputs as the set, the gradient through the three dense layers
+#include "nrv_lstm4fit.h"     // ... at depth NRV_FIT_LSTM4: BatchNorm'd lstm3 outputs as the set, the last Bi-LSTM's forward and backward
 #include "nrv_block.h"
 
 #include <algorithm>
@@ -459,6 +460,7 @@ struct DevModel {
   size_t l1w16, l1b16;        // lstm1 packed for the 16x16x4 kernel
   size_t l_ws[4];             // lstm2..4 weights split into three bf16 terms (index 1..3)
   size_t d1p, d1b, d2p, d2b, mop, mob, fw, fb, ow, ob;
+  size_t l4raw = 0;           // tensors 44 .. 49 as the file has them (nrv_fit_begin at depth NRV_FIT_LSTM4 starts from them)
   size_t h_ws, h_wb;          // head_mlp_split_kernel: split weights / biases
   // f16x2 mode (nrv_lstm_f16x2.h): lstm2..4 weights as two f16 terms, scaled biases, output scale /
   // shift with the buffer exponents folded in, the producers' scaled epilogue constants
@@ -681,6 +683,12 @@ struct nrv_handle {
     int depth = 0;
     float* x4[2] = {nullptr, nullptr};
     int64_t max_head_rows = (int64_t)1 << 21;                 // NRV_FIT_MAX_HEAD_ROWS, read by nrv_create
+    // depth NRV_FIT_LSTM4: the set is xb [cap][T][256] and y; the scratch of one chunk of a batch (nrv_lstm4fit.h) and the
+    // LSTM block's gradient sums
+    float* xb[2] = {nullptr, nullptr};
+    int64_t max_lstm4_rows = (int64_t)1 << 20;                // NRV_FIT_MAX_LSTM4_ROWS, read by nrv_create
+    float* d_l4 = nullptr; size_t cap_l4 = 0;                 // [X4 | dX4 | CS | GZ] of kL4ChunkRows rows
+    float* d_gl4 = nullptr; size_t cap_gl4 = 0;               // [kL4N]
     int* d_flag = nullptr; size_t cap_flag = 0;               // head_reduce_kernel's per-workgroup flags
     float* d_partial = nullptr; size_t cap_partial = 0;       // [workgroups][P]
     TailStat* d_pstat = nullptr; size_t cap_pstat = 0;        // [workgroups]
@@ -777,6 +785,11 @@ NRV_HOST_COLD static int upload_model(nrv_handle* h, int mi, const Blob& b, int 
     memcpy(cv + 240, b.t(7), 8 * 4);
     bn_fold(b.t(8), b.t(9), b.t(10), b.t(11), 8, cv + 248, cv + 256);
     d.conv = put(cv, 264);
+  }
+  {
+    static const size_t n4[6] = {256 * 256, 64 * 256, 256, 256 * 256, 64 * 256, 256};
+    d.l4raw = put(b.t(44), n4[0]);
+    for (int i = 1; i < 6; ++i) (void)put(b.t(44 + i), n4[i]);
   }
   std::vector<float> wp, bs;
   pack_dense16(b.t(32), 400, 64, wp);
@@ -1544,6 +1557,7 @@ int nrv_create(const nrv_weights* m1, const nrv_weights* m2, int T, int device, 
   if (const char* e4 = getenv("NRV_COALESCE")) h->coalesce = atoi(e4) != 0;
   if (const char* e6 = getenv("NRV_LABELS_BUDGET"); e6 && *e6) { const long long v = atoll(e6); if (v > 0) h->lab_budget = (size_t)v; }
   if (const char* e7 = getenv("NRV_FIT_MAX_ROWS"); e7 && *e7) { const long long v = atoll(e7); if (v > 0) h->fit.max_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
+  if (const char* e9 = getenv("NRV_FIT_MAX_LSTM4_ROWS"); e9 && *e9) { const long long v = atoll(e9); if (v > 0) h->fit.max_lstm4_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e8 = getenv("NRV_FIT_MAX_HEAD_ROWS"); e8 && *e8) { const long long v = atoll(e8); if (v > 0) h->fit.max_head_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e5 = getenv("NRV_POISON"); e5 && *e5) { h->poison_on = true; h->poison = (unsigned)strtoul(e5, nullptr, 16); }
   ok = ok && hipMalloc((void**)&h->d_sat, 4 * sizeof(unsigned)) == hipSuccess &&
@@ -1578,10 +1592,11 @@ void nrv_destroy(nrv_handle* h) {
   (void)hipFree(h->d_lab);
   for (char* p : h->lab_retired) (void)hipFree(p);
   for (int m = 0; m < 2; ++m) {
-    (void)hipFree(h->fit.flat[m]); (void)hipFree(h->fit.y[m]); (void)hipFree(h->fit.x4[m]);
+    (void)hipFree(h->fit.flat[m]); (void)hipFree(h->fit.y[m]); (void)hipFree(h->fit.x4[m]); (void)hipFree(h->fit.xb[m]);
     (void)hipFree(h->fit.m[m].d_par); (void)hipFree(h->fit.m[m].d_state); (void)hipFree(h->fit.m[m].d_lr);
   }
   (void)hipFree(h->fit.d_partial); (void)hipFree(h->fit.d_pstat); (void)hipFree(h->fit.d_order); (void)hipFree(h->fit.d_p); (void)hipFree(h->fit.d_flag);
+  (void)hipFree(h->fit.d_l4); (void)hipFree(h->fit.d_gl4);
   for (int st = 0; st < nrv_handle::kIn; ++st) if (h->ev_in[st]) (void)hipEventDestroy(h->ev_in[st]);
   for (int st = 0; st < 2; ++st) {
     if (h->ev_done[st]) (void)hipEventDestroy(h->ev_done[st]);
@@ -3707,21 +3722,26 @@ static int fit_scratch(nrv_handle* h, void** p, size_t* cap, size_t bytes) {
   return poison_fill(h, *p, c, h->stream);
 }
 // floats of one row of the set at the handle's depth, and the parameters of a model's vector
-static size_t fit_row_floats(const nrv_handle* h) { return h->fit.depth ? (size_t)h->T * 128 : 6 * (size_t)h->T; }
+static size_t fit_row_floats(const nrv_handle* h) {
+  return h->fit.depth == NRV_FIT_LSTM4 ? (size_t)h->T * 256 : h->fit.depth ? (size_t)h->T * 128 : 6 * (size_t)h->T;
+}
 static int fit_params_n(const nrv_handle* h, int model) {
   const int C = h->dm[model].C;
-  return h->fit.depth ? NRV_FIT_PARAMS_HEAD(h->T, C) : NRV_FIT_PARAMS(h->T, C);
+  return h->fit.depth == NRV_FIT_LSTM4 ? NRV_FIT_PARAMS_LSTM4(h->T, C) : h->fit.depth ? NRV_FIT_PARAMS_HEAD(h->T, C) : NRV_FIT_PARAMS(h->T, C);
 }
+// the current depth's set and its cap
+static float** fit_set(nrv_handle::Fit& F) { return F.depth == NRV_FIT_LSTM4 ? F.xb : F.depth ? F.x4 : F.flat; }
+static int64_t fit_cap_rows(const nrv_handle::Fit& F) { return F.depth == NRV_FIT_LSTM4 ? F.max_lstm4_rows : F.depth ? F.max_head_rows : F.max_rows; }
 // room for `need` rows in the set, the rows it holds kept
 static int fit_reserve(nrv_handle* h, int64_t need) {
   nrv_handle::Fit& F = h->fit;
   if (need <= F.cap) return NRV_OK;
   int64_t c = F.cap * 2 > need ? F.cap * 2 : need;
   if (c < 1024) c = 1024;
-  const int64_t cmax = F.depth ? F.max_head_rows : F.max_rows;
+  const int64_t cmax = fit_cap_rows(F);
   if (c > cmax) c = cmax;
   const size_t K = fit_row_floats(h);
-  float** const set = F.depth ? F.x4 : F.flat;
+  float** const set = fit_set(F);
   float* nf[2] = {nullptr, nullptr};
   uint8_t* ny[2] = {nullptr, nullptr};
   int rc = NRV_OK;
@@ -3770,6 +3790,15 @@ static int fit_enqueue(nrv_handle* h, const char* d_in, size_t off_starts, size_
       const int rc1 = run_group(h, h->d_sig[0] + w * kSig, d_feat + (s + w) * kFeat, nw, true, h->d_p[0][0] + w * 6, h->d_p[0][1] + w * 5,
                                 h->d_a[0][0] + w, h->d_a[0][1] + w, h->d_sat + 3);
       if (rc1) return rc1;
+      if (h->fit.depth == NRV_FIT_LSTM4) {                 // lstm4's f32 input (lstm3's output behind its BatchNorm), still in X3
+        L4GatherArgs g;
+        for (int m = 0; m < 2; ++m) { g.in[m] = h->X3[m]; g.x[m] = h->fit.xb[m]; }
+        g.slot = d_slot + s + w; g.n = nw; g.T = T; g.cap = h->fit.cap;
+        const long long total = (long long)nw * T * 64;
+        hipLaunchKernelGGL(l4_gather_kernel, dim3((unsigned)((total + 255) / 256), 2), dim3(256), 0, h->stream, g);
+        HIPCHK(h, hipGetLastError());
+        return (int)NRV_OK;
+      }
       if (h->fit.depth) {                                  // the head's f32 input (lstm4's output) of the group, still in X2
         HeadGatherArgs g;
         for (int m = 0; m < 2; ++m) { g.in[m] = h->X2[m]; g.x[m] = h->fit.x4[m]; }
@@ -3831,7 +3860,9 @@ int nrv_fit_add_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, cons
     for (int64_t i = 0; i < n_r; ++i) add += lb[i] != 0xFF && (lb[i] & 7) >= 1 && (lb[i] & 7) <= 5;
   }
   nrv_handle::Fit& F = h->fit;
-  if (F.depth && F.rows + add > F.max_head_rows)
+  if (F.depth == NRV_FIT_LSTM4 && F.rows + add > F.max_lstm4_rows)
+    return fit_refuse(h, who, "the call would pass the row cap of the training set at lstm4 depth (NRV_FIT_MAX_LSTM4_ROWS)");
+  if (F.depth == NRV_FIT_HEAD && F.rows + add > F.max_head_rows)
     return fit_refuse(h, who, "the call would pass the row cap of the training set at head depth (NRV_FIT_MAX_HEAD_ROWS)");
   if (!F.depth && F.rows + add > F.max_rows) return fit_refuse(h, who, "the call would pass the row cap of the training set (NRV_FIT_MAX_ROWS)");
   if (add == 0) return NRV_OK;
@@ -3885,6 +3916,7 @@ int nrv_fit_set_rows(nrv_handle* h, const float* flat1, const float* flat2, cons
   static const char* who = "nrv_fit_set_rows";
   int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)");
   if (h->fit.depth) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)");
   if (n < 0 || (n > 0 && (!flat1 || !flat2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
   if (n > h->fit.max_rows) return fit_refuse(h, who, "more rows than the cap of the training set (NRV_FIT_MAX_ROWS)");
@@ -3907,6 +3939,7 @@ int nrv_fit_get_rows(nrv_handle* h, int64_t first, int64_t count, float* flat1, 
   static const char* who = "nrv_fit_get_rows";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)");
   if (h->fit.depth) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)");
   if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3930,7 +3963,8 @@ int nrv_fit_set_depth(nrv_handle* h, int depth) {
   static const char* who = "nrv_fit_set_depth";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
-  if (depth != NRV_FIT_TAIL && depth != NRV_FIT_HEAD) return fit_refuse(h, who, "depth must be NRV_FIT_TAIL or NRV_FIT_HEAD");
+  if (depth != NRV_FIT_TAIL && depth != NRV_FIT_HEAD && depth != NRV_FIT_LSTM4)
+    return fit_refuse(h, who, "depth must be NRV_FIT_TAIL or NRV_FIT_HEAD, or NRV_FIT_LSTM4");
   nrv_handle::Fit& F = h->fit;
   if (F.rows != 0) return fit_refuse(h, who, "the training set is not empty (call nrv_fit_reset first)");
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3940,8 +3974,8 @@ int nrv_fit_set_depth(nrv_handle* h, int depth) {
   }
   if (depth == F.depth) return NRV_OK;
   for (int m = 0; m < 2; ++m) {
-    (void)hipFree(F.flat[m]); (void)hipFree(F.x4[m]); (void)hipFree(F.y[m]);
-    F.flat[m] = nullptr; F.x4[m] = nullptr; F.y[m] = nullptr;
+    (void)hipFree(F.flat[m]); (void)hipFree(F.x4[m]); (void)hipFree(F.xb[m]); (void)hipFree(F.y[m]);
+    F.flat[m] = nullptr; F.x4[m] = nullptr; F.xb[m] = nullptr; F.y[m] = nullptr;
     (void)hipFree(F.m[m].d_par); (void)hipFree(F.m[m].d_state);
     F.m[m].d_par = nullptr; F.m[m].d_state = nullptr;
   }
@@ -3954,6 +3988,7 @@ int nrv_fit_set_rows_head(nrv_handle* h, const float* x1, const float* x2, const
   static const char* who = "nrv_fit_set_rows_head";
   int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)");
   if (!h->fit.depth) return fit_refuse(h, who, "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_HEAD) on an empty set first)");
   if (n < 0 || (n > 0 && (!x1 || !x2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
   if (n > h->fit.max_head_rows) return fit_refuse(h, who, "more rows than the cap of the training set at head depth (NRV_FIT_MAX_HEAD_ROWS)");
@@ -3976,6 +4011,7 @@ int nrv_fit_get_rows_head(nrv_handle* h, int64_t first, int64_t count, float* x1
   static const char* who = "nrv_fit_get_rows_head";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)");
   if (!h->fit.depth) return fit_refuse(h, who, "the set is at tail depth (rows are main_out values: nrv_fit_get_rows)");
   if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3985,6 +4021,48 @@ int nrv_fit_get_rows_head(nrv_handle* h, int64_t first, int64_t count, float* x1
   uint8_t* const yy[2] = {y1, y2};
   for (int m = 0; m < 2; ++m) {
     if (xs[m]) HIPCHK(h, hipMemcpy(xs[m], h->fit.x4[m] + (size_t)first * K, (size_t)count * K * 4, hipMemcpyDeviceToHost));
+    if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
+  }
+  return NRV_OK;
+}
+
+int nrv_fit_set_rows_lstm4(nrv_handle* h, const float* xb1, const float* xb2, const uint8_t* y1, const uint8_t* y2, int64_t n) {
+  static const char* who = "nrv_fit_set_rows_lstm4";
+  int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_HEAD) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)");
+  if (h->fit.depth != NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_LSTM4) on an empty set first)");
+  if (n < 0 || (n > 0 && (!xb1 || !xb2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
+  if (n > h->fit.max_lstm4_rows) return fit_refuse(h, who, "more rows than the cap of the training set at lstm4 depth (NRV_FIT_MAX_LSTM4_ROWS)");
+  for (int64_t i = 0; i < n; ++i)
+    if (y1[i] > 5 || y2[i] > 4) return fit_refuse(h, who, "a label outside the model's classes (y1 0 .. 5, y2 0 .. 4)");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.rows = 0;
+  if (n == 0) return NRV_OK;
+  if ((rc = fit_reserve(h, n))) return rc;
+  const size_t K = fit_row_floats(h);
+  if ((rc = put(h, h->fit.xb[0], xb1, (size_t)n * K * 4, h->stream)) || (rc = put(h, h->fit.xb[1], xb2, (size_t)n * K * 4, h->stream)) ||
+      (rc = put(h, h->fit.y[0], y1, (size_t)n, h->stream)) || (rc = put(h, h->fit.y[1], y2, (size_t)n, h->stream)))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.rows = n;
+  return NRV_OK;
+}
+
+int nrv_fit_get_rows_lstm4(nrv_handle* h, int64_t first, int64_t count, float* xb1, float* xb2, uint8_t* y1, uint8_t* y2) {
+  static const char* who = "nrv_fit_get_rows_lstm4";
+  const int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_HEAD) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)");
+  if (h->fit.depth != NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at tail depth (rows are main_out values: nrv_fit_get_rows)");
+  if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (count == 0) return NRV_OK;
+  const size_t K = fit_row_floats(h);
+  float* const xs[2] = {xb1, xb2};
+  uint8_t* const yy[2] = {y1, y2};
+  for (int m = 0; m < 2; ++m) {
+    if (xs[m]) HIPCHK(h, hipMemcpy(xs[m], h->fit.xb[m] + (size_t)first * K, (size_t)count * K * 4, hipMemcpyDeviceToHost));
     if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
   }
   return NRV_OK;
@@ -4042,11 +4120,15 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
   else {
     const size_t src[4] = {d.fw, d.fb, d.ow, d.ob}, cnt[4] = {(size_t)16 * K, 16, (size_t)16 * C, (size_t)C};
     size_t at = 0;
+    if (h->fit.depth == NRV_FIT_LSTM4) {                    // tensors 44 .. 49, unfolded as the file has them
+      HIPCHK(h, hipMemcpyAsync(M.d_par, d.all + d.l4raw, (size_t)kL4N * 4, hipMemcpyDeviceToDevice, h->stream));
+      at = kL4N;
+    }
     if (h->fit.depth) {
       HIPCHK(h, hipStreamSynchronize(h->stream));
-      const int rc2 = fit_head_own(h, model, M.d_par);
+      const int rc2 = fit_head_own(h, model, M.d_par + at);
       if (rc2) return rc2;
-      at = kHfMlp;
+      at += kHfMlp;
     }
     for (int i = 0; i < 4; ++i) {
       HIPCHK(h, hipMemcpyAsync(M.d_par + at, d.all + src[i], cnt[i] * 4, hipMemcpyDeviceToDevice, h->stream));
@@ -4107,9 +4189,17 @@ static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
   int rc;
   if (h->fit.depth) {
     wg = (size_t)fit_head_wgs(b_max);
-    if ((rc = fit_scratch(h, (void**)&h->fit.d_flag, &h->fit.cap_flag, (size_t)((kHeadFitMaxP + 255) / 256) * 4))) return rc;
+    if ((rc = fit_scratch(h, (void**)&h->fit.d_flag, &h->fit.cap_flag, (size_t)(kL4N / 256 + (kHeadFitMaxP + 255) / 256) * 4))) return rc;
   }
-  if (grad && (rc = fit_scratch(h, (void**)&h->fit.d_partial, &h->fit.cap_partial, wg * fit_params_n(h, model) * 4))) return rc;
+  size_t pn = (size_t)fit_params_n(h, model);
+  if (h->fit.depth == NRV_FIT_LSTM4) {                       // one chunk's [X4 | dX4 | CS | GZ], the LSTM block's sums; partials of the head alone
+    const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
+    if ((rc = fit_scratch(h, (void**)&h->fit.d_l4, &h->fit.cap_l4, rows * h->T * (grad ? 896 : 128) * 4)) ||
+        (rc = fit_scratch(h, (void**)&h->fit.d_gl4, &h->fit.cap_gl4, (size_t)kL4N * 4)))
+      return rc;
+    pn -= kL4N;
+  }
+  if (grad && (rc = fit_scratch(h, (void**)&h->fit.d_partial, &h->fit.cap_partial, wg * pn * 4))) return rc;
   return fit_scratch(h, (void**)&h->fit.d_pstat, &h->fit.cap_pstat, wg * sizeof(TailStat));
 }
 
@@ -4125,7 +4215,46 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
   }
   nrv_handle::Fit::Model& M = h->fit.m[model];
   const int wg = fit_head_wgs(b), P = fit_params_n(h, model), blocks = (P + 255) / 256;
+  if (h->fit.depth == NRV_FIT_LSTM4) {
+    const int T = h->T;
+    const bool grad = mode != kTailEval;
+    const size_t rcap = (size_t)(b < kL4ChunkRows ? (b + 31) / 32 * 32 : kL4ChunkRows) * T;
+    float* const x4 = h->fit.d_l4;                          // the four arrays of fit_step_scratch, dX4 .. GZ only with grad
+    float* const dx4 = x4 + rcap * 128;
+    float* const cs = dx4 + rcap * 128;
+    float* const gz = cs + rcap * 128;
+    for (int c0 = 0; c0 < b; c0 += kL4ChunkRows) {
+      const int bc = b - c0 < kL4ChunkRows ? b - c0 : kL4ChunkRows, tiles = (bc + 31) / 32;
+      const L4Args la{h->fit.xb[model], d_rows + c0, M.d_par, x4, gz, cs, dx4, h->fit.d_gl4, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
+      if (h->act == 0) hipLaunchKernelGGL(l4_forward_kernel<0>, dim3(tiles, 2), dim3(256), 0, h->stream, la);
+      else hipLaunchKernelGGL(l4_forward_kernel<1>, dim3(tiles, 2), dim3(256), 0, h->stream, la);
+      HeadGradArgs a;
+      a.x = x4; a.y = h->fit.y[model]; a.rows = d_rows + c0; a.par = M.d_par + kL4N;
+      a.partial = h->fit.d_partial; a.pstat = h->fit.d_pstat; a.p_out = d_p ? d_p + (size_t)c0 * h->dm[model].C : nullptr;
+      a.T = T; a.C = h->dm[model].C; a.b = bc; a.lambda = M.o.lambda;
+      memcpy(a.cw, M.o.cw, sizeof a.cw);
+      a.dh1 = dx4; a.cont = c0 > 0 ? 1 : 0;
+      if (!grad) { hipLaunchKernelGGL((head_grad_kernel<false, true>), dim3(tiles), dim3(256), 0, h->stream, a); continue; }
+      hipLaunchKernelGGL((head_grad_kernel<true, true>), dim3(tiles), dim3(256), 0, h->stream, a);
+      if (h->act == 0) hipLaunchKernelGGL(l4_backward_kernel<0>, dim3(tiles, 2), dim3(256), 0, h->stream, la);
+      else hipLaunchKernelGGL(l4_backward_kernel<1>, dim3(tiles, 2), dim3(256), 0, h->stream, la);
+      hipLaunchKernelGGL(l4_wgrad_kernel, dim3(kL4WgM * kL4WgN, 2), dim3(256), 0, h->stream, la);
+    }
+    // the LSTM block is one "partial" of its own; the head's partials behind it; the flags of both launches in one array
+    const int PH = P - kL4N, bl4 = kL4N / 256;
+    const HeadAdamArgs u1{h->fit.d_gl4, h->fit.d_pstat, 1, b, kL4N, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
+                          (HeadState*)M.d_state, h->fit.d_flag, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+    const HeadAdamArgs u2{h->fit.d_partial, h->fit.d_pstat, wg, b, PH, mode, M.d_par + kL4N, M.d_par + P + kL4N, M.d_par + 2 * P + kL4N,
+                          M.d_par + 3 * P + kL4N, (HeadState*)M.d_state, h->fit.d_flag + bl4, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+    const HeadAdamArgs u{h->fit.d_partial, h->fit.d_pstat, wg, b, P, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
+                         (HeadState*)M.d_state, h->fit.d_flag, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+    hipLaunchKernelGGL(head_reduce_kernel, dim3(bl4), dim3(256), 0, h->stream, u1);
+    hipLaunchKernelGGL(head_reduce_kernel, dim3((PH + 255) / 256), dim3(256), 0, h->stream, u2);
+    hipLaunchKernelGGL(head_adam_kernel, dim3(blocks), dim3(256), 0, h->stream, u);
+    return;
+  }
   HeadGradArgs a;
+  a.dh1 = nullptr; a.cont = 0;
   a.x = h->fit.x4[model]; a.y = h->fit.y[model]; a.rows = d_rows; a.par = M.d_par;
   a.partial = h->fit.d_partial; a.pstat = h->fit.d_pstat; a.p_out = d_p;
   a.T = h->T; a.C = h->dm[model].C; a.b = b; a.lambda = M.o.lambda;

@@ -40,6 +40,8 @@ namespace nrv {
 //     rounded sqrt and division, lr_t from the host's f64 table).  Workgroup 0 moves the state; the step counter the update
 //     reads (t_cur) is a copy head_reduce_kernel made, so no workgroup can see the new one.
 // No atomics anywhere: two runs give the same bytes.
+// head_grad_kernel<GRAD, true> is the same kernel at depth NRV_FIT_LSTM4 (nrv_lstm4fit.h): x is the scratch X4 of one chunk of
+// the batch in batch order, the dh1 images are copied out for l4_backward_kernel, and a later chunk continues the partials.
 // ---------------------------------------------------------------------------------------
 constexpr int kHfW1 = 0, kHfB1 = 128 * 128, kHfW2 = kHfB1 + 128, kHfB2 = kHfW2 + 128 * 32, kHfWm = kHfB2 + 32,
               kHfBm = kHfWm + 32 * 6, kHfMlp = kHfBm + 6;                 // 20838: where the tail's vector starts
@@ -79,6 +81,12 @@ struct HeadGradArgs {
   int T, C, b;
   float lambda;
   float cw[6];
+  // depth NRV_FIT_LSTM4 (head_grad_kernel<., true>, nrv_lstm4fit.h): x holds the rows of one CHUNK of the batch in batch order
+  // (row i of the chunk is x[i], its label y[rows[i]]), dh1 [.][T][128] receives dh1 (l4_backward_kernel forms dX4 = dh1 W1^T
+  // from it: this kernel has no registers left for a fifth product), and with cont != 0 the
+  // workgroup continues the partial vector and the statistics that the chunks before left
+  float* dh1;
+  int cont;
 };
 
 // h1 and h2 of (32 rows, timestep t) into the wave's images; with MO main_out into flat[row * fsm + t * 6 + k] (0 behind
@@ -137,7 +145,7 @@ __device__ __forceinline__ void hf_forward(const float* __restrict__ par, const 
   }
 }
 
-template <bool GRAD>
+template <bool GRAD, bool L4 = false>
 __global__ void __launch_bounds__(256) head_grad_kernel(const HeadGradArgs a) {
   constexpr int KPMAX = 6 * kHeadMaxT;           // head_final_kernel's flat image
   constexpr int FSM = KPMAX + 4;
@@ -176,14 +184,17 @@ __global__ void __launch_bounds__(256) head_grad_kernel(const HeadGradArgs a) {
   for (int i = 0; i < 4; ++i) { gW1[i] = splat16(0.f); gW2[i] = splat16(0.f); }
   TailStat wst{0.0, 0.0, 0, 0};                  // thread 0's
   bool first = true;
+  bool cont = false;
+  if constexpr (L4) cont = a.cont != 0;
 
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, first = false) {
     const int n_here = a.b - tile * 32 < 32 ? a.b - tile * 32 : 32;
     __syncthreads();                             // the tile before is done with every image
     if (tid < 32) {
-      const long long row = tid < n_here ? (long long)a.rows[tile * 32 + tid] : -1;
-      rix[tid] = row;
+      long long row = tid < n_here ? (long long)a.rows[tile * 32 + tid] : -1;
       ys[tid] = row >= 0 ? (int)a.y[row] : 0;
+      if constexpr (L4) row = tid < n_here ? (long long)tile * 32 + tid : -1;
+      rix[tid] = row;
     }
     for (int i = tid; i < 32 * (KP - K); i += 256) flatv[(i / (KP - K)) * FSM + K + i % (KP - K)] = 0.f;
     if (tid < 16 * C) { wo[(tid / C) * 8 + tid % C] = outw[tid]; cen[(tid / 16) * 16 + tid % 16] = tpar[oCe + tid]; }
@@ -287,7 +298,7 @@ __global__ void __launch_bounds__(256) head_grad_kernel(const HeadGradArgs a) {
           for (int r = 0; r < n_here; ++r)
             if (ys[r] == cc) s = __builtin_fmaf(-two_l, featv[r * 17 + f] - cen[cc * 16 + f], s);
         }
-        out[kHfMlp + idx] = first ? s : out[kHfMlp + idx] + s;
+        out[kHfMlp + idx] = (first && !cont) ? s : out[kHfMlp + idx] + s;
       }
       __syncthreads();
       // dF = dz Wf^T where mo > 0, in place of the flat image
@@ -390,6 +401,13 @@ __global__ void __launch_bounds__(256) head_grad_kernel(const HeadGradArgs a) {
                 gW1[nt] = mfma32(av, img[((nt * 32 + l31) >> 2) * kHfPlane + r * 4 + (l31 & 3)], gW1[nt]);
             }
         }
+        if constexpr (L4) {                                // the four dh1 images to the chunk's scratch, 16 bytes a move
+          for (int i = tid; i < nt_here * 1024; i += 256) {
+            const int tt = i >> 10, kq = (i >> 5) & 31, r = i & 31;
+            if (r < n_here)
+              *(f32x4*)(a.dh1 + ((size_t)(tile * 32 + r) * T + tg + tt) * 128 + kq * 4) = *(const f32x4*)(wim + tt * WIM + kq * kHfPlane + r * 4);
+          }
+        }
         if (tid < 128) {
           for (int tt = 0; tt < nt_here; ++tt) {
             const float* hp = wim + tt * WIM + (tid >> 2) * kHfPlane + (tid & 3);
@@ -403,14 +421,21 @@ __global__ void __launch_bounds__(256) head_grad_kernel(const HeadGradArgs a) {
       }
     }
   }
-  if (tid == 0) a.pstat[blockIdx.x] = wst;
+  if (tid == 0) {
+    if (cont) {
+      const TailStat o = a.pstat[blockIdx.x];
+      wst.ce = o.ce + wst.ce; wst.center = o.center + wst.center; wst.correct += o.correct; wst.rows += o.rows;
+    }
+    a.pstat[blockIdx.x] = wst;
+  }
   if constexpr (GRAD) {
+    auto keep = [&](float* o, float v) { *o = cont ? *o + v : v; };
     // gW1: wave w owns rows 32 w .. of it; everything else is summed over the waves in ascending order
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-      for (int reg = 0; reg < 16; ++reg) out[kHfW1 + (wave * 32 + acc_row(reg, lane)) * 128 + nt * 32 + l31] = gW1[nt][reg];
-    if (tid < 128) out[kHfB1 + tid] = gb1;
+      for (int reg = 0; reg < 16; ++reg) keep(out + kHfW1 + (wave * 32 + acc_row(reg, lane)) * 128 + nt * 32 + l31, gW1[nt][reg]);
+    if (tid < 128) keep(out + kHfB1 + tid, gb1);
     __syncthreads();
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
@@ -424,12 +449,12 @@ __global__ void __launch_bounds__(256) head_grad_kernel(const HeadGradArgs a) {
     for (int i = tid; i < 128 * 32; i += 256) {
       float s = 0.f;
       for (int w = 0; w < 4; ++w) s += wim[w * WIM + i];
-      out[kHfW2 + i] = s;
+      keep(out + kHfW2 + i, s);
     }
     if (tid < 232 && (tid < 198 || tid >= 200)) {
       float s = 0.f;
       for (int w = 0; w < 4; ++w) s += wim[w * WIM + IM1 + tid];
-      out[tid < 192 ? kHfWm + tid : tid < 198 ? kHfBm + tid - 192 : kHfB2 + tid - 200] = s;
+      keep(out + (tid < 192 ? kHfWm + tid : tid < 198 ? kHfBm + tid - 192 : kHfB2 + tid - 200), s);
     }
   }
 }

@@ -48,8 +48,9 @@ SYMBOLS = [
     "nrv_fit_reset", "nrv_fit_count", "nrv_fit_add_reads_raw", "nrv_fit_set_rows", "nrv_fit_get_rows", "nrv_fit_begin",
     "nrv_fit_grad", "nrv_fit_epoch", "nrv_fit_eval", "nrv_fit_params",
     "nrv_fit_set_depth", "nrv_fit_depth", "nrv_fit_set_rows_head", "nrv_fit_get_rows_head",
+    "nrv_fit_set_rows_lstm4", "nrv_fit_get_rows_lstm4",
 ]
-FIT_TAIL, FIT_HEAD = 0, 1           # NRV_FIT_TAIL, NRV_FIT_HEAD
+FIT_TAIL, FIT_HEAD, FIT_LSTM4 = 0, 1, 4    # NRV_FIT_TAIL, NRV_FIT_HEAD, NRV_FIT_LSTM4 (the Bi-LSTM the fit starts at)
 FIT_MAX_BATCH = 65536               # NRV_FIT_MAX_BATCH
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 PROFILE_COLS = 48                   # NRV_PROFILE_COLS
@@ -179,6 +180,8 @@ _FIT_T = {                                                                      
     "nrv_fit_depth": [C.c_void_p],
     "nrv_fit_set_rows_head": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
     "nrv_fit_get_rows_head": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
+    "nrv_fit_set_rows_lstm4": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
+    "nrv_fit_get_rows_lstm4": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
 }
 
 
@@ -867,12 +870,13 @@ class Reviser:
     def fit_n_params(self, model) -> int:
         """The length of a model's parameter vector at the current depth."""
         c = self._n_class(model)
-        return (20838 if self.fit_depth() == FIT_HEAD else 0) + 96 * self.T + 16 + 16 * c + c + 16 * c
+        front = {FIT_TAIL: 0, FIT_HEAD: 20838, FIT_LSTM4: 164352 + 20838}[self.fit_depth()]
+        return front + 96 * self.T + 16 + 16 * c + c + 16 * c
 
     # ---- the second depth (nanoreviser_amd/headfit.py is the definition): the set holds lstm4 outputs [T][128] per window
     def fit_set_depth(self, depth):
-        """FIT_TAIL / FIT_HEAD (or "tail" / "head"), on an empty set only; forgets any fit_begin."""
-        depth = {"tail": FIT_TAIL, "head": FIT_HEAD}.get(depth, depth)
+        """FIT_TAIL / FIT_HEAD / FIT_LSTM4 (or "tail" / "head" / "lstm4"), on an empty set only; forgets any fit_begin."""
+        depth = {"tail": FIT_TAIL, "head": FIT_HEAD, "lstm4": FIT_LSTM4}.get(depth, depth)
         self._check(self._lib.nrv_fit_set_depth(self._h, int(depth)))
 
     def fit_depth(self) -> int:
@@ -896,6 +900,24 @@ class Reviser:
         out = (np.empty(sh, np.float32), np.empty(sh, np.float32), np.empty(count, np.uint8), np.empty(count, np.uint8))
         self._check(self._lib.nrv_fit_get_rows_head(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _U8P),
                                                     _ptr(out[3], _U8P)))
+        return out
+
+    # ---- the third depth (nanoreviser_amd/lstm4fit.py is the definition): the set holds BatchNorm'd lstm3 outputs [T][256]
+    def fit_set_rows_lstm4(self, xb1, xb2, y1, y2):
+        a1, a2 = _as_f32(xb1, (self.T, 256)), _as_f32(xb2, (self.T, 256))
+        a, b = (np.ascontiguousarray(v, dtype=np.uint8).reshape(-1) for v in (y1, y2))
+        n = a1.shape[0]
+        if a2.shape[0] != n or a.size != n or b.size != n:
+            raise ValueError("xb1 / xb2 / y1 / y2 must have one entry per row")
+        self._check(self._lib.nrv_fit_set_rows_lstm4(self._h, _ptr(a1, _FP), _ptr(a2, _FP), _ptr(a, _U8P), _ptr(b, _U8P), n))
+
+    def fit_get_rows_lstm4(self, first=0, count=None):
+        """-> (xb1, xb2, y1, y2) of rows [first, first + count), xb [count][T][256]."""
+        count = self.fit_count() - first if count is None else count
+        sh = (count, self.T, 256)
+        out = (np.empty(sh, np.float32), np.empty(sh, np.float32), np.empty(count, np.uint8), np.empty(count, np.uint8))
+        self._check(self._lib.nrv_fit_get_rows_lstm4(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _U8P),
+                                                     _ptr(out[3], _U8P)))
         return out
 
     @staticmethod

@@ -93,10 +93,16 @@ def forward(X, theta, T: int, C: int, dtype=np.float64):
 
 def batch_terms(X, y, theta, T: int, C: int, opts: FitOpts, dtype=np.float64):
     """One batch -> (g [P]: the gradient of L, FitStats of the batch with steps = nonfinite = 0)."""
+    return batch_terms_dx(X, y, theta, T, C, opts, dtype)[:2]
+
+
+def batch_terms_dx(X, y, theta, T: int, C: int, opts: FitOpts, dtype=np.float64):
+    """batch_terms and the data gradient behind it -> (g, FitStats, dX [b][T][128] = dh1 W1^T: the derivative of the batch's
+    SUM of row losses with respect to X - not divided by b, as dh1 is not).  lstm4fit.py goes on from it."""
     dt = np.dtype(dtype)
     theta = np.asarray(theta)
     parts = [a.astype(dt) for a in unpack(theta, T, C)]
-    W2, Wm, Wf, Wo, Ce = parts[2], parts[4], parts[6], parts[8], parts[10]
+    W1, W2, Wm, Wf, Wo, Ce = parts[0], parts[2], parts[4], parts[6], parts[8], parts[10]
     X, h1, h2, mo = mlp(X, theta, T, C, dt)
     y = np.asarray(y).astype(np.int64).reshape(-1)
     b = X.shape[0]
@@ -129,7 +135,7 @@ def batch_terms(X, y, theta, T: int, C: int, opts: FitOpts, dtype=np.float64):
              F.T @ dz, dz.sum(axis=0), f.T @ dl, dl.sum(axis=0), gCe, dt) / dt.type(b)
     st = FitStats(rows=b, correct=int((p.argmax(axis=1) == y).sum()), ce_sum=float(ce.astype(np.float64).sum()),
                   center_sum=float(cn.astype(np.float64).sum()))
-    return g, st
+    return g, st, dh1 @ W1.T
 
 
 def epoch(X, y, state: FitState, order, T: int, C: int, opts: FitOpts, dtype=np.float64) -> FitStats:

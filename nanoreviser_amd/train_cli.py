@@ -11,6 +11,10 @@ per labelled window; an epoch touches 6T floats per window.  Device only: the pr
 --fit_depth head moves the frozen boundary back to the output of lstm4: the three per-timestep dense layers (tensors 50 .. 55)
 are fitted too, a window is its 128 T lstm4 values (nanoreviser_amd/headfit.py is the definition).  The default, tail, is
 everything above, byte for byte.
+
+--fit_depth lstm4 moves it back once more, to the input of lstm4: the 256 -> 64 Bi-LSTM (tensors 44 .. 49, 164352 weights) is
+fitted with the head, a window is its 256 T BatchNorm'd lstm3 values (nanoreviser_amd/lstm4fit.py is the definition).  lstm4
+always starts from the loaded or continued model's own weights; --fit_init acts on the layers behind it as at head depth.
 """
 from __future__ import annotations
 
@@ -23,7 +27,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import cli, headfit, tailfit
+from . import cli, headfit, lstm4fit, tailfit
 from .weights import load_model, load_species
 
 HISTORY_HEAD = "epoch\tloss\tce\tcenter\tacc\tval_loss\tval_acc\tnonfinite"
@@ -51,7 +55,8 @@ def get_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("--fit_init", default="transfer", help="transfer (the loaded tail) or fresh (seeded Glorot-uniform, zero biases)")
     p.add_argument("--fit_depth", default="tail",
                    help="tail: tensors 56 .. 59 behind Flatten(main_out); head: tensors 50 .. 59 behind lstm4 (then --fit_init "
-                        "fresh keeps the shipped 50 .. 55 and fresh_head draws all five layers)")
+                        "fresh keeps the shipped 50 .. 55 and fresh_head draws all five layers); lstm4: tensors 44 .. 59, the "
+                        "last Bi-LSTM too (it always starts from the model's own weights)")
     p.add_argument("--model_dir", default=None, help="root of model/<species>/ (default: next to the package)")
     p.add_argument("-g", "--basecall_group", dest="basecall_group", default="Basecall_1D_000")
     p.add_argument("-s", "--basecall_subgroup", dest="basecall_subgroup", default="BaseCalled_template")
@@ -79,12 +84,12 @@ def check_args(a):
         return "--labels_from: not a directory"
     if a.model_type not in ("both", "model1", "model2"):
         return "--model_type must be both, model1 or model2"
-    if a.fit_depth not in ("tail", "head"):
-        return f"--fit_depth must be tail or head, not {a.fit_depth!r}"
+    if a.fit_depth not in ("tail", "head", "lstm4"):
+        return f"--fit_depth must be tail or head, or lstm4, not {a.fit_depth!r}"
     if a.fit_depth == "tail" and a.fit_init == "fresh_head":
         return "--fit_init fresh_head draws the three dense layers behind lstm4, which --fit_depth tail does not fit"
     if a.fit_init not in (("transfer", "fresh") if a.fit_depth == "tail" else ("transfer", "fresh", "fresh_head")):
-        return "--fit_init must be transfer or fresh" + (f" or fresh_head, not {a.fit_init!r}" if a.fit_depth == "head" else "")
+        return "--fit_init must be transfer or fresh" + (f" or fresh_head, not {a.fit_init!r}" if a.fit_depth != "tail" else "")
     if a.window_size is not None and not 1 <= a.window_size <= 32:
         return "-w must be in 1 .. 32"
     if a.epochs < 1:
@@ -128,8 +133,18 @@ def _start_head(a, k, m, T):
     return headfit.params_from_model(m), "transfer"
 
 
+def _start_lstm4(a, k, m, T):
+    """_start at --fit_depth lstm4: _start_head's vector behind tensors 44 .. 49 of the loaded or continued model."""
+    th, how = _start_head(a, k, m, T)
+    path = (a.model1_train_dir, a.model2_train_dir)[k]
+    front = lstm4fit.params_from_model(load_model(path) if path else m.with_window(T))
+    return lstm4fit.with_head(front, th), how
+
+
 def _start(a, k, m, T):
     """The starting parameter vector of model k (0 / 1) and where it came from."""
+    if a.fit_depth == "lstm4":
+        return _start_lstm4(a, k, m, T)
     if a.fit_depth == "head":
         return _start_head(a, k, m, T)
     path = (a.model1_train_dir, a.model2_train_dir)[k]
@@ -147,6 +162,9 @@ def _start(a, k, m, T):
     if a.fit_init == "fresh" or T != m.T:
         return tailfit.fresh_params(T, m.n_class, a.seed + k), "fresh"
     return tailfit.params_from_model(m), "transfer"
+
+
+_DEPTHS = {"tail": tailfit, "head": headfit, "lstm4": lstm4fit}
 
 
 def _default_factory(a, m1, m2):
@@ -203,7 +221,7 @@ def fit_model(a, rv, k, theta0, n_train, n_val, log=print):
         lines.append(f"{ep + 1}\t{loss:.6f}\t{ce:.6f}\t{cn:.6f}\t{st.acc():.6f}\t{vl}\t{va}\t{st.nonfinite}")
         log(f"[s:::] model{k + 1} epoch {ep + 1}/{a.epochs}: loss {loss:.4f} acc {st.acc():.4f} val_loss {vl} val_acc {va}")
     theta, _ = rv.fit_params(k)
-    assert theta.size == (headfit if a.fit_depth == "head" else tailfit).n_params(rv.T, C)
+    assert theta.size == _DEPTHS[a.fit_depth].n_params(rv.T, C)
     return theta, lines
 
 
@@ -224,8 +242,8 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
     rv = (reviser_factory or _default_factory)(a, m1.with_window(T), m2.with_window(T))
     try:
         rv.fit_reset()
-        if a.fit_depth == "head":
-            rv.fit_set_depth("head")
+        if a.fit_depth != "tail":
+            rv.fit_set_depth(a.fit_depth)
         used, skipped = add_reads(a, rv)
         n = rv.fit_count()
         if n == 0:
@@ -242,9 +260,10 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
             theta, lines = fit_model(a, rv, k, starts[k][0], n_train, n_val)
             st = stem(a.output_model, a.species, k + 1)
             m = (m1, m2)[k]
-            head = a.fit_depth == "head"
-            tailfit.write_f32(headfit.fitted_model(m, theta, T) if head else tailfit.fitted_model(m, theta, T), st)
-            (headfit if head else tailfit).unpack(theta, T, m.n_class)[-1].astype("<f4").tofile(st + "_centers.f32")
+            deep = a.fit_depth != "tail"
+            fit = _DEPTHS[a.fit_depth]
+            tailfit.write_f32(fit.fitted_model(m, theta, T), st)
+            fit.unpack(theta, T, m.n_class)[-1].astype("<f4").tofile(st + "_centers.f32")
             with open(st + "_history.tsv", "w") as fp:
                 fp.write(HISTORY_HEAD + "\n" + "\n".join(lines) + "\n")
             with open(st + "_summary.json", "w") as fp:
@@ -252,7 +271,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
                                        "validation_split": a.validation_split, "seed": a.seed, "lr": a.lr,
                                        "center_weight": a.center_weight, "class_weight": list(a.cw1 if k == 0 else a.cw2),
                                        "init": starts[k][1], "labels_from": os.path.abspath(a.labels_from),
-                                       **({"fit_depth": "head"} if head else {})},
+                                       **({"fit_depth": a.fit_depth} if deep else {})},
                            "rows": n, "train_rows": n_train, "val_rows": n_val, "reads": used,
                            "skipped_reads": [list(s) for s in skipped], "seconds": round(time.time() - t0, 3)}, fp, indent=1)
                 fp.write("\n")

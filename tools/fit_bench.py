@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Time nrv_fit_epoch at both fit depths (tail: tensors 56 .. 59; head: tensors 50 .. 59) on the device.  A plain script: it
-takes no part in bench.py and sets no bar.
+"""Time nrv_fit_epoch at the three fit depths (tail: tensors 56 .. 59; head: tensors 50 .. 59; lstm4: tensors 44 .. 59) on the
+device.  A plain script: it takes no part in bench.py and sets no bar.
 
-A set of seeded rows goes in through the unit doors (nrv_fit_set_rows / nrv_fit_set_rows_head), so the frozen backbone never
+A set of seeded rows goes in through the unit doors (nrv_fit_set_rows / _head / _lstm4), so the frozen backbone never
 runs: what is timed is one whole nrv_fit_epoch call - the upload of the row order, every batch's launches enqueued back to back
 and the one synchronise at the end - by a host clock around the call, which returns only after that synchronise.  Per depth:
 untimed epochs first (first launches load code objects and size the scratch buffers), then --repeats timed epochs; the median
@@ -26,7 +26,14 @@ def flop_per_row(depth, T, C):
     kernel's recomputation of the two wide forward products is NOT counted (it is the implementation's choice)."""
     tail = 2 * (96 * T + 16 * C) * 3
     mlp = 2 * T * (128 * 128 + 128 * 32 + 32 * 6)
-    return tail if depth == "tail" else tail + 3 * mlp - 2 * T * 128 * 128      # (no data gradient into X)
+    if depth == "tail":
+        return tail
+    if depth == "head":
+        return tail + 3 * mlp - 2 * T * 128 * 128          # (no data gradient into X)
+    # lstm4 depth: the head with its data gradient dX4 = dh1 W1^T; per direction the input and recurrent products forward, the
+    # recurrent data gradient dz U^T (none into Xb: lstm3 is frozen) and the two weight-gradient products
+    lstm = 2 * T * 2 * (256 * 256 + 64 * 256)
+    return tail + 3 * mlp + 2 * lstm + 2 * T * 2 * 64 * 256
 
 
 def main(argv=None):
@@ -40,7 +47,7 @@ def main(argv=None):
     ap.add_argument("--species", default="ecoli")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args(argv)
-    from nanoreviser_amd import headfit, tailfit
+    from nanoreviser_amd import headfit, lstm4fit, tailfit
     from nanoreviser_amd.engine import Reviser
     from nanoreviser_amd.weights import load_species
     T, k, n = a.window_size, a.model, a.rows
@@ -57,13 +64,17 @@ def main(argv=None):
     except Exception:
         pass
     try:
-        for depth in ("tail", "head"):
+        for depth in ("tail", "head", "lstm4"):
             rv.fit_reset()
             rv.fit_set_depth(depth)
             if depth == "tail":
                 F = np.maximum(rng.normal(0, 1, (n, 6 * T)), 0).astype(np.float32)
                 rv.fit_set_rows(F, F, y1, y2)
                 th = tailfit.fresh_params(T, C, a.seed)
+            elif depth == "lstm4":                         # the shipped lstm4 in front of a fresh head (lstm4 has no fresh start)
+                X = rng.normal(0, 1, (n, T, 256)).astype(np.float32)
+                rv.fit_set_rows_lstm4(X, X, y1, y2)
+                th = lstm4fit.with_head(lstm4fit.params_from_model((m1, m2)[k].with_window(T)), headfit.fresh_params(T, C, a.seed))
             else:
                 X = np.clip(rng.normal(0, 0.5, (n, T, 128)), -0.999, 0.999).astype(np.float32)
                 rv.fit_set_rows_head(X, X, y1, y2)
