@@ -827,6 +827,39 @@ int nrv_fit_get_rows_head(nrv_handle* h, int64_t first, int64_t count, float* x1
 int nrv_fit_set_rows_lstm4(nrv_handle* h, const float* xb1, const float* xb2, const uint8_t* y1, const uint8_t* y2, int64_t n);
 int nrv_fit_get_rows_lstm4(nrv_handle* h, int64_t first, int64_t count, float* xb1, float* xb2, uint8_t* y1, uint8_t* y2);
 
+/* ---- Fitting the 192 -> 128 Bi-LSTM with everything behind it: a fourth DEPTH of nrv_fit_* (opt-in) ----
+ * At depth NRV_FIT_LSTM3 the frozen boundary moves back to the input of lstm3, the Bi-LSTM where the read branch and the signal
+ * branch meet: fitted are its tensors 34 .. 39 (328704 weights) and everything the lstm4 depth fits (tensors 44 .. 59 and the
+ * centres).  nanoreviser_amd/lstm3fit.py is the definition.  Frozen: tensors 0 .. 33 (lstm1, lstm2, the signal branch) AND the
+ * BatchNorm between lstm3 and lstm4 (tensors 40 .. 43), which lies inside the fitted section and is applied in its inference
+ * form, Xb4 = h3 * sc + sh (one f32 multiply, one f32 add, sc / sh from the moving statistics as the handle holds them).  A
+ * STATED DEVIATION: Keras in training phase would normalise with the batch's statistics and fit gamma and beta; this depth
+ * fine-tunes with the moving statistics fixed.  The constant is 8: 2, 3, 5, 6, 7, 9 and -1 stay refused.
+ *   nrv_fit_set_depth  takes NRV_FIT_LSTM3 under the rules above.
+ * THE SET at this depth.  Per model x f32 [rows][T][192] - the BatchNorm'd f32 lstm2 output of the window (128 values), then
+ * signal_x_out (64 values), in the order of the model's concatenate, as the f32 lstm3 launch reads them - and the same y
+ * arrays.  A row is 768 T bytes; the depth's own cap is NRV_FIT_MAX_LSTM3_ROWS (environment, read by nrv_create; default 2^20,
+ * 8.9 GB per model at T = 11); a call that would pass it is refused whole, by that name.
+ *   nrv_fit_add_reads_raw  unchanged signature and label rule; the NRV_PREC_F32 kernels whatever the mode.  INSIDE each launch
+ *     group - behind the lstm2 launch and the signal branch, in front of the lstm4 launch, whose output overwrites lstm2's - a
+ *     gather moves the T x 192 values of every labelled window, 16 bytes at a time with plain stores, through the two views the
+ *     f32 lstm3 launch reads to the window's slot.  The group then runs to its end as at every depth.
+ *   nrv_fit_set_rows_lstm3 / nrv_fit_get_rows_lstm3  the unit doors, x [n][T][192].  Each depth's doors are refused at the
+ *     other depths under their own names; the handle stays usable.
+ * THE FIT.  One vector of NRV_FIT_PARAMS_LSTM3(T, C) = 328704 + NRV_FIT_PARAMS_LSTM4(T, C) floats:
+ *   [W3f [192][512] | U3f [128][512] | b3f [512] | W3b | U3b | b3b | the lstm4 depth's vector]
+ * row-major [in][out], gate columns i, f, c, o, forward direction first.  params NULL: the handle's own tensors 34 .. 39 and
+ * 44 .. 59 as the file has them and zero centres.  Forward: lstm3 as lstm4 above with H = 128, H3_t = [h_fw,t | h_bw,t],
+ * Xb4 = H3 sc + sh, then the lstm4 depth's forward and loss.  Backward: the lstm4 depth's, then dX3 = (sum over both
+ * directions, forward first, of dz4 W4^T) * sc, then back through time in lstm3 with dh = dX3_t[direction's half] +
+ * dz_{s+1} U3^T; gW3 = sum x_t^T dz, gU3 = sum h_{s-1}^T dz (raw h; exactly zero at T = 1), gb3 = sum dz
+ * (csrc/nrv_lstm3fit.h).  Chunks, reduction, finite check and Adam step as at lstm4 depth over the longer vector; no atomics,
+ * the same calls give the same bytes.  nrv_fit_eval runs the forward launches alone. */
+#define NRV_FIT_LSTM3 8
+#define NRV_FIT_PARAMS_LSTM3(T, C) (328704 + NRV_FIT_PARAMS_LSTM4(T, C))
+int nrv_fit_set_rows_lstm3(nrv_handle* h, const float* x1, const float* x2, const uint8_t* y1, const uint8_t* y2, int64_t n);
+int nrv_fit_get_rows_lstm3(nrv_handle* h, int64_t first, int64_t count, float* x1, float* x2, uint8_t* y1, uint8_t* y2);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

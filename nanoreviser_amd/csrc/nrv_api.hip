@@ -5,6 +5,7 @@
 #include "nrv_tailfit.h"      // the training set and the two kernels of a fitting step (nrv_fit_*, opt-in)
 #include "nrv_headfit.h"      // ... at depth NRV_FIT_HEAD: lstm4 outputs as the set, the gradient through the three dense layers
 #include "nrv_lstm4fit.h"     // ... at depth NRV_FIT_LSTM4: BatchNorm'd lstm3 outputs as the set, the last Bi-LSTM's forward and backward
+#include "nrv_lstm3fit.h"     // ... at depth NRV_FIT_LSTM3: lstm3's inputs as the set, the 192->128 Bi-LSTM's forward and backward, dX out of lstm4
 #include "nrv_block.h"
 
 #include <algorithm>
@@ -460,6 +461,7 @@ struct DevModel {
   size_t l1w16, l1b16;        // lstm1 packed for the 16x16x4 kernel
   size_t l_ws[4];             // lstm2..4 weights split into three bf16 terms (index 1..3)
   size_t d1p, d1b, d2p, d2b, mop, mob, fw, fb, ow, ob;
+  size_t l3raw = 0;           // tensors 34 .. 39 as the file has them (... at depth NRV_FIT_LSTM3)
   size_t l4raw = 0;           // tensors 44 .. 49 as the file has them (nrv_fit_begin at depth NRV_FIT_LSTM4 starts from them)
   size_t h_ws, h_wb;          // head_mlp_split_kernel: split weights / biases
   // f16x2 mode (nrv_lstm_f16x2.h): lstm2..4 weights as two f16 terms, scaled biases, output scale /
@@ -689,6 +691,15 @@ struct nrv_handle {
     int64_t max_lstm4_rows = (int64_t)1 << 20;                // NRV_FIT_MAX_LSTM4_ROWS, read by nrv_create
     float* d_l4 = nullptr; size_t cap_l4 = 0;                 // [X4 | dX4 | CS | GZ] of kL4ChunkRows rows
     float* d_gl4 = nullptr; size_t cap_gl4 = 0;               // [kL4N]
+    // depth NRV_FIT_LSTM3: the set is xin [cap][T][192] and y; one chunk's [H3 | XB | dX3 | CS | GZ] (nrv_lstm3fit.h) in front of
+    // the lstm4 depth's scratch, the lstm3 block's gradient sums, the identity row list of the lstm4 launches; while
+    // nrv_fit_add_reads_raw runs, l3_slot is the slot list of the group run_group is at (the gather runs inside the group)
+    float* xin[2] = {nullptr, nullptr};
+    int64_t max_lstm3_rows = (int64_t)1 << 20;                // NRV_FIT_MAX_LSTM3_ROWS, read by nrv_create
+    float* d_l3 = nullptr; size_t cap_l3 = 0;
+    float* d_gl3 = nullptr; size_t cap_gl3 = 0;               // [kL3N]
+    unsigned* d_ident = nullptr;                              // [kL4ChunkRows] 0, 1, 2, ...
+    const int* l3_slot = nullptr;
     int* d_flag = nullptr; size_t cap_flag = 0;               // head_reduce_kernel's per-workgroup flags
     float* d_partial = nullptr; size_t cap_partial = 0;       // [workgroups][P]
     TailStat* d_pstat = nullptr; size_t cap_pstat = 0;        // [workgroups]
@@ -785,6 +796,11 @@ NRV_HOST_COLD static int upload_model(nrv_handle* h, int mi, const Blob& b, int 
     memcpy(cv + 240, b.t(7), 8 * 4);
     bn_fold(b.t(8), b.t(9), b.t(10), b.t(11), 8, cv + 248, cv + 256);
     d.conv = put(cv, 264);
+  }
+  {
+    static const size_t n3[6] = {192 * 512, 128 * 512, 512, 192 * 512, 128 * 512, 512};
+    d.l3raw = put(b.t(34), n3[0]);
+    for (int i = 1; i < 6; ++i) (void)put(b.t(34 + i), n3[i]);
   }
   {
     static const size_t n4[6] = {256 * 256, 64 * 256, 256, 256 * 256, 64 * 256, 256};
@@ -1417,6 +1433,17 @@ static int run_group(nrv_handle* h, const float* d_sig, const float* d_feat, int
       launch_lstm_f32<32, 16, 128, 1, 1>(h, a, tiles);
     }
     if ((rc = mark(4))) return rc;
+    if (h->fit.l3_slot) {                        // nrv_fit_add_reads_raw at depth NRV_FIT_LSTM3: lstm3's two inputs of the group's
+      L3GatherArgs g;                            // labelled windows, before the next launch writes X4 over X2
+      for (int m = 0; m < 2; ++m) {
+        g.in0[m] = win_view(h->X2[m], 32);
+        g.in1[m] = read_mode ? ActView{h->S[m], 16, 1, 1, 0} : win_view(h->S[m], 16);
+        g.x[m] = h->fit.xin[m];
+      }
+      g.slot = h->fit.l3_slot; g.n = n; g.T = T; g.cap = h->fit.cap;
+      const long long total = (long long)n * T * 48;
+      hipLaunchKernelGGL(l3_gather_kernel, dim3((unsigned)((total + 255) / 256), 2), dim3(256), 0, h->stream, g);
+    }
     for (int m = 0; m < 2; ++m) {
       const DevModel& d = h->dm[m];
       a.m[m] = LstmModelParams{d.all + d.l_w[3], d.all + d.l_b[3], d.all + d.l_s[3], d.all + d.l_h[3],
@@ -1558,6 +1585,7 @@ int nrv_create(const nrv_weights* m1, const nrv_weights* m2, int T, int device, 
   if (const char* e6 = getenv("NRV_LABELS_BUDGET"); e6 && *e6) { const long long v = atoll(e6); if (v > 0) h->lab_budget = (size_t)v; }
   if (const char* e7 = getenv("NRV_FIT_MAX_ROWS"); e7 && *e7) { const long long v = atoll(e7); if (v > 0) h->fit.max_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e9 = getenv("NRV_FIT_MAX_LSTM4_ROWS"); e9 && *e9) { const long long v = atoll(e9); if (v > 0) h->fit.max_lstm4_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
+  if (const char* e10 = getenv("NRV_FIT_MAX_LSTM3_ROWS"); e10 && *e10) { const long long v = atoll(e10); if (v > 0) h->fit.max_lstm3_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e8 = getenv("NRV_FIT_MAX_HEAD_ROWS"); e8 && *e8) { const long long v = atoll(e8); if (v > 0) h->fit.max_head_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e5 = getenv("NRV_POISON"); e5 && *e5) { h->poison_on = true; h->poison = (unsigned)strtoul(e5, nullptr, 16); }
   ok = ok && hipMalloc((void**)&h->d_sat, 4 * sizeof(unsigned)) == hipSuccess &&
@@ -1592,11 +1620,12 @@ void nrv_destroy(nrv_handle* h) {
   (void)hipFree(h->d_lab);
   for (char* p : h->lab_retired) (void)hipFree(p);
   for (int m = 0; m < 2; ++m) {
-    (void)hipFree(h->fit.flat[m]); (void)hipFree(h->fit.y[m]); (void)hipFree(h->fit.x4[m]); (void)hipFree(h->fit.xb[m]);
+    (void)hipFree(h->fit.flat[m]); (void)hipFree(h->fit.y[m]); (void)hipFree(h->fit.x4[m]); (void)hipFree(h->fit.xb[m]); (void)hipFree(h->fit.xin[m]);
     (void)hipFree(h->fit.m[m].d_par); (void)hipFree(h->fit.m[m].d_state); (void)hipFree(h->fit.m[m].d_lr);
   }
   (void)hipFree(h->fit.d_partial); (void)hipFree(h->fit.d_pstat); (void)hipFree(h->fit.d_order); (void)hipFree(h->fit.d_p); (void)hipFree(h->fit.d_flag);
   (void)hipFree(h->fit.d_l4); (void)hipFree(h->fit.d_gl4);
+  (void)hipFree(h->fit.d_l3); (void)hipFree(h->fit.d_gl3); (void)hipFree(h->fit.d_ident);
   for (int st = 0; st < nrv_handle::kIn; ++st) if (h->ev_in[st]) (void)hipEventDestroy(h->ev_in[st]);
   for (int st = 0; st < 2; ++st) {
     if (h->ev_done[st]) (void)hipEventDestroy(h->ev_done[st]);
@@ -3723,15 +3752,17 @@ static int fit_scratch(nrv_handle* h, void** p, size_t* cap, size_t bytes) {
 }
 // floats of one row of the set at the handle's depth, and the parameters of a model's vector
 static size_t fit_row_floats(const nrv_handle* h) {
+  if (h->fit.depth == NRV_FIT_LSTM3) return (size_t)h->T * 192;
   return h->fit.depth == NRV_FIT_LSTM4 ? (size_t)h->T * 256 : h->fit.depth ? (size_t)h->T * 128 : 6 * (size_t)h->T;
 }
 static int fit_params_n(const nrv_handle* h, int model) {
   const int C = h->dm[model].C;
+  if (h->fit.depth == NRV_FIT_LSTM3) return NRV_FIT_PARAMS_LSTM3(h->T, C);
   return h->fit.depth == NRV_FIT_LSTM4 ? NRV_FIT_PARAMS_LSTM4(h->T, C) : h->fit.depth ? NRV_FIT_PARAMS_HEAD(h->T, C) : NRV_FIT_PARAMS(h->T, C);
 }
 // the current depth's set and its cap
-static float** fit_set(nrv_handle::Fit& F) { return F.depth == NRV_FIT_LSTM4 ? F.xb : F.depth ? F.x4 : F.flat; }
-static int64_t fit_cap_rows(const nrv_handle::Fit& F) { return F.depth == NRV_FIT_LSTM4 ? F.max_lstm4_rows : F.depth ? F.max_head_rows : F.max_rows; }
+static float** fit_set(nrv_handle::Fit& F) { return F.depth == NRV_FIT_LSTM3 ? F.xin : F.depth == NRV_FIT_LSTM4 ? F.xb : F.depth ? F.x4 : F.flat; }
+static int64_t fit_cap_rows(const nrv_handle::Fit& F) { return F.depth == NRV_FIT_LSTM3 ? F.max_lstm3_rows : F.depth == NRV_FIT_LSTM4 ? F.max_lstm4_rows : F.depth ? F.max_head_rows : F.max_rows; }
 // room for `need` rows in the set, the rows it holds kept
 static int fit_reserve(nrv_handle* h, int64_t need) {
   nrv_handle::Fit& F = h->fit;
@@ -3787,6 +3818,13 @@ static int fit_enqueue(nrv_handle* h, const char* d_in, size_t off_starts, size_
     launch_segment(h, n_reads, s, nb + T - 1, h->d_sig[0], (const int16_t*)d_in, (const int32_t*)(d_in + off_starts),
                    (const SegRead*)(d_in + off_reads));
     const int rc = for_groups(h, nb, [&](int64_t w, int nw) -> int {
+      if (h->fit.depth == NRV_FIT_LSTM3) {                 // the gather runs INSIDE the group, between lstm2 and lstm4
+        h->fit.l3_slot = d_slot + s + w;
+        const int rc3 = run_group(h, h->d_sig[0] + w * kSig, d_feat + (s + w) * kFeat, nw, true, h->d_p[0][0] + w * 6, h->d_p[0][1] + w * 5,
+                                  h->d_a[0][0] + w, h->d_a[0][1] + w, h->d_sat + 3);
+        h->fit.l3_slot = nullptr;
+        return rc3;
+      }
       const int rc1 = run_group(h, h->d_sig[0] + w * kSig, d_feat + (s + w) * kFeat, nw, true, h->d_p[0][0] + w * 6, h->d_p[0][1] + w * 5,
                                 h->d_a[0][0] + w, h->d_a[0][1] + w, h->d_sat + 3);
       if (rc1) return rc1;
@@ -3860,6 +3898,8 @@ int nrv_fit_add_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, cons
     for (int64_t i = 0; i < n_r; ++i) add += lb[i] != 0xFF && (lb[i] & 7) >= 1 && (lb[i] & 7) <= 5;
   }
   nrv_handle::Fit& F = h->fit;
+  if (F.depth == NRV_FIT_LSTM3 && F.rows + add > F.max_lstm3_rows)
+    return fit_refuse(h, who, "the call would pass the row cap of the training set at lstm3 depth (NRV_FIT_MAX_LSTM3_ROWS)");
   if (F.depth == NRV_FIT_LSTM4 && F.rows + add > F.max_lstm4_rows)
     return fit_refuse(h, who, "the call would pass the row cap of the training set at lstm4 depth (NRV_FIT_MAX_LSTM4_ROWS)");
   if (F.depth == NRV_FIT_HEAD && F.rows + add > F.max_head_rows)
@@ -3916,6 +3956,7 @@ int nrv_fit_set_rows(nrv_handle* h, const float* flat1, const float* flat2, cons
   static const char* who = "nrv_fit_set_rows";
   int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)");
   if (h->fit.depth) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)");
   if (n < 0 || (n > 0 && (!flat1 || !flat2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
@@ -3939,6 +3980,7 @@ int nrv_fit_get_rows(nrv_handle* h, int64_t first, int64_t count, float* flat1, 
   static const char* who = "nrv_fit_get_rows";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)");
   if (h->fit.depth) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)");
   if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
@@ -3963,8 +4005,8 @@ int nrv_fit_set_depth(nrv_handle* h, int depth) {
   static const char* who = "nrv_fit_set_depth";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
-  if (depth != NRV_FIT_TAIL && depth != NRV_FIT_HEAD && depth != NRV_FIT_LSTM4)
-    return fit_refuse(h, who, "depth must be NRV_FIT_TAIL or NRV_FIT_HEAD, or NRV_FIT_LSTM4");
+  if (depth != NRV_FIT_TAIL && depth != NRV_FIT_HEAD && depth != NRV_FIT_LSTM4 && depth != NRV_FIT_LSTM3)
+    return fit_refuse(h, who, "depth must be NRV_FIT_TAIL or NRV_FIT_HEAD, or NRV_FIT_LSTM4, or NRV_FIT_LSTM3");
   nrv_handle::Fit& F = h->fit;
   if (F.rows != 0) return fit_refuse(h, who, "the training set is not empty (call nrv_fit_reset first)");
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3974,8 +4016,8 @@ int nrv_fit_set_depth(nrv_handle* h, int depth) {
   }
   if (depth == F.depth) return NRV_OK;
   for (int m = 0; m < 2; ++m) {
-    (void)hipFree(F.flat[m]); (void)hipFree(F.x4[m]); (void)hipFree(F.xb[m]); (void)hipFree(F.y[m]);
-    F.flat[m] = nullptr; F.x4[m] = nullptr; F.xb[m] = nullptr; F.y[m] = nullptr;
+    (void)hipFree(F.flat[m]); (void)hipFree(F.x4[m]); (void)hipFree(F.xb[m]); (void)hipFree(F.xin[m]); (void)hipFree(F.y[m]);
+    F.flat[m] = nullptr; F.x4[m] = nullptr; F.xb[m] = nullptr; F.xin[m] = nullptr; F.y[m] = nullptr;
     (void)hipFree(F.m[m].d_par); (void)hipFree(F.m[m].d_state);
     F.m[m].d_par = nullptr; F.m[m].d_state = nullptr;
   }
@@ -3988,6 +4030,7 @@ int nrv_fit_set_rows_head(nrv_handle* h, const float* x1, const float* x2, const
   static const char* who = "nrv_fit_set_rows_head";
   int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)");
   if (!h->fit.depth) return fit_refuse(h, who, "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_HEAD) on an empty set first)");
   if (n < 0 || (n > 0 && (!x1 || !x2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
@@ -4011,6 +4054,7 @@ int nrv_fit_get_rows_head(nrv_handle* h, int64_t first, int64_t count, float* x1
   static const char* who = "nrv_fit_get_rows_head";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)");
   if (!h->fit.depth) return fit_refuse(h, who, "the set is at tail depth (rows are main_out values: nrv_fit_get_rows)");
   if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
@@ -4030,6 +4074,7 @@ int nrv_fit_set_rows_lstm4(nrv_handle* h, const float* xb1, const float* xb2, co
   static const char* who = "nrv_fit_set_rows_lstm4";
   int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_HEAD) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)");
   if (h->fit.depth != NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_LSTM4) on an empty set first)");
   if (n < 0 || (n > 0 && (!xb1 || !xb2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
@@ -4053,6 +4098,7 @@ int nrv_fit_get_rows_lstm4(nrv_handle* h, int64_t first, int64_t count, float* x
   static const char* who = "nrv_fit_get_rows_lstm4";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_HEAD) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)");
   if (h->fit.depth != NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at tail depth (rows are main_out values: nrv_fit_get_rows)");
   if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
@@ -4063,6 +4109,57 @@ int nrv_fit_get_rows_lstm4(nrv_handle* h, int64_t first, int64_t count, float* x
   uint8_t* const yy[2] = {y1, y2};
   for (int m = 0; m < 2; ++m) {
     if (xs[m]) HIPCHK(h, hipMemcpy(xs[m], h->fit.xb[m] + (size_t)first * K, (size_t)count * K * 4, hipMemcpyDeviceToHost));
+    if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
+  }
+  return NRV_OK;
+}
+
+static const char* fit_other_depth_set(const nrv_handle* h) {
+  return h->fit.depth == NRV_FIT_LSTM4 ? "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)"
+         : h->fit.depth == NRV_FIT_HEAD ? "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)"
+                                        : "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_LSTM3) on an empty set first)";
+}
+static const char* fit_other_depth_get(const nrv_handle* h) {
+  return h->fit.depth == NRV_FIT_LSTM4 ? "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)"
+         : h->fit.depth == NRV_FIT_HEAD ? "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)"
+                                        : "the set is at tail depth (rows are main_out values: nrv_fit_get_rows)";
+}
+
+int nrv_fit_set_rows_lstm3(nrv_handle* h, const float* x1, const float* x2, const uint8_t* y1, const uint8_t* y2, int64_t n) {
+  static const char* who = "nrv_fit_set_rows_lstm3";
+  int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (h->fit.depth != NRV_FIT_LSTM3) return fit_refuse(h, who, fit_other_depth_set(h));
+  if (n < 0 || (n > 0 && (!x1 || !x2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
+  if (n > h->fit.max_lstm3_rows) return fit_refuse(h, who, "more rows than the cap of the training set at lstm3 depth (NRV_FIT_MAX_LSTM3_ROWS)");
+  for (int64_t i = 0; i < n; ++i)
+    if (y1[i] > 5 || y2[i] > 4) return fit_refuse(h, who, "a label outside the model's classes (y1 0 .. 5, y2 0 .. 4)");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.rows = 0;
+  if (n == 0) return NRV_OK;
+  if ((rc = fit_reserve(h, n))) return rc;
+  const size_t K = fit_row_floats(h);
+  if ((rc = put(h, h->fit.xin[0], x1, (size_t)n * K * 4, h->stream)) || (rc = put(h, h->fit.xin[1], x2, (size_t)n * K * 4, h->stream)) ||
+      (rc = put(h, h->fit.y[0], y1, (size_t)n, h->stream)) || (rc = put(h, h->fit.y[1], y2, (size_t)n, h->stream)))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.rows = n;
+  return NRV_OK;
+}
+
+int nrv_fit_get_rows_lstm3(nrv_handle* h, int64_t first, int64_t count, float* x1, float* x2, uint8_t* y1, uint8_t* y2) {
+  static const char* who = "nrv_fit_get_rows_lstm3";
+  const int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (h->fit.depth != NRV_FIT_LSTM3) return fit_refuse(h, who, fit_other_depth_get(h));
+  if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (count == 0) return NRV_OK;
+  const size_t K = fit_row_floats(h);
+  float* const xs[2] = {x1, x2};
+  uint8_t* const yy[2] = {y1, y2};
+  for (int m = 0; m < 2; ++m) {
+    if (xs[m]) HIPCHK(h, hipMemcpy(xs[m], h->fit.xin[m] + (size_t)first * K, (size_t)count * K * 4, hipMemcpyDeviceToHost));
     if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
   }
   return NRV_OK;
@@ -4120,9 +4217,13 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
   else {
     const size_t src[4] = {d.fw, d.fb, d.ow, d.ob}, cnt[4] = {(size_t)16 * K, 16, (size_t)16 * C, (size_t)C};
     size_t at = 0;
-    if (h->fit.depth == NRV_FIT_LSTM4) {                    // tensors 44 .. 49, unfolded as the file has them
-      HIPCHK(h, hipMemcpyAsync(M.d_par, d.all + d.l4raw, (size_t)kL4N * 4, hipMemcpyDeviceToDevice, h->stream));
-      at = kL4N;
+    if (h->fit.depth == NRV_FIT_LSTM3) {                    // tensors 34 .. 39, unfolded as the file has them
+      HIPCHK(h, hipMemcpyAsync(M.d_par, d.all + d.l3raw, (size_t)kL3N * 4, hipMemcpyDeviceToDevice, h->stream));
+      at = kL3N;
+    }
+    if (h->fit.depth == NRV_FIT_LSTM4 || h->fit.depth == NRV_FIT_LSTM3) {      // tensors 44 .. 49, unfolded as the file has them
+      HIPCHK(h, hipMemcpyAsync(M.d_par + at, d.all + d.l4raw, (size_t)kL4N * 4, hipMemcpyDeviceToDevice, h->stream));
+      at += kL4N;
     }
     if (h->fit.depth) {
       HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -4189,10 +4290,23 @@ static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
   int rc;
   if (h->fit.depth) {
     wg = (size_t)fit_head_wgs(b_max);
-    if ((rc = fit_scratch(h, (void**)&h->fit.d_flag, &h->fit.cap_flag, (size_t)(kL4N / 256 + (kHeadFitMaxP + 255) / 256) * 4))) return rc;
+    if ((rc = fit_scratch(h, (void**)&h->fit.d_flag, &h->fit.cap_flag, (size_t)(kL3N / 256 + kL4N / 256 + (kHeadFitMaxP + 255) / 256) * 4))) return rc;
   }
   size_t pn = (size_t)fit_params_n(h, model);
-  if (h->fit.depth == NRV_FIT_LSTM4) {                       // one chunk's [X4 | dX4 | CS | GZ], the LSTM block's sums; partials of the head alone
+  if (h->fit.depth == NRV_FIT_LSTM3) {                       // one chunk's [H3 | XB | dX3 | CS | GZ], the lstm3 block's sums, the identity list
+    const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
+    if ((rc = fit_scratch(h, (void**)&h->fit.d_l3, &h->fit.cap_l3, rows * h->T * (grad ? 2048 : 512) * 4)) ||
+        (rc = fit_scratch(h, (void**)&h->fit.d_gl3, &h->fit.cap_gl3, (size_t)kL3N * 4)))
+      return rc;
+    if (!h->fit.d_ident) {
+      std::vector<unsigned> id(kL4ChunkRows);
+      for (int i = 0; i < kL4ChunkRows; ++i) id[i] = (unsigned)i;
+      HIPCHK(h, hipMalloc((void**)&h->fit.d_ident, (size_t)kL4ChunkRows * 4));
+      HIPCHK(h, hipMemcpy(h->fit.d_ident, id.data(), (size_t)kL4ChunkRows * 4, hipMemcpyHostToDevice));
+    }
+    pn -= kL3N;
+  }
+  if (h->fit.depth == NRV_FIT_LSTM4 || h->fit.depth == NRV_FIT_LSTM3) {                       // one chunk's [X4 | dX4 | CS | GZ], the LSTM block's sums; partials of the head alone
     const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
     if ((rc = fit_scratch(h, (void**)&h->fit.d_l4, &h->fit.cap_l4, rows * h->T * (grad ? 896 : 128) * 4)) ||
         (rc = fit_scratch(h, (void**)&h->fit.d_gl4, &h->fit.cap_gl4, (size_t)kL4N * 4)))
@@ -4215,21 +4329,36 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
   }
   nrv_handle::Fit::Model& M = h->fit.m[model];
   const int wg = fit_head_wgs(b), P = fit_params_n(h, model), blocks = (P + 255) / 256;
-  if (h->fit.depth == NRV_FIT_LSTM4) {
+  if (h->fit.depth == NRV_FIT_LSTM4 || h->fit.depth == NRV_FIT_LSTM3) {
     const int T = h->T;
     const bool grad = mode != kTailEval;
+    const bool l3 = h->fit.depth == NRV_FIT_LSTM3;
+    const int o3 = l3 ? kL3N : 0;                           // where the lstm4 depth's vector starts
+    const DevModel& dmod = h->dm[model];
     const size_t rcap = (size_t)(b < kL4ChunkRows ? (b + 31) / 32 * 32 : kL4ChunkRows) * T;
     float* const x4 = h->fit.d_l4;                          // the four arrays of fit_step_scratch, dX4 .. GZ only with grad
     float* const dx4 = x4 + rcap * 128;
     float* const cs = dx4 + rcap * 128;
     float* const gz = cs + rcap * 128;
+    float* const h3 = h->fit.d_l3;                          // depth NRV_FIT_LSTM3: the five arrays of fit_step_scratch, dX3 .. GZ only with grad
+    float* const xb4 = l3 ? h3 + rcap * 256 : nullptr;
+    float* const dx3 = l3 ? xb4 + rcap * 256 : nullptr;
+    float* const cs3 = l3 ? dx3 + rcap * 256 : nullptr;
+    float* const gz3 = l3 ? cs3 + rcap * 256 : nullptr;
     for (int c0 = 0; c0 < b; c0 += kL4ChunkRows) {
       const int bc = b - c0 < kL4ChunkRows ? b - c0 : kL4ChunkRows, tiles = (bc + 31) / 32;
-      const L4Args la{h->fit.xb[model], d_rows + c0, M.d_par, x4, gz, cs, dx4, h->fit.d_gl4, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
+      const L3Args l3a{h->fit.xin[model], d_rows + c0, M.d_par, dmod.all + dmod.l_s[2], dmod.all + dmod.l_h[2], h3, xb4, gz3, cs3, dx3, gz,
+                       h->fit.d_gl3, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
+      if (l3) {                                             // lstm3 forward: the scratch XB is "the set" of the lstm4 launches
+        if (h->act == 0) hipLaunchKernelGGL(l3_forward_kernel<0>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
+        else hipLaunchKernelGGL(l3_forward_kernel<1>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
+      }
+      const L4Args la{l3 ? xb4 : h->fit.xb[model], l3 ? h->fit.d_ident : d_rows + c0, M.d_par + o3, x4, gz, cs, dx4, h->fit.d_gl4, T, bc,
+                      grad ? 1 : 0, c0 > 0 ? 1 : 0};
       if (h->act == 0) hipLaunchKernelGGL(l4_forward_kernel<0>, dim3(tiles, 2), dim3(256), 0, h->stream, la);
       else hipLaunchKernelGGL(l4_forward_kernel<1>, dim3(tiles, 2), dim3(256), 0, h->stream, la);
       HeadGradArgs a;
-      a.x = x4; a.y = h->fit.y[model]; a.rows = d_rows + c0; a.par = M.d_par + kL4N;
+      a.x = x4; a.y = h->fit.y[model]; a.rows = d_rows + c0; a.par = M.d_par + o3 + kL4N;
       a.partial = h->fit.d_partial; a.pstat = h->fit.d_pstat; a.p_out = d_p ? d_p + (size_t)c0 * h->dm[model].C : nullptr;
       a.T = T; a.C = h->dm[model].C; a.b = bc; a.lambda = M.o.lambda;
       memcpy(a.cw, M.o.cw, sizeof a.cw);
@@ -4239,13 +4368,24 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
       if (h->act == 0) hipLaunchKernelGGL(l4_backward_kernel<0>, dim3(tiles, 2), dim3(256), 0, h->stream, la);
       else hipLaunchKernelGGL(l4_backward_kernel<1>, dim3(tiles, 2), dim3(256), 0, h->stream, la);
       hipLaunchKernelGGL(l4_wgrad_kernel, dim3(kL4WgM * kL4WgN, 2), dim3(256), 0, h->stream, la);
+      if (l3) {
+        const L4DxArgs da{gz, M.d_par + o3, dmod.all + dmod.l_s[2], dx3, bc * T};
+        hipLaunchKernelGGL(l4_dx_kernel, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, da);
+        if (h->act == 0) hipLaunchKernelGGL(l3_backward_kernel<0>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
+        else hipLaunchKernelGGL(l3_backward_kernel<1>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
+        hipLaunchKernelGGL(l3_wgrad_kernel, dim3(kL3WgM * kL3WgN, 2), dim3(256), 0, h->stream, l3a);
+      }
     }
     // the LSTM block is one "partial" of its own; the head's partials behind it; the flags of both launches in one array
-    const int PH = P - kL4N, bl4 = kL4N / 256;
-    const HeadAdamArgs u1{h->fit.d_gl4, h->fit.d_pstat, 1, b, kL4N, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
+    // (at depth NRV_FIT_LSTM3 the lstm3 block is one more single "partial" in front)
+    const int o4 = o3 + kL4N, PH = P - o4, bl3 = o3 / 256, bl4 = kL4N / 256;
+    const HeadAdamArgs u0{h->fit.d_gl3, h->fit.d_pstat, 1, b, kL3N, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
                           (HeadState*)M.d_state, h->fit.d_flag, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
-    const HeadAdamArgs u2{h->fit.d_partial, h->fit.d_pstat, wg, b, PH, mode, M.d_par + kL4N, M.d_par + P + kL4N, M.d_par + 2 * P + kL4N,
-                          M.d_par + 3 * P + kL4N, (HeadState*)M.d_state, h->fit.d_flag + bl4, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+    const HeadAdamArgs u1{h->fit.d_gl4, h->fit.d_pstat, 1, b, kL4N, mode, M.d_par + o3, M.d_par + P + o3, M.d_par + 2 * P + o3, M.d_par + 3 * P + o3,
+                          (HeadState*)M.d_state, h->fit.d_flag + bl3, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+    const HeadAdamArgs u2{h->fit.d_partial, h->fit.d_pstat, wg, b, PH, mode, M.d_par + o4, M.d_par + P + o4, M.d_par + 2 * P + o4,
+                          M.d_par + 3 * P + o4, (HeadState*)M.d_state, h->fit.d_flag + bl3 + bl4, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+    if (l3) hipLaunchKernelGGL(head_reduce_kernel, dim3(bl3), dim3(256), 0, h->stream, u0);
     const HeadAdamArgs u{h->fit.d_partial, h->fit.d_pstat, wg, b, P, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
                          (HeadState*)M.d_state, h->fit.d_flag, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
     hipLaunchKernelGGL(head_reduce_kernel, dim3(bl4), dim3(256), 0, h->stream, u1);

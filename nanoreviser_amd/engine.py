@@ -49,8 +49,10 @@ SYMBOLS = [
     "nrv_fit_grad", "nrv_fit_epoch", "nrv_fit_eval", "nrv_fit_params",
     "nrv_fit_set_depth", "nrv_fit_depth", "nrv_fit_set_rows_head", "nrv_fit_get_rows_head",
     "nrv_fit_set_rows_lstm4", "nrv_fit_get_rows_lstm4",
+    "nrv_fit_set_rows_lstm3", "nrv_fit_get_rows_lstm3",
 ]
 FIT_TAIL, FIT_HEAD, FIT_LSTM4 = 0, 1, 4    # NRV_FIT_TAIL, NRV_FIT_HEAD, NRV_FIT_LSTM4 (the Bi-LSTM the fit starts at)
+FIT_LSTM3 = 8                              # NRV_FIT_LSTM3
 FIT_MAX_BATCH = 65536               # NRV_FIT_MAX_BATCH
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 PROFILE_COLS = 48                   # NRV_PROFILE_COLS
@@ -182,6 +184,8 @@ _FIT_T = {                                                                      
     "nrv_fit_get_rows_head": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
     "nrv_fit_set_rows_lstm4": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
     "nrv_fit_get_rows_lstm4": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
+    "nrv_fit_set_rows_lstm3": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
+    "nrv_fit_get_rows_lstm3": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
 }
 
 
@@ -870,13 +874,14 @@ class Reviser:
     def fit_n_params(self, model) -> int:
         """The length of a model's parameter vector at the current depth."""
         c = self._n_class(model)
-        front = {FIT_TAIL: 0, FIT_HEAD: 20838, FIT_LSTM4: 164352 + 20838}[self.fit_depth()]
+        front = {FIT_TAIL: 0, FIT_HEAD: 20838, FIT_LSTM4: 164352 + 20838, FIT_LSTM3: 328704 + 164352 + 20838}[self.fit_depth()]
         return front + 96 * self.T + 16 + 16 * c + c + 16 * c
 
     # ---- the second depth (nanoreviser_amd/headfit.py is the definition): the set holds lstm4 outputs [T][128] per window
     def fit_set_depth(self, depth):
-        """FIT_TAIL / FIT_HEAD / FIT_LSTM4 (or "tail" / "head" / "lstm4"), on an empty set only; forgets any fit_begin."""
-        depth = {"tail": FIT_TAIL, "head": FIT_HEAD, "lstm4": FIT_LSTM4}.get(depth, depth)
+        """FIT_TAIL / FIT_HEAD / FIT_LSTM4 / FIT_LSTM3 (or "tail" / "head" / "lstm4" / "lstm3"), on an empty set only; forgets
+        any fit_begin."""
+        depth = {"tail": FIT_TAIL, "head": FIT_HEAD, "lstm4": FIT_LSTM4, "lstm3": FIT_LSTM3}.get(depth, depth)
         self._check(self._lib.nrv_fit_set_depth(self._h, int(depth)))
 
     def fit_depth(self) -> int:
@@ -917,6 +922,24 @@ class Reviser:
         sh = (count, self.T, 256)
         out = (np.empty(sh, np.float32), np.empty(sh, np.float32), np.empty(count, np.uint8), np.empty(count, np.uint8))
         self._check(self._lib.nrv_fit_get_rows_lstm4(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _U8P),
+                                                     _ptr(out[3], _U8P)))
+        return out
+
+    # ---- the fourth depth (nanoreviser_amd/lstm3fit.py is the definition): the set holds lstm3's inputs [T][192]
+    def fit_set_rows_lstm3(self, x1, x2, y1, y2):
+        a1, a2 = _as_f32(x1, (self.T, 192)), _as_f32(x2, (self.T, 192))
+        a, b = (np.ascontiguousarray(v, dtype=np.uint8).reshape(-1) for v in (y1, y2))
+        n = a1.shape[0]
+        if a2.shape[0] != n or a.size != n or b.size != n:
+            raise ValueError("x1 / x2 / y1 / y2 must have one entry per row")
+        self._check(self._lib.nrv_fit_set_rows_lstm3(self._h, _ptr(a1, _FP), _ptr(a2, _FP), _ptr(a, _U8P), _ptr(b, _U8P), n))
+
+    def fit_get_rows_lstm3(self, first=0, count=None):
+        """-> (x1, x2, y1, y2) of rows [first, first + count), x [count][T][192]."""
+        count = self.fit_count() - first if count is None else count
+        sh = (count, self.T, 192)
+        out = (np.empty(sh, np.float32), np.empty(sh, np.float32), np.empty(count, np.uint8), np.empty(count, np.uint8))
+        self._check(self._lib.nrv_fit_get_rows_lstm3(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _U8P),
                                                      _ptr(out[3], _U8P)))
         return out
 

@@ -130,6 +130,13 @@ def forward(Xb, theta, T: int, C: int, act: int = 0, dtype=np.float64):
 
 def batch_terms(Xb, y, theta, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64):
     """One batch -> (g [P]: the gradient of L, FitStats of the batch with steps = nonfinite = 0)."""
+    return batch_terms_dx(Xb, y, theta, T, C, opts, act, dtype)[:2]
+
+
+def batch_terms_dx(Xb, y, theta, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64):
+    """batch_terms and the data gradient behind it -> (g, FitStats, dXb [n][T][256]: the sum over both directions (forward
+    first) and all steps of dz W^T - the derivative of the batch's SUM of row losses, not divided by n).  lstm3fit.py goes on
+    from it."""
     dt = np.dtype(dtype)
     theta = np.asarray(theta)
     Xb, X4, keep = lstm(Xb, theta, T, C, act, dt)
@@ -138,8 +145,9 @@ def batch_terms(Xb, y, theta, T: int, C: int, opts: FitOpts, act: int = 0, dtype
     parts = [a.astype(dt) for a in unpack(theta, T, C)[:6]]
     one = dt.type(1)
     grads = []
+    dXb = np.zeros((n, T, D_X), dt)
     for d in range(2):
-        U = parts[3 * d + 1]
+        W, U = parts[3 * d], parts[3 * d + 1]
         k = keep[d]
         gW, gU, gb = np.zeros((D_X, 4 * H), dt), np.zeros((H, 4 * H), dt), np.zeros(4 * H, dt)
         dz_next = np.zeros((n, 4 * H), dt)
@@ -158,11 +166,12 @@ def batch_terms(Xb, y, theta, T: int, C: int, opts: FitOpts, act: int = 0, dtype
             gW += Xb[:, t].T @ dz
             gU += h_prev.T @ dz
             gb += dz.sum(axis=0)
+            dXb[:, t] += dz @ W.T
             dcf = dc * f
             dz_next = dz
         grads += [gW, gU, gb]
     g = np.concatenate([a.ravel() for a in grads]) / dt.type(n)
-    return np.concatenate([g.astype(dt), gh]), st
+    return np.concatenate([g.astype(dt), gh]), st, dXb
 
 
 def epoch(Xb, y, state: FitState, order, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64) -> FitStats:

@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
-"""Time nrv_fit_epoch at the three fit depths (tail: tensors 56 .. 59; head: tensors 50 .. 59; lstm4: tensors 44 .. 59) on the
-device.  A plain script: it takes no part in bench.py and sets no bar.
+"""Time nrv_fit_epoch at the four fit depths (tail: tensors 56 .. 59; head: tensors 50 .. 59; lstm4: tensors 44 .. 59; lstm3:
+tensors 34 .. 39 and 44 .. 59) on the device.  A plain script: it takes no part in bench.py and sets no bar.
 
-A set of seeded rows goes in through the unit doors (nrv_fit_set_rows / _head / _lstm4), so the frozen backbone never
+A set of seeded rows goes in through the unit doors (nrv_fit_set_rows / _head / _lstm4 / _lstm3), so the frozen backbone never
 runs: what is timed is one whole nrv_fit_epoch call - the upload of the row order, every batch's launches enqueued back to back
 and the one synchronise at the end - by a host clock around the call, which returns only after that synchronise.  Per depth:
 untimed epochs first (first launches load code objects and size the scratch buffers), then --repeats timed epochs; the median
 and the spread (min .. max) are printed as rows/s, then one JSON line with everything.
 
-    python tools/fit_bench.py [--rows 65536] [-b 512] [-w 11] [--warmup 3] [--repeats 9] [--model 0]
+    python tools/fit_bench.py [--rows 65536] [-b 512] [-w 11] [--warmup 3] [--repeats 9] [--model 0] [--depths tail,head,lstm4,lstm3]
 """
 import argparse
 import json
@@ -33,7 +33,13 @@ def flop_per_row(depth, T, C):
     # lstm4 depth: the head with its data gradient dX4 = dh1 W1^T; per direction the input and recurrent products forward, the
     # recurrent data gradient dz U^T (none into Xb: lstm3 is frozen) and the two weight-gradient products
     lstm = 2 * T * 2 * (256 * 256 + 64 * 256)
-    return tail + 3 * mlp + 2 * lstm + 2 * T * 2 * 64 * 256
+    l4 = tail + 3 * mlp + 2 * lstm + 2 * T * 2 * 64 * 256
+    if depth == "lstm4":
+        return l4
+    # lstm3 depth: the lstm4 depth with its data gradient dXb4 = dz4 W4^T; lstm3's two forward products, its recurrent data
+    # gradient and its two weight-gradient products, per direction
+    lstm3 = 2 * T * 2 * (192 * 512 + 128 * 512)
+    return l4 + 2 * T * 2 * 256 * 256 + 2 * lstm3 + 2 * T * 2 * 128 * 512
 
 
 def main(argv=None):
@@ -46,8 +52,9 @@ def main(argv=None):
     ap.add_argument("--model", type=int, default=0, choices=(0, 1))
     ap.add_argument("--species", default="ecoli")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--depths", default="tail,head,lstm4,lstm3", help="the depths to time, in this order")
     a = ap.parse_args(argv)
-    from nanoreviser_amd import headfit, lstm4fit, tailfit
+    from nanoreviser_amd import headfit, lstm3fit, lstm4fit, tailfit
     from nanoreviser_amd.engine import Reviser
     from nanoreviser_amd.weights import load_species
     T, k, n = a.window_size, a.model, a.rows
@@ -64,13 +71,19 @@ def main(argv=None):
     except Exception:
         pass
     try:
-        for depth in ("tail", "head", "lstm4"):
+        for depth in a.depths.split(","):
             rv.fit_reset()
             rv.fit_set_depth(depth)
             if depth == "tail":
                 F = np.maximum(rng.normal(0, 1, (n, 6 * T)), 0).astype(np.float32)
                 rv.fit_set_rows(F, F, y1, y2)
                 th = tailfit.fresh_params(T, C, a.seed)
+            elif depth == "lstm3":                         # the shipped lstm3 and lstm4 in front of a fresh head
+                X = rng.normal(0, 1, (n, T, 192)).astype(np.float32)
+                rv.fit_set_rows_lstm3(X, X, y1, y2)
+                m = (m1, m2)[k].with_window(T)
+                th4 = lstm4fit.with_head(lstm4fit.params_from_model(m), headfit.fresh_params(T, C, a.seed))
+                th = lstm3fit.with_lstm4(lstm3fit.params_from_model(m), th4)
             elif depth == "lstm4":                         # the shipped lstm4 in front of a fresh head (lstm4 has no fresh start)
                 X = rng.normal(0, 1, (n, T, 256)).astype(np.float32)
                 rv.fit_set_rows_lstm4(X, X, y1, y2)
