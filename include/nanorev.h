@@ -860,6 +860,41 @@ int nrv_fit_get_rows_lstm4(nrv_handle* h, int64_t first, int64_t count, float* x
 int nrv_fit_set_rows_lstm3(nrv_handle* h, const float* x1, const float* x2, const uint8_t* y1, const uint8_t* y2, int64_t n);
 int nrv_fit_get_rows_lstm3(nrv_handle* h, int64_t first, int64_t count, float* x1, float* x2, uint8_t* y1, uint8_t* y2);
 
+/* ---- Fitting the signal branch with lstm3 and everything behind it: a fifth DEPTH of nrv_fit_* (opt-in) ----
+ * At depth NRV_FIT_SIGNAL the part of the model that reads the raw current is fitted: conv1.kernel [3][1][8] and .bias (tensors
+ * 0, 1), conv2.kernel [3][8][8] and .bias (6, 7), sig_dense.kernel [400][64] and .bias (32, 33) - 25896 weights - and everything
+ * the lstm3 depth fits (34 .. 39, 44 .. 59 and the centres).  nanoreviser_amd/signalfit.py is the definition.  Frozen: lstm1,
+ * lstm2 and their BatchNorms (12 .. 31) AND the three BatchNorms inside the fitted section (2 .. 5, 8 .. 11, 40 .. 43).  TWO STATED
+ * DEVIATIONS: those three BatchNorms are applied in their inference form from the moving statistics as the handle holds them
+ * (behind a convolution relu(conv) * s + h, one f32 multiply and one f32 add), where Keras in training phase would normalise
+ * with the batch's statistics and fit gamma and beta; and the reference's Dropout(0.2) behind the identity block is not applied.
+ * The constant is 16: 2, 3, 5, 6, 7, 9 .. 15, 17 and -1 stay refused.
+ *   nrv_fit_set_depth  takes NRV_FIT_SIGNAL under the rules above.
+ * THE SET at this depth.  Per model x2 f32 [rows][T][128] - the BatchNorm'd f32 lstm2 output of the window - and the same y
+ * arrays; ONE sig f32 [rows][T][50] for both models - the normalised samples of the window's T events - because both read the
+ * same samples.  A row is 512 T bytes per model and 200 T bytes shared; the depth's own cap is NRV_FIT_MAX_SIGNAL_ROWS
+ * (environment, read by nrv_create; default 2^20); a call that would pass it is refused whole, by that name.
+ *   nrv_fit_add_reads_raw  unchanged signature and label rule; the NRV_PREC_F32 kernels whatever the mode.  Where the lstm3 depth
+ *     gathers, a gather moves every labelled window's T x 128 lstm2 values through the view the f32 lstm3 launch reads (16 bytes
+ *     at a time) and its T x 50 samples out of the group's event-major samples (window w, step t is event w + t; 8 bytes at a
+ *     time) to the window's slot, with plain stores.
+ *   nrv_fit_set_rows_signal / nrv_fit_get_rows_signal  the unit doors.  Each depth's doors are refused at the other depths under
+ *     their own names; the handle stays usable.
+ * THE FIT.  One vector of NRV_FIT_PARAMS_SIGNAL(T, C) = 25896 + NRV_FIT_PARAMS_LSTM3(T, C) floats:
+ *   [w1 24 | b1 8 | w2 192 | b2 8 | Ws 25600 | bs 64 | the lstm3 depth's vector]          tensors as the weight file has them.
+ * params NULL: the handle's own tensors and zero centres.  Forward per (row, t): a1 = relu(conv1(sig) + b1), c1 = a1 s1 + h1,
+ * a2 = relu(conv2(c1) + b2), F[p * 8 + o] = a2 s2 + h2 + sig[p] (`same` padding: taps outside the 50 samples are zero),
+ * S = F Ws + bs, Xin = [x2 | S], then the lstm3 depth's forward and loss.  Backward: the lstm3 depth's, then dS = columns
+ * 128 .. 191 of (sum over both directions, forward first, of dz3 W3^T), gWs = F^T dS, gbs = 1^T dS, dF = dS Ws^T, and back through
+ * the two convolutions with the ReLU sides decided on the forward value (csrc/nrv_signalfit.h).  Chunks, reduction, finite check
+ * over the whole vector and ONE Adam launch as at lstm3 depth; no atomics, the same calls give the same bytes.  nrv_fit_eval runs
+ * the forward launches alone. */
+#define NRV_FIT_SIGNAL 16
+#define NRV_FIT_PARAMS_SIGNAL(T, C) (25896 + NRV_FIT_PARAMS_LSTM3(T, C))
+int nrv_fit_set_rows_signal(nrv_handle* h, const float* x2_1, const float* x2_2, const float* sig, const uint8_t* y1, const uint8_t* y2,
+                            int64_t n);
+int nrv_fit_get_rows_signal(nrv_handle* h, int64_t first, int64_t count, float* x2_1, float* x2_2, float* sig, uint8_t* y1, uint8_t* y2);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

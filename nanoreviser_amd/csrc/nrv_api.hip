@@ -6,6 +6,7 @@
 #include "nrv_headfit.h"      // ... at depth NRV_FIT_HEAD: lstm4 outputs as the set, the gradient through the three dense layers
 #include "nrv_lstm4fit.h"     // ... at depth NRV_FIT_LSTM4: BatchNorm'd lstm3 outputs as the set, the last Bi-LSTM's forward and backward
 #include "nrv_lstm3fit.h"     // ... at depth NRV_FIT_LSTM3: lstm3's inputs as the set, the 192->128 Bi-LSTM's forward and backward, dX out of lstm4
+#include "nrv_signalfit.h"    // ... at depth NRV_FIT_SIGNAL: lstm2's outputs and the samples as the set, the signal branch's forward and backward, dS out of lstm3
 #include "nrv_block.h"
 
 #include <algorithm>
@@ -462,6 +463,7 @@ struct DevModel {
   size_t l_ws[4];             // lstm2..4 weights split into three bf16 terms (index 1..3)
   size_t d1p, d1b, d2p, d2b, mop, mob, fw, fb, ow, ob;
   size_t l3raw = 0;           // tensors 34 .. 39 as the file has them (... at depth NRV_FIT_LSTM3)
+  size_t sdraw = 0;           // tensor 32 as the file has it (... at depth NRV_FIT_SIGNAL)
   size_t l4raw = 0;           // tensors 44 .. 49 as the file has them (nrv_fit_begin at depth NRV_FIT_LSTM4 starts from them)
   size_t h_ws, h_wb;          // head_mlp_split_kernel: split weights / biases
   // f16x2 mode (nrv_lstm_f16x2.h): lstm2..4 weights as two f16 terms, scaled biases, output scale /
@@ -700,6 +702,15 @@ struct nrv_handle {
     float* d_gl3 = nullptr; size_t cap_gl3 = 0;               // [kL3N]
     unsigned* d_ident = nullptr;                              // [kL4ChunkRows] 0, 1, 2, ...
     const int* l3_slot = nullptr;
+    // depth NRV_FIT_SIGNAL: the set is x2 [cap][T][128] per model, ONE sig [cap][T][50] for both and y; one chunk's
+    // [Xin | F | dS] (nrv_signalfit.h) in front of the lstm3 depth's scratch, the conv block's partials and the dense block's sums;
+    // the gather runs where the lstm3 depth's does, on l3_slot
+    float* x2s[2] = {nullptr, nullptr};
+    float* sigs = nullptr;
+    int64_t max_signal_rows = (int64_t)1 << 20;               // NRV_FIT_MAX_SIGNAL_ROWS, read by nrv_create
+    float* d_sg = nullptr; size_t cap_sg = 0;
+    float* d_pconv = nullptr; size_t cap_pconv = 0;           // [workgroups][kSgConv]
+    float* d_gdense = nullptr; size_t cap_gdense = 0;         // [kSgDense]
     int* d_flag = nullptr; size_t cap_flag = 0;               // head_reduce_kernel's per-workgroup flags
     float* d_partial = nullptr; size_t cap_partial = 0;       // [workgroups][P]
     TailStat* d_pstat = nullptr; size_t cap_pstat = 0;        // [workgroups]
@@ -811,6 +822,7 @@ NRV_HOST_COLD static int upload_model(nrv_handle* h, int mi, const Blob& b, int 
   pack_dense16(b.t(32), 400, 64, wp);
   d.dpack = put(wp.data(), wp.size());
   d.dbias = put(b.t(33), 64);
+  d.sdraw = put(b.t(32), 400 * 64);
   pack_cnn_split(b.t(32), wp);
   d.dsplit = put(wp.data(), wp.size());
   const int lbase[4] = {12, 22, 34, 44}, lK[4] = {6, 32, 192, 256}, lH[4] = {16, 64, 128, 64};
@@ -1433,6 +1445,14 @@ static int run_group(nrv_handle* h, const float* d_sig, const float* d_feat, int
       launch_lstm_f32<32, 16, 128, 1, 1>(h, a, tiles);
     }
     if ((rc = mark(4))) return rc;
+    if (h->fit.l3_slot && h->fit.depth == NRV_FIT_SIGNAL) {      // ... at depth NRV_FIT_SIGNAL: lstm2's output and the samples
+      SigGatherArgs g;
+      for (int m = 0; m < 2; ++m) { g.in0[m] = win_view(h->X2[m], 32); g.x2[m] = h->fit.x2s[m]; }
+      g.sig_ev = d_sig; g.sig = h->fit.sigs;
+      g.slot = h->fit.l3_slot; g.n = n; g.T = T; g.cap = h->fit.cap;
+      const long long total = (long long)n * T * 57;
+      hipLaunchKernelGGL(sig_gather_kernel, dim3((unsigned)((total + 255) / 256), 2), dim3(256), 0, h->stream, g);
+    } else
     if (h->fit.l3_slot) {                        // nrv_fit_add_reads_raw at depth NRV_FIT_LSTM3: lstm3's two inputs of the group's
       L3GatherArgs g;                            // labelled windows, before the next launch writes X4 over X2
       for (int m = 0; m < 2; ++m) {
@@ -1585,6 +1605,7 @@ int nrv_create(const nrv_weights* m1, const nrv_weights* m2, int T, int device, 
   if (const char* e6 = getenv("NRV_LABELS_BUDGET"); e6 && *e6) { const long long v = atoll(e6); if (v > 0) h->lab_budget = (size_t)v; }
   if (const char* e7 = getenv("NRV_FIT_MAX_ROWS"); e7 && *e7) { const long long v = atoll(e7); if (v > 0) h->fit.max_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e9 = getenv("NRV_FIT_MAX_LSTM4_ROWS"); e9 && *e9) { const long long v = atoll(e9); if (v > 0) h->fit.max_lstm4_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
+  if (const char* e11 = getenv("NRV_FIT_MAX_SIGNAL_ROWS"); e11 && *e11) { const long long v = atoll(e11); if (v > 0) h->fit.max_signal_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e10 = getenv("NRV_FIT_MAX_LSTM3_ROWS"); e10 && *e10) { const long long v = atoll(e10); if (v > 0) h->fit.max_lstm3_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e8 = getenv("NRV_FIT_MAX_HEAD_ROWS"); e8 && *e8) { const long long v = atoll(e8); if (v > 0) h->fit.max_head_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e5 = getenv("NRV_POISON"); e5 && *e5) { h->poison_on = true; h->poison = (unsigned)strtoul(e5, nullptr, 16); }
@@ -1621,11 +1642,13 @@ void nrv_destroy(nrv_handle* h) {
   for (char* p : h->lab_retired) (void)hipFree(p);
   for (int m = 0; m < 2; ++m) {
     (void)hipFree(h->fit.flat[m]); (void)hipFree(h->fit.y[m]); (void)hipFree(h->fit.x4[m]); (void)hipFree(h->fit.xb[m]); (void)hipFree(h->fit.xin[m]);
+    (void)hipFree(h->fit.x2s[m]);
     (void)hipFree(h->fit.m[m].d_par); (void)hipFree(h->fit.m[m].d_state); (void)hipFree(h->fit.m[m].d_lr);
   }
   (void)hipFree(h->fit.d_partial); (void)hipFree(h->fit.d_pstat); (void)hipFree(h->fit.d_order); (void)hipFree(h->fit.d_p); (void)hipFree(h->fit.d_flag);
   (void)hipFree(h->fit.d_l4); (void)hipFree(h->fit.d_gl4);
   (void)hipFree(h->fit.d_l3); (void)hipFree(h->fit.d_gl3); (void)hipFree(h->fit.d_ident);
+  (void)hipFree(h->fit.sigs); (void)hipFree(h->fit.d_sg); (void)hipFree(h->fit.d_pconv); (void)hipFree(h->fit.d_gdense);
   for (int st = 0; st < nrv_handle::kIn; ++st) if (h->ev_in[st]) (void)hipEventDestroy(h->ev_in[st]);
   for (int st = 0; st < 2; ++st) {
     if (h->ev_done[st]) (void)hipEventDestroy(h->ev_done[st]);
@@ -3752,17 +3775,19 @@ static int fit_scratch(nrv_handle* h, void** p, size_t* cap, size_t bytes) {
 }
 // floats of one row of the set at the handle's depth, and the parameters of a model's vector
 static size_t fit_row_floats(const nrv_handle* h) {
+  if (h->fit.depth == NRV_FIT_SIGNAL) return (size_t)h->T * 128;          // (per model; the shared samples are T * 50 more)
   if (h->fit.depth == NRV_FIT_LSTM3) return (size_t)h->T * 192;
   return h->fit.depth == NRV_FIT_LSTM4 ? (size_t)h->T * 256 : h->fit.depth ? (size_t)h->T * 128 : 6 * (size_t)h->T;
 }
 static int fit_params_n(const nrv_handle* h, int model) {
   const int C = h->dm[model].C;
+  if (h->fit.depth == NRV_FIT_SIGNAL) return NRV_FIT_PARAMS_SIGNAL(h->T, C);
   if (h->fit.depth == NRV_FIT_LSTM3) return NRV_FIT_PARAMS_LSTM3(h->T, C);
   return h->fit.depth == NRV_FIT_LSTM4 ? NRV_FIT_PARAMS_LSTM4(h->T, C) : h->fit.depth ? NRV_FIT_PARAMS_HEAD(h->T, C) : NRV_FIT_PARAMS(h->T, C);
 }
 // the current depth's set and its cap
-static float** fit_set(nrv_handle::Fit& F) { return F.depth == NRV_FIT_LSTM3 ? F.xin : F.depth == NRV_FIT_LSTM4 ? F.xb : F.depth ? F.x4 : F.flat; }
-static int64_t fit_cap_rows(const nrv_handle::Fit& F) { return F.depth == NRV_FIT_LSTM3 ? F.max_lstm3_rows : F.depth == NRV_FIT_LSTM4 ? F.max_lstm4_rows : F.depth ? F.max_head_rows : F.max_rows; }
+static float** fit_set(nrv_handle::Fit& F) { return F.depth == NRV_FIT_SIGNAL ? F.x2s : F.depth == NRV_FIT_LSTM3 ? F.xin : F.depth == NRV_FIT_LSTM4 ? F.xb : F.depth ? F.x4 : F.flat; }
+static int64_t fit_cap_rows(const nrv_handle::Fit& F) { return F.depth == NRV_FIT_SIGNAL ? F.max_signal_rows : F.depth == NRV_FIT_LSTM3 ? F.max_lstm3_rows : F.depth == NRV_FIT_LSTM4 ? F.max_lstm4_rows : F.depth ? F.max_head_rows : F.max_rows; }
 // room for `need` rows in the set, the rows it holds kept
 static int fit_reserve(nrv_handle* h, int64_t need) {
   nrv_handle::Fit& F = h->fit;
@@ -3775,7 +3800,18 @@ static int fit_reserve(nrv_handle* h, int64_t need) {
   float** const set = fit_set(F);
   float* nf[2] = {nullptr, nullptr};
   uint8_t* ny[2] = {nullptr, nullptr};
+  float* nsig = nullptr;                                   // depth NRV_FIT_SIGNAL: the samples both models share
   int rc = NRV_OK;
+  if (F.depth == NRV_FIT_SIGNAL) {
+    const size_t KS = (size_t)h->T * kSig;
+    if (hipMalloc((void**)&nsig, (size_t)c * KS * 4) != hipSuccess) { h->err = "nrv_fit: out of device memory for the training set"; return NRV_E_NOMEM; }
+    if ((rc = poison_fill(h, nsig, (size_t)c * KS * 4, h->stream))) { (void)hipFree(nsig); return rc; }
+    if (F.rows > 0 && hipMemcpyAsync(nsig, F.sigs, (size_t)F.rows * KS * 4, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
+      h->err = "nrv_fit: copying the training set failed";
+      (void)hipFree(nsig);
+      return NRV_E_HIP;
+    }
+  }
   for (int m = 0; m < 2 && !rc; ++m) {
     if (hipMalloc((void**)&nf[m], (size_t)c * K * 4) != hipSuccess || hipMalloc((void**)&ny[m], ((size_t)c + 3) / 4 * 4) != hipSuccess) {
       h->err = "nrv_fit: out of device memory for the training set";
@@ -3794,8 +3830,10 @@ static int fit_reserve(nrv_handle* h, int64_t need) {
   if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) { h->err = "nrv_fit: growing the training set failed"; rc = NRV_E_HIP; }
   if (rc) {
     for (int m = 0; m < 2; ++m) { (void)hipFree(nf[m]); (void)hipFree(ny[m]); }
+    (void)hipFree(nsig);
     return rc;
   }
+  if (F.depth == NRV_FIT_SIGNAL) { (void)hipFree(F.sigs); F.sigs = nsig; }
   for (int m = 0; m < 2; ++m) {
     (void)hipFree(set[m]); (void)hipFree(F.y[m]);
     set[m] = nf[m]; F.y[m] = ny[m];
@@ -3818,7 +3856,7 @@ static int fit_enqueue(nrv_handle* h, const char* d_in, size_t off_starts, size_
     launch_segment(h, n_reads, s, nb + T - 1, h->d_sig[0], (const int16_t*)d_in, (const int32_t*)(d_in + off_starts),
                    (const SegRead*)(d_in + off_reads));
     const int rc = for_groups(h, nb, [&](int64_t w, int nw) -> int {
-      if (h->fit.depth == NRV_FIT_LSTM3) {                 // the gather runs INSIDE the group, between lstm2 and lstm4
+      if (h->fit.depth == NRV_FIT_LSTM3 || h->fit.depth == NRV_FIT_SIGNAL) {                 // the gather runs INSIDE the group, between lstm2 and lstm4
         h->fit.l3_slot = d_slot + s + w;
         const int rc3 = run_group(h, h->d_sig[0] + w * kSig, d_feat + (s + w) * kFeat, nw, true, h->d_p[0][0] + w * 6, h->d_p[0][1] + w * 5,
                                   h->d_a[0][0] + w, h->d_a[0][1] + w, h->d_sat + 3);
@@ -3898,6 +3936,8 @@ int nrv_fit_add_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, cons
     for (int64_t i = 0; i < n_r; ++i) add += lb[i] != 0xFF && (lb[i] & 7) >= 1 && (lb[i] & 7) <= 5;
   }
   nrv_handle::Fit& F = h->fit;
+  if (F.depth == NRV_FIT_SIGNAL && F.rows + add > F.max_signal_rows)
+    return fit_refuse(h, who, "the call would pass the row cap of the training set at signal depth (NRV_FIT_MAX_SIGNAL_ROWS)");
   if (F.depth == NRV_FIT_LSTM3 && F.rows + add > F.max_lstm3_rows)
     return fit_refuse(h, who, "the call would pass the row cap of the training set at lstm3 depth (NRV_FIT_MAX_LSTM3_ROWS)");
   if (F.depth == NRV_FIT_LSTM4 && F.rows + add > F.max_lstm4_rows)
@@ -3956,6 +3996,7 @@ int nrv_fit_set_rows(nrv_handle* h, const float* flat1, const float* flat2, cons
   static const char* who = "nrv_fit_set_rows";
   int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_set_rows_signal)");
   if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)");
   if (h->fit.depth) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)");
@@ -3980,6 +4021,7 @@ int nrv_fit_get_rows(nrv_handle* h, int64_t first, int64_t count, float* flat1, 
   static const char* who = "nrv_fit_get_rows";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_get_rows_signal)");
   if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)");
   if (h->fit.depth) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)");
@@ -4005,8 +4047,8 @@ int nrv_fit_set_depth(nrv_handle* h, int depth) {
   static const char* who = "nrv_fit_set_depth";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
-  if (depth != NRV_FIT_TAIL && depth != NRV_FIT_HEAD && depth != NRV_FIT_LSTM4 && depth != NRV_FIT_LSTM3)
-    return fit_refuse(h, who, "depth must be NRV_FIT_TAIL or NRV_FIT_HEAD, or NRV_FIT_LSTM4, or NRV_FIT_LSTM3");
+  if (depth != NRV_FIT_TAIL && depth != NRV_FIT_HEAD && depth != NRV_FIT_LSTM4 && depth != NRV_FIT_LSTM3 && depth != NRV_FIT_SIGNAL)
+    return fit_refuse(h, who, "depth must be NRV_FIT_TAIL or NRV_FIT_HEAD, or NRV_FIT_LSTM4, or NRV_FIT_LSTM3, or NRV_FIT_SIGNAL");
   nrv_handle::Fit& F = h->fit;
   if (F.rows != 0) return fit_refuse(h, who, "the training set is not empty (call nrv_fit_reset first)");
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -4018,9 +4060,11 @@ int nrv_fit_set_depth(nrv_handle* h, int depth) {
   for (int m = 0; m < 2; ++m) {
     (void)hipFree(F.flat[m]); (void)hipFree(F.x4[m]); (void)hipFree(F.xb[m]); (void)hipFree(F.xin[m]); (void)hipFree(F.y[m]);
     F.flat[m] = nullptr; F.x4[m] = nullptr; F.xb[m] = nullptr; F.xin[m] = nullptr; F.y[m] = nullptr;
+    (void)hipFree(F.x2s[m]); F.x2s[m] = nullptr;
     (void)hipFree(F.m[m].d_par); (void)hipFree(F.m[m].d_state);
     F.m[m].d_par = nullptr; F.m[m].d_state = nullptr;
   }
+  (void)hipFree(F.sigs); F.sigs = nullptr;
   F.cap = 0;
   F.depth = depth;
   return NRV_OK;
@@ -4030,6 +4074,7 @@ int nrv_fit_set_rows_head(nrv_handle* h, const float* x1, const float* x2, const
   static const char* who = "nrv_fit_set_rows_head";
   int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_set_rows_signal)");
   if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)");
   if (!h->fit.depth) return fit_refuse(h, who, "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_HEAD) on an empty set first)");
@@ -4054,6 +4099,7 @@ int nrv_fit_get_rows_head(nrv_handle* h, int64_t first, int64_t count, float* x1
   static const char* who = "nrv_fit_get_rows_head";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_get_rows_signal)");
   if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)");
   if (!h->fit.depth) return fit_refuse(h, who, "the set is at tail depth (rows are main_out values: nrv_fit_get_rows)");
@@ -4074,6 +4120,7 @@ int nrv_fit_set_rows_lstm4(nrv_handle* h, const float* xb1, const float* xb2, co
   static const char* who = "nrv_fit_set_rows_lstm4";
   int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_set_rows_signal)");
   if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_HEAD) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)");
   if (h->fit.depth != NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_LSTM4) on an empty set first)");
@@ -4098,6 +4145,7 @@ int nrv_fit_get_rows_lstm4(nrv_handle* h, int64_t first, int64_t count, float* x
   static const char* who = "nrv_fit_get_rows_lstm4";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_get_rows_signal)");
   if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_HEAD) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)");
   if (h->fit.depth != NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at tail depth (rows are main_out values: nrv_fit_get_rows)");
@@ -4115,12 +4163,14 @@ int nrv_fit_get_rows_lstm4(nrv_handle* h, int64_t first, int64_t count, float* x
 }
 
 static const char* fit_other_depth_set(const nrv_handle* h) {
-  return h->fit.depth == NRV_FIT_LSTM4 ? "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)"
+  return h->fit.depth == NRV_FIT_SIGNAL ? "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_set_rows_signal)"
+         : h->fit.depth == NRV_FIT_LSTM4 ? "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)"
          : h->fit.depth == NRV_FIT_HEAD ? "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)"
                                         : "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_LSTM3) on an empty set first)";
 }
 static const char* fit_other_depth_get(const nrv_handle* h) {
-  return h->fit.depth == NRV_FIT_LSTM4 ? "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)"
+  return h->fit.depth == NRV_FIT_SIGNAL ? "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_get_rows_signal)"
+         : h->fit.depth == NRV_FIT_LSTM4 ? "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)"
          : h->fit.depth == NRV_FIT_HEAD ? "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)"
                                         : "the set is at tail depth (rows are main_out values: nrv_fit_get_rows)";
 }
@@ -4162,6 +4212,56 @@ int nrv_fit_get_rows_lstm3(nrv_handle* h, int64_t first, int64_t count, float* x
     if (xs[m]) HIPCHK(h, hipMemcpy(xs[m], h->fit.xin[m] + (size_t)first * K, (size_t)count * K * 4, hipMemcpyDeviceToHost));
     if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
   }
+  return NRV_OK;
+}
+
+static const char* fit_not_signal(const nrv_handle* h, bool set) {
+  if (h->fit.depth == NRV_FIT_LSTM3)
+    return set ? "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)" : "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)";
+  if (h->fit.depth == NRV_FIT_TAIL && set) return "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_SIGNAL) on an empty set first)";
+  return set ? fit_other_depth_set(h) : fit_other_depth_get(h);
+}
+
+int nrv_fit_set_rows_signal(nrv_handle* h, const float* x2_1, const float* x2_2, const float* sig, const uint8_t* y1, const uint8_t* y2,
+                            int64_t n) {
+  static const char* who = "nrv_fit_set_rows_signal";
+  int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (h->fit.depth != NRV_FIT_SIGNAL) return fit_refuse(h, who, fit_not_signal(h, true));
+  if (n < 0 || (n > 0 && (!x2_1 || !x2_2 || !sig || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
+  if (n > h->fit.max_signal_rows) return fit_refuse(h, who, "more rows than the cap of the training set at signal depth (NRV_FIT_MAX_SIGNAL_ROWS)");
+  for (int64_t i = 0; i < n; ++i)
+    if (y1[i] > 5 || y2[i] > 4) return fit_refuse(h, who, "a label outside the model's classes (y1 0 .. 5, y2 0 .. 4)");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.rows = 0;
+  if (n == 0) return NRV_OK;
+  if ((rc = fit_reserve(h, n))) return rc;
+  const size_t K = fit_row_floats(h), KS = (size_t)h->T * kSig;
+  if ((rc = put(h, h->fit.x2s[0], x2_1, (size_t)n * K * 4, h->stream)) || (rc = put(h, h->fit.x2s[1], x2_2, (size_t)n * K * 4, h->stream)) ||
+      (rc = put(h, h->fit.sigs, sig, (size_t)n * KS * 4, h->stream)) ||
+      (rc = put(h, h->fit.y[0], y1, (size_t)n, h->stream)) || (rc = put(h, h->fit.y[1], y2, (size_t)n, h->stream)))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.rows = n;
+  return NRV_OK;
+}
+
+int nrv_fit_get_rows_signal(nrv_handle* h, int64_t first, int64_t count, float* x2_1, float* x2_2, float* sig, uint8_t* y1, uint8_t* y2) {
+  static const char* who = "nrv_fit_get_rows_signal";
+  const int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (h->fit.depth != NRV_FIT_SIGNAL) return fit_refuse(h, who, fit_not_signal(h, false));
+  if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (count == 0) return NRV_OK;
+  const size_t K = fit_row_floats(h), KS = (size_t)h->T * kSig;
+  float* const xs[2] = {x2_1, x2_2};
+  uint8_t* const yy[2] = {y1, y2};
+  for (int m = 0; m < 2; ++m) {
+    if (xs[m]) HIPCHK(h, hipMemcpy(xs[m], h->fit.x2s[m] + (size_t)first * K, (size_t)count * K * 4, hipMemcpyDeviceToHost));
+    if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
+  }
+  if (sig) HIPCHK(h, hipMemcpy(sig, h->fit.sigs + (size_t)first * KS, (size_t)count * KS * 4, hipMemcpyDeviceToHost));
   return NRV_OK;
 }
 
@@ -4217,11 +4317,18 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
   else {
     const size_t src[4] = {d.fw, d.fb, d.ow, d.ob}, cnt[4] = {(size_t)16 * K, 16, (size_t)16 * C, (size_t)C};
     size_t at = 0;
-    if (h->fit.depth == NRV_FIT_LSTM3) {                    // tensors 34 .. 39, unfolded as the file has them
-      HIPCHK(h, hipMemcpyAsync(M.d_par, d.all + d.l3raw, (size_t)kL3N * 4, hipMemcpyDeviceToDevice, h->stream));
-      at = kL3N;
+    if (h->fit.depth == NRV_FIT_SIGNAL) {                   // tensors 0, 1 and 6, 7 out of the conv image, 32 and 33 as the file has them
+      HIPCHK(h, hipMemcpyAsync(M.d_par, d.all + d.conv, (size_t)32 * 4, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(M.d_par + kSgW2, d.all + d.conv + 48, (size_t)200 * 4, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(M.d_par + kSgWs, d.all + d.sdraw, (size_t)400 * 64 * 4, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(M.d_par + kSgBs, d.all + d.dbias, (size_t)64 * 4, hipMemcpyDeviceToDevice, h->stream));
+      at = kSgN;
     }
-    if (h->fit.depth == NRV_FIT_LSTM4 || h->fit.depth == NRV_FIT_LSTM3) {      // tensors 44 .. 49, unfolded as the file has them
+    if (h->fit.depth == NRV_FIT_LSTM3 || h->fit.depth == NRV_FIT_SIGNAL) {                    // tensors 34 .. 39, unfolded as the file has them
+      HIPCHK(h, hipMemcpyAsync(M.d_par + at, d.all + d.l3raw, (size_t)kL3N * 4, hipMemcpyDeviceToDevice, h->stream));
+      at += kL3N;
+    }
+    if (h->fit.depth >= NRV_FIT_LSTM4) {      // tensors 44 .. 49, unfolded as the file has them
       HIPCHK(h, hipMemcpyAsync(M.d_par + at, d.all + d.l4raw, (size_t)kL4N * 4, hipMemcpyDeviceToDevice, h->stream));
       at += kL4N;
     }
@@ -4290,10 +4397,20 @@ static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
   int rc;
   if (h->fit.depth) {
     wg = (size_t)fit_head_wgs(b_max);
-    if ((rc = fit_scratch(h, (void**)&h->fit.d_flag, &h->fit.cap_flag, (size_t)(kL3N / 256 + kL4N / 256 + (kHeadFitMaxP + 255) / 256) * 4))) return rc;
+    if ((rc = fit_scratch(h, (void**)&h->fit.d_flag, &h->fit.cap_flag,
+                          (size_t)(1 + (kSgDense + 255) / 256 + kL3N / 256 + kL4N / 256 + (kHeadFitMaxP + 255) / 256) * 4)))
+      return rc;
   }
   size_t pn = (size_t)fit_params_n(h, model);
-  if (h->fit.depth == NRV_FIT_LSTM3) {                       // one chunk's [H3 | XB | dX3 | CS | GZ], the lstm3 block's sums, the identity list
+  if (h->fit.depth == NRV_FIT_SIGNAL) {                      // one chunk's [Xin | F | dS], the conv block's partials, the dense block's sums
+    const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
+    if ((rc = fit_scratch(h, (void**)&h->fit.d_sg, &h->fit.cap_sg, rows * h->T * (grad ? 656 : 192) * 4)) ||
+        (grad && (rc = fit_scratch(h, (void**)&h->fit.d_pconv, &h->fit.cap_pconv, (rows * h->T + 31) / 32 * kSgConv * 4))) ||
+        (rc = fit_scratch(h, (void**)&h->fit.d_gdense, &h->fit.cap_gdense, (size_t)kSgDense * 4)))
+      return rc;
+    pn -= kSgN;
+  }
+  if (h->fit.depth == NRV_FIT_LSTM3 || h->fit.depth == NRV_FIT_SIGNAL) {                       // one chunk's [H3 | XB | dX3 | CS | GZ], the lstm3 block's sums, the identity list
     const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
     if ((rc = fit_scratch(h, (void**)&h->fit.d_l3, &h->fit.cap_l3, rows * h->T * (grad ? 2048 : 512) * 4)) ||
         (rc = fit_scratch(h, (void**)&h->fit.d_gl3, &h->fit.cap_gl3, (size_t)kL3N * 4)))
@@ -4306,7 +4423,7 @@ static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
     }
     pn -= kL3N;
   }
-  if (h->fit.depth == NRV_FIT_LSTM4 || h->fit.depth == NRV_FIT_LSTM3) {                       // one chunk's [X4 | dX4 | CS | GZ], the LSTM block's sums; partials of the head alone
+  if (h->fit.depth >= NRV_FIT_LSTM4) {                       // one chunk's [X4 | dX4 | CS | GZ], the LSTM block's sums; partials of the head alone
     const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
     if ((rc = fit_scratch(h, (void**)&h->fit.d_l4, &h->fit.cap_l4, rows * h->T * (grad ? 896 : 128) * 4)) ||
         (rc = fit_scratch(h, (void**)&h->fit.d_gl4, &h->fit.cap_gl4, (size_t)kL4N * 4)))
@@ -4329,11 +4446,13 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
   }
   nrv_handle::Fit::Model& M = h->fit.m[model];
   const int wg = fit_head_wgs(b), P = fit_params_n(h, model), blocks = (P + 255) / 256;
-  if (h->fit.depth == NRV_FIT_LSTM4 || h->fit.depth == NRV_FIT_LSTM3) {
+  if (h->fit.depth >= NRV_FIT_LSTM4) {
     const int T = h->T;
     const bool grad = mode != kTailEval;
-    const bool l3 = h->fit.depth == NRV_FIT_LSTM3;
-    const int o3 = l3 ? kL3N : 0;                           // where the lstm4 depth's vector starts
+    const bool sg = h->fit.depth == NRV_FIT_SIGNAL;
+    const bool l3 = sg || h->fit.depth == NRV_FIT_LSTM3;
+    const int os = sg ? kSgN : 0;                           // where the lstm3 depth's vector starts
+    const int o3 = os + (l3 ? kL3N : 0);                    // where the lstm4 depth's vector starts
     const DevModel& dmod = h->dm[model];
     const size_t rcap = (size_t)(b < kL4ChunkRows ? (b + 31) / 32 * 32 : kL4ChunkRows) * T;
     float* const x4 = h->fit.d_l4;                          // the four arrays of fit_step_scratch, dX4 .. GZ only with grad
@@ -4345,9 +4464,16 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
     float* const dx3 = l3 ? xb4 + rcap * 256 : nullptr;
     float* const cs3 = l3 ? dx3 + rcap * 256 : nullptr;
     float* const gz3 = l3 ? cs3 + rcap * 256 : nullptr;
+    float* const xin = h->fit.d_sg;                         // depth NRV_FIT_SIGNAL: the three arrays of fit_step_scratch, F and dS only with grad
+    float* const fkeep = sg ? xin + rcap * 192 : nullptr;
+    float* const ds = sg ? fkeep + rcap * 400 : nullptr;
+    const int sg_wg = sg ? ((b < kL4ChunkRows ? b : kL4ChunkRows) * T + 31) / 32 : 0;     // workgroups of sig_backward_kernel in the first chunk: the conv block's partials
     for (int c0 = 0; c0 < b; c0 += kL4ChunkRows) {
       const int bc = b - c0 < kL4ChunkRows ? b - c0 : kL4ChunkRows, tiles = (bc + 31) / 32;
-      const L3Args l3a{h->fit.xin[model], d_rows + c0, M.d_par, dmod.all + dmod.l_s[2], dmod.all + dmod.l_h[2], h3, xb4, gz3, cs3, dx3, gz,
+      const SigArgs sa{h->fit.x2s[model], h->fit.sigs, d_rows + c0, M.d_par, dmod.all + dmod.conv, xin, fkeep, ds, gz3, h->fit.d_pconv,
+                       h->fit.d_gdense, T, bc * T, grad ? 1 : 0, c0 > 0 ? 1 : 0};
+      if (sg) hipLaunchKernelGGL(sig_forward_kernel, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
+      const L3Args l3a{sg ? xin : h->fit.xin[model], sg ? h->fit.d_ident : d_rows + c0, M.d_par + os, dmod.all + dmod.l_s[2], dmod.all + dmod.l_h[2], h3, xb4, gz3, cs3, dx3, gz,
                        h->fit.d_gl3, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
       if (l3) {                                             // lstm3 forward: the scratch XB is "the set" of the lstm4 launches
         if (h->act == 0) hipLaunchKernelGGL(l3_forward_kernel<0>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
@@ -4375,22 +4501,38 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
         else hipLaunchKernelGGL(l3_backward_kernel<1>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
         hipLaunchKernelGGL(l3_wgrad_kernel, dim3(kL3WgM * kL3WgN, 2), dim3(256), 0, h->stream, l3a);
       }
+      if (sg) {
+        hipLaunchKernelGGL(l3_dx_kernel, dim3((bc * T + 31) / 32), dim3(128), 0, h->stream, sa);
+        hipLaunchKernelGGL(sig_backward_kernel, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
+        hipLaunchKernelGGL(sig_wgrad_kernel, dim3(kSgWgM, 2), dim3(512), 0, h->stream, sa);
+      }
     }
     // the LSTM block is one "partial" of its own; the head's partials behind it; the flags of both launches in one array
     // (at depth NRV_FIT_LSTM3 the lstm3 block is one more single "partial" in front)
-    const int o4 = o3 + kL4N, PH = P - o4, bl3 = o3 / 256, bl4 = kL4N / 256;
-    const HeadAdamArgs u0{h->fit.d_gl3, h->fit.d_pstat, 1, b, kL3N, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
-                          (HeadState*)M.d_state, h->fit.d_flag, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+    // (at depth NRV_FIT_SIGNAL the conv block's partials and the dense block in front of that; 25896 is no multiple of 256, so
+    // every reduce launch has a flag range of its own and the update launch has as many workgroups as there are flags)
+    const int o4 = o3 + kL4N, PH = P - o4, bl3 = l3 ? kL3N / 256 : 0, bl4 = kL4N / 256;
+    const int bls = sg ? 1 + (kSgDense + 255) / 256 : 0;
+    if (sg) {
+      const HeadAdamArgs uc{h->fit.d_pconv, h->fit.d_pstat, sg_wg, b, kSgConv, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
+                            (HeadState*)M.d_state, h->fit.d_flag, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+      const HeadAdamArgs ud{h->fit.d_gdense, h->fit.d_pstat, 1, b, kSgDense, mode, M.d_par + kSgWs, M.d_par + P + kSgWs, M.d_par + 2 * P + kSgWs,
+                            M.d_par + 3 * P + kSgWs, (HeadState*)M.d_state, h->fit.d_flag + 1, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+      hipLaunchKernelGGL(head_reduce_kernel, dim3(1), dim3(256), 0, h->stream, uc);
+      hipLaunchKernelGGL(head_reduce_kernel, dim3(bls - 1), dim3(256), 0, h->stream, ud);
+    }
+    const HeadAdamArgs u0{h->fit.d_gl3, h->fit.d_pstat, 1, b, kL3N, mode, M.d_par + os, M.d_par + P + os, M.d_par + 2 * P + os, M.d_par + 3 * P + os,
+                          (HeadState*)M.d_state, h->fit.d_flag + bls, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
     const HeadAdamArgs u1{h->fit.d_gl4, h->fit.d_pstat, 1, b, kL4N, mode, M.d_par + o3, M.d_par + P + o3, M.d_par + 2 * P + o3, M.d_par + 3 * P + o3,
-                          (HeadState*)M.d_state, h->fit.d_flag + bl3, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+                          (HeadState*)M.d_state, h->fit.d_flag + bls + bl3, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
     const HeadAdamArgs u2{h->fit.d_partial, h->fit.d_pstat, wg, b, PH, mode, M.d_par + o4, M.d_par + P + o4, M.d_par + 2 * P + o4,
-                          M.d_par + 3 * P + o4, (HeadState*)M.d_state, h->fit.d_flag + bl3 + bl4, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+                          M.d_par + 3 * P + o4, (HeadState*)M.d_state, h->fit.d_flag + bls + bl3 + bl4, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
     if (l3) hipLaunchKernelGGL(head_reduce_kernel, dim3(bl3), dim3(256), 0, h->stream, u0);
     const HeadAdamArgs u{h->fit.d_partial, h->fit.d_pstat, wg, b, P, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
                          (HeadState*)M.d_state, h->fit.d_flag, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
     hipLaunchKernelGGL(head_reduce_kernel, dim3(bl4), dim3(256), 0, h->stream, u1);
     hipLaunchKernelGGL(head_reduce_kernel, dim3((PH + 255) / 256), dim3(256), 0, h->stream, u2);
-    hipLaunchKernelGGL(head_adam_kernel, dim3(blocks), dim3(256), 0, h->stream, u);
+    hipLaunchKernelGGL(head_adam_kernel, dim3(sg ? bls + bl3 + bl4 + (PH + 255) / 256 : blocks), dim3(256), 0, h->stream, u);
     return;
   }
   HeadGradArgs a;

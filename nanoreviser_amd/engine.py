@@ -50,9 +50,11 @@ SYMBOLS = [
     "nrv_fit_set_depth", "nrv_fit_depth", "nrv_fit_set_rows_head", "nrv_fit_get_rows_head",
     "nrv_fit_set_rows_lstm4", "nrv_fit_get_rows_lstm4",
     "nrv_fit_set_rows_lstm3", "nrv_fit_get_rows_lstm3",
+    "nrv_fit_set_rows_signal", "nrv_fit_get_rows_signal",
 ]
 FIT_TAIL, FIT_HEAD, FIT_LSTM4 = 0, 1, 4    # NRV_FIT_TAIL, NRV_FIT_HEAD, NRV_FIT_LSTM4 (the Bi-LSTM the fit starts at)
 FIT_LSTM3 = 8                              # NRV_FIT_LSTM3
+FIT_SIGNAL = 16                            # NRV_FIT_SIGNAL
 FIT_MAX_BATCH = 65536               # NRV_FIT_MAX_BATCH
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 PROFILE_COLS = 48                   # NRV_PROFILE_COLS
@@ -186,6 +188,8 @@ _FIT_T = {                                                                      
     "nrv_fit_get_rows_lstm4": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
     "nrv_fit_set_rows_lstm3": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
     "nrv_fit_get_rows_lstm3": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
+    "nrv_fit_set_rows_signal": [C.c_void_p, _FP, _FP, _FP, _U8P, _U8P, C.c_int64],
+    "nrv_fit_get_rows_signal": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _FP, _U8P, _U8P],
 }
 
 
@@ -874,14 +878,15 @@ class Reviser:
     def fit_n_params(self, model) -> int:
         """The length of a model's parameter vector at the current depth."""
         c = self._n_class(model)
-        front = {FIT_TAIL: 0, FIT_HEAD: 20838, FIT_LSTM4: 164352 + 20838, FIT_LSTM3: 328704 + 164352 + 20838}[self.fit_depth()]
+        front = {FIT_TAIL: 0, FIT_HEAD: 20838, FIT_LSTM4: 164352 + 20838, FIT_LSTM3: 328704 + 164352 + 20838,
+                 FIT_SIGNAL: 25896 + 328704 + 164352 + 20838}[self.fit_depth()]
         return front + 96 * self.T + 16 + 16 * c + c + 16 * c
 
     # ---- the second depth (nanoreviser_amd/headfit.py is the definition): the set holds lstm4 outputs [T][128] per window
     def fit_set_depth(self, depth):
-        """FIT_TAIL / FIT_HEAD / FIT_LSTM4 / FIT_LSTM3 (or "tail" / "head" / "lstm4" / "lstm3"), on an empty set only; forgets
-        any fit_begin."""
-        depth = {"tail": FIT_TAIL, "head": FIT_HEAD, "lstm4": FIT_LSTM4, "lstm3": FIT_LSTM3}.get(depth, depth)
+        """FIT_TAIL / FIT_HEAD / FIT_LSTM4 / FIT_LSTM3 / FIT_SIGNAL (or "tail" / "head" / "lstm4" / "lstm3" / "signal"), on an
+        empty set only; forgets any fit_begin."""
+        depth = {"tail": FIT_TAIL, "head": FIT_HEAD, "lstm4": FIT_LSTM4, "lstm3": FIT_LSTM3, "signal": FIT_SIGNAL}.get(depth, depth)
         self._check(self._lib.nrv_fit_set_depth(self._h, int(depth)))
 
     def fit_depth(self) -> int:
@@ -941,6 +946,27 @@ class Reviser:
         out = (np.empty(sh, np.float32), np.empty(sh, np.float32), np.empty(count, np.uint8), np.empty(count, np.uint8))
         self._check(self._lib.nrv_fit_get_rows_lstm3(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _U8P),
                                                      _ptr(out[3], _U8P)))
+        return out
+
+    # ---- the fifth depth (nanoreviser_amd/signalfit.py is the definition): the set holds lstm2 outputs [T][128] per model and
+    # ONE array of samples [T][50] for both
+    def fit_set_rows_signal(self, x2_1, x2_2, sig, y1, y2):
+        a1, a2, sg = _as_f32(x2_1, (self.T, 128)), _as_f32(x2_2, (self.T, 128)), _as_f32(sig, (self.T, 50))
+        a, b = (np.ascontiguousarray(v, dtype=np.uint8).reshape(-1) for v in (y1, y2))
+        n = a1.shape[0]
+        if a2.shape[0] != n or sg.shape[0] != n or a.size != n or b.size != n:
+            raise ValueError("x2_1 / x2_2 / sig / y1 / y2 must have one entry per row")
+        self._check(self._lib.nrv_fit_set_rows_signal(self._h, _ptr(a1, _FP), _ptr(a2, _FP), _ptr(sg, _FP), _ptr(a, _U8P),
+                                                      _ptr(b, _U8P), n))
+
+    def fit_get_rows_signal(self, first=0, count=None):
+        """-> (x2_1, x2_2, sig, y1, y2) of rows [first, first + count), x2 [count][T][128], sig [count][T][50]."""
+        count = self.fit_count() - first if count is None else count
+        sh = (count, self.T, 128)
+        out = (np.empty(sh, np.float32), np.empty(sh, np.float32), np.empty((count, self.T, 50), np.float32),
+               np.empty(count, np.uint8), np.empty(count, np.uint8))
+        self._check(self._lib.nrv_fit_get_rows_signal(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _FP),
+                                                      _ptr(out[3], _U8P), _ptr(out[4], _U8P)))
         return out
 
     @staticmethod

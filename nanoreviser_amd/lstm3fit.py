@@ -114,6 +114,13 @@ def forward(Xin, theta, sc, sh, T: int, C: int, act: int = 0, dtype=np.float64):
 
 def batch_terms(Xin, y, theta, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64):
     """One batch -> (g [P]: the gradient of L, FitStats of the batch with steps = nonfinite = 0)."""
+    return batch_terms_dx(Xin, y, theta, sc, sh, T, C, opts, act, dtype)[:2]
+
+
+def batch_terms_dx(Xin, y, theta, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64):
+    """batch_terms and the data gradient behind it -> (g, FitStats, dXin [n][T][192]: the sum over both directions (forward
+    first) and all steps of dz3 W3^T - the derivative of the batch's SUM of row losses, not divided by n).  signalfit.py goes on
+    from its columns 128 .. 191."""
     dt = np.dtype(dtype)
     theta = np.asarray(theta)
     Xin, H3, keep = lstm(Xin, theta, T, C, act, dt)
@@ -123,8 +130,9 @@ def batch_terms(Xin, y, theta, sc, sh, T: int, C: int, opts: FitOpts, act: int =
     parts = [a.astype(dt) for a in unpack(theta, T, C)[:6]]
     one = dt.type(1)
     grads = []
+    dXin = np.zeros((n, T, D_X), dt)
     for d in range(2):
-        U = parts[3 * d + 1]
+        W, U = parts[3 * d], parts[3 * d + 1]
         k = keep[d]
         gW, gU, gb = np.zeros((D_X, 4 * H), dt), np.zeros((H, 4 * H), dt), np.zeros(4 * H, dt)
         dz_next = np.zeros((n, 4 * H), dt)
@@ -143,11 +151,12 @@ def batch_terms(Xin, y, theta, sc, sh, T: int, C: int, opts: FitOpts, act: int =
             gW += Xin[:, t].T @ dz
             gU += h_prev.T @ dz
             gb += dz.sum(axis=0)
+            dXin[:, t] += dz @ W.T
             dcf = dc * f
             dz_next = dz
         grads += [gW, gU, gb]
     g = np.concatenate([a.ravel() for a in grads]) / dt.type(n)
-    return np.concatenate([g.astype(dt), g4]), st
+    return np.concatenate([g.astype(dt), g4]), st, dXin
 
 
 def epoch(Xin, y, state: FitState, order, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64) -> FitStats:

@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
-"""Time nrv_fit_epoch at the four fit depths (tail: tensors 56 .. 59; head: tensors 50 .. 59; lstm4: tensors 44 .. 59; lstm3:
-tensors 34 .. 39 and 44 .. 59) on the device.  A plain script: it takes no part in bench.py and sets no bar.
+"""Time nrv_fit_epoch at the five fit depths (tail: tensors 56 .. 59; head: tensors 50 .. 59; lstm4: tensors 44 .. 59; lstm3:
+tensors 34 .. 39 and 44 .. 59; signal: tensors 0, 1, 6, 7, 32 .. 39 and 44 .. 59) on the device.  A plain script: it takes no part in bench.py and sets no bar.
 
-A set of seeded rows goes in through the unit doors (nrv_fit_set_rows / _head / _lstm4 / _lstm3), so the frozen backbone never
+A set of seeded rows goes in through the unit doors (nrv_fit_set_rows / _head / _lstm4 / _lstm3 / _signal), so the frozen backbone never
 runs: what is timed is one whole nrv_fit_epoch call - the upload of the row order, every batch's launches enqueued back to back
 and the one synchronise at the end - by a host clock around the call, which returns only after that synchronise.  Per depth:
 untimed epochs first (first launches load code objects and size the scratch buffers), then --repeats timed epochs; the median
 and the spread (min .. max) are printed as rows/s, then one JSON line with everything.
 
-    python tools/fit_bench.py [--rows 65536] [-b 512] [-w 11] [--warmup 3] [--repeats 9] [--model 0] [--depths tail,head,lstm4,lstm3]
+    python tools/fit_bench.py [--rows 65536] [-b 512] [-w 11] [--warmup 3] [--repeats 9] [--model 0] [--depths tail,head,lstm4,lstm3,signal]
 """
 import argparse
 import json
@@ -39,7 +39,14 @@ def flop_per_row(depth, T, C):
     # lstm3 depth: the lstm4 depth with its data gradient dXb4 = dz4 W4^T; lstm3's two forward products, its recurrent data
     # gradient and its two weight-gradient products, per direction
     lstm3 = 2 * T * 2 * (192 * 512 + 128 * 512)
-    return l4 + 2 * T * 2 * 256 * 256 + 2 * lstm3 + 2 * T * 2 * 128 * 512
+    l3 = l4 + 2 * T * 2 * 256 * 256 + 2 * lstm3 + 2 * T * 2 * 128 * 512
+    if depth == "lstm3":
+        return l3
+    # signal depth: the lstm3 depth with the 64 signal columns of dXin = dz3 W3^T (both directions); per (row, t) the two
+    # convolutions and the 400 -> 64 product forward, gWs = F^T dS, dF = dS Ws^T, conv2's weight and data gradient and conv1's
+    # weight gradient; the backward launch's recomputation of a1, c1 and a2 is NOT counted
+    conv1, conv2, dense = 50 * 8 * 3, 50 * 8 * 24, 400 * 64
+    return l3 + 2 * T * (2 * 512 * 64 + (conv1 + conv2 + dense) + 2 * dense + 2 * conv2 + conv1)
 
 
 def main(argv=None):
@@ -52,9 +59,9 @@ def main(argv=None):
     ap.add_argument("--model", type=int, default=0, choices=(0, 1))
     ap.add_argument("--species", default="ecoli")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--depths", default="tail,head,lstm4,lstm3", help="the depths to time, in this order")
+    ap.add_argument("--depths", default="tail,head,lstm4,lstm3", help="the depths to time, in this order (signal is not in the default)")
     a = ap.parse_args(argv)
-    from nanoreviser_amd import headfit, lstm3fit, lstm4fit, tailfit
+    from nanoreviser_amd import headfit, lstm3fit, lstm4fit, signalfit, tailfit
     from nanoreviser_amd.engine import Reviser
     from nanoreviser_amd.weights import load_species
     T, k, n = a.window_size, a.model, a.rows
@@ -78,6 +85,12 @@ def main(argv=None):
                 F = np.maximum(rng.normal(0, 1, (n, 6 * T)), 0).astype(np.float32)
                 rv.fit_set_rows(F, F, y1, y2)
                 th = tailfit.fresh_params(T, C, a.seed)
+            elif depth == "signal":                        # the shipped signal branch, lstm3 and lstm4 in front of a fresh head
+                X = rng.normal(0, 1, (n, T, 128)).astype(np.float32)
+                rv.fit_set_rows_signal(X, X, rng.normal(0, 1, (n, T, 50)).astype(np.float32), y1, y2)
+                m = (m1, m2)[k].with_window(T)
+                th4 = lstm4fit.with_head(lstm4fit.params_from_model(m), headfit.fresh_params(T, C, a.seed))
+                th = signalfit.with_lstm3(signalfit.params_from_model(m), lstm3fit.with_lstm4(lstm3fit.params_from_model(m), th4))
             elif depth == "lstm3":                         # the shipped lstm3 and lstm4 in front of a fresh head
                 X = rng.normal(0, 1, (n, T, 192)).astype(np.float32)
                 rv.fit_set_rows_lstm3(X, X, y1, y2)
