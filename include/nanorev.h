@@ -895,6 +895,40 @@ int nrv_fit_set_rows_signal(nrv_handle* h, const float* x2_1, const float* x2_2,
                             int64_t n);
 int nrv_fit_get_rows_signal(nrv_handle* h, int64_t first, int64_t count, float* x2_1, float* x2_2, float* sig, uint8_t* y1, uint8_t* y2);
 
+/* ---- Fitting the read branch too - the whole model: the sixth and last DEPTH of nrv_fit_* (opt-in) ----
+ * At depth NRV_FIT_FULL lstm1 - the 6 -> 16 Bi-LSTM on the read features, tensors 12 .. 17, 2944 weights - and lstm2 - the 32 -> 64
+ * Bi-LSTM behind it, tensors 22 .. 27, 49664 weights - are fitted with everything the signal depth fits: every tensor of the 60
+ * that is no BatchNorm's has a gradient on the device.  nanoreviser_amd/fullfit.py is the definition.  Frozen: the five
+ * BatchNorms (2 .. 5, 8 .. 11, 18 .. 21, 28 .. 31, 40 .. 43).  THE STATED DEVIATIONS are the signal depth's, with bn_l1 and bn_l2
+ * under the first: X1b = h1 * s_l1 + h_l1 and X2b = h2 * s_l2 + h_l2 from the moving statistics as the handle holds them (one f32
+ * multiply and one f32 add), where Keras in training phase would normalise with the batch's statistics and fit gamma and beta;
+ * Dropout is not applied.  The constant is 32: 18 .. 31 and 33 are refused, and everything refused before stays refused.
+ *   nrv_fit_set_depth  takes NRV_FIT_FULL under the rules above.
+ * THE SET at this depth.  ONE sig f32 [rows][T][50] and ONE feat f32 [rows][T][6] for both models - the window's raw inputs, what
+ * nrv_predict* takes; both models read the same - and the same y arrays: 224 T bytes per row.  The depth's own cap is
+ * NRV_FIT_MAX_FULL_ROWS (environment, read by nrv_create; default 2^22, 10.3 GB at T = 11); a call that would pass it is refused
+ * whole, by that name.
+ *   nrv_fit_add_reads_raw  unchanged signature and label rule.  Nothing of the set depends on the network, so no launch group
+ *     runs: behind the segmentation of a stage, one gather moves every labelled window's T x 50 samples and T x 6 features out of
+ *     the stage's event-major arrays (window w, step t is event w + t; 8 bytes at a time) to the window's slot, with plain
+ *     stores.  The set is the same bytes in every precision mode.
+ *   nrv_fit_set_rows_full / nrv_fit_get_rows_full  the unit doors.  Each depth's doors are refused at the other depths under
+ *     their own names; the handle stays usable.
+ * THE FIT.  One vector of NRV_FIT_PARAMS_FULL(T, C) = 52608 + NRV_FIT_PARAMS_SIGNAL(T, C) floats:
+ *   [W1f [6][64] | U1f [16][64] | b1f [64] | W1b | U1b | b1b | W2f [32][256] | U2f [64][256] | b2f [256] | W2b | U2b | b2b |
+ *    the signal depth's vector]        kernels row-major [in][out], gate columns i, f, c, o, tensors as the weight file has them.
+ * params NULL: the handle's own tensors as the file has them, no BatchNorm folded in, and zero centres.  Forward: lstm1 and lstm2
+ * by the lstm3 depth's step rule (the backward direction walks t = T - 1 .. 0), Xin = [X2b | S], then the signal depth's forward
+ * and loss.  Backward: the signal depth's, with ALL 192 columns of dXin = sum over both directions, forward first, of dz3 W3^T;
+ * dH2 = dXin[.., :128] s_l2, back through time in lstm2, dH1 = (sum over both directions of dz2 W2^T) s_l1, back through time in
+ * lstm1; gW = sum x_t^T dz, gU = sum h_{s-1}^T dz (bytes of zero at T = 1), gb = sum dz (csrc/nrv_fullfit.h).  Chunks, finite check
+ * over the whole vector and ONE Adam launch as at signal depth; no atomics, the same calls give the same bytes.  nrv_fit_eval runs
+ * the forward launches alone. */
+#define NRV_FIT_FULL 32
+#define NRV_FIT_PARAMS_FULL(T, C) (52608 + NRV_FIT_PARAMS_SIGNAL(T, C))
+int nrv_fit_set_rows_full(nrv_handle* h, const float* sig, const float* feat, const uint8_t* y1, const uint8_t* y2, int64_t n);
+int nrv_fit_get_rows_full(nrv_handle* h, int64_t first, int64_t count, float* sig, float* feat, uint8_t* y1, uint8_t* y2);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

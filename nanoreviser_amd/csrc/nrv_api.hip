@@ -7,6 +7,7 @@
 #include "nrv_lstm4fit.h"     // ... at depth NRV_FIT_LSTM4: BatchNorm'd lstm3 outputs as the set, the last Bi-LSTM's forward and backward
 #include "nrv_lstm3fit.h"     // ... at depth NRV_FIT_LSTM3: lstm3's inputs as the set, the 192->128 Bi-LSTM's forward and backward, dX out of lstm4
 #include "nrv_signalfit.h"    // ... at depth NRV_FIT_SIGNAL: lstm2's outputs and the samples as the set, the signal branch's forward and backward, dS out of lstm3
+#include "nrv_fullfit.h"      // ... at depth NRV_FIT_FULL: the raw windows as the set, lstm1 and lstm2 forward and backward, all of dXin out of lstm3
 #include "nrv_block.h"
 
 #include <algorithm>
@@ -464,6 +465,7 @@ struct DevModel {
   size_t d1p, d1b, d2p, d2b, mop, mob, fw, fb, ow, ob;
   size_t l3raw = 0;           // tensors 34 .. 39 as the file has them (... at depth NRV_FIT_LSTM3)
   size_t sdraw = 0;           // tensor 32 as the file has it (... at depth NRV_FIT_SIGNAL)
+  size_t l1raw = 0, l2raw = 0;   // tensors 12 .. 17 and 22 .. 27 as the file has them (... at depth NRV_FIT_FULL)
   size_t l4raw = 0;           // tensors 44 .. 49 as the file has them (nrv_fit_begin at depth NRV_FIT_LSTM4 starts from them)
   size_t h_ws, h_wb;          // head_mlp_split_kernel: split weights / biases
   // f16x2 mode (nrv_lstm_f16x2.h): lstm2..4 weights as two f16 terms, scaled biases, output scale /
@@ -711,6 +713,13 @@ struct nrv_handle {
     float* d_sg = nullptr; size_t cap_sg = 0;
     float* d_pconv = nullptr; size_t cap_pconv = 0;           // [workgroups][kSgConv]
     float* d_gdense = nullptr; size_t cap_gdense = 0;         // [kSgDense]
+    // depth NRV_FIT_FULL: the set is ONE sig [cap][T][50] (sigs) and ONE feat [cap][T][6] for both models and y; one chunk's
+    // [X1b | H1 | H2 | dH2 | dH1 | CS1 | CS2 | GZ1 | GZ2] (nrv_fullfit.h) in front of the signal depth's scratch, the read
+    // block's kRdSlices partials
+    float* feats = nullptr;
+    int64_t max_full_rows = (int64_t)1 << 22;                 // NRV_FIT_MAX_FULL_ROWS, read by nrv_create
+    float* d_rd = nullptr; size_t cap_rd = 0;
+    float* d_grd = nullptr; size_t cap_grd = 0;               // [kRdSlices][kRdN]
     int* d_flag = nullptr; size_t cap_flag = 0;               // head_reduce_kernel's per-workgroup flags
     float* d_partial = nullptr; size_t cap_partial = 0;       // [workgroups][P]
     TailStat* d_pstat = nullptr; size_t cap_pstat = 0;        // [workgroups]
@@ -817,6 +826,13 @@ NRV_HOST_COLD static int upload_model(nrv_handle* h, int mi, const Blob& b, int 
     static const size_t n4[6] = {256 * 256, 64 * 256, 256, 256 * 256, 64 * 256, 256};
     d.l4raw = put(b.t(44), n4[0]);
     for (int i = 1; i < 6; ++i) (void)put(b.t(44 + i), n4[i]);
+  }
+  {
+    static const size_t n1[3] = {6 * 64, 16 * 64, 64}, n2[3] = {32 * 256, 64 * 256, 256};
+    d.l1raw = put(b.t(12), n1[0]);
+    for (int i = 1; i < 6; ++i) (void)put(b.t(12 + i), n1[i % 3]);
+    d.l2raw = put(b.t(22), n2[0]);
+    for (int i = 1; i < 6; ++i) (void)put(b.t(22 + i), n2[i % 3]);
   }
   std::vector<float> wp, bs;
   pack_dense16(b.t(32), 400, 64, wp);
@@ -1605,6 +1621,7 @@ int nrv_create(const nrv_weights* m1, const nrv_weights* m2, int T, int device, 
   if (const char* e6 = getenv("NRV_LABELS_BUDGET"); e6 && *e6) { const long long v = atoll(e6); if (v > 0) h->lab_budget = (size_t)v; }
   if (const char* e7 = getenv("NRV_FIT_MAX_ROWS"); e7 && *e7) { const long long v = atoll(e7); if (v > 0) h->fit.max_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e9 = getenv("NRV_FIT_MAX_LSTM4_ROWS"); e9 && *e9) { const long long v = atoll(e9); if (v > 0) h->fit.max_lstm4_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
+  if (const char* e12 = getenv("NRV_FIT_MAX_FULL_ROWS"); e12 && *e12) { const long long v = atoll(e12); if (v > 0) h->fit.max_full_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e11 = getenv("NRV_FIT_MAX_SIGNAL_ROWS"); e11 && *e11) { const long long v = atoll(e11); if (v > 0) h->fit.max_signal_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e10 = getenv("NRV_FIT_MAX_LSTM3_ROWS"); e10 && *e10) { const long long v = atoll(e10); if (v > 0) h->fit.max_lstm3_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
   if (const char* e8 = getenv("NRV_FIT_MAX_HEAD_ROWS"); e8 && *e8) { const long long v = atoll(e8); if (v > 0) h->fit.max_head_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
@@ -1648,6 +1665,7 @@ void nrv_destroy(nrv_handle* h) {
   (void)hipFree(h->fit.d_partial); (void)hipFree(h->fit.d_pstat); (void)hipFree(h->fit.d_order); (void)hipFree(h->fit.d_p); (void)hipFree(h->fit.d_flag);
   (void)hipFree(h->fit.d_l4); (void)hipFree(h->fit.d_gl4);
   (void)hipFree(h->fit.d_l3); (void)hipFree(h->fit.d_gl3); (void)hipFree(h->fit.d_ident);
+  (void)hipFree(h->fit.feats); (void)hipFree(h->fit.d_rd); (void)hipFree(h->fit.d_grd);
   (void)hipFree(h->fit.sigs); (void)hipFree(h->fit.d_sg); (void)hipFree(h->fit.d_pconv); (void)hipFree(h->fit.d_gdense);
   for (int st = 0; st < nrv_handle::kIn; ++st) if (h->ev_in[st]) (void)hipEventDestroy(h->ev_in[st]);
   for (int st = 0; st < 2; ++st) {
@@ -3775,19 +3793,21 @@ static int fit_scratch(nrv_handle* h, void** p, size_t* cap, size_t bytes) {
 }
 // floats of one row of the set at the handle's depth, and the parameters of a model's vector
 static size_t fit_row_floats(const nrv_handle* h) {
+  if (h->fit.depth == NRV_FIT_FULL) return 0;                              // (no per-model rows: the shared samples and features only)
   if (h->fit.depth == NRV_FIT_SIGNAL) return (size_t)h->T * 128;          // (per model; the shared samples are T * 50 more)
   if (h->fit.depth == NRV_FIT_LSTM3) return (size_t)h->T * 192;
   return h->fit.depth == NRV_FIT_LSTM4 ? (size_t)h->T * 256 : h->fit.depth ? (size_t)h->T * 128 : 6 * (size_t)h->T;
 }
 static int fit_params_n(const nrv_handle* h, int model) {
   const int C = h->dm[model].C;
+  if (h->fit.depth == NRV_FIT_FULL) return NRV_FIT_PARAMS_FULL(h->T, C);
   if (h->fit.depth == NRV_FIT_SIGNAL) return NRV_FIT_PARAMS_SIGNAL(h->T, C);
   if (h->fit.depth == NRV_FIT_LSTM3) return NRV_FIT_PARAMS_LSTM3(h->T, C);
   return h->fit.depth == NRV_FIT_LSTM4 ? NRV_FIT_PARAMS_LSTM4(h->T, C) : h->fit.depth ? NRV_FIT_PARAMS_HEAD(h->T, C) : NRV_FIT_PARAMS(h->T, C);
 }
 // the current depth's set and its cap
 static float** fit_set(nrv_handle::Fit& F) { return F.depth == NRV_FIT_SIGNAL ? F.x2s : F.depth == NRV_FIT_LSTM3 ? F.xin : F.depth == NRV_FIT_LSTM4 ? F.xb : F.depth ? F.x4 : F.flat; }
-static int64_t fit_cap_rows(const nrv_handle::Fit& F) { return F.depth == NRV_FIT_SIGNAL ? F.max_signal_rows : F.depth == NRV_FIT_LSTM3 ? F.max_lstm3_rows : F.depth == NRV_FIT_LSTM4 ? F.max_lstm4_rows : F.depth ? F.max_head_rows : F.max_rows; }
+static int64_t fit_cap_rows(const nrv_handle::Fit& F) { return F.depth == NRV_FIT_FULL ? F.max_full_rows : F.depth == NRV_FIT_SIGNAL ? F.max_signal_rows : F.depth == NRV_FIT_LSTM3 ? F.max_lstm3_rows : F.depth == NRV_FIT_LSTM4 ? F.max_lstm4_rows : F.depth ? F.max_head_rows : F.max_rows; }
 // room for `need` rows in the set, the rows it holds kept
 static int fit_reserve(nrv_handle* h, int64_t need) {
   nrv_handle::Fit& F = h->fit;
@@ -3800,27 +3820,39 @@ static int fit_reserve(nrv_handle* h, int64_t need) {
   float** const set = fit_set(F);
   float* nf[2] = {nullptr, nullptr};
   uint8_t* ny[2] = {nullptr, nullptr};
-  float* nsig = nullptr;                                   // depth NRV_FIT_SIGNAL: the samples both models share
+  float* nsig = nullptr;                                   // depth NRV_FIT_SIGNAL and NRV_FIT_FULL: the samples both models share
+  float* nfeat = nullptr;                                  // depth NRV_FIT_FULL: the features both models share
+  const bool full = F.depth == NRV_FIT_FULL;
   int rc = NRV_OK;
-  if (F.depth == NRV_FIT_SIGNAL) {
+  if (full) {
+    const size_t KF = (size_t)h->T * kFeat;
+    if (hipMalloc((void**)&nfeat, (size_t)c * KF * 4) != hipSuccess) { h->err = "nrv_fit: out of device memory for the training set"; return NRV_E_NOMEM; }
+    if ((rc = poison_fill(h, nfeat, (size_t)c * KF * 4, h->stream))) { (void)hipFree(nfeat); return rc; }
+    if (F.rows > 0 && hipMemcpyAsync(nfeat, F.feats, (size_t)F.rows * KF * 4, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
+      h->err = "nrv_fit: copying the training set failed";
+      (void)hipFree(nfeat);
+      return NRV_E_HIP;
+    }
+  }
+  if (F.depth == NRV_FIT_SIGNAL || full) {
     const size_t KS = (size_t)h->T * kSig;
-    if (hipMalloc((void**)&nsig, (size_t)c * KS * 4) != hipSuccess) { h->err = "nrv_fit: out of device memory for the training set"; return NRV_E_NOMEM; }
-    if ((rc = poison_fill(h, nsig, (size_t)c * KS * 4, h->stream))) { (void)hipFree(nsig); return rc; }
+    if (hipMalloc((void**)&nsig, (size_t)c * KS * 4) != hipSuccess) { h->err = "nrv_fit: out of device memory for the training set"; (void)hipFree(nfeat); return NRV_E_NOMEM; }
+    if ((rc = poison_fill(h, nsig, (size_t)c * KS * 4, h->stream))) { (void)hipFree(nsig); (void)hipFree(nfeat); return rc; }
     if (F.rows > 0 && hipMemcpyAsync(nsig, F.sigs, (size_t)F.rows * KS * 4, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
       h->err = "nrv_fit: copying the training set failed";
-      (void)hipFree(nsig);
+      (void)hipFree(nsig); (void)hipFree(nfeat);
       return NRV_E_HIP;
     }
   }
   for (int m = 0; m < 2 && !rc; ++m) {
-    if (hipMalloc((void**)&nf[m], (size_t)c * K * 4) != hipSuccess || hipMalloc((void**)&ny[m], ((size_t)c + 3) / 4 * 4) != hipSuccess) {
+    if ((!full && hipMalloc((void**)&nf[m], (size_t)c * K * 4) != hipSuccess) || hipMalloc((void**)&ny[m], ((size_t)c + 3) / 4 * 4) != hipSuccess) {
       h->err = "nrv_fit: out of device memory for the training set";
       rc = NRV_E_NOMEM;
       break;
     }
-    if ((rc = poison_fill(h, nf[m], (size_t)c * K * 4, h->stream)) || (rc = poison_fill(h, ny[m], ((size_t)c + 3) / 4 * 4, h->stream))) break;
+    if ((!full && (rc = poison_fill(h, nf[m], (size_t)c * K * 4, h->stream))) || (rc = poison_fill(h, ny[m], ((size_t)c + 3) / 4 * 4, h->stream))) break;
     if (F.rows > 0) {
-      if (hipMemcpyAsync(nf[m], set[m], (size_t)F.rows * K * 4, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
+      if ((!full && hipMemcpyAsync(nf[m], set[m], (size_t)F.rows * K * 4, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) ||
           hipMemcpyAsync(ny[m], F.y[m], (size_t)F.rows, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
         h->err = "nrv_fit: copying the training set failed";
         rc = NRV_E_HIP;
@@ -3830,13 +3862,17 @@ static int fit_reserve(nrv_handle* h, int64_t need) {
   if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) { h->err = "nrv_fit: growing the training set failed"; rc = NRV_E_HIP; }
   if (rc) {
     for (int m = 0; m < 2; ++m) { (void)hipFree(nf[m]); (void)hipFree(ny[m]); }
-    (void)hipFree(nsig);
+    (void)hipFree(nsig); (void)hipFree(nfeat);
     return rc;
   }
-  if (F.depth == NRV_FIT_SIGNAL) { (void)hipFree(F.sigs); F.sigs = nsig; }
+  if (F.depth == NRV_FIT_SIGNAL || full) { (void)hipFree(F.sigs); F.sigs = nsig; }
+  if (full) { (void)hipFree(F.feats); F.feats = nfeat; }
   for (int m = 0; m < 2; ++m) {
-    (void)hipFree(set[m]); (void)hipFree(F.y[m]);
-    set[m] = nf[m]; F.y[m] = ny[m];
+    (void)hipFree(F.y[m]);
+    F.y[m] = ny[m];
+    if (full) continue;
+    (void)hipFree(set[m]);
+    set[m] = nf[m];
   }
   F.cap = c;
   return NRV_OK;
@@ -3855,6 +3891,13 @@ static int fit_enqueue(nrv_handle* h, const char* d_in, size_t off_starts, size_
     if (rc0) return rc0;
     launch_segment(h, n_reads, s, nb + T - 1, h->d_sig[0], (const int16_t*)d_in, (const int32_t*)(d_in + off_starts),
                    (const SegRead*)(d_in + off_reads));
+    if (h->fit.depth == NRV_FIT_FULL) {                    // the set is the stage's raw inputs: no launch group runs for it
+      const FullGatherArgs g{h->d_sig[0], d_feat + s * kFeat, h->fit.sigs, h->fit.feats, d_slot + s, nb, T, (long long)h->fit.cap};
+      const long long total = (long long)nb * T * 28;
+      hipLaunchKernelGGL(full_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, g);
+      HIPCHK(h, hipGetLastError());
+      continue;
+    }
     const int rc = for_groups(h, nb, [&](int64_t w, int nw) -> int {
       if (h->fit.depth == NRV_FIT_LSTM3 || h->fit.depth == NRV_FIT_SIGNAL) {                 // the gather runs INSIDE the group, between lstm2 and lstm4
         h->fit.l3_slot = d_slot + s + w;
@@ -3936,6 +3979,8 @@ int nrv_fit_add_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, cons
     for (int64_t i = 0; i < n_r; ++i) add += lb[i] != 0xFF && (lb[i] & 7) >= 1 && (lb[i] & 7) <= 5;
   }
   nrv_handle::Fit& F = h->fit;
+  if (F.depth == NRV_FIT_FULL && F.rows + add > F.max_full_rows)
+    return fit_refuse(h, who, "the call would pass the row cap of the training set at full depth (NRV_FIT_MAX_FULL_ROWS)");
   if (F.depth == NRV_FIT_SIGNAL && F.rows + add > F.max_signal_rows)
     return fit_refuse(h, who, "the call would pass the row cap of the training set at signal depth (NRV_FIT_MAX_SIGNAL_ROWS)");
   if (F.depth == NRV_FIT_LSTM3 && F.rows + add > F.max_lstm3_rows)
@@ -3996,6 +4041,7 @@ int nrv_fit_set_rows(nrv_handle* h, const float* flat1, const float* flat2, cons
   static const char* who = "nrv_fit_set_rows";
   int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_FULL) return fit_refuse(h, who, "the set is at full depth (rows are samples and read features: nrv_fit_set_rows_full)");
   if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_set_rows_signal)");
   if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)");
@@ -4021,6 +4067,7 @@ int nrv_fit_get_rows(nrv_handle* h, int64_t first, int64_t count, float* flat1, 
   static const char* who = "nrv_fit_get_rows";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_FULL) return fit_refuse(h, who, "the set is at full depth (rows are samples and read features: nrv_fit_get_rows_full)");
   if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_get_rows_signal)");
   if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)");
@@ -4047,8 +4094,8 @@ int nrv_fit_set_depth(nrv_handle* h, int depth) {
   static const char* who = "nrv_fit_set_depth";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
-  if (depth != NRV_FIT_TAIL && depth != NRV_FIT_HEAD && depth != NRV_FIT_LSTM4 && depth != NRV_FIT_LSTM3 && depth != NRV_FIT_SIGNAL)
-    return fit_refuse(h, who, "depth must be NRV_FIT_TAIL or NRV_FIT_HEAD, or NRV_FIT_LSTM4, or NRV_FIT_LSTM3, or NRV_FIT_SIGNAL");
+  if (depth != NRV_FIT_TAIL && depth != NRV_FIT_HEAD && depth != NRV_FIT_LSTM4 && depth != NRV_FIT_LSTM3 && depth != NRV_FIT_SIGNAL && depth != NRV_FIT_FULL)
+    return fit_refuse(h, who, "depth must be NRV_FIT_TAIL or NRV_FIT_HEAD, or NRV_FIT_LSTM4, or NRV_FIT_LSTM3, or NRV_FIT_SIGNAL, or NRV_FIT_FULL");
   nrv_handle::Fit& F = h->fit;
   if (F.rows != 0) return fit_refuse(h, who, "the training set is not empty (call nrv_fit_reset first)");
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -4065,6 +4112,7 @@ int nrv_fit_set_depth(nrv_handle* h, int depth) {
     F.m[m].d_par = nullptr; F.m[m].d_state = nullptr;
   }
   (void)hipFree(F.sigs); F.sigs = nullptr;
+  (void)hipFree(F.feats); F.feats = nullptr;
   F.cap = 0;
   F.depth = depth;
   return NRV_OK;
@@ -4074,6 +4122,7 @@ int nrv_fit_set_rows_head(nrv_handle* h, const float* x1, const float* x2, const
   static const char* who = "nrv_fit_set_rows_head";
   int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_FULL) return fit_refuse(h, who, "the set is at full depth (rows are samples and read features: nrv_fit_set_rows_full)");
   if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_set_rows_signal)");
   if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)");
@@ -4099,6 +4148,7 @@ int nrv_fit_get_rows_head(nrv_handle* h, int64_t first, int64_t count, float* x1
   static const char* who = "nrv_fit_get_rows_head";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_FULL) return fit_refuse(h, who, "the set is at full depth (rows are samples and read features: nrv_fit_get_rows_full)");
   if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_get_rows_signal)");
   if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)");
@@ -4120,6 +4170,7 @@ int nrv_fit_set_rows_lstm4(nrv_handle* h, const float* xb1, const float* xb2, co
   static const char* who = "nrv_fit_set_rows_lstm4";
   int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_FULL) return fit_refuse(h, who, "the set is at full depth (rows are samples and read features: nrv_fit_set_rows_full)");
   if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_set_rows_signal)");
   if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_HEAD) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)");
@@ -4145,6 +4196,7 @@ int nrv_fit_get_rows_lstm4(nrv_handle* h, int64_t first, int64_t count, float* x
   static const char* who = "nrv_fit_get_rows_lstm4";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
+  if (h->fit.depth == NRV_FIT_FULL) return fit_refuse(h, who, "the set is at full depth (rows are samples and read features: nrv_fit_get_rows_full)");
   if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_get_rows_signal)");
   if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)");
   if (h->fit.depth == NRV_FIT_HEAD) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)");
@@ -4163,13 +4215,15 @@ int nrv_fit_get_rows_lstm4(nrv_handle* h, int64_t first, int64_t count, float* x
 }
 
 static const char* fit_other_depth_set(const nrv_handle* h) {
-  return h->fit.depth == NRV_FIT_SIGNAL ? "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_set_rows_signal)"
+  return h->fit.depth == NRV_FIT_FULL ? "the set is at full depth (rows are samples and read features: nrv_fit_set_rows_full)"
+         : h->fit.depth == NRV_FIT_SIGNAL ? "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_set_rows_signal)"
          : h->fit.depth == NRV_FIT_LSTM4 ? "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)"
          : h->fit.depth == NRV_FIT_HEAD ? "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)"
                                         : "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_LSTM3) on an empty set first)";
 }
 static const char* fit_other_depth_get(const nrv_handle* h) {
-  return h->fit.depth == NRV_FIT_SIGNAL ? "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_get_rows_signal)"
+  return h->fit.depth == NRV_FIT_FULL ? "the set is at full depth (rows are samples and read features: nrv_fit_get_rows_full)"
+         : h->fit.depth == NRV_FIT_SIGNAL ? "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_get_rows_signal)"
          : h->fit.depth == NRV_FIT_LSTM4 ? "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)"
          : h->fit.depth == NRV_FIT_HEAD ? "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)"
                                         : "the set is at tail depth (rows are main_out values: nrv_fit_get_rows)";
@@ -4265,6 +4319,50 @@ int nrv_fit_get_rows_signal(nrv_handle* h, int64_t first, int64_t count, float* 
   return NRV_OK;
 }
 
+static const char* fit_not_full(const nrv_handle* h, bool set) {
+  if (h->fit.depth == NRV_FIT_TAIL && set) return "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_FULL) on an empty set first)";
+  return fit_not_signal(h, set);
+}
+
+int nrv_fit_set_rows_full(nrv_handle* h, const float* sig, const float* feat, const uint8_t* y1, const uint8_t* y2, int64_t n) {
+  static const char* who = "nrv_fit_set_rows_full";
+  int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (h->fit.depth != NRV_FIT_FULL) return fit_refuse(h, who, fit_not_full(h, true));
+  if (n < 0 || (n > 0 && (!sig || !feat || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
+  if (n > h->fit.max_full_rows) return fit_refuse(h, who, "more rows than the cap of the training set at full depth (NRV_FIT_MAX_FULL_ROWS)");
+  for (int64_t i = 0; i < n; ++i)
+    if (y1[i] > 5 || y2[i] > 4) return fit_refuse(h, who, "a label outside the model's classes (y1 0 .. 5, y2 0 .. 4)");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.rows = 0;
+  if (n == 0) return NRV_OK;
+  if ((rc = fit_reserve(h, n))) return rc;
+  const size_t KS = (size_t)h->T * kSig, KF = (size_t)h->T * kFeat;
+  if ((rc = put(h, h->fit.sigs, sig, (size_t)n * KS * 4, h->stream)) || (rc = put(h, h->fit.feats, feat, (size_t)n * KF * 4, h->stream)) ||
+      (rc = put(h, h->fit.y[0], y1, (size_t)n, h->stream)) || (rc = put(h, h->fit.y[1], y2, (size_t)n, h->stream)))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->fit.rows = n;
+  return NRV_OK;
+}
+
+int nrv_fit_get_rows_full(nrv_handle* h, int64_t first, int64_t count, float* sig, float* feat, uint8_t* y1, uint8_t* y2) {
+  static const char* who = "nrv_fit_get_rows_full";
+  const int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (h->fit.depth != NRV_FIT_FULL) return fit_refuse(h, who, fit_not_full(h, false));
+  if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (count == 0) return NRV_OK;
+  const size_t KS = (size_t)h->T * kSig, KF = (size_t)h->T * kFeat;
+  uint8_t* const yy[2] = {y1, y2};
+  for (int m = 0; m < 2; ++m)
+    if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
+  if (sig) HIPCHK(h, hipMemcpy(sig, h->fit.sigs + (size_t)first * KS, (size_t)count * KS * 4, hipMemcpyDeviceToHost));
+  if (feat) HIPCHK(h, hipMemcpy(feat, h->fit.feats + (size_t)first * KF, (size_t)count * KF * 4, hipMemcpyDeviceToHost));
+  return NRV_OK;
+}
+
 // tensors 50 .. 55 of the handle's own model, row-major as the parameter vector has them, to the front of d_par: the device
 // holds the three kernels only in pack_dense's fragment order, which is undone here; the biases are there as they are
 static int fit_head_own(nrv_handle* h, int model, float* d_par) {
@@ -4317,14 +4415,20 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
   else {
     const size_t src[4] = {d.fw, d.fb, d.ow, d.ob}, cnt[4] = {(size_t)16 * K, 16, (size_t)16 * C, (size_t)C};
     size_t at = 0;
-    if (h->fit.depth == NRV_FIT_SIGNAL) {                   // tensors 0, 1 and 6, 7 out of the conv image, 32 and 33 as the file has them
-      HIPCHK(h, hipMemcpyAsync(M.d_par, d.all + d.conv, (size_t)32 * 4, hipMemcpyDeviceToDevice, h->stream));
-      HIPCHK(h, hipMemcpyAsync(M.d_par + kSgW2, d.all + d.conv + 48, (size_t)200 * 4, hipMemcpyDeviceToDevice, h->stream));
-      HIPCHK(h, hipMemcpyAsync(M.d_par + kSgWs, d.all + d.sdraw, (size_t)400 * 64 * 4, hipMemcpyDeviceToDevice, h->stream));
-      HIPCHK(h, hipMemcpyAsync(M.d_par + kSgBs, d.all + d.dbias, (size_t)64 * 4, hipMemcpyDeviceToDevice, h->stream));
-      at = kSgN;
+    const bool full = h->fit.depth == NRV_FIT_FULL;
+    float* const sgp = M.d_par + (full ? kRdN : 0);         // where the signal depth's vector starts
+    if (full) {                                             // tensors 12 .. 17 and 22 .. 27, unfolded as the file has them
+      HIPCHK(h, hipMemcpyAsync(M.d_par, d.all + d.l1raw, (size_t)kR1N * 4, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(M.d_par + kR1N, d.all + d.l2raw, (size_t)kR2N * 4, hipMemcpyDeviceToDevice, h->stream));
     }
-    if (h->fit.depth == NRV_FIT_LSTM3 || h->fit.depth == NRV_FIT_SIGNAL) {                    // tensors 34 .. 39, unfolded as the file has them
+    if (h->fit.depth == NRV_FIT_SIGNAL || full) {           // tensors 0, 1 and 6, 7 out of the conv image, 32 and 33 as the file has them
+      HIPCHK(h, hipMemcpyAsync(sgp, d.all + d.conv, (size_t)32 * 4, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(sgp + kSgW2, d.all + d.conv + 48, (size_t)200 * 4, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(sgp + kSgWs, d.all + d.sdraw, (size_t)400 * 64 * 4, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(sgp + kSgBs, d.all + d.dbias, (size_t)64 * 4, hipMemcpyDeviceToDevice, h->stream));
+      at = (full ? kRdN : 0) + kSgN;
+    }
+    if (h->fit.depth == NRV_FIT_LSTM3 || h->fit.depth == NRV_FIT_SIGNAL || full) {                    // tensors 34 .. 39, unfolded as the file has them
       HIPCHK(h, hipMemcpyAsync(M.d_par + at, d.all + d.l3raw, (size_t)kL3N * 4, hipMemcpyDeviceToDevice, h->stream));
       at += kL3N;
     }
@@ -4398,11 +4502,19 @@ static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
   if (h->fit.depth) {
     wg = (size_t)fit_head_wgs(b_max);
     if ((rc = fit_scratch(h, (void**)&h->fit.d_flag, &h->fit.cap_flag,
-                          (size_t)(1 + (kSgDense + 255) / 256 + kL3N / 256 + kL4N / 256 + (kHeadFitMaxP + 255) / 256) * 4)))
+                          (size_t)((kRdN + 255) / 256 + 1 + (kSgDense + 255) / 256 + kL3N / 256 + kL4N / 256 + (kHeadFitMaxP + 255) / 256) * 4)))
       return rc;
   }
   size_t pn = (size_t)fit_params_n(h, model);
-  if (h->fit.depth == NRV_FIT_SIGNAL) {                      // one chunk's [Xin | F | dS], the conv block's partials, the dense block's sums
+  const bool full = h->fit.depth == NRV_FIT_FULL;
+  if (full) {                                                // one chunk's nine arrays of nrv_fullfit.h, the read block's partials
+    const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
+    if ((rc = fit_scratch(h, (void**)&h->fit.d_rd, &h->fit.cap_rd, rows * h->T * (grad ? kRdPairGrad : kRdPair) * 4)) ||
+        (grad && (rc = fit_scratch(h, (void**)&h->fit.d_grd, &h->fit.cap_grd, (size_t)kRdSlices * kRdN * 4))))
+      return rc;
+    pn -= kRdN;
+  }
+  if (h->fit.depth == NRV_FIT_SIGNAL || full) {              // one chunk's [Xin | F | dS], the conv block's partials, the dense block's sums
     const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
     if ((rc = fit_scratch(h, (void**)&h->fit.d_sg, &h->fit.cap_sg, rows * h->T * (grad ? 656 : 192) * 4)) ||
         (grad && (rc = fit_scratch(h, (void**)&h->fit.d_pconv, &h->fit.cap_pconv, (rows * h->T + 31) / 32 * kSgConv * 4))) ||
@@ -4410,7 +4522,7 @@ static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
       return rc;
     pn -= kSgN;
   }
-  if (h->fit.depth == NRV_FIT_LSTM3 || h->fit.depth == NRV_FIT_SIGNAL) {                       // one chunk's [H3 | XB | dX3 | CS | GZ], the lstm3 block's sums, the identity list
+  if (h->fit.depth == NRV_FIT_LSTM3 || h->fit.depth == NRV_FIT_SIGNAL || full) {               // one chunk's [H3 | XB | dX3 | CS | GZ], the lstm3 block's sums, the identity list
     const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
     if ((rc = fit_scratch(h, (void**)&h->fit.d_l3, &h->fit.cap_l3, rows * h->T * (grad ? 2048 : 512) * 4)) ||
         (rc = fit_scratch(h, (void**)&h->fit.d_gl3, &h->fit.cap_gl3, (size_t)kL3N * 4)))
@@ -4449,9 +4561,11 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
   if (h->fit.depth >= NRV_FIT_LSTM4) {
     const int T = h->T;
     const bool grad = mode != kTailEval;
-    const bool sg = h->fit.depth == NRV_FIT_SIGNAL;
+    const bool full = h->fit.depth == NRV_FIT_FULL;
+    const bool sg = full || h->fit.depth == NRV_FIT_SIGNAL;
     const bool l3 = sg || h->fit.depth == NRV_FIT_LSTM3;
-    const int os = sg ? kSgN : 0;                           // where the lstm3 depth's vector starts
+    const int orr = full ? kRdN : 0;                        // where the signal depth's vector starts
+    const int os = orr + (sg ? kSgN : 0);                   // where the lstm3 depth's vector starts
     const int o3 = os + (l3 ? kL3N : 0);                    // where the lstm4 depth's vector starts
     const DevModel& dmod = h->dm[model];
     const size_t rcap = (size_t)(b < kL4ChunkRows ? (b + 31) / 32 * 32 : kL4ChunkRows) * T;
@@ -4467,12 +4581,34 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
     float* const xin = h->fit.d_sg;                         // depth NRV_FIT_SIGNAL: the three arrays of fit_step_scratch, F and dS only with grad
     float* const fkeep = sg ? xin + rcap * 192 : nullptr;
     float* const ds = sg ? fkeep + rcap * 400 : nullptr;
+    float* const x1b = h->fit.d_rd;                         // depth NRV_FIT_FULL: the nine arrays of fit_step_scratch, dH2 .. GZ2 only with grad
+    float* const h1 = full ? x1b + rcap * 32 : nullptr;
+    float* const h2 = full ? h1 + rcap * 32 : nullptr;
+    float* const dh2 = full ? h2 + rcap * 128 : nullptr;
+    float* const dh1 = full ? dh2 + rcap * 128 : nullptr;
+    float* const cs1 = full ? dh1 + rcap * 32 : nullptr;
+    float* const cs2 = full ? cs1 + rcap * 32 : nullptr;
+    float* const gz1 = full ? cs2 + rcap * 128 : nullptr;
+    float* const gz2 = full ? gz1 + rcap * 128 : nullptr;
     const int sg_wg = sg ? ((b < kL4ChunkRows ? b : kL4ChunkRows) * T + 31) / 32 : 0;     // workgroups of sig_backward_kernel in the first chunk: the conv block's partials
     for (int c0 = 0; c0 < b; c0 += kL4ChunkRows) {
       const int bc = b - c0 < kL4ChunkRows ? b - c0 : kL4ChunkRows, tiles = (bc + 31) / 32;
-      const SigArgs sa{h->fit.x2s[model], h->fit.sigs, d_rows + c0, M.d_par, dmod.all + dmod.conv, xin, fkeep, ds, gz3, h->fit.d_pconv,
-                       h->fit.d_gdense, T, bc * T, grad ? 1 : 0, c0 > 0 ? 1 : 0};
-      if (sg) hipLaunchKernelGGL(sig_forward_kernel, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
+      const SigArgs sa{full ? nullptr : h->fit.x2s[model], h->fit.sigs, d_rows + c0, M.d_par + orr, dmod.all + dmod.conv, xin, fkeep, ds, gz3,
+                       h->fit.d_pconv, h->fit.d_gdense, T, bc * T, grad ? 1 : 0, c0 > 0 ? 1 : 0, dh2, dmod.all + dmod.l_s[1]};
+      const RlArgs r1{h->fit.feats, d_rows + c0, M.d_par, dmod.all + dmod.l_s[0], dmod.all + dmod.l_h[0], h1, x1b, gz1, cs1, dh1,
+                      h->fit.d_grd, 32, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
+      const RlArgs r2{x1b, h->fit.d_ident, M.d_par + kR1N, dmod.all + dmod.l_s[1], dmod.all + dmod.l_h[1], h2, xin, gz2, cs2, dh2,
+                      full ? h->fit.d_grd + kR1N : nullptr, 192, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
+      if (full) {                                           // lstm1, lstm2 (X2b into columns 0 .. 127 of Xin), then S into the rest
+        if (h->act == 0) {
+          hipLaunchKernelGGL((rl_forward_kernel<6, 16, 0>), dim3(tiles, 2), dim3(128), 0, h->stream, r1);
+          hipLaunchKernelGGL((rl_forward_kernel<32, 64, 0>), dim3(tiles, 2), dim3(256), 0, h->stream, r2);
+        } else {
+          hipLaunchKernelGGL((rl_forward_kernel<6, 16, 1>), dim3(tiles, 2), dim3(128), 0, h->stream, r1);
+          hipLaunchKernelGGL((rl_forward_kernel<32, 64, 1>), dim3(tiles, 2), dim3(256), 0, h->stream, r2);
+        }
+        hipLaunchKernelGGL(sig_forward_kernel<false>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
+      } else if (sg) hipLaunchKernelGGL(sig_forward_kernel<true>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
       const L3Args l3a{sg ? xin : h->fit.xin[model], sg ? h->fit.d_ident : d_rows + c0, M.d_par + os, dmod.all + dmod.l_s[2], dmod.all + dmod.l_h[2], h3, xb4, gz3, cs3, dx3, gz,
                        h->fit.d_gl3, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
       if (l3) {                                             // lstm3 forward: the scratch XB is "the set" of the lstm4 launches
@@ -4502,9 +4638,20 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
         hipLaunchKernelGGL(l3_wgrad_kernel, dim3(kL3WgM * kL3WgN, 2), dim3(256), 0, h->stream, l3a);
       }
       if (sg) {
-        hipLaunchKernelGGL(l3_dx_kernel, dim3((bc * T + 31) / 32), dim3(128), 0, h->stream, sa);
+        if (full) hipLaunchKernelGGL(l3_dx_kernel<true>, dim3((bc * T + 31) / 32), dim3(384), 0, h->stream, sa);
+        else hipLaunchKernelGGL(l3_dx_kernel<false>, dim3((bc * T + 31) / 32), dim3(128), 0, h->stream, sa);
         hipLaunchKernelGGL(sig_backward_kernel, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
         hipLaunchKernelGGL(sig_wgrad_kernel, dim3(kSgWgM, 2), dim3(512), 0, h->stream, sa);
+      }
+      if (full) {
+        const RlDxArgs dxa{gz2, M.d_par + kR1N, dmod.all + dmod.l_s[0], dh1, bc * T};
+        if (h->act == 0) hipLaunchKernelGGL((rl_backward_kernel<32, 64, 0>), dim3(tiles, 2), dim3(256), 0, h->stream, r2);
+        else hipLaunchKernelGGL((rl_backward_kernel<32, 64, 1>), dim3(tiles, 2), dim3(256), 0, h->stream, r2);
+        hipLaunchKernelGGL((rl_dx_kernel<32, 64>), dim3((bc * T + 31) / 32), dim3(64), 0, h->stream, dxa);
+        if (h->act == 0) hipLaunchKernelGGL((rl_backward_kernel<6, 16, 0>), dim3(tiles, 2), dim3(128), 0, h->stream, r1);
+        else hipLaunchKernelGGL((rl_backward_kernel<6, 16, 1>), dim3(tiles, 2), dim3(128), 0, h->stream, r1);
+        hipLaunchKernelGGL((rl_wgrad_kernel<32, 64>), dim3(4 * 4, 2, kRdSlices), dim3(256), 0, h->stream, r2);
+        hipLaunchKernelGGL((rl_wgrad_kernel<6, 16>), dim3(1, 2, kRdSlices), dim3(256), 0, h->stream, r1);
       }
     }
     // the LSTM block is one "partial" of its own; the head's partials behind it; the flags of both launches in one array
@@ -4512,14 +4659,22 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
     // (at depth NRV_FIT_SIGNAL the conv block's partials and the dense block in front of that; 25896 is no multiple of 256, so
     // every reduce launch has a flag range of its own and the update launch has as many workgroups as there are flags)
     const int o4 = o3 + kL4N, PH = P - o4, bl3 = l3 ? kL3N / 256 : 0, bl4 = kL4N / 256;
-    const int bls = sg ? 1 + (kSgDense + 255) / 256 : 0;
-    if (sg) {
-      const HeadAdamArgs uc{h->fit.d_pconv, h->fit.d_pstat, sg_wg, b, kSgConv, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
+    // (at depth NRV_FIT_FULL the read block's kRdSlices partials in front of everything, with 206 flags of their own)
+    const int blr = full ? (kRdN + 255) / 256 : 0;
+    const int bls = blr + (sg ? 1 + (kSgDense + 255) / 256 : 0);
+    if (full) {
+      const HeadAdamArgs ur{h->fit.d_grd, h->fit.d_pstat, kRdSlices, b, kRdN, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
                             (HeadState*)M.d_state, h->fit.d_flag, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
-      const HeadAdamArgs ud{h->fit.d_gdense, h->fit.d_pstat, 1, b, kSgDense, mode, M.d_par + kSgWs, M.d_par + P + kSgWs, M.d_par + 2 * P + kSgWs,
-                            M.d_par + 3 * P + kSgWs, (HeadState*)M.d_state, h->fit.d_flag + 1, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+      hipLaunchKernelGGL(head_reduce_kernel, dim3(blr), dim3(256), 0, h->stream, ur);
+    }
+    if (sg) {
+      const int ow = orr + kSgWs;
+      const HeadAdamArgs uc{h->fit.d_pconv, h->fit.d_pstat, sg_wg, b, kSgConv, mode, M.d_par + orr, M.d_par + P + orr, M.d_par + 2 * P + orr, M.d_par + 3 * P + orr,
+                            (HeadState*)M.d_state, h->fit.d_flag + blr, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+      const HeadAdamArgs ud{h->fit.d_gdense, h->fit.d_pstat, 1, b, kSgDense, mode, M.d_par + ow, M.d_par + P + ow, M.d_par + 2 * P + ow,
+                            M.d_par + 3 * P + ow, (HeadState*)M.d_state, h->fit.d_flag + blr + 1, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
       hipLaunchKernelGGL(head_reduce_kernel, dim3(1), dim3(256), 0, h->stream, uc);
-      hipLaunchKernelGGL(head_reduce_kernel, dim3(bls - 1), dim3(256), 0, h->stream, ud);
+      hipLaunchKernelGGL(head_reduce_kernel, dim3(bls - blr - 1), dim3(256), 0, h->stream, ud);
     }
     const HeadAdamArgs u0{h->fit.d_gl3, h->fit.d_pstat, 1, b, kL3N, mode, M.d_par + os, M.d_par + P + os, M.d_par + 2 * P + os, M.d_par + 3 * P + os,
                           (HeadState*)M.d_state, h->fit.d_flag + bls, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};

@@ -80,6 +80,8 @@ struct SigArgs {
   float* pconv;                          // [workgroups][kSgConv] partial sums, not yet divided by b
   float* gdense;                         // [kSgDense] sums
   int T, M, keep, cont;                  // pairs of this chunk; keep: F is wanted; cont: not the batch's first chunk
+  float* dh2 = nullptr;                  // depth NRV_FIT_FULL: [M][128], dXin's lstm2 columns times s2 (l3_dx_kernel<true>)
+  const float* s2 = nullptr;             // [128] the frozen BatchNorm behind lstm2
 };
 
 // the 264-float image conv_positions reads: the vector's kernels and biases with the handle's frozen scales and shifts
@@ -88,7 +90,8 @@ __device__ __forceinline__ void sig_conv_image(const SigArgs& a, float* cwl, int
     cwl[i] = i < 32 ? a.par[i] : i < 48 ? a.conv[i] : i < 240 ? a.par[kSgW2 + i - 48] : i < 248 ? a.par[kSgB2 + i - 240] : a.conv[i];
 }
 
-// grid = ceil(M / 32)
+// grid = ceil(M / 32).  X2 = false (depth NRV_FIT_FULL): columns 0 .. 127 of Xin are another launch's, x2 is not read
+template <bool X2 = true>
 __global__ void __launch_bounds__(256) sig_forward_kernel(const SigArgs a) {
   constexpr int PLANE = 32 * 4 + 4;
   __shared__ __attribute__((aligned(16))) float img[100 * PLANE];
@@ -143,7 +146,7 @@ __global__ void __launch_bounds__(256) sig_forward_kernel(const SigArgs a) {
       if (m0 + row + 16 < a.M) a.xin[(size_t)(m0 + row + 16) * 192 + 128 + u] = acc1[reg];
     }
   }
-  for (int i = tid; i < 32 * 32; i += 256) {
+  if (X2) for (int i = tid; i < 32 * 32; i += 256) {
     const int r = i >> 5, q = i & 31;
     if (off[r] >= 0) *(f32x4*)(a.xin + (size_t)(m0 + r) * 192 + q * 4) = *(const f32x4*)(a.x2 + (size_t)off[r] * 128 + q * 4);
   }
@@ -154,8 +157,11 @@ __global__ void __launch_bounds__(256) sig_forward_kernel(const SigArgs a) {
     }
 }
 
-// grid = ceil(M / 32), 128 threads
-__global__ void __launch_bounds__(128) l3_dx_kernel(const SigArgs a) {
+// grid = ceil(M / 32), 128 threads.  FULL (depth NRV_FIT_FULL): 384 threads, the same product over all 192 columns of dXin - wave w
+// the columns 32 w .. - whose first 128 go to dh2 times s2
+template <bool FULL = false>
+__global__ void __launch_bounds__(FULL ? 384 : 128) l3_dx_kernel(const SigArgs a) {
+  constexpr int C0 = FULL ? 0 : 128;
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m0 = blockIdx.x * 32;
@@ -164,7 +170,7 @@ __global__ void __launch_bounds__(128) l3_dx_kernel(const SigArgs a) {
   for (int dir = 0; dir < 2; ++dir) {
     const float* arow = a.gz3 + ((size_t)(m0 + l31) * 2 + dir) * 512;
     // W3 [192 in][512 gate columns]: B[k = gate column][n = signal column] = W3[128 + n][k]
-    const float* w0 = a.par + kSgN + (size_t)dir * kL3Dir + (size_t)(128 + wave * 32 + l31) * 512;
+    const float* w0 = a.par + kSgN + (size_t)dir * kL3Dir + (size_t)(C0 + wave * 32 + l31) * 512;
 #pragma unroll 4
     for (int kg = 0; kg < 64; ++kg) {
       f32x4 av = {0.f, 0.f, 0.f, 0.f};
@@ -177,7 +183,9 @@ __global__ void __launch_bounds__(128) l3_dx_kernel(const SigArgs a) {
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
     const int m = m0 + acc_row(reg, lane);
-    if (m < a.M) a.dS[(size_t)m * 64 + wave * 32 + l31] = acc[reg];
+    if (m >= a.M) continue;
+    if (FULL && wave < 4) a.dh2[(size_t)m * 128 + wave * 32 + l31] = acc[reg] * a.s2[wave * 32 + l31];
+    else a.dS[(size_t)m * 64 + C0 + wave * 32 + l31 - 128] = acc[reg];
   }
 }
 

@@ -51,10 +51,12 @@ SYMBOLS = [
     "nrv_fit_set_rows_lstm4", "nrv_fit_get_rows_lstm4",
     "nrv_fit_set_rows_lstm3", "nrv_fit_get_rows_lstm3",
     "nrv_fit_set_rows_signal", "nrv_fit_get_rows_signal",
+    "nrv_fit_set_rows_full", "nrv_fit_get_rows_full",
 ]
 FIT_TAIL, FIT_HEAD, FIT_LSTM4 = 0, 1, 4    # NRV_FIT_TAIL, NRV_FIT_HEAD, NRV_FIT_LSTM4 (the Bi-LSTM the fit starts at)
 FIT_LSTM3 = 8                              # NRV_FIT_LSTM3
 FIT_SIGNAL = 16                            # NRV_FIT_SIGNAL
+FIT_FULL = 32                              # NRV_FIT_FULL
 FIT_MAX_BATCH = 65536               # NRV_FIT_MAX_BATCH
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 PROFILE_COLS = 48                   # NRV_PROFILE_COLS
@@ -190,6 +192,8 @@ _FIT_T = {                                                                      
     "nrv_fit_get_rows_lstm3": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
     "nrv_fit_set_rows_signal": [C.c_void_p, _FP, _FP, _FP, _U8P, _U8P, C.c_int64],
     "nrv_fit_get_rows_signal": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _FP, _U8P, _U8P],
+    "nrv_fit_set_rows_full": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
+    "nrv_fit_get_rows_full": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
 }
 
 
@@ -879,14 +883,16 @@ class Reviser:
         """The length of a model's parameter vector at the current depth."""
         c = self._n_class(model)
         front = {FIT_TAIL: 0, FIT_HEAD: 20838, FIT_LSTM4: 164352 + 20838, FIT_LSTM3: 328704 + 164352 + 20838,
-                 FIT_SIGNAL: 25896 + 328704 + 164352 + 20838}[self.fit_depth()]
+                 FIT_SIGNAL: 25896 + 328704 + 164352 + 20838,
+                 FIT_FULL: 52608 + 25896 + 328704 + 164352 + 20838}[self.fit_depth()]
         return front + 96 * self.T + 16 + 16 * c + c + 16 * c
 
     # ---- the second depth (nanoreviser_amd/headfit.py is the definition): the set holds lstm4 outputs [T][128] per window
     def fit_set_depth(self, depth):
-        """FIT_TAIL / FIT_HEAD / FIT_LSTM4 / FIT_LSTM3 / FIT_SIGNAL (or "tail" / "head" / "lstm4" / "lstm3" / "signal"), on an
-        empty set only; forgets any fit_begin."""
-        depth = {"tail": FIT_TAIL, "head": FIT_HEAD, "lstm4": FIT_LSTM4, "lstm3": FIT_LSTM3, "signal": FIT_SIGNAL}.get(depth, depth)
+        """FIT_TAIL / FIT_HEAD / FIT_LSTM4 / FIT_LSTM3 / FIT_SIGNAL / FIT_FULL (or "tail" / "head" / "lstm4" / "lstm3" / "signal" /
+        "full"), on an empty set only; forgets any fit_begin."""
+        depth = {"tail": FIT_TAIL, "head": FIT_HEAD, "lstm4": FIT_LSTM4, "lstm3": FIT_LSTM3, "signal": FIT_SIGNAL,
+                 "full": FIT_FULL}.get(depth, depth)
         self._check(self._lib.nrv_fit_set_depth(self._h, int(depth)))
 
     def fit_depth(self) -> int:
@@ -967,6 +973,25 @@ class Reviser:
                np.empty(count, np.uint8), np.empty(count, np.uint8))
         self._check(self._lib.nrv_fit_get_rows_signal(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _FP),
                                                       _ptr(out[3], _U8P), _ptr(out[4], _U8P)))
+        return out
+
+    # ---- the sixth depth (nanoreviser_amd/fullfit.py is the definition): the set holds ONE array of samples [T][50] and ONE of
+    # read features [T][6] for both models
+    def fit_set_rows_full(self, sig, feat, y1, y2):
+        sg, ft = _as_f32(sig, (self.T, 50)), _as_f32(feat, (self.T, 6))
+        a, b = (np.ascontiguousarray(v, dtype=np.uint8).reshape(-1) for v in (y1, y2))
+        n = sg.shape[0]
+        if ft.shape[0] != n or a.size != n or b.size != n:
+            raise ValueError("sig / feat / y1 / y2 must have one entry per row")
+        self._check(self._lib.nrv_fit_set_rows_full(self._h, _ptr(sg, _FP), _ptr(ft, _FP), _ptr(a, _U8P), _ptr(b, _U8P), n))
+
+    def fit_get_rows_full(self, first=0, count=None):
+        """-> (sig, feat, y1, y2) of rows [first, first + count), sig [count][T][50], feat [count][T][6]."""
+        count = self.fit_count() - first if count is None else count
+        out = (np.empty((count, self.T, 50), np.float32), np.empty((count, self.T, 6), np.float32),
+               np.empty(count, np.uint8), np.empty(count, np.uint8))
+        self._check(self._lib.nrv_fit_get_rows_full(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _U8P),
+                                                    _ptr(out[3], _U8P)))
         return out
 
     @staticmethod

@@ -120,6 +120,12 @@ def forward(x2, sig, theta, cb, sc, sh, T: int, C: int, act: int = 0, dtype=np.f
 def batch_terms(x2, sig, y, theta, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64):
     """One batch -> (g [P]: the gradient of L, FitStats of the batch with steps = nonfinite = 0).  ReLU sides are decided on the
     forward value; every gradient is divided by n as the LSTM blocks' are."""
+    return batch_terms_dx(x2, sig, y, theta, cb, sc, sh, T, C, opts, act, dtype)[:2]
+
+
+def batch_terms_dx(x2, sig, y, theta, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64):
+    """batch_terms and the data gradient behind it -> (g, FitStats, dx2 [n][T][128]: columns 0 .. 127 of lstm3fit's dXin - the
+    derivative of the batch's SUM of row losses by x2, not divided by n).  fullfit.py goes on from it."""
     dt = np.dtype(dtype)
     theta = np.asarray(theta)
     k = branch(sig, theta, cb, T, C, dt)
@@ -142,7 +148,7 @@ def batch_terms(x2, sig, y, theta, cb, sc, sh, T: int, C: int, opts: FitOpts, ac
     gw1 = np.stack([np.einsum("ntp,ntpo->o", sp[..., kk:kk + N_SIG_IN], da1) for kk in range(3)])
     gb1 = da1.sum(axis=(0, 1, 2))
     g = np.concatenate([a.ravel() for a in (gw1, gb1, gw2, gb2, gWs, gbs)]) / dt.type(n)
-    return np.concatenate([g.astype(dt), g3]), st
+    return np.concatenate([g.astype(dt), g3]), st, dXin[..., :128]
 
 
 def epoch(x2, sig, y, state: FitState, order, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0,

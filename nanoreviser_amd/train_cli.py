@@ -22,6 +22,12 @@ normalised samples (nanoreviser_amd/signalfit.py is the definition, and states t
 fitted section stay frozen in their inference form, the reference's Dropout is not applied).  The signal branch and lstm3 always
 start from the loaded or continued model's own weights; --fit_init acts on the layers behind lstm4.  (--fit_depth lstm3 is not
 offered.)
+
+--fit_depth full fits the read branch too - lstm1 (tensors 12 .. 17) and lstm2 (22 .. 27) - with everything --fit_depth signal
+fits: every tensor that is no BatchNorm's.  A window is its raw inputs, 50 T normalised samples and 6 T read features
+(nanoreviser_amd/fullfit.py is the definition; the five BatchNorms stay frozen in their inference form, Dropout is not applied).
+The four LSTMs and the signal branch start from the loaded or continued model's own weights; --fit_init acts on the layers
+behind lstm4, and a fresh initialisation of the LSTMs is not offered.
 """
 from __future__ import annotations
 
@@ -34,7 +40,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import cli, headfit, lstm4fit, signalfit, tailfit
+from . import cli, fullfit, headfit, lstm4fit, signalfit, tailfit
 from .weights import load_model, load_species
 
 HISTORY_HEAD = "epoch\tloss\tce\tcenter\tacc\tval_loss\tval_acc\tnonfinite"
@@ -64,7 +70,8 @@ def get_args(argv: Optional[Sequence[str]] = None):
                    help="tail: tensors 56 .. 59 behind Flatten(main_out); head: tensors 50 .. 59 behind lstm4 (then --fit_init "
                         "fresh keeps the shipped 50 .. 55 and fresh_head draws all five layers); lstm4: tensors 44 .. 59, the "
                         "last Bi-LSTM too (it always starts from the model's own weights); signal: the signal branch (0, 1, 6, 7, "
-                        "32, 33) and lstm3 (34 .. 39) in front of that, from the model's own weights")
+                        "32, 33) and lstm3 (34 .. 39) in front of that, from the model's own weights; full: lstm1 (12 .. 17) and "
+                        "lstm2 (22 .. 27) too - every tensor that is no BatchNorm's")
     p.add_argument("--model_dir", default=None, help="root of model/<species>/ (default: next to the package)")
     p.add_argument("-g", "--basecall_group", dest="basecall_group", default="Basecall_1D_000")
     p.add_argument("-s", "--basecall_subgroup", dest="basecall_subgroup", default="BaseCalled_template")
@@ -92,8 +99,8 @@ def check_args(a):
         return "--labels_from: not a directory"
     if a.model_type not in ("both", "model1", "model2"):
         return "--model_type must be both, model1 or model2"
-    if a.fit_depth not in ("tail", "head", "lstm4", "signal"):
-        return f"--fit_depth must be tail or head, or lstm4, or signal, not {a.fit_depth!r}"
+    if a.fit_depth not in ("tail", "head", "lstm4", "signal", "full"):
+        return f"--fit_depth must be tail or head, or lstm4, or signal, or full, not {a.fit_depth!r}"
     if a.fit_depth == "tail" and a.fit_init == "fresh_head":
         return "--fit_init fresh_head draws the three dense layers behind lstm4, which --fit_depth tail does not fit"
     if a.fit_init not in (("transfer", "fresh") if a.fit_depth == "tail" else ("transfer", "fresh", "fresh_head")):
@@ -157,8 +164,18 @@ def _start_signal(a, k, m, T):
     return signalfit.with_lstm3(front, signalfit.lstm3fit.with_lstm4(front[signalfit.N_SIGNAL:], th)), how
 
 
+def _start_full(a, k, m, T):
+    """_start at --fit_depth full: _start_signal's vector behind tensors 12 .. 17 and 22 .. 27 of the loaded or continued model."""
+    th, how = _start_signal(a, k, m, T)
+    path = (a.model1_train_dir, a.model2_train_dir)[k]
+    front = fullfit.params_from_model(load_model(path) if path else m.with_window(T))
+    return fullfit.with_signal(front, th), how
+
+
 def _start(a, k, m, T):
     """The starting parameter vector of model k (0 / 1) and where it came from."""
+    if a.fit_depth == "full":
+        return _start_full(a, k, m, T)
     if a.fit_depth == "signal":
         return _start_signal(a, k, m, T)
     if a.fit_depth == "lstm4":
@@ -182,7 +199,7 @@ def _start(a, k, m, T):
     return tailfit.params_from_model(m), "transfer"
 
 
-_DEPTHS = {"tail": tailfit, "head": headfit, "lstm4": lstm4fit, "signal": signalfit}
+_DEPTHS = {"tail": tailfit, "head": headfit, "lstm4": lstm4fit, "signal": signalfit, "full": fullfit}
 
 
 def _default_factory(a, m1, m2):

@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
-"""Time nrv_fit_epoch at the five fit depths (tail: tensors 56 .. 59; head: tensors 50 .. 59; lstm4: tensors 44 .. 59; lstm3:
-tensors 34 .. 39 and 44 .. 59; signal: tensors 0, 1, 6, 7, 32 .. 39 and 44 .. 59) on the device.  A plain script: it takes no part in bench.py and sets no bar.
+"""Time nrv_fit_epoch at the six fit depths (tail: tensors 56 .. 59; head: tensors 50 .. 59; lstm4: tensors 44 .. 59; lstm3:
+tensors 34 .. 39 and 44 .. 59; signal: tensors 0, 1, 6, 7, 32 .. 39 and 44 .. 59; full: every tensor that is no BatchNorm's) on the device.  A plain script: it takes no part in bench.py and sets no bar.
 
-A set of seeded rows goes in through the unit doors (nrv_fit_set_rows / _head / _lstm4 / _lstm3 / _signal), so the frozen backbone never
+A set of seeded rows goes in through the unit doors (nrv_fit_set_rows / _head / _lstm4 / _lstm3 / _signal / _full), so the frozen backbone never
 runs: what is timed is one whole nrv_fit_epoch call - the upload of the row order, every batch's launches enqueued back to back
 and the one synchronise at the end - by a host clock around the call, which returns only after that synchronise.  Per depth:
 untimed epochs first (first launches load code objects and size the scratch buffers), then --repeats timed epochs; the median
 and the spread (min .. max) are printed as rows/s, then one JSON line with everything.
 
-    python tools/fit_bench.py [--rows 65536] [-b 512] [-w 11] [--warmup 3] [--repeats 9] [--model 0] [--depths tail,head,lstm4,lstm3,signal]
+    python tools/fit_bench.py [--rows 65536] [-b 512] [-w 11] [--warmup 3] [--repeats 9] [--model 0] [--depths tail,head,lstm4,lstm3,signal,full]
 """
 import argparse
 import json
@@ -46,7 +46,14 @@ def flop_per_row(depth, T, C):
     # convolutions and the 400 -> 64 product forward, gWs = F^T dS, dF = dS Ws^T, conv2's weight and data gradient and conv1's
     # weight gradient; the backward launch's recomputation of a1, c1 and a2 is NOT counted
     conv1, conv2, dense = 50 * 8 * 3, 50 * 8 * 24, 400 * 64
-    return l3 + 2 * T * (2 * 512 * 64 + (conv1 + conv2 + dense) + 2 * dense + 2 * conv2 + conv1)
+    sg = l3 + 2 * T * (2 * 512 * 64 + (conv1 + conv2 + dense) + 2 * dense + 2 * conv2 + conv1)
+    if depth == "signal":
+        return sg
+    # full depth: the signal depth with the other 128 columns of dXin; per direction lstm2's two forward products, its
+    # recurrent data gradient, its two weight-gradient products and its data gradient dz2 W2^T; the same of lstm1 without a data
+    # gradient into the features
+    lstm2, lstm1 = 2 * T * 2 * (32 * 256 + 64 * 256), 2 * T * 2 * (6 * 64 + 16 * 64)
+    return (sg + 2 * T * 2 * 512 * 128 + 2 * lstm2 + 2 * T * 2 * (64 * 256 + 32 * 256) + 2 * lstm1 + 2 * T * 2 * 16 * 64)
 
 
 def main(argv=None):
@@ -59,9 +66,9 @@ def main(argv=None):
     ap.add_argument("--model", type=int, default=0, choices=(0, 1))
     ap.add_argument("--species", default="ecoli")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--depths", default="tail,head,lstm4,lstm3", help="the depths to time, in this order (signal is not in the default)")
+    ap.add_argument("--depths", default="tail,head,lstm4,lstm3", help="the depths to time, in this order (signal and full are not in the default)")
     a = ap.parse_args(argv)
-    from nanoreviser_amd import headfit, lstm3fit, lstm4fit, signalfit, tailfit
+    from nanoreviser_amd import fullfit, headfit, lstm3fit, lstm4fit, signalfit, tailfit
     from nanoreviser_amd.engine import Reviser
     from nanoreviser_amd.weights import load_species
     T, k, n = a.window_size, a.model, a.rows
@@ -85,6 +92,12 @@ def main(argv=None):
                 F = np.maximum(rng.normal(0, 1, (n, 6 * T)), 0).astype(np.float32)
                 rv.fit_set_rows(F, F, y1, y2)
                 th = tailfit.fresh_params(T, C, a.seed)
+            elif depth == "full":                          # the shipped model in front of a fresh head
+                rv.fit_set_rows_full(rng.normal(0, 1, (n, T, 50)).astype(np.float32), rng.normal(0, 1, (n, T, 6)).astype(np.float32), y1, y2)
+                m = (m1, m2)[k].with_window(T)
+                th4 = lstm4fit.with_head(lstm4fit.params_from_model(m), headfit.fresh_params(T, C, a.seed))
+                ths = signalfit.with_lstm3(signalfit.params_from_model(m), lstm3fit.with_lstm4(lstm3fit.params_from_model(m), th4))
+                th = fullfit.with_signal(fullfit.params_from_model(m), ths)
             elif depth == "signal":                        # the shipped signal branch, lstm3 and lstm4 in front of a fresh head
                 X = rng.normal(0, 1, (n, T, 128)).astype(np.float32)
                 rv.fit_set_rows_signal(X, X, rng.normal(0, 1, (n, T, 50)).astype(np.float32), y1, y2)
