@@ -929,6 +929,34 @@ int nrv_fit_get_rows_signal(nrv_handle* h, int64_t first, int64_t count, float* 
 int nrv_fit_set_rows_full(nrv_handle* h, const float* sig, const float* feat, const uint8_t* y1, const uint8_t* y2, int64_t n);
 int nrv_fit_get_rows_full(nrv_handle* h, int64_t first, int64_t count, float* sig, float* feat, uint8_t* y1, uint8_t* y2);
 
+/* ---- Re-estimating the BatchNorm statistics inside the fitted section from rows of the set (opt-in) ----
+ * nanoreviser_amd/bnfit.py is the definition.  The BatchNorms INSIDE the fitted section are, in tensor order: at depth
+ * NRV_FIT_LSTM3 bn_l3 (tensors 40 .. 43); at NRV_FIT_SIGNAL bn_c1 (2 .. 5), bn_c2 (8 .. 11), bn_l3; at NRV_FIT_FULL also bn_l1
+ * (18 .. 21) and bn_l2 (28 .. 31) between them; none at the other depths.  nrv_fit_begin at these three depths copies the
+ * handle's folded (scale, shift) pairs into a block of the FIT's own, and every fit launch reads a BatchNorm there: without a
+ * re-estimation every depth computes what it computed.  The handle's own model - nrv_predict*, the set's gathers - is never
+ * changed: to run a re-estimated model, write it (bnfit.with_stats) and create a handle from it.
+ *   nrv_fit_bn_reestimate  between nrv_fit_begin and the end of the fit, at any point, at the model's CURRENT parameters; Adam's
+ *     state and the step counter are left alone.  Per channel of each BatchNorm, over the given rows (an index may repeat): the
+ *     mean and the BIASED variance of the activation it normalises - bn_c1: a1 = relu(conv1(sig) + b1) over (row, t, the 50
+ *     samples); bn_c2: a2 = relu(conv2(c1) + b2) likewise; bn_l1 / bn_l2 / bn_l3: the RAW Bi-LSTM output over (row, t).  With
+ *     the pivot p = the LOADED moving mean: S1 = sum (x - p), S2 = sum (x - p)^2 in f64, m = S1 / N, mean = p + m,
+ *     var = max(S2 / N - m m, 0), no contraction, each rounded once to f32.  Stages in dependency order - {bn_c1, bn_l1},
+ *     {bn_c2, bn_l2}, {bn_l3} - one pass over the rows each (three at signal and full depth, one at lstm3 depth): behind a stage
+ *     its new statistics are folded with the loaded gamma and beta exactly as nrv_create folds a file's tensors, and the next
+ *     stage runs on them.  gamma and beta are never touched.  The forward launches are the fit's own, in its chunks
+ *     (csrc/nrv_bnfit.h: the moments); no atomics, the same calls give the same bytes.  Refused under its own name, the handle
+ *     staying usable: depths with no BatchNorm inside, no nrv_fit_begin for the model, n_rows <= 0, a row index outside the set,
+ *     a raw-read call in flight.
+ *   nrv_fit_bn_count  BatchNorms inside the section: 0, 1, 3 or 5.
+ *   nrv_fit_bn_get    BatchNorm `which` of them: info (tensor_base: its gamma's tensor; n: elements per channel of the last
+ *     re-estimation, 0 before any - then mean / var are the loaded statistics and s1 / s2 zero), mean, var [channels] f32,
+ *     s1, s2 [channels] f64; any output may be NULL. */
+typedef struct { int tensor_base; int channels; int64_t n; } nrv_fit_bn_info;
+int nrv_fit_bn_reestimate(nrv_handle* h, int model, const uint32_t* rows, int64_t n_rows);
+int nrv_fit_bn_count(nrv_handle* h);
+int nrv_fit_bn_get(nrv_handle* h, int model, int which, nrv_fit_bn_info* info, float* mean, float* var, double* s1, double* s2);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

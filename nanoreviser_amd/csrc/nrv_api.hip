@@ -8,6 +8,7 @@
 #include "nrv_lstm3fit.h"     // ... at depth NRV_FIT_LSTM3: lstm3's inputs as the set, the 192->128 Bi-LSTM's forward and backward, dX out of lstm4
 #include "nrv_signalfit.h"    // ... at depth NRV_FIT_SIGNAL: lstm2's outputs and the samples as the set, the signal branch's forward and backward, dS out of lstm3
 #include "nrv_fullfit.h"      // ... at depth NRV_FIT_FULL: the raw windows as the set, lstm1 and lstm2 forward and backward, all of dXin out of lstm3
+#include "nrv_bnfit.h"        // ... nrv_fit_bn_reestimate: the moments of the BatchNorms inside the fitted section, the fit-owned BatchNorm block
 #include "nrv_block.h"
 
 #include <algorithm>
@@ -454,6 +455,9 @@ static void bn_fold(const float* g, const float* be, const float* mu, const floa
   }
 }
 
+// the five BatchNorms nrv_fit_bn_* knows, in tensor order: first tensor (gamma), channels, first channel of the block's kBnCh
+static const struct { int tensor, C, at; } kFitBn[5] = {{2, 8, 0}, {8, 8, 8}, {18, 32, 16}, {28, 128, 48}, {40, 256, 176}};
+
 struct DevModel {
   float* all = nullptr;       // one allocation holding every packed tensor of the model
   size_t n = 0;
@@ -467,6 +471,9 @@ struct DevModel {
   size_t sdraw = 0;           // tensor 32 as the file has it (... at depth NRV_FIT_SIGNAL)
   size_t l1raw = 0, l2raw = 0;   // tensors 12 .. 17 and 22 .. 27 as the file has them (... at depth NRV_FIT_FULL)
   size_t l4raw = 0;           // tensors 44 .. 49 as the file has them (nrv_fit_begin at depth NRV_FIT_LSTM4 starts from them)
+  // host copies of the five BatchNorms' gamma, beta, moving mean and moving variance, kBnCh channels each in the order of the
+  // fit's BatchNorm block: what nrv_fit_bn_reestimate folds new statistics with
+  std::vector<float> bn_raw[4];
   size_t h_ws, h_wb;          // head_mlp_split_kernel: split weights / biases
   // f16x2 mode (nrv_lstm_f16x2.h): lstm2..4 weights as two f16 terms, scaled biases, output scale /
   // shift with the buffer exponents folded in, the producers' scaled epilogue constants
@@ -725,8 +732,16 @@ struct nrv_handle {
     TailStat* d_pstat = nullptr; size_t cap_pstat = 0;        // [workgroups]
     unsigned* d_order = nullptr; size_t cap_order = 0;        // row indices of a call
     float* d_p = nullptr; size_t cap_p = 0;                   // nrv_fit_eval's rows
+    double* d_bnpart = nullptr; size_t cap_bnpart = 0;        // nrv_fit_bn_reestimate: one chunk's partial moments of a stage
     struct Model {
       float* d_par = nullptr;                                 // [4][P]
+      // depths NRV_FIT_LSTM3 and deeper: the fit's own BatchNorm block [kBnFloats] (nrv_bnfit.h) - every fit launch reads its
+      // (scale, shift) pairs here - the running sums [2][kBnCh] of a re-estimation, and what nrv_fit_bn_get returns
+      float* d_bn = nullptr;
+      double* d_bnacc = nullptr;
+      std::vector<float> bn_mean, bn_var;
+      std::vector<double> bn_s1, bn_s2;
+      int64_t bn_n[5] = {0, 0, 0, 0, 0};
       TailState* d_state = nullptr;
       float* d_lr = nullptr; size_t cap_lr = 0;
       bool begun = false;
@@ -816,6 +831,10 @@ NRV_HOST_COLD static int upload_model(nrv_handle* h, int mi, const Blob& b, int 
     memcpy(cv + 240, b.t(7), 8 * 4);
     bn_fold(b.t(8), b.t(9), b.t(10), b.t(11), 8, cv + 248, cv + 256);
     d.conv = put(cv, 264);
+  }
+  for (int i = 0; i < 4; ++i) {
+    d.bn_raw[i].clear();
+    for (const auto& k : kFitBn) d.bn_raw[i].insert(d.bn_raw[i].end(), b.t(k.tensor + i), b.t(k.tensor + i) + k.C);
   }
   {
     static const size_t n3[6] = {192 * 512, 128 * 512, 512, 192 * 512, 128 * 512, 512};
@@ -1661,9 +1680,10 @@ void nrv_destroy(nrv_handle* h) {
     (void)hipFree(h->fit.flat[m]); (void)hipFree(h->fit.y[m]); (void)hipFree(h->fit.x4[m]); (void)hipFree(h->fit.xb[m]); (void)hipFree(h->fit.xin[m]);
     (void)hipFree(h->fit.x2s[m]);
     (void)hipFree(h->fit.m[m].d_par); (void)hipFree(h->fit.m[m].d_state); (void)hipFree(h->fit.m[m].d_lr);
+    (void)hipFree(h->fit.m[m].d_bn); (void)hipFree(h->fit.m[m].d_bnacc);
   }
   (void)hipFree(h->fit.d_partial); (void)hipFree(h->fit.d_pstat); (void)hipFree(h->fit.d_order); (void)hipFree(h->fit.d_p); (void)hipFree(h->fit.d_flag);
-  (void)hipFree(h->fit.d_l4); (void)hipFree(h->fit.d_gl4);
+  (void)hipFree(h->fit.d_l4); (void)hipFree(h->fit.d_gl4); (void)hipFree(h->fit.d_bnpart);
   (void)hipFree(h->fit.d_l3); (void)hipFree(h->fit.d_gl3); (void)hipFree(h->fit.d_ident);
   (void)hipFree(h->fit.feats); (void)hipFree(h->fit.d_rd); (void)hipFree(h->fit.d_grd);
   (void)hipFree(h->fit.sigs); (void)hipFree(h->fit.d_sg); (void)hipFree(h->fit.d_pconv); (void)hipFree(h->fit.d_gdense);
@@ -4447,6 +4467,24 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
       at += cnt[i];
     }
   }
+  if (h->fit.depth >= NRV_FIT_LSTM3) {                      // the fit's own BatchNorm block: the handle's folded pairs, the loaded statistics
+    if (!M.d_bn) {
+      HIPCHK(h, hipMalloc((void**)&M.d_bn, (size_t)kBnFloats * 4));
+      HIPCHK(h, hipMalloc((void**)&M.d_bnacc, (size_t)2 * kBnCh * 8));
+    }
+    int rcp;
+    if ((rcp = poison_fill(h, M.d_bn, (size_t)kBnFloats * 4, h->stream)) || (rcp = poison_fill(h, M.d_bnacc, (size_t)2 * kBnCh * 8, h->stream))) return rcp;
+    static const int ats[3] = {kBnS1, kBnS2, kBnS3}, ath[3] = {kBnH1, kBnH2, kBnH3}, nl[3] = {32, 128, 256};
+    HIPCHK(h, hipMemcpyAsync(M.d_bn + kBnConv, d.all + d.conv, (size_t)264 * 4, hipMemcpyDeviceToDevice, h->stream));
+    for (int l = 0; l < 3; ++l) {
+      HIPCHK(h, hipMemcpyAsync(M.d_bn + ats[l], d.all + d.l_s[l], (size_t)nl[l] * 4, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(M.d_bn + ath[l], d.all + d.l_h[l], (size_t)nl[l] * 4, hipMemcpyDeviceToDevice, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(M.d_bn + kBnPivot, d.bn_raw[2].data(), (size_t)kBnCh * 4, hipMemcpyHostToDevice, h->stream));
+    M.bn_mean = d.bn_raw[2]; M.bn_var = d.bn_raw[3];
+    M.bn_s1.assign(kBnCh, 0.0); M.bn_s2.assign(kBnCh, 0.0);
+    for (int i = 0; i < 5; ++i) M.bn_n[i] = 0;
+  }
   HIPCHK(h, hipMemsetAsync(M.d_state, 0, sizeof(TailState), h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   M.o = o; M.t = 0; M.begun = true;
@@ -4546,9 +4584,45 @@ static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
   return fit_scratch(h, (void**)&h->fit.d_pstat, &h->fit.cap_pstat, wg * sizeof(TailStat));
 }
 
+// nrv_fit_bn_reestimate: behind the forward launches of one chunk (rows c0 .. c0 + bc - 1 of b), the moments of the stage's
+// BatchNorms - stage 0: bn_c1, bn_l1; 1: bn_c2, bn_l2; 2: bn_l3, each only where it lies inside the fitted section - into the
+// partials, and their reduction onto the model's running sums (nrv_bnfit.h)
+static void fit_bn_moments(nrv_handle* h, int model, int stage, int c0, int bc, int b, const SigArgs& sa, const float* h1, const float* h2,
+                           const float* h3) {
+  nrv_handle::Fit::Model& M = h->fit.m[model];
+  const int T = h->T, Mc = bc * T, wg_col = (Mc + kBnRows - 1) / kBnRows, wg_conv = (Mc + 32 * kBnTiles - 1) / (32 * kBnTiles);
+  const bool full = h->fit.depth == NRV_FIT_FULL, sg = full || h->fit.depth == NRV_FIT_SIGNAL;
+  double* const pcol = h->fit.d_bnpart;                     // the two regions nrv_fit_bn_reestimate sized
+  double* const pconv = pcol + (size_t)kL4ChunkRows * T / kBnRows * 512 + 512;
+  BnReduceArgs ra{};
+  int nb = 0;
+  auto add = [&](int which, const double* part, int n_part, long long per_pair) {
+    ra.bn[nb++] = BnReduceArgs::One{part, n_part, kFitBn[which].C, kFitBn[which].at, (long long)b * T * per_pair};
+  };
+  if (stage < 2 && sg) {
+    const BnConvArgs ca{sa, M.d_bn + kBnPivot + kFitBn[stage].at, pconv};
+    if (stage == 0) hipLaunchKernelGGL(bn_conv_moments_kernel<1>, dim3(wg_conv), dim3(256), 0, h->stream, ca);
+    else hipLaunchKernelGGL(bn_conv_moments_kernel<2>, dim3(wg_conv), dim3(256), 0, h->stream, ca);
+    add(stage, pconv, wg_conv, kSig);
+  }
+  if (stage == 0 && full) {
+    hipLaunchKernelGGL(bn_col_moments_kernel<32>, dim3(wg_col), dim3(256), 0, h->stream, BnColArgs{h1, M.d_bn + kBnPivot + kFitBn[2].at, pcol, Mc});
+    add(2, pcol, wg_col, 1);
+  } else if (stage == 1 && full) {
+    hipLaunchKernelGGL(bn_col_moments_kernel<128>, dim3(wg_col), dim3(256), 0, h->stream, BnColArgs{h2, M.d_bn + kBnPivot + kFitBn[3].at, pcol, Mc});
+    add(3, pcol, wg_col, 1);
+  } else if (stage == 2) {
+    hipLaunchKernelGGL(bn_col_moments_kernel<256>, dim3(wg_col), dim3(256), 0, h->stream, BnColArgs{h3, M.d_bn + kBnPivot + kFitBn[4].at, pcol, Mc});
+    add(4, pcol, wg_col, 1);
+  }
+  ra.acc = M.d_bnacc; ra.blk = M.d_bn; ra.cont = c0 > 0 ? 1 : 0; ra.last = c0 + bc == b ? 1 : 0;
+  hipLaunchKernelGGL(bn_reduce_kernel, dim3(nb), dim3(256), 0, h->stream, ra);
+}
+
 // one batch of b rows onto the stream: the gradient (mode kTailGradOnly / kTailTrain) or the forward alone (kTailEval) and the
-// reduce / update behind it - two launches at tail depth, three at head depth
-static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, int mode, long long n_lr, float* d_p) {
+// reduce / update behind it - two launches at tail depth, three at head depth.  bn_stage >= 0 (nrv_fit_bn_reestimate, mode
+// kTailEval, depth NRV_FIT_LSTM3 or deeper): per chunk the forward launches up to lstm3 and fit_bn_moments, nothing else
+static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, int mode, long long n_lr, float* d_p, int bn_stage = -1) {
   if (!h->fit.depth) {
     const int wg = (b + 31) / 32;
     if (mode == kTailEval) hipLaunchKernelGGL(tail_grad_kernel<false>, dim3(wg), dim3(256), 0, h->stream, fit_grad_args(h, model, d_rows, b, d_p));
@@ -4567,7 +4641,9 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
     const int orr = full ? kRdN : 0;                        // where the signal depth's vector starts
     const int os = orr + (sg ? kSgN : 0);                   // where the lstm3 depth's vector starts
     const int o3 = os + (l3 ? kL3N : 0);                    // where the lstm4 depth's vector starts
-    const DevModel& dmod = h->dm[model];
+    // every BatchNorm inside the fitted section is read from the fit's own block (the handle's pairs until nrv_fit_bn_reestimate);
+    // the arguments that point into it are used at depth NRV_FIT_LSTM3 and deeper only, where the block exists
+    const float* const fbn = l3 ? M.d_bn : h->dm[model].all;
     const size_t rcap = (size_t)(b < kL4ChunkRows ? (b + 31) / 32 * 32 : kL4ChunkRows) * T;
     float* const x4 = h->fit.d_l4;                          // the four arrays of fit_step_scratch, dX4 .. GZ only with grad
     float* const dx4 = x4 + rcap * 128;
@@ -4593,11 +4669,11 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
     const int sg_wg = sg ? ((b < kL4ChunkRows ? b : kL4ChunkRows) * T + 31) / 32 : 0;     // workgroups of sig_backward_kernel in the first chunk: the conv block's partials
     for (int c0 = 0; c0 < b; c0 += kL4ChunkRows) {
       const int bc = b - c0 < kL4ChunkRows ? b - c0 : kL4ChunkRows, tiles = (bc + 31) / 32;
-      const SigArgs sa{full ? nullptr : h->fit.x2s[model], h->fit.sigs, d_rows + c0, M.d_par + orr, dmod.all + dmod.conv, xin, fkeep, ds, gz3,
-                       h->fit.d_pconv, h->fit.d_gdense, T, bc * T, grad ? 1 : 0, c0 > 0 ? 1 : 0, dh2, dmod.all + dmod.l_s[1]};
-      const RlArgs r1{h->fit.feats, d_rows + c0, M.d_par, dmod.all + dmod.l_s[0], dmod.all + dmod.l_h[0], h1, x1b, gz1, cs1, dh1,
+      const SigArgs sa{full ? nullptr : h->fit.x2s[model], h->fit.sigs, d_rows + c0, M.d_par + orr, fbn + kBnConv, xin, fkeep, ds, gz3,
+                       h->fit.d_pconv, h->fit.d_gdense, T, bc * T, grad ? 1 : 0, c0 > 0 ? 1 : 0, dh2, fbn + kBnS2};
+      const RlArgs r1{h->fit.feats, d_rows + c0, M.d_par, fbn + kBnS1, fbn + kBnH1, h1, x1b, gz1, cs1, dh1,
                       h->fit.d_grd, 32, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
-      const RlArgs r2{x1b, h->fit.d_ident, M.d_par + kR1N, dmod.all + dmod.l_s[1], dmod.all + dmod.l_h[1], h2, xin, gz2, cs2, dh2,
+      const RlArgs r2{x1b, h->fit.d_ident, M.d_par + kR1N, fbn + kBnS2, fbn + kBnH2, h2, xin, gz2, cs2, dh2,
                       full ? h->fit.d_grd + kR1N : nullptr, 192, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
       if (full) {                                           // lstm1, lstm2 (X2b into columns 0 .. 127 of Xin), then S into the rest
         if (h->act == 0) {
@@ -4609,12 +4685,13 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
         }
         hipLaunchKernelGGL(sig_forward_kernel<false>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
       } else if (sg) hipLaunchKernelGGL(sig_forward_kernel<true>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
-      const L3Args l3a{sg ? xin : h->fit.xin[model], sg ? h->fit.d_ident : d_rows + c0, M.d_par + os, dmod.all + dmod.l_s[2], dmod.all + dmod.l_h[2], h3, xb4, gz3, cs3, dx3, gz,
+      const L3Args l3a{sg ? xin : h->fit.xin[model], sg ? h->fit.d_ident : d_rows + c0, M.d_par + os, fbn + kBnS3, fbn + kBnH3, h3, xb4, gz3, cs3, dx3, gz,
                        h->fit.d_gl3, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
       if (l3) {                                             // lstm3 forward: the scratch XB is "the set" of the lstm4 launches
         if (h->act == 0) hipLaunchKernelGGL(l3_forward_kernel<0>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
         else hipLaunchKernelGGL(l3_forward_kernel<1>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
       }
+      if (bn_stage >= 0) { fit_bn_moments(h, model, bn_stage, c0, bc, b, sa, h1, h2, h3); continue; }
       const L4Args la{l3 ? xb4 : h->fit.xb[model], l3 ? h->fit.d_ident : d_rows + c0, M.d_par + o3, x4, gz, cs, dx4, h->fit.d_gl4, T, bc,
                       grad ? 1 : 0, c0 > 0 ? 1 : 0};
       if (h->act == 0) hipLaunchKernelGGL(l4_forward_kernel<0>, dim3(tiles, 2), dim3(256), 0, h->stream, la);
@@ -4631,7 +4708,7 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
       else hipLaunchKernelGGL(l4_backward_kernel<1>, dim3(tiles, 2), dim3(256), 0, h->stream, la);
       hipLaunchKernelGGL(l4_wgrad_kernel, dim3(kL4WgM * kL4WgN, 2), dim3(256), 0, h->stream, la);
       if (l3) {
-        const L4DxArgs da{gz, M.d_par + o3, dmod.all + dmod.l_s[2], dx3, bc * T};
+        const L4DxArgs da{gz, M.d_par + o3, fbn + kBnS3, dx3, bc * T};
         hipLaunchKernelGGL(l4_dx_kernel, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, da);
         if (h->act == 0) hipLaunchKernelGGL(l3_backward_kernel<0>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
         else hipLaunchKernelGGL(l3_backward_kernel<1>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
@@ -4644,7 +4721,7 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
         hipLaunchKernelGGL(sig_wgrad_kernel, dim3(kSgWgM, 2), dim3(512), 0, h->stream, sa);
       }
       if (full) {
-        const RlDxArgs dxa{gz2, M.d_par + kR1N, dmod.all + dmod.l_s[0], dh1, bc * T};
+        const RlDxArgs dxa{gz2, M.d_par + kR1N, fbn + kBnS1, dh1, bc * T};
         if (h->act == 0) hipLaunchKernelGGL((rl_backward_kernel<32, 64, 0>), dim3(tiles, 2), dim3(256), 0, h->stream, r2);
         else hipLaunchKernelGGL((rl_backward_kernel<32, 64, 1>), dim3(tiles, 2), dim3(256), 0, h->stream, r2);
         hipLaunchKernelGGL((rl_dx_kernel<32, 64>), dim3((bc * T + 31) / 32), dim3(64), 0, h->stream, dxa);
@@ -4654,6 +4731,7 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
         hipLaunchKernelGGL((rl_wgrad_kernel<6, 16>), dim3(1, 2, kRdSlices), dim3(256), 0, h->stream, r1);
       }
     }
+    if (bn_stage >= 0) return;
     // the LSTM block is one "partial" of its own; the head's partials behind it; the flags of both launches in one array
     // (at depth NRV_FIT_LSTM3 the lstm3 block is one more single "partial" in front)
     // (at depth NRV_FIT_SIGNAL the conv block's partials and the dense block in front of that; 25896 is no multiple of 256, so
@@ -4768,6 +4846,83 @@ int nrv_fit_params(nrv_handle* h, int model, float* params, int64_t* t) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (params) HIPCHK(h, hipMemcpy(params, h->fit.m[model].d_par, (size_t)fit_params_n(h, model) * 4, hipMemcpyDeviceToHost));
   if (t) *t = h->fit.m[model].t;
+  return NRV_OK;
+}
+
+// the BatchNorms inside the fitted section, as indices into kFitBn, in tensor order -> their number
+static int fit_bn_list(const nrv_handle* h, int (&list)[5]) {
+  static const int full[5] = {0, 1, 2, 3, 4}, sig[3] = {0, 1, 4};
+  const int d = h->fit.depth, n = d == NRV_FIT_FULL ? 5 : d == NRV_FIT_SIGNAL ? 3 : d == NRV_FIT_LSTM3 ? 1 : 0;
+  for (int i = 0; i < n; ++i) list[i] = n == 5 ? full[i] : n == 3 ? sig[i] : 4;
+  return n;
+}
+
+int nrv_fit_bn_count(nrv_handle* h) {
+  const int rc = check_handle(h);
+  int list[5];
+  return rc ? rc : fit_bn_list(h, list);
+}
+
+int nrv_fit_bn_reestimate(nrv_handle* h, int model, const uint32_t* rows, int64_t n_rows) {
+  static const char* who = "nrv_fit_bn_reestimate";
+  int rc = fit_enter(h, who);
+  if (rc) return rc;
+  int list[5];
+  const int nbn = fit_bn_list(h, list);
+  if (!nbn) return fit_refuse(h, who, "no BatchNorm lies inside the fitted section (depths NRV_FIT_LSTM3, NRV_FIT_SIGNAL and NRV_FIT_FULL have one)");
+  if (n_rows <= 0 || n_rows > INT32_MAX) return fit_refuse(h, who, "n_rows outside 1 .. 2^31 - 1");
+  if ((rc = fit_rows_in(h, who, model, rows, n_rows))) return rc;
+  nrv_handle::Fit::Model& M = h->fit.m[model];
+  const DevModel& d = h->dm[model];
+  const int T = h->T, b = (int)n_rows;
+  if ((rc = fit_step_scratch(h, model, b < kL4ChunkRows ? b : kL4ChunkRows, false)) ||
+      (rc = fit_scratch(h, (void**)&h->fit.d_bnpart, &h->fit.cap_bnpart, ((size_t)kL4ChunkRows * T / kBnRows * 512 + 512 + ((size_t)kL4ChunkRows * T / 256 + 1) * 16) * 8)))
+    return rc;
+  std::vector<float> blk((size_t)kBnFloats);
+  std::vector<double> acc((size_t)2 * kBnCh);
+  for (int stage = nbn == 1 ? 2 : 0; stage < 3; ++stage) {
+    fit_launch(h, model, h->fit.d_order, b, kTailEval, 0, nullptr, stage);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(blk.data(), M.d_bn, blk.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(acc.data(), M.d_bnacc, acc.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // the stage's BatchNorms: the new statistics folded as nrv_create folds the tensors of a file, into the block
+    static const int stage_of[5] = {0, 1, 0, 1, 2}, at_s[5] = {kBnConv + 32, kBnConv + 248, kBnS1, kBnS2, kBnS3},
+                     at_h[5] = {kBnConv + 40, kBnConv + 256, kBnH1, kBnH2, kBnH3};
+    for (int i = 0; i < nbn; ++i) {
+      const int w = list[i], at = kFitBn[w].at, C = kFitBn[w].C;
+      if (stage_of[w] != stage) continue;
+      for (int c = 0; c < C; ++c) {
+        M.bn_mean[at + c] = blk[kBnMean + at + c]; M.bn_var[at + c] = blk[kBnVar + at + c];
+        M.bn_s1[at + c] = acc[at + c]; M.bn_s2[at + c] = acc[kBnCh + at + c];
+      }
+      M.bn_n[w] = (int64_t)b * T * (w < 2 ? kSig : 1);
+      std::vector<float> sc(C), sh(C);
+      bn_fold(d.bn_raw[0].data() + at, d.bn_raw[1].data() + at, M.bn_mean.data() + at, M.bn_var.data() + at, C, sc.data(), sh.data());
+      HIPCHK(h, hipMemcpy(M.d_bn + at_s[w], sc.data(), (size_t)C * 4, hipMemcpyHostToDevice));
+      HIPCHK(h, hipMemcpy(M.d_bn + at_h[w], sh.data(), (size_t)C * 4, hipMemcpyHostToDevice));
+    }
+  }
+  return NRV_OK;
+}
+
+int nrv_fit_bn_get(nrv_handle* h, int model, int which, nrv_fit_bn_info* info, float* mean, float* var, double* s1, double* s2) {
+  static const char* who = "nrv_fit_bn_get";
+  const int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (model != 0 && model != 1) return fit_refuse(h, who, "model must be 0 or 1");
+  int list[5];
+  const int nbn = fit_bn_list(h, list);
+  if (!nbn) return fit_refuse(h, who, "no BatchNorm lies inside the fitted section (depths NRV_FIT_LSTM3, NRV_FIT_SIGNAL and NRV_FIT_FULL have one)");
+  const nrv_handle::Fit::Model& M = h->fit.m[model];
+  if (!M.begun) return fit_refuse(h, who, "no fit in progress for this model (call nrv_fit_begin first)");
+  if (which < 0 || which >= nbn) return fit_refuse(h, who, "which outside 0 .. nrv_fit_bn_count - 1");
+  const int w = list[which], at = kFitBn[w].at, C = kFitBn[w].C;
+  if (info) *info = nrv_fit_bn_info{kFitBn[w].tensor, C, M.bn_n[w]};
+  if (mean) memcpy(mean, M.bn_mean.data() + at, (size_t)C * 4);
+  if (var) memcpy(var, M.bn_var.data() + at, (size_t)C * 4);
+  if (s1) memcpy(s1, M.bn_s1.data() + at, (size_t)C * 8);
+  if (s2) memcpy(s2, M.bn_s2.data() + at, (size_t)C * 8);
   return NRV_OK;
 }
 

@@ -52,6 +52,7 @@ SYMBOLS = [
     "nrv_fit_set_rows_lstm3", "nrv_fit_get_rows_lstm3",
     "nrv_fit_set_rows_signal", "nrv_fit_get_rows_signal",
     "nrv_fit_set_rows_full", "nrv_fit_get_rows_full",
+    "nrv_fit_bn_reestimate", "nrv_fit_bn_count", "nrv_fit_bn_get",
 ]
 FIT_TAIL, FIT_HEAD, FIT_LSTM4 = 0, 1, 4    # NRV_FIT_TAIL, NRV_FIT_HEAD, NRV_FIT_LSTM4 (the Bi-LSTM the fit starts at)
 FIT_LSTM3 = 8                              # NRV_FIT_LSTM3
@@ -171,6 +172,10 @@ class _FitStats(C.Structure):                                                   
                 ("ce_sum", C.c_double), ("center_sum", C.c_double)]
 
 
+class _FitBnInfo(C.Structure):                                                               # nrv_fit_bn_info
+    _fields_ = [("tensor_base", C.c_int), ("channels", C.c_int), ("n", C.c_int64)]
+
+
 _FIT_T = {                                                                                   # the nrv_fit_* family
     "nrv_fit_reset": [C.c_void_p],
     "nrv_fit_count": [C.c_void_p],
@@ -194,6 +199,9 @@ _FIT_T = {                                                                      
     "nrv_fit_get_rows_signal": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _FP, _U8P, _U8P],
     "nrv_fit_set_rows_full": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
     "nrv_fit_get_rows_full": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
+    "nrv_fit_bn_reestimate": [C.c_void_p, C.c_int, _U32P, C.c_int64],
+    "nrv_fit_bn_count": [C.c_void_p],
+    "nrv_fit_bn_get": [C.c_void_p, C.c_int, C.c_int, C.POINTER(_FitBnInfo), _FP, _FP, _DP, _DP],
 }
 
 
@@ -1019,6 +1027,31 @@ class Reviser:
         s = _FitStats()
         self._check(self._lib.nrv_fit_eval(self._h, model, _ptr(r, _U32P), r.size, _ptr(p, _FP), C.byref(s)))
         return p, self._fit_stats(s)
+
+    def fit_bn_reestimate(self, model, rows):
+        """Re-estimate the moving statistics of every BatchNorm inside the fitted section over `rows` of the set, at the
+        current parameters (bnfit.py is the definition); the fit of this model runs on them from here on.  -> fit_bn_stats."""
+        r = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        self._check(self._lib.nrv_fit_bn_reestimate(self._h, model, _ptr(r, _U32P), r.size))
+        return self.fit_bn_stats(model)
+
+    def fit_bn_stats(self, model):
+        """-> {name: dict(tensor_base, n, mean, var f32, s1, s2 f64)} of the BatchNorms inside the fitted section; n = 0 and the
+        loaded statistics before any re-estimation."""
+        from .bnfit import BATCHNORMS
+        names = {base: k for k, (base, _) in BATCHNORMS.items()}
+        out = {}
+        count = self._lib.nrv_fit_bn_count(self._h)
+        if count < 0:
+            self._check(count)
+        for which in range(count):
+            info = _FitBnInfo()
+            self._check(self._lib.nrv_fit_bn_get(self._h, model, which, C.byref(info), None, None, None, None))
+            mean, var = np.empty(info.channels, np.float32), np.empty(info.channels, np.float32)
+            s1, s2 = np.empty(info.channels, np.float64), np.empty(info.channels, np.float64)
+            self._check(self._lib.nrv_fit_bn_get(self._h, model, which, None, _ptr(mean, _FP), _ptr(var, _FP), _ptr(s1, _DP), _ptr(s2, _DP)))
+            out[names[info.tensor_base]] = {"tensor_base": int(info.tensor_base), "n": int(info.n), "mean": mean, "var": var, "s1": s1, "s2": s2}
+        return out
 
     def fit_params(self, model):
         """-> (the parameter vector, t)."""

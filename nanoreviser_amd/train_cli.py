@@ -28,6 +28,12 @@ fits: every tensor that is no BatchNorm's.  A window is its raw inputs, 50 T nor
 (nanoreviser_amd/fullfit.py is the definition; the five BatchNorms stay frozen in their inference form, Dropout is not applied).
 The four LSTMs and the signal branch start from the loaded or continued model's own weights; --fit_init acts on the layers
 behind lstm4, and a fresh initialisation of the LSTMs is not offered.
+
+--bn_reestimate (off by default; --fit_depth signal or full) re-estimates the moving statistics of the BatchNorms inside the
+fitted section - three at signal depth, all five at full depth - on the device from the TRAINING rows, behind fit_begin and before
+the first epoch, at the starting parameters (nanoreviser_amd/bnfit.py is the definition).  Every epoch and every validation pass
+then runs on the new statistics, the written model carries them, and _summary.json gains a `bn_reestimate` entry.  gamma and beta
+stay the loaded ones.  With -e 0 nothing is fitted and the loaded model is written with re-estimated statistics alone.
 """
 from __future__ import annotations
 
@@ -40,7 +46,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import cli, fullfit, headfit, lstm4fit, signalfit, tailfit
+from . import bnfit, cli, fullfit, headfit, lstm4fit, signalfit, tailfit
 from .weights import load_model, load_species
 
 HISTORY_HEAD = "epoch\tloss\tce\tcenter\tacc\tval_loss\tval_acc\tnonfinite"
@@ -72,6 +78,9 @@ def get_args(argv: Optional[Sequence[str]] = None):
                         "last Bi-LSTM too (it always starts from the model's own weights); signal: the signal branch (0, 1, 6, 7, "
                         "32, 33) and lstm3 (34 .. 39) in front of that, from the model's own weights; full: lstm1 (12 .. 17) and "
                         "lstm2 (22 .. 27) too - every tensor that is no BatchNorm's")
+    p.add_argument("--bn_reestimate", action="store_true", default=argparse.SUPPRESS,        # (in the namespace only when given)
+                   help="re-estimate the moving statistics of the BatchNorms inside the fitted section from the training rows before "
+                        "the first epoch (--fit_depth signal or full); with -e 0 that alone is written")
     p.add_argument("--model_dir", default=None, help="root of model/<species>/ (default: next to the package)")
     p.add_argument("-g", "--basecall_group", dest="basecall_group", default="Basecall_1D_000")
     p.add_argument("-s", "--basecall_subgroup", dest="basecall_subgroup", default="BaseCalled_template")
@@ -87,6 +96,11 @@ def _weights(text, n, what):
     if len(w) != n or any(not np.isfinite(x) or x < 0 for x in w):
         raise ValueError(f"{what} takes {n} non-negative numbers separated by commas")
     return tuple(w)
+
+
+def bn_reestimate(a) -> bool:
+    """--bn_reestimate was given."""
+    return bool(getattr(a, "bn_reestimate", False))
 
 
 def check_args(a):
@@ -107,8 +121,10 @@ def check_args(a):
         return "--fit_init must be transfer or fresh" + (f" or fresh_head, not {a.fit_init!r}" if a.fit_depth != "tail" else "")
     if a.window_size is not None and not 1 <= a.window_size <= 32:
         return "-w must be in 1 .. 32"
-    if a.epochs < 1:
-        return "-e must be at least 1"
+    if bn_reestimate(a) and a.fit_depth not in ("signal", "full"):
+        return f"--bn_reestimate: no BatchNorm lies inside the fitted section at --fit_depth {a.fit_depth} (signal and full have them)"
+    if a.epochs < (0 if bn_reestimate(a) else 1):
+        return "-e must be at least 1" + (" (0 with --bn_reestimate)" if a.epochs < 0 else "")
     if not 1 <= a.batch_size <= tailfit.MAX_BATCH:
         return f"-b must be in 1 .. {tailfit.MAX_BATCH}"
     if not 0.0 <= a.validation_split < 1.0:
@@ -239,10 +255,11 @@ def add_reads(a, rv, log=print):
 
 
 def fit_model(a, rv, k, theta0, n_train, n_val, log=print):
-    """-> (theta, history lines)."""
+    """-> (theta, history lines, the re-estimated BatchNorm statistics or None)."""
     C = 6 if k == 0 else 5
     opts = tailfit.FitOpts(B=a.batch_size, lr=a.lr, lam=a.center_weight, cw=a.cw1 if k == 0 else a.cw2)
     rv.fit_begin(k, theta0, opts)
+    bn_stats = rv.fit_bn_reestimate(k, np.arange(n_train, dtype=np.uint32)) if bn_reestimate(a) else None
     val = np.arange(n_train, n_train + n_val, dtype=np.uint32)
     lines = []
     for ep in range(a.epochs):
@@ -257,7 +274,7 @@ def fit_model(a, rv, k, theta0, n_train, n_val, log=print):
         log(f"[s:::] model{k + 1} epoch {ep + 1}/{a.epochs}: loss {loss:.4f} acc {st.acc():.4f} val_loss {vl} val_acc {va}")
     theta, _ = rv.fit_params(k)
     assert theta.size == _DEPTHS[a.fit_depth].n_params(rv.T, C)
-    return theta, lines
+    return theta, lines, bn_stats
 
 
 def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
@@ -292,12 +309,13 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
         os.makedirs(os.path.join(a.output_model, a.species), exist_ok=True)
         which = [k for k in (0, 1) if a.model_type in ("both", f"model{k + 1}")]
         for k in which:
-            theta, lines = fit_model(a, rv, k, starts[k][0], n_train, n_val)
+            theta, lines, bn_stats = fit_model(a, rv, k, starts[k][0], n_train, n_val)
             st = stem(a.output_model, a.species, k + 1)
             m = (m1, m2)[k]
             deep = a.fit_depth != "tail"
             fit = _DEPTHS[a.fit_depth]
-            tailfit.write_f32(fit.fitted_model(m, theta, T), st)
+            fitted = fit.fitted_model(m, theta, T)
+            tailfit.write_f32(bnfit.with_stats(fitted, bn_stats) if bn_stats else fitted, st)
             fit.unpack(theta, T, m.n_class)[-1].astype("<f4").tofile(st + "_centers.f32")
             with open(st + "_history.tsv", "w") as fp:
                 fp.write(HISTORY_HEAD + "\n" + "\n".join(lines) + "\n")
@@ -307,6 +325,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
                                        "center_weight": a.center_weight, "class_weight": list(a.cw1 if k == 0 else a.cw2),
                                        "init": starts[k][1], "labels_from": os.path.abspath(a.labels_from),
                                        **({"fit_depth": a.fit_depth} if deep else {})},
+                           **({"bn_reestimate": bnfit.drift(bnfit.bn_of(m), bn_stats)} if bn_stats else {}),
                            "rows": n, "train_rows": n_train, "val_rows": n_val, "reads": used,
                            "skipped_reads": [list(s) for s in skipped], "seconds": round(time.time() - t0, 3)}, fp, indent=1)
                 fp.write("\n")

@@ -9,6 +9,10 @@ untimed epochs first (first launches load code objects and size the scratch buff
 and the spread (min .. max) are printed as rows/s, then one JSON line with everything.
 
     python tools/fit_bench.py [--rows 65536] [-b 512] [-w 11] [--warmup 3] [--repeats 9] [--model 0] [--depths tail,head,lstm4,lstm3,signal,full]
+
+--bn_reestimate times nrv_fit_bn_reestimate over all rows instead of the epoch (depths lstm3, signal and full; give them with
+--depths), by the same protocol, and in the same process nrv_fit_eval over the same rows as the yardstick: the rate in rows/s and
+the ratio of a re-estimation to its number of passes (three at signal and full depth, one at lstm3 depth) x one nrv_fit_eval.
 """
 import argparse
 import json
@@ -67,8 +71,9 @@ def main(argv=None):
     ap.add_argument("--species", default="ecoli")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--depths", default="tail,head,lstm4,lstm3", help="the depths to time, in this order (signal and full are not in the default)")
+    ap.add_argument("--bn_reestimate", action="store_true", help="time nrv_fit_bn_reestimate against nrv_fit_eval instead of the epoch")
     a = ap.parse_args(argv)
-    from nanoreviser_amd import fullfit, headfit, lstm3fit, lstm4fit, signalfit, tailfit
+    from nanoreviser_amd import bnfit, fullfit, headfit, lstm3fit, lstm4fit, signalfit, tailfit
     from nanoreviser_amd.engine import Reviser
     from nanoreviser_amd.weights import load_species
     T, k, n = a.window_size, a.model, a.rows
@@ -119,6 +124,32 @@ def main(argv=None):
                 rv.fit_set_rows_head(X, X, y1, y2)
                 th = headfit.fresh_params(T, C, a.seed)
             rv.fit_begin(k, th, opts)
+            if a.bn_reestimate:
+                rows = np.arange(n, dtype=np.uint32)
+                passes = len(bnfit.stages(depth))
+                calls = {"eval": lambda: rv.fit_eval(k, rows, want_p=False), "bn_reestimate": lambda: rv.fit_bn_reestimate(k, rows)}
+                secs = {}
+                for name, call in calls.items():           # nrv_fit_eval first: its kernels read the handle's statistics either way
+                    for _ in range(a.warmup):
+                        call()
+                    t = []
+                    for _ in range(a.repeats):
+                        t0 = time.perf_counter()
+                        call()                             # both return after the stream's synchronise
+                        t.append(time.perf_counter() - t0)
+                    secs[name] = np.array(t)
+                ev, bn = secs["eval"], secs["bn_reestimate"]
+                ratio = bn / (passes * np.median(ev))
+                out[depth] = {"passes": passes, "eval_ms_median": float(np.median(ev) * 1e3), "eval_ms_min": float(ev.min() * 1e3),
+                              "eval_ms_max": float(ev.max() * 1e3), "bn_ms_median": float(np.median(bn) * 1e3),
+                              "bn_ms_min": float(bn.min() * 1e3), "bn_ms_max": float(bn.max() * 1e3),
+                              "bn_rows_per_s_median": float(np.median(n / bn)), "bn_rows_per_s_min": float((n / bn).min()),
+                              "bn_rows_per_s_max": float((n / bn).max()), "ratio_to_eval_passes_median": float(np.median(ratio)),
+                              "ratio_to_eval_passes_min": float(ratio.min()), "ratio_to_eval_passes_max": float(ratio.max())}
+                print(f"{depth}: nrv_fit_bn_reestimate {np.median(n / bn):,.0f} rows/s (min {(n / bn).min():,.0f}, max {(n / bn).max():,.0f}), "
+                      f"{np.median(bn) * 1e3:.2f} ms; nrv_fit_eval {np.median(ev) * 1e3:.2f} ms (min {ev.min() * 1e3:.2f}, max "
+                      f"{ev.max() * 1e3:.2f}); ratio to {passes} x eval {np.median(ratio):.3f} (min {ratio.min():.3f}, max {ratio.max():.3f})")
+                continue
             for ep in range(a.warmup):
                 rv.fit_epoch(k, tailfit.epoch_order(n, a.seed, ep))
             secs = []
