@@ -458,6 +458,47 @@ static void bn_fold(const float* g, const float* be, const float* mu, const floa
 // the five BatchNorms nrv_fit_bn_* knows, in tensor order: first tensor (gamma), channels, first channel of the block's kBnCh
 static const struct { int tensor, C, at; } kFitBn[5] = {{2, 8, 0}, {8, 8, 8}, {18, 32, 16}, {28, 128, 48}, {40, 256, 176}};
 
+// The fit depths of nrv_fit_*, in depth order: everything that differs between them on the host.  The set of a depth is its row
+// arrays, each [rows][T][per_t] f32 and either one per model or one shared by both, and y per model; the doors take and return
+// them in this order, a per-model array as two pointers.
+struct FitDepth {
+  int code;                                  // NRV_FIT_*
+  const char *name, *code_name, *suffix;     // in messages; the constant's name; of the nrv_fit_set_rows* / _get_rows* doors
+  const char* phrase;                        // "rows are ..."
+  int n_arrays;
+  struct { int per_t; bool shared; } arrays[2];
+  int (*params)(int T, int C);               // the length of a model's vector
+  int64_t max_rows;                          // the row cap's default ...
+  const char *env, *at;                      // ... its environment variable, and how a cap message names the depth
+  bool mlp, l4, l3, sg, rd;                  // inside the fitted section: the head MLP, lstm4, lstm3, the signal branch, the read branch
+  int n_bn, bn[5];                           // the BatchNorms inside it, as indices into kFitBn, in tensor order
+};
+static const FitDepth kFitDepths[6] = {
+    {NRV_FIT_TAIL, "tail", "NRV_FIT_TAIL", "", "main_out values", 1, {{6, false}}, [](int T, int C) { return NRV_FIT_PARAMS(T, C); },
+     (int64_t)1 << 24, "NRV_FIT_MAX_ROWS", "", false, false, false, false, false, 0, {}},
+    {NRV_FIT_HEAD, "head", "NRV_FIT_HEAD", "_head", "lstm4 outputs", 1, {{128, false}},
+     [](int T, int C) { return NRV_FIT_PARAMS_HEAD(T, C); }, (int64_t)1 << 21, "NRV_FIT_MAX_HEAD_ROWS", " at head depth", true, false, false,
+     false, false, 0, {}},
+    {NRV_FIT_LSTM4, "lstm4", "NRV_FIT_LSTM4", "_lstm4", "BatchNorm'd lstm3 outputs", 1, {{256, false}},
+     [](int T, int C) { return NRV_FIT_PARAMS_LSTM4(T, C); }, (int64_t)1 << 20, "NRV_FIT_MAX_LSTM4_ROWS", " at lstm4 depth", true, true, false,
+     false, false, 0, {}},
+    {NRV_FIT_LSTM3, "lstm3", "NRV_FIT_LSTM3", "_lstm3", "lstm3's inputs", 1, {{192, false}},
+     [](int T, int C) { return NRV_FIT_PARAMS_LSTM3(T, C); }, (int64_t)1 << 20, "NRV_FIT_MAX_LSTM3_ROWS", " at lstm3 depth", true, true, true,
+     false, false, 1, {4}},
+    {NRV_FIT_SIGNAL, "signal", "NRV_FIT_SIGNAL", "_signal", "lstm2 outputs and samples", 2, {{128, false}, {kSig, true}},
+     [](int T, int C) { return NRV_FIT_PARAMS_SIGNAL(T, C); }, (int64_t)1 << 20, "NRV_FIT_MAX_SIGNAL_ROWS", " at signal depth", true, true, true,
+     true, false, 3, {0, 1, 4}},
+    {NRV_FIT_FULL, "full", "NRV_FIT_FULL", "_full", "samples and read features", 2, {{kSig, true}, {kFeat, true}},
+     [](int T, int C) { return NRV_FIT_PARAMS_FULL(T, C); }, (int64_t)1 << 22, "NRV_FIT_MAX_FULL_ROWS", " at full depth", true, true, true,
+     true, true, 5, {0, 1, 2, 3, 4}},
+};
+// the descriptor of a depth code, null for a number that is no depth
+static const FitDepth* fit_desc(int depth) {
+  for (const FitDepth& D : kFitDepths)
+    if (D.code == depth) return &D;
+  return nullptr;
+}
+
 struct DevModel {
   float* all = nullptr;       // one allocation holding every packed tensor of the model
   size_t n = 0;
@@ -684,47 +725,36 @@ struct nrv_handle {
   std::vector<char*> lab_retired;
   hipStream_t lab_stream = nullptr;
   size_t lab_budget = kLabelsBudget;     // bytes of direction words per batch of pairs (NRV_LABELS_BUDGET, read by nrv_create)
-  // nrv_fit_*: the training set of the per-window tail (per model flat [cap][6T] f32 and y [cap] u8, both models the same
-  // rows; grown on demand, poisoned under NRV_POISON, freed by nrv_destroy), the scratch of a step, and per model the
-  // parameter block [theta | m | v | g] with its state on the device.  Everything runs on the handle's stream.
+  // nrv_fit_*: the training set at the current depth (its arrays are kFitDepths' - x [cap][T][per_t] f32 per model, the arrays
+  // both models share, y [cap] u8 per model, both models the same rows; grown on demand, poisoned under NRV_POISON, freed by
+  // nrv_destroy), the scratch of a step, and per model the parameter block [theta | m | v | g] with its state on the device.
+  // Everything runs on the handle's stream.
   struct Fit {
-    float* flat[2] = {nullptr, nullptr};
+    float* x[2] = {nullptr, nullptr};                         // the depth's per-model array (null at depth NRV_FIT_FULL)
+    float* shared[2] = {nullptr, nullptr};                    // the depth's shared arrays in door order: sig; at NRV_FIT_FULL sig, feat
     uint8_t* y[2] = {nullptr, nullptr};
-    int64_t rows = 0, cap = 0, max_rows = (int64_t)1 << 24;   // NRV_FIT_MAX_ROWS, read by nrv_create
-    // depth NRV_FIT_HEAD (nrv_fit_set_depth, on an empty set only): the set is x4 [cap][T][128] and y, flat stays null; the
-    // other depth's arrays and both models' parameter blocks are freed when the depth changes, so `cap` counts one kind of row
-    int depth = 0;
-    float* x4[2] = {nullptr, nullptr};
-    int64_t max_head_rows = (int64_t)1 << 21;                 // NRV_FIT_MAX_HEAD_ROWS, read by nrv_create
-    // depth NRV_FIT_LSTM4: the set is xb [cap][T][256] and y; the scratch of one chunk of a batch (nrv_lstm4fit.h) and the
-    // LSTM block's gradient sums
-    float* xb[2] = {nullptr, nullptr};
-    int64_t max_lstm4_rows = (int64_t)1 << 20;                // NRV_FIT_MAX_LSTM4_ROWS, read by nrv_create
+    int64_t rows = 0, cap = 0;
+    int64_t max_rows[6] = {};                                 // the row cap of each depth of kFitDepths, set by nrv_create
+    // nrv_fit_set_depth (on an empty set only) frees the set and both models' parameter blocks when the depth changes, so
+    // `cap` counts one kind of row
+    int depth = NRV_FIT_TAIL;
+    // depth NRV_FIT_LSTM4 and deeper: the scratch of one chunk of a batch (nrv_lstm4fit.h) and the LSTM block's gradient sums
     float* d_l4 = nullptr; size_t cap_l4 = 0;                 // [X4 | dX4 | CS | GZ] of kL4ChunkRows rows
     float* d_gl4 = nullptr; size_t cap_gl4 = 0;               // [kL4N]
-    // depth NRV_FIT_LSTM3: the set is xin [cap][T][192] and y; one chunk's [H3 | XB | dX3 | CS | GZ] (nrv_lstm3fit.h) in front of
-    // the lstm4 depth's scratch, the lstm3 block's gradient sums, the identity row list of the lstm4 launches; while
-    // nrv_fit_add_reads_raw runs, l3_slot is the slot list of the group run_group is at (the gather runs inside the group)
-    float* xin[2] = {nullptr, nullptr};
-    int64_t max_lstm3_rows = (int64_t)1 << 20;                // NRV_FIT_MAX_LSTM3_ROWS, read by nrv_create
+    // depth NRV_FIT_LSTM3 and deeper: one chunk's [H3 | XB | dX3 | CS | GZ] (nrv_lstm3fit.h) in front of the lstm4 depth's
+    // scratch, the lstm3 block's gradient sums, the identity row list of the lstm4 launches; while nrv_fit_add_reads_raw runs,
+    // l3_slot is the slot list of the group run_group is at (the gather runs inside the group)
     float* d_l3 = nullptr; size_t cap_l3 = 0;
     float* d_gl3 = nullptr; size_t cap_gl3 = 0;               // [kL3N]
     unsigned* d_ident = nullptr;                              // [kL4ChunkRows] 0, 1, 2, ...
     const int* l3_slot = nullptr;
-    // depth NRV_FIT_SIGNAL: the set is x2 [cap][T][128] per model, ONE sig [cap][T][50] for both and y; one chunk's
-    // [Xin | F | dS] (nrv_signalfit.h) in front of the lstm3 depth's scratch, the conv block's partials and the dense block's sums;
-    // the gather runs where the lstm3 depth's does, on l3_slot
-    float* x2s[2] = {nullptr, nullptr};
-    float* sigs = nullptr;
-    int64_t max_signal_rows = (int64_t)1 << 20;               // NRV_FIT_MAX_SIGNAL_ROWS, read by nrv_create
+    // depth NRV_FIT_SIGNAL and deeper: one chunk's [Xin | F | dS] (nrv_signalfit.h) in front of the lstm3 depth's scratch, the
+    // conv block's partials and the dense block's sums; the gather runs where the lstm3 depth's does, on l3_slot
     float* d_sg = nullptr; size_t cap_sg = 0;
     float* d_pconv = nullptr; size_t cap_pconv = 0;           // [workgroups][kSgConv]
     float* d_gdense = nullptr; size_t cap_gdense = 0;         // [kSgDense]
-    // depth NRV_FIT_FULL: the set is ONE sig [cap][T][50] (sigs) and ONE feat [cap][T][6] for both models and y; one chunk's
-    // [X1b | H1 | H2 | dH2 | dH1 | CS1 | CS2 | GZ1 | GZ2] (nrv_fullfit.h) in front of the signal depth's scratch, the read
-    // block's kRdSlices partials
-    float* feats = nullptr;
-    int64_t max_full_rows = (int64_t)1 << 22;                 // NRV_FIT_MAX_FULL_ROWS, read by nrv_create
+    // depth NRV_FIT_FULL: one chunk's [X1b | H1 | H2 | dH2 | dH1 | CS1 | CS2 | GZ1 | GZ2] (nrv_fullfit.h) in front of the signal
+    // depth's scratch, the read block's kRdSlices partials
     float* d_rd = nullptr; size_t cap_rd = 0;
     float* d_grd = nullptr; size_t cap_grd = 0;               // [kRdSlices][kRdN]
     int* d_flag = nullptr; size_t cap_flag = 0;               // head_reduce_kernel's per-workgroup flags
@@ -775,6 +805,9 @@ namespace {
       return NRV_E_HIP;                                                                  \
     }                                                                                    \
   } while (0)
+
+// the descriptor of the handle's fit depth (nrv_fit_set_depth lets nothing else in)
+static const FitDepth& fit_at(const nrv_handle* h) { return *fit_desc(h->fit.depth); }
 
 // NRV_POISON: the handle's pattern into the 32-bit words of [p, p + bytes), on stream s (nothing when the switch is off)
 static int poison_fill(nrv_handle* h, void* p, size_t bytes, hipStream_t s) {
@@ -1480,10 +1513,10 @@ static int run_group(nrv_handle* h, const float* d_sig, const float* d_feat, int
       launch_lstm_f32<32, 16, 128, 1, 1>(h, a, tiles);
     }
     if ((rc = mark(4))) return rc;
-    if (h->fit.l3_slot && h->fit.depth == NRV_FIT_SIGNAL) {      // ... at depth NRV_FIT_SIGNAL: lstm2's output and the samples
+    if (h->fit.l3_slot && fit_at(h).sg) {        // ... at depth NRV_FIT_SIGNAL: lstm2's output and the samples
       SigGatherArgs g;
-      for (int m = 0; m < 2; ++m) { g.in0[m] = win_view(h->X2[m], 32); g.x2[m] = h->fit.x2s[m]; }
-      g.sig_ev = d_sig; g.sig = h->fit.sigs;
+      for (int m = 0; m < 2; ++m) { g.in0[m] = win_view(h->X2[m], 32); g.x2[m] = h->fit.x[m]; }
+      g.sig_ev = d_sig; g.sig = h->fit.shared[0];
       g.slot = h->fit.l3_slot; g.n = n; g.T = T; g.cap = h->fit.cap;
       const long long total = (long long)n * T * 57;
       hipLaunchKernelGGL(sig_gather_kernel, dim3((unsigned)((total + 255) / 256), 2), dim3(256), 0, h->stream, g);
@@ -1493,7 +1526,7 @@ static int run_group(nrv_handle* h, const float* d_sig, const float* d_feat, int
       for (int m = 0; m < 2; ++m) {
         g.in0[m] = win_view(h->X2[m], 32);
         g.in1[m] = read_mode ? ActView{h->S[m], 16, 1, 1, 0} : win_view(h->S[m], 16);
-        g.x[m] = h->fit.xin[m];
+        g.x[m] = h->fit.x[m];
       }
       g.slot = h->fit.l3_slot; g.n = n; g.T = T; g.cap = h->fit.cap;
       const long long total = (long long)n * T * 48;
@@ -1638,12 +1671,12 @@ int nrv_create(const nrv_weights* m1, const nrv_weights* m2, int T, int device, 
   if (const char* e3 = getenv("NRV_LANES")) h->lanes_on = atoi(e3) != 0;
   if (const char* e4 = getenv("NRV_COALESCE")) h->coalesce = atoi(e4) != 0;
   if (const char* e6 = getenv("NRV_LABELS_BUDGET"); e6 && *e6) { const long long v = atoll(e6); if (v > 0) h->lab_budget = (size_t)v; }
-  if (const char* e7 = getenv("NRV_FIT_MAX_ROWS"); e7 && *e7) { const long long v = atoll(e7); if (v > 0) h->fit.max_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
-  if (const char* e9 = getenv("NRV_FIT_MAX_LSTM4_ROWS"); e9 && *e9) { const long long v = atoll(e9); if (v > 0) h->fit.max_lstm4_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
-  if (const char* e12 = getenv("NRV_FIT_MAX_FULL_ROWS"); e12 && *e12) { const long long v = atoll(e12); if (v > 0) h->fit.max_full_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
-  if (const char* e11 = getenv("NRV_FIT_MAX_SIGNAL_ROWS"); e11 && *e11) { const long long v = atoll(e11); if (v > 0) h->fit.max_signal_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
-  if (const char* e10 = getenv("NRV_FIT_MAX_LSTM3_ROWS"); e10 && *e10) { const long long v = atoll(e10); if (v > 0) h->fit.max_lstm3_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
-  if (const char* e8 = getenv("NRV_FIT_MAX_HEAD_ROWS"); e8 && *e8) { const long long v = atoll(e8); if (v > 0) h->fit.max_head_rows = v > ((long long)1 << 31) - 1 ? ((long long)1 << 31) - 1 : v; }
+  for (int i = 0; i < 6; ++i) {                             // the row caps of the fit depths: the default, or the depth's variable
+    const long long lim = ((long long)1 << 31) - 1;
+    const char* e = getenv(kFitDepths[i].env);
+    const long long v = e && *e ? atoll(e) : 0;
+    h->fit.max_rows[i] = v > 0 ? (v > lim ? lim : v) : kFitDepths[i].max_rows;
+  }
   if (const char* e5 = getenv("NRV_POISON"); e5 && *e5) { h->poison_on = true; h->poison = (unsigned)strtoul(e5, nullptr, 16); }
   ok = ok && hipMalloc((void**)&h->d_sat, 4 * sizeof(unsigned)) == hipSuccess &&
        hipMemset(h->d_sat, 0, 4 * sizeof(unsigned)) == hipSuccess;
@@ -1677,16 +1710,15 @@ void nrv_destroy(nrv_handle* h) {
   (void)hipFree(h->d_lab);
   for (char* p : h->lab_retired) (void)hipFree(p);
   for (int m = 0; m < 2; ++m) {
-    (void)hipFree(h->fit.flat[m]); (void)hipFree(h->fit.y[m]); (void)hipFree(h->fit.x4[m]); (void)hipFree(h->fit.xb[m]); (void)hipFree(h->fit.xin[m]);
-    (void)hipFree(h->fit.x2s[m]);
+    (void)hipFree(h->fit.x[m]); (void)hipFree(h->fit.shared[m]); (void)hipFree(h->fit.y[m]);
     (void)hipFree(h->fit.m[m].d_par); (void)hipFree(h->fit.m[m].d_state); (void)hipFree(h->fit.m[m].d_lr);
     (void)hipFree(h->fit.m[m].d_bn); (void)hipFree(h->fit.m[m].d_bnacc);
   }
   (void)hipFree(h->fit.d_partial); (void)hipFree(h->fit.d_pstat); (void)hipFree(h->fit.d_order); (void)hipFree(h->fit.d_p); (void)hipFree(h->fit.d_flag);
   (void)hipFree(h->fit.d_l4); (void)hipFree(h->fit.d_gl4); (void)hipFree(h->fit.d_bnpart);
   (void)hipFree(h->fit.d_l3); (void)hipFree(h->fit.d_gl3); (void)hipFree(h->fit.d_ident);
-  (void)hipFree(h->fit.feats); (void)hipFree(h->fit.d_rd); (void)hipFree(h->fit.d_grd);
-  (void)hipFree(h->fit.sigs); (void)hipFree(h->fit.d_sg); (void)hipFree(h->fit.d_pconv); (void)hipFree(h->fit.d_gdense);
+  (void)hipFree(h->fit.d_rd); (void)hipFree(h->fit.d_grd);
+  (void)hipFree(h->fit.d_sg); (void)hipFree(h->fit.d_pconv); (void)hipFree(h->fit.d_gdense);
   for (int st = 0; st < nrv_handle::kIn; ++st) if (h->ev_in[st]) (void)hipEventDestroy(h->ev_in[st]);
   for (int st = 0; st < 2; ++st) {
     if (h->ev_done[st]) (void)hipEventDestroy(h->ev_done[st]);
@@ -3796,7 +3828,7 @@ static int fit_enter(nrv_handle* h, const char* who) {
   }
   return NRV_OK;
 }
-static int fit_refuse(nrv_handle* h, const char* who, const char* what) {
+static int fit_refuse(nrv_handle* h, const char* who, const std::string& what) {
   h->err = std::string(who) + ": " + what;
   return NRV_E_INVALID;
 }
@@ -3811,91 +3843,56 @@ static int fit_scratch(nrv_handle* h, void** p, size_t* cap, size_t bytes) {
   *cap = c;
   return poison_fill(h, *p, c, h->stream);
 }
-// floats of one row of the set at the handle's depth, and the parameters of a model's vector
-static size_t fit_row_floats(const nrv_handle* h) {
-  if (h->fit.depth == NRV_FIT_FULL) return 0;                              // (no per-model rows: the shared samples and features only)
-  if (h->fit.depth == NRV_FIT_SIGNAL) return (size_t)h->T * 128;          // (per model; the shared samples are T * 50 more)
-  if (h->fit.depth == NRV_FIT_LSTM3) return (size_t)h->T * 192;
-  return h->fit.depth == NRV_FIT_LSTM4 ? (size_t)h->T * 256 : h->fit.depth ? (size_t)h->T * 128 : 6 * (size_t)h->T;
+// the parameters of a model's vector at the handle's depth, and the depth's row cap with the words a refusal names it by
+static int fit_params_n(const nrv_handle* h, int model) { return fit_at(h).params(h->T, h->dm[model].C); }
+static int64_t fit_cap_rows(const nrv_handle* h) { return h->fit.max_rows[&fit_at(h) - kFitDepths]; }
+static std::string fit_cap_words(const nrv_handle* h) { return std::string(fit_at(h).at) + " (" + fit_at(h).env + ")"; }
+// the arrays of the set at the handle's depth - where the handle keeps each and its bytes per row - in door order: the depth's
+// row arrays, then y of model 0 and of model 1 -> their number
+struct FitArr { void** p; size_t row; };
+static int fit_arrays(nrv_handle* h, FitArr (&a)[6]) {
+  nrv_handle::Fit& F = h->fit;
+  const FitDepth& D = fit_at(h);
+  int n = 0, s = 0;
+  for (int i = 0; i < D.n_arrays; ++i) {
+    const size_t row = (size_t)h->T * D.arrays[i].per_t * 4;
+    if (D.arrays[i].shared) a[n++] = FitArr{(void**)&F.shared[s++], row};
+    else for (int m = 0; m < 2; ++m) a[n++] = FitArr{(void**)&F.x[m], row};
+  }
+  for (int m = 0; m < 2; ++m) a[n++] = FitArr{(void**)&F.y[m], 1};
+  return n;
 }
-static int fit_params_n(const nrv_handle* h, int model) {
-  const int C = h->dm[model].C;
-  if (h->fit.depth == NRV_FIT_FULL) return NRV_FIT_PARAMS_FULL(h->T, C);
-  if (h->fit.depth == NRV_FIT_SIGNAL) return NRV_FIT_PARAMS_SIGNAL(h->T, C);
-  if (h->fit.depth == NRV_FIT_LSTM3) return NRV_FIT_PARAMS_LSTM3(h->T, C);
-  return h->fit.depth == NRV_FIT_LSTM4 ? NRV_FIT_PARAMS_LSTM4(h->T, C) : h->fit.depth ? NRV_FIT_PARAMS_HEAD(h->T, C) : NRV_FIT_PARAMS(h->T, C);
-}
-// the current depth's set and its cap
-static float** fit_set(nrv_handle::Fit& F) { return F.depth == NRV_FIT_SIGNAL ? F.x2s : F.depth == NRV_FIT_LSTM3 ? F.xin : F.depth == NRV_FIT_LSTM4 ? F.xb : F.depth ? F.x4 : F.flat; }
-static int64_t fit_cap_rows(const nrv_handle::Fit& F) { return F.depth == NRV_FIT_FULL ? F.max_full_rows : F.depth == NRV_FIT_SIGNAL ? F.max_signal_rows : F.depth == NRV_FIT_LSTM3 ? F.max_lstm3_rows : F.depth == NRV_FIT_LSTM4 ? F.max_lstm4_rows : F.depth ? F.max_head_rows : F.max_rows; }
 // room for `need` rows in the set, the rows it holds kept
 static int fit_reserve(nrv_handle* h, int64_t need) {
   nrv_handle::Fit& F = h->fit;
   if (need <= F.cap) return NRV_OK;
   int64_t c = F.cap * 2 > need ? F.cap * 2 : need;
   if (c < 1024) c = 1024;
-  const int64_t cmax = fit_cap_rows(F);
+  const int64_t cmax = fit_cap_rows(h);
   if (c > cmax) c = cmax;
-  const size_t K = fit_row_floats(h);
-  float** const set = fit_set(F);
-  float* nf[2] = {nullptr, nullptr};
-  uint8_t* ny[2] = {nullptr, nullptr};
-  float* nsig = nullptr;                                   // depth NRV_FIT_SIGNAL and NRV_FIT_FULL: the samples both models share
-  float* nfeat = nullptr;                                  // depth NRV_FIT_FULL: the features both models share
-  const bool full = F.depth == NRV_FIT_FULL;
+  FitArr a[6];
+  const int n = fit_arrays(h, a);
+  void* grown[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int rc = NRV_OK;
-  if (full) {
-    const size_t KF = (size_t)h->T * kFeat;
-    if (hipMalloc((void**)&nfeat, (size_t)c * KF * 4) != hipSuccess) { h->err = "nrv_fit: out of device memory for the training set"; return NRV_E_NOMEM; }
-    if ((rc = poison_fill(h, nfeat, (size_t)c * KF * 4, h->stream))) { (void)hipFree(nfeat); return rc; }
-    if (F.rows > 0 && hipMemcpyAsync(nfeat, F.feats, (size_t)F.rows * KF * 4, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
-      h->err = "nrv_fit: copying the training set failed";
-      (void)hipFree(nfeat);
-      return NRV_E_HIP;
-    }
-  }
-  if (F.depth == NRV_FIT_SIGNAL || full) {
-    const size_t KS = (size_t)h->T * kSig;
-    if (hipMalloc((void**)&nsig, (size_t)c * KS * 4) != hipSuccess) { h->err = "nrv_fit: out of device memory for the training set"; (void)hipFree(nfeat); return NRV_E_NOMEM; }
-    if ((rc = poison_fill(h, nsig, (size_t)c * KS * 4, h->stream))) { (void)hipFree(nsig); (void)hipFree(nfeat); return rc; }
-    if (F.rows > 0 && hipMemcpyAsync(nsig, F.sigs, (size_t)F.rows * KS * 4, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
-      h->err = "nrv_fit: copying the training set failed";
-      (void)hipFree(nsig); (void)hipFree(nfeat);
-      return NRV_E_HIP;
-    }
-  }
-  for (int m = 0; m < 2 && !rc; ++m) {
-    if ((!full && hipMalloc((void**)&nf[m], (size_t)c * K * 4) != hipSuccess) || hipMalloc((void**)&ny[m], ((size_t)c + 3) / 4 * 4) != hipSuccess) {
+  for (int i = 0; i < n && !rc; ++i) {
+    const size_t bytes = ((size_t)c * a[i].row + 3) / 4 * 4;
+    if (hipMalloc(&grown[i], bytes) != hipSuccess) {
       h->err = "nrv_fit: out of device memory for the training set";
       rc = NRV_E_NOMEM;
-      break;
-    }
-    if ((!full && (rc = poison_fill(h, nf[m], (size_t)c * K * 4, h->stream))) || (rc = poison_fill(h, ny[m], ((size_t)c + 3) / 4 * 4, h->stream))) break;
-    if (F.rows > 0) {
-      if ((!full && hipMemcpyAsync(nf[m], set[m], (size_t)F.rows * K * 4, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) ||
-          hipMemcpyAsync(ny[m], F.y[m], (size_t)F.rows, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
-        h->err = "nrv_fit: copying the training set failed";
-        rc = NRV_E_HIP;
-      }
+    } else if (!(rc = poison_fill(h, grown[i], bytes, h->stream)) && F.rows > 0 &&
+               hipMemcpyAsync(grown[i], *a[i].p, (size_t)F.rows * a[i].row, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
+      h->err = "nrv_fit: copying the training set failed";
+      rc = NRV_E_HIP;
     }
   }
   if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) { h->err = "nrv_fit: growing the training set failed"; rc = NRV_E_HIP; }
-  if (rc) {
-    for (int m = 0; m < 2; ++m) { (void)hipFree(nf[m]); (void)hipFree(ny[m]); }
-    (void)hipFree(nsig); (void)hipFree(nfeat);
-    return rc;
+  for (int i = 0; i < n; ++i) {                            // all of the new arrays, or none
+    if (rc) { (void)hipFree(grown[i]); continue; }
+    (void)hipFree(*a[i].p);
+    *a[i].p = grown[i];
   }
-  if (F.depth == NRV_FIT_SIGNAL || full) { (void)hipFree(F.sigs); F.sigs = nsig; }
-  if (full) { (void)hipFree(F.feats); F.feats = nfeat; }
-  for (int m = 0; m < 2; ++m) {
-    (void)hipFree(F.y[m]);
-    F.y[m] = ny[m];
-    if (full) continue;
-    (void)hipFree(set[m]);
-    set[m] = nf[m];
-  }
-  F.cap = c;
-  return NRV_OK;
+  if (!rc) F.cap = c;
+  return rc;
 }
 
 // Every stage of the call onto the compute stream as raw_enqueue does it, on the kernels the handle's mode selects (the caller
@@ -3903,6 +3900,7 @@ static int fit_reserve(nrv_handle* h, int64_t need) {
 static int fit_enqueue(nrv_handle* h, const char* d_in, size_t off_starts, size_t off_reads, size_t off_feat, const int* d_slot,
                        int n_reads, int64_t n) {
   const int T = h->T;
+  const FitDepth& D = fit_at(h);                           // which gather fills the set: the deepest stage inside the fitted section
   const int stage = stage_windows(h, true);
   const float* d_feat = (const float*)(d_in + off_feat);
   for (int64_t s = 0; s < n; s += stage) {
@@ -3911,15 +3909,15 @@ static int fit_enqueue(nrv_handle* h, const char* d_in, size_t off_starts, size_
     if (rc0) return rc0;
     launch_segment(h, n_reads, s, nb + T - 1, h->d_sig[0], (const int16_t*)d_in, (const int32_t*)(d_in + off_starts),
                    (const SegRead*)(d_in + off_reads));
-    if (h->fit.depth == NRV_FIT_FULL) {                    // the set is the stage's raw inputs: no launch group runs for it
-      const FullGatherArgs g{h->d_sig[0], d_feat + s * kFeat, h->fit.sigs, h->fit.feats, d_slot + s, nb, T, (long long)h->fit.cap};
+    if (D.rd) {                                            // the set is the stage's raw inputs: no launch group runs for it
+      const FullGatherArgs g{h->d_sig[0], d_feat + s * kFeat, h->fit.shared[0], h->fit.shared[1], d_slot + s, nb, T, (long long)h->fit.cap};
       const long long total = (long long)nb * T * 28;
       hipLaunchKernelGGL(full_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, g);
       HIPCHK(h, hipGetLastError());
       continue;
     }
     const int rc = for_groups(h, nb, [&](int64_t w, int nw) -> int {
-      if (h->fit.depth == NRV_FIT_LSTM3 || h->fit.depth == NRV_FIT_SIGNAL) {                 // the gather runs INSIDE the group, between lstm2 and lstm4
+      if (D.l3) {                                          // lstm3's or the signal branch's inputs: the gather runs INSIDE the group, between lstm2 and lstm4
         h->fit.l3_slot = d_slot + s + w;
         const int rc3 = run_group(h, h->d_sig[0] + w * kSig, d_feat + (s + w) * kFeat, nw, true, h->d_p[0][0] + w * 6, h->d_p[0][1] + w * 5,
                                   h->d_a[0][0] + w, h->d_a[0][1] + w, h->d_sat + 3);
@@ -3929,18 +3927,18 @@ static int fit_enqueue(nrv_handle* h, const char* d_in, size_t off_starts, size_
       const int rc1 = run_group(h, h->d_sig[0] + w * kSig, d_feat + (s + w) * kFeat, nw, true, h->d_p[0][0] + w * 6, h->d_p[0][1] + w * 5,
                                 h->d_a[0][0] + w, h->d_a[0][1] + w, h->d_sat + 3);
       if (rc1) return rc1;
-      if (h->fit.depth == NRV_FIT_LSTM4) {                 // lstm4's f32 input (lstm3's output behind its BatchNorm), still in X3
+      if (D.l4) {                                          // lstm4's f32 input (lstm3's output behind its BatchNorm), still in X3
         L4GatherArgs g;
-        for (int m = 0; m < 2; ++m) { g.in[m] = h->X3[m]; g.x[m] = h->fit.xb[m]; }
+        for (int m = 0; m < 2; ++m) { g.in[m] = h->X3[m]; g.x[m] = h->fit.x[m]; }
         g.slot = d_slot + s + w; g.n = nw; g.T = T; g.cap = h->fit.cap;
         const long long total = (long long)nw * T * 64;
         hipLaunchKernelGGL(l4_gather_kernel, dim3((unsigned)((total + 255) / 256), 2), dim3(256), 0, h->stream, g);
         HIPCHK(h, hipGetLastError());
         return (int)NRV_OK;
       }
-      if (h->fit.depth) {                                  // the head's f32 input (lstm4's output) of the group, still in X2
+      if (D.mlp) {                                         // the head's f32 input (lstm4's output) of the group, still in X2
         HeadGatherArgs g;
-        for (int m = 0; m < 2; ++m) { g.in[m] = h->X2[m]; g.x[m] = h->fit.x4[m]; }
+        for (int m = 0; m < 2; ++m) { g.in[m] = h->X2[m]; g.x[m] = h->fit.x[m]; }
         g.slot = d_slot + s + w; g.n = nw; g.T = T; g.cap = h->fit.cap;
         const long long total = (long long)nw * T * 32;
         hipLaunchKernelGGL(head_gather_kernel, dim3((unsigned)((total + 255) / 256), 2), dim3(256), 0, h->stream, g);
@@ -3948,7 +3946,7 @@ static int fit_enqueue(nrv_handle* h, const char* d_in, size_t off_starts, size_
         return (int)NRV_OK;
       }
       TailGatherArgs g;
-      for (int m = 0; m < 2; ++m) { g.mo[m] = h->MO[m]; g.flat[m] = h->fit.flat[m]; }
+      for (int m = 0; m < 2; ++m) { g.mo[m] = h->MO[m]; g.flat[m] = h->fit.x[m]; }
       g.slot = d_slot + s + w; g.n = nw; g.T = T; g.cap = h->fit.cap;
       const long long total = (long long)nw * 6 * T;
       hipLaunchKernelGGL(tail_gather_kernel, dim3((unsigned)((total + 255) / 256), 2), dim3(256), 0, h->stream, g);
@@ -3999,17 +3997,7 @@ int nrv_fit_add_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, cons
     for (int64_t i = 0; i < n_r; ++i) add += lb[i] != 0xFF && (lb[i] & 7) >= 1 && (lb[i] & 7) <= 5;
   }
   nrv_handle::Fit& F = h->fit;
-  if (F.depth == NRV_FIT_FULL && F.rows + add > F.max_full_rows)
-    return fit_refuse(h, who, "the call would pass the row cap of the training set at full depth (NRV_FIT_MAX_FULL_ROWS)");
-  if (F.depth == NRV_FIT_SIGNAL && F.rows + add > F.max_signal_rows)
-    return fit_refuse(h, who, "the call would pass the row cap of the training set at signal depth (NRV_FIT_MAX_SIGNAL_ROWS)");
-  if (F.depth == NRV_FIT_LSTM3 && F.rows + add > F.max_lstm3_rows)
-    return fit_refuse(h, who, "the call would pass the row cap of the training set at lstm3 depth (NRV_FIT_MAX_LSTM3_ROWS)");
-  if (F.depth == NRV_FIT_LSTM4 && F.rows + add > F.max_lstm4_rows)
-    return fit_refuse(h, who, "the call would pass the row cap of the training set at lstm4 depth (NRV_FIT_MAX_LSTM4_ROWS)");
-  if (F.depth == NRV_FIT_HEAD && F.rows + add > F.max_head_rows)
-    return fit_refuse(h, who, "the call would pass the row cap of the training set at head depth (NRV_FIT_MAX_HEAD_ROWS)");
-  if (!F.depth && F.rows + add > F.max_rows) return fit_refuse(h, who, "the call would pass the row cap of the training set (NRV_FIT_MAX_ROWS)");
+  if (F.rows + add > fit_cap_rows(h)) return fit_refuse(h, who, "the call would pass the row cap of the training set" + fit_cap_words(h));
   if (add == 0) return NRV_OK;
   if ((rc = fit_reserve(h, F.rows + add)) || (rc = ensure_workspace(h))) return rc;
   const int tiles = (int)((N + kMergeTile - 1) / kMergeTile);
@@ -4057,52 +4045,107 @@ int nrv_fit_add_reads_raw(nrv_handle* h, const int16_t* raw, int64_t n_raw, cons
   return NRV_OK;
 }
 
-int nrv_fit_set_rows(nrv_handle* h, const float* flat1, const float* flat2, const uint8_t* y1, const uint8_t* y2, int64_t n) {
-  static const char* who = "nrv_fit_set_rows";
+// The row doors.  A door belongs to one depth; at another the refusal names the set's depth and its own doors - or, from a set
+// door at the depth a handle starts at, the nrv_fit_set_depth call that was left out
+static int fit_door_depth(nrv_handle* h, const char* who, int door_depth, bool set) {
+  const FitDepth &at = fit_at(h), &door = *fit_desc(door_depth);
+  if (&at == &door) return NRV_OK;
+  const std::string where = std::string("the set is at ") + at.name + " depth (";
+  if (set && &at == kFitDepths) return fit_refuse(h, who, where + "call nrv_fit_set_depth(" + door.code_name + ") on an empty set first)");
+  return fit_refuse(h, who, where + "rows are " + at.phrase + ": nrv_fit_" + (set ? "set" : "get") + "_rows" + at.suffix + ")");
+}
+// nrv_fit_set_rows*: `arrays` are the depth's row arrays in door order
+static int fit_rows_put(nrv_handle* h, const char* who, int door_depth, const float* const* arrays, const uint8_t* y1, const uint8_t* y2,
+                        int64_t n) {
   int rc = fit_enter(h, who);
-  if (rc) return rc;
-  if (h->fit.depth == NRV_FIT_FULL) return fit_refuse(h, who, "the set is at full depth (rows are samples and read features: nrv_fit_set_rows_full)");
-  if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_set_rows_signal)");
-  if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)");
-  if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)");
-  if (h->fit.depth) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)");
-  if (n < 0 || (n > 0 && (!flat1 || !flat2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
-  if (n > h->fit.max_rows) return fit_refuse(h, who, "more rows than the cap of the training set (NRV_FIT_MAX_ROWS)");
+  if (rc || (rc = fit_door_depth(h, who, door_depth, true))) return rc;
+  FitArr a[6];
+  const int na = fit_arrays(h, a);
+  const void* src[6];
+  for (int i = 0; i < na - 2; ++i) src[i] = arrays[i];
+  src[na - 2] = y1; src[na - 1] = y2;
+  bool all = true;
+  for (int i = 0; i < na; ++i) all = all && src[i];
+  if (n < 0 || (n > 0 && !all)) return fit_refuse(h, who, "null rows (or a negative count)");
+  if (n > fit_cap_rows(h)) return fit_refuse(h, who, "more rows than the cap of the training set" + fit_cap_words(h));
   for (int64_t i = 0; i < n; ++i)
     if (y1[i] > 5 || y2[i] > 4) return fit_refuse(h, who, "a label outside the model's classes (y1 0 .. 5, y2 0 .. 4)");
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->fit.rows = 0;
   if (n == 0) return NRV_OK;
   if ((rc = fit_reserve(h, n))) return rc;
-  const size_t K = 6 * (size_t)h->T;
-  if ((rc = put(h, h->fit.flat[0], flat1, (size_t)n * K * 4, h->stream)) || (rc = put(h, h->fit.flat[1], flat2, (size_t)n * K * 4, h->stream)) ||
-      (rc = put(h, h->fit.y[0], y1, (size_t)n, h->stream)) || (rc = put(h, h->fit.y[1], y2, (size_t)n, h->stream)))
-    return rc;
+  for (int i = 0; i < na; ++i)
+    if ((rc = put(h, *a[i].p, src[i], (size_t)n * a[i].row, h->stream))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->fit.rows = n;
   return NRV_OK;
 }
-
-int nrv_fit_get_rows(nrv_handle* h, int64_t first, int64_t count, float* flat1, float* flat2, uint8_t* y1, uint8_t* y2) {
-  static const char* who = "nrv_fit_get_rows";
-  const int rc = fit_enter(h, who);
-  if (rc) return rc;
-  if (h->fit.depth == NRV_FIT_FULL) return fit_refuse(h, who, "the set is at full depth (rows are samples and read features: nrv_fit_get_rows_full)");
-  if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_get_rows_signal)");
-  if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)");
-  if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)");
-  if (h->fit.depth) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)");
+// nrv_fit_get_rows*: any output may be null
+static int fit_rows_get(nrv_handle* h, const char* who, int door_depth, int64_t first, int64_t count, float* const* arrays, uint8_t* y1,
+                        uint8_t* y2) {
+  int rc = fit_enter(h, who);
+  if (rc || (rc = fit_door_depth(h, who, door_depth, false))) return rc;
   if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (count == 0) return NRV_OK;
-  const size_t K = 6 * (size_t)h->T;
-  float* const fl[2] = {flat1, flat2};
-  uint8_t* const yy[2] = {y1, y2};
-  for (int m = 0; m < 2; ++m) {
-    if (fl[m]) HIPCHK(h, hipMemcpy(fl[m], h->fit.flat[m] + (size_t)first * K, (size_t)count * K * 4, hipMemcpyDeviceToHost));
-    if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
-  }
+  FitArr a[6];
+  const int na = fit_arrays(h, a);
+  void* dst[6];
+  for (int i = 0; i < na - 2; ++i) dst[i] = arrays[i];
+  dst[na - 2] = y1; dst[na - 1] = y2;
+  for (int i = 0; i < na; ++i)
+    if (dst[i]) HIPCHK(h, hipMemcpy(dst[i], (const char*)*a[i].p + (size_t)first * a[i].row, (size_t)count * a[i].row, hipMemcpyDeviceToHost));
   return NRV_OK;
+}
+
+int nrv_fit_set_rows(nrv_handle* h, const float* flat1, const float* flat2, const uint8_t* y1, const uint8_t* y2, int64_t n) {
+  const float* const arrays[] = {flat1, flat2};
+  return fit_rows_put(h, "nrv_fit_set_rows", NRV_FIT_TAIL, arrays, y1, y2, n);
+}
+int nrv_fit_get_rows(nrv_handle* h, int64_t first, int64_t count, float* flat1, float* flat2, uint8_t* y1, uint8_t* y2) {
+  float* const arrays[] = {flat1, flat2};
+  return fit_rows_get(h, "nrv_fit_get_rows", NRV_FIT_TAIL, first, count, arrays, y1, y2);
+}
+int nrv_fit_set_rows_head(nrv_handle* h, const float* x1, const float* x2, const uint8_t* y1, const uint8_t* y2, int64_t n) {
+  const float* const arrays[] = {x1, x2};
+  return fit_rows_put(h, "nrv_fit_set_rows_head", NRV_FIT_HEAD, arrays, y1, y2, n);
+}
+int nrv_fit_get_rows_head(nrv_handle* h, int64_t first, int64_t count, float* x1, float* x2, uint8_t* y1, uint8_t* y2) {
+  float* const arrays[] = {x1, x2};
+  return fit_rows_get(h, "nrv_fit_get_rows_head", NRV_FIT_HEAD, first, count, arrays, y1, y2);
+}
+int nrv_fit_set_rows_lstm4(nrv_handle* h, const float* xb1, const float* xb2, const uint8_t* y1, const uint8_t* y2, int64_t n) {
+  const float* const arrays[] = {xb1, xb2};
+  return fit_rows_put(h, "nrv_fit_set_rows_lstm4", NRV_FIT_LSTM4, arrays, y1, y2, n);
+}
+int nrv_fit_get_rows_lstm4(nrv_handle* h, int64_t first, int64_t count, float* xb1, float* xb2, uint8_t* y1, uint8_t* y2) {
+  float* const arrays[] = {xb1, xb2};
+  return fit_rows_get(h, "nrv_fit_get_rows_lstm4", NRV_FIT_LSTM4, first, count, arrays, y1, y2);
+}
+int nrv_fit_set_rows_lstm3(nrv_handle* h, const float* x1, const float* x2, const uint8_t* y1, const uint8_t* y2, int64_t n) {
+  const float* const arrays[] = {x1, x2};
+  return fit_rows_put(h, "nrv_fit_set_rows_lstm3", NRV_FIT_LSTM3, arrays, y1, y2, n);
+}
+int nrv_fit_get_rows_lstm3(nrv_handle* h, int64_t first, int64_t count, float* x1, float* x2, uint8_t* y1, uint8_t* y2) {
+  float* const arrays[] = {x1, x2};
+  return fit_rows_get(h, "nrv_fit_get_rows_lstm3", NRV_FIT_LSTM3, first, count, arrays, y1, y2);
+}
+int nrv_fit_set_rows_signal(nrv_handle* h, const float* x2_1, const float* x2_2, const float* sig, const uint8_t* y1, const uint8_t* y2,
+                            int64_t n) {
+  const float* const arrays[] = {x2_1, x2_2, sig};
+  return fit_rows_put(h, "nrv_fit_set_rows_signal", NRV_FIT_SIGNAL, arrays, y1, y2, n);
+}
+int nrv_fit_get_rows_signal(nrv_handle* h, int64_t first, int64_t count, float* x2_1, float* x2_2, float* sig, uint8_t* y1, uint8_t* y2) {
+  float* const arrays[] = {x2_1, x2_2, sig};
+  return fit_rows_get(h, "nrv_fit_get_rows_signal", NRV_FIT_SIGNAL, first, count, arrays, y1, y2);
+}
+int nrv_fit_set_rows_full(nrv_handle* h, const float* sig, const float* feat, const uint8_t* y1, const uint8_t* y2, int64_t n) {
+  const float* const arrays[] = {sig, feat};
+  return fit_rows_put(h, "nrv_fit_set_rows_full", NRV_FIT_FULL, arrays, y1, y2, n);
+}
+int nrv_fit_get_rows_full(nrv_handle* h, int64_t first, int64_t count, float* sig, float* feat, uint8_t* y1, uint8_t* y2) {
+  float* const arrays[] = {sig, feat};
+  return fit_rows_get(h, "nrv_fit_get_rows_full", NRV_FIT_FULL, first, count, arrays, y1, y2);
 }
 
 int nrv_fit_depth(nrv_handle* h) {
@@ -4114,7 +4157,7 @@ int nrv_fit_set_depth(nrv_handle* h, int depth) {
   static const char* who = "nrv_fit_set_depth";
   const int rc = fit_enter(h, who);
   if (rc) return rc;
-  if (depth != NRV_FIT_TAIL && depth != NRV_FIT_HEAD && depth != NRV_FIT_LSTM4 && depth != NRV_FIT_LSTM3 && depth != NRV_FIT_SIGNAL && depth != NRV_FIT_FULL)
+  if (!fit_desc(depth))
     return fit_refuse(h, who, "depth must be NRV_FIT_TAIL or NRV_FIT_HEAD, or NRV_FIT_LSTM4, or NRV_FIT_LSTM3, or NRV_FIT_SIGNAL, or NRV_FIT_FULL");
   nrv_handle::Fit& F = h->fit;
   if (F.rows != 0) return fit_refuse(h, who, "the training set is not empty (call nrv_fit_reset first)");
@@ -4124,262 +4167,14 @@ int nrv_fit_set_depth(nrv_handle* h, int depth) {
     F.m[m].t = 0;
   }
   if (depth == F.depth) return NRV_OK;
-  for (int m = 0; m < 2; ++m) {
-    (void)hipFree(F.flat[m]); (void)hipFree(F.x4[m]); (void)hipFree(F.xb[m]); (void)hipFree(F.xin[m]); (void)hipFree(F.y[m]);
-    F.flat[m] = nullptr; F.x4[m] = nullptr; F.xb[m] = nullptr; F.xin[m] = nullptr; F.y[m] = nullptr;
-    (void)hipFree(F.x2s[m]); F.x2s[m] = nullptr;
+  for (int m = 0; m < 2; ++m) {                            // the set and the parameter blocks are the other depth's
+    (void)hipFree(F.x[m]); (void)hipFree(F.shared[m]); (void)hipFree(F.y[m]);
+    F.x[m] = nullptr; F.shared[m] = nullptr; F.y[m] = nullptr;
     (void)hipFree(F.m[m].d_par); (void)hipFree(F.m[m].d_state);
     F.m[m].d_par = nullptr; F.m[m].d_state = nullptr;
   }
-  (void)hipFree(F.sigs); F.sigs = nullptr;
-  (void)hipFree(F.feats); F.feats = nullptr;
   F.cap = 0;
   F.depth = depth;
-  return NRV_OK;
-}
-
-int nrv_fit_set_rows_head(nrv_handle* h, const float* x1, const float* x2, const uint8_t* y1, const uint8_t* y2, int64_t n) {
-  static const char* who = "nrv_fit_set_rows_head";
-  int rc = fit_enter(h, who);
-  if (rc) return rc;
-  if (h->fit.depth == NRV_FIT_FULL) return fit_refuse(h, who, "the set is at full depth (rows are samples and read features: nrv_fit_set_rows_full)");
-  if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_set_rows_signal)");
-  if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)");
-  if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)");
-  if (!h->fit.depth) return fit_refuse(h, who, "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_HEAD) on an empty set first)");
-  if (n < 0 || (n > 0 && (!x1 || !x2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
-  if (n > h->fit.max_head_rows) return fit_refuse(h, who, "more rows than the cap of the training set at head depth (NRV_FIT_MAX_HEAD_ROWS)");
-  for (int64_t i = 0; i < n; ++i)
-    if (y1[i] > 5 || y2[i] > 4) return fit_refuse(h, who, "a label outside the model's classes (y1 0 .. 5, y2 0 .. 4)");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->fit.rows = 0;
-  if (n == 0) return NRV_OK;
-  if ((rc = fit_reserve(h, n))) return rc;
-  const size_t K = fit_row_floats(h);
-  if ((rc = put(h, h->fit.x4[0], x1, (size_t)n * K * 4, h->stream)) || (rc = put(h, h->fit.x4[1], x2, (size_t)n * K * 4, h->stream)) ||
-      (rc = put(h, h->fit.y[0], y1, (size_t)n, h->stream)) || (rc = put(h, h->fit.y[1], y2, (size_t)n, h->stream)))
-    return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->fit.rows = n;
-  return NRV_OK;
-}
-
-int nrv_fit_get_rows_head(nrv_handle* h, int64_t first, int64_t count, float* x1, float* x2, uint8_t* y1, uint8_t* y2) {
-  static const char* who = "nrv_fit_get_rows_head";
-  const int rc = fit_enter(h, who);
-  if (rc) return rc;
-  if (h->fit.depth == NRV_FIT_FULL) return fit_refuse(h, who, "the set is at full depth (rows are samples and read features: nrv_fit_get_rows_full)");
-  if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_get_rows_signal)");
-  if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)");
-  if (h->fit.depth == NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)");
-  if (!h->fit.depth) return fit_refuse(h, who, "the set is at tail depth (rows are main_out values: nrv_fit_get_rows)");
-  if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (count == 0) return NRV_OK;
-  const size_t K = fit_row_floats(h);
-  float* const xs[2] = {x1, x2};
-  uint8_t* const yy[2] = {y1, y2};
-  for (int m = 0; m < 2; ++m) {
-    if (xs[m]) HIPCHK(h, hipMemcpy(xs[m], h->fit.x4[m] + (size_t)first * K, (size_t)count * K * 4, hipMemcpyDeviceToHost));
-    if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
-  }
-  return NRV_OK;
-}
-
-int nrv_fit_set_rows_lstm4(nrv_handle* h, const float* xb1, const float* xb2, const uint8_t* y1, const uint8_t* y2, int64_t n) {
-  static const char* who = "nrv_fit_set_rows_lstm4";
-  int rc = fit_enter(h, who);
-  if (rc) return rc;
-  if (h->fit.depth == NRV_FIT_FULL) return fit_refuse(h, who, "the set is at full depth (rows are samples and read features: nrv_fit_set_rows_full)");
-  if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_set_rows_signal)");
-  if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)");
-  if (h->fit.depth == NRV_FIT_HEAD) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)");
-  if (h->fit.depth != NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_LSTM4) on an empty set first)");
-  if (n < 0 || (n > 0 && (!xb1 || !xb2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
-  if (n > h->fit.max_lstm4_rows) return fit_refuse(h, who, "more rows than the cap of the training set at lstm4 depth (NRV_FIT_MAX_LSTM4_ROWS)");
-  for (int64_t i = 0; i < n; ++i)
-    if (y1[i] > 5 || y2[i] > 4) return fit_refuse(h, who, "a label outside the model's classes (y1 0 .. 5, y2 0 .. 4)");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->fit.rows = 0;
-  if (n == 0) return NRV_OK;
-  if ((rc = fit_reserve(h, n))) return rc;
-  const size_t K = fit_row_floats(h);
-  if ((rc = put(h, h->fit.xb[0], xb1, (size_t)n * K * 4, h->stream)) || (rc = put(h, h->fit.xb[1], xb2, (size_t)n * K * 4, h->stream)) ||
-      (rc = put(h, h->fit.y[0], y1, (size_t)n, h->stream)) || (rc = put(h, h->fit.y[1], y2, (size_t)n, h->stream)))
-    return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->fit.rows = n;
-  return NRV_OK;
-}
-
-int nrv_fit_get_rows_lstm4(nrv_handle* h, int64_t first, int64_t count, float* xb1, float* xb2, uint8_t* y1, uint8_t* y2) {
-  static const char* who = "nrv_fit_get_rows_lstm4";
-  const int rc = fit_enter(h, who);
-  if (rc) return rc;
-  if (h->fit.depth == NRV_FIT_FULL) return fit_refuse(h, who, "the set is at full depth (rows are samples and read features: nrv_fit_get_rows_full)");
-  if (h->fit.depth == NRV_FIT_SIGNAL) return fit_refuse(h, who, "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_get_rows_signal)");
-  if (h->fit.depth == NRV_FIT_LSTM3) return fit_refuse(h, who, "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)");
-  if (h->fit.depth == NRV_FIT_HEAD) return fit_refuse(h, who, "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)");
-  if (h->fit.depth != NRV_FIT_LSTM4) return fit_refuse(h, who, "the set is at tail depth (rows are main_out values: nrv_fit_get_rows)");
-  if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (count == 0) return NRV_OK;
-  const size_t K = fit_row_floats(h);
-  float* const xs[2] = {xb1, xb2};
-  uint8_t* const yy[2] = {y1, y2};
-  for (int m = 0; m < 2; ++m) {
-    if (xs[m]) HIPCHK(h, hipMemcpy(xs[m], h->fit.xb[m] + (size_t)first * K, (size_t)count * K * 4, hipMemcpyDeviceToHost));
-    if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
-  }
-  return NRV_OK;
-}
-
-static const char* fit_other_depth_set(const nrv_handle* h) {
-  return h->fit.depth == NRV_FIT_FULL ? "the set is at full depth (rows are samples and read features: nrv_fit_set_rows_full)"
-         : h->fit.depth == NRV_FIT_SIGNAL ? "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_set_rows_signal)"
-         : h->fit.depth == NRV_FIT_LSTM4 ? "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_set_rows_lstm4)"
-         : h->fit.depth == NRV_FIT_HEAD ? "the set is at head depth (rows are lstm4 outputs: nrv_fit_set_rows_head)"
-                                        : "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_LSTM3) on an empty set first)";
-}
-static const char* fit_other_depth_get(const nrv_handle* h) {
-  return h->fit.depth == NRV_FIT_FULL ? "the set is at full depth (rows are samples and read features: nrv_fit_get_rows_full)"
-         : h->fit.depth == NRV_FIT_SIGNAL ? "the set is at signal depth (rows are lstm2 outputs and samples: nrv_fit_get_rows_signal)"
-         : h->fit.depth == NRV_FIT_LSTM4 ? "the set is at lstm4 depth (rows are BatchNorm'd lstm3 outputs: nrv_fit_get_rows_lstm4)"
-         : h->fit.depth == NRV_FIT_HEAD ? "the set is at head depth (rows are lstm4 outputs: nrv_fit_get_rows_head)"
-                                        : "the set is at tail depth (rows are main_out values: nrv_fit_get_rows)";
-}
-
-int nrv_fit_set_rows_lstm3(nrv_handle* h, const float* x1, const float* x2, const uint8_t* y1, const uint8_t* y2, int64_t n) {
-  static const char* who = "nrv_fit_set_rows_lstm3";
-  int rc = fit_enter(h, who);
-  if (rc) return rc;
-  if (h->fit.depth != NRV_FIT_LSTM3) return fit_refuse(h, who, fit_other_depth_set(h));
-  if (n < 0 || (n > 0 && (!x1 || !x2 || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
-  if (n > h->fit.max_lstm3_rows) return fit_refuse(h, who, "more rows than the cap of the training set at lstm3 depth (NRV_FIT_MAX_LSTM3_ROWS)");
-  for (int64_t i = 0; i < n; ++i)
-    if (y1[i] > 5 || y2[i] > 4) return fit_refuse(h, who, "a label outside the model's classes (y1 0 .. 5, y2 0 .. 4)");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->fit.rows = 0;
-  if (n == 0) return NRV_OK;
-  if ((rc = fit_reserve(h, n))) return rc;
-  const size_t K = fit_row_floats(h);
-  if ((rc = put(h, h->fit.xin[0], x1, (size_t)n * K * 4, h->stream)) || (rc = put(h, h->fit.xin[1], x2, (size_t)n * K * 4, h->stream)) ||
-      (rc = put(h, h->fit.y[0], y1, (size_t)n, h->stream)) || (rc = put(h, h->fit.y[1], y2, (size_t)n, h->stream)))
-    return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->fit.rows = n;
-  return NRV_OK;
-}
-
-int nrv_fit_get_rows_lstm3(nrv_handle* h, int64_t first, int64_t count, float* x1, float* x2, uint8_t* y1, uint8_t* y2) {
-  static const char* who = "nrv_fit_get_rows_lstm3";
-  const int rc = fit_enter(h, who);
-  if (rc) return rc;
-  if (h->fit.depth != NRV_FIT_LSTM3) return fit_refuse(h, who, fit_other_depth_get(h));
-  if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (count == 0) return NRV_OK;
-  const size_t K = fit_row_floats(h);
-  float* const xs[2] = {x1, x2};
-  uint8_t* const yy[2] = {y1, y2};
-  for (int m = 0; m < 2; ++m) {
-    if (xs[m]) HIPCHK(h, hipMemcpy(xs[m], h->fit.xin[m] + (size_t)first * K, (size_t)count * K * 4, hipMemcpyDeviceToHost));
-    if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
-  }
-  return NRV_OK;
-}
-
-static const char* fit_not_signal(const nrv_handle* h, bool set) {
-  if (h->fit.depth == NRV_FIT_LSTM3)
-    return set ? "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_set_rows_lstm3)" : "the set is at lstm3 depth (rows are lstm3's inputs: nrv_fit_get_rows_lstm3)";
-  if (h->fit.depth == NRV_FIT_TAIL && set) return "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_SIGNAL) on an empty set first)";
-  return set ? fit_other_depth_set(h) : fit_other_depth_get(h);
-}
-
-int nrv_fit_set_rows_signal(nrv_handle* h, const float* x2_1, const float* x2_2, const float* sig, const uint8_t* y1, const uint8_t* y2,
-                            int64_t n) {
-  static const char* who = "nrv_fit_set_rows_signal";
-  int rc = fit_enter(h, who);
-  if (rc) return rc;
-  if (h->fit.depth != NRV_FIT_SIGNAL) return fit_refuse(h, who, fit_not_signal(h, true));
-  if (n < 0 || (n > 0 && (!x2_1 || !x2_2 || !sig || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
-  if (n > h->fit.max_signal_rows) return fit_refuse(h, who, "more rows than the cap of the training set at signal depth (NRV_FIT_MAX_SIGNAL_ROWS)");
-  for (int64_t i = 0; i < n; ++i)
-    if (y1[i] > 5 || y2[i] > 4) return fit_refuse(h, who, "a label outside the model's classes (y1 0 .. 5, y2 0 .. 4)");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->fit.rows = 0;
-  if (n == 0) return NRV_OK;
-  if ((rc = fit_reserve(h, n))) return rc;
-  const size_t K = fit_row_floats(h), KS = (size_t)h->T * kSig;
-  if ((rc = put(h, h->fit.x2s[0], x2_1, (size_t)n * K * 4, h->stream)) || (rc = put(h, h->fit.x2s[1], x2_2, (size_t)n * K * 4, h->stream)) ||
-      (rc = put(h, h->fit.sigs, sig, (size_t)n * KS * 4, h->stream)) ||
-      (rc = put(h, h->fit.y[0], y1, (size_t)n, h->stream)) || (rc = put(h, h->fit.y[1], y2, (size_t)n, h->stream)))
-    return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->fit.rows = n;
-  return NRV_OK;
-}
-
-int nrv_fit_get_rows_signal(nrv_handle* h, int64_t first, int64_t count, float* x2_1, float* x2_2, float* sig, uint8_t* y1, uint8_t* y2) {
-  static const char* who = "nrv_fit_get_rows_signal";
-  const int rc = fit_enter(h, who);
-  if (rc) return rc;
-  if (h->fit.depth != NRV_FIT_SIGNAL) return fit_refuse(h, who, fit_not_signal(h, false));
-  if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (count == 0) return NRV_OK;
-  const size_t K = fit_row_floats(h), KS = (size_t)h->T * kSig;
-  float* const xs[2] = {x2_1, x2_2};
-  uint8_t* const yy[2] = {y1, y2};
-  for (int m = 0; m < 2; ++m) {
-    if (xs[m]) HIPCHK(h, hipMemcpy(xs[m], h->fit.x2s[m] + (size_t)first * K, (size_t)count * K * 4, hipMemcpyDeviceToHost));
-    if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
-  }
-  if (sig) HIPCHK(h, hipMemcpy(sig, h->fit.sigs + (size_t)first * KS, (size_t)count * KS * 4, hipMemcpyDeviceToHost));
-  return NRV_OK;
-}
-
-static const char* fit_not_full(const nrv_handle* h, bool set) {
-  if (h->fit.depth == NRV_FIT_TAIL && set) return "the set is at tail depth (call nrv_fit_set_depth(NRV_FIT_FULL) on an empty set first)";
-  return fit_not_signal(h, set);
-}
-
-int nrv_fit_set_rows_full(nrv_handle* h, const float* sig, const float* feat, const uint8_t* y1, const uint8_t* y2, int64_t n) {
-  static const char* who = "nrv_fit_set_rows_full";
-  int rc = fit_enter(h, who);
-  if (rc) return rc;
-  if (h->fit.depth != NRV_FIT_FULL) return fit_refuse(h, who, fit_not_full(h, true));
-  if (n < 0 || (n > 0 && (!sig || !feat || !y1 || !y2))) return fit_refuse(h, who, "null rows (or a negative count)");
-  if (n > h->fit.max_full_rows) return fit_refuse(h, who, "more rows than the cap of the training set at full depth (NRV_FIT_MAX_FULL_ROWS)");
-  for (int64_t i = 0; i < n; ++i)
-    if (y1[i] > 5 || y2[i] > 4) return fit_refuse(h, who, "a label outside the model's classes (y1 0 .. 5, y2 0 .. 4)");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->fit.rows = 0;
-  if (n == 0) return NRV_OK;
-  if ((rc = fit_reserve(h, n))) return rc;
-  const size_t KS = (size_t)h->T * kSig, KF = (size_t)h->T * kFeat;
-  if ((rc = put(h, h->fit.sigs, sig, (size_t)n * KS * 4, h->stream)) || (rc = put(h, h->fit.feats, feat, (size_t)n * KF * 4, h->stream)) ||
-      (rc = put(h, h->fit.y[0], y1, (size_t)n, h->stream)) || (rc = put(h, h->fit.y[1], y2, (size_t)n, h->stream)))
-    return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->fit.rows = n;
-  return NRV_OK;
-}
-
-int nrv_fit_get_rows_full(nrv_handle* h, int64_t first, int64_t count, float* sig, float* feat, uint8_t* y1, uint8_t* y2) {
-  static const char* who = "nrv_fit_get_rows_full";
-  const int rc = fit_enter(h, who);
-  if (rc) return rc;
-  if (h->fit.depth != NRV_FIT_FULL) return fit_refuse(h, who, fit_not_full(h, false));
-  if (first < 0 || count < 0 || first > h->fit.rows || count > h->fit.rows - first) return fit_refuse(h, who, "rows outside the training set");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (count == 0) return NRV_OK;
-  const size_t KS = (size_t)h->T * kSig, KF = (size_t)h->T * kFeat;
-  uint8_t* const yy[2] = {y1, y2};
-  for (int m = 0; m < 2; ++m)
-    if (yy[m]) HIPCHK(h, hipMemcpy(yy[m], h->fit.y[m] + first, (size_t)count, hipMemcpyDeviceToHost));
-  if (sig) HIPCHK(h, hipMemcpy(sig, h->fit.sigs + (size_t)first * KS, (size_t)count * KS * 4, hipMemcpyDeviceToHost));
-  if (feat) HIPCHK(h, hipMemcpy(feat, h->fit.feats + (size_t)first * KF, (size_t)count * KF * 4, hipMemcpyDeviceToHost));
   return NRV_OK;
 }
 
@@ -4423,6 +4218,7 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
   if (o.B < 1 || o.B > NRV_FIT_MAX_BATCH) return fit_refuse(h, who, "B outside 1 .. NRV_FIT_MAX_BATCH");
   nrv_handle::Fit::Model& M = h->fit.m[model];
   const DevModel& d = h->dm[model];
+  const FitDepth& D = fit_at(h);
   const int C = d.C, K = 6 * h->T, P = fit_params_n(h, model);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   M.begun = false;
@@ -4435,28 +4231,27 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
   else {
     const size_t src[4] = {d.fw, d.fb, d.ow, d.ob}, cnt[4] = {(size_t)16 * K, 16, (size_t)16 * C, (size_t)C};
     size_t at = 0;
-    const bool full = h->fit.depth == NRV_FIT_FULL;
-    float* const sgp = M.d_par + (full ? kRdN : 0);         // where the signal depth's vector starts
-    if (full) {                                             // tensors 12 .. 17 and 22 .. 27, unfolded as the file has them
+    float* const sgp = M.d_par + (D.rd ? kRdN : 0);         // where the signal depth's vector starts
+    if (D.rd) {                                             // tensors 12 .. 17 and 22 .. 27, unfolded as the file has them
       HIPCHK(h, hipMemcpyAsync(M.d_par, d.all + d.l1raw, (size_t)kR1N * 4, hipMemcpyDeviceToDevice, h->stream));
       HIPCHK(h, hipMemcpyAsync(M.d_par + kR1N, d.all + d.l2raw, (size_t)kR2N * 4, hipMemcpyDeviceToDevice, h->stream));
     }
-    if (h->fit.depth == NRV_FIT_SIGNAL || full) {           // tensors 0, 1 and 6, 7 out of the conv image, 32 and 33 as the file has them
+    if (D.sg) {                                             // tensors 0, 1 and 6, 7 out of the conv image, 32 and 33 as the file has them
       HIPCHK(h, hipMemcpyAsync(sgp, d.all + d.conv, (size_t)32 * 4, hipMemcpyDeviceToDevice, h->stream));
       HIPCHK(h, hipMemcpyAsync(sgp + kSgW2, d.all + d.conv + 48, (size_t)200 * 4, hipMemcpyDeviceToDevice, h->stream));
       HIPCHK(h, hipMemcpyAsync(sgp + kSgWs, d.all + d.sdraw, (size_t)400 * 64 * 4, hipMemcpyDeviceToDevice, h->stream));
       HIPCHK(h, hipMemcpyAsync(sgp + kSgBs, d.all + d.dbias, (size_t)64 * 4, hipMemcpyDeviceToDevice, h->stream));
-      at = (full ? kRdN : 0) + kSgN;
+      at = (D.rd ? kRdN : 0) + kSgN;
     }
-    if (h->fit.depth == NRV_FIT_LSTM3 || h->fit.depth == NRV_FIT_SIGNAL || full) {                    // tensors 34 .. 39, unfolded as the file has them
+    if (D.l3) {                                             // tensors 34 .. 39, unfolded as the file has them
       HIPCHK(h, hipMemcpyAsync(M.d_par + at, d.all + d.l3raw, (size_t)kL3N * 4, hipMemcpyDeviceToDevice, h->stream));
       at += kL3N;
     }
-    if (h->fit.depth >= NRV_FIT_LSTM4) {      // tensors 44 .. 49, unfolded as the file has them
+    if (D.l4) {                                             // tensors 44 .. 49, unfolded as the file has them
       HIPCHK(h, hipMemcpyAsync(M.d_par + at, d.all + d.l4raw, (size_t)kL4N * 4, hipMemcpyDeviceToDevice, h->stream));
       at += kL4N;
     }
-    if (h->fit.depth) {
+    if (D.mlp) {
       HIPCHK(h, hipStreamSynchronize(h->stream));
       const int rc2 = fit_head_own(h, model, M.d_par + at);
       if (rc2) return rc2;
@@ -4467,7 +4262,7 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
       at += cnt[i];
     }
   }
-  if (h->fit.depth >= NRV_FIT_LSTM3) {                      // the fit's own BatchNorm block: the handle's folded pairs, the loaded statistics
+  if (D.l3) {                                               // the fit's own BatchNorm block: the handle's folded pairs, the loaded statistics
     if (!M.d_bn) {
       HIPCHK(h, hipMalloc((void**)&M.d_bn, (size_t)kBnFloats * 4));
       HIPCHK(h, hipMalloc((void**)&M.d_bnacc, (size_t)2 * kBnCh * 8));
@@ -4505,7 +4300,7 @@ static int fit_rows_in(nrv_handle* h, const char* who, int model, const uint32_t
 static TailGradArgs fit_grad_args(nrv_handle* h, int model, const unsigned* d_rows, int b, float* d_p) {
   const nrv_handle::Fit::Model& M = h->fit.m[model];
   TailGradArgs a;
-  a.flat = h->fit.flat[model]; a.y = h->fit.y[model]; a.rows = d_rows; a.par = M.d_par;
+  a.flat = h->fit.x[model]; a.y = h->fit.y[model]; a.rows = d_rows; a.par = M.d_par;
   a.partial = h->fit.d_partial; a.pstat = h->fit.d_pstat; a.p_out = d_p;
   a.T = h->T; a.C = h->dm[model].C; a.b = b; a.lambda = M.o.lambda;
   memcpy(a.cw, M.o.cw, sizeof a.cw);
@@ -4535,24 +4330,24 @@ static int fit_state_get(nrv_handle* h, int model, nrv_fit_stats* stats) {
 }
 static int fit_head_wgs(int b) { const int tiles = (b + 31) / 32; return tiles < kHeadFitMaxWg ? tiles : kHeadFitMaxWg; }
 static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
+  const FitDepth& D = fit_at(h);
   size_t wg = ((size_t)b_max + 31) / 32;
   int rc;
-  if (h->fit.depth) {
+  if (D.mlp) {
     wg = (size_t)fit_head_wgs(b_max);
     if ((rc = fit_scratch(h, (void**)&h->fit.d_flag, &h->fit.cap_flag,
                           (size_t)((kRdN + 255) / 256 + 1 + (kSgDense + 255) / 256 + kL3N / 256 + kL4N / 256 + (kHeadFitMaxP + 255) / 256) * 4)))
       return rc;
   }
   size_t pn = (size_t)fit_params_n(h, model);
-  const bool full = h->fit.depth == NRV_FIT_FULL;
-  if (full) {                                                // one chunk's nine arrays of nrv_fullfit.h, the read block's partials
+  if (D.rd) {                                                // one chunk's nine arrays of nrv_fullfit.h, the read block's partials
     const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
     if ((rc = fit_scratch(h, (void**)&h->fit.d_rd, &h->fit.cap_rd, rows * h->T * (grad ? kRdPairGrad : kRdPair) * 4)) ||
         (grad && (rc = fit_scratch(h, (void**)&h->fit.d_grd, &h->fit.cap_grd, (size_t)kRdSlices * kRdN * 4))))
       return rc;
     pn -= kRdN;
   }
-  if (h->fit.depth == NRV_FIT_SIGNAL || full) {              // one chunk's [Xin | F | dS], the conv block's partials, the dense block's sums
+  if (D.sg) {                                                // one chunk's [Xin | F | dS], the conv block's partials, the dense block's sums
     const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
     if ((rc = fit_scratch(h, (void**)&h->fit.d_sg, &h->fit.cap_sg, rows * h->T * (grad ? 656 : 192) * 4)) ||
         (grad && (rc = fit_scratch(h, (void**)&h->fit.d_pconv, &h->fit.cap_pconv, (rows * h->T + 31) / 32 * kSgConv * 4))) ||
@@ -4560,7 +4355,7 @@ static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
       return rc;
     pn -= kSgN;
   }
-  if (h->fit.depth == NRV_FIT_LSTM3 || h->fit.depth == NRV_FIT_SIGNAL || full) {               // one chunk's [H3 | XB | dX3 | CS | GZ], the lstm3 block's sums, the identity list
+  if (D.l3) {                                                // one chunk's [H3 | XB | dX3 | CS | GZ], the lstm3 block's sums, the identity list
     const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
     if ((rc = fit_scratch(h, (void**)&h->fit.d_l3, &h->fit.cap_l3, rows * h->T * (grad ? 2048 : 512) * 4)) ||
         (rc = fit_scratch(h, (void**)&h->fit.d_gl3, &h->fit.cap_gl3, (size_t)kL3N * 4)))
@@ -4573,7 +4368,7 @@ static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
     }
     pn -= kL3N;
   }
-  if (h->fit.depth >= NRV_FIT_LSTM4) {                       // one chunk's [X4 | dX4 | CS | GZ], the LSTM block's sums; partials of the head alone
+  if (D.l4) {                                                // one chunk's [X4 | dX4 | CS | GZ], the LSTM block's sums; partials of the head alone
     const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
     if ((rc = fit_scratch(h, (void**)&h->fit.d_l4, &h->fit.cap_l4, rows * h->T * (grad ? 896 : 128) * 4)) ||
         (rc = fit_scratch(h, (void**)&h->fit.d_gl4, &h->fit.cap_gl4, (size_t)kL4N * 4)))
@@ -4591,7 +4386,7 @@ static void fit_bn_moments(nrv_handle* h, int model, int stage, int c0, int bc, 
                            const float* h3) {
   nrv_handle::Fit::Model& M = h->fit.m[model];
   const int T = h->T, Mc = bc * T, wg_col = (Mc + kBnRows - 1) / kBnRows, wg_conv = (Mc + 32 * kBnTiles - 1) / (32 * kBnTiles);
-  const bool full = h->fit.depth == NRV_FIT_FULL, sg = full || h->fit.depth == NRV_FIT_SIGNAL;
+  const bool full = fit_at(h).rd, sg = fit_at(h).sg;
   double* const pcol = h->fit.d_bnpart;                     // the two regions nrv_fit_bn_reestimate sized
   double* const pconv = pcol + (size_t)kL4ChunkRows * T / kBnRows * 512 + 512;
   BnReduceArgs ra{};
@@ -4623,7 +4418,9 @@ static void fit_bn_moments(nrv_handle* h, int model, int stage, int c0, int bc, 
 // reduce / update behind it - two launches at tail depth, three at head depth.  bn_stage >= 0 (nrv_fit_bn_reestimate, mode
 // kTailEval, depth NRV_FIT_LSTM3 or deeper): per chunk the forward launches up to lstm3 and fit_bn_moments, nothing else
 static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, int mode, long long n_lr, float* d_p, int bn_stage = -1) {
-  if (!h->fit.depth) {
+  const FitDepth& D = fit_at(h);
+  const bool full = D.rd, sg = D.sg, l3 = D.l3;
+  if (!D.mlp) {
     const int wg = (b + 31) / 32;
     if (mode == kTailEval) hipLaunchKernelGGL(tail_grad_kernel<false>, dim3(wg), dim3(256), 0, h->stream, fit_grad_args(h, model, d_rows, b, d_p));
     else hipLaunchKernelGGL(tail_grad_kernel<true>, dim3(wg), dim3(256), 0, h->stream, fit_grad_args(h, model, d_rows, b, d_p));
@@ -4632,12 +4429,15 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
   }
   nrv_handle::Fit::Model& M = h->fit.m[model];
   const int wg = fit_head_wgs(b), P = fit_params_n(h, model), blocks = (P + 255) / 256;
-  if (h->fit.depth >= NRV_FIT_LSTM4) {
+  // the update of one block of the vector: `src` holds n_part partials of len gradients, the block starts at parameter `at`
+  // and its reduce launch's flags at `flag`
+  auto adam = [&](const float* src, int n_part, int len, int at, int flag) {
+    return HeadAdamArgs{src, h->fit.d_pstat, n_part, b, len, mode, M.d_par + at, M.d_par + P + at, M.d_par + 2 * P + at, M.d_par + 3 * P + at,
+                        (HeadState*)M.d_state, h->fit.d_flag + flag, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+  };
+  if (D.l4) {
     const int T = h->T;
     const bool grad = mode != kTailEval;
-    const bool full = h->fit.depth == NRV_FIT_FULL;
-    const bool sg = full || h->fit.depth == NRV_FIT_SIGNAL;
-    const bool l3 = sg || h->fit.depth == NRV_FIT_LSTM3;
     const int orr = full ? kRdN : 0;                        // where the signal depth's vector starts
     const int os = orr + (sg ? kSgN : 0);                   // where the lstm3 depth's vector starts
     const int o3 = os + (l3 ? kL3N : 0);                    // where the lstm4 depth's vector starts
@@ -4669,9 +4469,9 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
     const int sg_wg = sg ? ((b < kL4ChunkRows ? b : kL4ChunkRows) * T + 31) / 32 : 0;     // workgroups of sig_backward_kernel in the first chunk: the conv block's partials
     for (int c0 = 0; c0 < b; c0 += kL4ChunkRows) {
       const int bc = b - c0 < kL4ChunkRows ? b - c0 : kL4ChunkRows, tiles = (bc + 31) / 32;
-      const SigArgs sa{full ? nullptr : h->fit.x2s[model], h->fit.sigs, d_rows + c0, M.d_par + orr, fbn + kBnConv, xin, fkeep, ds, gz3,
+      const SigArgs sa{sg ? h->fit.x[model] : nullptr, h->fit.shared[0], d_rows + c0, M.d_par + orr, fbn + kBnConv, xin, fkeep, ds, gz3,
                        h->fit.d_pconv, h->fit.d_gdense, T, bc * T, grad ? 1 : 0, c0 > 0 ? 1 : 0, dh2, fbn + kBnS2};
-      const RlArgs r1{h->fit.feats, d_rows + c0, M.d_par, fbn + kBnS1, fbn + kBnH1, h1, x1b, gz1, cs1, dh1,
+      const RlArgs r1{h->fit.shared[1], d_rows + c0, M.d_par, fbn + kBnS1, fbn + kBnH1, h1, x1b, gz1, cs1, dh1,
                       h->fit.d_grd, 32, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
       const RlArgs r2{x1b, h->fit.d_ident, M.d_par + kR1N, fbn + kBnS2, fbn + kBnH2, h2, xin, gz2, cs2, dh2,
                       full ? h->fit.d_grd + kR1N : nullptr, 192, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
@@ -4685,14 +4485,14 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
         }
         hipLaunchKernelGGL(sig_forward_kernel<false>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
       } else if (sg) hipLaunchKernelGGL(sig_forward_kernel<true>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
-      const L3Args l3a{sg ? xin : h->fit.xin[model], sg ? h->fit.d_ident : d_rows + c0, M.d_par + os, fbn + kBnS3, fbn + kBnH3, h3, xb4, gz3, cs3, dx3, gz,
+      const L3Args l3a{sg ? xin : l3 ? h->fit.x[model] : nullptr, sg ? h->fit.d_ident : d_rows + c0, M.d_par + os, fbn + kBnS3, fbn + kBnH3, h3, xb4, gz3, cs3, dx3, gz,
                        h->fit.d_gl3, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
       if (l3) {                                             // lstm3 forward: the scratch XB is "the set" of the lstm4 launches
         if (h->act == 0) hipLaunchKernelGGL(l3_forward_kernel<0>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
         else hipLaunchKernelGGL(l3_forward_kernel<1>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
       }
       if (bn_stage >= 0) { fit_bn_moments(h, model, bn_stage, c0, bc, b, sa, h1, h2, h3); continue; }
-      const L4Args la{l3 ? xb4 : h->fit.xb[model], l3 ? h->fit.d_ident : d_rows + c0, M.d_par + o3, x4, gz, cs, dx4, h->fit.d_gl4, T, bc,
+      const L4Args la{l3 ? xb4 : h->fit.x[model], l3 ? h->fit.d_ident : d_rows + c0, M.d_par + o3, x4, gz, cs, dx4, h->fit.d_gl4, T, bc,
                       grad ? 1 : 0, c0 > 0 ? 1 : 0};
       if (h->act == 0) hipLaunchKernelGGL(l4_forward_kernel<0>, dim3(tiles, 2), dim3(256), 0, h->stream, la);
       else hipLaunchKernelGGL(l4_forward_kernel<1>, dim3(tiles, 2), dim3(256), 0, h->stream, la);
@@ -4740,44 +4540,27 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
     // (at depth NRV_FIT_FULL the read block's kRdSlices partials in front of everything, with 206 flags of their own)
     const int blr = full ? (kRdN + 255) / 256 : 0;
     const int bls = blr + (sg ? 1 + (kSgDense + 255) / 256 : 0);
-    if (full) {
-      const HeadAdamArgs ur{h->fit.d_grd, h->fit.d_pstat, kRdSlices, b, kRdN, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
-                            (HeadState*)M.d_state, h->fit.d_flag, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
-      hipLaunchKernelGGL(head_reduce_kernel, dim3(blr), dim3(256), 0, h->stream, ur);
-    }
+    if (full) hipLaunchKernelGGL(head_reduce_kernel, dim3(blr), dim3(256), 0, h->stream, adam(h->fit.d_grd, kRdSlices, kRdN, 0, 0));
     if (sg) {
-      const int ow = orr + kSgWs;
-      const HeadAdamArgs uc{h->fit.d_pconv, h->fit.d_pstat, sg_wg, b, kSgConv, mode, M.d_par + orr, M.d_par + P + orr, M.d_par + 2 * P + orr, M.d_par + 3 * P + orr,
-                            (HeadState*)M.d_state, h->fit.d_flag + blr, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
-      const HeadAdamArgs ud{h->fit.d_gdense, h->fit.d_pstat, 1, b, kSgDense, mode, M.d_par + ow, M.d_par + P + ow, M.d_par + 2 * P + ow,
-                            M.d_par + 3 * P + ow, (HeadState*)M.d_state, h->fit.d_flag + blr + 1, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
-      hipLaunchKernelGGL(head_reduce_kernel, dim3(1), dim3(256), 0, h->stream, uc);
-      hipLaunchKernelGGL(head_reduce_kernel, dim3(bls - blr - 1), dim3(256), 0, h->stream, ud);
+      hipLaunchKernelGGL(head_reduce_kernel, dim3(1), dim3(256), 0, h->stream, adam(h->fit.d_pconv, sg_wg, kSgConv, orr, blr));
+      hipLaunchKernelGGL(head_reduce_kernel, dim3(bls - blr - 1), dim3(256), 0, h->stream, adam(h->fit.d_gdense, 1, kSgDense, orr + kSgWs, blr + 1));
     }
-    const HeadAdamArgs u0{h->fit.d_gl3, h->fit.d_pstat, 1, b, kL3N, mode, M.d_par + os, M.d_par + P + os, M.d_par + 2 * P + os, M.d_par + 3 * P + os,
-                          (HeadState*)M.d_state, h->fit.d_flag + bls, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
-    const HeadAdamArgs u1{h->fit.d_gl4, h->fit.d_pstat, 1, b, kL4N, mode, M.d_par + o3, M.d_par + P + o3, M.d_par + 2 * P + o3, M.d_par + 3 * P + o3,
-                          (HeadState*)M.d_state, h->fit.d_flag + bls + bl3, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
-    const HeadAdamArgs u2{h->fit.d_partial, h->fit.d_pstat, wg, b, PH, mode, M.d_par + o4, M.d_par + P + o4, M.d_par + 2 * P + o4,
-                          M.d_par + 3 * P + o4, (HeadState*)M.d_state, h->fit.d_flag + bls + bl3 + bl4, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
-    if (l3) hipLaunchKernelGGL(head_reduce_kernel, dim3(bl3), dim3(256), 0, h->stream, u0);
-    const HeadAdamArgs u{h->fit.d_partial, h->fit.d_pstat, wg, b, P, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
-                         (HeadState*)M.d_state, h->fit.d_flag, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
-    hipLaunchKernelGGL(head_reduce_kernel, dim3(bl4), dim3(256), 0, h->stream, u1);
-    hipLaunchKernelGGL(head_reduce_kernel, dim3((PH + 255) / 256), dim3(256), 0, h->stream, u2);
-    hipLaunchKernelGGL(head_adam_kernel, dim3(sg ? bls + bl3 + bl4 + (PH + 255) / 256 : blocks), dim3(256), 0, h->stream, u);
+    if (l3) hipLaunchKernelGGL(head_reduce_kernel, dim3(bl3), dim3(256), 0, h->stream, adam(h->fit.d_gl3, 1, kL3N, os, bls));
+    hipLaunchKernelGGL(head_reduce_kernel, dim3(bl4), dim3(256), 0, h->stream, adam(h->fit.d_gl4, 1, kL4N, o3, bls + bl3));
+    hipLaunchKernelGGL(head_reduce_kernel, dim3((PH + 255) / 256), dim3(256), 0, h->stream, adam(h->fit.d_partial, wg, PH, o4, bls + bl3 + bl4));
+    hipLaunchKernelGGL(head_adam_kernel, dim3(sg ? bls + bl3 + bl4 + (PH + 255) / 256 : blocks), dim3(256), 0, h->stream,
+                       adam(h->fit.d_partial, wg, P, 0, 0));
     return;
   }
   HeadGradArgs a;
   a.dh1 = nullptr; a.cont = 0;
-  a.x = h->fit.x4[model]; a.y = h->fit.y[model]; a.rows = d_rows; a.par = M.d_par;
+  a.x = h->fit.x[model]; a.y = h->fit.y[model]; a.rows = d_rows; a.par = M.d_par;
   a.partial = h->fit.d_partial; a.pstat = h->fit.d_pstat; a.p_out = d_p;
   a.T = h->T; a.C = h->dm[model].C; a.b = b; a.lambda = M.o.lambda;
   memcpy(a.cw, M.o.cw, sizeof a.cw);
   if (mode == kTailEval) hipLaunchKernelGGL(head_grad_kernel<false>, dim3(wg), dim3(256), 0, h->stream, a);
   else hipLaunchKernelGGL(head_grad_kernel<true>, dim3(wg), dim3(256), 0, h->stream, a);
-  const HeadAdamArgs u{h->fit.d_partial, h->fit.d_pstat, wg, b, P, mode, M.d_par, M.d_par + P, M.d_par + 2 * P, M.d_par + 3 * P,
-                       (HeadState*)M.d_state, h->fit.d_flag, M.d_lr, M.t, n_lr, M.o.beta1, M.o.beta2, M.o.eps};
+  const HeadAdamArgs u = adam(h->fit.d_partial, wg, P, 0, 0);
   hipLaunchKernelGGL(head_reduce_kernel, dim3(blocks), dim3(256), 0, h->stream, u);
   hipLaunchKernelGGL(head_adam_kernel, dim3(blocks), dim3(256), 0, h->stream, u);
 }
@@ -4851,10 +4634,9 @@ int nrv_fit_params(nrv_handle* h, int model, float* params, int64_t* t) {
 
 // the BatchNorms inside the fitted section, as indices into kFitBn, in tensor order -> their number
 static int fit_bn_list(const nrv_handle* h, int (&list)[5]) {
-  static const int full[5] = {0, 1, 2, 3, 4}, sig[3] = {0, 1, 4};
-  const int d = h->fit.depth, n = d == NRV_FIT_FULL ? 5 : d == NRV_FIT_SIGNAL ? 3 : d == NRV_FIT_LSTM3 ? 1 : 0;
-  for (int i = 0; i < n; ++i) list[i] = n == 5 ? full[i] : n == 3 ? sig[i] : 4;
-  return n;
+  const FitDepth& D = fit_at(h);
+  for (int i = 0; i < D.n_bn; ++i) list[i] = D.bn[i];
+  return D.n_bn;
 }
 
 int nrv_fit_bn_count(nrv_handle* h) {

@@ -21,6 +21,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from . import fitdepth
 from .weights import ModelWeights, load_species
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -54,10 +55,7 @@ SYMBOLS = [
     "nrv_fit_set_rows_full", "nrv_fit_get_rows_full",
     "nrv_fit_bn_reestimate", "nrv_fit_bn_count", "nrv_fit_bn_get",
 ]
-FIT_TAIL, FIT_HEAD, FIT_LSTM4 = 0, 1, 4    # NRV_FIT_TAIL, NRV_FIT_HEAD, NRV_FIT_LSTM4 (the Bi-LSTM the fit starts at)
-FIT_LSTM3 = 8                              # NRV_FIT_LSTM3
-FIT_SIGNAL = 16                            # NRV_FIT_SIGNAL
-FIT_FULL = 32                              # NRV_FIT_FULL
+FIT_TAIL, FIT_HEAD, FIT_LSTM4, FIT_LSTM3, FIT_SIGNAL, FIT_FULL = (d.code for d in fitdepth.DEPTHS)   # NRV_FIT_*: 0, 1, 4, 8, 16, 32
 FIT_MAX_BATCH = 65536               # NRV_FIT_MAX_BATCH
 REPORT_COLS = 24                    # NRV_REPORT_COLS
 PROFILE_COLS = 48                   # NRV_PROFILE_COLS
@@ -180,8 +178,6 @@ _FIT_T = {                                                                      
     "nrv_fit_reset": [C.c_void_p],
     "nrv_fit_count": [C.c_void_p],
     "nrv_fit_add_reads_raw": _RAW_HEAD_T + _STATS[0] + [_U8P, _I64P],
-    "nrv_fit_set_rows": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
-    "nrv_fit_get_rows": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
     "nrv_fit_begin": [C.c_void_p, C.c_int, _FP, C.POINTER(_FitOpts)],
     "nrv_fit_grad": [C.c_void_p, C.c_int, _U32P, C.c_int, _FP, C.POINTER(_FitStats)],
     "nrv_fit_epoch": [C.c_void_p, C.c_int, _U32P, C.c_int64, C.POINTER(_FitStats)],
@@ -189,20 +185,13 @@ _FIT_T = {                                                                      
     "nrv_fit_params": [C.c_void_p, C.c_int, _FP, _I64P],
     "nrv_fit_set_depth": [C.c_void_p, C.c_int],
     "nrv_fit_depth": [C.c_void_p],
-    "nrv_fit_set_rows_head": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
-    "nrv_fit_get_rows_head": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
-    "nrv_fit_set_rows_lstm4": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
-    "nrv_fit_get_rows_lstm4": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
-    "nrv_fit_set_rows_lstm3": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
-    "nrv_fit_get_rows_lstm3": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
-    "nrv_fit_set_rows_signal": [C.c_void_p, _FP, _FP, _FP, _U8P, _U8P, C.c_int64],
-    "nrv_fit_get_rows_signal": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _FP, _U8P, _U8P],
-    "nrv_fit_set_rows_full": [C.c_void_p, _FP, _FP, _U8P, _U8P, C.c_int64],
-    "nrv_fit_get_rows_full": [C.c_void_p, C.c_int64, C.c_int64, _FP, _FP, _U8P, _U8P],
     "nrv_fit_bn_reestimate": [C.c_void_p, C.c_int, _U32P, C.c_int64],
     "nrv_fit_bn_count": [C.c_void_p],
     "nrv_fit_bn_get": [C.c_void_p, C.c_int, C.c_int, C.POINTER(_FitBnInfo), _FP, _FP, _DP, _DP],
 }
+for _d in fitdepth.DEPTHS:                                                                   # the row doors of every depth
+    _FIT_T["nrv_fit_set_rows" + _d.suffix] = [C.c_void_p] + [_FP] * len(_d.door_args()) + [_U8P, _U8P, C.c_int64]
+    _FIT_T["nrv_fit_get_rows" + _d.suffix] = [C.c_void_p, C.c_int64, C.c_int64] + [_FP] * len(_d.door_args()) + [_U8P, _U8P]
 
 
 _lib = None
@@ -858,23 +847,32 @@ class Reviser:
                                                     C.byref(added)))
         return int(added.value)
 
-    def fit_set_rows(self, flat1, flat2, y1, y2):
-        K = 6 * self.T
-        f1, f2 = _as_f32(flat1, (K,)), _as_f32(flat2, (K,))
+    def _fit_set(self, depth, arrays, y1, y2):
+        """The set door of `depth` (a name of fitdepth.DEPTHS): `arrays` are its float arrays in door order."""
+        d = fitdepth.BY_NAME[depth]
+        xs = [_as_f32(v, sh) for v, sh in zip(arrays, d.door_shapes(self.T))]
         a, b = (np.ascontiguousarray(v, dtype=np.uint8).reshape(-1) for v in (y1, y2))
-        n = f1.shape[0]
-        if f2.shape[0] != n or a.size != n or b.size != n:
-            raise ValueError("flat1 / flat2 / y1 / y2 must have one entry per row")
-        self._check(self._lib.nrv_fit_set_rows(self._h, _ptr(f1, _FP), _ptr(f2, _FP), _ptr(a, _U8P), _ptr(b, _U8P), n))
+        n = xs[0].shape[0]
+        if any(v.shape[0] != n for v in xs) or a.size != n or b.size != n:
+            raise ValueError(" / ".join(d.door_args() + ("y1", "y2")) + " must have one entry per row")
+        self._check(getattr(self._lib, "nrv_fit_set_rows" + d.suffix)(self._h, *(_ptr(v, _FP) for v in xs), _ptr(a, _U8P), _ptr(b, _U8P), n))
+
+    def _fit_get(self, depth, first, count):
+        """The get door of `depth` -> (its float arrays in door order ..., y1, y2) of rows [first, first + count)."""
+        d = fitdepth.BY_NAME[depth]
+        count = self.fit_count() - first if count is None else count
+        xs = tuple(np.empty((count,) + sh, np.float32) for sh in d.door_shapes(self.T))
+        ys = (np.empty(count, np.uint8), np.empty(count, np.uint8))
+        self._check(getattr(self._lib, "nrv_fit_get_rows" + d.suffix)(self._h, first, count, *(_ptr(v, _FP) for v in xs),
+                                                                      *(_ptr(v, _U8P) for v in ys)))
+        return xs + ys
+
+    def fit_set_rows(self, flat1, flat2, y1, y2):
+        self._fit_set("tail", (flat1, flat2), y1, y2)
 
     def fit_get_rows(self, first=0, count=None):
         """-> (flat1, flat2, y1, y2) of rows [first, first + count)."""
-        count = self.fit_count() - first if count is None else count
-        K = 6 * self.T
-        out = (np.empty((count, K), np.float32), np.empty((count, K), np.float32), np.empty(count, np.uint8), np.empty(count, np.uint8))
-        self._check(self._lib.nrv_fit_get_rows(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _U8P),
-                                               _ptr(out[3], _U8P)))
-        return out
+        return self._fit_get("tail", first, count)
 
     def fit_begin(self, model, params=None, opts=None):
         """opts: a tailfit.FitOpts (None: the engine's defaults); params: the vector [Wf | bf | Wo | bo | Ce] (None: the
@@ -890,17 +888,14 @@ class Reviser:
     def fit_n_params(self, model) -> int:
         """The length of a model's parameter vector at the current depth."""
         c = self._n_class(model)
-        front = {FIT_TAIL: 0, FIT_HEAD: 20838, FIT_LSTM4: 164352 + 20838, FIT_LSTM3: 328704 + 164352 + 20838,
-                 FIT_SIGNAL: 25896 + 328704 + 164352 + 20838,
-                 FIT_FULL: 52608 + 25896 + 328704 + 164352 + 20838}[self.fit_depth()]
-        return front + 96 * self.T + 16 + 16 * c + c + 16 * c
+        at = fitdepth.DEPTHS.index(fitdepth.BY_CODE[self.fit_depth()])
+        return sum(d.front for d in fitdepth.DEPTHS[:at + 1]) + 96 * self.T + 16 + 16 * c + c + 16 * c
 
     # ---- the second depth (nanoreviser_amd/headfit.py is the definition): the set holds lstm4 outputs [T][128] per window
     def fit_set_depth(self, depth):
         """FIT_TAIL / FIT_HEAD / FIT_LSTM4 / FIT_LSTM3 / FIT_SIGNAL / FIT_FULL (or "tail" / "head" / "lstm4" / "lstm3" / "signal" /
         "full"), on an empty set only; forgets any fit_begin."""
-        depth = {"tail": FIT_TAIL, "head": FIT_HEAD, "lstm4": FIT_LSTM4, "lstm3": FIT_LSTM3, "signal": FIT_SIGNAL,
-                 "full": FIT_FULL}.get(depth, depth)
+        depth = fitdepth.CODES.get(depth, depth)
         self._check(self._lib.nrv_fit_set_depth(self._h, int(depth)))
 
     def fit_depth(self) -> int:
@@ -910,97 +905,45 @@ class Reviser:
         return d
 
     def fit_set_rows_head(self, x1, x2, y1, y2):
-        a1, a2 = _as_f32(x1, (self.T, 128)), _as_f32(x2, (self.T, 128))
-        a, b = (np.ascontiguousarray(v, dtype=np.uint8).reshape(-1) for v in (y1, y2))
-        n = a1.shape[0]
-        if a2.shape[0] != n or a.size != n or b.size != n:
-            raise ValueError("x1 / x2 / y1 / y2 must have one entry per row")
-        self._check(self._lib.nrv_fit_set_rows_head(self._h, _ptr(a1, _FP), _ptr(a2, _FP), _ptr(a, _U8P), _ptr(b, _U8P), n))
+        self._fit_set("head", (x1, x2), y1, y2)
 
     def fit_get_rows_head(self, first=0, count=None):
         """-> (x1, x2, y1, y2) of rows [first, first + count), x [count][T][128]."""
-        count = self.fit_count() - first if count is None else count
-        sh = (count, self.T, 128)
-        out = (np.empty(sh, np.float32), np.empty(sh, np.float32), np.empty(count, np.uint8), np.empty(count, np.uint8))
-        self._check(self._lib.nrv_fit_get_rows_head(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _U8P),
-                                                    _ptr(out[3], _U8P)))
-        return out
+        return self._fit_get("head", first, count)
 
     # ---- the third depth (nanoreviser_amd/lstm4fit.py is the definition): the set holds BatchNorm'd lstm3 outputs [T][256]
     def fit_set_rows_lstm4(self, xb1, xb2, y1, y2):
-        a1, a2 = _as_f32(xb1, (self.T, 256)), _as_f32(xb2, (self.T, 256))
-        a, b = (np.ascontiguousarray(v, dtype=np.uint8).reshape(-1) for v in (y1, y2))
-        n = a1.shape[0]
-        if a2.shape[0] != n or a.size != n or b.size != n:
-            raise ValueError("xb1 / xb2 / y1 / y2 must have one entry per row")
-        self._check(self._lib.nrv_fit_set_rows_lstm4(self._h, _ptr(a1, _FP), _ptr(a2, _FP), _ptr(a, _U8P), _ptr(b, _U8P), n))
+        self._fit_set("lstm4", (xb1, xb2), y1, y2)
 
     def fit_get_rows_lstm4(self, first=0, count=None):
         """-> (xb1, xb2, y1, y2) of rows [first, first + count), xb [count][T][256]."""
-        count = self.fit_count() - first if count is None else count
-        sh = (count, self.T, 256)
-        out = (np.empty(sh, np.float32), np.empty(sh, np.float32), np.empty(count, np.uint8), np.empty(count, np.uint8))
-        self._check(self._lib.nrv_fit_get_rows_lstm4(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _U8P),
-                                                     _ptr(out[3], _U8P)))
-        return out
+        return self._fit_get("lstm4", first, count)
 
     # ---- the fourth depth (nanoreviser_amd/lstm3fit.py is the definition): the set holds lstm3's inputs [T][192]
     def fit_set_rows_lstm3(self, x1, x2, y1, y2):
-        a1, a2 = _as_f32(x1, (self.T, 192)), _as_f32(x2, (self.T, 192))
-        a, b = (np.ascontiguousarray(v, dtype=np.uint8).reshape(-1) for v in (y1, y2))
-        n = a1.shape[0]
-        if a2.shape[0] != n or a.size != n or b.size != n:
-            raise ValueError("x1 / x2 / y1 / y2 must have one entry per row")
-        self._check(self._lib.nrv_fit_set_rows_lstm3(self._h, _ptr(a1, _FP), _ptr(a2, _FP), _ptr(a, _U8P), _ptr(b, _U8P), n))
+        self._fit_set("lstm3", (x1, x2), y1, y2)
 
     def fit_get_rows_lstm3(self, first=0, count=None):
         """-> (x1, x2, y1, y2) of rows [first, first + count), x [count][T][192]."""
-        count = self.fit_count() - first if count is None else count
-        sh = (count, self.T, 192)
-        out = (np.empty(sh, np.float32), np.empty(sh, np.float32), np.empty(count, np.uint8), np.empty(count, np.uint8))
-        self._check(self._lib.nrv_fit_get_rows_lstm3(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _U8P),
-                                                     _ptr(out[3], _U8P)))
-        return out
+        return self._fit_get("lstm3", first, count)
 
     # ---- the fifth depth (nanoreviser_amd/signalfit.py is the definition): the set holds lstm2 outputs [T][128] per model and
     # ONE array of samples [T][50] for both
     def fit_set_rows_signal(self, x2_1, x2_2, sig, y1, y2):
-        a1, a2, sg = _as_f32(x2_1, (self.T, 128)), _as_f32(x2_2, (self.T, 128)), _as_f32(sig, (self.T, 50))
-        a, b = (np.ascontiguousarray(v, dtype=np.uint8).reshape(-1) for v in (y1, y2))
-        n = a1.shape[0]
-        if a2.shape[0] != n or sg.shape[0] != n or a.size != n or b.size != n:
-            raise ValueError("x2_1 / x2_2 / sig / y1 / y2 must have one entry per row")
-        self._check(self._lib.nrv_fit_set_rows_signal(self._h, _ptr(a1, _FP), _ptr(a2, _FP), _ptr(sg, _FP), _ptr(a, _U8P),
-                                                      _ptr(b, _U8P), n))
+        self._fit_set("signal", (x2_1, x2_2, sig), y1, y2)
 
     def fit_get_rows_signal(self, first=0, count=None):
         """-> (x2_1, x2_2, sig, y1, y2) of rows [first, first + count), x2 [count][T][128], sig [count][T][50]."""
-        count = self.fit_count() - first if count is None else count
-        sh = (count, self.T, 128)
-        out = (np.empty(sh, np.float32), np.empty(sh, np.float32), np.empty((count, self.T, 50), np.float32),
-               np.empty(count, np.uint8), np.empty(count, np.uint8))
-        self._check(self._lib.nrv_fit_get_rows_signal(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _FP),
-                                                      _ptr(out[3], _U8P), _ptr(out[4], _U8P)))
-        return out
+        return self._fit_get("signal", first, count)
 
     # ---- the sixth depth (nanoreviser_amd/fullfit.py is the definition): the set holds ONE array of samples [T][50] and ONE of
     # read features [T][6] for both models
     def fit_set_rows_full(self, sig, feat, y1, y2):
-        sg, ft = _as_f32(sig, (self.T, 50)), _as_f32(feat, (self.T, 6))
-        a, b = (np.ascontiguousarray(v, dtype=np.uint8).reshape(-1) for v in (y1, y2))
-        n = sg.shape[0]
-        if ft.shape[0] != n or a.size != n or b.size != n:
-            raise ValueError("sig / feat / y1 / y2 must have one entry per row")
-        self._check(self._lib.nrv_fit_set_rows_full(self._h, _ptr(sg, _FP), _ptr(ft, _FP), _ptr(a, _U8P), _ptr(b, _U8P), n))
+        self._fit_set("full", (sig, feat), y1, y2)
 
     def fit_get_rows_full(self, first=0, count=None):
         """-> (sig, feat, y1, y2) of rows [first, first + count), sig [count][T][50], feat [count][T][6]."""
-        count = self.fit_count() - first if count is None else count
-        out = (np.empty((count, self.T, 50), np.float32), np.empty((count, self.T, 6), np.float32),
-               np.empty(count, np.uint8), np.empty(count, np.uint8))
-        self._check(self._lib.nrv_fit_get_rows_full(self._h, first, count, _ptr(out[0], _FP), _ptr(out[1], _FP), _ptr(out[2], _U8P),
-                                                    _ptr(out[3], _U8P)))
-        return out
+        return self._fit_get("full", first, count)
 
     @staticmethod
     def _fit_stats(s):

@@ -46,7 +46,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import bnfit, cli, fullfit, headfit, lstm4fit, signalfit, tailfit
+from . import bnfit, cli, fitdepth, headfit, tailfit
 from .weights import load_model, load_species
 
 HISTORY_HEAD = "epoch\tloss\tce\tcenter\tacc\tval_loss\tval_acc\tnonfinite"
@@ -113,7 +113,7 @@ def check_args(a):
         return "--labels_from: not a directory"
     if a.model_type not in ("both", "model1", "model2"):
         return "--model_type must be both, model1 or model2"
-    if a.fit_depth not in ("tail", "head", "lstm4", "signal", "full"):
+    if a.fit_depth not in _DEPTHS:
         return f"--fit_depth must be tail or head, or lstm4, or signal, or full, not {a.fit_depth!r}"
     if a.fit_depth == "tail" and a.fit_init == "fresh_head":
         return "--fit_init fresh_head draws the three dense layers behind lstm4, which --fit_depth tail does not fit"
@@ -142,80 +142,36 @@ def stem(output_model, species, model_no):
     return os.path.join(output_model, species, f"{species}_win13_50ep_model{model_no}")
 
 
-def _start_head(a, k, m, T):
-    """_start at --fit_depth head: tensors 50 .. 59 of the loaded or continued model; a fresh tail keeps the shipped 50 .. 55
-    (they do not depend on T), fresh_head draws all five layers."""
-    path = (a.model1_train_dir, a.model2_train_dir)[k]
-    if path:
-        prev = load_model(path)
-        if prev.T != T or prev.n_class != m.n_class:
-            raise ValueError(f"{path}: a model of T = {prev.T} and {prev.n_class} classes, expected T = {T} and {m.n_class}")
-        th = headfit.params_from_model(prev)
-        cen = os.path.splitext(path)[0] + "_centers.f32"
-        if os.path.exists(cen):
-            c = np.fromfile(cen, "<f4")
-            if c.size == 16 * m.n_class:
-                th[-c.size:] = c
-        return th, "continued"
-    if a.fit_init == "fresh_head":
-        return headfit.fresh_params(T, m.n_class, a.seed + k), "fresh_head"
-    if a.fit_init == "fresh" or T != m.T:
-        return headfit.with_tail(headfit.params_from_model(m.with_window(T)), tailfit.fresh_params(T, m.n_class, a.seed + k)), "fresh"
-    return headfit.params_from_model(m), "transfer"
-
-
-def _start_lstm4(a, k, m, T):
-    """_start at --fit_depth lstm4: _start_head's vector behind tensors 44 .. 49 of the loaded or continued model."""
-    th, how = _start_head(a, k, m, T)
-    path = (a.model1_train_dir, a.model2_train_dir)[k]
-    front = lstm4fit.params_from_model(load_model(path) if path else m.with_window(T))
-    return lstm4fit.with_head(front, th), how
-
-
-def _start_signal(a, k, m, T):
-    """_start at --fit_depth signal: _start_lstm4's vector behind tensors 0, 1, 6, 7, 32 .. 39 of the loaded or continued model."""
-    th, how = _start_lstm4(a, k, m, T)
-    path = (a.model1_train_dir, a.model2_train_dir)[k]
-    front = signalfit.params_from_model(load_model(path) if path else m.with_window(T))
-    return signalfit.with_lstm3(front, signalfit.lstm3fit.with_lstm4(front[signalfit.N_SIGNAL:], th)), how
-
-
-def _start_full(a, k, m, T):
-    """_start at --fit_depth full: _start_signal's vector behind tensors 12 .. 17 and 22 .. 27 of the loaded or continued model."""
-    th, how = _start_signal(a, k, m, T)
-    path = (a.model1_train_dir, a.model2_train_dir)[k]
-    front = fullfit.params_from_model(load_model(path) if path else m.with_window(T))
-    return fullfit.with_signal(front, th), how
-
-
 def _start(a, k, m, T):
-    """The starting parameter vector of model k (0 / 1) and where it came from."""
-    if a.fit_depth == "full":
-        return _start_full(a, k, m, T)
-    if a.fit_depth == "signal":
-        return _start_signal(a, k, m, T)
-    if a.fit_depth == "lstm4":
-        return _start_lstm4(a, k, m, T)
-    if a.fit_depth == "head":
-        return _start_head(a, k, m, T)
+    """The starting parameter vector of model k (0 / 1) and where it came from.  --fit_init and a continued run's centres act on
+    the tail (at --fit_depth tail) or on tensors 50 .. 59 (at every other depth: a fresh tail keeps the shipped 50 .. 55, which do
+    not depend on T, fresh_head draws all five layers); what a deeper depth fits in front of them always starts from the loaded or
+    continued model's own weights."""
+    fit = tailfit if a.fit_depth == "tail" else headfit
     path = (a.model1_train_dir, a.model2_train_dir)[k]
+    own = m.with_window(T)
     if path:
-        prev = load_model(path)
-        if prev.T != T or prev.n_class != m.n_class:
-            raise ValueError(f"{path}: a model of T = {prev.T} and {prev.n_class} classes, expected T = {T} and {m.n_class}")
-        th = tailfit.params_from_model(prev)
+        own = load_model(path)
+        if own.T != T or own.n_class != m.n_class:
+            raise ValueError(f"{path}: a model of T = {own.T} and {own.n_class} classes, expected T = {T} and {m.n_class}")
+        th, how = fit.params_from_model(own), "continued"
         cen = os.path.splitext(path)[0] + "_centers.f32"
         if os.path.exists(cen):
             c = np.fromfile(cen, "<f4")
             if c.size == 16 * m.n_class:
                 th[-c.size:] = c
-        return th, "continued"
-    if a.fit_init == "fresh" or T != m.T:
-        return tailfit.fresh_params(T, m.n_class, a.seed + k), "fresh"
-    return tailfit.params_from_model(m), "transfer"
+    elif a.fit_init == "fresh_head":
+        th, how = headfit.fresh_params(T, m.n_class, a.seed + k), "fresh_head"
+    elif a.fit_init == "fresh" or T != m.T:
+        th, how = tailfit.fresh_params(T, m.n_class, a.seed + k), "fresh"
+        if fit is headfit:
+            th = headfit.with_tail(headfit.params_from_model(own), th)
+    else:
+        th, how = fit.params_from_model(m), "transfer"
+    return (th if fit is tailfit else fitdepth.start_vector(a.fit_depth, own, th)), how
 
 
-_DEPTHS = {"tail": tailfit, "head": headfit, "lstm4": lstm4fit, "signal": signalfit, "full": fullfit}
+_DEPTHS = {d.name: d.fit for d in fitdepth.DEPTHS if d.name != "lstm3"}      # --fit_depth lstm3 is not offered
 
 
 def _default_factory(a, m1, m2):

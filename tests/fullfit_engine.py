@@ -8,6 +8,7 @@ from nanoreviser_amd import fullfit as ff
 from nanoreviser_amd import lstm4fit as l4
 from nanoreviser_amd import signalfit as sf
 from nanoreviser_amd import tailfit as tf
+from nanoreviser_amd.fitdepth import CODES
 from tailfit_engine import FitEcho
 
 
@@ -26,7 +27,7 @@ class FullEcho(FitEcho):
         self.depth_calls, self.depth = calls, depth
 
     def fit_set_depth(self, depth):
-        depth = {"tail": 0, "head": 1, "lstm4": 4, "lstm3": 8, "signal": 16, "full": 32}.get(depth, depth)
+        depth = CODES.get(depth, depth)
         assert self.fit_count() == 0, "nrv_fit_set_depth: the training set is not empty"
         assert depth == 32, "this stand-in only knows the full depth"
         self.depth = int(depth)

@@ -5,6 +5,7 @@ import numpy as np
 
 from nanoreviser_amd import headfit as hf
 from nanoreviser_amd import tailfit as tf
+from nanoreviser_amd.fitdepth import CODES
 from tailfit_engine import FitEcho
 
 
@@ -21,7 +22,7 @@ class HeadEcho(FitEcho):
         self.depth_calls = calls
 
     def fit_set_depth(self, depth):
-        depth = {"tail": 0, "head": 1}.get(depth, depth)
+        depth = CODES.get(depth, depth)
         assert self.fit_count() == 0, "nrv_fit_set_depth: the training set is not empty"
         self.depth = int(depth)
         self.depth_calls.append(self.depth)

@@ -5,6 +5,7 @@ import numpy as np
 
 from nanoreviser_amd import lstm4fit as lf
 from nanoreviser_amd import tailfit as tf
+from nanoreviser_amd.fitdepth import CODES
 from tailfit_engine import FitEcho
 
 
@@ -21,7 +22,7 @@ class Lstm4Echo(FitEcho):
         self.depth_calls, self.depth = calls, depth
 
     def fit_set_depth(self, depth):
-        depth = {"tail": 0, "head": 1, "lstm4": 4}.get(depth, depth)
+        depth = CODES.get(depth, depth)
         assert self.fit_count() == 0, "nrv_fit_set_depth: the training set is not empty"
         assert depth == 4, "this stand-in only knows the lstm4 depth"
         self.depth = int(depth)

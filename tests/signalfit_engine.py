@@ -6,6 +6,7 @@ import numpy as np
 from nanoreviser_amd import lstm4fit as l4
 from nanoreviser_amd import signalfit as sf
 from nanoreviser_amd import tailfit as tf
+from nanoreviser_amd.fitdepth import CODES
 from tailfit_engine import FitEcho
 
 
@@ -24,7 +25,7 @@ class SignalEcho(FitEcho):
         self.depth_calls, self.depth = calls, depth
 
     def fit_set_depth(self, depth):
-        depth = {"tail": 0, "head": 1, "lstm4": 4, "lstm3": 8, "signal": 16}.get(depth, depth)
+        depth = CODES.get(depth, depth)
         assert self.fit_count() == 0, "nrv_fit_set_depth: the training set is not empty"
         assert depth == 16, "this stand-in only knows the signal depth"
         self.depth = int(depth)

@@ -73,7 +73,7 @@ def main(argv=None):
     ap.add_argument("--depths", default="tail,head,lstm4,lstm3", help="the depths to time, in this order (signal and full are not in the default)")
     ap.add_argument("--bn_reestimate", action="store_true", help="time nrv_fit_bn_reestimate against nrv_fit_eval instead of the epoch")
     a = ap.parse_args(argv)
-    from nanoreviser_amd import bnfit, fullfit, headfit, lstm3fit, lstm4fit, signalfit, tailfit
+    from nanoreviser_amd import bnfit, fitdepth, headfit, tailfit
     from nanoreviser_amd.engine import Reviser
     from nanoreviser_amd.weights import load_species
     T, k, n = a.window_size, a.model, a.rows
@@ -93,36 +93,18 @@ def main(argv=None):
         for depth in a.depths.split(","):
             rv.fit_reset()
             rv.fit_set_depth(depth)
-            if depth == "tail":
-                F = np.maximum(rng.normal(0, 1, (n, 6 * T)), 0).astype(np.float32)
-                rv.fit_set_rows(F, F, y1, y2)
-                th = tailfit.fresh_params(T, C, a.seed)
-            elif depth == "full":                          # the shipped model in front of a fresh head
-                rv.fit_set_rows_full(rng.normal(0, 1, (n, T, 50)).astype(np.float32), rng.normal(0, 1, (n, T, 6)).astype(np.float32), y1, y2)
-                m = (m1, m2)[k].with_window(T)
-                th4 = lstm4fit.with_head(lstm4fit.params_from_model(m), headfit.fresh_params(T, C, a.seed))
-                ths = signalfit.with_lstm3(signalfit.params_from_model(m), lstm3fit.with_lstm4(lstm3fit.params_from_model(m), th4))
-                th = fullfit.with_signal(fullfit.params_from_model(m), ths)
-            elif depth == "signal":                        # the shipped signal branch, lstm3 and lstm4 in front of a fresh head
-                X = rng.normal(0, 1, (n, T, 128)).astype(np.float32)
-                rv.fit_set_rows_signal(X, X, rng.normal(0, 1, (n, T, 50)).astype(np.float32), y1, y2)
-                m = (m1, m2)[k].with_window(T)
-                th4 = lstm4fit.with_head(lstm4fit.params_from_model(m), headfit.fresh_params(T, C, a.seed))
-                th = signalfit.with_lstm3(signalfit.params_from_model(m), lstm3fit.with_lstm4(lstm3fit.params_from_model(m), th4))
-            elif depth == "lstm3":                         # the shipped lstm3 and lstm4 in front of a fresh head
-                X = rng.normal(0, 1, (n, T, 192)).astype(np.float32)
-                rv.fit_set_rows_lstm3(X, X, y1, y2)
-                m = (m1, m2)[k].with_window(T)
-                th4 = lstm4fit.with_head(lstm4fit.params_from_model(m), headfit.fresh_params(T, C, a.seed))
-                th = lstm3fit.with_lstm4(lstm3fit.params_from_model(m), th4)
-            elif depth == "lstm4":                         # the shipped lstm4 in front of a fresh head (lstm4 has no fresh start)
-                X = rng.normal(0, 1, (n, T, 256)).astype(np.float32)
-                rv.fit_set_rows_lstm4(X, X, y1, y2)
-                th = lstm4fit.with_head(lstm4fit.params_from_model((m1, m2)[k].with_window(T)), headfit.fresh_params(T, C, a.seed))
-            else:
-                X = np.clip(rng.normal(0, 0.5, (n, T, 128)), -0.999, 0.999).astype(np.float32)
-                rv.fit_set_rows_head(X, X, y1, y2)
-                th = headfit.fresh_params(T, C, a.seed)
+            d = fitdepth.BY_NAME[depth]
+            # seeded rows of the depth's shapes, a per-model array the same for both models: non-negative like main_out's values
+            # at tail depth, inside (-1, 1) like lstm4's outputs at head depth, standard normal at the others
+            draw = {"tail": lambda sh: np.maximum(rng.normal(0, 1, sh), 0), "head": lambda sh: np.clip(rng.normal(0, 0.5, sh), -0.999, 0.999)}
+            xs = []
+            for r in d.rows:
+                xs += [draw.get(depth, lambda sh: rng.normal(0, 1, sh))((n,) + r.shape(T)).astype(np.float32)] * len(r.args)
+            getattr(rv, "fit_set_rows" + d.suffix)(*xs, y1, y2)
+            # a fresh tail at tail depth; at the others a fresh head behind the shipped model's own weights (the LSTMs and the
+            # signal branch have no fresh start)
+            fresh = tailfit.fresh_params(T, C, a.seed) if depth == "tail" else headfit.fresh_params(T, C, a.seed)
+            th = fitdepth.start_vector(depth, (m1, m2)[k].with_window(T), fresh)
             rv.fit_begin(k, th, opts)
             if a.bn_reestimate:
                 rows = np.arange(n, dtype=np.uint32)
