@@ -957,6 +957,35 @@ int nrv_fit_bn_reestimate(nrv_handle* h, int model, const uint32_t* rows, int64_
 int nrv_fit_bn_count(nrv_handle* h);
 int nrv_fit_bn_get(nrv_handle* h, int model, int which, nrv_fit_bn_info* info, float* mean, float* var, double* s1, double* s2);
 
+/* ---- Fitting gamma and beta of the BatchNorms inside the fitted section (opt-in) ----
+ * nanoreviser_amd/bnaffine.py is the definition.  A BatchNorm inside the section stays in its inference form on the CURRENT
+ * moving statistics, y = x s + h with r = 1 / sqrt(var + 1e-3), s = gamma r, h = beta - mean s, folded in f32 exactly as
+ * nrv_create folds a file's tensors; the statistics stay frozen during a step (Keras in training phase would normalise with the
+ * batch's - that deviation remains) and move only by nrv_fit_bn_reestimate.  gamma and beta become parameters:
+ *     g_gamma = r sum dy (x - mean) / b          g_beta = sum dy / b
+ * per channel over (row, t) (and the 50 samples for a conv BatchNorm), dy the derivative of the batch's SUM of row losses by the
+ * BatchNorm's output, x the activation it normalises; the sum is formed in the pivoted form, never as sum dy x - mean sum dy.
+ * THE VECTOR.  While the switch is on, nrv_fit_begin, _grad, _epoch, _eval and _params take and return vectors with a block in
+ * FRONT: for every BatchNorm inside, in tensor order, gamma [C] then beta [C] - NRV_FIT_PARAMS_BN(depth) floats.
+ *   nrv_fit_set_bn_affine  on = 1 / 0.  May be called with rows in the set (the set does not depend on it); forgets any
+ *     nrv_fit_begin of both models (the vector has another length).  nrv_fit_set_depth switches it off.  Refused under its own
+ *     name, the handle staying usable: a raw-read call in flight; on = 1 at a depth with no BatchNorm inside (NRV_FIT_TAIL,
+ *     NRV_FIT_HEAD, NRV_FIT_LSTM4).
+ *   nrv_fit_bn_affine      1 while it is on, else 0.
+ *   nrv_fit_begin          params = NULL starts the block from the handle's own gamma / beta; the pairs are folded ON THE DEVICE
+ *     from the block and the handle's statistics and are the bytes nrv_create folded.
+ *   a step                 the two sums leave the launch that holds the unscaled dy (csrc/nrv_bnaffine.h) as per-workgroup
+ *     partials, added in ascending order by a reduce launch with a flag range of its own; the block takes part in the finite
+ *     check over the whole vector and in the ONE Adam launch; behind the update one launch refolds (s, h) from the vector's
+ *     gamma / beta and the block's current mean / variance.  No atomics; the same calls give the same bytes; nrv_fit_epoch
+ *     still enqueues everything without a host synchronisation.
+ *   nrv_fit_bn_reestimate  folds each stage with the vector's CURRENT gamma / beta; the pivot stays the loaded mean; gamma,
+ *     beta, Adam's state and t keep their bytes, and later refolds use the new statistics.
+ * To run a fitted model, write it (bnaffine.fitted_model) and create a handle from it. */
+#define NRV_FIT_PARAMS_BN(depth) ((depth) == NRV_FIT_LSTM3 ? 512 : (depth) == NRV_FIT_SIGNAL ? 544 : (depth) == NRV_FIT_FULL ? 864 : 0)
+int nrv_fit_set_bn_affine(nrv_handle* h, int on);
+int nrv_fit_bn_affine(nrv_handle* h);
+
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be
  * complete in stream order.  The handle's own stream is a blocking stream, i.e. it is ordered

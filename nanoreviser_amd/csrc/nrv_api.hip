@@ -9,6 +9,7 @@
 #include "nrv_signalfit.h"    // ... at depth NRV_FIT_SIGNAL: lstm2's outputs and the samples as the set, the signal branch's forward and backward, dS out of lstm3
 #include "nrv_fullfit.h"      // ... at depth NRV_FIT_FULL: the raw windows as the set, lstm1 and lstm2 forward and backward, all of dXin out of lstm3
 #include "nrv_bnfit.h"        // ... nrv_fit_bn_reestimate: the moments of the BatchNorms inside the fitted section, the fit-owned BatchNorm block
+#include "nrv_bnaffine.h"     // ... nrv_fit_set_bn_affine: gamma / beta of those BatchNorms as parameters - the sums' epilogue, the refold
 #include "nrv_block.h"
 
 #include <algorithm>
@@ -763,6 +764,10 @@ struct nrv_handle {
     unsigned* d_order = nullptr; size_t cap_order = 0;        // row indices of a call
     float* d_p = nullptr; size_t cap_p = 0;                   // nrv_fit_eval's rows
     double* d_bnpart = nullptr; size_t cap_bnpart = 0;        // nrv_fit_bn_reestimate: one chunk's partial moments of a stage
+    // nrv_fit_set_bn_affine: gamma / beta of the BatchNorms inside the section are the front of the vector; the partials of
+    // their sums [workgroups of a batch's first chunk][NRV_FIT_PARAMS_BN] (nrv_bnaffine.h)
+    bool bn_affine = false;
+    float* d_pbn = nullptr; size_t cap_pbn = 0;
     struct Model {
       float* d_par = nullptr;                                 // [4][P]
       // depths NRV_FIT_LSTM3 and deeper: the fit's own BatchNorm block [kBnFloats] (nrv_bnfit.h) - every fit launch reads its
@@ -1715,7 +1720,7 @@ void nrv_destroy(nrv_handle* h) {
     (void)hipFree(h->fit.m[m].d_bn); (void)hipFree(h->fit.m[m].d_bnacc);
   }
   (void)hipFree(h->fit.d_partial); (void)hipFree(h->fit.d_pstat); (void)hipFree(h->fit.d_order); (void)hipFree(h->fit.d_p); (void)hipFree(h->fit.d_flag);
-  (void)hipFree(h->fit.d_l4); (void)hipFree(h->fit.d_gl4); (void)hipFree(h->fit.d_bnpart);
+  (void)hipFree(h->fit.d_l4); (void)hipFree(h->fit.d_gl4); (void)hipFree(h->fit.d_bnpart); (void)hipFree(h->fit.d_pbn);
   (void)hipFree(h->fit.d_l3); (void)hipFree(h->fit.d_gl3); (void)hipFree(h->fit.d_ident);
   (void)hipFree(h->fit.d_rd); (void)hipFree(h->fit.d_grd);
   (void)hipFree(h->fit.d_sg); (void)hipFree(h->fit.d_pconv); (void)hipFree(h->fit.d_gdense);
@@ -3844,7 +3849,8 @@ static int fit_scratch(nrv_handle* h, void** p, size_t* cap, size_t bytes) {
   return poison_fill(h, *p, c, h->stream);
 }
 // the parameters of a model's vector at the handle's depth, and the depth's row cap with the words a refusal names it by
-static int fit_params_n(const nrv_handle* h, int model) { return fit_at(h).params(h->T, h->dm[model].C); }
+static int fit_bn_block(const nrv_handle* h) { return h->fit.bn_affine ? NRV_FIT_PARAMS_BN(h->fit.depth) : 0; }   // the gamma / beta block in front
+static int fit_params_n(const nrv_handle* h, int model) { return fit_bn_block(h) + fit_at(h).params(h->T, h->dm[model].C); }
 static int64_t fit_cap_rows(const nrv_handle* h) { return h->fit.max_rows[&fit_at(h) - kFitDepths]; }
 static std::string fit_cap_words(const nrv_handle* h) { return std::string(fit_at(h).at) + " (" + fit_at(h).env + ")"; }
 // the arrays of the set at the handle's depth - where the handle keeps each and its bytes per row - in door order: the depth's
@@ -4153,6 +4159,15 @@ int nrv_fit_depth(nrv_handle* h) {
   return rc ? rc : h->fit.depth;
 }
 
+// the parameter blocks of both models are those of the other vector length: freed, nrv_fit_begin allocates them again
+static void fit_bn_affine_off(nrv_handle* h) {
+  for (int m = 0; m < 2; ++m) {
+    (void)hipFree(h->fit.m[m].d_par); (void)hipFree(h->fit.m[m].d_state);
+    h->fit.m[m].d_par = nullptr; h->fit.m[m].d_state = nullptr;
+  }
+  h->fit.bn_affine = false;
+}
+
 int nrv_fit_set_depth(nrv_handle* h, int depth) {
   static const char* who = "nrv_fit_set_depth";
   const int rc = fit_enter(h, who);
@@ -4166,6 +4181,7 @@ int nrv_fit_set_depth(nrv_handle* h, int depth) {
     F.m[m].begun = false;
     F.m[m].t = 0;
   }
+  if (F.bn_affine) fit_bn_affine_off(h);                   // the switch is off at every depth until it is set again
   if (depth == F.depth) return NRV_OK;
   for (int m = 0; m < 2; ++m) {                            // the set and the parameter blocks are the other depth's
     (void)hipFree(F.x[m]); (void)hipFree(F.shared[m]); (void)hipFree(F.y[m]);
@@ -4203,6 +4219,22 @@ static int fit_head_own(nrv_handle* h, int model, float* d_par) {
   return NRV_OK;
 }
 
+// bn_refold_kernel's arguments: every BatchNorm inside the section, gamma / beta in the vector's block, (s, h) and the
+// statistics in the model's block
+static BnRefoldArgs fit_refold_args(nrv_handle* h, int model) {
+  static const int at_s[5] = {kBnConv + 32, kBnConv + 248, kBnS1, kBnS2, kBnS3}, at_h[5] = {kBnConv + 40, kBnConv + 256, kBnH1, kBnH2, kBnH3};
+  const FitDepth& D = fit_at(h);
+  BnRefoldArgs a{};
+  int at = 0;
+  for (int i = 0; i < D.n_bn; ++i) {
+    const int w = D.bn[i];
+    a.bn[i] = BnRefoldArgs::One{kFitBn[w].C, at, at_s[w], at_h[w], kBnMean + kFitBn[w].at};
+    at += 2 * kFitBn[w].C;
+  }
+  a.par = h->fit.m[model].d_par; a.blk = h->fit.m[model].d_bn; a.var_off = kBnVar - kBnMean;
+  return a;
+}
+
 int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_opts* opts) {
   static const char* who = "nrv_fit_begin";
   const int rc = fit_enter(h, who);
@@ -4219,7 +4251,7 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
   nrv_handle::Fit::Model& M = h->fit.m[model];
   const DevModel& d = h->dm[model];
   const FitDepth& D = fit_at(h);
-  const int C = d.C, K = 6 * h->T, P = fit_params_n(h, model);
+  const int C = d.C, K = 6 * h->T, P = fit_params_n(h, model), ob = fit_bn_block(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   M.begun = false;
   if (!M.d_par) {
@@ -4229,12 +4261,20 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
   HIPCHK(h, hipMemsetAsync(M.d_par, 0, (size_t)4 * P * 4, h->stream));
   if (params) HIPCHK(h, hipMemcpyAsync(M.d_par, params, (size_t)P * 4, hipMemcpyHostToDevice, h->stream));
   else {
+    float* const par0 = M.d_par + ob;                       // the depth's own vector, behind the gamma / beta block
+    if (ob) {                                               // the block: gamma, beta of every BatchNorm inside as the file has them
+      std::vector<float> gb;
+      for (int i = 0; i < D.n_bn; ++i)
+        for (int k = 0; k < 2; ++k) gb.insert(gb.end(), d.bn_raw[k].begin() + kFitBn[D.bn[i]].at, d.bn_raw[k].begin() + kFitBn[D.bn[i]].at + kFitBn[D.bn[i]].C);
+      HIPCHK(h, hipMemcpyAsync(M.d_par, gb.data(), (size_t)ob * 4, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));           // (gb is a local)
+    }
     const size_t src[4] = {d.fw, d.fb, d.ow, d.ob}, cnt[4] = {(size_t)16 * K, 16, (size_t)16 * C, (size_t)C};
     size_t at = 0;
-    float* const sgp = M.d_par + (D.rd ? kRdN : 0);         // where the signal depth's vector starts
+    float* const sgp = par0 + (D.rd ? kRdN : 0);            // where the signal depth's vector starts
     if (D.rd) {                                             // tensors 12 .. 17 and 22 .. 27, unfolded as the file has them
-      HIPCHK(h, hipMemcpyAsync(M.d_par, d.all + d.l1raw, (size_t)kR1N * 4, hipMemcpyDeviceToDevice, h->stream));
-      HIPCHK(h, hipMemcpyAsync(M.d_par + kR1N, d.all + d.l2raw, (size_t)kR2N * 4, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(par0, d.all + d.l1raw, (size_t)kR1N * 4, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(par0 + kR1N, d.all + d.l2raw, (size_t)kR2N * 4, hipMemcpyDeviceToDevice, h->stream));
     }
     if (D.sg) {                                             // tensors 0, 1 and 6, 7 out of the conv image, 32 and 33 as the file has them
       HIPCHK(h, hipMemcpyAsync(sgp, d.all + d.conv, (size_t)32 * 4, hipMemcpyDeviceToDevice, h->stream));
@@ -4244,21 +4284,21 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
       at = (D.rd ? kRdN : 0) + kSgN;
     }
     if (D.l3) {                                             // tensors 34 .. 39, unfolded as the file has them
-      HIPCHK(h, hipMemcpyAsync(M.d_par + at, d.all + d.l3raw, (size_t)kL3N * 4, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(par0 + at, d.all + d.l3raw, (size_t)kL3N * 4, hipMemcpyDeviceToDevice, h->stream));
       at += kL3N;
     }
     if (D.l4) {                                             // tensors 44 .. 49, unfolded as the file has them
-      HIPCHK(h, hipMemcpyAsync(M.d_par + at, d.all + d.l4raw, (size_t)kL4N * 4, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(par0 + at, d.all + d.l4raw, (size_t)kL4N * 4, hipMemcpyDeviceToDevice, h->stream));
       at += kL4N;
     }
     if (D.mlp) {
       HIPCHK(h, hipStreamSynchronize(h->stream));
-      const int rc2 = fit_head_own(h, model, M.d_par + at);
+      const int rc2 = fit_head_own(h, model, par0 + at);
       if (rc2) return rc2;
       at += kHfMlp;
     }
     for (int i = 0; i < 4; ++i) {
-      HIPCHK(h, hipMemcpyAsync(M.d_par + at, d.all + src[i], cnt[i] * 4, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(par0 + at, d.all + src[i], cnt[i] * 4, hipMemcpyDeviceToDevice, h->stream));
       at += cnt[i];
     }
   }
@@ -4276,6 +4316,10 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
       HIPCHK(h, hipMemcpyAsync(M.d_bn + ath[l], d.all + d.l_h[l], (size_t)nl[l] * 4, hipMemcpyDeviceToDevice, h->stream));
     }
     HIPCHK(h, hipMemcpyAsync(M.d_bn + kBnPivot, d.bn_raw[2].data(), (size_t)kBnCh * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(M.d_bn + kBnMean, d.bn_raw[2].data(), (size_t)kBnCh * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(M.d_bn + kBnVar, d.bn_raw[3].data(), (size_t)kBnCh * 4, hipMemcpyHostToDevice, h->stream));
+    // with gamma / beta in the vector the pairs are folded from it on the device: from the handle's own they are nrv_create's bytes
+    if (ob) hipLaunchKernelGGL(bn_refold_kernel, dim3(D.n_bn), dim3(256), 0, h->stream, fit_refold_args(h, model));
     M.bn_mean = d.bn_raw[2]; M.bn_var = d.bn_raw[3];
     M.bn_s1.assign(kBnCh, 0.0); M.bn_s2.assign(kBnCh, 0.0);
     for (int i = 0; i < 5; ++i) M.bn_n[i] = 0;
@@ -4336,10 +4380,16 @@ static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
   if (D.mlp) {
     wg = (size_t)fit_head_wgs(b_max);
     if ((rc = fit_scratch(h, (void**)&h->fit.d_flag, &h->fit.cap_flag,
-                          (size_t)((kRdN + 255) / 256 + 1 + (kSgDense + 255) / 256 + kL3N / 256 + kL4N / 256 + (kHeadFitMaxP + 255) / 256) * 4)))
+                          (size_t)((NRV_FIT_PARAMS_BN(NRV_FIT_FULL) + 255) / 256 + (kRdN + 255) / 256 + 1 + (kSgDense + 255) / 256 + kL3N / 256 + kL4N / 256 +
+                                   (kHeadFitMaxP + 255) / 256) * 4)))
       return rc;
   }
   size_t pn = (size_t)fit_params_n(h, model);
+  if (fit_bn_block(h)) {                                     // the block's partials: one per workgroup of a chunk's ceil(M / 32)
+    const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
+    if (grad && (rc = fit_scratch(h, (void**)&h->fit.d_pbn, &h->fit.cap_pbn, (rows * h->T + 31) / 32 * fit_bn_block(h) * 4))) return rc;
+    pn -= fit_bn_block(h);
+  }
   if (D.rd) {                                                // one chunk's nine arrays of nrv_fullfit.h, the read block's partials
     const size_t rows = (size_t)(b_max < kL4ChunkRows ? (b_max + 31) / 32 * 32 : kL4ChunkRows);
     if ((rc = fit_scratch(h, (void**)&h->fit.d_rd, &h->fit.cap_rd, rows * h->T * (grad ? kRdPairGrad : kRdPair) * 4)) ||
@@ -4438,7 +4488,9 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
   if (D.l4) {
     const int T = h->T;
     const bool grad = mode != kTailEval;
-    const int orr = full ? kRdN : 0;                        // where the signal depth's vector starts
+    const int ob = fit_bn_block(h);                         // nrv_fit_set_bn_affine: the gamma / beta block in front of everything
+    const int obr = ob + (full ? kR1N : 0);                 // where lstm2's block starts
+    const int orr = ob + (full ? kRdN : 0);                 // where the signal depth's vector starts
     const int os = orr + (sg ? kSgN : 0);                   // where the lstm3 depth's vector starts
     const int o3 = os + (l3 ? kL3N : 0);                    // where the lstm4 depth's vector starts
     // every BatchNorm inside the fitted section is read from the fit's own block (the handle's pairs until nrv_fit_bn_reestimate);
@@ -4467,13 +4519,20 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
     float* const gz1 = full ? cs2 + rcap * 128 : nullptr;
     float* const gz2 = full ? gz1 + rcap * 128 : nullptr;
     const int sg_wg = sg ? ((b < kL4ChunkRows ? b : kL4ChunkRows) * T + 31) / 32 : 0;     // workgroups of sig_backward_kernel in the first chunk: the conv block's partials
+    const int bn_wg = ((b < kL4ChunkRows ? b : kL4ChunkRows) * T + 31) / 32;              // ... of the launches that leave the gamma / beta block's
+    // the sums of BatchNorm `which` (of kFitBn) over this chunk: its place in the block's partials, the block's current statistics
+    int bn_at[5] = {0, 0, 0, 0, 0};
+    for (int i = 0, at = 0; i < D.n_bn; at += 2 * kFitBn[D.bn[i]].C, ++i) bn_at[D.bn[i]] = at;
+    auto bn_sums = [&](int which, const float* x, int c0) {
+      return BnAffArgs{x, M.d_bn + kBnMean + kFitBn[which].at, M.d_bn + kBnVar + kFitBn[which].at, h->fit.d_pbn + bn_at[which], ob, c0 > 0 ? 1 : 0};
+    };
     for (int c0 = 0; c0 < b; c0 += kL4ChunkRows) {
       const int bc = b - c0 < kL4ChunkRows ? b - c0 : kL4ChunkRows, tiles = (bc + 31) / 32;
       const SigArgs sa{sg ? h->fit.x[model] : nullptr, h->fit.shared[0], d_rows + c0, M.d_par + orr, fbn + kBnConv, xin, fkeep, ds, gz3,
                        h->fit.d_pconv, h->fit.d_gdense, T, bc * T, grad ? 1 : 0, c0 > 0 ? 1 : 0, dh2, fbn + kBnS2};
-      const RlArgs r1{h->fit.shared[1], d_rows + c0, M.d_par, fbn + kBnS1, fbn + kBnH1, h1, x1b, gz1, cs1, dh1,
+      const RlArgs r1{h->fit.shared[1], d_rows + c0, M.d_par + ob, fbn + kBnS1, fbn + kBnH1, h1, x1b, gz1, cs1, dh1,
                       h->fit.d_grd, 32, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
-      const RlArgs r2{x1b, h->fit.d_ident, M.d_par + kR1N, fbn + kBnS2, fbn + kBnH2, h2, xin, gz2, cs2, dh2,
+      const RlArgs r2{x1b, h->fit.d_ident, M.d_par + obr, fbn + kBnS2, fbn + kBnH2, h2, xin, gz2, cs2, dh2,
                       full ? h->fit.d_grd + kR1N : nullptr, 192, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
       if (full) {                                           // lstm1, lstm2 (X2b into columns 0 .. 127 of Xin), then S into the rest
         if (h->act == 0) {
@@ -4509,22 +4568,26 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
       hipLaunchKernelGGL(l4_wgrad_kernel, dim3(kL4WgM * kL4WgN, 2), dim3(256), 0, h->stream, la);
       if (l3) {
         const L4DxArgs da{gz, M.d_par + o3, fbn + kBnS3, dx3, bc * T};
-        hipLaunchKernelGGL(l4_dx_kernel, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, da);
+        if (ob) hipLaunchKernelGGL(l4_dx_kernel<L4DxBnArgs>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, L4DxBnArgs{da, bn_sums(4, h3, c0)});
+        else hipLaunchKernelGGL(l4_dx_kernel<L4DxArgs>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, da);
         if (h->act == 0) hipLaunchKernelGGL(l3_backward_kernel<0>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
         else hipLaunchKernelGGL(l3_backward_kernel<1>, dim3(tiles, 2), dim3(256), 0, h->stream, l3a);
         hipLaunchKernelGGL(l3_wgrad_kernel, dim3(kL3WgM * kL3WgN, 2), dim3(256), 0, h->stream, l3a);
       }
       if (sg) {
-        if (full) hipLaunchKernelGGL(l3_dx_kernel<true>, dim3((bc * T + 31) / 32), dim3(384), 0, h->stream, sa);
+        if (full && ob) hipLaunchKernelGGL((l3_dx_kernel<true, SigBnArgs>), dim3((bc * T + 31) / 32), dim3(384), 0, h->stream, SigBnArgs{sa, bn_sums(3, h2, c0)});
+        else if (full) hipLaunchKernelGGL(l3_dx_kernel<true>, dim3((bc * T + 31) / 32), dim3(384), 0, h->stream, sa);
         else hipLaunchKernelGGL(l3_dx_kernel<false>, dim3((bc * T + 31) / 32), dim3(128), 0, h->stream, sa);
-        hipLaunchKernelGGL(sig_backward_kernel, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
+        if (ob) hipLaunchKernelGGL(sig_backward_kernel<SigBnArgs>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, SigBnArgs{sa, bn_sums(0, nullptr, c0)});
+        else hipLaunchKernelGGL(sig_backward_kernel<SigArgs>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
         hipLaunchKernelGGL(sig_wgrad_kernel, dim3(kSgWgM, 2), dim3(512), 0, h->stream, sa);
       }
       if (full) {
-        const RlDxArgs dxa{gz2, M.d_par + kR1N, fbn + kBnS1, dh1, bc * T};
+        const RlDxArgs dxa{gz2, M.d_par + obr, fbn + kBnS1, dh1, bc * T};
         if (h->act == 0) hipLaunchKernelGGL((rl_backward_kernel<32, 64, 0>), dim3(tiles, 2), dim3(256), 0, h->stream, r2);
         else hipLaunchKernelGGL((rl_backward_kernel<32, 64, 1>), dim3(tiles, 2), dim3(256), 0, h->stream, r2);
-        hipLaunchKernelGGL((rl_dx_kernel<32, 64>), dim3((bc * T + 31) / 32), dim3(64), 0, h->stream, dxa);
+        if (ob) hipLaunchKernelGGL((rl_dx_kernel<32, 64, RlDxBnArgs>), dim3((bc * T + 31) / 32), dim3(64), 0, h->stream, RlDxBnArgs{dxa, bn_sums(2, h1, c0)});
+        else hipLaunchKernelGGL((rl_dx_kernel<32, 64>), dim3((bc * T + 31) / 32), dim3(64), 0, h->stream, dxa);
         if (h->act == 0) hipLaunchKernelGGL((rl_backward_kernel<6, 16, 0>), dim3(tiles, 2), dim3(128), 0, h->stream, r1);
         else hipLaunchKernelGGL((rl_backward_kernel<6, 16, 1>), dim3(tiles, 2), dim3(128), 0, h->stream, r1);
         hipLaunchKernelGGL((rl_wgrad_kernel<32, 64>), dim3(4 * 4, 2, kRdSlices), dim3(256), 0, h->stream, r2);
@@ -4538,9 +4601,13 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
     // every reduce launch has a flag range of its own and the update launch has as many workgroups as there are flags)
     const int o4 = o3 + kL4N, PH = P - o4, bl3 = l3 ? kL3N / 256 : 0, bl4 = kL4N / 256;
     // (at depth NRV_FIT_FULL the read block's kRdSlices partials in front of everything, with 206 flags of their own)
-    const int blr = full ? (kRdN + 255) / 256 : 0;
+    // (with nrv_fit_set_bn_affine the gamma / beta block's partials in front of that, with 2, 3 or 4 flags of their own, and behind
+    // the update the refold of the fit's pairs)
+    const int blb = (ob + 255) / 256;
+    const int blr = blb + (full ? (kRdN + 255) / 256 : 0);
+    if (ob) hipLaunchKernelGGL(head_reduce_kernel, dim3(blb), dim3(256), 0, h->stream, adam(h->fit.d_pbn, bn_wg, ob, 0, 0));
     const int bls = blr + (sg ? 1 + (kSgDense + 255) / 256 : 0);
-    if (full) hipLaunchKernelGGL(head_reduce_kernel, dim3(blr), dim3(256), 0, h->stream, adam(h->fit.d_grd, kRdSlices, kRdN, 0, 0));
+    if (full) hipLaunchKernelGGL(head_reduce_kernel, dim3(blr - blb), dim3(256), 0, h->stream, adam(h->fit.d_grd, kRdSlices, kRdN, ob, blb));
     if (sg) {
       hipLaunchKernelGGL(head_reduce_kernel, dim3(1), dim3(256), 0, h->stream, adam(h->fit.d_pconv, sg_wg, kSgConv, orr, blr));
       hipLaunchKernelGGL(head_reduce_kernel, dim3(bls - blr - 1), dim3(256), 0, h->stream, adam(h->fit.d_gdense, 1, kSgDense, orr + kSgWs, blr + 1));
@@ -4548,8 +4615,9 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
     if (l3) hipLaunchKernelGGL(head_reduce_kernel, dim3(bl3), dim3(256), 0, h->stream, adam(h->fit.d_gl3, 1, kL3N, os, bls));
     hipLaunchKernelGGL(head_reduce_kernel, dim3(bl4), dim3(256), 0, h->stream, adam(h->fit.d_gl4, 1, kL4N, o3, bls + bl3));
     hipLaunchKernelGGL(head_reduce_kernel, dim3((PH + 255) / 256), dim3(256), 0, h->stream, adam(h->fit.d_partial, wg, PH, o4, bls + bl3 + bl4));
-    hipLaunchKernelGGL(head_adam_kernel, dim3(sg ? bls + bl3 + bl4 + (PH + 255) / 256 : blocks), dim3(256), 0, h->stream,
+    hipLaunchKernelGGL(head_adam_kernel, dim3(sg || ob ? bls + bl3 + bl4 + (PH + 255) / 256 : blocks), dim3(256), 0, h->stream,
                        adam(h->fit.d_partial, wg, P, 0, 0));
+    if (ob && mode == kTailTrain) hipLaunchKernelGGL(bn_refold_kernel, dim3(D.n_bn), dim3(256), 0, h->stream, fit_refold_args(h, model));
     return;
   }
   HeadGradArgs a;
@@ -4662,6 +4730,11 @@ int nrv_fit_bn_reestimate(nrv_handle* h, int model, const uint32_t* rows, int64_
     return rc;
   std::vector<float> blk((size_t)kBnFloats);
   std::vector<double> acc((size_t)2 * kBnCh);
+  std::vector<float> gb((size_t)fit_bn_block(h));            // nrv_fit_set_bn_affine: the stages are folded with the vector's CURRENT gamma / beta
+  if (!gb.empty()) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(gb.data(), M.d_par, gb.size() * 4, hipMemcpyDeviceToHost));
+  }
   for (int stage = nbn == 1 ? 2 : 0; stage < 3; ++stage) {
     fit_launch(h, model, h->fit.d_order, b, kTailEval, 0, nullptr, stage);
     HIPCHK(h, hipGetLastError());
@@ -4671,7 +4744,7 @@ int nrv_fit_bn_reestimate(nrv_handle* h, int model, const uint32_t* rows, int64_
     // the stage's BatchNorms: the new statistics folded as nrv_create folds the tensors of a file, into the block
     static const int stage_of[5] = {0, 1, 0, 1, 2}, at_s[5] = {kBnConv + 32, kBnConv + 248, kBnS1, kBnS2, kBnS3},
                      at_h[5] = {kBnConv + 40, kBnConv + 256, kBnH1, kBnH2, kBnH3};
-    for (int i = 0; i < nbn; ++i) {
+    for (int i = 0, gb_at = 0; i < nbn; gb_at += 2 * kFitBn[list[i]].C, ++i) {
       const int w = list[i], at = kFitBn[w].at, C = kFitBn[w].C;
       if (stage_of[w] != stage) continue;
       for (int c = 0; c < C; ++c) {
@@ -4680,12 +4753,35 @@ int nrv_fit_bn_reestimate(nrv_handle* h, int model, const uint32_t* rows, int64_
       }
       M.bn_n[w] = (int64_t)b * T * (w < 2 ? kSig : 1);
       std::vector<float> sc(C), sh(C);
-      bn_fold(d.bn_raw[0].data() + at, d.bn_raw[1].data() + at, M.bn_mean.data() + at, M.bn_var.data() + at, C, sc.data(), sh.data());
+      bn_fold(gb.empty() ? d.bn_raw[0].data() + at : gb.data() + gb_at, gb.empty() ? d.bn_raw[1].data() + at : gb.data() + gb_at + C,
+              M.bn_mean.data() + at, M.bn_var.data() + at, C, sc.data(), sh.data());
       HIPCHK(h, hipMemcpy(M.d_bn + at_s[w], sc.data(), (size_t)C * 4, hipMemcpyHostToDevice));
       HIPCHK(h, hipMemcpy(M.d_bn + at_h[w], sh.data(), (size_t)C * 4, hipMemcpyHostToDevice));
     }
   }
   return NRV_OK;
+}
+
+int nrv_fit_set_bn_affine(nrv_handle* h, int on) {
+  static const char* who = "nrv_fit_set_bn_affine";
+  const int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (on && !fit_at(h).n_bn)
+    return fit_refuse(h, who, "no BatchNorm lies inside the fitted section (depths NRV_FIT_LSTM3, NRV_FIT_SIGNAL and NRV_FIT_FULL have one)");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int m = 0; m < 2; ++m) {                            // any nrv_fit_begin is forgotten: its vector has the other length
+    h->fit.m[m].begun = false;
+    h->fit.m[m].t = 0;
+  }
+  if ((on != 0) == h->fit.bn_affine) return NRV_OK;
+  fit_bn_affine_off(h);
+  h->fit.bn_affine = on != 0;
+  return NRV_OK;
+}
+
+int nrv_fit_bn_affine(nrv_handle* h) {
+  const int rc = check_handle(h);
+  return rc ? rc : (h->fit.bn_affine ? 1 : 0);
 }
 
 int nrv_fit_bn_get(nrv_handle* h, int model, int which, nrv_fit_bn_info* info, float* mean, float* var, double* s1, double* s2) {

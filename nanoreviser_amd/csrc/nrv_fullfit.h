@@ -237,8 +237,10 @@ struct RlDxArgs {
   int M;                                 // chunk rows x T
 };
 // grid = ceil(M / 32), one wave per 32 input columns: dx = (dz_fw W_f^T + dz_bw W_b^T) sc, k ascending, forward direction first
-template <int DX, int H>
-__global__ void __launch_bounds__(DX * 2) rl_dx_kernel(const RlDxArgs a) {
+struct RlDxBnArgs : RlDxArgs { BnAffArgs bn; };             // nrv_fit_set_bn_affine: acc is dy of the BatchNorm in front of the layer
+// A = RlDxBnArgs also leaves that BatchNorm's two sums (nrv_bnaffine.h)
+template <int DX, int H, class A = RlDxArgs>
+__global__ void __launch_bounds__(DX * 2) rl_dx_kernel(const A a) {
   static_assert(DX % 32 == 0, "whole column tiles");
   constexpr int G = 4 * H;
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
@@ -259,6 +261,7 @@ __global__ void __launch_bounds__(DX * 2) rl_dx_kernel(const RlDxArgs a) {
     }
   }
   const float scn = a.sc[n];
+  if constexpr (std::is_same_v<A, RlDxBnArgs>) bn_dy_partial<DX>(a.bn, acc, lane, m0, a.M, n);
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
     const int m = m0 + acc_row(reg, lane);

@@ -2,6 +2,7 @@
 // the forward and the backward pass of that Bi-LSTM over a batch, the data gradient out of lstm4, and lstm3's weight gradients.
 #pragma once
 #include "nrv_lstm4fit.h"  // its four launches run unchanged on this depth's scratch Xb4
+#include "nrv_bnaffine.h"  // the variant of l4_dx_kernel that also leaves bn_l3's two sums
 
 namespace nrv {
 
@@ -164,8 +165,10 @@ struct L4DxArgs {
   float* dx3;                            // [M][256]
   int M;                                 // chunk rows x T
 };
-// grid = ceil(M / 32); wave w owns the 64 output columns 64 w ..
-__global__ void __launch_bounds__(256) l4_dx_kernel(const L4DxArgs a) {
+struct L4DxBnArgs : L4DxArgs { BnAffArgs bn; };             // nrv_fit_set_bn_affine: acc is bn_l3's dy before the scale
+// grid = ceil(M / 32); wave w owns the 64 output columns 64 w ..  A = L4DxBnArgs also leaves bn_l3's two sums (nrv_bnaffine.h)
+template <class A = L4DxArgs>
+__global__ void __launch_bounds__(256) l4_dx_kernel(const A a) {
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m0 = blockIdx.x * 32;
@@ -192,6 +195,7 @@ __global__ void __launch_bounds__(256) l4_dx_kernel(const L4DxArgs a) {
   for (int nt = 0; nt < 2; ++nt) {
     const int n = wave * 64 + nt * 32 + l31;
     const float scn = a.sc[n];
+    if constexpr (std::is_same_v<A, L4DxBnArgs>) bn_dy_partial<256>(a.bn, acc[nt], lane, m0, a.M, n);
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
       const int m = m0 + acc_row(reg, lane);

@@ -84,6 +84,8 @@ struct SigArgs {
   const float* s2 = nullptr;             // [128] the frozen BatchNorm behind lstm2
 };
 
+struct SigBnArgs : SigArgs { BnAffArgs bn; };               // nrv_fit_set_bn_affine: the launches that also leave a BatchNorm's two sums
+
 // the 264-float image conv_positions reads: the vector's kernels and biases with the handle's frozen scales and shifts
 __device__ __forceinline__ void sig_conv_image(const SigArgs& a, float* cwl, int tid) {
   for (int i = tid; i < 264; i += 256)
@@ -159,8 +161,10 @@ __global__ void __launch_bounds__(256) sig_forward_kernel(const SigArgs a) {
 
 // grid = ceil(M / 32), 128 threads.  FULL (depth NRV_FIT_FULL): 384 threads, the same product over all 192 columns of dXin - wave w
 // the columns 32 w .. - whose first 128 go to dh2 times s2
-template <bool FULL = false>
-__global__ void __launch_bounds__(FULL ? 384 : 128) l3_dx_kernel(const SigArgs a) {
+// A = SigBnArgs (nrv_fit_set_bn_affine, FULL only): the first 128 columns are bn_l2's dy before the scale, and their two sums are left
+template <bool FULL = false, class A = SigArgs>
+__global__ void __launch_bounds__(FULL ? 384 : 128) l3_dx_kernel(const A a) {
+  static_assert(FULL || std::is_same_v<A, SigArgs>, "bn_l2 lies inside the section at depth NRV_FIT_FULL only");
   constexpr int C0 = FULL ? 0 : 128;
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -180,6 +184,8 @@ __global__ void __launch_bounds__(FULL ? 384 : 128) l3_dx_kernel(const SigArgs a
       for (int j = 0; j < 4; ++j) acc = mfma32(av[j], bv[j], acc);
     }
   }
+  if constexpr (std::is_same_v<A, SigBnArgs>)
+    if (wave < 4) bn_dy_partial<128>(a.bn, acc, lane, m0, a.M, wave * 32 + l31);
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
     const int m = m0 + acc_row(reg, lane);
@@ -189,10 +195,40 @@ __global__ void __launch_bounds__(FULL ? 384 : 128) l3_dx_kernel(const SigArgs a
   }
 }
 
+
 constexpr int kSgDfs = 401, kSgC1s = 52 * 8 + 1, kSgSs = 53;          // odd row strides: the pairs' rows on different banks
 
-// grid = ceil(M / 32)
-__global__ void __launch_bounds__(256) sig_backward_kernel(const SigArgs a) {
+// The 16 sums (gamma [8] then beta [8]) every thread holds of one conv BatchNorm -> the workgroup's partial: the 256 threads are
+// added through LDS in two ascending rounds of 16, r is applied to the gamma sums, and the partial is stored or added (cont)
+__device__ __forceinline__ void bn_conv_partial(const BnAffArgs& b, const float (&sg)[8], const float (&sb)[8], int which, int tid) {
+#pragma clang fp contract(off)
+  __shared__ float red[16 * 256];
+  __shared__ float red2[16 * 16];
+#pragma unroll
+  for (int o = 0; o < 8; ++o) { red[o * 256 + tid] = sg[o]; red[(8 + o) * 256 + tid] = sb[o]; }
+  __syncthreads();
+  {
+    const int q = tid >> 4, sub = tid & 15;
+    float s = red[q * 256 + sub * 16];
+    for (int j = 1; j < 16; ++j) s += red[q * 256 + sub * 16 + j];
+    red2[q * 16 + sub] = s;
+  }
+  __syncthreads();
+  if (tid < 16) {
+    float s = red2[tid * 16];
+    for (int j = 1; j < 16; ++j) s += red2[tid * 16 + j];
+    if (tid < 8) s *= 1.f / __builtin_sqrtf(b.var[which * 8 + tid] + kBnEps);
+    float* out = b.part + (size_t)blockIdx.x * b.stride + which * 16 + tid;
+    *out = b.cont ? *out + s : s;
+  }
+  __syncthreads();
+}
+
+// grid = ceil(M / 32).  A = SigBnArgs (nrv_fit_set_bn_affine): also the two sums of bn_c2 (dy = dF, x = a2) and of bn_c1 (dy = dc1,
+// x = a1 recomputed in the forward launch's operation order), each thread over its own samples ascending
+template <class A = SigArgs>
+__global__ void __launch_bounds__(256) sig_backward_kernel(const A a) {
+  constexpr bool BN = std::is_same_v<A, SigBnArgs>;
   __shared__ float dfl[32 * kSgDfs];     // dF [pair][p * 8 + o], then da2 in its place
   __shared__ float c1l[32 * kSgC1s];     // c1 [pair][(p + 1) * 8 + ci] with a zero sample on either side, then da1 in its place
   __shared__ float sgl[32 * kSgSs];      // sig [pair][p + 1], likewise
@@ -260,6 +296,11 @@ __global__ void __launch_bounds__(256) sig_backward_kernel(const SigArgs a) {
   }
   __syncthreads();
   const float* w2 = cwl + 48;
+  float bsg[8], bsb[8];                                     // BN: this thread's sums of one conv BatchNorm
+  if constexpr (BN) {
+#pragma unroll
+    for (int o = 0; o < 8; ++o) { bsg[o] = 0.f; bsb[o] = 0.f; }
+  }
   for (int p = p0; p < p0 + np; ++p) {
     float z[8];
 #pragma unroll
@@ -272,10 +313,24 @@ __global__ void __launch_bounds__(256) sig_backward_kernel(const SigArgs a) {
 #pragma unroll
         for (int o = 0; o < 8; ++o) z[o] = __builtin_fmaf(cv, w2[(k * 8 + ci) * 8 + o], z[o]);
       }
+    if constexpr (BN) {
+#pragma clang fp contract(off)
+#pragma unroll
+      for (int o = 0; o < 8; ++o) {
+        const float dy = df[p * 8 + o];
+        bsb[o] += dy;
+        bsg[o] += dy * (__builtin_fmaxf(z[o], 0.f) - a.bn.mean[8 + o]);
+      }
+    }
 #pragma unroll
     for (int o = 0; o < 8; ++o) df[p * 8 + o] = z[o] > 0.f ? df[p * 8 + o] * w2[200 + o] : 0.f;
   }
   __syncthreads();
+  if constexpr (BN) {
+    bn_conv_partial(a.bn, bsg, bsb, 1, tid);
+#pragma unroll
+    for (int o = 0; o < 8; ++o) { bsg[o] = 0.f; bsb[o] = 0.f; }
+  }
   // gw2 [k][ci][o] and gb2 [o]: one thread per element, (pair, sample) ascending
   float* part = a.pconv + (size_t)blockIdx.x * kSgConv;
   if (tid < 200) {
@@ -307,11 +362,26 @@ __global__ void __launch_bounds__(256) sig_backward_kernel(const SigArgs a) {
         for (int ci = 0; ci < 8; ++ci) d[ci] = __builtin_fmaf(w2[(k * 8 + ci) * 8 + o], dv, d[ci]);
       }
     }
+    if constexpr (BN) {
+#pragma clang fp contract(off)
+      const float xm = sg[p], xc = sg[p + 1], xp = sg[p + 2];
+#pragma unroll
+      for (int ci = 0; ci < 8; ++ci) {
+        float v = cwl[24 + ci];
+        v = __builtin_fmaf(xm, cwl[ci], v);
+        v = __builtin_fmaf(xc, cwl[8 + ci], v);
+        v = __builtin_fmaf(xp, cwl[16 + ci], v);
+        v = __builtin_fmaxf(v, 0.f);
+        bsb[ci] += d[ci];
+        bsg[ci] += d[ci] * (v - a.bn.mean[ci]);
+      }
+    }
     const unsigned bits = m1l[r * 52 + p];
 #pragma unroll
     for (int ci = 0; ci < 8; ++ci) c1[(p + 1) * 8 + ci] = (bits >> ci & 1u) ? d[ci] * cwl[32 + ci] : 0.f;
   }
   __syncthreads();
+  if constexpr (BN) bn_conv_partial(a.bn, bsg, bsb, 0, tid);
   // gw1 [k][o] and gb1 [o]
   if (tid < 32) {
     const int o = tid & 7, k = tid >> 3;                    // 3: the bias

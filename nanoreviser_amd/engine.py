@@ -54,6 +54,7 @@ SYMBOLS = [
     "nrv_fit_set_rows_signal", "nrv_fit_get_rows_signal",
     "nrv_fit_set_rows_full", "nrv_fit_get_rows_full",
     "nrv_fit_bn_reestimate", "nrv_fit_bn_count", "nrv_fit_bn_get",
+    "nrv_fit_set_bn_affine", "nrv_fit_bn_affine",
 ]
 FIT_TAIL, FIT_HEAD, FIT_LSTM4, FIT_LSTM3, FIT_SIGNAL, FIT_FULL = (d.code for d in fitdepth.DEPTHS)   # NRV_FIT_*: 0, 1, 4, 8, 16, 32
 FIT_MAX_BATCH = 65536               # NRV_FIT_MAX_BATCH
@@ -187,6 +188,8 @@ _FIT_T = {                                                                      
     "nrv_fit_depth": [C.c_void_p],
     "nrv_fit_bn_reestimate": [C.c_void_p, C.c_int, _U32P, C.c_int64],
     "nrv_fit_bn_count": [C.c_void_p],
+    "nrv_fit_set_bn_affine": [C.c_void_p, C.c_int],
+    "nrv_fit_bn_affine": [C.c_void_p],
     "nrv_fit_bn_get": [C.c_void_p, C.c_int, C.c_int, C.POINTER(_FitBnInfo), _FP, _FP, _DP, _DP],
 }
 for _d in fitdepth.DEPTHS:                                                                   # the row doors of every depth
@@ -889,7 +892,8 @@ class Reviser:
         """The length of a model's parameter vector at the current depth."""
         c = self._n_class(model)
         at = fitdepth.DEPTHS.index(fitdepth.BY_CODE[self.fit_depth()])
-        return sum(d.front for d in fitdepth.DEPTHS[:at + 1]) + 96 * self.T + 16 + 16 * c + c + 16 * c
+        bn = fitdepth.DEPTHS[at].bn if self.fit_bn_affine() else 0
+        return bn + sum(d.front for d in fitdepth.DEPTHS[:at + 1]) + 96 * self.T + 16 + 16 * c + c + 16 * c
 
     # ---- the second depth (nanoreviser_amd/headfit.py is the definition): the set holds lstm4 outputs [T][128] per window
     def fit_set_depth(self, depth):
@@ -995,6 +999,18 @@ class Reviser:
             self._check(self._lib.nrv_fit_bn_get(self._h, model, which, None, _ptr(mean, _FP), _ptr(var, _FP), _ptr(s1, _DP), _ptr(s2, _DP)))
             out[names[info.tensor_base]] = {"tensor_base": int(info.tensor_base), "n": int(info.n), "mean": mean, "var": var, "s1": s1, "s2": s2}
         return out
+
+    def fit_set_bn_affine(self, on):
+        """Fit gamma and beta of the BatchNorms inside the fitted section too (nanoreviser_amd/bnaffine.py is the definition):
+        while it is on, every vector of fit_begin / fit_grad / fit_params has their block in front - fitdepth's `bn` floats.
+        Forgets any fit_begin; fit_set_depth switches it off."""
+        self._check(self._lib.nrv_fit_set_bn_affine(self._h, 1 if on else 0))
+
+    def fit_bn_affine(self) -> bool:
+        v = int(self._lib.nrv_fit_bn_affine(self._h))
+        if v < 0:
+            self._check(v)
+        return bool(v)
 
     def fit_params(self, model):
         """-> (the parameter vector, t)."""

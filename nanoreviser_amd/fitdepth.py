@@ -23,6 +23,7 @@ class Depth(NamedTuple):
     suffix: str               # of the nrv_fit_set_rows* / nrv_fit_get_rows* doors
     rows: Tuple[Rows, ...]    # the float arrays of a row, in door order
     front: int                # parameters this depth puts in front of the depth before it
+    bn: int = 0               # NRV_FIT_PARAMS_BN: the gamma / beta block in front of the vector while fit_set_bn_affine is on
 
     @property
     def fit(self):
@@ -40,10 +41,10 @@ DEPTHS = (
     Depth("tail", 0, "tailfit", "", (Rows(("flat1", "flat2"), lambda T: (6 * T,), False),), 0),
     Depth("head", 1, "headfit", "_head", (Rows(("x1", "x2"), lambda T: (T, 128), False),), 20838),
     Depth("lstm4", 4, "lstm4fit", "_lstm4", (Rows(("xb1", "xb2"), lambda T: (T, 256), False),), 164352),
-    Depth("lstm3", 8, "lstm3fit", "_lstm3", (Rows(("x1", "x2"), lambda T: (T, 192), False),), 328704),
+    Depth("lstm3", 8, "lstm3fit", "_lstm3", (Rows(("x1", "x2"), lambda T: (T, 192), False),), 328704, 512),
     Depth("signal", 16, "signalfit", "_signal",
-          (Rows(("x2_1", "x2_2"), lambda T: (T, 128), False), Rows(("sig",), lambda T: (T, 50), True)), 25896),
-    Depth("full", 32, "fullfit", "_full", (Rows(("sig",), lambda T: (T, 50), True), Rows(("feat",), lambda T: (T, 6), True)), 52608),
+          (Rows(("x2_1", "x2_2"), lambda T: (T, 128), False), Rows(("sig",), lambda T: (T, 50), True)), 25896, 544),
+    Depth("full", 32, "fullfit", "_full", (Rows(("sig",), lambda T: (T, 50), True), Rows(("feat",), lambda T: (T, 6), True)), 52608, 864),
 )
 BY_NAME = {d.name: d for d in DEPTHS}
 BY_CODE = {d.code: d for d in DEPTHS}

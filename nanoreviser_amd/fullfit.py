@@ -169,17 +169,20 @@ def forward(feat, sig, theta, rb, cb, sc, sh, T: int, C: int, act: int = 0, dtyp
     return (X2b,) + signalfit.forward(X2b, sig, np.asarray(theta)[N_READ:], cb, sc, sh, T, C, act, dtype)
 
 
-def batch_terms(feat, sig, y, theta, rb, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64):
+def batch_terms(feat, sig, y, theta, rb, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64, taps=None):
     """One batch -> (g [P]: the gradient of L, FitStats of the batch with steps = nonfinite = 0).  Gate derivatives are decided
-    on the forward value; every gradient is divided by n."""
+    on the forward value; every gradient is divided by n.  taps: a dict that receives signalfit's three pairs and "bn_l2":
+    (dx2, the raw H2), "bn_l1": (dX1b, the raw H1) - what bnaffine.py sums; nothing returned depends on it."""
     dt = np.dtype(dtype)
     theta = np.asarray(theta)
     k = read_branch(feat, theta, rb, T, C, act, dt)
     n = k["feat"].shape[0]
-    gs, st, dx2 = signalfit.batch_terms_dx(k["X2b"], sig, y, theta[N_READ:], cb, sc, sh, T, C, opts, act, dt)
+    gs, st, dx2 = signalfit.batch_terms_dx(k["X2b"], sig, y, theta[N_READ:], cb, sc, sh, T, C, opts, act, dt, taps)
     parts = [a.astype(dt) for a in unpack(theta, T, C)[:12]]
     s1, s2 = np.asarray(rb[0]).astype(dt), np.asarray(rb[2]).astype(dt)
     g2, dX1b = _bilstm_back(k["X1b"], k["H2"], k["k2"], dx2 * s2, parts[6:], 64, T, act, dt, True)
+    if taps is not None:
+        taps["bn_l2"], taps["bn_l1"] = (dx2, k["H2"]), (dX1b, k["H1"])
     g1, _ = _bilstm_back(k["feat"], k["H1"], k["k1"], dX1b * s1, parts[:6], 16, T, act, dt, False)
     g = np.concatenate([a.ravel() for a in g1 + g2]) / dt.type(n)
     return np.concatenate([g.astype(dt), gs]), st

@@ -117,15 +117,18 @@ def batch_terms(Xin, y, theta, sc, sh, T: int, C: int, opts: FitOpts, act: int =
     return batch_terms_dx(Xin, y, theta, sc, sh, T, C, opts, act, dtype)[:2]
 
 
-def batch_terms_dx(Xin, y, theta, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64):
+def batch_terms_dx(Xin, y, theta, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64, taps=None):
     """batch_terms and the data gradient behind it -> (g, FitStats, dXin [n][T][192]: the sum over both directions (forward
     first) and all steps of dz3 W3^T - the derivative of the batch's SUM of row losses, not divided by n).  signalfit.py goes on
-    from its columns 128 .. 191."""
+    from its columns 128 .. 191.  taps: a dict that receives "bn_l3": (dXb4, the raw H3) - what bnaffine.py sums; nothing
+    returned depends on it."""
     dt = np.dtype(dtype)
     theta = np.asarray(theta)
     Xin, H3, keep = lstm(Xin, theta, T, C, act, dt)
     n = Xin.shape[0]
     g4, st, dXb4 = lstm4fit.batch_terms_dx(bn(H3, sc, sh, dt), y, theta[N_LSTM3:], T, C, opts, act, dt)
+    if taps is not None:
+        taps["bn_l3"] = (dXb4, H3)
     dX3 = dXb4 * np.asarray(sc).astype(dt)
     parts = [a.astype(dt) for a in unpack(theta, T, C)[:6]]
     one = dt.type(1)

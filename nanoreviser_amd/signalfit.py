@@ -123,14 +123,16 @@ def batch_terms(x2, sig, y, theta, cb, sc, sh, T: int, C: int, opts: FitOpts, ac
     return batch_terms_dx(x2, sig, y, theta, cb, sc, sh, T, C, opts, act, dtype)[:2]
 
 
-def batch_terms_dx(x2, sig, y, theta, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64):
+def batch_terms_dx(x2, sig, y, theta, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64, taps=None):
     """batch_terms and the data gradient behind it -> (g, FitStats, dx2 [n][T][128]: columns 0 .. 127 of lstm3fit's dXin - the
-    derivative of the batch's SUM of row losses by x2, not divided by n).  fullfit.py goes on from it."""
+    derivative of the batch's SUM of row losses by x2, not divided by n).  fullfit.py goes on from it.  taps: a dict that
+    receives lstm3fit's "bn_l3" and "bn_c2": (dF [n][T][50][8], a2), "bn_c1": (dc1, a1) - what bnaffine.py sums; nothing returned
+    depends on it."""
     dt = np.dtype(dtype)
     theta = np.asarray(theta)
     k = branch(sig, theta, cb, T, C, dt)
     n = k["sig"].shape[0]
-    g3, st, dXin = lstm3fit.batch_terms_dx(xin(x2, k["S"], T, dt), y, theta[N_SIGNAL:], sc, sh, T, C, opts, act, dt)
+    g3, st, dXin = lstm3fit.batch_terms_dx(xin(x2, k["S"], T, dt), y, theta[N_SIGNAL:], sc, sh, T, C, opts, act, dt, taps)
     w1, b1, w2, b2, Ws, bs = [a.astype(dt) for a in unpack(theta, T, C)[:6]]
     s1, s2 = np.asarray(cb[0]).astype(dt), np.asarray(cb[2]).astype(dt)
     dS = dXin[..., 128:]
@@ -143,6 +145,8 @@ def batch_terms_dx(x2, sig, y, theta, cb, sc, sh, T: int, C: int, opts: FitOpts,
     gw2 = np.stack([np.einsum("ntpc,ntpo->co", cp[..., kk:kk + N_SIG_IN, :], da2) for kk in range(3)])
     gb2 = da2.sum(axis=(0, 1, 2))
     dc1 = sum(dp[..., 2 - kk:2 - kk + N_SIG_IN, :] @ w2[kk].T for kk in range(3))      # da2[p - kk + 1]
+    if taps is not None:
+        taps["bn_c2"], taps["bn_c1"] = (dF, k["a2"]), (dc1, k["a1"])
     da1 = np.where(k["a1"] > 0, dc1 * s1, dt.type(0))
     sp = np.pad(k["sig"], ((0, 0), (0, 0), (1, 1)))
     gw1 = np.stack([np.einsum("ntp,ntpo->o", sp[..., kk:kk + N_SIG_IN], da1) for kk in range(3)])

@@ -34,6 +34,12 @@ fitted section - three at signal depth, all five at full depth - on the device f
 the first epoch, at the starting parameters (nanoreviser_amd/bnfit.py is the definition).  Every epoch and every validation pass
 then runs on the new statistics, the written model carries them, and _summary.json gains a `bn_reestimate` entry.  gamma and beta
 stay the loaded ones.  With -e 0 nothing is fitted and the loaded model is written with re-estimated statistics alone.
+
+--fit_bn_affine (off by default; --fit_depth signal or full) fits gamma and beta of the BatchNorms inside the fitted section too:
+they go in front of the parameter vector and take part in every update, each BatchNorm still applied in its inference form on
+the moving statistics, which stay frozen during a step (nanoreviser_amd/bnaffine.py is the definition).  The written model
+carries the fitted gamma / beta, and _summary.json gains a `bn_affine` entry: per BatchNorm the largest |change of gamma| and
+|change of beta|.  With --bn_reestimate the statistics are re-estimated first, at the starting gamma / beta, then the fit runs.
 """
 from __future__ import annotations
 
@@ -46,7 +52,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import bnfit, cli, fitdepth, headfit, tailfit
+from . import bnaffine, bnfit, cli, fitdepth, headfit, tailfit
 from .weights import load_model, load_species
 
 HISTORY_HEAD = "epoch\tloss\tce\tcenter\tacc\tval_loss\tval_acc\tnonfinite"
@@ -81,6 +87,8 @@ def get_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("--bn_reestimate", action="store_true", default=argparse.SUPPRESS,        # (in the namespace only when given)
                    help="re-estimate the moving statistics of the BatchNorms inside the fitted section from the training rows before "
                         "the first epoch (--fit_depth signal or full); with -e 0 that alone is written")
+    p.add_argument("--fit_bn_affine", action="store_true", default=argparse.SUPPRESS,        # (in the namespace only when given)
+                   help="fit gamma and beta of the BatchNorms inside the fitted section too (--fit_depth signal or full)")
     p.add_argument("--model_dir", default=None, help="root of model/<species>/ (default: next to the package)")
     p.add_argument("-g", "--basecall_group", dest="basecall_group", default="Basecall_1D_000")
     p.add_argument("-s", "--basecall_subgroup", dest="basecall_subgroup", default="BaseCalled_template")
@@ -103,6 +111,11 @@ def bn_reestimate(a) -> bool:
     return bool(getattr(a, "bn_reestimate", False))
 
 
+def fit_bn_affine(a) -> bool:
+    """--fit_bn_affine was given."""
+    return bool(getattr(a, "fit_bn_affine", False))
+
+
 def check_args(a):
     """-> the message of the first refusal, or None."""
     if not a.fast5_base_dir or not os.path.isdir(a.fast5_base_dir):
@@ -123,6 +136,8 @@ def check_args(a):
         return "-w must be in 1 .. 32"
     if bn_reestimate(a) and a.fit_depth not in ("signal", "full"):
         return f"--bn_reestimate: no BatchNorm lies inside the fitted section at --fit_depth {a.fit_depth} (signal and full have them)"
+    if fit_bn_affine(a) and a.fit_depth not in ("signal", "full"):
+        return f"--fit_bn_affine: no BatchNorm lies inside the fitted section at --fit_depth {a.fit_depth} (signal and full have them)"
     if a.epochs < (0 if bn_reestimate(a) else 1):
         return "-e must be at least 1" + (" (0 with --bn_reestimate)" if a.epochs < 0 else "")
     if not 1 <= a.batch_size <= tailfit.MAX_BATCH:
@@ -168,7 +183,10 @@ def _start(a, k, m, T):
             th = headfit.with_tail(headfit.params_from_model(own), th)
     else:
         th, how = fit.params_from_model(m), "transfer"
-    return (th if fit is tailfit else fitdepth.start_vector(a.fit_depth, own, th)), how
+    th = th if fit is tailfit else fitdepth.start_vector(a.fit_depth, own, th)
+    if fit_bn_affine(a):                                   # gamma / beta of the loaded or continued model in front
+        th = np.concatenate([bnaffine.params_from_model(a.fit_depth, own)[:bnaffine.n_block(a.fit_depth)], th])
+    return th, how
 
 
 _DEPTHS = {d.name: d.fit for d in fitdepth.DEPTHS if d.name != "lstm3"}      # --fit_depth lstm3 is not offered
@@ -229,7 +247,7 @@ def fit_model(a, rv, k, theta0, n_train, n_val, log=print):
         lines.append(f"{ep + 1}\t{loss:.6f}\t{ce:.6f}\t{cn:.6f}\t{st.acc():.6f}\t{vl}\t{va}\t{st.nonfinite}")
         log(f"[s:::] model{k + 1} epoch {ep + 1}/{a.epochs}: loss {loss:.4f} acc {st.acc():.4f} val_loss {vl} val_acc {va}")
     theta, _ = rv.fit_params(k)
-    assert theta.size == _DEPTHS[a.fit_depth].n_params(rv.T, C)
+    assert theta.size == _DEPTHS[a.fit_depth].n_params(rv.T, C) + (bnaffine.n_block(a.fit_depth) if fit_bn_affine(a) else 0)
     return theta, lines, bn_stats
 
 
@@ -252,6 +270,8 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
         rv.fit_reset()
         if a.fit_depth != "tail":
             rv.fit_set_depth(a.fit_depth)
+        if fit_bn_affine(a):
+            rv.fit_set_bn_affine(True)
         used, skipped = add_reads(a, rv)
         n = rv.fit_count()
         if n == 0:
@@ -270,9 +290,14 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
             m = (m1, m2)[k]
             deep = a.fit_depth != "tail"
             fit = _DEPTHS[a.fit_depth]
-            fitted = fit.fitted_model(m, theta, T)
+            nb = bnaffine.n_block(a.fit_depth) if fit_bn_affine(a) else 0
+            fitted = bnaffine.fitted_model(a.fit_depth, m, theta, T) if nb else fit.fitted_model(m, theta, T)
             tailfit.write_f32(bnfit.with_stats(fitted, bn_stats) if bn_stats else fitted, st)
-            fit.unpack(theta, T, m.n_class)[-1].astype("<f4").tofile(st + "_centers.f32")
+            fit.unpack(theta[nb:], T, m.n_class)[-1].astype("<f4").tofile(st + "_centers.f32")
+            moved = {}
+            for name, (sg, sb) in (bnaffine.spans(a.fit_depth).items() if nb else ()):
+                d = np.abs(theta.astype(np.float64) - np.asarray(starts[k][0], np.float64))
+                moved[name] = {"max_dgamma": float(d[sg].max()), "max_dbeta": float(d[sb].max())}
             with open(st + "_history.tsv", "w") as fp:
                 fp.write(HISTORY_HEAD + "\n" + "\n".join(lines) + "\n")
             with open(st + "_summary.json", "w") as fp:
@@ -280,7 +305,9 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
                                        "validation_split": a.validation_split, "seed": a.seed, "lr": a.lr,
                                        "center_weight": a.center_weight, "class_weight": list(a.cw1 if k == 0 else a.cw2),
                                        "init": starts[k][1], "labels_from": os.path.abspath(a.labels_from),
-                                       **({"fit_depth": a.fit_depth} if deep else {})},
+                                       **({"fit_depth": a.fit_depth} if deep else {}),
+                                       **({"fit_bn_affine": True} if nb else {})},
+                           **({"bn_affine": moved} if nb else {}),
                            **({"bn_reestimate": bnfit.drift(bnfit.bn_of(m), bn_stats)} if bn_stats else {}),
                            "rows": n, "train_rows": n_train, "val_rows": n_val, "reads": used,
                            "skipped_reads": [list(s) for s in skipped], "seconds": round(time.time() - t0, 3)}, fp, indent=1)

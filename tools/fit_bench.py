@@ -13,6 +13,10 @@ and the spread (min .. max) are printed as rows/s, then one JSON line with every
 --bn_reestimate times nrv_fit_bn_reestimate over all rows instead of the epoch (depths lstm3, signal and full; give them with
 --depths), by the same protocol, and in the same process nrv_fit_eval over the same rows as the yardstick: the rate in rows/s and
 the ratio of a re-estimation to its number of passes (three at signal and full depth, one at lstm3 depth) x one nrv_fit_eval.
+
+--bn_affine times the epoch twice per depth in the same process (depths lstm3, signal and full; give them with --depths): with
+nrv_fit_set_bn_affine off, then on - gamma and beta of the BatchNorms inside the fitted section in front of the vector, from the
+model's own - by the same protocol, and prints the switch-on figure with the switch-off one next to it.
 """
 import argparse
 import json
@@ -72,8 +76,9 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--depths", default="tail,head,lstm4,lstm3", help="the depths to time, in this order (signal and full are not in the default)")
     ap.add_argument("--bn_reestimate", action="store_true", help="time nrv_fit_bn_reestimate against nrv_fit_eval instead of the epoch")
+    ap.add_argument("--bn_affine", action="store_true", help="time the epoch with nrv_fit_set_bn_affine off, then on, in one process")
     a = ap.parse_args(argv)
-    from nanoreviser_amd import bnfit, fitdepth, headfit, tailfit
+    from nanoreviser_amd import bnaffine, bnfit, fitdepth, headfit, tailfit
     from nanoreviser_amd.engine import Reviser
     from nanoreviser_amd.weights import load_species
     T, k, n = a.window_size, a.model, a.rows
@@ -132,16 +137,29 @@ def main(argv=None):
                       f"{np.median(bn) * 1e3:.2f} ms; nrv_fit_eval {np.median(ev) * 1e3:.2f} ms (min {ev.min() * 1e3:.2f}, max "
                       f"{ev.max() * 1e3:.2f}); ratio to {passes} x eval {np.median(ratio):.3f} (min {ratio.min():.3f}, max {ratio.max():.3f})")
                 continue
-            for ep in range(a.warmup):
-                rv.fit_epoch(k, tailfit.epoch_order(n, a.seed, ep))
-            secs = []
-            for ep in range(a.repeats):
-                order = tailfit.epoch_order(n, a.seed, a.warmup + ep)
-                t0 = time.perf_counter()
-                st = rv.fit_epoch(k, order)                # returns after the stream's synchronise
-                secs.append(time.perf_counter() - t0)
-                assert st.rows == n and st.nonfinite == 0, st
-            secs = np.array(secs)
+            def epochs():
+                for ep in range(a.warmup):
+                    rv.fit_epoch(k, tailfit.epoch_order(n, a.seed, ep))
+                secs = []
+                for ep in range(a.repeats):
+                    order = tailfit.epoch_order(n, a.seed, a.warmup + ep)
+                    t0 = time.perf_counter()
+                    st = rv.fit_epoch(k, order)            # returns after the stream's synchronise
+                    secs.append(time.perf_counter() - t0)
+                    assert st.rows == n and st.nonfinite == 0, st
+                return np.array(secs)
+            secs = epochs()
+            if a.bn_affine:                                # the same rows and start with the block in front, in the same process
+                off = secs
+                rv.fit_set_bn_affine(True)
+                nb = bnaffine.n_block(depth)
+                th = np.concatenate([bnaffine.params_from_model(depth, (m1, m2)[k].with_window(T))[:nb], th])
+                rv.fit_begin(k, th, opts)
+                secs = epochs()
+                nbat = -(-n // a.batch_size)
+                print(f"{depth}: switch off {np.median(n / off):,.0f} rows/s, {np.median(off) / nbat * 1e6:.1f} us per batch (epoch "
+                      f"{np.median(off) * 1e3:.2f} ms, min {off.min() * 1e3:.2f}, max {off.max() * 1e3:.2f}); switch on, {nb} more parameters, "
+                      f"x {np.median(secs) / np.median(off):.4f}:")
             rate = n / secs
             gf = flop_per_row(depth, T, C) * 1e-9
             out[depth] = {"params": int(th.size), "batches": -(-n // a.batch_size), "epoch_ms_median": float(np.median(secs) * 1e3),
@@ -149,6 +167,10 @@ def main(argv=None):
                           "rows_per_s_median": float(np.median(rate)), "rows_per_s_min": float(rate.min()),
                           "rows_per_s_max": float(rate.max()), "gflop_per_batch": gf * a.batch_size,
                           "gflop_per_s_median": float(np.median(rate) * gf)}
+            if a.bn_affine:
+                out[depth].update(bn_affine=True, off_epoch_ms_median=float(np.median(off) * 1e3), off_epoch_ms_min=float(off.min() * 1e3),
+                                  off_epoch_ms_max=float(off.max() * 1e3), off_rows_per_s_median=float(np.median(n / off)),
+                                  on_over_off_median=float(np.median(secs) / np.median(off)))
             print(f"{depth}: {np.median(rate):,.0f} rows/s (min {rate.min():,.0f}, max {rate.max():,.0f}); epoch of {n} rows in "
                   f"{np.median(secs) * 1e3:.2f} ms = {np.median(secs) / out[depth]['batches'] * 1e6:.1f} us per batch of {a.batch_size}; "
                   f"{out[depth]['gflop_per_s_median']:,.0f} GFLOP/s of the algorithm's own operations")
