@@ -867,7 +867,8 @@ int nrv_fit_get_rows_lstm3(nrv_handle* h, int64_t first, int64_t count, float* x
  * lstm2 and their BatchNorms (12 .. 31) AND the three BatchNorms inside the fitted section (2 .. 5, 8 .. 11, 40 .. 43).  TWO STATED
  * DEVIATIONS: those three BatchNorms are applied in their inference form from the moving statistics as the handle holds them
  * (behind a convolution relu(conv) * s + h, one f32 multiply and one f32 add), where Keras in training phase would normalise
- * with the batch's statistics and fit gamma and beta; and the reference's Dropout(0.2) behind the identity block is not applied.
+ * with the batch's statistics and fit gamma and beta; and the reference's Dropout(0.2) behind the identity block is not applied -
+ * a deviation that holds only while nrv_fit_set_dropout (below) is off.
  * The constant is 16: 2, 3, 5, 6, 7, 9 .. 15, 17 and -1 stay refused.
  *   nrv_fit_set_depth  takes NRV_FIT_SIGNAL under the rules above.
  * THE SET at this depth.  Per model x2 f32 [rows][T][128] - the BatchNorm'd f32 lstm2 output of the window - and the same y
@@ -902,7 +903,7 @@ int nrv_fit_get_rows_signal(nrv_handle* h, int64_t first, int64_t count, float* 
  * BatchNorms (2 .. 5, 8 .. 11, 18 .. 21, 28 .. 31, 40 .. 43).  THE STATED DEVIATIONS are the signal depth's, with bn_l1 and bn_l2
  * under the first: X1b = h1 * s_l1 + h_l1 and X2b = h2 * s_l2 + h_l2 from the moving statistics as the handle holds them (one f32
  * multiply and one f32 add), where Keras in training phase would normalise with the batch's statistics and fit gamma and beta;
- * Dropout is not applied.  The constant is 32: 18 .. 31 and 33 are refused, and everything refused before stays refused.
+ * Dropout is not applied while nrv_fit_set_dropout is off.  The constant is 32: 18 .. 31 and 33 are refused, and everything refused before stays refused.
  *   nrv_fit_set_depth  takes NRV_FIT_FULL under the rules above.
  * THE SET at this depth.  ONE sig f32 [rows][T][50] and ONE feat f32 [rows][T][6] for both models - the window's raw inputs, what
  * nrv_predict* takes; both models read the same - and the same y arrays: 224 T bytes per row.  The depth's own cap is
@@ -985,6 +986,37 @@ int nrv_fit_bn_get(nrv_handle* h, int model, int which, nrv_fit_bn_info* info, f
 #define NRV_FIT_PARAMS_BN(depth) ((depth) == NRV_FIT_LSTM3 ? 512 : (depth) == NRV_FIT_SIGNAL ? 544 : (depth) == NRV_FIT_FULL ? 864 : 0)
 int nrv_fit_set_bn_affine(nrv_handle* h, int on);
 int nrv_fit_bn_affine(nrv_handle* h);
+
+/* THE DROPOUT BEHIND THE IDENTITY BLOCK (opt-in; depths NRV_FIT_SIGNAL and NRV_FIT_FULL).  The reference model is identity block ->
+ * Dropout(0.2) -> Flatten -> Dense(400 -> 64); F [pair][400] (f = p * 8 + o) is that Flatten's output.  While the switch is on,
+ * nrv_fit_grad and nrv_fit_epoch drop F as Keras in training phase does; nanoreviser_amd/dropout.py is the definition.
+ * THE RULE.  No generator with a state: the mask is a pure function of (seed, draw, model, set row, t, element).  Element f
+ * belongs to quad q = f / 4; the four words of philox4x32_10(counter = (row, model << 16 | t * 100 + q, draw low, draw high),
+ * key = (seed low, seed high)) serve f = 4 q .. 4 q + 3 in order; `row` is the row's index in the set, not its place in a batch or
+ * a chunk; an element is kept iff its word >= thr = floor(rate * 2^32); keepf = (float)(1 - rate); forward Fd = F / keepf where
+ * kept, else 0; backward dF = dFd / keepf where kept, else 0 - both correctly rounded divisions.  sig_dense's gradient multiplies
+ * the dropped F.  `draw` counts batches and is a HOST counter per model.
+ *   nrv_fit_set_dropout       rate in [0, 1), 0 = off (the default); resets both models' draws to 0; does NOT forget an
+ *     nrv_fit_begin (the vector keeps its length).  nrv_fit_set_depth switches it off.  Refused under its own name, the handle
+ *     staying usable: a rate outside [0, 1); rate > 0 at a depth whose signal branch is frozen; a raw-read call in flight;
+ *     rate > 0 with T > 655 (t * 100 + q has 16 bits).
+ *   nrv_fit_dropout           the getter: rate, seed and both models' draws; any output may be NULL.
+ *   nrv_fit_set_dropout_draw  sets a model's draw (>= 0): what a continued run and the tests use.
+ *   nrv_fit_dropout_mask      the unit door: uint8 [b][T][400], 1 = kept, for b set rows (any uint32; repeats allowed) at `draw`.
+ *     Refused while the switch is off.
+ *   nrv_fit_begin             resets that model's draw to 0.
+ *   nrv_fit_grad              drops at the current draw and leaves it.
+ *   nrv_fit_epoch             batch k of the call drops at draw + k; the draw then advances by ceil(n / B), skipped non-finite
+ *     batches included; no host synchronisation inside an epoch.  The statistics are the dropped forward's, as Keras reports a
+ *     training loss.
+ *   nrv_fit_eval, nrv_fit_bn_reestimate   never drop.
+ * With the switch off every launch is the instantiation it was and every depth returns the bytes it returned.  No atomics; the
+ * same calls give the same bytes.  LEFT OUT: the draw is not persisted in a written model; dropout at depths whose signal
+ * branch is frozen (there is nothing to drop); normalising with the batch's statistics. */
+int nrv_fit_set_dropout(nrv_handle* h, double rate, uint64_t seed);
+int nrv_fit_dropout(nrv_handle* h, double* rate, uint64_t* seed, int64_t draw[2]);
+int nrv_fit_set_dropout_draw(nrv_handle* h, int model, int64_t draw);
+int nrv_fit_dropout_mask(nrv_handle* h, int model, const uint32_t* rows, int b, int64_t draw, uint8_t* mask);
 
 /* Same two calls with DEVICE pointers, enqueued on the handle's stream without a host sync
  * (call nrv_sync, or synchronise the stream you passed to nrv_set_stream).  The inputs must be

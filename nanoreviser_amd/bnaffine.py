@@ -109,15 +109,17 @@ def _bn_args(depth, pairs):
 
 
 def batch_terms(depth: str, x, sig, y, vec, stats, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64,
-                fold_dtype=np.float32):
-    """One batch -> (g [block + P]: the gradient of L, FitStats of the batch with steps = nonfinite = 0)."""
+                fold_dtype=np.float32, drop=None):
+    """One batch -> (g [block + P]: the gradient of L, FitStats of the batch with steps = nonfinite = 0).  drop: dropout.terms of
+    the batch's set rows (signal and full depth): bn_c2's dy is then the masked dF."""
     dt = np.dtype(dtype)
     fit = fitdepth.BY_NAME[depth].fit
     theta = np.asarray(vec)[n_block(depth):]
     pairs = pairs_of(depth, vec, stats, fold_dtype)
     taps = {}
     fn = fit.batch_terms if depth == "full" else fit.batch_terms_dx
-    out = fn(*_data(depth, x, sig), y, theta, *_bn_args(depth, pairs), T, C, opts, act, dt, taps=taps)
+    out = fn(*_data(depth, x, sig), y, theta, *_bn_args(depth, pairs), T, C, opts, act, dt, taps=taps,
+             **({} if drop is None else {"drop": drop}))
     g, st = out[0], out[1]
     n = dt.type(np.asarray(y).shape[0])
     front = []

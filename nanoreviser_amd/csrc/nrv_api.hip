@@ -10,6 +10,7 @@
 #include "nrv_fullfit.h"      // ... at depth NRV_FIT_FULL: the raw windows as the set, lstm1 and lstm2 forward and backward, all of dXin out of lstm3
 #include "nrv_bnfit.h"        // ... nrv_fit_bn_reestimate: the moments of the BatchNorms inside the fitted section, the fit-owned BatchNorm block
 #include "nrv_bnaffine.h"     // ... nrv_fit_set_bn_affine: gamma / beta of those BatchNorms as parameters - the sums' epilogue, the refold
+#include "nrv_dropout.h"      // ... nrv_fit_set_dropout: the Dropout behind the identity block - the random stream, the unit door's launch
 #include "nrv_block.h"
 
 #include <algorithm>
@@ -768,6 +769,13 @@ struct nrv_handle {
     // their sums [workgroups of a batch's first chunk][NRV_FIT_PARAMS_BN] (nrv_bnaffine.h)
     bool bn_affine = false;
     float* d_pbn = nullptr; size_t cap_pbn = 0;
+    // nrv_fit_set_dropout: the rate (0: off), what the launches compare and divide by, the seed; each model's draw counter is
+    // a host counter (Model::draw); nrv_fit_dropout_mask's bytes
+    double drop_rate = 0.0;
+    unsigned drop_thr = 0;
+    float drop_keepf = 1.f;
+    uint64_t drop_seed = 0;
+    unsigned char* d_mask = nullptr; size_t cap_mask = 0;
     struct Model {
       float* d_par = nullptr;                                 // [4][P]
       // depths NRV_FIT_LSTM3 and deeper: the fit's own BatchNorm block [kBnFloats] (nrv_bnfit.h) - every fit launch reads its
@@ -781,6 +789,7 @@ struct nrv_handle {
       float* d_lr = nullptr; size_t cap_lr = 0;
       bool begun = false;
       long long t = 0;
+      int64_t draw = 0;                                       // nrv_fit_set_dropout: the next batch's draw
       nrv_fit_opts o = {};
     } m[2];
   } fit;
@@ -1720,7 +1729,7 @@ void nrv_destroy(nrv_handle* h) {
     (void)hipFree(h->fit.m[m].d_bn); (void)hipFree(h->fit.m[m].d_bnacc);
   }
   (void)hipFree(h->fit.d_partial); (void)hipFree(h->fit.d_pstat); (void)hipFree(h->fit.d_order); (void)hipFree(h->fit.d_p); (void)hipFree(h->fit.d_flag);
-  (void)hipFree(h->fit.d_l4); (void)hipFree(h->fit.d_gl4); (void)hipFree(h->fit.d_bnpart); (void)hipFree(h->fit.d_pbn);
+  (void)hipFree(h->fit.d_l4); (void)hipFree(h->fit.d_gl4); (void)hipFree(h->fit.d_bnpart); (void)hipFree(h->fit.d_pbn); (void)hipFree(h->fit.d_mask);
   (void)hipFree(h->fit.d_l3); (void)hipFree(h->fit.d_gl3); (void)hipFree(h->fit.d_ident);
   (void)hipFree(h->fit.d_rd); (void)hipFree(h->fit.d_grd);
   (void)hipFree(h->fit.d_sg); (void)hipFree(h->fit.d_pconv); (void)hipFree(h->fit.d_gdense);
@@ -4182,6 +4191,8 @@ int nrv_fit_set_depth(nrv_handle* h, int depth) {
     F.m[m].t = 0;
   }
   if (F.bn_affine) fit_bn_affine_off(h);                   // the switch is off at every depth until it is set again
+  F.drop_rate = 0.0; F.drop_thr = 0; F.drop_keepf = 1.f;   // and so is the dropout
+  F.m[0].draw = F.m[1].draw = 0;
   if (depth == F.depth) return NRV_OK;
   for (int m = 0; m < 2; ++m) {                            // the set and the parameter blocks are the other depth's
     (void)hipFree(F.x[m]); (void)hipFree(F.shared[m]); (void)hipFree(F.y[m]);
@@ -4327,6 +4338,7 @@ int nrv_fit_begin(nrv_handle* h, int model, const float* params, const nrv_fit_o
   HIPCHK(h, hipMemsetAsync(M.d_state, 0, sizeof(TailState), h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   M.o = o; M.t = 0; M.begun = true;
+  M.draw = 0;
   return NRV_OK;
 }
 
@@ -4429,6 +4441,13 @@ static int fit_step_scratch(nrv_handle* h, int model, int b_max, bool grad) {
   return fit_scratch(h, (void**)&h->fit.d_pstat, &h->fit.cap_pstat, wg * sizeof(TailStat));
 }
 
+// nrv_fit_set_dropout: what the DROP launches and the unit door take, at `draw` of `model`
+static DropArgs fit_drop_args(const nrv_handle* h, int model, int64_t draw) {
+  const nrv_handle::Fit& F = h->fit;
+  return DropArgs{(unsigned)(F.drop_seed & 0xffffffffu), (unsigned)(F.drop_seed >> 32), (unsigned)((uint64_t)draw & 0xffffffffu),
+                  (unsigned)((uint64_t)draw >> 32), (unsigned)model << 16, F.drop_thr, F.drop_keepf};
+}
+
 // nrv_fit_bn_reestimate: behind the forward launches of one chunk (rows c0 .. c0 + bc - 1 of b), the moments of the stage's
 // BatchNorms - stage 0: bn_c1, bn_l1; 1: bn_c2, bn_l2; 2: bn_l3, each only where it lies inside the fitted section - into the
 // partials, and their reduction onto the model's running sums (nrv_bnfit.h)
@@ -4467,7 +4486,9 @@ static void fit_bn_moments(nrv_handle* h, int model, int stage, int c0, int bc, 
 // one batch of b rows onto the stream: the gradient (mode kTailGradOnly / kTailTrain) or the forward alone (kTailEval) and the
 // reduce / update behind it - two launches at tail depth, three at head depth.  bn_stage >= 0 (nrv_fit_bn_reestimate, mode
 // kTailEval, depth NRV_FIT_LSTM3 or deeper): per chunk the forward launches up to lstm3 and fit_bn_moments, nothing else
-static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, int mode, long long n_lr, float* d_p, int bn_stage = -1) {
+// draw >= 0 (nrv_fit_grad / _epoch while nrv_fit_set_dropout is on): the DROP instantiations of the two signal launches, at that draw
+static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, int mode, long long n_lr, float* d_p, int bn_stage = -1,
+                       int64_t draw = -1) {
   const FitDepth& D = fit_at(h);
   const bool full = D.rd, sg = D.sg, l3 = D.l3;
   if (!D.mlp) {
@@ -4519,6 +4540,8 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
     float* const gz1 = full ? cs2 + rcap * 128 : nullptr;
     float* const gz2 = full ? gz1 + rcap * 128 : nullptr;
     const int sg_wg = sg ? ((b < kL4ChunkRows ? b : kL4ChunkRows) * T + 31) / 32 : 0;     // workgroups of sig_backward_kernel in the first chunk: the conv block's partials
+    const bool drop = sg && grad && draw >= 0 && h->fit.drop_rate > 0.0;
+    const DropArgs dr = fit_drop_args(h, model, draw < 0 ? 0 : draw);
     const int bn_wg = ((b < kL4ChunkRows ? b : kL4ChunkRows) * T + 31) / 32;              // ... of the launches that leave the gamma / beta block's
     // the sums of BatchNorm `which` (of kFitBn) over this chunk: its place in the block's partials, the block's current statistics
     int bn_at[5] = {0, 0, 0, 0, 0};
@@ -4542,8 +4565,10 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
           hipLaunchKernelGGL((rl_forward_kernel<6, 16, 1>), dim3(tiles, 2), dim3(128), 0, h->stream, r1);
           hipLaunchKernelGGL((rl_forward_kernel<32, 64, 1>), dim3(tiles, 2), dim3(256), 0, h->stream, r2);
         }
-        hipLaunchKernelGGL(sig_forward_kernel<false>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
-      } else if (sg) hipLaunchKernelGGL(sig_forward_kernel<true>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
+        if (drop) hipLaunchKernelGGL((sig_forward_kernel<false, true>), dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, SigDrop<SigArgs>{sa, dr});
+        else hipLaunchKernelGGL(sig_forward_kernel<false>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
+      } else if (sg && drop) hipLaunchKernelGGL((sig_forward_kernel<true, true>), dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, SigDrop<SigArgs>{sa, dr});
+      else if (sg) hipLaunchKernelGGL(sig_forward_kernel<true>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
       const L3Args l3a{sg ? xin : l3 ? h->fit.x[model] : nullptr, sg ? h->fit.d_ident : d_rows + c0, M.d_par + os, fbn + kBnS3, fbn + kBnH3, h3, xb4, gz3, cs3, dx3, gz,
                        h->fit.d_gl3, T, bc, grad ? 1 : 0, c0 > 0 ? 1 : 0};
       if (l3) {                                             // lstm3 forward: the scratch XB is "the set" of the lstm4 launches
@@ -4578,7 +4603,10 @@ static void fit_launch(nrv_handle* h, int model, const unsigned* d_rows, int b, 
         if (full && ob) hipLaunchKernelGGL((l3_dx_kernel<true, SigBnArgs>), dim3((bc * T + 31) / 32), dim3(384), 0, h->stream, SigBnArgs{sa, bn_sums(3, h2, c0)});
         else if (full) hipLaunchKernelGGL(l3_dx_kernel<true>, dim3((bc * T + 31) / 32), dim3(384), 0, h->stream, sa);
         else hipLaunchKernelGGL(l3_dx_kernel<false>, dim3((bc * T + 31) / 32), dim3(128), 0, h->stream, sa);
-        if (ob) hipLaunchKernelGGL(sig_backward_kernel<SigBnArgs>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, SigBnArgs{sa, bn_sums(0, nullptr, c0)});
+        if (ob && drop) hipLaunchKernelGGL((sig_backward_kernel<SigBnArgs, true>), dim3((bc * T + 31) / 32), dim3(256), 0, h->stream,
+                                           SigDrop<SigBnArgs>{SigBnArgs{sa, bn_sums(0, nullptr, c0)}, dr});
+        else if (ob) hipLaunchKernelGGL(sig_backward_kernel<SigBnArgs>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, SigBnArgs{sa, bn_sums(0, nullptr, c0)});
+        else if (drop) hipLaunchKernelGGL((sig_backward_kernel<SigArgs, true>), dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, SigDrop<SigArgs>{sa, dr});
         else hipLaunchKernelGGL(sig_backward_kernel<SigArgs>, dim3((bc * T + 31) / 32), dim3(256), 0, h->stream, sa);
         hipLaunchKernelGGL(sig_wgrad_kernel, dim3(kSgWgM, 2), dim3(512), 0, h->stream, sa);
       }
@@ -4641,7 +4669,7 @@ int nrv_fit_grad(nrv_handle* h, int model, const uint32_t* rows, int b, float* g
   if (!grad || !rows) return fit_refuse(h, who, "null rows / grad");
   if ((rc = fit_rows_in(h, who, model, rows, b)) || (rc = fit_step_scratch(h, model, b, true)) || (rc = fit_state_put(h, model))) return rc;
   const int P = fit_params_n(h, model);
-  fit_launch(h, model, h->fit.d_order, b, kTailGradOnly, 0, nullptr);
+  fit_launch(h, model, h->fit.d_order, b, kTailGradOnly, 0, nullptr, -1, h->fit.drop_rate > 0.0 ? h->fit.m[model].draw : -1);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(grad, h->fit.m[model].d_par + 3 * (size_t)P, (size_t)P * 4, hipMemcpyDeviceToHost, h->stream));
   return fit_state_get(h, model, stats);
@@ -4664,8 +4692,9 @@ int nrv_fit_epoch(nrv_handle* h, int model, const uint32_t* order, int64_t n, nr
   if ((rc = put(h, M.d_lr, lr.data(), (size_t)nb * 4, h->stream)) || (rc = fit_state_put(h, model))) return rc;
   for (int64_t k = 0; k < nb; ++k) {
     const int b = (int)(n - k * B < B ? n - k * B : B);
-    fit_launch(h, model, h->fit.d_order + k * B, b, kTailTrain, nb, nullptr);
+    fit_launch(h, model, h->fit.d_order + k * B, b, kTailTrain, nb, nullptr, -1, h->fit.drop_rate > 0.0 ? M.draw + k : -1);
   }
+  if (h->fit.drop_rate > 0.0) M.draw += nb;                 // skipped non-finite batches included: a host counter
   HIPCHK(h, hipGetLastError());
   return fit_state_get(h, model, stats);
 }
@@ -4782,6 +4811,64 @@ int nrv_fit_set_bn_affine(nrv_handle* h, int on) {
 int nrv_fit_bn_affine(nrv_handle* h) {
   const int rc = check_handle(h);
   return rc ? rc : (h->fit.bn_affine ? 1 : 0);
+}
+
+int nrv_fit_set_dropout(nrv_handle* h, double rate, uint64_t seed) {
+  static const char* who = "nrv_fit_set_dropout";
+  const int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (!(rate >= 0.0 && rate < 1.0)) return fit_refuse(h, who, "rate must lie in [0, 1)");
+  if (rate > 0.0 && !fit_at(h).sg)
+    return fit_refuse(h, who, "the signal branch is frozen at this depth, there is nothing to drop (depths NRV_FIT_SIGNAL and NRV_FIT_FULL fit it)");
+  if (rate > 0.0 && h->T > 655) return fit_refuse(h, who, "T > 655: t * 100 + q would not fit the counter's 16 bits");
+  nrv_handle::Fit& F = h->fit;
+  F.drop_rate = rate;
+  F.drop_thr = (unsigned)std::floor(rate * 4294967296.0);
+  F.drop_keepf = (float)(1.0 - rate);
+  F.drop_seed = seed;
+  F.m[0].draw = F.m[1].draw = 0;
+  return NRV_OK;
+}
+
+int nrv_fit_dropout(nrv_handle* h, double* rate, uint64_t* seed, int64_t draw[2]) {
+  const int rc = check_handle(h);
+  if (rc) return rc;
+  if (rate) *rate = h->fit.drop_rate;
+  if (seed) *seed = h->fit.drop_seed;
+  if (draw) { draw[0] = h->fit.m[0].draw; draw[1] = h->fit.m[1].draw; }
+  return NRV_OK;
+}
+
+int nrv_fit_set_dropout_draw(nrv_handle* h, int model, int64_t draw) {
+  static const char* who = "nrv_fit_set_dropout_draw";
+  const int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (model != 0 && model != 1) return fit_refuse(h, who, "model must be 0 or 1");
+  if (draw < 0) return fit_refuse(h, who, "draw must not be negative");
+  h->fit.m[model].draw = draw;
+  return NRV_OK;
+}
+
+int nrv_fit_dropout_mask(nrv_handle* h, int model, const uint32_t* rows, int b, int64_t draw, uint8_t* mask) {
+  static const char* who = "nrv_fit_dropout_mask";
+  int rc = fit_enter(h, who);
+  if (rc) return rc;
+  if (model != 0 && model != 1) return fit_refuse(h, who, "model must be 0 or 1");
+  if (!(h->fit.drop_rate > 0.0)) return fit_refuse(h, who, "the dropout is off (call nrv_fit_set_dropout with a rate above 0 first)");
+  if (b < 1 || b > NRV_FIT_MAX_BATCH) return fit_refuse(h, who, "b outside 1 .. NRV_FIT_MAX_BATCH");
+  if (!rows || !mask) return fit_refuse(h, who, "null rows / mask");
+  if (draw < 0) return fit_refuse(h, who, "draw must not be negative");
+  const long long quads = (long long)b * h->T * 100;
+  if ((rc = fit_scratch(h, (void**)&h->fit.d_order, &h->fit.cap_order, (size_t)b * 4)) ||
+      (rc = fit_scratch(h, (void**)&h->fit.d_mask, &h->fit.cap_mask, (size_t)quads * 4)) ||
+      (rc = put(h, h->fit.d_order, rows, (size_t)b * 4, h->stream)))
+    return rc;
+  hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, h->stream,
+                     DropMaskArgs{fit_drop_args(h, model, draw), h->fit.d_order, h->fit.d_mask, h->T, quads});
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(mask, h->fit.d_mask, (size_t)quads * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return NRV_OK;
 }
 
 int nrv_fit_bn_get(nrv_handle* h, int model, int which, nrv_fit_bn_info* info, float* mean, float* var, double* s1, double* s2) {

@@ -3,6 +3,7 @@
 // gradient out of lstm3.
 #pragma once
 #include "nrv_cnn.h"       // conv_positions: the convolutions of the forward launch are the inference kernel's, not restated
+#include "nrv_dropout.h"   // nrv_fit_set_dropout: the keep bits of F's quads
 #include "nrv_lstm3fit.h"  // its launches run unchanged on this depth's scratch Xin
 
 namespace nrv {
@@ -10,7 +11,8 @@ namespace nrv {
 // ---------------------------------------------------------------------------------------
 // nanoreviser_amd/signalfit.py is the DEFINITION; include/nanorev.h (nrv_fit_*, "depth") states the rule.  Fitted are tensors 0, 1,
 // 6, 7, 32 .. 39, 44 .. 59 and the centres; the three BatchNorms inside the fitted section are FROZEN and applied in their
-// inference form (behind a convolution: relu(conv) * s + h), and the reference's Dropout is not applied.  One vector per model,
+// inference form (behind a convolution: relu(conv) * s + h), and the reference's Dropout is applied only while nrv_fit_set_dropout
+// is on (the DROP instantiations below; off, every launch is the instantiation it was).  One vector per model,
 // P = 25896 + NRV_FIT_PARAMS_LSTM3:
 //   [w1 [3][8] | b1 [8] | w2 [3][8][8] | b2 [8] | Ws [400][64] | bs [64] | the lstm3 depth's vector]
 // THE SET: per model x2 [rows][T][128] f32 (the BatchNorm'd f32 lstm2 output) and y [rows] u8; ONE sig [rows][T][50] f32 for both
@@ -85,6 +87,8 @@ struct SigArgs {
 };
 
 struct SigBnArgs : SigArgs { BnAffArgs bn; };               // nrv_fit_set_bn_affine: the launches that also leave a BatchNorm's two sums
+template <class A> struct SigDrop : A { DropArgs drop; };   // nrv_fit_set_dropout: the DROP instantiations' arguments
+template <class A, bool DROP> using SigDropOf = std::conditional_t<DROP, SigDrop<A>, A>;
 
 // the 264-float image conv_positions reads: the vector's kernels and biases with the handle's frozen scales and shifts
 __device__ __forceinline__ void sig_conv_image(const SigArgs& a, float* cwl, int tid) {
@@ -93,8 +97,10 @@ __device__ __forceinline__ void sig_conv_image(const SigArgs& a, float* cwl, int
 }
 
 // grid = ceil(M / 32).  X2 = false (depth NRV_FIT_FULL): columns 0 .. 127 of Xin are another launch's, x2 is not read
-template <bool X2 = true>
-__global__ void __launch_bounds__(256) sig_forward_kernel(const SigArgs a) {
+// DROP (nrv_fit_set_dropout): behind the convolutions every f32x4 of the img planes - quad kq of pair r - goes through the
+// dropout in place, one Philox call each, thread (r = tid % 32, kq = tid / 32 + 8 j); the product and a.F see the dropped F
+template <bool X2 = true, bool DROP = false>
+__global__ void __launch_bounds__(256) sig_forward_kernel(const SigDropOf<SigArgs, DROP> a) {
   constexpr int PLANE = 32 * 4 + 4;
   __shared__ __attribute__((aligned(16))) float img[100 * PLANE];
   __shared__ __attribute__((aligned(16))) float cwl[264];
@@ -122,6 +128,22 @@ __global__ void __launch_bounds__(256) sig_forward_kernel(const SigArgs a) {
     else conv_positions<6>(cwl, x, p0, r, img, PLANE);
   }
   __syncthreads();
+  if constexpr (DROP) {
+    const int r = tid & 31;
+    if (off[r] >= 0) {
+      const unsigned row = a.rows[(m0 + r) / a.T];
+      const int t = (m0 + r) % a.T;
+      for (int kq = tid >> 5; kq < 100; kq += 8) {
+        f32x4* const v = (f32x4*)(img + kq * PLANE + r * 4);
+        const unsigned keep = drop_keep4(a.drop, row, t, kq);
+        f32x4 x = *v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[j] = drop_apply(x[j], keep >> j & 1u, a.drop.keepf);
+        *v = x;
+      }
+    }
+    __syncthreads();
+  }
   {
     const int ct = wave, q4 = lane >> 4, r16 = lane & 15;
     const float* Ws = a.par + kSgWs + ct * 16 + r16;
@@ -226,8 +248,11 @@ __device__ __forceinline__ void bn_conv_partial(const BnAffArgs& b, const float 
 
 // grid = ceil(M / 32).  A = SigBnArgs (nrv_fit_set_bn_affine): also the two sums of bn_c2 (dy = dF, x = a2) and of bn_c1 (dy = dc1,
 // x = a1 recomputed in the forward launch's operation order), each thread over its own samples ascending
-template <class A = SigArgs>
-__global__ void __launch_bounds__(256) sig_backward_kernel(const A a) {
+// DROP (nrv_fit_set_dropout): dF goes through the dropout in a pass of its own behind the product, before anything reads it -
+// thread (pair r = tid % 32, quad q = tid / 32 + 8 j), one Philox call per quad; bn_c2's sums (dy = dF) see the masked dF.  z2, a1
+// and c1 lie in front of the dropout and are recomputed as they were
+template <class A = SigArgs, bool DROP = false>
+__global__ void __launch_bounds__(256) sig_backward_kernel(const SigDropOf<A, DROP> a) {
   constexpr bool BN = std::is_same_v<A, SigBnArgs>;
   __shared__ float dfl[32 * kSgDfs];     // dF [pair][p * 8 + o], then da2 in its place
   __shared__ float c1l[32 * kSgC1s];     // c1 [pair][(p + 1) * 8 + ci] with a zero sample on either side, then da1 in its place
@@ -273,6 +298,20 @@ __global__ void __launch_bounds__(256) sig_backward_kernel(const A a) {
     }
   }
   __syncthreads();
+  if constexpr (DROP) {
+    const int rr = tid & 31;
+    if (m0 + rr < a.M) {
+      const unsigned row = a.rows[(m0 + rr) / a.T];
+      const int t = (m0 + rr) % a.T;
+      for (int q = tid >> 5; q < 100; q += 8) {
+        float* const v = dfl + rr * kSgDfs + q * 4;
+        const unsigned keep = drop_keep4(a.drop, row, t, q);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = drop_apply(v[j], keep >> j & 1u, a.drop.keepf);
+      }
+    }
+    __syncthreads();
+  }
   // thread (pair r, sample chunk) as in the forward launch; the same operations in the same order, so the same sides
   const int chunk = wave * 2 + (lane >> 5), r = lane & 31;
   const int p0 = chunk < 2 ? 7 * chunk : 14 + 6 * (chunk - 2), np = chunk < 2 ? 7 : 6;

@@ -55,6 +55,7 @@ SYMBOLS = [
     "nrv_fit_set_rows_full", "nrv_fit_get_rows_full",
     "nrv_fit_bn_reestimate", "nrv_fit_bn_count", "nrv_fit_bn_get",
     "nrv_fit_set_bn_affine", "nrv_fit_bn_affine",
+    "nrv_fit_set_dropout", "nrv_fit_dropout", "nrv_fit_set_dropout_draw", "nrv_fit_dropout_mask",
 ]
 FIT_TAIL, FIT_HEAD, FIT_LSTM4, FIT_LSTM3, FIT_SIGNAL, FIT_FULL = (d.code for d in fitdepth.DEPTHS)   # NRV_FIT_*: 0, 1, 4, 8, 16, 32
 FIT_MAX_BATCH = 65536               # NRV_FIT_MAX_BATCH
@@ -190,6 +191,10 @@ _FIT_T = {                                                                      
     "nrv_fit_bn_count": [C.c_void_p],
     "nrv_fit_set_bn_affine": [C.c_void_p, C.c_int],
     "nrv_fit_bn_affine": [C.c_void_p],
+    "nrv_fit_set_dropout": [C.c_void_p, C.c_double, C.c_uint64],
+    "nrv_fit_dropout": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_int64)],
+    "nrv_fit_set_dropout_draw": [C.c_void_p, C.c_int, C.c_int64],
+    "nrv_fit_dropout_mask": [C.c_void_p, C.c_int, _U32P, C.c_int, C.c_int64, C.POINTER(C.c_uint8)],
     "nrv_fit_bn_get": [C.c_void_p, C.c_int, C.c_int, C.POINTER(_FitBnInfo), _FP, _FP, _DP, _DP],
 }
 for _d in fitdepth.DEPTHS:                                                                   # the row doors of every depth
@@ -1011,6 +1016,28 @@ class Reviser:
         if v < 0:
             self._check(v)
         return bool(v)
+
+    def fit_set_dropout(self, rate, seed=0):
+        """The reference's Dropout behind the identity block (nanoreviser_amd/dropout.py is the definition): rate in [0, 1), 0
+        switches it off; depths signal and full.  Resets both models' draw counters; fit_set_depth switches it off."""
+        self._check(self._lib.nrv_fit_set_dropout(self._h, float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def fit_dropout(self):
+        """-> (rate, seed, (draw of model 0, draw of model 1))."""
+        rate, seed, draw = C.c_double(0), C.c_uint64(0), (C.c_int64 * 2)()
+        self._check(self._lib.nrv_fit_dropout(self._h, C.byref(rate), C.byref(seed), draw))
+        return float(rate.value), int(seed.value), (int(draw[0]), int(draw[1]))
+
+    def fit_set_dropout_draw(self, model, draw):
+        """The draw the model's next batch drops at (fit_begin sets it to 0, fit_epoch advances it by its batches)."""
+        self._check(self._lib.nrv_fit_set_dropout_draw(self._h, model, int(draw)))
+
+    def fit_dropout_mask(self, model, rows, draw):
+        """-> uint8 [len(rows)][T][400], 1 = kept: dropout.keep_mask's bytes for these set rows, formed on the device."""
+        r = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        mask = np.empty((r.size, self.T, 400), np.uint8)
+        self._check(self._lib.nrv_fit_dropout_mask(self._h, model, _ptr(r, _U32P), r.size, int(draw), _ptr(mask, C.POINTER(C.c_uint8))))
+        return mask
 
     def fit_params(self, model):
         """-> (the parameter vector, t)."""

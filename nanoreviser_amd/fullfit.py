@@ -12,7 +12,8 @@ takes.  One vector per model,
 THE STATED DEVIATIONS are signalfit's, with two more BatchNorms under the first: bn_l1 (tensors 18 .. 21) and bn_l2 (28 .. 31)
 are FROZEN and applied in their inference form from the moving statistics, X1b = h1 * s_l1 + h_l1 and X2b = h2 * s_l2 + h_l2 - one
 multiply and one add, (s_l1, h_l1, s_l2, h_l2) - `rb` - as read_bn forms them.  The written model's BatchNorm tensors are the
-loaded ones, byte for byte.  Dropout is not applied.
+loaded ones, byte for byte.  Dropout is not applied - a deviation that holds only while the switch is off: with
+`drop = (mask, keepf)` (dropout.py; nrv_fit_set_dropout on the device) batch_terms and epoch drop F as signalfit does.
 
 Forward: lstm1 and lstm2 by lstm3fit's step rule with H = 16 and H = 64 (the backward direction walks t = T - 1 .. 0), then
 Xin = [X2b | S] and signalfit's forward.  Backward: signalfit's, whose batch_terms_dx also returns dXin[..., :128];
@@ -169,15 +170,17 @@ def forward(feat, sig, theta, rb, cb, sc, sh, T: int, C: int, act: int = 0, dtyp
     return (X2b,) + signalfit.forward(X2b, sig, np.asarray(theta)[N_READ:], cb, sc, sh, T, C, act, dtype)
 
 
-def batch_terms(feat, sig, y, theta, rb, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64, taps=None):
+def batch_terms(feat, sig, y, theta, rb, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64, taps=None,
+                drop=None):
     """One batch -> (g [P]: the gradient of L, FitStats of the batch with steps = nonfinite = 0).  Gate derivatives are decided
     on the forward value; every gradient is divided by n.  taps: a dict that receives signalfit's three pairs and "bn_l2":
-    (dx2, the raw H2), "bn_l1": (dX1b, the raw H1) - what bnaffine.py sums; nothing returned depends on it."""
+    (dx2, the raw H2), "bn_l1": (dX1b, the raw H1) - what bnaffine.py sums; nothing returned depends on it.  drop: dropout.terms of
+    the batch's set rows, handed to signalfit."""
     dt = np.dtype(dtype)
     theta = np.asarray(theta)
     k = read_branch(feat, theta, rb, T, C, act, dt)
     n = k["feat"].shape[0]
-    gs, st, dx2 = signalfit.batch_terms_dx(k["X2b"], sig, y, theta[N_READ:], cb, sc, sh, T, C, opts, act, dt, taps)
+    gs, st, dx2 = signalfit.batch_terms_dx(k["X2b"], sig, y, theta[N_READ:], cb, sc, sh, T, C, opts, act, dt, taps, drop)
     parts = [a.astype(dt) for a in unpack(theta, T, C)[:12]]
     s1, s2 = np.asarray(rb[0]).astype(dt), np.asarray(rb[2]).astype(dt)
     g2, dX1b = _bilstm_back(k["X1b"], k["H2"], k["k2"], dx2 * s2, parts[6:], 64, T, act, dt, True)
@@ -189,9 +192,9 @@ def batch_terms(feat, sig, y, theta, rb, cb, sc, sh, T: int, C: int, opts: FitOp
 
 
 def epoch(feat, sig, y, state: FitState, order, rb, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0,
-          dtype=np.float64) -> FitStats:
+          dtype=np.float64, drop=None) -> FitStats:
     """tailfit.epoch's rule on raw windows: consecutive batches of opts.B in the order of `order`, a batch with a non-finite
-    gradient skipped and counted, statistics before each update."""
+    gradient skipped and counted, statistics before each update.  drop: a dropout.Stream, as signalfit.epoch takes it."""
     dt = np.dtype(dtype)
     order = np.asarray(order, np.int64).reshape(-1)
     feat, sig, y = np.asarray(feat).reshape(-1, T, N_FEAT), np.asarray(sig).reshape(-1, T, N_SIG_IN), np.asarray(y)
@@ -199,7 +202,8 @@ def epoch(feat, sig, y, state: FitState, order, rb, cb, sc, sh, T: int, C: int, 
     for s in range(0, order.size, opts.B):
         idx = order[s:s + opts.B]
         with np.errstate(all="ignore"):
-            g, st = batch_terms(feat[idx], sig[idx], y[idx], state.theta, rb, cb, sc, sh, T, C, opts, act, dt)
+            g, st = batch_terms(feat[idx], sig[idx], y[idx], state.theta, rb, cb, sc, sh, T, C, opts, act, dt,
+                                drop=None if drop is None else drop.batch(s // opts.B, idx, T))
         if not np.isfinite(g).all():
             tot.nonfinite += 1
             continue
@@ -207,6 +211,8 @@ def epoch(feat, sig, y, state: FitState, order, rb, cb, sc, sh, T: int, C: int, 
         state.theta, state.m, state.v = adam_step(state.theta, state.m, state.v, g, opts, state.t, dt)
         st.steps = 1
         tot.add(st)
+    if drop is not None:
+        drop.advance(-(-order.size // opts.B))
     return tot
 
 

@@ -13,7 +13,10 @@ TWO STATED DEVIATIONS from Keras in training phase.
     inference form from the moving statistics, exactly as lstm3fit.py treats 40 .. 43: behind a convolution that is
     relu(conv) * s + h, one multiply and one add.  The written model's BatchNorm tensors are the loaded ones, byte for byte.
     (s1, h1, s2, h2) - `cb` - and (sc, sh) are arguments of every numeric function here.
- 2. The reference's Dropout(0.2) behind the identity block is not applied.
+ 2. The reference's Dropout(0.2) behind the identity block is not applied.  This deviation holds only while the switch is off:
+    with `drop = (mask, keepf)` (dropout.py; nrv_fit_set_dropout on the device) batch_terms* and epoch drop F as the reference
+    does - Fd = F / keepf where kept, else 0, and dF likewise on the way back.  drop = None changes nothing by a bit; evaluate
+    never drops.
 
 Forward, for each (row, t), p = 0 .. 49 a sample, o a channel; padding is `same`, out-of-range taps are zero:
   a1[p][o] = relu(b1[o] + sum_k sig[p + k - 1] w1[k][o])                 c1 = a1 * s1 + h1
@@ -27,7 +30,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import headfit, lstm3fit, lstm4fit, tailfit  # noqa: F401
+from . import dropout, headfit, lstm3fit, lstm4fit, tailfit  # noqa: F401
 from .lstm4fit import BN_EPS
 from .tailfit import (FitOpts, FitState, FitStats, adam_step, default_opts, epoch_order, lr_t, val_split,  # noqa: F401
                       write_f32)
@@ -87,9 +90,9 @@ def conv_bn(m):
 
 
 # ---- forward, loss, gradient ---------------------------------------------------------------------------------------------
-def branch(sig, theta, cb, T: int, C: int, dtype=np.float64):
+def branch(sig, theta, cb, T: int, C: int, dtype=np.float64, drop=None):
     """-> dict(sig [n][T][50], z1 / a1 / c1 [n][T][50][8], z2 / a2, F [n][T][400], S [n][T][64]); z are the conv
-    pre-activations."""
+    pre-activations.  drop = (mask uint8 [n][T][400], keepf): F is the DROPPED F, what S and gWs are formed from."""
     dt = np.dtype(dtype)
     w1, b1, w2, b2, Ws, bs = [a.astype(dt) for a in unpack(theta, T, C)[:6]]
     s1, h1, s2, h2 = [np.asarray(a).astype(dt) for a in cb]
@@ -101,7 +104,7 @@ def branch(sig, theta, cb, T: int, C: int, dtype=np.float64):
     cp = np.pad(c1, ((0, 0), (0, 0), (1, 1), (0, 0)))
     z2 = b2 + sum(cp[..., k:k + N_SIG_IN, :] @ w2[k] for k in range(3))
     a2 = np.maximum(z2, 0)
-    F = (a2 * s2 + h2 + sig[..., None]).reshape(-1, T, N_FLAT)
+    F = dropout.apply((a2 * s2 + h2 + sig[..., None]).reshape(-1, T, N_FLAT), drop, dt)
     return {"sig": sig, "z1": z1, "a1": a1, "c1": c1, "z2": z2, "a2": a2, "F": F, "S": F @ Ws + bs}
 
 
@@ -117,20 +120,21 @@ def forward(x2, sig, theta, cb, sc, sh, T: int, C: int, act: int = 0, dtype=np.f
     return (S,) + lstm3fit.forward(xin(x2, S, T, dtype), np.asarray(theta)[N_SIGNAL:], sc, sh, T, C, act, dtype)
 
 
-def batch_terms(x2, sig, y, theta, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64):
+def batch_terms(x2, sig, y, theta, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64, drop=None):
     """One batch -> (g [P]: the gradient of L, FitStats of the batch with steps = nonfinite = 0).  ReLU sides are decided on the
-    forward value; every gradient is divided by n as the LSTM blocks' are."""
-    return batch_terms_dx(x2, sig, y, theta, cb, sc, sh, T, C, opts, act, dtype)[:2]
+    forward value; every gradient is divided by n as the LSTM blocks' are.  drop: dropout.terms of the batch's set rows."""
+    return batch_terms_dx(x2, sig, y, theta, cb, sc, sh, T, C, opts, act, dtype, drop=drop)[:2]
 
 
-def batch_terms_dx(x2, sig, y, theta, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64, taps=None):
+def batch_terms_dx(x2, sig, y, theta, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0, dtype=np.float64, taps=None,
+                   drop=None):
     """batch_terms and the data gradient behind it -> (g, FitStats, dx2 [n][T][128]: columns 0 .. 127 of lstm3fit's dXin - the
     derivative of the batch's SUM of row losses by x2, not divided by n).  fullfit.py goes on from it.  taps: a dict that
     receives lstm3fit's "bn_l3" and "bn_c2": (dF [n][T][50][8], a2), "bn_c1": (dc1, a1) - what bnaffine.py sums; nothing returned
-    depends on it."""
+    depends on it.  drop = (mask, keepf): F and dF go through the dropout (the statistics are the dropped forward's)."""
     dt = np.dtype(dtype)
     theta = np.asarray(theta)
-    k = branch(sig, theta, cb, T, C, dt)
+    k = branch(sig, theta, cb, T, C, dt, drop)
     n = k["sig"].shape[0]
     g3, st, dXin = lstm3fit.batch_terms_dx(xin(x2, k["S"], T, dt), y, theta[N_SIGNAL:], sc, sh, T, C, opts, act, dt, taps)
     w1, b1, w2, b2, Ws, bs = [a.astype(dt) for a in unpack(theta, T, C)[:6]]
@@ -138,7 +142,7 @@ def batch_terms_dx(x2, sig, y, theta, cb, sc, sh, T: int, C: int, opts: FitOpts,
     dS = dXin[..., 128:]
     gWs = k["F"].reshape(-1, N_FLAT).T @ dS.reshape(-1, N_S)
     gbs = dS.reshape(-1, N_S).sum(axis=0)
-    dF = (dS @ Ws.T).reshape(n, T, N_SIG_IN, N_CH)
+    dF = dropout.apply(dS @ Ws.T, drop, dt).reshape(n, T, N_SIG_IN, N_CH)
     da2 = np.where(k["a2"] > 0, dF * s2, dt.type(0))
     cp = np.pad(k["c1"], ((0, 0), (0, 0), (1, 1), (0, 0)))
     dp = np.pad(da2, ((0, 0), (0, 0), (1, 1), (0, 0)))     # dp[q] = da2[q - 1]
@@ -156,9 +160,10 @@ def batch_terms_dx(x2, sig, y, theta, cb, sc, sh, T: int, C: int, opts: FitOpts,
 
 
 def epoch(x2, sig, y, state: FitState, order, cb, sc, sh, T: int, C: int, opts: FitOpts, act: int = 0,
-          dtype=np.float64) -> FitStats:
+          dtype=np.float64, drop=None) -> FitStats:
     """tailfit.epoch's rule on signal rows: consecutive batches of opts.B in the order of `order`, a batch with a non-finite
-    gradient skipped and counted, statistics before each update."""
+    gradient skipped and counted, statistics before each update.  drop: a dropout.Stream - batch k of the call drops at draw + k
+    on its set rows, and the stream advances by the number of batches, skipped ones included."""
     dt = np.dtype(dtype)
     order = np.asarray(order, np.int64).reshape(-1)
     x2, sig, y = np.asarray(x2).reshape(-1, T, 128), np.asarray(sig).reshape(-1, T, N_SIG_IN), np.asarray(y)
@@ -166,7 +171,8 @@ def epoch(x2, sig, y, state: FitState, order, cb, sc, sh, T: int, C: int, opts: 
     for s in range(0, order.size, opts.B):
         idx = order[s:s + opts.B]
         with np.errstate(all="ignore"):
-            g, st = batch_terms(x2[idx], sig[idx], y[idx], state.theta, cb, sc, sh, T, C, opts, act, dt)
+            g, st = batch_terms(x2[idx], sig[idx], y[idx], state.theta, cb, sc, sh, T, C, opts, act, dt,
+                                None if drop is None else drop.batch(s // opts.B, idx, T))
         if not np.isfinite(g).all():
             tot.nonfinite += 1
             continue
@@ -174,6 +180,8 @@ def epoch(x2, sig, y, state: FitState, order, cb, sc, sh, T: int, C: int, opts: 
         state.theta, state.m, state.v = adam_step(state.theta, state.m, state.v, g, opts, state.t, dt)
         st.steps = 1
         tot.add(st)
+    if drop is not None:
+        drop.advance(-(-order.size // opts.B))
     return tot
 
 

@@ -19,13 +19,13 @@ always starts from the loaded or continued model's own weights; --fit_init acts 
 --fit_depth signal fits the part of the model that reads the raw current - conv1, conv2 and sig_dense, tensors 0, 1, 6, 7, 32 and
 33 - with lstm3 (34 .. 39) and everything --fit_depth lstm4 fits; a window is its 128 T BatchNorm'd lstm2 values and its 50 T
 normalised samples (nanoreviser_amd/signalfit.py is the definition, and states the two deviations: the BatchNorms inside the
-fitted section stay frozen in their inference form, the reference's Dropout is not applied).  The signal branch and lstm3 always
+fitted section stay frozen in their inference form, the reference's Dropout is applied only with --dropout).  The signal branch and lstm3 always
 start from the loaded or continued model's own weights; --fit_init acts on the layers behind lstm4.  (--fit_depth lstm3 is not
 offered.)
 
 --fit_depth full fits the read branch too - lstm1 (tensors 12 .. 17) and lstm2 (22 .. 27) - with everything --fit_depth signal
 fits: every tensor that is no BatchNorm's.  A window is its raw inputs, 50 T normalised samples and 6 T read features
-(nanoreviser_amd/fullfit.py is the definition; the five BatchNorms stay frozen in their inference form, Dropout is not applied).
+(nanoreviser_amd/fullfit.py is the definition; the five BatchNorms stay frozen in their inference form, Dropout only with --dropout).
 The four LSTMs and the signal branch start from the loaded or continued model's own weights; --fit_init acts on the layers
 behind lstm4, and a fresh initialisation of the LSTMs is not offered.
 
@@ -40,6 +40,11 @@ they go in front of the parameter vector and take part in every update, each Bat
 the moving statistics, which stay frozen during a step (nanoreviser_amd/bnaffine.py is the definition).  The written model
 carries the fitted gamma / beta, and _summary.json gains a `bn_affine` entry: per BatchNorm the largest |change of gamma| and
 |change of beta|.  With --bn_reestimate the statistics are re-estimated first, at the starting gamma / beta, then the fit runs.
+
+--dropout RATE (0, off, by default; --fit_depth signal or full) applies the reference's Dropout behind the identity block to the
+training batches, 0.2 being the reference's rate (nanoreviser_amd/dropout.py is the definition): a reproducible mask per (seed,
+batch number, model, row, element), --dropout_seed (default --seed) being the seed.  The validation columns, --bn_reestimate and the
+written model's forward never drop.  _summary.json gains a `dropout` entry: rate, seed and both models' final draw counters.
 """
 from __future__ import annotations
 
@@ -89,6 +94,10 @@ def get_args(argv: Optional[Sequence[str]] = None):
                         "the first epoch (--fit_depth signal or full); with -e 0 that alone is written")
     p.add_argument("--fit_bn_affine", action="store_true", default=argparse.SUPPRESS,        # (in the namespace only when given)
                    help="fit gamma and beta of the BatchNorms inside the fitted section too (--fit_depth signal or full)")
+    p.add_argument("--dropout", type=float, default=argparse.SUPPRESS, metavar="RATE",            # (in the namespace only when given)
+                   help="the reference's Dropout behind the identity block on the training batches (--fit_depth signal or full); "
+                        "0.2 is the reference's rate, 0 (the default) is off")
+    p.add_argument("--dropout_seed", type=int, default=argparse.SUPPRESS, help="default: --seed")
     p.add_argument("--model_dir", default=None, help="root of model/<species>/ (default: next to the package)")
     p.add_argument("-g", "--basecall_group", dest="basecall_group", default="Basecall_1D_000")
     p.add_argument("-s", "--basecall_subgroup", dest="basecall_subgroup", default="BaseCalled_template")
@@ -116,6 +125,11 @@ def fit_bn_affine(a) -> bool:
     return bool(getattr(a, "fit_bn_affine", False))
 
 
+def dropout_rate(a) -> float:
+    """--dropout's rate; 0.0, off, when it was not given."""
+    return float(getattr(a, "dropout", 0.0))
+
+
 def check_args(a):
     """-> the message of the first refusal, or None."""
     if not a.fast5_base_dir or not os.path.isdir(a.fast5_base_dir):
@@ -138,6 +152,10 @@ def check_args(a):
         return f"--bn_reestimate: no BatchNorm lies inside the fitted section at --fit_depth {a.fit_depth} (signal and full have them)"
     if fit_bn_affine(a) and a.fit_depth not in ("signal", "full"):
         return f"--fit_bn_affine: no BatchNorm lies inside the fitted section at --fit_depth {a.fit_depth} (signal and full have them)"
+    if not 0.0 <= dropout_rate(a) < 1.0:
+        return "--dropout must be in [0, 1)"
+    if dropout_rate(a) > 0 and a.fit_depth not in ("signal", "full"):
+        return f"--dropout: the signal branch is frozen at --fit_depth {a.fit_depth}, there is nothing to drop (signal and full fit it)"
     if a.epochs < (0 if bn_reestimate(a) else 1):
         return "-e must be at least 1" + (" (0 with --bn_reestimate)" if a.epochs < 0 else "")
     if not 1 <= a.batch_size <= tailfit.MAX_BATCH:
@@ -272,6 +290,9 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
             rv.fit_set_depth(a.fit_depth)
         if fit_bn_affine(a):
             rv.fit_set_bn_affine(True)
+        drop, drop_seed = dropout_rate(a), getattr(a, "dropout_seed", a.seed) & 0xFFFFFFFFFFFFFFFF
+        if drop > 0:
+            rv.fit_set_dropout(drop, drop_seed)
         used, skipped = add_reads(a, rv)
         n = rv.fit_count()
         if n == 0:
@@ -298,6 +319,7 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
             for name, (sg, sb) in (bnaffine.spans(a.fit_depth).items() if nb else ()):
                 d = np.abs(theta.astype(np.float64) - np.asarray(starts[k][0], np.float64))
                 moved[name] = {"max_dgamma": float(d[sg].max()), "max_dbeta": float(d[sb].max())}
+            d_rate, d_seed, d_draw = rv.fit_dropout() if drop > 0 else (0.0, 0, ())          # one call: the state behind this model's fit
             with open(st + "_history.tsv", "w") as fp:
                 fp.write(HISTORY_HEAD + "\n" + "\n".join(lines) + "\n")
             with open(st + "_summary.json", "w") as fp:
@@ -306,7 +328,9 @@ def main(argv: Optional[Sequence[str]] = None, reviser_factory=None) -> int:
                                        "center_weight": a.center_weight, "class_weight": list(a.cw1 if k == 0 else a.cw2),
                                        "init": starts[k][1], "labels_from": os.path.abspath(a.labels_from),
                                        **({"fit_depth": a.fit_depth} if deep else {}),
-                                       **({"fit_bn_affine": True} if nb else {})},
+                                       **({"fit_bn_affine": True} if nb else {}),
+                                       **({"dropout": drop, "dropout_seed": drop_seed} if drop > 0 else {})},
+                           **({"dropout": {"rate": d_rate, "seed": d_seed, "draw": list(d_draw)}} if drop > 0 else {}),
                            **({"bn_affine": moved} if nb else {}),
                            **({"bn_reestimate": bnfit.drift(bnfit.bn_of(m), bn_stats)} if bn_stats else {}),
                            "rows": n, "train_rows": n_train, "val_rows": n_val, "reads": used,

@@ -17,6 +17,10 @@ the ratio of a re-estimation to its number of passes (three at signal and full d
 --bn_affine times the epoch twice per depth in the same process (depths lstm3, signal and full; give them with --depths): with
 nrv_fit_set_bn_affine off, then on - gamma and beta of the BatchNorms inside the fitted section in front of the vector, from the
 model's own - by the same protocol, and prints the switch-on figure with the switch-off one next to it.
+
+--dropout RATE times the epoch twice per depth in the same process (depths signal and full; give them with --depths): with
+nrv_fit_set_dropout off, then on at RATE (seed --seed) from the same start, by the same protocol, and prints the switch-on figure
+with the switch-off one next to it.
 """
 import argparse
 import json
@@ -77,7 +81,16 @@ def main(argv=None):
     ap.add_argument("--depths", default="tail,head,lstm4,lstm3", help="the depths to time, in this order (signal and full are not in the default)")
     ap.add_argument("--bn_reestimate", action="store_true", help="time nrv_fit_bn_reestimate against nrv_fit_eval instead of the epoch")
     ap.add_argument("--bn_affine", action="store_true", help="time the epoch with nrv_fit_set_bn_affine off, then on, in one process")
+    ap.add_argument("--dropout", type=float, default=0.0, metavar="RATE",
+                    help="time the epoch with nrv_fit_set_dropout off, then on at RATE, in one process (0.2 is the reference's rate)")
     a = ap.parse_args(argv)
+    if not 0.0 <= a.dropout < 1.0:
+        ap.error("--dropout must be in [0, 1)")
+    if a.dropout > 0 and (a.bn_affine or a.bn_reestimate):
+        ap.error("--dropout with --bn_affine or --bn_reestimate: one comparison per run (each times its own switch against the plain epoch)")
+    frozen = [d for d in a.depths.split(",") if d not in ("signal", "full")]
+    if a.dropout > 0 and frozen:
+        ap.error(f"--dropout: the signal branch is frozen at depth {', '.join(frozen)}, there is nothing to drop (give --depths signal,full)")
     from nanoreviser_amd import bnaffine, bnfit, fitdepth, headfit, tailfit
     from nanoreviser_amd.engine import Reviser
     from nanoreviser_amd.weights import load_species
@@ -160,6 +173,16 @@ def main(argv=None):
                 print(f"{depth}: switch off {np.median(n / off):,.0f} rows/s, {np.median(off) / nbat * 1e6:.1f} us per batch (epoch "
                       f"{np.median(off) * 1e3:.2f} ms, min {off.min() * 1e3:.2f}, max {off.max() * 1e3:.2f}); switch on, {nb} more parameters, "
                       f"x {np.median(secs) / np.median(off):.4f}:")
+            if a.dropout > 0:                              # the same rows and start with the switch on, in the same process
+                off = secs
+                rv.fit_set_dropout(a.dropout, a.seed)
+                rv.fit_begin(k, th, opts)
+                secs = epochs()
+                nbat = -(-n // a.batch_size)
+                assert rv.fit_dropout()[2][k] == nbat * (a.warmup + a.repeats)
+                print(f"{depth}: switch off {np.median(n / off):,.0f} rows/s, {np.median(off) / nbat * 1e6:.1f} us per batch (epoch "
+                      f"{np.median(off) * 1e3:.2f} ms, min {off.min() * 1e3:.2f}, max {off.max() * 1e3:.2f}); dropout {a.dropout:g} on, "
+                      f"x {np.median(secs) / np.median(off):.4f}:")
             rate = n / secs
             gf = flop_per_row(depth, T, C) * 1e-9
             out[depth] = {"params": int(th.size), "batches": -(-n // a.batch_size), "epoch_ms_median": float(np.median(secs) * 1e3),
@@ -167,6 +190,10 @@ def main(argv=None):
                           "rows_per_s_median": float(np.median(rate)), "rows_per_s_min": float(rate.min()),
                           "rows_per_s_max": float(rate.max()), "gflop_per_batch": gf * a.batch_size,
                           "gflop_per_s_median": float(np.median(rate) * gf)}
+            if a.dropout > 0:
+                out[depth].update(dropout=a.dropout, off_epoch_ms_median=float(np.median(off) * 1e3), off_epoch_ms_min=float(off.min() * 1e3),
+                                  off_epoch_ms_max=float(off.max() * 1e3), off_rows_per_s_median=float(np.median(n / off)),
+                                  on_over_off_median=float(np.median(secs) / np.median(off)))
             if a.bn_affine:
                 out[depth].update(bn_affine=True, off_epoch_ms_median=float(np.median(off) * 1e3), off_epoch_ms_min=float(off.min() * 1e3),
                                   off_epoch_ms_max=float(off.max() * 1e3), off_rows_per_s_median=float(np.median(n / off)),
